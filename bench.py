@@ -23,6 +23,9 @@ Extras    : (keys beside the contract's; the headline is never computed from the
             method2*             (N > 1) the same scheme with torch.distributed collectives, one process per GPU
             cpu_baseline         the oracle on this host's cores (N = 1 only)
 Output    : exactly one JSON line on rank 0.
+Dump      : --dump-outputs DIR writes what the timed path computed in its last step (C, or y with --op spmv) as
+            DIR/<name>.npy, float64.  C and y enter the timed steps as ones, so with the same arguments the dump is the
+            same from run to run whatever the settling phase did, and two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -38,6 +41,26 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "s-blas_amd", "python"))
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_BUDGET_BYTES = 63 * 10**6   # --dump-outputs: all files of the job together stay under 64 MB (headers included)
+DUMP_SEED = 211
+
+
+def dump_outputs(out_dir, arrays, share=1):
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float64.  When the arrays exceed this process's share of the
+    budget, each keeps the same fixed, seeded sample of its rows (first axis), and the row numbers go beside it as
+    <name>_rows.npy (float64), so that two builds still compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // share
+    sample = sum(a.nbytes for a in arrays.values()) > budget
+    total = sum(a.nbytes + 8 * a.shape[0] for a in arrays.values())       # sampled: values + row numbers
+    for name, a in arrays.items():
+        if sample:
+            keep = max(1, a.shape[0] * budget // total)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        print("dumped %s %s float64 to %s" % (name, "x".join(map(str, a.shape)), out_dir), file=sys.stderr, flush=True)
 
 
 def source_sha16():
@@ -210,6 +233,7 @@ def bench_spmv(args, torch, S, dev, dist, world, rank, name, rows, cols, nnz, rp
     settled = 0 if args.no_settle else settle(torch, lambda: S.spmv(rows, cols, rowptr, colidx, val, x, 1.0, 1.0, y))
     for _ in range(args.warmup):
         S.spmv(rows, cols, rowptr, colidx, val, x, 1.0, 1.0, y)
+    y.fill_(1.0)                                     # the timed steps start from y0 = 1, however many steps settled
     torch.cuda.synchronize()
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(args.steps)]
     if dist is not None:
@@ -230,10 +254,13 @@ def bench_spmv(args, torch, S, dev, dist, world, rank, name, rows, cols, nnz, rp
         elapsed = float(t.item())
     t_k = float(np.mean([e[0].elapsed_time(e[1]) for e in ev])) * 1e-3
     alg = nnz * 12 + (rows + 1) * 4 + 8 * cols + 16 * rows
+    y_last = y.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: y_last}, world)
     if rank == 0:
         rs = np.add.reduceat(v, rp[:-1].astype(np.int64)) if nnz else np.zeros(rows)
-        want = 1.0 + (settled + args.warmup + args.steps) * rs
-        if not np.allclose(y.cpu().numpy(), want, rtol=1e-9, atol=1e-9):
+        want = 1.0 + args.steps * rs
+        if not np.allclose(y_last, want, rtol=1e-9, atol=1e-9):
             raise SystemExit("spmv bench result mismatch")
         avg = nnz / max(rows, 1)
         sp_kernel = ("spmv_csr_lds_kernel" if avg > 96 else "spmv_csr_seg_kernel" if avg > 48 else
@@ -561,7 +588,11 @@ def main():
     ap.add_argument("--extras-timeout", type=float, default=420.0, help="seconds the product_merge child process may take")
     ap.add_argument("--op", choices=["spmm", "spmv"], default="spmm",
                     help="spmm (the headline metric) or spmv (same matrix, x = y0 = 1; secondary measurement)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import sblas_amd as S
@@ -642,7 +673,6 @@ def main():
     torch.cuda.synchronize()
     cold_ms = (time.perf_counter() - c0) / 10 * 1e3
     census = {k: c // 10 for k, c in S.panel_census().items()}
-    cold_steps = 10
 
     settled = 0 if args.no_settle else settle(torch, step)
     if dist is not None and not args.no_settle:
@@ -654,6 +684,7 @@ def main():
         settled += 40
     for _ in range(args.warmup):
         step()
+    C.fill_(1.0)                                    # the timed steps start from C0 = 1, however many steps settled
     torch.cuda.synchronize()
 
     barrier()
@@ -664,6 +695,7 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    C_last = C.clone() if args.dump_outputs else None   # the steps below go on accumulating into C
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -723,9 +755,13 @@ def main():
         t_dom = None                                 # the launcher's events bracket the LDS-tiled kernels only
     t_roof = t_dom if t_dom else t_stage2
 
+    if C_last is not None:                          # C as the caller sees it: rows x n, here in row-major order
+        dump_outputs(args.dump_outputs, {"C" if world == 1 else "C_rank%d" % rank: C_last.view(n, rows).cpu().numpy().T}, world)
+        del C_last
+
     # correctness guard on this rank's result: C = 1 + steps_total * A*B on 64-row windows (first panel, a middle one,
-    # the last rows) vs the oracle
-    total_steps = cold_steps + settled + args.warmup + args.steps + extra_steps
+    # the last rows) vs the oracle; C was reset to ones in front of the timed steps
+    total_steps = args.steps + extra_steps
     check, check_err = None, None
     failures = []                                   # result mismatches found on rank 0 (fatal, reported at the end)
     if rank == 0:

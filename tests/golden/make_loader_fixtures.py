@@ -1,8 +1,8 @@
-"""Generates tests/golden/loader_cases/*.mtx and loader_expected.json.
+"""Generates tests/golden/loader_cases/*.mtx, loader_expected.json and ash85_ref_loader.json.
 
 The .mtx inputs are written by this script (they are ours); the EXPECTED CSR arrays are produced by
-the reference's own loader (mmio.h + mmio_highlevel.h compiled from /root/reference into
-oracle/_ref/libref_loader.so by oracle/Makefile).  Run in the build container only:
+the reference's own loader (mmio.h + mmio_highlevel.h compiled from the reference tree into
+oracle/_ref/libref_loader.so by oracle/Makefile).  Run where that tree exists:
     python tests/golden/make_loader_fixtures.py
 """
 import json
@@ -81,6 +81,12 @@ CASES = {
 }
 
 
+def ref_arrays(path):
+    m, n, nnz, sym, rowptr, colidx, val = oracle_py.read_mtx_ref(path)
+    return dict(m=m, n=n, nnz=nnz, symmetric=sym, rowptr=rowptr.tolist(), colidx=colidx.tolist(),
+                val=[float(v).hex() for v in val])
+
+
 def main():
     if oracle_py.ref_loader() is None:
         raise SystemExit("oracle/_ref/libref_loader.so missing: run `make -C oracle` where /root/reference exists")
@@ -91,11 +97,13 @@ def main():
         path = os.path.join(out_dir, name + ".mtx")
         with open(path, "w") as f:
             f.write(text)
-        m, n, nnz, sym, rowptr, colidx, val = oracle_py.read_mtx_ref(path)
-        expected[name] = dict(m=m, n=n, nnz=nnz, symmetric=sym, rowptr=rowptr.tolist(), colidx=colidx.tolist(),
-                              val=[float(v).hex() for v in val])
+        expected[name] = ref_arrays(path)
     with open(os.path.join(HERE, "loader_expected.json"), "w") as f:
         json.dump(expected, f, indent=1)
+    ash85 = {"_provenance": "expected arrays = output of the reference's mmio_info/mmio_data (oracle/_ref) on ash85.mtx",
+             "ash85": ref_arrays(os.path.join(HERE, "ash85.mtx"))}
+    with open(os.path.join(HERE, "ash85_ref_loader.json"), "w") as f:
+        json.dump(ash85, f, indent=1)
     print("wrote", len(CASES), "cases")
 
 

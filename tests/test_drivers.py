@@ -10,7 +10,7 @@ import pytest
 from conftest import ASH85, GOLDEN, ROOT
 
 BIN = os.path.join(ROOT, "s-blas_amd", "bin")
-REF = "/root/reference"
+REF_DRIVERS = os.path.join(ROOT, "oracle", "_ref", "drivers")
 
 
 def run(exe, *args, cwd=None, env=None):
@@ -41,19 +41,16 @@ def test_cli_errors(sblas):
     assert rc != 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_reference_drivers_compile_unchanged_against_our_headers(sblas, tmp_path):
+@pytest.mark.skipif(not os.path.isdir(REF_DRIVERS), reason="oracle/_ref has no reference drivers (reference tree absent when build() ran)")
+def test_reference_drivers_compile_unchanged_against_our_headers(sblas):
     """Drop-in check: the reference's spmm_test.cu / spmv_test.cu / unit_test.cu, byte for byte, built with hipcc
-    against s-blas_amd/include + libsblas_hip.so.  The sources are copied to a temp dir OUTSIDE the repo only
-    because a quoted #include searches the including file's own directory first."""
+    against s-blas_amd/include + libsblas_hip.so.  build() compiles them where the reference tree exists (oracle/Makefile,
+    into oracle/_ref/drivers) and fails if one no longer compiles or links; here every one of them must be there."""
     for name in ("spmm_test", "spmv_test", "unit_test"):
-        src = tmp_path / (name + ".cu")
-        shutil.copyfile(os.path.join(REF, name + ".cu"), src)
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-x", "hip", str(src),
-               "-I" + os.path.join(ROOT, "s-blas_amd", "include"), "-I" + os.path.join(ROOT, "include"),
-               "-L" + os.path.join(ROOT, "s-blas_amd", "lib"), "-lsblas_hip", "-lpthread", "-o", str(tmp_path / name)]
-        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-2000:]
+        exe = os.path.join(REF_DRIVERS, name)
+        assert os.path.isfile(exe) and os.access(exe, os.X_OK), exe
+        with open(exe, "rb") as f:
+            assert f.read(4) == b"\x7fELF", exe
 
 
 @pytest.mark.gpu
