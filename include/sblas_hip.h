@@ -132,8 +132,38 @@ int sblas_hip_spmv_csr_f64_i32(int dev, void *stream,
                                const int32_t *rowptr, const int32_t *colidx, const double *val,
                                const double *x, double alpha, double beta, double *y);
 
+/* A per-matrix SpMV plan (the slot of rocSPARSE's csrmv_analysis / cusparseSpMV_preprocess).  The unplanned call above
+ * picks one kernel for the whole matrix from nnz / rows.  sblas_hip_spmv_plan_create copies rowptr to the host once,
+ * cuts the rows into work items of one kernel block each (sblas_spmv_plan_classify below: per 256-row tile the kernel its
+ * rows ask for; a row longer than SBLAS_SPMV_SPLIT_MIN cut into pieces of SBLAS_SPMV_SPLIT_PIECE nonzeros that run on as
+ * many workgroups), finds each LDS-window item's column window on the device and keeps all of it in a device buffer of
+ * its own; a planned call launches one kernel per non-empty class, in a fixed order, on `stream`.
+ *   - create / destroy allocate and synchronise `stream`; a planned call allocates nothing and never synchronises
+ *     (graph-capturable);
+ *   - the plan covers one structure: the same rowptr / colidx arrays and their contents.  Values (val, x) may change
+ *     freely; a call whose device, rows, cols, nnz or structure pointers differ from the plan's returns SBLAS_E_INVALID;
+ *   - one call at a time per plan (split rows keep their partial sums in the plan's buffer);
+ *   - results: a matrix whose tiles all ask for the kernel the unplanned call picks gives the unplanned call's bits.
+ *     Split rows are summed in another order (pieces in CSR order, then folded in piece order: deterministic, never
+ *     atomics), so their last bits can differ from the unplanned call's;
+ *   - a plan whose items are all of one lanes-per-row / stream / segmented class and has no split rows runs the
+ *     unplanned launch (its items are the unplanned kernel's blocks);
+ *   - SBLAS_SPMV_VARIANT set when the plan is made, or an empty matrix: the plan is inactive (info[0] = 0) and planned
+ *     calls run the unplanned launcher;
+ *   - SBLAS_VALIDATE=1: plan_create checks the structure on the device first (SBLAS_E_INVALID, no plan). */
+int sblas_hip_spmv_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                               const int32_t *rowptr, const int32_t *colidx, void **plan_out);
+int sblas_hip_spmv_plan_destroy(void *plan);
+/* out: [0] planned at all (0: calls run unplanned), work items of the lanes-per-row [1], stream with 4096 [2] / 6144 [3]
+ * products of LDS, segmented [4] and LDS-window [5] kernels, [6] split rows, [7] pieces of the split rows */
+int sblas_hip_spmv_plan_info(const void *plan, int64_t out[8]);
+int sblas_hip_spmv_csr_f64_i32_planned(const void *plan, int dev, void *stream,
+                                       int64_t rows, int64_t cols, int64_t nnz,
+                                       const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                       const double *x, double alpha, double beta, double *y);
+
 /* ---------------------------------------------------------------------------------------
- * y = beta * y + alpha * x   (elementwise, n elements)
+ * y = beta * y + alpha * x  (elementwise, n elements)
  * Replaces the denseVector_plusEqual_denseVector launches at matrix.h:613-625 and :714-726
  * (kernel.h:27-38).  Note the argument order mirrors the kernel: y is updated in place.
  * ------------------------------------------------------------------------------------- */
@@ -224,6 +254,26 @@ int64_t sblas_partition_nnz(const int32_t *rowptr, int32_t rows, int32_t nnz, in
 /* Leading-dimension block partition of DenseMatrix::sync2gpu(segment), matrix.h:554-568. */
 int sblas_partition_dense(int64_t first_order, int n_gpu, int i_gpu,
                           int64_t *offset, int64_t *dim);
+
+/* The SpMV plan's classifier (sblas_hip_spmv_plan_create runs it on a host copy of rowptr).  Cuts rows [0, rows) into
+ * work items of at most one kernel block of consecutive rows, four int32 each: first row, row count, kind
+ * (SBLAS_SPMV_ITEM_*), pieces (split items only, else 0).  Items come in row order and cover every row exactly once.
+ * nnz sets the matrix average the unplanned launcher would use.  split_min / piece <= 0 take the defaults below; a row
+ * with more than split_min nonzeros becomes a split item of ceil(len / piece) pieces.  Writes up to max_items items
+ * when `items` is not NULL and returns the number of items, or -1 (bad argument, descending row pointers). */
+#define SBLAS_SPMV_ITEM_LPR 0        /* lanes-per-row kernel, 4 lanes per row (64 rows per item)     */
+#define SBLAS_SPMV_ITEM_STREAM4096 1 /* stream kernel, 4096 products of LDS (256 rows)               */
+#define SBLAS_SPMV_ITEM_STREAM6144 2 /* stream kernel, 6144 products of LDS (256 rows)               */
+#define SBLAS_SPMV_ITEM_SEG 3        /* segmented kernel, four rows per wave (16 rows)               */
+#define SBLAS_SPMV_ITEM_LDS_S2 4     /* LDS-window kernel, 2 / 3 / 4 / 7 slices in flight (8 rows)   */
+#define SBLAS_SPMV_ITEM_LDS_S3 5
+#define SBLAS_SPMV_ITEM_LDS_S4 6
+#define SBLAS_SPMV_ITEM_LDS_S7 7
+#define SBLAS_SPMV_ITEM_SPLIT 8      /* one long row, cut into pieces                                */
+#define SBLAS_SPMV_SPLIT_MIN 12288   /* default: rows longer than two 6144-product stream runs       */
+#define SBLAS_SPMV_SPLIT_PIECE 4096  /* default nonzeros per piece (one 256-thread workgroup)        */
+int64_t sblas_spmv_plan_classify(const int32_t *rowptr, int64_t rows, int64_t nnz, int64_t split_min, int64_t piece,
+                                 int32_t *items, int64_t max_items);
 
 /* Dense initialiser of the reference's DenseMatrix(h, w, order) / DenseVector(len) constructors (matrix.h:519-528,
  * :663-672; utility.h:197; config.h:23 seed 211): srand(seed), then rand() / RAND_MAX in storage order (host memory). */

@@ -104,6 +104,23 @@ hipError_t validate_csr(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, 
 hipError_t panel_stats(unsigned long long out[4], bool reset);
 hipError_t launch_spmv(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
                        const double *val, const double *x, double alpha, double beta, double *y);
+// A per-matrix SpMV plan (capi.hip: sblas_hip_spmv_plan_*).  Work items of the kernel classes, grouped by class
+// (items + off[k] .. items + off[k + 1]; int4 {first row, row count, window lo, window hi}; the window only for the
+// LDS-window classes), the pieces of the split rows ({row, first nonzero, end, partial slot}), the split rows ({row,
+// first slot, pieces, 0}) and one partial sum per piece, all in the plan's device buffer.
+enum { SPMV_ITEM_LPR = 0, SPMV_ITEM_STREAM4096 = 1, SPMV_ITEM_STREAM6144 = 2, SPMV_ITEM_SEG = 3, SPMV_ITEM_LDS_S2 = 4,
+       SPMV_ITEM_LDS_S3 = 5, SPMV_ITEM_LDS_S4 = 6, SPMV_ITEM_LDS_S7 = 7, SPMV_ITEM_SPLIT = 8, SPMV_ITEM_KERNELS = 8 };
+struct SpmvPlanView {
+    int4 *items = nullptr;
+    int64_t off[SPMV_ITEM_KERNELS + 1] = {0};
+    const int4 *pieces = nullptr, *srows = nullptr;
+    double *partial = nullptr;
+    int64_t n_pieces = 0, n_split = 0;
+    bool as_unplanned = false; // every item is of one lanes-per-row / stream / segmented class: launch_spmv's launch
+};
+hipError_t spmv_plan_windows(hipStream_t s, int n, int4 *items, const int *rowptr, const int *colidx);
+hipError_t launch_spmv_planned(hipStream_t s, int cols, const SpmvPlanView &pv, const int *rowptr, const int *colidx,
+                               const double *val, const double *x, double alpha, double beta, double *y);
 hipError_t launch_axpby(hipStream_t s, int64_t n, double alpha, const double *x, double beta, double *y);
 void kernel_events_enable(bool on);
 hipError_t kernel_events_last_ms(float *ms);

@@ -17,12 +17,14 @@ __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_rea
 // L2), then the partial sums are folded with xor-shuffles inside the wave -- the wave64 successor of
 // the reference's unused sum_32_shfl (utility.h:241-246).
 // ---------------------------------------------------------------------------------------------
+// The kernels below are written as a body over the block's rows [row_begin, row_end) and two entry points: the
+// unplanned one derives that range from blockIdx.x (as it always has), the planned one reads it from its work item
+// (sblas_hip_spmv_plan_*: int4 {first row, row count, window lo, window hi}).
 template <int LPR>
-__global__ __launch_bounds__(256) void spmv_csr_kernel(int rows, const int *__restrict__ rowptr,
-                                                      const int *__restrict__ colidx,
-                                                      const double *__restrict__ val,
-                                                      const double *__restrict__ x, double alpha, double beta,
-                                                      double *__restrict__ y)
+__device__ __forceinline__ void spmv_csr_body(int row_begin, int row_end, const int *__restrict__ rowptr,
+                                              const int *__restrict__ colidx, const double *__restrict__ val,
+                                              const double *__restrict__ x, double alpha, double beta,
+                                              double *__restrict__ y)
 {
     constexpr int ROWS_PER_BLOCK = 256 / LPR;
     // a row far longer than the lane group was sized for (skewed matrices: the kernel is picked by the AVERAGE row
@@ -35,10 +37,10 @@ __global__ __launch_bounds__(256) void spmv_csr_kernel(int rows, const int *__re
     if (threadIdx.x == 0) n_long = 0;
     __syncthreads();
     const int l = threadIdx.x % LPR;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + threadIdx.x / LPR;
+    const int row = row_begin + threadIdx.x / LPR;
     double s0 = 0.0, s1 = 0.0;
     bool deferred = false;
-    if (row < rows) {
+    if (row < row_end) {
         const int p1 = rowptr[row + 1];
         int p = rowptr[row];
         deferred = p1 - p > LONG;
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(256) void spmv_csr_kernel(int rows, const int *__re
     double s = s0 + s1;
 #pragma unroll
     for (int m = LPR / 2; m > 0; m >>= 1) s += __shfl_xor(s, m, WAVE);
-    if (row < rows && l == 0 && !deferred) {
+    if (row < row_end && l == 0 && !deferred) {
         const double r = alpha * s;
         y[row] = (beta == 0.0) ? r : fma(beta, y[row], r);
     }
@@ -88,6 +90,25 @@ __global__ __launch_bounds__(256) void spmv_csr_kernel(int rows, const int *__re
         __syncthreads();
     }
 }
+template <int LPR>
+__global__ __launch_bounds__(256) void spmv_csr_kernel(int rows, const int *__restrict__ rowptr,
+                                                      const int *__restrict__ colidx,
+                                                      const double *__restrict__ val,
+                                                      const double *__restrict__ x, double alpha, double beta,
+                                                      double *__restrict__ y)
+{
+    spmv_csr_body<LPR>(blockIdx.x * (256 / LPR), rows, rowptr, colidx, val, x, alpha, beta, y);
+}
+template <int LPR>
+__global__ __launch_bounds__(256) void spmv_csr_planned_kernel(const int4 *__restrict__ items, const int *__restrict__ rowptr,
+                                                              const int *__restrict__ colidx,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ x, double alpha, double beta,
+                                                              double *__restrict__ y)
+{
+    const int4 it = items[blockIdx.x];
+    spmv_csr_body<LPR>(it.x, it.x + it.y, rowptr, colidx, val, x, alpha, beta, y);
+}
 
 // ---------------------------------------------------------------------------------------------
 // SpMV for short and medium rows (5..64 nonzeros per row on average), stream form.  The lanes-per-row kernel gives every row a lane group
@@ -106,17 +127,14 @@ constexpr int ST_ROWS = 256;
 constexpr int ST_LONG = 96;  // rows longer than this are summed by a whole wave
 __device__ __forceinline__ int st_skew(int q) { return q + (q >> 5); } // rows of equal length: spread the LDS banks
 template <int ST_CAP>
-__global__ __launch_bounds__(ST_ROWS) void spmv_csr_stream_kernel(int rows, const int *__restrict__ rowptr,
-                                                                 const int *__restrict__ colidx,
-                                                                 const double *__restrict__ val,
-                                                                 const double *__restrict__ x, double alpha, double beta,
-                                                                 double *__restrict__ y)
+__device__ __forceinline__ void spmv_csr_stream_body(int row0, int nr, const int *__restrict__ rowptr,
+                                                     const int *__restrict__ colidx, const double *__restrict__ val,
+                                                     const double *__restrict__ x, double alpha, double beta,
+                                                     double *__restrict__ y)
 {
     __shared__ double prod[ST_CAP + ST_CAP / 32 + 1];
     __shared__ int sp[ST_ROWS + 1];
     const int tid = threadIdx.x;
-    const int row0 = blockIdx.x * ST_ROWS;
-    const int nr = min(ST_ROWS, rows - row0);
     if (tid < nr) sp[tid] = rowptr[row0 + tid];
     if (tid == 0) sp[nr] = rowptr[row0 + nr];
     __syncthreads();
@@ -199,6 +217,27 @@ __global__ __launch_bounds__(ST_ROWS) void spmv_csr_stream_kernel(int rows, cons
         r0 = r1;
     }
 }
+template <int ST_CAP>
+__global__ __launch_bounds__(ST_ROWS) void spmv_csr_stream_kernel(int rows, const int *__restrict__ rowptr,
+                                                                 const int *__restrict__ colidx,
+                                                                 const double *__restrict__ val,
+                                                                 const double *__restrict__ x, double alpha, double beta,
+                                                                 double *__restrict__ y)
+{
+    const int row0 = blockIdx.x * ST_ROWS;
+    spmv_csr_stream_body<ST_CAP>(row0, min(ST_ROWS, rows - row0), rowptr, colidx, val, x, alpha, beta, y);
+}
+template <int ST_CAP>
+__global__ __launch_bounds__(ST_ROWS) void spmv_csr_stream_planned_kernel(const int4 *__restrict__ items,
+                                                                         const int *__restrict__ rowptr,
+                                                                         const int *__restrict__ colidx,
+                                                                         const double *__restrict__ val,
+                                                                         const double *__restrict__ x, double alpha,
+                                                                         double beta, double *__restrict__ y)
+{
+    const int4 it = items[blockIdx.x];
+    spmv_csr_stream_body<ST_CAP>(it.x, it.y, rowptr, colidx, val, x, alpha, beta, y);
+}
 
 // ---------------------------------------------------------------------------------------------
 // SpMV for medium rows (49..96 nonzeros), segmented form.  With one row per wave a 73-nonzero row (Queen_4147) fills
@@ -258,6 +297,61 @@ __global__ __launch_bounds__(256) void spmv_csr_seg_kernel(int rows, const int *
     }
 }
 
+// The planned form: the same code on the rows of its work item.  (Its own copy: written as one body called by both
+// kernels, the compiler gave the <4, 5> instantiation other register allocation -- 40 instead of 52 VGPRs -- and the planned
+// kernel ran 16 % slower on Queen-like rows.)
+template <int R, int S>
+__global__ __launch_bounds__(256) void spmv_csr_seg_planned_kernel(const int4 *__restrict__ items, const int *__restrict__ rowptr,
+                                                          const int *__restrict__ colidx,
+                                                          const double *__restrict__ val,
+                                                          const double *__restrict__ x, double alpha, double beta,
+                                                          double *__restrict__ y)
+{
+    static_assert(R >= 1 && R <= 16, "row pointers are broadcast from the first R + 1 lanes");
+    const int lane = threadIdx.x & 63;
+    const int4 it = items[blockIdx.x];
+    const int rows = it.x + it.y; // the end of the item's rows
+    const int r0 = it.x + (int)(threadIdx.x >> 6) * R;
+    if (r0 >= rows) return;
+    const int mine = rowptr[min(r0 + min(lane, R), rows)];
+    int b[R + 1];
+#pragma unroll
+    for (int i = 0; i <= R; ++i) b[i] = __builtin_amdgcn_readlane(mine, i);
+    const int p0 = b[0], p1 = b[R], last = p1 - 1;
+    double acc[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) acc[i] = 0.0;
+    for (int base = p0; base < p1; base += S * WAVE) {
+        int c[S];
+        double a[S], xv[S];
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            const int p = min(base + u * WAVE + lane, last);
+            c[u] = colidx[p];
+            a[u] = val[p];
+        }
+#pragma unroll
+        for (int u = 0; u < S; ++u) xv[u] = x[c[u]];
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            const int idx = base + u * WAVE + lane;
+            const double prod = (idx <= last) ? a[u] * xv[u] : 0.0;
+#pragma unroll
+            for (int i = 0; i < R; ++i) acc[i] += (idx >= b[i] && idx < b[i + 1]) ? prod : 0.0;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        double sum = acc[i];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) sum += __shfl_xor(sum, m, WAVE);
+        if (lane == i && r0 + i < rows) {
+            const double res = alpha * sum;
+            y[r0 + i] = (beta == 0.0) ? res : fma(beta, y[r0 + i], res);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // SpMV for long rows, x window in LDS (second attempt).  Diagnostics on the plain kernel: the A stream alone runs at
 // 6.8 TB/s with the same row-per-wave shape (tools/stream_bench.hip), replacing the gather by a one-line read still
@@ -277,19 +371,20 @@ constexpr int SPMV_LDS_THREADS = SPMV_LDS_ROWS * 64;
 constexpr int SPMV_LDS_CAP = 4608;  // doubles (36 KiB): four blocks per CU
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int RW, int S> // RW rows per wave (16 RW rows per block), S slices of 64 nonzeros fetched ahead per row
-__global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_kernel(int rows, int cols, const int *__restrict__ rowptr,
-                                                           const int *__restrict__ colidx,
-                                                           const double *__restrict__ val,
-                                                           const double *__restrict__ x, double alpha, double beta,
-                                                           double *__restrict__ y)
-{
+// RW rows per wave (8 RW rows per block), S slices of 64 nonzeros fetched ahead per row.  PLANNED: the block's column
+// window (plo, phi: first and last column its rows refer to) comes from the plan instead of the block-wide vote.
+template <int RW, int S, bool PLANNED>
+__device__ __forceinline__ void spmv_csr_lds_body(int blk, int rows, int cols, const int *__restrict__ rowptr,
+                                                  const int *__restrict__ colidx, const double *__restrict__ val,
+                                                  const double *__restrict__ x, double alpha, double beta,
+                                                  double *__restrict__ y, int plo, int phi)
+{ // blk: the block's first row in units of RW rows; rows: the end of the block's rows
     extern __shared__ __attribute__((aligned(16))) double xs[];
     __shared__ int sm_lo, sm_hi;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = wave_uniform(tid >> 6);
-    const int row0 = (blockIdx.x * SPMV_LDS_ROWS + wave) * RW;
-    if (tid == 0) {
+    const int row0 = (blk + wave) * RW;
+    if (!PLANNED && tid == 0) {
         sm_lo = 0x7fffffff;
         sm_hi = -1;
     }
@@ -314,7 +409,7 @@ __global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_kernel(int rows
     bool ce_valid = false;
 #pragma unroll
     for (int r = 0; r < RW; ++r)
-        if (has[r] && (lane >> 1) == r) {
+        if (!PLANNED && has[r] && (lane >> 1) == r) {
             ce = colidx[(lane & 1) ? last[r] : p0[r]];
             ce_valid = true;
         }
@@ -328,13 +423,16 @@ __global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_kernel(int rows
                 a[r][u] = val[p];
             }
         }
-    lds_barrier(); // sm_lo / sm_hi initialised
-    if (ce_valid) {
-        if (lane & 1) atomicMax(&sm_hi, ce);
-        else atomicMin(&sm_lo, ce);
+    int lo = plo, hi = phi;
+    if (!PLANNED) {
+        lds_barrier(); // sm_lo / sm_hi initialised
+        if (ce_valid) {
+            if (lane & 1) atomicMax(&sm_hi, ce);
+            else atomicMin(&sm_lo, ce);
+        }
+        lds_barrier();
+        lo = sm_lo, hi = sm_hi;
     }
-    lds_barrier();
-    int lo = sm_lo, hi = sm_hi;
     if (lo > hi) {
         lo = 0;
         hi = -1;
@@ -417,6 +515,26 @@ __global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_kernel(int rows
             y[row] = (beta == 0.0) ? res : fma(beta, y[row], res);
         }
     }
+}
+template <int RW, int S>
+__global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_kernel(int rows, int cols, const int *__restrict__ rowptr,
+                                                           const int *__restrict__ colidx,
+                                                           const double *__restrict__ val,
+                                                           const double *__restrict__ x, double alpha, double beta,
+                                                           double *__restrict__ y)
+{
+    spmv_csr_lds_body<RW, S, false>(blockIdx.x * SPMV_LDS_ROWS, rows, cols, rowptr, colidx, val, x, alpha, beta, y, 0, 0);
+}
+template <int S> // one row per wave
+__global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_planned_kernel(const int4 *__restrict__ items, int cols,
+                                                                   const int *__restrict__ rowptr,
+                                                                   const int *__restrict__ colidx,
+                                                                   const double *__restrict__ val,
+                                                                   const double *__restrict__ x, double alpha, double beta,
+                                                                   double *__restrict__ y)
+{
+    const int4 it = items[blockIdx.x];
+    spmv_csr_lds_body<1, S, true>(it.x, it.x + it.y, cols, rowptr, colidx, val, x, alpha, beta, y, it.z, it.w);
 }
 
 
@@ -514,6 +632,142 @@ hipError_t launch_spmv(hipStream_t s, int rows, int cols, int64_t nnz, const int
     if (avg <= 24.0) return spmv_go<16>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
     if (avg <= 48.0) return spmv_go<32>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
     return spmv_go<64>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Split rows (planned calls only).  A row of 10^5..10^6 nonzeros in the kernels above is walked by one block (stream,
+// lanes-per-row) or one wave (segmented, LDS-window) while the rest of the GPU idles.  The plan cuts such a row into
+// pieces of SBLAS_SPMV_SPLIT_PIECE nonzeros, contiguous in CSR order; one 256-thread workgroup sums a piece into a
+// partial of the plan's buffer, and a second kernel folds the partials of a row in piece order and applies alpha / beta.
+// No atomics, no workgroup waits on another: the order of every addition is fixed by the plan, so the result is the same
+// bits on every call.  Inside a piece thread t takes nonzeros t, t + 256, ... (UN loads in flight, clamped indices, as in
+// the stream kernel), the 64 lanes of a wave are folded by the xor-butterfly and the four waves in wave order.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void spmv_split_piece_kernel(const int4 *__restrict__ pieces,
+                                                              const int *__restrict__ colidx,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ x, double *__restrict__ partial)
+{
+    __shared__ double wsum[4];
+    const int4 pc = pieces[blockIdx.x]; // {row, first nonzero, end, partial slot}
+    const int tid = threadIdx.x;
+    const int last = pc.z - 1;
+    constexpr int UN = 8;
+    double acc = 0.0;
+    for (int p = pc.y + tid; p < pc.z; p += UN * 256) {
+        int c[UN];
+        double a[UN], xv[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int q = min(p + u * 256, last);
+            c[u] = colidx[q];
+            a[u] = val[q];
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) xv[u] = x[c[u]];
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+            if (p + u * 256 < pc.z) acc = fma(a[u], xv[u], acc);
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, WAVE);
+    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) partial[pc.w] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// one wave per split row: 64 partials loaded at a time, added in piece order by lane 0's walk through them (readlane)
+__device__ __forceinline__ double readlane_f64(double v, int l)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__global__ __launch_bounds__(64) void spmv_split_fold_kernel(const int4 *__restrict__ srows, const double *__restrict__ partial,
+                                                            double alpha, double beta, double *__restrict__ y)
+{
+    const int4 sr = srows[blockIdx.x]; // {row, first slot, pieces, -}
+    const int lane = threadIdx.x;
+    double sum = 0.0;
+    for (int j0 = 0; j0 < sr.z; j0 += 64) {
+        const double v = (j0 + lane < sr.z) ? partial[sr.y + j0 + lane] : 0.0;
+        const int m = min(64, sr.z - j0);
+        for (int j = 0; j < m; ++j) sum += readlane_f64(v, j);
+    }
+    if (lane == 0) {
+        const double res = alpha * sum;
+        y[sr.x] = (beta == 0.0) ? res : fma(beta, y[sr.x], res);
+    }
+}
+
+// the column window of every LDS-window item (first and last column its rows refer to): the block-wide vote of the
+// unplanned kernel, taken once when the plan is made
+__global__ __launch_bounds__(256) void spmv_plan_window_kernel(int n, int4 *__restrict__ items, const int *__restrict__ rowptr,
+                                                              const int *__restrict__ colidx)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int4 it = items[i];
+    int lo = 0x7fffffff, hi = -1;
+    for (int r = it.x; r < it.x + it.y; ++r) {
+        const int a0 = rowptr[r], a1 = rowptr[r + 1];
+        if (a1 > a0) {
+            lo = min(lo, colidx[a0]);
+            hi = max(hi, colidx[a1 - 1]);
+        }
+    }
+    it.z = lo;
+    it.w = hi;
+    items[i] = it;
+}
+
+hipError_t spmv_plan_windows(hipStream_t s, int n, int4 *items, const int *rowptr, const int *colidx)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(spmv_plan_window_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, items, rowptr, colidx);
+    return hipGetLastError();
+}
+
+// A planned call: one launch per non-empty class, in the order of the SBLAS_SPMV_ITEM_* numbers, then the split rows'
+// pieces and their fold.  Every launch writes rows no other launch writes.
+hipError_t launch_spmv_planned(hipStream_t s, int cols, const SpmvPlanView &pv, const int *rowptr, const int *colidx,
+                               const double *val, const double *x, double alpha, double beta, double *y)
+{
+    auto grid = [&](int k) { return dim3((unsigned)(pv.off[k + 1] - pv.off[k])); };
+    auto items = [&](int k) { return pv.items + pv.off[k]; };
+    auto has = [&](int k) { return pv.off[k + 1] > pv.off[k]; };
+    if (has(SPMV_ITEM_LPR))
+        hipLaunchKernelGGL(spmv_csr_planned_kernel<4>, grid(SPMV_ITEM_LPR), dim3(256), 0, s, items(SPMV_ITEM_LPR), rowptr,
+                           colidx, val, x, alpha, beta, y);
+    if (has(SPMV_ITEM_STREAM4096))
+        hipLaunchKernelGGL(spmv_csr_stream_planned_kernel<4096>, grid(SPMV_ITEM_STREAM4096), dim3(ST_ROWS), 0, s,
+                           items(SPMV_ITEM_STREAM4096), rowptr, colidx, val, x, alpha, beta, y);
+    if (has(SPMV_ITEM_STREAM6144))
+        hipLaunchKernelGGL(spmv_csr_stream_planned_kernel<6144>, grid(SPMV_ITEM_STREAM6144), dim3(ST_ROWS), 0, s,
+                           items(SPMV_ITEM_STREAM6144), rowptr, colidx, val, x, alpha, beta, y);
+    if (has(SPMV_ITEM_SEG))
+        hipLaunchKernelGGL((spmv_csr_seg_planned_kernel<4, 5>), grid(SPMV_ITEM_SEG), dim3(256), 0, s, items(SPMV_ITEM_SEG),
+                           rowptr, colidx, val, x, alpha, beta, y);
+#define SBLAS_SPMV_LDS_PLANNED(K, SV)                                                                                \
+    if (has(K)) {                                                                                                    \
+        raise_dynamic_lds((const void *)spmv_csr_lds_planned_kernel<SV>, (SPMV_LDS_CAP + 128) * sizeof(double));     \
+        hipLaunchKernelGGL(spmv_csr_lds_planned_kernel<SV>, grid(K), dim3(SPMV_LDS_THREADS),                         \
+                           (SPMV_LDS_CAP + 128) * sizeof(double), s, items(K), cols, rowptr, colidx, val, x, alpha,   \
+                           beta, y);                                                                                 \
+    }
+    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S2, 2)
+    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S3, 3)
+    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S4, 4)
+    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S7, 7)
+#undef SBLAS_SPMV_LDS_PLANNED
+    if (pv.n_pieces > 0) {
+        hipLaunchKernelGGL(spmv_split_piece_kernel, dim3((unsigned)pv.n_pieces), dim3(256), 0, s, pv.pieces, colidx, val, x,
+                           pv.partial);
+        hipLaunchKernelGGL(spmv_split_fold_kernel, dim3((unsigned)pv.n_split), dim3(64), 0, s, pv.srows, pv.partial, alpha,
+                           beta, y);
+    }
+    return hipGetLastError();
 }
 
 } // namespace sblas

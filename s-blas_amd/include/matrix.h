@@ -266,14 +266,14 @@ template <typename IdxType, typename DataType> class CsrSparseMatrix {
     CsrSparseMatrix()
         : csrRowPtr(NULL), csrColIdx(NULL), csrVal(NULL), csrRowPtr_gpu(NULL), csrColIdx_gpu(NULL),
           csrVal_gpu(NULL), nnz_gpu(NULL), starting_row_gpu(NULL), stoping_row_gpu(NULL), nnz(0), height(0),
-          width(0), n_gpu(0), policy(none), spmm_plan_gpu(NULL), spmm_plan_n(NULL)
+          width(0), n_gpu(0), policy(none), spmm_plan_gpu(NULL), spmm_plan_n(NULL), spmv_plan_gpu(NULL)
     {
     }
     // MatrixMarket file -> host CSR (one parse of the text; rows keep file order, see sblas_mm_read_csr)
     CsrSparseMatrix(const char *filename)
         : csrRowPtr(NULL), csrColIdx(NULL), csrVal(NULL), csrRowPtr_gpu(NULL), csrColIdx_gpu(NULL),
           csrVal_gpu(NULL), nnz_gpu(NULL), starting_row_gpu(NULL), stoping_row_gpu(NULL), nnz(0), height(0),
-          width(0), n_gpu(0), policy(none), spmm_plan_gpu(NULL), spmm_plan_n(NULL)
+          width(0), n_gpu(0), policy(none), spmm_plan_gpu(NULL), spmm_plan_n(NULL), spmv_plan_gpu(NULL)
     {
         int m = 0, n = 0, nnzA = 0, sym = 0;
         const int rc = mmio_info(&m, &n, &nnzA, &sym, filename);
@@ -310,6 +310,18 @@ template <typename IdxType, typename DataType> class CsrSparseMatrix {
             spmm_plan_gpu = NULL;
             spmm_plan_n = NULL;
         }
+        if (spmv_plan_gpu) { // (SBLAS_SPMV_PLAN=1, spmv.h)
+            for (unsigned i = 0; i < n_gpu; ++i)
+                if (spmv_plan_gpu[i] && spmv_plan_gpu[i] != spmv_plan_failed()) (void)sblas_hip_spmv_plan_destroy(spmv_plan_gpu[i]);
+            free(spmv_plan_gpu);
+            spmv_plan_gpu = NULL;
+        }
+    }
+    // marks a GPU whose SpMV plan could not be made (its calls run unplanned)
+    static void *spmv_plan_failed()
+    {
+        static char tag;
+        return &tag;
     }
     ~CsrSparseMatrix()
     {
@@ -336,6 +348,7 @@ template <typename IdxType, typename DataType> class CsrSparseMatrix {
         assert(policy != none);
         spmm_plan_gpu = (void **)calloc(n_gpu, sizeof(void *));
         spmm_plan_n = (int64_t *)calloc(n_gpu, sizeof(int64_t));
+        spmv_plan_gpu = (void **)calloc(n_gpu, sizeof(void *));
         SAFE_ALOC_HOST(csrRowPtr_gpu, n_gpu * sizeof(IdxType *));
         SAFE_ALOC_HOST(csrColIdx_gpu, n_gpu * sizeof(IdxType *));
         SAFE_ALOC_HOST(csrVal_gpu, n_gpu * sizeof(DataType *));
@@ -423,6 +436,8 @@ template <typename IdxType, typename DataType> class CsrSparseMatrix {
     // (not in the reference) per-GPU plan of the SpMM ops and the width it was made for; see spmm.h
     void **spmm_plan_gpu;
     int64_t *spmm_plan_n;
+    // (not in the reference) per-GPU SpMV plan of the row block, made by sblas_spmv_csr_v1 under SBLAS_SPMV_PLAN=1
+    void **spmv_plan_gpu;
 };
 
 // ----------------------------------------------------------------------------------------------

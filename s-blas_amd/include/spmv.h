@@ -1,7 +1,7 @@
 // spmv.h -- y = alpha * A * x + beta * y with A in CSR, on one or more MI355X (reference spmv.h:15-19, :35-39).
 //   sblas_spmv_csr_cpu  single-threaded host loop (the verifier)
 //   sblas_spmv_csr_v1   A split into nnz-balanced row blocks, x and y replicated; partial y merged by an RCCL
-//                       all-reduce, then y = beta*y + alpha*sum on every GPU
+//                       all-reduce, then y = beta*y + alpha*sum on every GPU (SBLAS_SPMV_PLAN=1: planned row blocks)
 #ifndef SBLAS_AMD_SPMV_H
 #define SBLAS_AMD_SPMV_H
 
@@ -54,6 +54,13 @@ void sblas_spmv_csr_v1(CsrSparseMatrix<IdxType, DataType> *pA, DenseVector<IdxTy
     // SBLAS_MERGE=allreduce for the reference's zero-filled y copy + all-reduce + axpby (spmv.h:60-138).
     const char *merge_mode = getenv("SBLAS_MERGE");
     const bool use_allreduce = merge_mode && !strcmp(merge_mode, "allreduce");
+    // SBLAS_SPMV_PLAN=1 (opt-in): each GPU's row block gets a per-matrix plan (sblas_hip_spmv_plan_*) at the first call,
+    // kept in the CsrSparseMatrix until its next sync2gpu; later calls run on it.  Opt-in because the plan sums the rows it
+    // splits in another order (their last bits can differ); without it every call is the unplanned one, as before.
+    static const bool plans = [] {
+        const char *e = getenv("SBLAS_SPMV_PLAN");
+        return e && e[0] == '1';
+    }();
     std::vector<DataType *> ycopy(n_gpu, (DataType *)NULL), gather(n_gpu, (DataType *)NULL);
     std::vector<void *> streams(n_gpu);
     std::vector<GPU_Timer *> timers(n_gpu);
@@ -75,11 +82,31 @@ void sblas_spmv_csr_v1(CsrSparseMatrix<IdxType, DataType> *pA, DenseVector<IdxTy
             ycopy[i] = (DataType *)sblas_rt::workspace(i, (size_t)m_i * sizeof(DataType), sblas_rt::WS_PARTIAL);
             gather[i] = (DataType *)sblas_rt::workspace(i, all_blocks * sizeof(DataType), sblas_rt::WS_GATHER);
         }
-        sblas_rt::must_sblas(
-            sblas_hip_spmv_csr(-1, streams[i], vt, it, m_i, K, (int64_t)pA->nnz_gpu[i], pA->csrRowPtr_gpu[i],
-                               pA->csrColIdx_gpu[i], pA->csrVal_gpu[i], pB->val_gpu[i], 1.0, use_allreduce ? 1.0 : 0.0,
-                               use_allreduce ? ycopy[i] + (size_t)pA->starting_row_gpu[i] : ycopy[i]),
-            "sblas_hip_spmv_csr");
+        DataType *yi = use_allreduce ? ycopy[i] + (size_t)pA->starting_row_gpu[i] : ycopy[i];
+        const double beta_i = use_allreduce ? 1.0 : 0.0;
+        void *plan = plans && vt == SBLAS_F64 && it == SBLAS_I32 && pA->spmv_plan_gpu ? pA->spmv_plan_gpu[i] : NULL;
+        if (plans && vt == SBLAS_F64 && it == SBLAS_I32 && pA->spmv_plan_gpu && !plan) { // first call: plan the row block
+            const int rc = sblas_hip_spmv_plan_create(-1, streams[i], m_i, K, (int64_t)pA->nnz_gpu[i],
+                                                      (const int32_t *)pA->csrRowPtr_gpu[i], (const int32_t *)pA->csrColIdx_gpu[i],
+                                                      &plan);
+            int64_t info[8] = {0};
+            if (rc == SBLAS_OK) (void)sblas_hip_spmv_plan_info(plan, info);
+            else plan = NULL; // not fatal: this GPU's calls run unplanned
+            pA->spmv_plan_gpu[i] = plan ? plan : pA->spmv_plan_failed();
+            cout << "GPU-" << i << " SpMV plan: " << (rc != SBLAS_OK ? "not made (" : info[0] ? "active (" : "inactive (")
+                 << (rc != SBLAS_OK ? sblas_hip_error_string(rc) : "made") << ")" << std::endl;
+        }
+        if (plan && plan != pA->spmv_plan_failed())
+            sblas_rt::must_sblas(sblas_hip_spmv_csr_f64_i32_planned(plan, -1, streams[i], m_i, K, (int64_t)pA->nnz_gpu[i],
+                                                                    (const int32_t *)pA->csrRowPtr_gpu[i],
+                                                                    (const int32_t *)pA->csrColIdx_gpu[i],
+                                                                    (const double *)pA->csrVal_gpu[i], (const double *)pB->val_gpu[i],
+                                                                    1.0, beta_i, (double *)yi),
+                                 "sblas_hip_spmv_csr_f64_i32_planned");
+        else
+            sblas_rt::must_sblas(sblas_hip_spmv_csr(-1, streams[i], vt, it, m_i, K, (int64_t)pA->nnz_gpu[i], pA->csrRowPtr_gpu[i],
+                                                    pA->csrColIdx_gpu[i], pA->csrVal_gpu[i], pB->val_gpu[i], 1.0, beta_i, yi),
+                                 "sblas_hip_spmv_csr");
         timers[i] = new GPU_Timer((hipStream_t)streams[i]);
         timers[i]->start_timer();
     }

@@ -29,6 +29,8 @@ EXPORTS = [
     "sblas_hip_allreduce_sum", "sblas_hip_merge_rowblocks", "sblas_partition_nnz_i64",
     "sblas_hip_debug_validate_csr_i32",
     "sblas_hip_spmm_plan_create", "sblas_hip_spmm_plan_destroy", "sblas_hip_spmm_plan_info", "sblas_hip_spmm_csr_f64_i32_planned",
+    "sblas_hip_spmv_plan_create", "sblas_hip_spmv_plan_destroy", "sblas_hip_spmv_plan_info", "sblas_hip_spmv_csr_f64_i32_planned",
+    "sblas_spmv_plan_classify",
 ]
 
 
@@ -72,6 +74,16 @@ def lib():
     L.sblas_hip_spmm_plan_info.argtypes = [vp, C.POINTER(i64)]
     L.sblas_hip_spmm_csr_f64_i32_planned.restype = C.c_int
     L.sblas_hip_spmm_csr_f64_i32_planned.argtypes = [vp, C.c_int, vp, i64, i64, i64, vp, vp, vp, vp, i64, i64, f64, f64, vp, i64, vp, sz]
+    L.sblas_hip_spmv_plan_create.restype = C.c_int
+    L.sblas_hip_spmv_plan_create.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, C.POINTER(vp)]
+    L.sblas_hip_spmv_plan_destroy.restype = C.c_int
+    L.sblas_hip_spmv_plan_destroy.argtypes = [vp]
+    L.sblas_hip_spmv_plan_info.restype = C.c_int
+    L.sblas_hip_spmv_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_spmv_csr_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_spmv_csr_f64_i32_planned.argtypes = [vp, C.c_int, vp, i64, i64, i64, vp, vp, vp, vp, f64, f64, vp]
+    L.sblas_spmv_plan_classify.restype = i64
+    L.sblas_spmv_plan_classify.argtypes = [vp, i64, i64, i64, i64, vp, i64]
     L.sblas_hip_dense_to_rowmajor_f64.restype = C.c_int
     L.sblas_hip_dense_to_rowmajor_f64.argtypes = [C.c_int, vp, i64, i64, vp, i64, vp, i64]
     L.sblas_hip_spmm_csr_rowmajorB_f64_i32.restype = C.c_int
@@ -174,6 +186,28 @@ def partition_nnz(rowptr, n_gpu, i_gpu):
     if num < 0:
         raise SblasError("sblas_partition_nnz failed (%d)" % num)
     return dict(start_row=s.value, stop_row=e.value, nnz=k.value, first_nnz=f.value, rowptr=buf[:num].copy())
+
+
+# kinds of the SpMV plan's work items (SBLAS_SPMV_ITEM_* in sblas_hip.h) and its default split parameters
+SPMV_ITEM_LPR, SPMV_ITEM_STREAM4096, SPMV_ITEM_STREAM6144, SPMV_ITEM_SEG = 0, 1, 2, 3
+SPMV_ITEM_LDS_S2, SPMV_ITEM_LDS_S3, SPMV_ITEM_LDS_S4, SPMV_ITEM_LDS_S7, SPMV_ITEM_SPLIT = 4, 5, 6, 7, 8
+SPMV_SPLIT_MIN, SPMV_SPLIT_PIECE = 12288, 4096
+
+
+def spmv_plan_classify(rowptr, nnz=None, split_min=0, piece=0):
+    """The SpMV plan's work items (sblas_spmv_plan_classify) as an (n, 4) int32 array of
+    (first row, row count, kind, pieces); nnz defaults to rowptr[-1]."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    rows = len(rowptr) - 1
+    nnz = int(rowptr[-1]) if nnz is None else int(nnz)
+    L = lib()
+    n = L.sblas_spmv_plan_classify(rowptr.ctypes.data, rows, nnz, split_min, piece, None, 0)
+    if n < 0:
+        raise SblasError("sblas_spmv_plan_classify refused the row pointers")
+    out = np.zeros((max(n, 1), 4), np.int32)
+    if L.sblas_spmv_plan_classify(rowptr.ctypes.data, rows, nnz, split_min, piece, out.ctypes.data, n) != n:
+        raise SblasError("sblas_spmv_plan_classify changed its answer")
+    return out[:n]
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -330,6 +364,53 @@ def spmv(rows, cols, rowptr, colidx, val, x, alpha, beta, y, stream=None, y_offs
         _dev_ptr(val, torch.float64, "val") if nnz else None,
         _dev_ptr(x, torch.float64, "x"), alpha, beta, _dev_ptr(y, torch.float64, "y") + 8 * y_offset)
     check(rc, "sblas_hip_spmv_csr_f64_i32")
+
+
+class SpmvPlan:
+    """A per-matrix SpMV plan (sblas_hip_spmv_plan_create): the work items of one structure (rowptr, colidx), taken once.
+    Keeps the structure tensors alive; destroy() / garbage collection frees the device buffer."""
+
+    def __init__(self, rows, cols, rowptr, colidx, stream=None):
+        import torch
+        self.rows, self.cols, self.rowptr, self.colidx = rows, cols, rowptr, colidx
+        self.nnz = int(colidx.numel())
+        self.handle = None
+        h = C.c_void_p()
+        check(lib().sblas_hip_spmv_plan_create(-1, _stream(stream), rows, cols, self.nnz, _dev_ptr(rowptr, torch.int32, "rowptr"),
+                                               _dev_ptr(colidx, torch.int32, "colidx") if self.nnz else None, C.byref(h)),
+              "sblas_hip_spmv_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        check(lib().sblas_hip_spmv_plan_info(self.handle, out), "sblas_hip_spmv_plan_info")
+        return dict(active=bool(out[0]), lanes=int(out[1]), stream4096=int(out[2]), stream6144=int(out[3]), segmented=int(out[4]),
+                    lds=int(out[5]), split_rows=int(out[6]), split_pieces=int(out[7]))
+
+    def spmv(self, val, x, alpha, beta, y, stream=None, y_offset=0, rows=None, nnz=None):
+        """The planned form of spmv(): y = alpha*A*x + beta*y.  rows / nnz override the plan's own (tests of the refusal)."""
+        import torch
+        rc = lib().sblas_hip_spmv_csr_f64_i32_planned(
+            self.handle, -1, _stream(stream), self.rows if rows is None else rows, self.cols,
+            self.nnz if nnz is None else nnz,
+            _dev_ptr(self.rowptr, torch.int32, "rowptr"), _dev_ptr(self.colidx, torch.int32, "colidx") if self.nnz else None,
+            _dev_ptr(val, torch.float64, "val") if self.nnz else None,
+            _dev_ptr(x, torch.float64, "x"), alpha, beta, _dev_ptr(y, torch.float64, "y") + 8 * y_offset)
+        return rc
+
+    def __call__(self, val, x, alpha, beta, y, stream=None, y_offset=0):
+        check(self.spmv(val, x, alpha, beta, y, stream, y_offset), "sblas_hip_spmv_csr_f64_i32_planned")
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_spmv_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
 
 
 def merge_rowblocks_local(M, N, starts, nrows, blocks, alpha, beta, Cmat, ldc=None, stream=None):

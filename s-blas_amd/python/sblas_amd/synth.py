@@ -219,3 +219,24 @@ def powerlaw(rows, avg=3.0, max_len=5000, alpha=2.25, seed=SEED, cols=None):
     # duplicates inside a row are legal CSR (the reference adds them up); leave them in
     val = rng.random(nnz) * 2.0 - 1.0
     return rowptr.astype(np.int32), colidx, val
+
+
+def mixed_banded(rows, short=7, long=150, half_band=2000, interleave=0, seed=SEED):
+    """A stencil part and a dense-coupling part in one matrix: rows // 2 banded rows of `short` nonzeros and the rest
+    of `long` (both over +-half_band, square).  interleave = 0: the short rows first, then the long ones; otherwise
+    the two kinds alternate in runs of `interleave` rows."""
+    n_short = rows // 2
+    rs, cs, vs = banded(rows, short, half_band, seed=seed)
+    rl, cl, vl = banded(rows, long, half_band, seed=seed + 1)
+    idx = np.arange(rows)
+    take_short = (idx < n_short) if not interleave else ((idx // interleave) % 2 == 0)
+    lens = np.where(take_short, np.diff(rs), np.diff(rl)).astype(np.int64)
+    rowptr = np.zeros(rows + 1, np.int64)
+    np.cumsum(lens, out=rowptr[1:])
+    # gather each row from the matrix it comes from
+    src_start = np.where(take_short, rs[:-1], rl[:-1]).astype(np.int64)
+    pos = np.repeat(src_start - rowptr[:-1], lens) + np.arange(int(rowptr[-1]))
+    from_short = np.repeat(take_short, lens)
+    colidx = np.where(from_short, cs[np.minimum(pos, len(cs) - 1)], cl[np.minimum(pos, len(cl) - 1)]).astype(np.int32)
+    val = np.where(from_short, vs[np.minimum(pos, len(vs) - 1)], vl[np.minimum(pos, len(vl) - 1)])
+    return rowptr.astype(np.int32), colidx, val
