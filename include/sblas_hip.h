@@ -232,6 +232,39 @@ int sblas_hip_allreduce_sum(void *comm, int vtype, void *const *bufs, void *cons
 int sblas_hip_merge_rowblocks(void *comm, int vtype, int64_t M, int64_t N, const int64_t *start_row,
                               const int64_t *num_rows, void *const *partial, void *const *gather, double alpha,
                               double beta, void *const *C, int64_t ldc, void *const *streams);
+
+/* ---------------------------------------------------------------------------------------
+ * Row-major dense operands.  The entry points above take B and C column-major; these take each of them in either
+ * order (order_b and order_c are independent; the calls above are the (COL, COL) case of these):
+ *   SBLAS_COL_MAJOR: B[k + j * ldb] (ldb >= cols), C[r + j * ldc] (ldc >= rows)
+ *   SBLAS_ROW_MAJOR: B[k * ldb + j] (ldb >= n),    C[r * ldc + j] (ldc >= n)   -- the layout of a contiguous torch
+ *                    tensor, cuSPARSE / rocSPARSE ORDER_ROW
+ * B's order reaches only the staging copy (a row-major B is copied row by row, no transpose), C's only the write-back
+ * of the stage-2 kernels.  The summation order is the same for every layout: the row-major result is the transpose of
+ * the column-major one bit for bit.  The workspace size (sblas_hip_spmm_csr_workspace, ..._f64_i32_workspace) and an
+ * SpMM plan (sblas_hip_spmm_plan_create) do not depend on either order: one of each serves all four combinations.
+ * <SBLAS_I32, SBLAS_F64> runs the tuned kernels (column chunking of wide B, range staging, plans and SBLAS_VALIDATE=1
+ * as in sblas_hip_spmm_csr_f64_i32), the other type pairs the typed kernels.  An order outside {0, 1}, a leading
+ * dimension below its minimum or a missing pointer returns SBLAS_E_INVALID before anything touches the device.
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_COL_MAJOR 0
+#define SBLAS_ROW_MAJOR 1
+int sblas_hip_spmm_csr_ordered(int dev, void *stream, int vtype, int itype, int64_t rows, int64_t cols, int64_t nnz,
+                               const void *rowptr, const void *colidx, const void *val,
+                               const void *B, int64_t ldb, int order_b, int64_t n, double alpha, double beta,
+                               void *C, int64_t ldc, int order_c, void *workspace, size_t workspace_bytes);
+int sblas_hip_spmm_csr_ordered_f64_i32_planned(const void *plan, int dev, void *stream, int64_t rows, int64_t cols,
+                                               int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                                               const double *val, const double *B, int64_t ldb, int order_b, int64_t n,
+                                               double alpha, double beta, double *C, int64_t ldc, int order_c,
+                                               void *workspace, size_t workspace_bytes);
+/* sblas_hip_merge_rowblocks with C in either order.  SBLAS_ROW_MAJOR: C[r] is row-major (ldc >= N) and so is every
+ * packed block: partial[q] is num_rows[q] x N at leading dimension N (contiguous, as in the column-major form), and so
+ * is its region of gather[r]; the RCCL send / recv moves the same bytes as for column-major C. */
+int sblas_hip_merge_rowblocks_ordered(void *comm, int vtype, int order, int64_t M, int64_t N, const int64_t *start_row,
+                                      const int64_t *num_rows, void *const *partial, void *const *gather, double alpha,
+                                      double beta, void *const *C, int64_t ldc, void *const *streams);
+
 /* sblas_partition_nnz (below) for 64-bit row pointers */
 int64_t sblas_partition_nnz_i64(const int64_t *rowptr, int64_t rows, int64_t nnz, int n_gpu, int i_gpu,
                                 int64_t *start_row, int64_t *stop_row, int64_t *nnz_i, int64_t *first_nnz,

@@ -42,6 +42,13 @@ inline int resolve_device(int dev)
     return cur;
 }
 
+// dense operand layouts (SBLAS_COL_MAJOR / SBLAS_ROW_MAJOR)
+inline bool order_ok(int order) { return order == SBLAS_COL_MAJOR || order == SBLAS_ROW_MAJOR; }
+// leading dimension of a dense operand with `rows` rows and n columns: column-major needs ld >= rows, row-major ld >= n
+inline bool ld_ok(int order, int64_t ld, int64_t rows, int64_t n) { return ld >= (order == SBLAS_ROW_MAJOR ? n : rows); }
+// column j0 of a dense operand
+template <typename T> inline T *col_at(T *p, int order, int64_t ld, int64_t j0) { return p + (order == SBLAS_ROW_MAJOR ? j0 : j0 * ld); }
+
 inline bool csr_args_ok(int64_t rows, int64_t cols, int64_t nnz, const void *rowptr, const void *colidx,
                         const void *val)
 {
@@ -147,38 +154,47 @@ size_t sblas_hip_spmm_csr_f64_i32_workspace(int64_t rows, int64_t cols, int64_t 
     return bt + sblas::workspace_tail_bytes(rows); // flags, one span and one class per row panel
 }
 
-int sblas_hip_dense_to_rowmajor_f64(int dev, void *stream, int64_t cols, int64_t n, const double *B,
-                                    int64_t ldb, double *Bt, int64_t ldbt)
+static int stage_full(int dev, void *stream, int64_t cols, int64_t n, const double *B, int64_t ldb, int order_b, double *Bt,
+                      int64_t ldbt)
 {
     if (cols < 0 || n < 0) return SBLAS_E_INVALID;
     if (cols == 0 || n == 0) return SBLAS_OK;
-    if (!B || !Bt || ldb < cols || ldbt < n || !ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
+    if (!B || !Bt || !ld_ok(order_b, ldb, cols, n) || ldbt < n || !ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
     DeviceScope scope(dev);
     if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    return sblas::launch_dense_to_rowmajor((hipStream_t)stream, cols, n, B, ldb, Bt, ldbt) == hipSuccess
+    return sblas::launch_dense_to_rowmajor((hipStream_t)stream, cols, n, B, ldb, Bt, ldbt, order_b == SBLAS_ROW_MAJOR) ==
+                   hipSuccess
                ? SBLAS_OK
                : SBLAS_E_HIP;
 }
 
+int sblas_hip_dense_to_rowmajor_f64(int dev, void *stream, int64_t cols, int64_t n, const double *B,
+                                    int64_t ldb, double *Bt, int64_t ldbt)
+{
+    return stage_full(dev, stream, cols, n, B, ldb, SBLAS_COL_MAJOR, Bt, ldbt);
+}
+
 // A has no nonzeros (cols == 0 or nnz == 0): C = beta * C, nothing else.  Neither the staging copy nor the panel
 // verdicts behind it are touched, so a NULL / empty workspace is fine here.
-static int scale_only(int dev, void *stream, int64_t rows, int64_t n, double beta, double *C, int64_t ldc)
+static int scale_only(int dev, void *stream, int64_t rows, int64_t n, double beta, double *C, int64_t ldc, int order_c)
 {
     if (beta == 1.0) return SBLAS_OK;
     DeviceScope scope(dev);
     if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    return sblas::launch_scale((hipStream_t)stream, rows, n, beta, C, ldc) == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+    return sblas::launch_scale((hipStream_t)stream, rows, n, beta, C, ldc, order_c == SBLAS_ROW_MAJOR) == hipSuccess
+               ? SBLAS_OK
+               : SBLAS_E_HIP;
 }
 
 static int spmm_staged(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
                        const int32_t *colidx, const double *val, const double *Bt, int64_t ldbt, int64_t n,
-                       double alpha, double beta, double *C, int64_t ldc, int pre_epoch)
+                       double alpha, double beta, double *C, int64_t ldc, int order_c, int pre_epoch)
 {
     if (!csr_args_ok(rows, cols, nnz, rowptr, colidx, val) || n < 0) return SBLAS_E_INVALID;
     if (rows == 0 || n == 0) return SBLAS_OK;
-    if (!C || ldc < rows || n > INT_MAX) return SBLAS_E_INVALID;
+    if (!C || !ld_ok(order_c, ldc, rows, n) || n > INT_MAX) return SBLAS_E_INVALID;
     if (!ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
-    if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc); // A*B = 0: no kernel reads Bt
+    if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc, order_c); // A*B = 0: no kernel reads Bt
     if (!Bt) return SBLAS_E_INVALID;
     // the kernels address Bt with 32-bit element offsets (row * ldbt + column)
     if (ldbt >= 64 && ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull) return SBLAS_E_INVALID; // 32-bit byte offsets
@@ -186,7 +202,8 @@ static int spmm_staged(int dev, void *stream, int64_t rows, int64_t cols, int64_
     if (scope.err != hipSuccess) return SBLAS_E_HIP;
     if ((reinterpret_cast<uintptr_t>(Bt) & 15u) != 0) return SBLAS_E_INVALID; // 16-byte tile loads
     return sblas::launch_spmm_rowpanel((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, val, Bt, ldbt,
-                                       (int)n, alpha, beta, C, ldc, spmm_variant(), pre_epoch) == hipSuccess
+                                       (int)n, alpha, beta, C, ldc, spmm_variant(), pre_epoch, nullptr,
+                                       order_c == SBLAS_ROW_MAJOR) == hipSuccess
                ? SBLAS_OK
                : SBLAS_E_HIP;
 }
@@ -196,7 +213,7 @@ int sblas_hip_spmm_csr_rowmajorB_f64_i32(int dev, void *stream, int64_t rows, in
                                          const double *Bt, int64_t ldbt, int64_t n, double alpha,
                                          double beta, double *C, int64_t ldc)
 {
-    return spmm_staged(dev, stream, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, 0);
+    return spmm_staged(dev, stream, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, SBLAS_COL_MAJOR, 0);
 }
 
 static int validate_if_asked(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
@@ -212,15 +229,20 @@ struct SpmmPlan {
     sblas::PlanView pv;
 };
 
+// The <f64, i32> SpMM of every entry point.  B and C each column- or row-major (order_b / order_c): B's layout reaches
+// only the staging launch, C's only the stage-2 epilogues; Bt, the workspace and the plan are the same for all four.
 static int spmm_impl(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
-                     const int32_t *colidx, const double *val, const double *B, int64_t ldb, int64_t n, double alpha,
-                     double beta, double *C, int64_t ldc, void *workspace, size_t workspace_bytes, const SpmmPlan *plan)
+                     const int32_t *colidx, const double *val, const double *B, int64_t ldb, int order_b, int64_t n,
+                     double alpha, double beta, double *C, int64_t ldc, int order_c, void *workspace,
+                     size_t workspace_bytes, const SpmmPlan *plan)
 {
+    if (!order_ok(order_b) || !order_ok(order_c)) return SBLAS_E_INVALID;
     if (!csr_args_ok(rows, cols, nnz, rowptr, colidx, val) || n < 0) return SBLAS_E_INVALID;
     if (rows == 0 || n == 0) return SBLAS_OK;
-    if (!C || ldc < rows) return SBLAS_E_INVALID;
-    if (cols > 0 && (!B || ldb < cols)) return SBLAS_E_INVALID;
-    if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc);
+    if (!C || !ld_ok(order_c, ldc, rows, n)) return SBLAS_E_INVALID;
+    if (cols > 0 && (!B || !ld_ok(order_b, ldb, cols, n))) return SBLAS_E_INVALID;
+    const bool row_b = order_b == SBLAS_ROW_MAJOR, row_c = order_c == SBLAS_ROW_MAJOR;
+    if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc, order_c);
     if (const int vrc = validate_if_asked(dev, stream, rows, cols, nnz, rowptr, colidx)) return vrc;
     const size_t need = sblas_hip_spmm_csr_f64_i32_workspace(rows, cols, nnz, n);
     if (need > 0 && (!workspace || workspace_bytes < need)) return SBLAS_E_WORKSPACE;
@@ -242,10 +264,12 @@ static int spmm_impl(int dev, void *stream, int64_t rows, int64_t cols, int64_t 
             DeviceScope scope(dev);
             if (scope.err != hipSuccess) return SBLAS_E_HIP;
             if ((reinterpret_cast<uintptr_t>(Bt) & 15u) != 0) return SBLAS_E_INVALID;
-            if (sblas::launch_stage_planned((hipStream_t)stream, cols, nj, B + j0 * ldb, ldb, Bt, ldbt, plan->pv) != hipSuccess)
+            if (sblas::launch_stage_planned((hipStream_t)stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, Bt, ldbt, plan->pv,
+                                            row_b) != hipSuccess)
                 return SBLAS_E_HIP;
             if (sblas::launch_spmm_rowpanel((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, val, Bt, ldbt, (int)nj,
-                                            alpha, beta, C + j0 * ldc, ldc, spmm_variant(), 0, &plan->pv) != hipSuccess)
+                                            alpha, beta, col_at(C, order_c, ldc, j0), ldc, spmm_variant(), 0, &plan->pv,
+                                            row_c) != hipSuccess)
                 return SBLAS_E_HIP;
             continue;
         }
@@ -258,8 +282,8 @@ static int spmm_impl(int dev, void *stream, int64_t rows, int64_t cols, int64_t 
                                      spmm_variant() == sblas::SPMM_VARIANT_DIRECT_MERGE ||
                                      !sblas::classify_worthwhile(rows, nnz, ldbt);
             pre_epoch = (!direct_only && ldbt == range_ldbt) ? range_epoch : 0;
-            if (sblas::launch_stage_range((hipStream_t)stream, cols, nj, B + j0 * ldb, ldb, Bt, ldbt, (int)rows, nnz,
-                                          rowptr, colidx, spmm_variant(), direct_only ? 0 : 1, &pre_epoch) != hipSuccess)
+            if (sblas::launch_stage_range((hipStream_t)stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, Bt, ldbt, (int)rows,
+                                          nnz, rowptr, colidx, spmm_variant(), direct_only ? 0 : 1, &pre_epoch, row_b) != hipSuccess)
                 return SBLAS_E_HIP;
             range_epoch = pre_epoch;
             range_ldbt = ldbt;
@@ -268,19 +292,19 @@ static int spmm_impl(int dev, void *stream, int64_t rows, int64_t cols, int64_t 
             sblas::classify_worthwhile(rows, nnz, ldbt) &&
             (ldbt >= 64 || (spmm_variant() != sblas::SPMM_VARIANT_DIRECT_MERGE &&
                             ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull <= 0xffffffffull)) &&
-            cols > 0 && nnz > 0 && ldb >= cols && ldbt_ok(ldbt, nj)) {
+            cols > 0 && nnz > 0 && ld_ok(order_b, ldb, cols, n) && ldbt_ok(ldbt, nj)) {
             // default path: the panel classifier rides in the staging launch (one launch and one gap less per call)
             DeviceScope scope(dev);
             if (scope.err != hipSuccess) return SBLAS_E_HIP;
-            if (sblas::launch_stage_classify((hipStream_t)stream, cols, nj, B + j0 * ldb, ldb, Bt, ldbt, (int)rows, rowptr,
-                                             colidx, spmm_variant(), &pre_epoch) != hipSuccess)
+            if (sblas::launch_stage_classify((hipStream_t)stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, Bt, ldbt, (int)rows,
+                                             rowptr, colidx, spmm_variant(), &pre_epoch, row_b) != hipSuccess)
                 return SBLAS_E_HIP;
         } else {
-            rc = sblas_hip_dense_to_rowmajor_f64(dev, stream, cols, nj, B + j0 * ldb, ldb, Bt, ldbt);
+            rc = stage_full(dev, stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, order_b, Bt, ldbt);
             if (rc != SBLAS_OK) return rc;
         }
-        rc = spmm_staged(dev, stream, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, nj, alpha, beta, C + j0 * ldc, ldc,
-                         pre_epoch);
+        rc = spmm_staged(dev, stream, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, nj, alpha, beta,
+                         col_at(C, order_c, ldc, j0), ldc, order_c, pre_epoch);
         if (rc != SBLAS_OK) return rc;
     }
     return SBLAS_OK;
@@ -291,8 +315,8 @@ int sblas_hip_spmm_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t cols
                                const double *B, int64_t ldb, int64_t n, double alpha, double beta,
                                double *C, int64_t ldc, void *workspace, size_t workspace_bytes)
 {
-    return spmm_impl(dev, stream, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, workspace,
-                     workspace_bytes, nullptr);
+    return spmm_impl(dev, stream, rows, cols, nnz, rowptr, colidx, val, B, ldb, SBLAS_COL_MAJOR, n, alpha, beta, C, ldc,
+                     SBLAS_COL_MAJOR, workspace, workspace_bytes, nullptr);
 }
 
 // ---- per-matrix plan (the slot of cusparseSpMM_bufferSize / preprocess, spmm.h:134-141) --------------------------
@@ -353,13 +377,25 @@ int sblas_hip_spmm_csr_f64_i32_planned(const void *plan, int dev, void *stream, 
                                        int64_t ldb, int64_t n, double alpha, double beta, double *C, int64_t ldc,
                                        void *workspace, size_t workspace_bytes)
 {
-    if (!plan) return SBLAS_E_INVALID;
+    return sblas_hip_spmm_csr_ordered_f64_i32_planned(plan, dev, stream, rows, cols, nnz, rowptr, colidx, val, B, ldb,
+                                                      SBLAS_COL_MAJOR, n, alpha, beta, C, ldc, SBLAS_COL_MAJOR, workspace,
+                                                      workspace_bytes);
+}
+
+int sblas_hip_spmm_csr_ordered_f64_i32_planned(const void *plan, int dev, void *stream, int64_t rows, int64_t cols,
+                                               int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                               const double *B, int64_t ldb, int order_b, int64_t n, double alpha,
+                                               double beta, double *C, int64_t ldc, int order_c, void *workspace,
+                                               size_t workspace_bytes)
+{
+    if (!plan || !order_ok(order_b) || !order_ok(order_c)) return SBLAS_E_INVALID;
     const SpmmPlan *p = static_cast<const SpmmPlan *>(plan);
     // the plan speaks for ONE structure: the same arrays it was made from (their contents are the caller's promise)
     // ... on the device its verdicts live on
     if (p->dev != resolve_device(dev) || p->rows != rows || p->cols != cols || p->nnz != nnz || p->rowptr != rowptr || p->colidx != colidx)
         return SBLAS_E_INVALID;
-    return spmm_impl(dev, stream, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, workspace, workspace_bytes, p);
+    return spmm_impl(dev, stream, rows, cols, nnz, rowptr, colidx, val, B, ldb, order_b, n, alpha, beta, C, ldc, order_c,
+                     workspace, workspace_bytes, p);
 }
 
 int sblas_hip_debug_validate_csr_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
@@ -614,23 +650,32 @@ int sblas_hip_spmm_csr(int dev, void *stream, int vtype, int itype, int64_t rows
                        const void *rowptr, const void *colidx, const void *val, const void *B, int64_t ldb, int64_t n,
                        double alpha, double beta, void *C, int64_t ldc, void *workspace, size_t workspace_bytes)
 {
-    if (!types_ok(vtype, itype)) return SBLAS_E_INVALID;
+    return sblas_hip_spmm_csr_ordered(dev, stream, vtype, itype, rows, cols, nnz, rowptr, colidx, val, B, ldb,
+                                      SBLAS_COL_MAJOR, n, alpha, beta, C, ldc, SBLAS_COL_MAJOR, workspace, workspace_bytes);
+}
+
+int sblas_hip_spmm_csr_ordered(int dev, void *stream, int vtype, int itype, int64_t rows, int64_t cols, int64_t nnz,
+                               const void *rowptr, const void *colidx, const void *val, const void *B, int64_t ldb,
+                               int order_b, int64_t n, double alpha, double beta, void *C, int64_t ldc, int order_c,
+                               void *workspace, size_t workspace_bytes)
+{
+    if (!types_ok(vtype, itype) || !order_ok(order_b) || !order_ok(order_c)) return SBLAS_E_INVALID;
     if (vtype == SBLAS_F64 && itype == SBLAS_I32)
-        return sblas_hip_spmm_csr_f64_i32(dev, stream, rows, cols, nnz, static_cast<const int32_t *>(rowptr),
-                                          static_cast<const int32_t *>(colidx), static_cast<const double *>(val),
-                                          static_cast<const double *>(B), ldb, n, alpha, beta, static_cast<double *>(C),
-                                          ldc, workspace, workspace_bytes);
+        return spmm_impl(dev, stream, rows, cols, nnz, static_cast<const int32_t *>(rowptr),
+                         static_cast<const int32_t *>(colidx), static_cast<const double *>(val),
+                         static_cast<const double *>(B), ldb, order_b, n, alpha, beta, static_cast<double *>(C), ldc,
+                         order_c, workspace, workspace_bytes, nullptr);
     if (rows < 0 || cols < 0 || nnz < 0 || n < 0 || !rowptr || (nnz > 0 && (!colidx || !val))) return SBLAS_E_INVALID;
     if (itype == SBLAS_I32 && (rows > INT_MAX - 64 || cols > INT_MAX || nnz > INT_MAX)) return SBLAS_E_INVALID;
     if (rows == 0 || n == 0) return SBLAS_OK;
-    if (!C || ldc < rows) return SBLAS_E_INVALID;
-    if (cols > 0 && (!B || ldb < cols)) return SBLAS_E_INVALID;
+    if (!C || !ld_ok(order_c, ldc, rows, n)) return SBLAS_E_INVALID;
+    if (cols > 0 && (!B || !ld_ok(order_b, ldb, cols, n))) return SBLAS_E_INVALID;
     const size_t need = (cols == 0 || nnz == 0) ? 0 : sblas::typed_spmm_workspace(vtype, cols, n);
     if (need > 0 && (!workspace || workspace_bytes < need)) return SBLAS_E_WORKSPACE;
     DeviceScope scope(dev);
     if (scope.err != hipSuccess) return SBLAS_E_HIP;
     return sblas::launch_typed_spmm((hipStream_t)stream, vtype, itype, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha,
-                                    beta, C, ldc, workspace) == hipSuccess
+                                    beta, C, ldc, workspace, order_b == SBLAS_ROW_MAJOR, order_c == SBLAS_ROW_MAJOR) == hipSuccess
                ? SBLAS_OK
                : SBLAS_E_HIP;
 }

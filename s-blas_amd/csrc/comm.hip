@@ -210,7 +210,7 @@ extern "C" int sblas_hip_merge_rowblocks_local_f64(int device, void *stream, int
         if (num_rows[q] > 0 && !src[q]) return SBLAS_E_INVALID;
     }
     if (device >= 0 && hipSetDevice(device) != hipSuccess) return SBLAS_E_HIP;
-    return sblas::launch_merge_rowblocks((hipStream_t)stream, M, N, g, src, start_row, num_rows, alpha, beta, C, ldc) ==
+    return sblas::launch_merge_rowblocks((hipStream_t)stream, M, N, g, src, start_row, num_rows, alpha, beta, C, ldc, false) ==
                    hipSuccess
                ? SBLAS_OK
                : SBLAS_E_HIP;
@@ -220,10 +220,23 @@ extern "C" int sblas_hip_merge_rowblocks(void *comm, int vtype, int64_t M, int64
                                          const int64_t *num_rows, void *const *partial, void *const *gather, double alpha,
                                          double beta, void *const *C, int64_t ldc, void *const *streams)
 {
+    return sblas_hip_merge_rowblocks_ordered(comm, vtype, SBLAS_COL_MAJOR, M, N, start_row, num_rows, partial, gather, alpha,
+                                             beta, C, ldc, streams);
+}
+
+// order = SBLAS_ROW_MAJOR: C is row-major (ldc >= N) and so is every packed block (num_rows[q] x N at leading dimension N,
+// contiguous like the column-major form): the exchange moves the same bytes, only the merge kernel indexes differently
+extern "C" int sblas_hip_merge_rowblocks_ordered(void *comm, int vtype, int order, int64_t M, int64_t N,
+                                                 const int64_t *start_row, const int64_t *num_rows, void *const *partial,
+                                                 void *const *gather, double alpha, double beta, void *const *C, int64_t ldc,
+                                                 void *const *streams)
+{
     if (vtype != SBLAS_F64 && vtype != SBLAS_F32) return SBLAS_E_INVALID;
+    if (order != SBLAS_COL_MAJOR && order != SBLAS_ROW_MAJOR) return SBLAS_E_INVALID;
+    const bool row_c = order == SBLAS_ROW_MAJOR;
     const size_t esz = vtype == SBLAS_F32 ? 4 : 8;
     const int rccl_type = vtype == SBLAS_F32 ? RCCL_FLOAT32 : RCCL_FLOAT64;
-    if (!comm || !start_row || !num_rows || !partial || !C || M < 0 || N < 0 || ldc < M) return SBLAS_E_INVALID;
+    if (!comm || !start_row || !num_rows || !partial || !C || M < 0 || N < 0 || ldc < (row_c ? N : M)) return SBLAS_E_INVALID;
     if (M == 0 || N == 0) return SBLAS_OK;
     CommSet &s = *static_cast<CommSet *>(comm);
     const int g = (int)s.devs.size();
@@ -277,8 +290,9 @@ extern "C" int sblas_hip_merge_rowblocks(void *comm, int vtype, int64_t M, int64
         const hipError_t e =
             vtype == SBLAS_F64
                 ? sblas::launch_merge_rowblocks(si, M, N, g, reinterpret_cast<const double *const *>(src), start_row, num_rows,
-                                                alpha, beta, static_cast<double *>(C[i]), ldc)
-                : sblas::launch_typed_merge_rowblocks(si, vtype, M, N, g, src, start_row, num_rows, alpha, beta, C[i], ldc);
+                                                alpha, beta, static_cast<double *>(C[i]), ldc, row_c)
+                : sblas::launch_typed_merge_rowblocks(si, vtype, M, N, g, src, start_row, num_rows, alpha, beta, C[i], ldc,
+                                                      row_c);
         if (e != hipSuccess) rc = SBLAS_E_HIP;
     }
     (void)hipSetDevice(prev);

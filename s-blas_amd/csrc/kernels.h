@@ -45,7 +45,29 @@ unsigned long long *panel_stats_device();
 hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
                             const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
                             const int2 *info, const int *tail, const int *cls, int panel_rows, int npanels, int epoch,
-                            unsigned long long *stats);
+                            unsigned long long *stats, bool row_c);
+
+// The epilogue of the stage-2 kernels for a ROW-MAJOR C (element (r, j) at C[r * ldc + j]).  Every such kernel parks its
+// panel of results in LDS and writes it back with alpha / beta applied; column-major C is walked with the row index
+// fastest (each kernel's own loop), row-major C here with the column index fastest, so the up-to-W outputs of one panel
+// row are one contiguous run of C.  at(r, j) reads the parked sum of panel row r, column j; keep(r) says whether the
+// kernel owns row r.  C addresses are 64-bit.  The summation order is not touched: a row-major result is the transpose of
+// the column-major one bit for bit.
+__device__ __forceinline__ double c_fma(double a, double b, double c) { return fma(a, b, c); }
+__device__ __forceinline__ float c_fma(float a, float b, float c) { return fmaf(a, b, c); }
+template <int W, typename T, typename At, typename Keep>
+__device__ __forceinline__ void store_rows_c(T *__restrict__ C, int64_t ldc, int64_t row0, int64_t col0, int prows, int nrows,
+                                             int ncols, int nthreads, T alpha, T beta, At at, Keep keep)
+{
+    for (int idx = threadIdx.x; idx < W * prows; idx += nthreads) {
+        const int j = idx % W, r = idx / W;
+        if (r < nrows && j < ncols && keep(r)) {
+            T *dst = C + (row0 + r) * ldc + (col0 + j);
+            const T sres = alpha * at(r, j);
+            *dst = (beta == T(0)) ? sres : c_fma(beta, *dst, sres);
+        }
+    }
+}
 
 // Experiment / test switches, read from the environment once (kernels.hip); options_reload() re-reads them.
 struct Options {
@@ -85,21 +107,23 @@ size_t plan_tail_bytes(int64_t rows);
 bool classify_worthwhile(int64_t rows, int64_t nnz, int64_t ldbt);
 hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx, int64_t ldbt,
                       int variant, bool use_range, PlanView *pv);
+// Layouts of the dense operands: row_b = B is row-major (cols x n, B[k * ldb + j]; only the staging launchers read B),
+// row_c = C is row-major (rows x n, C[r * ldc + j]; the stage-2 epilogues, the scale and the merge kernels).
 hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                                int64_t ldbt, const PlanView &pv);
+                                int64_t ldbt, const PlanView &pv, bool row_b);
 hipError_t launch_stage_range(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
                               int64_t ldbt, int rows, int64_t nnz, const int *rowptr, const int *colidx, int variant,
-                              int classify, int *epoch_out);
+                              int classify, int *epoch_out, bool row_b);
 hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb,
-                                    double *Bt, int64_t ldbt);
+                                    double *Bt, int64_t ldbt, bool row_b);
 hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
                                 const double *val, const double *Bt, int64_t ldbt, int n, double alpha,
-                                double beta, double *C, int64_t ldc, int variant, int pre_epoch = 0,
-                                const PlanView *pv = nullptr);
+                                double beta, double *C, int64_t ldc, int variant, int pre_epoch, const PlanView *pv,
+                                bool row_c);
 hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
                                  int64_t ldbt, int rows, const int *rowptr, const int *colidx, int variant,
-                                 int *epoch_out);
-hipError_t launch_scale(hipStream_t s, int64_t rows, int64_t n, double beta, double *C, int64_t ldc);
+                                 int *epoch_out, bool row_b);
+hipError_t launch_scale(hipStream_t s, int64_t rows, int64_t n, double beta, double *C, int64_t ldc, bool row_c);
 hipError_t validate_csr(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, const int *rowptr, const int *colidx, int *bad);
 hipError_t panel_stats(unsigned long long out[4], bool reset);
 hipError_t launch_spmv(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
@@ -126,7 +150,7 @@ void kernel_events_enable(bool on);
 hipError_t kernel_events_last_ms(float *ms);
 hipError_t launch_merge_rowblocks(hipStream_t s, int64_t M, int64_t N, int g, const double *const *src,
                                   const int64_t *start, const int64_t *nrows, double alpha, double beta, double *C,
-                                  int64_t ldc);
+                                  int64_t ldc, bool row_c);
 
 // typed_kernels.hip: the value / index types besides <int32, fp64> (reference utility.h:302-316)
 enum { VT_F64 = 0, VT_F32 = 1 };
@@ -135,13 +159,13 @@ int64_t typed_spmm_ldbt(int64_t n);
 size_t typed_spmm_workspace(int vt, int64_t cols, int64_t n);
 hipError_t launch_typed_spmm(hipStream_t s, int vt, int it, int64_t rows, int64_t cols, int64_t nnz, const void *rowptr,
                              const void *colidx, const void *val, const void *B, int64_t ldb, int64_t n, double alpha,
-                             double beta, void *C, int64_t ldc, void *ws);
+                             double beta, void *C, int64_t ldc, void *ws, bool row_b, bool row_c);
 hipError_t launch_typed_spmv(hipStream_t s, int vt, int it, int64_t rows, const void *rowptr, const void *colidx,
                              const void *val, const void *x, double alpha, double beta, void *y);
 hipError_t launch_typed_axpby(hipStream_t s, int vt, int64_t n, double alpha, const void *x, double beta, void *y);
 hipError_t launch_typed_sum_replicas(hipStream_t s, int vt, void *const *bufs, int g, int64_t n);
 hipError_t launch_typed_merge_rowblocks(hipStream_t s, int vt, int64_t M, int64_t N, int g, const void *const *src,
                                         const int64_t *start_row, const int64_t *num_rows, double alpha, double beta,
-                                        void *C, int64_t ldc);
+                                        void *C, int64_t ldc, bool row_c);
 
 } // namespace sblas

@@ -61,10 +61,35 @@ constexpr int STAGE_K = 32;
 // (every writer stores the same value), and tail[TAIL_STAGE_EPOCH] = stage_epoch always -- the two agree exactly when
 // the staging copy the stage-2 kernels are about to read holds an Inf or NaN (the MFMA kernel then leaves its panels
 // to the vector kernels: 0 * Inf from a block's zero fill would reach rows that never refer to that row of B).
+// RB: B is row-major (B[k * ldb + j], ldb >= n): row k of Bt is row k of B, so the tile is a strided row copy that goes
+// straight from B to Bt (reads and writes both along j), without the LDS transpose.  Same output, same stamps.
+template <bool RB>
 __device__ __forceinline__ void stage_tile(double (*tile)[STAGE_K + 1], int64_t k0, int64_t j0, int64_t cols, int64_t n,
                                            const double *__restrict__ B, int64_t ldb, double *__restrict__ Bt,
                                            int64_t ldbt, int *__restrict__ tail, int stage_epoch)
 {
+    if constexpr (RB) {
+        const int jl = threadIdx.x & 63, kq = threadIdx.x >> 6;
+        const int64_t j = j0 + jl;
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t kr = k0 + kq + 4 * u;
+            v[u] = (j < n && kr < cols) ? B[kr * ldb + j] : 0.0;
+        }
+        bool odd = false;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) odd |= (__double2hiint(v[u]) & 0x7ff00000) == 0x7ff00000;
+        if (__builtin_amdgcn_ballot_w64(odd) != 0ull && (threadIdx.x & 63) == 0) tail[TAIL_NONFINITE] = stage_epoch;
+        if (k0 == 0 && j0 == 0 && threadIdx.x == 0) tail[TAIL_STAGE_EPOCH] = stage_epoch;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t kr = k0 + kq + 4 * u;
+            if (kr < cols && j < ldbt) Bt[kr * ldbt + j] = v[u];
+            if (kr == cols && j < ldbt) Bt[kr * ldbt + j] = 0.0; // the all-zero row
+        }
+        return;
+    }
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     // all eight loads of a thread in flight before the first LDS store (the kernel is latency-bound otherwise)
     double v[8];
@@ -92,21 +117,22 @@ __device__ __forceinline__ void stage_tile(double (*tile)[STAGE_K + 1], int64_t 
         if (kr == cols && j < ldbt) Bt[kr * ldbt + j] = 0.0; // the all-zero row masked DPP slots point at
     }
 }
+template <bool RB>
 __global__ __launch_bounds__(256) void dense_to_rowmajor_kernel(int64_t cols, int64_t n,
                                                                const double *__restrict__ B, int64_t ldb,
                                                                double *__restrict__ Bt, int64_t ldbt,
                                                                int *__restrict__ tail, int stage_epoch)
 {
     __shared__ double tile[64][STAGE_K + 1];
-    stage_tile(tile, (int64_t)blockIdx.x * STAGE_K, (int64_t)blockIdx.y * 64, cols, n, B, ldb, Bt, ldbt, tail,
-               stage_epoch);
+    stage_tile<RB>(tile, (int64_t)blockIdx.x * STAGE_K, (int64_t)blockIdx.y * 64, cols, n, B, ldb, Bt, ldbt, tail,
+                   stage_epoch);
 }
 
 // Stage 1 for narrow blocks (ldbt = NC in {8, 16, 32}): a thread per row of Bt.  The reads of a wave run along k
 // (512 contiguous bytes per column of B), every thread writes its NC * 8 contiguous bytes of Bt, a wave 64 such rows
 // in a row.  (The 32 x 64 tile transposer above spends the time of a 64-column block on any narrower one: 16 us on the
-// bench shape against 2-3 us here.)
-template <int NC>
+// bench shape against 2-3 us here.)  RB: B row-major -- a thread reads its row's n contiguous values.
+template <int NC, bool RB>
 __device__ __forceinline__ void stage_rows_narrow(int64_t k0, int64_t cols, int64_t n, const double *__restrict__ B,
                                                   int64_t ldb, double *__restrict__ Bt, int *__restrict__ tail,
                                                   int stage_epoch)
@@ -114,7 +140,10 @@ __device__ __forceinline__ void stage_rows_narrow(int64_t k0, int64_t cols, int6
     const int64_t k = k0 + threadIdx.x;
     double v[NC];
 #pragma unroll
-    for (int j = 0; j < NC; ++j) v[j] = (j < n && k < cols) ? B[k + (int64_t)j * ldb] : 0.0;
+    for (int j = 0; j < NC; ++j) {
+        if constexpr (RB) v[j] = (j < n && k < cols) ? B[k * ldb + j] : 0.0;
+        else v[j] = (j < n && k < cols) ? B[k + (int64_t)j * ldb] : 0.0;
+    }
     bool odd = false;
 #pragma unroll
     for (int j = 0; j < NC; ++j) odd |= (__double2hiint(v[j]) & 0x7ff00000) == 0x7ff00000;
@@ -126,13 +155,13 @@ __device__ __forceinline__ void stage_rows_narrow(int64_t k0, int64_t cols, int6
         for (int j = 0; j < NC / 2; ++j) dst[j] = make_double2(v[2 * j], v[2 * j + 1]);
     }
 }
-template <int NC>
+template <int NC, bool RB>
 __global__ __launch_bounds__(256) void dense_to_rowmajor_narrow_kernel(int64_t cols, int64_t n,
                                                                       const double *__restrict__ B, int64_t ldb,
                                                                       double *__restrict__ Bt,
                                                                       int *__restrict__ tail, int stage_epoch)
 {
-    stage_rows_narrow<NC>((int64_t)blockIdx.x * 256, cols, n, B, ldb, Bt, tail, stage_epoch);
+    stage_rows_narrow<NC, RB>((int64_t)blockIdx.x * 256, cols, n, B, ldb, Bt, tail, stage_epoch);
 }
 
 // Stage 1 of a ROW BLOCK (method 2: rows << cols).  A block of a banded matrix refers to a narrow range of columns,
@@ -178,6 +207,7 @@ __global__ __launch_bounds__(256) void colrange_kernel(int64_t nnz, const int *_
     __shared__ int2 red[4];
     colrange_part(nnz, colidx, part, (int)blockIdx.x, (int)gridDim.x, red);
 }
+template <bool RB>
 __global__ __launch_bounds__(256) void stage_range_kernel(int64_t cols, int64_t n, const double *__restrict__ B,
                                                           int64_t ldb, double *__restrict__ Bt, int64_t ldbt,
                                                           int *__restrict__ tail, const int2 *__restrict__ part,
@@ -216,7 +246,7 @@ __global__ __launch_bounds__(256) void stage_range_kernel(int64_t cols, int64_t 
         int kt = kt0 + (int)(t / ny);
         if (kt > kt1) kt = kz;
         // stage_tile's own epoch store fires for tile (0, 0) only; it writes the same value
-        stage_tile(tile, (int64_t)kt * STAGE_K, (int64_t)ky * 64, cols, n, B, ldb, Bt, ldbt, tail, stage_epoch);
+        stage_tile<RB>(tile, (int64_t)kt * STAGE_K, (int64_t)ky * 64, cols, n, B, ldb, Bt, ldbt, tail, stage_epoch);
         __syncthreads();
     }
 }
@@ -522,6 +552,7 @@ __global__ __launch_bounds__(256) void classify_panels_kernel(int rows, int cols
 // Stage 1 and the panel classifier in one launch (the fused C-ABI entry: both depend only on the call's inputs, and
 // the classifier's dependent loads hide behind the staging traffic): the first ceil(npanels / 4) workgroups
 // (grid.y == 0 only) classify four panels each, the stage_blocks x grid.y behind them transpose B.
+template <bool RB>
 __global__ __launch_bounds__(256) void stage_classify_kernel(int64_t cols, int64_t n, const double *__restrict__ B,
                                                             int64_t ldb, double *__restrict__ Bt, int64_t ldbt,
                                                             int stage_blocks, int rows, int npanels, int panel_rows,
@@ -538,8 +569,8 @@ __global__ __launch_bounds__(256) void stage_classify_kernel(int64_t cols, int64
     // under the staging traffic (placed last they stuck out by ~3 us)
     const int cblocks = (npanels + 3) / 4;
     if ((int)blockIdx.x >= cblocks) {
-        stage_tile(tile, (int64_t)((int)blockIdx.x - cblocks) * STAGE_K, (int64_t)blockIdx.y * 64, cols, n, B, ldb, Bt,
-                   ldbt, tail, epoch);
+        stage_tile<RB>(tile, (int64_t)((int)blockIdx.x - cblocks) * STAGE_K, (int64_t)blockIdx.y * 64, cols, n, B, ldb, Bt,
+                       ldbt, tail, epoch);
     } else if (blockIdx.y == 0) {
         classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, (int)cols, npanels, panel_rows, rowptr, colidx,
                        max_row_len, min_density, min_rowlen, mfma_min_fill, merge_probe, tail, info, cls, epoch,
@@ -566,7 +597,7 @@ __global__ __launch_bounds__(256) void colrange_classify_kernel(int64_t nnz, int
                        bitmaps + (threadIdx.x >> 6) * MFMA_BITMAP_WORDS);
 }
 // ... and for narrow blocks (no matrix cores, no row-merging probe there)
-template <int NC>
+template <int NC, bool RB>
 __global__ __launch_bounds__(256) void stage_classify_narrow_kernel(int64_t cols, int64_t n, const double *__restrict__ B,
                                                                    int64_t ldb, double *__restrict__ Bt, int rows,
                                                                    int npanels, int panel_rows,
@@ -578,7 +609,7 @@ __global__ __launch_bounds__(256) void stage_classify_narrow_kernel(int64_t cols
 {
     const int cblocks = (npanels + 3) / 4;
     if ((int)blockIdx.x >= cblocks)
-        stage_rows_narrow<NC>((int64_t)((int)blockIdx.x - cblocks) * 256, cols, n, B, ldb, Bt, tail, epoch);
+        stage_rows_narrow<NC, RB>((int64_t)((int)blockIdx.x - cblocks) * 256, cols, n, B, ldb, Bt, tail, epoch);
     else
         classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, (int)cols, npanels, panel_rows, rowptr, colidx,
                        max_row_len, min_density, min_rowlen, 2.0f, 0, tail, info, cls, epoch, nullptr);
@@ -844,7 +875,7 @@ template <int N> __device__ __forceinline__ void vm_wait6()
 // wait, the two selections, the counting, the order check, the cursor update and the next window fetch are paid once per
 // (rows, tile) visit instead of once per 64 columns (with grid.y = ldbt / 64 every 64-column slice re-streams A's windows
 // and redoes all of it: N = 128 cost exactly twice N = 64).
-template <int G, int NH>
+template <int G, int NH, bool RC>
 __global__ __launch_bounds__(1024) void spmm_window6_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
@@ -1113,6 +1144,10 @@ __global__ __launch_bounds__(1024) void spmm_window6_kernel(
         const int ncols = min(64, n - colh);
         // (fetching the old C values in the prologue, to take their HBM latency out of the epilogue, did not pay: the
         //  registers they hold across the tile loop spill)
+        if constexpr (RC)
+            store_rows_c<64>(C, ldc, row0, colh, panel_rows, nrows, ncols, 1024, alpha, beta,
+                             [&](int r, int j) { return ctile[j * (RMAX + 1) + r]; }, [](int) { return true; });
+        else
         for (int idx = tid; idx < 64 * panel_rows; idx += 1024) {
             const int r = idx % panel_rows, j = idx / panel_rows;
             if (r < nrows && j < ncols) {
@@ -1265,7 +1300,7 @@ __device__ __noinline__ double row_direct_narrow(const int *__restrict__ colidx,
 // and window round trips: 48-row panels this way 0.117-0.118 ms per step against 0.124 with one workgroup of 144-row
 // panels per CU (and 0.134 with one workgroup of 48-row panels).  At 16 columns (two lanes per entry, spills at 64
 // registers) the same bought 1 %: not kept.
-template <int NC, int CP, int G, int LPE>
+template <int NC, int CP, int G, int LPE, bool RC>
 __global__ __launch_bounds__(1024, (NC == 8 && CP == 1 && G == 1) ? 8 : 4) void spmm_lanes_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int n, double alpha, double beta,
@@ -1472,6 +1507,10 @@ __global__ __launch_bounds__(1024, (NC == 8 && CP == 1 && G == 1) ? 8 : 4) void 
     __syncthreads(); // F
     const int nrows = min(panel_rows, rows - row0);
     const int ncols = min(NC, n);
+    if constexpr (RC)
+        store_rows_c<NC>(C, ldc, row0, 0, panel_rows, nrows, ncols, 1024, alpha, beta,
+                         [&](int r, int j) { return ctile[j * (RMAX + 1) + r]; }, [](int) { return true; });
+    else
     for (int idx = tid; idx < NC * panel_rows; idx += 1024) {
         const int r = idx % panel_rows, j = idx / panel_rows;
         if (r < nrows && j < ncols) {
@@ -1522,7 +1561,7 @@ __global__ __launch_bounds__(1024, (NC == 8 && CP == 1 && G == 1) ? 8 : 4) void 
 
 // GROUPS = 1: 128-column tile, one nonzero per instruction; 2: 64 columns, two nonzeros; 4: 32 columns, four (one per
 // DPP row) -- n <= 32 runs on the 64-column staging copy and reads the first half of every Bt row
-template <int GROUPS>
+template <int GROUPS, bool RC>
 __global__ __launch_bounds__(WIDE_WAVES * 64) void spmm_direct_dpp_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
@@ -1688,6 +1727,10 @@ __global__ __launch_bounds__(WIDE_WAVES * 64) void spmm_direct_dpp_kernel(
     }
     const int nrows = min(WIDE_PANEL, rows - row0);
     const int ncols = min(TILE_COLS, n - col0);
+    if constexpr (RC)
+        store_rows_c<TILE_COLS>(C, ldc, row0, col0, WIDE_PANEL, nrows, ncols, WIDE_WAVES * 64, alpha, beta,
+                                [&](int r, int j) { return ctile[j][r]; }, [&](int r) { return row_mine[r] != 0; });
+    else
     for (int idx = threadIdx.x; idx < TILE_COLS * WIDE_PANEL; idx += WIDE_WAVES * 64) {
         const int r = idx % WIDE_PANEL, j = idx / WIDE_PANEL;
         if (r < nrows && j < ncols && row_mine[r]) {
@@ -1760,6 +1803,7 @@ __device__ __forceinline__ void merged_sweeps(int cj, const double (&vj)[NR], in
     }
 }
 
+template <bool RC>
 __global__ __launch_bounds__(MERGE_WAVES * 64) void spmm_direct_merge_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
@@ -1856,6 +1900,10 @@ __global__ __launch_bounds__(MERGE_WAVES * 64) void spmm_direct_merge_kernel(
     __syncthreads();
     const int nrows = min(MERGE_PANEL, rows - row0);
     const int ncols = min(TILE_COLS, n - col0);
+    if constexpr (RC)
+        store_rows_c<TILE_COLS>(C, ldc, row0, col0, MERGE_PANEL, nrows, ncols, MERGE_WAVES * 64, alpha, beta,
+                                [&](int r, int j) { return ctile[j][r]; }, [&](int r) { return row_mine[r] != 0; });
+    else
     for (int idx = threadIdx.x; idx < TILE_COLS * MERGE_PANEL; idx += MERGE_WAVES * 64) {
         const int r = idx % MERGE_PANEL, j = idx / MERGE_PANEL;
         if (r < nrows && j < ncols && row_mine[r]) {
@@ -1871,7 +1919,7 @@ __global__ __launch_bounds__(MERGE_WAVES * 64) void spmm_direct_merge_kernel(
 // works on 64/G rows at once and every lane fetches its row's (col, val) itself (the G lanes of a
 // group read the same address, which the memory pipeline serves as one request).
 // ---------------------------------------------------------------------------------------------
-template <int G>
+template <int G, bool RC>
 __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, const int *__restrict__ rowptr,
                                                                   const int *__restrict__ colidx,
                                                                   const double *__restrict__ val,
@@ -1914,6 +1962,10 @@ __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, con
     }
     __syncthreads();
     const int nrows = min(PANEL_ROWS, rows - row0);
+    if constexpr (RC)
+        store_rows_c<G>(C, ldc, row0, 0, PANEL_ROWS, nrows, n, 256, alpha, beta, [&](int r, int j) { return ctile[j][r]; },
+                        [&](int r) { return row_mine[r] != 0; });
+    else
     for (int idx = threadIdx.x; idx < G * PANEL_ROWS; idx += 256) {
         const int r = idx % PANEL_ROWS, j = idx / PANEL_ROWS;
         if (r < nrows && j < n && row_mine[r]) {
@@ -1934,7 +1986,7 @@ __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, con
 // from 128 staged columns on wherever the classifier's vote prefers it to a row per wave (classify_panel).
 // ---------------------------------------------------------------------------------------------
 constexpr int ROWS_LONG = 512; // entries from which a row is computed by the whole workgroup
-template <int WV> // waves per workgroup (4 WV rows)
+template <int WV, bool RC> // waves per workgroup (4 WV rows); C row-major
 __global__ __launch_bounds__(WV * 64) void spmm_direct_rows_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
@@ -2049,6 +2101,10 @@ __global__ __launch_bounds__(WV * 64) void spmm_direct_rows_kernel(
     }
     const int nrows = min(ROWS_PANEL, rows - row0);
     const int ncols = min(64, n - col0);
+    if constexpr (RC)
+        store_rows_c<64>(C, ldc, row0, col0, ROWS_PANEL, nrows, ncols, WV * 64, alpha, beta,
+                         [&](int r, int j) { return ctile[j][r]; }, [&](int r) { return row_mine[r] != 0; });
+    else
     for (int idx = threadIdx.x; idx < 64 * ROWS_PANEL; idx += WV * 64) {
         const int r = idx % ROWS_PANEL, j = idx / ROWS_PANEL;
         if (r < nrows && j < ncols && row_mine[r]) {
@@ -2067,6 +2123,7 @@ __global__ __launch_bounds__(WV * 64) void spmm_direct_rows_kernel(
 // nonzero and keeps eight partial sums; the eight sums are folded across the wave by a halving exchange (4 + 2 + 1
 // shuffles, then three more: ten instead of 48) and lanes 0, 8, .., 56 write columns 0..7.
 // ---------------------------------------------------------------------------------------------
+template <bool RC>
 __global__ __launch_bounds__(256) void spmm_rows8_kernel(int rows, int cols, const int *__restrict__ rowptr,
                                                         const int *__restrict__ colidx,
                                                         const double *__restrict__ val,
@@ -2129,6 +2186,16 @@ __global__ __launch_bounds__(256) void spmm_rows8_kernel(int rows, int cols, con
     s += __shfl_xor(s, 4, WAVE);
     s += __shfl_xor(s, 2, WAVE);
     s += __shfl_xor(s, 1, WAVE);
+    if constexpr (RC) {
+        // row-major C: lanes 0..7 store columns 0..7, one contiguous run (lane 8 j holds column j's sum)
+        const double sj = __shfl(s, (lane & 7) * 8, WAVE);
+        if (lane < 8 && lane < n) {
+            double *dst = C + (int64_t)row * ldc + lane;
+            const double r = alpha * sj;
+            *dst = (beta == 0.0) ? r : fma(beta, *dst, r);
+        }
+        return;
+    }
     const int j = lane >> 3; // column of this lane's sum: (lane & 32 ? 4 : 0) + (lane & 16 ? 2 : 0) + (lane & 8 ? 1 : 0)
     if ((lane & 7) == 0 && j < n) {
         double *dst = C + (int64_t)j * ldc + row;
@@ -2162,14 +2229,15 @@ __global__ __launch_bounds__(256) void axpby_kernel(int64_t n, double alpha, con
     }
 }
 
-// C = beta * C on a rows x n column-major block (a matrix without nonzeros: A*B = 0).  beta = 0 stores zeros without
-// reading C (BLAS semantics: NaNs in C do not propagate).
+// C = beta * C on a rows x n column-major (RC: row-major) block (a matrix without nonzeros: A*B = 0).  beta = 0 stores
+// zeros without reading C (BLAS semantics: NaNs in C do not propagate).
+template <bool RC>
 __global__ __launch_bounds__(256) void scale_kernel(int64_t rows, int64_t n, double beta, double *__restrict__ C,
                                                    int64_t ldc)
 {
     const int64_t total = rows * n, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        double *dst = C + (i / rows) * ldc + (i % rows);
+        double *dst = RC ? C + (i / n) * ldc + (i % n) : C + (i / rows) * ldc + (i % rows);
         *dst = (beta == 0.0) ? 0.0 : beta * *dst;
     }
 }
@@ -2179,24 +2247,26 @@ __global__ __launch_bounds__(256) void scale_kernel(int64_t rows, int64_t n, dou
 // leading dimension m_q) and one pass that scatters them into place and applies alpha / beta:
 //   C[r, j] = beta * C[r, j] + alpha * sum over the blocks q that contain row r of src_q[r - start_q, j]
 // (a boundary row gets two terms, a row longer than nnz/g more).  Replaces the M x N zero fill, the all-reduce of
-// the full M x N buffer and the axpby pass of spmm.h:222-283 / spmv.h:60-138.
+// the full M x N buffer and the axpby pass of spmm.h:222-283 / spmv.h:60-138.  RC: C and the packed blocks are
+// row-major (block q: nrows_q x N at leading dimension N, as contiguous as the column-major form).
 struct RowBlocks {
     const double *src[MAX_REPLICAS];
     long long start[MAX_REPLICAS];
     long long nrows[MAX_REPLICAS];
 };
+template <bool RC>
 __global__ __launch_bounds__(256) void merge_rowblocks_kernel(long long M, long long N, int g, RowBlocks b, double alpha,
                                                              double beta, double *__restrict__ C, long long ldc)
 {
     const long long total = M * N, stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long long r = i % M, j = i / M;
+        const long long r = RC ? i / N : i % M, j = RC ? i % N : i / M;
         double s = 0.0;
         for (int q = 0; q < g; ++q) {
             const long long rel = r - b.start[q];
-            if (rel >= 0 && rel < b.nrows[q]) s += b.src[q][j * b.nrows[q] + rel];
+            if (rel >= 0 && rel < b.nrows[q]) s += b.src[q][RC ? rel * N + j : j * b.nrows[q] + rel];
         }
-        double *dst = C + j * ldc + r;
+        double *dst = RC ? C + r * ldc + j : C + j * ldc + r;
         const double res = alpha * s;
         *dst = (beta == 0.0) ? res : fma(beta, *dst, res);
     }
@@ -2531,21 +2601,30 @@ static float mfma_min_fill(int variant, int panel_rows, int64_t ldbt)
     return ldbt >= 128 ? 0.5f : 2.0f;
 }
 
-hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb,
-                                    double *Bt, int64_t ldbt)
+// the whole of B into Bt, stamps into hdr (the workspace's or a plan's header)
+template <bool RB>
+static void launch_stage_full(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt, int64_t ldbt,
+                              int *hdr, int epoch)
 {
-    dim3 grid((unsigned)((cols + 1 + STAGE_K - 1) / STAGE_K), (unsigned)((ldbt + 63) / 64));
-    int *hdr = reinterpret_cast<int *>(Bt + (size_t)(cols + 1) * (size_t)ldbt);
-    const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
+    const dim3 grid((unsigned)((cols + 1 + STAGE_K - 1) / STAGE_K), (unsigned)((ldbt + 63) / 64));
     const dim3 ngrid((unsigned)((cols + 1 + 255) / 256));
     if (ldbt == 8)
-        hipLaunchKernelGGL(dense_to_rowmajor_narrow_kernel<8>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
+        hipLaunchKernelGGL((dense_to_rowmajor_narrow_kernel<8, RB>), ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
     else if (ldbt == 16)
-        hipLaunchKernelGGL(dense_to_rowmajor_narrow_kernel<16>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
+        hipLaunchKernelGGL((dense_to_rowmajor_narrow_kernel<16, RB>), ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
     else if (ldbt == 32)
-        hipLaunchKernelGGL(dense_to_rowmajor_narrow_kernel<32>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
+        hipLaunchKernelGGL((dense_to_rowmajor_narrow_kernel<32, RB>), ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
     else
-        hipLaunchKernelGGL(dense_to_rowmajor_kernel, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
+        hipLaunchKernelGGL(dense_to_rowmajor_kernel<RB>, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
+}
+
+hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb,
+                                    double *Bt, int64_t ldbt, bool row_b)
+{
+    int *hdr = reinterpret_cast<int *>(Bt + (size_t)(cols + 1) * (size_t)ldbt);
+    const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
+    if (row_b) launch_stage_full<true>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
+    else launch_stage_full<false>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
     return hipGetLastError();
 }
 
@@ -2553,7 +2632,7 @@ hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, cons
 // the column-range launch and *epoch_out goes to launch_spmm_rowpanel; otherwise *epoch_out = 0.
 hipError_t launch_stage_range(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
                               int64_t ldbt, int rows, int64_t nnz, const int *rowptr, const int *colidx, int variant,
-                              int classify, int *epoch_out)
+                              int classify, int *epoch_out, bool row_b)
 {
     const Tail t = tail_of(Bt, cols, ldbt, rows);
     const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>((nnz + 4095) / 4096, TAIL_PARTS));
@@ -2575,8 +2654,14 @@ hipError_t launch_stage_range(hipStream_t s, int64_t cols, int64_t n, const doub
     const int64_t tiles = ((cols + 1 + STAGE_K - 1) / STAGE_K) * ((ldbt + 63) / 64);
     // (a staging pass has an epoch of its own: "B holds a non-finite value" must not stick to the later column chunks of
     //  the call, which reuse the first chunk's classifier epoch)
-    hipLaunchKernelGGL(stage_range_kernel, dim3((unsigned)std::min<int64_t>(tiles, 2048)), dim3(256), 0, s, cols, n, B,
-                       ldb, Bt, ldbt, t.hdr, t.parts, nparts, g_epoch.fetch_add(1, std::memory_order_relaxed));
+    const int stage_epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
+    const dim3 sgrid((unsigned)std::min<int64_t>(tiles, 2048));
+    if (row_b)
+        hipLaunchKernelGGL(stage_range_kernel<true>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, t.hdr, t.parts, nparts,
+                           stage_epoch);
+    else
+        hipLaunchKernelGGL(stage_range_kernel<false>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, t.hdr, t.parts, nparts,
+                           stage_epoch);
     *epoch_out = (classify || again) ? epoch : 0;
     return hipGetLastError();
 }
@@ -2584,7 +2669,7 @@ hipError_t launch_stage_range(hipStream_t s, int64_t cols, int64_t n, const doub
 // Stage 1 + classifier of the default path in one launch; the epoch goes to launch_spmm_rowpanel.
 hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
                                  int64_t ldbt, int rows, const int *rowptr, const int *colidx, int variant,
-                                 int *epoch_out)
+                                 int *epoch_out, bool row_b)
 {
     int info_rows = 0, g = 2;
     panel_plan(rows, ldbt, info_rows, g);
@@ -2594,21 +2679,24 @@ hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const d
     const Tail t = tail_of(Bt, cols, ldbt, rows);
     if (ldbt < 64) {
         const dim3 ngrid((unsigned)((cols + 1 + 255) / 256 + (np + 3) / 4));
-#define SBLAS_STAGE_NARROW(NC)                                                                                         \
-    hipLaunchKernelGGL(stage_classify_narrow_kernel<NC>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, rows, np, info_rows, \
+#define SBLAS_STAGE_NARROW(NC, RB)                                                                                     \
+    hipLaunchKernelGGL((stage_classify_narrow_kernel<NC, RB>), ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, rows, np, info_rows, \
                        rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt), t.hdr, t.info, t.cls, epoch)
-        if (ldbt == 8) SBLAS_STAGE_NARROW(8);
-        else if (ldbt == 16) SBLAS_STAGE_NARROW(16);
-        else SBLAS_STAGE_NARROW(32);
+        if (ldbt == 8) { if (row_b) SBLAS_STAGE_NARROW(8, true); else SBLAS_STAGE_NARROW(8, false); }
+        else if (ldbt == 16) { if (row_b) SBLAS_STAGE_NARROW(16, true); else SBLAS_STAGE_NARROW(16, false); }
+        else { if (row_b) SBLAS_STAGE_NARROW(32, true); else SBLAS_STAGE_NARROW(32, false); }
 #undef SBLAS_STAGE_NARROW
         *epoch_out = epoch;
         return hipGetLastError();
     }
     dim3 grid((unsigned)(stage_blocks + (np + 3) / 4), (unsigned)((ldbt + 63) / 64));
-    hipLaunchKernelGGL(stage_classify_kernel, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, stage_blocks, rows, np,
-                       info_rows, rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt),
-                       ldbt < 64 ? 2.0f : mfma_min_fill(variant, info_rows, ldbt),
-                       direct_probe(ldbt), t.hdr, t.info, t.cls, epoch);
+#define SBLAS_STAGE_WIDE(RB)                                                                                           \
+    hipLaunchKernelGGL(stage_classify_kernel<RB>, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, stage_blocks, rows, np,  \
+                       info_rows, rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt),        \
+                       ldbt < 64 ? 2.0f : mfma_min_fill(variant, info_rows, ldbt),                                       \
+                       direct_probe(ldbt), t.hdr, t.info, t.cls, epoch)
+    if (row_b) SBLAS_STAGE_WIDE(true); else SBLAS_STAGE_WIDE(false);
+#undef SBLAS_STAGE_WIDE
     *epoch_out = epoch;
     return hipGetLastError();
 }
@@ -2669,26 +2757,22 @@ hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int 
 // stage 1 of a planned call: the flags "B holds a non-finite value" go to the PLAN's header (where the stage-2 kernels
 // of the call look), the copy covers the plan's column range when the plan has one
 hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                                int64_t ldbt, const PlanView &pv)
+                                int64_t ldbt, const PlanView &pv, bool row_b)
 {
     const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
     int *hdr = pv.tail;
     if (pv.use_range && ldbt >= 64) {
         const int64_t tiles = ((cols + 1 + STAGE_K - 1) / STAGE_K) * ((ldbt + 63) / 64);
-        hipLaunchKernelGGL(stage_range_kernel, dim3((unsigned)std::min<int64_t>(tiles, 2048)), dim3(256), 0, s, cols, n, B, ldb,
-                           Bt, ldbt, hdr, reinterpret_cast<const int2 *>(hdr + TAIL_HDR), pv.nparts, epoch);
+        const dim3 sgrid((unsigned)std::min<int64_t>(tiles, 2048));
+        const int2 *parts = reinterpret_cast<const int2 *>(hdr + TAIL_HDR);
+        if (row_b)
+            hipLaunchKernelGGL(stage_range_kernel<true>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, parts, pv.nparts, epoch);
+        else
+            hipLaunchKernelGGL(stage_range_kernel<false>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, parts, pv.nparts, epoch);
         return hipGetLastError();
     }
-    const dim3 ngrid((unsigned)((cols + 1 + 255) / 256));
-    if (ldbt == 8)
-        hipLaunchKernelGGL(dense_to_rowmajor_narrow_kernel<8>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
-    else if (ldbt == 16)
-        hipLaunchKernelGGL(dense_to_rowmajor_narrow_kernel<16>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
-    else if (ldbt == 32)
-        hipLaunchKernelGGL(dense_to_rowmajor_narrow_kernel<32>, ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, hdr, epoch);
-    else
-        hipLaunchKernelGGL(dense_to_rowmajor_kernel, dim3((unsigned)((cols + 1 + STAGE_K - 1) / STAGE_K), (unsigned)((ldbt + 63) / 64)),
-                           dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
+    if (row_b) launch_stage_full<true>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
+    else launch_stage_full<false>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
     return hipGetLastError();
 }
 
@@ -2696,6 +2780,7 @@ hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const do
 // 1 M banded rows of 5 / 10 / 20 / 32 per row, N = 64, 4 | 8 | 16 waves: 0.547 | 0.554 | 0.571, 0.632 | 0.613 | 0.617, 0.973 |
 // 0.936 | 0.912, 1.22 | 1.17 | 1.14 ms; power-law rows averaging 3.2 (a 64-row workgroup waits for its longest row): 0.740 |
 // 0.830 | 0.957 ms.  (SBLAS_TUNE=*,*,*,<4|8|16> pins the size: A/B runs)
+template <bool RC>
 static void launch_direct_rows(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
                                const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
                                const int *hdr, const int *cls, int info_rows, int interleave, int epoch, int voted,
@@ -2706,7 +2791,7 @@ static void launch_direct_rows(hipStream_t s, int rows, int cols, const int *row
     const int rp = (rows + 4 * wv - 1) / (4 * wv);
     const dim3 grid((unsigned)rp, (unsigned)(ldbt / 64));
 #define SBLAS_ROWS_GO(WV)                                                                                             \
-    hipLaunchKernelGGL(spmm_direct_rows_kernel<WV>, grid, dim3(WV * 64), 0, s, rows, cols, rp, rowptr, colidx, val, Bt, \
+    hipLaunchKernelGGL((spmm_direct_rows_kernel<WV, RC>), grid, dim3(WV * 64), 0, s, rows, cols, rp, rowptr, colidx, val, Bt, \
                        ldbt, n, alpha, beta, C, ldc, hdr, cls, info_rows, interleave, epoch, voted)
     if (wv == 4) SBLAS_ROWS_GO(4);
     else if (wv == 8) SBLAS_ROWS_GO(8);
@@ -2714,7 +2799,8 @@ static void launch_direct_rows(hipStream_t s, int rows, int cols, const int *row
 #undef SBLAS_ROWS_GO
 }
 
-hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
+template <bool RC>
+static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
                                 const double *val, const double *Bt, int64_t ldbt, int n, double alpha,
                                 double beta, double *C, int64_t ldc, int variant, int pre_epoch, const PlanView *pv)
 {
@@ -2764,8 +2850,8 @@ hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             if (kev) (void)hipEventRecord(kev->a, s);
 #define SBLAS_LAUNCH_W6(GG, NH)                                                                                        \
     do {                                                                                                              \
-        raise_dynamic_lds((const void *)spmm_window6_kernel<GG, NH>, W2_LDS_BYTES);                                   \
-        hipLaunchKernelGGL((spmm_window6_kernel<GG, NH>), wgrid, dim3(1024), W2_LDS_BYTES, s, rows, cols, np, rowptr,   \
+        raise_dynamic_lds((const void *)spmm_window6_kernel<GG, NH, RC>, W2_LDS_BYTES);                               \
+        hipLaunchKernelGGL((spmm_window6_kernel<GG, NH, RC>), wgrid, dim3(1024), W2_LDS_BYTES, s, rows, cols, np, rowptr,   \
                            colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, t.info, t.cls, info_rows, (int)nnz); \
     } while (0)
             if (!need_window) {
@@ -2781,7 +2867,7 @@ hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             }
             if (mfma_possible && need_mfma) {
                 const hipError_t e = launch_spmm_mfma(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc,
-                                                      t.info, t.hdr, t.cls, info_rows, np, epoch, panel_stats_device());
+                                                      t.info, t.hdr, t.cls, info_rows, np, epoch, panel_stats_device(), RC);
                 if (e != hipSuccess) return e;
             }
             cls = t.cls;
@@ -2796,16 +2882,16 @@ hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
                               (variant != SPMM_VARIANT_DIRECT_DPP && avg_row < (ldbt == 64 ? 56.0 : 32.0)))) {
             // short rows: four rows per wave (64 staged columns, banded rows, 1 M rows, against the lane-group kernel: 32 per
             // row 1.08 | 1.14 ms, 48: 1.41 | 1.54, 64: 1.75 | 1.70, 100: 2.57 | 2.49)
-            launch_direct_rows(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
+            launch_direct_rows<RC>(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
                                interleave, epoch, 0, avg_row);
         } else if (ldbt == 64 && n <= 32) {
-            if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<4>, pad);
-            hipLaunchKernelGGL(spmm_direct_dpp_kernel<4>, dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, s,
+            if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<4, RC>, pad);
+            hipLaunchKernelGGL((spmm_direct_dpp_kernel<4, RC>), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, s,
                                rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls,
                                info_rows, interleave, epoch, dpp_long);
         } else if (ldbt == 64) {
-            if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<2>, pad);
-            hipLaunchKernelGGL(spmm_direct_dpp_kernel<2>, dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, s,
+            if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<2, RC>, pad);
+            hipLaunchKernelGGL((spmm_direct_dpp_kernel<2, RC>), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, s,
                                rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls,
                                info_rows, interleave, epoch, dpp_long);
         } else {
@@ -2816,21 +2902,21 @@ hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             // ... and whether four rows per wave on 64-column tiles suit them better than a row per wave on 128-column tiles
             const bool four = pv ? pv->four_rows : cls != nullptr && variant != SPMM_VARIANT_DIRECT_MERGE;
             if (four) {
-                launch_direct_rows(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
+                launch_direct_rows<RC>(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
                                    interleave, epoch, pv ? 0 : 1, avg_row);
             }
             if (merge) {
                 // rows that share their column pattern (multi-dof FEM): three rows per wave, shared Bt loads
                 const int mp = (rows + MERGE_PANEL - 1) / MERGE_PANEL;
                 const size_t lds = (size_t)128 * (MERGE_PANEL + 1) * sizeof(double);
-                raise_dynamic_lds((const void *)spmm_direct_merge_kernel, lds);
-                hipLaunchKernelGGL(spmm_direct_merge_kernel, dim3((unsigned)mp, (unsigned)(ldbt / 128)),
+                raise_dynamic_lds((const void *)spmm_direct_merge_kernel<RC>, lds);
+                hipLaunchKernelGGL(spmm_direct_merge_kernel<RC>, dim3((unsigned)mp, (unsigned)(ldbt / 128)),
                                    dim3(MERGE_WAVES * 64), lds, s, rows, cols, mp, rowptr, colidx, val, Bt, ldbt, n, alpha,
                                    beta, C, ldc, t.hdr, cls, info_rows, interleave, epoch);
             }
             if (plain) {
-                if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<1>, pad);
-                hipLaunchKernelGGL(spmm_direct_dpp_kernel<1>, dim3((unsigned)wide_panels, (unsigned)(ldbt / 128)),
+                if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<1, RC>, pad);
+                hipLaunchKernelGGL((spmm_direct_dpp_kernel<1, RC>), dim3((unsigned)wide_panels, (unsigned)(ldbt / 128)),
                                    dim3(WIDE_WAVES * 64), pad, s, rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n,
                                    alpha, beta, C, ldc, t.hdr, cls, info_rows, interleave, epoch, dpp_long);
             }
@@ -2861,8 +2947,8 @@ hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
 #define SBLAS_LAUNCH_LANES(NC, CP, GG) SBLAS_LAUNCH_LANES4(NC, CP, GG, 1)
 #define SBLAS_LAUNCH_LANES4(NC, CP, GG, LPE)                                                                           \
     do {                                                                                                              \
-        raise_dynamic_lds((const void *)spmm_lanes_kernel<NC, CP, GG, LPE>, WlGeom<NC, CP>::LDS_BYTES);               \
-        hipLaunchKernelGGL((spmm_lanes_kernel<NC, CP, GG, LPE>), dim3((unsigned)np), dim3(1024), (WlGeom<NC, CP>::LDS_BYTES), s, \
+        raise_dynamic_lds((const void *)spmm_lanes_kernel<NC, CP, GG, LPE, RC>, WlGeom<NC, CP>::LDS_BYTES);           \
+        hipLaunchKernelGGL((spmm_lanes_kernel<NC, CP, GG, LPE, RC>), dim3((unsigned)np), dim3(1024), (WlGeom<NC, CP>::LDS_BYTES), s, \
                            rows, cols, np, rowptr, colidx, val, Bt, n, alpha, beta, C, ldc, t.hdr, t.info, t.cls,      \
                            info_rows, (int)nnz);                                                                      \
     } while (0)
@@ -2899,27 +2985,38 @@ hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             // the row-per-wave kernel, four nonzeros per instruction: sixteen lanes x 16 bytes per nonzero (with 16 staged
             // columns the upper eight lanes of a DPP row read past the Bt row, into columns that are never stored)
             const int wide_panels = (rows + WIDE_PANEL - 1) / WIDE_PANEL;
-            hipLaunchKernelGGL(spmm_direct_dpp_kernel<4>, dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), 0, s, rows,
+            hipLaunchKernelGGL((spmm_direct_dpp_kernel<4, RC>), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), 0, s, rows,
                                cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
                                opt.direct_map, epoch, dpp_long);
         } else if (ldbt == 32) {
-            hipLaunchKernelGGL(spmm_rowpanel_narrow_kernel<32>, dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
+            hipLaunchKernelGGL((spmm_rowpanel_narrow_kernel<32, RC>), dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
                                Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         } else if (ldbt == 16) {
-            hipLaunchKernelGGL(spmm_rowpanel_narrow_kernel<16>, dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
+            hipLaunchKernelGGL((spmm_rowpanel_narrow_kernel<16, RC>), dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
                                Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         } else if (avg_row >= opt.rows8_min_avg && variant != SPMM_VARIANT_LANES) {
             // n <= 8, long rows: a wave per row, eight sums per lane (banded-random rows, band +-20000, 600 k rows,
             // N = 8: 64 / 128 / 200 / 300 per row: the lane groups win by 25 / 30 / 2 / 0 %; bench matrix, 399 per row,
             // band +-2000: the wave per row wins by 20 % -- tools/rows8_threshold.py)
-            hipLaunchKernelGGL(spmm_rows8_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, cols, rowptr,
+            hipLaunchKernelGGL(spmm_rows8_kernel<RC>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, cols, rowptr,
                                colidx, val, Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         } else {
-            hipLaunchKernelGGL(spmm_rowpanel_narrow_kernel<8>, dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
+            hipLaunchKernelGGL((spmm_rowpanel_narrow_kernel<8, RC>), dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
                                Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         }
     }
     return hipGetLastError();
+}
+
+hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
+                                const double *val, const double *Bt, int64_t ldbt, int n, double alpha,
+                                double beta, double *C, int64_t ldc, int variant, int pre_epoch, const PlanView *pv,
+                                bool row_c)
+{
+    return row_c ? spmm_rowpanel<true>(s, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, variant,
+                                       pre_epoch, pv)
+                 : spmm_rowpanel<false>(s, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, variant,
+                                        pre_epoch, pv);
 }
 
 // device address of the panel census (the matrix-core kernel lives in another translation unit)
@@ -2949,9 +3046,10 @@ hipError_t panel_stats(unsigned long long out[4], bool reset)
 }
 
 
-hipError_t launch_scale(hipStream_t s, int64_t rows, int64_t n, double beta, double *C, int64_t ldc)
+hipError_t launch_scale(hipStream_t s, int64_t rows, int64_t n, double beta, double *C, int64_t ldc, bool row_c)
 {
-    hipLaunchKernelGGL(scale_kernel, dim3(capped_grid(rows * n, 256)), dim3(256), 0, s, rows, n, beta, C, ldc);
+    if (row_c) hipLaunchKernelGGL(scale_kernel<true>, dim3(capped_grid(rows * n, 256)), dim3(256), 0, s, rows, n, beta, C, ldc);
+    else hipLaunchKernelGGL(scale_kernel<false>, dim3(capped_grid(rows * n, 256)), dim3(256), 0, s, rows, n, beta, C, ldc);
     return hipGetLastError();
 }
 
@@ -2963,7 +3061,7 @@ hipError_t launch_axpby(hipStream_t s, int64_t n, double alpha, const double *x,
 
 hipError_t launch_merge_rowblocks(hipStream_t s, int64_t M, int64_t N, int g, const double *const *src,
                                   const int64_t *start, const int64_t *nrows, double alpha, double beta, double *C,
-                                  int64_t ldc)
+                                  int64_t ldc, bool row_c)
 {
     RowBlocks b{};
     for (int q = 0; q < g; ++q) {
@@ -2971,8 +3069,12 @@ hipError_t launch_merge_rowblocks(hipStream_t s, int64_t M, int64_t N, int g, co
         b.start[q] = start[q];
         b.nrows[q] = nrows[q];
     }
-    hipLaunchKernelGGL(merge_rowblocks_kernel, dim3(capped_grid(M * N, 256)), dim3(256), 0, s, (long long)M,
-                       (long long)N, g, b, alpha, beta, C, (long long)ldc);
+    if (row_c)
+        hipLaunchKernelGGL(merge_rowblocks_kernel<true>, dim3(capped_grid(M * N, 256)), dim3(256), 0, s, (long long)M,
+                           (long long)N, g, b, alpha, beta, C, (long long)ldc);
+    else
+        hipLaunchKernelGGL(merge_rowblocks_kernel<false>, dim3(capped_grid(M * N, 256)), dim3(256), 0, s, (long long)M,
+                           (long long)N, g, b, alpha, beta, C, (long long)ldc);
     return hipGetLastError();
 }
 

@@ -49,7 +49,7 @@ __device__ __forceinline__ int wave_min_quads(int x)
                min(__builtin_amdgcn_readlane(x, 47), __builtin_amdgcn_readlane(x, 63)));
 }
 
-template <int NT, int BATCH>
+template <int NT, int BATCH, bool RC>
 __global__ __launch_bounds__(MFMA_MAX_WAVES * 64) void spmm_mfma_kernel(
     int rows, int cols, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
@@ -241,6 +241,10 @@ __global__ __launch_bounds__(MFMA_MAX_WAVES * 64) void spmm_mfma_kernel(
     }
     __syncthreads();
     const int ncols = min(NCOLS, n - col0);
+    if constexpr (RC)
+        store_rows_c<NCOLS>(C, ldc, row0, col0, panel_rows, prow, ncols, (int)blockDim.x, alpha, beta,
+                            [&](int r, int cj) { return ctile[cj * pr1 + r]; }, [](int) { return true; });
+    else
     for (int idx = tid; idx < NCOLS * panel_rows; idx += blockDim.x) {
         const int r = idx % panel_rows, cj = idx / panel_rows;
         if (r < prow && cj < ncols) {
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(MFMA_MAX_WAVES * 64) void spmm_mfma_kernel(
 hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
                             const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
                             const int2 *info, const int *tail, const int *cls, int panel_rows, int npanels, int epoch,
-                            unsigned long long *stats)
+                            unsigned long long *stats, bool row_c)
 {
     const int waves = (panel_rows + 15) / 16;
     if (waves < 1 || waves > MFMA_MAX_WAVES) return hipErrorInvalidValue;
@@ -262,12 +266,17 @@ hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr
     const size_t ctile_bytes = (size_t)(ldbt == 64 ? 64 : 128) * (size_t)(panel_rows + 1) * sizeof(double);
     size_t lds = img_bytes > ctile_bytes ? img_bytes : ctile_bytes;
     if ((size_t)options().tune[0] > lds && options().tune[0] <= 160 * 1024) lds = (size_t)options().tune[0]; // experiments: occupancy
-#define SBLAS_MFMA_LAUNCH(NTV, BV, GY)                                                                                \
+#define SBLAS_MFMA_LAUNCH1(NTV, BV, GY, RC)                                                                           \
     do {                                                                                                             \
-        raise_dynamic_lds((const void *)spmm_mfma_kernel<NTV, BV>, lds);                                             \
-        hipLaunchKernelGGL((spmm_mfma_kernel<NTV, BV>), dim3((unsigned)npanels, (unsigned)(GY)),                     \
+        raise_dynamic_lds((const void *)spmm_mfma_kernel<NTV, BV, RC>, lds);                                         \
+        hipLaunchKernelGGL((spmm_mfma_kernel<NTV, BV, RC>), dim3((unsigned)npanels, (unsigned)(GY)),                     \
                            dim3((unsigned)waves * 64u), lds, s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha,  \
                            beta, C, ldc, info, tail, cls, panel_rows, epoch, stats);                                 \
+    } while (0)
+#define SBLAS_MFMA_LAUNCH(NTV, BV, GY)                                                                                \
+    do {                                                                                                             \
+        if (row_c) SBLAS_MFMA_LAUNCH1(NTV, BV, GY, true);                                                            \
+        else SBLAS_MFMA_LAUNCH1(NTV, BV, GY, false);                                                                 \
     } while (0)
     const int batch = options().tune[1]; // experiments: operand blocks per stage
     if (ldbt == 64) {
@@ -279,6 +288,7 @@ hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr
         else SBLAS_MFMA_LAUNCH(8, 2, ldbt / 128);
     }
 #undef SBLAS_MFMA_LAUNCH
+#undef SBLAS_MFMA_LAUNCH1
     return hipGetLastError();
 }
 

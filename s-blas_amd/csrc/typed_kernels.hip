@@ -25,12 +25,23 @@ template <> __device__ __forceinline__ double fma_t<double>(double a, double b, 
 template <> __device__ __forceinline__ float fma_t<float>(float a, float b, float c) { return fmaf(a, b, c); }
 
 // Stage 1: B (cols x n, column-major, ld = ldb) -> Bt (cols x ldbt, row-major, zero padded to ldbt).
-template <typename T>
+// RB: B row-major (B[k * ldb + j]): a straight row copy, no LDS transpose.
+template <typename T, bool RB>
 __global__ __launch_bounds__(256) void typed_stage_kernel(int64_t cols, int64_t n, const T *__restrict__ B, int64_t ldb,
                                                          T *__restrict__ Bt, int64_t ldbt)
 {
     __shared__ T tile[64][33];
     const int64_t k0 = (int64_t)blockIdx.x * 32, j0 = (int64_t)blockIdx.y * 64;
+    if constexpr (RB) {
+        const int jl = threadIdx.x & 63, kq = threadIdx.x >> 6;
+        const int64_t j = j0 + jl;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t k = k0 + kq + 4 * u;
+            if (k < cols && j < ldbt) Bt[k * ldbt + j] = j < n ? B[k * ldb + j] : T(0);
+        }
+        return;
+    }
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -48,7 +59,7 @@ __global__ __launch_bounds__(256) void typed_stage_kernel(int64_t cols, int64_t 
 
 // Stage 2: a wave owns a row and 64 columns of C.  The row's (column, value) pairs are read 64 at a time, one per
 // lane, and handed round with shuffles; every nonzero is one coalesced 64-element read of a Bt row.
-template <typename I, typename T>
+template <typename I, typename T, bool RC>
 __global__ __launch_bounds__(256) void typed_spmm_kernel(int64_t rows, const I *__restrict__ rowptr,
                                                         const I *__restrict__ colidx, const T *__restrict__ val,
                                                         const T *__restrict__ Bt, int64_t ldbt, int64_t n, T alpha,
@@ -94,6 +105,10 @@ __global__ __launch_bounds__(256) void typed_spmm_kernel(int64_t rows, const I *
     }
     __syncthreads();
     const int64_t nrows = std::min<int64_t>(TY_ROWS, rows - row0), ncols = std::min<int64_t>(64, n - col0);
+    if constexpr (RC)
+        store_rows_c<64>(C, ldc, row0, col0, TY_ROWS, (int)nrows, (int)ncols, 256, alpha, beta,
+                         [&](int r, int j) { return ctile[j][r]; }, [](int) { return true; });
+    else
     for (int idx = threadIdx.x; idx < 64 * TY_ROWS; idx += 256) {
         const int r = idx % TY_ROWS, j = idx / TY_ROWS;
         if (r < nrows && j < ncols) {
@@ -125,12 +140,12 @@ __global__ __launch_bounds__(256) void typed_spmv_kernel(int64_t rows, const I *
     }
 }
 
-template <typename T>
+template <typename T, bool RC>
 __global__ __launch_bounds__(256) void typed_scale_kernel(int64_t rows, int64_t n, T beta, T *__restrict__ C, int64_t ldc)
 {
     const int64_t total = rows * n, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        T *dst = C + (i / rows) * ldc + (i % rows);
+        T *dst = RC ? C + (i / n) * ldc + (i % n) : C + (i / rows) * ldc + (i % rows);
         *dst = (beta == T(0)) ? T(0) : beta * *dst;
     }
 }
@@ -163,19 +178,19 @@ struct TypedBlocks {
     long long nrows[MAX_REPLICAS];
 };
 // the row-block merge of kernels.hip (merge_rowblocks_kernel) in the value type
-template <typename T>
+template <typename T, bool RC>
 __global__ __launch_bounds__(256) void typed_merge_rowblocks_kernel(long long M, long long N, int g, TypedBlocks b, T alpha,
                                                                    T beta, T *__restrict__ C, long long ldc)
 {
     const long long total = M * N, stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long long r = i % M, j = i / M;
+        const long long r = RC ? i / N : i % M, j = RC ? i % N : i / M;
         T s = T(0);
         for (int q = 0; q < g; ++q) {
             const long long rel = r - b.start[q];
-            if (rel >= 0 && rel < b.nrows[q]) s += static_cast<const T *>(b.src[q])[j * b.nrows[q] + rel];
+            if (rel >= 0 && rel < b.nrows[q]) s += static_cast<const T *>(b.src[q])[RC ? rel * N + j : j * b.nrows[q] + rel];
         }
-        T *dst = C + j * ldc + r;
+        T *dst = RC ? C + r * ldc + j : C + j * ldc + r;
         const T res = alpha * s;
         *dst = (beta == T(0)) ? res : fma_t<T>(beta, *dst, res);
     }
@@ -187,22 +202,22 @@ unsigned grid_for(int64_t items, int per_block)
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(b, 2048));
 }
 
-template <typename I, typename T>
+template <typename I, typename T, bool RB, bool RC>
 hipError_t spmm_typed(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, const void *rowptr, const void *colidx,
                       const void *val, const void *B, int64_t ldb, int64_t n, double alpha, double beta, void *C,
                       int64_t ldc, void *ws)
 {
     if (cols == 0 || nnz == 0) {
         if (beta != 1.0)
-            hipLaunchKernelGGL(typed_scale_kernel<T>, dim3(grid_for(rows * n, 256)), dim3(256), 0, s, rows, n, (T)beta,
+            hipLaunchKernelGGL((typed_scale_kernel<T, RC>), dim3(grid_for(rows * n, 256)), dim3(256), 0, s, rows, n, (T)beta,
                                static_cast<T *>(C), ldc);
         return hipGetLastError();
     }
     const int64_t ldbt = typed_spmm_ldbt(n);
     T *Bt = static_cast<T *>(ws);
-    hipLaunchKernelGGL(typed_stage_kernel<T>, dim3((unsigned)((cols + 31) / 32), (unsigned)(ldbt / 64)), dim3(256), 0, s, cols,
+    hipLaunchKernelGGL((typed_stage_kernel<T, RB>), dim3((unsigned)((cols + 31) / 32), (unsigned)(ldbt / 64)), dim3(256), 0, s, cols,
                        n, static_cast<const T *>(B), ldb, Bt, ldbt);
-    hipLaunchKernelGGL((typed_spmm_kernel<I, T>), dim3((unsigned)((rows + TY_ROWS - 1) / TY_ROWS), (unsigned)(ldbt / 64)),
+    hipLaunchKernelGGL((typed_spmm_kernel<I, T, RC>), dim3((unsigned)((rows + TY_ROWS - 1) / TY_ROWS), (unsigned)(ldbt / 64)),
                        dim3(256), 0, s, rows, static_cast<const I *>(rowptr), static_cast<const I *>(colidx),
                        static_cast<const T *>(val), Bt, ldbt, n, (T)alpha, (T)beta, static_cast<T *>(C), ldc);
     return hipGetLastError();
@@ -228,15 +243,27 @@ size_t typed_spmm_workspace(int vt, int64_t cols, int64_t n)
     return (size_t)cols * (size_t)typed_spmm_ldbt(n) * (vt == VT_F32 ? 4u : 8u);
 }
 
+template <typename I, typename T>
+static hipError_t spmm_typed_ordered(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, const void *rowptr,
+                                     const void *colidx, const void *val, const void *B, int64_t ldb, int64_t n, double alpha,
+                                     double beta, void *C, int64_t ldc, void *ws, bool row_b, bool row_c)
+{
+    if (row_b)
+        return row_c ? spmm_typed<I, T, true, true>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws)
+                     : spmm_typed<I, T, true, false>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws);
+    return row_c ? spmm_typed<I, T, false, true>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws)
+                 : spmm_typed<I, T, false, false>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws);
+}
+
 hipError_t launch_typed_spmm(hipStream_t s, int vt, int it, int64_t rows, int64_t cols, int64_t nnz, const void *rowptr,
                              const void *colidx, const void *val, const void *B, int64_t ldb, int64_t n, double alpha,
-                             double beta, void *C, int64_t ldc, void *ws)
+                             double beta, void *C, int64_t ldc, void *ws, bool row_b, bool row_c)
 {
     if (vt == VT_F32)
-        return it == IT_I64 ? spmm_typed<int64_t, float>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws)
-                            : spmm_typed<int32_t, float>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws);
-    return it == IT_I64 ? spmm_typed<int64_t, double>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws)
-                        : spmm_typed<int32_t, double>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws);
+        return it == IT_I64 ? spmm_typed_ordered<int64_t, float>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws, row_b, row_c)
+                            : spmm_typed_ordered<int32_t, float>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws, row_b, row_c);
+    return it == IT_I64 ? spmm_typed_ordered<int64_t, double>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws, row_b, row_c)
+                        : spmm_typed_ordered<int32_t, double>(s, rows, cols, nnz, rowptr, colidx, val, B, ldb, n, alpha, beta, C, ldc, ws, row_b, row_c);
 }
 
 hipError_t launch_typed_spmv(hipStream_t s, int vt, int it, int64_t rows, const void *rowptr, const void *colidx,
@@ -271,7 +298,7 @@ hipError_t launch_typed_sum_replicas(hipStream_t s, int vt, void *const *bufs, i
 
 hipError_t launch_typed_merge_rowblocks(hipStream_t s, int vt, int64_t M, int64_t N, int g, const void *const *src,
                                         const int64_t *start_row, const int64_t *num_rows, double alpha, double beta,
-                                        void *C, int64_t ldc)
+                                        void *C, int64_t ldc, bool row_c)
 {
     TypedBlocks b{};
     for (int q = 0; q < g; ++q) {
@@ -279,12 +306,15 @@ hipError_t launch_typed_merge_rowblocks(hipStream_t s, int vt, int64_t M, int64_
         b.start[q] = start_row[q];
         b.nrows[q] = num_rows[q];
     }
-    if (vt == VT_F32)
-        hipLaunchKernelGGL(typed_merge_rowblocks_kernel<float>, dim3(grid_for(M * N, 256)), dim3(256), 0, s, (long long)M,
-                           (long long)N, g, b, (float)alpha, (float)beta, static_cast<float *>(C), (long long)ldc);
-    else
-        hipLaunchKernelGGL(typed_merge_rowblocks_kernel<double>, dim3(grid_for(M * N, 256)), dim3(256), 0, s, (long long)M,
-                           (long long)N, g, b, alpha, beta, static_cast<double *>(C), (long long)ldc);
+#define SBLAS_TYPED_MERGE(T, RC)                                                                                       \
+    hipLaunchKernelGGL((typed_merge_rowblocks_kernel<T, RC>), dim3(grid_for(M * N, 256)), dim3(256), 0, s, (long long)M,      \
+                       (long long)N, g, b, (T)alpha, (T)beta, static_cast<T *>(C), (long long)ldc)
+    if (vt == VT_F32) {
+        if (row_c) SBLAS_TYPED_MERGE(float, true); else SBLAS_TYPED_MERGE(float, false);
+    } else {
+        if (row_c) SBLAS_TYPED_MERGE(double, true); else SBLAS_TYPED_MERGE(double, false);
+    }
+#undef SBLAS_TYPED_MERGE
     return hipGetLastError();
 }
 

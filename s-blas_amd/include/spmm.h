@@ -73,11 +73,12 @@ inline void require_col_major(const char *who, DenseMatrix<IdxType, DataType> *p
 // bufferSize / workspace step has at spmm.h:134-141) from the SECOND call for this matrix, GPU and width on (a caller
 // that multiplies once -- the reference's drivers -- pays nothing; making the plan synchronises the GPU's stream once);
 // the plan stays in the CsrSparseMatrix until its next sync2gpu, and every later call launches only the kernels that
-// have panels.  SBLAS_PLAN=0 keeps every call unplanned.
+// have panels.  SBLAS_PLAN=0 keeps every call unplanned.  order_b / order_c: SBLAS_COL_MAJOR or SBLAS_ROW_MAJOR (one plan
+// serves both).
 template <typename IdxType, typename DataType>
 inline int spmm_on_gpu(CsrSparseMatrix<IdxType, DataType> *pA, unsigned i, void *stream, int vt, int it, int64_t m, int64_t K,
-                       int64_t nnz, const DataType *B, int64_t ldb, int64_t n, double alpha, double beta, DataType *C,
-                       int64_t ldc, void *ws, size_t ws_bytes)
+                       int64_t nnz, const DataType *B, int64_t ldb, int order_b, int64_t n, double alpha, double beta,
+                       DataType *C, int64_t ldc, int order_c, void *ws, size_t ws_bytes)
 {
     static const bool plans = [] {
         const char *e = getenv("SBLAS_PLAN");
@@ -94,15 +95,17 @@ inline int spmm_on_gpu(CsrSparseMatrix<IdxType, DataType> *pA, unsigned i, void 
             pA->spmm_plan_n[i] = key;
         } else if (!mine) { // first call at this width, or a width other than the plan's (a ragged last tile): unplanned
             if (!pA->spmm_plan_gpu[i]) pA->spmm_plan_n[i] = -key;
-            return sblas_hip_spmm_csr(-1, stream, vt, it, m, K, nnz, pA->csrRowPtr_gpu[i], pA->csrColIdx_gpu[i], pA->csrVal_gpu[i],
-                                      B, ldb, n, alpha, beta, C, ldc, ws, ws_bytes);
+            return sblas_hip_spmm_csr_ordered(-1, stream, vt, it, m, K, nnz, pA->csrRowPtr_gpu[i], pA->csrColIdx_gpu[i],
+                                              pA->csrVal_gpu[i], B, ldb, order_b, n, alpha, beta, C, ldc, order_c, ws, ws_bytes);
         }
-        return sblas_hip_spmm_csr_f64_i32_planned(pA->spmm_plan_gpu[i], -1, stream, m, K, nnz, (const int32_t *)pA->csrRowPtr_gpu[i],
-                                                  (const int32_t *)pA->csrColIdx_gpu[i], (const double *)pA->csrVal_gpu[i],
-                                                  (const double *)B, ldb, n, alpha, beta, (double *)C, ldc, ws, ws_bytes);
+        return sblas_hip_spmm_csr_ordered_f64_i32_planned(pA->spmm_plan_gpu[i], -1, stream, m, K, nnz,
+                                                          (const int32_t *)pA->csrRowPtr_gpu[i],
+                                                          (const int32_t *)pA->csrColIdx_gpu[i], (const double *)pA->csrVal_gpu[i],
+                                                          (const double *)B, ldb, order_b, n, alpha, beta, (double *)C, ldc,
+                                                          order_c, ws, ws_bytes);
     }
-    return sblas_hip_spmm_csr(-1, stream, vt, it, m, K, nnz, pA->csrRowPtr_gpu[i], pA->csrColIdx_gpu[i], pA->csrVal_gpu[i], B, ldb,
-                              n, alpha, beta, C, ldc, ws, ws_bytes);
+    return sblas_hip_spmm_csr_ordered(-1, stream, vt, it, m, K, nnz, pA->csrRowPtr_gpu[i], pA->csrColIdx_gpu[i], pA->csrVal_gpu[i],
+                                      B, ldb, order_b, n, alpha, beta, C, ldc, order_c, ws, ws_bytes);
 }
 
 constexpr int64_t M2_TILE = 128; // column tile of method 2's SpMM / merge pipeline
@@ -130,15 +133,18 @@ void sblas_spmm_csr_v1(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxTy
         CUDA_SAFE_CALL(cudaSetDevice((int)i));
         const size_t ws_bytes = sblas_hip_spmm_csr_workspace(vt, it, M, K, nnz, n_i);
         void *ws = sblas_rt::workspace(i, ws_bytes);
-        sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, sblas_rt::stream(i), vt, it, M, K, nnz, pB->val_gpu[i], K, n_i,
-                                                       (double)alpha, (double)beta, pC->val_gpu[i], M, ws, ws_bytes),
+        sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, sblas_rt::stream(i), vt, it, M, K, nnz, pB->val_gpu[i], K,
+                                                       SBLAS_COL_MAJOR, n_i, (double)alpha, (double)beta, pC->val_gpu[i], M,
+                                                       SBLAS_COL_MAJOR, ws, ws_bytes),
                              "sblas_hip_spmm_csr");
     }
     for (unsigned i = 0; i < n_gpu; ++i) pC->sync2cpu(i); // stream-ordered after GPU i's kernels
 }
 
-// Method 2.  Preconditions: A.sync2gpu(g, segment); B, C .sync2gpu(g, replicate), col-major.
-// On return every C.val_gpu[i] holds the full result; the host copy is refreshed by C.sync2cpu(i).
+// Method 2.  Preconditions: A.sync2gpu(g, segment); B, C .sync2gpu(g, replicate).  B and C may each be column- or
+// row-major (the reference requires column-major for both, spmm.h:171-178; a row-major operand is passed on to the C ABI
+// as it is, with no transpose).  On return every C.val_gpu[i] holds the full result; the host copy is refreshed by
+// C.sync2cpu(i).
 template <typename IdxType, typename DataType>
 void sblas_spmm_csr_v2(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxType, DataType> *pB,
                        DenseMatrix<IdxType, DataType> *pC, DataType alpha, DataType beta, unsigned n_gpu)
@@ -146,10 +152,14 @@ void sblas_spmm_csr_v2(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxTy
     assert((pA->width) == (pB->height));
     assert((pA->height) == (pC->height));
     assert((pB->width) == (pC->width));
-    sblas_detail::require_col_major("SBLAS_SPMM_CSR_V2", pB, pC);
     const int vt = sblas_rt::vtype_of<DataType>("SBLAS_SPMM_CSR_V2"), it = sblas_rt::itype_of<IdxType>("SBLAS_SPMM_CSR_V2");
     assert(pA->policy == segment && pB->policy == replicate && pC->policy == replicate);
     const int64_t M = pA->height, K = pA->width, N = pB->width;
+    // layouts: a row-major C makes the packed blocks, C_copy and the merge row-major too (leading dimension N)
+    const int ob = pB->order == row_major ? SBLAS_ROW_MAJOR : SBLAS_COL_MAJOR;
+    const int oc = pC->order == row_major ? SBLAS_ROW_MAJOR : SBLAS_COL_MAJOR;
+    const bool c_row = oc == SBLAS_ROW_MAJOR;
+    const int64_t ldb = ob == SBLAS_ROW_MAJOR ? N : K, ldc = c_row ? N : M;
     const size_t cnt = (size_t)M * (size_t)N;
 
     // persistent communicator over the logical GPUs (created once, not per call)
@@ -168,9 +178,11 @@ void sblas_spmm_csr_v2(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxTy
     std::vector<DataType *> ccopy(n_gpu, (DataType *)NULL), gather(n_gpu, (DataType *)NULL);
     std::vector<void *> streams(n_gpu), mstreams(n_gpu);
     std::vector<GPU_Timer *> timers(n_gpu);
-    // two or more 128-column tiles: pipeline SpMM and merge over the tiles (SBLAS_M2_PIPELINE=0: one piece, serial)
+    // two or more 128-column tiles: pipeline SpMM and merge over the tiles (SBLAS_M2_PIPELINE=0: one piece, serial).
+    // Column-major C only: a column tile of a packed row-major block is not contiguous, so it cannot be sent as one
+    // piece; a row-major C takes the one-piece merge.
     const char *pipe_mode = getenv("SBLAS_M2_PIPELINE");
-    const bool pipelined = !use_allreduce && N >= 2 * sblas_detail::M2_TILE && !(pipe_mode && pipe_mode[0] == '0');
+    const bool pipelined = !use_allreduce && !c_row && N >= 2 * sblas_detail::M2_TILE && !(pipe_mode && pipe_mode[0] == '0');
     std::vector<int64_t> starts(n_gpu), nrows(n_gpu);
     size_t all_blocks = 0;
     for (unsigned i = 0; i < n_gpu; ++i) {
@@ -191,16 +203,17 @@ void sblas_spmm_csr_v2(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxTy
             // A_i * B accumulated (alpha = beta = 1) at its row offset, ld = M
             ccopy[i] = (DataType *)sblas_rt::workspace(i, cnt * sizeof(DataType), sblas_rt::WS_PARTIAL);
             CUDA_SAFE_CALL(hipMemsetAsync(ccopy[i], 0, cnt * sizeof(DataType), (hipStream_t)streams[i]));
-            sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, streams[i], vt, it, m_i, K, nnz_i, pB->val_gpu[i], K, N, 1.0, 1.0,
-                                                           ccopy[i] + (size_t)pA->starting_row_gpu[i], M, ws, ws_bytes),
+            const size_t off = (size_t)pA->starting_row_gpu[i] * (c_row ? (size_t)N : 1u);
+            sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, streams[i], vt, it, m_i, K, nnz_i, pB->val_gpu[i], ldb, ob, N, 1.0,
+                                                           1.0, ccopy[i] + off, ldc, oc, ws, ws_bytes),
                                  "sblas_hip_spmm_csr");
         } else {
             // packed m_i x N block, beta = 0: nothing to clear
             ccopy[i] = (DataType *)sblas_rt::workspace(i, (size_t)m_i * (size_t)N * sizeof(DataType), sblas_rt::WS_PARTIAL);
             gather[i] = (DataType *)sblas_rt::workspace(i, all_blocks * sizeof(DataType), sblas_rt::WS_GATHER);
             if (!pipelined)
-                sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, streams[i], vt, it, m_i, K, nnz_i, pB->val_gpu[i], K, N, 1.0, 0.0,
-                                                               ccopy[i], m_i, ws, ws_bytes),
+                sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, streams[i], vt, it, m_i, K, nnz_i, pB->val_gpu[i], ldb, ob, N,
+                                                               1.0, 0.0, ccopy[i], c_row ? N : m_i, oc, ws, ws_bytes),
                                      "sblas_hip_spmm_csr");
         }
         timers[i] = new GPU_Timer((hipStream_t)(pipelined ? mstreams[i] : streams[i]));
@@ -213,9 +226,9 @@ void sblas_spmm_csr_v2(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxTy
     } else if (!pipelined) {
         std::vector<void *> cptr(n_gpu);
         for (unsigned i = 0; i < n_gpu; ++i) cptr[i] = pC->val_gpu[i];
-        sblas_rt::must_sblas(sblas_hip_merge_rowblocks(comm, vt, M, N, starts.data(), nrows.data(),
-                                                       (void *const *)ccopy.data(), (void *const *)gather.data(),
-                                                       (double)alpha, (double)beta, cptr.data(), M, streams.data()),
+        sblas_rt::must_sblas(sblas_hip_merge_rowblocks_ordered(comm, vt, oc, M, N, starts.data(), nrows.data(),
+                                                               (void *const *)ccopy.data(), (void *const *)gather.data(),
+                                                               (double)alpha, (double)beta, cptr.data(), ldc, streams.data()),
                              "sblas_hip_merge_rowblocks");
     } else {
         // Column-tile pipeline (the reference is fully serial, spmm.h:253-265): the SpMM of tile c + 1 runs on the compute
@@ -240,8 +253,11 @@ void sblas_spmm_csr_v2(CsrSparseMatrix<IdxType, DataType> *pA, DenseMatrix<IdxTy
                 gtile[i] = gather[i] + (size_t)c0 * rows_all;
                 ctile[i] = pC->val_gpu[i] + (size_t)c0 * (size_t)M;
                 sblas_rt::must_sblas(sblas_detail::spmm_on_gpu(pA, i, streams[i], vt, it, m_i, K, nnz_i,
-                                                               pB->val_gpu[i] + (size_t)c0 * (size_t)K, K, Tc, 1.0, 0.0,
-                                                               (DataType *)ptile[i], m_i, ws, ws_bytes),
+                                                               // tile c of B: the view B + c0 (row-major, at ldb = N) or
+                                                               // B + c0 K (column-major)
+                                                               pB->val_gpu[i] + (size_t)c0 * (ob == SBLAS_ROW_MAJOR ? 1u : (size_t)K),
+                                                               ldb, ob, Tc, 1.0, 0.0, (DataType *)ptile[i], m_i,
+                                                               SBLAS_COL_MAJOR, ws, ws_bytes),
                                      "sblas_hip_spmm_csr");
                 hipEvent_t done = sblas_rt::event(i, (size_t)c);
                 CUDA_SAFE_CALL(hipEventRecord(done, (hipStream_t)streams[i]));

@@ -31,6 +31,7 @@ EXPORTS = [
     "sblas_hip_spmm_plan_create", "sblas_hip_spmm_plan_destroy", "sblas_hip_spmm_plan_info", "sblas_hip_spmm_csr_f64_i32_planned",
     "sblas_hip_spmv_plan_create", "sblas_hip_spmv_plan_destroy", "sblas_hip_spmv_plan_info", "sblas_hip_spmv_csr_f64_i32_planned",
     "sblas_spmv_plan_classify",
+    "sblas_hip_spmm_csr_ordered", "sblas_hip_spmm_csr_ordered_f64_i32_planned", "sblas_hip_merge_rowblocks_ordered",
 ]
 
 
@@ -136,6 +137,15 @@ def lib():
     L.sblas_hip_merge_rowblocks.restype = C.c_int
     L.sblas_hip_merge_rowblocks.argtypes = [vp, C.c_int, i64, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp),
                                             f64, f64, C.POINTER(vp), i64, C.POINTER(vp)]
+    L.sblas_hip_spmm_csr_ordered.restype = C.c_int
+    L.sblas_hip_spmm_csr_ordered.argtypes = [C.c_int, vp, C.c_int, C.c_int, i64, i64, i64, vp, vp, vp, vp, i64, C.c_int, i64,
+                                             f64, f64, vp, i64, C.c_int, vp, sz]
+    L.sblas_hip_spmm_csr_ordered_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_spmm_csr_ordered_f64_i32_planned.argtypes = [vp, C.c_int, vp, i64, i64, i64, vp, vp, vp, vp, i64, C.c_int, i64,
+                                                             f64, f64, vp, i64, C.c_int, vp, sz]
+    L.sblas_hip_merge_rowblocks_ordered.restype = C.c_int
+    L.sblas_hip_merge_rowblocks_ordered.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp),
+                                                    C.POINTER(vp), f64, f64, C.POINTER(vp), i64, C.POINTER(vp)]
     L.sblas_partition_nnz_i64.restype = i64
     L.sblas_partition_nnz_i64.argtypes = [vp, i64, i64, C.c_int, C.c_int] + [C.POINTER(i64)] * 4 + [vp]
     _lib = L
@@ -287,6 +297,19 @@ class SpmmPlan:
             _dev_ptr(workspace, torch.float64, "workspace") if workspace is not None and workspace.numel() else None,
             workspace.numel() * 8 if workspace is not None else 0)
         check(rc, "sblas_hip_spmm_csr_f64_i32_planned")
+
+    def spmm_ordered(self, val, B, ldb, order_b, n, alpha, beta, Cmat, ldc, order_c, workspace, stream=None, c_offset=0):
+        """The planned form of spmm_ordered() (float64 values, int32 indices): one plan serves every order pair."""
+        import torch
+        rc = lib().sblas_hip_spmm_csr_ordered_f64_i32_planned(
+            self.handle, -1, _stream(stream), self.rows, self.cols, self.nnz,
+            _dev_ptr(self.rowptr, torch.int32, "rowptr"), _dev_ptr(self.colidx, torch.int32, "colidx") if self.nnz else None,
+            _dev_ptr(val, torch.float64, "val") if self.nnz else None,
+            _dev_ptr(B, torch.float64, "B") if self.cols else None, ldb, order_b, n, alpha, beta,
+            _dev_ptr(Cmat, torch.float64, "C") + 8 * c_offset, ldc, order_c,
+            _dev_ptr(workspace, workspace.dtype, "workspace") if workspace is not None and workspace.numel() else None,
+            workspace.numel() * workspace.element_size() if workspace is not None else 0)
+        check(rc, "sblas_hip_spmm_csr_ordered_f64_i32_planned")
 
     def destroy(self):
         if self.handle:
@@ -575,3 +598,107 @@ def partition_nnz_i64(rowptr, n_gpu, i_gpu):
     if num < 0:
         raise SblasError("sblas_partition_nnz_i64 failed (%d)" % num)
     return dict(start_row=s.value, stop_row=e.value, nnz=k.value, first_nnz=f.value, rowptr=buf[:num].copy())
+
+
+# ------------------------------------------------------------------------------------------
+# row-major dense operands (sblas_hip_spmm_csr_ordered & co.)
+# ------------------------------------------------------------------------------------------
+COL_MAJOR, ROW_MAJOR = 0, 1
+
+
+def spmm_ordered(rows, cols, rowptr, colidx, val, B, ldb, order_b, n, alpha, beta, Cmat, ldc, order_c, workspace,
+                 stream=None, c_offset=0):
+    """sblas_hip_spmm_csr_ordered: C = alpha*A*B + beta*C with B and C each COL_MAJOR or ROW_MAJOR, in the tensors' own
+    value / index types (float64 / int32 runs the tuned kernels).  B, C: flat device tensors; c_offset: element offset
+    into Cmat.  workspace: any device tensor of at least spmm_typed_workspace_bytes(...) bytes (the same for every
+    order pair)."""
+    vt, it = _tags(val.dtype, rowptr.dtype)
+    nnz = int(colidx.numel())
+    rc = lib().sblas_hip_spmm_csr_ordered(
+        -1, _stream(stream), vt, it, rows, cols, nnz, _dev_ptr(rowptr, rowptr.dtype, "rowptr"),
+        _dev_ptr(colidx, rowptr.dtype, "colidx") if nnz else None, _dev_ptr(val, val.dtype, "val") if nnz else None,
+        _dev_ptr(B, val.dtype, "B") if cols else None, ldb, order_b, n, alpha, beta,
+        _dev_ptr(Cmat, val.dtype, "C") + Cmat.element_size() * c_offset, ldc, order_c,
+        _dev_ptr(workspace, workspace.dtype, "workspace") if workspace is not None and workspace.numel() else None,
+        workspace.numel() * workspace.element_size() if workspace is not None else 0)
+    check(rc, "sblas_hip_spmm_csr_ordered")
+
+
+def merge_rowblocks_ordered(comm, order, M, N, starts, nrows, partial, gather, alpha, beta, Cs, ldc, streams):
+    """merge_rowblocks_typed with C in either order (sblas_hip_merge_rowblocks_ordered).  ROW_MAJOR: C is row-major and
+    partial[q] holds an nrows[q] x N row-major block at leading dimension N."""
+    dt = Cs[0].dtype
+    vt, _ = _tags(dt, __import__("torch").int32)
+    g = len(partial)
+    st = (C.c_int64 * g)(*[int(v) for v in starts])
+    nr = (C.c_int64 * g)(*[int(v) for v in nrows])
+    ga = _typed_ptr_array(gather, dt, "gather", allow_none=True) if gather is not None else None
+    check(lib().sblas_hip_merge_rowblocks_ordered(comm, vt, order, M, N, st, nr,
+                                                  _typed_ptr_array(partial, dt, "partial", allow_none=True), ga, alpha, beta,
+                                                  _typed_ptr_array(Cs, dt, "C"), ldc, _stream_array(streams)),
+          "sblas_hip_merge_rowblocks_ordered")
+
+
+def _layout(t, rows, cols, what):
+    """(order, leading dimension) of a 2-D tensor view: strides (ld, 1) are row-major, (1, ld) column-major."""
+    if t.dim() != 2 or tuple(t.shape) != (rows, cols):
+        raise SblasError("%s must be a %d x %d tensor, got shape %s" % (what, rows, cols, tuple(t.shape)))
+    s0, s1 = t.stride()
+    if s1 == 1 and s0 >= max(cols, 1):
+        return ROW_MAJOR, s0
+    if s0 == 1 and s1 >= max(rows, 1):
+        return COL_MAJOR, s1
+    if rows <= 1 and s1 == 1:
+        return ROW_MAJOR, max(cols, 1)
+    if cols <= 1 and s0 == 1:
+        return COL_MAJOR, max(rows, 1)
+    raise SblasError("%s has strides %s: only (ld, 1) (row-major) or (1, ld) (column-major) views are supported" %
+                     (what, (s0, s1)))
+
+
+def _view_ptr(t, what):
+    import torch
+    if t.dtype != torch.float64:
+        raise SblasError("%s must be float64 (spmm_tensor handles float64 / int32 only; use spmm_ordered)" % what)
+    if not t.is_cuda:
+        raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+    return t.data_ptr()
+
+
+def spmm_tensor(A, B, C_, alpha, beta, workspace=None, plan=None, stream=None):
+    """C = alpha*A*B + beta*C on 2-D torch tensors, without a copy: each dense operand's order and leading dimension
+    come from its strides ((ld, 1) row-major, (1, ld) column-major), so contiguous tensors, .t() views and column slices
+    work as they are.  A = (rows, cols, rowptr, colidx, val); float64 values and int32 indices only.  workspace: None
+    (allocated here) or a device tensor of at least spmm_workspace_bytes(rows, cols, nnz, n) bytes; plan: an SpmmPlan
+    of A."""
+    import torch
+    rows, cols, rowptr, colidx, val = A
+    if val.dtype != torch.float64 or rowptr.dtype != torch.int32 or colidx.dtype != torch.int32:
+        raise SblasError("spmm_tensor handles float64 values and int32 indices only; use spmm_ordered for other types")
+    if B.dim() != 2 or C_.dim() != 2:
+        raise SblasError("B and C must be 2-D tensors")
+    n = int(C_.shape[1])
+    order_b, ldb = _layout(B, cols, n, "B")
+    order_c, ldc = _layout(C_, rows, n, "C")
+    pb, pc = _view_ptr(B, "B"), _view_ptr(C_, "C")
+    nnz = int(colidx.numel())
+    if workspace is None:
+        workspace = torch.empty((spmm_workspace_bytes(rows, cols, nnz, n) + 7) // 8, dtype=torch.float64, device=C_.device)
+    if not workspace.is_contiguous():
+        raise SblasError("workspace must be contiguous")
+    wptr = workspace.data_ptr() if workspace.numel() else None
+    wbytes = workspace.numel() * workspace.element_size()
+    L = lib()
+    ap = (_dev_ptr(rowptr, torch.int32, "rowptr"), _dev_ptr(colidx, torch.int32, "colidx") if nnz else None,
+          _dev_ptr(val, torch.float64, "val") if nnz else None)
+    if plan is not None:
+        if plan.rowptr.data_ptr() != rowptr.data_ptr() or plan.colidx.data_ptr() != colidx.data_ptr():
+            raise SblasError("the plan was made for another structure")
+        rc = L.sblas_hip_spmm_csr_ordered_f64_i32_planned(plan.handle, -1, _stream(stream), rows, cols, nnz, *ap,
+                                                          pb if cols else None, ldb, order_b, n, alpha, beta, pc, ldc, order_c,
+                                                          wptr, wbytes)
+        check(rc, "sblas_hip_spmm_csr_ordered_f64_i32_planned")
+    else:
+        rc = L.sblas_hip_spmm_csr_ordered(-1, _stream(stream), F64, I32, rows, cols, nnz, *ap, pb if cols else None, ldb,
+                                          order_b, n, alpha, beta, pc, ldc, order_c, wptr, wbytes)
+        check(rc, "sblas_hip_spmm_csr_ordered")
