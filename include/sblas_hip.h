@@ -96,6 +96,27 @@ int sblas_hip_spmm_plan_destroy(void *plan);
  * 1 row merging, 2 four rows per wave), [5] only the
  * block's column range of B is staged, [6] staged width, [7] rows per panel */
 int sblas_hip_spmm_plan_info(const void *plan, int64_t out[8]);
+/* A split plan: a plan as above whose very long rows are summed by many workgroups instead of one.  The direct kernels
+ * compute a row inside one workgroup, so a row of 10^5-10^6 entries keeps one CU busy while the rest of the chip waits.
+ * sblas_hip_spmm_plan_create_split makes the plan above, copies rowptr and the panel verdicts to the host once, and
+ * cuts every row of split_min+ entries in a panel the direct kernels own (sblas_spmm_split_classify below) into pieces
+ * of at most `piece` entries (split_min / piece <= 0: SBLAS_SPMM_SPLIT_MIN / SBLAS_SPMM_SPLIT_PIECE).  A planned call
+ * launches the direct kernels in a form that leaves those rows alone, then one workgroup per piece and column tile
+ * (sums into a partial row in the plan's buffer) and a fold kernel that adds a row's partials in piece order.
+ *   - create / destroy allocate and synchronise `stream`; a planned call allocates nothing, never synchronises and may
+ *     be captured in a graph, whatever the orders of B and C and however n is cut into column chunks;
+ *   - one call at a time per plan (the partial sums live in the plan's buffer);
+ *   - results: every row that is not split is bit-identical to the plain plan's; a split row is summed in another order
+ *     (pieces, then the pieces in order, no atomics), so its last bits can differ -- the same on every call;
+ *   - not split: rows of panels the LDS-tiled, lane-group or matrix-core kernels own, every row when the row-merging
+ *     kernel takes the direct panels, and every row of an inactive plan (info[0] = 0);
+ *   - a plan without split rows is the plain plan: the same kernels, the same bits. */
+int sblas_hip_spmm_plan_create_split(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                     const int32_t *rowptr, const int32_t *colidx, int64_t n, int64_t split_min,
+                                     int64_t piece, void **plan_out);
+/* out: [0] split rows, [1] pieces, [2] nonzeros in split rows, [3] bytes of the partial-sum buffer (pieces x staged
+ * width x 8).  All zero for a plan made by sblas_hip_spmm_plan_create. */
+int sblas_hip_spmm_plan_split_info(const void *plan, int64_t out[4]);
 int sblas_hip_spmm_csr_f64_i32_planned(const void *plan, int dev, void *stream,
                                        int64_t rows, int64_t cols, int64_t nnz,
                                        const int32_t *rowptr, const int32_t *colidx, const double *val,
@@ -307,6 +328,19 @@ int sblas_partition_dense(int64_t first_order, int n_gpu, int i_gpu,
 #define SBLAS_SPMV_SPLIT_PIECE 4096  /* default nonzeros per piece (one 256-thread workgroup)        */
 int64_t sblas_spmv_plan_classify(const int32_t *rowptr, int64_t rows, int64_t nnz, int64_t split_min, int64_t piece,
                                  int32_t *items, int64_t max_items);
+
+/* The split SpMM plan's classifier (sblas_hip_spmm_plan_create_split runs it on host copies of rowptr and the panel
+ * verdicts).  A row is split when it has at least split_min nonzeros and its panel is one the plan gives to the direct
+ * kernels: direct_mask holds one byte per panel of panel_rows rows (nonzero: direct), NULL means every panel.  A split
+ * row of len nonzeros becomes ceil(len / piece) pieces of consecutive nonzeros, at most `piece` each.  Records of four
+ * int32: first the pieces {row, first nonzero, end, partial slot} with slots 0, 1, .. in row order (the pieces of a row
+ * consecutive, in CSR order), then one record per split row {row, first slot, pieces, -1}.  split_min / piece <= 0
+ * take the defaults below.  Writes up to max_out records when `out` is not NULL and returns the number of records
+ * (pieces + split rows), or -1 (bad argument, row pointers descending or outside [0, nnz]). */
+#define SBLAS_SPMM_SPLIT_MIN 16384   /* default: rows of this many nonzeros or more are split        */
+#define SBLAS_SPMM_SPLIT_PIECE 4096  /* default nonzeros per piece (one 1024-thread workgroup)       */
+int64_t sblas_spmm_split_classify(const int32_t *rowptr, int64_t rows, int64_t nnz, int64_t split_min, int64_t piece,
+                                  const uint8_t *direct_mask, int64_t panel_rows, int32_t *out, int64_t max_out);
 
 /* Dense initialiser of the reference's DenseMatrix(h, w, order) / DenseVector(len) constructors (matrix.h:519-528,
  * :663-672; utility.h:197; config.h:23 seed 211): srand(seed), then rand() / RAND_MAX in storage order (host memory). */

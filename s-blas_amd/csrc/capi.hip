@@ -7,6 +7,7 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 #include "../../include/sblas_hip.h"
 #include "kernels.h"
 
@@ -226,6 +227,7 @@ struct SpmmPlan {
     const void *rowptr = nullptr, *colidx = nullptr;
     bool active = false;      // false: nothing to plan (empty matrix, a pinned direct variant): calls run unplanned
     void *buf = nullptr;
+    void *split_buf = nullptr; // a split plan's partial sums, row bitmap, pieces and split rows
     sblas::PlanView pv;
 };
 
@@ -320,8 +322,71 @@ int sblas_hip_spmm_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t cols
 }
 
 // ---- per-matrix plan (the slot of cusparseSpMM_bufferSize / preprocess, spmm.h:134-141) --------------------------
-int sblas_hip_spmm_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
-                               const int32_t *colidx, int64_t n, void **plan_out)
+static int spmm_plan_fail(SpmmPlan *p, void **plan_out, int rc)
+{
+    if (p->buf) (void)hipFree(p->buf);
+    if (p->split_buf) (void)hipFree(p->split_buf);
+    delete p;
+    *plan_out = nullptr;
+    return rc;
+}
+
+// A split plan's long rows (sblas_hip_spmm_plan_create_split): the classifier on host copies of rowptr and the panel
+// verdicts, then one device buffer -- partial sums, row bitmap, pieces, split rows.
+static hipError_t spmm_plan_split(SpmmPlan *p, hipStream_t s, const int32_t *rowptr, const std::vector<int> &cls,
+                                  int64_t split_min, int64_t piece, bool *bad_rowptr)
+{
+    sblas::PlanView &pv = p->pv;
+    const int64_t rows = p->rows;
+    std::vector<int32_t> rp((size_t)rows + 1);
+    hipError_t e = hipMemcpyAsync(rp.data(), rowptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    // the panels the direct kernels own; none when the row-merging kernel takes them
+    std::vector<uint8_t> mask(cls.size());
+    for (size_t q = 0; q < cls.size(); ++q) mask[q] = !pv.merge && (cls[q] & sblas::PANEL_CLASS_MASK) == sblas::PANEL_DIRECT;
+    const int64_t n_rec = sblas_spmm_split_classify(rp.data(), rows, p->nnz, split_min, piece, mask.data(), pv.info_rows, nullptr, 0);
+    if (n_rec < 0) {
+        *bad_rowptr = true;
+        return hipSuccess;
+    }
+    if (n_rec == 0) return hipSuccess; // nothing to split: the plain plan
+    std::vector<int4> rec((size_t)n_rec);
+    if (sblas_spmm_split_classify(rp.data(), rows, p->nnz, split_min, piece, mask.data(), pv.info_rows,
+                                  reinterpret_cast<int32_t *>(rec.data()), n_rec) != n_rec) {
+        *bad_rowptr = true;
+        return hipSuccess;
+    }
+    int64_t n_pieces = 0;
+    while (n_pieces < n_rec && rec[(size_t)n_pieces].w >= 0) ++n_pieces;
+    const int64_t n_split = n_rec - n_pieces;
+    const size_t words = ((size_t)rows + 31) / 32;
+    std::vector<unsigned> bits(words, 0u);
+    int64_t split_nnz = 0;
+    for (int64_t i = n_pieces; i < n_rec; ++i) {
+        const int r = rec[(size_t)i].x;
+        bits[(size_t)r / 32] |= 1u << (r % 32);
+        split_nnz += (int64_t)rp[(size_t)r + 1] - rp[(size_t)r];
+    }
+    const size_t partial_bytes = (size_t)n_pieces * (size_t)p->ldbt * sizeof(double);
+    const size_t bits_bytes = (words * sizeof(unsigned) + 15) / 16 * 16;
+    if ((e = hipMalloc(&p->split_buf, partial_bytes + bits_bytes + (size_t)n_rec * sizeof(int4))) != hipSuccess) return e;
+    char *base = static_cast<char *>(p->split_buf);
+    pv.partial = reinterpret_cast<double *>(base);
+    pv.split_bits = reinterpret_cast<const unsigned *>(base + partial_bytes);
+    pv.pieces = reinterpret_cast<const int4 *>(base + partial_bytes + bits_bytes);
+    pv.srows = pv.pieces + n_pieces;
+    if ((e = hipMemcpyAsync(base + partial_bytes, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(base + partial_bytes + bits_bytes, rec.data(), (size_t)n_rec * sizeof(int4), hipMemcpyHostToDevice, s)) !=
+        hipSuccess)
+        return e;
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e; // (the host images go next)
+    pv.n_pieces = n_pieces, pv.n_split = n_split, pv.split_nnz = split_nnz;
+    return hipSuccess;
+}
+
+static int spmm_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                            const int32_t *colidx, int64_t n, bool split, int64_t split_min, int64_t piece, void **plan_out)
 {
     if (!plan_out || !csr_args_ok(rows, cols, nnz, rowptr, colidx, reinterpret_cast<const void *>(1)) || n < 0) return SBLAS_E_INVALID;
     SpmmPlan *p = new SpmmPlan;
@@ -335,31 +400,56 @@ int sblas_hip_spmm_plan_create(int dev, void *stream, int64_t rows, int64_t cols
     if (ldbt < 64 && ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull) return SBLAS_OK; // 64-bit narrow kernels: unplanned
     if (!sblas::classify_worthwhile(rows, nnz, ldbt)) return SBLAS_OK; // short rows at a width of 64 columns or fewer: nothing is classified
     DeviceScope scope(dev);
-    if (scope.err != hipSuccess) { delete p; *plan_out = nullptr; return SBLAS_E_HIP; }
-    if (hipMalloc(&p->buf, sblas::plan_tail_bytes(rows)) != hipSuccess) { delete p; *plan_out = nullptr; return SBLAS_E_HIP; }
+    if (scope.err != hipSuccess) return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (hipMalloc(&p->buf, sblas::plan_tail_bytes(rows)) != hipSuccess) return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
     p->pv.tail = static_cast<int *>(p->buf);
     p->ldbt = ldbt;
     const int sr = sblas::options().stage_range;
     const bool use_range = ldbt >= 64 && (sr > 0 || (sr < 0 && range_staging_pays(rows, cols, nnz, ldbt)));
-    if (sblas::plan_build((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, ldbt, v, use_range, &p->pv) != hipSuccess) {
-        (void)hipFree(p->buf);
-        delete p;
-        *plan_out = nullptr;
-        return SBLAS_E_HIP;
+    std::vector<int> cls;
+    if (sblas::plan_build((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, ldbt, v, use_range, &p->pv,
+                          split ? &cls : nullptr) != hipSuccess)
+        return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (split) {
+        bool bad = false;
+        if (spmm_plan_split(p, (hipStream_t)stream, rowptr, cls, split_min, piece, &bad) != hipSuccess)
+            return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
+        if (bad) return spmm_plan_fail(p, plan_out, SBLAS_E_INVALID); // row pointers descending or outside [0, nnz]
     }
     p->active = true;
     return SBLAS_OK;
+}
+
+int sblas_hip_spmm_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                               const int32_t *colidx, int64_t n, void **plan_out)
+{
+    return spmm_plan_create(dev, stream, rows, cols, nnz, rowptr, colidx, n, false, 0, 0, plan_out);
+}
+
+int sblas_hip_spmm_plan_create_split(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                                     const int32_t *colidx, int64_t n, int64_t split_min, int64_t piece, void **plan_out)
+{
+    return spmm_plan_create(dev, stream, rows, cols, nnz, rowptr, colidx, n, true, split_min, piece, plan_out);
 }
 
 int sblas_hip_spmm_plan_destroy(void *plan)
 {
     if (!plan) return SBLAS_OK;
     SpmmPlan *p = static_cast<SpmmPlan *>(plan);
-    if (p->buf) {
+    if (p->buf || p->split_buf) {
         DeviceScope scope(p->dev);
-        (void)hipFree(p->buf);
+        if (p->buf) (void)hipFree(p->buf);
+        if (p->split_buf) (void)hipFree(p->split_buf);
     }
     delete p;
+    return SBLAS_OK;
+}
+
+int sblas_hip_spmm_plan_split_info(const void *plan, int64_t out[4])
+{
+    if (!plan || !out) return SBLAS_E_INVALID;
+    const SpmmPlan *p = static_cast<const SpmmPlan *>(plan);
+    out[0] = p->pv.n_split, out[1] = p->pv.n_pieces, out[2] = p->pv.split_nnz, out[3] = p->pv.n_pieces * p->ldbt * (int64_t)sizeof(double);
     return SBLAS_OK;
 }
 

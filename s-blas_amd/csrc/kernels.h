@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 namespace sblas {
 
@@ -102,11 +103,19 @@ struct PlanView {
     bool four_rows = false;     // ... to the four-rows-per-wave kernel (128+ staged columns)
     bool use_range = false;     // stage only the column range [lo, hi] of B
     int nparts = 0;
+    // a split plan's long rows (sblas_hip_spmm_plan_create_split; all null / 0 otherwise): one bit per row, the pieces
+    // {row, first nonzero, end, partial slot}, the split rows {row, first slot, pieces, -1} and one partial row of ldbt
+    // doubles per piece, in the plan's device buffer
+    const unsigned *split_bits = nullptr;
+    const int4 *pieces = nullptr, *srows = nullptr;
+    double *partial = nullptr;
+    int64_t n_pieces = 0, n_split = 0, split_nnz = 0;
 };
 size_t plan_tail_bytes(int64_t rows);
 bool classify_worthwhile(int64_t rows, int64_t nnz, int64_t ldbt);
+// cls_out (optional): the panel verdicts, one class word per panel of pv->info_rows rows, as the host read them
 hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx, int64_t ldbt,
-                      int variant, bool use_range, PlanView *pv);
+                      int variant, bool use_range, PlanView *pv, std::vector<int> *cls_out = nullptr);
 // Layouts of the dense operands: row_b = B is row-major (cols x n, B[k * ldb + j]; only the staging launchers read B),
 // row_c = C is row-major (rows x n, C[r * ldc + j]; the stage-2 epilogues, the scale and the merge kernels).
 hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,

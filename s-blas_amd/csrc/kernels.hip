@@ -739,6 +739,11 @@ __device__ __forceinline__ bool owns_window(const int *__restrict__ tail, const 
     const int c = cls[p] & PANEL_CLASS_MASK;
     return c == PANEL_WINDOW || (c == PANEL_MFMA_W && b_nonfinite(tail));
 }
+// a split plan's row bitmap (one bit per row, PlanView::split_bits): row r is computed by the split kernels
+__device__ __forceinline__ bool is_split_row(const unsigned *__restrict__ bits, int r)
+{
+    return (bits[r >> 5] >> (r & 31)) & 1u;
+}
 
 typedef int sblas_rsrc_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ sblas_rsrc_t make_rsrc(const void *p, unsigned stride, unsigned records)
@@ -1559,18 +1564,80 @@ __global__ __launch_bounds__(1024, (NC == 8 && CP == 1 && G == 1) ? 8 : 4) void 
                  : [gv] "v"(gv), [x0] "v"(B0.x), [y0] "v"(B0.y), [x1] "v"(B1.x), [y1] "v"(B1.y), [x2] "v"(B2.x),    \
                    [y2] "v"(B2.y), [x3] "v"(B3.x), [y3] "v"(B3.y))
 
+// The row-per-wave sweep: entries [p0, p1) of one row into (acc0, acc1), this lane's two columns of the tile (lb: their
+// byte offset in a Bt row; sub = lane & 15, half = which of the GROUPS nonzeros of a step the lane works on).  Shared by
+// spmm_direct_dpp_kernel and the pieces of split rows (spmm_split_piece_kernel).  Plain pointers: the kernels' __restrict__
+// parameters carry the aliasing facts, and __restrict__ here would reschedule the row-per-wave kernel.
+template <int GROUPS>
+__device__ __forceinline__ void dpp_sweep(const int *colidx, const double *val, const char *bt_bytes, unsigned ldb8,
+                                          unsigned lb, unsigned zero_off, int lane, int sub, int half, int p0, int p1,
+                                          double &acc0, double &acc1)
+{
+    constexpr int PER_STEP = 16 * GROUPS; // nonzeros handled by one 16-slot sweep
+    for (int p = p0; p < p1; p += WAVE) {
+        const int mine = p + lane;
+        int cj = 0;
+        double vj = 0.0;
+        if (mine < p1) {
+            cj = colidx[mine];
+            vj = val[mine];
+        }
+        const int cnt = min(WAVE, p1 - p);
+        for (int g0 = 0; g0 < cnt; g0 += PER_STEP) {
+            // slot `sub` of my DPP row takes chunk entry e
+            const int e = g0 + half * 16 + sub;
+            const int src = e << 2;
+            const int gc = __builtin_amdgcn_ds_bpermute(src, cj);
+            const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(vj));
+            const int hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(vj));
+            const bool on = e < cnt;
+            const unsigned co = on ? (unsigned)gc * ldb8 : zero_off;
+            const double gv = on ? __hiloint2double(hi, lo) : 0.0;
+            const int ng = min(16, cnt - g0); // live slots of the lower half's rows (>= the upper half's)
+            unsigned o0, o1, o2, o3, o4, o5, o6, o7;
+            double2 b0, b1, b2, b3, b4, b5, b6, b7;
+#define SBLAS_LD(O) (*reinterpret_cast<const double2 *>(bt_bytes + (O)))
+            SBLAS_DPP_OFF4(0, 1, 2, 3, o0, o1, o2, o3);
+            b0 = SBLAS_LD(o0); b1 = SBLAS_LD(o1); b2 = SBLAS_LD(o2); b3 = SBLAS_LD(o3);
+            if (ng > 4) {
+                SBLAS_DPP_OFF4(4, 5, 6, 7, o4, o5, o6, o7);
+                b4 = SBLAS_LD(o4); b5 = SBLAS_LD(o5); b6 = SBLAS_LD(o6); b7 = SBLAS_LD(o7);
+                SBLAS_DPP_FMA4x2(0, 1, 2, 3, b0, b1, b2, b3);
+                if (ng > 8) {
+                    SBLAS_DPP_OFF4(8, 9, 10, 11, o0, o1, o2, o3);
+                    b0 = SBLAS_LD(o0); b1 = SBLAS_LD(o1); b2 = SBLAS_LD(o2); b3 = SBLAS_LD(o3);
+                    SBLAS_DPP_FMA4x2(4, 5, 6, 7, b4, b5, b6, b7);
+                    if (ng > 12) {
+                        SBLAS_DPP_OFF4(12, 13, 14, 15, o4, o5, o6, o7);
+                        b4 = SBLAS_LD(o4); b5 = SBLAS_LD(o5); b6 = SBLAS_LD(o6); b7 = SBLAS_LD(o7);
+                        SBLAS_DPP_FMA4x2(8, 9, 10, 11, b0, b1, b2, b3);
+                        SBLAS_DPP_FMA4x2(12, 13, 14, 15, b4, b5, b6, b7);
+                    } else {
+                        SBLAS_DPP_FMA4x2(8, 9, 10, 11, b0, b1, b2, b3);
+                    }
+                } else {
+                    SBLAS_DPP_FMA4x2(4, 5, 6, 7, b4, b5, b6, b7);
+                }
+            } else {
+                SBLAS_DPP_FMA4x2(0, 1, 2, 3, b0, b1, b2, b3);
+            }
+#undef SBLAS_LD
+        }
+    }
+}
+
 // GROUPS = 1: 128-column tile, one nonzero per instruction; 2: 64 columns, two nonzeros; 4: 32 columns, four (one per
-// DPP row) -- n <= 32 runs on the 64-column staging copy and reads the first half of every Bt row
-template <int GROUPS, bool RC>
+// DPP row) -- n <= 32 runs on the 64-column staging copy and reads the first half of every Bt row.
+// SKIP: a split plan's call -- the rows marked in `split_bits` are left to the split kernels (neither swept nor written).
+template <int GROUPS, bool RC, bool SKIP = false>
 __global__ __launch_bounds__(WIDE_WAVES * 64) void spmm_direct_dpp_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
     double *__restrict__ C, int64_t ldc, const int *__restrict__ tail, const int *__restrict__ cls,
-    int info_panel_rows, int interleave, int epoch, int long_min)
+    int info_panel_rows, int interleave, int epoch, int long_min, const unsigned *__restrict__ split_bits = nullptr)
 {
     static_assert(GROUPS == 1 || GROUPS == 2 || GROUPS == 4, "lane groups of 64, 32 or 16 lanes");
     constexpr int TILE_COLS = 128 / GROUPS;
-    constexpr int PER_STEP = 16 * GROUPS; // nonzeros handled by one 16-slot sweep
     constexpr int GLANES = 64 / GROUPS;   // lanes that share a nonzero
     __shared__ double ctile[TILE_COLS][WIDE_PANEL + 1];
     // every panel windowed (the bench matrix): one scalar load of one shared address and out, instead of two
@@ -1601,6 +1668,7 @@ __global__ __launch_bounds__(WIDE_WAVES * 64) void spmm_direct_dpp_kernel(
         mine = owns_direct(tail, cls, row / info_panel_rows);
         if (mine && lane == 0 && blockIdx.y == 0 && row % info_panel_rows == 0) atomicAdd(&g_panel_stats[1], 1ull);
     }
+    if (SKIP && mine) mine = !is_split_row(split_bits, row);
     const int sub = lane & 15;
     const int half = lane / GLANES; // which of the GROUPS nonzeros of a step this lane works on
     const unsigned ldb8 = (unsigned)ldbt * 8u;                                       // bytes per Bt row
@@ -1609,59 +1677,7 @@ __global__ __launch_bounds__(WIDE_WAVES * 64) void spmm_direct_dpp_kernel(
     const char *__restrict__ bt_bytes = reinterpret_cast<const char *>(Bt);
 
     double acc0 = 0.0, acc1 = 0.0;
-    // entries [p0, p1) of one row into (acc0, acc1)
-    auto sweep = [&](int p0, int p1) {
-        for (int p = p0; p < p1; p += WAVE) {
-            const int mine = p + lane;
-            int cj = 0;
-            double vj = 0.0;
-            if (mine < p1) {
-                cj = colidx[mine];
-                vj = val[mine];
-            }
-            const int cnt = min(WAVE, p1 - p);
-            for (int g0 = 0; g0 < cnt; g0 += PER_STEP) {
-                // slot `sub` of my DPP row takes chunk entry e
-                const int e = g0 + half * 16 + sub;
-                const int src = e << 2;
-                const int gc = __builtin_amdgcn_ds_bpermute(src, cj);
-                const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(vj));
-                const int hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(vj));
-                const bool on = e < cnt;
-                const unsigned co = on ? (unsigned)gc * ldb8 : zero_off;
-                const double gv = on ? __hiloint2double(hi, lo) : 0.0;
-                const int ng = min(16, cnt - g0); // live slots of the lower half's rows (>= the upper half's)
-                unsigned o0, o1, o2, o3, o4, o5, o6, o7;
-                double2 b0, b1, b2, b3, b4, b5, b6, b7;
-#define SBLAS_LD(O) (*reinterpret_cast<const double2 *>(bt_bytes + (O)))
-                SBLAS_DPP_OFF4(0, 1, 2, 3, o0, o1, o2, o3);
-                b0 = SBLAS_LD(o0); b1 = SBLAS_LD(o1); b2 = SBLAS_LD(o2); b3 = SBLAS_LD(o3);
-                if (ng > 4) {
-                    SBLAS_DPP_OFF4(4, 5, 6, 7, o4, o5, o6, o7);
-                    b4 = SBLAS_LD(o4); b5 = SBLAS_LD(o5); b6 = SBLAS_LD(o6); b7 = SBLAS_LD(o7);
-                    SBLAS_DPP_FMA4x2(0, 1, 2, 3, b0, b1, b2, b3);
-                    if (ng > 8) {
-                        SBLAS_DPP_OFF4(8, 9, 10, 11, o0, o1, o2, o3);
-                        b0 = SBLAS_LD(o0); b1 = SBLAS_LD(o1); b2 = SBLAS_LD(o2); b3 = SBLAS_LD(o3);
-                        SBLAS_DPP_FMA4x2(4, 5, 6, 7, b4, b5, b6, b7);
-                        if (ng > 12) {
-                            SBLAS_DPP_OFF4(12, 13, 14, 15, o4, o5, o6, o7);
-                            b4 = SBLAS_LD(o4); b5 = SBLAS_LD(o5); b6 = SBLAS_LD(o6); b7 = SBLAS_LD(o7);
-                            SBLAS_DPP_FMA4x2(8, 9, 10, 11, b0, b1, b2, b3);
-                            SBLAS_DPP_FMA4x2(12, 13, 14, 15, b4, b5, b6, b7);
-                        } else {
-                            SBLAS_DPP_FMA4x2(8, 9, 10, 11, b0, b1, b2, b3);
-                        }
-                    } else {
-                        SBLAS_DPP_FMA4x2(4, 5, 6, 7, b4, b5, b6, b7);
-                    }
-                } else {
-                    SBLAS_DPP_FMA4x2(0, 1, 2, 3, b0, b1, b2, b3);
-                }
-#undef SBLAS_LD
-            }
-        }
-    };
+    auto sweep = [&](int p0, int p1) { dpp_sweep<GROUPS>(colidx, val, bt_bytes, ldb8, lb, zero_off, lane, sub, half, p0, p1, acc0, acc1); };
     // Skewed matrices: a row of tens of thousands of entries would keep ONE wave busy while the other fifteen of the
     // workgroup -- and, at the tail of the launch, the whole chip -- wait for it.  Rows of DPP_LONG+ entries are set
     // aside and computed by all sixteen waves together afterwards (each wave a slice of whole 64-entry chunks, the
@@ -1919,7 +1935,7 @@ __global__ __launch_bounds__(MERGE_WAVES * 64) void spmm_direct_merge_kernel(
 // works on 64/G rows at once and every lane fetches its row's (col, val) itself (the G lanes of a
 // group read the same address, which the memory pipeline serves as one request).
 // ---------------------------------------------------------------------------------------------
-template <int G, bool RC>
+template <int G, bool RC, bool SKIP = false> // SKIP: rows marked in split_bits are not computed (spmm_direct_dpp_kernel)
 __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, const int *__restrict__ rowptr,
                                                                   const int *__restrict__ colidx,
                                                                   const double *__restrict__ val,
@@ -1928,7 +1944,7 @@ __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, con
                                                                   double *__restrict__ C, int64_t ldc,
                                                                   const int *__restrict__ tail,
                                                                   const int *__restrict__ cls, int info_panel_rows,
-                                                                  int epoch)
+                                                                  int epoch, const unsigned *__restrict__ split_bits = nullptr)
 {
     constexpr int GROUPS = 256 / G;
     constexpr int RPG = PANEL_ROWS / GROUPS; // rows per group
@@ -1947,6 +1963,7 @@ __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, con
             mine = owns_direct(tail, cls, row / info_panel_rows);
             if (mine && l == 0 && row % info_panel_rows == 0) atomicAdd(&g_panel_stats[1], 1ull);
         }
+        if (SKIP && mine) mine = !is_split_row(split_bits, row);
         if (mine) {
             const int p0 = rowptr[row], p1 = rowptr[row + 1];
             int p = p0;
@@ -1986,12 +2003,12 @@ __global__ __launch_bounds__(256) void spmm_rowpanel_narrow_kernel(int rows, con
 // from 128 staged columns on wherever the classifier's vote prefers it to a row per wave (classify_panel).
 // ---------------------------------------------------------------------------------------------
 constexpr int ROWS_LONG = 512; // entries from which a row is computed by the whole workgroup
-template <int WV, bool RC> // waves per workgroup (4 WV rows); C row-major
+template <int WV, bool RC, bool SKIP = false> // waves per workgroup (4 WV rows); C row-major; SKIP as spmm_direct_dpp_kernel
 __global__ __launch_bounds__(WV * 64) void spmm_direct_rows_kernel(
     int rows, int cols, int npanels, const int *__restrict__ rowptr, const int *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ Bt, int64_t ldbt, int n, double alpha, double beta,
     double *__restrict__ C, int64_t ldc, const int *__restrict__ tail, const int *__restrict__ cls,
-    int info_panel_rows, int interleave, int epoch, int voted)
+    int info_panel_rows, int interleave, int epoch, int voted, const unsigned *__restrict__ split_bits = nullptr)
 {
     constexpr int ROWS_PANEL = 4 * WV;
     __shared__ double ctile[64][ROWS_PANEL + 1];
@@ -2018,6 +2035,7 @@ __global__ __launch_bounds__(WV * 64) void spmm_direct_rows_kernel(
         mine = owns_direct(tail, cls, row / info_panel_rows);
         if (mine && k == 0 && blockIdx.y == 0 && row % info_panel_rows == 0) atomicAdd(&g_panel_stats[1], 1ull);
     }
+    if (SKIP && mine) mine = !is_split_row(split_bits, row);
     const unsigned ldb8 = (unsigned)ldbt * 8u;
     const unsigned lb = (unsigned)(col0 * 8) + (unsigned)k * 16u; // columns 2k, 2k+1 (and 32+2k, 33+2k at +256 bytes)
     const unsigned zero_off = (unsigned)cols * ldb8;
@@ -2123,14 +2141,15 @@ __global__ __launch_bounds__(WV * 64) void spmm_direct_rows_kernel(
 // nonzero and keeps eight partial sums; the eight sums are folded across the wave by a halving exchange (4 + 2 + 1
 // shuffles, then three more: ten instead of 48) and lanes 0, 8, .., 56 write columns 0..7.
 // ---------------------------------------------------------------------------------------------
-template <bool RC>
+template <bool RC, bool SKIP = false> // SKIP as spmm_direct_dpp_kernel
 __global__ __launch_bounds__(256) void spmm_rows8_kernel(int rows, int cols, const int *__restrict__ rowptr,
                                                         const int *__restrict__ colidx,
                                                         const double *__restrict__ val,
                                                         const double *__restrict__ Bt, int n, double alpha,
                                                         double beta, double *__restrict__ C, int64_t ldc,
                                                         const int *__restrict__ tail, const int *__restrict__ cls,
-                                                        int info_panel_rows, int epoch)
+                                                        int info_panel_rows, int epoch,
+                                                        const unsigned *__restrict__ split_bits = nullptr)
 {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + wave_uniform(threadIdx.x >> 6);
@@ -2139,6 +2158,7 @@ __global__ __launch_bounds__(256) void spmm_rows8_kernel(int rows, int cols, con
         if (nothing_direct(tail, epoch) || !owns_direct(tail, cls, row / info_panel_rows)) return;
         if (lane == 0 && row % info_panel_rows == 0) atomicAdd(&g_panel_stats[1], 1ull);
     }
+    if (SKIP && is_split_row(split_bits, row)) return;
     const int p0 = wave_uniform(rowptr[row]), p1 = wave_uniform(rowptr[row + 1]);
     double a[8];
 #pragma unroll
@@ -2202,6 +2222,84 @@ __global__ __launch_bounds__(256) void spmm_rows8_kernel(int rows, int cols, con
         const double r = alpha * s;
         *dst = (beta == 0.0) ? r : fma(beta, *dst, r);
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Split rows of a split plan (sblas_hip_spmm_plan_create_split): a row of split_min+ entries in a panel of the direct
+// kernels is cut into pieces of consecutive entries (csrc/spmm_split.cpp).  The direct kernels' SKIP instantiations leave
+// such rows alone; one workgroup per (piece, column tile) sums a piece -- each of its sixteen waves a slice of whole
+// 64-entry chunks through the row-per-wave sweep, the wave sums added in LDS in wave order -- into the piece's partial
+// row (ldbt doubles in the plan's buffer), and the fold kernel adds the partials of a row in piece order and applies
+// alpha / beta.  No atomics, no waiting between workgroups: the kernel boundary hands the partials over, and every call
+// sums in the same order.  Tiles as in spmm_direct_dpp_kernel: GROUPS = 1 for 128-column tiles, 2 for 64 staged columns,
+// 4 for 8 / 16 / 32 (a 32-column sweep; with fewer staged columns the upper lanes of a DPP row read on into the next
+// Bt rows -- and past the all-zero row into the workspace tail -- and their sums are never stored).
+// ---------------------------------------------------------------------------------------------
+// Reading on past the all-zero row stays inside the workspace: the tail behind Bt (workspace_tail_bytes) is longer than
+// the 24 doubles a 32-column sweep over an 8-column Bt row reaches beyond it.
+static_assert(TAIL_HDR * sizeof(int) + TAIL_PARTS * sizeof(int2) >= (32 - 8) * sizeof(double),
+              "the workspace tail must cover the 32-column sweep's reads past the last Bt row");
+template <int GROUPS>
+__global__ __launch_bounds__(WIDE_WAVES * 64) void spmm_split_piece_kernel(const int4 *__restrict__ pieces, int cols,
+                                                                          const int *__restrict__ colidx,
+                                                                          const double *__restrict__ val,
+                                                                          const double *__restrict__ Bt, int64_t ldbt,
+                                                                          int n, double *__restrict__ partial)
+{
+    constexpr int TILE_COLS = 128 / GROUPS;
+    constexpr int GLANES = 64 / GROUPS;
+    __shared__ double lpart[WIDE_WAVES][TILE_COLS];
+    const int4 pc = pieces[blockIdx.x]; // {row, first nonzero, end, partial slot}
+    const int lane = threadIdx.x & 63;
+    const int wave = wave_uniform(threadIdx.x >> 6);
+    const int col0 = blockIdx.y * TILE_COLS;
+    const int sub = lane & 15;
+    const int half = lane / GLANES;
+    const unsigned ldb8 = (unsigned)ldbt * 8u;
+    const unsigned lb = (unsigned)(col0 * 8) + (unsigned)(lane % GLANES) * 16u;
+    const unsigned zero_off = (unsigned)cols * ldb8;
+    const int pa = wave_uniform(pc.y), pb = wave_uniform(pc.z);
+    const int slice = ((pb - pa + WIDE_WAVES - 1) / WIDE_WAVES + 63) & ~63; // whole 64-entry chunks per wave
+    const int s0 = min(pa + wave * slice, pb), s1 = min(s0 + slice, pb);
+    double acc0 = 0.0, acc1 = 0.0;
+    dpp_sweep<GROUPS>(colidx, val, reinterpret_cast<const char *>(Bt), ldb8, lb, zero_off, lane, sub, half, s0, s1, acc0, acc1);
+    if (GROUPS == 4) {
+        acc0 += __shfl_xor(acc0, 16, WAVE);
+        acc1 += __shfl_xor(acc1, 16, WAVE);
+    }
+    if (GROUPS >= 2) {
+        acc0 += __shfl_xor(acc0, 32, WAVE);
+        acc1 += __shfl_xor(acc1, 32, WAVE);
+    }
+    if (lane < GLANES) {
+        lpart[wave][2 * lane] = acc0;
+        lpart[wave][2 * lane + 1] = acc1;
+    }
+    __syncthreads();
+    const int ncols = min(TILE_COLS, n - col0);
+    if ((int)threadIdx.x < ncols) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < WIDE_WAVES; ++w) t += lpart[w][threadIdx.x];
+        partial[(int64_t)pc.w * ldbt + col0 + threadIdx.x] = t;
+    }
+}
+
+// one thread per (split row, column): the row's partials in piece order, then alpha / beta (beta == 0: C is not read)
+template <bool RC>
+__global__ __launch_bounds__(256) void spmm_split_fold_kernel(const int4 *__restrict__ srows, const double *__restrict__ partial,
+                                                             int64_t ldbt, int n, double alpha, double beta,
+                                                             double *__restrict__ C, int64_t ldc)
+{
+    const int4 sr = srows[blockIdx.x]; // {row, first slot, pieces, -1}
+    const int j = blockIdx.y * 256 + threadIdx.x;
+    if (j >= n) return;
+    const double *__restrict__ q = partial + (int64_t)sr.y * ldbt + j;
+    double t = 0.0;
+    for (int k = 0; k < sr.z; ++k) t += q[(int64_t)k * ldbt];
+    double *dst = RC ? C + (int64_t)sr.x * ldc + j : C + (int64_t)j * ldc + sr.x;
+    const double sres = alpha * t;
+    *dst = (beta == 0.0) ? sres : fma(beta, *dst, sres);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2546,6 +2644,8 @@ static Tail tail_at(int *hdr, int rows)
     t.cls = reinterpret_cast<int *>(t.info + panels);
     return t;
 }
+// (the tail follows Bt in every workspace: the 32-column sweeps over 8 / 16 staged columns -- spmm_direct_dpp_kernel<4>,
+//  spmm_split_piece_kernel<4> -- read up to 24 doubles past Bt's last row into it; see the static_assert there)
 size_t workspace_tail_bytes(int64_t rows)
 {
     const size_t panels = ((size_t)(rows > 0 ? rows : 0) + SPMM_MIN_PANEL_ROWS - 1) / SPMM_MIN_PANEL_ROWS;
@@ -2708,7 +2808,7 @@ hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const d
 size_t plan_tail_bytes(int64_t rows) { return workspace_tail_bytes(rows); }
 
 hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx, int64_t ldbt,
-                      int variant, bool use_range, PlanView *pv)
+                      int variant, bool use_range, PlanView *pv, std::vector<int> *cls_out)
 {
     const Tail t = tail_at(pv->tail, rows);
     int info_rows = 0, g = 2;
@@ -2751,6 +2851,7 @@ hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int 
     pv->four_rows = ldbt >= 128 && !pv->merge && hdr[TAIL_ROWS_EPOCH] == epoch;
     pv->use_range = use_range;
     pv->nparts = nparts;
+    if (cls_out) cls_out->swap(cls);
     return hipSuccess;
 }
 
@@ -2776,6 +2877,20 @@ hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const do
     return hipGetLastError();
 }
 
+// A direct kernel K<TA...> (TA in parentheses), or -- for a split plan's call, `skip` != null -- its SKIP instantiation
+// K<TA..., true> with the row map as the trailing argument.  LDS: dynamic LDS bytes (0: none, nothing raised).
+#define SBLAS_UNPAREN(...) __VA_ARGS__
+#define SBLAS_DIRECT_GO(K, TA, GRID, BLOCK, LDS, ...)                                                                 \
+    do {                                                                                                              \
+        if (skip) {                                                                                                   \
+            if (LDS) raise_dynamic_lds((const void *)K<SBLAS_UNPAREN TA, true>, LDS);                                 \
+            hipLaunchKernelGGL((K<SBLAS_UNPAREN TA, true>), GRID, BLOCK, LDS, s, __VA_ARGS__, skip);                  \
+        } else {                                                                                                      \
+            if (LDS) raise_dynamic_lds((const void *)K<SBLAS_UNPAREN TA>, LDS);                                       \
+            hipLaunchKernelGGL((K<SBLAS_UNPAREN TA>), GRID, BLOCK, LDS, s, __VA_ARGS__);                              \
+        }                                                                                                             \
+    } while (0)
+
 // the four-rows-per-wave direct kernel.  Workgroups of 4 waves (16 rows) for the shortest rows, 16 waves (64 rows) otherwise:
 // 1 M banded rows of 5 / 10 / 20 / 32 per row, N = 64, 4 | 8 | 16 waves: 0.547 | 0.554 | 0.571, 0.632 | 0.613 | 0.617, 0.973 |
 // 0.936 | 0.912, 1.22 | 1.17 | 1.14 ms; power-law rows averaging 3.2 (a 64-row workgroup waits for its longest row): 0.740 |
@@ -2784,19 +2899,38 @@ template <bool RC>
 static void launch_direct_rows(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
                                const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
                                const int *hdr, const int *cls, int info_rows, int interleave, int epoch, int voted,
-                               double avg_row)
+                               double avg_row, const unsigned *skip)
 {
     const int pin = options().tune[3];
     const int wv = pin == 4 || pin == 8 || pin == 16 ? pin : avg_row < 8.0 ? 4 : 16;
     const int rp = (rows + 4 * wv - 1) / (4 * wv);
     const dim3 grid((unsigned)rp, (unsigned)(ldbt / 64));
 #define SBLAS_ROWS_GO(WV)                                                                                             \
-    hipLaunchKernelGGL((spmm_direct_rows_kernel<WV, RC>), grid, dim3(WV * 64), 0, s, rows, cols, rp, rowptr, colidx, val, Bt, \
-                       ldbt, n, alpha, beta, C, ldc, hdr, cls, info_rows, interleave, epoch, voted)
+    SBLAS_DIRECT_GO(spmm_direct_rows_kernel, (WV, RC), grid, dim3(WV * 64), 0, rows, cols, rp, rowptr, colidx, val, Bt, ldbt, \
+                    n, alpha, beta, C, ldc, hdr, cls, info_rows, interleave, epoch, voted)
     if (wv == 4) SBLAS_ROWS_GO(4);
     else if (wv == 8) SBLAS_ROWS_GO(8);
     else SBLAS_ROWS_GO(16);
 #undef SBLAS_ROWS_GO
+}
+
+// the split rows of a split plan, after the direct kernels (which left them alone) on the same stream
+template <bool RC>
+static void launch_split(hipStream_t s, int cols, const int *colidx, const double *val, const double *Bt, int64_t ldbt, int n,
+                         double alpha, double beta, double *C, int64_t ldc, const PlanView &pv)
+{
+    const unsigned pieces = (unsigned)pv.n_pieces;
+    if (ldbt >= 128)
+        hipLaunchKernelGGL(spmm_split_piece_kernel<1>, dim3(pieces, (unsigned)((n + 127) / 128)), dim3(WIDE_WAVES * 64), 0, s,
+                           pv.pieces, cols, colidx, val, Bt, ldbt, n, pv.partial);
+    else if (ldbt == 64)
+        hipLaunchKernelGGL(spmm_split_piece_kernel<2>, dim3(pieces), dim3(WIDE_WAVES * 64), 0, s, pv.pieces, cols, colidx, val,
+                           Bt, ldbt, n, pv.partial);
+    else
+        hipLaunchKernelGGL(spmm_split_piece_kernel<4>, dim3(pieces), dim3(WIDE_WAVES * 64), 0, s, pv.pieces, cols, colidx, val,
+                           Bt, ldbt, n, pv.partial);
+    hipLaunchKernelGGL(spmm_split_fold_kernel<RC>, dim3((unsigned)pv.n_split, (unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       pv.srows, pv.partial, ldbt, n, alpha, beta, C, ldc);
 }
 
 template <bool RC>
@@ -2812,6 +2946,8 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
     const bool need_window = !pv || pv->n_window + pv->n_mfma_w > 0;
     const bool need_mfma = !pv || pv->n_mfma_w + pv->n_mfma_d > 0;
     const bool need_direct = !pv || pv->n_direct + pv->n_mfma_d > 0;
+    // a split plan: the direct kernels' SKIP instantiations, then the split kernels
+    const unsigned *skip = pv && pv->n_split > 0 ? pv->split_bits : nullptr;
     if (ldbt >= 64) {
         const Tail t = pv ? tail_at(pv->tail, rows) : tail_of(Bt, cols, ldbt, rows);
         const int *cls = nullptr;
@@ -2883,17 +3019,15 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             // short rows: four rows per wave (64 staged columns, banded rows, 1 M rows, against the lane-group kernel: 32 per
             // row 1.08 | 1.14 ms, 48: 1.41 | 1.54, 64: 1.75 | 1.70, 100: 2.57 | 2.49)
             launch_direct_rows<RC>(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                               interleave, epoch, 0, avg_row);
+                               interleave, epoch, 0, avg_row, skip);
         } else if (ldbt == 64 && n <= 32) {
-            if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<4, RC>, pad);
-            hipLaunchKernelGGL((spmm_direct_dpp_kernel<4, RC>), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, s,
-                               rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls,
-                               info_rows, interleave, epoch, dpp_long);
+            SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (4, RC), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, rows,
+                            cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
+                            interleave, epoch, dpp_long);
         } else if (ldbt == 64) {
-            if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<2, RC>, pad);
-            hipLaunchKernelGGL((spmm_direct_dpp_kernel<2, RC>), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, s,
-                               rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls,
-                               info_rows, interleave, epoch, dpp_long);
+            SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (2, RC), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, rows,
+                            cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
+                            interleave, epoch, dpp_long);
         } else {
             // 128-column tiles.  Classified calls launch both direct kernels: the classifier's vote (device side) says
             // whether the rows share column patterns, and the kernel whose call it is not leaves on one scalar load.
@@ -2903,7 +3037,7 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             const bool four = pv ? pv->four_rows : cls != nullptr && variant != SPMM_VARIANT_DIRECT_MERGE;
             if (four) {
                 launch_direct_rows<RC>(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                                   interleave, epoch, pv ? 0 : 1, avg_row);
+                                   interleave, epoch, pv ? 0 : 1, avg_row, skip);
             }
             if (merge) {
                 // rows that share their column pattern (multi-dof FEM): three rows per wave, shared Bt loads
@@ -2914,12 +3048,10 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
                                    dim3(MERGE_WAVES * 64), lds, s, rows, cols, mp, rowptr, colidx, val, Bt, ldbt, n, alpha,
                                    beta, C, ldc, t.hdr, cls, info_rows, interleave, epoch);
             }
-            if (plain) {
-                if (pad) raise_dynamic_lds((const void *)spmm_direct_dpp_kernel<1, RC>, pad);
-                hipLaunchKernelGGL((spmm_direct_dpp_kernel<1, RC>), dim3((unsigned)wide_panels, (unsigned)(ldbt / 128)),
-                                   dim3(WIDE_WAVES * 64), pad, s, rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n,
-                                   alpha, beta, C, ldc, t.hdr, cls, info_rows, interleave, epoch, dpp_long);
-            }
+            if (plain)
+                SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (1, RC), dim3((unsigned)wide_panels, (unsigned)(ldbt / 128)),
+                                dim3(WIDE_WAVES * 64), pad, rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta,
+                                C, ldc, t.hdr, cls, info_rows, interleave, epoch, dpp_long);
         }
     } else {
         // ---- narrow dense blocks (ldbt = 8 / 16 / 32): LDS-tiled lane-per-entry kernel on the panels that qualify,
@@ -2985,28 +3117,32 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
             // the row-per-wave kernel, four nonzeros per instruction: sixteen lanes x 16 bytes per nonzero (with 16 staged
             // columns the upper eight lanes of a DPP row read past the Bt row, into columns that are never stored)
             const int wide_panels = (rows + WIDE_PANEL - 1) / WIDE_PANEL;
-            hipLaunchKernelGGL((spmm_direct_dpp_kernel<4, RC>), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), 0, s, rows,
-                               cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                               opt.direct_map, epoch, dpp_long);
+            SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (4, RC), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), 0, rows,
+                            cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
+                            opt.direct_map, epoch, dpp_long);
         } else if (ldbt == 32) {
-            hipLaunchKernelGGL((spmm_rowpanel_narrow_kernel<32, RC>), dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
-                               Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
+            SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (32, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,
+                            alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         } else if (ldbt == 16) {
-            hipLaunchKernelGGL((spmm_rowpanel_narrow_kernel<16, RC>), dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
-                               Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
+            SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (16, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,
+                            alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         } else if (avg_row >= opt.rows8_min_avg && variant != SPMM_VARIANT_LANES) {
             // n <= 8, long rows: a wave per row, eight sums per lane (banded-random rows, band +-20000, 600 k rows,
             // N = 8: 64 / 128 / 200 / 300 per row: the lane groups win by 25 / 30 / 2 / 0 %; bench matrix, 399 per row,
             // band +-2000: the wave per row wins by 20 % -- tools/rows8_threshold.py)
-            hipLaunchKernelGGL(spmm_rows8_kernel<RC>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, cols, rowptr,
-                               colidx, val, Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
+            SBLAS_DIRECT_GO(spmm_rows8_kernel, (RC), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, rows, cols, rowptr, colidx,
+                            val, Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         } else {
-            hipLaunchKernelGGL((spmm_rowpanel_narrow_kernel<8, RC>), dim3(panels), dim3(256), 0, s, rows, rowptr, colidx, val,
-                               Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
+            SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (8, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,
+                            alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
         }
     }
+    if (skip) launch_split<RC>(s, cols, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, *pv);
     return hipGetLastError();
 }
+
+#undef SBLAS_DIRECT_GO
+#undef SBLAS_UNPAREN
 
 hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
                                 const double *val, const double *Bt, int64_t ldbt, int n, double alpha,

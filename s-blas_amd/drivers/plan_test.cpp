@@ -22,9 +22,15 @@ static bool repeated(int method, const char *path, int b_width, unsigned n_gpu, 
         sblas_spmm_csr_cpu<int, double>(&A, &B, &C_cpu, alpha, beta);
         const harness::Outcome o = harness::compare(C_cpu.val, C.val, C.get_mtx_num());
         int planned = 0;
-        for (unsigned i = 0; i < n_gpu; ++i) planned += A.spmm_plan_gpu && A.spmm_plan_gpu[i] != NULL;
-        printf("method %d call %d: %s, %d of %u GPUs planned, max rel err %.3g\n", method, c, o.correct ? "ok" : "MISMATCH", planned,
-               n_gpu, o.max_rel);
+        long long split_rows = 0; // rows the plans sum in pieces (SBLAS_SPMM_SPLIT=1)
+        for (unsigned i = 0; i < n_gpu; ++i) {
+            planned += A.spmm_plan_gpu && A.spmm_plan_gpu[i] != NULL;
+            int64_t si[4];
+            if (A.spmm_plan_gpu && A.spmm_plan_gpu[i] && sblas_hip_spmm_plan_split_info(A.spmm_plan_gpu[i], si) == SBLAS_OK)
+                split_rows += si[0];
+        }
+        printf("method %d call %d: %s, %d of %u GPUs planned, %lld split rows, max rel err %.3g\n", method, c,
+               o.correct ? "ok" : "MISMATCH", planned, n_gpu, split_rows, o.max_rel);
         ok = ok && o.correct;
         // no plan on the first call (a one-shot caller pays nothing), one per GPU from the second on (unless switched off);
         // method 2 beyond 128 columns calls the per-GPU product once per 128-column tile, so its second TILE is planned

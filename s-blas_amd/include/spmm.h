@@ -74,7 +74,8 @@ inline void require_col_major(const char *who, DenseMatrix<IdxType, DataType> *p
 // that multiplies once -- the reference's drivers -- pays nothing; making the plan synchronises the GPU's stream once);
 // the plan stays in the CsrSparseMatrix until its next sync2gpu, and every later call launches only the kernels that
 // have panels.  SBLAS_PLAN=0 keeps every call unplanned.  order_b / order_c: SBLAS_COL_MAJOR or SBLAS_ROW_MAJOR (one plan
-// serves both).
+// serves both).  SBLAS_SPMM_SPLIT=1 (opt-in) makes the plan a split plan (sblas_hip_spmm_plan_create_split): very long rows
+// are summed by many workgroups; opt-in because those rows are summed in another order (their last bits can differ).
 template <typename IdxType, typename DataType>
 inline int spmm_on_gpu(CsrSparseMatrix<IdxType, DataType> *pA, unsigned i, void *stream, int vt, int it, int64_t m, int64_t K,
                        int64_t nnz, const DataType *B, int64_t ldb, int order_b, int64_t n, double alpha, double beta,
@@ -84,13 +85,18 @@ inline int spmm_on_gpu(CsrSparseMatrix<IdxType, DataType> *pA, unsigned i, void 
         const char *e = getenv("SBLAS_PLAN");
         return !(e && e[0] == '0');
     }();
+    static const bool split = [] {
+        const char *e = getenv("SBLAS_SPMM_SPLIT");
+        return e && e[0] == '1';
+    }();
     if (plans && vt == SBLAS_F64 && it == SBLAS_I32 && pA->spmm_plan_gpu) {
         // a plan speaks for a staged width: every n with the same sblas_hip_spmm_ldbt(n) shares it (method 2's column tiles)
         const int64_t key = sblas_hip_spmm_ldbt(n);
         const bool mine = pA->spmm_plan_gpu[i] && pA->spmm_plan_n[i] == key;
         if (!mine && !pA->spmm_plan_gpu[i] && pA->spmm_plan_n[i] == -key) { // second call at this width: plan it
-            const int rc = sblas_hip_spmm_plan_create(-1, stream, m, K, nnz, (const int32_t *)pA->csrRowPtr_gpu[i],
-                                                      (const int32_t *)pA->csrColIdx_gpu[i], n, &pA->spmm_plan_gpu[i]);
+            const int32_t *rp = (const int32_t *)pA->csrRowPtr_gpu[i], *ci = (const int32_t *)pA->csrColIdx_gpu[i];
+            const int rc = split ? sblas_hip_spmm_plan_create_split(-1, stream, m, K, nnz, rp, ci, n, 0, 0, &pA->spmm_plan_gpu[i])
+                                 : sblas_hip_spmm_plan_create(-1, stream, m, K, nnz, rp, ci, n, &pA->spmm_plan_gpu[i]);
             if (rc != SBLAS_OK) return rc;
             pA->spmm_plan_n[i] = key;
         } else if (!mine) { // first call at this width, or a width other than the plan's (a ragged last tile): unplanned

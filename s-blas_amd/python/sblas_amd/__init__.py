@@ -32,6 +32,7 @@ EXPORTS = [
     "sblas_hip_spmv_plan_create", "sblas_hip_spmv_plan_destroy", "sblas_hip_spmv_plan_info", "sblas_hip_spmv_csr_f64_i32_planned",
     "sblas_spmv_plan_classify",
     "sblas_hip_spmm_csr_ordered", "sblas_hip_spmm_csr_ordered_f64_i32_planned", "sblas_hip_merge_rowblocks_ordered",
+    "sblas_hip_spmm_plan_create_split", "sblas_hip_spmm_plan_split_info", "sblas_spmm_split_classify",
 ]
 
 
@@ -69,6 +70,12 @@ def lib():
     L.sblas_hip_debug_validate_csr_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp]
     L.sblas_hip_spmm_plan_create.restype = C.c_int
     L.sblas_hip_spmm_plan_create.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, i64, C.POINTER(vp)]
+    L.sblas_hip_spmm_plan_create_split.restype = C.c_int
+    L.sblas_hip_spmm_plan_create_split.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, i64, i64, i64, C.POINTER(vp)]
+    L.sblas_hip_spmm_plan_split_info.restype = C.c_int
+    L.sblas_hip_spmm_plan_split_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_spmm_split_classify.restype = i64
+    L.sblas_spmm_split_classify.argtypes = [vp, i64, i64, i64, i64, vp, i64, vp, i64]
     L.sblas_hip_spmm_plan_destroy.restype = C.c_int
     L.sblas_hip_spmm_plan_destroy.argtypes = [vp]
     L.sblas_hip_spmm_plan_info.restype = C.c_int
@@ -220,6 +227,33 @@ def spmv_plan_classify(rowptr, nnz=None, split_min=0, piece=0):
     return out[:n]
 
 
+# the split SpMM plan's default parameters (SBLAS_SPMM_SPLIT_* in sblas_hip.h)
+SPMM_SPLIT_MIN, SPMM_SPLIT_PIECE = 16384, 4096
+
+
+def spmm_split_classify(rowptr, nnz=None, split_min=0, piece=0, direct_mask=None, panel_rows=0):
+    """The split SpMM plan's classifier (sblas_spmm_split_classify): (pieces, split_rows), int32 arrays of shape (P, 4)
+    {row, first nonzero, end, partial slot} and (S, 4) {row, first slot, pieces, -1}.  direct_mask: one flag per panel
+    of panel_rows rows (None: every panel); nnz defaults to rowptr[-1]."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    rows = len(rowptr) - 1
+    nnz = int(rowptr[-1]) if nnz is None else int(nnz)
+    mask = None if direct_mask is None else np.ascontiguousarray(np.asarray(direct_mask) != 0, np.uint8).ravel()
+    if mask is not None and (panel_rows <= 0 or len(mask) < (rows + panel_rows - 1) // panel_rows):
+        raise SblasError("direct_mask needs one entry per panel of panel_rows rows (%d rows)" % rows)
+    mptr = mask.ctypes.data if mask is not None else None
+    L = lib()
+    n = L.sblas_spmm_split_classify(rowptr.ctypes.data, rows, nnz, split_min, piece, mptr, panel_rows, None, 0)
+    if n < 0:
+        raise SblasError("sblas_spmm_split_classify refused its arguments")
+    out = np.zeros((max(n, 1), 4), np.int32)
+    if L.sblas_spmm_split_classify(rowptr.ctypes.data, rows, nnz, split_min, piece, mptr, panel_rows, out.ctypes.data, n) != n:
+        raise SblasError("sblas_spmm_split_classify changed its answer")
+    out = out[:n]
+    n_pieces = int(np.count_nonzero(out[:, 3] >= 0))
+    return out[:n_pieces], out[n_pieces:]
+
+
 def partition_dense(first_order, n_gpu, i_gpu):
     o, d = C.c_int64(), C.c_int64()
     check(lib().sblas_partition_dense(first_order, n_gpu, i_gpu, C.byref(o), C.byref(d)), "sblas_partition_dense")
@@ -266,17 +300,27 @@ def spmm(rows, cols, rowptr, colidx, val, B, ldb, n, alpha, beta, Cmat, ldc, wor
 
 class SpmmPlan:
     """A per-matrix plan (sblas_hip_spmm_plan_create): the panel verdicts of one structure (rowptr, colidx) at one
-    width n, taken once.  Keeps the structure tensors alive; destroy() / garbage collection frees the device buffer."""
+    width n, taken once.  Keeps the structure tensors alive; destroy() / garbage collection frees the device buffer.
+    split=True makes a split plan (sblas_hip_spmm_plan_create_split): rows of split_min+ nonzeros in the direct kernels'
+    panels are summed in pieces of at most `piece` nonzeros on workgroups of their own (0: the library's defaults)."""
 
-    def __init__(self, rows, cols, rowptr, colidx, n, stream=None):
+    def __init__(self, rows, cols, rowptr, colidx, n, stream=None, split=False, split_min=0, piece=0):
         import torch
         self.rows, self.cols, self.n, self.rowptr, self.colidx = rows, cols, n, rowptr, colidx
         self.nnz = int(colidx.numel())
         h = C.c_void_p()
-        check(lib().sblas_hip_spmm_plan_create(-1, _stream(stream), rows, cols, self.nnz, _dev_ptr(rowptr, torch.int32, "rowptr"),
-                                               _dev_ptr(colidx, torch.int32, "colidx") if self.nnz else None, n, C.byref(h)),
-              "sblas_hip_spmm_plan_create")
+        args = (-1, _stream(stream), rows, cols, self.nnz, _dev_ptr(rowptr, torch.int32, "rowptr"),
+                _dev_ptr(colidx, torch.int32, "colidx") if self.nnz else None, n)
+        if split:
+            check(lib().sblas_hip_spmm_plan_create_split(*args, split_min, piece, C.byref(h)), "sblas_hip_spmm_plan_create_split")
+        else:
+            check(lib().sblas_hip_spmm_plan_create(*args, C.byref(h)), "sblas_hip_spmm_plan_create")
         self.handle = h
+
+    def split_info(self):
+        out = (C.c_int64 * 4)()
+        check(lib().sblas_hip_spmm_plan_split_info(self.handle, out), "sblas_hip_spmm_plan_split_info")
+        return dict(split_rows=int(out[0]), pieces=int(out[1]), split_nnz=int(out[2]), partial_bytes=int(out[3]))
 
     def info(self):
         out = (C.c_int64 * 8)()
