@@ -286,6 +286,66 @@ int sblas_hip_merge_rowblocks_ordered(void *comm, int vtype, int order, int64_t 
                                       const int64_t *num_rows, void *const *partial, void *const *gather, double alpha,
                                       double beta, void *const *C, int64_t ldc, void *const *streams);
 
+/* ---------------------------------------------------------------------------------------
+ * Transposed products: y = alpha * A^T x + beta * y and C = alpha * A^T B + beta * C (cuSPARSE / rocSPARSE opA =
+ * TRANSPOSE).  A^T stored as CSR is A stored as CSC: colptr (cols + 1), rowidx (nnz), valT (nnz).  Column c lists its
+ * entries in CSR order (ascending row; duplicates keep their CSR order), the order of a stable sort of colidx, so every
+ * transposed row is summed in one defined order: the transpose uses no floating-point atomics and repeated runs are
+ * bit-identical.  With those arrays on the device, A^T x is sblas_hip_spmv_csr_f64_i32[_planned] on (colptr, rowidx,
+ * valT) with rows := cols and cols := rows, and A^T B the same for the SpMM entry points; the plan below does exactly that.
+ * ------------------------------------------------------------------------------------- */
+/* Bytes of workspace sblas_hip_csr_transpose_f64_i32 needs (0 when it needs none: nnz == 0 or cols <= 1).  Depends on nnz
+ * alone otherwise: 16 per nonzero for the sort's keys and payloads plus 1 KiB per 4096 nonzeros of digit counts. */
+size_t sblas_hip_csr_transpose_workspace(int64_t rows, int64_t cols, int64_t nnz);
+/* CSR (rows x cols) -> CSC on the device: colptr[cols + 1], rowidx[nnz], valT[nnz] and perm[nnz] (perm[i] = the CSR
+ * position of CSC entry i, so valT[i] = val[perm[i]]).  val and valT may both be NULL (structure only); perm may be NULL.
+ * nnz, rows and cols up to 2^31 - 1.  A stable LSD radix sort of the column indices, one 8-bit pass per byte of cols - 1
+ * (none for cols == 1).  Allocates nothing, never synchronises, graph-capturable; trusts the CSR contents like the other
+ * compute calls (SBLAS_VALIDATE=1 checks them first).  workspace: 16-byte aligned, sblas_hip_csr_transpose_workspace bytes. */
+int sblas_hip_csr_transpose_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                    const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                    int32_t *colptr, int32_t *rowidx, double *valT, int32_t *perm,
+                                    void *workspace, size_t workspace_bytes);
+/* dst[i] = src[idx[i]], i < n: refreshes valT from new values of A through perm.  Graph-capturable. */
+int sblas_hip_gather_f64(int dev, void *stream, int64_t n, const int32_t *idx, const double *src, double *dst);
+
+/* A transpose plan: A^T as CSR in buffers the plan owns (colptr, rowidx, valT, perm: (cols + 1) * 4 + 16 * nnz bytes),
+ * an SpMV plan over them and, for n > 0, an SpMM plan of width n (flags & SBLAS_TRANSPOSE_SPLIT: a split SpMM plan,
+ * sblas_hip_spmm_plan_create_split with the default limits).  A long column of A is a long row of A^T; the SpMV plan's
+ * split items and the split SpMM plan handle it.
+ *   - create allocates and synchronises `stream`.  It always checks the CSR on the device first
+ *     (sblas_hip_debug_validate_csr_i32): SBLAS_E_INVALID, no plan, and no transpose kernel runs on a bad structure.
+ *     cols up to 2^31 - 65 (A^T's rows).  A matrix with no columns makes a plan that holds nothing on the device (every
+ *     product is empty);
+ *   - the plan holds its own copy of the values: new values of A reach it ONLY through ..._update_values (one gather
+ *     launch; allocates nothing, graph-capturable).  Unlike the other plans, changing val in place is not seen;
+ *   - the product calls allocate nothing, never synchronise and may be captured in a graph.  They run the planned SpMV /
+ *     SpMM on the plan's arrays, so their bits are those of the planned calls on the same CSC arrays.  An SpMM of a
+ *     width other than the plan's runs the unplanned tuned SpMM (sblas_hip_spmm_csr_ordered) on them;
+ *   - A^T's shape sets the operands: x has rows entries and y cols; B is rows x n (SBLAS_COL_MAJOR ldb >= rows,
+ *     SBLAS_ROW_MAJOR ldb >= n), C is cols x n (ldc >= cols, or >= n row-major).  The SpMM workspace is
+ *     sblas_hip_spmm_csr_f64_i32_workspace(cols, rows, nnz, n) -- A^T's shape, rows and cols swapped;
+ *   - a call on another device than the plan's returns SBLAS_E_INVALID;
+ *   - one call at a time per plan, as for the plans above. */
+#define SBLAS_TRANSPOSE_SPLIT 1
+int sblas_hip_transpose_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                    const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                    int64_t n, int flags, void **plan_out);
+int sblas_hip_transpose_plan_update_values(void *plan, void *stream, const double *val);
+/* out: [0] the plan holds CSC arrays on the device, [1] nnz, [2] bytes of those arrays, [3] an SpMM plan exists, [4] its
+ * width, [5] split rows of the SpMV plan, [6] split rows of the SpMM plan (rows of A^T = columns of A), [7] 0 */
+int sblas_hip_transpose_plan_info(const void *plan, int64_t out[8]);
+/* the plan's device arrays (any output may be NULL); they live until the plan is destroyed */
+int sblas_hip_transpose_plan_csc(const void *plan, const int32_t **colptr, const int32_t **rowidx, const double **valT);
+int sblas_hip_transpose_plan_destroy(void *plan);
+/* y (cols) = alpha * A^T x (x: rows) + beta * y */
+int sblas_hip_spmv_csr_t_f64_i32_planned(const void *plan, int dev, void *stream, const double *x,
+                                         double alpha, double beta, double *y);
+/* C (cols x n) = alpha * A^T B (B: rows x n) + beta * C, either order of B and C */
+int sblas_hip_spmm_csr_t_f64_i32_planned(const void *plan, int dev, void *stream, const double *B, int64_t ldb,
+                                         int order_b, int64_t n, double alpha, double beta, double *C, int64_t ldc,
+                                         int order_c, void *workspace, size_t workspace_bytes);
+
 /* sblas_partition_nnz (below) for 64-bit row pointers */
 int64_t sblas_partition_nnz_i64(const int64_t *rowptr, int64_t rows, int64_t nnz, int n_gpu, int i_gpu,
                                 int64_t *start_row, int64_t *stop_row, int64_t *nnz_i, int64_t *first_nnz,

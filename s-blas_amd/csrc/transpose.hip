@@ -1,0 +1,536 @@
+// transpose.hip -- A^T on the device: CSR -> CSC (sblas_hip_csr_transpose_f64_i32), the value gather that refreshes it
+// (sblas_hip_gather_f64) and the transpose plan whose products run the existing planned SpMV / SpMM on the CSC arrays.
+//
+// The CSC order is fixed: column c lists its entries in CSR order (ascending row, duplicates as stored), which is what a
+// stable sort of the column indices gives.  The sort is an LSD radix sort of the colidx keys with the nonzero index k as
+// payload, one 8-bit digit per pass and only as many passes as cols - 1 has bytes:
+//   hist    one workgroup per tile of 4096 keys counts its digits (wave-private counters in LDS, no atomics);
+//   scan    exclusive scan of the digit-major histogram (digit d of tile t at d * tiles + t): every key's destination
+//           base is the count of smaller digits plus the same digit in earlier tiles;
+//   scatter the same tile ranks each key among the keys of its digit: a wave finds the lanes holding its digit with eight
+//           ballots, its rank is the number of those lanes below it, and per-wave running counters in LDS (seeded with
+//           the earlier waves' counts) carry the rank across the wave's 16 rounds.  Keys go out in (round, lane) order
+//           of each wave's contiguous 1024 keys, so every pass is stable.
+// Then colptr[c] = the number of sorted keys below c (a binary search per column: no scan over cols, no atomics), and
+// one pass over the nonzeros writes perm[i] = k, rowidx[i] = row(k) (binary search in rowptr) and valT[i] = val[k].
+// Nothing depends on scheduling: the same input gives the same bits on every run.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+#include "../../include/sblas_hip.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int T_THREADS = 256;                        // four waves
+constexpr int T_WAVES = T_THREADS / 64;
+constexpr int T_ROUNDS = 16;                          // keys per lane
+constexpr int64_t T_WAVE_KEYS = 64 * T_ROUNDS;        // contiguous keys of one wave
+constexpr int64_t T_TILE = T_WAVES * T_WAVE_KEYS;     // 4096 keys per workgroup
+constexpr int RADIX_BITS = 8;
+constexpr int RADIX = 1 << RADIX_BITS;
+constexpr int SCAN_ITEMS = 16;
+constexpr int64_t SCAN_TILE = T_THREADS * SCAN_ITEMS; // 4096 histogram entries per workgroup
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+
+// bits of the largest column index, and the 8-bit passes they take (0 for one column: the CSR order is already sorted)
+inline int key_bits(int64_t cols)
+{
+    int b = 0;
+    for (uint64_t v = cols > 1 ? (uint64_t)(cols - 1) : 0; v; v >>= 1) ++b;
+    return b;
+}
+inline int radix_passes(int64_t cols) { return (key_bits(cols) + RADIX_BITS - 1) / RADIX_BITS; }
+
+struct Workspace {
+    int32_t *keys[2] = {nullptr, nullptr}, *idx[2] = {nullptr, nullptr};
+    uint32_t *hist = nullptr, *bsum = nullptr;
+    int64_t tiles = 0, hist_len = 0, scan_blocks = 0;
+};
+
+// key / payload ping-pong buffers (16 B per nonzero), the digit-major histogram (1 KiB per tile) and the scan's block sums
+inline size_t workspace_layout(int64_t nnz, char *base, Workspace *w)
+{
+    const int64_t tiles = ceil_div(nnz, T_TILE), hist_len = (int64_t)RADIX * tiles, scan_blocks = ceil_div(hist_len, SCAN_TILE);
+    const size_t arr = align16((size_t)nnz * sizeof(int32_t));
+    size_t off = 0;
+    if (w) {
+        w->tiles = tiles, w->hist_len = hist_len, w->scan_blocks = scan_blocks;
+        for (int q = 0; q < 2; ++q) {
+            w->keys[q] = reinterpret_cast<int32_t *>(base + off), off += arr;
+            w->idx[q] = reinterpret_cast<int32_t *>(base + off), off += arr;
+        }
+        w->hist = reinterpret_cast<uint32_t *>(base + off), off += align16((size_t)hist_len * sizeof(uint32_t));
+        w->bsum = reinterpret_cast<uint32_t *>(base + off), off += align16((size_t)scan_blocks * sizeof(uint32_t));
+        return off;
+    }
+    return 4 * arr + align16((size_t)hist_len * sizeof(uint32_t)) + align16((size_t)scan_blocks * sizeof(uint32_t));
+}
+
+inline unsigned grid_for(int64_t n)
+{
+    const int64_t b = ceil_div(n, T_THREADS);
+    return (unsigned)(b < 1 ? 1 : b > 65536 ? 65536 : b); // grid-stride loops cover the rest
+}
+
+// the lanes of this wave whose (valid) key has digit d, as a 64-bit lane mask; every lane of the wave must call it
+__device__ inline uint64_t match_digit(uint32_t d, bool valid)
+{
+    uint64_t m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < RADIX_BITS; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const uint64_t v = __ballot(bit);
+        m &= bit ? v : ~v;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(T_THREADS) void radix_hist_kernel(const int32_t *__restrict__ keys, int64_t nnz, int shift,
+                                                               int64_t tiles, uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t cnt[T_WAVES][RADIX];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    for (int q = tid; q < T_WAVES * RADIX; q += T_THREADS) (&cnt[0][0])[q] = 0;
+    __syncthreads();
+    const int64_t t = blockIdx.x;
+    const int64_t base = t * T_TILE + (int64_t)w * T_WAVE_KEYS + lane;
+    volatile uint32_t *wc = cnt[w]; // wave-private: one leader per digit and round, rounds in order
+    for (int j = 0; j < T_ROUNDS; ++j) {
+        const int64_t i = base + (int64_t)j * 64;
+        const bool valid = i < nnz;
+        const uint32_t d = valid ? ((uint32_t)keys[i] >> shift) & (RADIX - 1) : 0u;
+        const uint64_t m = match_digit(d, valid);
+        if (valid && lane == __ffsll((unsigned long long)m) - 1) wc[d] = wc[d] + (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    uint32_t s = 0;
+    for (int q = 0; q < T_WAVES; ++q) s += cnt[q][tid];
+    hist[(int64_t)tid * tiles + t] = s;
+}
+
+__global__ __launch_bounds__(T_THREADS) void radix_scatter_kernel(const int32_t *__restrict__ keys_in,
+                                                                  const int32_t *__restrict__ idx_in, int64_t nnz, int shift,
+                                                                  int64_t tiles, const uint32_t *__restrict__ offs,
+                                                                  int32_t *__restrict__ keys_out, int32_t *__restrict__ idx_out)
+{
+    __shared__ uint32_t cnt[T_WAVES][RADIX];
+    __shared__ uint32_t keys[T_WAVES][T_WAVE_KEYS];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    for (int q = tid; q < T_WAVES * RADIX; q += T_THREADS) (&cnt[0][0])[q] = 0;
+    __syncthreads();
+    const int64_t t = blockIdx.x;
+    const int64_t base = t * T_TILE + (int64_t)w * T_WAVE_KEYS + lane;
+    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    volatile uint32_t *wc = cnt[w];
+    uint32_t *wkeys = keys[w]; // the wave's keys, read once from memory
+    for (int j = 0; j < T_ROUNDS; ++j) { // count this wave's digits
+        const int64_t i = base + (int64_t)j * 64;
+        const bool valid = i < nnz;
+        const uint32_t key = valid ? (uint32_t)keys_in[i] : 0u;
+        wkeys[j * 64 + lane] = key;
+        const uint32_t d = (key >> shift) & (RADIX - 1);
+        const uint64_t m = match_digit(d, valid);
+        if (valid && lane == __ffsll((unsigned long long)m) - 1) wc[d] = wc[d] + (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    { // a wave's first slot of digit d: the tile's base for d plus the earlier waves' keys of d
+        uint32_t run = offs[(int64_t)tid * tiles + t];
+        for (int q = 0; q < T_WAVES; ++q) {
+            const uint32_t c = cnt[q][tid];
+            cnt[q][tid] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    for (int j = 0; j < T_ROUNDS; ++j) {
+        const int64_t i = base + (int64_t)j * 64;
+        const bool valid = i < nnz;
+        const uint32_t key = wkeys[j * 64 + lane];
+        const uint32_t d = (key >> shift) & (RADIX - 1);
+        const uint64_t m = match_digit(d, valid);
+        if (valid) {
+            const uint32_t b = wc[d]; // every lane of the group reads before its leader moves the counter on
+            const uint32_t dst = b + (uint32_t)__popcll(m & below);
+            keys_out[dst] = (int32_t)key;
+            idx_out[dst] = idx_in ? idx_in[i] : (int32_t)i;
+            if (lane == __ffsll((unsigned long long)m) - 1) wc[d] = b + (uint32_t)__popcll(m);
+        }
+    }
+}
+
+// exclusive prefix of v over the workgroup's 256 threads
+__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total)
+{
+    __shared__ uint32_t wsum[T_WAVES];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    uint32_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    uint32_t pre = 0, all = 0;
+    for (int q = 0; q < T_WAVES; ++q) {
+        pre += q < w ? wsum[q] : 0u;
+        all += wsum[q];
+    }
+    __syncthreads();
+    *total = all;
+    return pre + x - v;
+}
+
+__global__ __launch_bounds__(T_THREADS) void scan_reduce_kernel(const uint32_t *__restrict__ a, int64_t n, uint32_t *__restrict__ bsum)
+{
+    const int64_t b0 = (int64_t)blockIdx.x * SCAN_TILE;
+    uint32_t s = 0;
+    for (int j = 0; j < SCAN_ITEMS; ++j) {
+        const int64_t i = b0 + (int64_t)j * T_THREADS + threadIdx.x;
+        if (i < n) s += a[i];
+    }
+    uint32_t total;
+    (void)block_exclusive_scan(s, &total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// one workgroup: exclusive scan of the block sums in place
+__global__ __launch_bounds__(T_THREADS) void scan_top_kernel(uint32_t *__restrict__ bsum, int64_t nb)
+{
+    uint32_t carry = 0;
+    for (int64_t c = 0; c < nb; c += T_THREADS) {
+        const int64_t i = c + threadIdx.x;
+        const uint32_t v = i < nb ? bsum[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_scan(v, &total);
+        if (i < nb) bsum[i] = carry + ex;
+        carry += total;
+    }
+}
+
+// exclusive scan of one tile in place (16 consecutive entries per thread), offset by the tile's block sum
+__global__ __launch_bounds__(T_THREADS) void scan_down_kernel(uint32_t *__restrict__ a, int64_t n, const uint32_t *__restrict__ bsum)
+{
+    const int64_t i0 = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
+    uint32_t v[SCAN_ITEMS], s = 0;
+#pragma unroll
+    for (int j = 0; j < SCAN_ITEMS; ++j) {
+        v[j] = i0 + j < n ? a[i0 + j] : 0u;
+        s += v[j];
+    }
+    uint32_t total;
+    uint32_t run = bsum[blockIdx.x] + block_exclusive_scan(s, &total);
+#pragma unroll
+    for (int j = 0; j < SCAN_ITEMS; ++j) {
+        if (i0 + j < n) a[i0 + j] = run;
+        run += v[j];
+    }
+}
+
+// colptr[c] = number of sorted keys below c, c = 0 .. cols
+__global__ __launch_bounds__(T_THREADS) void colptr_kernel(const int32_t *__restrict__ skeys, int64_t nnz, int64_t cols,
+                                                           int32_t *__restrict__ colptr)
+{
+    for (int64_t c = (int64_t)blockIdx.x * T_THREADS + threadIdx.x; c <= cols; c += (int64_t)gridDim.x * T_THREADS) {
+        int64_t lo = 0, hi = nnz;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)skeys[mid] < c) lo = mid + 1;
+            else hi = mid;
+        }
+        colptr[c] = (int32_t)lo;
+    }
+}
+
+// position i of the CSC arrays: nonzero k = sidx[i] (identity when no pass ran) of row r, rowptr[r] <= k < rowptr[r + 1]
+__global__ __launch_bounds__(T_THREADS) void transpose_finish_kernel(const int32_t *__restrict__ sidx, int64_t nnz,
+                                                                     const int32_t *__restrict__ rowptr, int64_t rows,
+                                                                     const double *__restrict__ val, int32_t *__restrict__ rowidx,
+                                                                     double *__restrict__ valT, int32_t *__restrict__ perm)
+{
+    for (int64_t i = (int64_t)blockIdx.x * T_THREADS + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * T_THREADS) {
+        const int32_t k = sidx ? sidx[i] : (int32_t)i;
+        int64_t lo = 0, hi = rows - 1; // the last row whose start is <= k (empty rows share their start with the next)
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (rowptr[mid] <= k) lo = mid;
+            else hi = mid - 1;
+        }
+        rowidx[i] = (int32_t)lo;
+        if (valT) valT[i] = val[k];
+        if (perm) perm[i] = k;
+    }
+}
+
+__global__ __launch_bounds__(T_THREADS) void gather_f64_kernel(int64_t n, const int32_t *__restrict__ idx,
+                                                               const double *__restrict__ src, double *__restrict__ dst)
+{
+    for (int64_t i = (int64_t)blockIdx.x * T_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * T_THREADS) dst[i] = src[idx[i]];
+}
+
+hipError_t scan_exclusive(hipStream_t s, uint32_t *a, int64_t n, uint32_t *bsum, int64_t nb)
+{
+    scan_reduce_kernel<<<(unsigned)nb, T_THREADS, 0, s>>>(a, n, bsum);
+    scan_top_kernel<<<1, T_THREADS, 0, s>>>(bsum, nb);
+    scan_down_kernel<<<(unsigned)nb, T_THREADS, 0, s>>>(a, n, bsum);
+    return hipGetLastError();
+}
+
+hipError_t run_transpose(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                         const double *val, int32_t *colptr, int32_t *rowidx, double *valT, int32_t *perm, void *workspace)
+{
+    const int32_t *skeys = colidx, *sidx = nullptr;
+    if (nnz > 0) {
+        Workspace w;
+        workspace_layout(nnz, static_cast<char *>(workspace), &w);
+        const int passes = radix_passes(cols);
+        for (int p = 0; p < passes; ++p) {
+            const int shift = p * RADIX_BITS;
+            radix_hist_kernel<<<(unsigned)w.tiles, T_THREADS, 0, s>>>(skeys, nnz, shift, w.tiles, w.hist);
+            hipError_t e = hipGetLastError();
+            if (e == hipSuccess) e = scan_exclusive(s, w.hist, w.hist_len, w.bsum, w.scan_blocks);
+            if (e != hipSuccess) return e;
+            radix_scatter_kernel<<<(unsigned)w.tiles, T_THREADS, 0, s>>>(skeys, sidx, nnz, shift, w.tiles, w.hist, w.keys[p & 1],
+                                                                         w.idx[p & 1]);
+            skeys = w.keys[p & 1], sidx = w.idx[p & 1];
+        }
+    }
+    colptr_kernel<<<grid_for(cols + 1), T_THREADS, 0, s>>>(skeys, nnz, cols, colptr);
+    if (nnz > 0)
+        transpose_finish_kernel<<<grid_for(nnz), T_THREADS, 0, s>>>(sidx, nnz, rowptr, rows, val, rowidx, valT, perm);
+    return hipGetLastError();
+}
+
+struct DeviceScope {
+    int prev = -1;
+    bool switched = false;
+    hipError_t err = hipSuccess;
+    explicit DeviceScope(int dev)
+    {
+        if (dev < 0) return;
+        err = hipGetDevice(&prev);
+        if (err != hipSuccess) return;
+        if (prev != dev) {
+            err = hipSetDevice(dev);
+            switched = (err == hipSuccess);
+        }
+    }
+    ~DeviceScope()
+    {
+        if (switched) (void)hipSetDevice(prev);
+    }
+};
+
+inline int resolve_device(int dev)
+{
+    if (dev >= 0) return dev;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return -1;
+    return cur;
+}
+
+inline bool order_ok(int order) { return order == SBLAS_COL_MAJOR || order == SBLAS_ROW_MAJOR; }
+inline bool ld_ok(int order, int64_t ld, int64_t rows, int64_t n) { return ld >= (order == SBLAS_ROW_MAJOR ? n : rows); }
+
+// the transpose's host-side argument checks (SBLAS_OK, SBLAS_E_INVALID or SBLAS_E_WORKSPACE)
+int transpose_args(int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                   const int32_t *colptr, const int32_t *rowidx, const double *valT, const void *workspace, size_t workspace_bytes)
+{
+    if (rows < 0 || cols < 0 || nnz < 0 || rows > INT_MAX || cols > INT_MAX || nnz > INT_MAX) return SBLAS_E_INVALID;
+    if (!rowptr || !colptr) return SBLAS_E_INVALID;
+    if (nnz > 0 && (!colidx || !rowidx || (val == nullptr) != (valT == nullptr))) return SBLAS_E_INVALID;
+    if (nnz > 0 && (rows == 0 || cols == 0)) return SBLAS_E_INVALID; // no row / column to hold a nonzero
+    const size_t need = sblas_hip_csr_transpose_workspace(rows, cols, nnz);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SBLAS_E_WORKSPACE;
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return SBLAS_E_INVALID;
+    return SBLAS_OK;
+}
+
+// A plan: A^T as CSR in buffers of its own, the SpMV plan over them and, for a width n > 0, an SpMM plan.
+struct TransposePlan {
+    int dev = -1;
+    int64_t rows = 0, cols = 0, nnz = 0, n = 0;
+    void *buf = nullptr; // colptr | rowidx | valT | perm
+    size_t bytes = 0;
+    int32_t *colptr = nullptr, *rowidx = nullptr, *perm = nullptr;
+    double *valT = nullptr;
+    void *spmv = nullptr, *spmm = nullptr;
+};
+
+int plan_fail(TransposePlan *p, void **plan_out, int rc)
+{
+    sblas_hip_transpose_plan_destroy(p);
+    *plan_out = nullptr;
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+size_t sblas_hip_csr_transpose_workspace(int64_t rows, int64_t cols, int64_t nnz)
+{
+    if (rows < 0 || cols < 0 || nnz <= 0 || nnz > INT_MAX || radix_passes(cols) == 0) return 0;
+    return workspace_layout(nnz, nullptr, nullptr);
+}
+
+int sblas_hip_csr_transpose_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                                    const int32_t *colidx, const double *val, int32_t *colptr, int32_t *rowidx, double *valT,
+                                    int32_t *perm, void *workspace, size_t workspace_bytes)
+{
+    if (const int rc = transpose_args(rows, cols, nnz, rowptr, colidx, val, colptr, rowidx, valT, workspace, workspace_bytes))
+        return rc;
+    if (sblas::options().validate && rows > 0 && nnz > 0) {
+        const int vrc = sblas_hip_debug_validate_csr_i32(dev, stream, rows, cols, nnz, rowptr, colidx);
+        if (vrc) return vrc;
+    }
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    return run_transpose((hipStream_t)stream, rows, cols, nnz, rowptr, colidx, val, colptr, rowidx, valT, perm, workspace) ==
+                   hipSuccess
+               ? SBLAS_OK
+               : SBLAS_E_HIP;
+}
+
+int sblas_hip_gather_f64(int dev, void *stream, int64_t n, const int32_t *idx, const double *src, double *dst)
+{
+    if (n < 0) return SBLAS_E_INVALID;
+    if (n == 0) return SBLAS_OK;
+    if (!idx || !src || !dst) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    gather_f64_kernel<<<grid_for(n), T_THREADS, 0, (hipStream_t)stream>>>(n, idx, src, dst);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_transpose_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                                    const int32_t *colidx, const double *val, int64_t n, int flags, void **plan_out)
+{
+    if (!plan_out) return SBLAS_E_INVALID;
+    *plan_out = nullptr;
+    // A^T has cols rows: the SpMV / SpMM entry points take at most INT_MAX - 64 of them
+    if (rows < 0 || cols < 0 || nnz < 0 || n < 0 || rows > INT_MAX || cols > INT_MAX - 64 || nnz > INT_MAX || n > INT_MAX)
+        return SBLAS_E_INVALID;
+    if (!rowptr || (nnz > 0 && (!colidx || !val)) || (flags & ~SBLAS_TRANSPOSE_SPLIT) != 0) return SBLAS_E_INVALID;
+    if (nnz > 0 && (rows == 0 || cols == 0)) return SBLAS_E_INVALID;
+    TransposePlan *p = new TransposePlan;
+    p->dev = resolve_device(dev), p->rows = rows, p->cols = cols, p->nnz = nnz, p->n = n;
+    if (cols == 0) { // A^T has no rows: every product is empty, nothing is held on the device
+        *plan_out = p;
+        return SBLAS_OK;
+    }
+    // the transpose kernels never see a column index outside [0, cols)
+    if (rows > 0) {
+        const int vrc = sblas_hip_debug_validate_csr_i32(dev, stream, rows, cols, nnz, rowptr, colidx);
+        if (vrc) return plan_fail(p, plan_out, vrc);
+    }
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cp = align16(((size_t)cols + 1) * sizeof(int32_t)), ri = align16((size_t)nnz * sizeof(int32_t));
+    const size_t vt = align16((size_t)nnz * sizeof(double));
+    p->bytes = cp + ri + vt + ri;
+    if (hipMalloc(&p->buf, p->bytes) != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
+    char *b = static_cast<char *>(p->buf);
+    p->colptr = reinterpret_cast<int32_t *>(b), p->rowidx = reinterpret_cast<int32_t *>(b + cp);
+    p->valT = reinterpret_cast<double *>(b + cp + ri), p->perm = reinterpret_cast<int32_t *>(b + cp + ri + vt);
+    const size_t wsb = sblas_hip_csr_transpose_workspace(rows, cols, nnz);
+    void *ws = nullptr;
+    if (wsb > 0 && hipMalloc(&ws, wsb) != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
+    hipError_t e = run_transpose(s, rows, cols, nnz, rowptr, colidx, val, p->colptr, p->rowidx, p->valT, p->perm, ws);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (ws) (void)hipFree(ws);
+    if (e != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
+    int rc = sblas_hip_spmv_plan_create(dev, stream, cols, rows, nnz, p->colptr, p->rowidx, &p->spmv);
+    if (rc == SBLAS_OK && n > 0)
+        rc = (flags & SBLAS_TRANSPOSE_SPLIT)
+                 ? sblas_hip_spmm_plan_create_split(dev, stream, cols, rows, nnz, p->colptr, p->rowidx, n, 0, 0, &p->spmm)
+                 : sblas_hip_spmm_plan_create(dev, stream, cols, rows, nnz, p->colptr, p->rowidx, n, &p->spmm);
+    if (rc != SBLAS_OK) return plan_fail(p, plan_out, rc);
+    *plan_out = p;
+    return SBLAS_OK;
+}
+
+int sblas_hip_transpose_plan_destroy(void *plan)
+{
+    if (!plan) return SBLAS_OK;
+    TransposePlan *p = static_cast<TransposePlan *>(plan);
+    if (p->spmv) sblas_hip_spmv_plan_destroy(p->spmv);
+    if (p->spmm) sblas_hip_spmm_plan_destroy(p->spmm);
+    if (p->buf) {
+        DeviceScope scope(p->dev);
+        (void)hipFree(p->buf);
+    }
+    delete p;
+    return SBLAS_OK;
+}
+
+int sblas_hip_transpose_plan_update_values(void *plan, void *stream, const double *val)
+{
+    if (!plan) return SBLAS_E_INVALID;
+    const TransposePlan *p = static_cast<const TransposePlan *>(plan);
+    if (p->nnz == 0) return SBLAS_OK;
+    if (!val) return SBLAS_E_INVALID;
+    return sblas_hip_gather_f64(p->dev, stream, p->nnz, p->perm, val, p->valT);
+}
+
+int sblas_hip_transpose_plan_info(const void *plan, int64_t out[8])
+{
+    if (!plan || !out) return SBLAS_E_INVALID;
+    const TransposePlan *p = static_cast<const TransposePlan *>(plan);
+    int64_t sv[8] = {0}, sm[4] = {0};
+    if (p->spmv) sblas_hip_spmv_plan_info(p->spmv, sv);
+    if (p->spmm) sblas_hip_spmm_plan_split_info(p->spmm, sm);
+    out[0] = p->buf != nullptr, out[1] = p->nnz, out[2] = (int64_t)p->bytes, out[3] = p->spmm != nullptr;
+    out[4] = p->spmm ? p->n : 0, out[5] = sv[6], out[6] = sm[0], out[7] = 0;
+    return SBLAS_OK;
+}
+
+int sblas_hip_transpose_plan_csc(const void *plan, const int32_t **colptr, const int32_t **rowidx, const double **valT)
+{
+    if (!plan) return SBLAS_E_INVALID;
+    const TransposePlan *p = static_cast<const TransposePlan *>(plan);
+    if (colptr) *colptr = p->colptr;
+    if (rowidx) *rowidx = p->rowidx;
+    if (valT) *valT = p->valT;
+    return SBLAS_OK;
+}
+
+int sblas_hip_spmv_csr_t_f64_i32_planned(const void *plan, int dev, void *stream, const double *x, double alpha, double beta,
+                                         double *y)
+{
+    if (!plan) return SBLAS_E_INVALID;
+    const TransposePlan *p = static_cast<const TransposePlan *>(plan);
+    if (p->dev != resolve_device(dev)) return SBLAS_E_INVALID;
+    if ((p->cols > 0 && !y) || (p->rows > 0 && !x)) return SBLAS_E_INVALID;
+    if (p->cols == 0) return SBLAS_OK;
+    return sblas_hip_spmv_csr_f64_i32_planned(p->spmv, dev, stream, p->cols, p->rows, p->nnz, p->colptr, p->rowidx, p->valT, x,
+                                              alpha, beta, y);
+}
+
+int sblas_hip_spmm_csr_t_f64_i32_planned(const void *plan, int dev, void *stream, const double *B, int64_t ldb, int order_b,
+                                         int64_t n, double alpha, double beta, double *C, int64_t ldc, int order_c,
+                                         void *workspace, size_t workspace_bytes)
+{
+    if (!plan || !order_ok(order_b) || !order_ok(order_c) || n < 0) return SBLAS_E_INVALID;
+    const TransposePlan *p = static_cast<const TransposePlan *>(plan);
+    if (p->dev != resolve_device(dev)) return SBLAS_E_INVALID;
+    if (n == 0) return SBLAS_OK;
+    // A^T's shape: B is rows x n, C is cols x n
+    if (!C || !ld_ok(order_c, ldc, p->cols, n)) return SBLAS_E_INVALID;
+    if (p->rows > 0 && (!B || !ld_ok(order_b, ldb, p->rows, n))) return SBLAS_E_INVALID;
+    if (p->cols == 0) return SBLAS_OK;
+    const size_t need = p->nnz > 0 ? sblas_hip_spmm_csr_f64_i32_workspace(p->cols, p->rows, p->nnz, n) : 0;
+    if (need > 0 && (!workspace || workspace_bytes < need)) return SBLAS_E_WORKSPACE;
+    if (p->spmm && n == p->n)
+        return sblas_hip_spmm_csr_ordered_f64_i32_planned(p->spmm, dev, stream, p->cols, p->rows, p->nnz, p->colptr, p->rowidx,
+                                                          p->valT, B, ldb, order_b, n, alpha, beta, C, ldc, order_c, workspace,
+                                                          workspace_bytes);
+    return sblas_hip_spmm_csr_ordered(dev, stream, SBLAS_F64, SBLAS_I32, p->cols, p->rows, p->nnz, p->colptr, p->rowidx, p->valT,
+                                      B, ldb, order_b, n, alpha, beta, C, ldc, order_c, workspace, workspace_bytes);
+}
+
+} // extern "C"

@@ -33,6 +33,10 @@ EXPORTS = [
     "sblas_spmv_plan_classify",
     "sblas_hip_spmm_csr_ordered", "sblas_hip_spmm_csr_ordered_f64_i32_planned", "sblas_hip_merge_rowblocks_ordered",
     "sblas_hip_spmm_plan_create_split", "sblas_hip_spmm_plan_split_info", "sblas_spmm_split_classify",
+    "sblas_hip_csr_transpose_workspace", "sblas_hip_csr_transpose_f64_i32", "sblas_hip_gather_f64",
+    "sblas_hip_transpose_plan_create", "sblas_hip_transpose_plan_update_values", "sblas_hip_transpose_plan_info",
+    "sblas_hip_transpose_plan_csc", "sblas_hip_transpose_plan_destroy", "sblas_hip_spmv_csr_t_f64_i32_planned",
+    "sblas_hip_spmm_csr_t_f64_i32_planned",
 ]
 
 
@@ -153,6 +157,26 @@ def lib():
     L.sblas_hip_merge_rowblocks_ordered.restype = C.c_int
     L.sblas_hip_merge_rowblocks_ordered.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(vp),
                                                     C.POINTER(vp), f64, f64, C.POINTER(vp), i64, C.POINTER(vp)]
+    L.sblas_hip_csr_transpose_workspace.restype = sz
+    L.sblas_hip_csr_transpose_workspace.argtypes = [i64, i64, i64]
+    L.sblas_hip_csr_transpose_f64_i32.restype = C.c_int
+    L.sblas_hip_csr_transpose_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+    L.sblas_hip_gather_f64.restype = C.c_int
+    L.sblas_hip_gather_f64.argtypes = [C.c_int, vp, i64, vp, vp, vp]
+    L.sblas_hip_transpose_plan_create.restype = C.c_int
+    L.sblas_hip_transpose_plan_create.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, C.c_int, C.POINTER(vp)]
+    L.sblas_hip_transpose_plan_update_values.restype = C.c_int
+    L.sblas_hip_transpose_plan_update_values.argtypes = [vp, vp, vp]
+    L.sblas_hip_transpose_plan_info.restype = C.c_int
+    L.sblas_hip_transpose_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_transpose_plan_csc.restype = C.c_int
+    L.sblas_hip_transpose_plan_csc.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_transpose_plan_destroy.restype = C.c_int
+    L.sblas_hip_transpose_plan_destroy.argtypes = [vp]
+    L.sblas_hip_spmv_csr_t_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_spmv_csr_t_f64_i32_planned.argtypes = [vp, C.c_int, vp, vp, f64, f64, vp]
+    L.sblas_hip_spmm_csr_t_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_spmm_csr_t_f64_i32_planned.argtypes = [vp, C.c_int, vp, vp, i64, C.c_int, i64, f64, f64, vp, i64, C.c_int, vp, sz]
     L.sblas_partition_nnz_i64.restype = i64
     L.sblas_partition_nnz_i64.argtypes = [vp, i64, i64, C.c_int, C.c_int] + [C.POINTER(i64)] * 4 + [vp]
     _lib = L
@@ -746,3 +770,169 @@ def spmm_tensor(A, B, C_, alpha, beta, workspace=None, plan=None, stream=None):
         rc = L.sblas_hip_spmm_csr_ordered(-1, _stream(stream), F64, I32, rows, cols, nnz, *ap, pb if cols else None, ldb,
                                           order_b, n, alpha, beta, pc, ldc, order_c, wptr, wbytes)
         check(rc, "sblas_hip_spmm_csr_ordered")
+
+
+# ------------------------------------------------------------------------------------------
+# transposed products (sblas_hip_csr_transpose_f64_i32, sblas_hip_transpose_plan_* & co.)
+# ------------------------------------------------------------------------------------------
+TRANSPOSE_SPLIT = 1
+
+
+def _typed(what, t, dtype):
+    """dtype and contiguity first (these wrappers say which is wrong even for a CPU tensor), then _dev_ptr's GPU check"""
+    if t.dtype != dtype or not t.is_contiguous():
+        raise SblasError("%s must be a contiguous %s tensor" % (what, dtype))
+
+
+def transpose_workspace_bytes(rows, cols, nnz):
+    return int(lib().sblas_hip_csr_transpose_workspace(rows, cols, nnz))
+
+
+def csr_transpose(rows, cols, rowptr, colidx, val=None, stream=None, with_perm=True):
+    """A (rows x cols CSR, int32 indices) as CSC on the device: (colptr, rowidx, valT, perm) torch tensors.  Column c lists
+    its entries in CSR order (a stable sort of colidx).  val=None: structure only (valT is None); with_perm=False: perm is
+    None.  Allocates its own workspace; stream-ordered, does not synchronise."""
+    import torch
+    nnz = int(colidx.numel())
+    _typed("rowptr", rowptr, torch.int32), _typed("colidx", colidx, torch.int32)
+    if val is not None:
+        _typed("val", val, torch.float64)
+    pr = _dev_ptr(rowptr, torch.int32, "rowptr")
+    pc = _dev_ptr(colidx, torch.int32, "colidx") if nnz else None
+    pv = _dev_ptr(val, torch.float64, "val") if val is not None and nnz else None
+    dev = rowptr.device
+    colptr = torch.empty(cols + 1, dtype=torch.int32, device=dev)
+    rowidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    valT = torch.empty(nnz, dtype=torch.float64, device=dev) if val is not None else None
+    perm = torch.empty(nnz, dtype=torch.int32, device=dev) if with_perm else None
+    wsb = transpose_workspace_bytes(rows, cols, nnz)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+    rc = lib().sblas_hip_csr_transpose_f64_i32(
+        -1, _stream(stream), rows, cols, nnz, pr, pc, pv, colptr.data_ptr(), rowidx.data_ptr() if nnz else None,
+        valT.data_ptr() if valT is not None and nnz else None, perm.data_ptr() if perm is not None and nnz else None,
+        ws.data_ptr() if ws is not None else None, wsb)
+    check(rc, "sblas_hip_csr_transpose_f64_i32")
+    return colptr, rowidx, valT, perm
+
+
+def gather(idx, src, dst, stream=None):
+    """dst[i] = src[idx[i]] (sblas_hip_gather_f64)."""
+    import torch
+    n = int(idx.numel())
+    _typed("idx", idx, torch.int32), _typed("src", src, torch.float64), _typed("dst", dst, torch.float64)
+    if dst.numel() < n:
+        raise SblasError("dst is shorter than idx")
+    check(lib().sblas_hip_gather_f64(-1, _stream(stream), n, _dev_ptr(idx, torch.int32, "idx") if n else None,
+                                     _dev_ptr(src, torch.float64, "src") if n else None,
+                                     _dev_ptr(dst, torch.float64, "dst") if n else None), "sblas_hip_gather_f64")
+
+
+class _DeviceArray:
+    """A view of n elements of a library-owned device array (torch.as_tensor reads __cuda_array_interface__)."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = dict(shape=(n,), typestr=typestr, data=(ptr, False), version=2, strides=None)
+
+
+class TransposePlan:
+    """A^T of one CSR matrix (sblas_hip_transpose_plan_create): the CSC arrays in the plan's own buffers, an SpMV plan over
+    them and, for n > 0, an SpMM plan of width n (split=True: a split SpMM plan).  The plan keeps its own values: after
+    val changes, call update_values(val).  destroy() / garbage collection frees the device buffers."""
+
+    def __init__(self, rows, cols, rowptr, colidx, val, n=0, split=False, stream=None):
+        import torch
+        self.rows, self.cols, self.n = rows, cols, n
+        self.nnz = int(colidx.numel())
+        self.handle = None
+        self.device = rowptr.device
+        _typed("rowptr", rowptr, torch.int32), _typed("colidx", colidx, torch.int32), _typed("val", val, torch.float64)
+        if val.numel() != self.nnz:
+            raise SblasError("val has %d entries, colidx %d" % (val.numel(), self.nnz))
+        h = C.c_void_p()
+        check(lib().sblas_hip_transpose_plan_create(
+            -1, _stream(stream), rows, cols, self.nnz, _dev_ptr(rowptr, torch.int32, "rowptr"),
+            _dev_ptr(colidx, torch.int32, "colidx") if self.nnz else None,
+            _dev_ptr(val, torch.float64, "val") if self.nnz else None, n, TRANSPOSE_SPLIT if split else 0, C.byref(h)),
+            "sblas_hip_transpose_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        check(lib().sblas_hip_transpose_plan_info(self.handle, out), "sblas_hip_transpose_plan_info")
+        return dict(active=bool(out[0]), nnz=int(out[1]), bytes=int(out[2]), spmm_plan=bool(out[3]), n=int(out[4]),
+                    spmv_split_rows=int(out[5]), spmm_split_rows=int(out[6]))
+
+    def csc(self):
+        """(colptr, rowidx, valT): torch copies of the plan's device arrays."""
+        import torch
+        cp, ri, vt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sblas_hip_transpose_plan_csc(self.handle, C.byref(cp), C.byref(ri), C.byref(vt)), "sblas_hip_transpose_plan_csc")
+        def one(p, n, typestr, dtype):
+            if n == 0:
+                return torch.empty(0, dtype=dtype, device=self.device)
+            if not p.value:          # a matrix without columns: the plan holds nothing, colptr = [0]
+                return torch.zeros(n, dtype=dtype, device=self.device)
+            return torch.as_tensor(_DeviceArray(p.value, n, typestr), device=self.device).clone()
+        out = (one(cp, self.cols + 1, "<i4", torch.int32), one(ri, self.nnz, "<i4", torch.int32),
+               one(vt, self.nnz, "<f8", torch.float64))
+        return tuple(out)
+
+    def update_values(self, val, stream=None):
+        import torch
+        _typed("val", val, torch.float64)
+        if val.numel() != self.nnz:
+            raise SblasError("val has %d entries, the plan %d" % (val.numel(), self.nnz))
+        check(lib().sblas_hip_transpose_plan_update_values(self.handle, _stream(stream),
+                                                           _dev_ptr(val, torch.float64, "val") if self.nnz else None),
+              "sblas_hip_transpose_plan_update_values")
+
+    def spmv(self, x, alpha, beta, y, stream=None):
+        """y (cols) = alpha * A^T x (x: rows) + beta * y."""
+        import torch
+        if x.numel() < self.rows or y.numel() < self.cols:
+            raise SblasError("A^T x needs x of %d and y of %d entries" % (self.rows, self.cols))
+        check(lib().sblas_hip_spmv_csr_t_f64_i32_planned(self.handle, -1, _stream(stream), _dev_ptr(x, torch.float64, "x"),
+                                                         alpha, beta, _dev_ptr(y, torch.float64, "y")),
+              "sblas_hip_spmv_csr_t_f64_i32_planned")
+
+    def spmm_ordered(self, B, ldb, order_b, n, alpha, beta, Cmat, ldc, order_c, workspace, stream=None):
+        """C (cols x n) = alpha * A^T B (B: rows x n) + beta * C, flat tensors in either order; workspace of at least
+        spmm_workspace_bytes(cols, rows, nnz, n) bytes (A^T's shape)."""
+        import torch
+        rc = lib().sblas_hip_spmm_csr_t_f64_i32_planned(
+            self.handle, -1, _stream(stream), _dev_ptr(B, torch.float64, "B") if self.rows else None, ldb, order_b, n, alpha,
+            beta, _dev_ptr(Cmat, torch.float64, "C"), ldc, order_c,
+            _dev_ptr(workspace, workspace.dtype, "workspace") if workspace is not None and workspace.numel() else None,
+            workspace.numel() * workspace.element_size() if workspace is not None else 0)
+        check(rc, "sblas_hip_spmm_csr_t_f64_i32_planned")
+
+    def spmm_tensor(self, B, C_, alpha, beta, workspace=None, stream=None):
+        """C = alpha * A^T B + beta * C on 2-D tensors; each operand's order and leading dimension come from its strides
+        (as spmm_tensor)."""
+        import torch
+        if B.dim() != 2 or C_.dim() != 2:
+            raise SblasError("B and C must be 2-D tensors")
+        n = int(C_.shape[1])
+        order_b, ldb = _layout(B, self.rows, n, "B")
+        order_c, ldc = _layout(C_, self.cols, n, "C")
+        pb, pc = _view_ptr(B, "B"), _view_ptr(C_, "C")
+        if workspace is None:
+            workspace = torch.empty((spmm_workspace_bytes(self.cols, self.rows, self.nnz, n) + 7) // 8, dtype=torch.float64,
+                                    device=C_.device)
+        if not workspace.is_contiguous():
+            raise SblasError("workspace must be contiguous")
+        rc = lib().sblas_hip_spmm_csr_t_f64_i32_planned(
+            self.handle, -1, _stream(stream), pb if self.rows else None, ldb, order_b, n, alpha, beta, pc, ldc, order_c,
+            workspace.data_ptr() if workspace.numel() else None, workspace.numel() * workspace.element_size())
+        check(rc, "sblas_hip_spmm_csr_t_f64_i32_planned")
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_transpose_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
