@@ -3,8 +3,9 @@
 the typed C-ABI entry points (sblas_hip_spmm_csr, sblas_hip_spmv_csr, ...); the checker is the oracle's restatement
 of sblas_spmm_csr_cpu<IdxType, DataType> / sblas_spmv_csr_cpu<IdxType, DataType> in the same types.
 
-Tolerances: fp64 as everywhere (1e-10 relative); fp32: 1e-4 relative + 1e-4 absolute -- sums of up to a few hundred
-fp32 terms of O(1), fused multiply-add on the GPU against multiply-then-add in the oracle.  "parity unpinned": the
+Tolerances here: fp64 as everywhere (1e-10 relative); fp32: 1e-4 relative + 1e-4 absolute -- sums of up to a few hundred
+fp32 terms of O(1), fused multiply-add on the GPU against multiply-then-add in the oracle.  The numerics bar of the same
+entry points is in test_gpu_numerics.py: exact on grids, gamma(L+2) with u = 2^-24 otherwise.  "parity unpinned": the
 reference holds no fp32 / int64 outputs (its drivers instantiate <int, double> only)."""
 import os
 import subprocess
