@@ -33,7 +33,6 @@ struct DeviceScope {
     }
 };
 
-inline int spmm_variant() { return sblas::options().spmm_variant; }
 // the device a `dev` argument means (dev < 0: the calling thread's current device); -1 when that cannot be told
 inline int resolve_device(int dev)
 {
@@ -119,14 +118,6 @@ static bool ldbt_ok(int64_t ldbt, int64_t n)
 // (Queen_4147 with N = 256: two chunks of 128).  SBLAS_SPMM_MAX_BT_BYTES lowers the limit (tests).
 static uint64_t bt_byte_limit() { return sblas::options().max_bt_bytes; }
 
-// Staging traffic saved if a row block's columns span no more than twice its rows, against the extra pass over the column
-// indices and one more launch (~5 us = 40 MB at staging speed; a quarter of nd24k at N = 128 breaks even, an eighth of a
-// Queen-like matrix at N = 256 runs 1.5x faster: tools/spmm_shapes.py --block)
-static bool range_staging_pays(int64_t rows, int64_t cols, int64_t nnz, int64_t ldbt)
-{
-    return cols > 2 * rows && (uint64_t)(cols - 2 * rows) * (uint64_t)ldbt * 16ull > (uint64_t)nnz * 8ull + (40ull << 20);
-}
-
 static int64_t spmm_chunk_cols(int64_t cols, int64_t n)
 {
     const uint64_t lim = bt_byte_limit();
@@ -155,24 +146,16 @@ size_t sblas_hip_spmm_csr_f64_i32_workspace(int64_t rows, int64_t cols, int64_t 
     return bt + sblas::workspace_tail_bytes(rows); // flags, one span and one class per row panel
 }
 
-static int stage_full(int dev, void *stream, int64_t cols, int64_t n, const double *B, int64_t ldb, int order_b, double *Bt,
-                      int64_t ldbt)
-{
-    if (cols < 0 || n < 0) return SBLAS_E_INVALID;
-    if (cols == 0 || n == 0) return SBLAS_OK;
-    if (!B || !Bt || !ld_ok(order_b, ldb, cols, n) || ldbt < n || !ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
-    DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    return sblas::launch_dense_to_rowmajor((hipStream_t)stream, cols, n, B, ldb, Bt, ldbt, order_b == SBLAS_ROW_MAJOR) ==
-                   hipSuccess
-               ? SBLAS_OK
-               : SBLAS_E_HIP;
-}
-
 int sblas_hip_dense_to_rowmajor_f64(int dev, void *stream, int64_t cols, int64_t n, const double *B,
                                     int64_t ldb, double *Bt, int64_t ldbt)
 {
-    return stage_full(dev, stream, cols, n, B, ldb, SBLAS_COL_MAJOR, Bt, ldbt);
+    if (cols < 0 || n < 0) return SBLAS_E_INVALID;
+    if (cols == 0 || n == 0) return SBLAS_OK;
+    if (!B || !Bt || ldb < cols || ldbt < n || !ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    return sblas::launch_dense_to_rowmajor((hipStream_t)stream, cols, n, B, ldb, Bt, ldbt, false) == hipSuccess ? SBLAS_OK
+                                                                                                             : SBLAS_E_HIP;
 }
 
 // A has no nonzeros (cols == 0 or nnz == 0): C = beta * C, nothing else.  Neither the staging copy nor the panel
@@ -187,34 +170,28 @@ static int scale_only(int dev, void *stream, int64_t rows, int64_t n, double bet
                : SBLAS_E_HIP;
 }
 
-static int spmm_staged(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
-                       const int32_t *colidx, const double *val, const double *Bt, int64_t ldbt, int64_t n,
-                       double alpha, double beta, double *C, int64_t ldc, int order_c, int pre_epoch)
-{
-    if (!csr_args_ok(rows, cols, nnz, rowptr, colidx, val) || n < 0) return SBLAS_E_INVALID;
-    if (rows == 0 || n == 0) return SBLAS_OK;
-    if (!C || !ld_ok(order_c, ldc, rows, n) || n > INT_MAX) return SBLAS_E_INVALID;
-    if (!ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
-    if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc, order_c); // A*B = 0: no kernel reads Bt
-    if (!Bt) return SBLAS_E_INVALID;
-    // the kernels address Bt with 32-bit element offsets (row * ldbt + column)
-    if (ldbt >= 64 && ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull) return SBLAS_E_INVALID; // 32-bit byte offsets
-    DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    if ((reinterpret_cast<uintptr_t>(Bt) & 15u) != 0) return SBLAS_E_INVALID; // 16-byte tile loads
-    return sblas::launch_spmm_rowpanel((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, val, Bt, ldbt,
-                                       (int)n, alpha, beta, C, ldc, spmm_variant(), pre_epoch, nullptr,
-                                       order_c == SBLAS_ROW_MAJOR) == hipSuccess
-               ? SBLAS_OK
-               : SBLAS_E_HIP;
-}
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; } // Bt: 16-byte tile loads
 
 int sblas_hip_spmm_csr_rowmajorB_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
                                          const int32_t *rowptr, const int32_t *colidx, const double *val,
                                          const double *Bt, int64_t ldbt, int64_t n, double alpha,
                                          double beta, double *C, int64_t ldc)
 {
-    return spmm_staged(dev, stream, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, SBLAS_COL_MAJOR, 0);
+    if (!csr_args_ok(rows, cols, nnz, rowptr, colidx, val) || n < 0) return SBLAS_E_INVALID;
+    if (rows == 0 || n == 0) return SBLAS_OK;
+    if (!C || ldc < rows || n > INT_MAX) return SBLAS_E_INVALID;
+    if (!ldbt_ok(ldbt, n)) return SBLAS_E_INVALID;
+    if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc, SBLAS_COL_MAJOR); // A*B = 0: no kernel reads Bt
+    if (!Bt || !aligned16(Bt)) return SBLAS_E_INVALID;
+    // the kernels address Bt with 32-bit element offsets (row * ldbt + column)
+    if (ldbt >= 64 && ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull) return SBLAS_E_INVALID; // 32-bit byte offsets
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    const sblas::SpmmStep st = sblas::spmm_step((int)rows, (int)cols, nnz, ldbt, nullptr, sblas::SpmmStep(), true);
+    return sblas::launch_spmm_rowpanel((hipStream_t)stream, st, (int)rows, (int)cols, nnz, rowptr, colidx, val, Bt, (int)n,
+                                       alpha, beta, C, ldc, false) == hipSuccess
+               ? SBLAS_OK
+               : SBLAS_E_HIP;
 }
 
 static int validate_if_asked(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
@@ -243,71 +220,27 @@ static int spmm_impl(int dev, void *stream, int64_t rows, int64_t cols, int64_t 
     if (rows == 0 || n == 0) return SBLAS_OK;
     if (!C || !ld_ok(order_c, ldc, rows, n)) return SBLAS_E_INVALID;
     if (cols > 0 && (!B || !ld_ok(order_b, ldb, cols, n))) return SBLAS_E_INVALID;
-    const bool row_b = order_b == SBLAS_ROW_MAJOR, row_c = order_c == SBLAS_ROW_MAJOR;
     if (cols == 0 || nnz == 0) return scale_only(dev, stream, rows, n, beta, C, ldc, order_c);
     if (const int vrc = validate_if_asked(dev, stream, rows, cols, nnz, rowptr, colidx)) return vrc;
-    const size_t need = sblas_hip_spmm_csr_f64_i32_workspace(rows, cols, nnz, n);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return SBLAS_E_WORKSPACE;
+    if (!workspace || workspace_bytes < sblas_hip_spmm_csr_f64_i32_workspace(rows, cols, nnz, n)) return SBLAS_E_WORKSPACE;
+    if (!aligned16(workspace)) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    const hipStream_t s = (hipStream_t)stream;
+    const bool row_b = order_b == SBLAS_ROW_MAJOR, row_c = order_c == SBLAS_ROW_MAJOR;
     double *Bt = static_cast<double *>(workspace);
     const int64_t w = spmm_chunk_cols(cols, n);
-    int range_epoch = 0;      // range staging: the first chunk's column range and panel verdicts serve the later chunks
-    int64_t range_ldbt = 0;
+    sblas::SpmmStep step; // the previous chunk's
     for (int64_t j0 = 0; j0 < n; j0 += w) { // one pass unless Bt would exceed the 32-bit offset window
         const int64_t nj = (n - j0 < w) ? n - j0 : w;
         const int64_t ldbt = chunk_ldbt(cols, n, nj);
-        int rc, pre_epoch = 0;
-        const int sr = sblas::options().stage_range;
-        // Staging traffic saved if the block's columns span no more than twice its rows, against the extra pass over the
-        // column indices and one more launch (~5 us = 40 MB at staging speed; a quarter of nd24k at N = 128 breaks even,
-        // an eighth of a Queen-like matrix at N = 256 runs 1.5x faster: tools/spmm_shapes.py --block)
-        const bool pays = range_staging_pays(rows, cols, nnz, ldbt);
-        if (plan && plan->active && ldbt == plan->ldbt && ldbt_ok(ldbt, nj)) {
-            // planned: stage (no classifier rides along), then only the stage-2 kernels that have panels
-            DeviceScope scope(dev);
-            if (scope.err != hipSuccess) return SBLAS_E_HIP;
-            if ((reinterpret_cast<uintptr_t>(Bt) & 15u) != 0) return SBLAS_E_INVALID;
-            if (sblas::launch_stage_planned((hipStream_t)stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, Bt, ldbt, plan->pv,
-                                            row_b) != hipSuccess)
-                return SBLAS_E_HIP;
-            if (sblas::launch_spmm_rowpanel((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, val, Bt, ldbt, (int)nj,
-                                            alpha, beta, col_at(C, order_c, ldc, j0), ldc, spmm_variant(), 0, &plan->pv,
-                                            row_c) != hipSuccess)
-                return SBLAS_E_HIP;
-            continue;
-        }
-        if (ldbt >= 64 && ldbt_ok(ldbt, nj) && (sr > 0 || (sr < 0 && pays))) {
-            // a row block (method 2): the row-major copy covers only the rows of B the block's nonzeros refer to
-            DeviceScope scope(dev);
-            if (scope.err != hipSuccess) return SBLAS_E_HIP;
-            const bool direct_only = spmm_variant() == sblas::SPMM_VARIANT_DIRECT_DPP ||
-                                     spmm_variant() == sblas::SPMM_VARIANT_DIRECT_ROWS ||
-                                     spmm_variant() == sblas::SPMM_VARIANT_DIRECT_MERGE ||
-                                     !sblas::classify_worthwhile(rows, nnz, ldbt);
-            pre_epoch = (!direct_only && ldbt == range_ldbt) ? range_epoch : 0;
-            if (sblas::launch_stage_range((hipStream_t)stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, Bt, ldbt, (int)rows,
-                                          nnz, rowptr, colidx, spmm_variant(), direct_only ? 0 : 1, &pre_epoch, row_b) != hipSuccess)
-                return SBLAS_E_HIP;
-            range_epoch = pre_epoch;
-            range_ldbt = ldbt;
-        } else if (spmm_variant() != sblas::SPMM_VARIANT_DIRECT_DPP && spmm_variant() != sblas::SPMM_VARIANT_DIRECT_ROWS &&
-            spmm_variant() != sblas::SPMM_VARIANT_LANES &&
-            sblas::classify_worthwhile(rows, nnz, ldbt) &&
-            (ldbt >= 64 || (spmm_variant() != sblas::SPMM_VARIANT_DIRECT_MERGE &&
-                            ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull <= 0xffffffffull)) &&
-            cols > 0 && nnz > 0 && ld_ok(order_b, ldb, cols, n) && ldbt_ok(ldbt, nj)) {
-            // default path: the panel classifier rides in the staging launch (one launch and one gap less per call)
-            DeviceScope scope(dev);
-            if (scope.err != hipSuccess) return SBLAS_E_HIP;
-            if (sblas::launch_stage_classify((hipStream_t)stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, Bt, ldbt, (int)rows,
-                                             rowptr, colidx, spmm_variant(), &pre_epoch, row_b) != hipSuccess)
-                return SBLAS_E_HIP;
-        } else {
-            rc = stage_full(dev, stream, cols, nj, col_at(B, order_b, ldb, j0), ldb, order_b, Bt, ldbt);
-            if (rc != SBLAS_OK) return rc;
-        }
-        rc = spmm_staged(dev, stream, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, nj, alpha, beta,
-                         col_at(C, order_c, ldc, j0), ldc, order_c, pre_epoch);
-        if (rc != SBLAS_OK) return rc;
+        const sblas::PlanView *pv = plan && plan->active && ldbt == plan->ldbt ? &plan->pv : nullptr;
+        step = sblas::spmm_step((int)rows, (int)cols, nnz, ldbt, pv, step);
+        if (sblas::launch_stage(s, step, (int)rows, cols, nnz, rowptr, colidx, nj, col_at(B, order_b, ldb, j0), ldb, Bt, row_b) !=
+                hipSuccess ||
+            sblas::launch_spmm_rowpanel(s, step, (int)rows, (int)cols, nnz, rowptr, colidx, val, Bt, (int)nj, alpha, beta,
+                                        col_at(C, order_c, ldc, j0), ldc, row_c) != hipSuccess)
+            return SBLAS_E_HIP;
     }
     return SBLAS_OK;
 }
@@ -392,23 +325,21 @@ static int spmm_plan_create(int dev, void *stream, int64_t rows, int64_t cols, i
     SpmmPlan *p = new SpmmPlan;
     p->dev = resolve_device(dev), p->rows = rows, p->cols = cols, p->nnz = nnz, p->n = n, p->rowptr = rowptr, p->colidx = colidx;
     *plan_out = p;
-    const int v = spmm_variant();
-    const bool classified = v == sblas::SPMM_VARIANT_AUTO || v == sblas::SPMM_VARIANT_MFMA || v == sblas::SPMM_VARIANT_NO_MFMA;
-    if (rows == 0 || cols == 0 || nnz == 0 || n == 0 || !classified) return SBLAS_OK; // nothing to plan
-    const int64_t w = spmm_chunk_cols(cols, n);
-    const int64_t ldbt = chunk_ldbt(cols, n, n < w ? n : w);
-    if (ldbt < 64 && ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull) return SBLAS_OK; // 64-bit narrow kernels: unplanned
-    if (!sblas::classify_worthwhile(rows, nnz, ldbt)) return SBLAS_OK; // short rows at a width of 64 columns or fewer: nothing is classified
+    if (rows == 0 || cols == 0 || nnz == 0 || n == 0) return SBLAS_OK; // nothing to plan
     DeviceScope scope(dev);
     if (scope.err != hipSuccess) return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
+    // the step of the first column chunk; where it classifies nothing (a pinned direct kernel, short rows, a narrow Bt
+    // beyond 32-bit offsets) the calls run unplanned
+    const int64_t w = spmm_chunk_cols(cols, n);
+    const int64_t ldbt = chunk_ldbt(cols, n, n < w ? n : w);
+    const sblas::SpmmStep st = sblas::spmm_step((int)rows, (int)cols, nnz, ldbt, nullptr);
+    if (!st.plannable) return SBLAS_OK;
     if (hipMalloc(&p->buf, sblas::plan_tail_bytes(rows)) != hipSuccess) return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
     p->pv.tail = static_cast<int *>(p->buf);
     p->ldbt = ldbt;
-    const int sr = sblas::options().stage_range;
-    const bool use_range = ldbt >= 64 && (sr > 0 || (sr < 0 && range_staging_pays(rows, cols, nnz, ldbt)));
     std::vector<int> cls;
-    if (sblas::plan_build((hipStream_t)stream, (int)rows, (int)cols, nnz, rowptr, colidx, ldbt, v, use_range, &p->pv,
-                          split ? &cls : nullptr) != hipSuccess)
+    if (sblas::plan_build((hipStream_t)stream, st, (int)rows, (int)cols, nnz, rowptr, colidx, &p->pv, split ? &cls : nullptr) !=
+        hipSuccess)
         return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
     if (split) {
         bool bad = false;

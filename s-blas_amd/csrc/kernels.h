@@ -112,26 +112,46 @@ struct PlanView {
     int64_t n_pieces = 0, n_split = 0, split_nnz = 0;
 };
 size_t plan_tail_bytes(int64_t rows);
-bool classify_worthwhile(int64_t rows, int64_t nnz, int64_t ldbt);
-// cls_out (optional): the panel verdicts, one class word per panel of pv->info_rows rows, as the host read them
-hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx, int64_t ldbt,
-                      int variant, bool use_range, PlanView *pv, std::vector<int> *cls_out = nullptr);
+
+// What one column chunk of an SpMM call does before stage 2, decided in one place (spmm_step): how B is staged, whether
+// stage 2 reads panel verdicts and where they come from, and the panel geometry the classifier and stage 2 agree on.
+enum {
+    STAGE_CALLER = 0,  // Bt comes from the caller (sblas_hip_spmm_csr_rowmajorB_f64_i32)
+    STAGE_FULL = 1,    // the whole of B
+    STAGE_FUSED = 2,   // the whole of B, the panel classifier in the same launch
+    STAGE_RANGE = 3,   // the rows of B a row block's nonzeros refer to, after a column-range pass
+    STAGE_PLANNED = 4, // the whole of B or the plan's column range, stamped into the plan's header
+};
+enum {
+    VERDICTS_NONE = 0,     // none: a direct kernel takes every panel
+    VERDICTS_STAGING = 1,  // the staging launch classifies (fused, or in the column-range pass)
+    VERDICTS_SEPARATE = 2, // a classifier launch of its own ahead of stage 2
+    VERDICTS_EARLIER = 3,  // an earlier column chunk of the same range-staged call classified
+    VERDICTS_PLAN = 4,     // the plan's
+};
+struct SpmmStep {
+    int staging = STAGE_FULL, verdicts = VERDICTS_NONE;
+    int64_t ldbt = 0;
+    int info_rows = 1, groups = 2, npanels = 0; // (1, 2, 0: nothing classified)
+    int epoch = 0;                              // of the verdicts, or of stage 2 alone
+    bool plannable = false;                     // a plan may keep the verdicts (sblas_hip_spmm_plan_create)
+    const PlanView *pv = nullptr;
+};
+// pv: the call's plan, when it was made at this ldbt; prev: the call's previous column chunk
+SpmmStep spmm_step(int rows, int cols, int64_t nnz, int64_t ldbt, const PlanView *pv, const SpmmStep &prev = SpmmStep(),
+                   bool caller_staged = false);
 // Layouts of the dense operands: row_b = B is row-major (cols x n, B[k * ldb + j]; only the staging launchers read B),
 // row_c = C is row-major (rows x n, C[r * ldc + j]; the stage-2 epilogues, the scale and the merge kernels).
-hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                                int64_t ldbt, const PlanView &pv, bool row_b);
-hipError_t launch_stage_range(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                              int64_t ldbt, int rows, int64_t nnz, const int *rowptr, const int *colidx, int variant,
-                              int classify, int *epoch_out, bool row_b);
+hipError_t launch_stage(hipStream_t s, const SpmmStep &st, int rows, int64_t cols, int64_t nnz, const int *rowptr,
+                        const int *colidx, int64_t n, const double *B, int64_t ldb, double *Bt, bool row_b);
+hipError_t launch_spmm_rowpanel(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr,
+                                const int *colidx, const double *val, const double *Bt, int n, double alpha, double beta,
+                                double *C, int64_t ldc, bool row_c);
+// the verdicts of the step's classifier into pv; cls_out (optional): one class word per panel, as the host read them
+hipError_t plan_build(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
+                      PlanView *pv, std::vector<int> *cls_out = nullptr);
 hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb,
                                     double *Bt, int64_t ldbt, bool row_b);
-hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
-                                const double *val, const double *Bt, int64_t ldbt, int n, double alpha,
-                                double beta, double *C, int64_t ldc, int variant, int pre_epoch, const PlanView *pv,
-                                bool row_c);
-hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                                 int64_t ldbt, int rows, const int *rowptr, const int *colidx, int variant,
-                                 int *epoch_out, bool row_b);
 hipError_t launch_scale(hipStream_t s, int64_t rows, int64_t n, double beta, double *C, int64_t ldc, bool row_c);
 hipError_t validate_csr(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, const int *rowptr, const int *colidx, int *bad);
 hipError_t panel_stats(unsigned long long out[4], bool reset);

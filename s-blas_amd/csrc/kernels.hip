@@ -345,12 +345,21 @@ constexpr size_t W2_LDS_BYTES = (2 * (size_t)W2_TILE + 64) * sizeof(double) + 64
 //             PANEL_DIRECT  everything else.
 // bitmap: MFMA_BITMAP_WORDS ints of LDS per wave (one bit per 4-column block of the sampled rows' span).
 constexpr int MFMA_BITMAP_WORDS = 1024; // 32768 blocks = 131072 columns of span
+// The classifier's thresholds (classify_args): the longest row a windowed panel may hold (32-bit buffer offsets inside a
+// wave's rows), nonzeros per spanned column and per row a panel needs for the LDS-tiled kernel, the block fill from which
+// it takes the matrix cores (> 1: never), what to probe for the direct kernels' sake (bit 0 row-merging, bit 1 row per wave).
+struct ClassifyArgs {
+    int max_row_len;
+    float min_density, min_rowlen, mfma_min_fill;
+    int merge_probe;
+};
 __device__ __forceinline__ void classify_panel(int p, int rows, int cols, int npanels, int panel_rows,
                                                const int *__restrict__ rowptr, const int *__restrict__ colidx,
-                                               int max_row_len, float min_density, float min_rowlen, float mfma_min_fill,
-                                               int merge_probe, int *__restrict__ tail, int2 *__restrict__ info,
+                                               ClassifyArgs a, int *__restrict__ tail, int2 *__restrict__ info,
                                                int *__restrict__ cls, int epoch, unsigned *__restrict__ bitmap)
 {
+    const int max_row_len = a.max_row_len, merge_probe = a.merge_probe;
+    const float min_density = a.min_density, min_rowlen = a.min_rowlen, mfma_min_fill = a.mfma_min_fill;
     const int lane = threadIdx.x & 63;
     if (p >= npanels) return;
     int first = 0x7fffffff, last = -1, len = 0, mlen = 0;
@@ -540,14 +549,13 @@ __device__ __forceinline__ void classify_panel(int p, int rows, int cols, int np
 }
 __global__ __launch_bounds__(256) void classify_panels_kernel(int rows, int cols, int npanels, int panel_rows,
                                                              const int *__restrict__ rowptr,
-                                                             const int *__restrict__ colidx, int max_row_len,
-                                                             float min_density, float min_rowlen, float mfma_min_fill, int merge_probe,
+                                                             const int *__restrict__ colidx, ClassifyArgs a,
                                                              int *__restrict__ tail, int2 *__restrict__ info,
                                                              int *__restrict__ cls, int epoch)
 {
     __shared__ unsigned bitmap[4][MFMA_BITMAP_WORDS];
-    classify_panel(blockIdx.x * 4 + (threadIdx.x >> 6), rows, cols, npanels, panel_rows, rowptr, colidx, max_row_len,
-                   min_density, min_rowlen, mfma_min_fill, merge_probe, tail, info, cls, epoch, bitmap[threadIdx.x >> 6]);
+    classify_panel(blockIdx.x * 4 + (threadIdx.x >> 6), rows, cols, npanels, panel_rows, rowptr, colidx, a, tail, info,
+                   cls, epoch, bitmap[threadIdx.x >> 6]);
 }
 // Stage 1 and the panel classifier in one launch (the fused C-ABI entry: both depend only on the call's inputs, and
 // the classifier's dependent loads hide behind the staging traffic): the first ceil(npanels / 4) workgroups
@@ -557,8 +565,7 @@ __global__ __launch_bounds__(256) void stage_classify_kernel(int64_t cols, int64
                                                             int64_t ldb, double *__restrict__ Bt, int64_t ldbt,
                                                             int stage_blocks, int rows, int npanels, int panel_rows,
                                                             const int *__restrict__ rowptr,
-                                                            const int *__restrict__ colidx, int max_row_len,
-                                                            float min_density, float min_rowlen, float mfma_min_fill, int merge_probe,
+                                                            const int *__restrict__ colidx, ClassifyArgs a,
                                                             int *__restrict__ tail, int2 *__restrict__ info,
                                                             int *__restrict__ cls, int epoch)
 {
@@ -572,9 +579,8 @@ __global__ __launch_bounds__(256) void stage_classify_kernel(int64_t cols, int64
         stage_tile<RB>(tile, (int64_t)((int)blockIdx.x - cblocks) * STAGE_K, (int64_t)blockIdx.y * 64, cols, n, B, ldb, Bt,
                        ldbt, tail, epoch);
     } else if (blockIdx.y == 0) {
-        classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, (int)cols, npanels, panel_rows, rowptr, colidx,
-                       max_row_len, min_density, min_rowlen, mfma_min_fill, merge_probe, tail, info, cls, epoch,
-                       reinterpret_cast<unsigned *>(&tile[0][0]) + (threadIdx.x >> 6) * MFMA_BITMAP_WORDS);
+        classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, (int)cols, npanels, panel_rows, rowptr, colidx, a,
+                       tail, info, cls, epoch, reinterpret_cast<unsigned *>(&tile[0][0]) + (threadIdx.x >> 6) * MFMA_BITMAP_WORDS);
     }
 }
 // The same for a row block: the classifier rides with the column-range pass (both read only A); the staging launch
@@ -582,8 +588,7 @@ __global__ __launch_bounds__(256) void stage_classify_kernel(int64_t cols, int64
 __global__ __launch_bounds__(256) void colrange_classify_kernel(int64_t nnz, int2 *__restrict__ part, int nparts, int rows,
                                                                int cols, int npanels, int panel_rows,
                                                                const int *__restrict__ rowptr,
-                                                               const int *__restrict__ colidx, int max_row_len,
-                                                               float min_density, float min_rowlen, float mfma_min_fill, int merge_probe,
+                                                               const int *__restrict__ colidx, ClassifyArgs a,
                                                                int *__restrict__ tail, int2 *__restrict__ info,
                                                                int *__restrict__ cls, int epoch)
 {
@@ -592,9 +597,8 @@ __global__ __launch_bounds__(256) void colrange_classify_kernel(int64_t nnz, int
     if ((int)blockIdx.x >= cblocks)
         colrange_part(nnz, colidx, part, (int)blockIdx.x - cblocks, nparts, reinterpret_cast<int2 *>(bitmaps));
     else
-        classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, cols, npanels, panel_rows, rowptr, colidx,
-                       max_row_len, min_density, min_rowlen, mfma_min_fill, merge_probe, tail, info, cls, epoch,
-                       bitmaps + (threadIdx.x >> 6) * MFMA_BITMAP_WORDS);
+        classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, cols, npanels, panel_rows, rowptr, colidx, a, tail,
+                       info, cls, epoch, bitmaps + (threadIdx.x >> 6) * MFMA_BITMAP_WORDS);
 }
 // ... and for narrow blocks (no matrix cores, no row-merging probe there)
 template <int NC, bool RB>
@@ -602,17 +606,16 @@ __global__ __launch_bounds__(256) void stage_classify_narrow_kernel(int64_t cols
                                                                    int64_t ldb, double *__restrict__ Bt, int rows,
                                                                    int npanels, int panel_rows,
                                                                    const int *__restrict__ rowptr,
-                                                                   const int *__restrict__ colidx, int max_row_len,
-                                                                   float min_density, float min_rowlen, int *__restrict__ tail,
-                                                                   int2 *__restrict__ info, int *__restrict__ cls,
-                                                                   int epoch)
+                                                                   const int *__restrict__ colidx, ClassifyArgs a,
+                                                                   int *__restrict__ tail, int2 *__restrict__ info,
+                                                                   int *__restrict__ cls, int epoch)
 {
     const int cblocks = (npanels + 3) / 4;
     if ((int)blockIdx.x >= cblocks)
         stage_rows_narrow<NC, RB>((int64_t)((int)blockIdx.x - cblocks) * 256, cols, n, B, ldb, Bt, tail, epoch);
     else
         classify_panel((int)blockIdx.x * 4 + (threadIdx.x >> 6), rows, (int)cols, npanels, panel_rows, rowptr, colidx,
-                       max_row_len, min_density, min_rowlen, 2.0f, 0, tail, info, cls, epoch, nullptr);
+                       ClassifyArgs{a.max_row_len, a.min_density, a.min_rowlen, 2.0f, 0}, tail, info, cls, epoch, nullptr);
 }
 // The stage-2 kernels run one after the other, so a matrix whose panels split between the matrix-core kernel and the
 // vector kernels pays for two half-empty launches (block-structured rows at the fill threshold, N = 128: 1.05 ms against
@@ -2621,6 +2624,7 @@ static void panel_plan(int rows, int64_t ldbt, int &info_rows, int &groups)
 }
 
 static std::atomic<int> g_epoch{1}; // tags one call's classifier verdicts and one staging pass (see classify_panel)
+static int next_epoch() { return g_epoch.fetch_add(1, std::memory_order_relaxed); }
 
 // The workspace behind the staging copy (kernels.h): header ints, one span per panel, one class per panel.
 struct Tail {
@@ -2662,14 +2666,14 @@ static float window_min_density(int panel_rows) { return options().window_densit
 // Nonzeros per row a panel must average to take the narrow LDS-tiled kernel (0 at 64+ staged columns).  Measured on banded rows
 // (tools/spmm_shapes.py banded:ROWS:PERROW:HALFBAND, 1 M rows) against the kernels that take the panel otherwise:
 // gpurun_out/r3_narrow_shapes*.txt, DESIGN 3.9.
-// (declared in kernels.h) A narrow call whose rows average less than three quarters of the bar does not classify at all: the classifier,
+// A narrow call whose rows average less than three quarters of the bar does not classify at all: the classifier,
 // an LDS-tiled launch that every workgroup leaves at once and the per-row ownership test of the direct kernel cost a
 // 1 M-row matrix of 5 nonzeros per row 0.23 ms of a 0.09 ms product (N = 8).
 static float window_min_rowlen(int64_t ldbt);
 // what the classifier looks at for the direct kernels' sake (128+ staged columns): bit 0 rows that share column patterns
 // (row-merging kernel), bit 1 column runs / row-length spread (row per wave or four rows per wave)
 static int direct_probe(int64_t ldbt) { return ldbt >= 128 ? (options().direct_merge ? 3 : 2) : 0; }
-bool classify_worthwhile(int64_t rows, int64_t nnz, int64_t ldbt)
+static bool classify_worthwhile(int64_t rows, int64_t nnz, int64_t ldbt)
 {
     // (128+ staged columns: the classifier also feeds the matrix-core and row-merging choices; a forced matrix-core run
     //  needs its verdicts at any width)
@@ -2722,82 +2726,154 @@ hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, cons
                                     double *Bt, int64_t ldbt, bool row_b)
 {
     int *hdr = reinterpret_cast<int *>(Bt + (size_t)(cols + 1) * (size_t)ldbt);
-    const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
+    const int epoch = next_epoch();
     if (row_b) launch_stage_full<true>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
     else launch_stage_full<false>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
     return hipGetLastError();
 }
 
-// Stage 1 of a row block: only the rows of B its nonzeros refer to.  With classify != 0 the panel classifier rides in
-// the column-range launch and *epoch_out goes to launch_spmm_rowpanel; otherwise *epoch_out = 0.
-hipError_t launch_stage_range(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                              int64_t ldbt, int rows, int64_t nnz, const int *rowptr, const int *colidx, int variant,
-                              int classify, int *epoch_out, bool row_b)
+// ---------------------------------------------------------------------------------------------
+// What a column chunk of an SpMM call does before stage 2, decided once (spmm_step) and carried out by launch_stage and
+// launch_spmm_rowpanel.  A plan (sblas_hip_spmm_plan_create) keeps the verdicts of the decision it asked for here.
+// ---------------------------------------------------------------------------------------------
+// SBLAS_SPMM_VARIANT: "dpp" and "rows" pin a direct kernel at every width, "merge" at 64+ staged columns (where the
+// row-merging kernel exists) and "lanes" at narrow ones (the lane-group kernel): no panel is classified there
+static bool variant_classifies(int v, int64_t ldbt)
 {
-    const Tail t = tail_of(Bt, cols, ldbt, rows);
-    const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>((nnz + 4095) / 4096, TAIL_PARTS));
-    // *epoch_out != 0 on entry: a later column chunk of the same call (same A, same ldbt, same workspace): the column
-    // range and the panel verdicts in the tail still stand, only B's next columns need staging
-    const bool again = *epoch_out != 0;
-    const int epoch = again ? *epoch_out : g_epoch.fetch_add(1, std::memory_order_relaxed);
-    if (!again && classify) {
-        int info_rows = 0, g = 2;
-        panel_plan(rows, ldbt, info_rows, g);
-        const int np = (rows + info_rows - 1) / info_rows;
-        hipLaunchKernelGGL(colrange_classify_kernel, dim3((unsigned)((np + 3) / 4 + nparts)), dim3(256), 0, s, nnz, t.parts,
-                           nparts, rows, (int)cols, np, info_rows, rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt),
-                           mfma_min_fill(variant, info_rows, ldbt), direct_probe(ldbt), t.hdr,
-                           t.info, t.cls, epoch);
-    } else if (!again) {
-        hipLaunchKernelGGL(colrange_kernel, dim3(nparts), dim3(256), 0, s, nnz, colidx, t.parts);
-    }
-    const int64_t tiles = ((cols + 1 + STAGE_K - 1) / STAGE_K) * ((ldbt + 63) / 64);
-    // (a staging pass has an epoch of its own: "B holds a non-finite value" must not stick to the later column chunks of
-    //  the call, which reuse the first chunk's classifier epoch)
-    const int stage_epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
-    const dim3 sgrid((unsigned)std::min<int64_t>(tiles, 2048));
-    if (row_b)
-        hipLaunchKernelGGL(stage_range_kernel<true>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, t.hdr, t.parts, nparts,
-                           stage_epoch);
-    else
-        hipLaunchKernelGGL(stage_range_kernel<false>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, t.hdr, t.parts, nparts,
-                           stage_epoch);
-    *epoch_out = (classify || again) ? epoch : 0;
-    return hipGetLastError();
+    return v != SPMM_VARIANT_DIRECT_DPP && v != SPMM_VARIANT_DIRECT_ROWS &&
+           v != (ldbt >= 64 ? SPMM_VARIANT_DIRECT_MERGE : SPMM_VARIANT_LANES);
+}
+// ... and only the variants that pin no kernel at any width take a plan
+static bool variant_plannable(int v)
+{
+    return v == SPMM_VARIANT_AUTO || v == SPMM_VARIANT_MFMA || v == SPMM_VARIANT_NO_MFMA;
+}
+// a staging copy of ldbt columns beyond the 32-bit byte offsets the 16- / 32-column direct kernel addresses Bt with
+static bool bt_beyond_32bit(int64_t cols, int64_t ldbt) { return ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull; }
+// Staging traffic saved if a row block's columns span no more than twice its rows, against the extra pass over the column
+// indices and one more launch (~5 us = 40 MB at staging speed; a quarter of nd24k at N = 128 breaks even, an eighth of a
+// Queen-like matrix at N = 256 runs 1.5x faster: tools/spmm_shapes.py --block)
+static bool range_staging_pays(int64_t rows, int64_t cols, int64_t nnz, int64_t ldbt)
+{
+    return cols > 2 * rows && (uint64_t)(cols - 2 * rows) * (uint64_t)ldbt * 16ull > (uint64_t)nnz * 8ull + (40ull << 20);
+}
+static int range_parts(int64_t nnz) { return (int)std::max<int64_t>(1, std::min<int64_t>((nnz + 4095) / 4096, TAIL_PARTS)); }
+static ClassifyArgs classify_args(int panel_rows, int64_t ldbt)
+{
+    return {1 << 24, window_min_density(panel_rows), window_min_rowlen(ldbt),
+            ldbt < 64 ? 2.0f : mfma_min_fill(options().spmm_variant, panel_rows, ldbt), direct_probe(ldbt)};
 }
 
-// Stage 1 + classifier of the default path in one launch; the epoch goes to launch_spmm_rowpanel.
-hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                                 int64_t ldbt, int rows, const int *rowptr, const int *colidx, int variant,
-                                 int *epoch_out, bool row_b)
+SpmmStep spmm_step(int rows, int cols, int64_t nnz, int64_t ldbt, const PlanView *pv, const SpmmStep &prev, bool caller_staged)
 {
-    int info_rows = 0, g = 2;
-    panel_plan(rows, ldbt, info_rows, g);
-    const int np = (rows + info_rows - 1) / info_rows;
-    const int stage_blocks = (int)((cols + 1 + STAGE_K - 1) / STAGE_K);
-    const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
-    const Tail t = tail_of(Bt, cols, ldbt, rows);
-    if (ldbt < 64) {
-        const dim3 ngrid((unsigned)((cols + 1 + 255) / 256 + (np + 3) / 4));
+    SpmmStep st;
+    st.ldbt = ldbt;
+    st.pv = pv;
+    if (pv) { // classified, voted on and counted once: only B is left to stage
+        st.staging = STAGE_PLANNED, st.verdicts = VERDICTS_PLAN;
+        st.info_rows = pv->info_rows, st.groups = pv->groups, st.epoch = pv->epoch;
+        st.npanels = (rows + st.info_rows - 1) / st.info_rows;
+        return st;
+    }
+    const Options &opt = options();
+    const bool classify = variant_classifies(opt.spmm_variant, ldbt) && (ldbt >= 64 || !bt_beyond_32bit(cols, ldbt)) &&
+                          classify_worthwhile(rows, nnz, ldbt);
+    // a row block (method 2): the row-major copy covers only the rows of B the block's nonzeros refer to
+    const bool range = !caller_staged && ldbt >= 64 &&
+                       (opt.stage_range > 0 || (opt.stage_range < 0 && range_staging_pays(rows, cols, nnz, ldbt)));
+    // the classifier rides in the staging launch (one launch and one gap less per call) wherever there is one
+    st.staging = caller_staged ? STAGE_CALLER : range ? STAGE_RANGE : classify ? STAGE_FUSED : STAGE_FULL;
+    st.plannable = classify && !caller_staged && variant_plannable(opt.spmm_variant);
+    if (classify) {
+        panel_plan(rows, ldbt, st.info_rows, st.groups);
+        st.npanels = (rows + st.info_rows - 1) / st.info_rows;
+    }
+    // a later column chunk of a range-staged call (same A, same ldbt, same workspace): the column range and the panel
+    // verdicts in the tail still stand, only B's next columns need staging
+    const bool again = classify && range && prev.staging == STAGE_RANGE && prev.verdicts != VERDICTS_NONE && prev.ldbt == ldbt;
+    st.verdicts = !classify ? VERDICTS_NONE : again ? VERDICTS_EARLIER : caller_staged ? VERDICTS_SEPARATE : VERDICTS_STAGING;
+    st.epoch = again ? prev.epoch : next_epoch();
+    return st;
+}
+
+// the column-range pass of a row block, with the panel classifier riding along (both read only A)
+static void launch_colrange(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr,
+                            const int *colidx, const Tail &t, bool classify)
+{
+    const int nparts = range_parts(nnz);
+    if (classify)
+        hipLaunchKernelGGL(colrange_classify_kernel, dim3((unsigned)((st.npanels + 3) / 4 + nparts)), dim3(256), 0, s, nnz,
+                           t.parts, nparts, rows, cols, st.npanels, st.info_rows, rowptr, colidx,
+                           classify_args(st.info_rows, st.ldbt), t.hdr, t.info, t.cls, st.epoch);
+    else
+        hipLaunchKernelGGL(colrange_kernel, dim3(nparts), dim3(256), 0, s, nnz, colidx, t.parts);
+}
+
+// The verdicts stage 2 reads: a classifier launch of its own where no staging launch carried one, then the matrix-wide
+// vote (128+ staged columns only: 64-column calls have neither the matrix-core nor the row-merging choice)
+static void launch_verdicts(hipStream_t s, const SpmmStep &st, int rows, int cols, const int *rowptr, const int *colidx,
+                            const Tail &t, bool classify)
+{
+    if (classify)
+        hipLaunchKernelGGL(classify_panels_kernel, dim3((unsigned)((st.npanels + 3) / 4)), dim3(256), 0, s, rows, cols,
+                           st.npanels, st.info_rows, rowptr, colidx, classify_args(st.info_rows, st.ldbt), t.hdr, t.info,
+                           t.cls, st.epoch);
+    if (st.ldbt >= 128)
+        hipLaunchKernelGGL(mfma_vote_kernel, dim3(1), dim3(1024), 0, s, st.npanels, t.hdr, t.info, t.cls, st.epoch,
+                           options().spmm_variant == SPMM_VARIANT_MFMA ? 1 : 0);
+}
+
+// Stage 1 of a chunk.  The flags "B holds a non-finite value" go to the header the stage-2 kernels of the call look at
+// (the plan's for a planned call) under an epoch of the staging pass's own, so that they stick neither to the later
+// column chunks of the call, which may reuse the first chunk's verdicts, nor to later calls of a plan; the fused launch
+// stamps the step's epoch into both.
+hipError_t launch_stage(hipStream_t s, const SpmmStep &st, int rows, int64_t cols, int64_t nnz, const int *rowptr,
+                        const int *colidx, int64_t n, const double *B, int64_t ldb, double *Bt, bool row_b)
+{
+    const int64_t ldbt = st.ldbt;
+    const Tail t = st.pv ? tail_at(st.pv->tail, rows) : tail_of(Bt, cols, ldbt, rows);
+    if (st.staging == STAGE_FUSED) {
+        const int np = st.npanels, epoch = st.epoch;
+        const ClassifyArgs ca = classify_args(st.info_rows, ldbt);
+        if (ldbt < 64) {
+            const dim3 ngrid((unsigned)((cols + 1 + 255) / 256 + (np + 3) / 4));
 #define SBLAS_STAGE_NARROW(NC, RB)                                                                                     \
-    hipLaunchKernelGGL((stage_classify_narrow_kernel<NC, RB>), ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, rows, np, info_rows, \
-                       rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt), t.hdr, t.info, t.cls, epoch)
-        if (ldbt == 8) { if (row_b) SBLAS_STAGE_NARROW(8, true); else SBLAS_STAGE_NARROW(8, false); }
-        else if (ldbt == 16) { if (row_b) SBLAS_STAGE_NARROW(16, true); else SBLAS_STAGE_NARROW(16, false); }
-        else { if (row_b) SBLAS_STAGE_NARROW(32, true); else SBLAS_STAGE_NARROW(32, false); }
+    hipLaunchKernelGGL((stage_classify_narrow_kernel<NC, RB>), ngrid, dim3(256), 0, s, cols, n, B, ldb, Bt, rows, np,       \
+                       st.info_rows, rowptr, colidx, ca, t.hdr, t.info, t.cls, epoch)
+            if (ldbt == 8) { if (row_b) SBLAS_STAGE_NARROW(8, true); else SBLAS_STAGE_NARROW(8, false); }
+            else if (ldbt == 16) { if (row_b) SBLAS_STAGE_NARROW(16, true); else SBLAS_STAGE_NARROW(16, false); }
+            else { if (row_b) SBLAS_STAGE_NARROW(32, true); else SBLAS_STAGE_NARROW(32, false); }
 #undef SBLAS_STAGE_NARROW
-        *epoch_out = epoch;
+            return hipGetLastError();
+        }
+        const int stage_blocks = (int)((cols + 1 + STAGE_K - 1) / STAGE_K);
+        const dim3 grid((unsigned)(stage_blocks + (np + 3) / 4), (unsigned)((ldbt + 63) / 64));
+        if (row_b)
+            hipLaunchKernelGGL(stage_classify_kernel<true>, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, stage_blocks, rows,
+                               np, st.info_rows, rowptr, colidx, ca, t.hdr, t.info, t.cls, epoch);
+        else
+            hipLaunchKernelGGL(stage_classify_kernel<false>, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, stage_blocks, rows,
+                               np, st.info_rows, rowptr, colidx, ca, t.hdr, t.info, t.cls, epoch);
         return hipGetLastError();
     }
-    dim3 grid((unsigned)(stage_blocks + (np + 3) / 4), (unsigned)((ldbt + 63) / 64));
-#define SBLAS_STAGE_WIDE(RB)                                                                                           \
-    hipLaunchKernelGGL(stage_classify_kernel<RB>, grid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, stage_blocks, rows, np,  \
-                       info_rows, rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt),        \
-                       ldbt < 64 ? 2.0f : mfma_min_fill(variant, info_rows, ldbt),                                       \
-                       direct_probe(ldbt), t.hdr, t.info, t.cls, epoch)
-    if (row_b) SBLAS_STAGE_WIDE(true); else SBLAS_STAGE_WIDE(false);
-#undef SBLAS_STAGE_WIDE
-    *epoch_out = epoch;
+    if (st.staging == STAGE_RANGE && st.verdicts != VERDICTS_EARLIER)
+        launch_colrange(s, st, rows, (int)cols, nnz, rowptr, colidx, t, st.verdicts == VERDICTS_STAGING);
+    const int stage_epoch = next_epoch();
+    if (st.staging == STAGE_RANGE || (st.staging == STAGE_PLANNED && st.pv->use_range)) {
+        const int nparts = st.pv ? st.pv->nparts : range_parts(nnz);
+        const int64_t tiles = ((cols + 1 + STAGE_K - 1) / STAGE_K) * ((ldbt + 63) / 64);
+        const dim3 sgrid((unsigned)std::min<int64_t>(tiles, 2048));
+        if (row_b)
+            hipLaunchKernelGGL(stage_range_kernel<true>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, t.hdr, t.parts, nparts,
+                               stage_epoch);
+        else
+            hipLaunchKernelGGL(stage_range_kernel<false>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, t.hdr, t.parts, nparts,
+                               stage_epoch);
+    } else if (row_b) {
+        launch_stage_full<true>(s, cols, n, B, ldb, Bt, ldbt, t.hdr, stage_epoch);
+    } else {
+        launch_stage_full<false>(s, cols, n, B, ldb, Bt, ldbt, t.hdr, stage_epoch);
+    }
     return hipGetLastError();
 }
 
@@ -2807,38 +2883,25 @@ hipError_t launch_stage_classify(hipStream_t s, int64_t cols, int64_t n, const d
 // ---------------------------------------------------------------------------------------------
 size_t plan_tail_bytes(int64_t rows) { return workspace_tail_bytes(rows); }
 
-hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx, int64_t ldbt,
-                      int variant, bool use_range, PlanView *pv, std::vector<int> *cls_out)
+hipError_t plan_build(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
+                      PlanView *pv, std::vector<int> *cls_out)
 {
     const Tail t = tail_at(pv->tail, rows);
-    int info_rows = 0, g = 2;
-    panel_plan(rows, ldbt, info_rows, g);
-    const int np = (rows + info_rows - 1) / info_rows;
-    const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
-    const float fill = ldbt < 64 ? 2.0f : mfma_min_fill(variant, info_rows, ldbt);
-    const int probe = direct_probe(ldbt);
+    const int np = st.npanels;
+    const bool use_range = st.staging == STAGE_RANGE;
     hipError_t e = hipMemsetAsync(t.hdr, 0, TAIL_HDR * sizeof(int), s);
     if (e != hipSuccess) return e;
-    const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>((nnz + 4095) / 4096, TAIL_PARTS));
-    if (use_range)
-        hipLaunchKernelGGL(colrange_classify_kernel, dim3((unsigned)((np + 3) / 4 + nparts)), dim3(256), 0, s, nnz, t.parts,
-                           nparts, rows, cols, np, info_rows, rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt), fill,
-                           probe, t.hdr, t.info, t.cls, epoch);
-    else
-        hipLaunchKernelGGL(classify_panels_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, rows, cols, np, info_rows,
-                           rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt), fill, probe, t.hdr, t.info, t.cls, epoch);
-    if (ldbt >= 128)
-        hipLaunchKernelGGL(mfma_vote_kernel, dim3(1), dim3(1024), 0, s, np, t.hdr, t.info, t.cls, epoch,
-                           variant == SPMM_VARIANT_MFMA ? 1 : 0);
+    if (use_range) launch_colrange(s, st, rows, cols, nnz, rowptr, colidx, t, true);
+    launch_verdicts(s, st, rows, cols, rowptr, colidx, t, !use_range);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // the one look the host takes
     std::vector<int> hdr(TAIL_HDR), cls(np);
     if ((e = hipMemcpyAsync(hdr.data(), t.hdr, TAIL_HDR * sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(cls.data(), t.cls, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    pv->epoch = epoch;
-    pv->info_rows = info_rows;
-    pv->groups = g;
+    pv->epoch = st.epoch;
+    pv->info_rows = st.info_rows;
+    pv->groups = st.groups;
     pv->n_window = pv->n_direct = pv->n_mfma_w = pv->n_mfma_d = 0;
     for (int p = 0; p < np; ++p) { // (a panel without nonzeros is PANEL_DIRECT: the direct kernel writes its beta * C)
         const int c = cls[p] & PANEL_CLASS_MASK;
@@ -2847,34 +2910,12 @@ hipError_t plan_build(hipStream_t s, int rows, int cols, int64_t nnz, const int 
         pv->n_mfma_w += c == PANEL_MFMA_W;
         pv->n_mfma_d += c == PANEL_MFMA_D;
     }
-    pv->merge = ldbt >= 128 && hdr[TAIL_MERGE_EPOCH] == epoch;
-    pv->four_rows = ldbt >= 128 && !pv->merge && hdr[TAIL_ROWS_EPOCH] == epoch;
+    pv->merge = st.ldbt >= 128 && hdr[TAIL_MERGE_EPOCH] == st.epoch;
+    pv->four_rows = st.ldbt >= 128 && !pv->merge && hdr[TAIL_ROWS_EPOCH] == st.epoch;
     pv->use_range = use_range;
-    pv->nparts = nparts;
+    pv->nparts = range_parts(nnz);
     if (cls_out) cls_out->swap(cls);
     return hipSuccess;
-}
-
-// stage 1 of a planned call: the flags "B holds a non-finite value" go to the PLAN's header (where the stage-2 kernels
-// of the call look), the copy covers the plan's column range when the plan has one
-hipError_t launch_stage_planned(hipStream_t s, int64_t cols, int64_t n, const double *B, int64_t ldb, double *Bt,
-                                int64_t ldbt, const PlanView &pv, bool row_b)
-{
-    const int epoch = g_epoch.fetch_add(1, std::memory_order_relaxed);
-    int *hdr = pv.tail;
-    if (pv.use_range && ldbt >= 64) {
-        const int64_t tiles = ((cols + 1 + STAGE_K - 1) / STAGE_K) * ((ldbt + 63) / 64);
-        const dim3 sgrid((unsigned)std::min<int64_t>(tiles, 2048));
-        const int2 *parts = reinterpret_cast<const int2 *>(hdr + TAIL_HDR);
-        if (row_b)
-            hipLaunchKernelGGL(stage_range_kernel<true>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, parts, pv.nparts, epoch);
-        else
-            hipLaunchKernelGGL(stage_range_kernel<false>, sgrid, dim3(256), 0, s, cols, n, B, ldb, Bt, ldbt, hdr, parts, pv.nparts, epoch);
-        return hipGetLastError();
-    }
-    if (row_b) launch_stage_full<true>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
-    else launch_stage_full<false>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
-    return hipGetLastError();
 }
 
 // A direct kernel K<TA...> (TA in parentheses), or -- for a split plan's call, `skip` != null -- its SKIP instantiation
@@ -2934,11 +2975,14 @@ static void launch_split(hipStream_t s, int cols, const int *colidx, const doubl
 }
 
 template <bool RC>
-static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
-                                const double *val, const double *Bt, int64_t ldbt, int n, double alpha,
-                                double beta, double *C, int64_t ldc, int variant, int pre_epoch, const PlanView *pv)
+static hipError_t spmm_rowpanel(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr,
+                                const int *colidx, const double *val, const double *Bt, int n, double alpha, double beta,
+                                double *C, int64_t ldc)
 {
     const Options &opt = options();
+    const int variant = opt.spmm_variant;
+    const int64_t ldbt = st.ldbt;
+    const PlanView *pv = st.pv;
     const double avg_row = rows > 0 ? (double)nnz / (double)rows : 0.0;
     const int dpp_long = opt.tune[2] > 0 ? opt.tune[2] : DPP_LONG; // (SBLAS_TUNE=*,*,<entries>: A/B runs of the long-row split)
     // a planned call (pv): the verdicts sit in the plan's buffer, nothing is classified or voted on, and only the kernels
@@ -2948,36 +2992,16 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
     const bool need_direct = !pv || pv->n_direct + pv->n_mfma_d > 0;
     // a split plan: the direct kernels' SKIP instantiations, then the split kernels
     const unsigned *skip = pv && pv->n_split > 0 ? pv->split_bits : nullptr;
+    const Tail t = pv ? tail_at(pv->tail, rows) : tail_of(Bt, cols, ldbt, rows);
+    // 1. the panel verdicts (spmm_step says where they come from); 2. LDS-tiled kernel and matrix-core kernel on the
+    // panels that qualify; 3. a direct kernel on the rest -- on everything when nothing is classified
+    const bool classified = st.verdicts != VERDICTS_NONE;
+    const int *cls = classified ? t.cls : nullptr;
+    const int info_rows = st.info_rows, np = st.npanels, epoch = st.epoch;
+    if (classified && !pv) launch_verdicts(s, st, rows, cols, rowptr, colidx, t, st.verdicts == VERDICTS_SEPARATE);
     if (ldbt >= 64) {
-        const Tail t = pv ? tail_at(pv->tail, rows) : tail_of(Bt, cols, ldbt, rows);
-        const int *cls = nullptr;
-        int info_rows = 1;
-        // pre_epoch != 0: launch_stage_classify has classified the panels already
-        // (64 staged columns and short rows throughout: everything goes to the four-rows-per-wave kernel unclassified)
-        const bool classified = pv || (variant != SPMM_VARIANT_DIRECT_DPP && variant != SPMM_VARIANT_DIRECT_ROWS &&
-                                       variant != SPMM_VARIANT_DIRECT_MERGE &&
-                                       (pre_epoch != 0 || classify_worthwhile(rows, nnz, ldbt)));
-        const bool preclassified = pv || (pre_epoch != 0 && classified);
-        const int epoch = pv ? pv->epoch : preclassified ? pre_epoch : g_epoch.fetch_add(1, std::memory_order_relaxed);
         if (classified) {
-            // 1. classify row panels; 2. LDS-tiled kernel and matrix-core kernel on the panels that qualify;
-            // 3. direct kernel on the rest
-            int gen6_g = 2;
-            panel_plan(rows, ldbt, info_rows, gen6_g);
-            if (pv) info_rows = pv->info_rows, gen6_g = pv->groups;
-            const int np = (rows + info_rows - 1) / info_rows;
-            if (!preclassified)
-                hipLaunchKernelGGL(classify_panels_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, rows, cols, np,
-                                   info_rows, rowptr, colidx, /* 32-bit buffer offsets inside a wave's rows */ 1 << 24,
-                                   /* a (row, tile) visit costs what ~8 nonzeros cost in the direct kernel: ask for 8
-                                      per row and 128-column tile on average */
-                                   window_min_density(info_rows), window_min_rowlen(ldbt), mfma_min_fill(variant, info_rows, ldbt),
-                                   direct_probe(ldbt), t.hdr, t.info, t.cls, epoch);
             const bool mfma_possible = mfma_min_fill(variant, info_rows, ldbt) <= 1.0f;
-            // matrix-wide decisions before stage 2 (128+ staged columns only: 64-column calls have neither choice)
-            if (ldbt >= 128 && !pv)
-                hipLaunchKernelGGL(mfma_vote_kernel, dim3(1), dim3(1024), 0, s, np, t.hdr, t.info, t.cls, epoch,
-                                   variant == SPMM_VARIANT_MFMA ? 1 : 0);
             // 128+ staged columns: two 64-column halves per workgroup, the selection work of a (rows, tile) visit shared
             // (SBLAS_TUNE=*,1 keeps one half per workgroup: A/B runs)
             const bool two_halves = ldbt >= 128 && opt.tune[1] != 1;
@@ -2991,7 +3015,7 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
                            colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, t.info, t.cls, info_rows, (int)nnz); \
     } while (0)
             if (!need_window) {
-            } else if (gen6_g == 3) {
+            } else if (st.groups == 3) {
                 SBLAS_LAUNCH_W6(3, 1);
             } else {
                 if (two_halves) SBLAS_LAUNCH_W6(2, 2); else SBLAS_LAUNCH_W6(2, 1);
@@ -3006,7 +3030,6 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
                                                       t.info, t.hdr, t.cls, info_rows, np, epoch, panel_stats_device(), RC);
                 if (e != hipSuccess) return e;
             }
-            cls = t.cls;
         }
         const int wide_panels = (rows + WIDE_PANEL - 1) / WIDE_PANEL;
         // 128-column tiles: one workgroup per CU through unused dynamic LDS (Queen-like rows at N = 256: +13 %, banded
@@ -3056,24 +3079,10 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
     } else {
         // ---- narrow dense blocks (ldbt = 8 / 16 / 32): LDS-tiled lane-per-entry kernel on the panels that qualify,
         // a direct kernel on the rest
-        const Tail t = pv ? tail_at(pv->tail, rows) : tail_of(Bt, cols, ldbt, rows);
         // the 16- / 32-column direct kernel addresses Bt with 32-bit byte offsets
-        const bool wide_offsets = ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull;
-        const bool classified = pv || (!wide_offsets && variant != SPMM_VARIANT_DIRECT_DPP && variant != SPMM_VARIANT_DIRECT_ROWS &&
-                                       variant != SPMM_VARIANT_LANES && (pre_epoch != 0 || classify_worthwhile(rows, nnz, ldbt)));
-        const bool preclassified = pv || (pre_epoch != 0 && classified);
-        const int epoch = pv ? pv->epoch : preclassified ? pre_epoch : g_epoch.fetch_add(1, std::memory_order_relaxed);
-        const int *cls = nullptr;
-        int info_rows = 1;
+        const bool wide_offsets = bt_beyond_32bit(cols, ldbt);
         if (classified) {
-            int g = 2;
-            lanes_plan(rows, (int)ldbt, info_rows, g);
-            if (pv) info_rows = pv->info_rows, g = pv->groups;
-            const int np = (rows + info_rows - 1) / info_rows;
-            if (!preclassified)
-                hipLaunchKernelGGL(classify_panels_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, rows, cols, np,
-                                   info_rows, rowptr, colidx, 1 << 24, window_min_density(info_rows), window_min_rowlen(ldbt), 2.0f, 0, t.hdr, t.info,
-                                   t.cls, epoch);
+            const int g = st.groups;
             KernelEvents *kev = kernel_events_slot();
             if (kev) (void)hipEventRecord(kev->a, s);
 #define SBLAS_LAUNCH_LANES(NC, CP, GG) SBLAS_LAUNCH_LANES4(NC, CP, GG, 1)
@@ -3105,7 +3114,6 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
                 (void)hipEventRecord(kev->b, s);
                 kev->recorded = true;
             }
-            cls = t.cls;
         }
         const unsigned panels = (unsigned)((rows + PANEL_ROWS - 1) / PANEL_ROWS);
         // short rows leave most of a row-per-wave sweep empty: lane groups below 24 / 16 nonzeros per row on average at 16 / 32
@@ -3144,15 +3152,12 @@ static hipError_t spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, 
 #undef SBLAS_DIRECT_GO
 #undef SBLAS_UNPAREN
 
-hipError_t launch_spmm_rowpanel(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
-                                const double *val, const double *Bt, int64_t ldbt, int n, double alpha,
-                                double beta, double *C, int64_t ldc, int variant, int pre_epoch, const PlanView *pv,
-                                bool row_c)
+hipError_t launch_spmm_rowpanel(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr,
+                                const int *colidx, const double *val, const double *Bt, int n, double alpha, double beta,
+                                double *C, int64_t ldc, bool row_c)
 {
-    return row_c ? spmm_rowpanel<true>(s, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, variant,
-                                       pre_epoch, pv)
-                 : spmm_rowpanel<false>(s, rows, cols, nnz, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, variant,
-                                        pre_epoch, pv);
+    return row_c ? spmm_rowpanel<true>(s, st, rows, cols, nnz, rowptr, colidx, val, Bt, n, alpha, beta, C, ldc)
+                 : spmm_rowpanel<false>(s, st, rows, cols, nnz, rowptr, colidx, val, Bt, n, alpha, beta, C, ldc);
 }
 
 // device address of the panel census (the matrix-core kernel lives in another translation unit)

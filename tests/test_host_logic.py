@@ -203,6 +203,7 @@ def test_argument_validation_returns_codes_without_a_gpu(sblas):
     assert f(-1, None, 4, 4, 3, one, one, one, one, 3, 4, 1.0, 0.0, one, 4, one, 1 << 20) == 1      # ldb < cols
     assert f(-1, None, 4, 4, 3, one, one, one, one, 4, 4, 1.0, 0.0, one, 3, one, 1 << 20) == 1      # ldc < rows
     assert f(-1, None, 4, 4, 3, one, one, one, one, 4, 4, 1.0, 0.0, one, 4, None, 0) == 3           # no workspace
+    assert f(-1, None, 4, 4, 3, one, one, one, one, 4, 4, 1.0, 0.0, one, 4, C.c_void_p(24), 1 << 20) == 1   # Bt not 16-byte aligned: refused before any launch
     assert f(-1, None, 0, 4, 0, one, None, None, one, 4, 4, 1.0, 0.0, one, 4, None, 0) == 0         # empty: no-op
     assert L.sblas_hip_spmv_csr_f64_i32(-1, None, 4, 4, 3, one, one, one, None, 1.0, 0.0, one) == 1
     assert L.sblas_hip_axpby_f64(-1, None, -5, 1.0, one, 1.0, one) == 1
