@@ -12,8 +12,14 @@ A step    : one call of the drop-in boundary sblas_hip_spmm_csr_f64_i32 on devic
 Multi-GPU : one process per GPU.  Method 1 partitions the dense columns and has no exchange step
             (spmm.h:83-161), so rank r multiplies the full A by its own 64-column block: per-GPU work is fixed,
             "scaling": "weak", no collective in the data path.
-Extras    : (keys beside the contract's; the headline is never computed from them)
+Plain run : sets up, settles the clocks, warms up, times the K steps, writes --dump-outputs and prints the line (metric,
+            value, unit, higher_is_better, dtype, ms_per_step, the run's shape and config, hbm_gbs_whole_step).
+            Everything below, and the result checks against the oracle, run only with --full.
+Extras    : (--full; keys beside the contract's; the headline is never computed from them)
             cold_ms_per_step     the first ten steps after a pause (idle clocks), before the settling phase
+            roofline, planned    per-kernel times from ten extra steps through the split entry points; the same step
+                                 through a per-matrix plan
+            oracle_check         C = 1 + steps * A*B on 64-row windows against the oracle
             secondary            BASELINE config 5's shape on this GPU: Queen-like rows, 300 000 rows, N = 256
             product_merge        method 2 (spmm.h:163-284) through the PRODUCT's own merge (comm.hip: persistent RCCL
                                  communicator, packed row-block exchange / all-reduce), one process driving all GPUs like
@@ -22,6 +28,8 @@ Extras    : (keys beside the contract's; the headline is never computed from the
                                  the ranks are folded onto it (rehearsal of the code path, not a scaling figure).
             method2*             (N > 1) the same scheme with torch.distributed collectives, one process per GPU
             cpu_baseline         the oracle on this host's cores (N = 1 only)
+            --op spmv            its roofline comes from events around the timed steps themselves and stays in a plain
+                                 run; --full adds the check y = 1 + steps * rowsum(A)
 Output    : exactly one JSON line on rank 0.
 Dump      : --dump-outputs DIR writes what the timed path computed in its last step (C, or y with --op spmv) as
             DIR/<name>.npy, float64.  C and y enter the timed steps as ones, so with the same arguments the dump is the
@@ -258,10 +266,11 @@ def bench_spmv(args, torch, S, dev, dist, world, rank, name, rows, cols, nnz, rp
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: y_last}, world)
     if rank == 0:
-        rs = np.add.reduceat(v, rp[:-1].astype(np.int64)) if nnz else np.zeros(rows)
-        want = 1.0 + args.steps * rs
-        if not np.allclose(y_last, want, rtol=1e-9, atol=1e-9):
-            raise SystemExit("spmv bench result mismatch")
+        if args.full:
+            rs = np.add.reduceat(v, rp[:-1].astype(np.int64)) if nnz else np.zeros(rows)
+            want = 1.0 + args.steps * rs
+            if not np.allclose(y_last, want, rtol=1e-9, atol=1e-9):
+                raise SystemExit("spmv bench result mismatch")
         avg = nnz / max(rows, 1)
         sp_kernel = ("spmv_csr_lds_kernel" if avg > 96 else "spmv_csr_seg_kernel" if avg > 48 else
                      "spmv_csr_stream_kernel" if avg > 2.5 else "spmv_csr_kernel")
@@ -575,17 +584,21 @@ def main():
     ap.add_argument("--ncols", type=int, default=64, help="dense columns per GPU (method 1)")
     ap.add_argument("--matrix", type=str, default=None, help="MatrixMarket file instead of the synthetic stand-in")
     ap.add_argument("--scale", type=float, default=1.0, help="row-count scale of the synthetic stand-in (rehearsal only)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-method2", action="store_true", help="skip the torch.distributed method-2 sections (N > 1)")
-    ap.add_argument("--no-extras", action="store_true", help="skip `secondary` and `product_merge` (profiling runs)")
-    ap.add_argument("--merge-steps", type=int, default=6, help="timed steps of each product_merge section")
-    ap.add_argument("--queen-rows", type=int, default=300000, help="rows of the Queen-like shape in the extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: cold steps, per-kernel and planned times, "
+                         "oracle checks, other widths and shapes, method 2, product_merge, the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-method2", action="store_true", help="--full: skip the torch.distributed method-2 sections (N > 1)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip `method1_widths`, `secondary` and `product_merge` (profiling runs)")
+    ap.add_argument("--merge-steps", type=int, default=6, help="--full: timed steps of each product_merge section")
+    ap.add_argument("--queen-rows", type=int, default=300000, help="--full: rows of the Queen-like shape in the extras")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real thing); gloo + --fold-ranks rehearses the N>1 code path on one GPU")
     ap.add_argument("--fold-ranks", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--product-merge-child", type=str, default=None,
                     help="internal: run the product_merge sections on the given comma-separated devices and print their JSON")
-    ap.add_argument("--extras-timeout", type=float, default=420.0, help="seconds the product_merge child process may take")
+    ap.add_argument("--extras-timeout", type=float, default=420.0, help="--full: seconds the product_merge child process may take")
     ap.add_argument("--op", choices=["spmm", "spmv"], default="spmm",
                     help="spmm (the headline metric) or spmv (same matrix, x = y0 = 1; secondary measurement)")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
@@ -663,16 +676,17 @@ def main():
         # the drop-in boundary itself: sblas_hip_spmm_csr_f64_i32 (staging + classifier in one launch, then stage 2)
         S.spmm(rows, cols, rowptr, colidx, val, B, cols, n, 1.0, 1.0, C, rows, Bt)
 
-    # cold figure: the first ten steps this process issues (idle clocks; what a caller making a handful of calls sees)
-    torch.cuda.synchronize()
-    time.sleep(0.5)
-    S.panel_census()
-    c0 = time.perf_counter()
-    for _ in range(10):
-        step()
-    torch.cuda.synchronize()
-    cold_ms = (time.perf_counter() - c0) / 10 * 1e3
-    census = {k: c // 10 for k, c in S.panel_census().items()}
+    if args.full:
+        # cold figure: the first ten steps this process issues (idle clocks; what a caller making a handful of calls sees)
+        torch.cuda.synchronize()
+        time.sleep(0.5)
+        S.panel_census()
+        c0 = time.perf_counter()
+        for _ in range(10):
+            step()
+        torch.cuda.synchronize()
+        cold_ms = (time.perf_counter() - c0) / 10 * 1e3
+        census = {k: c // 10 for k, c in S.panel_census().items()}
 
     settled = 0 if args.no_settle else settle(torch, step)
     if dist is not None and not args.no_settle:
@@ -695,11 +709,38 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    C_last = C.clone() if args.dump_outputs else None   # the steps below go on accumulating into C
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    def dump_c(Cd):                                 # C as the caller sees it: rows x n, here in row-major order
+        dump_outputs(args.dump_outputs, {"C" if world == 1 else "C_rank%d" % rank: Cd.view(n, rows).cpu().numpy().T}, world)
+
+    flops_step = 2.0 * nnz * n                      # per GPU
+    value = world * flops_step * args.steps / elapsed / 1e9
+    alg = algorithmic_bytes(rows, cols, nnz, n, True)
+    out = {
+        "metric": "SpMM GFLOP/s (2*nnz*N/t), CSR x dense N=64, fp64",
+        "value": round(value, 2), "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "settle_steps": settled,   # untimed steps in front of the warm-up until the clocks have settled (see settle())
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not args.matrix else "file",
+        "config": {"workload": "SpMM method-1 (dense-B column partition), %s, nnz=%d, N=%d columns per GPU, alpha=beta=1, "
+                               "B = srand(211)/rand() as the reference's DenseMatrix, inputs resident in HBM; "
+                               "step = B->row-major staging + row-panel SpMM" % (name, nnz, n),
+                   "rows": rows, "cols": cols, "nnz": nnz, "n_cols_per_gpu": n, "parallelism": "method1-colblock x%d" % world},
+        "hbm_gbs_whole_step": round(alg / (elapsed / args.steps) / 1e9, 1),
+    }
+    if not args.full:                               # a plain run: the headline line and nothing more
+        if args.dump_outputs:
+            dump_c(C)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    C_last = C.clone() if args.dump_outputs else None   # the steps below go on accumulating into C
 
     # per-kernel times, ten extra steps straight after the timed region (clocks still settled) through the SPLIT entry
     # points (staging | classifier + stage 2 -- the same kernels, one launch more than the fused entry): an event
@@ -755,8 +796,8 @@ def main():
         t_dom = None                                 # the launcher's events bracket the LDS-tiled kernels only
     t_roof = t_dom if t_dom else t_stage2
 
-    if C_last is not None:                          # C as the caller sees it: rows x n, here in row-major order
-        dump_outputs(args.dump_outputs, {"C" if world == 1 else "C_rank%d" % rank: C_last.view(n, rows).cpu().numpy().T}, world)
+    if C_last is not None:
+        dump_c(C_last)
         del C_last
 
     # correctness guard on this rank's result: C = 1 + steps_total * A*B on 64-row windows (first panel, a middle one,
@@ -772,21 +813,9 @@ def main():
             if world == 1:
                 raise SystemExit(failures[0])
 
-    flops_step = 2.0 * nnz * n                      # per GPU
-    value = world * flops_step * args.steps / elapsed / 1e9
-    alg = algorithmic_bytes(rows, cols, nnz, n, True)
     traffic, traffic_src = (measured_traffic(kernel, rows, nnz, n)
                             if os.environ.get("SBLAS_SPMM_VARIANT", "") in ("", "auto") else (None, None))
-    out = {
-        "metric": "SpMM GFLOP/s (2*nnz*N/t), CSR x dense N=64, fp64",
-        "value": round(value, 2), "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "settle_steps": settled,   # untimed steps in front of the warm-up until the clocks have settled (see settle())
-        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not args.matrix else "file",
-        "config": {"workload": "SpMM method-1 (dense-B column partition), %s, nnz=%d, N=%d columns per GPU, alpha=beta=1, "
-                               "B = srand(211)/rand() as the reference's DenseMatrix, inputs resident in HBM; "
-                               "step = B->row-major staging + row-panel SpMM" % (name, nnz, n),
-                   "rows": rows, "cols": cols, "nnz": nnz, "n_cols_per_gpu": n, "parallelism": "method1-colblock x%d" % world},
+    out.update({
         "roofline": {"bound": "hbm", "kernel": kernel,
                      "achieved": round(alg / t_roof / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(alg / t_roof / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -797,11 +826,10 @@ def main():
                      "stage2_ms_min": round(float(np.min(s2)), 5),
                      "staging_kernel_ms": round(t_stage1 * 1e3, 5),
                      "kernel_gflops": round(flops_step / t_roof / 1e9, 1), "panels": census},
-        "hbm_gbs_whole_step": round(alg / (elapsed / args.steps) / 1e9, 1),
         "planned": planned,
         "cold_ms_per_step": round(cold_ms, 5),      # first ten steps of the process, idle clocks, host wall incl. launches
         "oracle_check": check, "oracle_max_abs_diff": check_err,
-    }
+    })
 
     # ---- method 1, STRONG scaling: BASELINE's metric is N = 64 in total, and method 1 hands GPU i the columns
     # [i * ceil(64 / g), ...) of B and C with the full A (matrix.h:554-568): 32 / 16 / 8 columns per GPU at g = 2 / 4 / 8.

@@ -11,7 +11,7 @@ for a in default; do
              "SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM_RD SQ_IFETCH SQ_WAIT_INST_LDS SQ_INSTS_BRANCH SQ_WAVE_CYCLES" \
              "GRBM_GUI_ACTIVE GRBM_COUNT"; do
     i=$((i+1))
-    rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/a${a}_set$i -- python3 $R/bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-extras > $OUT/a${a}_set$i.log 2>&1
+    rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/a${a}_set$i -- python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-extras > $OUT/a${a}_set$i.log 2>&1
     echo "ablate $a set$i rc=$?"
   done
 done
