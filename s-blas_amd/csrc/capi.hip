@@ -5,61 +5,11 @@
 // SBLAS_VALIDATE=1 / sblas_hip_debug_validate_csr_i32 check them on the device first, at the price of a synchronisation.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdlib.h>
-#include <string.h>
+#include <memory>
 #include <vector>
 #include "../../include/sblas_hip.h"
+#include "capi_util.h"
 #include "kernels.h"
-
-namespace {
-
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceScope(int dev)
-    {
-        if (dev < 0) return;
-        err = hipGetDevice(&prev);
-        if (err != hipSuccess) return;
-        if (prev != dev) {
-            err = hipSetDevice(dev);
-            switched = (err == hipSuccess);
-        }
-    }
-    ~DeviceScope()
-    {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-// the device a `dev` argument means (dev < 0: the calling thread's current device); -1 when that cannot be told
-inline int resolve_device(int dev)
-{
-    if (dev >= 0) return dev;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return -1;
-    return cur;
-}
-
-// dense operand layouts (SBLAS_COL_MAJOR / SBLAS_ROW_MAJOR)
-inline bool order_ok(int order) { return order == SBLAS_COL_MAJOR || order == SBLAS_ROW_MAJOR; }
-// leading dimension of a dense operand with `rows` rows and n columns: column-major needs ld >= rows, row-major ld >= n
-inline bool ld_ok(int order, int64_t ld, int64_t rows, int64_t n) { return ld >= (order == SBLAS_ROW_MAJOR ? n : rows); }
-// column j0 of a dense operand
-template <typename T> inline T *col_at(T *p, int order, int64_t ld, int64_t j0) { return p + (order == SBLAS_ROW_MAJOR ? j0 : j0 * ld); }
-
-inline bool csr_args_ok(int64_t rows, int64_t cols, int64_t nnz, const void *rowptr, const void *colidx,
-                        const void *val)
-{
-    if (rows < 0 || cols < 0 || nnz < 0) return false;
-    if (rows > INT_MAX - 64 || cols > INT_MAX || nnz > INT_MAX) return false; // int32 index API
-    if (!rowptr) return false;
-    if (nnz > 0 && (!colidx || !val)) return false;
-    return true;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -170,8 +120,6 @@ static int scale_only(int dev, void *stream, int64_t rows, int64_t n, double bet
                : SBLAS_E_HIP;
 }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; } // Bt: 16-byte tile loads
-
 int sblas_hip_spmm_csr_rowmajorB_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
                                          const int32_t *rowptr, const int32_t *colidx, const double *val,
                                          const double *Bt, int64_t ldbt, int64_t n, double alpha,
@@ -197,16 +145,38 @@ int sblas_hip_spmm_csr_rowmajorB_f64_i32(int dev, void *stream, int64_t rows, in
 static int validate_if_asked(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
                              const int32_t *colidx);
 
-// A plan: the panel verdicts of one matrix structure at one staged width, taken once (sblas_hip_spmm_plan_create).
-struct SpmmPlan {
+namespace {
+
+// What a plan speaks for: ONE structure -- the same arrays it was made from (their contents are the caller's promise) --
+// on the device its buffers live on.  A planned call for anything else is refused.
+struct PlanKey {
     int dev = -1;
-    int64_t rows = 0, cols = 0, nnz = 0, n = 0, ldbt = 0;
+    int64_t rows = 0, cols = 0, nnz = 0;
     const void *rowptr = nullptr, *colidx = nullptr;
-    bool active = false;      // false: nothing to plan (empty matrix, a pinned direct variant): calls run unplanned
-    void *buf = nullptr;
-    void *split_buf = nullptr; // a split plan's partial sums, row bitmap, pieces and split rows
+    bool speaks_for(int dev_arg, int64_t r, int64_t c, int64_t z, const void *rp, const void *ci) const
+    {
+        return dev == resolve_device(dev_arg) && rows == r && cols == c && nnz == z && rowptr == rp && colidx == ci;
+    }
+};
+
+// A plan: the panel verdicts of one matrix structure at one staged width, taken once (sblas_hip_spmm_plan_create).
+struct SpmmPlan : PlanKey {
+    int64_t n = 0, ldbt = 0;
+    bool active = false;        // false: nothing to plan (empty matrix, a pinned direct variant): calls run unplanned
+    DeviceBuffer buf;
+    DeviceBuffer split_buf;     // a split plan's partial sums, row bitmap, pieces and split rows
     sblas::PlanView pv;
 };
+
+// A per-matrix SpMV plan (sblas_hip_spmv_plan_create).  One device buffer: the partial sums of the split pieces (doubles)
+// first, then the int4 work items of the kernel classes, the pieces and the split rows.
+struct SpmvPlan : PlanKey {
+    bool active = false; // false: empty matrix or a pinned SBLAS_SPMV_VARIANT: calls run unplanned
+    DeviceBuffer buf;
+    sblas::SpmvPlanView pv;
+};
+
+} // namespace
 
 // The <f64, i32> SpMM of every entry point.  B and C each column- or row-major (order_b / order_c): B's layout reaches
 // only the staging launch, C's only the stage-2 epilogues; Bt, the workspace and the plan are the same for all four.
@@ -255,14 +225,6 @@ int sblas_hip_spmm_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t cols
 }
 
 // ---- per-matrix plan (the slot of cusparseSpMM_bufferSize / preprocess, spmm.h:134-141) --------------------------
-static int spmm_plan_fail(SpmmPlan *p, void **plan_out, int rc)
-{
-    if (p->buf) (void)hipFree(p->buf);
-    if (p->split_buf) (void)hipFree(p->split_buf);
-    delete p;
-    *plan_out = nullptr;
-    return rc;
-}
 
 // A split plan's long rows (sblas_hip_spmm_plan_create_split): the classifier on host copies of rowptr and the panel
 // verdicts, then one device buffer -- partial sums, row bitmap, pieces, split rows.
@@ -303,15 +265,16 @@ static hipError_t spmm_plan_split(SpmmPlan *p, hipStream_t s, const int32_t *row
     }
     const size_t partial_bytes = (size_t)n_pieces * (size_t)p->ldbt * sizeof(double);
     const size_t bits_bytes = (words * sizeof(unsigned) + 15) / 16 * 16;
-    if ((e = hipMalloc(&p->split_buf, partial_bytes + bits_bytes + (size_t)n_rec * sizeof(int4))) != hipSuccess) return e;
-    char *base = static_cast<char *>(p->split_buf);
-    pv.partial = reinterpret_cast<double *>(base);
-    pv.split_bits = reinterpret_cast<const unsigned *>(base + partial_bytes);
-    pv.pieces = reinterpret_cast<const int4 *>(base + partial_bytes + bits_bytes);
+    if ((e = p->split_buf.alloc(p->dev, partial_bytes + bits_bytes + (size_t)n_rec * sizeof(int4))) != hipSuccess) return e;
+    pv.partial = p->split_buf.at<double>();
+    pv.split_bits = p->split_buf.at<const unsigned>(partial_bytes);
+    pv.pieces = p->split_buf.at<const int4>(partial_bytes + bits_bytes);
     pv.srows = pv.pieces + n_pieces;
-    if ((e = hipMemcpyAsync(base + partial_bytes, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(base + partial_bytes + bits_bytes, rec.data(), (size_t)n_rec * sizeof(int4), hipMemcpyHostToDevice, s)) !=
-        hipSuccess)
+    if ((e = hipMemcpyAsync(p->split_buf.at<void>(partial_bytes), bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice,
+                            s)) != hipSuccess)
+        return e;
+    if ((e = hipMemcpyAsync(p->split_buf.at<void>(partial_bytes + bits_bytes), rec.data(), (size_t)n_rec * sizeof(int4),
+                            hipMemcpyHostToDevice, s)) != hipSuccess)
         return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e; // (the host images go next)
     pv.n_pieces = n_pieces, pv.n_split = n_split, pv.split_nnz = split_nnz;
@@ -322,32 +285,36 @@ static int spmm_plan_create(int dev, void *stream, int64_t rows, int64_t cols, i
                             const int32_t *colidx, int64_t n, bool split, int64_t split_min, int64_t piece, void **plan_out)
 {
     if (!plan_out || !csr_args_ok(rows, cols, nnz, rowptr, colidx, reinterpret_cast<const void *>(1)) || n < 0) return SBLAS_E_INVALID;
-    SpmmPlan *p = new SpmmPlan;
+    *plan_out = nullptr;
+    std::unique_ptr<SpmmPlan> p(new SpmmPlan);
     p->dev = resolve_device(dev), p->rows = rows, p->cols = cols, p->nnz = nnz, p->n = n, p->rowptr = rowptr, p->colidx = colidx;
-    *plan_out = p;
-    if (rows == 0 || cols == 0 || nnz == 0 || n == 0) return SBLAS_OK; // nothing to plan
+    if (rows == 0 || cols == 0 || nnz == 0 || n == 0) { // nothing to plan
+        *plan_out = p.release();
+        return SBLAS_OK;
+    }
     DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
     // the step of the first column chunk; where it classifies nothing (a pinned direct kernel, short rows, a narrow Bt
     // beyond 32-bit offsets) the calls run unplanned
     const int64_t w = spmm_chunk_cols(cols, n);
     const int64_t ldbt = chunk_ldbt(cols, n, n < w ? n : w);
     const sblas::SpmmStep st = sblas::spmm_step((int)rows, (int)cols, nnz, ldbt, nullptr);
-    if (!st.plannable) return SBLAS_OK;
-    if (hipMalloc(&p->buf, sblas::plan_tail_bytes(rows)) != hipSuccess) return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
-    p->pv.tail = static_cast<int *>(p->buf);
-    p->ldbt = ldbt;
-    std::vector<int> cls;
-    if (sblas::plan_build((hipStream_t)stream, st, (int)rows, (int)cols, nnz, rowptr, colidx, &p->pv, split ? &cls : nullptr) !=
-        hipSuccess)
-        return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
-    if (split) {
-        bool bad = false;
-        if (spmm_plan_split(p, (hipStream_t)stream, rowptr, cls, split_min, piece, &bad) != hipSuccess)
-            return spmm_plan_fail(p, plan_out, SBLAS_E_HIP);
-        if (bad) return spmm_plan_fail(p, plan_out, SBLAS_E_INVALID); // row pointers descending or outside [0, nnz]
+    if (st.plannable) {
+        if (p->buf.alloc(p->dev, sblas::plan_tail_bytes(rows)) != hipSuccess) return SBLAS_E_HIP;
+        p->pv.tail = p->buf.at<int>();
+        p->ldbt = ldbt;
+        std::vector<int> cls;
+        if (sblas::plan_build((hipStream_t)stream, st, (int)rows, (int)cols, nnz, rowptr, colidx, &p->pv, split ? &cls : nullptr) !=
+            hipSuccess)
+            return SBLAS_E_HIP;
+        if (split) {
+            bool bad = false;
+            if (spmm_plan_split(p.get(), (hipStream_t)stream, rowptr, cls, split_min, piece, &bad) != hipSuccess) return SBLAS_E_HIP;
+            if (bad) return SBLAS_E_INVALID; // row pointers descending or outside [0, nnz]
+        }
+        p->active = true;
     }
-    p->active = true;
+    *plan_out = p.release();
     return SBLAS_OK;
 }
 
@@ -365,14 +332,7 @@ int sblas_hip_spmm_plan_create_split(int dev, void *stream, int64_t rows, int64_
 
 int sblas_hip_spmm_plan_destroy(void *plan)
 {
-    if (!plan) return SBLAS_OK;
-    SpmmPlan *p = static_cast<SpmmPlan *>(plan);
-    if (p->buf || p->split_buf) {
-        DeviceScope scope(p->dev);
-        if (p->buf) (void)hipFree(p->buf);
-        if (p->split_buf) (void)hipFree(p->split_buf);
-    }
-    delete p;
+    delete static_cast<SpmmPlan *>(plan);
     return SBLAS_OK;
 }
 
@@ -411,10 +371,7 @@ int sblas_hip_spmm_csr_ordered_f64_i32_planned(const void *plan, int dev, void *
 {
     if (!plan || !order_ok(order_b) || !order_ok(order_c)) return SBLAS_E_INVALID;
     const SpmmPlan *p = static_cast<const SpmmPlan *>(plan);
-    // the plan speaks for ONE structure: the same arrays it was made from (their contents are the caller's promise)
-    // ... on the device its verdicts live on
-    if (p->dev != resolve_device(dev) || p->rows != rows || p->cols != cols || p->nnz != nnz || p->rowptr != rowptr || p->colidx != colidx)
-        return SBLAS_E_INVALID;
+    if (!p->speaks_for(dev, rows, cols, nnz, rowptr, colidx)) return SBLAS_E_INVALID;
     return spmm_impl(dev, stream, rows, cols, nnz, rowptr, colidx, val, B, ldb, order_b, n, alpha, beta, C, ldc, order_c,
                      workspace, workspace_bytes, p);
 }
@@ -481,127 +438,75 @@ int sblas_hip_spmv_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t cols
 }
 
 // ---- per-matrix SpMV plan (the slot of csrmv_analysis / cusparseSpMV_preprocess) --------------------------------
-// One device buffer: the partial sums of the split pieces (doubles) first, then the int4 work items of the kernel
-// classes, the pieces and the split rows.
-struct SpmvPlan {
-    int dev = -1;
-    int64_t rows = 0, cols = 0, nnz = 0;
-    const void *rowptr = nullptr, *colidx = nullptr;
-    bool active = false; // false: empty matrix or a pinned SBLAS_SPMV_VARIANT: calls run unplanned
-    void *buf = nullptr;
-    sblas::SpmvPlanView pv;
-};
-
-static int spmv_plan_fail(SpmvPlan *p, void **plan_out, int rc)
-{
-    if (p->buf) (void)hipFree(p->buf);
-    delete p;
-    *plan_out = nullptr;
-    return rc;
-}
-
 int sblas_hip_spmv_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
                                const int32_t *colidx, void **plan_out)
 {
     if (!plan_out || !csr_args_ok(rows, cols, nnz, rowptr, colidx, reinterpret_cast<const void *>(1))) return SBLAS_E_INVALID;
     *plan_out = nullptr;
     if (const int vrc = validate_if_asked(dev, stream, rows, cols, nnz, rowptr, colidx)) return vrc;
-    SpmvPlan *p = new SpmvPlan;
+    std::unique_ptr<SpmvPlan> p(new SpmvPlan);
     p->dev = resolve_device(dev), p->rows = rows, p->cols = cols, p->nnz = nnz, p->rowptr = rowptr, p->colidx = colidx;
     if (rows == 0 || nnz == 0 || sblas::options().spmv_variant[0]) { // nothing to plan / a pinned kernel
-        *plan_out = p;
+        *plan_out = p.release();
         return SBLAS_OK;
     }
     DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return spmv_plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
     hipStream_t s = (hipStream_t)stream;
-    int32_t *rp = static_cast<int32_t *>(malloc(((size_t)rows + 1) * sizeof(int32_t)));
-    if (!rp) return spmv_plan_fail(p, plan_out, SBLAS_E_HIP);
-    if (hipMemcpyAsync(rp, rowptr, ((size_t)rows + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        free(rp);
-        return spmv_plan_fail(p, plan_out, SBLAS_E_HIP);
-    }
-    const int64_t n_items = sblas_spmv_plan_classify(rp, rows, nnz, 0, 0, nullptr, 0);
-    int32_t *it = n_items > 0 ? static_cast<int32_t *>(malloc((size_t)n_items * 4 * sizeof(int32_t))) : nullptr;
-    if (n_items <= 0 || !it || rp[0] < 0 || rp[rows] > nnz || sblas_spmv_plan_classify(rp, rows, nnz, 0, 0, it, n_items) != n_items) {
-        free(rp);
-        free(it);
-        return spmv_plan_fail(p, plan_out, SBLAS_E_INVALID); // row pointers descending or outside [0, nnz]
-    }
+    std::vector<int32_t> rp((size_t)rows + 1);
+    if (hipMemcpyAsync(rp.data(), rowptr, rp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return SBLAS_E_HIP;
+    const int64_t n_items = sblas_spmv_plan_classify(rp.data(), rows, nnz, 0, 0, nullptr, 0);
+    if (n_items <= 0 || rp[0] < 0 || rp[rows] > nnz) return SBLAS_E_INVALID; // row pointers descending or outside [0, nnz]
+    std::vector<int4> it((size_t)n_items);
+    if (sblas_spmv_plan_classify(rp.data(), rows, nnz, 0, 0, reinterpret_cast<int32_t *>(it.data()), n_items) != n_items)
+        return SBLAS_E_INVALID;
     // host image of the buffer: items grouped by class (in row order inside a class), then pieces, then split rows
     sblas::SpmvPlanView &pv = p->pv;
     int64_t cnt[sblas::SPMV_ITEM_KERNELS] = {0};
-    for (int64_t i = 0; i < n_items; ++i) {
-        const int k = it[4 * i + 2];
-        if (k == SBLAS_SPMV_ITEM_SPLIT) ++pv.n_split, pv.n_pieces += it[4 * i + 3];
-        else ++cnt[k];
+    for (const int4 &q : it) {
+        if (q.z == SBLAS_SPMV_ITEM_SPLIT) ++pv.n_split, pv.n_pieces += q.w;
+        else ++cnt[q.z];
     }
     for (int k = 0; k < sblas::SPMV_ITEM_KERNELS; ++k) pv.off[k + 1] = pv.off[k] + cnt[k];
     const int64_t n_kernel_items = pv.off[sblas::SPMV_ITEM_KERNELS];
-    const size_t partial_bytes = ((size_t)pv.n_pieces * sizeof(double) + 15) / 16 * 16;
-    const size_t n_int4 = (size_t)(n_kernel_items + pv.n_pieces + pv.n_split);
-    int4 *img = static_cast<int4 *>(malloc(n_int4 * sizeof(int4) + 16));
-    if (!img) {
-        free(rp);
-        free(it);
-        return spmv_plan_fail(p, plan_out, SBLAS_E_HIP);
-    }
-    int4 *pieces = img + n_kernel_items, *srows = pieces + pv.n_pieces;
+    std::vector<int4> img((size_t)(n_kernel_items + pv.n_pieces + pv.n_split));
     int64_t fill[sblas::SPMV_ITEM_KERNELS];
     for (int k = 0; k < sblas::SPMV_ITEM_KERNELS; ++k) fill[k] = pv.off[k];
-    int64_t slot = 0, nsplit = 0;
-    for (int64_t i = 0; i < n_items; ++i) {
-        const int32_t *q = it + 4 * i;
-        if (q[2] != SBLAS_SPMV_ITEM_SPLIT) {
-            img[fill[q[2]]++] = make_int4(q[0], q[1], 0, -1);
-            continue;
-        }
-        const int64_t b = rp[q[0]], e = rp[q[0] + 1];
-        srows[nsplit++] = make_int4(q[0], (int)slot, q[3], 0);
-        for (int j = 0; j < q[3]; ++j, ++slot) {
-            const int64_t pb = b + (int64_t)j * SBLAS_SPMV_SPLIT_PIECE;
-            const int64_t pe = pb + SBLAS_SPMV_SPLIT_PIECE < e ? pb + SBLAS_SPMV_SPLIT_PIECE : e;
-            pieces[slot] = make_int4(q[0], (int)pb, (int)pe, (int)slot);
-        }
-    }
-    free(rp);
-    free(it);
-    hipError_t e = hipMalloc(&p->buf, partial_bytes + n_int4 * sizeof(int4) + 16);
+    for (const int4 &q : it)
+        if (q.z != SBLAS_SPMV_ITEM_SPLIT) img[fill[q.z]++] = make_int4(q.x, q.y, 0, -1);
+    sblas::split_rows(rp.data(), rows, SBLAS_SPMV_SPLIT_PIECE, [](int64_t, int64_t len) { return len > SBLAS_SPMV_SPLIT_MIN; },
+                      reinterpret_cast<int32_t *>(img.data() + n_kernel_items), pv.n_pieces + pv.n_split);
+    const size_t partial_bytes = ((size_t)pv.n_pieces * sizeof(double) + 15) / 16 * 16;
+    hipError_t e = p->buf.alloc(p->dev, partial_bytes + img.size() * sizeof(int4) + 16);
     if (e == hipSuccess) {
-        char *base = static_cast<char *>(p->buf);
-        pv.partial = reinterpret_cast<double *>(base);
-        pv.items = reinterpret_cast<int4 *>(base + partial_bytes);
+        pv.partial = p->buf.at<double>();
+        pv.items = p->buf.at<int4>(partial_bytes);
         pv.pieces = pv.items + n_kernel_items;
         pv.srows = pv.pieces + pv.n_pieces;
-        e = hipMemcpyAsync(pv.items, img, n_int4 * sizeof(int4), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(pv.items, img.data(), img.size() * sizeof(int4), hipMemcpyHostToDevice, s);
     }
     if (e == hipSuccess)
-        e = sblas::spmv_plan_windows(s, (int)(pv.off[sblas::SPMV_ITEM_LDS_S7 + 1] - pv.off[sblas::SPMV_ITEM_LDS_S2]),
-                                     pv.items + pv.off[sblas::SPMV_ITEM_LDS_S2], rowptr, colidx);
+        e = sblas::spmv_plan_windows(s, (int)(pv.off[SBLAS_SPMV_ITEM_LDS_S7 + 1] - pv.off[SBLAS_SPMV_ITEM_LDS_S2]),
+                                     pv.items + pv.off[SBLAS_SPMV_ITEM_LDS_S2], rowptr, colidx);
     if (e == hipSuccess) e = hipStreamSynchronize(s); // (the host image is freed next)
-    free(img);
-    if (e != hipSuccess) return spmv_plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (e != hipSuccess) return SBLAS_E_HIP;
     // one class, no split rows: the items are the unplanned kernel's own blocks (aligned from row 0, the launcher's
-    // instantiation), so the unplanned launch computes the same thing without a load of the item at every block's start
-    // (1 M banded rows of 7: 31.6 against 30.7 us).  The LDS-window class keeps its items: they carry the column windows.
+    // instantiation: both follow spmv_kind), so the unplanned launch computes the same thing without a load of the item at
+    // every block's start (1 M banded rows of 7: 31.6 against 30.7 us).  The LDS-window class keeps its items: they carry
+    // the column windows.
     int classes = 0;
     for (int k = 0; k < sblas::SPMV_ITEM_KERNELS; ++k) classes += pv.off[k + 1] > pv.off[k];
-    pv.as_unplanned = classes == 1 && pv.n_split == 0 && pv.off[sblas::SPMV_ITEM_LDS_S2] == n_kernel_items;
+    pv.as_unplanned = classes == 1 && pv.n_split == 0 && pv.off[SBLAS_SPMV_ITEM_LDS_S2] == n_kernel_items;
     p->active = true;
-    *plan_out = p;
+    *plan_out = p.release();
     return SBLAS_OK;
 }
 
 int sblas_hip_spmv_plan_destroy(void *plan)
 {
-    if (!plan) return SBLAS_OK;
-    SpmvPlan *p = static_cast<SpmvPlan *>(plan);
-    if (p->buf) {
-        DeviceScope scope(p->dev);
-        (void)hipFree(p->buf);
-    }
-    delete p;
+    delete static_cast<SpmvPlan *>(plan);
     return SBLAS_OK;
 }
 
@@ -612,8 +517,8 @@ int sblas_hip_spmv_plan_info(const void *plan, int64_t out[8])
     const int64_t *off = p->pv.off;
     auto n = [&](int k) { return off[k + 1] - off[k]; };
     out[0] = p->active;
-    out[1] = n(sblas::SPMV_ITEM_LPR), out[2] = n(sblas::SPMV_ITEM_STREAM4096), out[3] = n(sblas::SPMV_ITEM_STREAM6144);
-    out[4] = n(sblas::SPMV_ITEM_SEG), out[5] = off[sblas::SPMV_ITEM_LDS_S7 + 1] - off[sblas::SPMV_ITEM_LDS_S2];
+    out[1] = n(SBLAS_SPMV_ITEM_LPR), out[2] = n(SBLAS_SPMV_ITEM_STREAM4096), out[3] = n(SBLAS_SPMV_ITEM_STREAM6144);
+    out[4] = n(SBLAS_SPMV_ITEM_SEG), out[5] = off[SBLAS_SPMV_ITEM_LDS_S7 + 1] - off[SBLAS_SPMV_ITEM_LDS_S2];
     out[6] = p->pv.n_split, out[7] = p->pv.n_pieces;
     return SBLAS_OK;
 }
@@ -624,10 +529,7 @@ int sblas_hip_spmv_csr_f64_i32_planned(const void *plan, int dev, void *stream, 
 {
     if (!plan) return SBLAS_E_INVALID;
     const SpmvPlan *p = static_cast<const SpmvPlan *>(plan);
-    // the plan speaks for ONE structure on one device (the contents of the arrays are the caller's promise)
-    if (p->dev != resolve_device(dev) || p->rows != rows || p->cols != cols || p->nnz != nnz || p->rowptr != rowptr ||
-        p->colidx != colidx)
-        return SBLAS_E_INVALID;
+    if (!p->speaks_for(dev, rows, cols, nnz, rowptr, colidx)) return SBLAS_E_INVALID;
     if (!p->active) return sblas_hip_spmv_csr_f64_i32(dev, stream, rows, cols, nnz, rowptr, colidx, val, x, alpha, beta, y);
     if (!csr_args_ok(rows, cols, nnz, rowptr, colidx, val)) return SBLAS_E_INVALID;
     if (!y || (cols > 0 && !x)) return SBLAS_E_INVALID;

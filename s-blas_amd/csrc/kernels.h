@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "../../include/sblas_hip.h"
 
 namespace sblas {
 
@@ -104,14 +105,46 @@ struct PlanView {
     bool use_range = false;     // stage only the column range [lo, hi] of B
     int nparts = 0;
     // a split plan's long rows (sblas_hip_spmm_plan_create_split; all null / 0 otherwise): one bit per row, the pieces
-    // {row, first nonzero, end, partial slot}, the split rows {row, first slot, pieces, -1} and one partial row of ldbt
-    // doubles per piece, in the plan's device buffer
+    // and the split rows (split_rows) and one partial row of ldbt doubles per piece, in the plan's device buffer
     const unsigned *split_bits = nullptr;
     const int4 *pieces = nullptr, *srows = nullptr;
     double *partial = nullptr;
     int64_t n_pieces = 0, n_split = 0, split_nnz = 0;
 };
 size_t plan_tail_bytes(int64_t rows);
+
+// The split rows of both plans (sblas_spmm_split_classify, sblas_hip_spmv_plan_create): the rows that split(row, len)
+// selects, cut into pieces of at most `piece` consecutive nonzeros.  Records of four int32: first the pieces {row, first
+// nonzero, end, partial slot} with slots 0, 1, .. in row order (the pieces of a row consecutive, in CSR order), then one
+// record per split row {row, first slot, pieces, -1}.  Writes the records below max_out when out is not null; returns the
+// number of records, or -1 when the row pointers descend.
+template <typename Split>
+int64_t split_rows(const int32_t *rowptr, int64_t rows, int64_t piece, Split split, int32_t *out, int64_t max_out)
+{
+    int64_t n_pieces = 0, n_split = 0;
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t len = (int64_t)rowptr[r + 1] - rowptr[r];
+        if (len < 0) return -1;
+        if (split(r, len)) ++n_split, n_pieces += (len + piece - 1) / piece;
+    }
+    if (!out) return n_pieces + n_split;
+    int64_t slot = 0, k = n_pieces; // pieces at [0, n_pieces), split rows behind them
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t b = rowptr[r], e = rowptr[r + 1];
+        if (!split(r, e - b)) continue;
+        if (k < max_out) {
+            int32_t *o = out + 4 * k;
+            o[0] = (int32_t)r, o[1] = (int32_t)slot, o[2] = (int32_t)((e - b + piece - 1) / piece), o[3] = -1;
+        }
+        ++k;
+        for (int64_t pb = b; pb < e; pb += piece, ++slot) {
+            if (slot >= max_out) continue;
+            int32_t *o = out + 4 * slot;
+            o[0] = (int32_t)r, o[1] = (int32_t)pb, o[2] = (int32_t)(pb + piece < e ? pb + piece : e), o[3] = (int32_t)slot;
+        }
+    }
+    return n_pieces + n_split;
+}
 
 // What one column chunk of an SpMM call does before stage 2, decided in one place (spmm_step): how B is staged, whether
 // stage 2 reads panel verdicts and where they come from, and the panel geometry the classifier and stage 2 agree on.
@@ -157,12 +190,21 @@ hipError_t validate_csr(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, 
 hipError_t panel_stats(unsigned long long out[4], bool reset);
 hipError_t launch_spmv(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
                        const double *val, const double *x, double alpha, double beta, double *y);
+// The SpMV kernel rule (spmv_plan.cpp): the SBLAS_SPMV_ITEM_* kind for rows of `avg` nonzeros on average -- launch_spmv's
+// choice for a whole matrix, the plan's for a tile.  family >= 0 (LPR, STREAM4096, SEG or LDS_S2: the first kind of a
+// kernel family) asks for the kind inside that family, whatever family avg itself falls in.
+int spmv_kind(double avg, int family = -1);
+// Rows per block of the instantiations spmv_kind picks (spmv_kernels.hip); a plan's work item is at most one block.
+constexpr int SPMV_LPR = 4;                   // lanes-per-row kernel: 4 lanes per row ...
+constexpr int SPMV_LPR_ROWS = 256 / SPMV_LPR; // ... 64 rows per 256-thread block
+constexpr int ST_ROWS = 256;                  // stream kernel: a row per thread
+constexpr int SPMV_SEG_R = 4;                 // segmented kernel: rows per wave ...
+constexpr int SPMV_SEG_ROWS = 4 * SPMV_SEG_R; // ... 16 rows per four-wave block
+constexpr int SPMV_LDS_ROWS = 8;              // LDS-window kernel: a row per wave, eight waves
 // A per-matrix SpMV plan (capi.hip: sblas_hip_spmv_plan_*).  Work items of the kernel classes, grouped by class
 // (items + off[k] .. items + off[k + 1]; int4 {first row, row count, window lo, window hi}; the window only for the
-// LDS-window classes), the pieces of the split rows ({row, first nonzero, end, partial slot}), the split rows ({row,
-// first slot, pieces, 0}) and one partial sum per piece, all in the plan's device buffer.
-enum { SPMV_ITEM_LPR = 0, SPMV_ITEM_STREAM4096 = 1, SPMV_ITEM_STREAM6144 = 2, SPMV_ITEM_SEG = 3, SPMV_ITEM_LDS_S2 = 4,
-       SPMV_ITEM_LDS_S3 = 5, SPMV_ITEM_LDS_S4 = 6, SPMV_ITEM_LDS_S7 = 7, SPMV_ITEM_SPLIT = 8, SPMV_ITEM_KERNELS = 8 };
+// LDS-window classes), the split-row records (split_rows) and one partial sum per piece, all in the plan's device buffer.
+constexpr int SPMV_ITEM_KERNELS = SBLAS_SPMV_ITEM_SPLIT; // the kinds SBLAS_SPMV_ITEM_LPR .. _LDS_S7 have a kernel each
 struct SpmvPlanView {
     int4 *items = nullptr;
     int64_t off[SPMV_ITEM_KERNELS + 1] = {0};

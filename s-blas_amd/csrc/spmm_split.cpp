@@ -7,9 +7,11 @@
 // launch.  Rows of split_min+ entries in panels the plan gives to the direct kernels are cut here into pieces of at most
 // `piece` consecutive entries; the pieces are summed by as many workgroups and folded in piece order (kernels.hip,
 // spmm_split_piece_kernel / spmm_split_fold_kernel).  Rows in panels of the LDS-tiled, lane-group or matrix-core kernels,
-// and rows the row-merging kernel takes, are never split: the caller masks those panels out.
+// and rows the row-merging kernel takes, are never split: the caller masks those panels out.  The records are those of
+// every split row (split_rows, kernels.h); this file keeps SpMM's choice of rows.
 #include <stdint.h>
 #include "../../include/sblas_hip.h"
+#include "kernels.h"
 
 extern "C" int64_t sblas_spmm_split_classify(const int32_t *rowptr, int64_t rows, int64_t nnz, int64_t split_min,
                                              int64_t piece, const uint8_t *direct_mask, int64_t panel_rows, int32_t *out,
@@ -20,27 +22,5 @@ extern "C" int64_t sblas_spmm_split_classify(const int32_t *rowptr, int64_t rows
     if (piece <= 0) piece = SBLAS_SPMM_SPLIT_PIECE;
     if (rows > 0 && (rowptr[0] < 0 || rowptr[rows] > nnz)) return -1;
     auto split = [&](int64_t r, int64_t len) { return len >= split_min && (!direct_mask || direct_mask[r / panel_rows]); };
-    int64_t n_pieces = 0, n_split = 0;
-    for (int64_t r = 0; r < rows; ++r) {
-        const int64_t len = (int64_t)rowptr[r + 1] - rowptr[r];
-        if (len < 0) return -1; // row pointers must not descend
-        if (split(r, len)) ++n_split, n_pieces += (len + piece - 1) / piece;
-    }
-    if (!out) return n_pieces + n_split;
-    int64_t slot = 0, k = n_pieces; // pieces at [0, n_pieces), split rows behind them
-    for (int64_t r = 0; r < rows; ++r) {
-        const int64_t b = rowptr[r], e = rowptr[r + 1];
-        if (!split(r, e - b)) continue;
-        if (k < max_out) {
-            int32_t *o = out + 4 * k;
-            o[0] = (int32_t)r, o[1] = (int32_t)slot, o[2] = (int32_t)((e - b + piece - 1) / piece), o[3] = -1;
-        }
-        ++k;
-        for (int64_t pb = b; pb < e; pb += piece, ++slot) {
-            if (slot >= max_out) continue;
-            int32_t *o = out + 4 * slot;
-            o[0] = (int32_t)r, o[1] = (int32_t)pb, o[2] = (int32_t)(pb + piece < e ? pb + piece : e), o[3] = (int32_t)slot;
-        }
-    }
-    return n_pieces + n_split;
+    return sblas::split_rows(rowptr, rows, piece, split, out, max_out);
 }

@@ -1,5 +1,6 @@
 // spmv_kernels.hip -- hand-written gfx950 (wave64) CSR SpMV kernels  y = alpha*A*x + beta*y  (replaces cusparseSpMV,
-// spmv.h:104-106).  The launcher at the end picks the kernel by row-length class.
+// spmv.h:104-106).  The launcher at the end takes the kernel that the kernel rule (spmv_kind, spmv_plan.cpp) picks by
+// row-length class; the SpMV plan classifies its tiles by the same rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -118,12 +119,11 @@ __global__ __launch_bounds__(256) void spmv_csr_planned_kernel(const int4 *__res
 // products in LDS, and thread r then adds up the products of row r in CSR order.  A block whose rows hold more than
 // the LDS can take (longer rows among the short ones) takes its rows in several runs.
 // ---------------------------------------------------------------------------------------------
-constexpr int ST_ROWS = 256;
-// ST_CAP = products per block held in LDS: 6144 (48 KiB + skew: three blocks per CU) or 4096 (33 KiB: four).  A block walks
-// its 256 rows in runs of up to ST_CAP products, and a block in its summing phase issues no loads, so what pays is the fewest
-// runs first and the most blocks per CU second (round 3; 1 M banded rows of 7 / 13 / 27 per row: 29.5 / 43.6 / 97.1 us with
-// 6144 against 24.2 / 36.6 / 82 us with 4096; 600 k rows of 48, three runs instead of two: 128 against 141 us): the
-// launcher picks per call from the average row length (stream_cap).
+// ST_ROWS rows per block (kernels.h).  ST_CAP = products per block held in LDS: 6144 (48 KiB + skew: three blocks per CU) or
+// 4096 (33 KiB: four).  A block walks its 256 rows in runs of up to ST_CAP products, and a block in its summing phase issues
+// no loads, so what pays is the fewest runs first and the most blocks per CU second (round 3; 1 M banded rows of 7 / 13 /
+// 27 per row: 29.5 / 43.6 / 97.1 us with 6144 against 24.2 / 36.6 / 82 us with 4096; 600 k rows of 48, three runs instead
+// of two: 128 against 141 us): the kernel rule picks per call from the average row length (spmv_kind).
 constexpr int ST_LONG = 96;  // rows longer than this are summed by a whole wave
 __device__ __forceinline__ int st_skew(int q) { return q + (q >> 5); } // rows of equal length: spread the LDS banks
 template <int ST_CAP>
@@ -366,8 +366,7 @@ __global__ __launch_bounds__(256) void spmv_csr_seg_planned_kernel(const int4 *_
 // in flight, window fetch, gathers, reduction), so that the CU's HBM requests do not come in two bursts.  Sixteen waves and
 // 40 KiB (two blocks per CU, round 2): bench matrix 68.3 us against 63.5-64.1 us now; 600 k banded rows of 160 / 260: 345 /
 // 489 us against 337 / 470; 300 k rows of 500 over +-3000 (span beyond the window either way): 529 against 489.
-constexpr int SPMV_LDS_ROWS = 8;    // = waves per block
-constexpr int SPMV_LDS_THREADS = SPMV_LDS_ROWS * 64;
+constexpr int SPMV_LDS_THREADS = SPMV_LDS_ROWS * 64; // a wave per row of the block (kernels.h)
 constexpr int SPMV_LDS_CAP = 4608;  // doubles (36 KiB): four blocks per CU
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -538,100 +537,86 @@ __global__ __launch_bounds__(SPMV_LDS_THREADS) void spmv_csr_lds_planned_kernel(
 }
 
 
-// the stream kernel with the LDS capacity that gives a block of average rows the fewest runs; a tie goes to the smaller one
-static hipError_t launch_stream(hipStream_t s, int rows, double avg, const int *rowptr, const int *colidx, const double *val,
-                                const double *x, double alpha, double beta, double *y)
+// One unplanned launch: the kernels' common arguments, and a launcher per kernel form.
+struct SpmvCall {
+    hipStream_t s;
+    int rows, cols;
+    const int *rowptr, *colidx;
+    const double *val, *x;
+    double alpha, beta;
+    double *y;
+};
+template <int LPR>
+static hipError_t spmv_go(const SpmvCall &c)
 {
-    const double per_block = avg * ST_ROWS;
-    const int runs4 = (int)((per_block + 4095.0) / 4096.0), runs6 = (int)((per_block + 6143.0) / 6144.0);
-    const dim3 grid((unsigned)((rows + ST_ROWS - 1) / ST_ROWS));
-    if (runs4 <= runs6)
-        hipLaunchKernelGGL(spmv_csr_stream_kernel<4096>, grid, dim3(ST_ROWS), 0, s, rows, rowptr, colidx, val, x, alpha, beta, y);
-    else
-        hipLaunchKernelGGL(spmv_csr_stream_kernel<6144>, grid, dim3(ST_ROWS), 0, s, rows, rowptr, colidx, val, x, alpha, beta, y);
+    constexpr int rpb = 256 / LPR;
+    hipLaunchKernelGGL(spmv_csr_kernel<LPR>, dim3((unsigned)((c.rows + rpb - 1) / rpb)), dim3(256), 0, c.s, c.rows, c.rowptr,
+                       c.colidx, c.val, c.x, c.alpha, c.beta, c.y);
+    return hipGetLastError();
+}
+template <int ST_CAP>
+static hipError_t spmv_stream_go(const SpmvCall &c)
+{
+    hipLaunchKernelGGL(spmv_csr_stream_kernel<ST_CAP>, dim3((unsigned)((c.rows + ST_ROWS - 1) / ST_ROWS)), dim3(ST_ROWS), 0, c.s,
+                       c.rows, c.rowptr, c.colidx, c.val, c.x, c.alpha, c.beta, c.y);
+    return hipGetLastError();
+}
+template <int R, int S>
+static hipError_t spmv_seg_go(const SpmvCall &c)
+{
+    hipLaunchKernelGGL((spmv_csr_seg_kernel<R, S>), dim3((unsigned)((c.rows + 4 * R - 1) / (4 * R))), dim3(256), 0, c.s, c.rows,
+                       c.rowptr, c.colidx, c.val, c.x, c.alpha, c.beta, c.y);
+    return hipGetLastError();
+}
+template <int RW, int S>
+static hipError_t spmv_lds_go(const SpmvCall &c)
+{
+    raise_dynamic_lds((const void *)spmv_csr_lds_kernel<RW, S>, (SPMV_LDS_CAP + 128) * sizeof(double));
+    hipLaunchKernelGGL((spmv_csr_lds_kernel<RW, S>), dim3((unsigned)((c.rows + SPMV_LDS_ROWS * RW - 1) / (SPMV_LDS_ROWS * RW))),
+                       dim3(SPMV_LDS_THREADS), (SPMV_LDS_CAP + 128) * sizeof(double), c.s, c.rows, c.cols, c.rowptr, c.colidx,
+                       c.val, c.x, c.alpha, c.beta, c.y);
     return hipGetLastError();
 }
 
-template <int LPR>
-static hipError_t spmv_go(hipStream_t s, int rows, const int *rowptr, const int *colidx, const double *val,
-                          const double *x, double alpha, double beta, double *y)
+// the unplanned instantiation of an SBLAS_SPMV_ITEM_* kind
+static hipError_t spmv_kind_go(const SpmvCall &c, int kind)
 {
-    constexpr int rpb = 256 / LPR;
-    hipLaunchKernelGGL(spmv_csr_kernel<LPR>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, rows,
-                       rowptr, colidx, val, x, alpha, beta, y);
-    return hipGetLastError();
+    switch (kind) {
+    case SBLAS_SPMV_ITEM_LDS_S2: return spmv_lds_go<1, 2>(c);
+    case SBLAS_SPMV_ITEM_LDS_S3: return spmv_lds_go<1, 3>(c);
+    case SBLAS_SPMV_ITEM_LDS_S4: return spmv_lds_go<1, 4>(c);
+    case SBLAS_SPMV_ITEM_LDS_S7: return spmv_lds_go<1, 7>(c);
+    case SBLAS_SPMV_ITEM_SEG: return spmv_seg_go<SPMV_SEG_R, 5>(c);
+    case SBLAS_SPMV_ITEM_STREAM4096: return spmv_stream_go<4096>(c);
+    case SBLAS_SPMV_ITEM_STREAM6144: return spmv_stream_go<6144>(c);
+    default: return spmv_go<SPMV_LPR>(c);
+    }
 }
 
 hipError_t launch_spmv(hipStream_t s, int rows, int cols, int64_t nnz, const int *rowptr, const int *colidx,
                        const double *val, const double *x, double alpha, double beta, double *y)
 {
+    const SpmvCall c{s, rows, cols, rowptr, colidx, val, x, alpha, beta, y};
     const double avg = rows > 0 ? (double)nnz / (double)rows : 0.0;
-    const char *sv = options().spmv_variant; // "" = auto; anything else pins a kernel (A/B runs, tests)
-    const bool autosel = !*sv;
+    const char *sv = options().spmv_variant; // "" = auto: the kernel rule; anything else pins a kernel (A/B runs, tests)
+    if (!*sv) return spmv_kind_go(c, spmv_kind(avg));
     auto is = [&](const char *name) { return !strcmp(sv, name); };
-#define SBLAS_SPMV_LDS(RWV, SV)                                                                                      \
-    do {                                                                                                             \
-        raise_dynamic_lds((const void *)spmv_csr_lds_kernel<RWV, SV>, (SPMV_LDS_CAP + 128) * sizeof(double));        \
-        hipLaunchKernelGGL((spmv_csr_lds_kernel<RWV, SV>),                                                           \
-                           dim3((unsigned)((rows + SPMV_LDS_ROWS * RWV - 1) / (SPMV_LDS_ROWS * RWV))), dim3(SPMV_LDS_THREADS),    \
-                           (SPMV_LDS_CAP + 128) * sizeof(double), s, rows, cols, rowptr, colidx, val, x, alpha, beta, y); \
-        return hipGetLastError();                                                                                    \
-    } while (0)
-#define SBLAS_SPMV_SEG(RV, SV)                                                                                       \
-    do {                                                                                                             \
-        hipLaunchKernelGGL((spmv_csr_seg_kernel<RV, SV>), dim3((unsigned)((rows + 4 * RV - 1) / (4 * RV))), dim3(256), \
-                           0, s, rows, rowptr, colidx, val, x, alpha, beta, y);                                      \
-        return hipGetLastError();                                                                                    \
-    } while (0)
-    if (autosel) {
-        // long rows: x window in LDS (bench matrix: 70-73 us vs 82-85 us for the lanes-per-row kernel); a block whose
-        // rows span more than the LDS window degrades to global gathers by itself.  Slices in flight per row: ~1.3-1.5 x
-        // the row length in 64-lane slices (600 k banded rows of 100 / 130 / 160 / 200 / 260, band +-2000: S = 2 / 3 / 3 /
-        // 4 / 7 take 273 / 307 / 315 / 360 / 433 us against 329 / 337 / 345 / 360 / 451 us with S = 4 throughout; the
-        // same order on a +-20000 band, tools/spmv_rowlen_sweep.py)
-        if (avg > 96.0) {
-            if (avg <= 115.0) SBLAS_SPMV_LDS(1, 2);
-            if (avg <= 180.0) SBLAS_SPMV_LDS(1, 3);
-            if (avg <= 230.0) SBLAS_SPMV_LDS(1, 4);
-            SBLAS_SPMV_LDS(1, 7);
-        }
-        // medium rows: R rows per wave, segmented (Queen-like rows, 73 per row: 232 us vs 395 us; banded synthetic rows
-        // of 36 / 72 / 90: 122 / 266 / 351 us vs 150 / 339 / 375 us for the lanes-per-row kernel)
-        if (avg > 64.0) SBLAS_SPMV_SEG(4, 5);
-        // short and medium rows (5 < avg <= 64): 256 rows per block streamed through LDS, in runs of up to 6144
-        // products (stencil-like rows of 7 / 13 / 27: 108 / 177 / 344 us vs 143 / 277 / 498 us for the lanes-per-row and
-        // segmented kernels; banded-random rows of 14 / 20 / 28 / 36 / 48: 46 / 62 / 85 / 116 / 161 vs 49 / 71 / 94 /
-        // 128 / 194; 1 M banded rows of 55 / 70: 207 / 256 us vs 250 / 281 us segmented; Queen-like rows of 73: 251 vs
-        // 256 us).  Rows beyond 96 take the kernel's slow path (a wave per row), so it stops where a spread of row
-        // lengths starts to reach that: Poisson rows of 60 on average tie, of 70 lose 4 %, of 80 7 %, of 90 27 % -- the launcher
-        // only knows the average.  Round 3 (four blocks per CU for short rows): 2 M uniform rows of 3 / 5: 35.9 / 40.0 us
-        // against 34.6-36.1 / 50.0 us for the lanes-per-row kernel, power-law rows averaging 3.2: 55.7 against 67 us -- the
-        // stream form from 2.5 per row on (round 2: from 5).
-        if (avg > 2.5) {
-            return launch_stream(s, rows, avg, rowptr, colidx, val, x, alpha, beta, y);
-        }
-        return spmv_go<4>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
-    }
-    if (is("lds")) SBLAS_SPMV_LDS(1, 7);
-    if (is("lds2")) SBLAS_SPMV_LDS(2, 7);
-    if (is("lds1s2")) SBLAS_SPMV_LDS(1, 2);
-    if (is("lds1s3")) SBLAS_SPMV_LDS(1, 3);
-    if (is("lds1s4")) SBLAS_SPMV_LDS(1, 4);
-    if (is("seg4")) SBLAS_SPMV_SEG(4, 5);
-    if (is("seg3")) SBLAS_SPMV_SEG(3, 4);
-    if (is("seg8")) SBLAS_SPMV_SEG(8, 5);
-    if (is("seg2")) SBLAS_SPMV_SEG(2, 3);
-#undef SBLAS_SPMV_LDS
-#undef SBLAS_SPMV_SEG
-    if (is("stream")) {
-        return launch_stream(s, rows, avg, rowptr, colidx, val, x, alpha, beta, y);
-    }
+    if (is("lds")) return spmv_kind_go(c, SBLAS_SPMV_ITEM_LDS_S7);
+    if (is("lds2")) return spmv_lds_go<2, 7>(c);
+    if (is("lds1s2")) return spmv_kind_go(c, SBLAS_SPMV_ITEM_LDS_S2);
+    if (is("lds1s3")) return spmv_kind_go(c, SBLAS_SPMV_ITEM_LDS_S3);
+    if (is("lds1s4")) return spmv_kind_go(c, SBLAS_SPMV_ITEM_LDS_S4);
+    if (is("seg4")) return spmv_kind_go(c, SBLAS_SPMV_ITEM_SEG);
+    if (is("seg3")) return spmv_seg_go<3, 4>(c);
+    if (is("seg8")) return spmv_seg_go<8, 5>(c);
+    if (is("seg2")) return spmv_seg_go<2, 3>(c);
+    if (is("stream")) return spmv_kind_go(c, spmv_kind(avg, SBLAS_SPMV_ITEM_STREAM4096));
     // "plain" (and anything unknown): lanes per row by average length
-    if (avg <= 6.0) return spmv_go<4>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
-    if (avg <= 12.0) return spmv_go<8>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
-    if (avg <= 24.0) return spmv_go<16>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
-    if (avg <= 48.0) return spmv_go<32>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
-    return spmv_go<64>(s, rows, rowptr, colidx, val, x, alpha, beta, y);
+    if (avg <= 6.0) return spmv_go<4>(c);
+    if (avg <= 12.0) return spmv_go<8>(c);
+    if (avg <= 24.0) return spmv_go<16>(c);
+    if (avg <= 48.0) return spmv_go<32>(c);
+    return spmv_go<64>(c);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -737,18 +722,18 @@ hipError_t launch_spmv_planned(hipStream_t s, int cols, const SpmvPlanView &pv, 
     auto grid = [&](int k) { return dim3((unsigned)(pv.off[k + 1] - pv.off[k])); };
     auto items = [&](int k) { return pv.items + pv.off[k]; };
     auto has = [&](int k) { return pv.off[k + 1] > pv.off[k]; };
-    if (has(SPMV_ITEM_LPR))
-        hipLaunchKernelGGL(spmv_csr_planned_kernel<4>, grid(SPMV_ITEM_LPR), dim3(256), 0, s, items(SPMV_ITEM_LPR), rowptr,
-                           colidx, val, x, alpha, beta, y);
-    if (has(SPMV_ITEM_STREAM4096))
-        hipLaunchKernelGGL(spmv_csr_stream_planned_kernel<4096>, grid(SPMV_ITEM_STREAM4096), dim3(ST_ROWS), 0, s,
-                           items(SPMV_ITEM_STREAM4096), rowptr, colidx, val, x, alpha, beta, y);
-    if (has(SPMV_ITEM_STREAM6144))
-        hipLaunchKernelGGL(spmv_csr_stream_planned_kernel<6144>, grid(SPMV_ITEM_STREAM6144), dim3(ST_ROWS), 0, s,
-                           items(SPMV_ITEM_STREAM6144), rowptr, colidx, val, x, alpha, beta, y);
-    if (has(SPMV_ITEM_SEG))
-        hipLaunchKernelGGL((spmv_csr_seg_planned_kernel<4, 5>), grid(SPMV_ITEM_SEG), dim3(256), 0, s, items(SPMV_ITEM_SEG),
+    if (has(SBLAS_SPMV_ITEM_LPR))
+        hipLaunchKernelGGL(spmv_csr_planned_kernel<SPMV_LPR>, grid(SBLAS_SPMV_ITEM_LPR), dim3(256), 0, s, items(SBLAS_SPMV_ITEM_LPR),
                            rowptr, colidx, val, x, alpha, beta, y);
+    if (has(SBLAS_SPMV_ITEM_STREAM4096))
+        hipLaunchKernelGGL(spmv_csr_stream_planned_kernel<4096>, grid(SBLAS_SPMV_ITEM_STREAM4096), dim3(ST_ROWS), 0, s,
+                           items(SBLAS_SPMV_ITEM_STREAM4096), rowptr, colidx, val, x, alpha, beta, y);
+    if (has(SBLAS_SPMV_ITEM_STREAM6144))
+        hipLaunchKernelGGL(spmv_csr_stream_planned_kernel<6144>, grid(SBLAS_SPMV_ITEM_STREAM6144), dim3(ST_ROWS), 0, s,
+                           items(SBLAS_SPMV_ITEM_STREAM6144), rowptr, colidx, val, x, alpha, beta, y);
+    if (has(SBLAS_SPMV_ITEM_SEG))
+        hipLaunchKernelGGL((spmv_csr_seg_planned_kernel<SPMV_SEG_R, 5>), grid(SBLAS_SPMV_ITEM_SEG), dim3(256), 0, s,
+                           items(SBLAS_SPMV_ITEM_SEG), rowptr, colidx, val, x, alpha, beta, y);
 #define SBLAS_SPMV_LDS_PLANNED(K, SV)                                                                                \
     if (has(K)) {                                                                                                    \
         raise_dynamic_lds((const void *)spmv_csr_lds_planned_kernel<SV>, (SPMV_LDS_CAP + 128) * sizeof(double));     \
@@ -756,10 +741,10 @@ hipError_t launch_spmv_planned(hipStream_t s, int cols, const SpmvPlanView &pv, 
                            (SPMV_LDS_CAP + 128) * sizeof(double), s, items(K), cols, rowptr, colidx, val, x, alpha,   \
                            beta, y);                                                                                 \
     }
-    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S2, 2)
-    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S3, 3)
-    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S4, 4)
-    SBLAS_SPMV_LDS_PLANNED(SPMV_ITEM_LDS_S7, 7)
+    SBLAS_SPMV_LDS_PLANNED(SBLAS_SPMV_ITEM_LDS_S2, 2)
+    SBLAS_SPMV_LDS_PLANNED(SBLAS_SPMV_ITEM_LDS_S3, 3)
+    SBLAS_SPMV_LDS_PLANNED(SBLAS_SPMV_ITEM_LDS_S4, 4)
+    SBLAS_SPMV_LDS_PLANNED(SBLAS_SPMV_ITEM_LDS_S7, 7)
 #undef SBLAS_SPMV_LDS_PLANNED
     if (pv.n_pieces > 0) {
         hipLaunchKernelGGL(spmv_split_piece_kernel, dim3((unsigned)pv.n_pieces), dim3(256), 0, s, pv.pieces, colidx, val, x,

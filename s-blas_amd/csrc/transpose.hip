@@ -17,7 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
+#include <memory>
 #include "../../include/sblas_hip.h"
+#include "capi_util.h"
 #include "kernels.h"
 
 namespace {
@@ -304,37 +306,6 @@ hipError_t run_transpose(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz,
     return hipGetLastError();
 }
 
-struct DeviceScope {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceScope(int dev)
-    {
-        if (dev < 0) return;
-        err = hipGetDevice(&prev);
-        if (err != hipSuccess) return;
-        if (prev != dev) {
-            err = hipSetDevice(dev);
-            switched = (err == hipSuccess);
-        }
-    }
-    ~DeviceScope()
-    {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-inline int resolve_device(int dev)
-{
-    if (dev >= 0) return dev;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return -1;
-    return cur;
-}
-
-inline bool order_ok(int order) { return order == SBLAS_COL_MAJOR || order == SBLAS_ROW_MAJOR; }
-inline bool ld_ok(int order, int64_t ld, int64_t rows, int64_t n) { return ld >= (order == SBLAS_ROW_MAJOR ? n : rows); }
-
 // the transpose's host-side argument checks (SBLAS_OK, SBLAS_E_INVALID or SBLAS_E_WORKSPACE)
 int transpose_args(int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
                    const int32_t *colptr, const int32_t *rowidx, const double *valT, const void *workspace, size_t workspace_bytes)
@@ -345,7 +316,7 @@ int transpose_args(int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowpt
     if (nnz > 0 && (rows == 0 || cols == 0)) return SBLAS_E_INVALID; // no row / column to hold a nonzero
     const size_t need = sblas_hip_csr_transpose_workspace(rows, cols, nnz);
     if (need > 0 && (!workspace || workspace_bytes < need)) return SBLAS_E_WORKSPACE;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return SBLAS_E_INVALID;
+    if (!aligned16(workspace)) return SBLAS_E_INVALID;
     return SBLAS_OK;
 }
 
@@ -353,19 +324,17 @@ int transpose_args(int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowpt
 struct TransposePlan {
     int dev = -1;
     int64_t rows = 0, cols = 0, nnz = 0, n = 0;
-    void *buf = nullptr; // colptr | rowidx | valT | perm
+    DeviceBuffer buf; // colptr | rowidx | valT | perm
     size_t bytes = 0;
     int32_t *colptr = nullptr, *rowidx = nullptr, *perm = nullptr;
     double *valT = nullptr;
     void *spmv = nullptr, *spmm = nullptr;
+    ~TransposePlan()
+    {
+        sblas_hip_spmv_plan_destroy(spmv);
+        sblas_hip_spmm_plan_destroy(spmm);
+    }
 };
-
-int plan_fail(TransposePlan *p, void **plan_out, int rc)
-{
-    sblas_hip_transpose_plan_destroy(p);
-    *plan_out = nullptr;
-    return rc;
-}
 
 } // namespace
 
@@ -416,55 +385,47 @@ int sblas_hip_transpose_plan_create(int dev, void *stream, int64_t rows, int64_t
         return SBLAS_E_INVALID;
     if (!rowptr || (nnz > 0 && (!colidx || !val)) || (flags & ~SBLAS_TRANSPOSE_SPLIT) != 0) return SBLAS_E_INVALID;
     if (nnz > 0 && (rows == 0 || cols == 0)) return SBLAS_E_INVALID;
-    TransposePlan *p = new TransposePlan;
+    std::unique_ptr<TransposePlan> p(new TransposePlan);
     p->dev = resolve_device(dev), p->rows = rows, p->cols = cols, p->nnz = nnz, p->n = n;
     if (cols == 0) { // A^T has no rows: every product is empty, nothing is held on the device
-        *plan_out = p;
+        *plan_out = p.release();
         return SBLAS_OK;
     }
     // the transpose kernels never see a column index outside [0, cols)
     if (rows > 0) {
         const int vrc = sblas_hip_debug_validate_csr_i32(dev, stream, rows, cols, nnz, rowptr, colidx);
-        if (vrc) return plan_fail(p, plan_out, vrc);
+        if (vrc) return vrc;
     }
     DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
     hipStream_t s = (hipStream_t)stream;
     const size_t cp = align16(((size_t)cols + 1) * sizeof(int32_t)), ri = align16((size_t)nnz * sizeof(int32_t));
     const size_t vt = align16((size_t)nnz * sizeof(double));
     p->bytes = cp + ri + vt + ri;
-    if (hipMalloc(&p->buf, p->bytes) != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
-    char *b = static_cast<char *>(p->buf);
-    p->colptr = reinterpret_cast<int32_t *>(b), p->rowidx = reinterpret_cast<int32_t *>(b + cp);
-    p->valT = reinterpret_cast<double *>(b + cp + ri), p->perm = reinterpret_cast<int32_t *>(b + cp + ri + vt);
-    const size_t wsb = sblas_hip_csr_transpose_workspace(rows, cols, nnz);
-    void *ws = nullptr;
-    if (wsb > 0 && hipMalloc(&ws, wsb) != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
-    hipError_t e = run_transpose(s, rows, cols, nnz, rowptr, colidx, val, p->colptr, p->rowidx, p->valT, p->perm, ws);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (ws) (void)hipFree(ws);
-    if (e != hipSuccess) return plan_fail(p, plan_out, SBLAS_E_HIP);
+    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) return SBLAS_E_HIP;
+    p->colptr = p->buf.at<int32_t>(), p->rowidx = p->buf.at<int32_t>(cp);
+    p->valT = p->buf.at<double>(cp + ri), p->perm = p->buf.at<int32_t>(cp + ri + vt);
+    {
+        const size_t wsb = sblas_hip_csr_transpose_workspace(rows, cols, nnz);
+        DeviceBuffer ws; // freed before the sub-plans are made
+        if (wsb > 0 && ws.alloc(p->dev, wsb) != hipSuccess) return SBLAS_E_HIP;
+        hipError_t e = run_transpose(s, rows, cols, nnz, rowptr, colidx, val, p->colptr, p->rowidx, p->valT, p->perm, ws.at<void>());
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return SBLAS_E_HIP;
+    }
     int rc = sblas_hip_spmv_plan_create(dev, stream, cols, rows, nnz, p->colptr, p->rowidx, &p->spmv);
     if (rc == SBLAS_OK && n > 0)
         rc = (flags & SBLAS_TRANSPOSE_SPLIT)
                  ? sblas_hip_spmm_plan_create_split(dev, stream, cols, rows, nnz, p->colptr, p->rowidx, n, 0, 0, &p->spmm)
                  : sblas_hip_spmm_plan_create(dev, stream, cols, rows, nnz, p->colptr, p->rowidx, n, &p->spmm);
-    if (rc != SBLAS_OK) return plan_fail(p, plan_out, rc);
-    *plan_out = p;
+    if (rc != SBLAS_OK) return rc;
+    *plan_out = p.release();
     return SBLAS_OK;
 }
 
 int sblas_hip_transpose_plan_destroy(void *plan)
 {
-    if (!plan) return SBLAS_OK;
-    TransposePlan *p = static_cast<TransposePlan *>(plan);
-    if (p->spmv) sblas_hip_spmv_plan_destroy(p->spmv);
-    if (p->spmm) sblas_hip_spmm_plan_destroy(p->spmm);
-    if (p->buf) {
-        DeviceScope scope(p->dev);
-        (void)hipFree(p->buf);
-    }
-    delete p;
+    delete static_cast<TransposePlan *>(plan);
     return SBLAS_OK;
 }
 
@@ -484,7 +445,7 @@ int sblas_hip_transpose_plan_info(const void *plan, int64_t out[8])
     int64_t sv[8] = {0}, sm[4] = {0};
     if (p->spmv) sblas_hip_spmv_plan_info(p->spmv, sv);
     if (p->spmm) sblas_hip_spmm_plan_split_info(p->spmm, sm);
-    out[0] = p->buf != nullptr, out[1] = p->nnz, out[2] = (int64_t)p->bytes, out[3] = p->spmm != nullptr;
+    out[0] = (bool)p->buf, out[1] = p->nnz, out[2] = (int64_t)p->bytes, out[3] = p->spmm != nullptr;
     out[4] = p->spmm ? p->n : 0, out[5] = sv[6], out[6] = sm[0], out[7] = 0;
     return SBLAS_OK;
 }
