@@ -346,6 +346,65 @@ int sblas_hip_spmm_csr_t_f64_i32_planned(const void *plan, int dev, void *stream
                                          int order_b, int64_t n, double alpha, double beta, double *C, int64_t ldc,
                                          int order_c, void *workspace, size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------
+ * CSR from COO triplets on the device, with re-assembly.  Input: nnz triplets (coo_row[k], coo_col[k], coo_val[k]) in
+ * any order, duplicates allowed; int32 indices, fp64 values; 0 <= row < rows, 0 <= col < cols; rows, cols and nnz below
+ * 2^31.  The contract:
+ *   - order: entries sorted by (row, col), equal (row, col) pairs in input order -- numpy.lexsort((coo_col, coo_row)),
+ *     which is stable.  perm[i] = the input position of sorted position i;
+ *   - SBLAS_COO_KEEP: every triplet becomes one CSR entry: colidx[i] = coo_col[perm[i]], val[i] = coo_val[perm[i]],
+ *     rowptr[r] = the number of triplets with row < r, runptr[i] = i (nnz + 1 entries).  Duplicates as stored: the form
+ *     every other entry point accepts;
+ *   - SBLAS_COO_SUM: one CSR entry per distinct (row, col).  Its value is the run's first value with each later value of
+ *     the run added to it one at a time in input order, ((v1 + v2) + v3) + ..., plain fp64 adds; a run of one is copied
+ *     (-0.0 stays -0.0).  The structure never depends on the values: a sum that cancels to zero stays as a stored zero,
+ *     and so do NaN and Inf.  runptr has csr_nnz + 1 entries: runptr[e] is the sorted position where entry e's run
+ *     starts, runptr[csr_nnz] = nnz.  csr_nnz = rowptr[rows];
+ *   - no floating-point atomics and nothing that depends on scheduling: the same input gives the same bits on every
+ *     run and under graph replay.
+ * One lane adds a whole run, which is what fixes the order; assembly runs are short.  A run of a million duplicates is
+ * added by one lane and is slow (the run's values are still fetched by a whole workgroup); there is no second
+ * summation order for it.
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_COO_KEEP 0
+#define SBLAS_COO_SUM 1
+/* Bytes of workspace sblas_hip_coo_to_csr_f64_i32 needs: 0 for nnz <= 0, otherwise 16 per triplet for the sort's keys and
+ * payloads (reused by the structure passes), 1 KiB per 4096 triplets of digit counts and the scans' block sums.  Depends
+ * on nnz alone. */
+size_t sblas_hip_coo_to_csr_workspace(int64_t rows, int64_t cols, int64_t nnz);
+/* COO -> CSR on the device, one shot: rowptr[rows + 1], colidx, val and, when not NULL, perm[nnz] and runptr.  The caller
+ * sizes colidx and val for nnz entries and runptr for nnz + 1; with SBLAS_COO_SUM the entry count is rowptr[rows] and
+ * what lies beyond it (beyond runptr[count]) is unspecified.  coo_val and val are both given or both NULL (structure
+ * only).  A stable LSD radix sort, 8 bits a pass: ceil(bits(cols - 1) / 8) + ceil(bits(rows - 1) / 8) passes (none for a
+ * dimension of 1).  Stream-ordered, allocates nothing, never synchronises, graph-capturable; trusts the triplets like
+ * the other compute calls -- except under SBLAS_VALIDATE=1, which checks the index ranges first and waits for the answer
+ * (SBLAS_E_INVALID, nothing else runs).  nnz == 0, rows == 0 and cols == 0 are valid when no triplet needs a place.
+ * workspace: 16-byte aligned, sblas_hip_coo_to_csr_workspace bytes. */
+int sblas_hip_coo_to_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                 const int32_t *coo_row, const int32_t *coo_col, const double *coo_val, int dup,
+                                 int32_t *rowptr, int32_t *colidx, double *val, int32_t *perm, int32_t *runptr,
+                                 void *workspace, size_t workspace_bytes);
+/* An assembly plan: the structure is fixed, the values change (a time step, a Newton iteration).
+ *   - create always checks the index ranges on the device first: a triplet outside the matrix returns SBLAS_E_INVALID, no
+ *     plan is made and no sort kernel runs on it.  It then sorts once into buffers the plan owns (rowptr, colidx, perm,
+ *     runptr: (rows + 1) * 4 + 12 * (nnz + 1) bytes), frees the sort workspace and synchronises `stream`;
+ *   - rowptr and colidx are ordinary device arrays: the SpMV, SpMM and transpose plans are built on them unchanged;
+ *   - assemble writes the CSR values of new triplet values: val_out[e] = the left-to-right sum of coo_val[perm[k]],
+ *     k in [runptr[e], runptr[e + 1]) (SBLAS_COO_KEEP: the plain gather).  One launch on the calling thread's current
+ *     device; allocates nothing, never synchronises, graph-capturable.  SBLAS_E_INVALID when the current device is not
+ *     the plan's;
+ *   - one call at a time per plan, as for the plans above. */
+int sblas_hip_coo_plan_create(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *coo_row,
+                              const int32_t *coo_col, int dup, void **plan_out);
+/* out: [0] rows, [1] cols, [2] input nnz, [3] CSR nnz, [4] longest run, [5] sort passes, [6] bytes held, [7] dup */
+int sblas_hip_coo_plan_info(const void *plan, int64_t out[8]);
+/* the plan's device arrays (any output may be NULL): rowptr (rows + 1), colidx (CSR nnz), perm (nnz), runptr (CSR nnz +
+ * 1); they live until the plan is destroyed */
+int sblas_hip_coo_plan_csr(const void *plan, const int32_t **rowptr, const int32_t **colidx, const int32_t **perm,
+                           const int32_t **runptr);
+int sblas_hip_coo_plan_assemble(const void *plan, void *stream, const double *coo_val, double *val_out);
+int sblas_hip_coo_plan_destroy(void *plan);
+
 /* sblas_partition_nnz (below) for 64-bit row pointers */
 int64_t sblas_partition_nnz_i64(const int64_t *rowptr, int64_t rows, int64_t nnz, int n_gpu, int i_gpu,
                                 int64_t *start_row, int64_t *stop_row, int64_t *nnz_i, int64_t *first_nnz,

@@ -1,4 +1,4 @@
-// capi_util.h -- helpers of the C-ABI entry points (capi.hip, transpose.hip): argument checks, the device switch of a
+// capi_util.h -- helpers of the C-ABI entry points (capi.hip, transpose.hip, coo.hip): argument checks, the device switch of a
 // call and the device buffers a plan owns.  Internal to each translation unit: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@ struct DeviceScope {
         if (prev != dev) {
             err = hipSetDevice(dev);
             switched = (err == hipSuccess);
+            if (!switched) (void)hipGetLastError(); // reported through err: the next launch check must not see it again
         }
     }
     ~DeviceScope()

@@ -299,6 +299,55 @@ template <typename IdxType, typename DataType> class CsrSparseMatrix {
         }
         printf("input matrix A: ( %i, %i ) nnz = %i\n", m, n, nnzA);
     }
+    // COO triplets (any order, duplicates allowed) -> host CSR, converted on GPU 0 (sblas_hip_coo_to_csr_f64_i32): the
+    // triplets go up, are sorted by (row, col) there -- equal pairs in input order -- and the CSR comes down into the
+    // usual pinned host arrays.  dup = SBLAS_COO_KEEP: one entry per triplet; SBLAS_COO_SUM: one entry per distinct
+    // (row, col), its duplicates added left to right in input order.  sync2gpu and the ops then work as ever.
+    CsrSparseMatrix(const CooSparseMatrix<IdxType, DataType> &coo, int dup = SBLAS_COO_KEEP)
+        : csrRowPtr(NULL), csrColIdx(NULL), csrVal(NULL), csrRowPtr_gpu(NULL), csrColIdx_gpu(NULL),
+          csrVal_gpu(NULL), nnz_gpu(NULL), starting_row_gpu(NULL), stoping_row_gpu(NULL), nnz(0), height(coo.height),
+          width(coo.width), n_gpu(0), policy(none), spmm_plan_gpu(NULL), spmm_plan_n(NULL), spmv_plan_gpu(NULL)
+    {
+        static_assert(std::is_same<IdxType, int>::value && std::is_same<DataType, double>::value,
+                      "CsrSparseMatrix from CooSparseMatrix: the device conversion exists for <int, double> only");
+        const size_t n = (size_t)coo.nnz, rp_bytes = ((size_t)height + 1) * sizeof(int);
+        hipStream_t s = sblas_rt::stream(0);
+        int *row = sblas_detail::to_device_async(0, (const int *)coo.cooRowIdx, n);
+        int *col = sblas_detail::to_device_async(0, (const int *)coo.cooColIdx, n);
+        double *cval = sblas_detail::to_device_async(0, (const double *)coo.cooVal, n);
+        int *rp = NULL, *ci = NULL;
+        double *v = NULL;
+        void *ws = NULL;
+        const size_t wsb = sblas_hip_coo_to_csr_workspace(height, width, (int64_t)n);
+        SAFE_ALOC_GPU(rp, rp_bytes);
+        SAFE_ALOC_GPU(ci, n * sizeof(int));
+        SAFE_ALOC_GPU(v, n * sizeof(double));
+        SAFE_ALOC_GPU(ws, wsb);
+        const int rc = sblas_hip_coo_to_csr_f64_i32(-1, s, height, width, (int64_t)n, row, col, cval, dup, rp, ci, v, NULL, NULL,
+                                                    wsb ? ws : NULL, wsb);
+        if (rc != SBLAS_OK) {
+            fprintf(stderr, "S-BLAS: COO -> CSR failed: %s\n", sblas_hip_error_string(rc));
+            exit(-1);
+        }
+        SAFE_ALOC_HOST(csrRowPtr, rp_bytes);
+        CUDA_SAFE_CALL(hipMemcpyAsync((int *)csrRowPtr, rp, rp_bytes, hipMemcpyDeviceToHost, s));
+        CUDA_SAFE_CALL(hipStreamSynchronize(s));
+        nnz = csrRowPtr[height]; // SBLAS_COO_SUM: the distinct (row, col) pairs
+        SAFE_ALOC_HOST(csrColIdx, get_col_idx_size());
+        SAFE_ALOC_HOST(csrVal, get_val_size());
+        if (nnz) {
+            CUDA_SAFE_CALL(hipMemcpyAsync(csrColIdx, ci, get_col_idx_size(), hipMemcpyDeviceToHost, s));
+            CUDA_SAFE_CALL(hipMemcpyAsync(csrVal, v, get_val_size(), hipMemcpyDeviceToHost, s));
+            CUDA_SAFE_CALL(hipStreamSynchronize(s));
+        }
+        SAFE_FREE_GPU(row);
+        SAFE_FREE_GPU(col);
+        SAFE_FREE_GPU(cval);
+        SAFE_FREE_GPU(rp);
+        SAFE_FREE_GPU(ci);
+        SAFE_FREE_GPU(v);
+        SAFE_FREE_GPU(ws);
+    }
     // the per-GPU SpMM plans (made by sblas_spmm_csr_v1 / _v2 on first use) describe the device copies: gone with them
     void drop_spmm_plans()
     {

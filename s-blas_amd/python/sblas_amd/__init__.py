@@ -37,6 +37,8 @@ EXPORTS = [
     "sblas_hip_transpose_plan_create", "sblas_hip_transpose_plan_update_values", "sblas_hip_transpose_plan_info",
     "sblas_hip_transpose_plan_csc", "sblas_hip_transpose_plan_destroy", "sblas_hip_spmv_csr_t_f64_i32_planned",
     "sblas_hip_spmm_csr_t_f64_i32_planned",
+    "sblas_hip_coo_to_csr_workspace", "sblas_hip_coo_to_csr_f64_i32", "sblas_hip_coo_plan_create", "sblas_hip_coo_plan_info",
+    "sblas_hip_coo_plan_csr", "sblas_hip_coo_plan_assemble", "sblas_hip_coo_plan_destroy",
 ]
 
 
@@ -173,6 +175,20 @@ def lib():
     L.sblas_hip_transpose_plan_csc.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.sblas_hip_transpose_plan_destroy.restype = C.c_int
     L.sblas_hip_transpose_plan_destroy.argtypes = [vp]
+    L.sblas_hip_coo_to_csr_workspace.restype = sz
+    L.sblas_hip_coo_to_csr_workspace.argtypes = [i64, i64, i64]
+    L.sblas_hip_coo_to_csr_f64_i32.restype = C.c_int
+    L.sblas_hip_coo_to_csr_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, sz]
+    L.sblas_hip_coo_plan_create.restype = C.c_int
+    L.sblas_hip_coo_plan_create.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, C.c_int, C.POINTER(vp)]
+    L.sblas_hip_coo_plan_info.restype = C.c_int
+    L.sblas_hip_coo_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_coo_plan_csr.restype = C.c_int
+    L.sblas_hip_coo_plan_csr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_coo_plan_assemble.restype = C.c_int
+    L.sblas_hip_coo_plan_assemble.argtypes = [vp, vp, vp, vp]
+    L.sblas_hip_coo_plan_destroy.restype = C.c_int
+    L.sblas_hip_coo_plan_destroy.argtypes = [vp]
     L.sblas_hip_spmv_csr_t_f64_i32_planned.restype = C.c_int
     L.sblas_hip_spmv_csr_t_f64_i32_planned.argtypes = [vp, C.c_int, vp, vp, f64, f64, vp]
     L.sblas_hip_spmm_csr_t_f64_i32_planned.restype = C.c_int
@@ -929,6 +945,164 @@ class TransposePlan:
     def destroy(self):
         if self.handle:
             lib().sblas_hip_transpose_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------------------------------
+# CSR from COO triplets (sblas_hip_coo_to_csr_f64_i32, sblas_hip_coo_plan_*)
+# ------------------------------------------------------------------------------------------
+COO_KEEP, COO_SUM = 0, 1
+_DUP = {"keep": COO_KEEP, "sum": COO_SUM}
+
+
+def _dup(dup):
+    if dup not in _DUP:
+        raise SblasError("dup must be 'keep' or 'sum', not %r" % (dup,))
+    return _DUP[dup]
+
+
+def _triplets(row, col, val):
+    """dtype, contiguity and lengths of a set of triplets (val may be None) -> nnz"""
+    import torch
+    _typed("row", row, torch.int32), _typed("col", col, torch.int32)
+    nnz = int(row.numel())
+    if int(col.numel()) != nnz:
+        raise SblasError("col has %d entries, row %d" % (col.numel(), nnz))
+    if val is not None:
+        _typed("val", val, torch.float64)
+        if int(val.numel()) != nnz:
+            raise SblasError("val has %d entries, row %d" % (val.numel(), nnz))
+    return nnz
+
+
+def coo_workspace_bytes(rows, cols, nnz):
+    return int(lib().sblas_hip_coo_to_csr_workspace(rows, cols, nnz))
+
+
+def coo_to_csr(rows, cols, row, col, val=None, dup="keep", stream=None):
+    """CSR of the triplets (row[k], col[k], val[k]) -- any order, duplicates allowed -- as (rowptr, colidx, val, perm,
+    runptr) torch tensors on the triplets' device.  Entries are sorted by (row, col), equal pairs in input order
+    (numpy.lexsort((col, row))); perm[i] is the input position of sorted position i.  dup="keep": one entry per triplet;
+    dup="sum": one entry per distinct (row, col), its run added left to right in input order, runptr[e] the sorted
+    position where entry e's run starts.  val=None: structure only (the returned val is None).  Allocates its own
+    workspace; stream-ordered.  "sum" trims colidx, val and runptr to the entry count, which it reads back from
+    rowptr[rows]: the one place that waits for the device."""
+    import torch
+    mode = _dup(dup)
+    nnz = _triplets(row, col, val)
+    pr = _dev_ptr(row, torch.int32, "row") if nnz else None
+    pc = _dev_ptr(col, torch.int32, "col") if nnz else None
+    pv = _dev_ptr(val, torch.float64, "val") if val is not None and nnz else None
+    if not row.is_cuda:
+        raise SblasError("row must be a GPU tensor (no CPU path exists)")
+    dev = row.device
+    with torch.cuda.device(dev):
+        rowptr = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+        colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+        out = torch.empty(nnz, dtype=torch.float64, device=dev) if val is not None else None
+        perm = torch.empty(nnz, dtype=torch.int32, device=dev)
+        runptr = torch.empty(nnz + 1, dtype=torch.int32, device=dev)
+        wsb = coo_workspace_bytes(rows, cols, nnz)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+        rc = lib().sblas_hip_coo_to_csr_f64_i32(
+            -1, _stream(stream), rows, cols, nnz, pr, pc, pv, mode, rowptr.data_ptr(), colidx.data_ptr() if nnz else None,
+            out.data_ptr() if out is not None and nnz else None, perm.data_ptr() if nnz else None, runptr.data_ptr(),
+            ws.data_ptr() if ws is not None else None, wsb)
+        check(rc, "sblas_hip_coo_to_csr_f64_i32")
+        if mode == COO_SUM and nnz:
+            if stream is not None:
+                stream.synchronize()
+            count = int(rowptr[rows].item())
+            colidx, runptr = colidx[:count], runptr[:count + 1]
+            out = out[:count] if out is not None else None
+    return rowptr, colidx, out, perm, runptr
+
+
+def coo_from_torch(t):
+    """(rows, cols, row, col, val) of a 2-D fp64 torch.sparse_coo_tensor, coalesced or not: int32 index tensors and the
+    values as stored, on the tensor's own device.  Nothing is sorted or summed here: that is coo_to_csr's / CooPlan's
+    work (they refuse a CPU tensor)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.layout != torch.sparse_coo:
+        raise SblasError("expected a torch.sparse_coo_tensor")
+    if t.dim() != 2 or t.sparse_dim() != 2:
+        raise SblasError("expected a 2-D sparse tensor with two sparse dimensions")
+    if t.dtype != torch.float64:
+        raise SblasError("expected float64 values, got %s" % t.dtype)
+    rows, cols = int(t.shape[0]), int(t.shape[1])
+    idx, val = t._indices(), t._values()
+    nnz = int(val.numel())
+    if rows >= 1 << 31 or cols >= 1 << 31 or nnz >= 1 << 31:
+        raise SblasError("rows, cols and nnz must be below 2^31 (int32 indices)")
+    return rows, cols, idx[0].to(torch.int32).contiguous(), idx[1].to(torch.int32).contiguous(), val.contiguous()
+
+
+class CooPlan:
+    """The sorted structure of one set of (row, col) triplets (sblas_hip_coo_plan_create): rowptr, colidx, perm and runptr
+    in the plan's own buffers.  assemble(val) turns new triplet values into CSR values with one launch.  Creation checks
+    the index ranges on the device and refuses a triplet outside the matrix.  destroy() / garbage collection frees the
+    device buffers."""
+
+    def __init__(self, rows, cols, row, col, dup="keep", stream=None):
+        import torch
+        self.rows, self.cols, self.dup = rows, cols, dup
+        self.handle = None
+        mode = _dup(dup)
+        self.nnz = _triplets(row, col, None)
+        self.device = row.device
+        h = C.c_void_p()
+        pr = _dev_ptr(row, torch.int32, "row") if self.nnz else None
+        pc = _dev_ptr(col, torch.int32, "col") if self.nnz else None
+        if not row.is_cuda:
+            raise SblasError("row must be a GPU tensor (no CPU path exists)")
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_coo_plan_create(-1, _stream(stream), rows, cols, self.nnz, pr, pc, mode, C.byref(h)),
+                  "sblas_hip_coo_plan_create")
+        self.handle = h
+        self.csr_nnz = self.info()["csr_nnz"]
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        check(lib().sblas_hip_coo_plan_info(self.handle, out), "sblas_hip_coo_plan_info")
+        return dict(rows=int(out[0]), cols=int(out[1]), nnz=int(out[2]), csr_nnz=int(out[3]), longest_run=int(out[4]),
+                    passes=int(out[5]), bytes=int(out[6]), dup="sum" if out[7] == COO_SUM else "keep")
+
+    def csr(self):
+        """(rowptr, colidx, perm, runptr): torch views of the plan's device arrays; they live as long as the plan."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(4)]
+        check(lib().sblas_hip_coo_plan_csr(self.handle, *[C.byref(p) for p in ptrs]), "sblas_hip_coo_plan_csr")
+        def one(p, n):
+            if n == 0:
+                return torch.empty(0, dtype=torch.int32, device=self.device)
+            return torch.as_tensor(_DeviceArray(p.value, n, "<i4"), device=self.device)
+        return tuple(one(p, n) for p, n in zip(ptrs, (self.rows + 1, self.csr_nnz, self.nnz, self.csr_nnz + 1)))
+
+    def assemble(self, val, out=None, stream=None):
+        """The CSR values of the triplet values `val` (csr_nnz of them), written to `out` when given.  One launch."""
+        import torch
+        _typed("val", val, torch.float64)
+        if val.numel() != self.nnz:
+            raise SblasError("val has %d entries, the plan %d" % (val.numel(), self.nnz))
+        if out is None:
+            out = torch.empty(self.csr_nnz, dtype=torch.float64, device=val.device)
+        _typed("out", out, torch.float64)
+        if out.numel() < self.csr_nnz:
+            raise SblasError("out has %d entries, the CSR %d" % (out.numel(), self.csr_nnz))
+        pv = _dev_ptr(val, torch.float64, "val") if self.nnz else None
+        po = _dev_ptr(out, torch.float64, "out") if self.nnz else None
+        check(lib().sblas_hip_coo_plan_assemble(self.handle, _stream(stream), pv, po), "sblas_hip_coo_plan_assemble")
+        return out
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_coo_plan_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
