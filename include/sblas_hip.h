@@ -405,6 +405,46 @@ int sblas_hip_coo_plan_csr(const void *plan, const int32_t **rowptr, const int32
 int sblas_hip_coo_plan_assemble(const void *plan, void *stream, const double *coo_val, double *val_out);
 int sblas_hip_coo_plan_destroy(void *plan);
 
+/* ---------------------------------------------------------------------------------------
+ * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
+ * (the gradient of C = A * B with respect to A's values with X = dC and Y = B; edge scores; residuals on a pattern).
+ *   - A gives its PATTERN only (rowptr, colidx).  Unsorted rows and duplicate entries are legal, as everywhere else; a
+ *     duplicate gets the same value twice.  rowptr is relative to the colidx / out pointers passed, so a re-based method-2
+ *     row block works with X advanced to the block's first row.  out: nnz values in CSR order.
+ *   - X is rows x k, Y is cols x k: row c of Y is what entry (r, c) is multiplied with.  In the cuSPARSE / rocSPARSE
+ *     wording (C = alpha * (A * B) o spy(C) + beta * C with B of shape k x cols) Y is B transposed: a row-major B is a
+ *     column-major Y with the same leading dimension, a column-major B a row-major Y.
+ *   - orders and leading dimensions as in sblas_hip_spmm_csr_ordered: SBLAS_ROW_MAJOR X[r * ldx + j] (ldx >= k),
+ *     SBLAS_COL_MAJOR X[r + j * ldx] (ldx >= rows, for Y ldy >= cols).  A row-major operand is read in place with 64-bit
+ *     offsets: 16-byte loads when both bases are 16-byte aligned and both leading dimensions even, 8-byte loads
+ *     otherwise (same bits).  A column-major operand is first copied row-major into the workspace by the SpMM staging
+ *     copy (64-bit addressing, no size limit of its own); sblas_hip_sddmm_csr_workspace is 0 when both are row-major and
+ *     grows only with the column-major ones.  workspace: 16-byte aligned.
+ *   - columns k .. ld - 1 of a row-major operand and whatever lies behind its last row are never loaded.
+ *   - beta == 0: out is not read (a NaN in it does not survive), as for C in SpMM.  alpha == 0 is no shortcut, as in
+ *     SpMM: the dot product is formed and multiplied, so NaN / Inf in the operands reach out.
+ *   - k == 0: out = alpha * 0 + beta * out (the operands may be NULL).  nnz == 0 (and with it rows == 0, cols == 0)
+ *     launches nothing.  A bad order, a leading dimension below its minimum, a missing pointer: SBLAS_E_INVALID; a
+ *     missing or short workspace: SBLAS_E_WORKSPACE; both before anything touches the device.
+ *   - stream-ordered, allocates nothing, never synchronises, graph-capturable.  SBLAS_VALIDATE=1 checks the structure
+ *     first (synchronises), as for SpMM.
+ *   - summation order: a function of k alone.  The bits of out[e] depend only on the k values of the two operand rows,
+ *     on k, alpha, beta and the old out[e] -- not on where e sits, its row's length, its neighbours, the operands'
+ *     orders, leading dimensions or alignment, or the run.  No floating-point atomics.  k is cut into slices of 128
+ *     elements (the last one shorter); a slice of kj elements is summed by G = 1, 2, 4, 8, 16 lanes for kj <= 4, 8,
+ *     32, 64, more: lane l adds the products of elements 2q, 2q + 1 for q = l, l + G, l + 2G, ... in that order, one fma
+ *     each, from +0; the G sums are folded s += s[l ^ 1], s += s[l ^ 2], s += s[l ^ 4], s += s[l ^ 8].  The first slice
+ *     gives out = alpha * s, or fma(beta, out, alpha * s); every later slice out = out + alpha * s.
+ * fp64 values and int32 indices only.
+ * ------------------------------------------------------------------------------------- */
+size_t sblas_hip_sddmm_csr_workspace(int64_t rows, int64_t cols, int64_t nnz, int64_t k, int order_x, int order_y);
+int sblas_hip_sddmm_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                const int32_t *rowptr, const int32_t *colidx,
+                                const double *X, int64_t ldx, int order_x,
+                                const double *Y, int64_t ldy, int order_y,
+                                int64_t k, double alpha, double beta, double *out,
+                                void *workspace, size_t workspace_bytes);
+
 /* sblas_partition_nnz (below) for 64-bit row pointers */
 int64_t sblas_partition_nnz_i64(const int64_t *rowptr, int64_t rows, int64_t nnz, int n_gpu, int i_gpu,
                                 int64_t *start_row, int64_t *stop_row, int64_t *nnz_i, int64_t *first_nnz,

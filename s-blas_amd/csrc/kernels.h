@@ -71,6 +71,17 @@ __device__ __forceinline__ void store_rows_c(T *__restrict__ C, int64_t ldc, int
     }
 }
 
+// Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one).  Give every XCD one contiguous
+// range of panels so that neighbouring panels -- which read overlapping Bt rows -- share an L2 (speed only;
+// any placement is correct).  Bijective for every panel count.
+__device__ __forceinline__ int xcd_contiguous_panel(int b, int npanels)
+{
+    const int xcd = b & 7, idx = b >> 3;
+    const int q = npanels >> 3, r = npanels & 7;
+    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    return base + idx;
+}
+
 // Experiment / test switches, read from the environment once (kernels.hip); options_reload() re-reads them.
 struct Options {
     int spmm_variant = SPMM_VARIANT_AUTO;

@@ -277,17 +277,7 @@ constexpr int WIDE_ROWS_PER_WAVE = 1;
 constexpr int WIDE_PANEL = WIDE_WAVES * WIDE_ROWS_PER_WAVE;
 constexpr int DPP_LONG = 4096;            // entries from which a row of the row-per-wave kernel is computed by the whole workgroup
 
-// Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one).  Give every XCD one contiguous
-// range of panels so that neighbouring panels -- which read overlapping Bt rows -- share an L2 (speed only;
-// any placement is correct).  Bijective for every panel count.
-__device__ __forceinline__ int xcd_contiguous_panel(int b, int npanels)
-{
-    const int xcd = b & 7, idx = b >> 3;
-    const int q = npanels >> 3, r = npanels & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
-
+// (xcd_contiguous_panel, the map of workgroups to panels, lives in kernels.h: sddmm.hip uses it too)
 
 // panel census of the windowed kernel: [0] windowed, [1] direct (too sparse over its span), [2] windowed but
 // recomputed by the fallback.  One atomic per panel; read through sblas_hip_debug_spmm_panel_stats.

@@ -39,6 +39,7 @@ EXPORTS = [
     "sblas_hip_spmm_csr_t_f64_i32_planned",
     "sblas_hip_coo_to_csr_workspace", "sblas_hip_coo_to_csr_f64_i32", "sblas_hip_coo_plan_create", "sblas_hip_coo_plan_info",
     "sblas_hip_coo_plan_csr", "sblas_hip_coo_plan_assemble", "sblas_hip_coo_plan_destroy",
+    "sblas_hip_sddmm_csr_workspace", "sblas_hip_sddmm_csr_f64_i32",
 ]
 
 
@@ -195,6 +196,11 @@ def lib():
     L.sblas_hip_spmm_csr_t_f64_i32_planned.argtypes = [vp, C.c_int, vp, vp, i64, C.c_int, i64, f64, f64, vp, i64, C.c_int, vp, sz]
     L.sblas_partition_nnz_i64.restype = i64
     L.sblas_partition_nnz_i64.argtypes = [vp, i64, i64, C.c_int, C.c_int] + [C.POINTER(i64)] * 4 + [vp]
+    L.sblas_hip_sddmm_csr_workspace.restype = sz
+    L.sblas_hip_sddmm_csr_workspace.argtypes = [i64, i64, i64, i64, C.c_int, C.c_int]
+    L.sblas_hip_sddmm_csr_f64_i32.restype = C.c_int
+    L.sblas_hip_sddmm_csr_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, C.c_int, vp, i64, C.c_int, i64, f64, f64,
+                                              vp, vp, sz]
     _lib = L
     return L
 
@@ -1110,3 +1116,66 @@ class CooPlan:
             self.destroy()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------------------
+# SDDMM on a CSR pattern (sblas_hip_sddmm_csr_f64_i32)
+# ------------------------------------------------------------------------------------------
+def sddmm_workspace_bytes(rows, cols, nnz, k, order_x=ROW_MAJOR, order_y=ROW_MAJOR):
+    """Bytes of workspace of an SDDMM call: 0 when both operands are ROW_MAJOR, a row-major copy per COL_MAJOR operand."""
+    return int(lib().sblas_hip_sddmm_csr_workspace(rows, cols, nnz, k, order_x, order_y))
+
+
+def _sddmm_call(rows, cols, nnz, prow, pcol, px, ldx, order_x, py, ldy, order_y, k, alpha, beta, pout, workspace, stream):
+    if workspace is not None and not workspace.is_contiguous():
+        raise SblasError("workspace must be contiguous")
+    wptr = workspace.data_ptr() if workspace is not None and workspace.numel() else None
+    wbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    check(lib().sblas_hip_sddmm_csr_f64_i32(-1, _stream(stream), rows, cols, nnz, prow, pcol, px, ldx, order_x, py, ldy, order_y,
+                                            k, alpha, beta, pout, wptr, wbytes), "sblas_hip_sddmm_csr_f64_i32")
+
+
+def sddmm(rows, cols, rowptr, colidx, X, ldx, order_x, Y, ldy, order_y, k, alpha, beta, out, workspace=None, stream=None,
+          x_offset=0, nnz=None):
+    """out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e] over the pattern (rowptr, colidx).  X (rows x k), Y
+    (cols x k): flat device tensors, each COL_MAJOR or ROW_MAJOR; x_offset: element offset into X (a re-based row block
+    points X at its first row).  out: nnz values in CSR order.  workspace: a device tensor of at least
+    sddmm_workspace_bytes(...) bytes, needed only for COL_MAJOR operands."""
+    import torch
+    nnz = int(colidx.numel()) if nnz is None else int(nnz)
+    px = _dev_ptr(X, torch.float64, "X") + 8 * x_offset if k and nnz else None
+    py = _dev_ptr(Y, torch.float64, "Y") if k and nnz else None
+    _sddmm_call(rows, cols, nnz, _dev_ptr(rowptr, torch.int32, "rowptr"), _dev_ptr(colidx, torch.int32, "colidx") if nnz else None,
+                px, ldx, order_x, py, ldy, order_y, k, alpha, beta, _dev_ptr(out, torch.float64, "out") if nnz else None,
+                workspace, stream)
+
+
+def sddmm_tensor(A, X, Y, out, alpha=1.0, beta=0.0, workspace=None, stream=None):
+    """SDDMM on 2-D torch tensors without a copy: A = (rows, cols, rowptr, colidx), X rows x k and Y cols x k with order and
+    leading dimension taken from their strides (as spmm_tensor), out a contiguous float64 tensor of nnz entries.
+    workspace: None (allocated here when a column-major operand needs one) or a device tensor of at least
+    sddmm_workspace_bytes(...) bytes."""
+    import torch
+    rows, cols, rowptr, colidx = A
+    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32:
+        raise SblasError("sddmm_tensor handles float64 values and int32 indices only")
+    if not isinstance(X, torch.Tensor) or not isinstance(Y, torch.Tensor) or X.dim() != 2 or Y.dim() != 2:
+        raise SblasError("X and Y must be 2-D tensors")
+    if X.dtype != torch.float64 or Y.dtype != torch.float64:
+        raise SblasError("X and Y must be float64 (sddmm_tensor handles float64 values and int32 indices only)")
+    k = int(X.shape[1])
+    order_x, ldx = _layout(X, rows, k, "X")      # shapes and strides first: they are wrong on any device
+    order_y, ldy = _layout(Y, cols, k, "Y")
+    px, py = _view_ptr(X, "X"), _view_ptr(Y, "Y")
+    nnz = int(colidx.numel())
+    if rowptr.numel() != rows + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), rows))
+    if out.dim() != 1 or out.numel() != nnz:
+        raise SblasError("out must hold one value per stored entry (%d), got shape %s" % (nnz, tuple(out.shape)))
+    pout = _dev_ptr(out, torch.float64, "out")
+    need = sddmm_workspace_bytes(rows, cols, nnz, k, order_x, order_y)
+    if workspace is None and need:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=out.device)
+    _sddmm_call(rows, cols, nnz, _dev_ptr(rowptr, torch.int32, "rowptr"), _dev_ptr(colidx, torch.int32, "colidx") if nnz else None,
+                px if k and nnz else None, ldx, order_x, py if k and nnz else None, ldy, order_y, k, alpha, beta,
+                pout if nnz else None, workspace, stream)

@@ -1,0 +1,191 @@
+"""Autograd for the sparse products: C = A B and y = A x differentiable in A's values and in the dense operand.
+
+    op = CsrOperator(rows, cols, rowptr, colidx, n=64)
+    C = op.matmul(val, B)         # val: nnz values (requires_grad or not), B: cols x n
+    y = op.matvec(val, x)
+
+Forward is the library's SpMM / SpMV.  Backward computes only the halves autograd asks for:
+    dval = SDDMM(X = dC, Y = B) on A's pattern        (sddmm_tensor; k = 1 for matvec)
+    dB   = A^T dC                                     (a TransposePlan the operator makes on the first backward that needs
+                                                       it and refreshes with the values of that forward)
+Backward of backward is not supported.  float64 values, int32 indices, GPU tensors only: there is no CPU path.
+torch is imported here, not by the package."""
+import torch
+
+from . import (SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor,
+               spmm_workspace_bytes)
+
+
+class CsrOperator:
+    """One CSR structure (rows x cols, int32 rowptr / colidx on the GPU) whose values change from call to call.  Owns the
+    plans and workspaces of its products and reuses them: n > 0 makes an SpmmPlan of that width (other widths run
+    unplanned) and the first matvec an SpmvPlan; split=True makes the split forms of the SpMM plans (very long rows and, in the transpose,
+    very long columns).  One call at a time per operator, as for the plans."""
+
+    def __init__(self, rows, cols, rowptr, colidx, n=0, split=False):
+        if not isinstance(rowptr, torch.Tensor) or not isinstance(colidx, torch.Tensor):
+            raise SblasError("rowptr and colidx must be torch tensors")
+        if not rowptr.is_cuda or not colidx.is_cuda:
+            raise SblasError("rowptr and colidx must be GPU tensors (no CPU path exists)")
+        if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32 or not rowptr.is_contiguous() or not colidx.is_contiguous():
+            raise SblasError("rowptr and colidx must be contiguous int32 tensors")
+        if rows < 0 or cols < 0 or rowptr.dim() != 1 or colidx.dim() != 1 or rowptr.numel() != rows + 1:
+            raise SblasError("rowptr must hold rows + 1 = %d entries, got shape %s" % (rows + 1, tuple(rowptr.shape)))
+        self.rows, self.cols, self.rowptr, self.colidx = int(rows), int(cols), rowptr, colidx
+        self.nnz = int(colidx.numel())
+        self.n, self.split = int(n), bool(split)
+        self.device = rowptr.device
+        self.spmm_plan = SpmmPlan(rows, cols, rowptr, colidx, n, split=split) if n > 0 and self.nnz else None
+        self.spmv_plan = None            # made by the first matvec
+        self.transpose_plan = None       # made by the first backward that needs dB / dx
+        self._ws = {}                    # workspaces by purpose, grown on demand
+
+    # ---- argument checks --------------------------------------------------------------------------------------------
+    def _check_val(self, val):
+        if not isinstance(val, torch.Tensor) or not val.is_cuda:
+            raise SblasError("val must be a GPU tensor (no CPU path exists)")
+        if val.dtype != torch.float64 or val.dim() != 1 or val.numel() != self.nnz:
+            raise SblasError("val must be a float64 tensor of %d entries, got %s %s" % (self.nnz, val.dtype, tuple(val.shape)))
+
+    def _check_dense(self, t, rows, what, dim):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+        if t.dtype != torch.float64:
+            raise SblasError("%s must be float64, got %s" % (what, t.dtype))
+        if t.dim() != dim or t.shape[0] != rows:
+            raise SblasError("%s must have %d dimension(s) and %d rows, got shape %s" % (what, dim, rows, tuple(t.shape)))
+        if dim == 2:
+            _layout(t, rows, int(t.shape[1]), what)   # raises on strides no kernel reads
+        elif t.numel() > 1 and t.stride(0) != 1:
+            raise SblasError("%s must be contiguous, got stride %d" % (what, t.stride(0)))
+
+    def _workspace(self, key, nbytes):
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
+            ws = self._ws[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
+        return ws
+
+    # ---- products ---------------------------------------------------------------------------------------------------
+    def matmul(self, val, B):
+        """C (rows x n) = A(val) @ B (cols x n), differentiable in val and B."""
+        self._check_val(val)
+        self._check_dense(B, self.cols, "B", 2)
+        return _Matmul.apply(val, B, self)
+
+    def matvec(self, val, x):
+        """y (rows) = A(val) @ x (cols), differentiable in val and x."""
+        self._check_val(val)
+        self._check_dense(x, self.cols, "x", 1)
+        return _Matvec.apply(val, x, self)
+
+    # ---- the pieces the Functions call --------------------------------------------------------------------------------
+    def _forward_mm(self, val, B):
+        n = int(B.shape[1])
+        C_ = torch.empty(self.rows, n, dtype=torch.float64, device=self.device)
+        if n == 0 or self.rows == 0:
+            return C_
+        plan = self.spmm_plan if n == self.n else None
+        ws = self._workspace("spmm", spmm_workspace_bytes(self.rows, self.cols, self.nnz, n))
+        spmm_tensor((self.rows, self.cols, self.rowptr, self.colidx, val), B, C_, 1.0, 0.0, workspace=ws, plan=plan)
+        return C_
+
+    def _forward_mv(self, val, x):
+        y = torch.empty(self.rows, dtype=torch.float64, device=self.device)
+        if self.rows == 0:
+            return y
+        if self.nnz == 0 or self.cols == 0:
+            return y.zero_()
+        if self.spmv_plan is None:
+            self.spmv_plan = SpmvPlan(self.rows, self.cols, self.rowptr, self.colidx)
+        self.spmv_plan(val, x, 1.0, 0.0, y)
+        return y
+
+    def _grad_val(self, dC, B):
+        """dval[e] = <dC[row(e), :], B[col(e), :]>"""
+        out = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        k = int(dC.shape[1])
+        need = sddmm_workspace_bytes(self.rows, self.cols, self.nnz, k, _layout(dC, self.rows, k, "dC")[0],
+                                     _layout(B, self.cols, k, "B")[0])
+        sddmm_tensor((self.rows, self.cols, self.rowptr, self.colidx), dC, B, out, 1.0, 0.0,
+                     workspace=self._workspace("sddmm", need) if need else None)
+        return out
+
+    def _transpose(self, val):
+        """A^T with the values of `val`: the plan keeps its own copy, so it is refreshed on every use"""
+        if self.transpose_plan is None:
+            self.transpose_plan = TransposePlan(self.rows, self.cols, self.rowptr, self.colidx, val, n=self.n, split=self.split)
+        else:
+            self.transpose_plan.update_values(val)
+        return self.transpose_plan
+
+    def _grad_dense_mm(self, val, dC):
+        n = int(dC.shape[1])
+        dB = torch.empty(self.cols, n, dtype=torch.float64, device=self.device)
+        if n == 0 or self.cols == 0:
+            return dB
+        tp = self._transpose(val)
+        ws = self._workspace("spmm_t", spmm_workspace_bytes(self.cols, self.rows, self.nnz, n))
+        tp.spmm_tensor(dC, dB, 1.0, 0.0, workspace=ws)
+        return dB
+
+    def _grad_dense_mv(self, val, dy):
+        dx = torch.empty(self.cols, dtype=torch.float64, device=self.device)
+        if self.cols == 0:
+            return dx
+        self._transpose(val).spmv(dy, 1.0, 0.0, dx)
+        return dx
+
+    def destroy(self):
+        for p in (self.spmm_plan, self.spmv_plan, self.transpose_plan):
+            if p is not None:
+                p.destroy()
+        self.spmm_plan = self.spmv_plan = self.transpose_plan = None
+        self._ws.clear()
+
+
+def _laid_out(g):
+    """An incoming gradient as a tensor the kernels can read: an expanded one (C.sum().backward() delivers strides
+    (0, 0)) or any other view that is neither (ld, 1) nor (1, ld) is made contiguous."""
+    if g.dim() == 1:
+        return g if g.numel() <= 1 or g.stride(0) == 1 else g.contiguous()
+    s0, s1 = g.stride()
+    r, c = g.shape
+    if (s1 == 1 and s0 >= max(c, 1)) or (s0 == 1 and s1 >= max(r, 1)):
+        return g
+    return g.contiguous()
+
+
+class _Matmul(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val, B, op):
+        ctx.op = op
+        ctx.save_for_backward(val, B)
+        return op._forward_mm(val.detach(), B.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dC):
+        val, B = ctx.saved_tensors
+        op = ctx.op
+        dC = _laid_out(dC)
+        dval = op._grad_val(dC, B) if ctx.needs_input_grad[0] else None
+        dB = op._grad_dense_mm(val, dC) if ctx.needs_input_grad[1] else None
+        return dval, dB, None
+
+
+class _Matvec(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val, x, op):
+        ctx.op = op
+        ctx.save_for_backward(val, x)
+        return op._forward_mv(val.detach(), x.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        val, x = ctx.saved_tensors
+        op = ctx.op
+        dy = _laid_out(dy)
+        dval = op._grad_val(dy.view(-1, 1), x.view(-1, 1)) if ctx.needs_input_grad[0] else None
+        dx = op._grad_dense_mv(val, dy) if ctx.needs_input_grad[1] else None
+        return dval, dx, None
