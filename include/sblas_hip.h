@@ -445,6 +445,44 @@ int sblas_hip_sddmm_csr_f64_i32(int dev, void *stream, int64_t rows, int64_t col
                                 int64_t k, double alpha, double beta, double *out,
                                 void *workspace, size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------
+ * Row-wise softmax on a CSR pattern (edge softmax) and its backward.  For every row, over its stored entries e in
+ * stored order:
+ *     forward    t[e] = scale * x[e],  m = max t,  s = sum exp(t[e] - m),  out[e] = exp(t[e] - m) / s
+ *     backward   d = sum p[e] * dp[e],  dx[e] = (scale * p[e]) * (dp[e] - d)        (p: the forward's output)
+ *   - only the pattern's rowptr is read; colidx is not an argument.  Unsorted rows and duplicate entries are ordinary
+ *     entries.  An empty row costs nothing and writes nothing.  out may be x; dx may be dp.
+ *   - rowptr is relative to the value pointers passed: a row-aligned block of a larger matrix (rows [r0, r1), row
+ *     pointers re-based to start at 0, the value pointers advanced to the block's first entry) gives the bits of the
+ *     whole call.  A block of sblas_partition_nnz is NOT a valid input when it cuts a row (it may): the softmax of a
+ *     piece of a row is not a piece of the row's softmax.
+ *   - workspace: sblas_hip_csr_softmax_workspace(rows, nnz) bytes, 16-byte aligned; it depends on rows and nnz alone and
+ *     is 0 when no row can exceed 4096 entries (nnz <= 4096).  It holds per-call partial results of rows longer than
+ *     that, nothing that outlives the call; forward and backward may share it.
+ *   - nnz == 0 launches nothing.  A missing pointer, a negative size, entries with rows == 0: SBLAS_E_INVALID; a missing
+ *     or short workspace: SBLAS_E_WORKSPACE (misaligned: SBLAS_E_INVALID); all before anything touches the device.
+ *   - stream-ordered, allocates nothing, never synchronises, graph-capturable.  SBLAS_VALIDATE=1 first checks that
+ *     rowptr starts at 0, never descends and ends at nnz (synchronises); a bad one is SBLAS_E_INVALID, nothing written.
+ *   - IEEE classes, those of torch.softmax on each row: a NaN anywhere in a row makes the whole row NaN (the max
+ *     propagates NaN); -Inf entries get +0 when the row has a finite entry; a row whose max is +Inf is NaN, so is a row
+ *     of -Inf only; scale == 0 is no shortcut (0 * Inf reaches the row); exp underflowing to subnormal or 0 is ordinary.
+ *   - summation order: a function of the row's length L alone.  The bits of out[e] depend only on the row's values in
+ *     stored order, on L and on scale -- not on which row it is, where its entries sit in the value array, the
+ *     neighbouring rows, workgroup boundaries, the run, or which kernel took the row.  No floating-point atomics.  With
+ *     the row's entries numbered 0 .. L - 1: leaf i is exp(t[i] - m) (backward: fma(p[i], dp[i], +0)); a cell is the 64
+ *     leaves from a multiple of 64, absent ones +0, folded v += v[l ^ 1], v += v[l ^ 2], v += v[l ^ 4], v += v[l ^ 8],
+ *     v += v[l ^ 16], v += v[l ^ 32]; a supercell is 64 cells from a multiple of 64, absent ones +0, their sums folded
+ *     the same way; the row sum is +0 plus the supercell sums, left to right.  scale * x, t - m, the division,
+ *     scale * p, dp - d and the last product are each rounded once (nothing is contracted into an fma).
+ * fp64 values and int32 row pointers only.
+ * ------------------------------------------------------------------------------------- */
+size_t sblas_hip_csr_softmax_workspace(int64_t rows, int64_t nnz);
+int sblas_hip_csr_softmax_f64_i32(int dev, void *stream, int64_t rows, int64_t nnz, const int32_t *rowptr,
+                                  const double *x, double scale, double *out, void *workspace, size_t workspace_bytes);
+int sblas_hip_csr_softmax_backward_f64_i32(int dev, void *stream, int64_t rows, int64_t nnz, const int32_t *rowptr,
+                                           const double *p, const double *dp, double scale, double *dx,
+                                           void *workspace, size_t workspace_bytes);
+
 /* sblas_partition_nnz (below) for 64-bit row pointers */
 int64_t sblas_partition_nnz_i64(const int64_t *rowptr, int64_t rows, int64_t nnz, int n_gpu, int i_gpu,
                                 int64_t *start_row, int64_t *stop_row, int64_t *nnz_i, int64_t *first_nnz,

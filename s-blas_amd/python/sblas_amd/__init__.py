@@ -40,6 +40,7 @@ EXPORTS = [
     "sblas_hip_coo_to_csr_workspace", "sblas_hip_coo_to_csr_f64_i32", "sblas_hip_coo_plan_create", "sblas_hip_coo_plan_info",
     "sblas_hip_coo_plan_csr", "sblas_hip_coo_plan_assemble", "sblas_hip_coo_plan_destroy",
     "sblas_hip_sddmm_csr_workspace", "sblas_hip_sddmm_csr_f64_i32",
+    "sblas_hip_csr_softmax_workspace", "sblas_hip_csr_softmax_f64_i32", "sblas_hip_csr_softmax_backward_f64_i32",
 ]
 
 
@@ -201,6 +202,12 @@ def lib():
     L.sblas_hip_sddmm_csr_f64_i32.restype = C.c_int
     L.sblas_hip_sddmm_csr_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, C.c_int, vp, i64, C.c_int, i64, f64, f64,
                                               vp, vp, sz]
+    L.sblas_hip_csr_softmax_workspace.restype = sz
+    L.sblas_hip_csr_softmax_workspace.argtypes = [i64, i64]
+    L.sblas_hip_csr_softmax_f64_i32.restype = C.c_int
+    L.sblas_hip_csr_softmax_f64_i32.argtypes = [C.c_int, vp, i64, i64, vp, vp, f64, vp, vp, sz]
+    L.sblas_hip_csr_softmax_backward_f64_i32.restype = C.c_int
+    L.sblas_hip_csr_softmax_backward_f64_i32.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, vp, vp, sz]
     _lib = L
     return L
 
@@ -1179,3 +1186,75 @@ def sddmm_tensor(A, X, Y, out, alpha=1.0, beta=0.0, workspace=None, stream=None)
     _sddmm_call(rows, cols, nnz, _dev_ptr(rowptr, torch.int32, "rowptr"), _dev_ptr(colidx, torch.int32, "colidx") if nnz else None,
                 px if k and nnz else None, ldx, order_x, py if k and nnz else None, ldy, order_y, k, alpha, beta,
                 pout if nnz else None, workspace, stream)
+
+
+# ------------------------------------------------------------------------------------------
+# Row-wise softmax on a CSR pattern (sblas_hip_csr_softmax_f64_i32 and its backward)
+# ------------------------------------------------------------------------------------------
+def csr_softmax_workspace_bytes(rows, nnz):
+    """Bytes of workspace of a softmax call or its backward: a function of rows and nnz alone, 0 while no row can be
+    longer than 4096 entries."""
+    return int(lib().sblas_hip_csr_softmax_workspace(rows, nnz))
+
+
+def _softmax_args(rowptr, tensors, workspace):
+    """(rows, nnz, row pointer, value pointers, workspace pointer, workspace bytes, workspace) of a softmax call on 1-D
+    float64 GPU tensors of equal length; the checks come before anything touches the device"""
+    import torch
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise SblasError("rowptr must be a 1-D tensor of rows + 1 entries")
+    if rowptr.dtype != torch.int32:
+        raise SblasError("csr_softmax handles float64 values and int32 row pointers only")
+    rows = int(rowptr.numel()) - 1
+    for what, t in tensors:                          # dtypes and shapes first: they are wrong on any device
+        if not isinstance(t, torch.Tensor):
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+        if t.dtype != torch.float64:
+            raise SblasError("%s must be float64, got %s" % (what, t.dtype))
+        if t.dim() != 1 or t.numel() != tensors[0][1].numel():
+            raise SblasError("%s must hold one value per stored entry (%d), got shape %s" % (what, tensors[0][1].numel(),
+                                                                                            tuple(t.shape)))
+    nnz = int(tensors[0][1].numel())
+    for what, t in tensors:
+        if not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+    prow = _dev_ptr(rowptr, torch.int32, "rowptr")
+    ptrs = [_dev_ptr(t, torch.float64, what) if nnz else None for what, t in tensors]
+    need = csr_softmax_workspace_bytes(rows, nnz)
+    if workspace is None and need:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=tensors[0][1].device)
+    if workspace is not None and not workspace.is_contiguous():
+        raise SblasError("workspace must be contiguous")
+    wptr = workspace.data_ptr() if workspace is not None and workspace.numel() else None
+    wbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    return rows, nnz, prow, ptrs, wptr, wbytes, workspace
+
+
+def csr_softmax(rowptr, x, out=None, scale=1.0, workspace=None, stream=None):
+    """out[e] = exp(scale * x[e] - m) / s over the stored entries of each row of the pattern `rowptr` (int32, rows + 1
+    entries, relative to x).  x: nnz float64 values on the GPU; out: the same (None: a new tensor; x itself: in place).
+    Precondition: x holds exactly rowptr[-1] values.  nnz is taken from x, and this call has no colidx to check it
+    against (sddmm_tensor and CsrOperator do): with a shorter x the kernels read and write past its end.  SBLAS_VALIDATE=1
+    refuses a rowptr that is not monotone or does not end at nnz, at the price of a synchronisation.
+    workspace: None (allocated here when rows may exceed 4096 entries) or a device tensor of at least
+    csr_softmax_workspace_bytes(rows, nnz) bytes.  Returns out."""
+    import torch
+    if out is None and isinstance(x, torch.Tensor):
+        out = torch.empty_like(x)
+    rows, nnz, prow, (px, pout), wptr, wbytes, _keep = _softmax_args(rowptr, [("x", x), ("out", out)], workspace)
+    check(lib().sblas_hip_csr_softmax_f64_i32(-1, _stream(stream), rows, nnz, prow, px, float(scale), pout, wptr, wbytes),
+          "sblas_hip_csr_softmax_f64_i32")
+    return out
+
+
+def csr_softmax_backward(rowptr, p, dp, dx=None, scale=1.0, workspace=None, stream=None):
+    """dx[e] = scale * p[e] * (dp[e] - sum over the row of p * dp): the gradient of csr_softmax with respect to x, from
+    its output p and the gradient dp of that output.  dx: None (a new tensor), or a tensor of nnz entries (dp itself: in
+    place).  The precondition of csr_softmax holds here too: p, dp and dx hold exactly rowptr[-1] values.  Returns dx."""
+    import torch
+    if dx is None and isinstance(dp, torch.Tensor):
+        dx = torch.empty_like(dp)
+    rows, nnz, prow, (pp, pdp, pdx), wptr, wbytes, _keep = _softmax_args(rowptr, [("p", p), ("dp", dp), ("dx", dx)], workspace)
+    check(lib().sblas_hip_csr_softmax_backward_f64_i32(-1, _stream(stream), rows, nnz, prow, pp, pdp, float(scale), pdx, wptr,
+                                                       wbytes), "sblas_hip_csr_softmax_backward_f64_i32")
+    return dx

@@ -3,17 +3,21 @@
     op = CsrOperator(rows, cols, rowptr, colidx, n=64)
     C = op.matmul(val, B)         # val: nnz values (requires_grad or not), B: cols x n
     y = op.matvec(val, x)
+    S = op.sddmm(X, Y)            # nnz scores on A's pattern: S[e] = <X[row e], Y[col e]>, differentiable in X and Y
+    P = op.softmax(S, scale=s)    # softmax of scale * S over the stored entries of each row, differentiable in S
 
 Forward is the library's SpMM / SpMV.  Backward computes only the halves autograd asks for:
     dval = SDDMM(X = dC, Y = B) on A's pattern        (sddmm_tensor; k = 1 for matvec)
     dB   = A^T dC                                     (a TransposePlan the operator makes on the first backward that needs
                                                        it and refreshes with the values of that forward)
+sddmm is the same pair read the other way: dX = A(dout) Y through the SpMM path, dY = A(dout)^T X through the
+TransposePlan.  softmax keeps its output and runs the library's softmax backward on it.
 Backward of backward is not supported.  float64 values, int32 indices, GPU tensors only: there is no CPU path.
 torch is imported here, not by the package."""
 import torch
 
-from . import (SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor,
-               spmm_workspace_bytes)
+from . import (SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, csr_softmax, csr_softmax_backward,
+               csr_softmax_workspace_bytes, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
 
 
 class CsrOperator:
@@ -78,6 +82,20 @@ class CsrOperator:
         self._check_dense(x, self.cols, "x", 1)
         return _Matvec.apply(val, x, self)
 
+    def sddmm(self, X, Y):
+        """out (nnz) with out[e] = <X[row(e), :], Y[col(e), :]> on A's pattern; X rows x k, Y cols x k, differentiable in
+        both."""
+        self._check_dense(X, self.rows, "X", 2)
+        self._check_dense(Y, self.cols, "Y", 2)
+        if X.shape[1] != Y.shape[1]:
+            raise SblasError("X and Y must have the same number of columns, got %d and %d" % (X.shape[1], Y.shape[1]))
+        return _Sddmm.apply(X, Y, self)
+
+    def softmax(self, val, scale=1.0):
+        """P (nnz) = softmax of scale * val over the stored entries of each row of A, differentiable in val."""
+        self._check_val(val)
+        return _Softmax.apply(val, self, float(scale))
+
     # ---- the pieces the Functions call --------------------------------------------------------------------------------
     def _forward_mm(self, val, B):
         n = int(B.shape[1])
@@ -135,6 +153,18 @@ class CsrOperator:
         self._transpose(val).spmv(dy, 1.0, 0.0, dx)
         return dx
 
+    def _softmax_workspace(self):
+        need = csr_softmax_workspace_bytes(self.rows, self.nnz)
+        return self._workspace("softmax", need) if need else None
+
+    def _forward_softmax(self, val, scale):
+        out = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        return csr_softmax(self.rowptr, val.contiguous(), out, scale, workspace=self._softmax_workspace())
+
+    def _grad_softmax(self, p, dp, scale):
+        dx = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        return csr_softmax_backward(self.rowptr, p, dp, dx, scale, workspace=self._softmax_workspace())
+
     def destroy(self):
         for p in (self.spmm_plan, self.spmv_plan, self.transpose_plan):
             if p is not None:
@@ -189,3 +219,36 @@ class _Matvec(torch.autograd.Function):
         dval = op._grad_val(dy.view(-1, 1), x.view(-1, 1)) if ctx.needs_input_grad[0] else None
         dx = op._grad_dense_mv(val, dy) if ctx.needs_input_grad[1] else None
         return dval, dx, None
+
+
+class _Sddmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, Y, op):
+        ctx.op = op
+        ctx.save_for_backward(X, Y)
+        return op._grad_val(X.detach(), Y.detach())      # the SDDMM itself: <X[row], Y[col]> per stored entry
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        X, Y = ctx.saved_tensors
+        op = ctx.op
+        dout = _laid_out(dout)
+        dX = op._forward_mm(dout, Y) if ctx.needs_input_grad[0] else None        # A(dout) Y
+        dY = op._grad_dense_mm(dout, X) if ctx.needs_input_grad[1] else None     # A(dout)^T X
+        return dX, dY, None
+
+
+class _Softmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val, op, scale):
+        ctx.op, ctx.scale = op, scale
+        p = op._forward_softmax(val.detach(), scale)
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dp):
+        p, = ctx.saved_tensors
+        return ctx.op._grad_softmax(p, _laid_out(dp), ctx.scale), None, None
