@@ -483,6 +483,52 @@ int sblas_hip_csr_softmax_backward_f64_i32(int dev, void *stream, int64_t rows, 
                                            const double *p, const double *dp, double scale, double *dx,
                                            void *workspace, size_t workspace_bytes);
 
+/* ---------------------------------------------------------------------------------------
+ * Fused attention on a CSR pattern and its backward.  For every row i, over its stored entries e in stored order, with
+ * c(e) = colidx[e]:
+ *     forward    s[e] = <Q[i, :], K[c(e), :]> (d elements),  t = scale * s,  m = max t,  z = sum exp(t - m),
+ *                p[e] = exp(t[e] - m) / z,  O[i, :] = sum_e p[e] V[c(e), :] (dv elements),  row_max[i] = m, row_sum[i] = z
+ *     backward   t, p again from Q, K, row_max, row_sum;  dp[e] = <dO[i, :], V[c(e), :]>,  D = sum_e p[e] dp[e],
+ *                dS[e] = (scale * p[e]) * (dp[e] - D),  dQ[i, :] = sum_e dS[e] K[c(e), :];  P and dS on request
+ *   - Q rows x d, K cols x d, V cols x dv, O / dO rows x dv, dQ rows x d: row-major, leading dimension >= width, any
+ *     alignment; elements beyond the width in a row are never read.  1 <= d, dv <= 128.  Anything else: SBLAS_E_INVALID.
+ *   - the forward writes no nnz-sized array.  row_max / row_sum (rows doubles each): both or neither; NULL for inference.
+ *     The backward writes dQ, P (nnz) and dS (nnz), each only when its pointer is not NULL, and does no work for what is
+ *     not asked (P alone forms no dp).  dK = A(dS)^T Q and dV = A(P)^T dO are the caller's transposed products.
+ *   - rows of every length, no plan, no host look at the structure.  workspace:
+ *     sblas_hip_csr_attention_workspace(rows, nnz, d, dv) bytes, 16-byte aligned, 0 when nnz <= 4096; it holds the
+ *     per-supercell figures and partial rows of rows longer than 4096 entries (about nnz / 4096 rows of max(d, dv)),
+ *     nothing that outlives the call; forward and backward may share it.
+ *   - an empty row: O[i, :] = +0, row_max = -Inf, row_sum = +0, dQ[i, :] = +0; nnz == 0 still writes those rows.
+ *   - argument checks come before anything touches the device (SBLAS_E_INVALID; SBLAS_E_WORKSPACE for a missing or short
+ *     workspace); stream-ordered, allocates nothing, never synchronises, graph-capturable.  SBLAS_VALIDATE=1 checks
+ *     rowptr and colidx first (synchronises).
+ *   - bits: P and dS are those of sblas_hip_csr_softmax_f64_i32 on sblas_hip_sddmm_csr_f64_i32's scores (alpha 1, beta 0)
+ *     and of the softmax backward on the SDDMM of dO and V.  O[i, :] and dQ[i, :] depend on Q[i, :] (dO[i, :]), the rows
+ *     of K and V the row's entries name in stored order, the row's length, d, dv and scale only -- not on the row's
+ *     index or place, its neighbours, leading dimensions, alignment or the kernel that took it.  With W the power of two
+ *     in [4, 64] covering min(width, 64) output columns and NG = 64 / W: inside a run (a row of up to 4096 entries, or
+ *     4096 entries of a longer row counted from its start) entry j goes to accumulator j % NG, which starts at +0 and
+ *     takes acc = fma(p[j], V[c(j), c], acc) in ascending j; the NG accumulators fold acc += acc[g ^ 1], acc[g ^ 2], ...;
+ *     a longer row is +0 plus its runs' rows, left to right.  No floating-point atomics.
+ *   - IEEE classes follow from those expressions: p == 0 and scale == 0 are no shortcut, a NaN row of P gives a NaN row
+ *     of O.
+ * fp64 values and int32 indices only.
+ * ------------------------------------------------------------------------------------- */
+size_t sblas_hip_csr_attention_workspace(int64_t rows, int64_t nnz, int64_t d, int64_t dv);
+int sblas_hip_csr_attention_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                    const int32_t *rowptr, const int32_t *colidx,
+                                    const double *Q, int64_t ldq, const double *K, int64_t ldk, const double *V, int64_t ldv,
+                                    int64_t d, int64_t dv, double scale, double *O, int64_t ldo,
+                                    double *row_max, double *row_sum, void *workspace, size_t workspace_bytes);
+int sblas_hip_csr_attention_backward_f64_i32(int dev, void *stream, int64_t rows, int64_t cols, int64_t nnz,
+                                             const int32_t *rowptr, const int32_t *colidx,
+                                             const double *Q, int64_t ldq, const double *K, int64_t ldk,
+                                             const double *V, int64_t ldv, int64_t d, int64_t dv, double scale,
+                                             const double *dO, int64_t lddo, const double *row_max, const double *row_sum,
+                                             double *dQ, int64_t lddq, double *P, double *dS,
+                                             void *workspace, size_t workspace_bytes);
+
 /* sblas_partition_nnz (below) for 64-bit row pointers */
 int64_t sblas_partition_nnz_i64(const int64_t *rowptr, int64_t rows, int64_t nnz, int n_gpu, int i_gpu,
                                 int64_t *start_row, int64_t *stop_row, int64_t *nnz_i, int64_t *first_nnz,

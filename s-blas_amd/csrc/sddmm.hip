@@ -26,64 +26,13 @@
 #include "../../include/sblas_hip.h"
 #include "capi_util.h"
 #include "kernels.h"
+#include "rowwise.h" // group_sum, load_piece, block_row_of
 
 namespace sblas {
 
 constexpr int SDDMM_THREADS = 256;
 constexpr int SDDMM_CHUNK = 1024; // nonzeros per workgroup: four per thread in the row-index scan
-constexpr int SDDMM_SLICE = 128;  // elements of k per launch
-
-// Lanes per nonzero for a slice of k elements, settled by measurement: a lane takes up to four elements
-// of each row for k <= 16 and up to eight beyond, i.e. up to four 16-byte loads per row in flight; fewer lanes with more
-// pieces each, or more lanes with one piece each, ran up to 1.4 x slower.
-static int sddmm_group(int64_t k) { return k <= 4 ? 1 : k <= 8 ? 2 : k <= 32 ? 4 : k <= 64 ? 8 : 16; }
-
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// The butterfly over the G lanes of a group (G lanes aligned inside a DPP row of 16).  Once the lanes of a quad hold one
-// sum, the half-row mirror hands every lane the sum of the other quad of its eight (what l ^ 4 would), and the row mirror
-// after it the sum of the other eight.
-template <int G> __device__ __forceinline__ double group_sum(double s)
-{
-    if constexpr (G >= 2) s += dpp_f64<0xB1>(s);  // quad_perm:[1,0,3,2]
-    if constexpr (G >= 4) s += dpp_f64<0x4E>(s);  // quad_perm:[2,3,0,1]
-    if constexpr (G >= 8) s += dpp_f64<0x141>(s); // row_half_mirror
-    if constexpr (G >= 16) s += dpp_f64<0x140>(s); // row_mirror
-    return s;
-}
-
-// elements j, j + 1 of a row, those below k only: what is masked off is never loaded (it may lie outside the operand)
-template <bool VEC, bool FULL> __device__ __forceinline__ double2 load_piece(const double *__restrict__ row, int j, int k)
-{
-    double2 v = make_double2(0.0, 0.0);
-    if (FULL || j + 1 < k) {
-        if constexpr (VEC) v = *reinterpret_cast<const double2 *>(row + j);
-        else v = make_double2(row[j], row[j + 1]);
-    } else if (j < k) {
-        v.x = row[j];
-    }
-    return v;
-}
-
-// largest r in [0, rows) with rowptr[r] <= e, for 0 <= e < rowptr[rows]; all 256 threads probe, 8 bits of the answer a round
-__device__ __forceinline__ int block_row_of(const int *__restrict__ rowptr, int rows, int e)
-{
-    int64_t lo = 0, hi = rows; // rowptr[lo] <= e < rowptr[hi]
-    while (hi - lo > 1) {
-        const int64_t step = (hi - lo + SDDMM_THREADS - 1) / SDDMM_THREADS;
-        const int64_t p = lo + ((int64_t)threadIdx.x + 1) * step;
-        const int below = (p < hi && rowptr[p] <= e) ? 1 : 0;
-        const int64_t cnt = __syncthreads_count(below);
-        const int64_t nlo = lo + cnt * step, nhi = lo + (cnt + 1) * step;
-        lo = nlo;
-        if (nhi < hi) hi = nhi;
-    }
-    return (int)lo;
-}
+// SDDMM_SLICE (elements of k per launch) and sddmm_group (lanes per nonzero for a slice): rowwise.h
 
 // k <= SDDMM_SLICE: one slice.  The piece loop has at most PASSES rounds (k <= 2 * G * PASSES), unrolled.  FULL: k ==
 // 2 * G * PASSES, no load is masked (the masks cost a fifth of the time at k = 64).
@@ -102,8 +51,8 @@ __global__ __launch_bounds__(SDDMM_THREADS) void sddmm_kernel(int rows, int nnz,
     const int cnt = min(SDDMM_CHUNK, nnz - e0);
 
     // ---- one row index per nonzero of the run ----
-    const int r_lo = block_row_of(rowptr, rows, e0);
-    const int r_hi = block_row_of(rowptr, rows, e0 + cnt - 1);
+    const int r_lo = block_row_of<SDDMM_THREADS>(rowptr, rows, e0);
+    const int r_hi = block_row_of<SDDMM_THREADS>(rowptr, rows, e0 + cnt - 1);
     for (int i = tid; i < SDDMM_CHUNK; i += SDDMM_THREADS) rowof[i] = r_lo;
     __syncthreads();
     for (int64_t r = (int64_t)r_lo + 1 + tid; r <= r_hi; r += SDDMM_THREADS) {

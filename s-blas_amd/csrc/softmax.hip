@@ -32,6 +32,7 @@
 #include "../../include/sblas_hip.h"
 #include "capi_util.h"
 #include "kernels.h"
+#include "rowwise.h" // fold_sum, fold_max, nmax, fwd_out, bwd_out, block_row_of, supercell_slot
 
 #pragma clang fp contract(off)
 
@@ -40,57 +41,14 @@ namespace {
 
 constexpr int SM_THREADS = 256;
 constexpr int SM_WAVES = SM_THREADS / 64;
-constexpr int SM_CELL = 64;     // leaves per cell: one wave-wide butterfly
-constexpr int SM_SUPER = 4096;  // leaves per supercell: 64 cells; the longest row the rows kernel takes
+constexpr int SM_CELL = ROW_CELL;   // leaves per cell: one wave-wide butterfly
+constexpr int SM_SUPER = ROW_SUPER; // leaves per supercell: 64 cells; the longest row the rows kernel takes
 constexpr int SM_REG_CELLS = 8; // cells of a row a wave keeps in registers
 constexpr int SM_GROUP = 8;     // lanes per row when the eight rows of a wave hold at most 8 entries each
 
-template <int CTRL> __device__ __forceinline__ double sm_dpp(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// the value the lane LEVEL places away holds (l ^ LEVEL), for lanes that already agree inside their group of LEVEL: the
-// quad permutes, then the half-row and row mirrors (sddmm.hip's group_sum), then lane permutes across the DPP rows
-template <int LEVEL> __device__ __forceinline__ double sm_partner(double v)
-{
-    if constexpr (LEVEL == 1) return sm_dpp<0xB1>(v);       // quad_perm:[1,0,3,2]
-    else if constexpr (LEVEL == 2) return sm_dpp<0x4E>(v);  // quad_perm:[2,3,0,1]
-    else if constexpr (LEVEL == 4) return sm_dpp<0x141>(v); // row_half_mirror
-    else if constexpr (LEVEL == 8) return sm_dpp<0x140>(v); // row_mirror
-    else return __shfl_xor(v, LEVEL, 64);
-}
-// NaN wins; otherwise the larger (which zero of +0 / -0 comes back does not matter: exp(+-0) = 1)
-__device__ __forceinline__ double nmax(double a, double b) { return (a > b || a != a) ? a : b; }
-
-template <int LANES> __device__ __forceinline__ double fold_sum(double v)
-{
-    if constexpr (LANES >= 2) v += sm_partner<1>(v);
-    if constexpr (LANES >= 4) v += sm_partner<2>(v);
-    if constexpr (LANES >= 8) v += sm_partner<4>(v);
-    if constexpr (LANES >= 16) v += sm_partner<8>(v);
-    if constexpr (LANES >= 32) v += sm_partner<16>(v);
-    if constexpr (LANES >= 64) v += sm_partner<32>(v);
-    return v;
-}
-template <int LANES> __device__ __forceinline__ double fold_max(double v)
-{
-    if constexpr (LANES >= 2) v = nmax(v, sm_partner<1>(v));
-    if constexpr (LANES >= 4) v = nmax(v, sm_partner<2>(v));
-    if constexpr (LANES >= 8) v = nmax(v, sm_partner<4>(v));
-    if constexpr (LANES >= 16) v = nmax(v, sm_partner<8>(v));
-    if constexpr (LANES >= 32) v = nmax(v, sm_partner<16>(v));
-    if constexpr (LANES >= 64) v = nmax(v, sm_partner<32>(v));
-    return v;
-}
-
-constexpr double NEG_INF = -__builtin_huge_val();
-
 // ---- the leaves and the outputs, the same expressions on every path --------------------------------------------------
 // forward: a = x; backward: a = p, b = dp
-__device__ __forceinline__ double fwd_out(double t, double m, double s) { return exp(t - m) / s; }
-__device__ __forceinline__ double bwd_out(double p, double dp, double d, double scale) { return (scale * p) * (dp - d); }
+// (fwd_out, bwd_out: rowwise.h)
 
 // One row of at most 64 * NC entries, kept in registers by one wave.  a, b, out are already advanced to the row.
 template <bool BWD, int NC>
@@ -214,24 +172,6 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_rows_kernel(int rows, cons
 }
 
 // ---- rows longer than SM_SUPER ----------------------------------------------------------------------------------------
-// largest r in [0, rows) with rowptr[r] <= e, for 0 <= e < rowptr[rows]: the row that holds entry e (sddmm.hip)
-__device__ __forceinline__ int sm_row_of(const int *__restrict__ rowptr, int rows, int e)
-{
-    int64_t lo = 0, hi = rows;
-    while (hi - lo > 1) {
-        const int64_t step = (hi - lo + SM_THREADS - 1) / SM_THREADS;
-        const int64_t p = lo + ((int64_t)threadIdx.x + 1) * step;
-        const int below = (p < hi && rowptr[p] <= e) ? 1 : 0;
-        const int64_t cnt = __syncthreads_count(below);
-        const int64_t nlo = lo + cnt * step, nhi = lo + (cnt + 1) * step;
-        lo = nlo;
-        if (nhi < hi) hi = nhi;
-    }
-    return (int)lo;
-}
-// the workspace slot of the supercell of a row (first entry row_beg) that starts at entry p
-__device__ __forceinline__ int64_t sm_slot(int64_t row_beg, int64_t p) { return 2 * (p / SM_SUPER) + (p == row_beg ? 1 : 0); }
-
 enum { PH_MAX = 0, PH_SUM = 1, PH_OUT = 2, PH_DOT = 3, PH_DX = 4 };
 
 // PHASE: PH_MAX -> pmax[slot]; PH_SUM reads the row's pmax -> psum[slot]; PH_OUT reads both -> out.
@@ -246,7 +186,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_long_kernel(int rows, int 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t e_first = (int64_t)blockIdx.x * SM_SUPER;
     const int64_t e_last = e_first + SM_SUPER - 1 < nnz ? e_first + SM_SUPER - 1 : (int64_t)nnz - 1;
-    const int r_a = sm_row_of(rowptr, rows, (int)e_first), r_b = sm_row_of(rowptr, rows, (int)e_last);
+    const int r_a = block_row_of<SM_THREADS>(rowptr, rows, (int)e_first), r_b = block_row_of<SM_THREADS>(rowptr, rows, (int)e_last);
     for (int which = 0; which < 2; ++which) {
         if (which == 1 && r_b == r_a) break;
         const int r = which ? r_b : r_a;
@@ -257,7 +197,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_long_kernel(int rows, int 
         if (p > e_last || p >= row_beg + len) continue;
         const int cnt = (int)(row_beg + len - p < SM_SUPER ? row_beg + len - p : SM_SUPER);
         const int ncell = (cnt + SM_CELL - 1) / SM_CELL;
-        const int64_t slot = sm_slot(row_beg, p);
+        const int64_t slot = supercell_slot(row_beg, p);
         const int64_t nsuper = (len + SM_SUPER - 1) / SM_SUPER;
         const double *ap = a + p;
         const double *bp = b + p; // backward only
@@ -276,7 +216,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_long_kernel(int rows, int 
         // the row's max, from the maxima of its supercells
         double m = NEG_INF;
         if constexpr (PHASE == PH_SUM || PHASE == PH_OUT) {
-            for (int64_t q = tid; q < nsuper; q += SM_THREADS) m = nmax(m, pmax[sm_slot(row_beg, row_beg + q * SM_SUPER)]);
+            for (int64_t q = tid; q < nsuper; q += SM_THREADS) m = nmax(m, pmax[supercell_slot(row_beg, row_beg + q * SM_SUPER)]);
             m = fold_max<64>(m);
             __syncthreads();
             if (lane == 0) wave_part[wave] = m;
@@ -303,7 +243,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_long_kernel(int rows, int 
         }
         if constexpr (PHASE == PH_OUT || PHASE == PH_DX) {
             double s = 0.0; // the supercell sums, left to right
-            for (int64_t q = 0; q < nsuper; ++q) s += psum[sm_slot(row_beg, row_beg + q * SM_SUPER)];
+            for (int64_t q = 0; q < nsuper; ++q) s += psum[supercell_slot(row_beg, row_beg + q * SM_SUPER)];
             for (int i = tid; i < cnt; i += SM_THREADS)
                 op[i] = PHASE == PH_DX ? bwd_out(ap[i], bp[i], s, scale) : fwd_out(scale * ap[i], m, s);
         }

@@ -41,6 +41,7 @@ EXPORTS = [
     "sblas_hip_coo_plan_csr", "sblas_hip_coo_plan_assemble", "sblas_hip_coo_plan_destroy",
     "sblas_hip_sddmm_csr_workspace", "sblas_hip_sddmm_csr_f64_i32",
     "sblas_hip_csr_softmax_workspace", "sblas_hip_csr_softmax_f64_i32", "sblas_hip_csr_softmax_backward_f64_i32",
+    "sblas_hip_csr_attention_workspace", "sblas_hip_csr_attention_f64_i32", "sblas_hip_csr_attention_backward_f64_i32",
 ]
 
 
@@ -208,6 +209,14 @@ def lib():
     L.sblas_hip_csr_softmax_f64_i32.argtypes = [C.c_int, vp, i64, i64, vp, vp, f64, vp, vp, sz]
     L.sblas_hip_csr_softmax_backward_f64_i32.restype = C.c_int
     L.sblas_hip_csr_softmax_backward_f64_i32.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, vp, vp, sz]
+    L.sblas_hip_csr_attention_workspace.restype = sz
+    L.sblas_hip_csr_attention_workspace.argtypes = [i64, i64, i64, i64]
+    L.sblas_hip_csr_attention_f64_i32.restype = C.c_int
+    L.sblas_hip_csr_attention_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, f64,
+                                                  vp, i64, vp, vp, vp, sz]
+    L.sblas_hip_csr_attention_backward_f64_i32.restype = C.c_int
+    L.sblas_hip_csr_attention_backward_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64,
+                                                           f64, vp, i64, vp, vp, vp, i64, vp, vp, vp, sz]
     _lib = L
     return L
 
@@ -1258,3 +1267,131 @@ def csr_softmax_backward(rowptr, p, dp, dx=None, scale=1.0, workspace=None, stre
     check(lib().sblas_hip_csr_softmax_backward_f64_i32(-1, _stream(stream), rows, nnz, prow, pp, pdp, float(scale), pdx, wptr,
                                                        wbytes), "sblas_hip_csr_softmax_backward_f64_i32")
     return dx
+
+
+# ------------------------------------------------------------------------------------------
+# Fused attention on a CSR pattern (sblas_hip_csr_attention_f64_i32 and its backward)
+# ------------------------------------------------------------------------------------------
+ATTENTION_MAX_WIDTH = 128      # widest Q / K / V row the fused kernels take
+
+
+def csr_attention_workspace_bytes(rows, nnz, d, dv):
+    """Bytes of workspace of a fused attention call or its backward: a function of (rows, nnz, d, dv) alone, 0 while no
+    row can be longer than 4096 entries; about nnz / 4096 rows of max(d, dv) doubles otherwise, never nnz itself."""
+    return int(lib().sblas_hip_csr_attention_workspace(rows, nnz, d, dv))
+
+
+def _attention_dense(t, rows, width, what):
+    """leading dimension of a row-major 2-D float64 tensor of `rows` rows (and `width` columns when given)"""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+    if t.dtype != torch.float64:
+        raise SblasError("%s must be float64, got %s" % (what, t.dtype))
+    if t.dim() != 2 or t.shape[0] != rows or (width is not None and t.shape[1] != width):
+        raise SblasError("%s must be a %d x %s tensor, got shape %s" % (what, rows, "k" if width is None else width, tuple(t.shape)))
+    w = int(t.shape[1])
+    if not 1 <= w <= ATTENTION_MAX_WIDTH:
+        raise SblasError("%s has %d columns: the fused attention kernels take 1 .. %d" % (what, w, ATTENTION_MAX_WIDTH))
+    order, ld = _layout(t, rows, w, what)
+    if order != ROW_MAJOR and rows > 1 and w > 1:
+        raise SblasError("%s must be row-major (strides (ld, 1)) for the fused attention kernels, got strides %s" %
+                         (what, tuple(t.stride())))
+    return ld if order == ROW_MAJOR else w
+
+
+def _attention_args(A, Q, K, V, others, workspace):
+    """the checks csr_attention and csr_attention_backward share, shapes and dtypes before devices; `others`: (name,
+    tensor, rows, width) of the further dense operands.  Returns the sizes, pointers and leading dimensions."""
+    import torch
+    rows, cols, rowptr, colidx = A
+    if not isinstance(rowptr, torch.Tensor) or not isinstance(colidx, torch.Tensor):
+        raise SblasError("rowptr and colidx must be GPU tensors (no CPU path exists)")
+    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32:
+        raise SblasError("csr_attention handles float64 values and int32 indices only")
+    if rowptr.dim() != 1 or rowptr.numel() != rows + 1 or colidx.dim() != 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), rows))
+    ldq = _attention_dense(Q, rows, None, "Q")
+    d = int(Q.shape[1])
+    ldk = _attention_dense(K, cols, d, "K")
+    ldv = _attention_dense(V, cols, None, "V")
+    dv = int(V.shape[1])
+    lds = [_attention_dense(t, r, d if w == "d" else dv, what) for what, t, r, w in others]
+    for what, t in [("rowptr", rowptr), ("colidx", colidx), ("Q", Q), ("K", K), ("V", V)] + [(o[0], o[1]) for o in others]:
+        if not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+    nnz = int(colidx.numel())
+    need = csr_attention_workspace_bytes(rows, nnz, d, dv)
+    if workspace is None and need:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=Q.device)
+    if workspace is not None and not workspace.is_contiguous():
+        raise SblasError("workspace must be contiguous")
+    wptr = workspace.data_ptr() if workspace is not None and workspace.numel() else None
+    wbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    prow = _dev_ptr(rowptr, torch.int32, "rowptr")
+    pcol = _dev_ptr(colidx, torch.int32, "colidx") if nnz else None
+    return rows, cols, nnz, d, dv, prow, pcol, ldq, ldk, ldv, lds, wptr, wbytes, workspace
+
+
+def _row_vector(t, rows, what):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+    if t.dim() != 1 or t.numel() != rows:
+        raise SblasError("%s must hold one value per row (%d), got shape %s" % (what, rows, tuple(t.shape)))
+    return _dev_ptr(t, torch.float64, what)
+
+
+def csr_attention(A, Q, K, V, scale=1.0, out=None, row_max=None, row_sum=None, workspace=None, stream=None):
+    """O = softmax(scale * Q K^T restricted to A's pattern) V in one pass, with no nnz-sized array: A = (rows, cols, rowptr,
+    colidx) (int32, on the GPU), Q rows x d, K cols x d, V cols x dv, float64, row-major with any leading dimension
+    (column slices work as they are), 1 <= d, dv <= 128.  out: rows x dv, row-major (None: a new tensor).  row_max,
+    row_sum: both or neither, one float64 per row: the row's max of scale * s and its sum of exp(t - max), all the
+    backward needs.  An empty row gives a +0 row, -Inf and +0.  workspace: None (allocated here when a row may exceed 4096
+    entries) or a device tensor of at least csr_attention_workspace_bytes(rows, nnz, d, dv) bytes.  Returns out."""
+    import torch
+    rows = A[0]
+    if out is None and isinstance(Q, torch.Tensor) and isinstance(V, torch.Tensor) and V.dim() == 2:
+        out = torch.empty(rows, int(V.shape[1]), dtype=torch.float64, device=Q.device)
+    if (row_max is None) != (row_sum is None):
+        raise SblasError("row_max and row_sum come together: both or neither")
+    (rows, cols, nnz, d, dv, prow, pcol, ldq, ldk, ldv, (ldo,), wptr, wbytes,
+     _keep) = _attention_args(A, Q, K, V, [("out", out, rows, "dv")], workspace)
+    pmax = _row_vector(row_max, rows, "row_max") if row_max is not None else None
+    psum = _row_vector(row_sum, rows, "row_sum") if row_sum is not None else None
+    check(lib().sblas_hip_csr_attention_f64_i32(-1, _stream(stream), rows, cols, nnz, prow, pcol, _view_ptr(Q, "Q"), ldq,
+                                                _view_ptr(K, "K"), ldk, _view_ptr(V, "V"), ldv, d, dv, float(scale),
+                                                _view_ptr(out, "out"), ldo, pmax, psum, wptr, wbytes),
+          "sblas_hip_csr_attention_f64_i32")
+    return out
+
+
+def csr_attention_backward(A, Q, K, V, dO, row_max, row_sum, scale=1.0, dQ=None, P=None, dS=None, workspace=None, stream=None):
+    """The backward of csr_attention from its inputs, the gradient dO (rows x dv) of its output and the row_max / row_sum it
+    wrote.  Each of dQ (rows x d, row-major), P and dS (nnz float64 each) is written when given and costs nothing when
+    None: P alone forms no <dO, V>.  P[e] is the attention probability of entry e, dS[e] the gradient of the score
+    <Q[i], K[c(e)]>; the caller forms dV = A(P)^T dO and dK = A(dS)^T Q with a TransposePlan.  P and dS are, bit for bit,
+    csr_softmax(sddmm(Q, K), scale) and csr_softmax_backward(P, sddmm(dO, V), scale).  Returns (dQ, P, dS)."""
+    import torch
+    rows = A[0]
+    if isinstance(A[3], torch.Tensor):                   # shapes first: they are wrong on any device
+        for what, t in (("P", P), ("dS", dS)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != A[3].numel()):
+                raise SblasError("%s must hold one value per stored entry (%d)" % (what, A[3].numel()))
+    others = []
+    if dQ is not None or dS is not None:
+        others.append(("dO", dO, rows, "dv"))
+    if dQ is not None:
+        others.append(("dQ", dQ, rows, "d"))
+    (rows, cols, nnz, d, dv, prow, pcol, ldq, ldk, ldv, lds, wptr, wbytes,
+     _keep) = _attention_args(A, Q, K, V, others, workspace)
+    lddo = lds[0] if others else dv
+    lddq = lds[-1] if dQ is not None else d
+    pp = _dev_ptr(P, torch.float64, "P") if P is not None and nnz else None
+    pds = _dev_ptr(dS, torch.float64, "dS") if dS is not None and nnz else None
+    check(lib().sblas_hip_csr_attention_backward_f64_i32(
+        -1, _stream(stream), rows, cols, nnz, prow, pcol, _view_ptr(Q, "Q"), ldq, _view_ptr(K, "K"), ldk, _view_ptr(V, "V"), ldv,
+        d, dv, float(scale), _view_ptr(dO, "dO") if others else None, lddo, _row_vector(row_max, rows, "row_max"),
+        _row_vector(row_sum, rows, "row_sum"), _view_ptr(dQ, "dQ") if dQ is not None else None, lddq, pp, pds, wptr, wbytes),
+        "sblas_hip_csr_attention_backward_f64_i32")
+    return dQ, P, dS

@@ -5,18 +5,22 @@
     y = op.matvec(val, x)
     S = op.sddmm(X, Y)            # nnz scores on A's pattern: S[e] = <X[row e], Y[col e]>, differentiable in X and Y
     P = op.softmax(S, scale=s)    # softmax of scale * S over the stored entries of each row, differentiable in S
+    O = op.attention(Q, K, V, scale=s)   # op.matmul(op.softmax(op.sddmm(Q, K), s), V) in one kernel, nothing nnz-sized kept
 
 Forward is the library's SpMM / SpMV.  Backward computes only the halves autograd asks for:
     dval = SDDMM(X = dC, Y = B) on A's pattern        (sddmm_tensor; k = 1 for matvec)
     dB   = A^T dC                                     (a TransposePlan the operator makes on the first backward that needs
                                                        it and refreshes with the values of that forward)
 sddmm is the same pair read the other way: dX = A(dout) Y through the SpMM path, dY = A(dout)^T X through the
-TransposePlan.  softmax keeps its output and runs the library's softmax backward on it.
+TransposePlan.  softmax keeps its output and runs the library's softmax backward on it.  attention keeps Q, K, V and two
+doubles per row; its backward recomputes the probabilities, takes dQ from the fused kernel and forms dK = A(dS)^T Q and
+dV = A(P)^T dO through the TransposePlan, from P and dS that live only inside that backward.
 Backward of backward is not supported.  float64 values, int32 indices, GPU tensors only: there is no CPU path.
 torch is imported here, not by the package."""
 import torch
 
-from . import (SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, csr_softmax, csr_softmax_backward,
+from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, csr_attention,
+               csr_attention_backward, csr_attention_workspace_bytes, csr_softmax, csr_softmax_backward,
                csr_softmax_workspace_bytes, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
 
 
@@ -96,6 +100,34 @@ class CsrOperator:
         self._check_val(val)
         return _Softmax.apply(val, self, float(scale))
 
+    def attention(self, Q, K, V, scale=1.0):
+        """O (rows x dv) = softmax(scale * Q K^T on A's pattern) V: what op.matmul(op.softmax(op.sddmm(Q, K), scale), V)
+        computes, in one fused kernel that writes no nnz-sized array and keeps only Q, K, V and two doubles per row for
+        the backward (the composition holds 16 bytes per stored entry at the peak of its forward, S beside P, and keeps
+        8, P, until its backward).  Q rows x d, K cols x d, V cols x dv;
+        differentiable in all three, and the backward forms only the gradients autograd asks for.  The probabilities
+        and score gradients are the composition's bit for bit, hence dK and dV too; O and dQ are accumulated in the
+        fused kernels' own fixed order (include/sblas_hip.h, "Fused attention"), a function of the row alone.
+        Inputs outside the fused kernels' limits -- d or dv above 128 (or 0), or a column-major Q, K or V -- run the
+        composition itself, with its bits for O and dQ as well.
+        Speed (measured against the composition in the same run): the fused route is slower wherever no
+        row is long -- 1.6 to 3.8 x forward on the banded bench matrix, a Queen-like grid and banded rows of 5 at 16 and
+        64 columns -- because a wave walks one row at a time and waits on the gathers of K and V rows through L2, where
+        the composition's SDDMM and (LDS-tiled) SpMM keep far more loads in flight; it is faster (0.5 x at 64 columns,
+        0.03 x at 16) on a power law with a 10^6-entry row, which it spreads over many waves.  It is kept for the memory."""
+        self._check_dense(Q, self.rows, "Q", 2)
+        self._check_dense(K, self.cols, "K", 2)
+        self._check_dense(V, self.cols, "V", 2)
+        if Q.shape[1] != K.shape[1]:
+            raise SblasError("Q and K must have the same number of columns, got %d and %d" % (Q.shape[1], K.shape[1]))
+        d, dv = int(Q.shape[1]), int(V.shape[1])
+        fused = 1 <= d <= ATTENTION_MAX_WIDTH and 1 <= dv <= ATTENTION_MAX_WIDTH and all(
+            _layout(t, r, w, what)[0] == ROW_MAJOR for t, r, w, what in ((Q, self.rows, d, "Q"), (K, self.cols, d, "K"),
+                                                                        (V, self.cols, dv, "V")))
+        if not fused:
+            return self.matmul(self.softmax(self.sddmm(Q, K), scale), V)
+        return _Attention.apply(Q, K, V, self, float(scale))
+
     # ---- the pieces the Functions call --------------------------------------------------------------------------------
     def _forward_mm(self, val, B):
         n = int(B.shape[1])
@@ -164,6 +196,13 @@ class CsrOperator:
     def _grad_softmax(self, p, dp, scale):
         dx = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
         return csr_softmax_backward(self.rowptr, p, dp, dx, scale, workspace=self._softmax_workspace())
+
+    def _attention_workspace(self, d, dv):
+        need = csr_attention_workspace_bytes(self.rows, self.nnz, d, dv)
+        return self._workspace("attention", need) if need else None
+
+    def _pattern(self):
+        return self.rows, self.cols, self.rowptr, self.colidx
 
     def destroy(self):
         for p in (self.spmm_plan, self.spmv_plan, self.transpose_plan):
@@ -252,3 +291,37 @@ class _Softmax(torch.autograd.Function):
     def backward(ctx, dp):
         p, = ctx.saved_tensors
         return ctx.op._grad_softmax(p, _laid_out(dp), ctx.scale), None, None
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Q, K, V, op, scale):
+        ctx.op, ctx.scale = op, scale
+        Q, K, V = Q.detach(), K.detach(), V.detach()
+        d, dv = int(Q.shape[1]), int(V.shape[1])
+        O = torch.empty(op.rows, dv, dtype=torch.float64, device=op.device)
+        m = z = None
+        if any(ctx.needs_input_grad[:3]):                # inference keeps nothing
+            m = torch.empty(op.rows, dtype=torch.float64, device=op.device)
+            z = torch.empty(op.rows, dtype=torch.float64, device=op.device)
+            ctx.save_for_backward(Q, K, V, m, z)
+        csr_attention(op._pattern(), Q, K, V, scale, O, m, z, workspace=op._attention_workspace(d, dv))
+        return O
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dO):
+        Q, K, V, m, z = ctx.saved_tensors
+        op = ctx.op
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        dO = _laid_out(dO)
+        dO_rows = dO if _layout(dO, op.rows, int(dO.shape[1]), "dO")[0] == ROW_MAJOR else dO.contiguous()
+        d, dv = int(Q.shape[1]), int(V.shape[1])
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=op.device)
+        dQ = new(op.rows, d) if need_q else None
+        P = new(op.nnz) if need_v else None              # transient: nothing nnz-sized outlives this call
+        dS = new(op.nnz) if need_k else None
+        csr_attention_backward(op._pattern(), Q, K, V, dO_rows, m, z, ctx.scale, dQ, P, dS, workspace=op._attention_workspace(d, dv))
+        dK = op._grad_dense_mm(dS, Q) if need_k else None    # A(dS)^T Q
+        dV = op._grad_dense_mm(P, dO) if need_v else None    # A(P)^T dO
+        return dQ, dK, dV, None, None
