@@ -8,6 +8,9 @@
  * same information the replaced call received (plain pointers and sizes, no C++ or torch
  * types).  The header-template layer in s-blas_amd/include/ (sblas.h, matrix.h, spmm.h, spmv.h)
  * forwards to these functions; INTEGRATION.md shows the binding a reference maintainer adds.
+ * The sparse-times-sparse product (sblas_hip_spgemm_plan_*: C = A * B for two CSR matrices, symbolic once, numeric per
+ * set of values) has no counterpart in the reference; it follows the plan idiom of the transpose and COO plans below and
+ * takes over the COO contract's left-to-right sum word for word.
  *
  * Conventions
  *   - all array arguments of the *_hip_* compute functions are DEVICE pointers on device `dev`
@@ -404,6 +407,78 @@ int sblas_hip_coo_plan_csr(const void *plan, const int32_t **rowptr, const int32
                            const int32_t **runptr);
 int sblas_hip_coo_plan_assemble(const void *plan, void *stream, const double *coo_val, double *val_out);
 int sblas_hip_coo_plan_destroy(void *plan);
+
+/* ---------------------------------------------------------------------------------------
+ * SpGEMM:  C = A * B   A: m x k CSR, B: k x n CSR, C: m x n CSR; fp64 values, int32 indices; m, k, n and every nnz
+ * below 2^31.  A plan: create does the symbolic work once, numeric fills C's values for new values of A and B on the
+ * same structure.  A and B may have unsorted rows and duplicate entries, as everywhere else; empty rows, m = 0, k = 0,
+ * n = 0 and nnz = 0 are valid.  The contract:
+ *   (S) structure: row i of C stores column j exactly when some stored a_ik and some stored b_kj exist.  Columns within
+ *       a row are ascending and distinct.  The structure never depends on the values: a sum that cancels stays as a
+ *       stored zero, and so do NaN and Inf.  rowptr_C has m + 1 int32 entries; if nnz(C) would reach 2^31, create
+ *       returns SBLAS_E_INVALID and makes no plan;
+ *   (V) values: number the products of C's row i by (position e of a_ik within A's row i, position f of b_kj within
+ *       B's row k), e the major index, both in stored order.  Each product is a * b with one rounding.  The value of
+ *       C[i, j] is the first product that lands on j with each later product that lands on j added to it one at a time
+ *       in that numbering, ((p1 + p2) + p3) + ..., plain fp64 adds; a single product is copied (-0.0 stays -0.0).  Put
+ *       another way, C is sblas_hip_coo_to_csr_f64_i32(..., SBLAS_COO_SUM) of the expanded triplets (i, j, a * b)
+ *       listed in that numbering, in structure and in values.  (Which NaN a sum holds -- its sign and payload -- is
+ *       the adder's choice where IEEE 754 leaves it open; that a NaN is there is part of the contract.);
+ *   (I) independence: the bits of C's row i are a function of A's row i, as stored, and of the rows of B it names, as
+ *       stored -- not of the row's index, its neighbours, the internal path that took it, chunk or workgroup
+ *       boundaries, or pointer alignment;
+ *   (D) determinism: no floating-point atomics and nothing that depends on scheduling; the same inputs give the same
+ *       bits on every run and under graph replay.  (Integer LDS atomics set bitmap bits; no output bit depends on
+ *       which lane comes first.)
+ * Two paths stand behind the contract.  The row path takes a row of C when every row of B is strictly ascending (sorted,
+ * no duplicates: what coo_to_csr "sum", the COO plan and the transpose plan's csc() produce; one pass over colidx_b at
+ * create decides it) and the row's column span -- from the least first to the greatest last column of the B rows it
+ * names -- is at most S_max: a wave, or a 16-lane group of it, owns the row and walks A's entries in stored order.  The
+ * general path takes every other row: chunks of consecutive general rows are expanded into triplets, sorted and
+ * run-summed by the COO passes.  sblas_hip_spgemm_classify is the host rule that decides (no GPU call; testable alone).
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_SPGEMM_AUTO 0
+#define SBLAS_SPGEMM_GENERAL 1 /* every row through the general path */
+/* a row's path, as sblas_hip_spgemm_classify reports it */
+#define SBLAS_SPGEMM_PATH_EMPTY 0   /* no product: nothing runs, the C row is empty */
+#define SBLAS_SPGEMM_PATH_ROW 1
+#define SBLAS_SPGEMM_PATH_GENERAL 2
+/* out: [0] S_max (columns), [1] LDS accumulator entries of the 64-lane form (a longer C row accumulates in val_c),
+ * [2] default chunk cap (products), [3] 0 */
+int sblas_hip_spgemm_limits(int64_t out[4]);
+/* The host rule.  products[i]: the products of row i (int64: a total may pass 2^31); span[i]: its column span;
+ * b_ascending: the verdict on B's rows; chunk_cap: 0 = default.  path[i] = SBLAS_SPGEMM_PATH_*: EMPTY when the row has
+ * no product, else ROW when b_ascending, flags == SBLAS_SPGEMM_AUTO and span[i] <= S_max, else GENERAL.  The general
+ * rows, numbered 0, 1, ... in row order, are cut into *n_chunks chunks: chunk c holds the general rows chunk_first[c] ..
+ * chunk_first[c + 1] - 1 (n_chunks + 1 entries are written, at most m + 1), consecutive, each with at most chunk_cap
+ * products unless it is a single row. */
+int sblas_hip_spgemm_classify(int64_t m, const int64_t *products, const int64_t *span, int b_ascending, int flags,
+                              int64_t chunk_cap, uint8_t *path /* m */, int64_t *chunk_first /* up to m + 1 */,
+                              int64_t *n_chunks);
+/* lanes that own a row-path row of a_len stored A entries: 16 while products <= 16 * a_len (the named B rows are short
+ * on average) and span <= S_max / 4, else 64.  The order within the row is the same in both. */
+int sblas_hip_spgemm_group_width(int64_t products, int64_t a_len, int64_t span);
+/* SBLAS_OK when nnz_c fits an int32 index (below 2^31), else SBLAS_E_INVALID: create's check on the counted nnz(C) */
+int sblas_hip_spgemm_check_nnz(int64_t nnz_c);
+/* create: checks on the device first that both rowptr start at 0 and never step down and that every column index is in
+ * range (SBLAS_E_INVALID, nothing else is launched), copies both structures into the plan, counts products and spans
+ * in one pass over A's rows, applies the host rule, and builds rowptr_C and colidx_C.  Synchronises `stream` several
+ * times.  A general row of more than 2^31 - 1 products is refused (SBLAS_E_INVALID).  The plan owns C's structure, the
+ * copies of A's and B's, the row lists and the general path's workspace, which is sized by the largest chunk. */
+int sblas_hip_spgemm_plan_create(int dev, void *stream, int64_t m, int64_t k, int64_t n, const int32_t *rowptr_a,
+                                 const int32_t *colidx_a, const int32_t *rowptr_b, const int32_t *colidx_b, int flags,
+                                 int64_t chunk_cap /* 0 = default */, void **plan_out);
+/* out: [0] m [1] k [2] n [3] nnz(C) [4] products in total [5] rows on the row path [6] rows on the general path
+ * [7] chunks [8] most products in one row [9] B strictly ascending (0/1) [10] bytes held [11] flags */
+int sblas_hip_spgemm_plan_info(const void *plan, int64_t out[12]);
+/* C's structure (either output may be NULL): rowptr_c (m + 1), colidx_c (nnz(C)); ordinary device arrays that live until
+ * the plan is destroyed: the SpMV, SpMM and transpose plans are built on them unchanged */
+int sblas_hip_spgemm_plan_csr(const void *plan, const int32_t **rowptr_c, const int32_t **colidx_c);
+/* val_c (nnz(C)) from val_a and val_b, in A's and B's stored order.  Stream-ordered on the calling thread's current
+ * device; allocates nothing, never synchronises, graph-capturable; one call at a time per plan.  The general path
+ * sorts its chunks again on every call.  SBLAS_E_INVALID when the current device is not the plan's. */
+int sblas_hip_spgemm_plan_numeric(const void *plan, void *stream, const double *val_a, const double *val_b, double *val_c);
+int sblas_hip_spgemm_plan_destroy(void *plan);
 
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A

@@ -42,6 +42,9 @@ EXPORTS = [
     "sblas_hip_sddmm_csr_workspace", "sblas_hip_sddmm_csr_f64_i32",
     "sblas_hip_csr_softmax_workspace", "sblas_hip_csr_softmax_f64_i32", "sblas_hip_csr_softmax_backward_f64_i32",
     "sblas_hip_csr_attention_workspace", "sblas_hip_csr_attention_f64_i32", "sblas_hip_csr_attention_backward_f64_i32",
+    "sblas_hip_spgemm_limits", "sblas_hip_spgemm_classify", "sblas_hip_spgemm_group_width", "sblas_hip_spgemm_check_nnz",
+    "sblas_hip_spgemm_plan_create", "sblas_hip_spgemm_plan_info", "sblas_hip_spgemm_plan_csr", "sblas_hip_spgemm_plan_numeric",
+    "sblas_hip_spgemm_plan_destroy",
 ]
 
 
@@ -217,6 +220,24 @@ def lib():
     L.sblas_hip_csr_attention_backward_f64_i32.restype = C.c_int
     L.sblas_hip_csr_attention_backward_f64_i32.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64,
                                                            f64, vp, i64, vp, vp, vp, i64, vp, vp, vp, sz]
+    L.sblas_hip_spgemm_limits.restype = C.c_int
+    L.sblas_hip_spgemm_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_hip_spgemm_classify.restype = C.c_int
+    L.sblas_hip_spgemm_classify.argtypes = [i64, vp, vp, C.c_int, C.c_int, i64, vp, vp, C.POINTER(i64)]
+    L.sblas_hip_spgemm_group_width.restype = C.c_int
+    L.sblas_hip_spgemm_group_width.argtypes = [i64, i64, i64]
+    L.sblas_hip_spgemm_check_nnz.restype = C.c_int
+    L.sblas_hip_spgemm_check_nnz.argtypes = [i64]
+    L.sblas_hip_spgemm_plan_create.restype = C.c_int
+    L.sblas_hip_spgemm_plan_create.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, vp, C.c_int, i64, C.POINTER(vp)]
+    L.sblas_hip_spgemm_plan_info.restype = C.c_int
+    L.sblas_hip_spgemm_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_spgemm_plan_csr.restype = C.c_int
+    L.sblas_hip_spgemm_plan_csr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_spgemm_plan_numeric.restype = C.c_int
+    L.sblas_hip_spgemm_plan_numeric.argtypes = [vp, vp, vp, vp, vp]
+    L.sblas_hip_spgemm_plan_destroy.restype = C.c_int
+    L.sblas_hip_spgemm_plan_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -314,6 +335,47 @@ def spmm_split_classify(rowptr, nnz=None, split_min=0, piece=0, direct_mask=None
     out = out[:n]
     n_pieces = int(np.count_nonzero(out[:, 3] >= 0))
     return out[:n_pieces], out[n_pieces:]
+
+
+# SpGEMM: plan flags and the host rule's row paths (SBLAS_SPGEMM_* in sblas_hip.h)
+SPGEMM_AUTO, SPGEMM_GENERAL = 0, 1
+SPGEMM_PATH_EMPTY, SPGEMM_PATH_ROW, SPGEMM_PATH_GENERAL = 0, 1, 2
+
+
+def spgemm_limits():
+    """The SpGEMM plan's limits (sblas_hip_spgemm_limits): dict(s_max, acc_cap, chunk_cap)."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_hip_spgemm_limits(out), "sblas_hip_spgemm_limits")
+    return dict(s_max=int(out[0]), acc_cap=int(out[1]), chunk_cap=int(out[2]))
+
+
+def spgemm_classify(products, span, b_ascending=True, general=False, chunk_cap=0):
+    """The SpGEMM plan's host rule (sblas_hip_spgemm_classify) -> (path, chunk_first): path[i] is SPGEMM_PATH_EMPTY, _ROW
+    or _GENERAL for row i; chunk c holds the general rows, numbered in row order, chunk_first[c] .. chunk_first[c + 1] - 1.
+    products and span are per-row int64 counts."""
+    products = np.ascontiguousarray(products, np.int64)
+    span = np.ascontiguousarray(span, np.int64)
+    m = len(products)
+    if len(span) != m:
+        raise SblasError("span has %d entries, products %d" % (len(span), m))
+    path = np.zeros(max(m, 1), np.uint8)
+    chunk_first = np.zeros(m + 1, np.int64)
+    n = C.c_int64()
+    rc = lib().sblas_hip_spgemm_classify(m, products.ctypes.data, span.ctypes.data, 1 if b_ascending else 0,
+                                         SPGEMM_GENERAL if general else SPGEMM_AUTO, int(chunk_cap), path.ctypes.data,
+                                         chunk_first.ctypes.data, C.byref(n))
+    check(rc, "sblas_hip_spgemm_classify")
+    return path[:m], chunk_first[:n.value + 1].copy()
+
+
+def spgemm_group_width(products, a_len, span):
+    """Lanes that own a row-path row (sblas_hip_spgemm_group_width): 16 or 64."""
+    return int(lib().sblas_hip_spgemm_group_width(int(products), int(a_len), int(span)))
+
+
+def spgemm_check_nnz(nnz_c):
+    """The return code of the plan's check on the counted nnz(C) (0: it fits an int32 index)."""
+    return int(lib().sblas_hip_spgemm_check_nnz(int(nnz_c)))
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -1132,6 +1194,109 @@ class CooPlan:
             self.destroy()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------------------
+# SpGEMM: C = A * B for two CSR matrices (sblas_hip_spgemm_plan_*)
+# ------------------------------------------------------------------------------------------
+class SpgemmPlan:
+    """The structure of C = A * B (sblas_hip_spgemm_plan_create): A is m x k, B is k x n, both CSR with int32 indices;
+    rows may be unsorted and hold duplicates.  Creation checks both structures on the device (a bad one raises), copies
+    them, and builds C's rowptr and colidx, which the plan owns.  multiply(val_a, val_b) fills C's values; it allocates
+    nothing inside the library and is graph-capturable.  general=True sends every row through the expand / sort / sum
+    path; chunk_cap bounds the products of one of its chunks (0: the default).  destroy() / garbage collection frees the
+    device buffers."""
+
+    def __init__(self, m, k, n, rowptr_a, colidx_a, rowptr_b, colidx_b, general=False, chunk_cap=0, stream=None):
+        import torch
+        self.m, self.k, self.n = m, k, n
+        self.handle = None
+        for name, t in (("rowptr_a", rowptr_a), ("colidx_a", colidx_a), ("rowptr_b", rowptr_b), ("colidx_b", colidx_b)):
+            _typed(name, t, torch.int32)
+            if not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+        if rowptr_a.numel() != m + 1 or rowptr_b.numel() != k + 1:
+            raise SblasError("rowptr_a needs m + 1 = %d entries and rowptr_b k + 1 = %d" % (m + 1, k + 1))
+        self.device = rowptr_a.device
+        self.nnz_a, self.nnz_b = int(colidx_a.numel()), int(colidx_b.numel())
+        h = C.c_void_p()
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_spgemm_plan_create(-1, _stream(stream), m, k, n, ptr(rowptr_a), ptr(colidx_a), ptr(rowptr_b),
+                                                     ptr(colidx_b), SPGEMM_GENERAL if general else SPGEMM_AUTO, int(chunk_cap),
+                                                     C.byref(h)), "sblas_hip_spgemm_plan_create")
+        self.handle = h
+        self.nnz_c = self.info()["nnz_c"]
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_spgemm_plan_info(self.handle, out), "sblas_hip_spgemm_plan_info")
+        return dict(m=int(out[0]), k=int(out[1]), n=int(out[2]), nnz_c=int(out[3]), products=int(out[4]), rows_row=int(out[5]),
+                    rows_general=int(out[6]), chunks=int(out[7]), max_row_products=int(out[8]), b_ascending=bool(out[9]),
+                    bytes=int(out[10]), general=out[11] == SPGEMM_GENERAL)
+
+    def csr(self):
+        """(rowptr_c, colidx_c): torch views of the plan's device arrays; they live as long as the plan."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(2)]
+        check(lib().sblas_hip_spgemm_plan_csr(self.handle, *[C.byref(p) for p in ptrs]), "sblas_hip_spgemm_plan_csr")
+        def one(p, n):
+            if n == 0:
+                return torch.empty(0, dtype=torch.int32, device=self.device)
+            return torch.as_tensor(_DeviceArray(p.value, n, "<i4"), device=self.device)
+        return tuple(one(p, n) for p, n in zip(ptrs, (self.m + 1, self.nnz_c)))
+
+    def multiply(self, val_a, val_b, out=None, stream=None):
+        """C's values (nnz_c of them) for the values val_a and val_b in A's and B's stored order, written to `out` when
+        given."""
+        import torch
+        _typed("val_a", val_a, torch.float64), _typed("val_b", val_b, torch.float64)
+        if val_a.numel() != self.nnz_a or val_b.numel() != self.nnz_b:
+            raise SblasError("val_a / val_b have %d / %d entries, the plan %d / %d" % (val_a.numel(), val_b.numel(), self.nnz_a, self.nnz_b))
+        if out is None:
+            out = torch.empty(self.nnz_c, dtype=torch.float64, device=self.device)
+        _typed("out", out, torch.float64)
+        if out.numel() < self.nnz_c:
+            raise SblasError("out has %d entries, C %d" % (out.numel(), self.nnz_c))
+        if self.nnz_c:
+            pa, pb, po = _dev_ptr(val_a, torch.float64, "val_a"), _dev_ptr(val_b, torch.float64, "val_b"), _dev_ptr(out, torch.float64, "out")
+        else:
+            pa = pb = po = None
+        check(lib().sblas_hip_spgemm_plan_numeric(self.handle, _stream(stream), pa, pb, po), "sblas_hip_spgemm_plan_numeric")
+        return out
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_spgemm_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def spgemm(A, B, stream=None):
+    """C = A * B, one shot: A = (m, k, rowptr, colidx, val) and B = (k, n, rowptr, colidx, val) as GPU tensors -> (rowptr_c,
+    colidx_c, val_c), tensors of their own (the plan made here is destroyed before returning)."""
+    m, k, rowptr_a, colidx_a, val_a = A
+    kb, n, rowptr_b, colidx_b, val_b = B
+    if k != kb:
+        raise SblasError("A is %d x %d, B is %d x %d" % (m, k, kb, n))
+    plan = SpgemmPlan(m, k, n, rowptr_a, colidx_a, rowptr_b, colidx_b, stream=stream)
+    try:
+        rowptr_c, colidx_c = plan.csr()
+        val_c = plan.multiply(val_a, val_b, stream=stream)
+        rowptr_c, colidx_c = rowptr_c.clone(), colidx_c.clone()
+        if stream is not None:
+            stream.synchronize()
+        else:
+            import torch
+            torch.cuda.current_stream().synchronize()
+    finally:
+        plan.destroy()
+    return rowptr_c, colidx_c, val_c
 
 
 # ------------------------------------------------------------------------------------------
