@@ -481,6 +481,86 @@ int sblas_hip_spgemm_plan_numeric(const void *plan, void *stream, const double *
 int sblas_hip_spgemm_plan_destroy(void *plan);
 
 /* ---------------------------------------------------------------------------------------
+ * Sparse triangular solves on a level-scheduled plan:  T x = alpha * b  (SpSV)  and  T X = alpha * B  for nrhs
+ * right-hand sides (SpSM); B and X row-major n x nrhs with leading dimensions ldb, ldx >= nrhs.
+ *   - T is the lower or upper triangle (fill) of a square n x n CSR matrix, fp64 values, int32 indices, n and nnz below
+ *     2^31.  Rows may be unsorted; off-diagonal duplicates add.  STORED ENTRIES IN THE OTHER TRIANGLE ARE IGNORED: a full
+ *     matrix can be passed for a Gauss-Seidel sweep, and a combined ILU(0) factor (unit-lower L and upper U in one CSR)
+ *     is solved by two plans on the same arrays.
+ *   - SBLAS_DIAG_UNIT ignores stored diagonal entries and uses 1.  SBLAS_DIAG_NON_UNIT needs exactly one stored diagonal
+ *     entry in every row: a missing or duplicated one, a column outside [0, n), a rowptr that does not start at 0, steps
+ *     down or does not end at nnz make create fail with SBLAS_E_INVALID and report the first such row in *bad_row; no
+ *     kernel runs on such a structure.  A numerically zero pivot is NOT checked: the division follows IEEE 754, and
+ *     Inf / NaN spread to the rows that depend on it.
+ *   - level(i) = 0 when row i has no selected off-diagonal entry (column < i for LOWER, > i for UPPER), else 1 + the
+ *     greatest level of the rows they name.  The rows of one level are independent.  Two kernels: WIDE, one launch for
+ *     one level; CHAIN, one launch of a single workgroup for a run of consecutive levels with a workgroup barrier
+ *     between them.  Nothing waits across workgroups (no flag polling, no cooperative launch, no grid barrier), there
+ *     are no atomics, and every loop's trip count comes from the plan.
+ *   - results contract.  SpSV: the bits of x[i] are a function of row i's stored entries (columns and values, in stored
+ *     order), the x values they name, b[i] and alpha -- NOT of the level structure, of the kernel that took the row, of
+ *     the mode or of chain_rows.  A row of p stored entries (both triangles and the diagonal counted) belongs to
+ *     G(p) = 4 (p <= 4), 16 (p <= 32) or 64 lanes; lane l sums the selected entries among the stored entries l, l + G,
+ *     l + 2G, ... in that order, one fused multiply-add each from +0; the lanes fold by a butterfly (l ^ 1, l ^ 2, ...);
+ *     then x[i] = (alpha * b[i] - sum) / t_ii with each of the three operations rounded on its own (t_ii = 1 under UNIT).
+ *     SpSM: lanes run along the right-hand sides, and column j sums row i's selected entries one after another in
+ *     stored order (fused multiply-adds from +0), then the same last expression: column j's bits are a function of
+ *     column j of B alone, independent of nrhs, ldb and ldx.  They need not equal SpSV's.
+ *   - in place (x == b; X == B with ldx == ldb) is allowed: row i alone reads b[i], and does so before it writes x[i].
+ *     Partial overlap is undefined.
+ *   - the transposed solve T^T x = alpha * b needs no kernel of its own: the transpose plan's csc() arrays are T^T as
+ *     CSR arrays of the opposite fill, and a solve plan on them is the transposed solve.
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_FILL_LOWER 0
+#define SBLAS_FILL_UPPER 1
+#define SBLAS_DIAG_NON_UNIT 0
+#define SBLAS_DIAG_UNIT 1
+#define SBLAS_SPTRSV_AUTO 0       /* a level above chain_rows rows: one wide launch; a run of narrower levels: one chain launch */
+#define SBLAS_SPTRSV_PER_LEVEL 1  /* every level a wide launch */
+#define SBLAS_SPTRSV_CHAIN_ONLY 2 /* one chain launch for everything (tests: the chain kernel loops over a wide level) */
+/* a launch's kind, as the schedule reports it */
+#define SBLAS_SPTRSV_LAUNCH_WIDE 0
+#define SBLAS_SPTRSV_LAUNCH_CHAIN 1
+/* out: [0] default chain_rows, [1] threads of the chain workgroup, [2] longest row of 4 lanes, [3] longest row of 16 lanes */
+int sblas_hip_sptrsv_limits(int64_t out[4]);
+/* The host rule, on HOST arrays (no GPU call; testable alone).  Checks the structure as described above, in this order:
+ * rowptr (*bad_row = the first row that ends before it starts; 0 when rowptr[0] != 0), then row by row the columns and,
+ * under NON_UNIT, the diagonal.  level_out[i] = level(i); *n_levels = the greatest level + 1 (0 when n == 0).  bad_row may
+ * be NULL; it is -1 on success. */
+int sblas_sptrsv_levels(int64_t n, const int32_t *rowptr, const int32_t *colidx, int fill, int diag,
+                        int32_t *level_out /* n */, int64_t *n_levels, int64_t *bad_row);
+/* The launches of a solve over levels of widths[l] rows: launch q covers the levels launch_first_out[q] ..
+ * launch_first_out[q + 1] - 1 (n_launches + 1 entries are written, at most n_levels + 1) and is of kind kind_out[q]
+ * (SBLAS_SPTRSV_LAUNCH_*; a wide launch is always one level).  flags = SBLAS_SPTRSV_*; chain_rows: 0 = default. */
+int sblas_sptrsv_schedule(int64_t n_levels, const int64_t *widths, int flags, int64_t chain_rows,
+                          uint8_t *kind_out /* up to n_levels */, int64_t *launch_first_out /* up to n_levels + 1 */,
+                          int64_t *n_launches);
+/* create: copies rowptr and colidx to the host once, runs the host rule, and uploads the rows ordered by (level, row)
+ * with each row's extent and diagonal position, the level pointer, and every level's rows packed into four-lane units
+ * (a row of G lanes is G / 4 of them).  Synchronises `stream`.
+ * The plan keeps the caller's rowptr / colidx POINTERS, which must outlive the plan and stay unchanged.  bad_row may be
+ * NULL.  n == 0 succeeds. */
+int sblas_hip_sptrsv_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr,
+                                 const int32_t *colidx, int fill, int diag, int flags, int64_t chain_rows /* 0 = default */,
+                                 void **plan_out, int64_t *bad_row);
+/* out: [0] n [1] nnz [2] fill [3] diag [4] levels [5] launches [6] wide launches [7] chain launches [8] rows of the widest
+ * level [9] stored entries of the longest row [10] device bytes held [11] flags */
+int sblas_hip_sptrsv_plan_info(const void *plan, int64_t out[12]);
+/* device views that live until the plan is destroyed (either output may be NULL; both NULL when n == 0): perm (n): the
+ * rows by (level, row); level_ptr (levels + 1): level l is perm[level_ptr[l] .. level_ptr[l + 1] - 1] */
+int sblas_hip_sptrsv_plan_order(const void *plan, const int32_t **perm, const int32_t **level_ptr);
+int sblas_hip_sptrsv_plan_destroy(void *plan);
+/* The solves.  Stream-ordered on the calling thread's current device; they allocate nothing and never synchronise: a
+ * fixed sequence of launches (graph-capturable as a linear chain of nodes) that takes new `val` on every call.
+ * rowptr / colidx must be the pointers the plan was made with, and the current device the plan's: SBLAS_E_INVALID
+ * otherwise, before anything is launched.  n == 0 and nrhs == 0 succeed and launch nothing. */
+int sblas_hip_sptrsv_f64_i32_planned(const void *plan, void *stream, const int32_t *rowptr, const int32_t *colidx,
+                                     const double *val, double alpha, const double *b, double *x);
+int sblas_hip_sptrsm_f64_i32_planned(const void *plan, void *stream, const int32_t *rowptr, const int32_t *colidx,
+                                     const double *val, int64_t nrhs, double alpha, const double *B, int64_t ldb,
+                                     double *X, int64_t ldx);
+
+/* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
  * (the gradient of C = A * B with respect to A's values with X = dC and Y = B; edge scores; residuals on a pattern).
  *   - A gives its PATTERN only (rowptr, colidx).  Unsorted rows and duplicate entries are legal, as everywhere else; a

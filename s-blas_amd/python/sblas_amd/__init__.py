@@ -45,6 +45,9 @@ EXPORTS = [
     "sblas_hip_spgemm_limits", "sblas_hip_spgemm_classify", "sblas_hip_spgemm_group_width", "sblas_hip_spgemm_check_nnz",
     "sblas_hip_spgemm_plan_create", "sblas_hip_spgemm_plan_info", "sblas_hip_spgemm_plan_csr", "sblas_hip_spgemm_plan_numeric",
     "sblas_hip_spgemm_plan_destroy",
+    "sblas_hip_sptrsv_limits", "sblas_sptrsv_levels", "sblas_sptrsv_schedule",
+    "sblas_hip_sptrsv_plan_create", "sblas_hip_sptrsv_plan_info", "sblas_hip_sptrsv_plan_order", "sblas_hip_sptrsv_plan_destroy",
+    "sblas_hip_sptrsv_f64_i32_planned", "sblas_hip_sptrsm_f64_i32_planned",
 ]
 
 
@@ -238,6 +241,24 @@ def lib():
     L.sblas_hip_spgemm_plan_numeric.argtypes = [vp, vp, vp, vp, vp]
     L.sblas_hip_spgemm_plan_destroy.restype = C.c_int
     L.sblas_hip_spgemm_plan_destroy.argtypes = [vp]
+    L.sblas_hip_sptrsv_limits.restype = C.c_int
+    L.sblas_hip_sptrsv_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_sptrsv_levels.restype = C.c_int
+    L.sblas_sptrsv_levels.argtypes = [i64, vp, vp, C.c_int, C.c_int, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_sptrsv_schedule.restype = C.c_int
+    L.sblas_sptrsv_schedule.argtypes = [i64, vp, C.c_int, i64, vp, vp, C.POINTER(i64)]
+    L.sblas_hip_sptrsv_plan_create.restype = C.c_int
+    L.sblas_hip_sptrsv_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_sptrsv_plan_info.restype = C.c_int
+    L.sblas_hip_sptrsv_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_sptrsv_plan_order.restype = C.c_int
+    L.sblas_hip_sptrsv_plan_order.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_sptrsv_plan_destroy.restype = C.c_int
+    L.sblas_hip_sptrsv_plan_destroy.argtypes = [vp]
+    L.sblas_hip_sptrsv_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_sptrsv_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, f64, vp, vp]
+    L.sblas_hip_sptrsm_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_sptrsm_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, i64, f64, vp, i64, vp, i64]
     _lib = L
     return L
 
@@ -376,6 +397,66 @@ def spgemm_group_width(products, a_len, span):
 def spgemm_check_nnz(nnz_c):
     """The return code of the plan's check on the counted nnz(C) (0: it fits an int32 index)."""
     return int(lib().sblas_hip_spgemm_check_nnz(int(nnz_c)))
+
+
+# triangular solves: fill, diagonal, plan modes and launch kinds (SBLAS_FILL_*, SBLAS_DIAG_*, SBLAS_SPTRSV_* in sblas_hip.h)
+FILL_LOWER, FILL_UPPER = 0, 1
+DIAG_NON_UNIT, DIAG_UNIT = 0, 1
+SPTRSV_AUTO, SPTRSV_PER_LEVEL, SPTRSV_CHAIN_ONLY = 0, 1, 2
+SPTRSV_LAUNCH_WIDE, SPTRSV_LAUNCH_CHAIN = 0, 1
+_SPTRSV_MODE = {"auto": SPTRSV_AUTO, "per_level": SPTRSV_PER_LEVEL, "chain": SPTRSV_CHAIN_ONLY}
+
+
+def _sptrsv_mode(mode):
+    if mode not in _SPTRSV_MODE:
+        raise SblasError("mode must be 'auto', 'per_level' or 'chain', not %r" % (mode,))
+    return _SPTRSV_MODE[mode]
+
+
+def _bad_structure(what, rc, bad_row):
+    """the SblasError of a refused triangular structure; it names the first bad row and carries it as .bad_row"""
+    where = ": row %d" % bad_row if bad_row >= 0 else ""
+    err = SblasError("%s failed: %s (code %d)%s" % (what, lib().sblas_hip_error_string(rc).decode(), rc, where))
+    err.bad_row = bad_row
+    return err
+
+
+def sptrsv_limits():
+    """The triangular solve's limits (sblas_hip_sptrsv_limits): dict(chain_rows, chain_threads, g4_max, g16_max) -- the
+    default chain_rows, the chain workgroup's threads, and the longest stored rows that 4 and 16 lanes take."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_hip_sptrsv_limits(out), "sblas_hip_sptrsv_limits")
+    return dict(chain_rows=int(out[0]), chain_threads=int(out[1]), g4_max=int(out[2]), g16_max=int(out[3]))
+
+
+def sptrsv_levels(n, rowptr, colidx, lower=True, unit_diag=False):
+    """The level of every row (sblas_sptrsv_levels, host arrays) -> (level, n_levels).  A refused structure raises an
+    SblasError whose .bad_row is the first bad row."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    if len(rowptr) != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (len(rowptr), n))
+    level = np.zeros(max(n, 1), np.int32)
+    n_levels, bad = C.c_int64(), C.c_int64(-1)
+    rc = lib().sblas_sptrsv_levels(n, rowptr.ctypes.data, colidx.ctypes.data if len(colidx) else None,
+                                   FILL_LOWER if lower else FILL_UPPER, DIAG_UNIT if unit_diag else DIAG_NON_UNIT,
+                                   level.ctypes.data, C.byref(n_levels), C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_sptrsv_levels", rc, bad.value)
+    return level[:n], int(n_levels.value)
+
+
+def sptrsv_schedule(widths, mode="auto", chain_rows=0):
+    """The launches of a solve over levels of the given widths (sblas_sptrsv_schedule) -> (kind, launch_first): launch q
+    is SPTRSV_LAUNCH_WIDE or _CHAIN and covers the levels launch_first[q] .. launch_first[q + 1] - 1."""
+    widths = np.ascontiguousarray(widths, np.int64)
+    L = len(widths)
+    kind = np.zeros(max(L, 1), np.uint8)
+    first = np.zeros(L + 1, np.int64)
+    n = C.c_int64()
+    check(lib().sblas_sptrsv_schedule(L, widths.ctypes.data, _sptrsv_mode(mode), int(chain_rows), kind.ctypes.data,
+                                      first.ctypes.data, C.byref(n)), "sblas_sptrsv_schedule")
+    return kind[:n.value].copy(), first[:n.value + 1].copy()
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -1297,6 +1378,135 @@ def spgemm(A, B, stream=None):
     finally:
         plan.destroy()
     return rowptr_c, colidx_c, val_c
+
+
+# ------------------------------------------------------------------------------------------
+# Sparse triangular solves: T x = alpha b, T X = alpha B (sblas_hip_sptrsv_plan_*)
+# ------------------------------------------------------------------------------------------
+class SptrsvPlan:
+    """The level schedule of one triangle of a square CSR matrix (sblas_hip_sptrsv_plan_create): the lower (lower=True) or
+    upper triangle of the n x n matrix (rowptr, colidx), int32 indices; rows may be unsorted, off-diagonal duplicates add,
+    and stored entries in the other triangle are ignored.  unit_diag=True ignores stored diagonals and uses 1; otherwise
+    every row needs exactly one.  A bad structure raises an SblasError that names the first bad row (.bad_row).  The plan
+    keeps rowptr and colidx alive and solves on them as they are: do not change them.  mode: "auto" (a level above
+    chain_rows rows is one launch, a run of narrower levels one single-workgroup launch), "per_level" or "chain";
+    chain_rows=0 takes the default.  solve() allocates nothing inside the library and is graph-capturable.  The
+    transposed solve: a plan with the opposite `lower` on TransposePlan.csc()'s (colptr, rowidx), solved with its valT."""
+
+    def __init__(self, n, rowptr, colidx, lower=True, unit_diag=False, mode="auto", chain_rows=0, stream=None):
+        import torch
+        self.n, self.lower, self.unit_diag, self.mode = n, bool(lower), bool(unit_diag), mode
+        self.handle = None
+        flags = _sptrsv_mode(mode)
+        for name, t in (("rowptr", rowptr), ("colidx", colidx)):
+            if not isinstance(t, torch.Tensor):
+                raise SblasError("%s must be a torch tensor" % name)
+            _typed(name, t, torch.int32)
+            if not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+        if rowptr.numel() != n + 1:
+            raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
+        self.rowptr, self.colidx = rowptr, colidx
+        self.device = rowptr.device
+        self.nnz = int(colidx.numel())
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_sptrsv_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
+                                                    colidx.data_ptr() if self.nnz else None,
+                                                    FILL_LOWER if lower else FILL_UPPER, DIAG_UNIT if unit_diag else DIAG_NON_UNIT,
+                                                    flags, int(chain_rows), C.byref(h), C.byref(bad))
+        if rc != 0:
+            raise _bad_structure("sblas_hip_sptrsv_plan_create", rc, bad.value)
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_sptrsv_plan_info(self.handle, out), "sblas_hip_sptrsv_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), lower=out[2] == FILL_LOWER, unit_diag=out[3] == DIAG_UNIT, levels=int(out[4]),
+                    launches=int(out[5]), wide_launches=int(out[6]), chain_launches=int(out[7]), widest_level=int(out[8]),
+                    longest_row=int(out[9]), bytes=int(out[10]), mode=[k for k, v in _SPTRSV_MODE.items() if v == out[11]][0])
+
+    def levels(self):
+        """(perm, level_ptr): torch views of the plan's device arrays -- the rows ordered by (level, row), and level l as
+        perm[level_ptr[l] : level_ptr[l + 1]]; they live as long as the plan."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(2)]
+        check(lib().sblas_hip_sptrsv_plan_order(self.handle, *[C.byref(p) for p in ptrs]), "sblas_hip_sptrsv_plan_order")
+        if self.n == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device)
+        lv = self.info()["levels"]
+        return tuple(torch.as_tensor(_DeviceArray(p.value, k, "<i4"), device=self.device) for p, k in zip(ptrs, (self.n, lv + 1)))
+
+    def solve(self, val, b, x=None, alpha=1.0, stream=None):
+        """x with T x = alpha * b for the values val (in stored order).  A 1-D b of n entries is one right-hand side
+        (SpSV); a 2-D n x nrhs b with strides (ld, 1) is nrhs of them (SpSM), read by its stride.  x: like b (x is b: in
+        place); made here when None.  Returns x."""
+        import torch
+        for name, t in (("val", val), ("b", b)) + ((("x", x),) if x is not None else ()):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            if t.dtype != torch.float64:
+                raise SblasError("%s must be float64, got %s" % (name, t.dtype))
+        if not val.is_contiguous() or val.numel() != self.nnz:
+            raise SblasError("val must be contiguous with one value per stored entry (%d), got %d" % (self.nnz, val.numel()))
+        if b.dim() not in (1, 2) or b.shape[0] != self.n:
+            raise SblasError("b must hold %d entries or be %d x nrhs, got shape %s" % (self.n, self.n, tuple(b.shape)))
+        if x is None:
+            x = torch.empty(tuple(b.shape), dtype=torch.float64, device=self.device)
+        if tuple(x.shape) != tuple(b.shape):
+            raise SblasError("x has shape %s, b %s" % (tuple(x.shape), tuple(b.shape)))
+        pr, pc = self.rowptr.data_ptr(), (self.colidx.data_ptr() if self.nnz else None)
+        pv = val.data_ptr() if self.nnz else None
+        if b.dim() == 1:
+            for name, t in (("b", b), ("x", x)):
+                if self.n > 1 and t.stride(0) != 1:
+                    raise SblasError("%s must be contiguous" % name)
+            check(lib().sblas_hip_sptrsv_f64_i32_planned(self.handle, _stream(stream), pr, pc, pv, float(alpha),
+                                                         b.data_ptr() if self.n else None, x.data_ptr() if self.n else None),
+                  "sblas_hip_sptrsv_f64_i32_planned")
+            return x
+        nrhs = int(b.shape[1])
+        ld = []
+        for name, t in (("b", b), ("x", x)):
+            if nrhs > 1 and t.stride(1) != 1:
+                raise SblasError("%s must be row-major (strides (ld, 1)), got strides %s" % (name, tuple(t.stride())))
+            l = int(t.stride(0)) if self.n > 1 else max(nrhs, 1)
+            if l < nrhs:
+                raise SblasError("%s has a leading dimension of %d for %d columns" % (name, l, nrhs))
+            ld.append(max(l, 1))
+        live = self.n > 0 and nrhs > 0
+        check(lib().sblas_hip_sptrsm_f64_i32_planned(self.handle, _stream(stream), pr, pc, pv, nrhs, float(alpha),
+                                                     b.data_ptr() if live else None, ld[0], x.data_ptr() if live else None, ld[1]),
+              "sblas_hip_sptrsm_f64_i32_planned")
+        return x
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_sptrsv_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def sptrsv(A, b, lower=True, unit_diag=False, alpha=1.0, stream=None):
+    """x with T x = alpha * b, one shot: A = (n, rowptr, colidx, val) as GPU tensors, T its lower or upper triangle; b 1-D,
+    or 2-D for several right-hand sides.  The plan made here is destroyed before returning."""
+    n, rowptr, colidx, val = A
+    plan = SptrsvPlan(n, rowptr, colidx, lower=lower, unit_diag=unit_diag, stream=stream)
+    try:
+        x = plan.solve(val, b, alpha=alpha, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        else:
+            import torch
+            torch.cuda.current_stream().synchronize()
+    finally:
+        plan.destroy()
+    return x
 
 
 # ------------------------------------------------------------------------------------------
