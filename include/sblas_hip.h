@@ -740,6 +740,62 @@ int64_t sblas_spmv_plan_classify(const int32_t *rowptr, int64_t rows, int64_t nn
 int64_t sblas_spmm_split_classify(const int32_t *rowptr, int64_t rows, int64_t nnz, int64_t split_min, int64_t piece,
                                   const uint8_t *direct_mask, int64_t panel_rows, int32_t *out, int64_t max_out);
 
+/* The SpMM kernel rule as a host function (no GPU): what one column chunk of an SpMM call of these sizes does -- how B
+ * is staged, where the panel verdicts come from, the panel geometry, and which stage-2 kernels are launched with which
+ * template arguments, in launch order -- under the environment switches as last read (sblas_hip_debug_reload_env).
+ * ldbt is the staged width (sblas_hip_spmm_ldbt), n <= ldbt the chunk's columns, ncu the device's compute units.
+ * caller_staged != 0: the call of sblas_hip_spmm_csr_rowmajorB_f64_i32.  plan: NULL for an unplanned call, else the
+ * SBLAS_SPMM_RULE_PLAN_FIELDS counts of a plan (sblas_hip_spmm_plan_info / _split_info) the rule reads.  Writes up to
+ * max_out of the SBLAS_SPMM_RULE_FIELDS values when `out` is not NULL and returns SBLAS_SPMM_RULE_FIELDS, or -1 (bad
+ * argument). */
+enum {
+    SBLAS_SPMM_RULE_PLAN_N_WINDOW = 0, /* panels of the LDS-tiled kernel                                   */
+    SBLAS_SPMM_RULE_PLAN_N_DIRECT,     /* ... of the direct kernels                                        */
+    SBLAS_SPMM_RULE_PLAN_N_MFMA_W,     /* ... of the matrix-core kernel, falling back to the LDS-tiled one */
+    SBLAS_SPMM_RULE_PLAN_N_MFMA_D,     /* ... falling back to the direct kernels                           */
+    SBLAS_SPMM_RULE_PLAN_MERGE,        /* the vote gave the direct panels to the row-merging kernel        */
+    SBLAS_SPMM_RULE_PLAN_FOUR_ROWS,    /* ... to the four-rows-per-wave kernel                             */
+    SBLAS_SPMM_RULE_PLAN_N_SPLIT,      /* split rows (a split plan)                                        */
+    SBLAS_SPMM_RULE_PLAN_PANEL_ROWS,   /* panel height                                                     */
+    SBLAS_SPMM_RULE_PLAN_GROUPS,       /* groups of four rows per wave                                     */
+    SBLAS_SPMM_RULE_PLAN_FIELDS
+};
+enum {
+    /* stage 1 */
+    SBLAS_SPMM_RULE_STAGING = 0,     /* 0 caller's Bt, 1 whole B, 2 whole B + classifier in one launch, 3 column range, 4 planned */
+    SBLAS_SPMM_RULE_VERDICTS,        /* 0 none, 1 from the staging launch, 2 a launch of their own, 3 an earlier chunk's, 4 the plan's */
+    SBLAS_SPMM_RULE_PANEL_ROWS,      /* panel height (1: nothing classified)                              */
+    SBLAS_SPMM_RULE_GROUPS,          /* groups of four rows per wave                                      */
+    SBLAS_SPMM_RULE_PANELS,          /* classified panels                                                 */
+    SBLAS_SPMM_RULE_PLANNABLE,       /* sblas_hip_spmm_plan_create would keep the verdicts                */
+    /* stage 2, in launch order; 0 = not launched */
+    SBLAS_SPMM_RULE_TILED,           /* 1 spmm_window6_kernel<G, NH>, 2 spmm_lanes_kernel<NC, CP, G, LPE> */
+    SBLAS_SPMM_RULE_TILED_G,
+    SBLAS_SPMM_RULE_W6_NH,
+    SBLAS_SPMM_RULE_W6_GRID_Y,       /* workgroups along the dense columns                                */
+    SBLAS_SPMM_RULE_LANES_NC,
+    SBLAS_SPMM_RULE_LANES_CP,
+    SBLAS_SPMM_RULE_LANES_LPE,
+    SBLAS_SPMM_RULE_MFMA,            /* the matrix-core kernel ...                                        */
+    SBLAS_SPMM_RULE_MFMA_BATCH,      /* ... operand blocks per stage                                      */
+    SBLAS_SPMM_RULE_MFMA_LDS_FLOOR,  /* ... least dynamic LDS, bytes                                      */
+    SBLAS_SPMM_RULE_FOUR_ROWS,       /* four-rows-per-wave direct kernel ...                              */
+    SBLAS_SPMM_RULE_FOUR_ROWS_WAVES, /* ... waves per workgroup                                           */
+    SBLAS_SPMM_RULE_FOUR_ROWS_VOTED, /* ... 1: runs only where the device-side vote says so               */
+    SBLAS_SPMM_RULE_MERGE,           /* row-merging direct kernel                                         */
+    SBLAS_SPMM_RULE_DPP_GROUPS,      /* row-per-wave direct kernel: its GROUPS (1, 2, 4) ...              */
+    SBLAS_SPMM_RULE_DPP_PAD,         /* ... dynamic LDS pad, bytes                                        */
+    SBLAS_SPMM_RULE_DPP_LONG,        /* ... entries from which the whole workgroup computes a row         */
+    SBLAS_SPMM_RULE_NARROW,          /* lane-group direct kernel: 8, 16 or 32 columns                     */
+    SBLAS_SPMM_RULE_ROWS8,           /* wave-per-row direct kernel of 8 columns                           */
+    SBLAS_SPMM_RULE_INTERLEAVE,      /* panel map of the direct kernels: 1 interleave, 0 contiguous, -1 by span */
+    SBLAS_SPMM_RULE_SKIP,            /* a split plan: SKIP instantiations, then the split kernels ...     */
+    SBLAS_SPMM_RULE_SPLIT_GROUPS,    /* ... with this GROUPS                                              */
+    SBLAS_SPMM_RULE_FIELDS
+};
+int64_t sblas_spmm_rule_describe(int64_t rows, int64_t cols, int64_t nnz, int64_t ldbt, int64_t n, int64_t ncu,
+                                 int caller_staged, const int64_t *plan, int64_t *out, int64_t max_out);
+
 /* Dense initialiser of the reference's DenseMatrix(h, w, order) / DenseVector(len) constructors (matrix.h:519-528,
  * :663-672; utility.h:197; config.h:23 seed 211): srand(seed), then rand() / RAND_MAX in storage order (host memory). */
 int sblas_host_fill_rand0to1(double *dst, int64_t count, unsigned seed);

@@ -42,12 +42,14 @@ enum { PANEL_DIRECT = 0, PANEL_WINDOW = 1, PANEL_MFMA_W = 2, PANEL_MFMA_D = 3,
        PANEL_PHASE_SHIFT = 9 /* two bits: (row index where a group of three such rows starts) mod 3 */,
        PANEL_WAVE_ROWS = 0x800 /* flag: columns in runs, or row lengths far apart: a row per wave suits the panel */ };
 constexpr int MFMA_MAX_WAVES = 8; // 16 rows per wave: panels of up to 128 rows (taller panels never take the MFMA kernel)
+constexpr int W6_GMAX = 3;        // spmm_window6_kernel: groups of four rows per wave, 2 or 3 (template parameter)
+constexpr int DPP_LONG = 4096;    // entries from which a row of the row-per-wave kernel is computed by the whole workgroup
 size_t workspace_tail_bytes(int64_t rows);
 unsigned long long *panel_stats_device();
 hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
                             const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
                             const int2 *info, const int *tail, const int *cls, int panel_rows, int npanels, int epoch,
-                            unsigned long long *stats, bool row_c);
+                            unsigned long long *stats, bool row_c, int batch, size_t lds_floor);
 
 // The epilogue of the stage-2 kernels for a ROW-MAJOR C (element (r, j) at C[r * ldc + j]).  Every such kernel parks its
 // panel of results in LDS and writes it back with alpha / beta applied; column-major C is walked with the row index
@@ -82,7 +84,7 @@ __device__ __forceinline__ int xcd_contiguous_panel(int b, int npanels)
     return base + idx;
 }
 
-// Experiment / test switches, read from the environment once (kernels.hip); options_reload() re-reads them.
+// Experiment / test switches, read from the environment once (spmm_rule.cpp); options_reload() re-reads them.
 struct Options {
     int spmm_variant = SPMM_VARIANT_AUTO;
     char spmv_variant[16] = {0};          // "" = auto
@@ -95,12 +97,23 @@ struct Options {
     double rows8_min_avg = 256.0;         // SBLAS_ROWS8_MIN_AVG
     float window_density = 0.42f;         // SBLAS_WINDOW_DENSITY: the LDS-tiled kernel's bar, in nonzeros per spanned column of a 16-row slice of a panel
     int panel_rows = 0, panel_groups = 0; // SBLAS_SPMM_PANEL_ROWS
-    int tune[4] = {0, 0, 0, 0};           // SBLAS_TUNE
+    // SBLAS_TUNE=a,b,c,d: four integers for A/B runs, each parsed once (options_parse) into everything it switches
+    int lanes_copies = 1;                 // a = 2 | 4: copies of a Bt row in the narrow LDS tile (8 columns: 2 or 4; 16 columns: 2, which also caps the groups per wave at two)
+    size_t mfma_lds_floor = 0;            // 0 < a <= 160 KiB: least dynamic LDS of the matrix-core kernel (occupancy)
+    bool one_half = false;                // b = 1: one 64-column half per LDS-tiled workgroup at 128+ staged columns (and three groups per wave allowed)
+    int rowlen_bar = 0;                   // b > 1: the classifier's average-row-length bar at every width (0: the measured ones)
+    int mfma_batch64 = 2;                 // b = 3 | 4: operand blocks per stage of the matrix-core kernel at 64 staged columns
+    int mfma_batch128 = 2;                // b = 1: ... at 128+ staged columns
+    int dpp_long = DPP_LONG;              // c > 0: entries from which the row-per-wave kernel splits a row over its sixteen waves
+    bool lanes32_one_lane = false;        // d = 1: 32 columns with one lane per entry and one group per wave
+    int rows_waves = 0;                   // d = 4 | 8 | 16: waves per workgroup of the four-rows kernel (0: by row length)
     bool validate = false;                // SBLAS_VALIDATE=1: every SpMM / SpMV call checks the CSR contents first (synchronises; debugging)
     float mfma_min_fill = -1.0f;          // SBLAS_MFMA_MIN_FILL: block fill from which a panel takes the MFMA kernel (< 0: built-in rule)
 };
 const Options &options();
 void options_reload();
+int compute_units(); // of the current device (kernels.hip)
+int next_epoch();    // tags one call's classifier verdicts and one staging pass (see classify_panel)
 void raise_dynamic_lds(const void *fn, size_t bytes);
 
 // A per-matrix plan (capi.hip: sblas_hip_spmm_plan_*): the panel verdicts of one (A, staged width) pair kept in a device
@@ -184,6 +197,46 @@ struct SpmmStep {
 // pv: the call's plan, when it was made at this ldbt; prev: the call's previous column chunk
 SpmmStep spmm_step(int rows, int cols, int64_t nnz, int64_t ldbt, const PlanView *pv, const SpmmStep &prev = SpmmStep(),
                    bool caller_staged = false);
+// The classifier's thresholds (classify_args): the longest row a windowed panel may hold (32-bit buffer offsets inside a
+// wave's rows), nonzeros per spanned column and per row a panel needs for the LDS-tiled kernel, the block fill from which
+// it takes the matrix cores (> 1: never), what to probe for the direct kernels' sake (bit 0 row-merging, bit 1 row per wave).
+struct ClassifyArgs {
+    int max_row_len;
+    float min_density, min_rowlen, mfma_min_fill;
+    int merge_probe;
+};
+ClassifyArgs classify_args(int panel_rows, int64_t ldbt);
+int range_parts(int64_t nnz); // (min, max) pairs of the column-range pass of a row block
+
+// What stage 2 of a chunk launches, in launch order (spmm_stage2, spmm_rule.cpp: DESIGN.md 3's selection table);
+// launch_spmm_rowpanel carries it out and decides nothing.  Template arguments are spelled as the kernels take them.
+enum { TILED_NONE = 0, TILED_WINDOW6 = 1 /* spmm_window6_kernel<G, NH> */, TILED_LANES = 2 /* spmm_lanes_kernel<NC, CP, G, LPE> */ };
+struct SpmmStage2 {
+    // 1. the LDS-tiled kernel on the panels that qualify
+    int tiled = TILED_NONE;
+    int g = 0;                  // groups of four rows per wave (either kernel)
+    int nh = 0, grid_y = 0;     // spmm_window6_kernel: 64-column halves per workgroup, workgroups along the columns
+    int nc = 0, cp = 0, lpe = 0; // spmm_lanes_kernel: staged columns, copies of a Bt row in the tile, lanes per entry
+    // 2. the matrix-core kernel on its panels (spmm_mfma_kernel)
+    bool mfma = false;
+    int mfma_batch = 0;         // operand blocks per stage
+    size_t mfma_lds_floor = 0;  // least dynamic LDS (0: what the panel needs)
+    // 3. the direct kernels on the rest, in this order; classified calls at 128+ columns launch up to three of them and
+    // the device-side vote picks (voted), everywhere else exactly one runs
+    bool four_rows = false;     // spmm_direct_rows_kernel<WV>
+    int rows_waves = 0, voted = 0;
+    bool merge = false;         // spmm_direct_merge_kernel
+    int dpp = 0;                // spmm_direct_dpp_kernel<GROUPS>: 1, 2 or 4 (0: not launched)
+    size_t dpp_pad = 0;         // ... its dynamic LDS pad
+    int dpp_long = 0;           // ... entries from which the whole workgroup computes a row
+    int narrow = 0;             // spmm_rowpanel_narrow_kernel<8 | 16 | 32> (0: not launched)
+    bool rows8 = false;         // spmm_rows8_kernel
+    int interleave = -1;        // panel map of the direct kernels: 1 interleave, 0 contiguous, -1 by the classifier's span
+    // 4. a split plan: the direct kernels above in their SKIP instantiations, then spmm_split_piece_kernel<GROUPS> + fold
+    bool skip = false;
+    int split_groups = 0;
+};
+SpmmStage2 spmm_stage2(const SpmmStep &st, int rows, int cols, int64_t nnz, int n);
 // Layouts of the dense operands: row_b = B is row-major (cols x n, B[k * ldb + j]; only the staging launchers read B),
 // row_c = C is row-major (rows x n, C[r * ldc + j]; the stage-2 epilogues, the scale and the merge kernels).
 hipError_t launch_stage(hipStream_t s, const SpmmStep &st, int rows, int64_t cols, int64_t nnz, const int *rowptr,

@@ -1,6 +1,6 @@
 // kernels.hip -- hand-written gfx950 (CDNA4, wave64) SpMM kernels of the S-BLAS CSR hot path.
 //
-// SpMM  C = alpha*A*B + beta*C   (stage 1 + stage 2; the launcher at the end of this file picks the kernels)
+// SpMM  C = alpha*A*B + beta*C   (stage 1 + stage 2; spmm_rule.cpp picks the kernels, the launchers at the end of this file run them)
 //   dense_to_rowmajor_kernel     B (col-major) -> Bt (row-major, zero padded, one all-zero row)          [stage 1]
 //   stage_classify_kernel        stage 1 + classify_panels_kernel in one launch (fused C-ABI entry)
 //   classify_panels_kernel       per row panel: column span and class (LDS-tiled / direct / matrix cores), shared-rows flag
@@ -26,11 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
-#include <string.h>
-#include <stdio.h>
 #include <mutex>
 #include <vector>
 #include "kernels.h"
@@ -275,7 +272,6 @@ constexpr int PANEL_ROWS = 32;   // narrow kernels (256 threads)
 constexpr int WIDE_WAVES = 16;
 constexpr int WIDE_ROWS_PER_WAVE = 1;
 constexpr int WIDE_PANEL = WIDE_WAVES * WIDE_ROWS_PER_WAVE;
-constexpr int DPP_LONG = 4096;            // entries from which a row of the row-per-wave kernel is computed by the whole workgroup
 
 // (xcd_contiguous_panel, the map of workgroups to panels, lives in kernels.h: sddmm.hip uses it too)
 
@@ -335,14 +331,7 @@ constexpr size_t W2_LDS_BYTES = (2 * (size_t)W2_TILE + 64) * sizeof(double) + 64
 //             PANEL_DIRECT  everything else.
 // bitmap: MFMA_BITMAP_WORDS ints of LDS per wave (one bit per 4-column block of the sampled rows' span).
 constexpr int MFMA_BITMAP_WORDS = 1024; // 32768 blocks = 131072 columns of span
-// The classifier's thresholds (classify_args): the longest row a windowed panel may hold (32-bit buffer offsets inside a
-// wave's rows), nonzeros per spanned column and per row a panel needs for the LDS-tiled kernel, the block fill from which
-// it takes the matrix cores (> 1: never), what to probe for the direct kernels' sake (bit 0 row-merging, bit 1 row per wave).
-struct ClassifyArgs {
-    int max_row_len;
-    float min_density, min_rowlen, mfma_min_fill;
-    int merge_probe;
-};
+// (the classifier's thresholds, ClassifyArgs: kernels.h; their values: classify_args, spmm_rule.cpp)
 __device__ __forceinline__ void classify_panel(int p, int rows, int cols, int npanels, int panel_rows,
                                                const int *__restrict__ rowptr, const int *__restrict__ colidx,
                                                ClassifyArgs a, int *__restrict__ tail, int2 *__restrict__ info,
@@ -809,7 +798,6 @@ __device__ __forceinline__ void dma_rows_vector(unsigned lds_addr, const char *a
 }
 
 static_assert(4 * 4 * 2 >= SPMM_MIN_PANEL_ROWS, "the workspace reserves one verdict per SPMM_MIN_PANEL_ROWS rows");
-constexpr int W6_GMAX = 3;                   // groups of four rows per wave: 2 or 3 (template parameter)
 
 
 // tile membership for one 16-entry half of the four windows; all per-lane (k = lane & 15 is the entry number inside
@@ -2414,7 +2402,7 @@ hipError_t validate_csr(hipStream_t s, int64_t rows, int64_t cols, int64_t nnz, 
 }
 
 // compute units of the current device (queried once per device)
-static int compute_units()
+int compute_units()
 {
     static std::atomic<int> cached[16]; // (zero-initialised; any thread may fill a slot, all write the same value)
     int dev = 0;
@@ -2455,72 +2443,6 @@ hipError_t kernel_events_last_ms(float *ms)
     return hipEventElapsedTime(ms, g_kev[dev].a, g_kev[dev].b);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Experiment / test switches.  The environment is read ONCE (first launch) into this struct; tests that change a
-// switch inside one process call sblas_hip_debug_reload_env() afterwards.  Nothing here changes results.
-// ---------------------------------------------------------------------------------------------
-static Options g_options;
-static std::atomic<bool> g_options_loaded{false};
-static std::mutex g_options_mu;
-static void options_parse(Options &o)
-{
-    o = Options{};
-    const char *e;
-    if ((e = getenv("SBLAS_SPMM_VARIANT")) && *e) {
-        if (!strcmp(e, "dpp")) o.spmm_variant = SPMM_VARIANT_DIRECT_DPP;
-        else if (!strcmp(e, "rows")) o.spmm_variant = SPMM_VARIANT_DIRECT_ROWS;
-        else if (!strcmp(e, "lanes")) o.spmm_variant = SPMM_VARIANT_LANES;
-        else if (!strcmp(e, "merge")) o.spmm_variant = SPMM_VARIANT_DIRECT_MERGE;
-        else if (!strcmp(e, "mfma")) o.spmm_variant = SPMM_VARIANT_MFMA;
-        else if (!strcmp(e, "nomfma")) o.spmm_variant = SPMM_VARIANT_NO_MFMA;
-    }
-    if ((e = getenv("SBLAS_SPMV_VARIANT")) && *e && strcmp(e, "auto")) {
-        strncpy(o.spmv_variant, e, sizeof o.spmv_variant - 1);
-    }
-    if ((e = getenv("SBLAS_SPMM_MIN_LDBT")) && *e) o.tier16 = o.tier32 = atoi(e) < 64;
-    if ((e = getenv("SBLAS_SPMM_MAX_BT_BYTES")) && *e) {
-        const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v >= 4096 && v < 0xffffffffull) o.max_bt_bytes = v;
-    }
-    if ((e = getenv("SBLAS_DIRECT_LDS")) && *e) o.direct_lds = atoi(e);
-    if ((e = getenv("SBLAS_DIRECT_MERGE")) && *e) o.direct_merge = atoi(e);
-    if ((e = getenv("SBLAS_STAGE_RANGE")) && *e) o.stage_range = atoi(e);
-    if ((e = getenv("SBLAS_DIRECT_MAP")) && *e) o.direct_map = !strcmp(e, "interleave") ? 1 : !strcmp(e, "contiguous") ? 0 : -1;
-    if ((e = getenv("SBLAS_ROWS8_MIN_AVG")) && *e) o.rows8_min_avg = atof(e);
-    if ((e = getenv("SBLAS_WINDOW_DENSITY")) && *e) o.window_density = (float)atof(e);
-    if ((e = getenv("SBLAS_SPMM_PANEL_ROWS")) && *e) { /* "<rows>" or "<rows>,<groups>" */
-        o.panel_rows = atoi(e);
-        o.panel_groups = strchr(e, ',') ? atoi(strchr(e, ',') + 1) : 0;
-    }
-    if ((e = getenv("SBLAS_MFMA_MIN_FILL")) && *e) o.mfma_min_fill = (float)atof(e);
-    if ((e = getenv("SBLAS_VALIDATE")) && *e) o.validate = atoi(e) != 0;
-    if ((e = getenv("SBLAS_TUNE")) && *e) { /* "a,b,c,d" (or "a:b:c:d"): free integers for kernel experiments */
-        char buf[96];
-        strncpy(buf, e, sizeof buf - 1);
-        buf[sizeof buf - 1] = 0;
-        for (char *c = buf; *c; ++c)
-            if (*c == ':') *c = ',';
-        sscanf(buf, "%d,%d,%d,%d", &o.tune[0], &o.tune[1], &o.tune[2], &o.tune[3]);
-    }
-}
-const Options &options()
-{
-    if (!g_options_loaded.load(std::memory_order_acquire)) {
-        std::lock_guard<std::mutex> lock(g_options_mu);
-        if (!g_options_loaded.load(std::memory_order_relaxed)) {
-            options_parse(g_options);
-            g_options_loaded.store(true, std::memory_order_release);
-        }
-    }
-    return g_options;
-}
-void options_reload()
-{
-    std::lock_guard<std::mutex> lock(g_options_mu);
-    options_parse(g_options);
-    g_options_loaded.store(true, std::memory_order_release);
-}
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: raise it once per (kernel, device), not per launch
 void raise_dynamic_lds(const void *fn, size_t bytes)
 {
@@ -2540,81 +2462,6 @@ void raise_dynamic_lds(const void *fn, size_t bytes)
     seen.push_back({fn, dev, bytes});
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-
-// Sixth generation, one workgroup per CU at a time: the groups per wave (2 or 3) and the panel height (a multiple of
-// the rows of a wave) that minimise rounds x (height + per-tile fixed cost).
-static void gen6_plan(int rows, int &info_rows, int &gen6_g, int gmax = W6_GMAX)
-{
-    const int ncu = compute_units();
-    int best = 128;
-    long best_cost = -1;
-    gen6_g = 2;
-    for (int g = 2; g <= gmax; ++g)
-        for (int r = 12 * 4 * g; r >= 4 * 4 * g; r -= 4 * g) {
-            const long panels = (rows + r - 1) / r;
-            // measured on the bench matrix: three groups per wave cost ~15 % more per row
-            const long cost = ((panels + ncu - 1) / ncu) * (long)(r + 40) * (g == 3 ? 23 : 20);
-            if (best_cost < 0 || cost < best_cost) {
-                best_cost = cost;
-                best = r;
-                gen6_g = g;
-            }
-        }
-    info_rows = best;
-    const Options &opt = options();
-    if (opt.panel_rows > 0) { /* experiments */
-        const int r = opt.panel_rows, g = opt.panel_groups ? opt.panel_groups : (r % 12 == 0 && r > 128 ? 3 : 2);
-        if (g >= 2 && g <= gmax && r >= SPMM_MIN_PANEL_ROWS && r <= 48 * g && r % (4 * g) == 0) { // (workspace: a verdict per 32 rows)
-            info_rows = r;
-            gen6_g = g;
-        }
-    }
-}
-
-// Panel height of the narrow LDS-tiled kernel: twelve consumer waves of G groups of four rows; G is capped by the
-// registers NC accumulators per group take (8 columns: 3, 16 and 32: 1).
-static void lanes_plan(int rows, int ldbt, int &info_rows, int &groups)
-{
-    const int ncu = compute_units();
-    const int gmax = ldbt <= 8 ? 3 : ldbt <= 16 ? (options().tune[0] == 2 ? 2 : 3) : options().tune[3] != 1 ? 2 : 1;
-    long best_cost = -1;
-    info_rows = 48;
-    groups = 1;
-    // 8 columns: one group of rows per wave, two workgroups per CU (see spmm_lanes_kernel); SBLAS_SPMM_PANEL_ROWS overrides
-    for (int g = 1; g <= gmax && ldbt > 8; ++g)
-        for (int r = 12 * 4 * g; r >= 4 * 4 * g; r -= 4 * g) {
-            if (r < SPMM_MIN_PANEL_ROWS) continue;
-            const long panels = (rows + r - 1) / r;
-            const long cost = ((panels + ncu - 1) / ncu) * (long)(r + 40);
-            if (best_cost < 0 || cost < best_cost) {
-                best_cost = cost;
-                info_rows = r;
-                groups = g;
-            }
-        }
-    const Options &opt = options();
-    if (opt.panel_rows > 0) { /* experiments */
-        const int r = opt.panel_rows, g = opt.panel_groups ? opt.panel_groups : 1;
-        if (g >= 1 && g <= gmax && r >= SPMM_MIN_PANEL_ROWS && r <= 48 * g && r % (4 * g) == 0) {
-            info_rows = r;
-            groups = g;
-        }
-    }
-}
-
-// the panel height the classifier and the stage-2 kernels of a call agree on
-static void panel_plan(int rows, int64_t ldbt, int &info_rows, int &groups)
-{
-    if (ldbt < 64) lanes_plan(rows, (int)ldbt, info_rows, groups);
-    // (128+ staged columns: two column halves per workgroup, whose accumulators leave room for two groups per wave)
-    // (... and so does SBLAS_SPMM_VARIANT=mfma at 64 columns: the matrix-core kernel takes panels of up to 16 rows x
-    //  MFMA_MAX_WAVES, and three groups per wave would give 132- / 144-row panels it silently leaves alone: ADVICE r2)
-    else gen6_plan(rows, info_rows, groups,
-                   ((ldbt >= 128 && options().tune[1] != 1) || options().spmm_variant == SPMM_VARIANT_MFMA) ? 2 : W6_GMAX);
-}
-
-static std::atomic<int> g_epoch{1}; // tags one call's classifier verdicts and one staging pass (see classify_panel)
-static int next_epoch() { return g_epoch.fetch_add(1, std::memory_order_relaxed); }
 
 // The workspace behind the staging copy (kernels.h): header ints, one span per panel, one class per panel.
 struct Tail {
@@ -2645,55 +2492,6 @@ size_t workspace_tail_bytes(int64_t rows)
     const size_t panels = ((size_t)(rows > 0 ? rows : 0) + SPMM_MIN_PANEL_ROWS - 1) / SPMM_MIN_PANEL_ROWS;
     return (TAIL_HDR * sizeof(int) + TAIL_PARTS * sizeof(int2) + panels * (sizeof(int2) + sizeof(int)) + 31) / 16 * 16; // whole 16-byte units
 }
-// block fill from which a panel goes to the matrix cores (fp64 MFMA and fp64 vector FMA have the same peak on gfx950,
-// so the zero fill of a block is paid in full): measured break-even against the vector kernels, tools/spmm_shapes.py blocks:ROWS:FILL
-// Nonzeros a panel must hold per column of its span to take the LDS-tiled kernel: every row of a B tile it loads is then
-// used that many times on average.  0.42 per 16 rows = 2.5 uses for a 96-row panel -- measured on banded rows, 1 M
-// rows, N = 64 (tools/spmm_shapes.py banded:ROWS:PERROW:HALFBAND with SBLAS_WINDOW_DENSITY): at 1.4 uses the direct
-// kernel wins by 36 %, at 2.1-2.4 the two are within 5 %, from 2.75 on the LDS-tiled kernel wins (6 % ... 70 % at 6 uses,
-// where round 1's bar stood).
-static float window_min_density(int panel_rows) { return options().window_density * (float)panel_rows / 16.0f; }
-// Nonzeros per row a panel must average to take the narrow LDS-tiled kernel (0 at 64+ staged columns).  Measured on banded rows
-// (tools/spmm_shapes.py banded:ROWS:PERROW:HALFBAND, 1 M rows) against the kernels that take the panel otherwise:
-// gpurun_out/r3_narrow_shapes*.txt, DESIGN 3.9.
-// A narrow call whose rows average less than three quarters of the bar does not classify at all: the classifier,
-// an LDS-tiled launch that every workgroup leaves at once and the per-row ownership test of the direct kernel cost a
-// 1 M-row matrix of 5 nonzeros per row 0.23 ms of a 0.09 ms product (N = 8).
-static float window_min_rowlen(int64_t ldbt);
-// what the classifier looks at for the direct kernels' sake (128+ staged columns): bit 0 rows that share column patterns
-// (row-merging kernel), bit 1 column runs / row-length spread (row per wave or four rows per wave)
-static int direct_probe(int64_t ldbt) { return ldbt >= 128 ? (options().direct_merge ? 3 : 2) : 0; }
-static bool classify_worthwhile(int64_t rows, int64_t nnz, int64_t ldbt)
-{
-    // (128+ staged columns: the classifier also feeds the matrix-core and row-merging choices; a forced matrix-core run
-    //  needs its verdicts at any width)
-    return ldbt >= 128 || (ldbt >= 64 && options().spmm_variant == SPMM_VARIANT_MFMA) || (rows > 0 && (double)nnz >= 0.75 * (double)window_min_rowlen(ldbt) * (double)rows);
-}
-static float window_min_rowlen(int64_t ldbt)
-{
-    const int t = options().tune[1];
-    if (t > 1) return (float)t; /* SBLAS_TUNE=*,<nonzeros per row>: threshold sweeps */
-    // 64+ columns, banded rows, 1 M rows, LDS-tiled kernel | four rows per wave (ms): N = 64: 5 per row .737 | .565, 16: .796 | .669,
-    // 24: .849 | .804, 32: .924 | .944, 48: 1.06 | 1.22; N = 256: 16: 3.01 | 2.65, 24: 3.17 | 3.20, 32: 3.41 | 3.76
-    if (ldbt >= 64) return 24.0f;
-    // banded rows, 1 M rows, LDS-tiled kernel | lane groups (ms): N = 8: 27 per row .418 | .283, 40: .464 | .377, 60: .524 | .547,
-    // 80: .466 | .554; N = 16: 10: .452 | .287, 27: .483 | .540; N = 32: 10: .672 | .553, 27: .711 | 1.04
-    return ldbt <= 8 ? 56.0f : ldbt <= 16 ? 20.0f : 16.0f;
-}
-static float mfma_min_fill(int variant, int panel_rows, int64_t ldbt)
-{
-    if (panel_rows > 16 * MFMA_MAX_WAVES) return 2.0f; // the matrix-core kernel runs one wave per 16 rows of a panel
-    if (variant == SPMM_VARIANT_MFMA) return 0.0f;
-    if (variant == SPMM_VARIANT_NO_MFMA) return 2.0f;
-    // Measured (tools/spmm_shapes.py): a chunk step of the matrix-core kernel costs ~2600 cycles of
-    // instruction issue whatever the width, so it needs 128+ dense columns (8+ MFMAs per block) to pay: block-
-    // structured rows at 60 % fill, N = 128: 0.57 ms against 0.65 ms for the LDS-tiled kernel; N = 64: 0.40 against
-    // 0.31 ms; N = 256 at 35 % fill: 1.55 against 1.29 ms; grid-structured Queen-like rows (fill 0.32), N = 256: 2.33
-    // against 2.16 ms for the direct kernel.  64-column calls therefore never take it unless SBLAS_MFMA_MIN_FILL says so.
-    const float f = options().mfma_min_fill;
-    if (f >= 0.0f) return f;
-    return ldbt >= 128 ? 0.5f : 2.0f;
-}
 
 // the whole of B into Bt, stamps into hdr (the workspace's or a plan's header)
 template <bool RB>
@@ -2720,70 +2518,6 @@ hipError_t launch_dense_to_rowmajor(hipStream_t s, int64_t cols, int64_t n, cons
     if (row_b) launch_stage_full<true>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
     else launch_stage_full<false>(s, cols, n, B, ldb, Bt, ldbt, hdr, epoch);
     return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// What a column chunk of an SpMM call does before stage 2, decided once (spmm_step) and carried out by launch_stage and
-// launch_spmm_rowpanel.  A plan (sblas_hip_spmm_plan_create) keeps the verdicts of the decision it asked for here.
-// ---------------------------------------------------------------------------------------------
-// SBLAS_SPMM_VARIANT: "dpp" and "rows" pin a direct kernel at every width, "merge" at 64+ staged columns (where the
-// row-merging kernel exists) and "lanes" at narrow ones (the lane-group kernel): no panel is classified there
-static bool variant_classifies(int v, int64_t ldbt)
-{
-    return v != SPMM_VARIANT_DIRECT_DPP && v != SPMM_VARIANT_DIRECT_ROWS &&
-           v != (ldbt >= 64 ? SPMM_VARIANT_DIRECT_MERGE : SPMM_VARIANT_LANES);
-}
-// ... and only the variants that pin no kernel at any width take a plan
-static bool variant_plannable(int v)
-{
-    return v == SPMM_VARIANT_AUTO || v == SPMM_VARIANT_MFMA || v == SPMM_VARIANT_NO_MFMA;
-}
-// a staging copy of ldbt columns beyond the 32-bit byte offsets the 16- / 32-column direct kernel addresses Bt with
-static bool bt_beyond_32bit(int64_t cols, int64_t ldbt) { return ((uint64_t)cols + 1) * (uint64_t)ldbt * 8ull > 0xffffffffull; }
-// Staging traffic saved if a row block's columns span no more than twice its rows, against the extra pass over the column
-// indices and one more launch (~5 us = 40 MB at staging speed; a quarter of nd24k at N = 128 breaks even, an eighth of a
-// Queen-like matrix at N = 256 runs 1.5x faster: tools/spmm_shapes.py --block)
-static bool range_staging_pays(int64_t rows, int64_t cols, int64_t nnz, int64_t ldbt)
-{
-    return cols > 2 * rows && (uint64_t)(cols - 2 * rows) * (uint64_t)ldbt * 16ull > (uint64_t)nnz * 8ull + (40ull << 20);
-}
-static int range_parts(int64_t nnz) { return (int)std::max<int64_t>(1, std::min<int64_t>((nnz + 4095) / 4096, TAIL_PARTS)); }
-static ClassifyArgs classify_args(int panel_rows, int64_t ldbt)
-{
-    return {1 << 24, window_min_density(panel_rows), window_min_rowlen(ldbt),
-            ldbt < 64 ? 2.0f : mfma_min_fill(options().spmm_variant, panel_rows, ldbt), direct_probe(ldbt)};
-}
-
-SpmmStep spmm_step(int rows, int cols, int64_t nnz, int64_t ldbt, const PlanView *pv, const SpmmStep &prev, bool caller_staged)
-{
-    SpmmStep st;
-    st.ldbt = ldbt;
-    st.pv = pv;
-    if (pv) { // classified, voted on and counted once: only B is left to stage
-        st.staging = STAGE_PLANNED, st.verdicts = VERDICTS_PLAN;
-        st.info_rows = pv->info_rows, st.groups = pv->groups, st.epoch = pv->epoch;
-        st.npanels = (rows + st.info_rows - 1) / st.info_rows;
-        return st;
-    }
-    const Options &opt = options();
-    const bool classify = variant_classifies(opt.spmm_variant, ldbt) && (ldbt >= 64 || !bt_beyond_32bit(cols, ldbt)) &&
-                          classify_worthwhile(rows, nnz, ldbt);
-    // a row block (method 2): the row-major copy covers only the rows of B the block's nonzeros refer to
-    const bool range = !caller_staged && ldbt >= 64 &&
-                       (opt.stage_range > 0 || (opt.stage_range < 0 && range_staging_pays(rows, cols, nnz, ldbt)));
-    // the classifier rides in the staging launch (one launch and one gap less per call) wherever there is one
-    st.staging = caller_staged ? STAGE_CALLER : range ? STAGE_RANGE : classify ? STAGE_FUSED : STAGE_FULL;
-    st.plannable = classify && !caller_staged && variant_plannable(opt.spmm_variant);
-    if (classify) {
-        panel_plan(rows, ldbt, st.info_rows, st.groups);
-        st.npanels = (rows + st.info_rows - 1) / st.info_rows;
-    }
-    // a later column chunk of a range-staged call (same A, same ldbt, same workspace): the column range and the panel
-    // verdicts in the tail still stand, only B's next columns need staging
-    const bool again = classify && range && prev.staging == STAGE_RANGE && prev.verdicts != VERDICTS_NONE && prev.ldbt == ldbt;
-    st.verdicts = !classify ? VERDICTS_NONE : again ? VERDICTS_EARLIER : caller_staged ? VERDICTS_SEPARATE : VERDICTS_STAGING;
-    st.epoch = again ? prev.epoch : next_epoch();
-    return st;
 }
 
 // the column-range pass of a row block, with the panel classifier riding along (both read only A)
@@ -2922,221 +2656,150 @@ hipError_t plan_build(hipStream_t s, const SpmmStep &st, int rows, int cols, int
         }                                                                                                             \
     } while (0)
 
-// the four-rows-per-wave direct kernel.  Workgroups of 4 waves (16 rows) for the shortest rows, 16 waves (64 rows) otherwise:
-// 1 M banded rows of 5 / 10 / 20 / 32 per row, N = 64, 4 | 8 | 16 waves: 0.547 | 0.554 | 0.571, 0.632 | 0.613 | 0.617, 0.973 |
-// 0.936 | 0.912, 1.22 | 1.17 | 1.14 ms; power-law rows averaging 3.2 (a 64-row workgroup waits for its longest row): 0.740 |
-// 0.830 | 0.957 ms.  (SBLAS_TUNE=*,*,*,<4|8|16> pins the size: A/B runs)
-template <bool RC>
-static void launch_direct_rows(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
-                               const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
-                               const int *hdr, const int *cls, int info_rows, int interleave, int epoch, int voted,
-                               double avg_row, const unsigned *skip)
-{
-    const int pin = options().tune[3];
-    const int wv = pin == 4 || pin == 8 || pin == 16 ? pin : avg_row < 8.0 ? 4 : 16;
-    const int rp = (rows + 4 * wv - 1) / (4 * wv);
-    const dim3 grid((unsigned)rp, (unsigned)(ldbt / 64));
-#define SBLAS_ROWS_GO(WV)                                                                                             \
-    SBLAS_DIRECT_GO(spmm_direct_rows_kernel, (WV, RC), grid, dim3(WV * 64), 0, rows, cols, rp, rowptr, colidx, val, Bt, ldbt, \
-                    n, alpha, beta, C, ldc, hdr, cls, info_rows, interleave, epoch, voted)
-    if (wv == 4) SBLAS_ROWS_GO(4);
-    else if (wv == 8) SBLAS_ROWS_GO(8);
-    else SBLAS_ROWS_GO(16);
-#undef SBLAS_ROWS_GO
-}
-
-// the split rows of a split plan, after the direct kernels (which left them alone) on the same stream
-template <bool RC>
-static void launch_split(hipStream_t s, int cols, const int *colidx, const double *val, const double *Bt, int64_t ldbt, int n,
-                         double alpha, double beta, double *C, int64_t ldc, const PlanView &pv)
-{
-    const unsigned pieces = (unsigned)pv.n_pieces;
-    if (ldbt >= 128)
-        hipLaunchKernelGGL(spmm_split_piece_kernel<1>, dim3(pieces, (unsigned)((n + 127) / 128)), dim3(WIDE_WAVES * 64), 0, s,
-                           pv.pieces, cols, colidx, val, Bt, ldbt, n, pv.partial);
-    else if (ldbt == 64)
-        hipLaunchKernelGGL(spmm_split_piece_kernel<2>, dim3(pieces), dim3(WIDE_WAVES * 64), 0, s, pv.pieces, cols, colidx, val,
-                           Bt, ldbt, n, pv.partial);
-    else
-        hipLaunchKernelGGL(spmm_split_piece_kernel<4>, dim3(pieces), dim3(WIDE_WAVES * 64), 0, s, pv.pieces, cols, colidx, val,
-                           Bt, ldbt, n, pv.partial);
-    hipLaunchKernelGGL(spmm_split_fold_kernel<RC>, dim3((unsigned)pv.n_split, (unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                       pv.srows, pv.partial, ldbt, n, alpha, beta, C, ldc);
-}
-
+// Stage 2 of a chunk: walks the descriptor spmm_stage2 (spmm_rule.cpp) filled, in its order.  Nothing is decided here:
+// every kernel family appears once, dispatched on the template arguments the descriptor names; arguments without an
+// instantiation are an error.
 template <bool RC>
 static hipError_t spmm_rowpanel(hipStream_t s, const SpmmStep &st, int rows, int cols, int64_t nnz, const int *rowptr,
                                 const int *colidx, const double *val, const double *Bt, int n, double alpha, double beta,
                                 double *C, int64_t ldc)
 {
-    const Options &opt = options();
-    const int variant = opt.spmm_variant;
+    const SpmmStage2 d = spmm_stage2(st, rows, cols, nnz, n);
     const int64_t ldbt = st.ldbt;
     const PlanView *pv = st.pv;
-    const double avg_row = rows > 0 ? (double)nnz / (double)rows : 0.0;
-    const int dpp_long = opt.tune[2] > 0 ? opt.tune[2] : DPP_LONG; // (SBLAS_TUNE=*,*,<entries>: A/B runs of the long-row split)
-    // a planned call (pv): the verdicts sit in the plan's buffer, nothing is classified or voted on, and only the kernels
-    // that have panels are launched
-    const bool need_window = !pv || pv->n_window + pv->n_mfma_w > 0;
-    const bool need_mfma = !pv || pv->n_mfma_w + pv->n_mfma_d > 0;
-    const bool need_direct = !pv || pv->n_direct + pv->n_mfma_d > 0;
-    // a split plan: the direct kernels' SKIP instantiations, then the split kernels
-    const unsigned *skip = pv && pv->n_split > 0 ? pv->split_bits : nullptr;
+    // a planned call (pv): the verdicts sit in the plan's buffer, nothing is classified or voted on
     const Tail t = pv ? tail_at(pv->tail, rows) : tail_of(Bt, cols, ldbt, rows);
-    // 1. the panel verdicts (spmm_step says where they come from); 2. LDS-tiled kernel and matrix-core kernel on the
-    // panels that qualify; 3. a direct kernel on the rest -- on everything when nothing is classified
     const bool classified = st.verdicts != VERDICTS_NONE;
     const int *cls = classified ? t.cls : nullptr;
     const int info_rows = st.info_rows, np = st.npanels, epoch = st.epoch;
+    const unsigned *skip = d.skip ? pv->split_bits : nullptr;
+    bool missing = false; // the descriptor names template arguments that have no instantiation
     if (classified && !pv) launch_verdicts(s, st, rows, cols, rowptr, colidx, t, st.verdicts == VERDICTS_SEPARATE);
-    if (ldbt >= 64) {
-        if (classified) {
-            const bool mfma_possible = mfma_min_fill(variant, info_rows, ldbt) <= 1.0f;
-            // 128+ staged columns: two 64-column halves per workgroup, the selection work of a (rows, tile) visit shared
-            // (SBLAS_TUNE=*,1 keeps one half per workgroup: A/B runs)
-            const bool two_halves = ldbt >= 128 && opt.tune[1] != 1;
-            dim3 wgrid((unsigned)np, (unsigned)(ldbt / (two_halves ? 128 : 64)));
-            KernelEvents *kev = kernel_events_slot();
-            if (kev) (void)hipEventRecord(kev->a, s);
-#define SBLAS_LAUNCH_W6(GG, NH)                                                                                        \
-    do {                                                                                                              \
+
+    // 1. the LDS-tiled kernel, between the kernel events
+    if (classified) {
+        KernelEvents *kev = kernel_events_slot();
+        if (kev) (void)hipEventRecord(kev->a, s);
+        if (d.tiled == TILED_WINDOW6) {
+            const dim3 wgrid((unsigned)np, (unsigned)d.grid_y);
+#define SBLAS_W6_CASE(GG, NH)                                                                                          \
+    case GG * 10 + NH:                                                                                                \
         raise_dynamic_lds((const void *)spmm_window6_kernel<GG, NH, RC>, W2_LDS_BYTES);                               \
         hipLaunchKernelGGL((spmm_window6_kernel<GG, NH, RC>), wgrid, dim3(1024), W2_LDS_BYTES, s, rows, cols, np, rowptr,   \
                            colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, t.info, t.cls, info_rows, (int)nnz); \
-    } while (0)
-            if (!need_window) {
-            } else if (st.groups == 3) {
-                SBLAS_LAUNCH_W6(3, 1);
-            } else {
-                if (two_halves) SBLAS_LAUNCH_W6(2, 2); else SBLAS_LAUNCH_W6(2, 1);
+        break;
+            switch (d.g * 10 + d.nh) {
+                SBLAS_W6_CASE(2, 1) SBLAS_W6_CASE(2, 2) SBLAS_W6_CASE(3, 1)
+            default: missing = true;
             }
-#undef SBLAS_LAUNCH_W6
-            if (kev) {
-                (void)hipEventRecord(kev->b, s);
-                kev->recorded = true;
-            }
-            if (mfma_possible && need_mfma) {
-                const hipError_t e = launch_spmm_mfma(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc,
-                                                      t.info, t.hdr, t.cls, info_rows, np, epoch, panel_stats_device(), RC);
-                if (e != hipSuccess) return e;
-            }
-        }
-        const int wide_panels = (rows + WIDE_PANEL - 1) / WIDE_PANEL;
-        // 128-column tiles: one workgroup per CU through unused dynamic LDS (Queen-like rows at N = 256: +13 %, banded
-        // matrix at N = 128: +3 %); SBLAS_DIRECT_LDS overrides (experiments: rows in flight vs L2 reach)
-        const size_t pad = opt.direct_lds >= 0 ? (size_t)opt.direct_lds : (ldbt == 64 ? 0 : 90000);
-        const int interleave = opt.direct_map; // -1: by the span the classifier recorded
-        if (!need_direct) {
-        } else if (n > 32 && (variant == SPMM_VARIANT_DIRECT_ROWS ||
-                              (variant != SPMM_VARIANT_DIRECT_DPP && avg_row < (ldbt == 64 ? 56.0 : 32.0)))) {
-            // short rows: four rows per wave (64 staged columns, banded rows, 1 M rows, against the lane-group kernel: 32 per
-            // row 1.08 | 1.14 ms, 48: 1.41 | 1.54, 64: 1.75 | 1.70, 100: 2.57 | 2.49)
-            launch_direct_rows<RC>(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                               interleave, epoch, 0, avg_row, skip);
-        } else if (ldbt == 64 && n <= 32) {
-            SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (4, RC), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, rows,
-                            cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                            interleave, epoch, dpp_long);
-        } else if (ldbt == 64) {
-            SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (2, RC), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), pad, rows,
-                            cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                            interleave, epoch, dpp_long);
-        } else {
-            // 128-column tiles.  Classified calls launch both direct kernels: the classifier's vote (device side) says
-            // whether the rows share column patterns, and the kernel whose call it is not leaves on one scalar load.
-            const bool merge = pv ? pv->merge : variant == SPMM_VARIANT_DIRECT_MERGE || (cls != nullptr && opt.direct_merge);
-            const bool plain = pv ? !pv->merge && !pv->four_rows : variant != SPMM_VARIANT_DIRECT_MERGE;
-            // ... and whether four rows per wave on 64-column tiles suit them better than a row per wave on 128-column tiles
-            const bool four = pv ? pv->four_rows : cls != nullptr && variant != SPMM_VARIANT_DIRECT_MERGE;
-            if (four) {
-                launch_direct_rows<RC>(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                                   interleave, epoch, pv ? 0 : 1, avg_row, skip);
-            }
-            if (merge) {
-                // rows that share their column pattern (multi-dof FEM): three rows per wave, shared Bt loads
-                const int mp = (rows + MERGE_PANEL - 1) / MERGE_PANEL;
-                const size_t lds = (size_t)128 * (MERGE_PANEL + 1) * sizeof(double);
-                raise_dynamic_lds((const void *)spmm_direct_merge_kernel<RC>, lds);
-                hipLaunchKernelGGL(spmm_direct_merge_kernel<RC>, dim3((unsigned)mp, (unsigned)(ldbt / 128)),
-                                   dim3(MERGE_WAVES * 64), lds, s, rows, cols, mp, rowptr, colidx, val, Bt, ldbt, n, alpha,
-                                   beta, C, ldc, t.hdr, cls, info_rows, interleave, epoch);
-            }
-            if (plain)
-                SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (1, RC), dim3((unsigned)wide_panels, (unsigned)(ldbt / 128)),
-                                dim3(WIDE_WAVES * 64), pad, rows, cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta,
-                                C, ldc, t.hdr, cls, info_rows, interleave, epoch, dpp_long);
-        }
-    } else {
-        // ---- narrow dense blocks (ldbt = 8 / 16 / 32): LDS-tiled lane-per-entry kernel on the panels that qualify,
-        // a direct kernel on the rest
-        // the 16- / 32-column direct kernel addresses Bt with 32-bit byte offsets
-        const bool wide_offsets = bt_beyond_32bit(cols, ldbt);
-        if (classified) {
-            const int g = st.groups;
-            KernelEvents *kev = kernel_events_slot();
-            if (kev) (void)hipEventRecord(kev->a, s);
-#define SBLAS_LAUNCH_LANES(NC, CP, GG) SBLAS_LAUNCH_LANES4(NC, CP, GG, 1)
-#define SBLAS_LAUNCH_LANES4(NC, CP, GG, LPE)                                                                           \
-    do {                                                                                                              \
+#undef SBLAS_W6_CASE
+        } else if (d.tiled == TILED_LANES) {
+#define SBLAS_LANES_CASE(NC, CP, GG, LPE)                                                                              \
+    case ((NC * 10 + CP) * 10 + GG) * 10 + LPE:                                                                       \
         raise_dynamic_lds((const void *)spmm_lanes_kernel<NC, CP, GG, LPE, RC>, WlGeom<NC, CP>::LDS_BYTES);           \
         hipLaunchKernelGGL((spmm_lanes_kernel<NC, CP, GG, LPE, RC>), dim3((unsigned)np), dim3(1024), (WlGeom<NC, CP>::LDS_BYTES), s, \
                            rows, cols, np, rowptr, colidx, val, Bt, n, alpha, beta, C, ldc, t.hdr, t.info, t.cls,      \
                            info_rows, (int)nnz);                                                                      \
-    } while (0)
-            const int cp = opt.tune[0]; /* experiments: copies of a Bt row in the LDS tile */
-            if (!need_window) {
-            } else if (ldbt == 8) {
-                if (cp == 4) { if (g == 3) SBLAS_LAUNCH_LANES(8, 4, 3); else if (g == 2) SBLAS_LAUNCH_LANES(8, 4, 2); else SBLAS_LAUNCH_LANES(8, 4, 1); }
-                else if (cp == 2) { if (g == 3) SBLAS_LAUNCH_LANES(8, 2, 3); else if (g == 2) SBLAS_LAUNCH_LANES(8, 2, 2); else SBLAS_LAUNCH_LANES(8, 2, 1); }
-                else { if (g == 3) SBLAS_LAUNCH_LANES(8, 1, 3); else if (g == 2) SBLAS_LAUNCH_LANES(8, 1, 2); else SBLAS_LAUNCH_LANES(8, 1, 1); }
-            } else if (ldbt == 16) {
-                if (cp == 2) { if (g == 2) SBLAS_LAUNCH_LANES(16, 2, 2); else SBLAS_LAUNCH_LANES(16, 2, 1); }
-                else if (g == 3) SBLAS_LAUNCH_LANES4(16, 1, 3, 2);   // two lanes per entry: eight accumulators per lane and group
-                else { if (g == 2) SBLAS_LAUNCH_LANES(16, 1, 2); else SBLAS_LAUNCH_LANES(16, 1, 1); }
-            } else {
-                // 32 columns: two lanes per entry (sixteen accumulators per lane: two groups of rows per wave fit), or a
-                // lane per entry with one group (SBLAS_TUNE=*,*,*,1: A/B runs)
-                if (g == 2) SBLAS_LAUNCH_LANES4(32, 1, 2, 2); else if (opt.tune[3] == 1) SBLAS_LAUNCH_LANES(32, 1, 1); else SBLAS_LAUNCH_LANES4(32, 1, 1, 2);
+        break;
+            switch (((d.nc * 10 + d.cp) * 10 + d.g) * 10 + d.lpe) {
+                SBLAS_LANES_CASE(8, 1, 1, 1) SBLAS_LANES_CASE(8, 1, 2, 1) SBLAS_LANES_CASE(8, 1, 3, 1)
+                SBLAS_LANES_CASE(8, 2, 1, 1) SBLAS_LANES_CASE(8, 2, 2, 1) SBLAS_LANES_CASE(8, 2, 3, 1)
+                SBLAS_LANES_CASE(8, 4, 1, 1) SBLAS_LANES_CASE(8, 4, 2, 1) SBLAS_LANES_CASE(8, 4, 3, 1)
+                SBLAS_LANES_CASE(16, 1, 1, 1) SBLAS_LANES_CASE(16, 1, 2, 1) SBLAS_LANES_CASE(16, 1, 3, 2)
+                SBLAS_LANES_CASE(16, 2, 1, 1) SBLAS_LANES_CASE(16, 2, 2, 1)
+                SBLAS_LANES_CASE(32, 1, 1, 1) SBLAS_LANES_CASE(32, 1, 1, 2) SBLAS_LANES_CASE(32, 1, 2, 2)
+            default: missing = true;
             }
-#undef SBLAS_LAUNCH_LANES
-#undef SBLAS_LAUNCH_LANES4
-            if (kev) {
-                (void)hipEventRecord(kev->b, s);
-                kev->recorded = true;
-            }
+#undef SBLAS_LANES_CASE
         }
-        const unsigned panels = (unsigned)((rows + PANEL_ROWS - 1) / PANEL_ROWS);
-        // short rows leave most of a row-per-wave sweep empty: lane groups below 24 / 16 nonzeros per row on average at 16 / 32
-        // columns (banded rows of 5 / 10 per row, 1 M rows: N = 16 0.214 / 0.287 ms against 0.585 / 0.667 row per wave; N = 32
-        // 0.403 / 0.553 against 0.691 / 0.758; from 27 per row on the row-per-wave kernel wins)
-        const bool short_rows = ldbt >= 16 && avg_row < (ldbt == 16 ? 24.0 : 16.0) && variant != SPMM_VARIANT_DIRECT_DPP;
-        if (!need_direct) {
-        } else if (ldbt >= 16 && !wide_offsets && variant != SPMM_VARIANT_LANES && !short_rows) {
-            // the row-per-wave kernel, four nonzeros per instruction: sixteen lanes x 16 bytes per nonzero (with 16 staged
-            // columns the upper eight lanes of a DPP row read past the Bt row, into columns that are never stored)
-            const int wide_panels = (rows + WIDE_PANEL - 1) / WIDE_PANEL;
-            SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (4, RC), dim3((unsigned)wide_panels, 1u), dim3(WIDE_WAVES * 64), 0, rows,
-                            cols, wide_panels, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
-                            opt.direct_map, epoch, dpp_long);
-        } else if (ldbt == 32) {
-            SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (32, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,
-                            alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
-        } else if (ldbt == 16) {
-            SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (16, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,
-                            alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
-        } else if (avg_row >= opt.rows8_min_avg && variant != SPMM_VARIANT_LANES) {
-            // n <= 8, long rows: a wave per row, eight sums per lane (banded-random rows, band +-20000, 600 k rows,
-            // N = 8: 64 / 128 / 200 / 300 per row: the lane groups win by 25 / 30 / 2 / 0 %; bench matrix, 399 per row,
-            // band +-2000: the wave per row wins by 20 % -- tools/rows8_threshold.py)
-            SBLAS_DIRECT_GO(spmm_rows8_kernel, (RC), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, rows, cols, rowptr, colidx,
-                            val, Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
-        } else {
-            SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (8, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,
-                            alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
+        if (kev) {
+            (void)hipEventRecord(kev->b, s);
+            kev->recorded = true;
         }
     }
-    if (skip) launch_split<RC>(s, cols, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, *pv);
-    return hipGetLastError();
+
+    // 2. the matrix-core kernel
+    if (d.mfma) {
+        const hipError_t e = launch_spmm_mfma(s, rows, cols, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.info, t.hdr,
+                                              t.cls, info_rows, np, epoch, panel_stats_device(), RC, d.mfma_batch, d.mfma_lds_floor);
+        if (e != hipSuccess) return e;
+    }
+
+    // 3. the direct kernels
+    if (d.four_rows) {
+        const int rp = (rows + 4 * d.rows_waves - 1) / (4 * d.rows_waves);
+#define SBLAS_ROWS_CASE(WV)                                                                                            \
+    case WV:                                                                                                          \
+        SBLAS_DIRECT_GO(spmm_direct_rows_kernel, (WV, RC), dim3((unsigned)rp, (unsigned)(ldbt / 64)), dim3(WV * 64), 0, rows, \
+                        cols, rp, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, d.interleave, \
+                        epoch, d.voted);                                                                              \
+        break;
+        switch (d.rows_waves) {
+            SBLAS_ROWS_CASE(4) SBLAS_ROWS_CASE(8) SBLAS_ROWS_CASE(16)
+        default: missing = true;
+        }
+#undef SBLAS_ROWS_CASE
+    }
+    if (d.merge) {
+        // rows that share their column pattern (multi-dof FEM): three rows per wave, shared Bt loads
+        const int mp = (rows + MERGE_PANEL - 1) / MERGE_PANEL;
+        const size_t lds = (size_t)128 * (MERGE_PANEL + 1) * sizeof(double);
+        raise_dynamic_lds((const void *)spmm_direct_merge_kernel<RC>, lds);
+        hipLaunchKernelGGL(spmm_direct_merge_kernel<RC>, dim3((unsigned)mp, (unsigned)(ldbt / 128)), dim3(MERGE_WAVES * 64), lds,
+                           s, rows, cols, mp, rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows,
+                           d.interleave, epoch);
+    }
+    if (d.dpp) {
+        // GROUPS 1: 128-column tiles, one workgroup column per tile; 2 and 4: one sweep over 64 / 32 columns
+        const int wide_panels = (rows + WIDE_PANEL - 1) / WIDE_PANEL;
+        const dim3 grid((unsigned)wide_panels, d.dpp == 1 ? (unsigned)(ldbt / 128) : 1u);
+#define SBLAS_DPP_CASE(GR)                                                                                             \
+    case GR:                                                                                                          \
+        SBLAS_DIRECT_GO(spmm_direct_dpp_kernel, (GR, RC), grid, dim3(WIDE_WAVES * 64), d.dpp_pad, rows, cols, wide_panels,  \
+                        rowptr, colidx, val, Bt, ldbt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, d.interleave, epoch,   \
+                        d.dpp_long);                                                                                  \
+        break;
+        switch (d.dpp) {
+            SBLAS_DPP_CASE(1) SBLAS_DPP_CASE(2) SBLAS_DPP_CASE(4)
+        default: missing = true;
+        }
+#undef SBLAS_DPP_CASE
+    }
+    if (d.narrow) {
+        const unsigned panels = (unsigned)((rows + PANEL_ROWS - 1) / PANEL_ROWS);
+#define SBLAS_NARROW_CASE(NC)                                                                                          \
+    case NC:                                                                                                          \
+        SBLAS_DIRECT_GO(spmm_rowpanel_narrow_kernel, (NC, RC), dim3(panels), dim3(256), 0, rows, rowptr, colidx, val, Bt, n,  \
+                        alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);                                           \
+        break;
+        switch (d.narrow) {
+            SBLAS_NARROW_CASE(8) SBLAS_NARROW_CASE(16) SBLAS_NARROW_CASE(32)
+        default: missing = true;
+        }
+#undef SBLAS_NARROW_CASE
+    }
+    if (d.rows8)
+        SBLAS_DIRECT_GO(spmm_rows8_kernel, (RC), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, rows, cols, rowptr, colidx, val,
+                        Bt, n, alpha, beta, C, ldc, t.hdr, cls, info_rows, epoch);
+
+    // 4. the split rows of a split plan, after the direct kernels (which left them alone) on the same stream
+    if (d.skip) {
+        const dim3 pgrid((unsigned)pv->n_pieces, d.split_groups == 1 ? (unsigned)((n + 127) / 128) : 1u);
+#define SBLAS_SPLIT_CASE(GR)                                                                                           \
+    case GR:                                                                                                          \
+        hipLaunchKernelGGL(spmm_split_piece_kernel<GR>, pgrid, dim3(WIDE_WAVES * 64), 0, s, pv->pieces, cols, colidx, val, Bt, \
+                           ldbt, n, pv->partial);                                                                     \
+        break;
+        switch (d.split_groups) {
+            SBLAS_SPLIT_CASE(1) SBLAS_SPLIT_CASE(2) SBLAS_SPLIT_CASE(4)
+        default: missing = true;
+        }
+#undef SBLAS_SPLIT_CASE
+        hipLaunchKernelGGL(spmm_split_fold_kernel<RC>, dim3((unsigned)pv->n_split, (unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                           pv->srows, pv->partial, ldbt, n, alpha, beta, C, ldc);
+    }
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : missing ? hipErrorInvalidValue : hipSuccess;
 }
 
 #undef SBLAS_DIRECT_GO

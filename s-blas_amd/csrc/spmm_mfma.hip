@@ -258,14 +258,14 @@ __global__ __launch_bounds__(MFMA_MAX_WAVES * 64) void spmm_mfma_kernel(
 hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr, const int *colidx, const double *val,
                             const double *Bt, int64_t ldbt, int n, double alpha, double beta, double *C, int64_t ldc,
                             const int2 *info, const int *tail, const int *cls, int panel_rows, int npanels, int epoch,
-                            unsigned long long *stats, bool row_c)
+                            unsigned long long *stats, bool row_c, int batch, size_t lds_floor)
 {
     const int waves = (panel_rows + 15) / 16;
     if (waves < 1 || waves > MFMA_MAX_WAVES) return hipErrorInvalidValue;
     const size_t img_bytes = (size_t)waves * MFMA_WAVE_LDS;
     const size_t ctile_bytes = (size_t)(ldbt == 64 ? 64 : 128) * (size_t)(panel_rows + 1) * sizeof(double);
     size_t lds = img_bytes > ctile_bytes ? img_bytes : ctile_bytes;
-    if ((size_t)options().tune[0] > lds && options().tune[0] <= 160 * 1024) lds = (size_t)options().tune[0]; // experiments: occupancy
+    if (lds_floor > lds) lds = lds_floor; // (experiments: occupancy)
 #define SBLAS_MFMA_LAUNCH1(NTV, BV, GY, RC)                                                                           \
     do {                                                                                                             \
         raise_dynamic_lds((const void *)spmm_mfma_kernel<NTV, BV, RC>, lds);                                         \
@@ -278,14 +278,16 @@ hipError_t launch_spmm_mfma(hipStream_t s, int rows, int cols, const int *rowptr
         if (row_c) SBLAS_MFMA_LAUNCH1(NTV, BV, GY, true);                                                            \
         else SBLAS_MFMA_LAUNCH1(NTV, BV, GY, false);                                                                 \
     } while (0)
-    const int batch = options().tune[1]; // experiments: operand blocks per stage
+    // batch: operand blocks per stage (spmm_stage2 names it: 2, 3 or 4 at 64 staged columns, 1 or 2 from 128 on)
     if (ldbt == 64) {
         if (batch == 4) SBLAS_MFMA_LAUNCH(4, 4, 1);
         else if (batch == 3) SBLAS_MFMA_LAUNCH(4, 3, 1);
-        else SBLAS_MFMA_LAUNCH(4, 2, 1);
+        else if (batch == 2) SBLAS_MFMA_LAUNCH(4, 2, 1);
+        else return hipErrorInvalidValue;
     } else { // (256 columns per wave -- half the chunk steps of two 128-column passes -- spills: 128 accumulator registers)
         if (batch == 1) SBLAS_MFMA_LAUNCH(8, 1, ldbt / 128);
-        else SBLAS_MFMA_LAUNCH(8, 2, ldbt / 128);
+        else if (batch == 2) SBLAS_MFMA_LAUNCH(8, 2, ldbt / 128);
+        else return hipErrorInvalidValue;
     }
 #undef SBLAS_MFMA_LAUNCH
 #undef SBLAS_MFMA_LAUNCH1

@@ -33,6 +33,7 @@ EXPORTS = [
     "sblas_spmv_plan_classify",
     "sblas_hip_spmm_csr_ordered", "sblas_hip_spmm_csr_ordered_f64_i32_planned", "sblas_hip_merge_rowblocks_ordered",
     "sblas_hip_spmm_plan_create_split", "sblas_hip_spmm_plan_split_info", "sblas_spmm_split_classify",
+    "sblas_spmm_rule_describe",
     "sblas_hip_csr_transpose_workspace", "sblas_hip_csr_transpose_f64_i32", "sblas_hip_gather_f64",
     "sblas_hip_transpose_plan_create", "sblas_hip_transpose_plan_update_values", "sblas_hip_transpose_plan_info",
     "sblas_hip_transpose_plan_csc", "sblas_hip_transpose_plan_destroy", "sblas_hip_spmv_csr_t_f64_i32_planned",
@@ -91,6 +92,8 @@ def lib():
     L.sblas_hip_spmm_plan_split_info.argtypes = [vp, C.POINTER(i64)]
     L.sblas_spmm_split_classify.restype = i64
     L.sblas_spmm_split_classify.argtypes = [vp, i64, i64, i64, i64, vp, i64, vp, i64]
+    L.sblas_spmm_rule_describe.restype = i64
+    L.sblas_spmm_rule_describe.argtypes = [i64, i64, i64, i64, i64, i64, C.c_int, vp, vp, i64]
     L.sblas_hip_spmm_plan_destroy.restype = C.c_int
     L.sblas_hip_spmm_plan_destroy.argtypes = [vp]
     L.sblas_hip_spmm_plan_info.restype = C.c_int
@@ -356,6 +359,36 @@ def spmm_split_classify(rowptr, nnz=None, split_min=0, piece=0, direct_mask=None
     out = out[:n]
     n_pieces = int(np.count_nonzero(out[:, 3] >= 0))
     return out[:n_pieces], out[n_pieces:]
+
+
+# the fields of sblas_spmm_rule_describe, in the order of the SBLAS_SPMM_RULE_* / SBLAS_SPMM_RULE_PLAN_* enums of sblas_hip.h
+SPMM_RULE_FIELDS = (
+    "staging", "verdicts", "panel_rows", "groups", "panels", "plannable",
+    "tiled", "tiled_g", "w6_nh", "w6_grid_y", "lanes_nc", "lanes_cp", "lanes_lpe",
+    "mfma", "mfma_batch", "mfma_lds_floor",
+    "four_rows", "four_rows_waves", "four_rows_voted", "merge", "dpp_groups", "dpp_pad", "dpp_long", "narrow", "rows8",
+    "interleave", "skip", "split_groups")
+SPMM_RULE_PLAN_FIELDS = ("n_window", "n_direct", "n_mfma_w", "n_mfma_d", "merge", "four_rows", "n_split", "panel_rows", "groups")
+
+
+def spmm_rule(rows, cols, nnz, ldbt, n=None, ncu=256, caller_staged=False, plan=None):
+    """The SpMM kernel rule (sblas_spmm_rule_describe; no GPU): what one column chunk of these sizes stages, classifies
+    and launches, as a dict over SPMM_RULE_FIELDS.  n defaults to ldbt; plan: None for an unplanned call, else a dict over
+    SPMM_RULE_PLAN_FIELDS (missing counts are 0)."""
+    n = ldbt if n is None else n
+    pl = None
+    if plan is not None:
+        unknown = set(plan) - set(SPMM_RULE_PLAN_FIELDS)
+        if unknown:
+            raise SblasError("spmm_rule: unknown plan fields %s" % sorted(unknown))
+        pl = np.array([int(plan.get(k, 0)) for k in SPMM_RULE_PLAN_FIELDS], np.int64)
+    out = np.zeros(len(SPMM_RULE_FIELDS), np.int64)
+    got = lib().sblas_spmm_rule_describe(rows, cols, nnz, ldbt, n, ncu, int(bool(caller_staged)),
+                                         None if pl is None else pl.ctypes.data, out.ctypes.data, len(out))
+    if got != len(out):
+        raise SblasError("sblas_spmm_rule_describe refused its arguments" if got < 0 else
+                         "sblas_spmm_rule_describe has %d fields, SPMM_RULE_FIELDS %d" % (got, len(out)))
+    return dict(zip(SPMM_RULE_FIELDS, out.tolist()))
 
 
 # SpGEMM: plan flags and the host rule's row paths (SBLAS_SPGEMM_* in sblas_hip.h)
