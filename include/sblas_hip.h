@@ -561,6 +561,59 @@ int sblas_hip_sptrsm_f64_i32_planned(const void *plan, void *stream, const int32
                                      double *X, int64_t ldx);
 
 /* ---------------------------------------------------------------------------------------
+ * ILU(0) on a level-scheduled plan, factored on the device:  lu = ILU0(A)  for a square n x n CSR matrix, fp64 values,
+ * int32 indices, n and nnz below 2^31, with the same pattern in and out.  lu holds the strictly-lower entries of the
+ * unit-lower L (its diagonal is not stored) and the diagonal and upper entries of U: exactly what two solve plans
+ * (SBLAS_FILL_LOWER with SBLAS_DIAG_UNIT, and SBLAS_FILL_UPPER) on (rowptr, colidx, lu) consume.
+ *   - structure.  Every row must be strictly ascending in column (sorted, nothing doubled: ILU(0) of a pattern with a
+ *     doubled entry is not defined) and must store its diagonal.  create refuses anything else with SBLAS_E_INVALID,
+ *     names the first bad row in *bad_row and launches nothing.  The checks run in this order: rowptr (as
+ *     sblas_sptrsv_levels: starts at 0, never steps down; in create also: ends at nnz, reported as row n - 1, first of
+ *     all), then every column's range in every row, then row by row the ascending order and the diagonal.
+ *   - arithmetic: the row-wise (IKJ) elimination, and the bits are pinned.  w starts as row i of val and ends as row i of
+ *     lu.  For the stored entries e of row i with column k < i, in stored (ascending) order: l = w[e] / lu[diag(k)],
+ *     w[e] = l, and for every stored entry f of row k with column j > k, if row i stores column j at p:
+ *     w[p] = w[p] - l * lu[f], the product rounded and then the difference rounded (no fused multiply-add).  No sum is
+ *     ever folded across lanes: each entry receives its updates one after another in ascending k.  So the bits of lu are
+ *     a function of val and the pattern alone -- NOT of the schedule, the mode, chain_rows, or of which lanes or kernel
+ *     took a row -- and a ten-line scalar loop on the host reproduces them exactly.
+ *   - pivots.  A zero pivot is NOT checked: the division follows IEEE 754, and Inf / NaN reach the dependants only.  The
+ *     plan exposes each row's diagonal position as a device array (plan_diag): one gather inspects the pivots.
+ *   - in place (lu == val) is allowed.  Partial overlap is undefined.
+ *   - schedule: the lower solve's.  Row i needs the finished rows k < i it stores an entry for, so the levels are
+ *     sblas_sptrsv_levels(LOWER, NON_UNIT) and the launches sblas_sptrsv_schedule: WIDE, one launch for one level; CHAIN,
+ *     one launch of a single workgroup for a run of consecutive levels with a workgroup barrier between them.  Nothing
+ *     waits across workgroups, there are no atomics, and every loop's trip count comes from the structure.  A row of p
+ *     stored entries belongs to the solves' G(p) lanes; up to [4] of the limits it is factored in LDS, beyond that by a
+ *     whole wave in lu itself.
+ * ------------------------------------------------------------------------------------- */
+/* out: [0] default chain_rows (unmeasured: the solves' default), [1] threads of the chain workgroup, [2] longest row of
+ * 4 lanes, [3] longest row of 16 lanes, [4] longest row whose working copy lives in LDS, [5] threads of a wide workgroup */
+int sblas_hip_ilu0_limits(int64_t out[6]);
+/* The structure check, on HOST arrays (no GPU call; testable alone), in the order given above.  diag_pos_out (n, may be
+ * NULL): the position of every row's diagonal in val.  bad_row may be NULL; it is -1 on success. */
+int sblas_ilu0_check(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t *diag_pos_out, int64_t *bad_row);
+/* create: copies rowptr and colidx to the host once, runs the check and the solves' host rule, and uploads every level's
+ * rows packed into four-lane units, the level pointer and the diagonal positions.  Synchronises `stream`.  The plan
+ * keeps the caller's rowptr / colidx POINTERS, which must outlive the plan and stay unchanged.  flags = SBLAS_SPTRSV_AUTO /
+ * PER_LEVEL / CHAIN_ONLY; chain_rows: 0 = default.  bad_row may be NULL.  n == 0 succeeds. */
+int sblas_hip_ilu0_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                               int flags, int64_t chain_rows /* 0 = default */, void **plan_out, int64_t *bad_row);
+/* out: [0] n [1] nnz [2] levels [3] launches [4] wide launches [5] chain launches [6] rows of the widest level [7] stored
+ * entries of the longest row [8] rows on the long tier [9] device bytes held [10] flags [11] chain_rows in force */
+int sblas_hip_ilu0_plan_info(const void *plan, int64_t out[12]);
+/* diag_pos: a device int32[n] that lives until the plan is destroyed (NULL when n == 0): the position of each row's
+ * diagonal in val and lu */
+int sblas_hip_ilu0_plan_diag(const void *plan, const int32_t **diag_pos);
+int sblas_hip_ilu0_plan_destroy(void *plan);
+/* The factorisation.  Stream-ordered on the calling thread's current device; allocates nothing and never synchronises:
+ * a fixed sequence of launches (graph-capturable as a linear chain of nodes) that takes new `val` on every call.
+ * rowptr / colidx must be the pointers the plan was made with, and the current device the plan's: SBLAS_E_INVALID
+ * otherwise, before anything is launched.  n == 0 succeeds and launches nothing. */
+int sblas_hip_ilu0_f64_i32_planned(const void *plan, void *stream, const int32_t *rowptr, const int32_t *colidx,
+                                   const double *val, double *lu);
+
+/* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
  * (the gradient of C = A * B with respect to A's values with X = dC and Y = B; edge scores; residuals on a pattern).
  *   - A gives its PATTERN only (rowptr, colidx).  Unsorted rows and duplicate entries are legal, as everywhere else; a

@@ -49,6 +49,8 @@ EXPORTS = [
     "sblas_hip_sptrsv_limits", "sblas_sptrsv_levels", "sblas_sptrsv_schedule",
     "sblas_hip_sptrsv_plan_create", "sblas_hip_sptrsv_plan_info", "sblas_hip_sptrsv_plan_order", "sblas_hip_sptrsv_plan_destroy",
     "sblas_hip_sptrsv_f64_i32_planned", "sblas_hip_sptrsm_f64_i32_planned",
+    "sblas_hip_ilu0_limits", "sblas_ilu0_check", "sblas_hip_ilu0_plan_create", "sblas_hip_ilu0_plan_info",
+    "sblas_hip_ilu0_plan_diag", "sblas_hip_ilu0_plan_destroy", "sblas_hip_ilu0_f64_i32_planned",
 ]
 
 
@@ -262,6 +264,20 @@ def lib():
     L.sblas_hip_sptrsv_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, f64, vp, vp]
     L.sblas_hip_sptrsm_f64_i32_planned.restype = C.c_int
     L.sblas_hip_sptrsm_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, i64, f64, vp, i64, vp, i64]
+    L.sblas_hip_ilu0_limits.restype = C.c_int
+    L.sblas_hip_ilu0_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_ilu0_check.restype = C.c_int
+    L.sblas_ilu0_check.argtypes = [i64, vp, vp, vp, C.POINTER(i64)]
+    L.sblas_hip_ilu0_plan_create.restype = C.c_int
+    L.sblas_hip_ilu0_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, i64, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_ilu0_plan_info.restype = C.c_int
+    L.sblas_hip_ilu0_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_ilu0_plan_diag.restype = C.c_int
+    L.sblas_hip_ilu0_plan_diag.argtypes = [vp, C.POINTER(vp)]
+    L.sblas_hip_ilu0_plan_destroy.restype = C.c_int
+    L.sblas_hip_ilu0_plan_destroy.argtypes = [vp]
+    L.sblas_hip_ilu0_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_ilu0_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -490,6 +506,32 @@ def sptrsv_schedule(widths, mode="auto", chain_rows=0):
     check(lib().sblas_sptrsv_schedule(L, widths.ctypes.data, _sptrsv_mode(mode), int(chain_rows), kind.ctypes.data,
                                       first.ctypes.data, C.byref(n)), "sblas_sptrsv_schedule")
     return kind[:n.value].copy(), first[:n.value + 1].copy()
+
+
+def ilu0_limits():
+    """ILU(0)'s limits (sblas_hip_ilu0_limits): dict(chain_rows, chain_threads, g4_max, g16_max, lds_max, wide_threads) --
+    the default chain_rows, the chain workgroup's threads, the longest stored rows that 4 and 16 lanes take, the longest
+    row whose working copy lives in LDS, and a wide workgroup's threads."""
+    out = (C.c_int64 * 6)()
+    check(lib().sblas_hip_ilu0_limits(out), "sblas_hip_ilu0_limits")
+    return dict(chain_rows=int(out[0]), chain_threads=int(out[1]), g4_max=int(out[2]), g16_max=int(out[3]), lds_max=int(out[4]),
+                wide_threads=int(out[5]))
+
+
+def ilu0_check(n, rowptr, colidx):
+    """ILU(0)'s structure check (sblas_ilu0_check, host arrays) -> the position of every row's diagonal.  Rows must be
+    strictly ascending in column and store their diagonal; a refused structure raises an SblasError whose .bad_row is the
+    first bad row."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    if len(rowptr) != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (len(rowptr), n))
+    diag = np.zeros(max(n, 1), np.int32)
+    bad = C.c_int64(-1)
+    rc = lib().sblas_ilu0_check(n, rowptr.ctypes.data, colidx.ctypes.data if len(colidx) else None, diag.ctypes.data, C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_ilu0_check", rc, bad.value)
+    return diag[:n]
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -1540,6 +1582,145 @@ def sptrsv(A, b, lower=True, unit_diag=False, alpha=1.0, stream=None):
     finally:
         plan.destroy()
     return x
+
+
+# ------------------------------------------------------------------------------------------
+# ILU(0) on the device: lu = ILU0(A) on A's own pattern (sblas_hip_ilu0_plan_*)
+# ------------------------------------------------------------------------------------------
+class Ilu0Plan:
+    """The level schedule of ILU(0) of the square n x n CSR matrix (rowptr, colidx), int32 indices
+    (sblas_hip_ilu0_plan_create).  Every row must be strictly ascending in column and store its diagonal; a bad
+    structure raises an SblasError that names the first bad row (.bad_row).  The plan keeps rowptr and colidx alive and
+    factors on them as they are: do not change them.  mode and chain_rows as for SptrsvPlan.  factor() allocates nothing
+    inside the library and is graph-capturable; its bits are a function of val and the pattern alone."""
+
+    def __init__(self, n, rowptr, colidx, mode="auto", chain_rows=0, stream=None):
+        import torch
+        self.n, self.mode = n, mode
+        self.handle = None
+        self._solvers = None
+        flags = _sptrsv_mode(mode)
+        for name, t in (("rowptr", rowptr), ("colidx", colidx)):
+            if not isinstance(t, torch.Tensor):
+                raise SblasError("%s must be a torch tensor" % name)
+            _typed(name, t, torch.int32)
+            if not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+        if rowptr.numel() != n + 1:
+            raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
+        self.rowptr, self.colidx = rowptr, colidx
+        self.device = rowptr.device
+        self.nnz = int(colidx.numel())
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_ilu0_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
+                                                  colidx.data_ptr() if self.nnz else None, flags, int(chain_rows),
+                                                  C.byref(h), C.byref(bad))
+        if rc != 0:
+            raise _bad_structure("sblas_hip_ilu0_plan_create", rc, bad.value)
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_ilu0_plan_info(self.handle, out), "sblas_hip_ilu0_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), levels=int(out[2]), launches=int(out[3]), wide_launches=int(out[4]),
+                    chain_launches=int(out[5]), widest_level=int(out[6]), longest_row=int(out[7]), long_rows=int(out[8]),
+                    bytes=int(out[9]), mode=[k for k, v in _SPTRSV_MODE.items() if v == out[10]][0], chain_rows=int(out[11]))
+
+    def diag(self):
+        """The position of each row's diagonal in val and lu: a torch view (int32, n) of the plan's device array; it
+        lives as long as the plan."""
+        import torch
+        if self.n == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device)
+        p = C.c_void_p()
+        check(lib().sblas_hip_ilu0_plan_diag(self.handle, C.byref(p)), "sblas_hip_ilu0_plan_diag")
+        return torch.as_tensor(_DeviceArray(p.value, self.n, "<i4"), device=self.device)
+
+    def _values(self, name, t):
+        import torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+        if t.dtype != torch.float64:
+            raise SblasError("%s must be float64, got %s" % (name, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() != self.nnz:
+            raise SblasError("%s must be contiguous with one value per stored entry (%d), got %d" % (name, self.nnz, t.numel()))
+
+    def factor(self, val, out=None, stream=None):
+        """lu = ILU0(A) for the values val (in stored order): L's strictly-lower entries and U's diagonal and upper
+        entries on A's pattern.  out: made here when None; out is val factors in place.  Returns out."""
+        import torch
+        self._values("val", val)
+        if out is None:
+            out = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        self._values("out", out)
+        check(lib().sblas_hip_ilu0_f64_i32_planned(self.handle, _stream(stream), self.rowptr.data_ptr(),
+                                                   self.colidx.data_ptr() if self.nnz else None,
+                                                   val.data_ptr() if self.nnz else None, out.data_ptr() if self.nnz else None),
+              "sblas_hip_ilu0_f64_i32_planned")
+        return out
+
+    def pivots(self, lu, out=None, stream=None):
+        """U's diagonal, lu[diag()], by one gather; a zero, Inf or NaN in it is what factor() does not report."""
+        import torch
+        self._values("lu", lu)
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        if self.n:
+            gather(self.diag(), lu, out, stream=stream)
+        return out
+
+    def solvers(self):
+        """(lower, upper): the two SptrsvPlans on the plan's own arrays that consume a factor -- L with its unit diagonal
+        implied, U with its stored one.  Made at the first call and kept until destroy()."""
+        if self._solvers is None:
+            lower = SptrsvPlan(self.n, self.rowptr, self.colidx, lower=True, unit_diag=True)
+            try:
+                upper = SptrsvPlan(self.n, self.rowptr, self.colidx, lower=False, unit_diag=False)
+            except Exception:
+                lower.destroy()
+                raise
+            self._solvers = (lower, upper)
+        return self._solvers
+
+    def apply(self, lu, r, out=None, tmp=None, stream=None):
+        """out = U^-1 (L^-1 r), the preconditioner's action; r: n entries, or n x nrhs row-major.  tmp holds L^-1 r (made
+        here when None; with tmp and out given, and solvers() called before, nothing is allocated)."""
+        lower, upper = self.solvers()
+        tmp = lower.solve(lu, r, x=tmp, stream=stream)
+        return upper.solve(lu, tmp, x=out, stream=stream)
+
+    def destroy(self):
+        if self._solvers is not None:
+            for plan in self._solvers:
+                plan.destroy()
+            self._solvers = None
+        if self.handle:
+            lib().sblas_hip_ilu0_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def ilu0(A, stream=None):
+    """lu = ILU0(A), one shot: A = (n, rowptr, colidx, val) as GPU tensors.  The plan made here is destroyed before
+    returning."""
+    n, rowptr, colidx, val = A
+    plan = Ilu0Plan(n, rowptr, colidx, stream=stream)
+    try:
+        lu = plan.factor(val, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        else:
+            import torch
+            torch.cuda.current_stream().synchronize()
+    finally:
+        plan.destroy()
+    return lu
 
 
 # ------------------------------------------------------------------------------------------
