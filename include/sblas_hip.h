@@ -40,6 +40,7 @@ extern "C" {
 #define SBLAS_E_RCCL 4      /* RCCL unavailable or a collective failed                 */
 #define SBLAS_E_IO 5        /* MatrixMarket file could not be read / parsed            */
 #define SBLAS_E_NOGPU 6     /* no HIP device visible                                   */
+#define SBLAS_E_INTERNAL 7  /* a device loop made no progress: a bug, reported, not spun on */
 
 int sblas_hip_version(void);
 const char *sblas_hip_error_string(int code);
@@ -612,6 +613,71 @@ int sblas_hip_ilu0_plan_destroy(void *plan);
  * otherwise, before anything is launched.  n == 0 succeeds and launches nothing. */
 int sblas_hip_ilu0_f64_i32_planned(const void *plan, void *stream, const int32_t *rowptr, const int32_t *colidx,
                                    const double *val, double *lu);
+
+/* ---------------------------------------------------------------------------------------
+ * Multicolour reordering:  a graph colouring of a square n x n CSR pattern on the device, and the symmetric permutation
+ * B = P A P^T of a CSR matrix on a plan.  int32 indices, fp64 values, n and nnz below 2^31.  Numbering the rows colour by
+ * colour bounds the levels of both triangles of B by the number of colours, which is what the level-scheduled solves
+ * and ILU(0) above pay for.
+ *   - the graph.  u is a neighbour of v when u != v and the pattern stores (v, u) or (u, v).  The pattern need not be
+ *     symmetric; rows may be unsorted, hold duplicates and lack a diagonal; diagonal entries are ignored.  A rowptr that
+ *     does not start at 0, steps down or (create only, checked first, reported as row n - 1) does not end at nnz, and a
+ *     column outside [0, n), are refused with SBLAS_E_INVALID and the first bad row, in the order of sblas_sptrsv_levels.
+ *   - the rule, BIT-EXACT and schedule-free.  In wrapping uint32 arithmetic
+ *         h(v) = fmix32((uint32)v + 0x9E3779B9u * (seed + 1u)),
+ *         fmix32(x): x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+ *     fmix32 is a bijection on 32-bit words, so no two vertices tie.  Visit the vertices in descending h: color[v] is the
+ *     smallest c >= 0 that no already-coloured neighbour holds.  The device runs the parallel form (Jones-Plassmann): in
+ *     a round, an uncoloured vertex none of whose uncoloured neighbours has a higher h takes its first fit.  A vertex's
+ *     colour depends on its neighbours of higher h alone, so both forms give the same colours whatever the schedule:
+ *     color is a function of the pattern and seed.
+ *   - derived arrays.  perm: the vertices sorted by (colour, vertex); inv: its inverse; color_ptr (colours + 1): class c is
+ *     perm[color_ptr[c] .. color_ptr[c + 1] - 1].
+ *   - consequences.  Every class is an independent set.  With B = P A P^T for this perm, the lower and the upper triangle
+ *     of B each have at most `colours` levels; when the pattern is structurally symmetric each has exactly `colours`,
+ *     because a vertex of colour c has a neighbour of every colour below c.
+ * ------------------------------------------------------------------------------------- */
+/* out: [0] longest p of 4 lanes, [1] longest p of 16 lanes (p = the stored entries of row v of A plus those of row v of
+ * A^T; beyond: a whole wave), [2] colours one pass of the round kernel sees (the window), [3] threads of a round workgroup */
+int sblas_hip_color_limits(int64_t out[4]);
+/* The host rule, on HOST arrays (no GPU call; testable alone): the scalar loop above.  color_out[v] = the colour;
+ * *n_colors = the greatest colour + 1 (0 when n == 0); *sync_rounds (may be NULL) = the rounds of the parallel form when
+ * every round sees only the colours of the rounds before it.  bad_row may be NULL; it is -1 on success. */
+int sblas_csr_color(int64_t n, const int32_t *rowptr, const int32_t *colidx, uint32_t seed, int32_t *color_out /* n */,
+                    int64_t *n_colors, int64_t *sync_rounds, int64_t *bad_row);
+/* create: copies rowptr and colidx to the host once (the check, and which lane group takes each vertex), transposes the
+ * pattern on the device, runs rounds until nothing is uncoloured, and sorts by colour.  The plan owns color, perm, inv and
+ * color_ptr; everything else is freed, and the caller's arrays are not kept.  Synchronises `stream`.  Rounds are separate
+ * launches; nothing waits across workgroups.  The device takes at most *sync_rounds rounds; how many is not part of the
+ * contract.  A round that colours nothing while vertices remain returns SBLAS_E_INTERNAL.  n == 0 succeeds. */
+int sblas_hip_color_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                                uint32_t seed, void **plan_out, int64_t *bad_row);
+/* out: [0] n [1] nnz [2] colours [3] rounds [4] vertices of the largest class [5] of the smallest class [6] the largest
+ * degree p (stored entries, both directions, duplicates and the diagonal counted) [7] device bytes held */
+int sblas_hip_color_plan_info(const void *plan, int64_t out[8]);
+/* device views that live until the plan is destroyed (any output may be NULL; all NULL when n == 0): color (n), perm (n),
+ * inv (n), color_ptr (colours + 1) */
+int sblas_hip_color_plan_order(const void *plan, const int32_t **color, const int32_t **perm, const int32_t **inv,
+                               const int32_t **color_ptr);
+int sblas_hip_color_plan_destroy(void *plan);
+/* B = P A P^T for ANY permutation perm (device, n entries; row r of B is row perm[r] of A): row r of B holds the entries
+ * of row perm[r] of A with columns relabelled inv[col], sorted ascending by new column, equal columns in A's stored
+ * order.  A's rows may be unsorted; B's are always sorted (duplicates stay: ILU(0) still needs a pattern without them).
+ * src[e] = the place in A of B's entry e.  create checks the structure (SBLAS_E_INVALID) and that perm is a permutation:
+ * *bad = the first index i whose perm[i] lies outside [0, n) or repeats an earlier entry (-1 otherwise; may be NULL).
+ * The plan owns rowptr_b, colidx_b, src and inv and keeps none of the caller's arrays.  Synchronises `stream`. */
+int sblas_hip_permute_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                                  const int32_t *perm, void **plan_out, int64_t *bad);
+/* out: [0] n [1] nnz [2] 8-bit passes of the sort [3] device bytes held */
+int sblas_hip_permute_plan_info(const void *plan, int64_t out[4]);
+/* device views that live until the plan is destroyed (any output may be NULL): rowptr_b (n + 1), colidx_b (nnz), src (nnz) */
+int sblas_hip_permute_plan_csr(const void *plan, const int32_t **rowptr_b, const int32_t **colidx_b, const int32_t **src);
+/* inv (n; NULL when n == 0): vectors move with sblas_hip_gather_f64, x_B = x_A[perm] and x_A = x_B[inv] */
+int sblas_hip_permute_plan_inverse(const void *plan, const int32_t **inv);
+/* val_b[e] = val_a[src[e]].  Stream-ordered on the calling thread's current device, which must be the plan's; one launch,
+ * allocates nothing, never synchronises, graph-capturable.  val_b must not overlap val_a. */
+int sblas_hip_permute_plan_values(const void *plan, void *stream, const double *val_a, double *val_b);
+int sblas_hip_permute_plan_destroy(void *plan);
 
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A

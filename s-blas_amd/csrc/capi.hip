@@ -25,6 +25,7 @@ const char *sblas_hip_error_string(int code)
     case SBLAS_E_RCCL: return "RCCL unavailable or collective failed";
     case SBLAS_E_IO: return "MatrixMarket read/parse failure";
     case SBLAS_E_NOGPU: return "no HIP device";
+    case SBLAS_E_INTERNAL: return "internal error (a device loop made no progress)";
     default: return "unknown sblas error";
     }
 }

@@ -51,6 +51,10 @@ EXPORTS = [
     "sblas_hip_sptrsv_f64_i32_planned", "sblas_hip_sptrsm_f64_i32_planned",
     "sblas_hip_ilu0_limits", "sblas_ilu0_check", "sblas_hip_ilu0_plan_create", "sblas_hip_ilu0_plan_info",
     "sblas_hip_ilu0_plan_diag", "sblas_hip_ilu0_plan_destroy", "sblas_hip_ilu0_f64_i32_planned",
+    "sblas_hip_color_limits", "sblas_csr_color", "sblas_hip_color_plan_create", "sblas_hip_color_plan_info",
+    "sblas_hip_color_plan_order", "sblas_hip_color_plan_destroy",
+    "sblas_hip_permute_plan_create", "sblas_hip_permute_plan_info", "sblas_hip_permute_plan_csr", "sblas_hip_permute_plan_inverse",
+    "sblas_hip_permute_plan_values", "sblas_hip_permute_plan_destroy",
 ]
 
 
@@ -278,6 +282,30 @@ def lib():
     L.sblas_hip_ilu0_plan_destroy.argtypes = [vp]
     L.sblas_hip_ilu0_f64_i32_planned.restype = C.c_int
     L.sblas_hip_ilu0_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.sblas_hip_color_limits.restype = C.c_int
+    L.sblas_hip_color_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_csr_color.restype = C.c_int
+    L.sblas_csr_color.argtypes = [i64, vp, vp, C.c_uint32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_hip_color_plan_create.restype = C.c_int
+    L.sblas_hip_color_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_color_plan_info.restype = C.c_int
+    L.sblas_hip_color_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_color_plan_order.restype = C.c_int
+    L.sblas_hip_color_plan_order.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_color_plan_destroy.restype = C.c_int
+    L.sblas_hip_color_plan_destroy.argtypes = [vp]
+    L.sblas_hip_permute_plan_create.restype = C.c_int
+    L.sblas_hip_permute_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_permute_plan_info.restype = C.c_int
+    L.sblas_hip_permute_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_permute_plan_csr.restype = C.c_int
+    L.sblas_hip_permute_plan_csr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_permute_plan_inverse.restype = C.c_int
+    L.sblas_hip_permute_plan_inverse.argtypes = [vp, C.POINTER(vp)]
+    L.sblas_hip_permute_plan_values.restype = C.c_int
+    L.sblas_hip_permute_plan_values.argtypes = [vp, vp, vp, vp]
+    L.sblas_hip_permute_plan_destroy.restype = C.c_int
+    L.sblas_hip_permute_plan_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -532,6 +560,32 @@ def ilu0_check(n, rowptr, colidx):
     if rc != 0:
         raise _bad_structure("sblas_ilu0_check", rc, bad.value)
     return diag[:n]
+
+
+def color_limits():
+    """The colouring's limits (sblas_hip_color_limits): dict(g4_max, g16_max, window, threads) -- the greatest p (stored
+    entries of row v of A plus those of row v of A^T) that 4 and 16 lanes take, the colours one pass of the round kernel
+    sees, and a round workgroup's threads."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_hip_color_limits(out), "sblas_hip_color_limits")
+    return dict(g4_max=int(out[0]), g16_max=int(out[1]), window=int(out[2]), threads=int(out[3]))
+
+
+def color_ref(n, rowptr, colidx, seed=0):
+    """The colouring rule on host arrays (sblas_csr_color) -> (color, n_colors, sync_rounds): first fit in descending
+    h(v) = fmix32(v + 0x9E3779B9 * (seed + 1)), and the rounds of the parallel form when every round sees only the colours
+    of the rounds before it.  A refused structure raises an SblasError whose .bad_row is the first bad row."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    if len(rowptr) != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (len(rowptr), n))
+    color = np.zeros(max(n, 1), np.int32)
+    n_colors, rounds, bad = C.c_int64(), C.c_int64(), C.c_int64(-1)
+    rc = lib().sblas_csr_color(n, rowptr.ctypes.data, colidx.ctypes.data if len(colidx) else None, int(seed) & 0xffffffff,
+                               color.ctypes.data, C.byref(n_colors), C.byref(rounds), C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_csr_color", rc, bad.value)
+    return color[:n], int(n_colors.value), int(rounds.value)
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -1721,6 +1775,203 @@ def ilu0(A, stream=None):
     finally:
         plan.destroy()
     return lu
+
+
+# ------------------------------------------------------------------------------------------
+# Multicolour reordering: a device graph colouring and P A P^T on a plan (sblas_hip_color_plan_*, sblas_hip_permute_plan_*)
+# ------------------------------------------------------------------------------------------
+def _structure(n, rowptr, colidx):
+    """the checks every structure plan makes on (rowptr, colidx) before the library sees them -> nnz"""
+    import torch
+    for name, t in (("rowptr", rowptr), ("colidx", colidx)):
+        if not isinstance(t, torch.Tensor):
+            raise SblasError("%s must be a torch tensor" % name)
+        _typed(name, t, torch.int32)
+        if not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+    if rowptr.numel() != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
+    return int(colidx.numel())
+
+
+class ColorPlan:
+    """A colouring of the n x n CSR pattern (rowptr, colidx), int32 indices (sblas_hip_color_plan_create): no stored
+    off-diagonal entry joins two vertices of one colour.  The pattern need not be symmetric; rows may be unsorted, hold
+    duplicates and lack a diagonal.  The colours are those of color_ref(): a function of the pattern and seed alone.  A
+    bad structure raises an SblasError that names the first bad row (.bad_row).  The plan owns its arrays and keeps
+    neither rowptr nor colidx.  Numbering the rows colour by colour (permute()) bounds the levels of both triangles by
+    the number of colours."""
+
+    def __init__(self, n, rowptr, colidx, seed=0, stream=None):
+        import torch
+        self.n, self.seed = n, int(seed) & 0xffffffff
+        self.handle = None
+        self.nnz = _structure(n, rowptr, colidx)
+        self.device = rowptr.device
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_color_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
+                                                   colidx.data_ptr() if self.nnz else None, self.seed, C.byref(h), C.byref(bad))
+        if rc != 0:
+            raise _bad_structure("sblas_hip_color_plan_create", rc, bad.value)
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        check(lib().sblas_hip_color_plan_info(self.handle, out), "sblas_hip_color_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), colors=int(out[2]), rounds=int(out[3]), largest_class=int(out[4]),
+                    smallest_class=int(out[5]), largest_degree=int(out[6]), bytes=int(out[7]))
+
+    def order(self):
+        """(color, perm, inv, color_ptr): torch views of the plan's device arrays -- the colour of every vertex, the
+        vertices by (colour, vertex), the inverse of that, and class c as perm[color_ptr[c] : color_ptr[c + 1]]; they
+        live as long as the plan."""
+        import torch
+        if self.n == 0:
+            empty = lambda: torch.empty(0, dtype=torch.int32, device=self.device)
+            return empty(), empty(), empty(), torch.zeros(1, dtype=torch.int32, device=self.device)
+        ptrs = [C.c_void_p() for _ in range(4)]
+        check(lib().sblas_hip_color_plan_order(self.handle, *[C.byref(p) for p in ptrs]), "sblas_hip_color_plan_order")
+        sizes = (self.n, self.n, self.n, self.info()["colors"] + 1)
+        return tuple(torch.as_tensor(_DeviceArray(p.value, k, "<i4"), device=self.device) for p, k in zip(ptrs, sizes))
+
+    def permute(self, rowptr, colidx, stream=None):
+        """The PermutePlan of (rowptr, colidx) -- this pattern, or another of the same size -- under the plan's perm."""
+        return PermutePlan(self.n, rowptr, colidx, self.order()[1], stream=stream)
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_color_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class PermutePlan:
+    """B = P A P^T of the n x n CSR matrix (rowptr, colidx) for a permutation perm (int32, on the GPU; row r of B is row
+    perm[r] of A) (sblas_hip_permute_plan_create).  B's rows come out sorted by column whatever A's order, equal columns
+    in A's stored order.  A perm with an entry outside [0, n) or a repeated one raises an SblasError whose .bad_index (and,
+    as elsewhere, .bad_row) is the first such index.  The plan owns B's structure and keeps none of the caller's arrays (perm is copied)."""
+
+    def __init__(self, n, rowptr, colidx, perm, stream=None):
+        import torch
+        self.n = n
+        self.handle = None
+        self.nnz = _structure(n, rowptr, colidx)
+        if not isinstance(perm, torch.Tensor):
+            raise SblasError("perm must be a torch tensor")
+        _typed("perm", perm, torch.int32)
+        if not perm.is_cuda:
+            raise SblasError("perm must be a GPU tensor (no CPU path exists)")
+        if perm.numel() != n:
+            raise SblasError("perm has %d entries for %d rows" % (perm.numel(), n))
+        self.device = rowptr.device
+        self.perm = perm.clone()                                                # to_permuted() gathers through it
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_permute_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
+                                                     colidx.data_ptr() if self.nnz else None,
+                                                     self.perm.data_ptr() if n else None, C.byref(h), C.byref(bad))
+        if rc != 0:
+            where = ": perm[%d] is out of range or repeated" % bad.value if bad.value >= 0 else ""
+            err = SblasError("sblas_hip_permute_plan_create failed: %s (code %d)%s" % (lib().sblas_hip_error_string(rc).decode(), rc, where))
+            err.bad_index = err.bad_row = bad.value
+            raise err
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 4)()
+        check(lib().sblas_hip_permute_plan_info(self.handle, out), "sblas_hip_permute_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), passes=int(out[2]), bytes=int(out[3]))
+
+    def _view(self, p, k):
+        import torch
+        if k == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device)
+        return torch.as_tensor(_DeviceArray(p.value, k, "<i4"), device=self.device)
+
+    def csr(self):
+        """(rowptr_b, colidx_b, src): torch views of the plan's device arrays; B's entry e is A's entry src[e].  They live
+        as long as the plan."""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        check(lib().sblas_hip_permute_plan_csr(self.handle, *[C.byref(p) for p in ptrs]), "sblas_hip_permute_plan_csr")
+        return tuple(self._view(p, k) for p, k in zip(ptrs, (self.n + 1, self.nnz, self.nnz)))
+
+    def inverse(self):
+        """inv (int32, n): a torch view of the plan's device array, inv[perm[r]] = r"""
+        p = C.c_void_p()
+        check(lib().sblas_hip_permute_plan_inverse(self.handle, C.byref(p)), "sblas_hip_permute_plan_inverse")
+        return self._view(p, self.n)
+
+    def _vector(self, name, t, k):
+        import torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+        if t.dtype != torch.float64:
+            raise SblasError("%s must be float64, got %s" % (name, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() != k:
+            raise SblasError("%s must be contiguous with %d entries, got %d" % (name, k, t.numel()))
+
+    def _out(self, x, out, k):
+        import torch
+        if out is None:
+            out = torch.empty(k, dtype=torch.float64, device=self.device)
+        self._vector("out", out, k)
+        if k and out.data_ptr() == x.data_ptr():
+            raise SblasError("out must not be the input: a gather in place is not defined")
+        return out
+
+    def values(self, val, out=None, stream=None):
+        """B's values for A's values val (in A's stored order): out[e] = val[src[e]].  One launch; with out given nothing
+        is allocated, and the call is graph-capturable.  Returns out."""
+        self._vector("val", val, self.nnz)
+        out = self._out(val, out, self.nnz)
+        check(lib().sblas_hip_permute_plan_values(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                                  out.data_ptr() if self.nnz else None), "sblas_hip_permute_plan_values")
+        return out
+
+    def to_permuted(self, x, out=None, stream=None):
+        """x_B = x_A[perm]: a vector of A's numbering in B's"""
+        self._vector("x", x, self.n)
+        out = self._out(x, out, self.n)
+        if self.n:
+            gather(self.perm, x, out, stream=stream)
+        return out
+
+    def from_permuted(self, x, out=None, stream=None):
+        """x_A = x_B[inv]: a vector of B's numbering in A's"""
+        self._vector("x", x, self.n)
+        out = self._out(x, out, self.n)
+        if self.n:
+            gather(self.inverse(), x, out, stream=stream)
+        return out
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_permute_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def csr_color(A, seed=0, stream=None):
+    """(color, perm, color_ptr) of the pattern A = (n, rowptr, colidx) as GPU tensors, one shot: tensors of their own.
+    The plan made here is destroyed before returning."""
+    n, rowptr, colidx = A[:3]
+    plan = ColorPlan(n, rowptr, colidx, seed=seed, stream=stream)
+    try:
+        color, perm, _, color_ptr = (t.clone() for t in plan.order())
+    finally:
+        plan.destroy()
+    return color, perm, color_ptr
 
 
 # ------------------------------------------------------------------------------------------
