@@ -1022,6 +1022,8 @@ def _layout(t, rows, cols, what):
     if t.dim() != 2 or tuple(t.shape) != (rows, cols):
         raise SblasError("%s must be a %d x %d tensor, got shape %s" % (what, rows, cols, tuple(t.shape)))
     s0, s1 = t.stride()
+    if rows == 0 or cols == 0:                    # no element: whatever strides the tensor carries (numpy's are (0, 0)) say nothing
+        return ROW_MAJOR, max(cols, 1)
     if s1 == 1 and s0 >= max(cols, 1):
         return ROW_MAJOR, s0
     if s0 == 1 and s1 >= max(rows, 1):
@@ -1597,7 +1599,7 @@ class SptrsvPlan:
         nrhs = int(b.shape[1])
         ld = []
         for name, t in (("b", b), ("x", x)):
-            if nrhs > 1 and t.stride(1) != 1:
+            if self.n > 0 and nrhs > 1 and t.stride(1) != 1:               # without rows there are no strides to read
                 raise SblasError("%s must be row-major (strides (ld, 1)), got strides %s" % (name, tuple(t.stride())))
             l = int(t.stride(0)) if self.n > 1 else max(nrhs, 1)
             if l < nrhs:

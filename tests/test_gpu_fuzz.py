@@ -1,6 +1,8 @@
 """A bounded run of tools/fuzz_parity.py inside the GPU suite: random matrix families, row blocks, leading dimensions,
 alpha / beta, kernel-selection switches and value / index types against the oracle (the tool's docstring has the
-details; a failing case prints its parameters and `python tools/fuzz_parity.py --seed 3 --only K` replays it)."""
+details; a failing case prints its parameters and `python tools/fuzz_parity.py --seed 3 --only K` replays it).
+SpMM and SpMV only: the plans added since (transpose, COO, SpGEMM, SDDMM, softmax, attention, the solves, ILU(0),
+colouring) have their randomised test in tests/test_gpu_fuzz_plans.py (tools/fuzz_plans.py)."""
 import importlib.util
 import os
 

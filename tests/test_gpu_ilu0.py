@@ -235,6 +235,17 @@ def test_n_0_and_n_1(env):
     plan.destroy()
 
 
+def test_apply_on_an_empty_block_with_numpys_strides(env):
+    """found by tools/fuzz_plans.py: apply() on a matrix without rows refused a 0 x 3 block that came from numpy, whose
+    strides are (0, 0) (SptrsvPlan.solve read them as a layout)"""
+    S, torch, cuda = env
+    plan = S.Ilu0Plan(0, *up(torch, cuda, np.zeros(1, np.int32), np.zeros(0, np.int32)))
+    empty = torch.zeros(0, dtype=torch.float64, device=cuda)
+    r = empty.as_strided((0, 3), (0, 0))
+    assert tuple(plan.apply(empty, r).shape) == (0, 3)
+    plan.destroy()
+
+
 def test_factor_and_apply_replay_in_a_graph_after_val_and_r_are_overwritten(env):
     S, torch, cuda = env
     rng, n, rp, ci, val = small_case(22, n=1200)

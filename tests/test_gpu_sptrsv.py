@@ -234,6 +234,20 @@ def test_n_0_and_n_1(env):
     assert tuple(X.shape) == (0, 3)
 
 
+def test_an_empty_block_of_right_hand_sides_with_numpys_strides(env):
+    """found by tools/fuzz_plans.py (ilu0, a matrix without rows): a 0 x 3 array from numpy reaches torch with the strides
+    (0, 0), contiguous as torch sees it; solve() read stride(1) != 1 as "not row-major" and refused it"""
+    S, torch, cuda = env
+    plan = S.SptrsvPlan(0, *up(torch, cuda, np.zeros(1, np.int32), np.zeros(0, np.int32)))
+    val = torch.zeros(0, dtype=torch.float64, device=cuda)
+    B = torch.zeros(0, dtype=torch.float64, device=cuda).as_strided((0, 3), (0, 0))
+    assert B.is_contiguous() and B.stride() == (0, 0)
+    X = plan.solve(val, B)
+    assert tuple(X.shape) == (0, 3)
+    assert plan.solve(val, B, x=B) is B
+    plan.destroy()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # exact grid
 # ---------------------------------------------------------------------------------------------------------------------

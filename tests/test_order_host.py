@@ -93,6 +93,17 @@ def test_layout_of_tensor_views(sblas):
         sblas._layout(t, 6, 7, "B")                        # wrong shape
 
 
+def test_a_tensor_without_elements_has_no_strides_to_refuse(sblas):
+    """an empty array that comes from numpy carries the strides (0, 0); torch calls it contiguous, and so does the library"""
+    import numpy as np
+    import torch
+    for shape in ((0, 3), (3, 0), (0, 0)):
+        t = torch.from_numpy(np.zeros(shape)).as_strided(shape, (0, 0))
+        assert t.is_contiguous()
+        assert sblas._layout(t, shape[0], shape[1], "B") == (sblas.ROW_MAJOR, max(shape[1], 1))
+        assert sblas._layout(torch.zeros(shape, dtype=torch.float64), shape[0], shape[1], "B") == (sblas.ROW_MAJOR, max(shape[1], 1))
+
+
 def test_spmm_tensor_rejects_strides_and_dtypes(sblas):
     import torch
     rp = torch.zeros(7, dtype=torch.int32)
