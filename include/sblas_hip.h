@@ -182,6 +182,10 @@ int sblas_hip_spmv_plan_destroy(void *plan);
 /* out: [0] planned at all (0: calls run unplanned), work items of the lanes-per-row [1], stream with 4096 [2] / 6144 [3]
  * products of LDS, segmented [4] and LDS-window [5] kernels, [6] split rows, [7] pieces of the split rows */
 int sblas_hip_spmv_plan_info(const void *plan, int64_t out[8]);
+/* SBLAS_OK when the plan speaks for this device (< 0: the current one), these sizes and exactly these structure
+ * pointers, SBLAS_E_INVALID otherwise: what a planned call checks, for a caller that keeps the plan inside a plan */
+int sblas_hip_spmv_plan_speaks_for(const void *plan, int dev, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                                   const int32_t *colidx);
 int sblas_hip_spmv_csr_f64_i32_planned(const void *plan, int dev, void *stream,
                                        int64_t rows, int64_t cols, int64_t nnz,
                                        const int32_t *rowptr, const int32_t *colidx, const double *val,
@@ -547,6 +551,9 @@ int sblas_hip_sptrsv_plan_create(int dev, void *stream, int64_t n, int64_t nnz, 
 /* out: [0] n [1] nnz [2] fill [3] diag [4] levels [5] launches [6] wide launches [7] chain launches [8] rows of the widest
  * level [9] stored entries of the longest row [10] device bytes held [11] flags */
 int sblas_hip_sptrsv_plan_info(const void *plan, int64_t out[12]);
+/* SBLAS_OK when the plan lives on device `dev` (< 0: the current one) and was made for exactly these rowptr / colidx
+ * pointers, SBLAS_E_INVALID otherwise: what a planned solve checks, for a caller that keeps the plan inside a plan */
+int sblas_hip_sptrsv_plan_speaks_for(const void *plan, int dev, const int32_t *rowptr, const int32_t *colidx);
 /* device views that live until the plan is destroyed (either output may be NULL; both NULL when n == 0): perm (n): the
  * rows by (level, row); level_ptr (levels + 1): level l is perm[level_ptr[l] .. level_ptr[l + 1] - 1] */
 int sblas_hip_sptrsv_plan_order(const void *plan, const int32_t **perm, const int32_t **level_ptr);
@@ -678,6 +685,116 @@ int sblas_hip_permute_plan_inverse(const void *plan, const int32_t **inv);
  * allocates nothing, never synchronises, graph-capturable.  val_b must not overlap val_a. */
 int sblas_hip_permute_plan_values(const void *plan, void *stream, const double *val_a, double *val_b);
 int sblas_hip_permute_plan_destroy(void *plan);
+
+/* ---------------------------------------------------------------------------------------
+ * Krylov solvers on a plan, resident on the device:  PCG (A symmetric positive definite) and BiCGStab (A square) for
+ * A x = b, fp64 values, int32 indices, with no preconditioner, Jacobi (an inverse-diagonal vector) or ILU(0) (two solve
+ * plans on A's own rowptr / colidx and a factor lu).  The loop never leaves the device: the host enqueues iterations
+ * and reads one scalar block back when it chooses to.
+ *   - the pinned dot product.  dot(n, x, y) is two launches; nothing waits across workgroups and there are no atomics.
+ *     The vector is cut into cells of C = 2048 consecutive elements, whatever the device.  A cell is summed by 256 lanes:
+ *     lane t takes elements t, t + 256, ... of the cell in that order, acc = acc + x[i] * y[i] from +0 with the PRODUCT
+ *     ROUNDED AND THEN THE SUM ROUNDED (no fused multiply-add); absent elements are skipped.  The 256 lane sums fold by
+ *     the butterfly v[l] = v[l] + v[l ^ m] for m = 1, 2, ... 128, and lane 0's value is partial[c].  The second launch is
+ *     one workgroup of W = 256 lanes: lane t adds partial[t], partial[t + 256], ... in order from +0, then the same
+ *     butterfly.  So the bits are a function of n and the two vectors alone -- not of the grid, the CU count, the stream
+ *     or the pointers' alignment -- and sblas_krylov_dot_ref restates them in plain C++.  (Two roundings rather than one
+ *     fused multiply-add: it is ILU(0)'s rule, the kernels are bound by memory either way, and a numpy expression can
+ *     restate a rounded product and a rounded sum but not a fused one.  Which NaN a sum of several NaNs returns is not
+ *     part of the contract.)  n == 0 gives +0.  The multi-dot form computes up to three dots in one pass over memory;
+ *     each has exactly the single dot's bits.
+ *   - the updates.  Every elementwise update rounds each product and each sum on its own, in the order written:
+ *       PCG       x = x + alpha * p;  r = r - alpha * q;  [Jacobi: z = dinv * r;]  p = z + beta * p
+ *       BiCGStab  p = r + beta * (p - omega * v);  s = r - alpha * v;  x = (x + alpha * p^) + omega * s^;  r = s - omega * t
+ *                 [Jacobi: p^ = dinv * p, s^ = dinv * s, in the pass that writes p, s]
+ *     The pass that writes r is also stage 1 of (r, r) (and of (r, z) with Jacobi, of (r^, r) in BiCGStab), with the
+ *     dot's order.  The scalars are read from the device scalar block; the host passes none.
+ *   - the scalar step.  The single workgroup that folds a dot's cells also takes the step that follows, each operation
+ *     rounded on its own:  alpha = rho / (p, q)  [BiCGStab: rho / (r^, v)],  omega = (t, s) / (t, t),  |r| = sqrt((r, r)),
+ *     beta = rho_new / rho  [BiCGStab: (rho_new / rho) * (alpha / omega)],  with rho = (r, z) [BiCGStab: (r^, r)]; it
+ *     evaluates  |r| <= max(rtol * |b|, atol),  counts the iteration and sets the status word:
+ *     SBLAS_KRYLOV_RUNNING, _CONVERGED, _LIMIT (max_iter iterations done, test not met) or _BREAKDOWN (a denominator is
+ *     zero or not finite; SBLAS_KRYLOV_DENOM_* names it).  The test comes before the limit and before beta.  BiCGStab's
+ *     (t, s), (t, t) and (s, s) share one pass: when (t, t) is 0 and sqrt((s, s)) already meets the test, omega = 0 and
+ *     the iteration ends as x + alpha * p^ with r = s, converged, instead of breaking down on its own success.
+ *   - the freeze.  Once the status is not RUNNING the update kernels return at entry and the scalar steps change
+ *     nothing: x, r, the count and |r| stay exactly those of the iteration that met the test (or of the last iteration
+ *     before a breakdown), however many iterations were already enqueued.  Their SpMVs, solves and dot stages still
+ *     run, into the plan's work vectors only.
+ *   - edges.  n == 0: converged at iteration 0.  b == 0 (|b|^2 sums to 0): x = 0, converged at 0, nothing is divided.
+ *     |r0| already within the tolerance: converged at 0, x untouched.  max_iter == 0: LIMIT at 0 unless converged.
+ *     A NaN anywhere never gives CONVERGED: comparisons with it are false.
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_KRYLOV_PCG 0
+#define SBLAS_KRYLOV_BICGSTAB 1
+#define SBLAS_PRECOND_NONE 0
+#define SBLAS_PRECOND_JACOBI 1
+#define SBLAS_PRECOND_ILU0 2
+#define SBLAS_KRYLOV_RUNNING 0
+#define SBLAS_KRYLOV_CONVERGED 1
+#define SBLAS_KRYLOV_BREAKDOWN 2
+#define SBLAS_KRYLOV_LIMIT 3
+#define SBLAS_KRYLOV_DENOM_PQ 1    /* (p, q) of PCG's alpha                  */
+#define SBLAS_KRYLOV_DENOM_RHO 2   /* the previous rho, of beta              */
+#define SBLAS_KRYLOV_DENOM_RV 3    /* (r^, v) of BiCGStab's alpha            */
+#define SBLAS_KRYLOV_DENOM_TT 4    /* (t, t) of BiCGStab's omega             */
+#define SBLAS_KRYLOV_DENOM_OMEGA 5 /* omega, of BiCGStab's beta              */
+/* the fused updates of sblas_hip_krylov_update_f64 and their vectors, in order */
+#define SBLAS_KRYLOV_UP_PCG_XR 0  /* x, r, p, q [, dinv, z]: partials (r, r) [, (r, z)]   */
+#define SBLAS_KRYLOV_UP_PCG_P 1   /* p, z                                                  */
+#define SBLAS_KRYLOV_UP_BICG_P 2  /* p, r, v [, dinv, p^]                                  */
+#define SBLAS_KRYLOV_UP_BICG_S 3  /* s, r, v [, dinv, s^]                                  */
+#define SBLAS_KRYLOV_UP_BICG_XR 4 /* x, r, p^, s^, s, t, r^: partials (r, r), (r^, r)      */
+/* HOST functions (no GPU call; testable alone).  limits: [0] cell size C, [1] stage-2 width W (and lanes of a cell),
+ * [2] work vectors of PCG, [3] of BiCGStab (ILU(0) adds the solves' temporary to either), [4] dots of one pass */
+int sblas_krylov_limits(int64_t out[5]);
+/* the pinned dot product restated in plain C++, on host arrays */
+double sblas_krylov_dot_ref(int64_t n, const double *x, const double *y);
+/* Launches of ONE iteration: the solver's own kernels, one per SpMV (a planned SpMV of k kernel classes launches k), and
+ * the two solves' of every M^-1 with ILU(0) -- lower_info / upper_info are the out[12] of sblas_hip_sptrsv_plan_info
+ * (read: [5] launches; NULL unless ILU(0)).  PCG: 6, with ILU(0) 8 + lower + upper.  BiCGStab: 10 + 2 (lower + upper).
+ * -1 for a bad argument. */
+int64_t sblas_krylov_launches(int method, int precond, const int64_t *lower_info, const int64_t *upper_info);
+/* The pinned dot on its own: out[k] = (x[k], y[k]) for k < ndots <= 3, one pass over memory and one fold; x, y: HOST
+ * arrays of ndots device pointers, out: ndots doubles on the device.  workspace: at least ..._dot_workspace(n, ndots)
+ * bytes on the device, 8-byte aligned (SBLAS_E_WORKSPACE when missing or short).  Stream-ordered, allocates nothing,
+ * never synchronises, graph-capturable. */
+size_t sblas_hip_krylov_dot_workspace(int64_t n, int ndots);
+int sblas_hip_krylov_dot_f64(int dev, void *stream, int64_t n, int ndots, const double *const *x, const double *const *y,
+                             double *out, void *workspace, size_t workspace_bytes);
+/* One fused update on its own (what the solvers launch; for tests and for loops composed by the caller).  scalars: a
+ * device block of 16 eight-byte slots -- [0] status as int64 (anything but SBLAS_KRYLOV_RUNNING: the call writes
+ * nothing), [4] alpha, [5] beta, [6] omega as doubles.  v: a HOST array of nv device pointers in the order given at
+ * SBLAS_KRYLOV_UP_*; jacobi != 0 adds dinv and the preconditioned vector.  partial: device doubles, dot k of the pass at
+ * partial[k * cells + c], cells = ceil(n / C) (NULL for an update without one). */
+int sblas_hip_krylov_update_f64(int dev, void *stream, int op, int jacobi, int64_t n, const double *scalars, double *const *v,
+                                int nv, double *partial);
+/* create: host work and one allocation (the scalar block, the partials and the work vectors).  spmv_plan: a handle of
+ * sblas_hip_spmv_plan_create on the same (n, n, nnz, rowptr, colidx), or NULL for the unplanned SpMV.  precond ILU0:
+ * lower_plan (SBLAS_FILL_LOWER, SBLAS_DIAG_UNIT) and upper_plan (SBLAS_FILL_UPPER, SBLAS_DIAG_NON_UNIT) of
+ * sblas_hip_sptrsv_plan_create on the same rowptr / colidx; otherwise both NULL.  A plan of another device, structure,
+ * fill or diag is refused (SBLAS_E_INVALID).  The plan keeps the POINTERS and the handles, which must outlive it. */
+int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr,
+                                 const int32_t *colidx, const void *spmv_plan, int precond, const void *lower_plan,
+                                 const void *upper_plan, void **plan_out);
+/* out: [0] n [1] nnz [2] method [3] precond [4] work vectors owned [5] bytes of one [6] bytes of the partials [7] bytes of
+ * the scalar block [8] device bytes held [9] launches of one iteration (sblas_krylov_launches) */
+int sblas_hip_krylov_plan_info(const void *plan, int64_t out[10]);
+int sblas_hip_krylov_plan_destroy(void *plan);
+/* start: |b|, r = b - A x (A x by the SpMV, then one rounded difference), the test at iteration 0, z and the first
+ * direction.  x on entry is the initial guess and is updated in place by iterate; val, lu_or_dinv (the factor for ILU0,
+ * the inverse diagonal for JACOBI, ignored for NONE), b and x must stay valid and unchanged by others until the solve is
+ * over.  rtol, atol >= 0, max_iter >= 0.  Stream-ordered on the calling thread's current device, which must be the
+ * plan's; allocates nothing, never synchronises. */
+int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const double *lu_or_dinv, const double *b, double *x,
+                           double rtol, double atol, int64_t max_iter);
+/* iterate: enqueues k iterations.  Allocates nothing and never synchronises: a fixed linear sequence of launches
+ * (graph-capturable as a chain).  SBLAS_E_INVALID before start. */
+int sblas_hip_krylov_iterate(void *plan, void *stream, int64_t k);
+/* status: copies the scalar block back and synchronises `stream` -- the only call of a solve that does.  out: [0]
+ * status [1] iterations [2] |r| of the recurrence [3] |b| [4] alpha [5] beta [6] omega (the last of each) [7] the
+ * SBLAS_KRYLOV_DENOM_* of a breakdown, else 0. */
+int sblas_hip_krylov_status(const void *plan, void *stream, double out[8]);
 
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A

@@ -511,6 +511,13 @@ int sblas_hip_spmv_plan_destroy(void *plan)
     return SBLAS_OK;
 }
 
+int sblas_hip_spmv_plan_speaks_for(const void *plan, int dev, int64_t rows, int64_t cols, int64_t nnz, const int32_t *rowptr,
+                                   const int32_t *colidx)
+{
+    if (!plan) return SBLAS_E_INVALID;
+    return static_cast<const SpmvPlan *>(plan)->speaks_for(dev, rows, cols, nnz, rowptr, colidx) ? SBLAS_OK : SBLAS_E_INVALID;
+}
+
 int sblas_hip_spmv_plan_info(const void *plan, int64_t out[8])
 {
     if (!plan || !out) return SBLAS_E_INVALID;

@@ -1,0 +1,608 @@
+// krylov.hip -- device-resident Krylov solvers on a plan: PCG and BiCGStab.  Everything a solver does
+// between two SpMVs (or triangular solves) is one of three kernels:
+//   dot     stage 1 of up to KRYLOV_MAX_DOTS dot products in one pass over memory: one workgroup a cell of KRYLOV_CELL
+//           elements, the cell's sum to partial[c];
+//   update  a fused elementwise update of the recurrence's vectors, which is also stage 1 of the dots of what it wrote;
+//   fold    stage 2: ONE workgroup folds the cells' sums and its lane 0 takes the scalar step that follows from them
+//           (alpha, beta, omega, |r|, the stopping test, the iteration count, the status word), in the device scalar block.
+// Nothing waits across workgroups: no flag polling, no cooperative launch, no atomics.  The only synchronisation is the
+// kernel boundary and __syncthreads().  The host passes no scalar of the recurrence and reads none back before status().
+//
+// The freeze.  Once the status word is not RUNNING, every update kernel returns at entry (the flag is one uniform load,
+// read once) and lane 0 of every fold changes nothing.  So x, r, the iteration count and |r| stay exactly what they were
+// when the test was met, however many further iterations were already enqueued; the SpMVs, solves and dot stages of those
+// iterations still run, into work vectors and partials only.
+//
+// Arithmetic.  Every product and every sum is rounded on its own: this file is compiled with contraction off, so no
+// multiply-add is fused, in the dots or in the updates, and a numpy expression of the same shape reproduces the bits.
+// The order of a dot's additions is a function of n alone (include/sblas_hip.h; sblas_krylov_dot_ref restates it): a
+// cell is a workgroup whatever the device, so neither the grid nor the CU count can reach it.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+#include <initializer_list>
+#include <memory>
+#include "../../include/sblas_hip.h"
+#include "capi_util.h"
+#include "krylov.h"
+
+#pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
+
+using namespace sblas;
+
+namespace {
+
+// internal update ops, after the public SBLAS_KRYLOV_UP_* ones
+enum { UP_COPY = 5, UP_START_PCG = 6, UP_START_BICG = 7 };
+// fold ops: what lane 0 does with the folded sums d[0 .. nd - 1]
+enum {
+    FOLD_OUT = 0,     // out[k] = d[k]                                  (sblas_hip_krylov_dot_f64)
+    FOLD_START_B,     // |b|, the tolerance, and the block's first state (flag: BiCGStab)
+    FOLD_START_R,     // |r0| and the test at iteration 0; rho = d[nd - 1]
+    FOLD_RHO0,        // rho = d[0]                                     (PCG with ILU(0): (r0, z0))
+    FOLD_PCG_ALPHA,   // alpha = rho / (p, q)
+    FOLD_PCG_RES,     // |r|, count, test; flag: then beta = d[nd - 1] / rho
+    FOLD_PCG_BETA,    // beta = d[0] / rho                              (PCG with ILU(0))
+    FOLD_BICG_ALPHA,  // alpha = rho / (r^, v)
+    FOLD_BICG_OMEGA,  // omega = (t, s) / (t, t); d[2] = (s, s) for the half step that already meets the test
+    FOLD_BICG_RES     // |r|, count, test, beta = ((r^, r) / rho) * (alpha / omega)
+};
+
+struct UpArgs {
+    int64_t n, cells;
+    double *blk;  // the scalar block
+    double *part; // cells' sums: dot k of the pass at part[k * cells + c]
+    double *v[8];
+};
+
+struct DotArgs {
+    int64_t n, cells;
+    const double *x[KRYLOV_MAX_DOTS], *y[KRYLOV_MAX_DOTS];
+    double *part;
+};
+
+// the butterfly l ^ 1 .. l ^ 32 inside a wave: every lane ends with the same bits (IEEE addition commutes)
+__device__ __forceinline__ double wave_fold(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m);
+    return v;
+}
+
+// The 256 lane sums of NP dots folded by the butterfly l ^ 1 .. l ^ 128; steps 64 and 128 go through LDS: lane 0 of the
+// butterfly ends with (w0 + w1) + (w2 + w3) of the four waves' sums.  Every thread returns with out[] set.
+template <int NP> __device__ __forceinline__ void group_fold(const double (&acc)[NP], double (&out)[NP])
+{
+    __shared__ double ws[NP][4];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const double v = wave_fold(acc[q]);
+        if ((threadIdx.x & 63) == 0) ws[q][threadIdx.x >> 6] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NP; ++q) out[q] = (ws[q][0] + ws[q][1]) + (ws[q][2] + ws[q][3]);
+}
+
+// Lane t of cell c takes elements t, t + 256, ... of the cell in that order; absent elements are skipped.
+template <class F> __device__ __forceinline__ void cell_walk(int64_t n, F f)
+{
+    const int64_t first = (int64_t)blockIdx.x * KRYLOV_CELL;
+    if (first + KRYLOV_CELL <= n) {
+#pragma unroll
+        for (int k = 0; k < KRYLOV_PER_LANE; ++k) f(first + threadIdx.x + k * KRYLOV_LANES);
+    } else {
+        for (int k = 0; k < KRYLOV_PER_LANE; ++k) {
+            const int64_t i = first + threadIdx.x + k * KRYLOV_LANES;
+            if (i < n) f(i);
+        }
+    }
+}
+
+template <int NP> __device__ __forceinline__ void cell_store(const double (&acc)[NP], double *part, int64_t cells)
+{
+    double out[NP];
+    group_fold<NP>(acc, out);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) part[q * cells + blockIdx.x] = out[q];
+    }
+}
+
+// ---- dot, stage 1 ----------------------------------------------------------------------------------------------------
+template <int ND> __global__ __launch_bounds__(KRYLOV_LANES) void krylov_dot_kernel(const DotArgs a)
+{
+    double acc[ND];
+#pragma unroll
+    for (int q = 0; q < ND; ++q) acc[q] = 0.0;
+    cell_walk(a.n, [&](int64_t i) {
+#pragma unroll
+        for (int q = 0; q < ND; ++q) acc[q] = acc[q] + a.x[q][i] * a.y[q][i];
+    });
+    cell_store<ND>(acc, a.part, a.cells);
+}
+
+// ---- the fused updates -----------------------------------------------------------------------------------------------
+// JAC: the Jacobi preconditioner rides in the same pass (z = dinv o r, and its partials).  Vectors are not __restrict__:
+// without a preconditioner z is r, and p^, s^ are p, s.
+template <int OP, bool JAC> __global__ __launch_bounds__(KRYLOV_LANES) void krylov_update_kernel(const UpArgs a)
+{
+    const long long *ib = reinterpret_cast<const long long *>(a.blk);
+    constexpr bool START = OP == UP_START_PCG || OP == UP_START_BICG;
+    if (!START && ib[KS_STATUS] != SBLAS_KRYLOV_RUNNING) return; // block-uniform, read once: the freeze
+    const double al = a.blk[KS_ALPHA], be = a.blk[KS_BETA], om = a.blk[KS_OMEGA];
+    const bool zero_x = START && ib[KS_ZERO_X] != 0;
+    double *const *v = a.v;
+    if constexpr (OP == SBLAS_KRYLOV_UP_PCG_XR) { // x, r, p, q, dinv, z
+        double acc[JAC ? 2 : 1] = {};
+        cell_walk(a.n, [&](int64_t i) {
+            v[0][i] = v[0][i] + al * v[2][i];
+            const double ri = v[1][i] - al * v[3][i];
+            v[1][i] = ri;
+            acc[0] = acc[0] + ri * ri;
+            if constexpr (JAC) {
+                const double zi = v[4][i] * ri;
+                v[5][i] = zi;
+                acc[1] = acc[1] + ri * zi;
+            }
+        });
+        cell_store<JAC ? 2 : 1>(acc, a.part, a.cells);
+    } else if constexpr (OP == SBLAS_KRYLOV_UP_PCG_P) { // p, z
+        cell_walk(a.n, [&](int64_t i) { v[0][i] = v[1][i] + be * v[0][i]; });
+    } else if constexpr (OP == UP_COPY) { // dst, src
+        cell_walk(a.n, [&](int64_t i) { v[0][i] = v[1][i]; });
+    } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_P) { // p, r, v, dinv, p^
+        cell_walk(a.n, [&](int64_t i) {
+            const double pi = v[1][i] + be * (v[0][i] - om * v[2][i]);
+            v[0][i] = pi;
+            if constexpr (JAC) v[4][i] = v[3][i] * pi;
+        });
+    } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_S) { // s, r, v, dinv, s^
+        cell_walk(a.n, [&](int64_t i) {
+            const double si = v[1][i] - al * v[2][i];
+            v[0][i] = si;
+            if constexpr (JAC) v[4][i] = v[3][i] * si;
+        });
+    } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_XR) { // x, r, p^, s^, s, t, r^
+        double acc[2] = {};
+        cell_walk(a.n, [&](int64_t i) {
+            v[0][i] = (v[0][i] + al * v[2][i]) + om * v[3][i];
+            const double ri = v[4][i] - om * v[5][i];
+            v[1][i] = ri;
+            acc[0] = acc[0] + ri * ri;
+            acc[1] = acc[1] + v[6][i] * ri;
+        });
+        cell_store<2>(acc, a.part, a.cells);
+    } else if constexpr (OP == UP_START_PCG) { // r, b, q (= A x0), dinv, z, x
+        double acc[JAC ? 2 : 1] = {};
+        cell_walk(a.n, [&](int64_t i) {
+            if (zero_x) v[5][i] = 0.0; // b == 0: x = 0, and b - A x0 is not formed
+            const double ri = zero_x ? 0.0 : v[1][i] - v[2][i];
+            v[0][i] = ri;
+            acc[0] = acc[0] + ri * ri;
+            if constexpr (JAC) {
+                const double zi = zero_x ? 0.0 : v[3][i] * ri;
+                v[4][i] = zi;
+                acc[1] = acc[1] + ri * zi;
+            }
+        });
+        cell_store<JAC ? 2 : 1>(acc, a.part, a.cells);
+    } else { // UP_START_BICG: r, b, v (= A x0 on entry, 0 on exit), r^, p, x
+        double acc[1] = {};
+        cell_walk(a.n, [&](int64_t i) {
+            if (zero_x) v[5][i] = 0.0;
+            const double ri = zero_x ? 0.0 : v[1][i] - v[2][i];
+            v[0][i] = ri, v[3][i] = ri, v[4][i] = 0.0, v[2][i] = 0.0;
+            acc[0] = acc[0] + ri * ri;
+        });
+        cell_store<1>(acc, a.part, a.cells);
+    }
+}
+
+// ---- stage 2, which is also the scalar step ----------------------------------------------------------------------------
+__device__ __forceinline__ bool bad_denominator(double d) { return d == 0.0 || !isfinite(d); }
+
+__device__ __forceinline__ void break_down(double *blk, long long which)
+{
+    long long *ib = reinterpret_cast<long long *>(blk);
+    ib[KS_STATUS] = SBLAS_KRYLOV_BREAKDOWN, ib[KS_WHICH] = which;
+}
+
+// |r|, the count and the test; true when the recurrence goes on
+__device__ __forceinline__ bool residual_step(double *blk, double rr, bool count)
+{
+    long long *ib = reinterpret_cast<long long *>(blk);
+    const double rnorm = sqrt(rr);
+    blk[KS_RNORM] = rnorm;
+    if (count) ib[KS_ITER] = ib[KS_ITER] + 1;
+    if (rnorm <= blk[KS_TOL]) ib[KS_STATUS] = SBLAS_KRYLOV_CONVERGED;
+    else if (ib[KS_ITER] >= ib[KS_MAX_ITER]) ib[KS_STATUS] = SBLAS_KRYLOV_LIMIT;
+    else return true;
+    return false;
+}
+
+__global__ __launch_bounds__(KRYLOV_LANES) void krylov_fold_kernel(int op, int nd, int flag, int64_t cells, const double *part, double *blk,
+                                                                  double rtol, double atol, long long max_iter)
+{
+    // lane t adds partial[t], partial[t + 256], ... in order from +0, then the same butterfly
+    double acc[KRYLOV_MAX_DOTS] = {}, d[KRYLOV_MAX_DOTS];
+    for (int64_t c = threadIdx.x; c < cells; c += KRYLOV_LANES)
+        for (int q = 0; q < nd; ++q) acc[q] = acc[q] + part[q * cells + c];
+    group_fold<KRYLOV_MAX_DOTS>(acc, d);
+    if (threadIdx.x != 0) return;
+    long long *ib = reinterpret_cast<long long *>(blk);
+    if (op == FOLD_OUT) {
+        for (int q = 0; q < nd; ++q) blk[q] = d[q];
+        return;
+    }
+    if (op == FOLD_START_B) {
+        const double bnorm = sqrt(d[0]), t = rtol * bnorm;
+        // every slot by its own type: a slot is never read as the other one
+        blk[KS_RNORM] = 0.0, blk[KS_ALPHA] = 0.0, blk[KS_BETA] = 0.0, blk[KS_RHO] = 0.0, blk[KS_OMEGA] = flag ? 1.0 : 0.0;
+        blk[KS_BNORM] = bnorm, blk[KS_TOL] = t >= atol ? t : atol;
+        ib[KS_ITER] = 0, ib[KS_WHICH] = 0, ib[KS_MAX_ITER] = max_iter;
+        const bool zero = d[0] == 0.0; // b == 0: x = 0, converged at iteration 0, and nothing is divided
+        ib[KS_ZERO_X] = zero, ib[KS_STATUS] = zero ? SBLAS_KRYLOV_CONVERGED : SBLAS_KRYLOV_RUNNING;
+        return;
+    }
+    if (ib[KS_STATUS] != SBLAS_KRYLOV_RUNNING) return; // frozen: the scalars stay what they were
+    const double rho = blk[KS_RHO];
+    switch (op) {
+    case FOLD_START_R:
+        blk[KS_RHO] = d[nd - 1];
+        residual_step(blk, d[0], false);
+        break;
+    case FOLD_RHO0: blk[KS_RHO] = d[0]; break;
+    case FOLD_PCG_ALPHA:
+    case FOLD_BICG_ALPHA:
+        if (bad_denominator(d[0])) break_down(blk, op == FOLD_PCG_ALPHA ? SBLAS_KRYLOV_DENOM_PQ : SBLAS_KRYLOV_DENOM_RV);
+        else blk[KS_ALPHA] = rho / d[0];
+        break;
+    case FOLD_PCG_RES:
+        if (!residual_step(blk, d[0], true) || !flag) break;
+        [[fallthrough]];
+    case FOLD_PCG_BETA: {
+        const double rho_new = d[op == FOLD_PCG_RES ? nd - 1 : 0];
+        if (bad_denominator(rho)) break_down(blk, SBLAS_KRYLOV_DENOM_RHO);
+        else blk[KS_BETA] = rho_new / rho, blk[KS_RHO] = rho_new;
+        break;
+    }
+    case FOLD_BICG_OMEGA:
+        // t = 0 because s already meets the test (A s^ of a vanished s): the half step is the answer, omega = 0 takes it
+        if (d[1] == 0.0 && sqrt(d[2]) <= blk[KS_TOL]) blk[KS_OMEGA] = 0.0;
+        else if (bad_denominator(d[1])) break_down(blk, SBLAS_KRYLOV_DENOM_TT);
+        else blk[KS_OMEGA] = d[0] / d[1];
+        break;
+    case FOLD_BICG_RES:
+        if (!residual_step(blk, d[0], true)) break;
+        if (bad_denominator(rho)) break_down(blk, SBLAS_KRYLOV_DENOM_RHO);
+        else if (bad_denominator(blk[KS_OMEGA])) break_down(blk, SBLAS_KRYLOV_DENOM_OMEGA);
+        else blk[KS_BETA] = (d[1] / rho) * (blk[KS_ALPHA] / blk[KS_OMEGA]), blk[KS_RHO] = d[1];
+        break;
+    default: break;
+    }
+}
+
+// ---- launches ----------------------------------------------------------------------------------------------------------
+inline void launch_dot(hipStream_t s, int nd, const DotArgs &a)
+{
+    const unsigned grid = (unsigned)a.cells;
+    if (nd == 1) krylov_dot_kernel<1><<<grid, KRYLOV_LANES, 0, s>>>(a);
+    else if (nd == 2) krylov_dot_kernel<2><<<grid, KRYLOV_LANES, 0, s>>>(a);
+    else krylov_dot_kernel<3><<<grid, KRYLOV_LANES, 0, s>>>(a);
+}
+
+inline void launch_fold(hipStream_t s, int op, int nd, int flag, int64_t cells, const double *part, double *blk, double rtol = 0.0,
+                        double atol = 0.0, int64_t max_iter = 0)
+{
+    krylov_fold_kernel<<<1, KRYLOV_LANES, 0, s>>>(op, nd, flag, cells, part, blk, rtol, atol, (long long)max_iter);
+}
+
+template <int OP> inline void launch_update_op(hipStream_t s, bool jac, const UpArgs &a)
+{
+    const unsigned grid = (unsigned)a.cells;
+    if (jac) krylov_update_kernel<OP, true><<<grid, KRYLOV_LANES, 0, s>>>(a);
+    else krylov_update_kernel<OP, false><<<grid, KRYLOV_LANES, 0, s>>>(a);
+}
+
+inline void launch_update(hipStream_t s, int op, bool jac, const UpArgs &a)
+{
+    switch (op) {
+    case SBLAS_KRYLOV_UP_PCG_XR: return launch_update_op<SBLAS_KRYLOV_UP_PCG_XR>(s, jac, a);
+    case SBLAS_KRYLOV_UP_PCG_P: return launch_update_op<SBLAS_KRYLOV_UP_PCG_P>(s, false, a);
+    case SBLAS_KRYLOV_UP_BICG_P: return launch_update_op<SBLAS_KRYLOV_UP_BICG_P>(s, jac, a);
+    case SBLAS_KRYLOV_UP_BICG_S: return launch_update_op<SBLAS_KRYLOV_UP_BICG_S>(s, jac, a);
+    case SBLAS_KRYLOV_UP_BICG_XR: return launch_update_op<SBLAS_KRYLOV_UP_BICG_XR>(s, false, a);
+    case UP_COPY: return launch_update_op<UP_COPY>(s, false, a);
+    case UP_START_PCG: return launch_update_op<UP_START_PCG>(s, jac, a);
+    default: return launch_update_op<UP_START_BICG>(s, false, a);
+    }
+}
+
+inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
+
+struct KrylovPlan {
+    int dev = -1, method = 0, precond = 0;
+    int64_t n = 0, nnz = 0, cells = 0;
+    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
+    const void *spmv = nullptr, *lower = nullptr, *upper = nullptr;
+    int n_vectors = 0;
+    size_t vector_bytes = 0, partial_bytes = 0, bytes = 0;
+    DeviceBuffer buf; // block | partials | vectors
+    double *blk = nullptr, *part = nullptr, *vec = nullptr;
+    // one solve: start() keeps what iterate() needs
+    bool started = false;
+    const double *val = nullptr, *pre = nullptr;
+    double *x = nullptr;
+    double *w(int k) const { return vec + (size_t)k * (vector_bytes / 8); }
+};
+
+// vectors of the plan, by slot
+enum { V_R = 0, V_P = 1, V_Q = 2, V_Z = 3, V_TMP_PCG = 4 };
+enum { B_R = 0, B_RHAT = 1, B_P = 2, B_V = 3, B_S = 4, B_T = 5, B_PH = 6, B_SH = 7, B_TMP = 8 };
+
+int spmv(const KrylovPlan *p, hipStream_t s, const double *x, double *y)
+{
+    if (p->spmv)
+        return sblas_hip_spmv_csr_f64_i32_planned(p->spmv, -1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
+    return sblas_hip_spmv_csr_f64_i32(-1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
+}
+
+// out = U^-1 (L^-1 in) with the factor the caller gave start()
+int ilu_apply(const KrylovPlan *p, hipStream_t s, const double *in, double *tmp, double *out)
+{
+    const int rc = sblas_hip_sptrsv_f64_i32_planned(p->lower, s, p->rowptr, p->colidx, p->pre, 1.0, in, tmp);
+    if (rc != SBLAS_OK) return rc;
+    return sblas_hip_sptrsv_f64_i32_planned(p->upper, s, p->rowptr, p->colidx, p->pre, 1.0, tmp, out);
+}
+
+UpArgs up_args(const KrylovPlan *p, std::initializer_list<double *> v)
+{
+    UpArgs a{p->n, p->cells, p->blk, p->part, {}};
+    int k = 0;
+    for (double *q : v) a.v[k++] = q;
+    return a;
+}
+
+void dot(const KrylovPlan *p, hipStream_t s, const double *x0, const double *y0, const double *x1 = nullptr, const double *y1 = nullptr,
+         const double *x2 = nullptr, const double *y2 = nullptr)
+{
+    DotArgs a{p->n, p->cells, {x0, x1, x2}, {y0, y1, y2}, p->part};
+    launch_dot(s, x2 ? 3 : x1 ? 2 : 1, a);
+}
+
+int pcg_iteration(const KrylovPlan *p, hipStream_t s)
+{
+    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = p->precond == SBLAS_PRECOND_ILU0;
+    double *r = p->w(V_R), *pp = p->w(V_P), *q = p->w(V_Q), *z = p->precond == SBLAS_PRECOND_NONE ? r : p->w(V_Z);
+    int rc = spmv(p, s, pp, q);
+    if (rc != SBLAS_OK) return rc;
+    dot(p, s, pp, q);
+    launch_fold(s, FOLD_PCG_ALPHA, 1, 0, p->cells, p->part, p->blk);
+    launch_update(s, SBLAS_KRYLOV_UP_PCG_XR, jac, up_args(p, {p->x, r, pp, q, const_cast<double *>(p->pre), z}));
+    launch_fold(s, FOLD_PCG_RES, jac ? 2 : 1, !ilu, p->cells, p->part, p->blk);
+    if (ilu) {
+        if ((rc = ilu_apply(p, s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
+        dot(p, s, r, z);
+        launch_fold(s, FOLD_PCG_BETA, 1, 0, p->cells, p->part, p->blk);
+    }
+    launch_update(s, SBLAS_KRYLOV_UP_PCG_P, false, up_args(p, {pp, z}));
+    return SBLAS_OK;
+}
+
+int bicgstab_iteration(const KrylovPlan *p, hipStream_t s)
+{
+    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = p->precond == SBLAS_PRECOND_ILU0, none = p->precond == SBLAS_PRECOND_NONE;
+    double *r = p->w(B_R), *rh = p->w(B_RHAT), *pp = p->w(B_P), *v = p->w(B_V), *sv = p->w(B_S), *t = p->w(B_T);
+    double *ph = none ? pp : p->w(B_PH), *sh = none ? sv : p->w(B_SH), *dinv = const_cast<double *>(p->pre);
+    int rc;
+    launch_update(s, SBLAS_KRYLOV_UP_BICG_P, jac, up_args(p, {pp, r, v, dinv, ph}));
+    if (ilu && (rc = ilu_apply(p, s, pp, p->w(B_TMP), ph)) != SBLAS_OK) return rc;
+    if ((rc = spmv(p, s, ph, v)) != SBLAS_OK) return rc;
+    dot(p, s, rh, v);
+    launch_fold(s, FOLD_BICG_ALPHA, 1, 0, p->cells, p->part, p->blk);
+    launch_update(s, SBLAS_KRYLOV_UP_BICG_S, jac, up_args(p, {sv, r, v, dinv, sh}));
+    if (ilu && (rc = ilu_apply(p, s, sv, p->w(B_TMP), sh)) != SBLAS_OK) return rc;
+    if ((rc = spmv(p, s, sh, t)) != SBLAS_OK) return rc;
+    dot(p, s, t, sv, t, t, sv, sv);
+    launch_fold(s, FOLD_BICG_OMEGA, 3, 0, p->cells, p->part, p->blk);
+    launch_update(s, SBLAS_KRYLOV_UP_BICG_XR, false, up_args(p, {p->x, r, ph, sh, sv, t, rh}));
+    launch_fold(s, FOLD_BICG_RES, 2, 0, p->cells, p->part, p->blk);
+    return SBLAS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+size_t sblas_hip_krylov_dot_workspace(int64_t n, int ndots)
+{
+    if (n < 0 || ndots < 1 || ndots > KRYLOV_MAX_DOTS) return 0;
+    const size_t sums = (size_t)ndots * (size_t)krylov_cells(n);
+    return (sums ? sums : 1) * sizeof(double); // never 0: a workspace is always asked for
+}
+
+int sblas_hip_krylov_dot_f64(int dev, void *stream, int64_t n, int ndots, const double *const *x, const double *const *y, double *out,
+                             void *workspace, size_t workspace_bytes)
+{
+    if (n < 0 || n > INT_MAX || ndots < 1 || ndots > KRYLOV_MAX_DOTS || !x || !y || !out) return SBLAS_E_INVALID;
+    for (int q = 0; q < ndots; ++q)
+        if (n > 0 && (!x[q] || !y[q])) return SBLAS_E_INVALID;
+    if (!workspace || workspace_bytes < sblas_hip_krylov_dot_workspace(n, ndots)) return SBLAS_E_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    DotArgs a{n, krylov_cells(n), {}, {}, static_cast<double *>(workspace)};
+    for (int q = 0; q < ndots; ++q) a.x[q] = x[q], a.y[q] = y[q];
+    if (a.cells > 0) launch_dot(s, ndots, a);
+    launch_fold(s, FOLD_OUT, ndots, 0, a.cells, a.part, out);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_krylov_update_f64(int dev, void *stream, int op, int jacobi, int64_t n, const double *scalars, double *const *v, int nv,
+                                double *partial)
+{
+    static const int need[5] = {4, 2, 3, 3, 7}, parts[5] = {1, 0, 0, 0, 2};
+    if (op < SBLAS_KRYLOV_UP_PCG_XR || op > SBLAS_KRYLOV_UP_BICG_XR || n < 0 || n > INT_MAX || !scalars || !v) return SBLAS_E_INVALID;
+    const bool jac = jacobi != 0 && op != SBLAS_KRYLOV_UP_PCG_P && op != SBLAS_KRYLOV_UP_BICG_XR;
+    const int want = need[op] + (jac ? 2 : 0);
+    if (nv < want || nv > 8) return SBLAS_E_INVALID;
+    if (n == 0) return SBLAS_OK;
+    for (int q = 0; q < want; ++q)
+        if (!v[q]) return SBLAS_E_INVALID;
+    if (parts[op] && !partial) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    UpArgs a{n, krylov_cells(n), const_cast<double *>(scalars), partial, {}};
+    for (int q = 0; q < want; ++q) a.v[q] = v[q];
+    launch_update((hipStream_t)stream, op, jac, a);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                                 const void *spmv_plan, int precond, const void *lower_plan, const void *upper_plan, void **plan_out)
+{
+    (void)stream; // nothing is copied: create is host work and one allocation
+    if (!plan_out) return SBLAS_E_INVALID;
+    *plan_out = nullptr;
+    if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
+    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0) return SBLAS_E_INVALID;
+    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
+    if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
+    const int device = resolve_device(dev);
+    if (spmv_plan && sblas_hip_spmv_plan_speaks_for(spmv_plan, device, n, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    if (precond == SBLAS_PRECOND_ILU0) {
+        if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
+        const void *plans[2] = {lower_plan, upper_plan};
+        const int fill[2] = {SBLAS_FILL_LOWER, SBLAS_FILL_UPPER}, diag[2] = {SBLAS_DIAG_UNIT, SBLAS_DIAG_NON_UNIT};
+        for (int k = 0; k < 2; ++k) {
+            int64_t info[12];
+            if (sblas_hip_sptrsv_plan_info(plans[k], info) != SBLAS_OK) return SBLAS_E_INVALID;
+            if (info[0] != n || info[1] != nnz || info[2] != fill[k] || info[3] != diag[k]) return SBLAS_E_INVALID;
+            if (sblas_hip_sptrsv_plan_speaks_for(plans[k], device, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+        }
+    } else if (lower_plan || upper_plan) {
+        return SBLAS_E_INVALID;
+    }
+    std::unique_ptr<KrylovPlan> p(new KrylovPlan);
+    p->dev = device, p->method = method, p->precond = precond, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
+    p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan, p->lower = lower_plan, p->upper = upper_plan;
+    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + (precond == SBLAS_PRECOND_ILU0);
+    if (n == 0) {
+        *plan_out = p.release();
+        return SBLAS_OK;
+    }
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    const size_t block_bytes = pad256(KRYLOV_BLOCK_SLOTS * 8);
+    p->vector_bytes = pad256((size_t)n * 8);
+    p->partial_bytes = pad256((size_t)KRYLOV_MAX_DOTS * (size_t)p->cells * 8);
+    p->bytes = block_bytes + p->partial_bytes + (size_t)p->n_vectors * p->vector_bytes;
+    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) return SBLAS_E_HIP;
+    p->blk = p->buf.at<double>(), p->part = p->buf.at<double>(block_bytes), p->vec = p->buf.at<double>(block_bytes + p->partial_bytes);
+    *plan_out = p.release();
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_plan_info(const void *plan, int64_t out[10])
+{
+    if (!plan || !out) return SBLAS_E_INVALID;
+    const KrylovPlan *p = static_cast<const KrylovPlan *>(plan);
+    int64_t lower[12] = {0}, upper[12] = {0};
+    if (p->precond == SBLAS_PRECOND_ILU0) {
+        sblas_hip_sptrsv_plan_info(p->lower, lower);
+        sblas_hip_sptrsv_plan_info(p->upper, upper);
+    }
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
+    out[6] = (int64_t)p->partial_bytes, out[7] = KRYLOV_BLOCK_SLOTS * 8, out[8] = (int64_t)p->bytes;
+    out[9] = sblas_krylov_launches(p->method, p->precond, lower, upper);
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_plan_destroy(void *plan)
+{
+    delete static_cast<KrylovPlan *>(plan);
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const double *lu_or_dinv, const double *b, double *x, double rtol,
+                           double atol, int64_t max_iter)
+{
+    KrylovPlan *p = static_cast<KrylovPlan *>(plan);
+    if (!p) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || max_iter < 0) return SBLAS_E_INVALID; // a NaN tolerance is refused too
+    p->started = false;
+    if (p->n == 0) {
+        p->started = true;
+        return SBLAS_OK;
+    }
+    if (!b || !x || (p->nnz > 0 && !val) || (p->precond != SBLAS_PRECOND_NONE && !lu_or_dinv)) return SBLAS_E_INVALID;
+    p->val = val, p->pre = p->precond == SBLAS_PRECOND_NONE ? nullptr : lu_or_dinv, p->x = x;
+    hipStream_t s = (hipStream_t)stream;
+    const bool pcg = p->method == SBLAS_KRYLOV_PCG, jac = p->precond == SBLAS_PRECOND_JACOBI;
+    int rc;
+    dot(p, s, b, b);
+    launch_fold(s, FOLD_START_B, 1, !pcg, p->cells, p->part, p->blk, rtol, atol, max_iter);
+    double *bb = const_cast<double *>(b), *dinv = const_cast<double *>(p->pre);
+    if (pcg) {
+        double *r = p->w(V_R), *q = p->w(V_Q), *z = p->precond == SBLAS_PRECOND_NONE ? r : p->w(V_Z);
+        if ((rc = spmv(p, s, x, q)) != SBLAS_OK) return rc;
+        launch_update(s, UP_START_PCG, jac, up_args(p, {r, bb, q, dinv, z, x}));
+        launch_fold(s, FOLD_START_R, jac ? 2 : 1, 0, p->cells, p->part, p->blk);
+        if (p->precond == SBLAS_PRECOND_ILU0) {
+            if ((rc = ilu_apply(p, s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
+            dot(p, s, r, z);
+            launch_fold(s, FOLD_RHO0, 1, 0, p->cells, p->part, p->blk);
+        }
+        launch_update(s, UP_COPY, false, up_args(p, {p->w(V_P), z}));
+    } else {
+        double *v = p->w(B_V);
+        if ((rc = spmv(p, s, x, v)) != SBLAS_OK) return rc;
+        launch_update(s, UP_START_BICG, false, up_args(p, {p->w(B_R), bb, v, p->w(B_RHAT), p->w(B_P), x}));
+        launch_fold(s, FOLD_START_R, 1, 0, p->cells, p->part, p->blk);
+    }
+    if (hipGetLastError() != hipSuccess) return SBLAS_E_HIP;
+    p->started = true;
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_iterate(void *plan, void *stream, int64_t k)
+{
+    const KrylovPlan *p = static_cast<const KrylovPlan *>(plan);
+    if (!p || k < 0 || !p->started) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (p->n == 0) return SBLAS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t it = 0; it < k; ++it) {
+        const int rc = p->method == SBLAS_KRYLOV_PCG ? pcg_iteration(p, s) : bicgstab_iteration(p, s);
+        if (rc != SBLAS_OK) return rc;
+    }
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_krylov_status(const void *plan, void *stream, double out[8])
+{
+    const KrylovPlan *p = static_cast<const KrylovPlan *>(plan);
+    if (!p || !out || !p->started) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    for (int q = 0; q < 8; ++q) out[q] = 0.0;
+    if (p->n == 0) {
+        out[0] = SBLAS_KRYLOV_CONVERGED;
+        return SBLAS_OK;
+    }
+    double h[KRYLOV_BLOCK_SLOTS];
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(h, p->blk, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return SBLAS_E_HIP;
+    long long ih[KRYLOV_BLOCK_SLOTS];
+    memcpy(ih, h, sizeof ih);
+    out[0] = (double)ih[KS_STATUS], out[1] = (double)ih[KS_ITER], out[2] = h[KS_RNORM], out[3] = h[KS_BNORM];
+    out[4] = h[KS_ALPHA], out[5] = h[KS_BETA], out[6] = h[KS_OMEGA], out[7] = (double)ih[KS_WHICH];
+    return SBLAS_OK;
+}
+
+} // extern "C"

@@ -360,6 +360,13 @@ int sblas_hip_sptrsv_plan_info(const void *plan, int64_t out[12])
     return SBLAS_OK;
 }
 
+int sblas_hip_sptrsv_plan_speaks_for(const void *plan, int dev, const int32_t *rowptr, const int32_t *colidx)
+{
+    const SptrsvPlan *p = static_cast<const SptrsvPlan *>(plan);
+    if (!p || p->dev != resolve_device(dev)) return SBLAS_E_INVALID;
+    return rowptr == p->rowptr && colidx == p->colidx ? SBLAS_OK : SBLAS_E_INVALID;
+}
+
 int sblas_hip_sptrsv_plan_order(const void *plan, const int32_t **perm, const int32_t **level_ptr)
 {
     if (!plan) return SBLAS_E_INVALID;

@@ -55,6 +55,10 @@ EXPORTS = [
     "sblas_hip_color_plan_order", "sblas_hip_color_plan_destroy",
     "sblas_hip_permute_plan_create", "sblas_hip_permute_plan_info", "sblas_hip_permute_plan_csr", "sblas_hip_permute_plan_inverse",
     "sblas_hip_permute_plan_values", "sblas_hip_permute_plan_destroy",
+    "sblas_hip_spmv_plan_speaks_for", "sblas_hip_sptrsv_plan_speaks_for",
+    "sblas_krylov_limits", "sblas_krylov_dot_ref", "sblas_krylov_launches", "sblas_hip_krylov_dot_workspace", "sblas_hip_krylov_dot_f64",
+    "sblas_hip_krylov_update_f64", "sblas_hip_krylov_plan_create", "sblas_hip_krylov_plan_info", "sblas_hip_krylov_plan_destroy",
+    "sblas_hip_krylov_start", "sblas_hip_krylov_iterate", "sblas_hip_krylov_status",
 ]
 
 
@@ -306,6 +310,34 @@ def lib():
     L.sblas_hip_permute_plan_values.argtypes = [vp, vp, vp, vp]
     L.sblas_hip_permute_plan_destroy.restype = C.c_int
     L.sblas_hip_permute_plan_destroy.argtypes = [vp]
+    L.sblas_hip_spmv_plan_speaks_for.restype = C.c_int
+    L.sblas_hip_spmv_plan_speaks_for.argtypes = [vp, C.c_int, i64, i64, i64, vp, vp]
+    L.sblas_hip_sptrsv_plan_speaks_for.restype = C.c_int
+    L.sblas_hip_sptrsv_plan_speaks_for.argtypes = [vp, C.c_int, vp, vp]
+    L.sblas_krylov_limits.restype = C.c_int
+    L.sblas_krylov_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_krylov_dot_ref.restype = f64
+    L.sblas_krylov_dot_ref.argtypes = [i64, vp, vp]
+    L.sblas_krylov_launches.restype = i64
+    L.sblas_krylov_launches.argtypes = [C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_hip_krylov_dot_workspace.restype = sz
+    L.sblas_hip_krylov_dot_workspace.argtypes = [i64, C.c_int]
+    L.sblas_hip_krylov_dot_f64.restype = C.c_int
+    L.sblas_hip_krylov_dot_f64.argtypes = [C.c_int, vp, i64, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, vp, sz]
+    L.sblas_hip_krylov_update_f64.restype = C.c_int
+    L.sblas_hip_krylov_update_f64.argtypes = [C.c_int, vp, C.c_int, C.c_int, i64, vp, C.POINTER(vp), C.c_int, vp]
+    L.sblas_hip_krylov_plan_create.restype = C.c_int
+    L.sblas_hip_krylov_plan_create.argtypes = [C.c_int, vp, C.c_int, i64, i64, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp)]
+    L.sblas_hip_krylov_plan_info.restype = C.c_int
+    L.sblas_hip_krylov_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_krylov_plan_destroy.restype = C.c_int
+    L.sblas_hip_krylov_plan_destroy.argtypes = [vp]
+    L.sblas_hip_krylov_start.restype = C.c_int
+    L.sblas_hip_krylov_start.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, i64]
+    L.sblas_hip_krylov_iterate.restype = C.c_int
+    L.sblas_hip_krylov_iterate.argtypes = [vp, vp, i64]
+    L.sblas_hip_krylov_status.restype = C.c_int
+    L.sblas_hip_krylov_status.argtypes = [vp, vp, C.POINTER(f64)]
     _lib = L
     return L
 
@@ -586,6 +618,48 @@ def color_ref(n, rowptr, colidx, seed=0):
     if rc != 0:
         raise _bad_structure("sblas_csr_color", rc, bad.value)
     return color[:n], int(n_colors.value), int(rounds.value)
+
+
+# Krylov solvers: methods, preconditioners, status words and the denominators a breakdown names (SBLAS_KRYLOV_*, SBLAS_PRECOND_*)
+KRYLOV_PCG, KRYLOV_BICGSTAB = 0, 1
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_ILU0 = 0, 1, 2
+KRYLOV_RUNNING, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN, KRYLOV_LIMIT = 0, 1, 2, 3
+KRYLOV_STATUS = {KRYLOV_RUNNING: "running", KRYLOV_CONVERGED: "converged", KRYLOV_BREAKDOWN: "breakdown", KRYLOV_LIMIT: "limit"}
+KRYLOV_DENOM = {0: None, 1: "(p, q)", 2: "rho", 3: "(r^, v)", 4: "(t, t)", 5: "omega"}
+KRYLOV_UPDATES = {"pcg_xr": 0, "pcg_p": 1, "bicg_p": 2, "bicg_s": 3, "bicg_xr": 4}
+_KRYLOV_METHOD = {"pcg": KRYLOV_PCG, "bicgstab": KRYLOV_BICGSTAB}
+
+
+def krylov_limits():
+    """The Krylov solvers' limits (sblas_krylov_limits): dict(cell, width, pcg_vectors, bicgstab_vectors, max_dots) -- the
+    elements of a dot product's cell, the lanes of its second stage, the work vectors each method owns (ILU(0) adds the
+    solves' temporary) and the dots one pass over memory can carry."""
+    out = (C.c_int64 * 5)()
+    check(lib().sblas_krylov_limits(out), "sblas_krylov_limits")
+    return dict(cell=int(out[0]), width=int(out[1]), pcg_vectors=int(out[2]), bicgstab_vectors=int(out[3]), max_dots=int(out[4]))
+
+
+def krylov_dot_ref(x, y):
+    """The pinned dot product restated on the host (sblas_krylov_dot_ref), on numpy arrays -> float"""
+    x = np.ascontiguousarray(x, np.float64).ravel()
+    y = np.ascontiguousarray(y, np.float64).ravel()
+    if len(x) != len(y):
+        raise SblasError("x has %d entries, y %d" % (len(x), len(y)))
+    return float(lib().sblas_krylov_dot_ref(len(x), x.ctypes.data, y.ctypes.data))
+
+
+def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches=0):
+    """Launches of one iteration (sblas_krylov_launches).  precond: None, "jacobi" or "ilu0"; lower_launches /
+    upper_launches: SptrsvPlan.info()["launches"] of the two solves, read with "ilu0" only."""
+    if method not in _KRYLOV_METHOD:
+        raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
+    code = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0}.get(precond, -1)
+    lo, up = (C.c_int64 * 12)(), (C.c_int64 * 12)()
+    lo[5], up[5] = int(lower_launches), int(upper_launches)
+    n = int(lib().sblas_krylov_launches(_KRYLOV_METHOD[method], code, lo, up))
+    if n < 0:
+        raise SblasError("sblas_krylov_launches refused its arguments")
+    return n
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -1974,6 +2048,249 @@ def csr_color(A, seed=0, stream=None):
     finally:
         plan.destroy()
     return color, perm, color_ptr
+
+
+# ------------------------------------------------------------------------------------------
+# Krylov solvers on a plan, resident on the device: PCG and BiCGStab (sblas_hip_krylov_*)
+# ------------------------------------------------------------------------------------------
+def _krylov_vector(name, t, n, device=None):
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+    if t.dtype != torch.float64:
+        raise SblasError("%s must be float64, got %s" % (name, t.dtype))
+    if t.dim() != 1 or not t.is_contiguous() or t.numel() != n:
+        raise SblasError("%s must be contiguous with %d entries, got shape %s" % (name, n, tuple(t.shape)))
+    if device is not None and t.device != device:
+        raise SblasError("%s is on %s, the plan on %s" % (name, t.device, device))
+
+
+def krylov_dots(pairs, out=None, workspace=None, stream=None):
+    """The pinned dot products (x, y) of up to three pairs in ONE pass over memory (sblas_hip_krylov_dot_f64): a device
+    tensor of len(pairs) doubles, each with exactly the bits krylov_dot gives alone.  No synchronisation; with out and
+    workspace (a float64 tensor of at least len(pairs) * ceil(n / cell) entries) given, nothing is allocated."""
+    import torch
+    k = len(pairs)
+    if not 1 <= k <= 3:
+        raise SblasError("one to three pairs, not %d" % k)
+    n = pairs[0][0].numel() if isinstance(pairs[0][0], torch.Tensor) else -1
+    for q, (x, y) in enumerate(pairs):
+        _krylov_vector("x[%d]" % q, x, n), _krylov_vector("y[%d]" % q, y, n, x.device)
+    device = pairs[0][0].device
+    if out is None:
+        out = torch.empty(k, dtype=torch.float64, device=device)
+    _krylov_vector("out", out, k, device)
+    need = int(lib().sblas_hip_krylov_dot_workspace(n, k))
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous():
+        raise SblasError("workspace must be a contiguous float64 GPU tensor")
+    xs = (C.c_void_p * k)(*[x.data_ptr() if n else None for x, _ in pairs])
+    ys = (C.c_void_p * k)(*[y.data_ptr() if n else None for _, y in pairs])
+    with torch.cuda.device(device):
+        check(lib().sblas_hip_krylov_dot_f64(-1, _stream(stream), n, k, xs, ys, out.data_ptr(), workspace.data_ptr(),
+                                             workspace.numel() * 8), "sblas_hip_krylov_dot_f64")
+    return out
+
+
+def krylov_dot(x, y, out=None, workspace=None, stream=None):
+    """The pinned dot product (x, y): a one-element device tensor, no synchronisation.  Its bits are krylov_dot_ref's: a
+    function of n and the two vectors alone."""
+    return krylov_dots([(x, y)], out=out, workspace=workspace, stream=stream)
+
+
+def krylov_update(op, scalars, vectors, partial=None, jacobi=False, stream=None):
+    """One fused update of the solvers on its own (sblas_hip_krylov_update_f64).  op: a key of KRYLOV_UPDATES; scalars: a
+    device block of 16 eight-byte slots ([0] status as int64 -- anything but 0 and the call writes nothing -- [4] alpha,
+    [5] beta, [6] omega); vectors: the op's vectors in the header's order, n entries each; partial: float64, at least
+    2 * ceil(n / cell) entries, for the ops that are also a dot's first stage."""
+    import torch
+    if op not in KRYLOV_UPDATES:
+        raise SblasError("op must be one of %s, not %r" % (sorted(KRYLOV_UPDATES), op))
+    n = vectors[0].numel() if len(vectors) and isinstance(vectors[0], torch.Tensor) else -1
+    for q, t in enumerate(vectors):
+        _krylov_vector("vectors[%d]" % q, t, n)
+    _krylov_vector("scalars", scalars, 16)
+    if partial is not None:
+        _krylov_vector("partial", partial, partial.numel() if isinstance(partial, torch.Tensor) else -1)
+        if partial.numel() < 2 * -(-n // krylov_limits()["cell"]):
+            raise SblasError("partial is too short")
+    v = (C.c_void_p * len(vectors))(*[t.data_ptr() if n else None for t in vectors])
+    with torch.cuda.device(scalars.device):
+        check(lib().sblas_hip_krylov_update_f64(-1, _stream(stream), KRYLOV_UPDATES[op], 1 if jacobi else 0, n, scalars.data_ptr(), v,
+                                                len(vectors), partial.data_ptr() if partial is not None and partial.numel() else None),
+              "sblas_hip_krylov_update_f64")
+
+
+class KrylovPlan:
+    """A Krylov solver for A x = b on the n x n CSR structure (rowptr, colidx), int32 indices, resident on the device
+    (sblas_hip_krylov_plan_create).  method: "pcg" (A symmetric positive definite) or "bicgstab".  spmv_plan: an SpmvPlan on
+    the same tensors, or None.  precond: None, "jacobi" (start / solve take dinv, the inverse diagonal) or an Ilu0Plan on
+    the same tensors (they take lu, its factor; a pair (lower, upper) of SptrsvPlans serves too).  The plan owns the work
+    vectors, the partial sums and the scalar block, and keeps the tensors and plans it was given alive.
+
+    start() forms r = b - A x and the first direction; iterate(k) enqueues k iterations without allocating or
+    synchronising (graph-capturable); status() is the one call that synchronises.  Once the stopping test
+    |r| <= max(rtol |b|, atol) is met on the device, the iterations already enqueued change nothing: x, the count and
+    |r| are those of the iteration that met it, whatever check_every is.  Every bit is pinned (include/sblas_hip.h).
+
+    A system in the multicolour order is the caller's composition:
+        color = ColorPlan(n, rowptr, colidx); perm = color.permute(rowptr, colidx); rp, ci, _ = perm.csr()
+        ilu = Ilu0Plan(n, rp, ci); val_b = perm.values(val); lu = ilu.factor(val_b)
+        x_b, st = KrylovPlan(n, rp, ci, precond=ilu).solve(val_b, perm.to_permuted(b), lu=lu)
+        x = perm.from_permuted(x_b)"""
+
+    def __init__(self, n, rowptr, colidx, method="pcg", spmv_plan=None, precond=None, stream=None):
+        import torch
+        self.handle = None
+        if method not in _KRYLOV_METHOD:
+            raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
+        self.n, self.method = n, method
+        self.nnz = _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        self.spmv_plan, self.precond = spmv_plan, precond
+        lower = upper = None
+        if precond is None:
+            self.precond_kind = PRECOND_NONE
+        elif isinstance(precond, str) and precond == "jacobi":
+            self.precond_kind = PRECOND_JACOBI
+        elif isinstance(precond, Ilu0Plan):
+            self.precond_kind = PRECOND_ILU0
+            lower, upper = precond.solvers()
+        elif isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
+            self.precond_kind = PRECOND_ILU0
+            lower, upper = precond
+        else:
+            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan or a pair of SptrsvPlans, not %r" % (precond,))
+        if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
+            raise SblasError("spmv_plan must be an SpmvPlan or None")
+        self._solvers = (lower, upper)
+        self._keep = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_krylov_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                    colidx.data_ptr() if self.nnz else None,
+                                                    spmv_plan.handle if spmv_plan is not None else None, self.precond_kind,
+                                                    lower.handle if lower is not None else None,
+                                                    upper.handle if upper is not None else None, C.byref(h))
+        check(rc, "sblas_hip_krylov_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 10)()
+        check(lib().sblas_hip_krylov_plan_info(self.handle, out), "sblas_hip_krylov_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
+                    precond=(None, "jacobi", "ilu0")[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
+                    scalar_bytes=int(out[7]), bytes=int(out[8]), launches=int(out[9]))
+
+    def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
+        """Begins a solve: x on entry is the initial guess and is updated in place by iterate().  lu: the ILU(0) factor
+        (precond an Ilu0Plan); dinv: the inverse diagonal (precond "jacobi").  Every refusal comes before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device), _krylov_vector("b", b, self.n, self.device)
+        _krylov_vector("x", x, self.n, self.device)
+        pre = None
+        if self.precond_kind == PRECOND_ILU0:
+            if lu is None:
+                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
+            _krylov_vector("lu", lu, self.nnz, self.device)
+            pre = lu
+        elif self.precond_kind == PRECOND_JACOBI:
+            if dinv is None:
+                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
+            _krylov_vector("dinv", dinv, self.n, self.device)
+            pre = dinv
+        if self.n and x.data_ptr() == b.data_ptr():
+            raise SblasError("x must not be b")
+        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
+            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_krylov_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                              pre.data_ptr() if pre is not None and pre.numel() else None,
+                                              b.data_ptr() if self.n else None, x.data_ptr() if self.n else None,
+                                              float(rtol), float(atol), int(max_iter))
+        check(rc, "sblas_hip_krylov_start")
+        self._keep = (val, b, x, pre)
+
+    def iterate(self, k, stream=None):
+        """Enqueues k iterations: allocates nothing, never synchronises, graph-capturable as a chain."""
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_krylov_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_krylov_iterate")
+
+    def status(self, stream=None):
+        """Copies the scalar block back and synchronises the stream -> dict(status, code, iterations, rnorm, bnorm, alpha,
+        beta, omega, breakdown): status is "running", "converged", "breakdown" or "limit"; breakdown names the zero or
+        non-finite denominator (a value of KRYLOV_DENOM) or is None."""
+        import torch
+        out = (C.c_double * 8)()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_krylov_status(self.handle, _stream(stream), out), "sblas_hip_krylov_status")
+        return dict(status=KRYLOV_STATUS[int(out[0])], code=int(out[0]), iterations=int(out[1]), rnorm=float(out[2]), bnorm=float(out[3]),
+                    alpha=float(out[4]), beta=float(out[5]), omega=float(out[6]), breakdown=KRYLOV_DENOM[int(out[7])])
+
+    def solve(self, val, b, x=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
+        """start(), then iterate(check_every) / status() until the status is not "running" -> (x, status dict).  x: the
+        initial guess, updated in place (zeros made here when None).  The result does not depend on check_every."""
+        import torch
+        if int(check_every) < 1:
+            raise SblasError("check_every must be at least 1")
+        if x is None:
+            _krylov_vector("b", b, self.n, self.device)
+            x = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        self.start(val, b, x, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
+        while True:
+            self.iterate(int(check_every), stream=stream)
+            st = self.status(stream=stream)
+            if st["code"] != KRYLOV_RUNNING:
+                return x, st
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_krylov_plan_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _krylov_one_shot(method, A, b, precond, x, kw):
+    import torch
+    n, rowptr, colidx, val = A
+    if precond not in (None, "jacobi", "ilu0"):
+        raise SblasError("precond must be None, 'jacobi' or 'ilu0', not %r" % (precond,))
+    ilu = plan = None
+    lu = dinv = None
+    try:
+        if precond is not None:                                           # both read the diagonal's places off the ILU(0) plan
+            ilu = Ilu0Plan(n, rowptr, colidx)
+            if precond == "ilu0":
+                lu = ilu.factor(val)
+            else:
+                dinv = ilu.pivots(val).reciprocal_()
+        plan = KrylovPlan(n, rowptr, colidx, method=method, precond=ilu if precond == "ilu0" else precond)
+        return plan.solve(val, b, x=x, lu=lu, dinv=dinv, **kw)
+    finally:
+        if plan is not None:
+            plan.destroy()
+        if ilu is not None:
+            ilu.destroy()
+
+
+def pcg(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
+    """x with A x = b by preconditioned CG, one shot: A = (n, rowptr, colidx, val) as GPU tensors, symmetric positive
+    definite; precond None, "jacobi" or "ilu0" (rows sorted with a stored diagonal for the last two).  -> (x, status
+    dict).  The plans made here are destroyed before returning."""
+    return _krylov_one_shot("pcg", A, b, precond, x, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
+
+
+def bicgstab(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
+    """x with A x = b by preconditioned BiCGStab, one shot, as pcg(); A need not be symmetric."""
+    return _krylov_one_shot("bicgstab", A, b, precond, x, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
 
 
 # ------------------------------------------------------------------------------------------
