@@ -540,6 +540,17 @@ int sblas_sptrsv_levels(int64_t n, const int32_t *rowptr, const int32_t *colidx,
 int sblas_sptrsv_schedule(int64_t n_levels, const int64_t *widths, int flags, int64_t chain_rows,
                           uint8_t *kind_out /* up to n_levels */, int64_t *launch_first_out /* up to n_levels + 1 */,
                           int64_t *n_launches);
+/* The lanes of a level plan, on HOST arrays (no GPU call; testable alone): what the solves' and ILU(0)'s creates upload,
+ * with the neutral record (row, unit number within the row) in place of theirs.  level[i] in [0, n_levels) is row i's
+ * level; only the differences of rowptr are read.  perm_out: the rows by (level, row); level l is perm_out[level_ptr_out[l]
+ * .. level_ptr_out[l + 1] - 1] and the units level_unit_ptr_out[l] .. level_unit_ptr_out[l + 1] - 1.  A unit is four lanes.
+ * A row of p stored entries owns G(p) / 4 consecutive units, numbered unit_q_out = 0 .. G(p) / 4 - 1, and its first unit
+ * lies a multiple of G(p) / 4 units from the start of its level; rows ascend inside a level; a unit that pads the
+ * alignment has unit_row_out = -1 and unit_q_out = 0.  *n_units = the units of all levels.  Every output array may be
+ * NULL: a call with all of them NULL sizes the unit arrays.  A level outside [0, n_levels) is SBLAS_E_INVALID. */
+int sblas_sptrsv_pack(int64_t n, const int32_t *rowptr, const int32_t *level, int64_t n_levels, int32_t *perm_out /* n */,
+                      int32_t *level_ptr_out /* n_levels + 1 */, int64_t *level_unit_ptr_out /* n_levels + 1 */,
+                      int32_t *unit_row_out /* *n_units */, int32_t *unit_q_out /* *n_units */, int64_t *n_units);
 /* create: copies rowptr and colidx to the host once, runs the host rule, and uploads the rows ordered by (level, row)
  * with each row's extent and diagonal position, the level pointer, and every level's rows packed into four-lane units
  * (a row of G lanes is G / 4 of them).  Synchronises `stream`.

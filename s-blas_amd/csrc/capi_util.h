@@ -1,10 +1,12 @@
-// capi_util.h -- helpers of the C-ABI entry points (capi.hip, transpose.hip, coo.hip): argument checks, the device switch of a
-// call and the device buffers a plan owns.  Internal to each translation unit: nothing here is exported.
+// capi_util.h -- helpers of the C-ABI entry points (capi.hip, transpose.hip, coo.hip, the structure plans): argument checks,
+// the device switch of a call, the device buffers a plan owns, and a structure's way to the host and a plan's to the device.
+// Internal to each translation unit: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 #include <utility>
+#include <vector>
 #include "../../include/sblas_hip.h"
 
 namespace {
@@ -90,5 +92,43 @@ private:
     void *p_ = nullptr;
     int dev_ = -1;
 };
+
+// (rowptr, colidx) of an n-row structure (n > 0) brought to the host once on stream s, which is synchronised: every check
+// and the whole schedule of a structure plan are host work.  A rowptr that does not end at nnz is refused here, as row
+// n - 1 and before every other check: the host rules follow rowptr into a colidx of nnz entries.
+inline int fetch_structure(hipStream_t s, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                           std::vector<int32_t> &h_rowptr, std::vector<int32_t> &h_colidx, int64_t *bad_row)
+{
+    h_rowptr.resize((size_t)n + 1), h_colidx.resize((size_t)nnz);
+    hipError_t e = hipMemcpyAsync(h_rowptr.data(), rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(h_colidx.data(), colidx, (size_t)nnz * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return SBLAS_E_HIP;
+    if (h_rowptr[n] != nnz) {
+        if (bad_row) *bad_row = n - 1;
+        return SBLAS_E_INVALID;
+    }
+    return SBLAS_OK;
+}
+
+// A host array on its way into a plan's buffer; offset: where upload_segments() put it.
+struct Segment {
+    const void *src;
+    size_t bytes, offset;
+    template <typename T> explicit Segment(const std::vector<T> &v) : src(v.data()), bytes(v.size() * sizeof(T)), offset(0) {}
+};
+
+// Allocates buf on dev for the segments one after another, each padded to 16 bytes, and uploads them on s, which is
+// synchronised: the host arrays are read until here.  *total: the bytes allocated.
+inline hipError_t upload_segments(DeviceBuffer &buf, int dev, hipStream_t s, Segment *seg, int count, size_t *total)
+{
+    *total = 0;
+    for (int k = 0; k < count; ++k) seg[k].offset = *total, *total += (seg[k].bytes + 15) / 16 * 16;
+    hipError_t e = buf.alloc(dev, *total);
+    for (int k = 0; k < count && e == hipSuccess; ++k)
+        e = hipMemcpyAsync(buf.at<char>(seg[k].offset), seg[k].src, seg[k].bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
 
 } // namespace

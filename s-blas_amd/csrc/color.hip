@@ -211,15 +211,10 @@ int sblas_hip_color_plan_create(int dev, void *stream, int64_t n, int64_t nnz, c
     hipStream_t s = (hipStream_t)stream;
 
     // the structure comes to the host once, as in the solves: the check, and which lane group takes each vertex
-    std::vector<int32_t> h_rowptr((size_t)n + 1), h_colidx((size_t)nnz);
-    hipError_t e = hipMemcpyAsync(h_rowptr.data(), rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(h_colidx.data(), colidx, (size_t)nnz * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return SBLAS_E_HIP;
-    if (h_rowptr[n] != nnz) { // first, as in the solves: the host rule follows rowptr into a colidx of nnz entries
-        if (bad_row) *bad_row = n - 1;
-        return SBLAS_E_INVALID;
-    }
+    std::vector<int32_t> h_rowptr, h_colidx;
+    const int frc = fetch_structure(s, n, nnz, rowptr, colidx, h_rowptr, h_colidx, bad_row);
+    if (frc != SBLAS_OK) return frc;
+    hipError_t e = hipSuccess;
     std::vector<int32_t> lists[3]; // the vertices of 4, 16 and 64 lanes, ascending
     {
         std::vector<int32_t> h_tptr, h_tidx;

@@ -1,8 +1,7 @@
-// ilu0.h -- the sizes ilu0.hip's kernels and ilu0_plan.cpp's host rule agree on, and the host rule's internal interface.
+// ilu0.h -- the sizes ilu0.hip's kernels and ilu0_plan.cpp's host rule agree on, and the kernels' unit record.
 // No HIP in here: ilu0_plan.cpp is testable on a CPU box.
 #pragma once
 #include <stdint.h>
-#include <vector>
 #include "sptrsv.h"
 
 namespace sblas {
@@ -22,17 +21,9 @@ constexpr int ILU0_LDS_PER_LANE = 4;
 constexpr int64_t ILU0_LDS_MAX = 64 * ILU0_LDS_PER_LANE;
 static_assert(SPTRSV_G4_MAX <= 4 * ILU0_LDS_PER_LANE && SPTRSV_G16_MAX <= 16 * ILU0_LDS_PER_LANE, "a row fits its group's slice");
 
-// A unit is four lanes of a launch, as in the solves.  A row of G(p) lanes is G(p) / 4 consecutive units that all carry
-// the row's record, aligned to G(p) lanes inside its level, so that a lane's place in its row is its place in the level
-// modulo G(p); a unit that pads the alignment has row = -1.
+// ILU(0)'s unit record (level_plan.h): every unit of a row carries the row's record; a unit that pads has row = -1.
 struct Ilu0Unit {
     int32_t row, beg, diag, end; // the row's extent in val and the position of its diagonal
 };
-static_assert(sizeof(Ilu0Unit) == 16, "one 16-byte load per unit");
-
-// The rows by (level, row) packed into units: level l is units[level_unit_ptr[l] .. level_unit_ptr[l + 1] - 1].
-// level: from sblas_sptrsv_levels(LOWER, NON_UNIT); diag_pos: from sblas_ilu0_check.  widths[l]: rows of level l.
-void ilu0_pack(int64_t n, const int32_t *rowptr, const int32_t *diag_pos, const int32_t *level, int64_t n_levels,
-               std::vector<Ilu0Unit> &units, std::vector<int64_t> &level_unit_ptr, std::vector<int64_t> &widths);
 
 } // namespace sblas

@@ -3,11 +3,7 @@
 // in one CSR, which is what two triangular-solve plans (lower / unit, upper) on (rowptr, colidx, lu) consume.
 //
 // The schedule is the lower solve's: row i needs the finished rows k < i it stores an entry for.  A factorisation is a
-// fixed sequence of launches of two kernels, as a solve is:
-//   wide   one level a launch; the level's rows, in ascending row order, spread over the grid;
-//   chain  one workgroup walks a run of consecutive levels with __syncthreads() between them.
-// Nothing waits across workgroups: no flag polling, no cooperative launch, no grid barrier, no atomics.  The only
-// synchronisation is the kernel boundary and __syncthreads(), and every loop's trip count comes from the structure.
+// fixed sequence of wide and chain launches, as a solve is, on the same walks (level_kernels.h).
 //
 // factor_row() is the one expression of a row, shared by both kernels.  A row of p stored entries belongs to G(p) lanes
 // (the solves' G).  Two tiers:
@@ -26,12 +22,8 @@
 //
 // Visibility of row k.  Its values are read from lu, never from val, with plain global loads, and were stored with
 // plain global stores by an earlier launch (the kernel boundary orders everything) or by this workgroup before the
-// barrier.  __syncthreads() is a workgroup-scope release and acquire: every wave waits for its stores (s_waitcnt
-// vmcnt(0)) before it arrives, and no load of lu for a later level is issued before it leaves (what is fetched ahead of
-// the barrier is plan data, which no kernel writes).  The waves of one workgroup run on one CU and share its vector L1,
-// which is write-through and sees the CU's own stores; the hazard of a stale L1 line exists only between CUs, and no
-// other workgroup runs in a chain launch.  lu and val are not __restrict__: they may be the same array, and lu is read
-// and written in one launch, which also keeps it off the scalar path.
+// barrier of the chain walk, whose argument is in level_kernels.h.  lu and val are not __restrict__: they may be the same
+// array, and lu is read and written in one launch, which also keeps it off the scalar path.
 //
 // Results contract: each entry receives its updates one after another in ascending k, each as a rounded product and a
 // rounded difference; no sum is folded across lanes.  The bits of lu are a function of val and the pattern alone.
@@ -41,20 +33,14 @@
 #include <memory>
 #include <vector>
 #include "../../include/sblas_hip.h"
-#include "capi_util.h"
 #include "ilu0.h"
+#include "level_kernels.h"
 
 using namespace sblas;
 
 namespace {
 
 constexpr Ilu0Unit NO_UNIT{-1, 0, 0, 0};
-
-__device__ __forceinline__ Ilu0Unit load_unit(const Ilu0Unit *__restrict__ units, int64_t u)
-{
-    const int4 v = *reinterpret_cast<const int4 *>(units + u);
-    return Ilu0Unit{v.x, v.y, v.z, v.w};
-}
 
 __device__ __forceinline__ double sub_prod(double w, double l, double u)
 {
@@ -152,8 +138,7 @@ __global__ __launch_bounds__(ILU0_WIDE_THREADS) void ilu0_wide_kernel(int64_t fi
 {
     __shared__ int32_t lcol[ILU0_WIDE_THREADS * ILU0_LDS_PER_LANE];
     __shared__ double lval[ILU0_WIDE_THREADS * ILU0_LDS_PER_LANE];
-    const int64_t un = ((int64_t)blockIdx.x * ILU0_WIDE_THREADS + threadIdx.x) >> 2;
-    factor_row(un < count ? load_unit(units, first + un) : NO_UNIT, rowptr, colidx, diag_pos, val, lu, lcol, lval);
+    factor_row(wide_unit<ILU0_WIDE_THREADS>(first, count, units, NO_UNIT), rowptr, colidx, diag_pos, val, lu, lcol, lval);
 }
 
 // ---- chain: levels l0 .. l1 - 1 in one workgroup; a level wider than the workgroup is looped over --------------------
@@ -166,44 +151,15 @@ __global__ __launch_bounds__(ILU0_CHAIN_THREADS) void ilu0_chain_kernel(int64_t 
 {
     __shared__ int32_t lcol[ILU0_CHAIN_THREADS * ILU0_LDS_PER_LANE];
     __shared__ double lval[ILU0_CHAIN_THREADS * ILU0_LDS_PER_LANE];
-    constexpr int PASS = ILU0_CHAIN_THREADS / 4; // units of one pass
-    const int mine = threadIdx.x >> 2;
-    // The plan's arrays do not depend on lu: the next level's extent and this thread's first unit of it are fetched
-    // while the current level is factored.
-    int64_t first = level_unit_ptr[l0], end = level_unit_ptr[l0 + 1];
-    Ilu0Unit cur = mine < end - first ? load_unit(units, first + mine) : NO_UNIT;
-    for (int64_t l = l0; l < l1; ++l) {
-        const int64_t count = end - first, next_end = l + 1 < l1 ? level_unit_ptr[l + 2] : end;
-        const Ilu0Unit next = l + 1 < l1 && mine < next_end - end ? load_unit(units, end + mine) : NO_UNIT;
-        factor_row(cur, rowptr, colidx, diag_pos, val, lu, lcol, lval);
-        for (int64_t u0 = PASS; u0 < count; u0 += PASS) { // the same trip count in every thread
-            const int64_t un = u0 + mine;
-            factor_row(un < count ? load_unit(units, first + un) : NO_UNIT, rowptr, colidx, diag_pos, val, lu, lcol, lval);
-        }
-        __syncthreads(); // this level's rows of lu, stored by this workgroup, are what the next level loads
-        first = end, end = next_end, cur = next;
-    }
+    chain_walk<ILU0_CHAIN_THREADS>(l0, l1, level_unit_ptr, units, NO_UNIT,
+                                   [&](const Ilu0Unit u) { factor_row(u, rowptr, colidx, diag_pos, val, lu, lcol, lval); });
 }
 
-struct Launch {
-    int64_t l0, l1; // levels
-    bool chain;
-};
-
-struct Ilu0Plan {
-    int dev = -1, flags = 0;
-    int64_t n = 0, nnz = 0, levels = 0, wide = 0, chains = 0, widest = 0, longest = 0, long_rows = 0, chain_rows = 0;
-    size_t bytes = 0;
-    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
-    DeviceBuffer buf;                                   // units | level_unit_ptr | diag_pos
+struct Ilu0Plan : LevelPlan { // buf: units | level_unit_ptr | diag_pos
+    int64_t long_rows = 0;
     Ilu0Unit *units = nullptr;
-    int64_t *level_unit_ptr = nullptr;
     int32_t *diag_pos = nullptr;
-    std::vector<int64_t> h_level_unit_ptr;
-    std::vector<Launch> launches;
 };
-
-inline size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
 
 } // namespace
 
@@ -212,74 +168,37 @@ extern "C" {
 int sblas_hip_ilu0_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, int flags,
                                int64_t chain_rows, void **plan_out, int64_t *bad_row)
 {
-    if (bad_row) *bad_row = -1;
-    if (!plan_out) return SBLAS_E_INVALID;
-    *plan_out = nullptr;
-    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX || chain_rows < 0) return SBLAS_E_INVALID;
-    if (flags != SBLAS_SPTRSV_AUTO && flags != SBLAS_SPTRSV_PER_LEVEL && flags != SBLAS_SPTRSV_CHAIN_ONLY) return SBLAS_E_INVALID;
-    if ((n > 0 && !rowptr) || (nnz > 0 && !colidx)) return SBLAS_E_INVALID;
     std::unique_ptr<Ilu0Plan> p(new Ilu0Plan);
-    p->dev = resolve_device(dev), p->flags = flags, p->n = n, p->nnz = nnz;
-    p->rowptr = rowptr, p->colidx = colidx;
-    p->chain_rows = chain_rows > 0 ? chain_rows : ILU0_CHAIN_ROWS;
+    if (!level_plan_begin(*p, dev, n, nnz, rowptr, colidx, flags, chain_rows, ILU0_CHAIN_ROWS, plan_out, bad_row)) return SBLAS_E_INVALID;
     if (n == 0) {
-        if (nnz != 0) return SBLAS_E_INVALID;
         *plan_out = p.release();
         return SBLAS_OK;
     }
     DeviceScope scope(dev);
     if (scope.err != hipSuccess) return SBLAS_E_HIP;
     hipStream_t s = (hipStream_t)stream;
-
-    // the structure comes to the host once; every check and the whole schedule are host work
-    std::vector<int32_t> h_rowptr((size_t)n + 1), h_colidx((size_t)nnz);
-    hipError_t e = hipMemcpyAsync(h_rowptr.data(), rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(h_colidx.data(), colidx, (size_t)nnz * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return SBLAS_E_HIP;
-    if (h_rowptr[n] != nnz) { // first, as in the solves: the host rule follows rowptr into a colidx of nnz entries
-        if (bad_row) *bad_row = n - 1;
-        return SBLAS_E_INVALID;
-    }
-    std::vector<int32_t> dpos((size_t)n), level((size_t)n);
-    int rc = sblas_ilu0_check(n, h_rowptr.data(), h_colidx.data(), dpos.data(), bad_row);
+    std::vector<int32_t> h_rowptr, h_colidx, dpos((size_t)n), level((size_t)n);
+    int rc = fetch_structure(s, n, nnz, rowptr, colidx, h_rowptr, h_colidx, bad_row);
     if (rc != SBLAS_OK) return rc;
-    int64_t n_levels = 0;
-    rc = sblas_sptrsv_levels(n, h_rowptr.data(), h_colidx.data(), SBLAS_FILL_LOWER, SBLAS_DIAG_NON_UNIT, level.data(), &n_levels, bad_row);
+    rc = sblas_ilu0_check(n, h_rowptr.data(), h_colidx.data(), dpos.data(), bad_row);
     if (rc != SBLAS_OK) return rc;
-    p->levels = n_levels;
+    rc = sblas_sptrsv_levels(n, h_rowptr.data(), h_colidx.data(), SBLAS_FILL_LOWER, SBLAS_DIAG_NON_UNIT, level.data(), &p->levels, bad_row);
+    if (rc != SBLAS_OK) return rc;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t len = (int64_t)h_rowptr[i + 1] - h_rowptr[i];
         p->longest = len > p->longest ? len : p->longest;
         p->long_rows += len > ILU0_LDS_MAX;
     }
-    std::vector<Ilu0Unit> units;
-    std::vector<int64_t> widths;
-    ilu0_pack(n, h_rowptr.data(), dpos.data(), level.data(), n_levels, units, p->h_level_unit_ptr, widths);
-    for (int64_t w : widths) p->widest = w > p->widest ? w : p->widest;
+    LevelOrder o;
+    std::vector<Ilu0Unit> units; // every unit of a row carries the row's record
+    const auto unit_of = [&](int32_t i, int32_t) { return Ilu0Unit{i, h_rowptr[i], dpos[i], h_rowptr[i + 1]}; };
+    level_pack(n, h_rowptr.data(), level.data(), p->levels, unit_of, NO_UNIT, o, units);
+    if (level_launches(o.widths, flags, p->chain_rows, p->sched) != SBLAS_OK) return SBLAS_E_INVALID;
 
-    // the launches
-    std::vector<uint8_t> kind((size_t)n_levels);
-    std::vector<int64_t> lfirst((size_t)n_levels + 1);
-    int64_t n_launches = 0;
-    if (sblas_sptrsv_schedule(n_levels, widths.data(), flags, p->chain_rows, kind.data(), lfirst.data(), &n_launches) != SBLAS_OK)
-        return SBLAS_E_INVALID;
-    for (int64_t q = 0; q < n_launches; ++q) {
-        const bool chain = kind[q] == SBLAS_SPTRSV_LAUNCH_CHAIN;
-        p->launches.push_back(Launch{lfirst[q], lfirst[q + 1], chain});
-        ++(chain ? p->chains : p->wide);
-    }
-
-    const size_t o_up = units.size() * sizeof(Ilu0Unit), o_dpos = o_up + pad16(((size_t)n_levels + 1) * 8);
-    const size_t total = o_dpos + pad16((size_t)n * 4);
-    if (p->buf.alloc(p->dev, total) != hipSuccess) return SBLAS_E_HIP;
-    p->bytes = total;
-    p->units = p->buf.at<Ilu0Unit>(), p->level_unit_ptr = p->buf.at<int64_t>(o_up), p->diag_pos = p->buf.at<int32_t>(o_dpos);
-    e = hipMemcpyAsync(p->units, units.data(), units.size() * sizeof(Ilu0Unit), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->level_unit_ptr, p->h_level_unit_ptr.data(), ((size_t)n_levels + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->diag_pos, dpos.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s); // the host vectors are read until here
-    if (e != hipSuccess) return SBLAS_E_HIP;
+    Segment seg[3] = {Segment(units), Segment(o.level_unit_ptr), Segment(dpos)};
+    if (upload_segments(p->buf, p->dev, s, seg, 3, &p->bytes) != hipSuccess) return SBLAS_E_HIP;
+    p->units = p->buf.at<Ilu0Unit>(), p->level_unit_ptr = p->buf.at<int64_t>(seg[1].offset), p->diag_pos = p->buf.at<int32_t>(seg[2].offset);
+    p->h_level_unit_ptr = std::move(o.level_unit_ptr);
     *plan_out = p.release();
     return SBLAS_OK;
 }
@@ -288,8 +207,9 @@ int sblas_hip_ilu0_plan_info(const void *plan, int64_t out[12])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const Ilu0Plan *p = static_cast<const Ilu0Plan *>(plan);
-    out[0] = p->n, out[1] = p->nnz, out[2] = p->levels, out[3] = (int64_t)p->launches.size(), out[4] = p->wide, out[5] = p->chains;
-    out[6] = p->widest, out[7] = p->longest, out[8] = p->long_rows, out[9] = (int64_t)p->bytes, out[10] = p->flags, out[11] = p->chain_rows;
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->levels, out[3] = (int64_t)p->sched.launches.size(), out[4] = p->sched.wide;
+    out[5] = p->sched.chains, out[6] = p->sched.widest, out[7] = p->longest, out[8] = p->long_rows, out[9] = (int64_t)p->bytes;
+    out[10] = p->flags, out[11] = p->chain_rows;
     return SBLAS_OK;
 }
 
@@ -310,19 +230,17 @@ int sblas_hip_ilu0_f64_i32_planned(const void *plan, void *stream, const int32_t
                                    double *lu)
 {
     const Ilu0Plan *p = static_cast<const Ilu0Plan *>(plan);
-    if (!p) return SBLAS_E_INVALID;
-    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
-    if (rowptr != p->rowptr || colidx != p->colidx) return SBLAS_E_INVALID;
+    const int rc = level_plan_speaks_for(p, -1, rowptr, colidx);
+    if (rc != SBLAS_OK) return rc;
     if (p->n == 0) return SBLAS_OK;
     if (!val || !lu) return SBLAS_E_INVALID; // n > 0: every row stores its diagonal
     hipStream_t s = (hipStream_t)stream;
-    for (const Launch &q : p->launches) {
+    for (const Launch &q : p->sched.launches) {
         if (q.chain) {
             ilu0_chain_kernel<<<1, ILU0_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, p->units, rowptr, colidx, p->diag_pos, val, lu);
         } else {
             const int64_t first = p->h_level_unit_ptr[q.l0], count = p->h_level_unit_ptr[q.l1] - first;
-            const unsigned grid = (unsigned)((4 * count + ILU0_WIDE_THREADS - 1) / ILU0_WIDE_THREADS);
-            ilu0_wide_kernel<<<grid, ILU0_WIDE_THREADS, 0, s>>>(first, count, p->units, rowptr, colidx, p->diag_pos, val, lu);
+            ilu0_wide_kernel<<<wide_grid(4 * count, ILU0_WIDE_THREADS), ILU0_WIDE_THREADS, 0, s>>>(first, count, p->units, rowptr, colidx, p->diag_pos, val, lu);
         }
     }
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;

@@ -1,8 +1,8 @@
-// ilu0_plan.cpp -- the host rule of the ILU(0) plan (sblas_hip_ilu0_plan_create, ilu0.hip): the structure check, the
-// limits, and the packing of every level's rows into lane units.  Pure functions of host arrays; no GPU call in this
-// file, so it is testable on a CPU box.  The levels and the launches are the triangular solves' (sblas_sptrsv_levels with
-// LOWER and NON_UNIT, sblas_sptrsv_schedule): row i of the factor needs the finished rows k < i it stores an entry for,
-// which is exactly what row i of a lower solve needs.
+// ilu0_plan.cpp -- the host rule of the ILU(0) plan (sblas_hip_ilu0_plan_create, ilu0.hip): the structure check and the
+// limits.  Pure functions of host arrays; no GPU call in this file, so it is testable on a CPU box.  The levels, the
+// packing into lane units and the launches are the triangular solves' (sblas_sptrsv_levels with LOWER and NON_UNIT,
+// level_plan.h): row i of the factor needs the finished rows k < i it stores an entry for, which is exactly what row i
+// of a lower solve needs.
 #include <limits.h>
 #include <stdint.h>
 #include "../../include/sblas_hip.h"
@@ -49,37 +49,3 @@ int sblas_ilu0_check(int64_t n, const int32_t *rowptr, const int32_t *colidx, in
 }
 
 } // extern "C"
-
-namespace sblas {
-
-void ilu0_pack(int64_t n, const int32_t *rowptr, const int32_t *diag_pos, const int32_t *level, int64_t n_levels,
-               std::vector<Ilu0Unit> &units, std::vector<int64_t> &level_unit_ptr, std::vector<int64_t> &widths)
-{
-    // rows by (level, row): a counting sort, stable in the row
-    std::vector<int64_t> lp((size_t)n_levels + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++lp[(size_t)level[i] + 1];
-    widths.assign(lp.begin() + 1, lp.end());
-    for (int64_t l = 0; l < n_levels; ++l) lp[l + 1] += lp[l];
-    std::vector<int32_t> perm((size_t)n);
-    std::vector<int64_t> fillpos(lp.begin(), lp.end() - 1);
-    for (int64_t i = 0; i < n; ++i) perm[fillpos[level[i]]++] = (int32_t)i;
-    // every level packs its rows, in order, into four-lane units; a row of G lanes starts on a multiple of G lanes of
-    // its level, and padding units fill the gaps
-    const Ilu0Unit no_unit{-1, 0, 0, 0};
-    units.clear();
-    units.reserve((size_t)n + (size_t)n / 4);
-    level_unit_ptr.assign((size_t)n_levels + 1, 0);
-    for (int64_t l = 0; l < n_levels; ++l) {
-        const size_t first = units.size();
-        level_unit_ptr[l] = (int64_t)first;
-        for (int64_t k = lp[l]; k < lp[l + 1]; ++k) {
-            const int32_t i = perm[k];
-            const size_t per_row = (size_t)1 << (sptrsv_group_shift((int64_t)rowptr[i + 1] - rowptr[i]) - 2);
-            while ((units.size() - first) % per_row) units.push_back(no_unit);
-            for (size_t q = 0; q < per_row; ++q) units.push_back(Ilu0Unit{i, rowptr[i], diag_pos[i], rowptr[i + 1]});
-        }
-    }
-    level_unit_ptr[n_levels] = (int64_t)units.size();
-}
-
-} // namespace sblas

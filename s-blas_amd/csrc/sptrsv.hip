@@ -1,21 +1,10 @@
 // sptrsv.hip -- sparse triangular solves on a level-scheduled plan: T x = alpha b (SpSV) and
 // T X = alpha B for nrhs right-hand sides (SpSM), T the lower or upper triangle of a square CSR matrix.
 //
-// The plan sorts the rows by (level, row) once (the host rule: sptrsv_plan.cpp); a solve is then a fixed sequence of
-// launches of two kernels:
-//   wide   one level a launch; the level's rows, in ascending row order, spread over the grid;
-//   chain  one workgroup walks a run of consecutive levels with __syncthreads() between them.
-// Nothing waits across workgroups: no flag polling, no cooperative launch, no grid barrier, no atomics.  The only
-// synchronisation is the kernel boundary and __syncthreads(), and every loop's trip count comes from the plan.
-//
-// Visibility inside a chain launch: x is written with plain global stores and read with plain global loads.
-// __syncthreads() is a workgroup-scope release and acquire around the barrier: every wave waits for its stores
-// (s_waitcnt vmcnt(0)) before it arrives, and no load of x for a later level is issued before it leaves (what is fetched
-// ahead of the barrier is plan data, which no kernel writes).  The waves of one
-// workgroup run on one CU and share its vector L1, which is write-through and sees the CU's own stores; the hazard of a
-// stale L1 line exists only between CUs, and no other workgroup runs in a chain launch.  Between launches the kernel
-// boundary orders everything.  x and b are not __restrict__: they may be the same array, and x is read and written in
-// one launch.
+// The plan sorts the rows by (level, row) once (the host rules: sptrsv_plan.cpp, level_plan.h); a solve is then a fixed
+// sequence of wide and chain launches.  The two walks, and why x stored before a chain launch's barrier is what is
+// loaded behind it, are in level_kernels.h.  x and b are not __restrict__: they may be the same array, and x is read and
+// written in one launch.
 //
 // Results contract: solve_row() is the one expression of x[i], shared by both kernels.  Its bits are a function of the
 // row's stored entries (columns and values, in stored order), the x values they name, b[i] and alpha: the lane group's
@@ -28,7 +17,7 @@
 #include <memory>
 #include <vector>
 #include "../../include/sblas_hip.h"
-#include "capi_util.h"
+#include "level_kernels.h"
 #include "rowwise.h"
 #include "sptrsv.h"
 
@@ -38,17 +27,10 @@ namespace {
 
 constexpr int WIDE_THREADS = 256;
 
-// a row as the SpSM kernels meet it, in (level, row) order: one 16-byte load
+// a row as the SpSM kernels meet it, in (level, row) order: one 16-byte load (load_unit)
 struct RowDesc {
     int32_t row, beg, end, diag; // diag: position of the stored diagonal in val, -1 under SBLAS_DIAG_UNIT
 };
-static_assert(sizeof(RowDesc) == 16, "one 16-byte load per row");
-
-__device__ __forceinline__ RowDesc load_desc(const RowDesc *__restrict__ desc, int64_t k)
-{
-    const int4 v = *reinterpret_cast<const int4 *>(desc + k);
-    return RowDesc{v.x, v.y, v.z, v.w};
-}
 
 __device__ __forceinline__ double finish_row(double alpha, double bi, double sum, double pivot)
 {
@@ -57,20 +39,12 @@ __device__ __forceinline__ double finish_row(double alpha, double bi, double sum
     return (t - sum) / pivot;
 }
 
-// A unit is four lanes of a launch.  A row of G(p) lanes is G(p) / 4 consecutive units, aligned to G(p) lanes inside its
-// level; a unit that pads that alignment has row = -1.  tag: in a row's first unit the position of the stored diagonal in
-// val (-1 under SBLAS_DIAG_UNIT); in its unit number s > 0, -2 - s.
+// SpSV's unit record (level_plan.h: four lanes of a launch; a pad has row = -1).  tag: in a row's first unit the position
+// of the stored diagonal in val (-1 under SBLAS_DIAG_UNIT); in its unit number s > 0, -2 - s.
 struct Unit {
     int32_t row, beg, end, tag;
 };
-static_assert(sizeof(Unit) == 16, "one 16-byte load per unit");
 constexpr Unit NO_UNIT{-1, 0, 0, -1};
-
-__device__ __forceinline__ Unit load_unit(const Unit *__restrict__ units, int64_t u)
-{
-    const int4 v = *reinterpret_cast<const int4 *>(units + u);
-    return Unit{v.x, v.y, v.z, v.w};
-}
 
 // x[row] for the row of unit u.  Every lane of the wave calls this together (the butterfly moves data between lanes);
 // `quad` is the lane's place in its unit.
@@ -137,9 +111,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sptrsv_wide_kernel(int64_t first
                                                                    const int32_t *__restrict__ colidx, const double *__restrict__ val,
                                                                    double alpha, const double *b, double *x)
 {
-    const int64_t t = (int64_t)blockIdx.x * WIDE_THREADS + threadIdx.x;
-    const int64_t u = t >> 2;
-    solve_row(u < count ? load_unit(units, first + u) : NO_UNIT, (int)(t & 3), lower != 0, colidx, val, alpha, b, x);
+    solve_row(wide_unit<WIDE_THREADS>(first, count, units, NO_UNIT), threadIdx.x & 3, lower != 0, colidx, val, alpha, b, x);
 }
 
 // SpSM: rows first .. first + rows - 1 of the order, a slot of 1 << wshift lanes each
@@ -151,7 +123,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void sptrsm_wide_kernel(int64_t first
     const int64_t t = (int64_t)blockIdx.x * WIDE_THREADS + threadIdx.x;
     const int64_t r = t >> wshift;
     if (r >= rows) return;
-    solve_row_m(load_desc(desc, first + r), (int)(t & ((1 << wshift) - 1)), 1 << wshift, lower != 0, colidx, val, nrhs, alpha, B, ldb, X, ldx);
+    solve_row_m(load_unit(desc, first + r), (int)(t & ((1 << wshift) - 1)), 1 << wshift, lower != 0, colidx, val, nrhs, alpha, B, ldb, X, ldx);
 }
 
 // ---- chain: levels l0 .. l1 - 1 in one workgroup; a level wider than the workgroup is looped over ------------
@@ -162,23 +134,8 @@ __global__ __launch_bounds__(SPTRSV_CHAIN_THREADS) void sptrsv_chain_kernel(int6
                                                                             const double *__restrict__ val, double alpha, const double *b,
                                                                             double *x)
 {
-    constexpr int PASS = SPTRSV_CHAIN_THREADS / 4; // units of one pass
-    const int mine = threadIdx.x >> 2, quad = threadIdx.x & 3;
-    // The plan's arrays do not depend on x: the next level's extent and this thread's first unit of it are fetched while
-    // the current level is solved, so that behind the barrier only the row's entries and x are waited for.
-    int64_t first = level_unit_ptr[l0], end = level_unit_ptr[l0 + 1];
-    Unit cur = mine < end - first ? load_unit(units, first + mine) : NO_UNIT;
-    for (int64_t l = l0; l < l1; ++l) {
-        const int64_t count = end - first, next_end = l + 1 < l1 ? level_unit_ptr[l + 2] : end;
-        const Unit next = l + 1 < l1 && mine < next_end - end ? load_unit(units, end + mine) : NO_UNIT;
-        solve_row(cur, quad, lower != 0, colidx, val, alpha, b, x);
-        for (int64_t u0 = PASS; u0 < count; u0 += PASS) { // the same trip count in every thread
-            const int64_t u = u0 + mine;
-            solve_row(u < count ? load_unit(units, first + u) : NO_UNIT, quad, lower != 0, colidx, val, alpha, b, x);
-        }
-        __syncthreads(); // this level's x, stored by this workgroup, is what the next level loads
-        first = end, end = next_end, cur = next;
-    }
+    chain_walk<SPTRSV_CHAIN_THREADS>(l0, l1, level_unit_ptr, units, NO_UNIT,
+                                     [&](const Unit u) { solve_row(u, threadIdx.x & 3, lower != 0, colidx, val, alpha, b, x); });
 }
 
 __global__ __launch_bounds__(SPTRSV_CHAIN_THREADS) void sptrsm_chain_kernel(int64_t l0, int64_t l1, int wshift, int lower,
@@ -192,48 +149,25 @@ __global__ __launch_bounds__(SPTRSV_CHAIN_THREADS) void sptrsm_chain_kernel(int6
     for (int64_t l = l0; l < l1; ++l) {
         const int64_t first = level_ptr[l], rows = level_ptr[l + 1] - first;
         for (int64_t r = slot; r < rows; r += slots)
-            solve_row_m(load_desc(desc, first + r), lane, 1 << wshift, lower != 0, colidx, val, nrhs, alpha, B, ldb, X, ldx);
+            solve_row_m(load_unit(desc, first + r), lane, 1 << wshift, lower != 0, colidx, val, nrhs, alpha, B, ldb, X, ldx);
         __syncthreads();
     }
 }
 
-struct Launch {
-    int64_t l0, l1; // levels
-    bool chain;
-};
-
-struct SptrsvPlan {
-    int dev = -1, fill = 0, diag = 0, flags = 0;
-    int64_t n = 0, nnz = 0, levels = 0, wide = 0, chains = 0, widest = 0, longest = 0, chain_rows = 0;
-    size_t bytes = 0;
-    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
-    DeviceBuffer buf;                                   // units | desc | level_unit_ptr | perm | level_ptr
-    Unit *units = nullptr;                              // SpSV: the rows of every level packed into four-lane units
-    RowDesc *desc = nullptr;                            // SpSM: the rows by (level, row)
-    int64_t *level_unit_ptr = nullptr;
+struct SptrsvPlan : LevelPlan { // buf: units | desc | level_unit_ptr | perm | level_ptr
+    int fill = 0, diag = 0;
+    Unit *units = nullptr;   // SpSV: the rows of every level packed into four-lane units
+    RowDesc *desc = nullptr; // SpSM: the rows by (level, row)
     int32_t *perm = nullptr, *level_ptr = nullptr;
     std::vector<int32_t> h_level_ptr;
-    std::vector<int64_t> h_level_unit_ptr;
-    std::vector<Launch> launches;
 };
 
-inline size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
-inline unsigned wide_grid(int64_t lanes) { return (unsigned)((lanes + WIDE_THREADS - 1) / WIDE_THREADS); }
 // lanes along the right-hand sides: the least power of two that covers nrhs, a wave at the most
 inline int rhs_shift(int64_t nrhs)
 {
     int s = 0;
     while (s < 6 && ((int64_t)1 << s) < nrhs) ++s;
     return s;
-}
-
-// 0 when the call may run; the plan's device must be current and the structure the one the plan was made for
-int call_ok(const SptrsvPlan *p, const int32_t *rowptr, const int32_t *colidx)
-{
-    if (!p) return SBLAS_E_INVALID;
-    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
-    if (rowptr != p->rowptr || colidx != p->colidx) return SBLAS_E_INVALID;
-    return SBLAS_OK;
 }
 
 } // namespace
@@ -243,110 +177,48 @@ extern "C" {
 int sblas_hip_sptrsv_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
                                  int fill, int diag, int flags, int64_t chain_rows, void **plan_out, int64_t *bad_row)
 {
-    if (bad_row) *bad_row = -1;
-    if (!plan_out) return SBLAS_E_INVALID;
-    *plan_out = nullptr;
-    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX || chain_rows < 0) return SBLAS_E_INVALID;
+    std::unique_ptr<SptrsvPlan> p(new SptrsvPlan);
+    if (!level_plan_begin(*p, dev, n, nnz, rowptr, colidx, flags, chain_rows, SPTRSV_CHAIN_ROWS, plan_out, bad_row)) return SBLAS_E_INVALID;
     if (fill != SBLAS_FILL_LOWER && fill != SBLAS_FILL_UPPER) return SBLAS_E_INVALID;
     if (diag != SBLAS_DIAG_NON_UNIT && diag != SBLAS_DIAG_UNIT) return SBLAS_E_INVALID;
-    if (flags != SBLAS_SPTRSV_AUTO && flags != SBLAS_SPTRSV_PER_LEVEL && flags != SBLAS_SPTRSV_CHAIN_ONLY) return SBLAS_E_INVALID;
-    if ((n > 0 && !rowptr) || (nnz > 0 && !colidx)) return SBLAS_E_INVALID;
-    std::unique_ptr<SptrsvPlan> p(new SptrsvPlan);
-    p->dev = resolve_device(dev), p->fill = fill, p->diag = diag, p->flags = flags, p->n = n, p->nnz = nnz;
-    p->rowptr = rowptr, p->colidx = colidx;
-    p->chain_rows = chain_rows > 0 ? chain_rows : SPTRSV_CHAIN_ROWS;
+    p->fill = fill, p->diag = diag;
     if (n == 0) {
-        if (nnz != 0) return SBLAS_E_INVALID;
         *plan_out = p.release();
         return SBLAS_OK;
     }
     DeviceScope scope(dev);
     if (scope.err != hipSuccess) return SBLAS_E_HIP;
     hipStream_t s = (hipStream_t)stream;
-
-    // the structure comes to the host once; every check and the whole schedule are host work
-    std::vector<int32_t> h_rowptr((size_t)n + 1), h_colidx((size_t)nnz);
-    hipError_t e = hipMemcpyAsync(h_rowptr.data(), rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(h_colidx.data(), colidx, (size_t)nnz * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return SBLAS_E_HIP;
-    if (h_rowptr[n] != nnz) { // first: the host rule follows rowptr into a colidx of nnz entries
-        if (bad_row) *bad_row = n - 1;
-        return SBLAS_E_INVALID;
-    }
-    std::vector<int32_t> level((size_t)n);
-    int64_t n_levels = 0;
-    const int rc = sblas_sptrsv_levels(n, h_rowptr.data(), h_colidx.data(), fill, diag, level.data(), &n_levels, bad_row);
+    std::vector<int32_t> h_rowptr, h_colidx, level((size_t)n);
+    int rc = fetch_structure(s, n, nnz, rowptr, colidx, h_rowptr, h_colidx, bad_row);
     if (rc != SBLAS_OK) return rc;
-    p->levels = n_levels;
+    rc = sblas_sptrsv_levels(n, h_rowptr.data(), h_colidx.data(), fill, diag, level.data(), &p->levels, bad_row);
+    if (rc != SBLAS_OK) return rc;
 
-    // rows by (level, row): a counting sort, stable in the row
-    std::vector<int32_t> &lp = p->h_level_ptr;
-    lp.assign((size_t)n_levels + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++lp[(size_t)level[i] + 1];
-    std::vector<int64_t> widths((size_t)n_levels);
-    for (int64_t l = 0; l < n_levels; ++l) {
-        widths[l] = lp[l + 1];
-        p->widest = widths[l] > p->widest ? widths[l] : p->widest;
-        lp[l + 1] += lp[l];
-    }
-    std::vector<int32_t> perm((size_t)n), fillpos(lp.begin(), lp.end() - 1);
-    std::vector<RowDesc> desc((size_t)n);
+    std::vector<int32_t> dpos((size_t)n, -1); // every row's stored diagonal
     for (int64_t i = 0; i < n; ++i) {
-        const int32_t k = fillpos[level[i]]++;
-        perm[k] = (int32_t)i;
-        int32_t dpos = -1;
         if (diag == SBLAS_DIAG_NON_UNIT)
             for (int32_t q = h_rowptr[i]; q < h_rowptr[i + 1]; ++q)
-                if (h_colidx[q] == i) dpos = q;
-        desc[k] = RowDesc{(int32_t)i, h_rowptr[i], h_rowptr[i + 1], dpos};
+                if (h_colidx[q] == i) dpos[i] = q;
         const int64_t len = (int64_t)h_rowptr[i + 1] - h_rowptr[i];
         p->longest = len > p->longest ? len : p->longest;
     }
-    // SpSV's lanes: every level packs its rows, in order, into four-lane units; a row of G lanes starts on a multiple of
-    // G lanes of its level (its butterfly stays inside one DPP row, or is one wave), and padding units fill the gaps
-    std::vector<Unit> units;
-    units.reserve((size_t)n + (size_t)n / 4);
-    std::vector<int64_t> &up = p->h_level_unit_ptr;
-    up.assign((size_t)n_levels + 1, 0);
-    for (int64_t l = 0; l < n_levels; ++l) {
-        up[l] = (int64_t)units.size();
-        for (int32_t k = lp[l]; k < lp[l + 1]; ++k) {
-            const RowDesc &d = desc[k];
-            const size_t per_row = (size_t)1 << (sptrsv_group_shift((int64_t)d.end - d.beg) - 2); // units of this row
-            while ((units.size() - (size_t)up[l]) % per_row) units.push_back(NO_UNIT);
-            units.push_back(Unit{d.row, d.beg, d.end, d.diag});
-            for (size_t q = 1; q < per_row; ++q) units.push_back(Unit{d.row, d.beg, d.end, -2 - (int32_t)q});
-        }
+    LevelOrder o;
+    std::vector<Unit> units; // SpSV's lanes
+    const auto unit_of = [&](int32_t i, int32_t q) { return Unit{i, h_rowptr[i], h_rowptr[i + 1], q ? -2 - q : dpos[i]}; };
+    level_pack(n, h_rowptr.data(), level.data(), p->levels, unit_of, NO_UNIT, o, units);
+    std::vector<RowDesc> desc((size_t)n); // SpSM's rows
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t i = o.perm[k];
+        desc[k] = RowDesc{i, h_rowptr[i], h_rowptr[i + 1], dpos[i]};
     }
-    up[n_levels] = (int64_t)units.size();
+    if (level_launches(o.widths, flags, p->chain_rows, p->sched) != SBLAS_OK) return SBLAS_E_INVALID;
 
-    // the launches
-    std::vector<uint8_t> kind((size_t)n_levels);
-    std::vector<int64_t> lfirst((size_t)n_levels + 1);
-    int64_t n_launches = 0;
-    if (sblas_sptrsv_schedule(n_levels, widths.data(), flags, chain_rows, kind.data(), lfirst.data(), &n_launches) != SBLAS_OK)
-        return SBLAS_E_INVALID;
-    for (int64_t q = 0; q < n_launches; ++q) {
-        const bool chain = kind[q] == SBLAS_SPTRSV_LAUNCH_CHAIN;
-        p->launches.push_back(Launch{lfirst[q], lfirst[q + 1], chain});
-        ++(chain ? p->chains : p->wide);
-    }
-
-    const size_t o_desc = units.size() * sizeof(Unit), o_up = o_desc + (size_t)n * sizeof(RowDesc);
-    const size_t o_perm = o_up + pad16(((size_t)n_levels + 1) * 8), o_lp = o_perm + pad16((size_t)n * 4);
-    const size_t total = o_lp + pad16(((size_t)n_levels + 1) * 4);
-    if (p->buf.alloc(p->dev, total) != hipSuccess) return SBLAS_E_HIP;
-    p->bytes = total;
-    p->units = p->buf.at<Unit>(), p->desc = p->buf.at<RowDesc>(o_desc), p->level_unit_ptr = p->buf.at<int64_t>(o_up);
-    p->perm = p->buf.at<int32_t>(o_perm), p->level_ptr = p->buf.at<int32_t>(o_lp);
-    e = hipMemcpyAsync(p->units, units.data(), units.size() * sizeof(Unit), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->desc, desc.data(), (size_t)n * sizeof(RowDesc), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->level_unit_ptr, up.data(), ((size_t)n_levels + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->perm, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->level_ptr, lp.data(), ((size_t)n_levels + 1) * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s); // the host vectors are read until here
-    if (e != hipSuccess) return SBLAS_E_HIP;
+    Segment seg[5] = {Segment(units), Segment(desc), Segment(o.level_unit_ptr), Segment(o.perm), Segment(o.level_ptr)};
+    if (upload_segments(p->buf, p->dev, s, seg, 5, &p->bytes) != hipSuccess) return SBLAS_E_HIP;
+    p->units = p->buf.at<Unit>(), p->desc = p->buf.at<RowDesc>(seg[1].offset), p->level_unit_ptr = p->buf.at<int64_t>(seg[2].offset);
+    p->perm = p->buf.at<int32_t>(seg[3].offset), p->level_ptr = p->buf.at<int32_t>(seg[4].offset);
+    p->h_level_unit_ptr = std::move(o.level_unit_ptr), p->h_level_ptr = std::move(o.level_ptr);
     *plan_out = p.release();
     return SBLAS_OK;
 }
@@ -355,16 +227,15 @@ int sblas_hip_sptrsv_plan_info(const void *plan, int64_t out[12])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const SptrsvPlan *p = static_cast<const SptrsvPlan *>(plan);
-    out[0] = p->n, out[1] = p->nnz, out[2] = p->fill, out[3] = p->diag, out[4] = p->levels, out[5] = (int64_t)p->launches.size();
-    out[6] = p->wide, out[7] = p->chains, out[8] = p->widest, out[9] = p->longest, out[10] = (int64_t)p->bytes, out[11] = p->flags;
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->fill, out[3] = p->diag, out[4] = p->levels, out[5] = (int64_t)p->sched.launches.size();
+    out[6] = p->sched.wide, out[7] = p->sched.chains, out[8] = p->sched.widest, out[9] = p->longest, out[10] = (int64_t)p->bytes;
+    out[11] = p->flags;
     return SBLAS_OK;
 }
 
 int sblas_hip_sptrsv_plan_speaks_for(const void *plan, int dev, const int32_t *rowptr, const int32_t *colidx)
 {
-    const SptrsvPlan *p = static_cast<const SptrsvPlan *>(plan);
-    if (!p || p->dev != resolve_device(dev)) return SBLAS_E_INVALID;
-    return rowptr == p->rowptr && colidx == p->colidx ? SBLAS_OK : SBLAS_E_INVALID;
+    return level_plan_speaks_for(static_cast<const SptrsvPlan *>(plan), dev, rowptr, colidx);
 }
 
 int sblas_hip_sptrsv_plan_order(const void *plan, const int32_t **perm, const int32_t **level_ptr)
@@ -386,18 +257,18 @@ int sblas_hip_sptrsv_f64_i32_planned(const void *plan, void *stream, const int32
                                      double alpha, const double *b, double *x)
 {
     const SptrsvPlan *p = static_cast<const SptrsvPlan *>(plan);
-    const int rc = call_ok(p, rowptr, colidx);
+    const int rc = level_plan_speaks_for(p, -1, rowptr, colidx);
     if (rc != SBLAS_OK) return rc;
     if (p->n == 0) return SBLAS_OK;
     if (!b || !x || (p->nnz > 0 && !val)) return SBLAS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int lower = p->fill == SBLAS_FILL_LOWER;
-    for (const Launch &q : p->launches) {
+    for (const Launch &q : p->sched.launches) {
         if (q.chain) {
             sptrsv_chain_kernel<<<1, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, lower, p->level_unit_ptr, p->units, colidx, val, alpha, b, x);
         } else {
             const int64_t first = p->h_level_unit_ptr[q.l0], count = p->h_level_unit_ptr[q.l1] - first;
-            sptrsv_wide_kernel<<<wide_grid(4 * count), WIDE_THREADS, 0, s>>>(first, count, lower, p->units, colidx, val, alpha, b, x);
+            sptrsv_wide_kernel<<<wide_grid(4 * count, WIDE_THREADS), WIDE_THREADS, 0, s>>>(first, count, lower, p->units, colidx, val, alpha, b, x);
         }
     }
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
@@ -407,19 +278,19 @@ int sblas_hip_sptrsm_f64_i32_planned(const void *plan, void *stream, const int32
                                      int64_t nrhs, double alpha, const double *B, int64_t ldb, double *X, int64_t ldx)
 {
     const SptrsvPlan *p = static_cast<const SptrsvPlan *>(plan);
-    const int rc = call_ok(p, rowptr, colidx);
+    const int rc = level_plan_speaks_for(p, -1, rowptr, colidx);
     if (rc != SBLAS_OK) return rc;
     if (nrhs < 0 || ldb < nrhs || ldx < nrhs) return SBLAS_E_INVALID;
     if (p->n == 0 || nrhs == 0) return SBLAS_OK;
     if (!B || !X || (p->nnz > 0 && !val)) return SBLAS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int lower = p->fill == SBLAS_FILL_LOWER, ws = rhs_shift(nrhs);
-    for (const Launch &q : p->launches) {
+    for (const Launch &q : p->sched.launches) {
         if (q.chain) {
             sptrsm_chain_kernel<<<1, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, ws, lower, p->level_ptr, p->desc, colidx, val, nrhs, alpha, B, ldb, X, ldx);
         } else {
             const int64_t first = p->h_level_ptr[q.l0], rows = p->h_level_ptr[q.l1] - first;
-            sptrsm_wide_kernel<<<wide_grid(rows << ws), WIDE_THREADS, 0, s>>>(first, rows, ws, lower, p->desc, colidx, val, nrhs, alpha, B, ldb, X, ldx);
+            sptrsm_wide_kernel<<<wide_grid(rows << ws, WIDE_THREADS), WIDE_THREADS, 0, s>>>(first, rows, ws, lower, p->desc, colidx, val, nrhs, alpha, B, ldb, X, ldx);
         }
     }
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;

@@ -46,7 +46,7 @@ EXPORTS = [
     "sblas_hip_spgemm_limits", "sblas_hip_spgemm_classify", "sblas_hip_spgemm_group_width", "sblas_hip_spgemm_check_nnz",
     "sblas_hip_spgemm_plan_create", "sblas_hip_spgemm_plan_info", "sblas_hip_spgemm_plan_csr", "sblas_hip_spgemm_plan_numeric",
     "sblas_hip_spgemm_plan_destroy",
-    "sblas_hip_sptrsv_limits", "sblas_sptrsv_levels", "sblas_sptrsv_schedule",
+    "sblas_hip_sptrsv_limits", "sblas_sptrsv_levels", "sblas_sptrsv_schedule", "sblas_sptrsv_pack",
     "sblas_hip_sptrsv_plan_create", "sblas_hip_sptrsv_plan_info", "sblas_hip_sptrsv_plan_order", "sblas_hip_sptrsv_plan_destroy",
     "sblas_hip_sptrsv_f64_i32_planned", "sblas_hip_sptrsm_f64_i32_planned",
     "sblas_hip_ilu0_limits", "sblas_ilu0_check", "sblas_hip_ilu0_plan_create", "sblas_hip_ilu0_plan_info",
@@ -260,6 +260,8 @@ def lib():
     L.sblas_sptrsv_levels.argtypes = [i64, vp, vp, C.c_int, C.c_int, vp, C.POINTER(i64), C.POINTER(i64)]
     L.sblas_sptrsv_schedule.restype = C.c_int
     L.sblas_sptrsv_schedule.argtypes = [i64, vp, C.c_int, i64, vp, vp, C.POINTER(i64)]
+    L.sblas_sptrsv_pack.restype = C.c_int
+    L.sblas_sptrsv_pack.argtypes = [i64, vp, vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.sblas_hip_sptrsv_plan_create.restype = C.c_int
     L.sblas_hip_sptrsv_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, C.c_int, C.c_int, i64, C.POINTER(vp), C.POINTER(i64)]
     L.sblas_hip_sptrsv_plan_info.restype = C.c_int
@@ -566,6 +568,24 @@ def sptrsv_schedule(widths, mode="auto", chain_rows=0):
     check(lib().sblas_sptrsv_schedule(L, widths.ctypes.data, _sptrsv_mode(mode), int(chain_rows), kind.ctypes.data,
                                       first.ctypes.data, C.byref(n)), "sblas_sptrsv_schedule")
     return kind[:n.value].copy(), first[:n.value + 1].copy()
+
+
+def sptrsv_pack(n, rowptr, level, n_levels):
+    """The lanes of a level plan (sblas_sptrsv_pack, host arrays) -> (perm, level_ptr, level_unit_ptr, unit_row, unit_q):
+    the rows by (level, row), where each level's rows and four-lane units begin, and for every unit its row (-1: a pad) and
+    its number within the row."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    level = np.ascontiguousarray(level, np.int32)
+    if len(rowptr) != n + 1 or len(level) != n:
+        raise SblasError("rowptr has %d entries and level %d for %d rows" % (len(rowptr), len(level), n))
+    args = (n, rowptr.ctypes.data, level.ctypes.data if n else None, n_levels)
+    units = C.c_int64()
+    check(lib().sblas_sptrsv_pack(*args, None, None, None, None, None, C.byref(units)), "sblas_sptrsv_pack")
+    perm, level_ptr, level_unit_ptr = np.zeros(n, np.int32), np.zeros(n_levels + 1, np.int32), np.zeros(n_levels + 1, np.int64)
+    unit_row, unit_q = np.zeros(units.value, np.int32), np.zeros(units.value, np.int32)
+    check(lib().sblas_sptrsv_pack(*args, *[a.ctypes.data if len(a) else None for a in (perm, level_ptr, level_unit_ptr, unit_row, unit_q)],
+                                  C.byref(units)), "sblas_sptrsv_pack")
+    return perm, level_ptr, level_unit_ptr, unit_row, unit_q
 
 
 def ilu0_limits():
@@ -1585,6 +1605,20 @@ def spgemm(A, B, stream=None):
     return rowptr_c, colidx_c, val_c
 
 
+def _structure(n, rowptr, colidx):
+    """the checks every structure plan makes on (rowptr, colidx) before the library sees them -> nnz"""
+    import torch
+    for name, t in (("rowptr", rowptr), ("colidx", colidx)):
+        if not isinstance(t, torch.Tensor):
+            raise SblasError("%s must be a torch tensor" % name)
+        _typed(name, t, torch.int32)
+        if not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+    if rowptr.numel() != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
+    return int(colidx.numel())
+
+
 # ------------------------------------------------------------------------------------------
 # Sparse triangular solves: T x = alpha b, T X = alpha B (sblas_hip_sptrsv_plan_*)
 # ------------------------------------------------------------------------------------------
@@ -1603,17 +1637,9 @@ class SptrsvPlan:
         self.n, self.lower, self.unit_diag, self.mode = n, bool(lower), bool(unit_diag), mode
         self.handle = None
         flags = _sptrsv_mode(mode)
-        for name, t in (("rowptr", rowptr), ("colidx", colidx)):
-            if not isinstance(t, torch.Tensor):
-                raise SblasError("%s must be a torch tensor" % name)
-            _typed(name, t, torch.int32)
-            if not t.is_cuda:
-                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
-        if rowptr.numel() != n + 1:
-            raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
+        self.nnz = _structure(n, rowptr, colidx)
         self.rowptr, self.colidx = rowptr, colidx
         self.device = rowptr.device
-        self.nnz = int(colidx.numel())
         h, bad = C.c_void_p(), C.c_int64(-1)
         with torch.cuda.device(self.device):
             rc = lib().sblas_hip_sptrsv_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
@@ -1730,17 +1756,9 @@ class Ilu0Plan:
         self.handle = None
         self._solvers = None
         flags = _sptrsv_mode(mode)
-        for name, t in (("rowptr", rowptr), ("colidx", colidx)):
-            if not isinstance(t, torch.Tensor):
-                raise SblasError("%s must be a torch tensor" % name)
-            _typed(name, t, torch.int32)
-            if not t.is_cuda:
-                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
-        if rowptr.numel() != n + 1:
-            raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
+        self.nnz = _structure(n, rowptr, colidx)
         self.rowptr, self.colidx = rowptr, colidx
         self.device = rowptr.device
-        self.nnz = int(colidx.numel())
         h, bad = C.c_void_p(), C.c_int64(-1)
         with torch.cuda.device(self.device):
             rc = lib().sblas_hip_ilu0_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
@@ -1856,20 +1874,6 @@ def ilu0(A, stream=None):
 # ------------------------------------------------------------------------------------------
 # Multicolour reordering: a device graph colouring and P A P^T on a plan (sblas_hip_color_plan_*, sblas_hip_permute_plan_*)
 # ------------------------------------------------------------------------------------------
-def _structure(n, rowptr, colidx):
-    """the checks every structure plan makes on (rowptr, colidx) before the library sees them -> nnz"""
-    import torch
-    for name, t in (("rowptr", rowptr), ("colidx", colidx)):
-        if not isinstance(t, torch.Tensor):
-            raise SblasError("%s must be a torch tensor" % name)
-        _typed(name, t, torch.int32)
-        if not t.is_cuda:
-            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
-    if rowptr.numel() != n + 1:
-        raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), n))
-    return int(colidx.numel())
-
-
 class ColorPlan:
     """A colouring of the n x n CSR pattern (rowptr, colidx), int32 indices (sblas_hip_color_plan_create): no stored
     off-diagonal entry joins two vertices of one colour.  The pattern need not be symmetric; rows may be unsorted, hold

@@ -4,6 +4,7 @@ unsorted and hold off-diagonal duplicates (they add) and entries in the other tr
 stored diagonals and uses 1.
 
 - levels(): level(i) = 0 when row i selects no off-diagonal entry, else 1 + the greatest level among the rows named.
+- pack(): the rows by (level, row) and every level's four-lane units, each row aligned to its own unit count.
 - reference(): forward / backward substitution in double-double (the error-free pieces of numerics.py).
 - residual_bound(): the rounding-error bound on the residual that every correct evaluation order satisfies.
 - grid_problem(): integer data on which every order of every sum is exact, so the solve must return x with ==.
@@ -48,6 +49,33 @@ def levels(n, rowptr, colidx, lower=True):
 
 def level_widths(lv, n_levels):
     return np.bincount(lv, minlength=n_levels).astype(np.int64)
+
+
+def units_per_row(p, g4_max, g16_max):
+    """four-lane units of a row of p stored entries: G(p) / 4 for G = 4 (p <= g4_max), 16 (p <= g16_max) or 64 lanes"""
+    return 1 if p <= g4_max else 4 if p <= g16_max else 16
+
+
+def pack(n, rowptr, level, n_levels, g4_max, g16_max):
+    """-> (perm, level_ptr, level_unit_ptr, unit_row, unit_q) by the rule's own words: the rows sorted stably by level;
+    in a level each row takes its units_per_row() units numbered from 0, starting on a multiple of that count from the
+    level's start, and (-1, 0) pads the gaps"""
+    rp = np.asarray(rowptr, np.int64)
+    perm = np.argsort(np.asarray(level, np.int64), kind="stable")
+    level_ptr, level_unit_ptr, unit_row, unit_q = [0], [0], [], []
+    for l in range(n_levels):
+        rows = [int(i) for i in perm if level[i] == l]
+        at = 0                                                              # units of this level so far
+        for i in rows:
+            per = units_per_row(rp[i + 1] - rp[i], g4_max, g16_max)
+            pads = -at % per
+            unit_row += [-1] * pads + [i] * per
+            unit_q += [0] * pads + list(range(per))
+            at += pads + per
+        level_ptr.append(level_ptr[-1] + len(rows))
+        level_unit_ptr.append(level_unit_ptr[-1] + at)
+    return (perm.astype(np.int32), np.array(level_ptr, np.int32), np.array(level_unit_ptr, np.int64),
+            np.array(unit_row, np.int32), np.array(unit_q, np.int32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
