@@ -808,6 +808,102 @@ int sblas_hip_krylov_iterate(void *plan, void *stream, int64_t k);
 int sblas_hip_krylov_status(const void *plan, void *stream, double out[8]);
 
 /* ---------------------------------------------------------------------------------------
+ * Restarted GMRES(m) on a plan of its own, resident on the device:  right-preconditioned GMRES for A x = b with A square,
+ * fp64 values, int32 indices, restart length 1 <= m <= SBLAS_GMRES_MAX_RESTART, the preconditioners of the Krylov plan
+ * (none, Jacobi, ILU(0)) and its style: start / iterate / status, only status synchronises, no atomics, nothing waits
+ * across workgroups, no allocation after create, iterate is a linear graph-capturable chain, and every bit is pinned.
+ * It is not a third method of sblas_hip_krylov_plan_create, which goes on refusing anything but PCG and BiCGStab.
+ * One ITERATION is one Arnoldi step -- one SpMV and one M^-1 -- and max_iter counts those.
+ *   - start.  |b| by the pinned dot;  r = b - A x (the SpMV, then one rounded difference);  beta = sqrt((r, r));  the test
+ *     at iteration 0 with the Krylov plan's edges (b == 0: x = 0, converged at 0; |r0| within the tolerance: x untouched;
+ *     max_iter == 0: LIMIT; n == 0: converged);  v_0 = r / beta, A ROUNDED DIVISION PER ELEMENT, not a multiplication by
+ *     a reciprocal;  g = beta e_1.  A beta that is not finite is a BREAKDOWN (SBLAS_GMRES_DENOM_BETA), here and at a restart.
+ *   - step j (0 <= j < m).  z = M^-1 v_j (Jacobi: dinv o v_j, written by the pass that writes v_j);  w = A z;  classical
+ *     Gram-Schmidt done twice:  h_i = (v_i, w) for i <= j in one multi-dot pass, then w = w - h_0 v_0 - h_1 v_1 - ... - h_j v_j
+ *     ascending with each product rounded and each difference rounded;  c_i = (v_i, w), h_i = h_i + c_i, and
+ *     w = w - sum c_i v_i in the same order, a pass that is also stage 1 of (w, w);  eta = sqrt((w, w));  the scalar
+ *     step;  v_{j+1} = w / eta, a rounded division per element.
+ *   - the multi-dot.  out[i] = (V[i], w) for up to 65 columns in ONE pass over memory: a cell of the pinned dot is a
+ *     workgroup, lane t keeps its eight elements of w in registers and walks the columns.  Every out[i] has exactly the
+ *     bits of sblas_hip_krylov_dot_f64 on (V[i], w): the same lane order, the rounded product and then the rounded sum,
+ *     the same butterfly, the same second stage (one workgroup folds the dots one after another).
+ *   - the scalar step (sblas_gmres_step_ref restates it; host and device compile one text), each operation rounded on
+ *     its own, in this order:  for i < j:  t = c_i h_i + s_i h_{i+1};  h_{i+1} = (-s_i) h_i + c_i h_{i+1};  h_i = t.
+ *     d = sqrt(h_j h_j + eta eta).  c_j = h_j / d;  s_j = eta / d;  R_jj = d (R_ij = h_i above it).  g_{j+1} = (-s_j) g_j;
+ *     g_j = c_j g_j.  The residual of the recurrence is |g_{j+1}|.  Then the iteration is counted, then the test
+ *     |g_{j+1}| <= max(rtol |b|, atol), then the limit.  d zero or not finite: BREAKDOWN (SBLAS_GMRES_DENOM_GIVENS) with
+ *     nothing but h changed, so the columns before j stay valid.  eta == 0 with d != 0 (the lucky breakdown) gives
+ *     g_{j+1} = 0, which meets any tolerance: CONVERGED, and the division by eta never runs.  A NaN never converges.
+ *   - closing a cycle forms x:  y from R y = g over the k finished columns (sblas_gmres_solve_ref: for i = k - 1 .. 0:
+ *     t = g_i; for l = i + 1 .. k - 1 ascending t = t - R_il y_l; y_i = t / R_ii);  u = y_0 v_0, then u = u + y_l v_l
+ *     ascending, rounded product and rounded sum;  z = M^-1 u;  x = x + z.  k is read on the device.  A close is
+ *     enqueued after the m-th step of every cycle and at the end of every iterate call; it acts only when the cycle is
+ *     full or the status is not RUNNING, and a correction is still unapplied, and then marks it applied.
+ *   - the restart, behind the close of a full cycle while RUNNING:  r = b - A x, beta = sqrt((r, r)), the test on this
+ *     true residual (it may end CONVERGED with nothing pending), the restart counted, then v_0 and g as in start.
+ *   - the position.  The kernels read j from the device block, never from the launch; the host counts steps only to
+ *     know where a close and a restart belong in the chain.  A step enqueued behind a full cycle (a captured chain
+ *     replayed from another position) does nothing until the chain's next close and restart have run.
+ *   - the freeze.  Once the status is not RUNNING, every kernel that writes x, V, g, R, c, s, the count or the status
+ *     returns at entry or changes nothing, the acting close excepted: x, the count, |r| and the restart count do not
+ *     depend on how many iterations were already enqueued.  max_iter stops at exactly max_iter with x formed from the
+ *     columns finished so far.
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_GMRES_MAX_RESTART 64
+#define SBLAS_GMRES_DENOM_GIVENS 6 /* d = sqrt(h_j^2 + eta^2) of a Givens rotation   */
+#define SBLAS_GMRES_DENOM_BETA 7   /* |b - A x| as a cycle begins is not finite      */
+/* HOST functions (no GPU call; testable alone).  limits: [0] largest restart length [1] default restart length [2]
+ * columns of one multi-dot [3], [4] work vectors of a plan = [3] * m + [4] (ILU(0) adds the solves' temporary) [5] bytes of
+ * the scalar block [6] bytes of the small-matrix block (R by columns, c, s, g, y, h) [7] columns whose loads one lane
+ * keeps in flight together in the multi-dot */
+int sblas_gmres_limits(int64_t out[8]);
+/* The scalar step of Arnoldi step j (0 <= j < 64) on host arrays.  h: j + 1 entries, rotated in place; eta = |w|; c, s:
+ * entries 0 .. j - 1 read, entry j written; g: entries j and j + 1 written; rcol: column j of R, j + 1 entries written;
+ * tol = max(rtol |b|, atol); *iterations counted; *rnorm = |g_{j+1}|; *which = SBLAS_GMRES_DENOM_GIVENS on a breakdown,
+ * which leaves everything but h as it was.  Returns the SBLAS_KRYLOV_* status, -1 for a bad argument. */
+int sblas_gmres_step_ref(int j, double *h, double eta, double *c, double *s, double *g, double *rcol, double tol,
+                         int64_t max_iter, int64_t *iterations, double *rnorm, int64_t *which);
+/* The back substitution on host arrays: y (k entries) from R y = g, R by columns with leading dimension ldr >= k, k <= 64 */
+int sblas_gmres_solve_ref(int k, const double *R, int ldr, const double *g, double *y);
+/* Launches: out[0] of one step (the same for every j), out[1] of a close, out[2] of a restart, out[3] of start; counted
+ * as sblas_krylov_launches counts (one per SpMV, lower_info / upper_info [5] per solve with ILU(0), NULL otherwise).
+ * step 9 + lower + upper, close 3 + lower + upper, restart 4, start 6.  Returns those of a full cycle,
+ * m * out[0] + out[1] + out[2], or -1 for a bad argument. */
+int64_t sblas_gmres_launches(int m, int precond, const int64_t *lower_info, const int64_t *upper_info, int64_t out[4]);
+/* The multi-dot on its own: out[i] = (V + i * ldv, w) for i < k <= 65; V, w, out on the device, ldv >= n when k > 1.
+ * workspace: at least ..._dots_workspace(n, k) bytes on the device, 8-byte aligned (SBLAS_E_WORKSPACE when missing or
+ * short).  Two launches.  Stream-ordered, allocates nothing, never synchronises, graph-capturable. */
+size_t sblas_hip_gmres_dots_workspace(int64_t n, int k);
+int sblas_hip_gmres_dots_f64(int dev, void *stream, int64_t n, int k, const double *V, int64_t ldv, const double *w,
+                             double *out, void *workspace, size_t workspace_bytes);
+/* w = w - h_0 v_0 - ... - h_{k-1} v_{k-1}, ascending, h on the device (k <= 65).  partial: NULL, or ceil(n / 2048) device
+ * doubles that receive stage 1 of (w, w) over the new w.  One launch. */
+int sblas_hip_gmres_project_f64(int dev, void *stream, int64_t n, int k, const double *V, int64_t ldv, const double *h,
+                                double *w, double *partial);
+/* u = y_0 v_0 + y_1 v_1 + ... ascending, y on the device (k <= 65); u must not overlap V.  One launch. */
+int sblas_hip_gmres_combine_f64(int dev, void *stream, int64_t n, int k, const double *V, int64_t ldv, const double *y,
+                                double *u);
+/* create: host work and one allocation, zeroed on `stream`, which is synchronised (the two blocks, the partials,
+ * V = restart + 1 columns, w, u, z [, the solves' temporary]).  spmv_plan, precond, lower_plan, upper_plan and the
+ * refusals: as sblas_hip_krylov_plan_create.  The plan keeps the POINTERS and the handles, which must outlive it. */
+int sblas_hip_gmres_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                                int restart, const void *spmv_plan, int precond, const void *lower_plan,
+                                const void *upper_plan, void **plan_out);
+/* out: [0] n [1] nnz [2] restart [3] precond [4] work vectors owned [5] bytes of one (the column stride of V) [6] bytes of
+ * the partials [7] bytes of the scalar block [8] of the small-matrix block [9] device bytes held [10] launches of a step
+ * [11] of a close [12] of a restart [13] of a full cycle */
+int sblas_hip_gmres_plan_info(const void *plan, int64_t out[14]);
+int sblas_hip_gmres_plan_destroy(void *plan);
+/* start / iterate / status: as the Krylov plan's.  iterate enqueues k steps, a close and a restart behind every m-th
+ * step since start, and a close at its end.  status out: [0] status [1] iterations [2] |r| of the recurrence (|b - A x|
+ * when a cycle has just begun) [3] |b| [4] restarts [5] finished columns of the open cycle [6] the last eta (beta when
+ * a cycle has just begun) [7] the denominator of a breakdown, else 0. */
+int sblas_hip_gmres_start(void *plan, void *stream, const double *val, const double *lu_or_dinv, const double *b, double *x,
+                          double rtol, double atol, int64_t max_iter);
+int sblas_hip_gmres_iterate(void *plan, void *stream, int64_t k);
+int sblas_hip_gmres_status(const void *plan, void *stream, double out[8]);
+
+/* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
  * (the gradient of C = A * B with respect to A's values with X = dC and Y = B; edge scores; residuals on a pattern).
  *   - A gives its PATTERN only (rowptr, colidx).  Unsorted rows and duplicate entries are legal, as everywhere else; a

@@ -59,6 +59,10 @@ EXPORTS = [
     "sblas_krylov_limits", "sblas_krylov_dot_ref", "sblas_krylov_launches", "sblas_hip_krylov_dot_workspace", "sblas_hip_krylov_dot_f64",
     "sblas_hip_krylov_update_f64", "sblas_hip_krylov_plan_create", "sblas_hip_krylov_plan_info", "sblas_hip_krylov_plan_destroy",
     "sblas_hip_krylov_start", "sblas_hip_krylov_iterate", "sblas_hip_krylov_status",
+    "sblas_gmres_limits", "sblas_gmres_step_ref", "sblas_gmres_solve_ref", "sblas_gmres_launches", "sblas_hip_gmres_dots_workspace",
+    "sblas_hip_gmres_dots_f64", "sblas_hip_gmres_project_f64", "sblas_hip_gmres_combine_f64", "sblas_hip_gmres_plan_create",
+    "sblas_hip_gmres_plan_info", "sblas_hip_gmres_plan_destroy", "sblas_hip_gmres_start", "sblas_hip_gmres_iterate",
+    "sblas_hip_gmres_status",
 ]
 
 
@@ -340,6 +344,34 @@ def lib():
     L.sblas_hip_krylov_iterate.argtypes = [vp, vp, i64]
     L.sblas_hip_krylov_status.restype = C.c_int
     L.sblas_hip_krylov_status.argtypes = [vp, vp, C.POINTER(f64)]
+    L.sblas_gmres_limits.restype = C.c_int
+    L.sblas_gmres_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_gmres_step_ref.restype = C.c_int
+    L.sblas_gmres_step_ref.argtypes = [C.c_int, vp, f64, vp, vp, vp, vp, f64, i64, C.POINTER(i64), C.POINTER(f64), C.POINTER(i64)]
+    L.sblas_gmres_solve_ref.restype = C.c_int
+    L.sblas_gmres_solve_ref.argtypes = [C.c_int, vp, C.c_int, vp, vp]
+    L.sblas_gmres_launches.restype = i64
+    L.sblas_gmres_launches.argtypes = [C.c_int, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_hip_gmres_dots_workspace.restype = sz
+    L.sblas_hip_gmres_dots_workspace.argtypes = [i64, C.c_int]
+    L.sblas_hip_gmres_dots_f64.restype = C.c_int
+    L.sblas_hip_gmres_dots_f64.argtypes = [C.c_int, vp, i64, C.c_int, vp, i64, vp, vp, vp, sz]
+    L.sblas_hip_gmres_project_f64.restype = C.c_int
+    L.sblas_hip_gmres_project_f64.argtypes = [C.c_int, vp, i64, C.c_int, vp, i64, vp, vp, vp]
+    L.sblas_hip_gmres_combine_f64.restype = C.c_int
+    L.sblas_hip_gmres_combine_f64.argtypes = [C.c_int, vp, i64, C.c_int, vp, i64, vp, vp]
+    L.sblas_hip_gmres_plan_create.restype = C.c_int
+    L.sblas_hip_gmres_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(vp)]
+    L.sblas_hip_gmres_plan_info.restype = C.c_int
+    L.sblas_hip_gmres_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_gmres_plan_destroy.restype = C.c_int
+    L.sblas_hip_gmres_plan_destroy.argtypes = [vp]
+    L.sblas_hip_gmres_start.restype = C.c_int
+    L.sblas_hip_gmres_start.argtypes = [vp, vp, vp, vp, vp, vp, f64, f64, i64]
+    L.sblas_hip_gmres_iterate.restype = C.c_int
+    L.sblas_hip_gmres_iterate.argtypes = [vp, vp, i64]
+    L.sblas_hip_gmres_status.restype = C.c_int
+    L.sblas_hip_gmres_status.argtypes = [vp, vp, C.POINTER(f64)]
     _lib = L
     return L
 
@@ -680,6 +712,70 @@ def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches
     if n < 0:
         raise SblasError("sblas_krylov_launches refused its arguments")
     return n
+
+
+# Restarted GMRES: the denominators a breakdown names continue the Krylov solvers' (SBLAS_GMRES_DENOM_*)
+GMRES_DENOM = dict(KRYLOV_DENOM)
+GMRES_DENOM.update({6: "givens", 7: "beta"})
+_PRECOND_CODE = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0}
+
+
+def gmres_limits():
+    """GMRES's limits (sblas_gmres_limits): dict(max_restart, default_restart, max_dots, vectors_per_restart,
+    vectors_fixed, scalar_bytes, matrix_bytes, dot_group).  A plan of restart m owns vectors_per_restart * m +
+    vectors_fixed work vectors (ILU(0) adds the solves' temporary)."""
+    out = (C.c_int64 * 8)()
+    check(lib().sblas_gmres_limits(out), "sblas_gmres_limits")
+    keys = ("max_restart", "default_restart", "max_dots", "vectors_per_restart", "vectors_fixed", "scalar_bytes", "matrix_bytes", "dot_group")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def gmres_step_ref(j, h, eta, c, s, g, tol, iterations=0, max_iter=1000):
+    """The scalar step of Arnoldi step j restated on the host (sblas_gmres_step_ref).  h: the j + 1 entries of the new
+    Hessenberg column; c, s: the rotations so far (at least j entries); g: at least j + 1 entries.  Nothing given is
+    changed -> dict(status, code, h, c, s, g, rcol, iterations, rnorm, breakdown) with c, s of j + 1 and g of j + 2
+    entries; rnorm is None and c, s, g are the given ones after a breakdown."""
+    j = int(j)
+    if not 0 <= j < gmres_limits()["max_restart"]:
+        raise SblasError("j must be in [0, %d), not %d" % (gmres_limits()["max_restart"], j))
+    pad = lambda a, k: np.concatenate([np.asarray(a, np.float64).ravel()[:k], np.zeros(max(k - len(np.ravel(a)), 0))])
+    if len(np.ravel(h)) != j + 1 or len(np.ravel(c)) < j or len(np.ravel(s)) < j or len(np.ravel(g)) < j + 1:
+        raise SblasError("h needs j + 1 entries, c and s at least j, g at least j + 1")
+    h, c, s, g, rcol = pad(h, j + 1), pad(c, j + 1), pad(s, j + 1), pad(g, j + 2), np.zeros(j + 1)
+    it, rnorm, which = C.c_int64(int(iterations)), C.c_double(float("nan")), C.c_int64(0)
+    code = lib().sblas_gmres_step_ref(j, h.ctypes.data, float(eta), c.ctypes.data, s.ctypes.data, g.ctypes.data, rcol.ctypes.data,
+                                      float(tol), int(max_iter), C.byref(it), C.byref(rnorm), C.byref(which))
+    if code < 0:
+        raise SblasError("sblas_gmres_step_ref refused its arguments")
+    broke = code == KRYLOV_BREAKDOWN
+    return dict(status=KRYLOV_STATUS[code], code=code, h=h, c=c[:j] if broke else c, s=s[:j] if broke else s, g=g[:j + 1] if broke else g,
+                rcol=None if broke else rcol, iterations=int(it.value), rnorm=None if broke else float(rnorm.value),
+                breakdown=GMRES_DENOM[int(which.value)])
+
+
+def gmres_solve_ref(R, g):
+    """The back substitution restated on the host (sblas_gmres_solve_ref): y with R y = g over k = R.shape[0] columns; R
+    is the k x k upper triangle as a numpy matrix (R[i, l]), g has at least k entries."""
+    R = np.asarray(R, np.float64)
+    k = R.shape[0] if R.ndim == 2 else -1
+    if R.ndim != 2 or R.shape[1] != k or len(np.ravel(g)) < k:
+        raise SblasError("R must be k x k and g have at least k entries")
+    cols = np.ascontiguousarray(R.T)                                         # by columns: entry (i, l) at l * k + i
+    g = np.ascontiguousarray(np.ravel(g)[:k], np.float64)
+    y = np.zeros(k)
+    check(lib().sblas_gmres_solve_ref(k, cols.ctypes.data, max(k, 1), g.ctypes.data, y.ctypes.data), "sblas_gmres_solve_ref")
+    return y
+
+
+def gmres_launches(restart=30, precond=None, lower_launches=0, upper_launches=0):
+    """Launches of GMRES (sblas_gmres_launches) -> dict(step, close, restart, start, cycle); a step's do not depend on j.
+    precond: None, "jacobi" or "ilu0"; lower_launches / upper_launches: SptrsvPlan.info()["launches"], read with "ilu0" only."""
+    lo, up, out = (C.c_int64 * 12)(), (C.c_int64 * 12)(), (C.c_int64 * 4)()
+    lo[5], up[5] = int(lower_launches), int(upper_launches)
+    cycle = int(lib().sblas_gmres_launches(int(restart), _PRECOND_CODE.get(precond, -1), lo, up, out))
+    if cycle < 0:
+        raise SblasError("sblas_gmres_launches refused its arguments")
+    return dict(step=int(out[0]), close=int(out[1]), restart=int(out[2]), start=int(out[3]), cycle=cycle)
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -2262,7 +2358,7 @@ class KrylovPlan:
             pass
 
 
-def _krylov_one_shot(method, A, b, precond, x, kw):
+def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
     import torch
     n, rowptr, colidx, val = A
     if precond not in (None, "jacobi", "ilu0"):
@@ -2276,7 +2372,8 @@ def _krylov_one_shot(method, A, b, precond, x, kw):
                 lu = ilu.factor(val)
             else:
                 dinv = ilu.pivots(val).reciprocal_()
-        plan = KrylovPlan(n, rowptr, colidx, method=method, precond=ilu if precond == "ilu0" else precond)
+        pre = ilu if precond == "ilu0" else precond
+        plan = make(n, rowptr, colidx, pre) if make is not None else KrylovPlan(n, rowptr, colidx, method=method, precond=pre)
         return plan.solve(val, b, x=x, lu=lu, dinv=dinv, **kw)
     finally:
         if plan is not None:
@@ -2295,6 +2392,224 @@ def pcg(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_ev
 def bicgstab(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
     """x with A x = b by preconditioned BiCGStab, one shot, as pcg(); A need not be symmetric."""
     return _krylov_one_shot("bicgstab", A, b, precond, x, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
+
+
+# ------------------------------------------------------------------------------------------
+# Restarted GMRES(m) on a plan of its own (sblas_hip_gmres_*)
+# ------------------------------------------------------------------------------------------
+def _gmres_columns(V, k_max):
+    """V: k columns of n entries as a (k, n) float64 GPU tensor with unit stride along a column and one stride between
+    columns (a view with a larger stride serves) -> (k, n, ldv)"""
+    import torch
+    if not isinstance(V, torch.Tensor) or not V.is_cuda:
+        raise SblasError("V must be a GPU tensor (no CPU path exists)")
+    if V.dtype != torch.float64 or V.dim() != 2:
+        raise SblasError("V must be a float64 tensor of shape (columns, n)")
+    k, n = V.shape
+    if not 1 <= k <= k_max:
+        raise SblasError("one to %d columns, not %d" % (k_max, k))
+    if n > 1 and V.stride(1) != 1:
+        raise SblasError("a column of V must be contiguous")
+    ldv = V.stride(0) if k > 1 else max(n, 1)
+    if k > 1 and ldv < n:
+        raise SblasError("the column stride %d is below n = %d" % (ldv, n))
+    return k, n, ldv
+
+
+def gmres_dots(V, w, out=None, workspace=None, stream=None):
+    """out[i] = (V[i], w) for up to 65 columns in ONE pass over memory (sblas_hip_gmres_dots_f64), each with exactly the bits
+    krylov_dot(V[i], w) gives.  V: (k, n), see _gmres_columns.  No synchronisation; with out and workspace (float64, at
+    least k * ceil(n / cell) entries) given, nothing is allocated."""
+    import torch
+    k, n, ldv = _gmres_columns(V, gmres_limits()["max_dots"])
+    _krylov_vector("w", w, n, V.device)
+    if out is None:
+        out = torch.empty(k, dtype=torch.float64, device=V.device)
+    _krylov_vector("out", out, k, V.device)
+    need = int(lib().sblas_hip_gmres_dots_workspace(n, k))
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=V.device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous():
+        raise SblasError("workspace must be a contiguous float64 GPU tensor")
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_gmres_dots_f64(-1, _stream(stream), n, k, V.data_ptr() if n else None, ldv, w.data_ptr() if n else None,
+                                             out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8), "sblas_hip_gmres_dots_f64")
+    return out
+
+
+def gmres_project(V, h, w, partial=None, stream=None):
+    """w = w - h[0] V[0] - h[1] V[1] - ... in place, ascending, each product and each difference rounded
+    (sblas_hip_gmres_project_f64); h: k doubles on the device.  partial: None, or a float64 tensor of at least
+    ceil(n / cell) entries that receives the first stage of (w, w) over the new w."""
+    import torch
+    k, n, ldv = _gmres_columns(V, gmres_limits()["max_dots"])
+    _krylov_vector("w", w, n, V.device), _krylov_vector("h", h, k, V.device)
+    if partial is not None:
+        _krylov_vector("partial", partial, partial.numel() if isinstance(partial, torch.Tensor) else -1, V.device)
+        if partial.numel() < -(-n // krylov_limits()["cell"]):
+            raise SblasError("partial is too short")
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_gmres_project_f64(-1, _stream(stream), n, k, V.data_ptr() if n else None, ldv, h.data_ptr(),
+                                                w.data_ptr() if n else None,
+                                                partial.data_ptr() if partial is not None and partial.numel() else None),
+              "sblas_hip_gmres_project_f64")
+    return w
+
+
+def gmres_combine(V, y, out=None, stream=None):
+    """u = y[0] V[0], then u = u + y[l] V[l] ascending, rounded product and rounded sum (sblas_hip_gmres_combine_f64) ->
+    u (out when given; it must not be part of V)."""
+    import torch
+    k, n, ldv = _gmres_columns(V, gmres_limits()["max_dots"])
+    _krylov_vector("y", y, k, V.device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=V.device)
+    _krylov_vector("out", out, n, V.device)
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_gmres_combine_f64(-1, _stream(stream), n, k, V.data_ptr() if n else None, ldv, y.data_ptr(),
+                                                out.data_ptr() if n else None), "sblas_hip_gmres_combine_f64")
+    return out
+
+
+class GmresPlan:
+    """Right-preconditioned restarted GMRES(restart) for A x = b on the n x n CSR structure (rowptr, colidx), int32
+    indices, resident on the device (sblas_hip_gmres_plan_create).  A need not be symmetric.  spmv_plan and precond: as
+    KrylovPlan's.  A plan of its own rather than a method of KrylovPlan: it owns restart + 1 basis vectors and the small
+    triangular system beside the work vectors, and one iteration is one Arnoldi step (one SpMV, one M^-1).
+
+    start() forms r = b - A x and v_0; iterate(k) enqueues k steps -- with a close (x = x + M^-1 V y) and a restart
+    behind every restart-th step, and a close at its end -- without allocating or synchronising (graph-capturable);
+    status() is the one call that synchronises.  Once the test |g_{j+1}| <= max(rtol |b|, atol) is met on the device,
+    what is already enqueued only forms x from the finished columns: x, the count, |r| and the restart count do not
+    depend on check_every.  Every bit is pinned (include/sblas_hip.h)."""
+
+    def __init__(self, n, rowptr, colidx, restart=30, spmv_plan=None, precond=None, stream=None):
+        import torch
+        self.handle = None
+        if isinstance(restart, bool) or not isinstance(restart, int) or not 1 <= restart <= gmres_limits()["max_restart"]:
+            raise SblasError("restart must be an integer in [1, %d], not %r" % (gmres_limits()["max_restart"], restart))
+        self.n, self.restart = n, restart
+        self.spmv_plan, self.precond = spmv_plan, precond
+        lower = upper = None
+        if precond is None:
+            self.precond_kind = PRECOND_NONE
+        elif isinstance(precond, str) and precond == "jacobi":
+            self.precond_kind = PRECOND_JACOBI
+        elif isinstance(precond, Ilu0Plan):
+            self.precond_kind = PRECOND_ILU0
+            lower, upper = precond.solvers()
+        elif isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
+            self.precond_kind = PRECOND_ILU0
+            lower, upper = precond
+        else:
+            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan or a pair of SptrsvPlans, not %r" % (precond,))
+        if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
+            raise SblasError("spmv_plan must be an SpmvPlan or None")
+        self.nnz = _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        self._solvers = (lower, upper)
+        self._keep = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_gmres_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
+                                                   colidx.data_ptr() if self.nnz else None, restart,
+                                                   spmv_plan.handle if spmv_plan is not None else None, self.precond_kind,
+                                                   lower.handle if lower is not None else None,
+                                                   upper.handle if upper is not None else None, C.byref(h))
+        check(rc, "sblas_hip_gmres_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 14)()
+        check(lib().sblas_hip_gmres_plan_info(self.handle, out), "sblas_hip_gmres_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=(None, "jacobi", "ilu0")[out[3]], vectors=int(out[4]),
+                    vector_bytes=int(out[5]), partial_bytes=int(out[6]), scalar_bytes=int(out[7]), matrix_bytes=int(out[8]),
+                    bytes=int(out[9]), step_launches=int(out[10]), close_launches=int(out[11]), restart_launches=int(out[12]),
+                    cycle_launches=int(out[13]))
+
+    def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
+        """Begins a solve: x on entry is the initial guess and is updated in place as cycles close.  lu: the ILU(0) factor
+        (precond an Ilu0Plan); dinv: the inverse diagonal (precond "jacobi").  Every refusal comes before any launch."""
+        import torch
+        if x is b:
+            raise SblasError("x must not be b")
+        _krylov_vector("val", val, self.nnz, self.device), _krylov_vector("b", b, self.n, self.device)
+        _krylov_vector("x", x, self.n, self.device)
+        pre = None
+        if self.precond_kind == PRECOND_ILU0:
+            if lu is None:
+                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
+            _krylov_vector("lu", lu, self.nnz, self.device)
+            pre = lu
+        elif self.precond_kind == PRECOND_JACOBI:
+            if dinv is None:
+                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
+            _krylov_vector("dinv", dinv, self.n, self.device)
+            pre = dinv
+        if self.n and x.data_ptr() == b.data_ptr():
+            raise SblasError("x must not be b")
+        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
+            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_gmres_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                             pre.data_ptr() if pre is not None and pre.numel() else None,
+                                             b.data_ptr() if self.n else None, x.data_ptr() if self.n else None,
+                                             float(rtol), float(atol), int(max_iter))
+        check(rc, "sblas_hip_gmres_start")
+        self._keep = (val, b, x, pre)
+
+    def iterate(self, k, stream=None):
+        """Enqueues k Arnoldi steps and the closes and restarts that belong with them: allocates nothing, never
+        synchronises, graph-capturable as a chain."""
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_gmres_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_gmres_iterate")
+
+    def status(self, stream=None):
+        """Copies the scalar block back and synchronises the stream -> dict(status, code, iterations, rnorm, bnorm,
+        restarts, columns, eta, breakdown): columns are the finished ones of the open cycle, breakdown a value of
+        GMRES_DENOM or None."""
+        import torch
+        out = (C.c_double * 8)()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_gmres_status(self.handle, _stream(stream), out), "sblas_hip_gmres_status")
+        return dict(status=KRYLOV_STATUS[int(out[0])], code=int(out[0]), iterations=int(out[1]), rnorm=float(out[2]), bnorm=float(out[3]),
+                    restarts=int(out[4]), columns=int(out[5]), eta=float(out[6]), breakdown=GMRES_DENOM[int(out[7])])
+
+    def solve(self, val, b, x=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
+        """start(), then iterate(check_every) / status() until the status is not "running" -> (x, status dict).  x: the
+        initial guess, updated in place (zeros made here when None).  The result does not depend on check_every."""
+        import torch
+        if int(check_every) < 1:
+            raise SblasError("check_every must be at least 1")
+        if x is None:
+            _krylov_vector("b", b, self.n, self.device)
+            x = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        self.start(val, b, x, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
+        while True:
+            self.iterate(int(check_every), stream=stream)
+            st = self.status(stream=stream)
+            if st["code"] != KRYLOV_RUNNING:
+                return x, st
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_gmres_plan_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def gmres(A, b, precond=None, restart=30, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
+    """x with A x = b by right-preconditioned restarted GMRES(restart), one shot, as pcg(); A need not be symmetric and
+    max_iter counts Arnoldi steps."""
+    return _krylov_one_shot(None, A, b, precond, x, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every),
+                            make=lambda n, rowptr, colidx, pre: GmresPlan(n, rowptr, colidx, restart=restart, precond=pre))
 
 
 # ------------------------------------------------------------------------------------------
