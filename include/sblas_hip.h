@@ -764,7 +764,8 @@ double sblas_krylov_dot_ref(int64_t n, const double *x, const double *y);
 /* Launches of ONE iteration: the solver's own kernels, one per SpMV (a planned SpMV of k kernel classes launches k), and
  * the two solves' of every M^-1 with ILU(0) -- lower_info / upper_info are the out[12] of sblas_hip_sptrsv_plan_info
  * (read: [5] launches; NULL unless ILU(0)).  PCG: 6, with ILU(0) 8 + lower + upper.  BiCGStab: 10 + 2 (lower + upper).
- * -1 for a bad argument. */
+ * With SBLAS_PRECOND_AMG lower_info is the out[12] of sblas_hip_amg_plan_info ([5]: launches of one cycle), upper_info is
+ * not read, and the counts are ILU(0)'s with the cycle's launches as the M^-1's.  -1 for a bad argument. */
 int64_t sblas_krylov_launches(int method, int precond, const int64_t *lower_info, const int64_t *upper_info);
 /* The pinned dot on its own: out[k] = (x[k], y[k]) for k < ndots <= 3, one pass over memory and one fold; x, y: HOST
  * arrays of ndots device pointers, out: ndots doubles on the device.  workspace: at least ..._dot_workspace(n, ndots)
@@ -784,7 +785,11 @@ int sblas_hip_krylov_update_f64(int dev, void *stream, int op, int jacobi, int64
  * sblas_hip_spmv_plan_create on the same (n, n, nnz, rowptr, colidx), or NULL for the unplanned SpMV.  precond ILU0:
  * lower_plan (SBLAS_FILL_LOWER, SBLAS_DIAG_UNIT) and upper_plan (SBLAS_FILL_UPPER, SBLAS_DIAG_NON_UNIT) of
  * sblas_hip_sptrsv_plan_create on the same rowptr / colidx; otherwise both NULL.  A plan of another device, structure,
- * fill or diag is refused (SBLAS_E_INVALID).  The plan keeps the POINTERS and the handles, which must outlive it. */
+ * fill or diag is refused (SBLAS_E_INVALID).  precond SBLAS_PRECOND_AMG: the handle of sblas_hip_amg_plan_create on the
+ * same (n, nnz, rowptr, colidx) travels as lower_plan and upper_plan is NULL; it is verified with
+ * sblas_hip_amg_plan_speaks_for, its cycle takes exactly the place of ILU(0)'s two solves (the same dots, folds, freeze
+ * and extra work vector), and start's lu_or_dinv is ignored: the AMG plan holds its values from its own setup.  The
+ * plan keeps the POINTERS and the handles, which must outlive it. */
 int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr,
                                  const int32_t *colidx, const void *spmv_plan, int precond, const void *lower_plan,
                                  const void *upper_plan, void **plan_out);
@@ -868,7 +873,8 @@ int sblas_gmres_solve_ref(int k, const double *R, int ldr, const double *g, doub
 /* Launches: out[0] of one step (the same for every j), out[1] of a close, out[2] of a restart, out[3] of start; counted
  * as sblas_krylov_launches counts (one per SpMV, lower_info / upper_info [5] per solve with ILU(0), NULL otherwise).
  * step 9 + lower + upper, close 3 + lower + upper, restart 4, start 6.  Returns those of a full cycle,
- * m * out[0] + out[1] + out[2], or -1 for a bad argument. */
+ * m * out[0] + out[1] + out[2], or -1 for a bad argument.  SBLAS_PRECOND_AMG: as sblas_krylov_launches (lower_info is the
+ * AMG plan's info, its [5] the launches of an M^-1). */
 int64_t sblas_gmres_launches(int m, int precond, const int64_t *lower_info, const int64_t *upper_info, int64_t out[4]);
 /* The multi-dot on its own: out[i] = (V + i * ldv, w) for i < k <= 65; V, w, out on the device, ldv >= n when k > 1.
  * workspace: at least ..._dots_workspace(n, k) bytes on the device, 8-byte aligned (SBLAS_E_WORKSPACE when missing or
@@ -902,6 +908,99 @@ int sblas_hip_gmres_start(void *plan, void *stream, const double *val, const dou
                           double rtol, double atol, int64_t max_iter);
 int sblas_hip_gmres_iterate(void *plan, void *stream, int64_t k);
 int sblas_hip_gmres_status(const void *plan, void *stream, double out[8]);
+
+/* ---------------------------------------------------------------------------------------
+ * Aggregation AMG on a device plan:  z = M^-1 r by ONE V(nu, nu) cycle of a plain (unsmoothed) aggregation multigrid from
+ * a zero guess, for a square CSR matrix with fp64 values and int32 indices whose rows are strictly ascending and store
+ * their diagonal (ILU(0)'s structure contract and its refusal, which names the first bad row).  create works on the
+ * structure, setup is numeric and repeatable, apply is a fixed graph-capturable sequence of launches that allocates
+ * nothing, never synchronises, uses no atomics and in which nothing waits across workgroups.  M^-1 is symmetric when A
+ * is, so PCG may use it; the Krylov and GMRES plans take the handle with SBLAS_PRECOND_AMG.  Every bit is pinned:
+ *   - aggregation of level l (sblas_amg_aggregate).  The strong neighbours of row i are its stored off-diagonal
+ *     entries; with values and theta > 0 only those with |a_ij| >= theta * max_{k != i} |a_ik| (the product rounded).
+ *     Only row i's own entries are consulted.  The vertices are walked in descending fmix32(v + 0x9E3779B9 * (seed + l +
+ *     1)) (the colouring's priority, which has no ties); a vertex is a ROOT unless one of its strong neighbours already
+ *     is.  Roots are numbered in ascending vertex index; every other vertex joins the first root among its strong
+ *     neighbours in stored order.  members: the vertices by (aggregate, vertex); aggptr: n_agg + 1 entries.
+ *   - the coarse pattern is the COO plan (SBLAS_COO_SUM) of the triplets (agg[row(e)], agg[col(e)]) for e in stored
+ *     order; the coarse values are its re-assembly: duplicates added left to right in input order.
+ *   - coarsening goes on while n_l > coarse_max and l + 1 < max_levels; a level that does not reduce n is discarded.
+ *     With theta > 0 the coarse levels' strength tests use coarse values formed on the host in the same order from the
+ *     val given to create; the hierarchy is then fixed, and setup with other values keeps the aggregates.
+ *   - setup.  wd_i = omega / a_ii (SBLAS_AMG_JACOBI, default omega 2/3) or omega / sum_e |a_ie| added sequentially in
+ *     stored order from +0 (SBLAS_AMG_L1, default omega 1), a rounded division.  A diagonal that is not finite and > 0 is
+ *     flagged on the device as the least (level, row); sblas_hip_amg_plan_check reads the flag and is the one call that
+ *     synchronises.
+ *   - the row sweep  y_i = x_i + wd_i * (b_i - s_i):  s_i is the row sum in the triangular solves' order over the whole
+ *     row -- G(p) = 4 / 16 / 64 lanes for a stored length p <= 4 / <= 32 / beyond, lane l the entries l, l + G, ... with
+ *     one fused multiply-add each from +0, the lanes folded by the butterfly l ^ 1, l ^ 2, ... -- then a rounded
+ *     difference, a rounded product and a rounded sum.  The residual mode writes b_i - s_i; the first sweep from zero
+ *     is y_i = wd_i * b_i.  x and y are distinct arrays.
+ *   - restriction  b_c[I] = the residual summed over aggregate I's members in ascending vertex order, sequentially from
+ *     +0;  prolongation  x_i = x_i + coarse_scale * e[agg[i]], a rounded product and a rounded sum.
+ *   - a cycle on level l: nu sweeps (the first from zero), residual, restrict, the cycle of level l + 1, prolong, nu
+ *     sweeps.  The coarsest level runs coarse_sweeps sweeps from zero and nothing else.  (2 nu + 3) launches a level and
+ *     coarse_sweeps on the coarsest (sblas_amg_launches).
+ * ------------------------------------------------------------------------------------- */
+#define SBLAS_PRECOND_AMG 3
+#define SBLAS_AMG_JACOBI 0
+#define SBLAS_AMG_L1 1
+#define SBLAS_AMG_SWEEP 0    /* modes of sblas_hip_amg_sweep_f64 */
+#define SBLAS_AMG_RESIDUAL 1
+#define SBLAS_AMG_FIRST 2
+/* HOST functions (no GPU call; testable alone).  limits: [0], [1] the longest stored rows that 4 and 16 lanes take [2]
+ * threads of a workgroup [3] default coarse_max [4] default max_levels [5] default nu [6] default coarse_sweeps [7] the
+ * largest max_levels */
+int sblas_amg_limits(int64_t out[8]);
+/* One level's aggregation on host arrays.  val: NULL for structure only (then theta must be 0); theta in [0, 1].  agg,
+ * members: n entries; aggptr: room for n + 1, *n_agg + 1 written.  SBLAS_E_INVALID with *bad_row for a bad structure. */
+int sblas_amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
+                        uint32_t level, int32_t *agg, int32_t *aggptr, int32_t *members, int64_t *n_agg, int64_t *bad_row);
+/* launches of one apply on `levels` levels; -1 for a bad argument (nu, coarse_sweeps >= 1; levels in [0, 64]) */
+int64_t sblas_amg_launches(int levels, int nu, int coarse_sweeps);
+/* setup's wd on host arrays (omega as given, no default).  *bad_row: the first row whose diagonal is not finite and > 0
+ * (reported, SBLAS_OK all the same, as the device flags it), or a row without a diagonal (SBLAS_E_INVALID). */
+int sblas_amg_wd_ref(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, int smoother, double omega,
+                     double *wd, int64_t *bad_row);
+/* The whole cycle in plain C++ on host arrays: arrays of `levels` pointers (agg, aggptr, members: levels - 1 are read; level
+ * l's aggptr has n[l + 1] + 1 entries).  z must not be r. */
+int sblas_amg_cycle_ref(int levels, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx,
+                        const double *const *val, const double *const *wd, const int32_t *const *agg,
+                        const int32_t *const *aggptr, const int32_t *const *members, int nu, int coarse_sweeps,
+                        double coarse_scale, const double *r, double *z);
+/* create: the hierarchy, host work with the device sorts of the COO plans; `stream` is synchronised.  val: device values,
+ * read (once) only when theta > 0, else NULL.  coarse_max, max_levels: 0 takes the default.  Refused before any launch:
+ * a bad structure (*bad_row), n or nnz beyond INT_MAX, theta outside [0, 1] or NaN, theta > 0 without val.  The plan
+ * keeps the POINTERS rowptr and colidx (level 0 sweeps on them) and owns everything else. */
+int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
+                              const double *val, double theta, int64_t coarse_max, int max_levels, uint32_t seed,
+                              void **plan_out, int64_t *bad_row);
+/* out: [0] n [1] nnz [2] levels [3] nu [4] coarse_sweeps [5] launches of one apply [6] rows of all levels [7] stored
+ * entries of all levels [8] device bytes held [9] smoother [10] 1 after a setup [11] rows of the coarsest level */
+int sblas_hip_amg_plan_info(const void *plan, int64_t out[12]);
+/* One level's device arrays.  sizes: [0] n [1] nnz [2] aggregates = n of the next level (0 on the coarsest) [3] four-lane
+ * units of a sweep launch.  ptrs: rowptr, colidx, val, wd, agg, aggptr, members (the last three NULL on the coarsest; val
+ * of level 0 is setup's pointer, NULL before it). */
+int sblas_hip_amg_plan_level(const void *plan, int level, int64_t sizes[4], const void *ptrs[7]);
+/* setup: every level's values and wd, device work only: allocates nothing, never synchronises, graph-capturable.
+ * omega: 0 takes the smoother's default.  The plan keeps the POINTER val, which level 0 sweeps on: it must stay valid and
+ * unchanged until the next setup.  Stream-ordered on the calling thread's current device, which must be the plan's. */
+int sblas_hip_amg_plan_setup(void *plan, void *stream, const double *val, int smoother, double omega, int nu, int coarse_sweeps,
+                             double coarse_scale);
+/* apply: z = M^-1 r.  Refused before setup and when z overlaps r.  The plan owns every level vector. */
+int sblas_hip_amg_plan_apply(const void *plan, void *stream, const double *r, double *z);
+/* check: out[0] level, out[1] row of the least flagged diagonal of the last setup, or -1, -1; synchronises `stream` */
+int sblas_hip_amg_plan_check(const void *plan, void *stream, int64_t out[2]);
+/* SBLAS_OK when the plan lives on device `dev` (< 0: the current one) and was made for exactly this structure */
+int sblas_hip_amg_plan_speaks_for(const void *plan, int dev, int64_t n, int64_t nnz, const int32_t *rowptr,
+                                  const int32_t *colidx);
+int sblas_hip_amg_plan_destroy(void *plan);
+/* The single kernels on level `level` of a plan (for tests and for loops composed by the caller); one launch each.
+ * sweep: mode SBLAS_AMG_SWEEP / _RESIDUAL / _FIRST (x unread), after a setup; y must overlap neither x nor b.
+ * restrict: bc[I] over level `level`'s aggregates (not the coarsest level).  prolong: x_i += scale * e[agg[i]]. */
+int sblas_hip_amg_sweep_f64(const void *plan, void *stream, int level, int mode, const double *b, const double *x, double *y);
+int sblas_hip_amg_restrict_f64(const void *plan, void *stream, int level, const double *res, double *bc);
+int sblas_hip_amg_prolong_f64(const void *plan, void *stream, int level, double scale, const double *e, double *x);
 
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A

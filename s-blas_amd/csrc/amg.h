@@ -1,0 +1,82 @@
+// amg.h -- what amg.hip's kernels and amg_rule.cpp's host rule agree on: the lane groups of a row sweep,
+// the defaults, the order of a V-cycle as ONE walk both sides instantiate, and the host rule's internal interface.  No
+// HIP in here: amg_rule.cpp is testable on a CPU box.
+#pragma once
+#include <stdint.h>
+#include <vector>
+#include "sptrsv.h"
+
+namespace sblas {
+
+// A row of p stored entries is summed by the solves' G(p) lanes (sptrsv_group_shift): 4 lanes up to AMG_G4_MAX, 16 up to
+// AMG_G16_MAX, a whole wave beyond.
+constexpr int64_t AMG_G4_MAX = SPTRSV_G4_MAX;
+constexpr int64_t AMG_G16_MAX = SPTRSV_G16_MAX;
+constexpr int AMG_THREADS = 256; // a workgroup of every AMG kernel: four waves
+constexpr int64_t AMG_COARSE_MAX = 64;
+constexpr int AMG_MAX_LEVELS = 20;
+constexpr int AMG_LEVEL_CAP = 64; // max_levels is at most this
+constexpr int AMG_NU = 1;
+constexpr int AMG_COARSE_SWEEPS = 8;
+constexpr int AMG_SWEEP_CAP = 1 << 20; // nu and coarse_sweeps are at most this: launch counts stay far inside int64
+
+// The vectors of one level.  b: the right-hand side (level 0: the caller's r); x[0], x[1]: the two iterates a sweep
+// ping-pongs between (other rows gather x while y is written); res: the residual that is restricted.  Level 0's last
+// write must land in the caller's z, so z is whichever of x[0] / x[1] the parity of the level's writes selects
+// (amg_first_buffer).
+//
+// One V(nu, nu) cycle from a zero guess, as calls on `ops` -- the device enqueues a launch for each, the host
+// reference computes it, the launch counter counts it.  `cur` is the index of the buffer that holds the level's iterate.
+//   first(l, dst)          x[dst] = wd o b                        (the first sweep from zero)
+//   sweep(l, src, dst)     x[dst] = x[src] + wd o (b - A x[src])
+//   residual(l, src)       res = b - A x[src]
+//   restrict_to(l)         b of level l + 1 = sums of res over the aggregates of level l
+//   prolong(l, dst)        x[dst] of level l += scale * (the iterate of level l + 1)[agg]
+// The iterate of level l ends in x[amg_last_buffer(...)], which both sides compute the same way.
+inline int amg_level_writes(int level, int levels, int nu, int coarse_sweeps) { return level + 1 == levels ? coarse_sweeps : 2 * nu; }
+// the buffer the first write goes to, so that the last one lands in buffer 1
+inline int amg_first_buffer(int level, int levels, int nu, int coarse_sweeps)
+{
+    return amg_level_writes(level, levels, nu, coarse_sweeps) % 2 ? 1 : 0;
+}
+constexpr int AMG_RESULT_BUFFER = 1; // every level's iterate ends here (level 0: the caller's z)
+
+template <typename Ops> void amg_cycle(int levels, int nu, int coarse_sweeps, Ops &ops, int level = 0)
+{
+    if (levels <= 0) return;
+    int cur = amg_first_buffer(level, levels, nu, coarse_sweeps);
+    ops.first(level, cur);
+    if (level + 1 == levels) {
+        for (int k = 1; k < coarse_sweeps; ++k) ops.sweep(level, cur, cur ^ 1), cur ^= 1;
+        return;
+    }
+    for (int k = 1; k < nu; ++k) ops.sweep(level, cur, cur ^ 1), cur ^= 1;
+    ops.residual(level, cur);
+    ops.restrict_to(level);
+    amg_cycle(levels, nu, coarse_sweeps, ops, level + 1);
+    ops.prolong(level, cur);
+    for (int k = 0; k < nu; ++k) ops.sweep(level, cur, cur ^ 1), cur ^= 1;
+}
+
+// launches of one cycle: every call of the walk is one launch
+struct AmgCount {
+    int64_t n = 0;
+    void first(int, int) { ++n; }
+    void sweep(int, int, int) { ++n; }
+    void residual(int, int) { ++n; }
+    void restrict_to(int) { ++n; }
+    void prolong(int, int) { ++n; }
+};
+
+inline bool amg_cycle_args_ok(int levels, int nu, int coarse_sweeps)
+{
+    return levels >= 0 && levels <= AMG_LEVEL_CAP && nu >= 1 && nu <= AMG_SWEEP_CAP && coarse_sweeps >= 1 && coarse_sweeps <= AMG_SWEEP_CAP;
+}
+inline bool amg_theta_ok(double theta) { return theta >= 0.0 && theta <= 1.0; } // a NaN fails both
+
+// One level's aggregation on host arrays (sblas_amg_aggregate without the argument checks): agg (n), aggptr (n_agg + 1,
+// resized here), members (n) -> n_agg.  val may be null (structure only).
+int64_t amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
+                      uint32_t level, int32_t *agg, std::vector<int32_t> &aggptr, int32_t *members);
+
+} // namespace sblas

@@ -1,0 +1,466 @@
+// amg.hip -- plain (unsmoothed) aggregation AMG on a device plan: z = M^-1 r by one V(nu, nu) cycle from
+// a zero guess, for a square CSR matrix with fp64 values, int32 indices, strictly ascending rows and a stored diagonal.
+//
+// create is host work, as the level plans do it: every level is aggregated on the host by the pinned rule of
+// amg_rule.cpp, and the coarse pattern of a level is the COO plan (dup = sum) of the triplets (agg[row], agg[col]) in
+// stored order, sorted once on the device.  setup is device work only: a level's values are the COO plan's re-assembly of
+// the level above (duplicates added left to right in input order) and one kernel writes the smoother's wd = omega / d.
+// apply is a fixed sequence of launches of four kernels, the walk of amg.h:
+//   sweep     y_i = x_i + wd_i (b_i - s_i), or the residual b_i - s_i, s_i the row sum in the solves' pinned order;
+//   first     y_i = wd_i b_i, the first sweep from a zero guess;
+//   restrict  b_c[I] = the sum of the residual over aggregate I's members, ascending, by one thread;
+//   prolong   x_i = x_i + scale * e[agg[i]].
+// Nothing waits across workgroups: no flag polling, no cooperative launch, no atomics in apply; the only synchronisation
+// is the kernel boundary.  apply allocates nothing and never synchronises.
+//
+// Results contract: sweep_row() is the one expression of a row.  Its bits are a function of the row's stored entries in
+// stored order, the x values they name, b_i, x_i and wd_i: the lane group's width G(p) depends on the stored length p
+// alone, lane l takes the entries l, l + G, ... with one fused multiply-add each from +0, and the lanes fold by the
+// butterfly of rowwise.h -- exactly the triangular solves' row sum (sptrsv.hip) over the whole row.  The rows are packed
+// into waves as a solve's wide level packs them (level_plan.h with one level): which rows share a wave does not enter
+// any row's sum.  Everything else is rounded operation by operation: this file is compiled with contraction off.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <memory>
+#include <vector>
+#include "../../include/sblas_hip.h"
+#include "amg.h"
+#include "level_kernels.h"
+#include "rowwise.h"
+
+#pragma clang fp contract(off) // file scope: a * b + c below is two roundings; the row sum calls the fused one by name
+
+using namespace sblas;
+
+namespace {
+
+// four lanes of a sweep launch (level_plan.h); q: the unit's number in its row; a pad has row = -1
+struct Unit {
+    int32_t row, beg, end, q;
+};
+constexpr Unit NO_UNIT{-1, 0, 0, 0};
+constexpr unsigned long long FLAG_CLEAN = ~0ull;
+
+enum { MODE_SWEEP = 0, MODE_RESIDUAL = 1, MODE_FIRST = 2 };
+
+// Row u.row of y.  Every lane of the wave calls this together (the butterfly moves data between lanes); `quad` is the
+// lane's place in its unit.  x and y are distinct arrays: other rows gather x while this one writes y.
+template <int MODE>
+__device__ __forceinline__ void sweep_row(const Unit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val,
+                                          const double *__restrict__ wd, const double *__restrict__ b, const double *__restrict__ x,
+                                          double *__restrict__ y)
+{
+    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg), G = 1 << gs;
+    const int lane = 4 * u.q + quad; // the lane's place among the row's G lanes
+    const bool writer = u.row >= 0 && lane == 0;
+    // what the row's last step needs travels with its first entries instead of waiting behind the fold
+    const double bi = writer ? b[u.row] : 0.0;
+    const double xi = writer && MODE == MODE_SWEEP ? x[u.row] : 0.0;
+    const double wi = writer && MODE == MODE_SWEEP ? wd[u.row] : 0.0;
+    double s = 0.0;
+    if (u.row >= 0)
+        for (int64_t e = (int64_t)u.beg + lane; e < u.end; e += G) s = __builtin_fma(val[e], x[colidx[e]], s);
+    const double f4 = fold_sum<4>(s);
+    double f16 = f4 + lane_partner<4>(f4);
+    f16 += lane_partner<8>(f16);
+    double f64 = f16 + lane_partner<16>(f16);
+    f64 += lane_partner<32>(f64);
+    if (writer) {
+        const double d = bi - (gs == 2 ? f4 : gs == 4 ? f16 : f64);
+        if constexpr (MODE == MODE_RESIDUAL) {
+            y[u.row] = d;
+        } else {
+            const double t = wi * d;
+            y[u.row] = xi + t;
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(AMG_THREADS) void amg_sweep_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ colidx,
+                                                                const double *__restrict__ val, const double *__restrict__ wd,
+                                                                const double *__restrict__ b, const double *__restrict__ x,
+                                                                double *__restrict__ y)
+{
+    sweep_row<MODE>(wide_unit<AMG_THREADS>(0, count, units, NO_UNIT), threadIdx.x & 3, colidx, val, wd, b, x, y);
+}
+
+// the first sweep from a zero guess: the row sums vanish, x_i + wd_i (b_i - 0) is wd_i b_i
+__global__ __launch_bounds__(AMG_THREADS) void amg_first_kernel(int64_t n, const double *__restrict__ wd, const double *__restrict__ b,
+                                                                double *__restrict__ y)
+{
+    const int64_t i = (int64_t)blockIdx.x * AMG_THREADS + threadIdx.x;
+    if (i < n) y[i] = wd[i] * b[i];
+}
+
+// one thread an aggregate: its members ascending, sequentially from +0
+__global__ __launch_bounds__(AMG_THREADS) void amg_restrict_kernel(int64_t n_agg, const int32_t *__restrict__ aggptr,
+                                                                   const int32_t *__restrict__ members, const double *__restrict__ res,
+                                                                   double *__restrict__ bc)
+{
+    const int64_t a = (int64_t)blockIdx.x * AMG_THREADS + threadIdx.x;
+    if (a >= n_agg) return;
+    double s = 0.0;
+    for (int64_t k = aggptr[a]; k < aggptr[a + 1]; ++k) s = s + res[members[k]];
+    bc[a] = s;
+}
+
+__global__ __launch_bounds__(AMG_THREADS) void amg_prolong_kernel(int64_t n, const int32_t *__restrict__ agg, double scale,
+                                                                  const double *__restrict__ e, double *__restrict__ x)
+{
+    const int64_t i = (int64_t)blockIdx.x * AMG_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const double t = scale * e[agg[i]];
+    x[i] = x[i] + t;
+}
+
+// wd_i = omega / a_ii (Jacobi) or omega / sum_e |a_ie| (l1, sequentially in stored order from +0).  A diagonal that is
+// not finite and > 0 is reported as (level, row) in *flag: the least such pair, whichever thread finds it first -- an
+// integer minimum is the same in every order.
+__global__ __launch_bounds__(AMG_THREADS) void amg_wd_kernel(int64_t n, int level, int smoother, double omega, const int32_t *__restrict__ rowptr,
+                                                             const int32_t *__restrict__ dpos, const double *__restrict__ val,
+                                                             double *__restrict__ wd, unsigned long long *flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * AMG_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const double d = val[dpos[i]];
+    double den = d;
+    if (smoother == SBLAS_AMG_L1) {
+        double s = 0.0;
+        for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) s = s + fabs(val[e]);
+        den = s;
+    }
+    wd[i] = omega / den;
+    if (!(isfinite(d) && d > 0.0)) atomicMin(flag, ((unsigned long long)level << 32) | (unsigned long long)i);
+}
+
+inline unsigned grid_of(int64_t threads) { return (unsigned)((threads + AMG_THREADS - 1) / AMG_THREADS); }
+
+struct AmgLevel {
+    int64_t n = 0, nnz = 0, n_coarse = 0, units = 0;
+    const int32_t *rowptr = nullptr, *colidx = nullptr; // level 0: the caller's; below: the COO plan's of the level above
+    const double *val = nullptr;                        // level 0: setup's; below: own_val
+    void *coo = nullptr;                                // the plan that makes level l + 1's structure and values
+    DeviceBuffer ibuf, dbuf;                            // units | dpos | agg | aggptr | members;  wd | x0 | x1 | res | b | val
+    Unit *d_units = nullptr;
+    int32_t *dpos = nullptr, *agg = nullptr, *aggptr = nullptr, *members = nullptr;
+    double *wd = nullptr, *x[2] = {nullptr, nullptr}, *res = nullptr, *b = nullptr, *own_val = nullptr;
+    size_t bytes = 0;
+    ~AmgLevel()
+    {
+        if (coo) sblas_hip_coo_plan_destroy(coo);
+    }
+};
+
+struct AmgPlan {
+    int dev = -1;
+    int64_t n = 0, nnz = 0;
+    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
+    double theta = 0.0;
+    uint32_t seed = 0;
+    std::vector<std::unique_ptr<AmgLevel>> lv;
+    DeviceBuffer block; // the flag word
+    unsigned long long *flag = nullptr;
+    // setup's
+    bool ready = false;
+    int smoother = SBLAS_AMG_JACOBI, nu = AMG_NU, coarse_sweeps = AMG_COARSE_SWEEPS;
+    double omega = 0.0, scale = 1.0;
+    int levels() const { return (int)lv.size(); }
+};
+
+void launch_sweep(hipStream_t s, const AmgLevel &L, int mode, const double *b, const double *x, double *y)
+{
+    if (mode == MODE_FIRST) amg_first_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, L.wd, b, y);
+    else if (mode == MODE_RESIDUAL)
+        amg_sweep_kernel<MODE_RESIDUAL><<<wide_grid(4 * L.units, AMG_THREADS), AMG_THREADS, 0, s>>>(L.units, L.d_units, L.colidx, L.val, L.wd, b, x, y);
+    else
+        amg_sweep_kernel<MODE_SWEEP><<<wide_grid(4 * L.units, AMG_THREADS), AMG_THREADS, 0, s>>>(L.units, L.d_units, L.colidx, L.val, L.wd, b, x, y);
+}
+
+// the walk of amg.h as launches; level 0 reads the caller's r and ends in the caller's z
+struct DeviceOps {
+    const AmgPlan *p;
+    hipStream_t s;
+    const double *r;
+    double *z;
+    const double *b(int l) const { return l ? p->lv[(size_t)l]->b : r; }
+    double *x(int l, int k) const { return l == 0 && k == AMG_RESULT_BUFFER ? z : p->lv[(size_t)l]->x[k]; }
+    void first(int l, int dst) { launch_sweep(s, *p->lv[(size_t)l], MODE_FIRST, b(l), nullptr, x(l, dst)); }
+    void sweep(int l, int src, int dst) { launch_sweep(s, *p->lv[(size_t)l], MODE_SWEEP, b(l), x(l, src), x(l, dst)); }
+    void residual(int l, int src) { launch_sweep(s, *p->lv[(size_t)l], MODE_RESIDUAL, b(l), x(l, src), p->lv[(size_t)l]->res); }
+    void restrict_to(int l)
+    {
+        const AmgLevel &L = *p->lv[(size_t)l];
+        amg_restrict_kernel<<<grid_of(L.n_coarse), AMG_THREADS, 0, s>>>(L.n_coarse, L.aggptr, L.members, L.res, p->lv[(size_t)l + 1]->b);
+    }
+    void prolong(int l, int dst)
+    {
+        const AmgLevel &L = *p->lv[(size_t)l];
+        amg_prolong_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, L.agg, p->scale, x(l + 1, AMG_RESULT_BUFFER), x(l, dst));
+    }
+};
+
+bool overlap(const double *a, const double *b, int64_t n) { return a < b + n && b < a + n; }
+
+// the plan's level `level` for a single-kernel entry, or null
+const AmgLevel *level_of(const void *plan, int level, bool need_setup)
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || level < 0 || level >= p->levels() || (need_setup && !p->ready) || p->dev != resolve_device(-1)) return nullptr;
+    return p->lv[(size_t)level].get();
+}
+
+} // namespace
+
+extern "C" {
+
+int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                              double theta, int64_t coarse_max, int max_levels, uint32_t seed, void **plan_out, int64_t *bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (!plan_out) return SBLAS_E_INVALID;
+    *plan_out = nullptr;
+    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
+    if (!amg_theta_ok(theta) || (theta > 0.0 && !val)) return SBLAS_E_INVALID;
+    if (coarse_max < 0 || max_levels < 0 || max_levels > AMG_LEVEL_CAP) return SBLAS_E_INVALID;
+    if ((n > 0 && !rowptr) || (nnz > 0 && !colidx)) return SBLAS_E_INVALID;
+    if (coarse_max == 0) coarse_max = AMG_COARSE_MAX;
+    if (max_levels == 0) max_levels = AMG_MAX_LEVELS;
+    std::unique_ptr<AmgPlan> p(new AmgPlan);
+    p->dev = resolve_device(dev), p->n = n, p->nnz = nnz, p->rowptr = rowptr, p->colidx = colidx, p->theta = theta, p->seed = seed;
+    if (n == 0) {
+        *plan_out = p.release();
+        return SBLAS_OK;
+    }
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> h_rowptr, h_colidx;
+    std::vector<double> h_val;
+    int rc = fetch_structure(s, n, nnz, rowptr, colidx, h_rowptr, h_colidx, bad_row);
+    if (rc != SBLAS_OK) return rc;
+    const bool by_value = theta > 0.0;
+    if (by_value) {
+        h_val.resize((size_t)nnz);
+        if (hipMemcpyAsync(h_val.data(), val, (size_t)nnz * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return SBLAS_E_HIP;
+    }
+    if (p->block.alloc(p->dev, 256) != hipSuccess) return SBLAS_E_HIP;
+    p->flag = p->block.at<unsigned long long>();
+    if (hipMemsetAsync(p->flag, 0xff, 256, s) != hipSuccess) return SBLAS_E_HIP;
+
+    const int32_t *d_rowptr = rowptr, *d_colidx = colidx;
+    int64_t nl = n, nnzl = nnz;
+    for (int l = 0;; ++l) {
+        std::unique_ptr<AmgLevel> L(new AmgLevel);
+        L->n = nl, L->nnz = nnzl, L->rowptr = d_rowptr, L->colidx = d_colidx;
+        std::vector<int32_t> dpos((size_t)nl), agg, aggptr, members;
+        int64_t bad = -1;
+        rc = sblas_ilu0_check(nl, h_rowptr.data(), h_colidx.data(), dpos.data(), &bad);
+        if (rc != SBLAS_OK) { // level 0: the caller's structure; below it cannot happen (the COO plan sorts, a diagonal is always present)
+            if (bad_row) *bad_row = bad;
+            return rc;
+        }
+        std::vector<int32_t> c_rowptr, c_colidx;
+        std::vector<double> c_val;
+        if (nl > coarse_max && l + 1 < max_levels) {
+            agg.resize((size_t)nl), members.resize((size_t)nl);
+            const int64_t nc = amg_aggregate(nl, h_rowptr.data(), h_colidx.data(), by_value ? h_val.data() : nullptr, theta, seed, (uint32_t)l,
+                                             agg.data(), aggptr, members.data());
+            if (nc < nl) { // a level that does not reduce n is discarded
+                std::vector<int32_t> trow((size_t)nnzl), tcol((size_t)nnzl);
+                for (int64_t i = 0; i < nl; ++i)
+                    for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) trow[(size_t)e] = agg[(size_t)i], tcol[(size_t)e] = agg[(size_t)h_colidx[e]];
+                DeviceBuffer trip;
+                size_t tb = 0;
+                Segment tseg[2] = {Segment(trow), Segment(tcol)};
+                if (upload_segments(trip, p->dev, s, tseg, 2, &tb) != hipSuccess) return SBLAS_E_HIP;
+                rc = sblas_hip_coo_plan_create(p->dev, s, nc, nc, nnzl, trip.at<int32_t>(), trip.at<int32_t>(tseg[1].offset), SBLAS_COO_SUM, &L->coo);
+                if (rc != SBLAS_OK) return rc;
+                int64_t ci[8];
+                const int32_t *c_rp = nullptr, *c_ci = nullptr, *c_perm = nullptr, *c_run = nullptr;
+                sblas_hip_coo_plan_info(L->coo, ci);
+                sblas_hip_coo_plan_csr(L->coo, &c_rp, &c_ci, &c_perm, &c_run);
+                const int64_t nnzc = ci[3];
+                int64_t cbad = -1;
+                rc = fetch_structure(s, nc, nnzc, c_rp, c_ci, c_rowptr, c_colidx, &cbad);
+                if (rc != SBLAS_OK) return SBLAS_E_HIP;
+                if (by_value) { // the coarse values of the strength test, in the assemble order
+                    std::vector<int32_t> perm((size_t)nnzl), run((size_t)nnzc + 1);
+                    if (hipMemcpyAsync(perm.data(), c_perm, (size_t)nnzl * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipMemcpyAsync(run.data(), c_run, ((size_t)nnzc + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipStreamSynchronize(s) != hipSuccess)
+                        return SBLAS_E_HIP;
+                    c_val.resize((size_t)nnzc);
+                    for (int64_t e = 0; e < nnzc; ++e) {
+                        double v = h_val[(size_t)perm[(size_t)run[(size_t)e]]];
+                        for (int64_t k = (int64_t)run[(size_t)e] + 1; k < run[(size_t)e + 1]; ++k) v = v + h_val[(size_t)perm[(size_t)k]];
+                        c_val[(size_t)e] = v;
+                    }
+                }
+                L->n_coarse = nc;
+                d_rowptr = c_rp, d_colidx = c_ci;
+            }
+        }
+        const bool last = L->n_coarse == 0;
+        if (last) agg.clear(), aggptr.clear(), members.clear();
+        // the rows packed as one wide level of a solve
+        std::vector<int32_t> zero_level((size_t)nl, 0);
+        LevelOrder o;
+        std::vector<Unit> units;
+        const auto unit_of = [&](int32_t i, int32_t q) { return Unit{i, h_rowptr[(size_t)i], h_rowptr[(size_t)i + 1], q}; };
+        level_pack(nl, h_rowptr.data(), zero_level.data(), 1, unit_of, NO_UNIT, o, units);
+        L->units = (int64_t)units.size();
+        Segment seg[5] = {Segment(units), Segment(dpos), Segment(agg), Segment(aggptr), Segment(members)};
+        size_t ib = 0;
+        if (upload_segments(L->ibuf, p->dev, s, seg, last ? 2 : 5, &ib) != hipSuccess) return SBLAS_E_HIP; // the coarsest has no aggregates
+        L->d_units = L->ibuf.at<Unit>(), L->dpos = L->ibuf.at<int32_t>(seg[1].offset);
+        if (!last) L->agg = L->ibuf.at<int32_t>(seg[2].offset), L->aggptr = L->ibuf.at<int32_t>(seg[3].offset), L->members = L->ibuf.at<int32_t>(seg[4].offset);
+        // doubles: wd | x0 | x1 (below level 0) | res (above the coarsest) | b, val (below level 0)
+        const size_t vec = ((size_t)nl * 8 + 255) / 256 * 256, vals = ((size_t)nnzl * 8 + 255) / 256 * 256;
+        const size_t db = vec * (2 + (l > 0 ? 2 : 0) + (last ? 0 : 1)) + (l > 0 ? vals : 0);
+        if (L->dbuf.alloc(p->dev, db) != hipSuccess) return SBLAS_E_HIP;
+        size_t off = 0;
+        const auto take = [&](size_t bytes) {
+            double *q = L->dbuf.at<double>(off);
+            off += bytes;
+            return q;
+        };
+        L->wd = take(vec), L->x[0] = take(vec);
+        if (l > 0) L->x[1] = take(vec), L->b = take(vec);
+        if (!last) L->res = take(vec);
+        if (l > 0) L->own_val = take(vals), L->val = L->own_val;
+        L->bytes = ib + db;
+        p->lv.push_back(std::move(L));
+        if (last) break;
+        nl = p->lv.back()->n_coarse, nnzl = (int64_t)c_colidx.size();
+        h_rowptr.swap(c_rowptr), h_colidx.swap(c_colidx), h_val.swap(c_val);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return SBLAS_E_HIP;
+    *plan_out = p.release();
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_info(const void *plan, int64_t out[12])
+{
+    if (!plan || !out) return SBLAS_E_INVALID;
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    int64_t rows = 0, entries = 0, bytes = p->flag ? 256 : 0;
+    for (const auto &L : p->lv) rows += L->n, entries += L->nnz, bytes += (int64_t)L->bytes;
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->levels(), out[3] = p->nu, out[4] = p->coarse_sweeps;
+    out[5] = sblas_amg_launches(p->levels(), p->nu, p->coarse_sweeps);
+    out[6] = rows, out[7] = entries, out[8] = bytes, out[9] = p->smoother, out[10] = p->ready, out[11] = p->lv.empty() ? 0 : p->lv.back()->n;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_level(const void *plan, int level, int64_t sizes[4], const void *ptrs[7])
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !sizes || !ptrs || level < 0 || level >= p->levels()) return SBLAS_E_INVALID;
+    const AmgLevel &L = *p->lv[(size_t)level];
+    sizes[0] = L.n, sizes[1] = L.nnz, sizes[2] = L.n_coarse, sizes[3] = L.units;
+    ptrs[0] = L.rowptr, ptrs[1] = L.colidx, ptrs[2] = L.val, ptrs[3] = L.wd, ptrs[4] = L.agg, ptrs[5] = L.aggptr, ptrs[6] = L.members;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_speaks_for(const void *plan, int dev, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx)
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || p->dev != resolve_device(dev)) return SBLAS_E_INVALID;
+    return n == p->n && nnz == p->nnz && rowptr == p->rowptr && colidx == p->colidx ? SBLAS_OK : SBLAS_E_INVALID;
+}
+
+int sblas_hip_amg_plan_destroy(void *plan)
+{
+    delete static_cast<AmgPlan *>(plan);
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_setup(void *plan, void *stream, const double *val, int smoother, double omega, int nu, int coarse_sweeps,
+                             double coarse_scale)
+{
+    AmgPlan *p = static_cast<AmgPlan *>(plan);
+    if (!p) return SBLAS_E_INVALID;
+    if (smoother != SBLAS_AMG_JACOBI && smoother != SBLAS_AMG_L1) return SBLAS_E_INVALID;
+    if (!(omega >= 0.0) || !isfinite(omega) || !isfinite(coarse_scale)) return SBLAS_E_INVALID;
+    if (!amg_cycle_args_ok(p->levels(), nu, coarse_sweeps)) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (p->n > 0 && !val) return SBLAS_E_INVALID;
+    if (omega == 0.0) omega = smoother == SBLAS_AMG_L1 ? 1.0 : 2.0 / 3.0;
+    p->ready = false;
+    p->smoother = smoother, p->omega = omega, p->nu = nu, p->coarse_sweeps = coarse_sweeps, p->scale = coarse_scale;
+    if (p->n == 0) {
+        p->ready = true;
+        return SBLAS_OK;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(p->flag, 0xff, 8, s) != hipSuccess) return SBLAS_E_HIP;
+    p->lv[0]->val = val;
+    for (int l = 0; l < p->levels(); ++l) {
+        AmgLevel &L = *p->lv[(size_t)l];
+        amg_wd_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, l, smoother, omega, L.rowptr, L.dpos, L.val, L.wd, p->flag);
+        if (l + 1 < p->levels()) {
+            const int rc = sblas_hip_coo_plan_assemble(L.coo, s, L.val, p->lv[(size_t)l + 1]->own_val);
+            if (rc != SBLAS_OK) return rc;
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return SBLAS_E_HIP;
+    p->ready = true;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_apply(const void *plan, void *stream, const double *r, double *z)
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !p->ready) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (p->n == 0) return SBLAS_OK;
+    if (!r || !z || overlap(r, z, p->n)) return SBLAS_E_INVALID;
+    DeviceOps ops{p, (hipStream_t)stream, r, z};
+    amg_cycle(p->levels(), p->nu, p->coarse_sweeps, ops);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_plan_check(const void *plan, void *stream, int64_t out[2])
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !out) return SBLAS_E_INVALID;
+    out[0] = out[1] = -1;
+    if (p->n == 0) return SBLAS_OK;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    unsigned long long w = FLAG_CLEAN;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(&w, p->flag, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SBLAS_E_HIP;
+    if (w != FLAG_CLEAN) out[0] = (int64_t)(w >> 32), out[1] = (int64_t)(w & 0xffffffffull);
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_sweep_f64(const void *plan, void *stream, int level, int mode, const double *b, const double *x, double *y)
+{
+    const AmgLevel *L = level_of(plan, level, true);
+    if (!L || mode < MODE_SWEEP || mode > MODE_FIRST) return SBLAS_E_INVALID;
+    if (L->n == 0) return SBLAS_OK;
+    if (!b || !y || overlap(b, y, L->n) || (mode != MODE_FIRST && (!x || overlap(x, y, L->n)))) return SBLAS_E_INVALID;
+    launch_sweep((hipStream_t)stream, *L, mode, b, x, y);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_restrict_f64(const void *plan, void *stream, int level, const double *res, double *bc)
+{
+    const AmgLevel *L = level_of(plan, level, false);
+    if (!L || L->n_coarse == 0 || !res || !bc) return SBLAS_E_INVALID;
+    amg_restrict_kernel<<<grid_of(L->n_coarse), AMG_THREADS, 0, (hipStream_t)stream>>>(L->n_coarse, L->aggptr, L->members, res, bc);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_prolong_f64(const void *plan, void *stream, int level, double scale, const double *e, double *x)
+{
+    const AmgLevel *L = level_of(plan, level, false);
+    if (!L || L->n_coarse == 0 || !e || !x) return SBLAS_E_INVALID;
+    amg_prolong_kernel<<<grid_of(L->n), AMG_THREADS, 0, (hipStream_t)stream>>>(L->n, L->agg, scale, e, x);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+} // extern "C"

@@ -1,0 +1,239 @@
+// amg_rule.cpp -- the host rule of the aggregation AMG plan (amg.hip): the pinned aggregation of one
+// level, the smoother's diagonal, the launch count and the whole V-cycle restated in plain C++.  Pure functions of host
+// arrays; no GPU call in this file, so it is testable on a CPU box (and under a host sanitizer).
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <algorithm>
+#include <vector>
+#include "../../include/sblas_hip.h"
+#include "amg.h"
+#include "color.h"
+
+#pragma clang fp contract(off) // every product and sum below is rounded on its own; the row sums call fma() by name
+
+namespace sblas {
+
+int64_t amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
+                      uint32_t level, int32_t *agg, std::vector<int32_t> &aggptr, int32_t *members)
+{
+    const bool by_value = val != nullptr && theta > 0.0;
+    // strong(i, e): entry e of row i is a strong off-diagonal one.  Only row i's own entries are consulted.
+    std::vector<double> bound; // theta * max_{k != i} |a_ik|, the product rounded
+    if (by_value) {
+        bound.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            double m = 0.0;
+            for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+                const double a = fabs(val[e]);
+                if (colidx[e] != i && a > m) m = a;
+            }
+            bound[(size_t)i] = theta * m;
+        }
+    }
+    const auto strong = [&](int64_t i, int64_t e) { return colidx[e] != i && (!by_value || fabs(val[e]) >= bound[(size_t)i]); };
+
+    // roots: the greedy maximal independent set in descending priority (no two vertices tie)
+    const uint32_t salt = color_salt(seed + level);
+    std::vector<int32_t> order((size_t)n);
+    for (int64_t v = 0; v < n; ++v) order[(size_t)v] = (int32_t)v;
+    std::sort(order.begin(), order.end(),
+              [&](int32_t a, int32_t b) { return color_priority((uint32_t)a, salt) > color_priority((uint32_t)b, salt); });
+    std::vector<char> root((size_t)n, 0);
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t v = order[(size_t)k];
+        bool free_of_roots = true;
+        for (int64_t e = rowptr[v]; e < rowptr[v + 1] && free_of_roots; ++e)
+            if (strong(v, e) && root[(size_t)colidx[e]]) free_of_roots = false;
+        root[(size_t)v] = free_of_roots;
+    }
+    // aggregates: roots numbered in ascending vertex index; every other vertex joins the first root among its strong
+    // neighbours in stored order (it has one: otherwise it would be a root)
+    int64_t n_agg = 0;
+    for (int64_t v = 0; v < n; ++v) agg[v] = root[(size_t)v] ? (int32_t)n_agg++ : -1;
+    for (int64_t v = 0; v < n; ++v) {
+        if (root[(size_t)v]) continue;
+        for (int64_t e = rowptr[v]; e < rowptr[v + 1]; ++e)
+            if (strong(v, e) && root[(size_t)colidx[e]]) {
+                agg[v] = agg[colidx[e]];
+                break;
+            }
+    }
+    // members: the vertices by (aggregate, vertex), a counting sort stable in the vertex
+    aggptr.assign((size_t)n_agg + 1, 0);
+    for (int64_t v = 0; v < n; ++v) ++aggptr[(size_t)agg[v] + 1];
+    for (int64_t a = 0; a < n_agg; ++a) aggptr[(size_t)a + 1] += aggptr[(size_t)a];
+    std::vector<int32_t> fill(aggptr.begin(), aggptr.end() - 1);
+    for (int64_t v = 0; v < n; ++v) members[fill[(size_t)agg[v]]++] = (int32_t)v;
+    return n_agg;
+}
+
+} // namespace sblas
+
+namespace {
+
+using namespace sblas;
+
+// the row sum in the solves' pinned order: G(p) lanes, lane l the entries l, l + G, ... with one fused multiply-add each
+// from +0, then the butterfly l ^ 1, l ^ 2, ... as written; lane 0 holds the result
+double row_sum(const int32_t *colidx, const double *val, int64_t beg, int64_t end, const double *x)
+{
+    const int G = 1 << sptrsv_group_shift(end - beg);
+    double v[64], w[64];
+    for (int l = 0; l < G; ++l) {
+        double s = 0.0;
+        for (int64_t e = beg + l; e < end; e += G) s = fma(val[e], x[colidx[e]], s);
+        v[l] = s;
+    }
+    for (int m = 1; m < G; m <<= 1) {
+        for (int l = 0; l < G; ++l) w[l] = v[l] + v[l ^ m];
+        for (int l = 0; l < G; ++l) v[l] = w[l];
+    }
+    return v[0];
+}
+
+struct RefLevel {
+    int64_t n;
+    const int32_t *rowptr, *colidx, *agg, *aggptr, *members;
+    const double *val, *wd;
+    std::vector<double> own_b, own_x[2], res;
+    const double *b;
+    double *x[2];
+};
+
+struct RefOps {
+    std::vector<RefLevel> &lv;
+    double scale;
+    void first(int l, int dst)
+    {
+        RefLevel &L = lv[(size_t)l];
+        for (int64_t i = 0; i < L.n; ++i) L.x[dst][i] = L.wd[i] * L.b[i];
+    }
+    void sweep(int l, int src, int dst)
+    {
+        RefLevel &L = lv[(size_t)l];
+        for (int64_t i = 0; i < L.n; ++i) {
+            const double s = row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
+            const double d = L.b[i] - s, t = L.wd[i] * d;
+            L.x[dst][i] = L.x[src][i] + t;
+        }
+    }
+    void residual(int l, int src)
+    {
+        RefLevel &L = lv[(size_t)l];
+        for (int64_t i = 0; i < L.n; ++i) L.res[(size_t)i] = L.b[i] - row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
+    }
+    void restrict_to(int l)
+    {
+        RefLevel &L = lv[(size_t)l], &Cs = lv[(size_t)l + 1];
+        for (int64_t a = 0; a < Cs.n; ++a) {
+            double s = 0.0;
+            for (int64_t k = L.aggptr[a]; k < L.aggptr[a + 1]; ++k) s = s + L.res[(size_t)L.members[k]];
+            Cs.own_b[(size_t)a] = s;
+        }
+    }
+    void prolong(int l, int dst)
+    {
+        RefLevel &L = lv[(size_t)l], &Cs = lv[(size_t)l + 1];
+        const double *e = Cs.x[AMG_RESULT_BUFFER];
+        for (int64_t i = 0; i < L.n; ++i) {
+            const double t = scale * e[L.agg[i]];
+            L.x[dst][i] = L.x[dst][i] + t;
+        }
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+int sblas_amg_limits(int64_t out[8])
+{
+    if (!out) return SBLAS_E_INVALID;
+    out[0] = AMG_G4_MAX, out[1] = AMG_G16_MAX, out[2] = AMG_THREADS, out[3] = AMG_COARSE_MAX, out[4] = AMG_MAX_LEVELS;
+    out[5] = AMG_NU, out[6] = AMG_COARSE_SWEEPS, out[7] = AMG_LEVEL_CAP;
+    return SBLAS_OK;
+}
+
+int sblas_amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
+                        uint32_t level, int32_t *agg, int32_t *aggptr, int32_t *members, int64_t *n_agg, int64_t *bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (n_agg) *n_agg = 0;
+    if (n < 0 || n > INT_MAX || !rowptr || !aggptr || !n_agg) return SBLAS_E_INVALID;
+    if (!amg_theta_ok(theta) || (theta > 0.0 && !val)) return SBLAS_E_INVALID;
+    if (n > 0 && (!agg || !members)) return SBLAS_E_INVALID;
+    const int rc = sblas_ilu0_check(n, rowptr, colidx, nullptr, bad_row);
+    if (rc != SBLAS_OK) return rc;
+    std::vector<int32_t> ptr;
+    *n_agg = amg_aggregate(n, rowptr, colidx, val, theta, seed, level, agg, ptr, members);
+    for (size_t a = 0; a < ptr.size(); ++a) aggptr[a] = ptr[a];
+    return SBLAS_OK;
+}
+
+int64_t sblas_amg_launches(int levels, int nu, int coarse_sweeps)
+{
+    if (!amg_cycle_args_ok(levels, nu, coarse_sweeps)) return -1;
+    AmgCount c;
+    amg_cycle(levels, nu, coarse_sweeps, c);
+    return c.n;
+}
+
+int sblas_amg_wd_ref(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, int smoother, double omega, double *wd,
+                     int64_t *bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (n < 0 || n > INT_MAX || !rowptr || (smoother != SBLAS_AMG_JACOBI && smoother != SBLAS_AMG_L1)) return SBLAS_E_INVALID;
+    if (n > 0 && (!colidx || !val || !wd)) return SBLAS_E_INVALID;
+    for (int64_t i = 0; i < n; ++i) {
+        double d = 0.0, l1 = 0.0;
+        bool found = false;
+        for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            if (colidx[e] == i) d = val[e], found = true;
+            l1 = l1 + fabs(val[e]);
+        }
+        if (!found) {
+            if (bad_row) *bad_row = i;
+            return SBLAS_E_INVALID;
+        }
+        wd[i] = omega / (smoother == SBLAS_AMG_L1 ? l1 : d);
+        if (!(isfinite(d) && d > 0.0) && bad_row && *bad_row < 0) *bad_row = i; // reported, not refused: as the device flags it
+    }
+    return SBLAS_OK;
+}
+
+int sblas_amg_cycle_ref(int levels, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
+                        const double *const *wd, const int32_t *const *agg, const int32_t *const *aggptr, const int32_t *const *members,
+                        int nu, int coarse_sweeps, double coarse_scale, const double *r, double *z)
+{
+    if (!amg_cycle_args_ok(levels, nu, coarse_sweeps)) return SBLAS_E_INVALID;
+    if (levels == 0) return SBLAS_OK;
+    if (!n || !rowptr || !colidx || !val || !wd) return SBLAS_E_INVALID;
+    if (levels > 1 && (!agg || !aggptr || !members)) return SBLAS_E_INVALID;
+    for (int l = 0; l < levels; ++l) {
+        if (n[l] < 0 || n[l] > INT_MAX || !rowptr[l]) return SBLAS_E_INVALID;
+        if (n[l] > 0 && (!wd[l] || (rowptr[l][n[l]] > 0 && (!colidx[l] || !val[l])))) return SBLAS_E_INVALID;
+        if (l + 1 < levels && n[l] > 0 && (!agg[l] || !aggptr[l] || !members[l])) return SBLAS_E_INVALID;
+    }
+    if (n[0] > 0 && (!r || !z || r == z)) return SBLAS_E_INVALID;
+    std::vector<RefLevel> lv((size_t)levels);
+    for (int l = 0; l < levels; ++l) {
+        RefLevel &L = lv[(size_t)l];
+        const bool last = l + 1 == levels;
+        L.n = n[l], L.rowptr = rowptr[l], L.colidx = colidx[l], L.val = val[l], L.wd = wd[l];
+        L.agg = last ? nullptr : agg[l], L.aggptr = last ? nullptr : aggptr[l], L.members = last ? nullptr : members[l];
+        L.own_x[0].assign((size_t)L.n, 0.0), L.res.assign(last ? 0 : (size_t)L.n, 0.0);
+        L.x[0] = L.own_x[0].data();
+        if (l == 0) {
+            L.b = r, L.x[1] = z;
+        } else {
+            L.own_b.assign((size_t)L.n, 0.0), L.own_x[1].assign((size_t)L.n, 0.0);
+            L.b = L.own_b.data(), L.x[1] = L.own_x[1].data();
+        }
+    }
+    RefOps ops{lv, coarse_scale};
+    amg_cycle(levels, nu, coarse_sweeps, ops);
+    return SBLAS_OK;
+}
+
+} // extern "C"

@@ -304,9 +304,11 @@ int spmv(const KrylovPlan *p, hipStream_t s, const double *x, double *y)
     return sblas_hip_spmv_csr_f64_i32(-1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
 }
 
-// out = U^-1 (L^-1 in) with the factor the caller gave start()
+// out = U^-1 (L^-1 in) with the factor the caller gave start(); with AMG, one cycle of the plan in `lower` with the
+// values of its own setup (in and out are distinct work vectors, tmp stays unused)
 int ilu_apply(const KrylovPlan *p, hipStream_t s, const double *in, double *tmp, double *out)
 {
+    if (p->precond == SBLAS_PRECOND_AMG) return sblas_hip_amg_plan_apply(p->lower, s, in, out);
     const int rc = sblas_hip_sptrsv_f64_i32_planned(p->lower, s, p->rowptr, p->colidx, p->pre, 1.0, in, tmp);
     if (rc != SBLAS_OK) return rc;
     return sblas_hip_sptrsv_f64_i32_planned(p->upper, s, p->rowptr, p->colidx, p->pre, 1.0, tmp, out);
@@ -329,7 +331,7 @@ void dot(const KrylovPlan *p, hipStream_t s, const double *x0, const double *y0,
 
 int pcg_iteration(const KrylovPlan *p, hipStream_t s)
 {
-    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = p->precond == SBLAS_PRECOND_ILU0;
+    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG;
     double *r = p->w(V_R), *pp = p->w(V_P), *q = p->w(V_Q), *z = p->precond == SBLAS_PRECOND_NONE ? r : p->w(V_Z);
     int rc = spmv(p, s, pp, q);
     if (rc != SBLAS_OK) return rc;
@@ -348,7 +350,8 @@ int pcg_iteration(const KrylovPlan *p, hipStream_t s)
 
 int bicgstab_iteration(const KrylovPlan *p, hipStream_t s)
 {
-    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = p->precond == SBLAS_PRECOND_ILU0, none = p->precond == SBLAS_PRECOND_NONE;
+    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, none = p->precond == SBLAS_PRECOND_NONE;
+    const bool ilu = p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG;
     double *r = p->w(B_R), *rh = p->w(B_RHAT), *pp = p->w(B_P), *v = p->w(B_V), *sv = p->w(B_S), *t = p->w(B_T);
     double *ph = none ? pp : p->w(B_PH), *sh = none ? sv : p->w(B_SH), *dinv = const_cast<double *>(p->pre);
     int rc;
@@ -423,12 +426,16 @@ int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, i
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0) return SBLAS_E_INVALID;
+    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG)
+        return SBLAS_E_INVALID;
     if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
     if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
     const int device = resolve_device(dev);
     if (spmv_plan && sblas_hip_spmv_plan_speaks_for(spmv_plan, device, n, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    if (precond == SBLAS_PRECOND_ILU0) {
+    if (precond == SBLAS_PRECOND_AMG) { // the AMG handle travels in lower_plan's place
+        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
+        if (sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    } else if (precond == SBLAS_PRECOND_ILU0) {
         if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
         const void *plans[2] = {lower_plan, upper_plan};
         const int fill[2] = {SBLAS_FILL_LOWER, SBLAS_FILL_UPPER}, diag[2] = {SBLAS_DIAG_UNIT, SBLAS_DIAG_NON_UNIT};
@@ -444,7 +451,7 @@ int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, i
     std::unique_ptr<KrylovPlan> p(new KrylovPlan);
     p->dev = device, p->method = method, p->precond = precond, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
     p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan, p->lower = lower_plan, p->upper = upper_plan;
-    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + (precond == SBLAS_PRECOND_ILU0);
+    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + (precond == SBLAS_PRECOND_ILU0 || precond == SBLAS_PRECOND_AMG);
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -469,6 +476,8 @@ int sblas_hip_krylov_plan_info(const void *plan, int64_t out[10])
     if (p->precond == SBLAS_PRECOND_ILU0) {
         sblas_hip_sptrsv_plan_info(p->lower, lower);
         sblas_hip_sptrsv_plan_info(p->upper, upper);
+    } else if (p->precond == SBLAS_PRECOND_AMG) {
+        sblas_hip_amg_plan_info(p->lower, lower);
     }
     out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
     out[6] = (int64_t)p->partial_bytes, out[7] = KRYLOV_BLOCK_SLOTS * 8, out[8] = (int64_t)p->bytes;
@@ -494,8 +503,9 @@ int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const do
         p->started = true;
         return SBLAS_OK;
     }
-    if (!b || !x || (p->nnz > 0 && !val) || (p->precond != SBLAS_PRECOND_NONE && !lu_or_dinv)) return SBLAS_E_INVALID;
-    p->val = val, p->pre = p->precond == SBLAS_PRECOND_NONE ? nullptr : lu_or_dinv, p->x = x;
+    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG holds its own values
+    if (!b || !x || (p->nnz > 0 && !val) || (takes_pre && !lu_or_dinv)) return SBLAS_E_INVALID;
+    p->val = val, p->pre = takes_pre ? lu_or_dinv : nullptr, p->x = x;
     hipStream_t s = (hipStream_t)stream;
     const bool pcg = p->method == SBLAS_KRYLOV_PCG, jac = p->precond == SBLAS_PRECOND_JACOBI;
     int rc;
@@ -507,7 +517,7 @@ int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const do
         if ((rc = spmv(p, s, x, q)) != SBLAS_OK) return rc;
         launch_update(s, UP_START_PCG, jac, up_args(p, {r, bb, q, dinv, z, x}));
         launch_fold(s, FOLD_START_R, jac ? 2 : 1, 0, p->cells, p->part, p->blk);
-        if (p->precond == SBLAS_PRECOND_ILU0) {
+        if (p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG) {
             if ((rc = ilu_apply(p, s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
             dot(p, s, r, z);
             launch_fold(s, FOLD_RHO0, 1, 0, p->cells, p->part, p->blk);

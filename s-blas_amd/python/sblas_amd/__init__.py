@@ -63,6 +63,10 @@ EXPORTS = [
     "sblas_hip_gmres_dots_f64", "sblas_hip_gmres_project_f64", "sblas_hip_gmres_combine_f64", "sblas_hip_gmres_plan_create",
     "sblas_hip_gmres_plan_info", "sblas_hip_gmres_plan_destroy", "sblas_hip_gmres_start", "sblas_hip_gmres_iterate",
     "sblas_hip_gmres_status",
+    "sblas_amg_limits", "sblas_amg_aggregate", "sblas_amg_launches", "sblas_amg_wd_ref", "sblas_amg_cycle_ref",
+    "sblas_hip_amg_plan_create", "sblas_hip_amg_plan_info", "sblas_hip_amg_plan_level", "sblas_hip_amg_plan_setup",
+    "sblas_hip_amg_plan_apply", "sblas_hip_amg_plan_check", "sblas_hip_amg_plan_speaks_for", "sblas_hip_amg_plan_destroy",
+    "sblas_hip_amg_sweep_f64", "sblas_hip_amg_restrict_f64", "sblas_hip_amg_prolong_f64",
 ]
 
 
@@ -372,6 +376,38 @@ def lib():
     L.sblas_hip_gmres_iterate.argtypes = [vp, vp, i64]
     L.sblas_hip_gmres_status.restype = C.c_int
     L.sblas_hip_gmres_status.argtypes = [vp, vp, C.POINTER(f64)]
+    L.sblas_amg_limits.restype = C.c_int
+    L.sblas_amg_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_amg_aggregate.restype = C.c_int
+    L.sblas_amg_aggregate.argtypes = [i64, vp, vp, vp, f64, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_amg_launches.restype = i64
+    L.sblas_amg_launches.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.sblas_amg_wd_ref.restype = C.c_int
+    L.sblas_amg_wd_ref.argtypes = [i64, vp, vp, vp, C.c_int, f64, vp, C.POINTER(i64)]
+    L.sblas_amg_cycle_ref.restype = C.c_int
+    L.sblas_amg_cycle_ref.argtypes = [C.c_int, C.POINTER(i64)] + [C.POINTER(vp)] * 7 + [C.c_int, C.c_int, f64, vp, vp]
+    L.sblas_hip_amg_plan_create.restype = C.c_int
+    L.sblas_hip_amg_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, i64, C.c_int, C.c_uint32, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_amg_plan_info.restype = C.c_int
+    L.sblas_hip_amg_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_amg_plan_level.restype = C.c_int
+    L.sblas_hip_amg_plan_level.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(vp)]
+    L.sblas_hip_amg_plan_setup.restype = C.c_int
+    L.sblas_hip_amg_plan_setup.argtypes = [vp, vp, vp, C.c_int, f64, C.c_int, C.c_int, f64]
+    L.sblas_hip_amg_plan_apply.restype = C.c_int
+    L.sblas_hip_amg_plan_apply.argtypes = [vp, vp, vp, vp]
+    L.sblas_hip_amg_plan_check.restype = C.c_int
+    L.sblas_hip_amg_plan_check.argtypes = [vp, vp, C.POINTER(i64)]
+    L.sblas_hip_amg_plan_speaks_for.restype = C.c_int
+    L.sblas_hip_amg_plan_speaks_for.argtypes = [vp, C.c_int, i64, i64, vp, vp]
+    L.sblas_hip_amg_plan_destroy.restype = C.c_int
+    L.sblas_hip_amg_plan_destroy.argtypes = [vp]
+    L.sblas_hip_amg_sweep_f64.restype = C.c_int
+    L.sblas_hip_amg_sweep_f64.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.sblas_hip_amg_restrict_f64.restype = C.c_int
+    L.sblas_hip_amg_restrict_f64.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.sblas_hip_amg_prolong_f64.restype = C.c_int
+    L.sblas_hip_amg_prolong_f64.argtypes = [vp, vp, C.c_int, f64, vp, vp]
     _lib = L
     return L
 
@@ -674,7 +710,7 @@ def color_ref(n, rowptr, colidx, seed=0):
 
 # Krylov solvers: methods, preconditioners, status words and the denominators a breakdown names (SBLAS_KRYLOV_*, SBLAS_PRECOND_*)
 KRYLOV_PCG, KRYLOV_BICGSTAB = 0, 1
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_ILU0 = 0, 1, 2
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_ILU0, PRECOND_AMG = 0, 1, 2, 3
 KRYLOV_RUNNING, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN, KRYLOV_LIMIT = 0, 1, 2, 3
 KRYLOV_STATUS = {KRYLOV_RUNNING: "running", KRYLOV_CONVERGED: "converged", KRYLOV_BREAKDOWN: "breakdown", KRYLOV_LIMIT: "limit"}
 KRYLOV_DENOM = {0: None, 1: "(p, q)", 2: "rho", 3: "(r^, v)", 4: "(t, t)", 5: "omega"}
@@ -702,10 +738,11 @@ def krylov_dot_ref(x, y):
 
 def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches=0):
     """Launches of one iteration (sblas_krylov_launches).  precond: None, "jacobi" or "ilu0"; lower_launches /
-    upper_launches: SptrsvPlan.info()["launches"] of the two solves, read with "ilu0" only."""
+    upper_launches: SptrsvPlan.info()["launches"] of the two solves, read with "ilu0" only; with "amg" lower_launches is
+    AmgPlan.info()["launches"], one cycle's."""
     if method not in _KRYLOV_METHOD:
         raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
-    code = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0}.get(precond, -1)
+    code = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG}.get(precond, -1)
     lo, up = (C.c_int64 * 12)(), (C.c_int64 * 12)()
     lo[5], up[5] = int(lower_launches), int(upper_launches)
     n = int(lib().sblas_krylov_launches(_KRYLOV_METHOD[method], code, lo, up))
@@ -717,7 +754,7 @@ def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches
 # Restarted GMRES: the denominators a breakdown names continue the Krylov solvers' (SBLAS_GMRES_DENOM_*)
 GMRES_DENOM = dict(KRYLOV_DENOM)
 GMRES_DENOM.update({6: "givens", 7: "beta"})
-_PRECOND_CODE = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0}
+_PRECOND_CODE = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG}
 
 
 def gmres_limits():
@@ -776,6 +813,97 @@ def gmres_launches(restart=30, precond=None, lower_launches=0, upper_launches=0)
     if cycle < 0:
         raise SblasError("sblas_gmres_launches refused its arguments")
     return dict(step=int(out[0]), close=int(out[1]), restart=int(out[2]), start=int(out[3]), cycle=cycle)
+
+
+# Aggregation AMG: smoothers and sweep modes (SBLAS_AMG_*)
+AMG_SMOOTHERS = {"jacobi": 0, "l1": 1}
+AMG_SWEEP_MODES = {"sweep": 0, "residual": 1, "first": 2}
+
+
+def amg_limits():
+    """The AMG plan's limits (sblas_amg_limits): dict(g4_max, g16_max, threads, coarse_max, max_levels, nu, coarse_sweeps,
+    level_cap) -- the longest stored rows that 4 and 16 lanes sum, a workgroup's threads, the defaults, and the largest
+    max_levels."""
+    out = (C.c_int64 * 8)()
+    check(lib().sblas_amg_limits(out), "sblas_amg_limits")
+    keys = ("g4_max", "g16_max", "threads", "coarse_max", "max_levels", "nu", "coarse_sweeps", "level_cap")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def amg_aggregate(n, rowptr, colidx, val=None, theta=0.0, seed=0, level=0):
+    """One level's pinned aggregation on host arrays (sblas_amg_aggregate) -> (agg, aggptr, members): every vertex's
+    aggregate, and the vertices by (aggregate, vertex) with aggptr of n_agg + 1 entries.  Roots are the greedy maximal
+    independent set over the strong neighbours in descending fmix32(v + 0x9E3779B9 * (seed + level + 1)).  A refused
+    structure raises an SblasError whose .bad_row is the first bad row."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    if len(rowptr) != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (len(rowptr), n))
+    if val is not None:
+        val = np.ascontiguousarray(val, np.float64)
+        if len(val) != len(colidx):
+            raise SblasError("val has %d entries, colidx %d" % (len(val), len(colidx)))
+    agg, aggptr, members = np.zeros(max(n, 1), np.int32), np.zeros(n + 1, np.int32), np.zeros(max(n, 1), np.int32)
+    n_agg, bad = C.c_int64(), C.c_int64(-1)
+    rc = lib().sblas_amg_aggregate(n, rowptr.ctypes.data, colidx.ctypes.data if len(colidx) else None,
+                                   val.ctypes.data if val is not None else None, float(theta), int(seed) & 0xffffffff,
+                                   int(level) & 0xffffffff, agg.ctypes.data, aggptr.ctypes.data, members.ctypes.data, C.byref(n_agg),
+                                   C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_amg_aggregate", rc, bad.value)
+    return agg[:n], aggptr[:n_agg.value + 1].copy(), members[:n]
+
+
+def amg_launches(levels, nu=1, coarse_sweeps=8):
+    """Launches of one AmgPlan.apply (sblas_amg_launches): (2 nu + 3) a level above the coarsest, coarse_sweeps on it."""
+    k = int(lib().sblas_amg_launches(int(levels), int(nu), int(coarse_sweeps)))
+    if k < 0:
+        raise SblasError("sblas_amg_launches refused its arguments")
+    return k
+
+
+def amg_wd_ref(n, rowptr, colidx, val, smoother="jacobi", omega=None):
+    """setup's wd on host arrays (sblas_amg_wd_ref) -> (wd, bad_row): omega / a_ii, or omega / sum |a_ie| for "l1";
+    bad_row is the first row whose diagonal is not finite and > 0, or -1."""
+    if smoother not in AMG_SMOOTHERS:
+        raise SblasError("smoother must be 'jacobi' or 'l1', not %r" % (smoother,))
+    if omega is None:
+        omega = 1.0 if smoother == "l1" else 2.0 / 3.0
+    rowptr, colidx = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colidx, np.int32)
+    val = np.ascontiguousarray(val, np.float64)
+    wd, bad = np.zeros(max(n, 1)), C.c_int64(-1)
+    rc = lib().sblas_amg_wd_ref(n, rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, AMG_SMOOTHERS[smoother], float(omega),
+                                wd.ctypes.data, C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_amg_wd_ref", rc, bad.value)
+    return wd[:n], int(bad.value)
+
+
+def amg_cycle_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
+    """The whole V-cycle in plain C++ on host arrays (sblas_amg_cycle_ref) -> z.  levels: a list of dicts with n, rowptr,
+    colidx, val, wd and, on all but the last, agg, aggptr, members (numpy arrays)."""
+    k = len(levels)
+    if k == 0:
+        return np.zeros(0)
+    keep = []
+
+    def column(name, dtype, upto):
+        arr = (C.c_void_p * k)()
+        for l in range(upto):
+            a = np.ascontiguousarray(levels[l][name], dtype)
+            keep.append(a)
+            arr[l] = a.ctypes.data if a.size else None
+        return arr
+    ns = (C.c_int64 * k)(*[int(L["n"]) for L in levels])
+    r = np.ascontiguousarray(r, np.float64)
+    if len(r) != ns[0]:
+        raise SblasError("r has %d entries for %d rows" % (len(r), ns[0]))
+    z = np.zeros(max(len(r), 1))
+    check(lib().sblas_amg_cycle_ref(k, ns, column("rowptr", np.int32, k), column("colidx", np.int32, k), column("val", np.float64, k),
+                                    column("wd", np.float64, k), column("agg", np.int32, k - 1), column("aggptr", np.int32, k - 1),
+                                    column("members", np.int32, k - 1), int(nu), int(coarse_sweeps), float(coarse_scale),
+                                    r.ctypes.data if len(r) else None, z.ctypes.data), "sblas_amg_cycle_ref")
+    return z[:len(r)]
 
 
 def partition_dense(first_order, n_gpu, i_gpu):
@@ -2150,9 +2278,6 @@ def csr_color(A, seed=0, stream=None):
     return color, perm, color_ptr
 
 
-# ------------------------------------------------------------------------------------------
-# Krylov solvers on a plan, resident on the device: PCG and BiCGStab (sblas_hip_krylov_*)
-# ------------------------------------------------------------------------------------------
 def _krylov_vector(name, t, n, device=None):
     import torch
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -2165,6 +2290,175 @@ def _krylov_vector(name, t, n, device=None):
         raise SblasError("%s is on %s, the plan on %s" % (name, t.device, device))
 
 
+# ------------------------------------------------------------------------------------------
+# Aggregation AMG: a V-cycle preconditioner on a device plan (sblas_hip_amg_plan_*)
+# ------------------------------------------------------------------------------------------
+class AmgPlan:
+    """Plain aggregation AMG of the square n x n CSR matrix (rowptr, colidx), int32 indices (sblas_hip_amg_plan_create):
+    apply() is z = M^-1 r by one V(nu, nu) cycle from a zero guess.  Every row must be strictly ascending in column and
+    store its diagonal; a bad structure raises an SblasError that names the first bad row (.bad_row).  theta > 0 keeps
+    only the strong entries |a_ij| >= theta * max_k |a_ik| in the aggregation and needs val; the hierarchy is then fixed.
+    The plan keeps rowptr and colidx alive and sweeps level 0 on them: do not change them.  setup(val) forms every
+    level's values and the smoother on the device and is repeatable; setup and apply allocate nothing inside the library,
+    never synchronise and are graph-capturable; check() is the one call that synchronises.  Every bit is pinned
+    (include/sblas_hip.h; amg_cycle_ref restates a cycle on the host).  KrylovPlan and GmresPlan take the plan as precond."""
+
+    def __init__(self, n, rowptr, colidx, val=None, theta=0.0, coarse_max=64, max_levels=20, seed=0, stream=None):
+        import torch
+        self.n, self.handle, self._val = n, None, None
+        self.nnz = _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        theta = float(theta)
+        if not 0.0 <= theta <= 1.0:
+            raise SblasError("theta must be in [0, 1], not %r" % (theta,))
+        if theta > 0.0 and val is None:
+            raise SblasError("theta > 0 needs val, the values the strength test reads")
+        if val is not None:
+            _krylov_vector("val", val, self.nnz, self.device)
+        if int(coarse_max) < 1 or not 1 <= int(max_levels) <= amg_limits()["level_cap"]:
+            raise SblasError("coarse_max must be at least 1 and max_levels in [1, %d]" % amg_limits()["level_cap"])
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_amg_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr() if n else None,
+                                                 colidx.data_ptr() if self.nnz else None,
+                                                 val.data_ptr() if val is not None and theta > 0.0 and self.nnz else None, theta,
+                                                 int(coarse_max), int(max_levels), int(seed) & 0xffffffff, C.byref(h), C.byref(bad))
+        if rc != 0:
+            raise _bad_structure("sblas_hip_amg_plan_create", rc, bad.value)
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_amg_plan_info(self.handle, out), "sblas_hip_amg_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), levels=int(out[2]), nu=int(out[3]), coarse_sweeps=int(out[4]), launches=int(out[5]),
+                    rows=int(out[6]), entries=int(out[7]), bytes=int(out[8]), smoother=("jacobi", "l1")[out[9]], ready=bool(out[10]),
+                    coarsest=int(out[11]), operator_complexity=(out[7] / out[1] if out[1] else 1.0))
+
+    def level(self, l):
+        """Level l's device arrays as torch views that live as long as the plan: dict(n, nnz, n_coarse, units, rowptr,
+        colidx, val, wd, agg, aggptr, members); agg, aggptr and members are None on the coarsest level, val (and wd's
+        content) is there after setup()."""
+        import torch
+        sizes, ptrs = (C.c_int64 * 4)(), (C.c_void_p * 7)()
+        check(lib().sblas_hip_amg_plan_level(self.handle, int(l), sizes, ptrs), "sblas_hip_amg_plan_level")
+        n, nnz, nc = int(sizes[0]), int(sizes[1]), int(sizes[2])
+        view = lambda p, k, t: torch.as_tensor(_DeviceArray(p, k, t), device=self.device) if p and k else None
+        return dict(n=n, nnz=nnz, n_coarse=nc, units=int(sizes[3]), rowptr=view(ptrs[0], n + 1, "<i4"), colidx=view(ptrs[1], nnz, "<i4"),
+                    val=view(ptrs[2], nnz, "<f8"), wd=view(ptrs[3], n, "<f8"), agg=view(ptrs[4], n if nc else 0, "<i4"),
+                    aggptr=view(ptrs[5], nc + 1 if nc else 0, "<i4"), members=view(ptrs[6], n if nc else 0, "<i4"))
+
+    def levels(self):
+        """[(n, nnz)] of every level, the finest first"""
+        out = []
+        for l in range(self.info()["levels"]):
+            sizes, ptrs = (C.c_int64 * 4)(), (C.c_void_p * 7)()
+            check(lib().sblas_hip_amg_plan_level(self.handle, l, sizes, ptrs), "sblas_hip_amg_plan_level")
+            out.append((int(sizes[0]), int(sizes[1])))
+        return out
+
+    def setup(self, val, smoother="jacobi", omega=None, nu=1, coarse_sweeps=8, coarse_scale=1.0, stream=None):
+        """Every level's values (the Galerkin sums of the aggregates) and the smoother's omega / d from val, on the
+        device.  smoother: "jacobi" (omega defaults to 2/3) or "l1" (1).  The plan keeps val alive and sweeps level 0 on
+        it: do not change it before the next setup.  Every refusal comes before any launch."""
+        import torch
+        if smoother not in AMG_SMOOTHERS:
+            raise SblasError("smoother must be 'jacobi' or 'l1', not %r" % (smoother,))
+        _krylov_vector("val", val, self.nnz, self.device)
+        if omega is None:
+            omega = 0.0
+        elif not (float(omega) > 0.0 and float(omega) < float("inf")):
+            raise SblasError("omega must be positive and finite, not %r" % (omega,))
+        if int(nu) < 1 or int(coarse_sweeps) < 1:
+            raise SblasError("nu and coarse_sweeps must be at least 1")
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_amg_plan_setup(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                                AMG_SMOOTHERS[smoother], float(omega), int(nu), int(coarse_sweeps), float(coarse_scale))
+        check(rc, "sblas_hip_amg_plan_setup")
+        self._val = val
+
+    def apply(self, r, out=None, stream=None):
+        """out = M^-1 r: one V-cycle from a zero guess.  out: made here when None; it must not be r.  Returns out."""
+        import torch
+        _krylov_vector("r", r, self.n, self.device)
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        _krylov_vector("out", out, self.n, self.device)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_amg_plan_apply(self.handle, _stream(stream), r.data_ptr() if self.n else None,
+                                                out.data_ptr() if self.n else None)
+        check(rc, "sblas_hip_amg_plan_apply")
+        return out
+
+    def check(self, stream=None):
+        """None, or (level, row) of the least diagonal the last setup() found not finite and > 0.  Synchronises."""
+        import torch
+        out = (C.c_int64 * 2)()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_amg_plan_check(self.handle, _stream(stream), out), "sblas_hip_amg_plan_check")
+        return None if out[0] < 0 else (int(out[0]), int(out[1]))
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_amg_plan_destroy(self.handle)
+            self.handle = None
+        self._val = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _amg_level_vector(name, t, n, plan):
+    _krylov_vector(name, t, n, plan.device)
+    return t.data_ptr() if n else None
+
+
+def _amg_level_sizes(plan, level):
+    sizes, ptrs = (C.c_int64 * 4)(), (C.c_void_p * 7)()
+    check(lib().sblas_hip_amg_plan_level(plan.handle, int(level), sizes, ptrs), "sblas_hip_amg_plan_level")
+    return int(sizes[0]), int(sizes[2])
+
+
+def amg_sweep(plan, level, b, x, y, mode="sweep", stream=None):
+    """One launch of the row sweep on level `level` of an AmgPlan after setup() (sblas_hip_amg_sweep_f64): mode "sweep"
+    y = x + wd o (b - A x), "residual" y = b - A x, "first" y = wd o b (x may be None).  y must be neither x nor b."""
+    import torch
+    if mode not in AMG_SWEEP_MODES:
+        raise SblasError("mode must be 'sweep', 'residual' or 'first', not %r" % (mode,))
+    n, _ = _amg_level_sizes(plan, level)
+    pb, py = _amg_level_vector("b", b, n, plan), _amg_level_vector("y", y, n, plan)
+    px = _amg_level_vector("x", x, n, plan) if (mode != "first" or x is not None) else None
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_sweep_f64(plan.handle, _stream(stream), int(level), AMG_SWEEP_MODES[mode], pb, px, py),
+              "sblas_hip_amg_sweep_f64")
+    return y
+
+
+def amg_restrict(plan, level, res, bc, stream=None):
+    """bc[I] = the sum of res over aggregate I of level `level`, ascending (sblas_hip_amg_restrict_f64)"""
+    import torch
+    n, nc = _amg_level_sizes(plan, level)
+    pr, pc = _amg_level_vector("res", res, n, plan), _amg_level_vector("bc", bc, nc, plan)
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_restrict_f64(plan.handle, _stream(stream), int(level), pr, pc), "sblas_hip_amg_restrict_f64")
+    return bc
+
+
+def amg_prolong(plan, level, e, x, scale=1.0, stream=None):
+    """x_i = x_i + scale * e[agg[i]] on level `level` (sblas_hip_amg_prolong_f64)"""
+    import torch
+    n, nc = _amg_level_sizes(plan, level)
+    pe, px = _amg_level_vector("e", e, nc, plan), _amg_level_vector("x", x, n, plan)
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_prolong_f64(plan.handle, _stream(stream), int(level), float(scale), pe, px), "sblas_hip_amg_prolong_f64")
+    return x
+
+
+# ------------------------------------------------------------------------------------------
+# Krylov solvers on a plan, resident on the device: PCG and BiCGStab (sblas_hip_krylov_*)
+# ------------------------------------------------------------------------------------------
 def krylov_dots(pairs, out=None, workspace=None, stream=None):
     """The pinned dot products (x, y) of up to three pairs in ONE pass over memory (sblas_hip_krylov_dot_f64): a device
     tensor of len(pairs) doubles, each with exactly the bits krylov_dot gives alone.  No synchronisation; with out and
@@ -2260,8 +2554,11 @@ class KrylovPlan:
         elif isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
             self.precond_kind = PRECOND_ILU0
             lower, upper = precond
+        elif isinstance(precond, AmgPlan):                                  # the handle travels in the lower plan's place
+            self.precond_kind = PRECOND_AMG
+            lower = precond
         else:
-            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan or a pair of SptrsvPlans, not %r" % (precond,))
+            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans or an AmgPlan, not %r" % (precond,))
         if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
             raise SblasError("spmv_plan must be an SpmvPlan or None")
         self._solvers = (lower, upper)
@@ -2280,7 +2577,7 @@ class KrylovPlan:
         out = (C.c_int64 * 10)()
         check(lib().sblas_hip_krylov_plan_info(self.handle, out), "sblas_hip_krylov_plan_info")
         return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
-                    precond=(None, "jacobi", "ilu0")[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
+                    precond=(None, "jacobi", "ilu0", "amg")[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
                     scalar_bytes=int(out[7]), bytes=int(out[8]), launches=int(out[9]))
 
     def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
@@ -2361,18 +2658,21 @@ class KrylovPlan:
 def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
     import torch
     n, rowptr, colidx, val = A
-    if precond not in (None, "jacobi", "ilu0"):
-        raise SblasError("precond must be None, 'jacobi' or 'ilu0', not %r" % (precond,))
-    ilu = plan = None
+    if precond not in (None, "jacobi", "ilu0", "amg"):
+        raise SblasError("precond must be None, 'jacobi', 'ilu0' or 'amg', not %r" % (precond,))
+    ilu = plan = amg = None
     lu = dinv = None
     try:
-        if precond is not None:                                           # both read the diagonal's places off the ILU(0) plan
+        if precond == "amg":                                              # the defaults: V(1, 1), Jacobi 2/3, structure only
+            amg = AmgPlan(n, rowptr, colidx)
+            amg.setup(val)
+        elif precond is not None:                                           # both read the diagonal's places off the ILU(0) plan
             ilu = Ilu0Plan(n, rowptr, colidx)
             if precond == "ilu0":
                 lu = ilu.factor(val)
             else:
                 dinv = ilu.pivots(val).reciprocal_()
-        pre = ilu if precond == "ilu0" else precond
+        pre = ilu if precond == "ilu0" else amg if precond == "amg" else precond
         plan = make(n, rowptr, colidx, pre) if make is not None else KrylovPlan(n, rowptr, colidx, method=method, precond=pre)
         return plan.solve(val, b, x=x, lu=lu, dinv=dinv, **kw)
     finally:
@@ -2380,6 +2680,8 @@ def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
             plan.destroy()
         if ilu is not None:
             ilu.destroy()
+        if amg is not None:
+            amg.destroy()
 
 
 def pcg(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
@@ -2501,8 +2803,11 @@ class GmresPlan:
         elif isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
             self.precond_kind = PRECOND_ILU0
             lower, upper = precond
+        elif isinstance(precond, AmgPlan):                                  # the handle travels in the lower plan's place
+            self.precond_kind = PRECOND_AMG
+            lower = precond
         else:
-            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan or a pair of SptrsvPlans, not %r" % (precond,))
+            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans or an AmgPlan, not %r" % (precond,))
         if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
             raise SblasError("spmv_plan must be an SpmvPlan or None")
         self.nnz = _structure(n, rowptr, colidx)
@@ -2522,7 +2827,7 @@ class GmresPlan:
     def info(self):
         out = (C.c_int64 * 14)()
         check(lib().sblas_hip_gmres_plan_info(self.handle, out), "sblas_hip_gmres_plan_info")
-        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=(None, "jacobi", "ilu0")[out[3]], vectors=int(out[4]),
+        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=(None, "jacobi", "ilu0", "amg")[out[3]], vectors=int(out[4]),
                     vector_bytes=int(out[5]), partial_bytes=int(out[6]), scalar_bytes=int(out[7]), matrix_bytes=int(out[8]),
                     bytes=int(out[9]), step_launches=int(out[10]), close_launches=int(out[11]), restart_launches=int(out[12]),
                     cycle_launches=int(out[13]))

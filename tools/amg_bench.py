@@ -1,0 +1,160 @@
+"""Aggregation AMG on the device (AmgPlan: sblas_hip_amg_plan_*) against the other preconditioners, on one GPU.
+
+Per matrix: the hierarchy (level sizes, operator complexity, launches of a cycle), the host-clock time of create and of
+the first setup, device-event times of setup, of one apply, of Ilu0Plan.apply and of the planned SpMV on the same matrix
+(the median over `--rounds` rounds and every round, the routes alternating round by round), and PCG to 1e-8 with no
+preconditioner, Jacobi, ILU(0), ILU(0) in the multicolour order and AMG in one process: iterations, status and the
+host-clock time of each solve.
+
+Every matrix is measured in a child process of its own under its own time limit, one at a time, and nothing is started
+after a child that failed or ran out of time.  One JSON object per matrix on stdout; --out writes the list.
+
+  python tools/amg_bench.py [--inputs nd24k,grid,bidiagonal,banded5,powerlaw] [--rounds 5] [--out profiles/r19_amg.json]
+
+Matrices: those of tools/ilu0_bench.py made symmetric -- the same sorted symmetric patterns, every off-diagonal pair
+given the value of its lower entry, the diagonal 1 + the row's absolute off-diagonal sum: symmetric positive definite."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "s-blas_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def symmetric(n, rp, ci, val):
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp.astype(np.int64)))
+    col = ci.astype(np.int64)
+    lo, hi = np.maximum(row, col), np.minimum(row, col)                      # the entry of the lower triangle names the pair
+    key = row * n + col
+    pos = np.searchsorted(key, lo * n + hi)                                  # rows ascend: the keys are sorted
+    val = val[pos].copy()
+    dg = row == col
+    val[dg] = 1.0 + np.bincount(row, weights=np.where(dg, 0.0, np.abs(val)), minlength=n)
+    return val
+
+
+def solve_timed(torch, fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    x, st = fn()
+    torch.cuda.synchronize()
+    return dict(iterations=st["iterations"], status=st["status"], rnorm=st["rnorm"], bnorm=st["bnorm"], ms=(time.perf_counter() - t0) * 1e3), x
+
+
+def measure(name, args):
+    import torch
+    import sblas_amd as S
+    import ilu0_bench as IB
+    import sptrsv_bench as TB
+    dev = torch.device("cuda:0")
+    label, n, rp, ci, val = IB.build(name, args)
+    val = symmetric(n, rp, ci, val)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    drp, dci, dval = up(rp), up(ci), up(val)
+    rec = dict(matrix=label + ", symmetric", n=n, nnz=int(len(ci)), limits=S.amg_limits(), device=torch.cuda.get_device_name(0))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    amg = S.AmgPlan(n, drp, dci)
+    torch.cuda.synchronize()
+    rec["create_ms"] = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    amg.setup(dval)
+    torch.cuda.synchronize()
+    rec["first_setup_ms"] = (time.perf_counter() - t0) * 1e3
+    rec["info"], rec["levels"], rec["check"] = amg.info(), amg.levels(), amg.check()
+    ilu = S.Ilu0Plan(n, drp, dci)
+    lu = ilu.factor(dval)
+    spmv = S.SpmvPlan(n, n, drp, dci)
+    b = up(np.random.default_rng(5).random(n) * 2 - 1)
+    z, y, tmp = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
+    ilu.solvers()
+    fns = {"amg_setup": lambda: amg.setup(dval), "amg_apply": lambda: amg.apply(b, out=z),
+           "ilu0_apply": lambda: ilu.apply(lu, b, out=y, tmp=tmp), "spmv": lambda: spmv(dval, b, 1.0, 0.0, y)}
+    for k, (ms, each) in TB.timed(torch, fns, args.rounds).items():
+        rec["%s_ms" % k], rec["%s_rounds" % k] = ms, each
+    rec["apply_over_ilu0_apply"] = rec["amg_apply_ms"] / rec["ilu0_apply_ms"]
+    rec["apply_over_spmv"] = rec["amg_apply_ms"] / rec["spmv_ms"]
+    rec["ilu0_solve_launches"] = [p.info()["launches"] for p in ilu.solvers()]
+
+    kw = dict(rtol=1e-8, max_iter=args.max_iter, check_every=32)
+    pcg = {}
+    plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv)
+    pcg["none"], _ = solve_timed(torch, lambda: plan.solve(dval, b, **kw))
+    plan.destroy()
+    plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv, precond="jacobi")
+    dinv = ilu.pivots(dval).reciprocal_()
+    pcg["jacobi"], _ = solve_timed(torch, lambda: plan.solve(dval, b, dinv=dinv, **kw))
+    plan.destroy()
+    plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv, precond=ilu)
+    pcg["ilu0"], _ = solve_timed(torch, lambda: plan.solve(dval, b, lu=lu, **kw))
+    plan.destroy()
+    plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv, precond=amg)
+    pcg["amg"], _ = solve_timed(torch, lambda: plan.solve(dval, b, **kw))
+    plan.destroy()
+    # ILU(0) in the multicolour order: the caller's composition (KrylovPlan's docstring)
+    color = S.ColorPlan(n, drp, dci)
+    perm = color.permute(drp, dci)
+    crp, cci, _ = perm.csr()
+    cilu = S.Ilu0Plan(n, crp, cci)
+    cval = perm.values(dval)
+    clu = cilu.factor(cval)
+    cb = perm.to_permuted(b)
+    plan = S.KrylovPlan(n, crp, cci, precond=cilu)
+    pcg["ilu0_multicolour"], _ = solve_timed(torch, lambda: plan.solve(cval, cb, lu=clu, **kw))
+    pcg["ilu0_multicolour"]["colours"] = color.info().get("colors")
+    plan.destroy()
+    rec["pcg"] = pcg
+    for p in (cilu, perm, color, ilu, spmv, amg):
+        p.destroy()
+    print(json.dumps(rec), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--inputs", default="nd24k,grid,bidiagonal,banded5,powerlaw")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--rows", type=int, default=1000000)
+    ap.add_argument("--grid-side", type=int, default=1000)
+    ap.add_argument("--nd24k-scale", type=float, default=1.0)
+    ap.add_argument("--max-iter", type=int, default=2000)
+    ap.add_argument("--limit", type=int, default=240, help="seconds a matrix may take")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--one", default=None, help="(internal) measure this matrix in this process")
+    args = ap.parse_args()
+    if args.one:
+        return measure(args.one, args)
+
+    results, failed = [], None
+    for name in args.inputs.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--one", name, "--rounds", str(args.rounds), "--rows", str(args.rows),
+               "--grid-side", str(args.grid_side), "--nd24k-scale", str(args.nd24k_scale), "--max-iter", str(args.max_iter)]
+        try:
+            run = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=args.limit)
+        except subprocess.TimeoutExpired:
+            failed = dict(matrix=name, failed="no result within %d s" % args.limit)
+        else:
+            lines = [l for l in run.stdout.decode().splitlines() if l.startswith("{")]
+            if run.returncode != 0 or not lines:
+                failed = dict(matrix=name, failed="exit status %d" % run.returncode)
+            else:
+                results.append(json.loads(lines[-1]))
+                print(lines[-1], flush=True)
+        if failed:                                                          # nothing is started after a failure
+            results.append(failed)
+            print(json.dumps(failed), flush=True)
+            break
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,282 @@
+// amg_rule_check.cpp -- a stand-alone program over the AMG plan's host rule (s-blas_amd/csrc/amg_rule.cpp with ILU(0)'s
+// structure check from ilu0_plan.cpp; no GPU, no HIP runtime), made to be built with a host sanitizer:
+//   clang++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all tools/amg_rule_check.cpp \
+//       s-blas_amd/csrc/amg_rule.cpp s-blas_amd/csrc/ilu0_plan.cpp -o /tmp/amg_rule_check && /tmp/amg_rule_check
+// It aggregates small matrices (n = 0 and 1, a diagonal, a tridiagonal, a grid, a clique, a star, an anisotropic grid
+// with theta) out of arrays of exactly the sizes the contract names, so that a read or write past either end is the
+// sanitizer's to find, checks every aggregate's invariants, builds the Galerkin hierarchy with a second, naive
+// restatement of the COO order, runs the cycle reference on it against a restatement of the written order, and holds
+// the launch counts against a hand count.
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <map>
+#include <vector>
+#include "../include/sblas_hip.h"
+
+#pragma clang fp contract(off)
+
+struct Csr {
+    int64_t n = 0;
+    std::vector<int32_t> rowptr{0}, colidx;
+    std::vector<double> val;
+    void row(const std::map<int32_t, double> &r)
+    {
+        for (const auto &kv : r) colidx.push_back(kv.first), val.push_back(kv.second);
+        rowptr.push_back((int32_t)colidx.size());
+        ++n;
+    }
+};
+
+static Csr grid(int side, double ax, double ay)
+{
+    Csr a;
+    for (int y = 0; y < side; ++y)
+        for (int x = 0; x < side; ++x) {
+            std::map<int32_t, double> r;
+            r[y * side + x] = 2 * ax + 2 * ay;
+            if (x > 0) r[y * side + x - 1] = -ax;
+            if (x + 1 < side) r[y * side + x + 1] = -ax;
+            if (y > 0) r[(y - 1) * side + x] = -ay;
+            if (y + 1 < side) r[(y + 1) * side + x] = -ay;
+            a.row(r);
+        }
+    return a;
+}
+
+struct Level {
+    Csr a;
+    std::vector<double> wd;
+    std::vector<int32_t> agg, aggptr, members;
+};
+
+static int bad = 0;
+static void expect(bool ok, const char *what)
+{
+    if (!ok) ++bad, fprintf(stderr, "amg_rule_check: %s\n", what);
+}
+
+// one level's aggregation out of exact-size arrays, with its invariants
+static int64_t aggregate(const Csr &a, double theta, uint32_t seed, uint32_t level, Level &out)
+{
+    const int64_t n = a.n;
+    std::vector<int32_t> agg((size_t)n), members((size_t)n), aggptr((size_t)n + 1);
+    int64_t n_agg = -1, row = 0;
+    const int rc = sblas_amg_aggregate(n, a.rowptr.data(), a.colidx.data(), theta > 0 ? a.val.data() : nullptr, theta, seed, level, agg.data(),
+                                       aggptr.data(), members.data(), &n_agg, &row);
+    expect(rc == SBLAS_OK && row == -1 && n_agg >= 0 && n_agg <= n, "aggregate accepts a sound structure");
+    aggptr.resize((size_t)n_agg + 1);
+    expect(aggptr[0] == 0 && aggptr[(size_t)n_agg] == n, "aggptr spans the vertices");
+    std::vector<int> seen((size_t)n, 0);
+    for (int64_t g = 0; g < n_agg; ++g)
+        for (int32_t k = aggptr[(size_t)g]; k < aggptr[(size_t)g + 1]; ++k) {
+            expect(agg[(size_t)members[(size_t)k]] == g, "a member lies in its aggregate");
+            expect(k == aggptr[(size_t)g] || members[(size_t)k] > members[(size_t)k - 1], "members ascend inside an aggregate");
+            ++seen[(size_t)members[(size_t)k]];
+        }
+    for (int64_t v = 0; v < n; ++v) expect(seen[(size_t)v] == 1, "every vertex is in exactly one aggregate");
+    out.agg = agg, out.aggptr = aggptr, out.members = members;
+    return n_agg;
+}
+
+// the triplets (agg[row], agg[col]) in stored order, sorted by (row, col) with equal pairs in input order, summed left to right
+static Csr galerkin(const Csr &a, const std::vector<int32_t> &agg, int64_t nc)
+{
+    std::vector<size_t> order(a.colidx.size());
+    std::vector<int32_t> tr(order.size()), tc(order.size());
+    for (int64_t i = 0; i < a.n; ++i)
+        for (int32_t e = a.rowptr[(size_t)i]; e < a.rowptr[(size_t)i + 1]; ++e) tr[(size_t)e] = agg[(size_t)i], tc[(size_t)e] = agg[(size_t)a.colidx[(size_t)e]];
+    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return tr[x] != tr[y] ? tr[x] < tr[y] : tc[x] < tc[y]; });
+    Csr c;
+    c.n = nc;
+    c.rowptr.assign((size_t)nc + 1, 0);
+    for (size_t k = 0; k < order.size(); ++k) {
+        const size_t e = order[k];
+        if (k > 0 && tr[e] == tr[order[k - 1]] && tc[e] == tc[order[k - 1]]) {
+            c.val.back() = c.val.back() + a.val[e];
+        } else {
+            c.colidx.push_back(tc[e]), c.val.push_back(a.val[e]);
+            ++c.rowptr[(size_t)tr[e] + 1];
+        }
+    }
+    for (int64_t g = 0; g < nc; ++g) c.rowptr[(size_t)g + 1] += c.rowptr[(size_t)g];
+    return c;
+}
+
+static std::vector<Level> hierarchy(const Csr &a, double theta, int64_t coarse_max, int smoother, double omega)
+{
+    std::vector<Level> lv;
+    if (a.n == 0) return lv;
+    Csr cur = a;
+    for (;;) {
+        Level L;
+        L.a = cur;
+        L.wd.resize((size_t)cur.n);
+        int64_t row = 0;
+        expect(sblas_amg_wd_ref(cur.n, cur.rowptr.data(), cur.colidx.data(), cur.val.data(), smoother, omega, L.wd.data(), &row) == SBLAS_OK && row == -1,
+               "wd of a sound level");
+        const bool coarsen = cur.n > coarse_max && lv.size() + 1 < 20;
+        int64_t nc = cur.n;
+        if (coarsen) nc = aggregate(cur, theta, 0, (uint32_t)lv.size(), L);
+        if (nc >= cur.n) L.agg.clear(), L.aggptr.clear(), L.members.clear();
+        lv.push_back(L);
+        if (nc >= cur.n) return lv;
+        cur = galerkin(cur, lv.back().agg, nc);
+    }
+}
+
+// the written order once more
+static double row_sum(const Csr &a, int64_t i, const std::vector<double> &x)
+{
+    const int p = a.rowptr[(size_t)i + 1] - a.rowptr[(size_t)i], G = p <= 4 ? 4 : p <= 32 ? 16 : 64;
+    std::vector<double> v((size_t)G, 0.0), w((size_t)G);
+    for (int l = 0; l < G; ++l)
+        for (int e = a.rowptr[(size_t)i] + l; e < a.rowptr[(size_t)i + 1]; e += G) v[(size_t)l] = fma(a.val[(size_t)e], x[(size_t)a.colidx[(size_t)e]], v[(size_t)l]);
+    for (int m = 1; m < G; m <<= 1) {
+        for (int l = 0; l < G; ++l) w[(size_t)l] = v[(size_t)l] + v[(size_t)(l ^ m)];
+        v = w;
+    }
+    return v[0];
+}
+
+static std::vector<double> sweep(const Level &L, const std::vector<double> &b, const std::vector<double> &x, bool residual)
+{
+    std::vector<double> y((size_t)L.a.n);
+    for (int64_t i = 0; i < L.a.n; ++i) {
+        const double d = b[(size_t)i] - row_sum(L.a, i, x), t = L.wd[(size_t)i] * d;
+        y[(size_t)i] = residual ? d : x[(size_t)i] + t;
+    }
+    return y;
+}
+
+static std::vector<double> cycle(const std::vector<Level> &lv, size_t l, const std::vector<double> &b, int nu, int cs, double scale)
+{
+    const Level &L = lv[l];
+    std::vector<double> x((size_t)L.a.n);
+    for (int64_t i = 0; i < L.a.n; ++i) x[(size_t)i] = L.wd[(size_t)i] * b[(size_t)i];
+    if (l + 1 == lv.size()) {
+        for (int k = 1; k < cs; ++k) x = sweep(L, b, x, false);
+        return x;
+    }
+    for (int k = 1; k < nu; ++k) x = sweep(L, b, x, false);
+    const std::vector<double> res = sweep(L, b, x, true);
+    std::vector<double> bc(L.aggptr.size() - 1);
+    for (size_t g = 0; g + 1 < L.aggptr.size(); ++g) {
+        double s = 0.0;
+        for (int32_t k = L.aggptr[g]; k < L.aggptr[g + 1]; ++k) s = s + res[(size_t)L.members[(size_t)k]];
+        bc[g] = s;
+    }
+    const std::vector<double> e = cycle(lv, l + 1, bc, nu, cs, scale);
+    for (int64_t i = 0; i < L.a.n; ++i) {
+        const double t = scale * e[(size_t)L.agg[(size_t)i]];
+        x[(size_t)i] = x[(size_t)i] + t;
+    }
+    for (int k = 0; k < nu; ++k) x = sweep(L, b, x, false);
+    return x;
+}
+
+static void check_case(const char *name, const Csr &a, double theta, int64_t coarse_max, size_t want_levels)
+{
+    for (int smoother = 0; smoother < 2; ++smoother)
+        for (int nu = 1; nu <= 2; ++nu) {
+            const double omega = smoother ? 1.0 : 2.0 / 3.0, scale = nu == 1 ? 1.0 : 1.5;
+            const std::vector<Level> lv = hierarchy(a, theta, coarse_max, smoother, omega);
+            if (want_levels) expect(lv.size() == want_levels, name);
+            const int k = (int)lv.size();
+            std::vector<int64_t> n;
+            std::vector<const int32_t *> rp, ci, agg, aggptr, members;
+            std::vector<const double *> val, wd;
+            for (const Level &L : lv) {
+                n.push_back(L.a.n), rp.push_back(L.a.rowptr.data()), ci.push_back(L.a.colidx.data()), val.push_back(L.a.val.data());
+                wd.push_back(L.wd.data()), agg.push_back(L.agg.data()), aggptr.push_back(L.aggptr.data()), members.push_back(L.members.data());
+            }
+            std::vector<double> r((size_t)a.n), z((size_t)a.n, -7.0);
+            for (size_t i = 0; i < r.size(); ++i) r[i] = sin(1.0 + (double)i) + 0.25;
+            const int rc = sblas_amg_cycle_ref(k, n.data(), rp.data(), ci.data(), val.data(), wd.data(), agg.data(), aggptr.data(), members.data(), nu,
+                                               3, scale, r.data(), z.data());
+            expect(rc == SBLAS_OK, "cycle_ref accepts a sound hierarchy");
+            if (k > 0) {
+                const std::vector<double> want = cycle(lv, 0, r, nu, 3, scale);
+                expect(memcmp(want.data(), z.data(), z.size() * 8) == 0, name);
+                expect(sblas_amg_cycle_ref(k, n.data(), rp.data(), ci.data(), val.data(), wd.data(), agg.data(), aggptr.data(), members.data(), nu, 3,
+                                           scale, r.data(), r.data()) == SBLAS_E_INVALID,
+                       "z must not be r");
+            }
+            expect(sblas_amg_launches(k, nu, 3) == (k == 0 ? 0 : (int64_t)(k - 1) * (2 * nu + 3) + 3), "launches of a cycle");
+        }
+}
+
+int main()
+{
+    int64_t lim[8];
+    expect(sblas_amg_limits(lim) == SBLAS_OK && sblas_amg_limits(nullptr) == SBLAS_E_INVALID, "limits");
+    expect(lim[0] == 4 && lim[1] == 32 && lim[3] == 64 && lim[4] == 20 && lim[5] == 1 && lim[6] == 8, "the defaults");
+    expect(sblas_amg_launches(4, 1, 8) == 23 && sblas_amg_launches(1, 1, 8) == 8 && sblas_amg_launches(0, 1, 8) == 0, "launch counts");
+    expect(sblas_amg_launches(-1, 1, 8) == -1 && sblas_amg_launches(3, 0, 8) == -1 && sblas_amg_launches(3, 1, 0) == -1, "launch refusals");
+
+    Csr empty, one, diag, tri, clique, star;
+    one.row({{0, 2.0}});
+    for (int i = 0; i < 40; ++i) diag.row({{i, 1.0 + i % 3}});
+    for (int i = 0; i < 300; ++i) {
+        std::map<int32_t, double> r{{i, 2.0}};
+        if (i > 0) r[i - 1] = -1.0;
+        if (i + 1 < 300) r[i + 1] = -1.0;
+        tri.row(r);
+    }
+    for (int i = 0; i < 70; ++i) {
+        std::map<int32_t, double> r;
+        for (int j = 0; j < 70; ++j) r[j] = i == j ? 71.0 : -1.0;
+        clique.row(r);
+    }
+    {
+        std::map<int32_t, double> hub;
+        for (int j = 0; j < 200; ++j) hub[j] = j ? -1.0 : 200.0;
+        star.row(hub);
+        for (int i = 1; i < 200; ++i) star.row({{0, -1.0}, {i, 2.0}});
+    }
+    check_case("n = 0", empty, 0.0, 64, 0);
+    check_case("n = 1", one, 0.0, 64, 1);
+    check_case("diagonal: one level", diag, 0.0, 8, 1);
+    check_case("tridiagonal", tri, 0.0, 16, 0);
+    check_case("grid", grid(12, 1.0, 1.0), 0.0, 16, 0);
+    check_case("clique", clique, 0.0, 16, 2);
+    check_case("star", star, 0.0, 64, 0);
+    check_case("anisotropic grid", grid(10, 1.0, 0.01), 0.25, 16, 0);
+
+    // refusals, each with its row
+    {
+        Csr g = grid(4, 1.0, 1.0);
+        std::vector<int32_t> agg(16), ptr(17), mem(16);
+        int64_t n_agg = 0, row = -1;
+        std::swap(g.colidx[(size_t)g.rowptr[5]], g.colidx[(size_t)g.rowptr[5] + 1]); // row 5 no longer ascends
+        expect(sblas_amg_aggregate(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.0, 0, 0, agg.data(), ptr.data(), mem.data(), &n_agg, &row) ==
+                       SBLAS_E_INVALID && row == 5,
+               "an unsorted row is named");
+        g = grid(4, 1.0, 1.0);
+        for (int32_t e = g.rowptr[9]; e < g.rowptr[10]; ++e)
+            if (g.colidx[(size_t)e] == 9) g.colidx[(size_t)e] = 8; // row 9 loses its diagonal (and doubles a column)
+        expect(sblas_amg_aggregate(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.0, 0, 0, agg.data(), ptr.data(), mem.data(), &n_agg, &row) ==
+                       SBLAS_E_INVALID && row == 9,
+               "a missing diagonal is named");
+        g = grid(4, 1.0, 1.0);
+        const double thetas[3] = {-0.5, 1.5, NAN};
+        for (double t : thetas)
+            expect(sblas_amg_aggregate(16, g.rowptr.data(), g.colidx.data(), g.val.data(), t, 0, 0, agg.data(), ptr.data(), mem.data(), &n_agg, &row) ==
+                       SBLAS_E_INVALID,
+                   "theta outside [0, 1]");
+        expect(sblas_amg_aggregate(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.25, 0, 0, agg.data(), ptr.data(), mem.data(), &n_agg, &row) ==
+                   SBLAS_E_INVALID,
+               "theta > 0 without values");
+        std::vector<double> wd(16);
+        for (int32_t e = g.rowptr[7]; e < g.rowptr[8]; ++e)
+            if (g.colidx[(size_t)e] == 7) g.val[(size_t)e] = 0.0;
+        expect(sblas_amg_wd_ref(16, g.rowptr.data(), g.colidx.data(), g.val.data(), SBLAS_AMG_JACOBI, 0.5, wd.data(), &row) == SBLAS_OK && row == 7,
+               "a zero diagonal is reported");
+    }
+    if (bad) return fprintf(stderr, "amg_rule_check: %d failures\n", bad), 1;
+    printf("amg_rule_check: ok\n");
+    return 0;
+}
