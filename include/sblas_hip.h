@@ -1002,6 +1002,9 @@ int sblas_hip_amg_sweep_f64(const void *plan, void *stream, int level, int mode,
 int sblas_hip_amg_restrict_f64(const void *plan, void *stream, int level, const double *res, double *bc);
 int sblas_hip_amg_prolong_f64(const void *plan, void *stream, int level, double scale, const double *e, double *x);
 
+/* Smoothed aggregation on the same plan (SBLAS_AMG_SMOOTHED, sblas_hip_amg_plan_create_ex, the coarsening guard and their
+ * host references) is declared in sblas_hip_amg_sa.h, which this header includes at its end. */
+
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
  * (the gradient of C = A * B with respect to A's values with X = dC and Y = B; edge scores; residuals on a pattern).
@@ -1255,4 +1258,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #ifdef __cplusplus
 }
 #endif
+#include "sblas_hip_amg_sa.h"
 #endif /* SBLAS_HIP_H */

@@ -74,6 +74,19 @@ inline bool amg_cycle_args_ok(int levels, int nu, int coarse_sweeps)
 }
 inline bool amg_theta_ok(double theta) { return theta >= 0.0 && theta <= 1.0; } // a NaN fails both
 
+// Smoothed aggregation.  The coarsening guard: a level of n rows whose aggregation leaves n_next is kept
+// only when it reduces n at all (the plain plan's rule) and n_next <= (1 - min_reduction) * n, the product rounded once.
+constexpr double AMG_PROLONG_OMEGA = 2.0 / 3.0;        // 4 / (3 rho) with rho(D^-1 A) taken as 2: no eigenvalue estimate
+constexpr double AMG_SMOOTHED_MIN_REDUCTION = 0.2;     // the Python layer's default for a smoothed plan
+inline bool amg_min_reduction_ok(double m) { return m >= 0.0 && m < 1.0; } // a NaN fails both
+inline bool amg_prolong_omega_ok(double w) { return w > 0.0 && w <= 1.79769313486231570815e308; } // finite, > 0; a NaN fails
+inline bool amg_keep_level(int64_t n, int64_t n_next, double min_reduction)
+{
+    const double bound = (1.0 - min_reduction) * (double)n;
+    return n_next < n && (double)n_next <= bound;
+}
+enum { AMG_RESTRICT = 0, AMG_PROLONG = 1 }; // modes of the transfer row product
+
 // One level's aggregation on host arrays (sblas_amg_aggregate without the argument checks): agg (n), aggptr (n_agg + 1,
 // resized here), members (n) -> n_agg.  val may be null (structure only).
 int64_t amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,

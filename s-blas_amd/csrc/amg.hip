@@ -19,6 +19,16 @@
 // butterfly of rowwise.h -- exactly the triangular solves' row sum (sptrsv.hip) over the whole row.  The rows are packed
 // into waves as a solve's wide level packs them (level_plan.h with one level): which rows share a wave does not enter
 // any row's sum.  Everything else is rounded operation by operation: this file is compiled with contraction off.
+//
+// Smoothed aggregation (sblas_hip_amg_plan_create_ex with SBLAS_AMG_SMOOTHED) keeps all of the above and
+// replaces a level's transfers.  The tentative aggregates are the same rule's.  P_l's pattern is the COO plan (dup = sum) of
+// the triplets (row(e), agg[col(e)]) in A_l's stored order; its values are that plan's re-assembly of t, where q_i =
+// omega_P / a_ii (a rounded division), t_e = -(q_i a_ie) off the diagonal and 1 - q_i a_ii on it (a rounded product, then
+// a rounded difference).  omega_P defaults to 2/3 = 4 / (3 rho) with rho(D^-1 A) taken as 2: no eigenvalue estimate; A is
+// used unfiltered.  R_l = P_l^T by the device transpose (stable), its values gathered; A_{l+1} = R_l (A_l P_l) by two
+// SpGEMM plans.  Both transfers of a cycle are transfer_row(): the sweep's row sum over a stored row of R_l (restrict:
+// b_{l+1}[I] = s_I) or P_l (prolong: x_i = x_i + scale s_i, in place: only the coarse vector is gathered).  A level is
+// kept only when amg_keep_level() says so (the coarsening guard, min_reduction), decided right after the aggregation.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -116,6 +126,60 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_prolong_kernel(int64_t n, con
     x[i] = x[i] + t;
 }
 
+// Row u.row of a transfer operator M (R_l or P_l) times `in`, sweep_row's row sum.  Every lane of the wave calls this
+// together.  `out` is never gathered: the prolongation updates it in place.
+template <int MODE>
+__device__ __forceinline__ void transfer_row(const Unit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val, double scale,
+                                             const double *__restrict__ in, double *__restrict__ out)
+{
+    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg), G = 1 << gs;
+    const int lane = 4 * u.q + quad;
+    const bool writer = u.row >= 0 && lane == 0;
+    const double xi = writer && MODE == AMG_PROLONG ? out[u.row] : 0.0; // travels with the first entries, as in sweep_row
+    double s = 0.0;
+    if (u.row >= 0)
+        for (int64_t e = (int64_t)u.beg + lane; e < u.end; e += G) s = __builtin_fma(val[e], in[colidx[e]], s);
+    const double f4 = fold_sum<4>(s);
+    double f16 = f4 + lane_partner<4>(f4);
+    f16 += lane_partner<8>(f16);
+    double f64 = f16 + lane_partner<16>(f16);
+    f64 += lane_partner<32>(f64);
+    if (writer) {
+        const double si = gs == 2 ? f4 : gs == 4 ? f16 : f64;
+        if constexpr (MODE == AMG_RESTRICT) {
+            out[u.row] = si;
+        } else {
+            const double t = scale * si;
+            out[u.row] = xi + t;
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(AMG_THREADS) void amg_transfer_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ colidx,
+                                                                   const double *__restrict__ val, double scale, const double *__restrict__ in,
+                                                                   double *__restrict__ out)
+{
+    transfer_row<MODE>(wide_unit<AMG_THREADS>(0, count, units, NO_UNIT), threadIdx.x & 3, colidx, val, scale, in, out);
+}
+
+// t for every stored entry of A_l, over the sweep's units: the row's G(p) lanes take the entries l, l + G, ...; every lane
+// forms q_i itself (one address a row).  No lane talks to another, so a pad's lanes leave at once.
+__global__ __launch_bounds__(AMG_THREADS) void amg_pvalues_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ dpos,
+                                                                  const double *__restrict__ val, double omega_p, double *__restrict__ t)
+{
+    const Unit u = wide_unit<AMG_THREADS>(0, count, units, NO_UNIT);
+    if (u.row < 0) return;
+    const int G = 1 << sptrsv_group_shift((int64_t)u.end - u.beg);
+    const int lane = 4 * u.q + (threadIdx.x & 3);
+    const int64_t dp = dpos[u.row];
+    const double q = omega_p / val[dp];
+    for (int64_t e = (int64_t)u.beg + lane; e < u.end; e += G) {
+        const double prod = q * val[e];
+        t[e] = e == dp ? 1.0 - prod : -prod;
+    }
+}
+
 // wd_i = omega / a_ii (Jacobi) or omega / sum_e |a_ie| (l1, sequentially in stored order from +0).  A diagonal that is
 // not finite and > 0 is reported as (level, row) in *flag: the least such pair, whichever thread finds it first -- an
 // integer minimum is the same in every order.
@@ -148,9 +212,19 @@ struct AmgLevel {
     int32_t *dpos = nullptr, *agg = nullptr, *aggptr = nullptr, *members = nullptr;
     double *wd = nullptr, *x[2] = {nullptr, nullptr}, *res = nullptr, *b = nullptr, *own_val = nullptr;
     size_t bytes = 0;
+    // a smoothed level above the coarsest: `coo` makes P_l; R_l = P_l^T; ap = A_l P_l, rap = R_l ap = A_{l+1}
+    void *ap = nullptr, *rap = nullptr;
+    int64_t nnz_p = 0, nnz_ap = 0, p_units = 0, r_units = 0;
+    const int32_t *p_rowptr = nullptr, *p_colidx = nullptr;                 // the COO plan's
+    int32_t *r_rowptr = nullptr, *r_colidx = nullptr, *r_perm = nullptr; // tbuf: r_rowptr | r_colidx | r_perm | P's units | R's units
+    Unit *d_p_units = nullptr, *d_r_units = nullptr;
+    double *p_val = nullptr, *r_val = nullptr, *ap_val = nullptr;           // tval: p_val | r_val | ap_val
+    DeviceBuffer tbuf, ubuf, tval;
     ~AmgLevel()
     {
         if (coo) sblas_hip_coo_plan_destroy(coo);
+        if (ap) sblas_hip_spgemm_plan_destroy(ap);
+        if (rap) sblas_hip_spgemm_plan_destroy(rap);
     }
 };
 
@@ -160,8 +234,13 @@ struct AmgPlan {
     const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
     double theta = 0.0;
     uint32_t seed = 0;
+    int prolongator = SBLAS_AMG_PLAIN;
+    double omega_p = 0.0, min_reduction = 0.0;
     std::vector<std::unique_ptr<AmgLevel>> lv;
-    DeviceBuffer block; // the flag word
+    DeviceBuffer block, tscratch; // the flag word; a smoothed plan's t, sized by the level with the most entries
+    double *t = nullptr;
+    size_t t_bytes = 0;
+    bool smoothed() const { return prolongator == SBLAS_AMG_SMOOTHED; }
     unsigned long long *flag = nullptr;
     // setup's
     bool ready = false;
@@ -179,6 +258,37 @@ void launch_sweep(hipStream_t s, const AmgLevel &L, int mode, const double *b, c
         amg_sweep_kernel<MODE_SWEEP><<<wide_grid(4 * L.units, AMG_THREADS), AMG_THREADS, 0, s>>>(L.units, L.d_units, L.colidx, L.val, L.wd, b, x, y);
 }
 
+void launch_restrict(hipStream_t s, const AmgPlan &p, const AmgLevel &L, const double *res, double *bc)
+{
+    if (p.smoothed())
+        amg_transfer_kernel<AMG_RESTRICT><<<wide_grid(4 * L.r_units, AMG_THREADS), AMG_THREADS, 0, s>>>(L.r_units, L.d_r_units, L.r_colidx, L.r_val, 0.0, res, bc);
+    else
+        amg_restrict_kernel<<<grid_of(L.n_coarse), AMG_THREADS, 0, s>>>(L.n_coarse, L.aggptr, L.members, res, bc);
+}
+
+void launch_prolong(hipStream_t s, const AmgPlan &p, const AmgLevel &L, double scale, const double *e, double *x)
+{
+    if (p.smoothed())
+        amg_transfer_kernel<AMG_PROLONG><<<wide_grid(4 * L.p_units, AMG_THREADS), AMG_THREADS, 0, s>>>(L.p_units, L.d_p_units, L.p_colidx, L.p_val, scale, e, x);
+    else
+        amg_prolong_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, L.agg, scale, e, x);
+}
+
+void launch_pvalues(hipStream_t s, const AmgLevel &L, double omega_p, const double *val, double *t)
+{
+    amg_pvalues_kernel<<<wide_grid(4 * L.units, AMG_THREADS), AMG_THREADS, 0, s>>>(L.units, L.d_units, L.dpos, val, omega_p, t);
+}
+
+// A smoothed level's numeric chain after its t: P's values, R's, A P and R (A P) into `coarse`.  Launches only.
+int smoothed_values(hipStream_t s, const AmgPlan &p, const AmgLevel &L, const double *val, const double *t, double *coarse)
+{
+    int rc = sblas_hip_coo_plan_assemble(L.coo, s, t, L.p_val);
+    if (rc == SBLAS_OK) rc = sblas_hip_gather_f64(p.dev, s, L.nnz_p, L.r_perm, L.p_val, L.r_val);
+    if (rc == SBLAS_OK) rc = sblas_hip_spgemm_plan_numeric(L.ap, s, val, L.p_val, L.ap_val);
+    if (rc == SBLAS_OK) rc = sblas_hip_spgemm_plan_numeric(L.rap, s, L.r_val, L.ap_val, coarse);
+    return rc;
+}
+
 // the walk of amg.h as launches; level 0 reads the caller's r and ends in the caller's z
 struct DeviceOps {
     const AmgPlan *p;
@@ -193,12 +303,11 @@ struct DeviceOps {
     void restrict_to(int l)
     {
         const AmgLevel &L = *p->lv[(size_t)l];
-        amg_restrict_kernel<<<grid_of(L.n_coarse), AMG_THREADS, 0, s>>>(L.n_coarse, L.aggptr, L.members, L.res, p->lv[(size_t)l + 1]->b);
+        launch_restrict(s, *p, L, L.res, p->lv[(size_t)l + 1]->b);
     }
     void prolong(int l, int dst)
     {
-        const AmgLevel &L = *p->lv[(size_t)l];
-        amg_prolong_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, L.agg, p->scale, x(l + 1, AMG_RESULT_BUFFER), x(l, dst));
+        launch_prolong(s, *p, *p->lv[(size_t)l], p->scale, x(l + 1, AMG_RESULT_BUFFER), x(l, dst));
     }
 };
 
@@ -219,9 +328,20 @@ extern "C" {
 int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
                               double theta, int64_t coarse_max, int max_levels, uint32_t seed, void **plan_out, int64_t *bad_row)
 {
+    return sblas_hip_amg_plan_create_ex(dev, stream, n, nnz, rowptr, colidx, val, theta, coarse_max, max_levels, seed, SBLAS_AMG_PLAIN, 0.0, 0.0,
+                                        plan_out, bad_row);
+}
+
+int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                 double theta, int64_t coarse_max, int max_levels, uint32_t seed, int prolongator, double prolong_omega,
+                                 double min_reduction, void **plan_out, int64_t *bad_row)
+{
     if (bad_row) *bad_row = -1;
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
+    if (prolongator != SBLAS_AMG_PLAIN && prolongator != SBLAS_AMG_SMOOTHED) return SBLAS_E_INVALID;
+    const bool smoothed = prolongator == SBLAS_AMG_SMOOTHED;
+    if ((smoothed && !amg_prolong_omega_ok(prolong_omega)) || !amg_min_reduction_ok(min_reduction)) return SBLAS_E_INVALID;
     if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
     if (!amg_theta_ok(theta) || (theta > 0.0 && !val)) return SBLAS_E_INVALID;
     if (coarse_max < 0 || max_levels < 0 || max_levels > AMG_LEVEL_CAP) return SBLAS_E_INVALID;
@@ -230,6 +350,7 @@ int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, con
     if (max_levels == 0) max_levels = AMG_MAX_LEVELS;
     std::unique_ptr<AmgPlan> p(new AmgPlan);
     p->dev = resolve_device(dev), p->n = n, p->nnz = nnz, p->rowptr = rowptr, p->colidx = colidx, p->theta = theta, p->seed = seed;
+    p->prolongator = prolongator, p->omega_p = smoothed ? prolong_omega : 0.0, p->min_reduction = min_reduction;
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -252,7 +373,9 @@ int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, con
     if (hipMemsetAsync(p->flag, 0xff, 256, s) != hipSuccess) return SBLAS_E_HIP;
 
     const int32_t *d_rowptr = rowptr, *d_colidx = colidx;
-    int64_t nl = n, nnzl = nnz;
+    const double *d_val = val; // theta > 0 on a smoothed plan: the level's values on the device, for the numeric chain
+    int64_t nl = n, nnzl = nnz, nnz_most = nnz;
+    DeviceBuffer val_here, val_next; // such a level's values, and the next one's
     for (int l = 0;; ++l) {
         std::unique_ptr<AmgLevel> L(new AmgLevel);
         L->n = nl, L->nnz = nnzl, L->rowptr = d_rowptr, L->colidx = d_colidx;
@@ -269,7 +392,9 @@ int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, con
             agg.resize((size_t)nl), members.resize((size_t)nl);
             const int64_t nc = amg_aggregate(nl, h_rowptr.data(), h_colidx.data(), by_value ? h_val.data() : nullptr, theta, seed, (uint32_t)l,
                                              agg.data(), aggptr, members.data());
-            if (nc < nl) { // a level that does not reduce n is discarded
+            if (smoothed && amg_keep_level(nl, nc, min_reduction)) {
+                L->n_coarse = nc; // the transfer operators and the products: after this level's own arrays are on the device
+            } else if (!smoothed && amg_keep_level(nl, nc, min_reduction)) { // a level that does not reduce n (enough) is discarded
                 std::vector<int32_t> trow((size_t)nnzl), tcol((size_t)nnzl);
                 for (int64_t i = 0; i < nl; ++i)
                     for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) trow[(size_t)e] = agg[(size_t)i], tcol[(size_t)e] = agg[(size_t)h_colidx[e]];
@@ -333,10 +458,100 @@ int sblas_hip_amg_plan_create(int dev, void *stream, int64_t n, int64_t nnz, con
         if (!last) L->res = take(vec);
         if (l > 0) L->own_val = take(vals), L->val = L->own_val;
         L->bytes = ib + db;
+        if (smoothed && !last) {
+            const int64_t nc = L->n_coarse;
+            // P_l: the COO plan of (row(e), agg[col(e)]) in stored order
+            std::vector<int32_t> trow((size_t)nnzl), tcol((size_t)nnzl);
+            for (int64_t i = 0; i < nl; ++i)
+                for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) trow[(size_t)e] = (int32_t)i, tcol[(size_t)e] = agg[(size_t)h_colidx[e]];
+            DeviceBuffer trip;
+            size_t tb = 0;
+            Segment tseg[2] = {Segment(trow), Segment(tcol)};
+            if (upload_segments(trip, p->dev, s, tseg, 2, &tb) != hipSuccess) return SBLAS_E_HIP;
+            rc = sblas_hip_coo_plan_create(p->dev, s, nl, nc, nnzl, trip.at<int32_t>(), trip.at<int32_t>(tseg[1].offset), SBLAS_COO_SUM, &L->coo);
+            if (rc != SBLAS_OK) return rc;
+            int64_t ci[8], gi[12];
+            sblas_hip_coo_plan_info(L->coo, ci);
+            sblas_hip_coo_plan_csr(L->coo, &L->p_rowptr, &L->p_colidx, nullptr, nullptr);
+            const int64_t nnzp = L->nnz_p = ci[3];
+            L->bytes += (size_t)ci[6];
+            // the units of P's rows, and of R's once its row pointer is known; R_l = P_l^T by the device transpose
+            std::vector<int32_t> hp_rowptr, hp_colidx, hr_rowptr((size_t)nc + 1);
+            int64_t pbad = -1;
+            if (fetch_structure(s, nl, nnzp, L->p_rowptr, L->p_colidx, hp_rowptr, hp_colidx, &pbad) != SBLAS_OK) return SBLAS_E_HIP;
+            const size_t i_rp = ((size_t)nc + 1 + 3) / 4 * 4, i_e = ((size_t)nnzp + 3) / 4 * 4; // int32 counts, 16-byte steps
+            DeviceBuffer tws;
+            const size_t ws_bytes = sblas_hip_csr_transpose_workspace(nl, nc, nnzp);
+            if (tws.alloc(p->dev, ws_bytes ? ws_bytes : 16) != hipSuccess) return SBLAS_E_HIP;
+            const size_t rbytes = (i_rp + 2 * i_e) * 4 + 16; // r_rowptr | r_colidx | r_perm
+            if (L->tbuf.alloc(p->dev, rbytes) != hipSuccess) return SBLAS_E_HIP;
+            L->r_rowptr = L->tbuf.at<int32_t>(), L->r_colidx = L->tbuf.at<int32_t>(i_rp * 4), L->r_perm = L->tbuf.at<int32_t>((i_rp + i_e) * 4);
+            rc = sblas_hip_csr_transpose_f64_i32(p->dev, s, nl, nc, nnzp, L->p_rowptr, L->p_colidx, nullptr, L->r_rowptr, L->r_colidx, nullptr,
+                                                 L->r_perm, tws.at<char>(), ws_bytes);
+            if (rc != SBLAS_OK) return rc;
+            if (hipMemcpyAsync(hr_rowptr.data(), L->r_rowptr, ((size_t)nc + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess)
+                return SBLAS_E_HIP;
+            std::vector<int32_t> zero_p((size_t)nl, 0), zero_r((size_t)nc, 0);
+            LevelOrder op, orr;
+            std::vector<Unit> p_units, r_units;
+            const auto p_unit = [&](int32_t i, int32_t q) { return Unit{i, hp_rowptr[(size_t)i], hp_rowptr[(size_t)i + 1], q}; };
+            const auto r_unit = [&](int32_t i, int32_t q) { return Unit{i, hr_rowptr[(size_t)i], hr_rowptr[(size_t)i + 1], q}; };
+            level_pack(nl, hp_rowptr.data(), zero_p.data(), 1, p_unit, NO_UNIT, op, p_units);
+            level_pack(nc, hr_rowptr.data(), zero_r.data(), 1, r_unit, NO_UNIT, orr, r_units);
+            L->p_units = (int64_t)p_units.size(), L->r_units = (int64_t)r_units.size();
+            Segment useg[2] = {Segment(p_units), Segment(r_units)};
+            size_t ub = 0;
+            if (upload_segments(L->ubuf, p->dev, s, useg, 2, &ub) != hipSuccess) return SBLAS_E_HIP;
+            L->d_p_units = L->ubuf.at<Unit>(), L->d_r_units = L->ubuf.at<Unit>(useg[1].offset);
+            // the products' plans: A_l P_l, then R_l (A_l P_l); a product too large for int32 is refused there
+            rc = sblas_hip_spgemm_plan_create(p->dev, s, nl, nl, nc, d_rowptr, d_colidx, L->p_rowptr, L->p_colidx, SBLAS_SPGEMM_AUTO, 0, &L->ap);
+            if (rc != SBLAS_OK) return rc;
+            const int32_t *ap_rp = nullptr, *ap_ci = nullptr, *c_rp = nullptr, *c_ci = nullptr;
+            sblas_hip_spgemm_plan_info(L->ap, gi);
+            sblas_hip_spgemm_plan_csr(L->ap, &ap_rp, &ap_ci);
+            L->nnz_ap = gi[3], L->bytes += (size_t)gi[10];
+            rc = sblas_hip_spgemm_plan_create(p->dev, s, nc, nl, nc, L->r_rowptr, L->r_colidx, ap_rp, ap_ci, SBLAS_SPGEMM_AUTO, 0, &L->rap);
+            if (rc != SBLAS_OK) return rc;
+            sblas_hip_spgemm_plan_info(L->rap, gi);
+            sblas_hip_spgemm_plan_csr(L->rap, &c_rp, &c_ci);
+            const int64_t nnzc = gi[3];
+            L->bytes += (size_t)gi[10];
+            int64_t cbad = -1;
+            if (fetch_structure(s, nc, nnzc, c_rp, c_ci, c_rowptr, c_colidx, &cbad) != SBLAS_OK) return SBLAS_E_HIP;
+            const size_t v_p = ((size_t)nnzp * 8 + 255) / 256 * 256, v_ap = ((size_t)L->nnz_ap * 8 + 255) / 256 * 256;
+            if (L->tval.alloc(p->dev, 2 * v_p + v_ap + 256) != hipSuccess) return SBLAS_E_HIP;
+            L->p_val = L->tval.at<double>(), L->r_val = L->tval.at<double>(v_p), L->ap_val = L->tval.at<double>(2 * v_p);
+            L->bytes += rbytes + ub + 2 * v_p + v_ap + 256;
+            if (by_value) { // the coarse values of the next level's strength test: the numeric chain, once, on the given values
+                DeviceBuffer t_tmp;
+                if (t_tmp.alloc(p->dev, (size_t)nnzl * 8 + 256) != hipSuccess || val_next.alloc(p->dev, (size_t)nnzc * 8 + 256) != hipSuccess)
+                    return SBLAS_E_HIP;
+                launch_pvalues(s, *L, p->omega_p, d_val, t_tmp.at<double>());
+                rc = smoothed_values(s, *p, *L, d_val, t_tmp.at<double>(), val_next.at<double>());
+                if (rc != SBLAS_OK) return rc;
+                c_val.resize((size_t)nnzc);
+                if (hipMemcpyAsync(c_val.data(), val_next.at<double>(), (size_t)nnzc * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess)
+                    return SBLAS_E_HIP;
+            }
+            d_rowptr = c_rp, d_colidx = c_ci;
+            if (nnzc > nnz_most) nnz_most = nnzc;
+        }
         p->lv.push_back(std::move(L));
         if (last) break;
         nl = p->lv.back()->n_coarse, nnzl = (int64_t)c_colidx.size();
         h_rowptr.swap(c_rowptr), h_colidx.swap(c_colidx), h_val.swap(c_val);
+        if (smoothed && by_value) { // the next level's values stay on the device for its own chain
+            DeviceBuffer done(std::move(val_here));
+            val_here = std::move(val_next);
+            d_val = val_here.at<double>();
+        }
+    }
+    if (smoothed) {
+        p->t_bytes = (size_t)nnz_most * 8 + 256;
+        if (p->tscratch.alloc(p->dev, p->t_bytes) != hipSuccess) return SBLAS_E_HIP;
+        p->t = p->tscratch.at<double>();
     }
     if (hipStreamSynchronize(s) != hipSuccess) return SBLAS_E_HIP;
     *plan_out = p.release();
@@ -347,7 +562,7 @@ int sblas_hip_amg_plan_info(const void *plan, int64_t out[12])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const AmgPlan *p = static_cast<const AmgPlan *>(plan);
-    int64_t rows = 0, entries = 0, bytes = p->flag ? 256 : 0;
+    int64_t rows = 0, entries = 0, bytes = (p->flag ? 256 : 0) + (int64_t)p->t_bytes;
     for (const auto &L : p->lv) rows += L->n, entries += L->nnz, bytes += (int64_t)L->bytes;
     out[0] = p->n, out[1] = p->nnz, out[2] = p->levels(), out[3] = p->nu, out[4] = p->coarse_sweeps;
     out[5] = sblas_amg_launches(p->levels(), p->nu, p->coarse_sweeps);
@@ -362,6 +577,24 @@ int sblas_hip_amg_plan_level(const void *plan, int level, int64_t sizes[4], cons
     const AmgLevel &L = *p->lv[(size_t)level];
     sizes[0] = L.n, sizes[1] = L.nnz, sizes[2] = L.n_coarse, sizes[3] = L.units;
     ptrs[0] = L.rowptr, ptrs[1] = L.colidx, ptrs[2] = L.val, ptrs[3] = L.wd, ptrs[4] = L.agg, ptrs[5] = L.aggptr, ptrs[6] = L.members;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_transfer(const void *plan, int level, int64_t sizes[3], const void *ptrs[6])
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !sizes || !ptrs || !p->smoothed() || level < 0 || level + 1 >= p->levels()) return SBLAS_E_INVALID;
+    const AmgLevel &L = *p->lv[(size_t)level];
+    sizes[0] = L.n, sizes[1] = L.n_coarse, sizes[2] = L.nnz_p;
+    ptrs[0] = L.p_rowptr, ptrs[1] = L.p_colidx, ptrs[2] = L.p_val, ptrs[3] = L.r_rowptr, ptrs[4] = L.r_colidx, ptrs[5] = L.r_val;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_options(const void *plan, double out[4])
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !out) return SBLAS_E_INVALID;
+    out[0] = (double)p->prolongator, out[1] = p->omega_p, out[2] = p->min_reduction, out[3] = 0.0;
     return SBLAS_OK;
 }
 
@@ -402,7 +635,9 @@ int sblas_hip_amg_plan_setup(void *plan, void *stream, const double *val, int sm
         AmgLevel &L = *p->lv[(size_t)l];
         amg_wd_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, l, smoother, omega, L.rowptr, L.dpos, L.val, L.wd, p->flag);
         if (l + 1 < p->levels()) {
-            const int rc = sblas_hip_coo_plan_assemble(L.coo, s, L.val, p->lv[(size_t)l + 1]->own_val);
+            double *coarse = p->lv[(size_t)l + 1]->own_val;
+            if (p->smoothed()) launch_pvalues(s, L, p->omega_p, L.val, p->t);
+            const int rc = p->smoothed() ? smoothed_values(s, *p, L, L.val, p->t, coarse) : sblas_hip_coo_plan_assemble(L.coo, s, L.val, coarse);
             if (rc != SBLAS_OK) return rc;
         }
     }
@@ -451,7 +686,8 @@ int sblas_hip_amg_restrict_f64(const void *plan, void *stream, int level, const 
 {
     const AmgLevel *L = level_of(plan, level, false);
     if (!L || L->n_coarse == 0 || !res || !bc) return SBLAS_E_INVALID;
-    amg_restrict_kernel<<<grid_of(L->n_coarse), AMG_THREADS, 0, (hipStream_t)stream>>>(L->n_coarse, L->aggptr, L->members, res, bc);
+    if (static_cast<const AmgPlan *>(plan)->smoothed() && (!static_cast<const AmgPlan *>(plan)->ready || res == bc)) return SBLAS_E_INVALID; // R's values are setup's
+    launch_restrict((hipStream_t)stream, *static_cast<const AmgPlan *>(plan), *L, res, bc);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }
 
@@ -459,7 +695,18 @@ int sblas_hip_amg_prolong_f64(const void *plan, void *stream, int level, double 
 {
     const AmgLevel *L = level_of(plan, level, false);
     if (!L || L->n_coarse == 0 || !e || !x) return SBLAS_E_INVALID;
-    amg_prolong_kernel<<<grid_of(L->n), AMG_THREADS, 0, (hipStream_t)stream>>>(L->n, L->agg, scale, e, x);
+    if (static_cast<const AmgPlan *>(plan)->smoothed() && (!static_cast<const AmgPlan *>(plan)->ready || e == x)) return SBLAS_E_INVALID; // P's values are setup's
+    launch_prolong((hipStream_t)stream, *static_cast<const AmgPlan *>(plan), *L, scale, e, x);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_pvalues_f64(const void *plan, void *stream, int level, const double *val, double *t)
+{
+    const AmgLevel *L = level_of(plan, level, false);
+    if (!L || !static_cast<const AmgPlan *>(plan)->smoothed()) return SBLAS_E_INVALID;
+    if (L->nnz == 0) return SBLAS_OK;
+    if (!val || !t || overlap(val, t, L->nnz)) return SBLAS_E_INVALID;
+    launch_pvalues((hipStream_t)stream, *L, static_cast<const AmgPlan *>(plan)->omega_p, val, t);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }
 

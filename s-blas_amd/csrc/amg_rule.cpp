@@ -1,10 +1,13 @@
 // amg_rule.cpp -- the host rule of the aggregation AMG plan (amg.hip): the pinned aggregation of one
 // level, the smoother's diagonal, the launch count and the whole V-cycle restated in plain C++.  Pure functions of host
 // arrays; no GPU call in this file, so it is testable on a CPU box (and under a host sanitizer).
+// For smoothed aggregation it also holds the coarsening guard, the prolongator P in the pinned order (the
+// COO sum of (row(e), agg[col(e)], t_e)), the transfers' row product in lane order and the walk with general P and R.
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <algorithm>
+#include <utility>
 #include <vector>
 #include "../../include/sblas_hip.h"
 #include "amg.h"
@@ -143,9 +146,151 @@ struct RefOps {
     }
 };
 
+// the rectangular row product of the smoothed plan's transfers: row_sum over every row of M
+void transfer_rows(int mode, int64_t rows, const int32_t *rowptr, const int32_t *colidx, const double *val, double scale, const double *in,
+                   double *out)
+{
+    for (int64_t i = 0; i < rows; ++i) {
+        const double s = row_sum(colidx, val, rowptr[i], rowptr[i + 1], in);
+        if (mode == AMG_RESTRICT) {
+            out[i] = s;
+        } else {
+            const double t = scale * s;
+            out[i] = out[i] + t;
+        }
+    }
+}
+
+// the walk's transfers with general P and R; everything else is RefOps'
+struct RefOpsSa : RefOps {
+    const int32_t *const *p_rowptr, *const *p_colidx, *const *r_rowptr, *const *r_colidx;
+    const double *const *p_val, *const *r_val;
+    void restrict_to(int l)
+    {
+        RefLevel &L = lv[(size_t)l], &Cs = lv[(size_t)l + 1];
+        transfer_rows(AMG_RESTRICT, Cs.n, r_rowptr[l], r_colidx[l], r_val[l], 0.0, L.res.data(), Cs.own_b.data());
+    }
+    void prolong(int l, int dst)
+    {
+        RefLevel &L = lv[(size_t)l], &Cs = lv[(size_t)l + 1];
+        transfer_rows(AMG_PROLONG, L.n, p_rowptr[l], p_colidx[l], p_val[l], scale, Cs.x[AMG_RESULT_BUFFER], L.x[dst]);
+    }
+};
+
+// the vectors of the reference levels: level 0 reads the caller's r and ends in the caller's z
+void ref_levels(std::vector<RefLevel> &lv, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
+                const double *const *wd, const double *r, double *z)
+{
+    const int levels = (int)lv.size();
+    for (int l = 0; l < levels; ++l) {
+        RefLevel &L = lv[(size_t)l];
+        const bool last = l + 1 == levels;
+        L.n = n[l], L.rowptr = rowptr[l], L.colidx = colidx[l], L.val = val[l], L.wd = wd[l];
+        L.agg = L.aggptr = L.members = nullptr;
+        L.own_x[0].assign((size_t)L.n, 0.0), L.res.assign(last ? 0 : (size_t)L.n, 0.0);
+        L.x[0] = L.own_x[0].data();
+        if (l == 0) {
+            L.b = r, L.x[1] = z;
+        } else {
+            L.own_b.assign((size_t)L.n, 0.0), L.own_x[1].assign((size_t)L.n, 0.0);
+            L.b = L.own_b.data(), L.x[1] = L.own_x[1].data();
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
+
+int sblas_amg_keep_level(int64_t n, int64_t n_next, double min_reduction)
+{
+    if (n < 0 || n_next < 0 || !amg_min_reduction_ok(min_reduction)) return -1;
+    return amg_keep_level(n, n_next, min_reduction) ? 1 : 0;
+}
+
+int sblas_amg_prolongator_ref(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, const int32_t *agg, int64_t n_agg,
+                              double prolong_omega, int32_t *p_rowptr, int32_t *p_colidx, double *p_val, int64_t *p_nnz, int64_t *bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (p_nnz) *p_nnz = 0;
+    if (n < 0 || n > INT_MAX || n_agg < 0 || n_agg > INT_MAX || !rowptr || !p_rowptr || !p_nnz) return SBLAS_E_INVALID;
+    if (!amg_prolong_omega_ok(prolong_omega)) return SBLAS_E_INVALID;
+    if (n > 0 && (!agg || (rowptr[n] > 0 && (!colidx || !val)))) return SBLAS_E_INVALID;
+    for (int64_t i = 0; i < n; ++i)
+        if (agg[i] < 0 || agg[i] >= n_agg) return SBLAS_E_INVALID;
+    std::vector<std::pair<int32_t, double>> row; // (agg[col(e)], t_e) in stored order
+    int64_t count = 0;
+    p_rowptr[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        int64_t dp = -1;
+        for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            if (colidx[e] < 0 || colidx[e] >= n) {
+                if (bad_row) *bad_row = i;
+                return SBLAS_E_INVALID;
+            }
+            if (colidx[e] == i && dp < 0) dp = e;
+        }
+        if (dp < 0) {
+            if (bad_row) *bad_row = i;
+            return SBLAS_E_INVALID;
+        }
+        const double q = prolong_omega / val[dp];
+        row.clear();
+        for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            const double prod = q * val[e];
+            row.emplace_back(agg[colidx[e]], e == dp ? 1.0 - prod : -prod);
+        }
+        // the COO plan's order: by column, equal columns in input order, each run added left to right
+        std::stable_sort(row.begin(), row.end(), [](const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) { return a.first < b.first; });
+        for (size_t k = 0; k < row.size();) {
+            double v = row[k].second;
+            size_t j = k + 1;
+            for (; j < row.size() && row[j].first == row[k].first; ++j) v = v + row[j].second;
+            if (p_colidx) p_colidx[count] = row[k].first;
+            if (p_val) p_val[count] = v;
+            ++count, k = j;
+        }
+        if (count > INT_MAX) return SBLAS_E_INVALID;
+        p_rowptr[i + 1] = (int32_t)count;
+    }
+    *p_nnz = count;
+    return SBLAS_OK;
+}
+
+int sblas_amg_transfer_ref(int mode, int64_t rows, const int32_t *rowptr, const int32_t *colidx, const double *val, double scale,
+                           const double *in, double *out)
+{
+    if ((mode != AMG_RESTRICT && mode != AMG_PROLONG) || rows < 0 || rows > INT_MAX || !rowptr) return SBLAS_E_INVALID;
+    if (rows > 0 && (!out || out == in || (rowptr[rows] > 0 && (!colidx || !val || !in)))) return SBLAS_E_INVALID;
+    transfer_rows(mode, rows, rowptr, colidx, val, scale, in, out);
+    return SBLAS_OK;
+}
+
+int sblas_amg_cycle_sa_ref(int levels, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
+                           const double *const *wd, const int32_t *const *p_rowptr, const int32_t *const *p_colidx, const double *const *p_val,
+                           const int32_t *const *r_rowptr, const int32_t *const *r_colidx, const double *const *r_val, int nu,
+                           int coarse_sweeps, double coarse_scale, const double *r, double *z)
+{
+    if (!amg_cycle_args_ok(levels, nu, coarse_sweeps)) return SBLAS_E_INVALID;
+    if (levels == 0) return SBLAS_OK;
+    if (!n || !rowptr || !colidx || !val || !wd) return SBLAS_E_INVALID;
+    if (levels > 1 && (!p_rowptr || !p_colidx || !p_val || !r_rowptr || !r_colidx || !r_val)) return SBLAS_E_INVALID;
+    for (int l = 0; l < levels; ++l) {
+        if (n[l] < 0 || n[l] > INT_MAX || !rowptr[l]) return SBLAS_E_INVALID;
+        if (n[l] > 0 && (!wd[l] || (rowptr[l][n[l]] > 0 && (!colidx[l] || !val[l])))) return SBLAS_E_INVALID;
+        if (l + 1 < levels) {
+            if (!p_rowptr[l] || !r_rowptr[l]) return SBLAS_E_INVALID;
+            if (p_rowptr[l][n[l]] > 0 && (!p_colidx[l] || !p_val[l])) return SBLAS_E_INVALID;
+            if (n[l + 1] >= 0 && r_rowptr[l][n[l + 1]] > 0 && (!r_colidx[l] || !r_val[l])) return SBLAS_E_INVALID;
+        }
+    }
+    if (n[0] > 0 && (!r || !z || r == z)) return SBLAS_E_INVALID;
+    std::vector<RefLevel> lv((size_t)levels);
+    ref_levels(lv, n, rowptr, colidx, val, wd, r, z);
+    RefOpsSa ops{{lv, coarse_scale}, p_rowptr, p_colidx, r_rowptr, r_colidx, p_val, r_val};
+    amg_cycle(levels, nu, coarse_sweeps, ops);
+    return SBLAS_OK;
+}
 
 int sblas_amg_limits(int64_t out[8])
 {

@@ -68,6 +68,11 @@ EXPORTS = [
     "sblas_hip_amg_plan_apply", "sblas_hip_amg_plan_check", "sblas_hip_amg_plan_speaks_for", "sblas_hip_amg_plan_destroy",
     "sblas_hip_amg_sweep_f64", "sblas_hip_amg_restrict_f64", "sblas_hip_amg_prolong_f64",
 ]
+# what include/sblas_hip_amg_sa.h declares (smoothed aggregation); kept apart from EXPORTS, which names sblas_hip.h's own
+EXPORTS_AMG_SA = [
+    "sblas_amg_keep_level", "sblas_amg_prolongator_ref", "sblas_amg_transfer_ref", "sblas_amg_cycle_sa_ref",
+    "sblas_hip_amg_plan_create_ex", "sblas_hip_amg_plan_transfer", "sblas_hip_amg_plan_options", "sblas_hip_amg_pvalues_f64",
+]
 
 
 class SblasError(RuntimeError):
@@ -408,6 +413,23 @@ def lib():
     L.sblas_hip_amg_restrict_f64.argtypes = [vp, vp, C.c_int, vp, vp]
     L.sblas_hip_amg_prolong_f64.restype = C.c_int
     L.sblas_hip_amg_prolong_f64.argtypes = [vp, vp, C.c_int, f64, vp, vp]
+    L.sblas_amg_keep_level.restype = C.c_int
+    L.sblas_amg_keep_level.argtypes = [i64, i64, f64]
+    L.sblas_amg_prolongator_ref.restype = C.c_int
+    L.sblas_amg_prolongator_ref.argtypes = [i64, vp, vp, vp, vp, i64, f64, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_amg_transfer_ref.restype = C.c_int
+    L.sblas_amg_transfer_ref.argtypes = [C.c_int, i64, vp, vp, vp, f64, vp, vp]
+    L.sblas_amg_cycle_sa_ref.restype = C.c_int
+    L.sblas_amg_cycle_sa_ref.argtypes = [C.c_int, C.POINTER(i64)] + [C.POINTER(vp)] * 10 + [C.c_int, C.c_int, f64, vp, vp]
+    L.sblas_hip_amg_plan_create_ex.restype = C.c_int
+    L.sblas_hip_amg_plan_create_ex.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, i64, C.c_int, C.c_uint32, C.c_int, f64, f64,
+                                               C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_amg_plan_transfer.restype = C.c_int
+    L.sblas_hip_amg_plan_transfer.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(vp)]
+    L.sblas_hip_amg_plan_options.restype = C.c_int
+    L.sblas_hip_amg_plan_options.argtypes = [vp, C.POINTER(f64)]
+    L.sblas_hip_amg_pvalues_f64.restype = C.c_int
+    L.sblas_hip_amg_pvalues_f64.argtypes = [vp, vp, C.c_int, vp, vp]
     _lib = L
     return L
 
@@ -903,6 +925,93 @@ def amg_cycle_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
                                     column("wd", np.float64, k), column("agg", np.int32, k - 1), column("aggptr", np.int32, k - 1),
                                     column("members", np.int32, k - 1), int(nu), int(coarse_sweeps), float(coarse_scale),
                                     r.ctypes.data if len(r) else None, z.ctypes.data), "sblas_amg_cycle_ref")
+    return z[:len(r)]
+
+
+# Smoothed aggregation: the prolongators and the modes of the transfer row product (SBLAS_AMG_*)
+AMG_PROLONGATORS = {"plain": 0, "smoothed": 1}
+AMG_TRANSFER_MODES = {"restrict": 0, "prolong": 1}
+AMG_PROLONG_OMEGA = 2.0 / 3.0
+AMG_SMOOTHED_MIN_REDUCTION = 0.2
+
+
+def amg_keep_level(n, n_next, min_reduction=0.0):
+    """The coarsening guard (sblas_amg_keep_level): a level of n rows whose aggregation leaves n_next is kept when
+    n_next < n and float(n_next) <= (1.0 - min_reduction) * float(n), the product rounded once."""
+    rc = lib().sblas_amg_keep_level(int(n), int(n_next), float(min_reduction))
+    if rc < 0:
+        raise SblasError("sblas_amg_keep_level refused its arguments: sizes >= 0, min_reduction in [0, 1)")
+    return bool(rc)
+
+
+def amg_prolongator_ref(n, rowptr, colidx, val, agg, n_agg, prolong_omega=AMG_PROLONG_OMEGA):
+    """The smoothed prolongator on host arrays in the pinned order (sblas_amg_prolongator_ref) -> (p_rowptr, p_colidx,
+    p_val): n rows by n_agg columns, the COO sum of the triplets (row(e), agg[col(e)], t_e)."""
+    rowptr, colidx = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colidx, np.int32)
+    val, agg = np.ascontiguousarray(val, np.float64), np.ascontiguousarray(agg, np.int32)
+    n = int(n)
+    if len(rowptr) != n + 1 or len(agg) != n or len(colidx) != len(val) or (n and rowptr[n] != len(colidx)):
+        raise SblasError("rowptr must have n + 1 entries, agg n, colidx and val rowptr[n]")
+    nnz = len(colidx)
+    prp, pci, pv = np.zeros(n + 1, np.int32), np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1), np.float64)
+    count, bad = C.c_int64(0), C.c_int64(-1)
+    rc = lib().sblas_amg_prolongator_ref(n, rowptr.ctypes.data, colidx.ctypes.data if nnz else None, val.ctypes.data if nnz else None,
+                                         agg.ctypes.data if n else None, int(n_agg), float(prolong_omega), prp.ctypes.data, pci.ctypes.data,
+                                         pv.ctypes.data, C.byref(count), C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_amg_prolongator_ref", rc, bad.value)
+    return prp, pci[:count.value].copy(), pv[:count.value].copy()
+
+
+def amg_transfer_ref(mode, rowptr, colidx, val, x, out=None, scale=1.0):
+    """The transfers' row product in lane order on host arrays (sblas_amg_transfer_ref).  mode "restrict": -> s, the row
+    sums of the CSR (rowptr, colidx, val) on x; "prolong": -> out + scale * s (out is not changed)."""
+    if mode not in AMG_TRANSFER_MODES:
+        raise SblasError("mode must be 'restrict' or 'prolong', not %r" % (mode,))
+    rowptr, colidx = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colidx, np.int32)
+    val, x = np.ascontiguousarray(val, np.float64), np.ascontiguousarray(x, np.float64)
+    rows = len(rowptr) - 1
+    if rows < 0 or len(colidx) != len(val) or (rows and rowptr[rows] != len(colidx)) or (len(colidx) and int(colidx.max()) >= len(x)):
+        raise SblasError("a CSR of len(rowptr) - 1 rows whose columns name entries of x")
+    if mode == "prolong":
+        if out is None or len(out) != rows:
+            raise SblasError("prolong needs out, one entry a row")
+        y = np.array(out, np.float64)
+    else:
+        y = np.zeros(rows)
+    buf = y if rows else np.zeros(1)
+    check(lib().sblas_amg_transfer_ref(AMG_TRANSFER_MODES[mode], rows, rowptr.ctypes.data, colidx.ctypes.data if len(colidx) else None,
+                                       val.ctypes.data if len(val) else None, float(scale), x.ctypes.data if len(x) else None,
+                                       buf.ctypes.data), "sblas_amg_transfer_ref")
+    return y
+
+
+def amg_cycle_sa_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
+    """The V-cycle with general transfer operators in plain C++ on host arrays (sblas_amg_cycle_sa_ref) -> z.  levels: a
+    list of dicts with n, rowptr, colidx, val, wd and, on all but the last, p_rowptr, p_colidx, p_val, r_rowptr, r_colidx,
+    r_val (numpy arrays)."""
+    k = len(levels)
+    if k == 0:
+        return np.zeros(0)
+    keep = []
+
+    def column(name, dtype, upto):
+        arr = (C.c_void_p * k)()
+        for l in range(upto):
+            a = np.ascontiguousarray(levels[l][name], dtype)
+            keep.append(a)
+            arr[l] = a.ctypes.data if a.size else None
+        return arr
+    ns = (C.c_int64 * k)(*[int(L["n"]) for L in levels])
+    r = np.ascontiguousarray(r, np.float64)
+    if len(r) != ns[0]:
+        raise SblasError("r has %d entries for %d rows" % (len(r), ns[0]))
+    z = np.zeros(max(len(r), 1))
+    check(lib().sblas_amg_cycle_sa_ref(k, ns, column("rowptr", np.int32, k), column("colidx", np.int32, k), column("val", np.float64, k),
+                                       column("wd", np.float64, k), column("p_rowptr", np.int32, k - 1), column("p_colidx", np.int32, k - 1),
+                                       column("p_val", np.float64, k - 1), column("r_rowptr", np.int32, k - 1),
+                                       column("r_colidx", np.int32, k - 1), column("r_val", np.float64, k - 1), int(nu), int(coarse_sweeps),
+                                       float(coarse_scale), r.ctypes.data if len(r) else None, z.ctypes.data), "sblas_amg_cycle_sa_ref")
     return z[:len(r)]
 
 
@@ -2301,10 +2410,24 @@ class AmgPlan:
     The plan keeps rowptr and colidx alive and sweeps level 0 on them: do not change them.  setup(val) forms every
     level's values and the smoother on the device and is repeatable; setup and apply allocate nothing inside the library,
     never synchronise and are graph-capturable; check() is the one call that synchronises.  Every bit is pinned
-    (include/sblas_hip.h; amg_cycle_ref restates a cycle on the host).  KrylovPlan and GmresPlan take the plan as precond."""
+    (include/sblas_hip.h; amg_cycle_ref restates a cycle on the host).  KrylovPlan and GmresPlan take the plan as precond.
+    prolongator="smoothed" (sblas_hip_amg_plan_create_ex, include/sblas_hip_amg_sa.h) smooths the prolongator: P = (I -
+    prolong_omega D^-1 A) T over the same aggregates, R = P^T, the coarse matrix R (A P) by two SpGEMM plans, the
+    transfers of a cycle one row-product kernel; transfer(l) shows P and R and amg_cycle_sa_ref restates the cycle.
+    min_reduction in [0, 1) is the coarsening guard (amg_keep_level): a level is kept only when it removes at least that
+    share of the rows; None means 0 (any reduction, as before) for a plain plan and 0.2 for a smoothed one."""
 
-    def __init__(self, n, rowptr, colidx, val=None, theta=0.0, coarse_max=64, max_levels=20, seed=0, stream=None):
+    def __init__(self, n, rowptr, colidx, val=None, theta=0.0, coarse_max=64, max_levels=20, seed=0, stream=None, prolongator="plain",
+                 prolong_omega=AMG_PROLONG_OMEGA, min_reduction=None):
         import torch
+        if prolongator not in AMG_PROLONGATORS:
+            raise SblasError("prolongator must be 'plain' or 'smoothed', not %r" % (prolongator,))
+        if min_reduction is None:                                          # plain: today's rule, any reduction keeps a level
+            min_reduction = AMG_SMOOTHED_MIN_REDUCTION if prolongator == "smoothed" else 0.0
+        if not 0.0 <= float(min_reduction) < 1.0:
+            raise SblasError("min_reduction must be in [0, 1), not %r" % (min_reduction,))
+        if prolongator == "smoothed" and not 0.0 < float(prolong_omega) < float("inf"):
+            raise SblasError("prolong_omega must be positive and finite, not %r" % (prolong_omega,))
         self.n, self.handle, self._val = n, None, None
         self.nnz = _structure(n, rowptr, colidx)
         self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
@@ -2319,20 +2442,42 @@ class AmgPlan:
             raise SblasError("coarse_max must be at least 1 and max_levels in [1, %d]" % amg_limits()["level_cap"])
         h, bad = C.c_void_p(), C.c_int64(-1)
         with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_amg_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr() if n else None,
-                                                 colidx.data_ptr() if self.nnz else None,
-                                                 val.data_ptr() if val is not None and theta > 0.0 and self.nnz else None, theta,
-                                                 int(coarse_max), int(max_levels), int(seed) & 0xffffffff, C.byref(h), C.byref(bad))
+            args = (-1, _stream(stream), n, self.nnz, rowptr.data_ptr() if n else None, colidx.data_ptr() if self.nnz else None,
+                    val.data_ptr() if val is not None and theta > 0.0 and self.nnz else None, theta, int(coarse_max), int(max_levels),
+                    int(seed) & 0xffffffff)
+            if prolongator == "plain" and float(min_reduction) == 0.0:     # the entry point as it was
+                name = "sblas_hip_amg_plan_create"
+                rc = lib().sblas_hip_amg_plan_create(*args, C.byref(h), C.byref(bad))
+            else:
+                name = "sblas_hip_amg_plan_create_ex"
+                rc = lib().sblas_hip_amg_plan_create_ex(*args, AMG_PROLONGATORS[prolongator], float(prolong_omega), float(min_reduction),
+                                                        C.byref(h), C.byref(bad))
         if rc != 0:
-            raise _bad_structure("sblas_hip_amg_plan_create", rc, bad.value)
+            raise _bad_structure(name, rc, bad.value)
         self.handle = h
 
     def info(self):
         out = (C.c_int64 * 12)()
         check(lib().sblas_hip_amg_plan_info(self.handle, out), "sblas_hip_amg_plan_info")
+        opt = (C.c_double * 4)()
+        check(lib().sblas_hip_amg_plan_options(self.handle, opt), "sblas_hip_amg_plan_options")
         return dict(n=int(out[0]), nnz=int(out[1]), levels=int(out[2]), nu=int(out[3]), coarse_sweeps=int(out[4]), launches=int(out[5]),
                     rows=int(out[6]), entries=int(out[7]), bytes=int(out[8]), smoother=("jacobi", "l1")[out[9]], ready=bool(out[10]),
-                    coarsest=int(out[11]), operator_complexity=(out[7] / out[1] if out[1] else 1.0))
+                    coarsest=int(out[11]), operator_complexity=(out[7] / out[1] if out[1] else 1.0),
+                    prolongator=("plain", "smoothed")[int(opt[0])], prolong_omega=float(opt[1]), min_reduction=float(opt[2]))
+
+    def transfer(self, l):
+        """A smoothed plan's transfer operators between level l and l + 1 as torch views that live as long as the plan
+        (sblas_hip_amg_plan_transfer): dict(n, n_coarse, nnz, p_rowptr, p_colidx, p_val, r_rowptr, r_colidx, r_val); P is
+        n x n_coarse, R = P^T; the values are there after setup().  Refused on a plain plan and on the coarsest level."""
+        import torch
+        sizes, ptrs = (C.c_int64 * 3)(), (C.c_void_p * 6)()
+        check(lib().sblas_hip_amg_plan_transfer(self.handle, int(l), sizes, ptrs), "sblas_hip_amg_plan_transfer")
+        n, nc, nnz = int(sizes[0]), int(sizes[1]), int(sizes[2])
+        view = lambda p, k, t: torch.as_tensor(_DeviceArray(p, k, t), device=self.device) if p and k else None
+        return dict(n=n, n_coarse=nc, nnz=nnz, p_rowptr=view(ptrs[0], n + 1, "<i4"), p_colidx=view(ptrs[1], nnz, "<i4"),
+                    p_val=view(ptrs[2], nnz, "<f8"), r_rowptr=view(ptrs[3], nc + 1, "<i4"), r_colidx=view(ptrs[4], nnz, "<i4"),
+                    r_val=view(ptrs[5], nnz, "<f8"))
 
     def level(self, l):
         """Level l's device arrays as torch views that live as long as the plan: dict(n, nnz, n_coarse, units, rowptr,
@@ -2436,8 +2581,22 @@ def amg_sweep(plan, level, b, x, y, mode="sweep", stream=None):
     return y
 
 
+def amg_pvalues(plan, level, val, t, stream=None):
+    """t for every stored entry of level `level` of a smoothed AmgPlan from the level's values val
+    (sblas_hip_amg_pvalues_f64): -(q_i a_ie) off the diagonal, 1 - q_i a_ii on it, q_i = prolong_omega / a_ii."""
+    import torch
+    sizes, ptrs = (C.c_int64 * 4)(), (C.c_void_p * 7)()
+    check(lib().sblas_hip_amg_plan_level(plan.handle, int(level), sizes, ptrs), "sblas_hip_amg_plan_level")
+    nnz = int(sizes[1])
+    pv, pt = _amg_level_vector("val", val, nnz, plan), _amg_level_vector("t", t, nnz, plan)
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_pvalues_f64(plan.handle, _stream(stream), int(level), pv, pt), "sblas_hip_amg_pvalues_f64")
+    return t
+
+
 def amg_restrict(plan, level, res, bc, stream=None):
-    """bc[I] = the sum of res over aggregate I of level `level`, ascending (sblas_hip_amg_restrict_f64)"""
+    """bc[I] = the sum of res over aggregate I of level `level`, ascending; on a smoothed plan after setup(), row I of
+    R times res in the sweep's order (sblas_hip_amg_restrict_f64)"""
     import torch
     n, nc = _amg_level_sizes(plan, level)
     pr, pc = _amg_level_vector("res", res, n, plan), _amg_level_vector("bc", bc, nc, plan)
@@ -2447,7 +2606,8 @@ def amg_restrict(plan, level, res, bc, stream=None):
 
 
 def amg_prolong(plan, level, e, x, scale=1.0, stream=None):
-    """x_i = x_i + scale * e[agg[i]] on level `level` (sblas_hip_amg_prolong_f64)"""
+    """x_i = x_i + scale * e[agg[i]] on level `level`; on a smoothed plan after setup(), x_i + scale * (row i of P times
+    e) (sblas_hip_amg_prolong_f64)"""
     import torch
     n, nc = _amg_level_sizes(plan, level)
     pe, px = _amg_level_vector("e", e, nc, plan), _amg_level_vector("x", x, n, plan)
@@ -2658,13 +2818,13 @@ class KrylovPlan:
 def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
     import torch
     n, rowptr, colidx, val = A
-    if precond not in (None, "jacobi", "ilu0", "amg"):
-        raise SblasError("precond must be None, 'jacobi', 'ilu0' or 'amg', not %r" % (precond,))
+    if precond not in (None, "jacobi", "ilu0", "amg", "amg_smoothed"):
+        raise SblasError("precond must be None, 'jacobi', 'ilu0', 'amg' or 'amg_smoothed', not %r" % (precond,))
     ilu = plan = amg = None
     lu = dinv = None
     try:
-        if precond == "amg":                                              # the defaults: V(1, 1), Jacobi 2/3, structure only
-            amg = AmgPlan(n, rowptr, colidx)
+        if precond in ("amg", "amg_smoothed"):                            # the defaults: V(1, 1), Jacobi 2/3, structure only
+            amg = AmgPlan(n, rowptr, colidx, prolongator="smoothed" if precond == "amg_smoothed" else "plain")
             amg.setup(val)
         elif precond is not None:                                           # both read the diagonal's places off the ILU(0) plan
             ilu = Ilu0Plan(n, rowptr, colidx)
@@ -2672,7 +2832,7 @@ def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
                 lu = ilu.factor(val)
             else:
                 dinv = ilu.pivots(val).reciprocal_()
-        pre = ilu if precond == "ilu0" else amg if precond == "amg" else precond
+        pre = ilu if precond == "ilu0" else amg if amg is not None else precond
         plan = make(n, rowptr, colidx, pre) if make is not None else KrylovPlan(n, rowptr, colidx, method=method, precond=pre)
         return plan.solve(val, b, x=x, lu=lu, dinv=dinv, **kw)
     finally:

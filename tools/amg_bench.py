@@ -9,10 +9,16 @@ host-clock time of each solve.
 Every matrix is measured in a child process of its own under its own time limit, one at a time, and nothing is started
 after a child that failed or ran out of time.  One JSON object per matrix on stdout; --out writes the list.
 
-  python tools/amg_bench.py [--inputs nd24k,grid,bidiagonal,banded5,powerlaw] [--rounds 5] [--out profiles/r19_amg.json]
+  python tools/amg_bench.py [--inputs nd24k,grid,bidiagonal,banded5,powerlaw,laplace] [--rounds 5] [--out profiles/r19_amg.json]
+                            [--prolongator plain,smoothed] [--min-reduction 0.2]
+
+--prolongator: the plans measured in the same process, one after the other ("plain", "smoothed" or both); the first one's
+figures keep the record's old keys, every one's are under "prolongators".  --min-reduction: the coarsening guard of every
+plan (default: the library's, 0 for plain and 0.2 for smoothed).
 
 Matrices: those of tools/ilu0_bench.py made symmetric -- the same sorted symmetric patterns, every off-diagonal pair
-given the value of its lower entry, the diagonal 1 + the row's absolute off-diagonal sum: symmetric positive definite."""
+given the value of its lower entry, the diagonal 1 + the row's absolute off-diagonal sum: symmetric positive definite --
+and `laplace`: the unscaled five-point Laplacian (4 on the diagonal, -1 beside it) of side --grid-side, the tests' matrix."""
 import argparse
 import json
 import os
@@ -39,6 +45,17 @@ def symmetric(n, rp, ci, val):
     return val
 
 
+def laplace(side):
+    """the five-point Laplacian of side x side points, rows ascending: (n, rowptr, colidx, val)"""
+    idx = np.arange(side * side, dtype=np.int64)
+    x, y = idx % side, idx // side
+    cols = np.stack([idx - side, idx - 1, idx, idx + 1, idx + side], axis=1)
+    keep = np.stack([y > 0, x > 0, np.ones_like(x, bool), x + 1 < side, y + 1 < side], axis=1)
+    vals = np.broadcast_to(np.array([-1.0, -1.0, 4.0, -1.0, -1.0]), cols.shape)
+    rp = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int32)
+    return side * side, rp, cols[keep].astype(np.int32), vals[keep].copy()
+
+
 def solve_timed(torch, fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -53,33 +70,50 @@ def measure(name, args):
     import ilu0_bench as IB
     import sptrsv_bench as TB
     dev = torch.device("cuda:0")
-    label, n, rp, ci, val = IB.build(name, args)
-    val = symmetric(n, rp, ci, val)
+    if name == "laplace":
+        n, rp, ci, val = laplace(args.grid_side)
+        label = "five-point Laplacian %d^2, unscaled" % args.grid_side
+    else:
+        label, n, rp, ci, val = IB.build(name, args)
+        val = symmetric(n, rp, ci, val)
+        label += ", symmetric"
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     drp, dci, dval = up(rp), up(ci), up(val)
-    rec = dict(matrix=label + ", symmetric", n=n, nnz=int(len(ci)), limits=S.amg_limits(), device=torch.cuda.get_device_name(0))
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    amg = S.AmgPlan(n, drp, dci)
-    torch.cuda.synchronize()
-    rec["create_ms"] = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    amg.setup(dval)
-    torch.cuda.synchronize()
-    rec["first_setup_ms"] = (time.perf_counter() - t0) * 1e3
-    rec["info"], rec["levels"], rec["check"] = amg.info(), amg.levels(), amg.check()
+    rec = dict(matrix=label, n=n, nnz=int(len(ci)), limits=S.amg_limits(), device=torch.cuda.get_device_name(0))
+    kinds = args.prolongator.split(",")
+    plans, per = {}, {}
+    for kind in kinds:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plans[kind] = S.AmgPlan(n, drp, dci, prolongator=kind, min_reduction=args.min_reduction)
+        torch.cuda.synchronize()
+        per[kind] = dict(create_ms=(time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        plans[kind].setup(dval)
+        torch.cuda.synchronize()
+        per[kind]["first_setup_ms"] = (time.perf_counter() - t0) * 1e3
+        per[kind]["info"], per[kind]["levels"], per[kind]["check"] = plans[kind].info(), plans[kind].levels(), plans[kind].check()
+    amg = plans[kinds[0]]
+    rec.update(per[kinds[0]])
     ilu = S.Ilu0Plan(n, drp, dci)
     lu = ilu.factor(dval)
     spmv = S.SpmvPlan(n, n, drp, dci)
     b = up(np.random.default_rng(5).random(n) * 2 - 1)
     z, y, tmp = torch.empty_like(b), torch.empty_like(b), torch.empty_like(b)
     ilu.solvers()
-    fns = {"amg_setup": lambda: amg.setup(dval), "amg_apply": lambda: amg.apply(b, out=z),
-           "ilu0_apply": lambda: ilu.apply(lu, b, out=y, tmp=tmp), "spmv": lambda: spmv(dval, b, 1.0, 0.0, y)}
+    fns = {"amg_setup": lambda: amg.setup(dval), "amg_apply": lambda: amg.apply(b, out=z)}
+    for kind in kinds[1:]:
+        fns["amg_%s_setup" % kind] = lambda kind=kind: plans[kind].setup(dval)
+        fns["amg_%s_apply" % kind] = lambda kind=kind: plans[kind].apply(b, out=z)
+    fns.update({"ilu0_apply": lambda: ilu.apply(lu, b, out=y, tmp=tmp), "spmv": lambda: spmv(dval, b, 1.0, 0.0, y)})
     for k, (ms, each) in TB.timed(torch, fns, args.rounds).items():
         rec["%s_ms" % k], rec["%s_rounds" % k] = ms, each
     rec["apply_over_ilu0_apply"] = rec["amg_apply_ms"] / rec["ilu0_apply_ms"]
     rec["apply_over_spmv"] = rec["amg_apply_ms"] / rec["spmv_ms"]
+    for kind in kinds:
+        tag = "amg" if kind == kinds[0] else "amg_%s" % kind
+        per[kind].update(setup_ms=rec["%s_setup_ms" % tag], apply_ms=rec["%s_apply_ms" % tag], apply_rounds=rec["%s_apply_rounds" % tag],
+                         apply_over_spmv=rec["%s_apply_ms" % tag] / rec["spmv_ms"])
     rec["ilu0_solve_launches"] = [p.info()["launches"] for p in ilu.solvers()]
 
     kw = dict(rtol=1e-8, max_iter=args.max_iter, check_every=32)
@@ -94,9 +128,11 @@ def measure(name, args):
     plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv, precond=ilu)
     pcg["ilu0"], _ = solve_timed(torch, lambda: plan.solve(dval, b, lu=lu, **kw))
     plan.destroy()
-    plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv, precond=amg)
-    pcg["amg"], _ = solve_timed(torch, lambda: plan.solve(dval, b, **kw))
-    plan.destroy()
+    for kind in kinds:
+        plan = S.KrylovPlan(n, drp, dci, spmv_plan=spmv, precond=plans[kind])
+        per[kind]["pcg"], _ = solve_timed(torch, lambda: plan.solve(dval, b, **kw))
+        pcg["amg" if kind == kinds[0] else "amg_%s" % kind] = per[kind]["pcg"]
+        plan.destroy()
     # ILU(0) in the multicolour order: the caller's composition (KrylovPlan's docstring)
     color = S.ColorPlan(n, drp, dci)
     perm = color.permute(drp, dci)
@@ -109,8 +145,8 @@ def measure(name, args):
     pcg["ilu0_multicolour"], _ = solve_timed(torch, lambda: plan.solve(cval, cb, lu=clu, **kw))
     pcg["ilu0_multicolour"]["colours"] = color.info().get("colors")
     plan.destroy()
-    rec["pcg"] = pcg
-    for p in (cilu, perm, color, ilu, spmv, amg):
+    rec["pcg"], rec["prolongators"] = pcg, per
+    for p in (cilu, perm, color, ilu, spmv) + tuple(plans.values()):
         p.destroy()
     print(json.dumps(rec), flush=True)
 
@@ -123,6 +159,8 @@ def main():
     ap.add_argument("--grid-side", type=int, default=1000)
     ap.add_argument("--nd24k-scale", type=float, default=1.0)
     ap.add_argument("--max-iter", type=int, default=2000)
+    ap.add_argument("--prolongator", default="plain", help="plain, smoothed or both, comma-separated")
+    ap.add_argument("--min-reduction", type=float, default=None, help="the coarsening guard (default: the library's)")
     ap.add_argument("--limit", type=int, default=240, help="seconds a matrix may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--one", default=None, help="(internal) measure this matrix in this process")
@@ -133,7 +171,9 @@ def main():
     results, failed = [], None
     for name in args.inputs.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--one", name, "--rounds", str(args.rounds), "--rows", str(args.rows),
-               "--grid-side", str(args.grid_side), "--nd24k-scale", str(args.nd24k_scale), "--max-iter", str(args.max_iter)]
+               "--grid-side", str(args.grid_side), "--nd24k-scale", str(args.nd24k_scale), "--max-iter", str(args.max_iter), "--prolongator", args.prolongator]
+        if args.min_reduction is not None:
+            cmd += ["--min-reduction", str(args.min_reduction)]
         try:
             run = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=args.limit)
         except subprocess.TimeoutExpired:

@@ -6,7 +6,10 @@
 // with theta) out of arrays of exactly the sizes the contract names, so that a read or write past either end is the
 // sanitizer's to find, checks every aggregate's invariants, builds the Galerkin hierarchy with a second, naive
 // restatement of the COO order, runs the cycle reference on it against a restatement of the written order, and holds
-// the launch counts against a hand count.
+// the launch counts against a hand count.  For smoothed aggregation it holds the coarsening guard against its expression,
+// builds P (sblas_amg_prolongator_ref, counted first and then written into arrays of exactly that size), R = P^T and the two
+// products in a naive restatement of the pinned orders, and runs sblas_amg_transfer_ref and sblas_amg_cycle_sa_ref
+// against the written order once more, n = 0 and 1 included.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -209,6 +212,180 @@ static void check_case(const char *name, const Csr &a, double theta, int64_t coa
         }
 }
 
+// ---- smoothed aggregation ----
+typedef std::vector<std::vector<std::pair<int32_t, double>>> Rows; // every row's (column, value) in the pinned numbering
+
+// sorted by column, equal columns in input order, each run added left to right
+static Csr sum_rows(const Rows &rows)
+{
+    Csr c;
+    for (const auto &r : rows) {
+        std::vector<std::pair<int32_t, double>> s(r);
+        std::stable_sort(s.begin(), s.end(), [](const std::pair<int32_t, double> &x, const std::pair<int32_t, double> &y) { return x.first < y.first; });
+        for (size_t k = 0; k < s.size(); ++k) {
+            if (k > 0 && s[k].first == s[k - 1].first) c.val.back() = c.val.back() + s[k].second;
+            else c.colidx.push_back(s[k].first), c.val.push_back(s[k].second);
+        }
+        c.rowptr.push_back((int32_t)c.colidx.size());
+        ++c.n;
+    }
+    return c;
+}
+
+static Csr product(const Csr &a, const Csr &b)
+{
+    Rows rows((size_t)a.n);
+    for (int64_t i = 0; i < a.n; ++i)
+        for (int32_t e = a.rowptr[(size_t)i]; e < a.rowptr[(size_t)i + 1]; ++e)
+            for (int32_t f = b.rowptr[(size_t)a.colidx[(size_t)e]]; f < b.rowptr[(size_t)a.colidx[(size_t)e] + 1]; ++f)
+                rows[(size_t)i].emplace_back(b.colidx[(size_t)f], a.val[(size_t)e] * b.val[(size_t)f]);
+    return sum_rows(rows);
+}
+
+static Csr transpose(const Csr &p, int64_t cols)
+{
+    Rows rows((size_t)cols);
+    for (int64_t i = 0; i < p.n; ++i)
+        for (int32_t e = p.rowptr[(size_t)i]; e < p.rowptr[(size_t)i + 1]; ++e) rows[(size_t)p.colidx[(size_t)e]].emplace_back((int32_t)i, p.val[(size_t)e]);
+    return sum_rows(rows); // rows ascend already and no pair repeats: nothing is added
+}
+
+struct SaLevel {
+    Csr a, p, r;
+    std::vector<double> wd;
+};
+
+static Csr prolongator(const Csr &a, const std::vector<int32_t> &agg, int64_t nc, double omega_p)
+{
+    // the library's, counted first, then written into arrays of exactly that size
+    std::vector<int32_t> prp((size_t)a.n + 1);
+    int64_t count = -1, row = 0;
+    expect(sblas_amg_prolongator_ref(a.n, a.rowptr.data(), a.colidx.data(), a.val.data(), agg.data(), nc, omega_p, prp.data(), nullptr, nullptr, &count,
+                                     &row) == SBLAS_OK && row == -1 && count >= a.n,
+           "prolongator_ref counts");
+    Csr p;
+    p.n = a.n, p.rowptr.assign((size_t)a.n + 1, 0), p.colidx.resize((size_t)count), p.val.resize((size_t)count);
+    int64_t again = -1;
+    expect(sblas_amg_prolongator_ref(a.n, a.rowptr.data(), a.colidx.data(), a.val.data(), agg.data(), nc, omega_p, p.rowptr.data(), p.colidx.data(),
+                                     p.val.data(), &again, &row) == SBLAS_OK && again == count,
+           "prolongator_ref writes what it counted");
+    // the rule once more
+    Rows rows((size_t)a.n);
+    for (int64_t i = 0; i < a.n; ++i) {
+        double d = 0.0;
+        for (int32_t e = a.rowptr[(size_t)i]; e < a.rowptr[(size_t)i + 1]; ++e)
+            if (a.colidx[(size_t)e] == i) d = a.val[(size_t)e];
+        const double q = omega_p / d;
+        for (int32_t e = a.rowptr[(size_t)i]; e < a.rowptr[(size_t)i + 1]; ++e) {
+            const double prod = q * a.val[(size_t)e];
+            rows[(size_t)i].emplace_back(agg[(size_t)a.colidx[(size_t)e]], a.colidx[(size_t)e] == i ? 1.0 - prod : -prod);
+        }
+    }
+    const Csr want = sum_rows(rows);
+    expect(want.rowptr == p.rowptr && want.colidx == p.colidx && want.val.size() == p.val.size() &&
+               (p.val.empty() || memcmp(want.val.data(), p.val.data(), p.val.size() * 8) == 0),
+           "prolongator_ref has the rule's bits");
+    return p;
+}
+
+static std::vector<double> transfer(const Csr &m, const std::vector<double> &in)
+{
+    std::vector<double> s((size_t)m.n);
+    for (int64_t i = 0; i < m.n; ++i) s[(size_t)i] = row_sum(m, i, in);
+    return s;
+}
+
+static std::vector<double> cycle_sa(const std::vector<SaLevel> &lv, size_t l, const std::vector<double> &b, int nu, int cs, double scale)
+{
+    Level L;
+    L.a = lv[l].a, L.wd = lv[l].wd;
+    std::vector<double> x((size_t)L.a.n);
+    for (int64_t i = 0; i < L.a.n; ++i) x[(size_t)i] = L.wd[(size_t)i] * b[(size_t)i];
+    if (l + 1 == lv.size()) {
+        for (int k = 1; k < cs; ++k) x = sweep(L, b, x, false);
+        return x;
+    }
+    for (int k = 1; k < nu; ++k) x = sweep(L, b, x, false);
+    const std::vector<double> e = cycle_sa(lv, l + 1, transfer(lv[l].r, sweep(L, b, x, true)), nu, cs, scale);
+    const std::vector<double> pe = transfer(lv[l].p, e);
+    for (int64_t i = 0; i < L.a.n; ++i) {
+        const double t = scale * pe[(size_t)i];
+        x[(size_t)i] = x[(size_t)i] + t;
+    }
+    for (int k = 0; k < nu; ++k) x = sweep(L, b, x, false);
+    return x;
+}
+
+static void check_smoothed(const char *name, const Csr &a, double theta, int64_t coarse_max, double min_reduction, size_t want_levels)
+{
+    std::vector<SaLevel> lv;
+    Csr cur = a;
+    while (a.n > 0) {
+        SaLevel S;
+        S.a = cur;
+        S.wd.resize((size_t)cur.n);
+        int64_t row = 0;
+        expect(sblas_amg_wd_ref(cur.n, cur.rowptr.data(), cur.colidx.data(), cur.val.data(), SBLAS_AMG_JACOBI, 2.0 / 3.0, S.wd.data(), &row) == SBLAS_OK,
+               "wd of a smoothed level");
+        Level L;
+        int64_t nc = cur.n;
+        if (cur.n > coarse_max && lv.size() + 1 < 20) nc = aggregate(cur, theta, 0, (uint32_t)lv.size(), L);
+        const int keep = sblas_amg_keep_level(cur.n, nc, min_reduction);
+        expect(keep == (nc < cur.n && (double)nc <= (1.0 - min_reduction) * (double)cur.n ? 1 : 0), "keep_level is its expression");
+        if (!keep) {
+            lv.push_back(S);
+            break;
+        }
+        S.p = prolongator(cur, L.agg, nc, 2.0 / 3.0);
+        S.r = transpose(S.p, nc);
+        lv.push_back(S);
+        cur = product(S.r, product(cur, S.p));
+    }
+    if (want_levels) expect(lv.size() == want_levels, name);
+    const int k = (int)lv.size();
+    std::vector<int64_t> n;
+    std::vector<const int32_t *> rp, ci, prp, pci, rrp, rci;
+    std::vector<const double *> val, wd, pv, rv;
+    for (const SaLevel &S : lv) {
+        n.push_back(S.a.n), rp.push_back(S.a.rowptr.data()), ci.push_back(S.a.colidx.data()), val.push_back(S.a.val.data()), wd.push_back(S.wd.data());
+        prp.push_back(S.p.rowptr.data()), pci.push_back(S.p.colidx.data()), pv.push_back(S.p.val.data());
+        rrp.push_back(S.r.rowptr.data()), rci.push_back(S.r.colidx.data()), rv.push_back(S.r.val.data());
+    }
+    std::vector<double> r((size_t)a.n), z((size_t)a.n, -7.0);
+    for (size_t i = 0; i < r.size(); ++i) r[i] = sin(1.0 + (double)i) + 0.25;
+    for (int nu = 1; nu <= 2; ++nu) {
+        const double scale = nu == 1 ? 1.0 : 1.5;
+        expect(sblas_amg_cycle_sa_ref(k, n.data(), rp.data(), ci.data(), val.data(), wd.data(), prp.data(), pci.data(), pv.data(), rrp.data(), rci.data(),
+                                      rv.data(), nu, 3, scale, r.data(), z.data()) == SBLAS_OK,
+               "cycle_sa_ref accepts a sound hierarchy");
+        if (k > 0) {
+            const std::vector<double> want = cycle_sa(lv, 0, r, nu, 3, scale);
+            expect(memcmp(want.data(), z.data(), z.size() * 8) == 0, name);
+            expect(sblas_amg_cycle_sa_ref(k, n.data(), rp.data(), ci.data(), val.data(), wd.data(), prp.data(), pci.data(), pv.data(), rrp.data(),
+                                          rci.data(), rv.data(), nu, 3, scale, r.data(), r.data()) == SBLAS_E_INVALID,
+                   "z must not be r");
+        }
+    }
+    for (size_t l = 0; l + 1 < lv.size(); ++l) { // the transfers alone, out of exact-size arrays
+        const SaLevel &S = lv[l];
+        std::vector<double> res((size_t)S.a.n), e((size_t)S.r.n), bc((size_t)S.r.n, -7.0), x((size_t)S.a.n);
+        for (size_t i = 0; i < res.size(); ++i) res[i] = cos(2.0 + (double)i), x[i] = 0.5 - (double)(i % 5);
+        for (size_t i = 0; i < e.size(); ++i) e[i] = sin(3.0 + (double)i);
+        expect(sblas_amg_transfer_ref(SBLAS_AMG_RESTRICT, S.r.n, S.r.rowptr.data(), S.r.colidx.data(), S.r.val.data(), 0.0, res.data(), bc.data()) == SBLAS_OK,
+               "transfer_ref restricts");
+        const std::vector<double> want_bc = transfer(S.r, res), pe = transfer(S.p, e);
+        expect(memcmp(want_bc.data(), bc.data(), bc.size() * 8) == 0, "the restriction's bits");
+        std::vector<double> want_x(x);
+        for (size_t i = 0; i < x.size(); ++i) {
+            const double t = 1.5 * pe[i];
+            want_x[i] = x[i] + t;
+        }
+        expect(sblas_amg_transfer_ref(SBLAS_AMG_PROLONG, S.a.n, S.p.rowptr.data(), S.p.colidx.data(), S.p.val.data(), 1.5, e.data(), x.data()) == SBLAS_OK,
+               "transfer_ref prolongs");
+        expect(memcmp(want_x.data(), x.data(), x.size() * 8) == 0, "the prolongation's bits");
+    }
+}
+
 int main()
 {
     int64_t lim[8];
@@ -245,6 +422,46 @@ int main()
     check_case("clique", clique, 0.0, 16, 2);
     check_case("star", star, 0.0, 64, 0);
     check_case("anisotropic grid", grid(10, 1.0, 0.01), 0.25, 16, 0);
+
+    // smoothed aggregation: the same matrices; the star stays one level under the guard and loses a vertex a level without
+    check_smoothed("smoothed n = 0", empty, 0.0, 64, 0.2, 0);
+    check_smoothed("smoothed n = 1", one, 0.0, 64, 0.2, 1);
+    check_smoothed("smoothed diagonal: one level", diag, 0.0, 8, 0.2, 1);
+    check_smoothed("smoothed tridiagonal", tri, 0.0, 16, 0.2, 0);
+    check_smoothed("smoothed grid", grid(12, 1.0, 1.0), 0.0, 16, 0.2, 0);
+    check_smoothed("smoothed clique", clique, 0.0, 16, 0.0, 2);
+    check_smoothed("smoothed star, guarded", star, 0.0, 64, 0.2, 1);
+    check_smoothed("smoothed anisotropic grid", grid(10, 1.0, 0.01), 0.25, 16, 0.2, 0);
+    {
+        expect(sblas_amg_keep_level(10, 8, 0.2) == 1 && sblas_amg_keep_level(10, 9, 0.2) == 0 && sblas_amg_keep_level(10, 9, 0.0) == 1 &&
+                   sblas_amg_keep_level(10, 10, 0.0) == 0 && sblas_amg_keep_level(0, 0, 0.0) == 0,
+               "keep_level at its boundaries");
+        expect(sblas_amg_keep_level(-1, 0, 0.0) == -1 && sblas_amg_keep_level(4, -1, 0.0) == -1 && sblas_amg_keep_level(4, 2, 1.0) == -1 &&
+                   sblas_amg_keep_level(4, 2, -0.5) == -1 && sblas_amg_keep_level(4, 2, NAN) == -1,
+               "keep_level refusals");
+        Csr g = grid(4, 1.0, 1.0);
+        std::vector<int32_t> agg(16, 0), prp(17);
+        int64_t count = 0, row = -1;
+        const double omegas[4] = {0.0, -1.0, NAN, INFINITY};
+        for (double w : omegas)
+            expect(sblas_amg_prolongator_ref(16, g.rowptr.data(), g.colidx.data(), g.val.data(), agg.data(), 1, w, prp.data(), nullptr, nullptr, &count, &row) ==
+                       SBLAS_E_INVALID,
+                   "omega_P must be finite and > 0");
+        agg[7] = 1;
+        expect(sblas_amg_prolongator_ref(16, g.rowptr.data(), g.colidx.data(), g.val.data(), agg.data(), 1, 0.5, prp.data(), nullptr, nullptr, &count, &row) ==
+                   SBLAS_E_INVALID,
+               "an aggregate beyond n_agg");
+        agg[7] = 0;
+        for (int32_t e = g.rowptr[9]; e < g.rowptr[10]; ++e)
+            if (g.colidx[(size_t)e] == 9) g.colidx[(size_t)e] = 8;
+        expect(sblas_amg_prolongator_ref(16, g.rowptr.data(), g.colidx.data(), g.val.data(), agg.data(), 1, 0.5, prp.data(), nullptr, nullptr, &count, &row) ==
+                       SBLAS_E_INVALID && row == 9,
+               "a missing diagonal is named");
+        std::vector<double> v(16, 1.0);
+        expect(sblas_amg_transfer_ref(2, 16, g.rowptr.data(), g.colidx.data(), g.val.data(), 1.0, v.data(), v.data()) == SBLAS_E_INVALID &&
+                   sblas_amg_transfer_ref(SBLAS_AMG_RESTRICT, 16, g.rowptr.data(), g.colidx.data(), g.val.data(), 1.0, v.data(), v.data()) == SBLAS_E_INVALID,
+               "transfer_ref refusals");
+    }
 
     // refusals, each with its row
     {
