@@ -1003,7 +1003,8 @@ int sblas_hip_amg_restrict_f64(const void *plan, void *stream, int level, const 
 int sblas_hip_amg_prolong_f64(const void *plan, void *stream, int level, double scale, const double *e, double *x);
 
 /* Smoothed aggregation on the same plan (SBLAS_AMG_SMOOTHED, sblas_hip_amg_plan_create_ex, the coarsening guard and their
- * host references) is declared in sblas_hip_amg_sa.h, which this header includes at its end. */
+ * host references) is declared in sblas_hip_amg_sa.h, which this header includes at its end; aggregation on the device
+ * (sblas_hip_amg_plan_create_dev, sblas_hip_amg_aggregate_i32, sblas_amg_roots_rounds_ref) in sblas_hip_amg_dev.h, likewise. */
 
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
@@ -1259,4 +1260,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 }
 #endif
 #include "sblas_hip_amg_sa.h"
+#include "sblas_hip_amg_dev.h"
 #endif /* SBLAS_HIP_H */

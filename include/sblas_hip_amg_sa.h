@@ -68,7 +68,8 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
  * (n_{l+1}) [2] the stored entries of P, and of R.  ptrs: P's rowptr, colidx, val; R's rowptr, colidx, val (the values
  * are there after a setup).  Refused on a plain plan and on the coarsest level. */
 int sblas_hip_amg_plan_transfer(const void *plan, int level, int64_t sizes[3], const void *ptrs[6]);
-/* out: [0] the prolongator [1] omega_P (0 on a plain plan) [2] min_reduction [3] 0 */
+/* out: [0] the prolongator [1] omega_P (0 on a plain plan) [2] min_reduction [3] the aggregation mode
+ * (SBLAS_AMG_AGG_*, sblas_hip_amg_dev.h; 0 for every plan made by the creates above) */
 int sblas_hip_amg_plan_options(const void *plan, double out[4]);
 /* The prolongator-values kernel alone on level `level` of a smoothed plan: t (the level's nnz) from val; one launch. */
 int sblas_hip_amg_pvalues_f64(const void *plan, void *stream, int level, const double *val, double *t);

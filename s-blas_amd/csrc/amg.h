@@ -92,4 +92,12 @@ enum { AMG_RESTRICT = 0, AMG_PROLONG = 1 }; // modes of the transfer row product
 int64_t amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
                       uint32_t level, int32_t *agg, std::vector<int32_t> &aggptr, int32_t *members);
 
+// The bound of the strength test, theta * max_{k != i} |a_ik| for every row (val != null, theta > 0): amg_aggregate's.
+void amg_strength_bounds(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, std::vector<double> &bound);
+
+// The same rule in synchronous rounds (sblas_amg_roots_rounds_ref without the argument checks): root (n
+// bytes, 1 = root) -> the rounds that decided a vertex.
+int64_t amg_roots_rounds(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed, uint32_t level,
+                         unsigned char *root);
+
 } // namespace sblas

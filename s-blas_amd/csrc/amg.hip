@@ -29,6 +29,13 @@
 // SpGEMM plans.  Both transfers of a cycle are transfer_row(): the sweep's row sum over a stored row of R_l (restrict:
 // b_{l+1}[I] = s_I) or P_l (prolong: x_i = x_i + scale s_i, in place: only the coarse vector is gathered).  A level is
 // kept only when amg_keep_level() says so (the coarsening guard, min_reduction), decided right after the aggregation.
+//
+// Aggregation on the device (sblas_hip_amg_plan_create_dev with SBLAS_AMG_AGG_DEVICE) builds the same
+// plan, array for array, without the host rule: every level is aggregated by sblas_hip_amg_aggregate_i32
+// (amg_aggregate.hip) on the level's device arrays, one kernel writes the triplets from agg (a thread an entry), with
+// theta > 0 the next level's values are the COO plan's assembly on the device (the same left-to-right sums), and below
+// level 0 dpos comes from a kernel: only level 0's structure (for the check that names the first bad row), every level's
+// row pointer (level_pack) and scalars come to the host.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -180,6 +187,42 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_pvalues_kernel(int64_t count,
     }
 }
 
+// The triplets of a level's COO plan from agg, a thread an entry: entry e of row i is (agg[i], agg[col(e)]) for the plain
+// plan's coarse pattern (COARSE_ROWS) and (i, agg[col(e)]) for P.  The row of e by bisection of rowptr, as the
+// permutation plan's relabel kernel finds it.
+template <bool COARSE_ROWS>
+__global__ __launch_bounds__(AMG_THREADS) void amg_triplets_kernel(int64_t nnz, int64_t n, const int32_t *__restrict__ rowptr,
+                                                                   const int32_t *__restrict__ colidx, const int32_t *__restrict__ agg,
+                                                                   int32_t *__restrict__ trow, int32_t *__restrict__ tcol)
+{
+    const int64_t e = (int64_t)blockIdx.x * AMG_THREADS + threadIdx.x;
+    if (e >= nnz) return;
+    int64_t lo = 0, hi = n - 1; // the last row whose start is <= e (empty rows share their start with the next)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (rowptr[mid] <= e) lo = mid;
+        else hi = mid - 1;
+    }
+    trow[e] = COARSE_ROWS ? agg[lo] : (int32_t)lo;
+    tcol[e] = agg[colidx[e]];
+}
+
+// dpos[i] = the place of the diagonal in the strictly ascending row i, by bisection.  A level below the first always
+// stores it: row I of a coarse pattern holds the image of a member's diagonal entry.
+__global__ __launch_bounds__(AMG_THREADS) void amg_dpos_kernel(int64_t n, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
+                                                               int32_t *__restrict__ dpos)
+{
+    const int64_t i = (int64_t)blockIdx.x * AMG_THREADS + threadIdx.x;
+    if (i >= n) return;
+    int64_t lo = rowptr[i], hi = rowptr[i + 1]; // the first entry whose column is not below i
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)colidx[mid] < i) lo = mid + 1;
+        else hi = mid;
+    }
+    dpos[i] = (int32_t)lo;
+}
+
 // wd_i = omega / a_ii (Jacobi) or omega / sum_e |a_ie| (l1, sequentially in stored order from +0).  A diagonal that is
 // not finite and > 0 is reported as (level, row) in *flag: the least such pair, whichever thread finds it first -- an
 // integer minimum is the same in every order.
@@ -234,7 +277,7 @@ struct AmgPlan {
     const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
     double theta = 0.0;
     uint32_t seed = 0;
-    int prolongator = SBLAS_AMG_PLAIN;
+    int prolongator = SBLAS_AMG_PLAIN, aggregation = SBLAS_AMG_AGG_HOST;
     double omega_p = 0.0, min_reduction = 0.0;
     std::vector<std::unique_ptr<AmgLevel>> lv;
     DeviceBuffer block, tscratch; // the flag word; a smoothed plan's t, sized by the level with the most entries
@@ -321,6 +364,15 @@ const AmgLevel *level_of(const void *plan, int level, bool need_setup)
     return p->lv[(size_t)level].get();
 }
 
+// a level's row pointer alone on its way to the host (aggregation on the device: nothing nnz-sized follows it)
+int fetch_rowptr(hipStream_t s, int64_t n, int64_t nnz, const int32_t *rowptr, std::vector<int32_t> &h_rowptr)
+{
+    h_rowptr.resize((size_t)n + 1);
+    if (hipMemcpyAsync(h_rowptr.data(), rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return SBLAS_E_HIP;
+    return h_rowptr[(size_t)n] == nnz ? SBLAS_OK : SBLAS_E_INTERNAL;
+}
+
 } // namespace
 
 extern "C" {
@@ -336,9 +388,19 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
                                  double theta, int64_t coarse_max, int max_levels, uint32_t seed, int prolongator, double prolong_omega,
                                  double min_reduction, void **plan_out, int64_t *bad_row)
 {
+    return sblas_hip_amg_plan_create_dev(dev, stream, n, nnz, rowptr, colidx, val, theta, coarse_max, max_levels, seed, prolongator, prolong_omega,
+                                         min_reduction, SBLAS_AMG_AGG_HOST, plan_out, bad_row);
+}
+
+int sblas_hip_amg_plan_create_dev(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                  double theta, int64_t coarse_max, int max_levels, uint32_t seed, int prolongator, double prolong_omega,
+                                  double min_reduction, int aggregation, void **plan_out, int64_t *bad_row)
+{
     if (bad_row) *bad_row = -1;
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
+    if (aggregation != SBLAS_AMG_AGG_HOST && aggregation != SBLAS_AMG_AGG_DEVICE) return SBLAS_E_INVALID;
+    const bool dev_agg = aggregation == SBLAS_AMG_AGG_DEVICE;
     if (prolongator != SBLAS_AMG_PLAIN && prolongator != SBLAS_AMG_SMOOTHED) return SBLAS_E_INVALID;
     const bool smoothed = prolongator == SBLAS_AMG_SMOOTHED;
     if ((smoothed && !amg_prolong_omega_ok(prolong_omega)) || !amg_min_reduction_ok(min_reduction)) return SBLAS_E_INVALID;
@@ -350,7 +412,7 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
     if (max_levels == 0) max_levels = AMG_MAX_LEVELS;
     std::unique_ptr<AmgPlan> p(new AmgPlan);
     p->dev = resolve_device(dev), p->n = n, p->nnz = nnz, p->rowptr = rowptr, p->colidx = colidx, p->theta = theta, p->seed = seed;
-    p->prolongator = prolongator, p->omega_p = smoothed ? prolong_omega : 0.0, p->min_reduction = min_reduction;
+    p->prolongator = prolongator, p->omega_p = smoothed ? prolong_omega : 0.0, p->min_reduction = min_reduction, p->aggregation = aggregation;
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -363,7 +425,7 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
     int rc = fetch_structure(s, n, nnz, rowptr, colidx, h_rowptr, h_colidx, bad_row);
     if (rc != SBLAS_OK) return rc;
     const bool by_value = theta > 0.0;
-    if (by_value) {
+    if (by_value && !dev_agg) {
         h_val.resize((size_t)nnz);
         if (hipMemcpyAsync(h_val.data(), val, (size_t)nnz * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return SBLAS_E_HIP;
@@ -376,43 +438,85 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
     const double *d_val = val; // theta > 0 on a smoothed plan: the level's values on the device, for the numeric chain
     int64_t nl = n, nnzl = nnz, nnz_most = nnz;
     DeviceBuffer val_here, val_next; // such a level's values, and the next one's
+    // the device aggregation's scratch, sized by level 0 (the levels only shrink): agg | aggptr | members, and its workspace
+    DeviceBuffer agg_tmp, agg_ws;
+    const size_t agg_arr = ((size_t)n * 4 + 15) / 16 * 16, agg_ptr = (((size_t)n + 1) * 4 + 15) / 16 * 16;
+    const size_t agg_ws_bytes = dev_agg ? sblas_hip_amg_aggregate_workspace(n, nnz) : 0;
+    if (dev_agg && n > coarse_max && max_levels > 1 &&
+        (agg_tmp.alloc(p->dev, 2 * agg_arr + agg_ptr) != hipSuccess || agg_ws.alloc(p->dev, agg_ws_bytes) != hipSuccess))
+        return SBLAS_E_HIP;
+    int32_t *const d_agg = agg_tmp ? agg_tmp.at<int32_t>() : nullptr, *const d_aggptr = agg_tmp ? agg_tmp.at<int32_t>(agg_arr) : nullptr;
+    int32_t *const d_members = agg_tmp ? agg_tmp.at<int32_t>(agg_arr + agg_ptr) : nullptr;
     for (int l = 0;; ++l) {
         std::unique_ptr<AmgLevel> L(new AmgLevel);
         L->n = nl, L->nnz = nnzl, L->rowptr = d_rowptr, L->colidx = d_colidx;
         std::vector<int32_t> dpos((size_t)nl), agg, aggptr, members;
         int64_t bad = -1;
-        rc = sblas_ilu0_check(nl, h_rowptr.data(), h_colidx.data(), dpos.data(), &bad);
-        if (rc != SBLAS_OK) { // level 0: the caller's structure; below it cannot happen (the COO plan sorts, a diagonal is always present)
-            if (bad_row) *bad_row = bad;
-            return rc;
+        if (!dev_agg || l == 0) {
+            rc = sblas_ilu0_check(nl, h_rowptr.data(), h_colidx.data(), dpos.data(), &bad);
+            if (rc != SBLAS_OK) { // level 0: the caller's structure; below it cannot happen (the COO plan sorts, a diagonal is always present)
+                if (bad_row) *bad_row = bad;
+                return rc;
+            }
         }
         std::vector<int32_t> c_rowptr, c_colidx;
         std::vector<double> c_val;
+        int64_t nnz_next = 0;
+        // the triplets of this level's COO plan: written on the host and uploaded, or by a kernel from the device's agg
+        DeviceBuffer trip;
+        int32_t *d_trow = nullptr, *d_tcol = nullptr;
+        const auto make_triplets = [&](bool coarse_rows) -> int {
+            if (dev_agg) {
+                const size_t tr = ((size_t)nnzl * 4 + 15) / 16 * 16;
+                if (trip.alloc(p->dev, 2 * tr + 16) != hipSuccess) return SBLAS_E_HIP;
+                d_trow = trip.at<int32_t>(), d_tcol = trip.at<int32_t>(tr);
+                if (nnzl == 0) return SBLAS_OK;
+                if (coarse_rows) amg_triplets_kernel<true><<<grid_of(nnzl), AMG_THREADS, 0, s>>>(nnzl, nl, L->rowptr, L->colidx, d_agg, d_trow, d_tcol);
+                else amg_triplets_kernel<false><<<grid_of(nnzl), AMG_THREADS, 0, s>>>(nnzl, nl, L->rowptr, L->colidx, d_agg, d_trow, d_tcol);
+                return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+            }
+            std::vector<int32_t> trow((size_t)nnzl), tcol((size_t)nnzl);
+            for (int64_t i = 0; i < nl; ++i)
+                for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e)
+                    trow[(size_t)e] = coarse_rows ? agg[(size_t)i] : (int32_t)i, tcol[(size_t)e] = agg[(size_t)h_colidx[e]];
+            size_t tb = 0;
+            Segment tseg[2] = {Segment(trow), Segment(tcol)};
+            if (upload_segments(trip, p->dev, s, tseg, 2, &tb) != hipSuccess) return SBLAS_E_HIP;
+            d_trow = trip.at<int32_t>(), d_tcol = trip.at<int32_t>(tseg[1].offset);
+            return SBLAS_OK;
+        };
         if (nl > coarse_max && l + 1 < max_levels) {
-            agg.resize((size_t)nl), members.resize((size_t)nl);
-            const int64_t nc = amg_aggregate(nl, h_rowptr.data(), h_colidx.data(), by_value ? h_val.data() : nullptr, theta, seed, (uint32_t)l,
-                                             agg.data(), aggptr, members.data());
+            int64_t nc = 0;
+            if (dev_agg) {
+                int64_t rounds = 0;
+                rc = sblas_hip_amg_aggregate_i32(p->dev, s, nl, nnzl, d_rowptr, d_colidx, by_value ? d_val : nullptr, theta, seed, (uint32_t)l, d_agg,
+                                                 d_aggptr, d_members, agg_ws.at<char>(), agg_ws_bytes, &nc, &rounds);
+                if (rc != SBLAS_OK) return rc;
+            } else {
+                agg.resize((size_t)nl), members.resize((size_t)nl);
+                nc = amg_aggregate(nl, h_rowptr.data(), h_colidx.data(), by_value ? h_val.data() : nullptr, theta, seed, (uint32_t)l, agg.data(), aggptr,
+                                   members.data());
+            }
             if (smoothed && amg_keep_level(nl, nc, min_reduction)) {
                 L->n_coarse = nc; // the transfer operators and the products: after this level's own arrays are on the device
             } else if (!smoothed && amg_keep_level(nl, nc, min_reduction)) { // a level that does not reduce n (enough) is discarded
-                std::vector<int32_t> trow((size_t)nnzl), tcol((size_t)nnzl);
-                for (int64_t i = 0; i < nl; ++i)
-                    for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) trow[(size_t)e] = agg[(size_t)i], tcol[(size_t)e] = agg[(size_t)h_colidx[e]];
-                DeviceBuffer trip;
-                size_t tb = 0;
-                Segment tseg[2] = {Segment(trow), Segment(tcol)};
-                if (upload_segments(trip, p->dev, s, tseg, 2, &tb) != hipSuccess) return SBLAS_E_HIP;
-                rc = sblas_hip_coo_plan_create(p->dev, s, nc, nc, nnzl, trip.at<int32_t>(), trip.at<int32_t>(tseg[1].offset), SBLAS_COO_SUM, &L->coo);
+                rc = make_triplets(true);
+                if (rc != SBLAS_OK) return rc;
+                rc = sblas_hip_coo_plan_create(p->dev, s, nc, nc, nnzl, d_trow, d_tcol, SBLAS_COO_SUM, &L->coo);
                 if (rc != SBLAS_OK) return rc;
                 int64_t ci[8];
                 const int32_t *c_rp = nullptr, *c_ci = nullptr, *c_perm = nullptr, *c_run = nullptr;
                 sblas_hip_coo_plan_info(L->coo, ci);
                 sblas_hip_coo_plan_csr(L->coo, &c_rp, &c_ci, &c_perm, &c_run);
-                const int64_t nnzc = ci[3];
+                const int64_t nnzc = nnz_next = ci[3];
                 int64_t cbad = -1;
-                rc = fetch_structure(s, nc, nnzc, c_rp, c_ci, c_rowptr, c_colidx, &cbad);
+                rc = dev_agg ? fetch_rowptr(s, nc, nnzc, c_rp, c_rowptr) : fetch_structure(s, nc, nnzc, c_rp, c_ci, c_rowptr, c_colidx, &cbad);
                 if (rc != SBLAS_OK) return SBLAS_E_HIP;
-                if (by_value) { // the coarse values of the strength test, in the assemble order
+                if (by_value && dev_agg) { // the coarse values of the strength test: the plan's own assembly, the same left-to-right sums
+                    if (val_next.alloc(p->dev, (size_t)nnzc * 8 + 256) != hipSuccess) return SBLAS_E_HIP;
+                    rc = sblas_hip_coo_plan_assemble(L->coo, s, d_val, val_next.at<double>());
+                    if (rc != SBLAS_OK) return rc;
+                } else if (by_value) { // the coarse values of the strength test, in the assemble order
                     std::vector<int32_t> perm((size_t)nnzl), run((size_t)nnzc + 1);
                     if (hipMemcpyAsync(perm.data(), c_perm, (size_t)nnzl * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
                         hipMemcpyAsync(run.data(), c_run, ((size_t)nnzc + 1) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -440,7 +544,23 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
         L->units = (int64_t)units.size();
         Segment seg[5] = {Segment(units), Segment(dpos), Segment(agg), Segment(aggptr), Segment(members)};
         size_t ib = 0;
-        if (upload_segments(L->ibuf, p->dev, s, seg, last ? 2 : 5, &ib) != hipSuccess) return SBLAS_E_HIP; // the coarsest has no aggregates
+        if (dev_agg) { // the same layout; only the units (and level 0's dpos) are uploaded, the rest is copied or made on the device
+            const size_t nc = (size_t)L->n_coarse;
+            seg[2].bytes = seg[4].bytes = (size_t)nl * 4, seg[3].bytes = (nc + 1) * 4;
+            for (int k = 0; k < (last ? 2 : 5); ++k) seg[k].offset = ib, ib += (seg[k].bytes + 15) / 16 * 16;
+            hipError_t e = L->ibuf.alloc(p->dev, ib);
+            if (e == hipSuccess) e = hipMemcpyAsync(L->ibuf.at<char>(), units.data(), seg[0].bytes, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess && l == 0) e = hipMemcpyAsync(L->ibuf.at<char>(seg[1].offset), dpos.data(), seg[1].bytes, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess && l > 0) {
+                amg_dpos_kernel<<<grid_of(nl), AMG_THREADS, 0, s>>>(nl, L->rowptr, L->colidx, L->ibuf.at<int32_t>(seg[1].offset));
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess && !last) e = hipMemcpyAsync(L->ibuf.at<char>(seg[2].offset), d_agg, seg[2].bytes, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && !last) e = hipMemcpyAsync(L->ibuf.at<char>(seg[3].offset), d_aggptr, seg[3].bytes, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && !last) e = hipMemcpyAsync(L->ibuf.at<char>(seg[4].offset), d_members, seg[4].bytes, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s); // the host vector of the units is read until here
+            if (e != hipSuccess) return SBLAS_E_HIP;
+        } else if (upload_segments(L->ibuf, p->dev, s, seg, last ? 2 : 5, &ib) != hipSuccess) return SBLAS_E_HIP; // the coarsest has no aggregates
         L->d_units = L->ibuf.at<Unit>(), L->dpos = L->ibuf.at<int32_t>(seg[1].offset);
         if (!last) L->agg = L->ibuf.at<int32_t>(seg[2].offset), L->aggptr = L->ibuf.at<int32_t>(seg[3].offset), L->members = L->ibuf.at<int32_t>(seg[4].offset);
         // doubles: wd | x0 | x1 (below level 0) | res (above the coarsest) | b, val (below level 0)
@@ -461,14 +581,9 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
         if (smoothed && !last) {
             const int64_t nc = L->n_coarse;
             // P_l: the COO plan of (row(e), agg[col(e)]) in stored order
-            std::vector<int32_t> trow((size_t)nnzl), tcol((size_t)nnzl);
-            for (int64_t i = 0; i < nl; ++i)
-                for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) trow[(size_t)e] = (int32_t)i, tcol[(size_t)e] = agg[(size_t)h_colidx[e]];
-            DeviceBuffer trip;
-            size_t tb = 0;
-            Segment tseg[2] = {Segment(trow), Segment(tcol)};
-            if (upload_segments(trip, p->dev, s, tseg, 2, &tb) != hipSuccess) return SBLAS_E_HIP;
-            rc = sblas_hip_coo_plan_create(p->dev, s, nl, nc, nnzl, trip.at<int32_t>(), trip.at<int32_t>(tseg[1].offset), SBLAS_COO_SUM, &L->coo);
+            rc = make_triplets(false);
+            if (rc != SBLAS_OK) return rc;
+            rc = sblas_hip_coo_plan_create(p->dev, s, nl, nc, nnzl, d_trow, d_tcol, SBLAS_COO_SUM, &L->coo);
             if (rc != SBLAS_OK) return rc;
             int64_t ci[8], gi[12];
             sblas_hip_coo_plan_info(L->coo, ci);
@@ -478,7 +593,8 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
             // the units of P's rows, and of R's once its row pointer is known; R_l = P_l^T by the device transpose
             std::vector<int32_t> hp_rowptr, hp_colidx, hr_rowptr((size_t)nc + 1);
             int64_t pbad = -1;
-            if (fetch_structure(s, nl, nnzp, L->p_rowptr, L->p_colidx, hp_rowptr, hp_colidx, &pbad) != SBLAS_OK) return SBLAS_E_HIP;
+            if ((dev_agg ? fetch_rowptr(s, nl, nnzp, L->p_rowptr, hp_rowptr) : fetch_structure(s, nl, nnzp, L->p_rowptr, L->p_colidx, hp_rowptr, hp_colidx, &pbad)) != SBLAS_OK)
+                return SBLAS_E_HIP;
             const size_t i_rp = ((size_t)nc + 1 + 3) / 4 * 4, i_e = ((size_t)nnzp + 3) / 4 * 4; // int32 counts, 16-byte steps
             DeviceBuffer tws;
             const size_t ws_bytes = sblas_hip_csr_transpose_workspace(nl, nc, nnzp);
@@ -515,10 +631,11 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
             if (rc != SBLAS_OK) return rc;
             sblas_hip_spgemm_plan_info(L->rap, gi);
             sblas_hip_spgemm_plan_csr(L->rap, &c_rp, &c_ci);
-            const int64_t nnzc = gi[3];
+            const int64_t nnzc = nnz_next = gi[3];
             L->bytes += (size_t)gi[10];
             int64_t cbad = -1;
-            if (fetch_structure(s, nc, nnzc, c_rp, c_ci, c_rowptr, c_colidx, &cbad) != SBLAS_OK) return SBLAS_E_HIP;
+            if ((dev_agg ? fetch_rowptr(s, nc, nnzc, c_rp, c_rowptr) : fetch_structure(s, nc, nnzc, c_rp, c_ci, c_rowptr, c_colidx, &cbad)) != SBLAS_OK)
+                return SBLAS_E_HIP;
             const size_t v_p = ((size_t)nnzp * 8 + 255) / 256 * 256, v_ap = ((size_t)L->nnz_ap * 8 + 255) / 256 * 256;
             if (L->tval.alloc(p->dev, 2 * v_p + v_ap + 256) != hipSuccess) return SBLAS_E_HIP;
             L->p_val = L->tval.at<double>(), L->r_val = L->tval.at<double>(v_p), L->ap_val = L->tval.at<double>(2 * v_p);
@@ -530,8 +647,8 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
                 launch_pvalues(s, *L, p->omega_p, d_val, t_tmp.at<double>());
                 rc = smoothed_values(s, *p, *L, d_val, t_tmp.at<double>(), val_next.at<double>());
                 if (rc != SBLAS_OK) return rc;
-                c_val.resize((size_t)nnzc);
-                if (hipMemcpyAsync(c_val.data(), val_next.at<double>(), (size_t)nnzc * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                if (!dev_agg) c_val.resize((size_t)nnzc); // the host rule reads them; the device's aggregation reads val_next in place
+                if ((!dev_agg && hipMemcpyAsync(c_val.data(), val_next.at<double>(), (size_t)nnzc * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
                     hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess)
                     return SBLAS_E_HIP;
             }
@@ -540,9 +657,9 @@ int sblas_hip_amg_plan_create_ex(int dev, void *stream, int64_t n, int64_t nnz, 
         }
         p->lv.push_back(std::move(L));
         if (last) break;
-        nl = p->lv.back()->n_coarse, nnzl = (int64_t)c_colidx.size();
+        nl = p->lv.back()->n_coarse, nnzl = nnz_next;
         h_rowptr.swap(c_rowptr), h_colidx.swap(c_colidx), h_val.swap(c_val);
-        if (smoothed && by_value) { // the next level's values stay on the device for its own chain
+        if (by_value && (smoothed || dev_agg)) { // the next level's values stay on the device for its own chain (and aggregation)
             DeviceBuffer done(std::move(val_here));
             val_here = std::move(val_next);
             d_val = val_here.at<double>();
@@ -594,7 +711,7 @@ int sblas_hip_amg_plan_options(const void *plan, double out[4])
 {
     const AmgPlan *p = static_cast<const AmgPlan *>(plan);
     if (!p || !out) return SBLAS_E_INVALID;
-    out[0] = (double)p->prolongator, out[1] = p->omega_p, out[2] = p->min_reduction, out[3] = 0.0;
+    out[0] = (double)p->prolongator, out[1] = p->omega_p, out[2] = p->min_reduction, out[3] = (double)p->aggregation;
     return SBLAS_OK;
 }
 

@@ -17,23 +17,28 @@
 
 namespace sblas {
 
+// theta * max_{k != i} |a_ik|, the product rounded: the maximum by `a > m` from m = 0, so a NaN entry is never the
+// maximum (and, through |a| >= bound, never strong); a row with no off-diagonal entry has bound 0
+void amg_strength_bounds(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, std::vector<double> &bound)
+{
+    bound.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        double m = 0.0;
+        for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            const double a = fabs(val[e]);
+            if (colidx[e] != i && a > m) m = a;
+        }
+        bound[(size_t)i] = theta * m;
+    }
+}
+
 int64_t amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
                       uint32_t level, int32_t *agg, std::vector<int32_t> &aggptr, int32_t *members)
 {
     const bool by_value = val != nullptr && theta > 0.0;
     // strong(i, e): entry e of row i is a strong off-diagonal one.  Only row i's own entries are consulted.
-    std::vector<double> bound; // theta * max_{k != i} |a_ik|, the product rounded
-    if (by_value) {
-        bound.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            double m = 0.0;
-            for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
-                const double a = fabs(val[e]);
-                if (colidx[e] != i && a > m) m = a;
-            }
-            bound[(size_t)i] = theta * m;
-        }
-    }
+    std::vector<double> bound;
+    if (by_value) amg_strength_bounds(n, rowptr, colidx, val, theta, bound);
     const auto strong = [&](int64_t i, int64_t e) { return colidx[e] != i && (!by_value || fabs(val[e]) >= bound[(size_t)i]); };
 
     // roots: the greedy maximal independent set in descending priority (no two vertices tie)
@@ -69,6 +74,41 @@ int64_t amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, c
     std::vector<int32_t> fill(aggptr.begin(), aggptr.end() - 1);
     for (int64_t v = 0; v < n; ++v) members[fill[(size_t)agg[v]]++] = (int32_t)v;
     return n_agg;
+}
+
+int64_t amg_roots_rounds(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed, uint32_t level,
+                         unsigned char *root)
+{
+    const bool by_value = val != nullptr && theta > 0.0;
+    std::vector<double> bound;
+    if (by_value) amg_strength_bounds(n, rowptr, colidx, val, theta, bound);
+    const uint32_t salt = color_salt(seed + level);
+    std::vector<int8_t> state((size_t)n, -1); // -1 undecided, 0 non-root, 1 root: final once written
+    std::vector<int32_t> open((size_t)n), still;
+    std::vector<std::pair<int32_t, int8_t>> decided;
+    for (int64_t v = 0; v < n; ++v) open[(size_t)v] = (int32_t)v;
+    int64_t rounds = 0;
+    while (!open.empty()) {
+        decided.clear(), still.clear();
+        for (const int32_t v : open) { // reads only the states of the rounds before this one
+            const uint32_t hv = color_priority((uint32_t)v, salt);
+            bool non_root = false, wait = false;
+            for (int64_t e = rowptr[v]; e < rowptr[v + 1] && !non_root; ++e) {
+                const int32_t u = colidx[e];
+                if (u == v || (by_value && !(fabs(val[e]) >= bound[(size_t)v])) || !(color_priority((uint32_t)u, salt) > hv)) continue;
+                if (state[(size_t)u] == 1) non_root = true;
+                else if (state[(size_t)u] < 0) wait = true;
+            }
+            if (non_root || !wait) decided.emplace_back(v, non_root ? 0 : 1);
+            else still.push_back(v);
+        }
+        if (decided.empty()) return -1; // cannot happen: the open vertex of greatest priority waits for nobody
+        for (const auto &d : decided) state[(size_t)d.first] = d.second;
+        open.swap(still);
+        ++rounds;
+    }
+    for (int64_t v = 0; v < n; ++v) root[v] = state[(size_t)v] == 1;
+    return rounds;
 }
 
 } // namespace sblas
@@ -313,6 +353,22 @@ int sblas_amg_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx,
     std::vector<int32_t> ptr;
     *n_agg = amg_aggregate(n, rowptr, colidx, val, theta, seed, level, agg, ptr, members);
     for (size_t a = 0; a < ptr.size(); ++a) aggptr[a] = ptr[a];
+    return SBLAS_OK;
+}
+
+int sblas_amg_roots_rounds_ref(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *val, double theta, uint32_t seed,
+                               uint32_t level, unsigned char *root_out, int64_t *rounds, int64_t *bad_row)
+{
+    if (bad_row) *bad_row = -1;
+    if (rounds) *rounds = 0;
+    if (n < 0 || n > INT_MAX || !rowptr || !rounds) return SBLAS_E_INVALID;
+    if (!amg_theta_ok(theta) || (theta > 0.0 && !val)) return SBLAS_E_INVALID;
+    if (n > 0 && !root_out) return SBLAS_E_INVALID;
+    const int rc = sblas_ilu0_check(n, rowptr, colidx, nullptr, bad_row);
+    if (rc != SBLAS_OK) return rc;
+    const int64_t r = amg_roots_rounds(n, rowptr, colidx, val, theta, seed, level, root_out);
+    if (r < 0) return SBLAS_E_INTERNAL;
+    *rounds = r;
     return SBLAS_OK;
 }
 

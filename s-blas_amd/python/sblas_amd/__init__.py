@@ -73,6 +73,10 @@ EXPORTS_AMG_SA = [
     "sblas_amg_keep_level", "sblas_amg_prolongator_ref", "sblas_amg_transfer_ref", "sblas_amg_cycle_sa_ref",
     "sblas_hip_amg_plan_create_ex", "sblas_hip_amg_plan_transfer", "sblas_hip_amg_plan_options", "sblas_hip_amg_pvalues_f64",
 ]
+# what include/sblas_hip_amg_dev.h declares (aggregation on the device)
+EXPORTS_AMG_DEV = [
+    "sblas_amg_roots_rounds_ref", "sblas_hip_amg_aggregate_workspace", "sblas_hip_amg_aggregate_i32", "sblas_hip_amg_plan_create_dev",
+]
 
 
 class SblasError(RuntimeError):
@@ -430,6 +434,16 @@ def lib():
     L.sblas_hip_amg_plan_options.argtypes = [vp, C.POINTER(f64)]
     L.sblas_hip_amg_pvalues_f64.restype = C.c_int
     L.sblas_hip_amg_pvalues_f64.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.sblas_amg_roots_rounds_ref.restype = C.c_int
+    L.sblas_amg_roots_rounds_ref.argtypes = [i64, vp, vp, vp, f64, C.c_uint32, C.c_uint32, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_hip_amg_aggregate_workspace.restype = sz
+    L.sblas_hip_amg_aggregate_workspace.argtypes = [i64, i64]
+    L.sblas_hip_amg_aggregate_i32.restype = C.c_int
+    L.sblas_hip_amg_aggregate_i32.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, sz,
+                                              C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_hip_amg_plan_create_dev.restype = C.c_int
+    L.sblas_hip_amg_plan_create_dev.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, i64, C.c_int, C.c_uint32, C.c_int, f64, f64, C.c_int,
+                                                C.POINTER(vp), C.POINTER(i64)]
     _lib = L
     return L
 
@@ -874,6 +888,72 @@ def amg_aggregate(n, rowptr, colidx, val=None, theta=0.0, seed=0, level=0):
     if rc != 0:
         raise _bad_structure("sblas_amg_aggregate", rc, bad.value)
     return agg[:n], aggptr[:n_agg.value + 1].copy(), members[:n]
+
+
+AMG_AGGREGATIONS = {"host": 0, "device": 1}                                # SBLAS_AMG_AGG_*
+
+
+def amg_roots_rounds_ref(n, rowptr, colidx, val=None, theta=0.0, seed=0, level=0):
+    """The aggregation rule in synchronous rounds on host arrays (sblas_amg_roots_rounds_ref) -> (root, rounds): root[v]
+    is True for the roots of amg_aggregate, rounds counts the rounds that decided a vertex -- the upper bound of
+    amg_aggregate_device's.  The arguments and refusals of amg_aggregate."""
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    if len(rowptr) != n + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (len(rowptr), n))
+    if val is not None:
+        val = np.ascontiguousarray(val, np.float64)
+        if len(val) != len(colidx):
+            raise SblasError("val has %d entries, colidx %d" % (len(val), len(colidx)))
+    root = np.zeros(max(n, 1), np.uint8)
+    rounds, bad = C.c_int64(), C.c_int64(-1)
+    rc = lib().sblas_amg_roots_rounds_ref(n, rowptr.ctypes.data, colidx.ctypes.data if len(colidx) else None,
+                                          val.ctypes.data if val is not None else None, float(theta), int(seed) & 0xffffffff,
+                                          int(level) & 0xffffffff, root.ctypes.data, C.byref(rounds), C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_amg_roots_rounds_ref", rc, bad.value)
+    return root[:n].astype(bool), int(rounds.value)
+
+
+def amg_aggregate_device(n, rowptr, colidx, val=None, theta=0.0, seed=0, level=0, stream=None):
+    """One level's aggregation on the device (sblas_hip_amg_aggregate_i32) -> (agg, aggptr, members, rounds): torch int32
+    tensors equal to amg_aggregate's, and the Jones-Plassmann rounds taken (at most amg_roots_rounds_ref's).  rowptr,
+    colidx (int32) and val (float64, needed when theta > 0) are GPU tensors.  The entry point trusts the structure, so
+    it is checked here on the host first (sblas_ilu0_check): a refused one raises an SblasError with .bad_row and
+    nothing is launched.  Synchronises."""
+    import torch
+    nnz = _structure(n, rowptr, colidx)
+    theta = float(theta)
+    if not 0.0 <= theta <= 1.0:
+        raise SblasError("theta must be in [0, 1], not %r" % (theta,))
+    if theta > 0.0 and val is None:
+        raise SblasError("theta > 0 needs val, the values the strength test reads")
+    device = rowptr.device
+    if colidx.device != device or not rowptr.is_contiguous() or not colidx.is_contiguous():
+        raise SblasError("rowptr and colidx must be contiguous tensors on one device")
+    if val is not None:
+        _krylov_vector("val", val, nnz, device)
+    h_rp, h_ci = rowptr.cpu().numpy(), colidx.cpu().numpy()
+    bad = C.c_int64(-1)
+    if n > 0 and int(h_rp[n]) != nnz:
+        raise _bad_structure("sblas_hip_amg_aggregate_i32", 1, n - 1)
+    rc = lib().sblas_ilu0_check(n, h_rp.ctypes.data, h_ci.ctypes.data if nnz else None, None, C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_hip_amg_aggregate_i32", rc, bad.value)
+    agg = torch.empty(n, dtype=torch.int32, device=device)
+    aggptr = torch.empty(n + 1, dtype=torch.int32, device=device)
+    members = torch.empty(n, dtype=torch.int32, device=device)
+    bytes_ = int(lib().sblas_hip_amg_aggregate_workspace(n, nnz))
+    ws = torch.empty(max(bytes_, 16), dtype=torch.uint8, device=device)
+    n_agg, rounds = C.c_int64(), C.c_int64()
+    with torch.cuda.device(device):
+        rc = lib().sblas_hip_amg_aggregate_i32(-1, _stream(stream), n, nnz, rowptr.data_ptr() if n else None, colidx.data_ptr() if nnz else None,
+                                               val.data_ptr() if val is not None and theta > 0.0 and nnz else None, theta,
+                                               int(seed) & 0xffffffff, int(level) & 0xffffffff, agg.data_ptr() if n else None,
+                                               aggptr.data_ptr(), members.data_ptr() if n else None, ws.data_ptr(), bytes_, C.byref(n_agg),
+                                               C.byref(rounds))
+    check(rc, "sblas_hip_amg_aggregate_i32")
+    return agg, aggptr[:n_agg.value + 1], members, int(rounds.value)
 
 
 def amg_launches(levels, nu=1, coarse_sweeps=8):
@@ -2415,13 +2495,17 @@ class AmgPlan:
     prolong_omega D^-1 A) T over the same aggregates, R = P^T, the coarse matrix R (A P) by two SpGEMM plans, the
     transfers of a cycle one row-product kernel; transfer(l) shows P and R and amg_cycle_sa_ref restates the cycle.
     min_reduction in [0, 1) is the coarsening guard (amg_keep_level): a level is kept only when it removes at least that
-    share of the rows; None means 0 (any reduction, as before) for a plain plan and 0.2 for a smoothed one."""
+    share of the rows; None means 0 (any reduction, as before) for a plain plan and 0.2 for a smoothed one.
+    aggregation="device" (sblas_hip_amg_plan_create_dev, include/sblas_hip_amg_dev.h) aggregates every level on the device
+    in Jones-Plassmann rounds and builds the same plan, array for array; "host" (the default) is create as it was."""
 
     def __init__(self, n, rowptr, colidx, val=None, theta=0.0, coarse_max=64, max_levels=20, seed=0, stream=None, prolongator="plain",
-                 prolong_omega=AMG_PROLONG_OMEGA, min_reduction=None):
+                 prolong_omega=AMG_PROLONG_OMEGA, min_reduction=None, aggregation="host"):
         import torch
         if prolongator not in AMG_PROLONGATORS:
             raise SblasError("prolongator must be 'plain' or 'smoothed', not %r" % (prolongator,))
+        if aggregation not in AMG_AGGREGATIONS:
+            raise SblasError("aggregation must be 'host' or 'device', not %r" % (aggregation,))
         if min_reduction is None:                                          # plain: today's rule, any reduction keeps a level
             min_reduction = AMG_SMOOTHED_MIN_REDUCTION if prolongator == "smoothed" else 0.0
         if not 0.0 <= float(min_reduction) < 1.0:
@@ -2445,7 +2529,11 @@ class AmgPlan:
             args = (-1, _stream(stream), n, self.nnz, rowptr.data_ptr() if n else None, colidx.data_ptr() if self.nnz else None,
                     val.data_ptr() if val is not None and theta > 0.0 and self.nnz else None, theta, int(coarse_max), int(max_levels),
                     int(seed) & 0xffffffff)
-            if prolongator == "plain" and float(min_reduction) == 0.0:     # the entry point as it was
+            if aggregation != "host":
+                name = "sblas_hip_amg_plan_create_dev"
+                rc = lib().sblas_hip_amg_plan_create_dev(*args, AMG_PROLONGATORS[prolongator], float(prolong_omega), float(min_reduction),
+                                                         AMG_AGGREGATIONS[aggregation], C.byref(h), C.byref(bad))
+            elif prolongator == "plain" and float(min_reduction) == 0.0:   # the entry point as it was
                 name = "sblas_hip_amg_plan_create"
                 rc = lib().sblas_hip_amg_plan_create(*args, C.byref(h), C.byref(bad))
             else:
@@ -2464,7 +2552,8 @@ class AmgPlan:
         return dict(n=int(out[0]), nnz=int(out[1]), levels=int(out[2]), nu=int(out[3]), coarse_sweeps=int(out[4]), launches=int(out[5]),
                     rows=int(out[6]), entries=int(out[7]), bytes=int(out[8]), smoother=("jacobi", "l1")[out[9]], ready=bool(out[10]),
                     coarsest=int(out[11]), operator_complexity=(out[7] / out[1] if out[1] else 1.0),
-                    prolongator=("plain", "smoothed")[int(opt[0])], prolong_omega=float(opt[1]), min_reduction=float(opt[2]))
+                    prolongator=("plain", "smoothed")[int(opt[0])], prolong_omega=float(opt[1]), min_reduction=float(opt[2]),
+                    aggregation=("host", "device")[int(opt[3])])
 
     def transfer(self, l):
         """A smoothed plan's transfer operators between level l and l + 1 as torch views that live as long as the plan

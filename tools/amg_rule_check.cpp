@@ -9,7 +9,9 @@
 // the launch counts against a hand count.  For smoothed aggregation it holds the coarsening guard against its expression,
 // builds P (sblas_amg_prolongator_ref, counted first and then written into arrays of exactly that size), R = P^T and the two
 // products in a naive restatement of the pinned orders, and runs sblas_amg_transfer_ref and sblas_amg_cycle_sa_ref
-// against the written order once more, n = 0 and 1 included.
+// against the written order once more, n = 0 and 1 included.  For the device aggregation it runs the rule in
+// synchronous rounds (sblas_amg_roots_rounds_ref) on the same matrices with a root array of exactly n bytes and holds its
+// roots against sblas_amg_aggregate's.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -386,6 +388,29 @@ static void check_smoothed(const char *name, const Csr &a, double theta, int64_t
     }
 }
 
+// the rule in synchronous rounds out of exact-size arrays: its roots are the greedy walk's, numbered in ascending order
+static void check_rounds(const char *name, const Csr &a, double theta)
+{
+    const int64_t n = a.n;
+    const uint32_t salts[3][2] = {{0, 0}, {7, 0}, {0, 3}};
+    for (const auto &sl : salts) {
+        Level L;
+        const int64_t n_agg = aggregate(a, theta, sl[0], sl[1], L);
+        std::vector<unsigned char> root((size_t)n, 2);
+        int64_t rounds = -1, row = 0;
+        const int rc = sblas_amg_roots_rounds_ref(n, a.rowptr.data(), a.colidx.data(), theta > 0 ? a.val.data() : nullptr, theta, sl[0], sl[1],
+                                                  root.data(), &rounds, &row);
+        expect(rc == SBLAS_OK && row == -1, name);
+        expect(n == 0 ? rounds == 0 : (rounds >= 1 && rounds <= n), "the rounds that decided a vertex: one at least, n at most");
+        int64_t k = 0;
+        for (int64_t v = 0; v < n; ++v) {
+            expect(root[(size_t)v] <= 1, "every vertex is decided");
+            if (root[(size_t)v] == 1) expect(L.agg[(size_t)v] == k++, "the roots carry the aggregates' numbers in ascending order");
+        }
+        expect(k == n_agg, "one root an aggregate");
+    }
+}
+
 int main()
 {
     int64_t lim[8];
@@ -492,6 +517,29 @@ int main()
             if (g.colidx[(size_t)e] == 7) g.val[(size_t)e] = 0.0;
         expect(sblas_amg_wd_ref(16, g.rowptr.data(), g.colidx.data(), g.val.data(), SBLAS_AMG_JACOBI, 0.5, wd.data(), &row) == SBLAS_OK && row == 7,
                "a zero diagonal is reported");
+    }
+    // the rule in synchronous rounds: the same matrices, and its refusals
+    check_rounds("rounds n = 0", empty, 0.0);
+    check_rounds("rounds n = 1", one, 0.0);
+    check_rounds("rounds diagonal", diag, 0.0);
+    check_rounds("rounds tridiagonal", tri, 0.0);
+    check_rounds("rounds grid", grid(12, 1.0, 1.0), 0.0);
+    check_rounds("rounds clique", clique, 0.0);
+    check_rounds("rounds star", star, 0.0);
+    check_rounds("rounds anisotropic grid", grid(10, 1.0, 0.01), 0.25);
+    check_rounds("rounds anisotropic grid, theta 1", grid(10, 1.0, 0.01), 1.0);
+    {
+        Csr g = grid(4, 1.0, 1.0);
+        std::vector<unsigned char> root(16);
+        int64_t rounds = 0, row = -1;
+        expect(sblas_amg_roots_rounds_ref(16, g.rowptr.data(), g.colidx.data(), g.val.data(), NAN, 0, 0, root.data(), &rounds, &row) == SBLAS_E_INVALID &&
+                   sblas_amg_roots_rounds_ref(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.25, 0, 0, root.data(), &rounds, &row) == SBLAS_E_INVALID &&
+                   sblas_amg_roots_rounds_ref(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.0, 0, 0, nullptr, &rounds, &row) == SBLAS_E_INVALID &&
+                   sblas_amg_roots_rounds_ref(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.0, 0, 0, root.data(), nullptr, &row) == SBLAS_E_INVALID,
+               "rounds_ref refusals");
+        std::swap(g.colidx[(size_t)g.rowptr[5]], g.colidx[(size_t)g.rowptr[5] + 1]);
+        expect(sblas_amg_roots_rounds_ref(16, g.rowptr.data(), g.colidx.data(), nullptr, 0.0, 0, 0, root.data(), &rounds, &row) == SBLAS_E_INVALID && row == 5,
+               "rounds_ref names an unsorted row");
     }
     if (bad) return fprintf(stderr, "amg_rule_check: %d failures\n", bad), 1;
     printf("amg_rule_check: ok\n");
