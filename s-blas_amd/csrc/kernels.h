@@ -73,6 +73,60 @@ __device__ __forceinline__ void store_rows_c(T *__restrict__ C, int64_t ldc, int
     }
 }
 
+// The same epilogue in two steps for the 1024-thread LDS-tiled kernel and its 64-column halves, either layout of C:
+// panel_c_fetch issues EVERY old-C load of the thread into registers (none at all when beta == 0) and returns without
+// using them, so the kernel can put barriers and the parking of its sums between the two steps and pay one memory
+// round trip per panel instead of one per trip; panel_c_store applies them.  The thread -> (row, column) map is fixed
+// and needs no division: row-major C as store_rows_c<64> with 1024 threads (a wave on the 64 columns of one row, rows
+// 16 apart per trip); column-major C with a half-wave on 32 consecutive rows of one column (trip i: rows 32 (i / 2) ..,
+// column 32 (i % 2) + tid / 32).  RMAX / 16 trips cover 64 columns x RMAX rows in both; trips past nrows are dead for
+// the whole workgroup.  Same fma(beta, old, alpha * sum) as store_rows_c.
+template <bool RC> __device__ __forceinline__ void panel_c_map(int i, int &r, int &j)
+{
+    const int tid = (int)threadIdx.x;
+    if (RC) r = (tid >> 6) + 16 * i, j = tid & 63;
+    else r = 32 * (i >> 1) + (tid & 31), j = 32 * (i & 1) + (tid >> 5);
+}
+template <bool RC> __device__ __forceinline__ int64_t panel_c_index(int64_t ldc, int64_t row0, int64_t col0, int r, int j)
+{
+    return RC ? (row0 + r) * ldc + (col0 + j) : (col0 + j) * ldc + (row0 + r);
+}
+template <bool RC, int TRIPS>
+__device__ __forceinline__ void panel_c_fetch(const double *__restrict__ C, int64_t ldc, int64_t row0, int64_t col0, int nrows,
+                                              int ncols, double beta, double (&old)[TRIPS])
+{
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) old[i] = 0.0;
+    if (beta == 0.0) return; // C is not read
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) {
+        int r, j;
+        panel_c_map<RC>(i, r, j);
+        if (r < nrows && j < ncols) old[i] = C[panel_c_index<RC>(ldc, row0, col0, r, j)];
+    }
+}
+template <bool RC, int TRIPS, typename At>
+__device__ __forceinline__ void panel_c_store(double *__restrict__ C, int64_t ldc, int64_t row0, int64_t col0, int nrows,
+                                              int ncols, double alpha, double beta, const double (&old)[TRIPS], At at)
+{
+    double sum[TRIPS]; // (read ahead of the stores: one LDS round trip, not one per trip)
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) {
+        int r, j;
+        panel_c_map<RC>(i, r, j);
+        sum[i] = (r < nrows && j < ncols) ? at(r, j) : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) {
+        int r, j;
+        panel_c_map<RC>(i, r, j);
+        if (r < nrows && j < ncols) {
+            const double sres = alpha * sum[i];
+            C[panel_c_index<RC>(ldc, row0, col0, r, j)] = (beta == 0.0) ? sres : c_fma(beta, old[i], sres);
+        }
+    }
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one).  Give every XCD one contiguous
 // range of panels so that neighbouring panels -- which read overlapping Bt rows -- share an L2 (speed only;
 // any placement is correct).  Bijective for every panel count.

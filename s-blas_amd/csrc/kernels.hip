@@ -1079,6 +1079,12 @@ __global__ __launch_bounds__(1024) void spmm_window6_kernel(
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) window_wait6<0>(wca[g], wva[g], wcb[g], wvb[g]); // retire the unused last fetches
+    // the old values of C (beta != 0), every load of the thread at once and ahead of the order check, barriers V and F
+    // and the parking of the sums, which run under their round trip; they land in registers the tile loop has just
+    // given up (windows, block scratch), so nothing is held across the loop
+    const int nrows = min(panel_rows, rows - row0);
+    double oldc[RMAX / 16];
+    panel_c_fetch<RC>(C, ldc, row0, col0, nrows, min(64, n - col0), beta, oldc);
     int bad = viol != 0ull ? 1 : 0;
 #pragma unroll
     for (int g = 0; g < G; ++g)
@@ -1091,10 +1097,16 @@ __global__ __launch_bounds__(1024) void spmm_window6_kernel(
     // park the panel as [column][row] in the (now dead) tile buffers and write it back along rows, one 64-column half
     // at a time
     double *ctile = smem;
-    const int nrows = min(panel_rows, rows - row0);
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
         const int colh = col0 + 64 * h;
+        const int ncols = min(64, n - colh);
+        if (h > 0) {
+            panel_c_fetch<RC>(C, ldc, row0, colh, nrows, ncols, beta, oldc); // (the previous half's are used up)
+            __syncthreads();                                                 // the previous half has been written back
+        }
+        // (the two cases are kept apart down to barrier F: with the fallback's loads and the parking in one block the
+        //  compiler puts a vmcnt(0) in front of the parking, and the old C values are waited for there)
         if (fell_back) {
             // recompute straight from L2, one column per lane: acc[h][g][j] <- row 4g+j of the wave
             const unsigned lane_off = (unsigned)(colh + lane);
@@ -1111,14 +1123,13 @@ __global__ __launch_bounds__(1024) void spmm_window6_kernel(
                     }
                     acc[h][g][j] = row_direct(colidx, val, Bt, ld32, lane_off, lane, a, b);
                 }
-        }
-        if (h > 0) __syncthreads(); // the previous half has been written back
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            if (fell_back) {
+            for (int g = 0; g < G; ++g)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) ctile[lane * (RMAX + 1) + wave * RW + 4 * g + j] = acc[h][g][j];
-            } else {
+        } else {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
                 const int rr = wave * RW + 4 * g + q;
                 ctile[(2 * k) * (RMAX + 1) + rr] = acc[h][g][0];
                 ctile[(2 * k + 1) * (RMAX + 1) + rr] = acc[h][g][1];
@@ -1127,21 +1138,9 @@ __global__ __launch_bounds__(1024) void spmm_window6_kernel(
             }
         }
         __syncthreads(); // F
-        const int ncols = min(64, n - colh);
-        // (fetching the old C values in the prologue, to take their HBM latency out of the epilogue, did not pay: the
-        //  registers they hold across the tile loop spill)
-        if constexpr (RC)
-            store_rows_c<64>(C, ldc, row0, colh, panel_rows, nrows, ncols, 1024, alpha, beta,
-                             [&](int r, int j) { return ctile[j * (RMAX + 1) + r]; }, [](int) { return true; });
-        else
-        for (int idx = tid; idx < 64 * panel_rows; idx += 1024) {
-            const int r = idx % panel_rows, j = idx / panel_rows;
-            if (r < nrows && j < ncols) {
-                double *dst = C + (int64_t)(colh + j) * ldc + (row0 + r);
-                const double sres = alpha * ctile[j * (RMAX + 1) + r];
-                *dst = (beta == 0.0) ? sres : fma(beta, *dst, sres);
-            }
-        }
+        // (fetching the old C values in the PROLOGUE did not pay: the registers they hold across the tile loop spill)
+        panel_c_store<RC>(C, ldc, row0, colh, nrows, ncols, alpha, beta, oldc,
+                          [&](int r, int j) { return ctile[j * (RMAX + 1) + r]; });
     }
 }
 
