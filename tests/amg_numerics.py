@@ -1,6 +1,7 @@
 """What the AMG tests share: the cases, the aggregation restated as a scalar loop, the hierarchy built in numpy from a set
-of aggregates, the V-cycle restated with the row sums in lane order, and the solver loops composed from parts.  No GPU
-and no library call in here (fma is the C library's, by ctypes: Python's math.fma where it exists)."""
+of aggregates, the V-cycle restated with the row sums in lane order, and the plain host loops "it solves" is held
+against (the loops composed from parts are in solver_compose.py).  No GPU and no library call in here (fma is the C
+library's, by ctypes: Python's math.fma where it exists)."""
 import ctypes
 import ctypes.util
 import math
@@ -275,70 +276,17 @@ def launches(levels, nu=1, coarse_sweeps=8):
     return 0 if levels == 0 else (levels - 1) * (2 * nu + 3) + coarse_sweeps
 
 
-# ---- the solver loops composed from parts: matvec(v), apply(v), dot(a, b) on numpy vectors --------------------------------
-def composed_pcg(matvec, apply, dot, b, x0, rtol, max_iter):
-    tol = max(rtol * math.sqrt(dot(b, b)), 0.0)
-    x = x0.copy()
-    r = b - matvec(x)
-    rnorm = math.sqrt(dot(r, r))
-    if rnorm <= tol:
-        return x, 0, rnorm, "converged"
+# ---- the host loops "it solves" is held against (the loops composed from parts live in solver_compose.py) ------------------
+def host_pcg(n, rp, ci, val, b, apply, tol, limit=1000, x0=None):
+    """plain float64 PCG with M^-1 = apply -> (iterations until |r| <= tol |b|, x); from x = 0, or from the guess x0, which
+    is returned at once when it already meets the test"""
+    x, r, stop = np.zeros(n), b.copy(), tol * np.linalg.norm(b)
+    if x0 is not None:
+        x, r = x0.copy(), b - KN.matvec(n, rp, ci, val, x0)
+        if np.linalg.norm(r) <= stop:
+            return 0, x
     z = apply(r)
-    rho = dot(r, z)
-    p = z.copy()
-    it = 0
-    while True:
-        q = matvec(p)
-        alpha = rho / dot(p, q)
-        x = x + alpha * p
-        r = r - alpha * q
-        rnorm, it = math.sqrt(dot(r, r)), it + 1
-        if rnorm <= tol:
-            return x, it, rnorm, "converged"
-        if it >= max_iter:
-            return x, it, rnorm, "limit"
-        z = apply(r)
-        rho_new = dot(r, z)
-        beta, rho = rho_new / rho, rho_new
-        p = z + beta * p
-
-
-def composed_bicgstab(matvec, apply, dot, b, x0, rtol, max_iter):
-    tol = max(rtol * math.sqrt(dot(b, b)), 0.0)
-    x = x0.copy()
-    r = b - matvec(x)
-    rho = dot(r, r)
-    rnorm = math.sqrt(rho)
-    if rnorm <= tol:
-        return x, 0, rnorm, "converged"
-    rh, p, v = r.copy(), np.zeros_like(r), np.zeros_like(r)
-    alpha, beta, omega, it = 0.0, 0.0, 1.0, 0
-    while True:
-        p = r + beta * (p - omega * v)
-        ph = apply(p)
-        v = matvec(ph)
-        alpha = rho / dot(rh, v)
-        s = r - alpha * v
-        sh = apply(s)
-        t = matvec(sh)
-        tt = dot(t, t)
-        omega = 0.0 if tt == 0.0 and math.sqrt(dot(s, s)) <= tol else dot(t, s) / tt
-        x = (x + alpha * ph) + omega * sh
-        r = s - omega * t
-        rnorm, it = math.sqrt(dot(r, r)), it + 1
-        if rnorm <= tol:
-            return x, it, rnorm, "converged"
-        if it >= max_iter:
-            return x, it, rnorm, "limit"
-        rho_new = dot(rh, r)
-        beta, rho = (rho_new / rho) * (alpha / omega), rho_new
-
-
-def host_pcg(n, rp, ci, val, b, apply, tol, limit=1000):
-    """plain float64 PCG with M^-1 = apply -> (iterations until |r| <= tol |b|, x)"""
-    x, r = np.zeros(n), b.copy()
-    z = apply(r)
-    p, rz, stop = z.copy(), r @ z, tol * np.linalg.norm(b)
+    p, rz = z.copy(), r @ z
     for it in range(1, limit + 1):
         q = KN.matvec(n, rp, ci, val, p)
         alpha = rz / (p @ q)
@@ -351,60 +299,29 @@ def host_pcg(n, rp, ci, val, b, apply, tol, limit=1000):
     return limit + 1, x
 
 
-def composed_gmres(matvec, apply, dot, dots, b, x0, restart, rtol, max_iter):
-    """GMRES(restart) in the written order (gmres_numerics restates the scalar steps); dots(V, w) -> [(v_i, w)] by the single
-    pinned dot -> dict(x, status, iterations, restarts, rnorm, bnorm, columns, breakdown)"""
-    import gmres_numerics as GN
-    bb = dot(b, b)
-    bnorm = math.sqrt(bb)
-    tol = max(rtol * bnorm, 0.0)
-    x = x0.copy()
-    it = restarts = k = 0
-    result = lambda status, rnorm, why=None: dict(x=x, status=status, iterations=it, restarts=restarts, rnorm=rnorm, bnorm=bnorm, columns=k,
-                                                  breakdown=why)
-    if bb == 0.0:
-        x = np.zeros_like(x)
-        return result(GN.CONVERGED, 0.0)
-    r = b - matvec(x)
-    beta = math.sqrt(dot(r, r))
-    status = GN.begin_py(beta, tol, it, max_iter)
-    rnorm = beta
-    while status == GN.RUNNING:
-        V = [r / beta]
-        g, c, s = [beta], [], []
-        R = np.zeros((restart, restart))
-        k, why = 0, None
-        for j in range(restart):
-            w = matvec(apply(V[j]))
-            h = dots(V, w)
-            for i in range(j + 1):
-                w = w - h[i] * V[i]
-            c2 = dots(V, w)
-            h = [h[i] + c2[i] for i in range(j + 1)]
-            for i in range(j + 1):
-                w = w - c2[i] * V[i]
-            eta = math.sqrt(dot(w, w))
-            step = GN.step_py(j, h, eta, c, s, g, tol, it, max_iter)
-            status = step["status"]
-            if status == GN.BREAKDOWN:
-                why = step["breakdown"]
-                break
-            c, s, g, it, rnorm, k = step["c"], step["s"], step["g"], step["iterations"], step["rnorm"], j + 1
-            R[:k, j] = step["rcol"]
-            if status != GN.RUNNING:
-                break
-            with np.errstate(all="ignore"):
-                V.append(w / eta)
-        if k:                                                                # the close: x = x + M^-1 (V y)
-            y = GN.solve_py(R[:k, :k].tolist(), g)
-            u = y[0] * V[0]
-            for i in range(1, k):
-                u = u + y[i] * V[i]
-            x = x + apply(u)
-        if status != GN.RUNNING:
-            return result(status, rnorm, why)
-        r = b - matvec(x)                                                    # the restart, on the true residual
-        beta = math.sqrt(dot(r, r))
-        restarts, k, rnorm = restarts + 1, 0, beta
-        status = GN.begin_py(beta, tol, it, max_iter)
-    return result(status, rnorm, "beta" if status == GN.BREAKDOWN else None)
+def host_bicgstab(n, rp, ci, val, b, apply, tol, limit=1000, x0=None):
+    """plain float64 BiCGStab with M^-1 = apply, right-preconditioned -> (iterations until |r| <= tol |b|, x)"""
+    x = np.zeros(n) if x0 is None else x0.copy()
+    r = b - KN.matvec(n, rp, ci, val, x)
+    stop = tol * np.linalg.norm(b)
+    if np.linalg.norm(r) <= stop:
+        return 0, x
+    rh, p, v = r.copy(), np.zeros(n), np.zeros(n)
+    rho, alpha, omega = r @ r, 1.0, 1.0
+    beta = 0.0
+    for it in range(1, limit + 1):
+        p = r + beta * (p - omega * v)
+        ph = apply(p)
+        v = KN.matvec(n, rp, ci, val, ph)
+        alpha = rho / (rh @ v)
+        s = r - alpha * v
+        sh = apply(s)
+        t = KN.matvec(n, rp, ci, val, sh)
+        tt = t @ t
+        omega = (t @ s) / tt if tt != 0.0 else 0.0
+        x, r = x + alpha * ph + omega * sh, s - omega * t
+        if np.linalg.norm(r) <= stop:
+            return it, x
+        rho, old = rh @ r, rho
+        beta = (rho / old) * (alpha / omega)
+    return limit + 1, x

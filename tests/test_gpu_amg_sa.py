@@ -11,6 +11,7 @@ import pytest
 import amg_numerics as AN
 import amg_sa_numerics as SA
 import krylov_numerics as KN
+import solver_compose as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -269,33 +270,8 @@ def test_a_plain_plan_through_create_ex_is_the_old_creates(env, name):
 # ---------------------------------------------------------------------------------------------------------------------
 # in the solvers
 # ---------------------------------------------------------------------------------------------------------------------
-class Parts:
-    """the pieces a composed loop is built from: A v by the unplanned SpMV, M^-1 v by AmgPlan.apply, the pinned dot"""
-
-    def __init__(self, env, n, rp, ci, val):
-        S, torch, cuda = self.env = env
-        self.n = n
-        self.drp, self.dci, self.dval = up(torch, cuda, rp, ci, val)
-        self.amg = S.AmgPlan(n, self.drp, self.dci, prolongator="smoothed")
-        self.amg.setup(self.dval)
-
-    def matvec(self, v):
-        S, torch, cuda = self.env
-        dv, = up(torch, cuda, v)
-        q = torch.empty_like(dv)
-        S.spmv(self.n, self.n, self.drp, self.dci, self.dval, dv, 1.0, 0.0, q)
-        return q.cpu().numpy()
-
-    def apply(self, v):
-        S, torch, cuda = self.env
-        return self.amg.apply(up(torch, cuda, v)[0]).cpu().numpy()
-
-    def dot(self, a, b):
-        S, torch, cuda = self.env
-        return float(S.krylov_dot(*up(torch, cuda, a, b)).cpu().numpy()[0])
-
-    def dots(self, V, w):
-        return [self.dot(v, w) for v in V]
+def Parts(env, n, rp, ci, val):
+    return SC.Parts(env, n, rp, ci, val, "amg_smoothed", planned=False)
 
 
 @pytest.fixture(scope="module")
@@ -320,7 +296,7 @@ def test_krylov_with_a_smoothed_plan_equals_its_composition(env, lap, conv, meth
     M = lap if method == "pcg" else conv
     n, b, P = M["n"], M["b"], M["P"]
     x0 = 0.1 * np.random.default_rng(31).standard_normal(n)
-    loop = AN.composed_pcg if method == "pcg" else AN.composed_bicgstab
+    loop = SC.composed_pcg if method == "pcg" else SC.composed_bicgstab
     want_x, want_it, want_rnorm, want_status = loop(P.matvec, P.apply, P.dot, b, x0, RTOL, 1000)
     plan = S.KrylovPlan(n, P.drp, P.dci, method=method, precond=P.amg)
     info = plan.info()
@@ -347,7 +323,7 @@ def test_gmres_with_a_smoothed_plan_equals_its_composition(env, conv):
     n, b, P = conv["n"], conv["b"], conv["P"]
     x0 = 0.1 * np.random.default_rng(31).standard_normal(n)
     for restart in (30, 5):                                                 # 5: closes and restarts with a cycle in them
-        want = AN.composed_gmres(P.matvec, P.apply, P.dot, P.dots, b, x0, restart, RTOL, 1000)
+        want = SC.composed_gmres(P.matvec, P.apply, P.dot, P.dots, b, x0, restart, RTOL, 1000)
         plan = S.GmresPlan(n, P.drp, P.dci, restart=restart, precond=P.amg)
         info = plan.info()
         db, = up(torch, cuda, b)

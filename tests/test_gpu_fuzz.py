@@ -2,7 +2,8 @@
 alpha / beta, kernel-selection switches and value / index types against the oracle (the tool's docstring has the
 details; a failing case prints its parameters and `python tools/fuzz_parity.py --seed 3 --only K` replays it).
 SpMM and SpMV only: the plans added since (transpose, COO, SpGEMM, SDDMM, softmax, attention, the solves, ILU(0),
-colouring) have their randomised test in tests/test_gpu_fuzz_plans.py (tools/fuzz_plans.py)."""
+colouring) have their randomised test in tests/test_gpu_fuzz_plans.py (tools/fuzz_plans.py), and the solvers on top of
+them (PCG, BiCGStab, GMRES, with ILU(0) and AMG inside) in tests/test_gpu_fuzz_solvers.py (tools/fuzz_solvers.py)."""
 import importlib.util
 import os
 

@@ -1,17 +1,16 @@
 """Restarted GMRES on the GPU (GmresPlan, gmres, gmres_dots, gmres_project, gmres_combine) against tests/gmres_numerics.py.
 
 Every bit is pinned, so most checks are ==: the multi-dot against the single pinned dot column by column, the projection
-and the combination against numpy's expression of the same shape, and a whole solve against a loop composed in this file
-from SpmvPlan / spmv, Ilu0Plan.apply, krylov_dot, numpy updates and the scalar step in Python floats.  Only "it solves"
+and the combination against numpy's expression of the same shape, and a whole solve against a loop composed (in
+tests/solver_compose.py) from SpmvPlan / spmv, Ilu0Plan.apply, krylov_dot, numpy updates and the scalar step in Python floats.  Only "it solves"
 holds a tolerance, and that one comes from a host GMRES's own residual."""
-import math
-
 import numpy as np
 import pytest
 
 import gmres_numerics as GN
 import ilu0_numerics as IN
 import krylov_numerics as KN
+import solver_compose as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -153,123 +152,7 @@ def test_projection_and_combination_round_twice(env, n):
 # ---------------------------------------------------------------------------------------------------------------------
 # the solver equals its own composition
 # ---------------------------------------------------------------------------------------------------------------------
-class Parts:
-    """the pieces a composed loop is built from: A v by SpmvPlan (or the unplanned SpMV), M^-1 v by Ilu0Plan.apply or a
-    numpy product with dinv, the pinned dot on the device; vectors live in numpy between them"""
-
-    def __init__(self, env, n, rp, ci, val, precond, planned=True):
-        S, torch, cuda = self.env = env
-        self.n, self.precond = n, precond
-        self.drp, self.dci, self.dval = up(torch, cuda, rp, ci, val)
-        self.spmv = S.SpmvPlan(n, n, self.drp, self.dci) if planned else None
-        self.ilu = self.lu = self.dinv = self.ddinv = None
-        if precond == "ilu0":
-            self.ilu = S.Ilu0Plan(n, self.drp, self.dci)
-            self.lu = self.ilu.factor(self.dval)
-        elif precond == "jacobi":
-            self.dinv = 1.0 / val[IN.check(n, rp, ci)[0]]
-            self.ddinv, = up(torch, cuda, self.dinv)
-
-    def plan(self, restart):
-        S = self.env[0]
-        return S.GmresPlan(self.n, self.drp, self.dci, restart=restart, spmv_plan=self.spmv,
-                           precond=self.ilu if self.precond == "ilu0" else self.precond)
-
-    def kw(self):
-        return dict(lu=self.lu, dinv=self.ddinv)
-
-    def matvec(self, v):
-        S, torch, cuda = self.env
-        dv, = up(torch, cuda, v)
-        q = torch.empty_like(dv)
-        if self.spmv is not None:
-            self.spmv(self.dval, dv, 1.0, 0.0, q)
-        else:
-            S.spmv(self.n, self.n, self.drp, self.dci, self.dval, dv, 1.0, 0.0, q)
-        return q.cpu().numpy()
-
-    def apply(self, v):
-        S, torch, cuda = self.env
-        if self.precond == "ilu0":
-            return self.ilu.apply(self.lu, up(torch, cuda, v)[0]).cpu().numpy()
-        return self.dinv * v if self.precond == "jacobi" else v
-
-    def dot(self, a, b):
-        S, torch, cuda = self.env
-        return float(S.krylov_dot(*up(torch, cuda, a, b)).cpu().numpy()[0])
-
-    def dots(self, dV, w):
-        """[(v_i, w)] by the single pinned dot, one call a column, against device copies of the columns"""
-        S, torch, cuda = self.env
-        dw, = up(torch, cuda, w)
-        out = torch.empty(len(dV), dtype=torch.float64, device=cuda)
-        for i, dv in enumerate(dV):
-            S.krylov_dot(dv, dw, out=out[i:i + 1])
-        return [float(v) for v in out.cpu().numpy()]
-
-    def destroy(self):
-        for p in (self.spmv, self.ilu):
-            if p is not None:
-                p.destroy()
-
-
-def composed_gmres(P, b, x0, restart, rtol, max_iter):
-    """GMRES(restart) in the written order -> dict(x, status, iterations, restarts, rnorm, bnorm, columns, breakdown)"""
-    S, torch, cuda = P.env
-    bb = P.dot(b, b)
-    bnorm = math.sqrt(bb)
-    tol = max(rtol * bnorm, 0.0)
-    x = x0.copy()
-    it = restarts = k = 0
-    result = lambda status, rnorm, why=None: dict(x=x, status=status, iterations=it, restarts=restarts, rnorm=rnorm, bnorm=bnorm, columns=k,
-                                                  breakdown=why)
-    if bb == 0.0:
-        x = np.zeros_like(x)
-        return result(GN.CONVERGED, 0.0)
-    r = b - P.matvec(x)
-    beta = math.sqrt(P.dot(r, r))
-    status = GN.begin_py(beta, tol, it, max_iter)
-    rnorm = beta
-    while status == GN.RUNNING:
-        V, dV = [r / beta], up(torch, cuda, r / beta)
-        g, c, s = [beta], [], []
-        R = np.zeros((restart, restart))
-        k, why = 0, None
-        for j in range(restart):
-            w = P.matvec(P.apply(V[j]))
-            h = P.dots(dV, w)
-            for i in range(j + 1):
-                w = w - h[i] * V[i]
-            c2 = P.dots(dV, w)
-            h = [h[i] + c2[i] for i in range(j + 1)]
-            for i in range(j + 1):
-                w = w - c2[i] * V[i]
-            eta = math.sqrt(P.dot(w, w))
-            step = GN.step_py(j, h, eta, c, s, g, tol, it, max_iter)
-            status = step["status"]
-            if status == GN.BREAKDOWN:                                       # column j is dropped; the ones before it stay
-                why = step["breakdown"]
-                break
-            c, s, g, it, rnorm, k = step["c"], step["s"], step["g"], step["iterations"], step["rnorm"], j + 1
-            R[:k, j] = step["rcol"]
-            if status != GN.RUNNING:
-                break
-            with np.errstate(all="ignore"):
-                V.append(w / eta)
-            dV += up(torch, cuda, V[-1])
-        if k:                                                                # the close: x = x + M^-1 (V y)
-            y = GN.solve_py(R[:k, :k].tolist(), g)
-            u = y[0] * V[0]
-            for i in range(1, k):
-                u = u + y[i] * V[i]
-            x = x + P.apply(u)
-        if status != GN.RUNNING:
-            return result(status, rnorm, why)
-        r = b - P.matvec(x)                                                  # the restart, on the true residual
-        beta = math.sqrt(P.dot(r, r))
-        restarts, k, rnorm = restarts + 1, 0, beta
-        status = GN.begin_py(beta, tol, it, max_iter)
-    return result(status, rnorm, "beta" if status == GN.BREAKDOWN else None)
+Parts, composed_gmres = SC.Parts, SC.composed_gmres
 
 
 def agrees(st, x, want):
@@ -297,7 +180,7 @@ def test_the_solver_equals_its_own_composition(env, matrix, restart, precond, pl
     S, torch, cuda = env
     n, rp, ci, val, b, x0 = problem(MATRICES[matrix]())
     P = Parts(env, n, rp, ci, val, precond, planned=planned)
-    want = composed_gmres(P, b, x0, restart, RTOL, 1000)
+    want = composed_gmres(P.matvec, P.apply, P.dot, P.dots, b, x0, restart, RTOL, 1000)
     plan = P.plan(restart)
     info = plan.info()
     db, dx = up(torch, cuda, b, x0)
@@ -356,7 +239,7 @@ def test_max_iter_stops_at_exactly_max_iter(env, conv):
     P = conv["P"]
     plan = P.plan(5)
     db, = up(torch, cuda, conv["b"])
-    want = composed_gmres(P, conv["b"], conv["x0"], 5, RTOL, 7)            # a full cycle, a restart, two columns, the limit
+    want = composed_gmres(P.matvec, P.apply, P.dot, P.dots, conv["b"], conv["x0"], 5, RTOL, 7)   # a full cycle, a restart, two columns, the limit
     assert (want["status"], want["iterations"], want["restarts"], want["columns"]) == ("limit", 7, 1, 2)
     for every in (50, 1, 3):
         dx, = up(torch, cuda, conv["x0"])
@@ -367,7 +250,7 @@ def test_max_iter_stops_at_exactly_max_iter(env, conv):
     dx, = up(torch, cuda, conv["x0"])
     x, st = plan.solve(P.dval, db, x=dx, rtol=RTOL, max_iter=0)
     assert (st["status"], st["iterations"], st["restarts"], st["columns"]) == ("limit", 0, 0, 0) and same(x.cpu().numpy(), conv["x0"])
-    agrees(st, x, composed_gmres(P, conv["b"], conv["x0"], 5, RTOL, 0))
+    agrees(st, x, composed_gmres(P.matvec, P.apply, P.dot, P.dots, conv["b"], conv["x0"], 5, RTOL, 0))
     plan.destroy()
 
 

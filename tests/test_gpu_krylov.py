@@ -1,7 +1,7 @@
 """The Krylov solvers on the GPU (KrylovPlan, krylov_dot, pcg, bicgstab) against tests/krylov_numerics.py.
 
 Every bit is pinned, so most checks are ==: the device dot against its host restatement, each fused update against numpy's
-expression of the same shape, and a whole solve against a loop composed in this file from SpmvPlan, Ilu0Plan.apply,
+expression of the same shape, and a whole solve against a loop composed (in tests/solver_compose.py) from SpmvPlan, Ilu0Plan.apply,
 krylov_dot and numpy updates with the scalar steps in Python floats.  Only "it solves" holds a tolerance, and that one
 comes from the host loop's own residual."""
 import math
@@ -12,6 +12,7 @@ import pytest
 import color_numerics as CN
 import ilu0_numerics as IN
 import krylov_numerics as KN
+import solver_compose as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -155,113 +156,7 @@ def test_fused_updates_round_twice_and_carry_the_dots_first_stage(env, n):
 # ---------------------------------------------------------------------------------------------------------------------
 # the solver equals its own composition
 # ---------------------------------------------------------------------------------------------------------------------
-class Parts:
-    """the pieces a composed loop is built from: A v by SpmvPlan (or the unplanned SpMV), M^-1 v by Ilu0Plan.apply or a
-    numpy product with dinv, the pinned dot on the device; vectors live in numpy between them"""
-
-    def __init__(self, env, n, rp, ci, val, precond, planned=True):
-        S, torch, cuda = self.env = env
-        self.n, self.precond = n, precond
-        self.drp, self.dci, self.dval = up(torch, cuda, rp, ci, val)
-        self.spmv = S.SpmvPlan(n, n, self.drp, self.dci) if planned else None
-        self.ilu = self.lu = self.dinv = self.ddinv = None
-        if precond == "ilu0":
-            self.ilu = S.Ilu0Plan(n, self.drp, self.dci)
-            self.lu = self.ilu.factor(self.dval)
-        elif precond == "jacobi":
-            self.dinv = 1.0 / val[IN.check(n, rp, ci)[0]]
-            self.ddinv, = up(torch, cuda, self.dinv)
-
-    def plan(self, method):
-        S = self.env[0]
-        return S.KrylovPlan(self.n, self.drp, self.dci, method=method, spmv_plan=self.spmv,
-                            precond=self.ilu if self.precond == "ilu0" else self.precond)
-
-    def kw(self):
-        return dict(lu=self.lu, dinv=self.ddinv)
-
-    def matvec(self, v):
-        S, torch, cuda = self.env
-        dv, = up(torch, cuda, v)
-        q = torch.empty_like(dv)
-        if self.spmv is not None:
-            self.spmv(self.dval, dv, 1.0, 0.0, q)
-        else:
-            S.spmv(self.n, self.n, self.drp, self.dci, self.dval, dv, 1.0, 0.0, q)
-        return q.cpu().numpy()
-
-    def apply(self, v):
-        S, torch, cuda = self.env
-        if self.precond == "ilu0":
-            return self.ilu.apply(self.lu, up(torch, cuda, v)[0]).cpu().numpy()
-        return self.dinv * v if self.precond == "jacobi" else v
-
-    def dot(self, a, b):
-        S, torch, cuda = self.env
-        return float(S.krylov_dot(*up(torch, cuda, a, b)).cpu().numpy()[0])
-
-    def destroy(self):
-        for p in (self.spmv, self.ilu):
-            if p is not None:
-                p.destroy()
-
-
-def composed_pcg(P, b, x0, rtol, max_iter):
-    tol = max(rtol * math.sqrt(P.dot(b, b)), 0.0)
-    x = x0.copy()
-    r = b - P.matvec(x)
-    rnorm = math.sqrt(P.dot(r, r))
-    if rnorm <= tol:
-        return x, 0, rnorm, "converged"
-    z = P.apply(r)
-    rho = P.dot(r, z)
-    p = z.copy()
-    it = 0
-    while True:
-        q = P.matvec(p)
-        alpha = rho / P.dot(p, q)
-        x = x + alpha * p
-        r = r - alpha * q
-        rnorm, it = math.sqrt(P.dot(r, r)), it + 1
-        if rnorm <= tol:
-            return x, it, rnorm, "converged"
-        if it >= max_iter:
-            return x, it, rnorm, "limit"
-        z = P.apply(r)
-        rho_new = P.dot(r, z)
-        beta, rho = rho_new / rho, rho_new
-        p = z + beta * p
-
-
-def composed_bicgstab(P, b, x0, rtol, max_iter):
-    tol = max(rtol * math.sqrt(P.dot(b, b)), 0.0)
-    x = x0.copy()
-    r = b - P.matvec(x)
-    rho = P.dot(r, r)
-    rnorm = math.sqrt(rho)
-    if rnorm <= tol:
-        return x, 0, rnorm, "converged"
-    rh, p, v = r.copy(), np.zeros_like(r), np.zeros_like(r)
-    alpha, beta, omega, it = 0.0, 0.0, 1.0, 0
-    while True:
-        p = r + beta * (p - omega * v)
-        ph = P.apply(p)
-        v = P.matvec(ph)
-        alpha = rho / P.dot(rh, v)
-        s = r - alpha * v
-        sh = P.apply(s)
-        t = P.matvec(sh)
-        tt = P.dot(t, t)
-        omega = 0.0 if tt == 0.0 and math.sqrt(P.dot(s, s)) <= tol else P.dot(t, s) / tt
-        x = (x + alpha * ph) + omega * sh
-        r = s - omega * t
-        rnorm, it = math.sqrt(P.dot(r, r)), it + 1
-        if rnorm <= tol:
-            return x, it, rnorm, "converged"
-        if it >= max_iter:
-            return x, it, rnorm, "limit"
-        rho_new = P.dot(rh, r)
-        beta, rho = (rho_new / rho) * (alpha / omega), rho_new
+Parts, composed_pcg, composed_bicgstab = SC.Parts, SC.composed_pcg, SC.composed_bicgstab
 
 
 CASES = [("pcg", "laplacian32", "ilu0", True), ("pcg", "laplacian32", "jacobi", True), ("pcg", "laplacian32", None, False),
@@ -277,7 +172,7 @@ def test_the_solver_equals_its_own_composition(env, method, matrix, precond, pla
     rng = np.random.default_rng(30)
     b, x0 = rng.standard_normal(n), 0.1 * rng.standard_normal(n)
     P = Parts(env, n, rp, ci, val, precond, planned=planned)
-    want_x, want_it, want_rnorm, want_status = (composed_pcg if method == "pcg" else composed_bicgstab)(P, b, x0, RTOL, 1000)
+    want_x, want_it, want_rnorm, want_status = (composed_pcg if method == "pcg" else composed_bicgstab)(P.matvec, P.apply, P.dot, b, x0, RTOL, 1000)
     plan = P.plan(method)
     info = plan.info()
     db, dx = up(torch, cuda, b, x0)
