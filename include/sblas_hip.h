@@ -943,8 +943,10 @@ int sblas_hip_gmres_status(const void *plan, void *stream, double out[8]);
  *     coarse_sweeps on the coarsest (sblas_amg_launches).
  * ------------------------------------------------------------------------------------- */
 #define SBLAS_PRECOND_AMG 3
+#define SBLAS_PRECOND_CHEBYSHEV 4 /* sblas_hip_cheby.h: the plan's handle in lower_plan's place, upper_plan NULL */
 #define SBLAS_AMG_JACOBI 0
 #define SBLAS_AMG_L1 1
+#define SBLAS_AMG_CHEBYSHEV 2 /* sblas_hip_cheby.h: sblas_hip_amg_plan_setup_ex */
 #define SBLAS_AMG_SWEEP 0    /* modes of sblas_hip_amg_sweep_f64 */
 #define SBLAS_AMG_RESIDUAL 1
 #define SBLAS_AMG_FIRST 2
@@ -1004,7 +1006,9 @@ int sblas_hip_amg_prolong_f64(const void *plan, void *stream, int level, double 
 
 /* Smoothed aggregation on the same plan (SBLAS_AMG_SMOOTHED, sblas_hip_amg_plan_create_ex, the coarsening guard and their
  * host references) is declared in sblas_hip_amg_sa.h, which this header includes at its end; aggregation on the device
- * (sblas_hip_amg_plan_create_dev, sblas_hip_amg_aggregate_i32, sblas_amg_roots_rounds_ref) in sblas_hip_amg_dev.h, likewise. */
+ * (sblas_hip_amg_plan_create_dev, sblas_hip_amg_aggregate_i32, sblas_amg_roots_rounds_ref) in sblas_hip_amg_dev.h, likewise;
+ * the Chebyshev smoother (SBLAS_AMG_CHEBYSHEV, sblas_hip_amg_plan_setup_ex, sblas_hip_amg_plan_eig) and the plan of its own
+ * (sblas_hip_cheby_plan_*, SBLAS_PRECOND_CHEBYSHEV) in sblas_hip_cheby.h, likewise. */
 
 /* ---------------------------------------------------------------------------------------
  * SDDMM on a CSR pattern:  out[e] = alpha * <X[row(e), :], Y[col(e), :]> + beta * out[e]  for every stored entry e of A
@@ -1261,4 +1265,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #endif
 #include "sblas_hip_amg_sa.h"
 #include "sblas_hip_amg_dev.h"
+#include "sblas_hip_cheby.h"
 #endif /* SBLAS_HIP_H */

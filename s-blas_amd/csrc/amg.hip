@@ -36,14 +36,23 @@
 // theta > 0 the next level's values are the COO plan's assembly on the device (the same left-to-right sums), and below
 // level 0 dpos comes from a kernel: only level 0's structure (for the check that names the first bad row), every level's
 // row pointer (level_pack) and scalars come to the host.
+//
+// The Chebyshev smoother (sblas_hip_amg_plan_setup_ex with SBLAS_AMG_CHEBYSHEV) keeps all of the above and
+// replaces a level's smoothings: the walk of amg.h takes a polynomial of `degree` launches where it takes a sweep, the
+// launches are cheby.hip's (cheby_launch.h: one ChebyOperator a level, wd as its dinv), and setup runs a level's eigenvalue
+// estimate where it ran the level's wd kernel.  Its buffers are made by a plan's first such setup, never by any other.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 #include <memory>
 #include <vector>
 #include "../../include/sblas_hip.h"
 #include "amg.h"
+#include "cheby.h"
+#include "cheby_launch.h"
+#include "krylov.h"
 #include "level_kernels.h"
 #include "rowwise.h"
 
@@ -263,6 +272,11 @@ struct AmgLevel {
     Unit *d_p_units = nullptr, *d_r_units = nullptr;
     double *p_val = nullptr, *r_val = nullptr, *ap_val = nullptr;           // tval: p_val | r_val | ap_val
     DeviceBuffer tbuf, ubuf, tval;
+    // the Chebyshev smoother's, made by the plan's first such setup: d | the scalar block with the table | the dots' partials
+    DeviceBuffer cbuf;
+    double *d = nullptr;
+    ChebyOperator cheb;
+    size_t cheb_bytes = 0;
     ~AmgLevel()
     {
         if (coo) sblas_hip_coo_plan_destroy(coo);
@@ -289,6 +303,12 @@ struct AmgPlan {
     bool ready = false;
     int smoother = SBLAS_AMG_JACOBI, nu = AMG_NU, coarse_sweeps = AMG_COARSE_SWEEPS;
     double omega = 0.0, scale = 1.0;
+    // the Chebyshev smoother's: the estimate's four work vectors, sized by level 0 and shared by the levels (they run one
+    // after the other), made with the levels' buffers by the first such setup
+    DeviceBuffer ebuf;
+    double *est[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t cheb_bytes = 0;
+    int degree = 0; // of the last setup: 0 with the Jacobi and l1 sweeps
     int levels() const { return (int)lv.size(); }
 };
 
@@ -342,6 +362,12 @@ struct DeviceOps {
     double *x(int l, int k) const { return l == 0 && k == AMG_RESULT_BUFFER ? z : p->lv[(size_t)l]->x[k]; }
     void first(int l, int dst) { launch_sweep(s, *p->lv[(size_t)l], MODE_FIRST, b(l), nullptr, x(l, dst)); }
     void sweep(int l, int src, int dst) { launch_sweep(s, *p->lv[(size_t)l], MODE_SWEEP, b(l), x(l, src), x(l, dst)); }
+    void poly_first(int l, int dst) { cheby_first_launch(s, p->lv[(size_t)l]->cheb, b(l), p->lv[(size_t)l]->d, x(l, dst)); }
+    void poly_guess(int l, int src, int dst) { cheby_guess_launch(s, p->lv[(size_t)l]->cheb, b(l), x(l, src), p->lv[(size_t)l]->d, x(l, dst)); }
+    void poly_step(int l, int k, int src, int dst)
+    {
+        cheby_step_launch(s, p->lv[(size_t)l]->cheb, k, b(l), x(l, src), p->lv[(size_t)l]->d, x(l, dst));
+    }
     void residual(int l, int src) { launch_sweep(s, *p->lv[(size_t)l], MODE_RESIDUAL, b(l), x(l, src), p->lv[(size_t)l]->res); }
     void restrict_to(int l)
     {
@@ -679,10 +705,10 @@ int sblas_hip_amg_plan_info(const void *plan, int64_t out[12])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const AmgPlan *p = static_cast<const AmgPlan *>(plan);
-    int64_t rows = 0, entries = 0, bytes = (p->flag ? 256 : 0) + (int64_t)p->t_bytes;
-    for (const auto &L : p->lv) rows += L->n, entries += L->nnz, bytes += (int64_t)L->bytes;
+    int64_t rows = 0, entries = 0, bytes = (p->flag ? 256 : 0) + (int64_t)p->t_bytes + (int64_t)p->cheb_bytes;
+    for (const auto &L : p->lv) rows += L->n, entries += L->nnz, bytes += (int64_t)L->bytes + (int64_t)L->cheb_bytes;
     out[0] = p->n, out[1] = p->nnz, out[2] = p->levels(), out[3] = p->nu, out[4] = p->coarse_sweeps;
-    out[5] = sblas_amg_launches(p->levels(), p->nu, p->coarse_sweeps);
+    out[5] = p->degree ? sblas_amg_launches_cheb(p->levels(), p->nu, p->coarse_sweeps, p->degree) : sblas_amg_launches(p->levels(), p->nu, p->coarse_sweeps);
     out[6] = rows, out[7] = entries, out[8] = bytes, out[9] = p->smoother, out[10] = p->ready, out[11] = p->lv.empty() ? 0 : p->lv.back()->n;
     return SBLAS_OK;
 }
@@ -731,26 +757,78 @@ int sblas_hip_amg_plan_destroy(void *plan)
 int sblas_hip_amg_plan_setup(void *plan, void *stream, const double *val, int smoother, double omega, int nu, int coarse_sweeps,
                              double coarse_scale)
 {
+    if (smoother != SBLAS_AMG_JACOBI && smoother != SBLAS_AMG_L1) return SBLAS_E_INVALID;
+    return sblas_hip_amg_plan_setup_ex(plan, stream, val, smoother, omega, nu, coarse_sweeps, coarse_scale, 0, 0, 0.0, 0.0);
+}
+
+namespace {
+
+// The Chebyshev smoother's buffers, once a plan: a level's direction vector, scalar block and partial sums, and the
+// estimate's four work vectors sized by level 0.  An allocation: refused while the stream is capturing.
+int cheb_allocate(AmgPlan *p, hipStream_t s)
+{
+    if (p->ebuf) return SBLAS_OK;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &capturing) != hipSuccess) return SBLAS_E_HIP;
+    if (capturing != hipStreamCaptureStatusNone) return SBLAS_E_INVALID;
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    for (auto &Lp : p->lv) {
+        AmgLevel &L = *Lp;
+        const size_t vec = pad((size_t)L.n * 8), block = pad((size_t)CHEBY_BLOCK_SLOTS * 8), part = pad((size_t)krylov_cells(L.n) * 8);
+        if (!L.cbuf && L.cbuf.alloc(p->dev, vec + block + part) != hipSuccess) return SBLAS_E_HIP; // kept if a later one fails
+        L.d = L.cbuf.at<double>();
+        L.cheb.n = L.n, L.cheb.units = L.units, L.cheb.d_units = L.d_units, L.cheb.rowptr = L.rowptr, L.cheb.colidx = L.colidx, L.cheb.dpos = L.dpos;
+        L.cheb.dinv = L.wd, L.cheb.blk = L.cbuf.at<double>(vec), L.cheb.part = L.cbuf.at<double>(vec + block);
+        L.cheb_bytes = vec + block + part;
+        if (hipMemsetAsync(L.cheb.blk, 0, block, s) != hipSuccess) return SBLAS_E_HIP;
+    }
+    const size_t vec0 = pad((size_t)p->n * 8);
+    if (p->ebuf.alloc(p->dev, 4 * vec0) != hipSuccess) return SBLAS_E_HIP;
+    for (int k = 0; k < 4; ++k) p->est[k] = p->ebuf.at<double>((size_t)k * vec0);
+    p->cheb_bytes = 4 * vec0;
+    return SBLAS_OK;
+}
+
+} // namespace
+
+int sblas_hip_amg_plan_setup_ex(void *plan, void *stream, const double *val, int smoother, double omega, int nu, int coarse_sweeps,
+                                double coarse_scale, int degree, int eig_steps, double eig_boost, double eig_ratio)
+{
     AmgPlan *p = static_cast<AmgPlan *>(plan);
     if (!p) return SBLAS_E_INVALID;
-    if (smoother != SBLAS_AMG_JACOBI && smoother != SBLAS_AMG_L1) return SBLAS_E_INVALID;
+    const bool cheb = smoother == SBLAS_AMG_CHEBYSHEV;
+    if (smoother != SBLAS_AMG_JACOBI && smoother != SBLAS_AMG_L1 && !cheb) return SBLAS_E_INVALID;
     if (!(omega >= 0.0) || !isfinite(omega) || !isfinite(coarse_scale)) return SBLAS_E_INVALID;
     if (!amg_cycle_args_ok(p->levels(), nu, coarse_sweeps)) return SBLAS_E_INVALID;
+    if (cheb && (omega != 0.0 || !amg_cheb_args_ok(degree, coarse_sweeps) || !cheby_steps_ok(eig_steps) || !cheby_boost_ok(eig_boost) ||
+                 !cheby_ratio_ok(eig_ratio)))
+        return SBLAS_E_INVALID; // omega is left unset with the polynomial
     if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
     if (p->n > 0 && !val) return SBLAS_E_INVALID;
     if (omega == 0.0) omega = smoother == SBLAS_AMG_L1 ? 1.0 : 2.0 / 3.0;
+    hipStream_t s = (hipStream_t)stream;
+    if (cheb && p->n > 0) {
+        const int rc = cheb_allocate(p, s);
+        if (rc != SBLAS_OK) return rc;
+    }
     p->ready = false;
-    p->smoother = smoother, p->omega = omega, p->nu = nu, p->coarse_sweeps = coarse_sweeps, p->scale = coarse_scale;
+    p->smoother = smoother, p->omega = cheb ? 0.0 : omega, p->nu = nu, p->coarse_sweeps = coarse_sweeps, p->scale = coarse_scale;
+    p->degree = cheb ? degree : 0;
     if (p->n == 0) {
         p->ready = true;
         return SBLAS_OK;
     }
-    hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(p->flag, 0xff, 8, s) != hipSuccess) return SBLAS_E_HIP;
     p->lv[0]->val = val;
     for (int l = 0; l < p->levels(); ++l) {
         AmgLevel &L = *p->lv[(size_t)l];
-        amg_wd_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, l, smoother, omega, L.rowptr, L.dpos, L.val, L.wd, p->flag);
+        if (cheb) { // wd = 1 / a_ii, the level's estimate (salt seed + l) and its table; the coarsest's has coarse_sweeps entries
+            L.cheb.val = L.val;
+            cheby_setup_launches(s, L.cheb, p->flag, l, p->seed, eig_steps, eig_boost, eig_ratio, (double)NAN, l + 1 == p->levels() ? coarse_sweeps : degree,
+                                 p->est[0], p->est[1], p->est[2], p->est[3]);
+        } else {
+            amg_wd_kernel<<<grid_of(L.n), AMG_THREADS, 0, s>>>(L.n, l, smoother, omega, L.rowptr, L.dpos, L.val, L.wd, p->flag);
+        }
         if (l + 1 < p->levels()) {
             double *coarse = p->lv[(size_t)l + 1]->own_val;
             if (p->smoothed()) launch_pvalues(s, L, p->omega_p, L.val, p->t);
@@ -771,7 +849,7 @@ int sblas_hip_amg_plan_apply(const void *plan, void *stream, const double *r, do
     if (p->n == 0) return SBLAS_OK;
     if (!r || !z || overlap(r, z, p->n)) return SBLAS_E_INVALID;
     DeviceOps ops{p, (hipStream_t)stream, r, z};
-    amg_cycle(p->levels(), p->nu, p->coarse_sweeps, ops);
+    amg_cycle(p->levels(), p->nu, p->coarse_sweeps, ops, 0, p->degree);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }
 
@@ -786,6 +864,26 @@ int sblas_hip_amg_plan_check(const void *plan, void *stream, int64_t out[2])
     hipStream_t s = (hipStream_t)stream;
     if (hipMemcpyAsync(&w, p->flag, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SBLAS_E_HIP;
     if (w != FLAG_CLEAN) out[0] = (int64_t)(w >> 32), out[1] = (int64_t)(w & 0xffffffffull);
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_eig(const void *plan, void *stream, int level, double out[4], double *table, int *entries)
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !out || !p->ready || p->degree == 0 || level < 0 || level >= p->levels()) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    const AmgLevel &L = *p->lv[(size_t)level];
+    const int count = level + 1 == p->levels() ? p->coarse_sweeps : p->degree;
+    double h[CS_ALPHAS];
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(h, L.cheb.blk, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && table) e = hipMemcpyAsync(table, L.cheb.blk + CS_TABLE, (size_t)count * 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return SBLAS_E_HIP;
+    long long m;
+    memcpy(&m, &h[CS_M], 8);
+    out[0] = (double)m, out[1] = h[CS_RITZ], out[2] = h[CS_G], out[3] = h[CS_LMAX];
+    if (entries) *entries = count;
     return SBLAS_OK;
 }
 

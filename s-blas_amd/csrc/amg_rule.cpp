@@ -117,24 +117,6 @@ namespace {
 
 using namespace sblas;
 
-// the row sum in the solves' pinned order: G(p) lanes, lane l the entries l, l + G, ... with one fused multiply-add each
-// from +0, then the butterfly l ^ 1, l ^ 2, ... as written; lane 0 holds the result
-double row_sum(const int32_t *colidx, const double *val, int64_t beg, int64_t end, const double *x)
-{
-    const int G = 1 << sptrsv_group_shift(end - beg);
-    double v[64], w[64];
-    for (int l = 0; l < G; ++l) {
-        double s = 0.0;
-        for (int64_t e = beg + l; e < end; e += G) s = fma(val[e], x[colidx[e]], s);
-        v[l] = s;
-    }
-    for (int m = 1; m < G; m <<= 1) {
-        for (int l = 0; l < G; ++l) w[l] = v[l] + v[l ^ m];
-        for (int l = 0; l < G; ++l) v[l] = w[l];
-    }
-    return v[0];
-}
-
 struct RefLevel {
     int64_t n;
     const int32_t *rowptr, *colidx, *agg, *aggptr, *members;
@@ -142,6 +124,8 @@ struct RefLevel {
     std::vector<double> own_b, own_x[2], res;
     const double *b;
     double *x[2];
+    const double *table = nullptr; // the Chebyshev smoother's (c1_k, c2_k), the level's own; d is its direction vector
+    std::vector<double> d;
 };
 
 struct RefOps {
@@ -156,15 +140,41 @@ struct RefOps {
     {
         RefLevel &L = lv[(size_t)l];
         for (int64_t i = 0; i < L.n; ++i) {
-            const double s = row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
+            const double s = amg_row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
             const double d = L.b[i] - s, t = L.wd[i] * d;
             L.x[dst][i] = L.x[src][i] + t;
+        }
+    }
+    void poly_first(int l, int dst)
+    {
+        RefLevel &L = lv[(size_t)l];
+        for (int64_t i = 0; i < L.n; ++i) {
+            const double t = L.wd[i] * L.b[i];
+            L.d[(size_t)i] = L.table[1] * t;
+            L.x[dst][i] = L.d[(size_t)i];
+        }
+    }
+    void poly_guess(int l, int src, int dst) { poly(l, 0, src, dst); }
+    void poly_step(int l, int k, int src, int dst) { poly(l, k, src, dst); }
+    void poly(int l, int k, int src, int dst)
+    {
+        RefLevel &L = lv[(size_t)l];
+        for (int64_t i = 0; i < L.n; ++i) {
+            const double s = amg_row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
+            const double res = L.b[i] - s, t = L.wd[i] * res;
+            double dn = L.table[2 * k + 1] * t;
+            if (k > 0) {
+                const double kept = L.table[2 * k] * L.d[(size_t)i];
+                dn = kept + dn;
+            }
+            L.d[(size_t)i] = dn;
+            L.x[dst][i] = L.x[src][i] + dn;
         }
     }
     void residual(int l, int src)
     {
         RefLevel &L = lv[(size_t)l];
-        for (int64_t i = 0; i < L.n; ++i) L.res[(size_t)i] = L.b[i] - row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
+        for (int64_t i = 0; i < L.n; ++i) L.res[(size_t)i] = L.b[i] - amg_row_sum(L.colidx, L.val, L.rowptr[i], L.rowptr[i + 1], L.x[src]);
     }
     void restrict_to(int l)
     {
@@ -191,7 +201,7 @@ void transfer_rows(int mode, int64_t rows, const int32_t *rowptr, const int32_t 
                    double *out)
 {
     for (int64_t i = 0; i < rows; ++i) {
-        const double s = row_sum(colidx, val, rowptr[i], rowptr[i + 1], in);
+        const double s = amg_row_sum(colidx, val, rowptr[i], rowptr[i + 1], in);
         if (mode == AMG_RESTRICT) {
             out[i] = s;
         } else {
@@ -219,7 +229,7 @@ struct RefOpsSa : RefOps {
 
 // the vectors of the reference levels: level 0 reads the caller's r and ends in the caller's z
 void ref_levels(std::vector<RefLevel> &lv, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
-                const double *const *wd, const double *r, double *z)
+                const double *const *wd, const double *r, double *z, const double *const *table = nullptr)
 {
     const int levels = (int)lv.size();
     for (int l = 0; l < levels; ++l) {
@@ -227,6 +237,7 @@ void ref_levels(std::vector<RefLevel> &lv, const int64_t *n, const int32_t *cons
         const bool last = l + 1 == levels;
         L.n = n[l], L.rowptr = rowptr[l], L.colidx = colidx[l], L.val = val[l], L.wd = wd[l];
         L.agg = L.aggptr = L.members = nullptr;
+        if (table) L.table = table[l], L.d.assign((size_t)L.n, 0.0);
         L.own_x[0].assign((size_t)L.n, 0.0), L.res.assign(last ? 0 : (size_t)L.n, 0.0);
         L.x[0] = L.own_x[0].data();
         if (l == 0) {
@@ -311,8 +322,21 @@ int sblas_amg_cycle_sa_ref(int levels, const int64_t *n, const int32_t *const *r
                            const int32_t *const *r_rowptr, const int32_t *const *r_colidx, const double *const *r_val, int nu,
                            int coarse_sweeps, double coarse_scale, const double *r, double *z)
 {
+    return sblas_amg_cycle_cheb_sa_ref(levels, n, rowptr, colidx, val, wd, nullptr, p_rowptr, p_colidx, p_val, r_rowptr, r_colidx, r_val, nu, 0,
+                                       coarse_sweeps, coarse_scale, r, z);
+}
+
+int sblas_amg_cycle_cheb_sa_ref(int levels, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
+                                const double *const *wd, const double *const *table, const int32_t *const *p_rowptr,
+                                const int32_t *const *p_colidx, const double *const *p_val, const int32_t *const *r_rowptr,
+                                const int32_t *const *r_colidx, const double *const *r_val, int nu, int degree, int coarse_sweeps,
+                                double coarse_scale, const double *r, double *z)
+{
     if (!amg_cycle_args_ok(levels, nu, coarse_sweeps)) return SBLAS_E_INVALID;
+    if (degree != 0 && (!amg_cheb_args_ok(degree, coarse_sweeps) || (levels > 0 && !table))) return SBLAS_E_INVALID;
     if (levels == 0) return SBLAS_OK;
+    for (int l = 0; degree != 0 && l < levels; ++l)
+        if (!table[l]) return SBLAS_E_INVALID;
     if (!n || !rowptr || !colidx || !val || !wd) return SBLAS_E_INVALID;
     if (levels > 1 && (!p_rowptr || !p_colidx || !p_val || !r_rowptr || !r_colidx || !r_val)) return SBLAS_E_INVALID;
     for (int l = 0; l < levels; ++l) {
@@ -326,9 +350,9 @@ int sblas_amg_cycle_sa_ref(int levels, const int64_t *n, const int32_t *const *r
     }
     if (n[0] > 0 && (!r || !z || r == z)) return SBLAS_E_INVALID;
     std::vector<RefLevel> lv((size_t)levels);
-    ref_levels(lv, n, rowptr, colidx, val, wd, r, z);
+    ref_levels(lv, n, rowptr, colidx, val, wd, r, z, degree != 0 ? table : nullptr);
     RefOpsSa ops{{lv, coarse_scale}, p_rowptr, p_colidx, r_rowptr, r_colidx, p_val, r_val};
-    amg_cycle(levels, nu, coarse_sweeps, ops);
+    amg_cycle(levels, nu, coarse_sweeps, ops, 0, degree);
     return SBLAS_OK;
 }
 
@@ -403,12 +427,31 @@ int sblas_amg_wd_ref(int64_t n, const int32_t *rowptr, const int32_t *colidx, co
     return SBLAS_OK;
 }
 
+int64_t sblas_amg_launches_cheb(int levels, int nu, int coarse_sweeps, int degree)
+{
+    if (!amg_cycle_args_ok(levels, nu, coarse_sweeps) || !amg_cheb_args_ok(degree, coarse_sweeps)) return -1;
+    AmgCount c;
+    amg_cycle(levels, nu, coarse_sweeps, c, 0, degree);
+    return c.n;
+}
+
 int sblas_amg_cycle_ref(int levels, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
                         const double *const *wd, const int32_t *const *agg, const int32_t *const *aggptr, const int32_t *const *members,
                         int nu, int coarse_sweeps, double coarse_scale, const double *r, double *z)
 {
+    return sblas_amg_cycle_cheb_ref(levels, n, rowptr, colidx, val, wd, nullptr, agg, aggptr, members, nu, 0, coarse_sweeps, coarse_scale, r, z);
+}
+
+int sblas_amg_cycle_cheb_ref(int levels, const int64_t *n, const int32_t *const *rowptr, const int32_t *const *colidx, const double *const *val,
+                             const double *const *wd, const double *const *table, const int32_t *const *agg, const int32_t *const *aggptr,
+                             const int32_t *const *members, int nu, int degree, int coarse_sweeps, double coarse_scale, const double *r,
+                             double *z)
+{
     if (!amg_cycle_args_ok(levels, nu, coarse_sweeps)) return SBLAS_E_INVALID;
+    if (degree != 0 && (!amg_cheb_args_ok(degree, coarse_sweeps) || (levels > 0 && !table))) return SBLAS_E_INVALID;
     if (levels == 0) return SBLAS_OK;
+    for (int l = 0; degree != 0 && l < levels; ++l)
+        if (!table[l]) return SBLAS_E_INVALID;
     if (!n || !rowptr || !colidx || !val || !wd) return SBLAS_E_INVALID;
     if (levels > 1 && (!agg || !aggptr || !members)) return SBLAS_E_INVALID;
     for (int l = 0; l < levels; ++l) {
@@ -423,6 +466,7 @@ int sblas_amg_cycle_ref(int levels, const int64_t *n, const int32_t *const *rowp
         const bool last = l + 1 == levels;
         L.n = n[l], L.rowptr = rowptr[l], L.colidx = colidx[l], L.val = val[l], L.wd = wd[l];
         L.agg = last ? nullptr : agg[l], L.aggptr = last ? nullptr : aggptr[l], L.members = last ? nullptr : members[l];
+        if (degree != 0) L.table = table[l], L.d.assign((size_t)L.n, 0.0);
         L.own_x[0].assign((size_t)L.n, 0.0), L.res.assign(last ? 0 : (size_t)L.n, 0.0);
         L.x[0] = L.own_x[0].data();
         if (l == 0) {
@@ -433,7 +477,7 @@ int sblas_amg_cycle_ref(int levels, const int64_t *n, const int32_t *const *rowp
         }
     }
     RefOps ops{lv, coarse_scale};
-    amg_cycle(levels, nu, coarse_sweeps, ops);
+    amg_cycle(levels, nu, coarse_sweeps, ops, 0, degree);
     return SBLAS_OK;
 }
 

@@ -395,10 +395,14 @@ int spmv(const GmresPlan *p, hipStream_t s, const double *x, double *y)
 }
 
 // out = U^-1 (L^-1 in) with the factor the caller gave start(); out may be in.  With AMG: one cycle of the plan in
-// `lower` with the values of its own setup; its out must not overlap in.
+// `lower` with the values of its own setup; its out must not overlap in.  With CHEBYSHEV: the polynomial of the plan in
+// `lower`, likewise.
+inline bool own_values(int precond) { return precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV; }
+inline bool precond_applied(int precond) { return precond == SBLAS_PRECOND_ILU0 || own_values(precond); }
 int ilu_apply(const GmresPlan *p, hipStream_t s, const double *in, double *out)
 {
     if (p->precond == SBLAS_PRECOND_AMG) return sblas_hip_amg_plan_apply(p->lower, s, in, out);
+    if (p->precond == SBLAS_PRECOND_CHEBYSHEV) return sblas_hip_cheby_plan_apply(p->lower, s, in, out);
     const int rc = sblas_hip_sptrsv_f64_i32_planned(p->lower, s, p->rowptr, p->colidx, p->pre, 1.0, in, p->tmp());
     if (rc != SBLAS_OK) return rc;
     return sblas_hip_sptrsv_f64_i32_planned(p->upper, s, p->rowptr, p->colidx, p->pre, 1.0, p->tmp(), out);
@@ -414,7 +418,7 @@ void normalise(const GmresPlan *p, hipStream_t s)
 int gmres_step_launches(const GmresPlan *p, hipStream_t s)
 {
     const unsigned grid = (unsigned)p->cells;
-    const bool ilu = p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG;
+    const bool ilu = precond_applied(p->precond);
     int rc;
     if (ilu && (rc = ilu_apply(p, s, p->z(), p->u())) != SBLAS_OK) return rc; // u is free between two closes
     if ((rc = spmv(p, s, ilu ? p->u() : p->z(), p->w())) != SBLAS_OK) return rc;
@@ -438,7 +442,7 @@ int gmres_close_launches(const GmresPlan *p, hipStream_t s)
     if (p->precond == SBLAS_PRECOND_ILU0) {
         const int rc = ilu_apply(p, s, p->u(), p->u());
         if (rc != SBLAS_OK) return rc;
-    } else if (p->precond == SBLAS_PRECOND_AMG) { // a cycle does not run in place: the correction is read from the temporary
+    } else if (own_values(p->precond)) { // a cycle (a polynomial) does not run in place: the correction is read from the temporary
         const int rc = ilu_apply(p, s, p->u(), p->tmp());
         if (rc != SBLAS_OK) return rc;
         a.u = p->tmp();
@@ -522,7 +526,7 @@ int sblas_hip_gmres_plan_create(int dev, void *stream, int64_t n, int64_t nnz, c
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
     if (restart < 1 || restart > GMRES_MAX_RESTART) return SBLAS_E_INVALID;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG)
+    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && !precond_applied(precond))
         return SBLAS_E_INVALID;
     if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
     if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
@@ -531,6 +535,9 @@ int sblas_hip_gmres_plan_create(int dev, void *stream, int64_t n, int64_t nnz, c
     if (precond == SBLAS_PRECOND_AMG) { // the AMG handle travels in lower_plan's place
         if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
         if (sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    } else if (precond == SBLAS_PRECOND_CHEBYSHEV) { // and so does the Chebyshev plan's
+        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
+        if (sblas_hip_cheby_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
     } else if (precond == SBLAS_PRECOND_ILU0) {
         if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
         const void *plans[2] = {lower_plan, upper_plan};
@@ -547,7 +554,7 @@ int sblas_hip_gmres_plan_create(int dev, void *stream, int64_t n, int64_t nnz, c
     std::unique_ptr<GmresPlan> p(new GmresPlan);
     p->dev = device, p->m = restart, p->precond = precond, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
     p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan, p->lower = lower_plan, p->upper = upper_plan;
-    p->n_vectors = restart + 1 + GMRES_EXTRA_VECTORS + (precond == SBLAS_PRECOND_ILU0 || precond == SBLAS_PRECOND_AMG);
+    p->n_vectors = restart + 1 + GMRES_EXTRA_VECTORS + precond_applied(precond);
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -578,6 +585,8 @@ int sblas_hip_gmres_plan_info(const void *plan, int64_t out[14])
         sblas_hip_sptrsv_plan_info(p->upper, upper);
     } else if (p->precond == SBLAS_PRECOND_AMG) {
         sblas_hip_amg_plan_info(p->lower, lower);
+    } else if (p->precond == SBLAS_PRECOND_CHEBYSHEV) {
+        sblas_hip_cheby_plan_info(p->lower, lower);
     }
     out[0] = p->n, out[1] = p->nnz, out[2] = p->m, out[3] = p->precond, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
     out[6] = (int64_t)p->partial_bytes, out[7] = GMRES_BLOCK_SLOTS * 8, out[8] = (int64_t)GMRES_MATRIX_DOUBLES * 8, out[9] = (int64_t)p->bytes;
@@ -604,7 +613,7 @@ int sblas_hip_gmres_start(void *plan, void *stream, const double *val, const dou
         p->started = true;
         return SBLAS_OK;
     }
-    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG holds its own values
+    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG and Chebyshev hold their own values
     if (!b || !x || (p->nnz > 0 && !val) || (takes_pre && !lu_or_dinv)) return SBLAS_E_INVALID;
     p->val = val, p->pre = takes_pre ? lu_or_dinv : nullptr, p->b = b, p->x = x, p->pos = 0;
     hipStream_t s = (hipStream_t)stream;

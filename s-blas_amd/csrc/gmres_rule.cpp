@@ -45,13 +45,15 @@ int sblas_gmres_solve_ref(int k, const double *R, int ldr, const double *g, doub
 int64_t sblas_gmres_launches(int m, int precond, const int64_t *lower_info, const int64_t *upper_info, int64_t out[4])
 {
     if (m < 1 || m > sblas::GMRES_MAX_RESTART || !out) return -1;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG)
+    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG &&
+        precond != SBLAS_PRECOND_CHEBYSHEV)
         return -1;
     int64_t apply = 0; // launches of one M^-1: the two solves' ([5] of sblas_hip_sptrsv_plan_info)
     if (precond == SBLAS_PRECOND_ILU0) {
         if (!lower_info || !upper_info || lower_info[5] < 0 || upper_info[5] < 0) return -1;
         apply = lower_info[5] + upper_info[5];
-    } else if (precond == SBLAS_PRECOND_AMG) { // one cycle ([5] of sblas_hip_amg_plan_info) in the two solves' place
+    } else if (precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV) { // one cycle ([5] of sblas_hip_amg_plan_info), or one
+                                                                                      // polynomial ([5] of sblas_hip_cheby_plan_info: the degree), in the two solves' place
         if (!lower_info || lower_info[5] < 0) return -1;
         apply = lower_info[5];
     }

@@ -36,6 +36,10 @@ using namespace sblas;
 
 namespace {
 
+// a preconditioner that is applied by launches of its own between the updates: the two solves, an AMG cycle, a polynomial
+inline bool precond_applied(int precond) { return precond == SBLAS_PRECOND_ILU0 || precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV; }
+inline bool precond_known(int precond) { return precond == SBLAS_PRECOND_NONE || precond == SBLAS_PRECOND_JACOBI || precond_applied(precond); }
+
 // internal update ops, after the public SBLAS_KRYLOV_UP_* ones
 enum { UP_COPY = 5, UP_START_PCG = 6, UP_START_BICG = 7 };
 // fold ops: what lane 0 does with the folded sums d[0 .. nd - 1]
@@ -305,10 +309,12 @@ int spmv(const KrylovPlan *p, hipStream_t s, const double *x, double *y)
 }
 
 // out = U^-1 (L^-1 in) with the factor the caller gave start(); with AMG, one cycle of the plan in `lower` with the
-// values of its own setup (in and out are distinct work vectors, tmp stays unused)
+// values of its own setup (in and out are distinct work vectors, tmp stays unused); with CHEBYSHEV the polynomial of the
+// plan in `lower`, likewise
 int ilu_apply(const KrylovPlan *p, hipStream_t s, const double *in, double *tmp, double *out)
 {
     if (p->precond == SBLAS_PRECOND_AMG) return sblas_hip_amg_plan_apply(p->lower, s, in, out);
+    if (p->precond == SBLAS_PRECOND_CHEBYSHEV) return sblas_hip_cheby_plan_apply(p->lower, s, in, out);
     const int rc = sblas_hip_sptrsv_f64_i32_planned(p->lower, s, p->rowptr, p->colidx, p->pre, 1.0, in, tmp);
     if (rc != SBLAS_OK) return rc;
     return sblas_hip_sptrsv_f64_i32_planned(p->upper, s, p->rowptr, p->colidx, p->pre, 1.0, tmp, out);
@@ -331,7 +337,7 @@ void dot(const KrylovPlan *p, hipStream_t s, const double *x0, const double *y0,
 
 int pcg_iteration(const KrylovPlan *p, hipStream_t s)
 {
-    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG;
+    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = precond_applied(p->precond);
     double *r = p->w(V_R), *pp = p->w(V_P), *q = p->w(V_Q), *z = p->precond == SBLAS_PRECOND_NONE ? r : p->w(V_Z);
     int rc = spmv(p, s, pp, q);
     if (rc != SBLAS_OK) return rc;
@@ -351,7 +357,7 @@ int pcg_iteration(const KrylovPlan *p, hipStream_t s)
 int bicgstab_iteration(const KrylovPlan *p, hipStream_t s)
 {
     const bool jac = p->precond == SBLAS_PRECOND_JACOBI, none = p->precond == SBLAS_PRECOND_NONE;
-    const bool ilu = p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG;
+    const bool ilu = precond_applied(p->precond);
     double *r = p->w(B_R), *rh = p->w(B_RHAT), *pp = p->w(B_P), *v = p->w(B_V), *sv = p->w(B_S), *t = p->w(B_T);
     double *ph = none ? pp : p->w(B_PH), *sh = none ? sv : p->w(B_SH), *dinv = const_cast<double *>(p->pre);
     int rc;
@@ -426,8 +432,7 @@ int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, i
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG)
-        return SBLAS_E_INVALID;
+    if (!precond_known(precond)) return SBLAS_E_INVALID;
     if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
     if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
     const int device = resolve_device(dev);
@@ -435,6 +440,9 @@ int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, i
     if (precond == SBLAS_PRECOND_AMG) { // the AMG handle travels in lower_plan's place
         if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
         if (sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    } else if (precond == SBLAS_PRECOND_CHEBYSHEV) { // and so does the Chebyshev plan's
+        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
+        if (sblas_hip_cheby_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
     } else if (precond == SBLAS_PRECOND_ILU0) {
         if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
         const void *plans[2] = {lower_plan, upper_plan};
@@ -451,7 +459,7 @@ int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, i
     std::unique_ptr<KrylovPlan> p(new KrylovPlan);
     p->dev = device, p->method = method, p->precond = precond, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
     p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan, p->lower = lower_plan, p->upper = upper_plan;
-    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + (precond == SBLAS_PRECOND_ILU0 || precond == SBLAS_PRECOND_AMG);
+    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + precond_applied(precond);
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -478,6 +486,8 @@ int sblas_hip_krylov_plan_info(const void *plan, int64_t out[10])
         sblas_hip_sptrsv_plan_info(p->upper, upper);
     } else if (p->precond == SBLAS_PRECOND_AMG) {
         sblas_hip_amg_plan_info(p->lower, lower);
+    } else if (p->precond == SBLAS_PRECOND_CHEBYSHEV) {
+        sblas_hip_cheby_plan_info(p->lower, lower);
     }
     out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
     out[6] = (int64_t)p->partial_bytes, out[7] = KRYLOV_BLOCK_SLOTS * 8, out[8] = (int64_t)p->bytes;
@@ -503,7 +513,7 @@ int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const do
         p->started = true;
         return SBLAS_OK;
     }
-    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG holds its own values
+    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG and Chebyshev hold their own values
     if (!b || !x || (p->nnz > 0 && !val) || (takes_pre && !lu_or_dinv)) return SBLAS_E_INVALID;
     p->val = val, p->pre = takes_pre ? lu_or_dinv : nullptr, p->x = x;
     hipStream_t s = (hipStream_t)stream;
@@ -517,7 +527,7 @@ int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const do
         if ((rc = spmv(p, s, x, q)) != SBLAS_OK) return rc;
         launch_update(s, UP_START_PCG, jac, up_args(p, {r, bb, q, dinv, z, x}));
         launch_fold(s, FOLD_START_R, jac ? 2 : 1, 0, p->cells, p->part, p->blk);
-        if (p->precond == SBLAS_PRECOND_ILU0 || p->precond == SBLAS_PRECOND_AMG) {
+        if (precond_applied(p->precond)) {
             if ((rc = ilu_apply(p, s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
             dot(p, s, r, z);
             launch_fold(s, FOLD_RHO0, 1, 0, p->cells, p->part, p->blk);

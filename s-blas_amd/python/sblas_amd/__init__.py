@@ -77,6 +77,15 @@ EXPORTS_AMG_SA = [
 EXPORTS_AMG_DEV = [
     "sblas_amg_roots_rounds_ref", "sblas_hip_amg_aggregate_workspace", "sblas_hip_amg_aggregate_i32", "sblas_hip_amg_plan_create_dev",
 ]
+# what include/sblas_hip_cheby.h declares (Chebyshev smoothing on a device eigenvalue estimate)
+EXPORTS_CHEBY = [
+    "sblas_cheby_limits", "sblas_cheby_start_ref", "sblas_cheby_lanczos_ref", "sblas_cheby_ritz_ref", "sblas_cheby_rowbound_ref",
+    "sblas_cheby_lambda_ref", "sblas_cheby_coef_ref", "sblas_cheby_apply_ref",
+    "sblas_hip_cheby_plan_create", "sblas_hip_cheby_plan_setup", "sblas_hip_cheby_plan_apply", "sblas_hip_cheby_plan_smooth",
+    "sblas_hip_cheby_plan_check", "sblas_hip_cheby_plan_scalars", "sblas_hip_cheby_plan_info", "sblas_hip_cheby_plan_speaks_for",
+    "sblas_hip_cheby_plan_destroy",
+    "sblas_hip_amg_plan_setup_ex", "sblas_hip_amg_plan_eig", "sblas_amg_launches_cheb", "sblas_amg_cycle_cheb_ref", "sblas_amg_cycle_cheb_sa_ref",
+]
 
 
 class SblasError(RuntimeError):
@@ -444,6 +453,51 @@ def lib():
     L.sblas_hip_amg_plan_create_dev.restype = C.c_int
     L.sblas_hip_amg_plan_create_dev.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, f64, i64, C.c_int, C.c_uint32, C.c_int, f64, f64, C.c_int,
                                                 C.POINTER(vp), C.POINTER(i64)]
+    u32 = C.c_uint32
+    L.sblas_cheby_limits.restype = C.c_int
+    L.sblas_cheby_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_cheby_start_ref.restype = C.c_int
+    L.sblas_cheby_start_ref.argtypes = [i64, u32, u32, vp]
+    L.sblas_cheby_lanczos_ref.restype = C.c_int
+    L.sblas_cheby_lanczos_ref.argtypes = [i64, vp, vp, vp, u32, u32, C.c_int, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.sblas_cheby_ritz_ref.restype = C.c_int
+    L.sblas_cheby_ritz_ref.argtypes = [C.c_int, vp, vp, vp, vp, C.POINTER(f64)]
+    L.sblas_cheby_rowbound_ref.restype = C.c_int
+    L.sblas_cheby_rowbound_ref.argtypes = [i64, vp, vp, vp, C.POINTER(f64), C.POINTER(i64)]
+    L.sblas_cheby_lambda_ref.restype = f64
+    L.sblas_cheby_lambda_ref.argtypes = [i64, f64, f64, f64]
+    L.sblas_cheby_coef_ref.restype = C.c_int
+    L.sblas_cheby_coef_ref.argtypes = [f64, f64, C.c_int, vp, C.POINTER(f64)]
+    L.sblas_cheby_apply_ref.restype = C.c_int
+    L.sblas_cheby_apply_ref.argtypes = [i64, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.POINTER(i64)]
+    L.sblas_hip_cheby_plan_create.restype = C.c_int
+    L.sblas_hip_cheby_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, C.c_int, f64, f64, u32, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_cheby_plan_setup.restype = C.c_int
+    L.sblas_hip_cheby_plan_setup.argtypes = [vp, vp, vp, f64]
+    L.sblas_hip_cheby_plan_apply.restype = C.c_int
+    L.sblas_hip_cheby_plan_apply.argtypes = [vp, vp, vp, vp]
+    L.sblas_hip_cheby_plan_smooth.restype = C.c_int
+    L.sblas_hip_cheby_plan_smooth.argtypes = [vp, vp, vp, vp, vp]
+    L.sblas_hip_cheby_plan_check.restype = C.c_int
+    L.sblas_hip_cheby_plan_check.argtypes = [vp, vp, C.POINTER(f64)]
+    L.sblas_hip_cheby_plan_scalars.restype = C.c_int
+    L.sblas_hip_cheby_plan_scalars.argtypes = [vp, vp, vp, vp, vp]
+    L.sblas_hip_cheby_plan_info.restype = C.c_int
+    L.sblas_hip_cheby_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_cheby_plan_speaks_for.restype = C.c_int
+    L.sblas_hip_cheby_plan_speaks_for.argtypes = [vp, C.c_int, i64, i64, vp, vp]
+    L.sblas_hip_cheby_plan_destroy.restype = C.c_int
+    L.sblas_hip_cheby_plan_destroy.argtypes = [vp]
+    L.sblas_hip_amg_plan_setup_ex.restype = C.c_int
+    L.sblas_hip_amg_plan_setup_ex.argtypes = [vp, vp, vp, C.c_int, f64, C.c_int, C.c_int, f64, C.c_int, C.c_int, f64, f64]
+    L.sblas_hip_amg_plan_eig.restype = C.c_int
+    L.sblas_hip_amg_plan_eig.argtypes = [vp, vp, C.c_int, C.POINTER(f64), vp, C.POINTER(C.c_int)]
+    L.sblas_amg_launches_cheb.restype = i64
+    L.sblas_amg_launches_cheb.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.sblas_amg_cycle_cheb_ref.restype = C.c_int
+    L.sblas_amg_cycle_cheb_ref.argtypes = [C.c_int, C.POINTER(i64)] + [C.POINTER(vp)] * 8 + [C.c_int, C.c_int, C.c_int, f64, vp, vp]
+    L.sblas_amg_cycle_cheb_sa_ref.restype = C.c_int
+    L.sblas_amg_cycle_cheb_sa_ref.argtypes = [C.c_int, C.POINTER(i64)] + [C.POINTER(vp)] * 11 + [C.c_int, C.c_int, C.c_int, f64, vp, vp]
     _lib = L
     return L
 
@@ -746,7 +800,7 @@ def color_ref(n, rowptr, colidx, seed=0):
 
 # Krylov solvers: methods, preconditioners, status words and the denominators a breakdown names (SBLAS_KRYLOV_*, SBLAS_PRECOND_*)
 KRYLOV_PCG, KRYLOV_BICGSTAB = 0, 1
-PRECOND_NONE, PRECOND_JACOBI, PRECOND_ILU0, PRECOND_AMG = 0, 1, 2, 3
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_ILU0, PRECOND_AMG, PRECOND_CHEBYSHEV = 0, 1, 2, 3, 4
 KRYLOV_RUNNING, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN, KRYLOV_LIMIT = 0, 1, 2, 3
 KRYLOV_STATUS = {KRYLOV_RUNNING: "running", KRYLOV_CONVERGED: "converged", KRYLOV_BREAKDOWN: "breakdown", KRYLOV_LIMIT: "limit"}
 KRYLOV_DENOM = {0: None, 1: "(p, q)", 2: "rho", 3: "(r^, v)", 4: "(t, t)", 5: "omega"}
@@ -775,10 +829,10 @@ def krylov_dot_ref(x, y):
 def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches=0):
     """Launches of one iteration (sblas_krylov_launches).  precond: None, "jacobi" or "ilu0"; lower_launches /
     upper_launches: SptrsvPlan.info()["launches"] of the two solves, read with "ilu0" only; with "amg" lower_launches is
-    AmgPlan.info()["launches"], one cycle's."""
+    AmgPlan.info()["launches"], one cycle's; with "chebyshev" it is the polynomial's degree."""
     if method not in _KRYLOV_METHOD:
         raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
-    code = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG}.get(precond, -1)
+    code = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG, "chebyshev": PRECOND_CHEBYSHEV}.get(precond, -1)
     lo, up = (C.c_int64 * 12)(), (C.c_int64 * 12)()
     lo[5], up[5] = int(lower_launches), int(upper_launches)
     n = int(lib().sblas_krylov_launches(_KRYLOV_METHOD[method], code, lo, up))
@@ -790,7 +844,7 @@ def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches
 # Restarted GMRES: the denominators a breakdown names continue the Krylov solvers' (SBLAS_GMRES_DENOM_*)
 GMRES_DENOM = dict(KRYLOV_DENOM)
 GMRES_DENOM.update({6: "givens", 7: "beta"})
-_PRECOND_CODE = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG}
+_PRECOND_CODE = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG, "chebyshev": PRECOND_CHEBYSHEV}
 
 
 def gmres_limits():
@@ -842,7 +896,8 @@ def gmres_solve_ref(R, g):
 
 def gmres_launches(restart=30, precond=None, lower_launches=0, upper_launches=0):
     """Launches of GMRES (sblas_gmres_launches) -> dict(step, close, restart, start, cycle); a step's do not depend on j.
-    precond: None, "jacobi" or "ilu0"; lower_launches / upper_launches: SptrsvPlan.info()["launches"], read with "ilu0" only."""
+    precond: None, "jacobi" or "ilu0"; lower_launches / upper_launches: SptrsvPlan.info()["launches"], read with "ilu0" only;
+    with "amg" lower_launches is one cycle's, with "chebyshev" the polynomial's degree."""
     lo, up, out = (C.c_int64 * 12)(), (C.c_int64 * 12)(), (C.c_int64 * 4)()
     lo[5], up[5] = int(lower_launches), int(upper_launches)
     cycle = int(lib().sblas_gmres_launches(int(restart), _PRECOND_CODE.get(precond, -1), lo, up, out))
@@ -853,6 +908,7 @@ def gmres_launches(restart=30, precond=None, lower_launches=0, upper_launches=0)
 
 # Aggregation AMG: smoothers and sweep modes (SBLAS_AMG_*)
 AMG_SMOOTHERS = {"jacobi": 0, "l1": 1}
+AMG_CHEBYSHEV = 2                                                           # SBLAS_AMG_CHEBYSHEV: AmgPlan.setup(smoother="chebyshev")
 AMG_SWEEP_MODES = {"sweep": 0, "residual": 1, "first": 2}
 
 
@@ -956,9 +1012,13 @@ def amg_aggregate_device(n, rowptr, colidx, val=None, theta=0.0, seed=0, level=0
     return agg, aggptr[:n_agg.value + 1], members, int(rounds.value)
 
 
-def amg_launches(levels, nu=1, coarse_sweeps=8):
-    """Launches of one AmgPlan.apply (sblas_amg_launches): (2 nu + 3) a level above the coarsest, coarse_sweeps on it."""
-    k = int(lib().sblas_amg_launches(int(levels), int(nu), int(coarse_sweeps)))
+def amg_launches(levels, nu=1, coarse_sweeps=8, degree=0):
+    """Launches of one AmgPlan.apply (sblas_amg_launches): (2 nu + 3) a level above the coarsest, coarse_sweeps on it; with
+    the Chebyshev smoother of `degree` >= 1 (sblas_amg_launches_cheb) (2 nu degree + 3) a level."""
+    if degree:
+        k = int(lib().sblas_amg_launches_cheb(int(levels), int(nu), int(coarse_sweeps), int(degree)))
+    else:
+        k = int(lib().sblas_amg_launches(int(levels), int(nu), int(coarse_sweeps)))
     if k < 0:
         raise SblasError("sblas_amg_launches refused its arguments")
     return k
@@ -981,9 +1041,10 @@ def amg_wd_ref(n, rowptr, colidx, val, smoother="jacobi", omega=None):
     return wd[:n], int(bad.value)
 
 
-def amg_cycle_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
+def amg_cycle_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0, degree=0):
     """The whole V-cycle in plain C++ on host arrays (sblas_amg_cycle_ref) -> z.  levels: a list of dicts with n, rowptr,
-    colidx, val, wd and, on all but the last, agg, aggptr, members (numpy arrays)."""
+    colidx, val, wd and, on all but the last, agg, aggptr, members (numpy arrays).  degree >= 1: the Chebyshev smoother
+    (sblas_amg_cycle_cheb_ref): wd holds 1 / a_ii and every level has table, its (c1_k, c2_k) rows."""
     k = len(levels)
     if k == 0:
         return np.zeros(0)
@@ -1001,6 +1062,13 @@ def amg_cycle_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
     if len(r) != ns[0]:
         raise SblasError("r has %d entries for %d rows" % (len(r), ns[0]))
     z = np.zeros(max(len(r), 1))
+    if degree:
+        check(lib().sblas_amg_cycle_cheb_ref(k, ns, column("rowptr", np.int32, k), column("colidx", np.int32, k), column("val", np.float64, k),
+                                             column("wd", np.float64, k), column("table", np.float64, k), column("agg", np.int32, k - 1),
+                                             column("aggptr", np.int32, k - 1), column("members", np.int32, k - 1), int(nu), int(degree),
+                                             int(coarse_sweeps), float(coarse_scale), r.ctypes.data if len(r) else None, z.ctypes.data),
+              "sblas_amg_cycle_cheb_ref")
+        return z[:len(r)]
     check(lib().sblas_amg_cycle_ref(k, ns, column("rowptr", np.int32, k), column("colidx", np.int32, k), column("val", np.float64, k),
                                     column("wd", np.float64, k), column("agg", np.int32, k - 1), column("aggptr", np.int32, k - 1),
                                     column("members", np.int32, k - 1), int(nu), int(coarse_sweeps), float(coarse_scale),
@@ -1066,10 +1134,10 @@ def amg_transfer_ref(mode, rowptr, colidx, val, x, out=None, scale=1.0):
     return y
 
 
-def amg_cycle_sa_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
+def amg_cycle_sa_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0, degree=0):
     """The V-cycle with general transfer operators in plain C++ on host arrays (sblas_amg_cycle_sa_ref) -> z.  levels: a
     list of dicts with n, rowptr, colidx, val, wd and, on all but the last, p_rowptr, p_colidx, p_val, r_rowptr, r_colidx,
-    r_val (numpy arrays)."""
+    r_val (numpy arrays).  degree >= 1: the Chebyshev smoother (sblas_amg_cycle_cheb_sa_ref), as amg_cycle_ref's."""
     k = len(levels)
     if k == 0:
         return np.zeros(0)
@@ -1087,6 +1155,14 @@ def amg_cycle_sa_ref(levels, r, nu=1, coarse_sweeps=8, coarse_scale=1.0):
     if len(r) != ns[0]:
         raise SblasError("r has %d entries for %d rows" % (len(r), ns[0]))
     z = np.zeros(max(len(r), 1))
+    if degree:
+        check(lib().sblas_amg_cycle_cheb_sa_ref(k, ns, column("rowptr", np.int32, k), column("colidx", np.int32, k), column("val", np.float64, k),
+                                                column("wd", np.float64, k), column("table", np.float64, k), column("p_rowptr", np.int32, k - 1),
+                                                column("p_colidx", np.int32, k - 1), column("p_val", np.float64, k - 1),
+                                                column("r_rowptr", np.int32, k - 1), column("r_colidx", np.int32, k - 1),
+                                                column("r_val", np.float64, k - 1), int(nu), int(degree), int(coarse_sweeps), float(coarse_scale),
+                                                r.ctypes.data if len(r) else None, z.ctypes.data), "sblas_amg_cycle_cheb_sa_ref")
+        return z[:len(r)]
     check(lib().sblas_amg_cycle_sa_ref(k, ns, column("rowptr", np.int32, k), column("colidx", np.int32, k), column("val", np.float64, k),
                                        column("wd", np.float64, k), column("p_rowptr", np.int32, k - 1), column("p_colidx", np.int32, k - 1),
                                        column("p_val", np.float64, k - 1), column("r_rowptr", np.int32, k - 1),
@@ -2497,7 +2573,9 @@ class AmgPlan:
     min_reduction in [0, 1) is the coarsening guard (amg_keep_level): a level is kept only when it removes at least that
     share of the rows; None means 0 (any reduction, as before) for a plain plan and 0.2 for a smoothed one.
     aggregation="device" (sblas_hip_amg_plan_create_dev, include/sblas_hip_amg_dev.h) aggregates every level on the device
-    in Jones-Plassmann rounds and builds the same plan, array for array; "host" (the default) is create as it was."""
+    in Jones-Plassmann rounds and builds the same plan, array for array; "host" (the default) is create as it was.
+    setup(val, smoother="chebyshev", degree=2, ...) (include/sblas_hip_cheby.h) smooths with a Chebyshev polynomial in
+    D^-1 A on every level's own device estimate of lambda_max; eig() shows the estimates."""
 
     def __init__(self, n, rowptr, colidx, val=None, theta=0.0, coarse_max=64, max_levels=20, seed=0, stream=None, prolongator="plain",
                  prolong_omega=AMG_PROLONG_OMEGA, min_reduction=None, aggregation="host"):
@@ -2512,7 +2590,7 @@ class AmgPlan:
             raise SblasError("min_reduction must be in [0, 1), not %r" % (min_reduction,))
         if prolongator == "smoothed" and not 0.0 < float(prolong_omega) < float("inf"):
             raise SblasError("prolong_omega must be positive and finite, not %r" % (prolong_omega,))
-        self.n, self.handle, self._val = n, None, None
+        self.n, self.handle, self._val, self._cheb_ready = n, None, None, False
         self.nnz = _structure(n, rowptr, colidx)
         self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
         theta = float(theta)
@@ -2550,7 +2628,7 @@ class AmgPlan:
         opt = (C.c_double * 4)()
         check(lib().sblas_hip_amg_plan_options(self.handle, opt), "sblas_hip_amg_plan_options")
         return dict(n=int(out[0]), nnz=int(out[1]), levels=int(out[2]), nu=int(out[3]), coarse_sweeps=int(out[4]), launches=int(out[5]),
-                    rows=int(out[6]), entries=int(out[7]), bytes=int(out[8]), smoother=("jacobi", "l1")[out[9]], ready=bool(out[10]),
+                    rows=int(out[6]), entries=int(out[7]), bytes=int(out[8]), smoother=("jacobi", "l1", "chebyshev")[out[9]], ready=bool(out[10]),
                     coarsest=int(out[11]), operator_complexity=(out[7] / out[1] if out[1] else 1.0),
                     prolongator=("plain", "smoothed")[int(opt[0])], prolong_omega=float(opt[1]), min_reduction=float(opt[2]),
                     aggregation=("host", "device")[int(opt[3])])
@@ -2590,13 +2668,21 @@ class AmgPlan:
             out.append((int(sizes[0]), int(sizes[1])))
         return out
 
-    def setup(self, val, smoother="jacobi", omega=None, nu=1, coarse_sweeps=8, coarse_scale=1.0, stream=None):
+    def setup(self, val, smoother="jacobi", omega=None, nu=1, coarse_sweeps=8, coarse_scale=1.0, stream=None, degree=2, eig_steps=10,
+              eig_boost=1.1, eig_ratio=30.0):
         """Every level's values (the Galerkin sums of the aggregates) and the smoother's omega / d from val, on the
         device.  smoother: "jacobi" (omega defaults to 2/3) or "l1" (1).  The plan keeps val alive and sweeps level 0 on
-        it: do not change it before the next setup.  Every refusal comes before any launch."""
+        it: do not change it before the next setup.  Every refusal comes before any launch.
+        smoother="chebyshev" (sblas_hip_amg_plan_setup_ex, include/sblas_hip_cheby.h): every smoothing is one Chebyshev
+        polynomial of `degree` in D^-1 A on the level's own estimate of lambda_max (eig_steps, eig_boost, eig_ratio as
+        ChebyshevPlan's), the coarsest level one polynomial of degree coarse_sweeps (at most 64); omega must be left unset.
+        A plan's first such setup allocates the levels' extra vectors and is refused while a stream capture is under way;
+        eig() shows every level's estimate."""
         import torch
+        if smoother == "chebyshev":
+            return self._setup_chebyshev(val, omega, nu, coarse_sweeps, coarse_scale, stream, degree, eig_steps, eig_boost, eig_ratio)
         if smoother not in AMG_SMOOTHERS:
-            raise SblasError("smoother must be 'jacobi' or 'l1', not %r" % (smoother,))
+            raise SblasError("smoother must be 'jacobi', 'l1' or 'chebyshev', not %r" % (smoother,))
         _krylov_vector("val", val, self.nnz, self.device)
         if omega is None:
             omega = 0.0
@@ -2609,6 +2695,38 @@ class AmgPlan:
                                                 AMG_SMOOTHERS[smoother], float(omega), int(nu), int(coarse_sweeps), float(coarse_scale))
         check(rc, "sblas_hip_amg_plan_setup")
         self._val = val
+
+    def _setup_chebyshev(self, val, omega, nu, coarse_sweeps, coarse_scale, stream, degree, eig_steps, eig_boost, eig_ratio):
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        if omega is not None:
+            raise SblasError("omega must be left unset with the Chebyshev smoother")
+        _cheby_options(degree, eig_steps, eig_boost, eig_ratio)
+        if int(nu) < 1 or not 1 <= int(coarse_sweeps) <= cheby_limits()["max_degree"]:
+            raise SblasError("nu must be at least 1 and coarse_sweeps in [1, %d] with the Chebyshev smoother" % cheby_limits()["max_degree"])
+        with torch.cuda.device(self.device):
+            if not self._cheb_ready and torch.cuda.is_current_stream_capturing():
+                raise SblasError("the plan's first Chebyshev setup allocates its vectors: run it once before capturing a graph")
+            rc = lib().sblas_hip_amg_plan_setup_ex(self.handle, _stream(stream), val.data_ptr() if self.nnz else None, AMG_CHEBYSHEV, 0.0,
+                                                   int(nu), int(coarse_sweeps), float(coarse_scale), degree, eig_steps, float(eig_boost),
+                                                   float(eig_ratio))
+        if rc != 0 and not self._cheb_ready:
+            raise SblasError("sblas_hip_amg_plan_setup_ex refused (code %d): the plan's first Chebyshev setup allocates its vectors and "
+                             "cannot run while a stream capture is under way" % rc)
+        check(rc, "sblas_hip_amg_plan_setup_ex")
+        self._val, self._cheb_ready = val, True
+
+    def eig(self, stream=None):
+        """Every level's estimate after a Chebyshev setup (sblas_hip_amg_plan_eig): a list of dict(m, ritz, g, lambda_max,
+        table), table the level's (c1_k, c2_k) rows.  Synchronises."""
+        import torch
+        levels = []
+        for l in range(self.info()["levels"]):
+            out, table, count = (C.c_double * 4)(), np.zeros((64, 2)), C.c_int(0)
+            with torch.cuda.device(self.device):
+                check(lib().sblas_hip_amg_plan_eig(self.handle, _stream(stream), l, out, table.ctypes.data, C.byref(count)), "sblas_hip_amg_plan_eig")
+            levels.append(dict(m=int(out[0]), ritz=float(out[1]), g=float(out[2]), lambda_max=float(out[3]), table=table[:count.value].copy()))
+        return levels
 
     def apply(self, r, out=None, stream=None):
         """out = M^-1 r: one V-cycle from a zero guess.  out: made here when None; it must not be r.  Returns out."""
@@ -2703,6 +2821,229 @@ def amg_prolong(plan, level, e, x, scale=1.0, stream=None):
     with torch.cuda.device(plan.device):
         check(lib().sblas_hip_amg_prolong_f64(plan.handle, _stream(stream), int(level), float(scale), pe, px), "sblas_hip_amg_prolong_f64")
     return x
+
+
+# ------------------------------------------------------------------------------------------
+# Chebyshev smoothing on a device eigenvalue estimate (sblas_cheby_*, sblas_hip_cheby_plan_*; include/sblas_hip_cheby.h)
+# ------------------------------------------------------------------------------------------
+def cheby_limits():
+    """The Chebyshev plan's limits (sblas_cheby_limits): dict(threads, max_degree, max_steps, degree, eig_steps, bisections,
+    block_slots)."""
+    out = (C.c_int64 * 8)()
+    check(lib().sblas_cheby_limits(out), "sblas_cheby_limits")
+    return dict(zip(("threads", "max_degree", "max_steps", "degree", "eig_steps", "bisections", "block_slots"), (int(v) for v in out)))
+
+
+def _cheby_csr(n, rowptr, colidx, val):
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    val = np.ascontiguousarray(val, np.float64)
+    if len(rowptr) != int(n) + 1 or len(colidx) != len(val) or (n and int(rowptr[-1]) != len(colidx)):
+        raise SblasError("rowptr needs n + 1 entries that end at len(colidx) == len(val)")
+    return rowptr, colidx, val
+
+
+def _cheby_options(degree=None, eig_steps=None, eig_boost=None, eig_ratio=None):
+    """every refusal of the options, before any launch (a NaN fails every comparison)"""
+    lim = cheby_limits()
+    if degree is not None and (isinstance(degree, bool) or not isinstance(degree, int) or not 1 <= degree <= lim["max_degree"]):
+        raise SblasError("degree must be an integer in [1, %d], not %r" % (lim["max_degree"], degree))
+    if eig_steps is not None and (isinstance(eig_steps, bool) or not isinstance(eig_steps, int) or not 1 <= eig_steps <= lim["max_steps"]):
+        raise SblasError("eig_steps must be an integer in [1, %d], not %r" % (lim["max_steps"], eig_steps))
+    if eig_boost is not None and not 1.0 <= float(eig_boost) < float("inf"):
+        raise SblasError("eig_boost must be finite and at least 1, not %r" % (eig_boost,))
+    if eig_ratio is not None and not 1.0 < float(eig_ratio) < float("inf"):
+        raise SblasError("eig_ratio must be finite and greater than 1, not %r" % (eig_ratio,))
+
+
+def cheby_start_ref(n, seed=0, level=0):
+    """The estimate's start vector b0 (sblas_cheby_start_ref): (2 h(i) + 1) 2^-32 - 1 with h the colouring's priority hash
+    of salt seed + level -> numpy float64."""
+    b0 = np.zeros(int(n))
+    check(lib().sblas_cheby_start_ref(int(n), int(seed) & 0xffffffff, int(level) & 0xffffffff, b0.ctypes.data), "sblas_cheby_start_ref")
+    return b0
+
+
+def cheby_lanczos_ref(n, rowptr, colidx, val, eig_steps=10, seed=0, level=0):
+    """The estimate's recurrence on the host (sblas_cheby_lanczos_ref) -> dict(alpha, beta, m, bad_row): alpha has m
+    entries, beta max(m - 1, 0); bad_row is the least row whose diagonal is not finite and > 0, or None."""
+    _cheby_options(eig_steps=eig_steps)
+    rowptr, colidx, val = _cheby_csr(n, rowptr, colidx, val)
+    alpha, beta, m, bad = np.zeros(eig_steps), np.zeros(eig_steps), C.c_int64(0), C.c_int64(-1)
+    rc = lib().sblas_cheby_lanczos_ref(int(n), rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, int(seed) & 0xffffffff,
+                                       int(level) & 0xffffffff, eig_steps, alpha.ctypes.data, beta.ctypes.data, C.byref(m), C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_cheby_lanczos_ref", rc, bad.value)
+    k = int(m.value)
+    return dict(alpha=alpha[:k], beta=beta[:max(k - 1, 0)], m=k, bad_row=None if bad.value < 0 else int(bad.value))
+
+
+def cheby_ritz_ref(alpha, beta):
+    """The tridiagonal of m = len(alpha) >= 1 finished steps and its largest eigenvalue by Sturm bisection
+    (sblas_cheby_ritz_ref) -> dict(t, e2, ritz)."""
+    alpha, beta = np.ascontiguousarray(alpha, np.float64).ravel(), np.ascontiguousarray(beta, np.float64).ravel()
+    m = len(alpha)
+    if not 1 <= m <= cheby_limits()["max_steps"] or len(beta) < m - 1:
+        raise SblasError("alpha needs 1 to %d entries and beta at least one fewer" % cheby_limits()["max_steps"])
+    t, e2, ritz = np.zeros(m), np.zeros(m), C.c_double(0.0)
+    check(lib().sblas_cheby_ritz_ref(m, alpha.ctypes.data, beta.ctypes.data, t.ctypes.data, e2.ctypes.data, C.byref(ritz)), "sblas_cheby_ritz_ref")
+    return dict(t=t, e2=e2[:m - 1], ritz=float(ritz.value))
+
+
+def cheby_rowbound_ref(n, rowptr, colidx, val):
+    """g = max_i (sum_e |a_ie| / a_ii) in the pinned order (sblas_cheby_rowbound_ref) -> float"""
+    rowptr, colidx, val = _cheby_csr(n, rowptr, colidx, val)
+    g, bad = C.c_double(0.0), C.c_int64(-1)
+    rc = lib().sblas_cheby_rowbound_ref(int(n), rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, C.byref(g), C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_cheby_rowbound_ref", rc, bad.value)
+    return float(g.value)
+
+
+def cheby_lambda_ref(m, ritz, g, eig_boost=1.1):
+    """lambda_max = min(eig_boost * ritz, g) after m >= 1 steps, g after none (sblas_cheby_lambda_ref)"""
+    _cheby_options(eig_boost=eig_boost)
+    return float(lib().sblas_cheby_lambda_ref(int(m), float(ritz), float(g), float(eig_boost)))
+
+
+def cheby_coef_ref(lambda_max, degree=4, eig_ratio=30.0):
+    """The coefficient table on [lambda_max / eig_ratio, lambda_max] (sblas_cheby_coef_ref) -> dict(table, lambda_min):
+    table is degree x 2, the rows (c1_k, c2_k)."""
+    _cheby_options(degree=degree, eig_ratio=eig_ratio)
+    if float(lambda_max) != float(lambda_max):
+        raise SblasError("lambda_max must not be a NaN")
+    table, low = np.zeros((degree, 2)), C.c_double(0.0)
+    check(lib().sblas_cheby_coef_ref(float(lambda_max), float(eig_ratio), degree, table.ctypes.data, C.byref(low)), "sblas_cheby_coef_ref")
+    return dict(table=table, lambda_min=float(low.value))
+
+
+def cheby_apply_ref(n, rowptr, colidx, val, table, b, x=None):
+    """The polynomial of degree len(table) applied to b on the host (sblas_cheby_apply_ref): from zero, or from the guess
+    x -> numpy float64."""
+    rowptr, colidx, val = _cheby_csr(n, rowptr, colidx, val)
+    table = np.ascontiguousarray(table, np.float64)
+    if table.ndim != 2 or table.shape[1] != 2:
+        raise SblasError("table must be degree x 2")
+    _cheby_options(degree=int(table.shape[0]))
+    b = np.ascontiguousarray(b, np.float64).ravel()
+    if x is not None:
+        x = np.ascontiguousarray(x, np.float64).ravel()
+    if len(b) != n or (x is not None and len(x) != n):
+        raise SblasError("b and x need n = %d entries" % n)
+    y, bad = np.zeros(int(n)), C.c_int64(-1)
+    rc = lib().sblas_cheby_apply_ref(int(n), rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, table.ctypes.data, int(table.shape[0]),
+                                     b.ctypes.data, x.ctypes.data if x is not None else None, y.ctypes.data, C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_cheby_apply_ref", rc, bad.value)
+    return y
+
+
+class ChebyshevPlan:
+    """z = p(D^-1 A) D^-1 r for the square n x n CSR matrix (rowptr, colidx), int32 indices (sblas_hip_cheby_plan_create):
+    p is the Chebyshev polynomial of `degree` on [lambda_max / eig_ratio, lambda_max], and lambda_max(D^-1 A) is estimated
+    on the device by eig_steps steps of Jacobi-preconditioned CG from a hashed start vector, boosted by eig_boost and
+    capped by the row bound max_i sum_e |a_ie| / a_ii.  Every row must be strictly ascending in column and store its
+    diagonal; a bad structure raises an SblasError that names the first bad row (.bad_row).  The plan keeps rowptr and
+    colidx alive and sweeps on them: do not change them.  setup(val) is device work only, repeatable and graph-capturable;
+    apply() and smooth() are `degree` launches of one row kernel, allocate nothing inside the library and never
+    synchronise; check() is the one call that synchronises.  Every bit is pinned (include/sblas_hip_cheby.h; the
+    cheby_*_ref functions restate it on the host).  KrylovPlan and GmresPlan take the plan as precond."""
+
+    def __init__(self, n, rowptr, colidx, degree=4, eig_steps=10, eig_boost=1.1, eig_ratio=30.0, seed=0, stream=None):
+        import torch
+        self.n, self.handle, self._val = n, None, None
+        _cheby_options(degree, eig_steps, eig_boost, eig_ratio)
+        self.nnz = _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        self.degree = degree
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_cheby_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr() if n else None,
+                                                   colidx.data_ptr() if self.nnz else None, degree, eig_steps, float(eig_boost),
+                                                   float(eig_ratio), int(seed) & 0xffffffff, C.byref(h), C.byref(bad))
+        if rc != 0:
+            raise _bad_structure("sblas_hip_cheby_plan_create", rc, bad.value)
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_cheby_plan_info(self.handle, out), "sblas_hip_cheby_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), degree=int(out[2]), eig_steps=int(out[3]), units=int(out[4]), launches=int(out[5]),
+                    bytes=int(out[6]), ready=bool(out[7]), setup_launches=int(out[8]), seed=int(out[9]))
+
+    def setup(self, val, lambda_max=None, stream=None):
+        """dinv, the row bound and the coefficient table from val, on the device; lambda_max None runs the estimate, a
+        finite positive lambda_max takes its place (through the same scalar kernel).  The plan keeps val alive and sweeps
+        on it: do not change it before the next setup.  Every refusal comes before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        if lambda_max is None:
+            lambda_max = float("nan")
+        elif not 0.0 < float(lambda_max) < float("inf"):
+            raise SblasError("lambda_max must be positive and finite (or None for the estimate), not %r" % (lambda_max,))
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_cheby_plan_setup(self.handle, _stream(stream), val.data_ptr() if self.nnz else None, float(lambda_max))
+        check(rc, "sblas_hip_cheby_plan_setup")
+        self._val = val
+
+    def apply(self, r, out=None, stream=None):
+        """out = p(D^-1 A) D^-1 r from a zero guess.  out: made here when None; it must not be r.  Returns out."""
+        import torch
+        _krylov_vector("r", r, self.n, self.device)
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        _krylov_vector("out", out, self.n, self.device)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_cheby_plan_apply(self.handle, _stream(stream), r.data_ptr() if self.n else None,
+                                                  out.data_ptr() if self.n else None)
+        check(rc, "sblas_hip_cheby_plan_apply")
+        return out
+
+    def smooth(self, b, x, out=None, stream=None):
+        """out = x + p(D^-1 A) D^-1 (b - A x): the polynomial from the guess x.  out must be neither b nor x."""
+        import torch
+        _krylov_vector("b", b, self.n, self.device), _krylov_vector("x", x, self.n, self.device)
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        _krylov_vector("out", out, self.n, self.device)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_cheby_plan_smooth(self.handle, _stream(stream), b.data_ptr() if self.n else None,
+                                                   x.data_ptr() if self.n else None, out.data_ptr() if self.n else None)
+        check(rc, "sblas_hip_cheby_plan_smooth")
+        return out
+
+    def check(self, stream=None):
+        """What the last setup() found -> dict(bad_row, m, ritz, g, lambda_max, lambda_min): bad_row is the least row whose
+        diagonal is not finite and > 0, or None; m the finished steps of the estimate.  Synchronises."""
+        import torch
+        out = (C.c_double * 6)()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_cheby_plan_check(self.handle, _stream(stream), out), "sblas_hip_cheby_plan_check")
+        return dict(bad_row=None if out[0] < 0 else int(out[0]), m=int(out[1]), ritz=float(out[2]), g=float(out[3]), lambda_max=float(out[4]),
+                    lambda_min=float(out[5]))
+
+    def scalars(self, stream=None):
+        """The estimate's alpha (m entries) and beta (m - 1) and the coefficient table (degree x 2) of the last setup(), as
+        numpy arrays (sblas_hip_cheby_plan_scalars).  Synchronises."""
+        import torch
+        m = self.check(stream)["m"]
+        alpha, beta, table = np.zeros(cheby_limits()["max_steps"]), np.zeros(cheby_limits()["max_steps"]), np.zeros((self.degree, 2))
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_cheby_plan_scalars(self.handle, _stream(stream), alpha.ctypes.data, beta.ctypes.data, table.ctypes.data),
+                  "sblas_hip_cheby_plan_scalars")
+        return dict(alpha=alpha[:m], beta=beta[:max(m - 1, 0)], table=table)
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_cheby_plan_destroy(self.handle)
+            self.handle = None
+        self._val = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------------------------------------------
@@ -2806,8 +3147,12 @@ class KrylovPlan:
         elif isinstance(precond, AmgPlan):                                  # the handle travels in the lower plan's place
             self.precond_kind = PRECOND_AMG
             lower = precond
+        elif isinstance(precond, ChebyshevPlan):                            # and so does the Chebyshev plan's
+            self.precond_kind = PRECOND_CHEBYSHEV
+            lower = precond
         else:
-            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans or an AmgPlan, not %r" % (precond,))
+            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan or a ChebyshevPlan, not %r"
+                             % (precond,))
         if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
             raise SblasError("spmv_plan must be an SpmvPlan or None")
         self._solvers = (lower, upper)
@@ -2826,7 +3171,7 @@ class KrylovPlan:
         out = (C.c_int64 * 10)()
         check(lib().sblas_hip_krylov_plan_info(self.handle, out), "sblas_hip_krylov_plan_info")
         return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
-                    precond=(None, "jacobi", "ilu0", "amg")[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
+                    precond=(None, "jacobi", "ilu0", "amg", "chebyshev")[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
                     scalar_bytes=int(out[7]), bytes=int(out[8]), launches=int(out[9]))
 
     def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
@@ -2907,13 +3252,16 @@ class KrylovPlan:
 def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
     import torch
     n, rowptr, colidx, val = A
-    if precond not in (None, "jacobi", "ilu0", "amg", "amg_smoothed"):
-        raise SblasError("precond must be None, 'jacobi', 'ilu0', 'amg' or 'amg_smoothed', not %r" % (precond,))
+    if precond not in (None, "jacobi", "ilu0", "amg", "amg_smoothed", "chebyshev"):
+        raise SblasError("precond must be None, 'jacobi', 'ilu0', 'amg', 'amg_smoothed' or 'chebyshev', not %r" % (precond,))
     ilu = plan = amg = None
     lu = dinv = None
     try:
         if precond in ("amg", "amg_smoothed"):                            # the defaults: V(1, 1), Jacobi 2/3, structure only
             amg = AmgPlan(n, rowptr, colidx, prolongator="smoothed" if precond == "amg_smoothed" else "plain")
+            amg.setup(val)
+        elif precond == "chebyshev":                                        # the defaults: degree 4 on the device's estimate
+            amg = ChebyshevPlan(n, rowptr, colidx)
             amg.setup(val)
         elif precond is not None:                                           # both read the diagonal's places off the ILU(0) plan
             ilu = Ilu0Plan(n, rowptr, colidx)
@@ -3055,8 +3403,12 @@ class GmresPlan:
         elif isinstance(precond, AmgPlan):                                  # the handle travels in the lower plan's place
             self.precond_kind = PRECOND_AMG
             lower = precond
+        elif isinstance(precond, ChebyshevPlan):                            # and so does the Chebyshev plan's
+            self.precond_kind = PRECOND_CHEBYSHEV
+            lower = precond
         else:
-            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans or an AmgPlan, not %r" % (precond,))
+            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan or a ChebyshevPlan, not %r"
+                             % (precond,))
         if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
             raise SblasError("spmv_plan must be an SpmvPlan or None")
         self.nnz = _structure(n, rowptr, colidx)
@@ -3076,7 +3428,7 @@ class GmresPlan:
     def info(self):
         out = (C.c_int64 * 14)()
         check(lib().sblas_hip_gmres_plan_info(self.handle, out), "sblas_hip_gmres_plan_info")
-        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=(None, "jacobi", "ilu0", "amg")[out[3]], vectors=int(out[4]),
+        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=(None, "jacobi", "ilu0", "amg", "chebyshev")[out[3]], vectors=int(out[4]),
                     vector_bytes=int(out[5]), partial_bytes=int(out[6]), scalar_bytes=int(out[7]), matrix_bytes=int(out[8]),
                     bytes=int(out[9]), step_launches=int(out[10]), close_launches=int(out[11]), restart_launches=int(out[12]),
                     cycle_launches=int(out[13]))
