@@ -59,6 +59,7 @@ inline bool csr_args_ok(int64_t rows, int64_t cols, int64_t nnz, const void *row
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; } // Bt: 16-byte tile loads
+inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; } // a segment of a solver plan's one buffer
 
 // One device allocation of a plan.  It is made on the current device (the caller's DeviceScope) and freed on the device
 // it was made for, whichever device is current then.

@@ -256,7 +256,6 @@ __global__ void cheby_finish_kernel(double *blk, int estimated, double boost, do
 }
 
 inline unsigned grid_of(int64_t threads) { return (unsigned)((threads + CHEBY_THREADS - 1) / CHEBY_THREADS); }
-inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
 
 struct ChebyPlan {
     int dev = -1, degree = 0, steps = 0;

@@ -25,7 +25,7 @@
 #include <string.h>
 #include <memory>
 #include "../../include/sblas_hip.h"
-#include "capi_util.h"
+#include "precond.h"
 
 #pragma clang fp contract(off) // file scope, ahead of gmres.h: a * b + c is two roundings in the scalar step and below
 
@@ -349,13 +349,12 @@ __global__ __launch_bounds__(KRYLOV_LANES) void gmres_fold_kernel(int op, int nd
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct GmresPlan {
-    int dev = -1, m = 0, precond = 0;
+    int dev = -1, m = 0;
     int64_t n = 0, nnz = 0, cells = 0, ldv = 0;
     const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
-    const void *spmv = nullptr, *lower = nullptr, *upper = nullptr;
+    const void *spmv = nullptr;
+    PrecondSeat pre; // start() gives it the caller's values
     int n_vectors = 0;
     size_t vector_bytes = 0, partial_bytes = 0, bytes = 0;
     DeviceBuffer buf; // block | small matrices | partials | V, w, u, z [, the solves' temporary]
@@ -363,7 +362,7 @@ struct GmresPlan {
     // one solve: start() keeps what iterate() needs
     bool started = false;
     int pos = 0; // steps enqueued since the chain's last restart (or start): where the next close and restart belong
-    const double *val = nullptr, *pre = nullptr, *b = nullptr;
+    const double *val = nullptr, *b = nullptr;
     double *x = nullptr;
     double *col(int k) const { return vec + (size_t)k * (size_t)ldv; }
     double *w() const { return col(m + 1); }
@@ -384,44 +383,23 @@ ColArgs col_args(const GmresPlan *p, int mode, const double *coef, double *w, do
 
 VecArgs vec_args(const GmresPlan *p)
 {
-    return VecArgs{p->n, p->cells, p->ldv, p->blk, p->part, p->vec, p->w(), p->z(), p->x, p->b, p->pre, p->u()};
-}
-
-int spmv(const GmresPlan *p, hipStream_t s, const double *x, double *y)
-{
-    if (p->spmv)
-        return sblas_hip_spmv_csr_f64_i32_planned(p->spmv, -1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
-    return sblas_hip_spmv_csr_f64_i32(-1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
-}
-
-// out = U^-1 (L^-1 in) with the factor the caller gave start(); out may be in.  With AMG: one cycle of the plan in
-// `lower` with the values of its own setup; its out must not overlap in.  With CHEBYSHEV: the polynomial of the plan in
-// `lower`, likewise.
-inline bool own_values(int precond) { return precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV; }
-inline bool precond_applied(int precond) { return precond == SBLAS_PRECOND_ILU0 || own_values(precond); }
-int ilu_apply(const GmresPlan *p, hipStream_t s, const double *in, double *out)
-{
-    if (p->precond == SBLAS_PRECOND_AMG) return sblas_hip_amg_plan_apply(p->lower, s, in, out);
-    if (p->precond == SBLAS_PRECOND_CHEBYSHEV) return sblas_hip_cheby_plan_apply(p->lower, s, in, out);
-    const int rc = sblas_hip_sptrsv_f64_i32_planned(p->lower, s, p->rowptr, p->colidx, p->pre, 1.0, in, p->tmp());
-    if (rc != SBLAS_OK) return rc;
-    return sblas_hip_sptrsv_f64_i32_planned(p->upper, s, p->rowptr, p->colidx, p->pre, 1.0, p->tmp(), out);
+    return VecArgs{p->n, p->cells, p->ldv, p->blk, p->part, p->vec, p->w(), p->z(), p->x, p->b, p->pre.values, p->u()};
 }
 
 void normalise(const GmresPlan *p, hipStream_t s)
 {
     const unsigned grid = (unsigned)p->cells;
-    if (p->precond == SBLAS_PRECOND_JACOBI) gmres_normal_kernel<true><<<grid, KRYLOV_LANES, 0, s>>>(vec_args(p));
+    if (p->pre.jacobi()) gmres_normal_kernel<true><<<grid, KRYLOV_LANES, 0, s>>>(vec_args(p));
     else gmres_normal_kernel<false><<<grid, KRYLOV_LANES, 0, s>>>(vec_args(p));
 }
 
 int gmres_step_launches(const GmresPlan *p, hipStream_t s)
 {
     const unsigned grid = (unsigned)p->cells;
-    const bool ilu = precond_applied(p->precond);
+    const bool ilu = p->pre.applied();
     int rc;
-    if (ilu && (rc = ilu_apply(p, s, p->z(), p->u())) != SBLAS_OK) return rc; // u is free between two closes
-    if ((rc = spmv(p, s, ilu ? p->u() : p->z(), p->w())) != SBLAS_OK) return rc;
+    if (ilu && (rc = p->pre.apply(s, p->z(), p->tmp(), p->u())) != SBLAS_OK) return rc; // u is free between two closes
+    if ((rc = plan_spmv(p, s, ilu ? p->u() : p->z(), p->w())) != SBLAS_OK) return rc;
     gmres_dots_kernel<<<grid, KRYLOV_LANES, 0, s>>>(col_args(p, MODE_FIRST, nullptr, p->w(), p->part));
     fold(p, s, GF_H1);
     gmres_project_kernel<<<grid, KRYLOV_LANES, 0, s>>>(col_args(p, MODE_ACTIVE, p->mat + GM_H, p->w(), nullptr));
@@ -439,22 +417,20 @@ int gmres_close_launches(const GmresPlan *p, hipStream_t s)
     gmres_close_kernel<<<1, 64, 0, s>>>(p->blk, p->mat);
     gmres_combine_kernel<<<grid, KRYLOV_LANES, 0, s>>>(col_args(p, MODE_CLOSE, p->mat + GM_Y, p->u(), nullptr));
     VecArgs a = vec_args(p);
-    if (p->precond == SBLAS_PRECOND_ILU0) {
-        const int rc = ilu_apply(p, s, p->u(), p->u());
+    if (p->pre.applied()) { // in place where M^-1 may run so; else the correction is read from the temporary
+        double *out = p->pre.in_place() ? p->u() : p->tmp();
+        const int rc = p->pre.apply(s, p->u(), p->tmp(), out);
         if (rc != SBLAS_OK) return rc;
-    } else if (own_values(p->precond)) { // a cycle (a polynomial) does not run in place: the correction is read from the temporary
-        const int rc = ilu_apply(p, s, p->u(), p->tmp());
-        if (rc != SBLAS_OK) return rc;
-        a.u = p->tmp();
+        a.u = out;
     }
-    if (p->precond == SBLAS_PRECOND_JACOBI) gmres_x_kernel<true><<<grid, KRYLOV_LANES, 0, s>>>(a);
+    if (p->pre.jacobi()) gmres_x_kernel<true><<<grid, KRYLOV_LANES, 0, s>>>(a);
     else gmres_x_kernel<false><<<grid, KRYLOV_LANES, 0, s>>>(a);
     return SBLAS_OK;
 }
 
 int gmres_restart_launches(const GmresPlan *p, hipStream_t s)
 {
-    const int rc = spmv(p, s, p->x, p->w());
+    const int rc = plan_spmv(p, s, p->x, p->w());
     if (rc != SBLAS_OK) return rc;
     gmres_residual_kernel<false><<<(unsigned)p->cells, KRYLOV_LANES, 0, s>>>(vec_args(p));
     fold(p, s, GF_BEGIN_RESTART);
@@ -526,35 +502,16 @@ int sblas_hip_gmres_plan_create(int dev, void *stream, int64_t n, int64_t nnz, c
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
     if (restart < 1 || restart > GMRES_MAX_RESTART) return SBLAS_E_INVALID;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && !precond_applied(precond))
-        return SBLAS_E_INVALID;
+    if (!precond_known(precond)) return SBLAS_E_INVALID;
     if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
     if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
     const int device = resolve_device(dev);
     if (spmv_plan && sblas_hip_spmv_plan_speaks_for(spmv_plan, device, n, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    if (precond == SBLAS_PRECOND_AMG) { // the AMG handle travels in lower_plan's place
-        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
-        if (sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    } else if (precond == SBLAS_PRECOND_CHEBYSHEV) { // and so does the Chebyshev plan's
-        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
-        if (sblas_hip_cheby_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    } else if (precond == SBLAS_PRECOND_ILU0) {
-        if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
-        const void *plans[2] = {lower_plan, upper_plan};
-        const int fill[2] = {SBLAS_FILL_LOWER, SBLAS_FILL_UPPER}, diag[2] = {SBLAS_DIAG_UNIT, SBLAS_DIAG_NON_UNIT};
-        for (int k = 0; k < 2; ++k) {
-            int64_t info[12];
-            if (sblas_hip_sptrsv_plan_info(plans[k], info) != SBLAS_OK) return SBLAS_E_INVALID;
-            if (info[0] != n || info[1] != nnz || info[2] != fill[k] || info[3] != diag[k]) return SBLAS_E_INVALID;
-            if (sblas_hip_sptrsv_plan_speaks_for(plans[k], device, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-        }
-    } else if (lower_plan || upper_plan) {
-        return SBLAS_E_INVALID;
-    }
     std::unique_ptr<GmresPlan> p(new GmresPlan);
-    p->dev = device, p->m = restart, p->precond = precond, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
-    p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan, p->lower = lower_plan, p->upper = upper_plan;
-    p->n_vectors = restart + 1 + GMRES_EXTRA_VECTORS + precond_applied(precond);
+    if (p->pre.bind(precond, lower_plan, upper_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    p->dev = device, p->m = restart, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
+    p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan;
+    p->n_vectors = restart + 1 + GMRES_EXTRA_VECTORS + p->pre.applied();
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -579,18 +536,11 @@ int sblas_hip_gmres_plan_info(const void *plan, int64_t out[14])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const GmresPlan *p = static_cast<const GmresPlan *>(plan);
-    int64_t lower[12] = {0}, upper[12] = {0}, launches[4] = {0};
-    if (p->precond == SBLAS_PRECOND_ILU0) {
-        sblas_hip_sptrsv_plan_info(p->lower, lower);
-        sblas_hip_sptrsv_plan_info(p->upper, upper);
-    } else if (p->precond == SBLAS_PRECOND_AMG) {
-        sblas_hip_amg_plan_info(p->lower, lower);
-    } else if (p->precond == SBLAS_PRECOND_CHEBYSHEV) {
-        sblas_hip_cheby_plan_info(p->lower, lower);
-    }
-    out[0] = p->n, out[1] = p->nnz, out[2] = p->m, out[3] = p->precond, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
+    int64_t lower[12], upper[12], launches[4] = {0};
+    p->pre.info(lower, upper);
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->m, out[3] = p->pre.kind, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
     out[6] = (int64_t)p->partial_bytes, out[7] = GMRES_BLOCK_SLOTS * 8, out[8] = (int64_t)GMRES_MATRIX_DOUBLES * 8, out[9] = (int64_t)p->bytes;
-    out[13] = sblas_gmres_launches(p->m, p->precond, lower, upper, launches);
+    out[13] = sblas_gmres_launches(p->m, p->pre.kind, lower, upper, launches);
     out[10] = launches[0], out[11] = launches[1], out[12] = launches[2];
     return SBLAS_OK;
 }
@@ -613,15 +563,14 @@ int sblas_hip_gmres_start(void *plan, void *stream, const double *val, const dou
         p->started = true;
         return SBLAS_OK;
     }
-    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG and Chebyshev hold their own values
-    if (!b || !x || (p->nnz > 0 && !val) || (takes_pre && !lu_or_dinv)) return SBLAS_E_INVALID;
-    p->val = val, p->pre = takes_pre ? lu_or_dinv : nullptr, p->b = b, p->x = x, p->pos = 0;
+    if (!b || !x || (p->nnz > 0 && !val) || !p->pre.take(lu_or_dinv)) return SBLAS_E_INVALID;
+    p->val = val, p->b = b, p->x = x, p->pos = 0;
     hipStream_t s = (hipStream_t)stream;
     const unsigned grid = (unsigned)p->cells;
     // (b, b) by the multi-dot of one column: the single dot's bits
     gmres_dots_kernel<<<grid, KRYLOV_LANES, 0, s>>>(ColArgs{p->n, p->cells, p->ldv, 1, MODE_FREE, b, nullptr, const_cast<double *>(b), p->part, nullptr});
     fold(p, s, GF_START_B, rtol, atol, max_iter);
-    const int rc = spmv(p, s, x, p->w());
+    const int rc = plan_spmv(p, s, x, p->w());
     if (rc != SBLAS_OK) return rc;
     gmres_residual_kernel<true><<<grid, KRYLOV_LANES, 0, s>>>(vec_args(p));
     fold(p, s, GF_BEGIN_START);

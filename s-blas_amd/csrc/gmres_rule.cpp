@@ -8,6 +8,7 @@
 #pragma clang fp contract(off) // ahead of gmres.h: every product and every sum of its functions is rounded on its own
 
 #include "gmres.h"
+#include "precond_rule.h"
 
 static_assert(SBLAS_GMRES_DENOM_GIVENS == sblas::GMRES_DENOM_GIVENS && SBLAS_GMRES_DENOM_BETA == sblas::GMRES_DENOM_BETA, "gmres.h restates them");
 static_assert(SBLAS_KRYLOV_RUNNING == sblas::GMRES_RUNNING && SBLAS_KRYLOV_CONVERGED == sblas::GMRES_CONVERGED &&
@@ -45,18 +46,8 @@ int sblas_gmres_solve_ref(int k, const double *R, int ldr, const double *g, doub
 int64_t sblas_gmres_launches(int m, int precond, const int64_t *lower_info, const int64_t *upper_info, int64_t out[4])
 {
     if (m < 1 || m > sblas::GMRES_MAX_RESTART || !out) return -1;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG &&
-        precond != SBLAS_PRECOND_CHEBYSHEV)
-        return -1;
-    int64_t apply = 0; // launches of one M^-1: the two solves' ([5] of sblas_hip_sptrsv_plan_info)
-    if (precond == SBLAS_PRECOND_ILU0) {
-        if (!lower_info || !upper_info || lower_info[5] < 0 || upper_info[5] < 0) return -1;
-        apply = lower_info[5] + upper_info[5];
-    } else if (precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV) { // one cycle ([5] of sblas_hip_amg_plan_info), or one
-                                                                                      // polynomial ([5] of sblas_hip_cheby_plan_info: the degree), in the two solves' place
-        if (!lower_info || lower_info[5] < 0) return -1;
-        apply = lower_info[5];
-    }
+    const int64_t apply = sblas::precond_launches(precond, lower_info, upper_info); // launches of one M^-1
+    if (apply < 0) return -1;
     // step (the same for every j: the kernels read j from the block): [M^-1;] SpMV; multi-dot, fold; projection;
     // multi-dot, fold; projection with (w, w); fold and scalar step; normalisation
     out[0] = 9 + apply;

@@ -25,8 +25,8 @@
 #include <initializer_list>
 #include <memory>
 #include "../../include/sblas_hip.h"
-#include "capi_util.h"
 #include "krylov.h"
+#include "precond.h"
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
 
@@ -35,10 +35,6 @@
 using namespace sblas;
 
 namespace {
-
-// a preconditioner that is applied by launches of its own between the updates: the two solves, an AMG cycle, a polynomial
-inline bool precond_applied(int precond) { return precond == SBLAS_PRECOND_ILU0 || precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV; }
-inline bool precond_known(int precond) { return precond == SBLAS_PRECOND_NONE || precond == SBLAS_PRECOND_JACOBI || precond_applied(precond); }
 
 // internal update ops, after the public SBLAS_KRYLOV_UP_* ones
 enum { UP_COPY = 5, UP_START_PCG = 6, UP_START_BICG = 7 };
@@ -279,20 +275,19 @@ inline void launch_update(hipStream_t s, int op, bool jac, const UpArgs &a)
     }
 }
 
-inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct KrylovPlan {
-    int dev = -1, method = 0, precond = 0;
+    int dev = -1, method = 0;
     int64_t n = 0, nnz = 0, cells = 0;
     const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
-    const void *spmv = nullptr, *lower = nullptr, *upper = nullptr;
+    const void *spmv = nullptr;
+    PrecondSeat pre; // start() gives it the caller's values
     int n_vectors = 0;
     size_t vector_bytes = 0, partial_bytes = 0, bytes = 0;
     DeviceBuffer buf; // block | partials | vectors
     double *blk = nullptr, *part = nullptr, *vec = nullptr;
     // one solve: start() keeps what iterate() needs
     bool started = false;
-    const double *val = nullptr, *pre = nullptr;
+    const double *val = nullptr;
     double *x = nullptr;
     double *w(int k) const { return vec + (size_t)k * (vector_bytes / 8); }
 };
@@ -300,25 +295,6 @@ struct KrylovPlan {
 // vectors of the plan, by slot
 enum { V_R = 0, V_P = 1, V_Q = 2, V_Z = 3, V_TMP_PCG = 4 };
 enum { B_R = 0, B_RHAT = 1, B_P = 2, B_V = 3, B_S = 4, B_T = 5, B_PH = 6, B_SH = 7, B_TMP = 8 };
-
-int spmv(const KrylovPlan *p, hipStream_t s, const double *x, double *y)
-{
-    if (p->spmv)
-        return sblas_hip_spmv_csr_f64_i32_planned(p->spmv, -1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
-    return sblas_hip_spmv_csr_f64_i32(-1, s, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, x, 1.0, 0.0, y);
-}
-
-// out = U^-1 (L^-1 in) with the factor the caller gave start(); with AMG, one cycle of the plan in `lower` with the
-// values of its own setup (in and out are distinct work vectors, tmp stays unused); with CHEBYSHEV the polynomial of the
-// plan in `lower`, likewise
-int ilu_apply(const KrylovPlan *p, hipStream_t s, const double *in, double *tmp, double *out)
-{
-    if (p->precond == SBLAS_PRECOND_AMG) return sblas_hip_amg_plan_apply(p->lower, s, in, out);
-    if (p->precond == SBLAS_PRECOND_CHEBYSHEV) return sblas_hip_cheby_plan_apply(p->lower, s, in, out);
-    const int rc = sblas_hip_sptrsv_f64_i32_planned(p->lower, s, p->rowptr, p->colidx, p->pre, 1.0, in, tmp);
-    if (rc != SBLAS_OK) return rc;
-    return sblas_hip_sptrsv_f64_i32_planned(p->upper, s, p->rowptr, p->colidx, p->pre, 1.0, tmp, out);
-}
 
 UpArgs up_args(const KrylovPlan *p, std::initializer_list<double *> v)
 {
@@ -337,16 +313,16 @@ void dot(const KrylovPlan *p, hipStream_t s, const double *x0, const double *y0,
 
 int pcg_iteration(const KrylovPlan *p, hipStream_t s)
 {
-    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, ilu = precond_applied(p->precond);
-    double *r = p->w(V_R), *pp = p->w(V_P), *q = p->w(V_Q), *z = p->precond == SBLAS_PRECOND_NONE ? r : p->w(V_Z);
-    int rc = spmv(p, s, pp, q);
+    const bool jac = p->pre.jacobi(), ilu = p->pre.applied();
+    double *r = p->w(V_R), *pp = p->w(V_P), *q = p->w(V_Q), *z = p->pre.none() ? r : p->w(V_Z);
+    int rc = plan_spmv(p, s, pp, q);
     if (rc != SBLAS_OK) return rc;
     dot(p, s, pp, q);
     launch_fold(s, FOLD_PCG_ALPHA, 1, 0, p->cells, p->part, p->blk);
-    launch_update(s, SBLAS_KRYLOV_UP_PCG_XR, jac, up_args(p, {p->x, r, pp, q, const_cast<double *>(p->pre), z}));
+    launch_update(s, SBLAS_KRYLOV_UP_PCG_XR, jac, up_args(p, {p->x, r, pp, q, const_cast<double *>(p->pre.values), z}));
     launch_fold(s, FOLD_PCG_RES, jac ? 2 : 1, !ilu, p->cells, p->part, p->blk);
     if (ilu) {
-        if ((rc = ilu_apply(p, s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
+        if ((rc = p->pre.apply(s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
         dot(p, s, r, z);
         launch_fold(s, FOLD_PCG_BETA, 1, 0, p->cells, p->part, p->blk);
     }
@@ -356,19 +332,18 @@ int pcg_iteration(const KrylovPlan *p, hipStream_t s)
 
 int bicgstab_iteration(const KrylovPlan *p, hipStream_t s)
 {
-    const bool jac = p->precond == SBLAS_PRECOND_JACOBI, none = p->precond == SBLAS_PRECOND_NONE;
-    const bool ilu = precond_applied(p->precond);
+    const bool jac = p->pre.jacobi(), none = p->pre.none(), ilu = p->pre.applied();
     double *r = p->w(B_R), *rh = p->w(B_RHAT), *pp = p->w(B_P), *v = p->w(B_V), *sv = p->w(B_S), *t = p->w(B_T);
-    double *ph = none ? pp : p->w(B_PH), *sh = none ? sv : p->w(B_SH), *dinv = const_cast<double *>(p->pre);
+    double *ph = none ? pp : p->w(B_PH), *sh = none ? sv : p->w(B_SH), *dinv = const_cast<double *>(p->pre.values);
     int rc;
     launch_update(s, SBLAS_KRYLOV_UP_BICG_P, jac, up_args(p, {pp, r, v, dinv, ph}));
-    if (ilu && (rc = ilu_apply(p, s, pp, p->w(B_TMP), ph)) != SBLAS_OK) return rc;
-    if ((rc = spmv(p, s, ph, v)) != SBLAS_OK) return rc;
+    if (ilu && (rc = p->pre.apply(s, pp, p->w(B_TMP), ph)) != SBLAS_OK) return rc;
+    if ((rc = plan_spmv(p, s, ph, v)) != SBLAS_OK) return rc;
     dot(p, s, rh, v);
     launch_fold(s, FOLD_BICG_ALPHA, 1, 0, p->cells, p->part, p->blk);
     launch_update(s, SBLAS_KRYLOV_UP_BICG_S, jac, up_args(p, {sv, r, v, dinv, sh}));
-    if (ilu && (rc = ilu_apply(p, s, sv, p->w(B_TMP), sh)) != SBLAS_OK) return rc;
-    if ((rc = spmv(p, s, sh, t)) != SBLAS_OK) return rc;
+    if (ilu && (rc = p->pre.apply(s, sv, p->w(B_TMP), sh)) != SBLAS_OK) return rc;
+    if ((rc = plan_spmv(p, s, sh, t)) != SBLAS_OK) return rc;
     dot(p, s, t, sv, t, t, sv, sv);
     launch_fold(s, FOLD_BICG_OMEGA, 3, 0, p->cells, p->part, p->blk);
     launch_update(s, SBLAS_KRYLOV_UP_BICG_XR, false, up_args(p, {p->x, r, ph, sh, sv, t, rh}));
@@ -437,29 +412,11 @@ int sblas_hip_krylov_plan_create(int dev, void *stream, int method, int64_t n, i
     if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
     const int device = resolve_device(dev);
     if (spmv_plan && sblas_hip_spmv_plan_speaks_for(spmv_plan, device, n, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    if (precond == SBLAS_PRECOND_AMG) { // the AMG handle travels in lower_plan's place
-        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
-        if (sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    } else if (precond == SBLAS_PRECOND_CHEBYSHEV) { // and so does the Chebyshev plan's
-        if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
-        if (sblas_hip_cheby_plan_speaks_for(lower_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    } else if (precond == SBLAS_PRECOND_ILU0) {
-        if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
-        const void *plans[2] = {lower_plan, upper_plan};
-        const int fill[2] = {SBLAS_FILL_LOWER, SBLAS_FILL_UPPER}, diag[2] = {SBLAS_DIAG_UNIT, SBLAS_DIAG_NON_UNIT};
-        for (int k = 0; k < 2; ++k) {
-            int64_t info[12];
-            if (sblas_hip_sptrsv_plan_info(plans[k], info) != SBLAS_OK) return SBLAS_E_INVALID;
-            if (info[0] != n || info[1] != nnz || info[2] != fill[k] || info[3] != diag[k]) return SBLAS_E_INVALID;
-            if (sblas_hip_sptrsv_plan_speaks_for(plans[k], device, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-        }
-    } else if (lower_plan || upper_plan) {
-        return SBLAS_E_INVALID;
-    }
     std::unique_ptr<KrylovPlan> p(new KrylovPlan);
-    p->dev = device, p->method = method, p->precond = precond, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
-    p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan, p->lower = lower_plan, p->upper = upper_plan;
-    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + precond_applied(precond);
+    if (p->pre.bind(precond, lower_plan, upper_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    p->dev = device, p->method = method, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
+    p->rowptr = rowptr, p->colidx = colidx, p->spmv = spmv_plan;
+    p->n_vectors = (method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS) + p->pre.applied();
     if (n == 0) {
         *plan_out = p.release();
         return SBLAS_OK;
@@ -480,18 +437,11 @@ int sblas_hip_krylov_plan_info(const void *plan, int64_t out[10])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const KrylovPlan *p = static_cast<const KrylovPlan *>(plan);
-    int64_t lower[12] = {0}, upper[12] = {0};
-    if (p->precond == SBLAS_PRECOND_ILU0) {
-        sblas_hip_sptrsv_plan_info(p->lower, lower);
-        sblas_hip_sptrsv_plan_info(p->upper, upper);
-    } else if (p->precond == SBLAS_PRECOND_AMG) {
-        sblas_hip_amg_plan_info(p->lower, lower);
-    } else if (p->precond == SBLAS_PRECOND_CHEBYSHEV) {
-        sblas_hip_cheby_plan_info(p->lower, lower);
-    }
-    out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
+    int64_t lower[12], upper[12];
+    p->pre.info(lower, upper);
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->pre.kind, out[4] = p->n_vectors, out[5] = (int64_t)p->vector_bytes;
     out[6] = (int64_t)p->partial_bytes, out[7] = KRYLOV_BLOCK_SLOTS * 8, out[8] = (int64_t)p->bytes;
-    out[9] = sblas_krylov_launches(p->method, p->precond, lower, upper);
+    out[9] = sblas_krylov_launches(p->method, p->pre.kind, lower, upper);
     return SBLAS_OK;
 }
 
@@ -513,29 +463,28 @@ int sblas_hip_krylov_start(void *plan, void *stream, const double *val, const do
         p->started = true;
         return SBLAS_OK;
     }
-    const bool takes_pre = p->precond == SBLAS_PRECOND_JACOBI || p->precond == SBLAS_PRECOND_ILU0; // AMG and Chebyshev hold their own values
-    if (!b || !x || (p->nnz > 0 && !val) || (takes_pre && !lu_or_dinv)) return SBLAS_E_INVALID;
-    p->val = val, p->pre = takes_pre ? lu_or_dinv : nullptr, p->x = x;
+    if (!b || !x || (p->nnz > 0 && !val) || !p->pre.take(lu_or_dinv)) return SBLAS_E_INVALID;
+    p->val = val, p->x = x;
     hipStream_t s = (hipStream_t)stream;
-    const bool pcg = p->method == SBLAS_KRYLOV_PCG, jac = p->precond == SBLAS_PRECOND_JACOBI;
+    const bool pcg = p->method == SBLAS_KRYLOV_PCG, jac = p->pre.jacobi();
     int rc;
     dot(p, s, b, b);
     launch_fold(s, FOLD_START_B, 1, !pcg, p->cells, p->part, p->blk, rtol, atol, max_iter);
-    double *bb = const_cast<double *>(b), *dinv = const_cast<double *>(p->pre);
+    double *bb = const_cast<double *>(b), *dinv = const_cast<double *>(p->pre.values);
     if (pcg) {
-        double *r = p->w(V_R), *q = p->w(V_Q), *z = p->precond == SBLAS_PRECOND_NONE ? r : p->w(V_Z);
-        if ((rc = spmv(p, s, x, q)) != SBLAS_OK) return rc;
+        double *r = p->w(V_R), *q = p->w(V_Q), *z = p->pre.none() ? r : p->w(V_Z);
+        if ((rc = plan_spmv(p, s, x, q)) != SBLAS_OK) return rc;
         launch_update(s, UP_START_PCG, jac, up_args(p, {r, bb, q, dinv, z, x}));
         launch_fold(s, FOLD_START_R, jac ? 2 : 1, 0, p->cells, p->part, p->blk);
-        if (precond_applied(p->precond)) {
-            if ((rc = ilu_apply(p, s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
+        if (p->pre.applied()) {
+            if ((rc = p->pre.apply(s, r, p->w(V_TMP_PCG), z)) != SBLAS_OK) return rc;
             dot(p, s, r, z);
             launch_fold(s, FOLD_RHO0, 1, 0, p->cells, p->part, p->blk);
         }
         launch_update(s, UP_COPY, false, up_args(p, {p->w(V_P), z}));
     } else {
         double *v = p->w(B_V);
-        if ((rc = spmv(p, s, x, v)) != SBLAS_OK) return rc;
+        if ((rc = plan_spmv(p, s, x, v)) != SBLAS_OK) return rc;
         launch_update(s, UP_START_BICG, false, up_args(p, {p->w(B_R), bb, v, p->w(B_RHAT), p->w(B_P), x}));
         launch_fold(s, FOLD_START_R, 1, 0, p->cells, p->part, p->blk);
     }

@@ -5,6 +5,7 @@
 #include <vector>
 #include "../../include/sblas_hip.h"
 #include "krylov.h"
+#include "precond_rule.h"
 
 #pragma clang fp contract(off) // a product is rounded, then the sum: as on the device
 
@@ -64,22 +65,11 @@ double sblas_krylov_dot_ref(int64_t n, const double *x, const double *y)
 int64_t sblas_krylov_launches(int method, int precond, const int64_t *lower_info, const int64_t *upper_info)
 {
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return -1;
-    if (precond != SBLAS_PRECOND_NONE && precond != SBLAS_PRECOND_JACOBI && precond != SBLAS_PRECOND_ILU0 && precond != SBLAS_PRECOND_AMG &&
-        precond != SBLAS_PRECOND_CHEBYSHEV)
-        return -1;
-    int64_t apply = 0; // launches of one M^-1: the two solves' ([5] of sblas_hip_sptrsv_plan_info)
-    if (precond == SBLAS_PRECOND_ILU0) {
-        if (!lower_info || !upper_info || lower_info[5] < 0 || upper_info[5] < 0) return -1;
-        apply = lower_info[5] + upper_info[5];
-    } else if (precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV) { // one cycle ([5] of sblas_hip_amg_plan_info), or one
-                                                                                      // polynomial ([5] of sblas_hip_cheby_plan_info: the degree), in the two solves' place
-        if (!lower_info || lower_info[5] < 0) return -1;
-        apply = lower_info[5];
-    }
-    const bool applied = precond == SBLAS_PRECOND_ILU0 || precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV;
+    const int64_t apply = sblas::precond_launches(precond, lower_info, upper_info); // launches of one M^-1
+    if (apply < 0) return -1;
     if (method == SBLAS_KRYLOV_PCG) {
-        // SpMV; (p, q): stage 1, fold; x / r update; fold; p update -- with ILU(0): M^-1, (r, z): stage 1, fold
-        return applied ? 8 + apply : 6;
+        // SpMV; (p, q): stage 1, fold; x / r update; fold; p update -- with an applied M^-1: M^-1, (r, z): stage 1, fold
+        return sblas::precond_applied(precond) ? 8 + apply : 6;
     }
     // p update; SpMV; (r^, v): stage 1, fold; s update; SpMV; (t, s), (t, t) and (s, s): stage 1, fold; x / r update; fold
     return 10 + 2 * apply;

@@ -1,0 +1,35 @@
+// precond_rule.h -- the rule of the preconditioner kinds (SBLAS_PRECOND_*), once: which codes are known and what each
+// kind asks of a solver.  krylov_rule.cpp and gmres_rule.cpp count launches by it, and the seat a solver plan holds
+// (precond.h) decides by it.  No HIP in here: the rule files are testable on a CPU box.  A new kind is added here and
+// in precond.h, nowhere else.
+#pragma once
+#include <stdint.h>
+#include "../../include/sblas_hip.h"
+
+namespace sblas {
+
+// applied by launches of its own between the solver's kernels: the two solves, an AMG cycle, a polynomial.  (Jacobi
+// rides in the solvers' own kernels.)
+inline bool precond_applied(int kind) { return kind == SBLAS_PRECOND_ILU0 || kind == SBLAS_PRECOND_AMG || kind == SBLAS_PRECOND_CHEBYSHEV; }
+inline bool precond_known(int kind) { return kind == SBLAS_PRECOND_NONE || kind == SBLAS_PRECOND_JACOBI || precond_applied(kind); }
+// takes the caller's values at start (the inverse diagonal, the factor); the other kinds hold those of their own setup
+inline bool precond_takes_values(int kind) { return kind == SBLAS_PRECOND_JACOBI || kind == SBLAS_PRECOND_ILU0; }
+// may run with out == in: the two solves go through a temporary; a cycle or a polynomial reads in while it writes out
+inline bool precond_in_place(int kind) { return kind == SBLAS_PRECOND_ILU0; }
+// holds two plans, lower and upper; every other applied kind holds one handle in lower's place and no upper
+inline bool precond_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
+
+// Launches of one M^-1, from [5] of the plans' info (sblas_hip_sptrsv_plan_info of the two solves; with one handle
+// sblas_hip_amg_plan_info, one cycle's, or sblas_hip_cheby_plan_info, the degree).  0 for a kind that is not applied,
+// whatever the infos; -1 for an unknown kind, a missing info or a negative [5].
+inline int64_t precond_launches(int kind, const int64_t *lower_info, const int64_t *upper_info)
+{
+    if (!precond_known(kind)) return -1;
+    if (!precond_applied(kind)) return 0;
+    if (!lower_info || lower_info[5] < 0) return -1;
+    if (!precond_pair(kind)) return lower_info[5];
+    if (!upper_info || upper_info[5] < 0) return -1;
+    return lower_info[5] + upper_info[5];
+}
+
+} // namespace sblas

@@ -806,6 +806,8 @@ KRYLOV_STATUS = {KRYLOV_RUNNING: "running", KRYLOV_CONVERGED: "converged", KRYLO
 KRYLOV_DENOM = {0: None, 1: "(p, q)", 2: "rho", 3: "(r^, v)", 4: "(t, t)", 5: "omega"}
 KRYLOV_UPDATES = {"pcg_xr": 0, "pcg_p": 1, "bicg_p": 2, "bicg_s": 3, "bicg_xr": 4}
 _KRYLOV_METHOD = {"pcg": KRYLOV_PCG, "bicgstab": KRYLOV_BICGSTAB}
+_PRECOND_NAME = (None, "jacobi", "ilu0", "amg", "chebyshev")                # a kind's name, at its code PRECOND_*
+_PRECOND_CODE = {name: code for code, name in enumerate(_PRECOND_NAME)}
 
 
 def krylov_limits():
@@ -832,10 +834,9 @@ def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches
     AmgPlan.info()["launches"], one cycle's; with "chebyshev" it is the polynomial's degree."""
     if method not in _KRYLOV_METHOD:
         raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
-    code = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG, "chebyshev": PRECOND_CHEBYSHEV}.get(precond, -1)
     lo, up = (C.c_int64 * 12)(), (C.c_int64 * 12)()
     lo[5], up[5] = int(lower_launches), int(upper_launches)
-    n = int(lib().sblas_krylov_launches(_KRYLOV_METHOD[method], code, lo, up))
+    n = int(lib().sblas_krylov_launches(_KRYLOV_METHOD[method], _PRECOND_CODE.get(precond, -1), lo, up))
     if n < 0:
         raise SblasError("sblas_krylov_launches refused its arguments")
     return n
@@ -844,7 +845,6 @@ def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches
 # Restarted GMRES: the denominators a breakdown names continue the Krylov solvers' (SBLAS_GMRES_DENOM_*)
 GMRES_DENOM = dict(KRYLOV_DENOM)
 GMRES_DENOM.update({6: "givens", 7: "beta"})
-_PRECOND_CODE = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "ilu0": PRECOND_ILU0, "amg": PRECOND_AMG, "chebyshev": PRECOND_CHEBYSHEV}
 
 
 def gmres_limits():
@@ -3106,73 +3106,46 @@ def krylov_update(op, scalars, vectors, partial=None, jacobi=False, stream=None)
               "sblas_hip_krylov_update_f64")
 
 
-class KrylovPlan:
-    """A Krylov solver for A x = b on the n x n CSR structure (rowptr, colidx), int32 indices, resident on the device
-    (sblas_hip_krylov_plan_create).  method: "pcg" (A symmetric positive definite) or "bicgstab".  spmv_plan: an SpmvPlan on
-    the same tensors, or None.  precond: None, "jacobi" (start / solve take dinv, the inverse diagonal) or an Ilu0Plan on
-    the same tensors (they take lu, its factor; a pair (lower, upper) of SptrsvPlans serves too).  The plan owns the work
-    vectors, the partial sums and the scalar block, and keeps the tensors and plans it was given alive.
+def _precond_seat(precond):
+    """precond as a solver plan takes it -> (kind, lower, upper): the code PRECOND_* and the plans whose handles go with it.
+    An AmgPlan's or a ChebyshevPlan's handle travels in the lower plan's place, with no upper one."""
+    if precond is None:
+        return PRECOND_NONE, None, None
+    if isinstance(precond, str) and precond == "jacobi":
+        return PRECOND_JACOBI, None, None
+    if isinstance(precond, Ilu0Plan):
+        return (PRECOND_ILU0,) + tuple(precond.solvers())
+    if isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
+        return PRECOND_ILU0, precond[0], precond[1]
+    if isinstance(precond, AmgPlan):
+        return PRECOND_AMG, precond, None
+    if isinstance(precond, ChebyshevPlan):
+        return PRECOND_CHEBYSHEV, precond, None
+    raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan or a ChebyshevPlan, not %r" % (precond,))
 
-    start() forms r = b - A x and the first direction; iterate(k) enqueues k iterations without allocating or
-    synchronising (graph-capturable); status() is the one call that synchronises.  Once the stopping test
-    |r| <= max(rtol |b|, atol) is met on the device, the iterations already enqueued change nothing: x, the count and
-    |r| are those of the iteration that met it, whatever check_every is.  Every bit is pinned (include/sblas_hip.h).
 
-    A system in the multicolour order is the caller's composition:
-        color = ColorPlan(n, rowptr, colidx); perm = color.permute(rowptr, colidx); rp, ci, _ = perm.csr()
-        ilu = Ilu0Plan(n, rp, ci); val_b = perm.values(val); lu = ilu.factor(val_b)
-        x_b, st = KrylovPlan(n, rp, ci, precond=ilu).solve(val_b, perm.to_permuted(b), lu=lu)
-        x = perm.from_permuted(x_b)"""
+class _SolverPlan:
+    """What KrylovPlan and GmresPlan share: the seat of the preconditioner, start / iterate / solve and the handle's end.
+    A subclass names its C functions in _c (sblas_hip_<_c>_start, ...), checks its own arguments, creates the handle and
+    gives info() and status()."""
 
-    def __init__(self, n, rowptr, colidx, method="pcg", spmv_plan=None, precond=None, stream=None):
-        import torch
-        self.handle = None
-        if method not in _KRYLOV_METHOD:
-            raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
-        self.n, self.method = n, method
-        self.nnz = _structure(n, rowptr, colidx)
-        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+    def _seat(self, spmv_plan, precond):
+        """refuses precond, then spmv_plan -> what plan_create takes after the structure: (spmv, kind, lower, upper)"""
         self.spmv_plan, self.precond = spmv_plan, precond
-        lower = upper = None
-        if precond is None:
-            self.precond_kind = PRECOND_NONE
-        elif isinstance(precond, str) and precond == "jacobi":
-            self.precond_kind = PRECOND_JACOBI
-        elif isinstance(precond, Ilu0Plan):
-            self.precond_kind = PRECOND_ILU0
-            lower, upper = precond.solvers()
-        elif isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
-            self.precond_kind = PRECOND_ILU0
-            lower, upper = precond
-        elif isinstance(precond, AmgPlan):                                  # the handle travels in the lower plan's place
-            self.precond_kind = PRECOND_AMG
-            lower = precond
-        elif isinstance(precond, ChebyshevPlan):                            # and so does the Chebyshev plan's
-            self.precond_kind = PRECOND_CHEBYSHEV
-            lower = precond
-        else:
-            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan or a ChebyshevPlan, not %r"
-                             % (precond,))
+        self.precond_kind, lower, upper = _precond_seat(precond)
         if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
             raise SblasError("spmv_plan must be an SpmvPlan or None")
         self._solvers = (lower, upper)
         self._keep = None
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_krylov_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
-                                                    colidx.data_ptr() if self.nnz else None,
-                                                    spmv_plan.handle if spmv_plan is not None else None, self.precond_kind,
-                                                    lower.handle if lower is not None else None,
-                                                    upper.handle if upper is not None else None, C.byref(h))
-        check(rc, "sblas_hip_krylov_plan_create")
-        self.handle = h
+        return (spmv_plan.handle if spmv_plan is not None else None, self.precond_kind,
+                lower.handle if lower is not None else None, upper.handle if upper is not None else None)
 
-    def info(self):
-        out = (C.c_int64 * 10)()
-        check(lib().sblas_hip_krylov_plan_info(self.handle, out), "sblas_hip_krylov_plan_info")
-        return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
-                    precond=(None, "jacobi", "ilu0", "amg", "chebyshev")[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
-                    scalar_bytes=int(out[7]), bytes=int(out[8]), launches=int(out[9]))
+    def _bind(self, n, rowptr, colidx):
+        self.n, self.nnz = n, _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+
+    def _call(self, name):
+        return getattr(lib(), "sblas_hip_%s_%s" % (self._c, name))
 
     def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
         """Begins a solve: x on entry is the initial guess and is updated in place by iterate().  lu: the ILU(0) factor
@@ -3196,29 +3169,19 @@ class KrylovPlan:
         if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
             raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
         with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_krylov_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
-                                              pre.data_ptr() if pre is not None and pre.numel() else None,
-                                              b.data_ptr() if self.n else None, x.data_ptr() if self.n else None,
-                                              float(rtol), float(atol), int(max_iter))
-        check(rc, "sblas_hip_krylov_start")
+            rc = self._call("start")(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                     pre.data_ptr() if pre is not None and pre.numel() else None,
+                                     b.data_ptr() if self.n else None, x.data_ptr() if self.n else None,
+                                     float(rtol), float(atol), int(max_iter))
+        check(rc, "sblas_hip_%s_start" % self._c)
         self._keep = (val, b, x, pre)
 
     def iterate(self, k, stream=None):
-        """Enqueues k iterations: allocates nothing, never synchronises, graph-capturable as a chain."""
+        """Enqueues k iterations (GMRES: Arnoldi steps, and the closes and restarts that belong with them): allocates
+        nothing, never synchronises, graph-capturable as a chain."""
         import torch
         with torch.cuda.device(self.device):
-            check(lib().sblas_hip_krylov_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_krylov_iterate")
-
-    def status(self, stream=None):
-        """Copies the scalar block back and synchronises the stream -> dict(status, code, iterations, rnorm, bnorm, alpha,
-        beta, omega, breakdown): status is "running", "converged", "breakdown" or "limit"; breakdown names the zero or
-        non-finite denominator (a value of KRYLOV_DENOM) or is None."""
-        import torch
-        out = (C.c_double * 8)()
-        with torch.cuda.device(self.device):
-            check(lib().sblas_hip_krylov_status(self.handle, _stream(stream), out), "sblas_hip_krylov_status")
-        return dict(status=KRYLOV_STATUS[int(out[0])], code=int(out[0]), iterations=int(out[1]), rnorm=float(out[2]), bnorm=float(out[3]),
-                    alpha=float(out[4]), beta=float(out[5]), omega=float(out[6]), breakdown=KRYLOV_DENOM[int(out[7])])
+            check(self._call("iterate")(self.handle, _stream(stream), int(k)), "sblas_hip_%s_iterate" % self._c)
 
     def solve(self, val, b, x=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
         """start(), then iterate(check_every) / status() until the status is not "running" -> (x, status dict).  x: the
@@ -3238,7 +3201,7 @@ class KrylovPlan:
 
     def destroy(self):
         if self.handle:
-            lib().sblas_hip_krylov_plan_destroy(self.handle)
+            self._call("plan_destroy")(self.handle)
             self.handle = None
         self._keep = None
 
@@ -3247,6 +3210,60 @@ class KrylovPlan:
             self.destroy()
         except Exception:
             pass
+
+
+class KrylovPlan(_SolverPlan):
+    """A Krylov solver for A x = b on the n x n CSR structure (rowptr, colidx), int32 indices, resident on the device
+    (sblas_hip_krylov_plan_create).  method: "pcg" (A symmetric positive definite) or "bicgstab".  spmv_plan: an SpmvPlan on
+    the same tensors, or None.  precond: None, "jacobi" (start / solve take dinv, the inverse diagonal) or an Ilu0Plan on
+    the same tensors (they take lu, its factor; a pair (lower, upper) of SptrsvPlans serves too).  The plan owns the work
+    vectors, the partial sums and the scalar block, and keeps the tensors and plans it was given alive.
+
+    start() forms r = b - A x and the first direction; iterate(k) enqueues k iterations without allocating or
+    synchronising (graph-capturable); status() is the one call that synchronises.  Once the stopping test
+    |r| <= max(rtol |b|, atol) is met on the device, the iterations already enqueued change nothing: x, the count and
+    |r| are those of the iteration that met it, whatever check_every is.  Every bit is pinned (include/sblas_hip.h).
+
+    A system in the multicolour order is the caller's composition:
+        color = ColorPlan(n, rowptr, colidx); perm = color.permute(rowptr, colidx); rp, ci, _ = perm.csr()
+        ilu = Ilu0Plan(n, rp, ci); val_b = perm.values(val); lu = ilu.factor(val_b)
+        x_b, st = KrylovPlan(n, rp, ci, precond=ilu).solve(val_b, perm.to_permuted(b), lu=lu)
+        x = perm.from_permuted(x_b)"""
+
+    _c = "krylov"
+
+    def __init__(self, n, rowptr, colidx, method="pcg", spmv_plan=None, precond=None, stream=None):
+        import torch
+        self.handle = None
+        if method not in _KRYLOV_METHOD:
+            raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
+        self.method = method
+        self._bind(n, rowptr, colidx)
+        seat = self._seat(spmv_plan, precond)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_krylov_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                    colidx.data_ptr() if self.nnz else None, *seat, C.byref(h))
+        check(rc, "sblas_hip_krylov_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 10)()
+        check(lib().sblas_hip_krylov_plan_info(self.handle, out), "sblas_hip_krylov_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
+                    precond=_PRECOND_NAME[out[3]], vectors=int(out[4]), vector_bytes=int(out[5]), partial_bytes=int(out[6]),
+                    scalar_bytes=int(out[7]), bytes=int(out[8]), launches=int(out[9]))
+
+    def status(self, stream=None):
+        """Copies the scalar block back and synchronises the stream -> dict(status, code, iterations, rnorm, bnorm, alpha,
+        beta, omega, breakdown): status is "running", "converged", "breakdown" or "limit"; breakdown names the zero or
+        non-finite denominator (a value of KRYLOV_DENOM) or is None."""
+        import torch
+        out = (C.c_double * 8)()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_krylov_status(self.handle, _stream(stream), out), "sblas_hip_krylov_status")
+        return dict(status=KRYLOV_STATUS[int(out[0])], code=int(out[0]), iterations=int(out[1]), rnorm=float(out[2]), bnorm=float(out[3]),
+                    alpha=float(out[4]), beta=float(out[5]), omega=float(out[6]), breakdown=KRYLOV_DENOM[int(out[7])])
 
 
 def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
@@ -3370,7 +3387,7 @@ def gmres_combine(V, y, out=None, stream=None):
     return out
 
 
-class GmresPlan:
+class GmresPlan(_SolverPlan):
     """Right-preconditioned restarted GMRES(restart) for A x = b on the n x n CSR structure (rowptr, colidx), int32
     indices, resident on the device (sblas_hip_gmres_plan_create).  A need not be symmetric.  spmv_plan and precond: as
     KrylovPlan's.  A plan of its own rather than a method of KrylovPlan: it owns restart + 1 basis vectors and the small
@@ -3382,94 +3399,36 @@ class GmresPlan:
     what is already enqueued only forms x from the finished columns: x, the count, |r| and the restart count do not
     depend on check_every.  Every bit is pinned (include/sblas_hip.h)."""
 
+    _c = "gmres"
+
     def __init__(self, n, rowptr, colidx, restart=30, spmv_plan=None, precond=None, stream=None):
         import torch
         self.handle = None
         if isinstance(restart, bool) or not isinstance(restart, int) or not 1 <= restart <= gmres_limits()["max_restart"]:
             raise SblasError("restart must be an integer in [1, %d], not %r" % (gmres_limits()["max_restart"], restart))
-        self.n, self.restart = n, restart
-        self.spmv_plan, self.precond = spmv_plan, precond
-        lower = upper = None
-        if precond is None:
-            self.precond_kind = PRECOND_NONE
-        elif isinstance(precond, str) and precond == "jacobi":
-            self.precond_kind = PRECOND_JACOBI
-        elif isinstance(precond, Ilu0Plan):
-            self.precond_kind = PRECOND_ILU0
-            lower, upper = precond.solvers()
-        elif isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond):
-            self.precond_kind = PRECOND_ILU0
-            lower, upper = precond
-        elif isinstance(precond, AmgPlan):                                  # the handle travels in the lower plan's place
-            self.precond_kind = PRECOND_AMG
-            lower = precond
-        elif isinstance(precond, ChebyshevPlan):                            # and so does the Chebyshev plan's
-            self.precond_kind = PRECOND_CHEBYSHEV
-            lower = precond
-        else:
-            raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan or a ChebyshevPlan, not %r"
-                             % (precond,))
-        if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
-            raise SblasError("spmv_plan must be an SpmvPlan or None")
-        self.nnz = _structure(n, rowptr, colidx)
-        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
-        self._solvers = (lower, upper)
-        self._keep = None
+        self.restart = restart
+        seat = self._seat(spmv_plan, precond)
+        self._bind(n, rowptr, colidx)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = lib().sblas_hip_gmres_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
-                                                   colidx.data_ptr() if self.nnz else None, restart,
-                                                   spmv_plan.handle if spmv_plan is not None else None, self.precond_kind,
-                                                   lower.handle if lower is not None else None,
-                                                   upper.handle if upper is not None else None, C.byref(h))
+                                                   colidx.data_ptr() if self.nnz else None, restart, *seat, C.byref(h))
         check(rc, "sblas_hip_gmres_plan_create")
         self.handle = h
 
     def info(self):
         out = (C.c_int64 * 14)()
         check(lib().sblas_hip_gmres_plan_info(self.handle, out), "sblas_hip_gmres_plan_info")
-        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=(None, "jacobi", "ilu0", "amg", "chebyshev")[out[3]], vectors=int(out[4]),
+        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=_PRECOND_NAME[out[3]], vectors=int(out[4]),
                     vector_bytes=int(out[5]), partial_bytes=int(out[6]), scalar_bytes=int(out[7]), matrix_bytes=int(out[8]),
                     bytes=int(out[9]), step_launches=int(out[10]), close_launches=int(out[11]), restart_launches=int(out[12]),
                     cycle_launches=int(out[13]))
 
     def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
-        """Begins a solve: x on entry is the initial guess and is updated in place as cycles close.  lu: the ILU(0) factor
-        (precond an Ilu0Plan); dinv: the inverse diagonal (precond "jacobi").  Every refusal comes before any launch."""
-        import torch
+        """As KrylovPlan.start(); x is updated in place as cycles close.  x is b is refused before anything is looked at."""
         if x is b:
             raise SblasError("x must not be b")
-        _krylov_vector("val", val, self.nnz, self.device), _krylov_vector("b", b, self.n, self.device)
-        _krylov_vector("x", x, self.n, self.device)
-        pre = None
-        if self.precond_kind == PRECOND_ILU0:
-            if lu is None:
-                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
-            _krylov_vector("lu", lu, self.nnz, self.device)
-            pre = lu
-        elif self.precond_kind == PRECOND_JACOBI:
-            if dinv is None:
-                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
-            _krylov_vector("dinv", dinv, self.n, self.device)
-            pre = dinv
-        if self.n and x.data_ptr() == b.data_ptr():
-            raise SblasError("x must not be b")
-        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
-            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
-        with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_gmres_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
-                                             pre.data_ptr() if pre is not None and pre.numel() else None,
-                                             b.data_ptr() if self.n else None, x.data_ptr() if self.n else None,
-                                             float(rtol), float(atol), int(max_iter))
-        check(rc, "sblas_hip_gmres_start")
-        self._keep = (val, b, x, pre)
-
-    def iterate(self, k, stream=None):
-        """Enqueues k Arnoldi steps and the closes and restarts that belong with them: allocates nothing, never
-        synchronises, graph-capturable as a chain."""
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib().sblas_hip_gmres_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_gmres_iterate")
+        super().start(val, b, x, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
 
     def status(self, stream=None):
         """Copies the scalar block back and synchronises the stream -> dict(status, code, iterations, rnorm, bnorm,
@@ -3481,34 +3440,6 @@ class GmresPlan:
             check(lib().sblas_hip_gmres_status(self.handle, _stream(stream), out), "sblas_hip_gmres_status")
         return dict(status=KRYLOV_STATUS[int(out[0])], code=int(out[0]), iterations=int(out[1]), rnorm=float(out[2]), bnorm=float(out[3]),
                     restarts=int(out[4]), columns=int(out[5]), eta=float(out[6]), breakdown=GMRES_DENOM[int(out[7])])
-
-    def solve(self, val, b, x=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
-        """start(), then iterate(check_every) / status() until the status is not "running" -> (x, status dict).  x: the
-        initial guess, updated in place (zeros made here when None).  The result does not depend on check_every."""
-        import torch
-        if int(check_every) < 1:
-            raise SblasError("check_every must be at least 1")
-        if x is None:
-            _krylov_vector("b", b, self.n, self.device)
-            x = torch.zeros(self.n, dtype=torch.float64, device=self.device)
-        self.start(val, b, x, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
-        while True:
-            self.iterate(int(check_every), stream=stream)
-            st = self.status(stream=stream)
-            if st["code"] != KRYLOV_RUNNING:
-                return x, st
-
-    def destroy(self):
-        if self.handle:
-            lib().sblas_hip_gmres_plan_destroy(self.handle)
-            self.handle = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def gmres(A, b, precond=None, restart=30, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):

@@ -213,3 +213,51 @@ def test_python_refusals_need_no_gpu(sblas):
     with pytest.raises(E):
         sblas.krylov_launches("gmres")
     assert set(sblas.krylov_limits()) == {"cell", "width", "pcg_vectors", "bicgstab_vectors", "max_dots"}
+
+
+KINDS = (None, "jacobi", "ilu0", "amg", "chebyshev")                         # by code: SBLAS_PRECOND_*
+
+
+def test_the_two_launch_rules_agree_on_one_application(sblas):
+    """one M^-1 costs the same launches under PCG, BiCGStab and GMRES: the kind rule is written once (precond_rule.h)"""
+    for precond in KINDS:
+        for lower in (0, 1, 7):
+            for upper in (0, 1, 7):
+                pcg = sblas.krylov_launches("pcg", precond, lower, upper)
+                bicg = sblas.krylov_launches("bicgstab", precond, lower, upper)
+                g = sblas.gmres_launches(5, precond, lower, upper)
+                apply = g["close"] - 3
+                if precond in ("ilu0", "amg", "chebyshev"):                  # applied by launches of their own
+                    assert apply == (lower + upper if precond == "ilu0" else lower), (precond, lower, upper)
+                    assert g["step"] - 9 == pcg - 8, (precond, lower, upper)
+                else:
+                    assert apply == 0 and pcg == 6, (precond, lower, upper)
+                assert g["step"] - 9 == apply, (precond, lower, upper)
+                assert bicg - 10 == 2 * apply, (precond, lower, upper)
+
+
+def test_the_raw_launch_rules_refuse_the_same_arguments(sblas):
+    import ctypes as C
+    L = sblas.lib()
+
+    def info(v):
+        if v is None:
+            return None
+        a = (C.c_int64 * 12)()
+        a[5] = v
+        return a
+
+    refused = 0
+    for precond in range(-1, 6):
+        for lower in (None, -1, 3):
+            for upper in (None, -1, 3):
+                out = (C.c_int64 * 4)()
+                k = [L.sblas_krylov_launches(method, precond, info(lower), info(upper)) for method in (0, 1)]
+                g = L.sblas_gmres_launches(30, precond, info(lower), info(upper), out)
+                assert (k[0] == -1) == (k[1] == -1) == (g == -1), (precond, lower, upper, k, g)
+                # what is refused, said once more: an unknown kind; ILU(0) without both infos; a cycle or a polynomial
+                # without the lower one
+                want = precond not in range(5) or (precond == 2 and (lower != 3 or upper != 3)) or (precond in (3, 4) and lower != 3)
+                assert (g == -1) == want, (precond, lower, upper, g)
+                refused += g == -1
+    assert refused == 2 * 9 + 8 + 2 * 6

@@ -147,6 +147,19 @@ int main()
         bad += sblas_gmres_launches(30, SBLAS_PRECOND_NONE, nullptr, nullptr, nullptr) != -1;
         lower[5] = -1;
         bad += sblas_gmres_launches(30, SBLAS_PRECOND_ILU0, lower, upper, out) != -1;
+        // every kind (and the codes on either side), with each info missing, negative or good: an applied kind adds its
+        // M^-1 to a step and to a close, ILU(0) from both infos and a cycle or a polynomial from the lower one alone
+        for (int precond = -1; precond <= 5; ++precond)
+            for (int lo = 0; lo < 3; ++lo)
+                for (int up = 0; up < 3; ++up) {
+                    lower[5] = lo == 1 ? -1 : 3, upper[5] = up == 1 ? -1 : 7;
+                    const int64_t *li = lo ? lower : nullptr, *ui = up ? upper : nullptr;
+                    const bool solves = precond == SBLAS_PRECOND_ILU0, single = precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV;
+                    const bool refused = precond < 0 || precond > 4 || (solves && (lo != 2 || up != 2)) || (single && lo != 2);
+                    const int64_t apply = solves ? 10 : single ? 3 : 0, got = sblas_gmres_launches(2, precond, li, ui, out);
+                    if (refused) bad += got != -1;
+                    else bad += got != 2 * (9 + apply) + (3 + apply) + 4 || out[0] != 9 + apply || out[1] != 3 + apply || out[2] != 4 || out[3] != 6;
+                }
     }
     if (bad) printf("gmres rule check: %d FAILED\n", bad);
     else printf("gmres rule check: ok\n");

@@ -77,6 +77,19 @@ int main()
     bad += sblas_krylov_launches(SBLAS_KRYLOV_PCG, 3, nullptr, nullptr) != -1;
     lower[5] = -1;
     bad += sblas_krylov_launches(SBLAS_KRYLOV_PCG, SBLAS_PRECOND_ILU0, lower, upper) != -1;
+    // every kind (and the codes on either side), with each info missing, negative or good: an applied kind adds its M^-1
+    // once to PCG and twice to BiCGStab, ILU(0) from both infos and a cycle or a polynomial from the lower one alone
+    for (int precond = -1; precond <= 5; ++precond)
+        for (int lo = 0; lo < 3; ++lo)
+            for (int up = 0; up < 3; ++up) {
+                lower[5] = lo == 1 ? -1 : 3, upper[5] = up == 1 ? -1 : 7;
+                const int64_t *li = lo ? lower : nullptr, *ui = up ? upper : nullptr;
+                const bool solves = precond == SBLAS_PRECOND_ILU0, single = precond == SBLAS_PRECOND_AMG || precond == SBLAS_PRECOND_CHEBYSHEV;
+                const bool refused = precond < 0 || precond > 4 || (solves && (lo != 2 || up != 2)) || (single && lo != 2);
+                const int64_t apply = solves ? 10 : 3;
+                bad += sblas_krylov_launches(SBLAS_KRYLOV_PCG, precond, li, ui) != (refused ? -1 : solves || single ? 8 + apply : 6);
+                bad += sblas_krylov_launches(SBLAS_KRYLOV_BICGSTAB, precond, li, ui) != (refused ? -1 : solves || single ? 10 + 2 * apply : 10);
+            }
     if (bad) printf("krylov rule check: %d FAILED\n", bad);
     else printf("krylov rule check: ok\n");
     return bad != 0;
