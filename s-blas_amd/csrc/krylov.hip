@@ -30,7 +30,8 @@
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
 
-#include "krylov_fold.h" // wave_fold, group_fold, cell_walk, cell_store: shared with gmres.hip
+#include "krylov_fold.h"   // wave_fold, group_fold, cell_walk, cell_store: shared with gmres.hip and krylov_multi.hip
+#include "krylov_scalar.h" // the fold ops and lane 0's scalar step: shared with krylov_multi.hip
 
 using namespace sblas;
 
@@ -38,20 +39,6 @@ namespace {
 
 // internal update ops, after the public SBLAS_KRYLOV_UP_* ones
 enum { UP_COPY = 5, UP_START_PCG = 6, UP_START_BICG = 7 };
-// fold ops: what lane 0 does with the folded sums d[0 .. nd - 1]
-enum {
-    FOLD_OUT = 0,     // out[k] = d[k]                                  (sblas_hip_krylov_dot_f64)
-    FOLD_START_B,     // |b|, the tolerance, and the block's first state (flag: BiCGStab)
-    FOLD_START_R,     // |r0| and the test at iteration 0; rho = d[nd - 1]
-    FOLD_RHO0,        // rho = d[0]                                     (PCG with ILU(0): (r0, z0))
-    FOLD_PCG_ALPHA,   // alpha = rho / (p, q)
-    FOLD_PCG_RES,     // |r|, count, test; flag: then beta = d[nd - 1] / rho
-    FOLD_PCG_BETA,    // beta = d[0] / rho                              (PCG with ILU(0))
-    FOLD_BICG_ALPHA,  // alpha = rho / (r^, v)
-    FOLD_BICG_OMEGA,  // omega = (t, s) / (t, t); d[2] = (s, s) for the half step that already meets the test
-    FOLD_BICG_RES     // |r|, count, test, beta = ((r^, r) / rho) * (alpha / omega)
-};
-
 struct UpArgs {
     int64_t n, cells;
     double *blk;  // the scalar block
@@ -156,87 +143,17 @@ template <int OP, bool JAC> __global__ __launch_bounds__(KRYLOV_LANES) void kryl
 }
 
 // ---- stage 2, which is also the scalar step ----------------------------------------------------------------------------
-__device__ __forceinline__ bool bad_denominator(double d) { return d == 0.0 || !isfinite(d); }
-
-__device__ __forceinline__ void break_down(double *blk, long long which)
-{
-    long long *ib = reinterpret_cast<long long *>(blk);
-    ib[KS_STATUS] = SBLAS_KRYLOV_BREAKDOWN, ib[KS_WHICH] = which;
-}
-
-// |r|, the count and the test; true when the recurrence goes on
-__device__ __forceinline__ bool residual_step(double *blk, double rr, bool count)
-{
-    long long *ib = reinterpret_cast<long long *>(blk);
-    const double rnorm = sqrt(rr);
-    blk[KS_RNORM] = rnorm;
-    if (count) ib[KS_ITER] = ib[KS_ITER] + 1;
-    if (rnorm <= blk[KS_TOL]) ib[KS_STATUS] = SBLAS_KRYLOV_CONVERGED;
-    else if (ib[KS_ITER] >= ib[KS_MAX_ITER]) ib[KS_STATUS] = SBLAS_KRYLOV_LIMIT;
-    else return true;
-    return false;
-}
-
 __global__ __launch_bounds__(KRYLOV_LANES) void krylov_fold_kernel(int op, int nd, int flag, int64_t cells, const double *part, double *blk,
                                                                   double rtol, double atol, long long max_iter)
 {
-    // lane t adds partial[t], partial[t + 256], ... in order from +0, then the same butterfly
-    double acc[KRYLOV_MAX_DOTS] = {}, d[KRYLOV_MAX_DOTS];
-    for (int64_t c = threadIdx.x; c < cells; c += KRYLOV_LANES)
-        for (int q = 0; q < nd; ++q) acc[q] = acc[q] + part[q * cells + c];
-    group_fold<KRYLOV_MAX_DOTS>(acc, d);
+    double d[KRYLOV_MAX_DOTS];
+    cells_fold(nd, cells, part, cells, d);
     if (threadIdx.x != 0) return;
-    long long *ib = reinterpret_cast<long long *>(blk);
     if (op == FOLD_OUT) {
         for (int q = 0; q < nd; ++q) blk[q] = d[q];
         return;
     }
-    if (op == FOLD_START_B) {
-        const double bnorm = sqrt(d[0]), t = rtol * bnorm;
-        // every slot by its own type: a slot is never read as the other one
-        blk[KS_RNORM] = 0.0, blk[KS_ALPHA] = 0.0, blk[KS_BETA] = 0.0, blk[KS_RHO] = 0.0, blk[KS_OMEGA] = flag ? 1.0 : 0.0;
-        blk[KS_BNORM] = bnorm, blk[KS_TOL] = t >= atol ? t : atol;
-        ib[KS_ITER] = 0, ib[KS_WHICH] = 0, ib[KS_MAX_ITER] = max_iter;
-        const bool zero = d[0] == 0.0; // b == 0: x = 0, converged at iteration 0, and nothing is divided
-        ib[KS_ZERO_X] = zero, ib[KS_STATUS] = zero ? SBLAS_KRYLOV_CONVERGED : SBLAS_KRYLOV_RUNNING;
-        return;
-    }
-    if (ib[KS_STATUS] != SBLAS_KRYLOV_RUNNING) return; // frozen: the scalars stay what they were
-    const double rho = blk[KS_RHO];
-    switch (op) {
-    case FOLD_START_R:
-        blk[KS_RHO] = d[nd - 1];
-        residual_step(blk, d[0], false);
-        break;
-    case FOLD_RHO0: blk[KS_RHO] = d[0]; break;
-    case FOLD_PCG_ALPHA:
-    case FOLD_BICG_ALPHA:
-        if (bad_denominator(d[0])) break_down(blk, op == FOLD_PCG_ALPHA ? SBLAS_KRYLOV_DENOM_PQ : SBLAS_KRYLOV_DENOM_RV);
-        else blk[KS_ALPHA] = rho / d[0];
-        break;
-    case FOLD_PCG_RES:
-        if (!residual_step(blk, d[0], true) || !flag) break;
-        [[fallthrough]];
-    case FOLD_PCG_BETA: {
-        const double rho_new = d[op == FOLD_PCG_RES ? nd - 1 : 0];
-        if (bad_denominator(rho)) break_down(blk, SBLAS_KRYLOV_DENOM_RHO);
-        else blk[KS_BETA] = rho_new / rho, blk[KS_RHO] = rho_new;
-        break;
-    }
-    case FOLD_BICG_OMEGA:
-        // t = 0 because s already meets the test (A s^ of a vanished s): the half step is the answer, omega = 0 takes it
-        if (d[1] == 0.0 && sqrt(d[2]) <= blk[KS_TOL]) blk[KS_OMEGA] = 0.0;
-        else if (bad_denominator(d[1])) break_down(blk, SBLAS_KRYLOV_DENOM_TT);
-        else blk[KS_OMEGA] = d[0] / d[1];
-        break;
-    case FOLD_BICG_RES:
-        if (!residual_step(blk, d[0], true)) break;
-        if (bad_denominator(rho)) break_down(blk, SBLAS_KRYLOV_DENOM_RHO);
-        else if (bad_denominator(blk[KS_OMEGA])) break_down(blk, SBLAS_KRYLOV_DENOM_OMEGA);
-        else blk[KS_BETA] = (d[1] / rho) * (blk[KS_ALPHA] / blk[KS_OMEGA]), blk[KS_RHO] = d[1];
-        break;
-    default: break;
-    }
+    krylov_scalar_step(op, nd, flag, d, blk, rtol, atol, max_iter); // krylov_scalar.h: the one text of the step
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------

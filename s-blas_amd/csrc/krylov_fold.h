@@ -31,6 +31,16 @@ template <int NP> __device__ __forceinline__ void group_fold(const double (&acc)
     for (int q = 0; q < NP; ++q) out[q] = (ws[q][0] + ws[q][1]) + (ws[q][2] + ws[q][3]);
 }
 
+// Stage 2 of nd <= KRYLOV_MAX_DOTS dots: lane t adds partial[t], partial[t + 256], ... of each dot in order from +0, then
+// the same butterfly.  Dot q's cells' sums start at part + q * stride.  Every thread returns with d[] set.
+__device__ __forceinline__ void cells_fold(int nd, int64_t cells, const double *part, int64_t stride, double (&d)[KRYLOV_MAX_DOTS])
+{
+    double acc[KRYLOV_MAX_DOTS] = {};
+    for (int64_t c = threadIdx.x; c < cells; c += KRYLOV_LANES)
+        for (int q = 0; q < nd; ++q) acc[q] = acc[q] + part[q * stride + c];
+    group_fold<KRYLOV_MAX_DOTS>(acc, d);
+}
+
 // Lane t of cell c takes elements t, t + 256, ... of the cell in that order; absent elements are skipped.
 template <class F> __device__ __forceinline__ void cell_walk(int64_t n, F f)
 {

@@ -1,0 +1,694 @@
+// krylov_multi.hip -- PCG and BiCGStab for s right-hand sides at once: s independent recurrences that
+// share A and run in lockstep, one SpMM per product instead of s SpMVs.  X, B and the work blocks are n x s row-major.
+// Everything between two SpMMs is one of krylov.hip's three kernels, widened by a column tile:
+//   dot     stage 1 of up to KRYLOV_MAX_DOTS dots of every column in one pass: one workgroup a cell of KRYLOV_CELL rows
+//           and a tile of KRYLOV_MULTI_TILE columns, a lane its row's eight doubles of each operand and one accumulator
+//           per column and dot; the sum of dot k, column j, cell c to part[(k * s + j) * cells + c];
+//   update  the fused updates of krylov.hip with column j's own alpha, beta, omega from scalar block j, also stage 1 of
+//           the dots of what they wrote;
+//   fold    stage 2: one workgroup PER COLUMN folds that column's cells and its lane 0 takes the scalar step on block j
+//           (krylov_scalar.h: the text krylov.hip runs).
+// A column's dot walks its rows exactly as krylov.hip's dot walks a vector (cell_walk's order, the same butterfly), so
+// it has the pinned dot's bits on the strided column.  Nothing waits across workgroups: no flag polling, no cooperative
+// launch, no atomics.  The host passes no scalar of the recurrence.
+//
+// The freeze, per column.  A tile reads its columns' status words once (uniform loads) into a mask.  A tile whose
+// columns are all frozen returns at entry; a mixed tile predicates every load and store by the mask, so a frozen column
+// of any vector is neither read nor written; lane 0 of a frozen column's fold changes nothing.  The SpMM still
+// multiplies the frozen columns of the direction block, into work blocks only.
+//
+// Width of the accesses.  A full tile whose columns all run moves a row's eight doubles as four 16-byte accesses when
+// every base and leading dimension of the launch is a multiple of 16 bytes (decided on the host, a template flag);
+// anything else -- the ragged last tile, a mixed tile, an odd leading dimension, a base offset by one element -- goes
+// double by double.  Same values, same order, same bits.
+//
+// Arithmetic.  Contraction is off at file scope, as in krylov.hip: every product and every sum is rounded on its own.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+#include <string.h>
+#include <initializer_list>
+#include <memory>
+#include <type_traits>
+#include "../../include/sblas_hip.h"
+#include "capi_util.h"
+#include "krylov.h"
+#include "krylov_multi.h"
+#include "precond_rule.h"
+
+#pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
+
+#include "krylov_fold.h"   // wave_fold, group_fold, cells_fold
+#include "krylov_scalar.h" // the fold ops and the scalar step
+
+using namespace sblas;
+
+namespace {
+
+constexpr int T = KRYLOV_MULTI_TILE;
+// internal update ops, after the public SBLAS_KRYLOV_UP_* ones (krylov.hip's)
+enum { UP_COPY = 5, UP_START_PCG = 6, UP_START_BICG = 7 };
+
+struct MUpArgs {
+    int64_t n, cells;
+    int s;
+    double *blk;  // s scalar blocks
+    double *part; // dot k, column j, cell c at part[(k * s + j) * cells + c]
+    double *v[8];
+    int64_t ld[8]; // of v[q]; a dinv vector's is not read
+};
+
+struct MDotArgs {
+    int64_t n, cells;
+    int s;
+    const double *x[KRYLOV_MAX_DOTS], *y[KRYLOV_MAX_DOTS];
+    int64_t ldx[KRYLOV_MAX_DOTS], ldy[KRYLOV_MAX_DOTS];
+    double *part;
+};
+
+// ---- a row's eight columns ---------------------------------------------------------------------------------------------
+// FAST: four 16-byte accesses (the launch's alignment allows it, the tile is full and every column runs).  Otherwise
+// column by column under the mask: a column outside it is not touched and reads as 0.
+template <bool FAST> __device__ __forceinline__ void ld8(const double *p, unsigned mask, double (&x)[T])
+{
+    if constexpr (FAST) {
+        const double2 *q = reinterpret_cast<const double2 *>(p);
+#pragma unroll
+        for (int c = 0; c < T / 2; ++c) {
+            const double2 t = q[c];
+            x[2 * c] = t.x, x[2 * c + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < T; ++c) x[c] = (mask >> c & 1u) ? p[c] : 0.0;
+    }
+}
+
+template <bool FAST> __device__ __forceinline__ void st8(double *p, unsigned mask, const double (&x)[T])
+{
+    if constexpr (FAST) {
+        double2 *q = reinterpret_cast<double2 *>(p);
+#pragma unroll
+        for (int c = 0; c < T / 2; ++c) q[c] = make_double2(x[2 * c], x[2 * c + 1]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < T; ++c)
+            if (mask >> c & 1u) p[c] = x[c];
+    }
+}
+
+// Which cell and which column tile a workgroup takes.  The grid is one-dimensional, cells x tiles workgroups, numbered so
+// that the tiles of one cell are KRYLOV_MULTI_GROUP ids apart and next to each other in time: cells go in groups of
+// KRYLOV_MULTI_GROUP, and inside a group the id runs over the cells first, then over the tiles.  At s > 8 two tiles of
+// a cell read halves of the same memory lines (a row is s * 8 bytes, a tile 64 of them); workgroup ids that differ by
+// the number of L2 partitions are dispatched to the same partition, so the second tile finds the lines the first one
+// fetched.  The numbering cannot reach a bit: a (cell, tile) pair computes the same sums wherever it runs.
+constexpr int KRYLOV_MULTI_GROUP = 8;
+struct TileId {
+    int64_t cell;
+    int tile;
+};
+__device__ __forceinline__ TileId tile_id(int64_t cells, int s)
+{
+    const int64_t per = (int64_t)KRYLOV_MULTI_GROUP * ((s + T - 1) / T), id = blockIdx.x, g = id / per, rem = id - g * per;
+    const int64_t left = cells - KRYLOV_MULTI_GROUP * g, gc = left < KRYLOV_MULTI_GROUP ? left : KRYLOV_MULTI_GROUP; // the last group is short
+    return TileId{KRYLOV_MULTI_GROUP * g + rem % gc, (int)(rem / gc)};
+}
+
+// Lane t of a cell takes rows t, t + 256, ... of the cell in that order (cell_walk's order); absent rows are skipped.
+// Not unrolled eight times as cell_walk is: a row is already eight columns of every operand in registers.
+template <class F> __device__ __forceinline__ void row_walk(int64_t cell, int64_t n, F f)
+{
+    const int64_t first = cell * KRYLOV_CELL;
+#pragma unroll 2
+    for (int k = 0; k < KRYLOV_PER_LANE; ++k) {
+        const int64_t i = first + threadIdx.x + k * KRYLOV_LANES;
+        if (i < n) f(i);
+    }
+}
+
+// the tile's ND * T lane sums through group_fold; lane 0 stores the columns of the mask
+template <int ND> __device__ __forceinline__ void tile_store(const double (&acc)[ND * T], double *part, int s, int64_t cells, int64_t cell, int j0, unsigned mask)
+{
+    double out[ND * T];
+    group_fold<ND * T>(acc, out);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k)
+#pragma unroll
+            for (int c = 0; c < T; ++c)
+                if (mask >> c & 1u) part[((int64_t)k * s + j0 + c) * cells + cell] = out[k * T + c];
+    }
+}
+
+// ---- dot, stage 1 ----------------------------------------------------------------------------------------------------
+// not a part of the freeze: like krylov.hip's dot it reads work blocks (or the caller's operands) and writes partials
+template <int ND, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES) void multi_dot_kernel(const MDotArgs a)
+{
+    const TileId id = tile_id(a.cells, a.s);
+    const int j0 = id.tile * T, w = a.s - j0 < T ? a.s - j0 : T;
+    const unsigned mask = (1u << w) - 1u;
+    double acc[ND * T];
+#pragma unroll
+    for (int q = 0; q < ND * T; ++q) acc[q] = 0.0;
+    auto body = [&](auto fast) {
+        constexpr bool F = decltype(fast)::value;
+        row_walk(id.cell, a.n, [&](int64_t i) {
+#pragma unroll
+            for (int q = 0; q < ND; ++q) {
+                double x[T], y[T];
+                ld8<F>(a.x[q] + i * a.ldx[q] + j0, mask, x);
+                ld8<F>(a.y[q] + i * a.ldy[q] + j0, mask, y);
+#pragma unroll
+                for (int c = 0; c < T; ++c) acc[q * T + c] = acc[q * T + c] + x[c] * y[c];
+            }
+        });
+    };
+    if (WIDE && w == T) body(std::true_type{});
+    else body(std::false_type{});
+    tile_store<ND>(acc, a.part, a.s, a.cells, id.cell, j0, mask);
+}
+
+// ---- the fused updates -----------------------------------------------------------------------------------------------
+// krylov.hip's updates on eight columns of a row, column c with its own scalars.  JAC: dinv[i] is read once per row.
+// Blocks are not __restrict__: without a preconditioner Z is R, and P^, S^ are P, S.
+template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES) void multi_update_kernel(const MUpArgs a)
+{
+    constexpr bool START = OP == UP_START_PCG || OP == UP_START_BICG;
+    const TileId id = tile_id(a.cells, a.s);
+    const int j0 = id.tile * T, w = a.s - j0 < T ? a.s - j0 : T;
+    unsigned mask = 0, zmask = 0; // the columns that run; of a start pass, those with b == 0
+    double al[T], be[T], om[T];
+#pragma unroll
+    for (int c = 0; c < T; ++c) {
+        al[c] = be[c] = om[c] = 0.0;
+        if (c < w) { // block-uniform, read once: the freeze
+            const double *b = a.blk + (size_t)(j0 + c) * KRYLOV_BLOCK_SLOTS;
+            const long long *ib = reinterpret_cast<const long long *>(b);
+            if (START || ib[KS_STATUS] == SBLAS_KRYLOV_RUNNING) mask |= 1u << c;
+            if (START && ib[KS_ZERO_X] != 0) zmask |= 1u << c;
+            if (!START) al[c] = b[KS_ALPHA], be[c] = b[KS_BETA], om[c] = b[KS_OMEGA];
+        }
+    }
+    if (mask == 0) return; // every column of the tile is frozen
+    double *const *v = a.v;
+    const int64_t *ld = a.ld;
+    constexpr int NP = (OP == SBLAS_KRYLOV_UP_PCG_XR || OP == UP_START_PCG) ? (JAC ? 2 : 1) : OP == SBLAS_KRYLOV_UP_BICG_XR ? 2 : OP == UP_START_BICG ? 1 : 0;
+    double acc[(NP ? NP : 1) * T];
+#pragma unroll
+    for (int q = 0; q < (NP ? NP : 1) * T; ++q) acc[q] = 0.0;
+    auto at = [&](int q, int64_t i) { return v[q] + i * ld[q] + j0; };
+    auto body = [&](auto fast) {
+        constexpr bool F = decltype(fast)::value;
+        row_walk(id.cell, a.n, [&](int64_t i) {
+            if constexpr (OP == SBLAS_KRYLOV_UP_PCG_XR) { // x, r, p, q, dinv, z
+                double x[T], p[T], r[T], q[T];
+                ld8<F>(at(0, i), mask, x), ld8<F>(at(2, i), mask, p);
+#pragma unroll
+                for (int c = 0; c < T; ++c) x[c] = x[c] + al[c] * p[c];
+                st8<F>(at(0, i), mask, x);
+                ld8<F>(at(1, i), mask, r), ld8<F>(at(3, i), mask, q);
+#pragma unroll
+                for (int c = 0; c < T; ++c) {
+                    r[c] = r[c] - al[c] * q[c];
+                    acc[c] = acc[c] + r[c] * r[c];
+                }
+                st8<F>(at(1, i), mask, r);
+                if constexpr (JAC) {
+                    const double di = v[4][i];
+                    double z[T];
+#pragma unroll
+                    for (int c = 0; c < T; ++c) {
+                        z[c] = di * r[c];
+                        acc[T + c] = acc[T + c] + r[c] * z[c];
+                    }
+                    st8<F>(at(5, i), mask, z);
+                }
+            } else if constexpr (OP == SBLAS_KRYLOV_UP_PCG_P) { // p, z
+                double p[T], z[T];
+                ld8<F>(at(0, i), mask, p), ld8<F>(at(1, i), mask, z);
+#pragma unroll
+                for (int c = 0; c < T; ++c) p[c] = z[c] + be[c] * p[c];
+                st8<F>(at(0, i), mask, p);
+            } else if constexpr (OP == UP_COPY) { // dst, src
+                double x[T];
+                ld8<F>(at(1, i), mask, x);
+                st8<F>(at(0, i), mask, x);
+            } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_P) { // p, r, v, dinv, p^
+                double p[T], r[T], vv[T];
+                ld8<F>(at(0, i), mask, p), ld8<F>(at(1, i), mask, r), ld8<F>(at(2, i), mask, vv);
+#pragma unroll
+                for (int c = 0; c < T; ++c) p[c] = r[c] + be[c] * (p[c] - om[c] * vv[c]);
+                st8<F>(at(0, i), mask, p);
+                if constexpr (JAC) {
+                    const double di = v[3][i];
+#pragma unroll
+                    for (int c = 0; c < T; ++c) p[c] = di * p[c];
+                    st8<F>(at(4, i), mask, p);
+                }
+            } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_S) { // s, r, v, dinv, s^
+                double sv[T], r[T], vv[T];
+                ld8<F>(at(1, i), mask, r), ld8<F>(at(2, i), mask, vv);
+#pragma unroll
+                for (int c = 0; c < T; ++c) sv[c] = r[c] - al[c] * vv[c];
+                st8<F>(at(0, i), mask, sv);
+                if constexpr (JAC) {
+                    const double di = v[3][i];
+#pragma unroll
+                    for (int c = 0; c < T; ++c) sv[c] = di * sv[c];
+                    st8<F>(at(4, i), mask, sv);
+                }
+            } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_XR) { // x, r, p^, s^, s, t, r^
+                double x[T], ph[T], sh[T];
+                ld8<F>(at(0, i), mask, x), ld8<F>(at(2, i), mask, ph), ld8<F>(at(3, i), mask, sh);
+#pragma unroll
+                for (int c = 0; c < T; ++c) x[c] = (x[c] + al[c] * ph[c]) + om[c] * sh[c];
+                st8<F>(at(0, i), mask, x);
+                double sv[T], t[T], rh[T];
+                ld8<F>(at(4, i), mask, sv), ld8<F>(at(5, i), mask, t), ld8<F>(at(6, i), mask, rh);
+#pragma unroll
+                for (int c = 0; c < T; ++c) {
+                    sv[c] = sv[c] - om[c] * t[c];
+                    acc[c] = acc[c] + sv[c] * sv[c];
+                    acc[T + c] = acc[T + c] + rh[c] * sv[c];
+                }
+                st8<F>(at(1, i), mask, sv);
+            } else if constexpr (OP == UP_START_PCG) { // r, b, q (= A x0), dinv, z, x
+                double b[T], q[T], r[T];
+                ld8<F>(at(1, i), mask, b), ld8<F>(at(2, i), mask, q);
+                double *x = at(5, i);
+#pragma unroll
+                for (int c = 0; c < T; ++c) {
+                    const bool zero = zmask >> c & 1u; // b == 0: x = 0, and b - A x0 is not formed
+                    if (zero) x[c] = 0.0;
+                    r[c] = zero ? 0.0 : b[c] - q[c];
+                    acc[c] = acc[c] + r[c] * r[c];
+                }
+                st8<F>(at(0, i), mask, r);
+                if constexpr (JAC) {
+                    const double di = v[3][i];
+                    double z[T];
+#pragma unroll
+                    for (int c = 0; c < T; ++c) {
+                        z[c] = (zmask >> c & 1u) ? 0.0 : di * r[c];
+                        acc[T + c] = acc[T + c] + r[c] * z[c];
+                    }
+                    st8<F>(at(4, i), mask, z);
+                }
+            } else { // UP_START_BICG: r, b, v (= A x0 on entry, 0 on exit), r^, p, x
+                double b[T], q[T], r[T], zero8[T];
+                ld8<F>(at(1, i), mask, b), ld8<F>(at(2, i), mask, q);
+                double *x = at(5, i);
+#pragma unroll
+                for (int c = 0; c < T; ++c) {
+                    const bool zero = zmask >> c & 1u;
+                    if (zero) x[c] = 0.0;
+                    r[c] = zero ? 0.0 : b[c] - q[c];
+                    zero8[c] = 0.0;
+                    acc[c] = acc[c] + r[c] * r[c];
+                }
+                st8<F>(at(0, i), mask, r), st8<F>(at(3, i), mask, r);
+                st8<F>(at(4, i), mask, zero8), st8<F>(at(2, i), mask, zero8);
+            }
+        });
+    };
+    if (WIDE && mask == (1u << T) - 1u) body(std::true_type{});
+    else body(std::false_type{});
+    if constexpr (NP > 0) tile_store<NP>(acc, a.part, a.s, a.cells, id.cell, j0, mask);
+}
+
+// ---- stage 2, which is also the scalar step: one workgroup a column -------------------------------------------------------
+__global__ __launch_bounds__(KRYLOV_LANES) void multi_fold_kernel(int op, int nd, int flag, int s, int64_t cells, const double *part, double *blk,
+                                                                 double *out, double rtol, double atol, long long max_iter)
+{
+    const int j = (int)blockIdx.x;
+    double d[KRYLOV_MAX_DOTS];
+    cells_fold(nd, cells, part + (int64_t)j * cells, (int64_t)s * cells, d); // krylov.hip's lane walk over column j's cells
+    if (threadIdx.x != 0) return;
+    if (op == FOLD_OUT) {
+        for (int q = 0; q < nd; ++q) out[(int64_t)q * s + j] = d[q];
+        return;
+    }
+    krylov_scalar_step(op, nd, flag, d, blk + (size_t)j * KRYLOV_BLOCK_SLOTS, rtol, atol, max_iter);
+}
+
+// ---- launches ----------------------------------------------------------------------------------------------------------
+inline bool wide16(const void *p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)(ld * 8)) & 15u) == 0; }
+
+inline unsigned tile_grid(int64_t cells, int s) { return (unsigned)(cells * krylov_multi_tiles(s)); } // tile_id() numbers it
+
+template <int ND> inline void launch_dot_nd(hipStream_t st, bool wide, const MDotArgs &a)
+{
+    if (wide) multi_dot_kernel<ND, true><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+    else multi_dot_kernel<ND, false><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+}
+
+inline void launch_dot(hipStream_t st, int nd, const MDotArgs &a)
+{
+    bool wide = true;
+    for (int q = 0; q < nd; ++q) wide = wide && wide16(a.x[q], a.ldx[q]) && wide16(a.y[q], a.ldy[q]);
+    if (nd == 1) launch_dot_nd<1>(st, wide, a);
+    else if (nd == 2) launch_dot_nd<2>(st, wide, a);
+    else launch_dot_nd<3>(st, wide, a);
+}
+
+inline void launch_fold(hipStream_t st, int op, int nd, int flag, int s, int64_t cells, const double *part, double *blk, double *out = nullptr,
+                        double rtol = 0.0, double atol = 0.0, int64_t max_iter = 0)
+{
+    multi_fold_kernel<<<(unsigned)s, KRYLOV_LANES, 0, st>>>(op, nd, flag, s, cells, part, blk, out, rtol, atol, (long long)max_iter);
+}
+
+template <int OP, bool JAC> inline void launch_update_op(hipStream_t st, bool wide, const MUpArgs &a)
+{
+    if (wide) multi_update_kernel<OP, JAC, true><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+    else multi_update_kernel<OP, JAC, false><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+}
+
+// blocks of an op (the single update's counts) and the place of dinv among them with Jacobi, else -1
+const int NEED[8] = {4, 2, 3, 3, 7, 2, 3, 6};
+inline int dinv_place(int op, bool jac)
+{
+    if (!jac) return -1;
+    return op == SBLAS_KRYLOV_UP_PCG_XR ? 4 : op == SBLAS_KRYLOV_UP_BICG_P || op == SBLAS_KRYLOV_UP_BICG_S || op == UP_START_PCG ? 3 : -1;
+}
+inline int blocks_of(int op, bool jac)
+{
+    if (op == UP_START_PCG) return 6; // r, b, q, dinv, z, x: x is the last, with or without Jacobi
+    return NEED[op] + (dinv_place(op, jac) >= 0 ? 2 : 0);
+}
+
+inline void launch_update(hipStream_t st, int op, bool jac, const MUpArgs &a)
+{
+    jac = dinv_place(op, jac) >= 0;
+    const int nv = blocks_of(op, jac), dp = dinv_place(op, jac);
+    bool wide = true;
+    for (int q = 0; q < nv; ++q)
+        if (q != dp && a.v[q]) wide = wide && wide16(a.v[q], a.ld[q]);
+    switch (op) {
+    case SBLAS_KRYLOV_UP_PCG_XR: return jac ? launch_update_op<SBLAS_KRYLOV_UP_PCG_XR, true>(st, wide, a) : launch_update_op<SBLAS_KRYLOV_UP_PCG_XR, false>(st, wide, a);
+    case SBLAS_KRYLOV_UP_PCG_P: return launch_update_op<SBLAS_KRYLOV_UP_PCG_P, false>(st, wide, a);
+    case SBLAS_KRYLOV_UP_BICG_P: return jac ? launch_update_op<SBLAS_KRYLOV_UP_BICG_P, true>(st, wide, a) : launch_update_op<SBLAS_KRYLOV_UP_BICG_P, false>(st, wide, a);
+    case SBLAS_KRYLOV_UP_BICG_S: return jac ? launch_update_op<SBLAS_KRYLOV_UP_BICG_S, true>(st, wide, a) : launch_update_op<SBLAS_KRYLOV_UP_BICG_S, false>(st, wide, a);
+    case SBLAS_KRYLOV_UP_BICG_XR: return launch_update_op<SBLAS_KRYLOV_UP_BICG_XR, false>(st, wide, a);
+    case UP_COPY: return launch_update_op<UP_COPY, false>(st, wide, a);
+    case UP_START_PCG: return jac ? launch_update_op<UP_START_PCG, true>(st, wide, a) : launch_update_op<UP_START_PCG, false>(st, wide, a);
+    default: return launch_update_op<UP_START_BICG, false>(st, wide, a);
+    }
+}
+
+// ---- the plan ----------------------------------------------------------------------------------------------------------
+struct MultiPlan {
+    int dev = -1, method = 0, precond = 0, s = 0;
+    int64_t n = 0, nnz = 0, cells = 0;
+    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
+    void *spmm = nullptr;                               // the plan's own, for width s
+    int n_blocks = 0;
+    size_t block_bytes = 0, partial_bytes = 0, scalar_bytes = 0, ws_bytes = 0, bytes = 0;
+    DeviceBuffer buf; // scalar blocks | partials | the SpMM's workspace | work blocks
+    double *blk = nullptr, *part = nullptr, *vec = nullptr;
+    void *ws = nullptr;
+    // one solve: start() keeps what iterate() needs
+    bool started = false;
+    const double *val = nullptr, *dinv = nullptr;
+    double *x = nullptr;
+    int64_t ldx = 0;
+    bool jacobi() const { return precond == SBLAS_PRECOND_JACOBI; }
+    double *w(int k) const { return vec + (size_t)k * (block_bytes / 8); }
+    ~MultiPlan()
+    {
+        if (spmm) sblas_hip_spmm_plan_destroy(spmm);
+    }
+};
+
+// work blocks of the plan, by slot (krylov.hip's)
+enum { V_R = 0, V_P = 1, V_Q = 2, V_Z = 3 };
+enum { B_R = 0, B_RHAT = 1, B_P = 2, B_V = 3, B_S = 4, B_T = 5, B_PH = 6, B_SH = 7 };
+
+struct Blk {
+    double *p;
+    int64_t ld;
+};
+
+MUpArgs up_args(const MultiPlan *p, std::initializer_list<Blk> v)
+{
+    MUpArgs a{p->n, p->cells, p->s, p->blk, p->part, {}, {}};
+    int k = 0;
+    for (const Blk &q : v) a.v[k] = q.p, a.ld[k] = q.ld, ++k;
+    return a;
+}
+
+void dot(const MultiPlan *p, hipStream_t st, Blk x0, Blk y0, Blk x1 = {nullptr, 0}, Blk y1 = {nullptr, 0}, Blk x2 = {nullptr, 0}, Blk y2 = {nullptr, 0})
+{
+    MDotArgs a{p->n, p->cells, p->s, {x0.p, x1.p, x2.p}, {y0.p, y1.p, y2.p}, {x0.ld, x1.ld, x2.ld}, {y0.ld, y1.ld, y2.ld}, p->part};
+    launch_dot(st, x2.p ? 3 : x1.p ? 2 : 1, a);
+}
+
+void fold(const MultiPlan *p, hipStream_t st, int op, int nd, int flag, double rtol = 0.0, double atol = 0.0, int64_t max_iter = 0)
+{
+    launch_fold(st, op, nd, flag, p->s, p->cells, p->part, p->blk, nullptr, rtol, atol, max_iter);
+}
+
+// out = A in: ONE planned SpMM, both blocks row-major, alpha 1 and beta 0
+int product(const MultiPlan *p, hipStream_t st, const double *in, int64_t ldin, double *out)
+{
+    return sblas_hip_spmm_csr_ordered_f64_i32_planned(p->spmm, p->dev, st, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, in, ldin,
+                                                      SBLAS_ROW_MAJOR, p->s, 1.0, 0.0, out, p->s, SBLAS_ROW_MAJOR, p->ws, p->ws_bytes);
+}
+
+int pcg_iteration(const MultiPlan *p, hipStream_t st)
+{
+    const bool jac = p->jacobi();
+    const int64_t s = p->s;
+    const Blk x{p->x, p->ldx}, r{p->w(V_R), s}, pp{p->w(V_P), s}, q{p->w(V_Q), s}, z{jac ? p->w(V_Z) : p->w(V_R), s};
+    const Blk dinv{const_cast<double *>(p->dinv), 0};
+    const int rc = product(p, st, pp.p, s, q.p);
+    if (rc != SBLAS_OK) return rc;
+    dot(p, st, pp, q);
+    fold(p, st, FOLD_PCG_ALPHA, 1, 0);
+    launch_update(st, SBLAS_KRYLOV_UP_PCG_XR, jac, up_args(p, {x, r, pp, q, dinv, z}));
+    fold(p, st, FOLD_PCG_RES, jac ? 2 : 1, 1);
+    launch_update(st, SBLAS_KRYLOV_UP_PCG_P, false, up_args(p, {pp, z}));
+    return SBLAS_OK;
+}
+
+int bicgstab_iteration(const MultiPlan *p, hipStream_t st)
+{
+    const bool jac = p->jacobi();
+    const int64_t s = p->s;
+    const Blk x{p->x, p->ldx}, r{p->w(B_R), s}, rh{p->w(B_RHAT), s}, pp{p->w(B_P), s}, v{p->w(B_V), s}, sv{p->w(B_S), s}, t{p->w(B_T), s};
+    const Blk ph = jac ? Blk{p->w(B_PH), s} : pp, sh = jac ? Blk{p->w(B_SH), s} : sv, dinv{const_cast<double *>(p->dinv), 0};
+    int rc;
+    launch_update(st, SBLAS_KRYLOV_UP_BICG_P, jac, up_args(p, {pp, r, v, dinv, ph}));
+    if ((rc = product(p, st, ph.p, s, v.p)) != SBLAS_OK) return rc;
+    dot(p, st, rh, v);
+    fold(p, st, FOLD_BICG_ALPHA, 1, 0);
+    launch_update(st, SBLAS_KRYLOV_UP_BICG_S, jac, up_args(p, {sv, r, v, dinv, sh}));
+    if ((rc = product(p, st, sh.p, s, t.p)) != SBLAS_OK) return rc;
+    dot(p, st, t, sv, t, t, sv, sv);
+    fold(p, st, FOLD_BICG_OMEGA, 3, 0);
+    launch_update(st, SBLAS_KRYLOV_UP_BICG_XR, false, up_args(p, {x, r, ph, sh, sv, t, rh}));
+    fold(p, st, FOLD_BICG_RES, 2, 0);
+    return SBLAS_OK;
+}
+
+// the bytes an n x s block at leading dimension ld spans
+inline size_t span_bytes(int64_t n, int s, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)s) * 8 : 0; }
+
+} // namespace
+
+extern "C" {
+
+size_t sblas_hip_krylov_multi_dot_workspace(int64_t n, int nrhs, int ndots)
+{
+    if (n < 0 || !krylov_multi_width_ok(nrhs) || ndots < 1 || ndots > KRYLOV_MAX_DOTS) return 0;
+    const size_t sums = (size_t)ndots * (size_t)nrhs * (size_t)krylov_cells(n);
+    return (sums ? sums : 1) * sizeof(double); // never 0: a workspace is always asked for
+}
+
+int sblas_hip_krylov_multi_dot_f64(int dev, void *stream, int64_t n, int nrhs, int ndots, const double *const *x, const int64_t *ldx,
+                                   const double *const *y, const int64_t *ldy, double *out, void *workspace, size_t workspace_bytes)
+{
+    if (n < 0 || n > INT_MAX || !krylov_multi_width_ok(nrhs) || ndots < 1 || ndots > KRYLOV_MAX_DOTS) return SBLAS_E_INVALID;
+    if (!x || !y || !ldx || !ldy || !out) return SBLAS_E_INVALID;
+    for (int q = 0; q < ndots; ++q) {
+        if (n > 0 && (!x[q] || !y[q])) return SBLAS_E_INVALID;
+        if (ldx[q] < nrhs || ldy[q] < nrhs) return SBLAS_E_INVALID;
+        if (n > 0 && ((reinterpret_cast<uintptr_t>(x[q]) | reinterpret_cast<uintptr_t>(y[q])) & 7u)) return SBLAS_E_INVALID;
+    }
+    if (!workspace || workspace_bytes < sblas_hip_krylov_multi_dot_workspace(n, nrhs, ndots)) return SBLAS_E_WORKSPACE;
+    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(out)) & 7u) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    MDotArgs a{n, krylov_cells(n), nrhs, {}, {}, {}, {}, static_cast<double *>(workspace)};
+    for (int q = 0; q < ndots; ++q) a.x[q] = x[q], a.y[q] = y[q], a.ldx[q] = ldx[q], a.ldy[q] = ldy[q];
+    if (a.cells > 0) launch_dot(st, ndots, a);
+    launch_fold(st, FOLD_OUT, ndots, 0, nrhs, a.cells, a.part, nullptr, out);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_krylov_multi_update_f64(int dev, void *stream, int op, int jacobi, int64_t n, int nrhs, const double *scalars,
+                                      double *const *v, const int64_t *ld, int nv, double *partial)
+{
+    static const int parts[5] = {1, 0, 0, 0, 2};
+    if (op < SBLAS_KRYLOV_UP_PCG_XR || op > SBLAS_KRYLOV_UP_BICG_XR || n < 0 || n > INT_MAX || !krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    if (!scalars || !v || !ld || (reinterpret_cast<uintptr_t>(scalars) & 7u)) return SBLAS_E_INVALID;
+    const bool jac = dinv_place(op, jacobi != 0) >= 0;
+    const int want = blocks_of(op, jac), dp = dinv_place(op, jac);
+    if (nv < want || nv > 8) return SBLAS_E_INVALID;
+    for (int q = 0; q < want; ++q) {
+        if (q != dp && ld[q] < nrhs) return SBLAS_E_INVALID;
+        if (n > 0 && (!v[q] || (reinterpret_cast<uintptr_t>(v[q]) & 7u))) return SBLAS_E_INVALID;
+    }
+    if (n == 0) return SBLAS_OK;
+    if (parts[op] && (!partial || (reinterpret_cast<uintptr_t>(partial) & 7u))) return SBLAS_E_INVALID;
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    MUpArgs a{n, krylov_cells(n), nrhs, const_cast<double *>(scalars), partial, {}, {}};
+    for (int q = 0; q < want; ++q) a.v[q] = v[q], a.ld[q] = q == dp ? 0 : ld[q];
+    launch_update((hipStream_t)stream, op, jac, a);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_krylov_multi_plan_create(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr,
+                                       const int32_t *colidx, int nrhs, int precond, void **plan_out)
+{
+    if (!plan_out) return SBLAS_E_INVALID;
+    *plan_out = nullptr;
+    if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
+    if (!precond_multi(precond)) return SBLAS_E_INVALID; // precond_rule.h: ILU(0), AMG and Chebyshev have no multi-column apply
+    if (!krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
+    if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
+    const int device = resolve_device(dev);
+    std::unique_ptr<MultiPlan> p(new MultiPlan);
+    p->dev = device, p->method = method, p->precond = precond, p->s = nrhs, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
+    p->rowptr = rowptr, p->colidx = colidx;
+    p->n_blocks = method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS;
+    if (n == 0) {
+        *plan_out = p.release();
+        return SBLAS_OK;
+    }
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    int rc = sblas_hip_spmm_plan_create(device, stream, n, n, nnz, rowptr, colidx, nrhs, &p->spmm);
+    if (rc != SBLAS_OK) return rc;
+    p->scalar_bytes = pad256((size_t)nrhs * KRYLOV_BLOCK_SLOTS * 8);
+    p->partial_bytes = pad256((size_t)KRYLOV_MAX_DOTS * (size_t)nrhs * (size_t)p->cells * 8);
+    p->ws_bytes = pad256(sblas_hip_spmm_csr_f64_i32_workspace(n, n, nnz, nrhs));
+    p->block_bytes = pad256((size_t)n * (size_t)nrhs * 8);
+    p->bytes = p->scalar_bytes + p->partial_bytes + p->ws_bytes + (size_t)p->n_blocks * p->block_bytes;
+    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) return SBLAS_E_HIP;
+    p->blk = p->buf.at<double>(), p->part = p->buf.at<double>(p->scalar_bytes);
+    p->ws = p->ws_bytes ? p->buf.at<double>(p->scalar_bytes + p->partial_bytes) : nullptr;
+    p->vec = p->buf.at<double>(p->scalar_bytes + p->partial_bytes + p->ws_bytes);
+    // the work blocks start from zero: a product with beta 0 into a block that never held a value
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(p->blk, 0, p->bytes, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
+    *plan_out = p.release();
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_multi_plan_info(const void *plan, int64_t out[12])
+{
+    if (!plan || !out) return SBLAS_E_INVALID;
+    const MultiPlan *p = static_cast<const MultiPlan *>(plan);
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->s, out[5] = p->n_blocks;
+    out[6] = (int64_t)p->block_bytes, out[7] = (int64_t)p->partial_bytes, out[8] = (int64_t)p->scalar_bytes, out[9] = (int64_t)p->ws_bytes;
+    out[10] = (int64_t)p->bytes, out[11] = sblas_krylov_multi_launches(p->method, p->precond, 0);
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_multi_plan_destroy(void *plan)
+{
+    delete static_cast<MultiPlan *>(plan);
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_multi_start(void *plan, void *stream, const double *val, const double *dinv, const double *B, int64_t ldb, double *X,
+                                 int64_t ldx, double rtol, double atol, int64_t max_iter)
+{
+    MultiPlan *p = static_cast<MultiPlan *>(plan);
+    if (!p) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || max_iter < 0) return SBLAS_E_INVALID; // a NaN tolerance is refused too
+    if (ldb < p->s || ldx < p->s) return SBLAS_E_INVALID;
+    p->started = false;
+    if (p->n == 0) {
+        p->started = true;
+        return SBLAS_OK;
+    }
+    const bool jac = p->jacobi();
+    if (!B || !X || (p->nnz > 0 && !val) || (jac && !dinv)) return SBLAS_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
+    if (b0 < x0 + span_bytes(p->n, p->s, ldx) && x0 < b0 + span_bytes(p->n, p->s, ldb)) return SBLAS_E_INVALID; // X overlaps B
+    p->val = val, p->dinv = jac ? dinv : nullptr, p->x = X, p->ldx = ldx;
+    hipStream_t st = (hipStream_t)stream;
+    const bool pcg = p->method == SBLAS_KRYLOV_PCG;
+    const int64_t s = p->s;
+    const Blk b{const_cast<double *>(B), ldb}, x{X, ldx}, di{const_cast<double *>(p->dinv), 0};
+    int rc;
+    // The work blocks start every solve from zero.  A column that is frozen from the start is never written, yet the SpMM
+    // multiplies it -- and a non-finite value a previous solve left there would select other SpMM kernels for the whole
+    // product.  So the bits of a solve are a function of its own operands alone.
+    if (hipMemsetAsync(p->vec, 0, (size_t)p->n_blocks * p->block_bytes, st) != hipSuccess) return SBLAS_E_HIP;
+    dot(p, st, b, b);
+    fold(p, st, FOLD_START_B, 1, !pcg, rtol, atol, max_iter);
+    if (pcg) {
+        const Blk r{p->w(V_R), s}, q{p->w(V_Q), s}, z{jac ? p->w(V_Z) : p->w(V_R), s}, pp{p->w(V_P), s};
+        if ((rc = product(p, st, X, ldx, q.p)) != SBLAS_OK) return rc;
+        launch_update(st, UP_START_PCG, jac, up_args(p, {r, b, q, di, z, x}));
+        fold(p, st, FOLD_START_R, jac ? 2 : 1, 0);
+        launch_update(st, UP_COPY, false, up_args(p, {pp, z}));
+    } else {
+        const Blk r{p->w(B_R), s}, v{p->w(B_V), s}, rh{p->w(B_RHAT), s}, pp{p->w(B_P), s};
+        if ((rc = product(p, st, X, ldx, v.p)) != SBLAS_OK) return rc;
+        launch_update(st, UP_START_BICG, false, up_args(p, {r, b, v, rh, pp, x}));
+        fold(p, st, FOLD_START_R, 1, 0);
+    }
+    if (hipGetLastError() != hipSuccess) return SBLAS_E_HIP;
+    p->started = true;
+    return SBLAS_OK;
+}
+
+int sblas_hip_krylov_multi_iterate(void *plan, void *stream, int64_t k)
+{
+    const MultiPlan *p = static_cast<const MultiPlan *>(plan);
+    if (!p || k < 0 || !p->started) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (p->n == 0) return SBLAS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t it = 0; it < k; ++it) {
+        const int rc = p->method == SBLAS_KRYLOV_PCG ? pcg_iteration(p, st) : bicgstab_iteration(p, st);
+        if (rc != SBLAS_OK) return rc;
+    }
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_krylov_multi_status(const void *plan, void *stream, double *out)
+{
+    const MultiPlan *p = static_cast<const MultiPlan *>(plan);
+    if (!p || !out || !p->started) return SBLAS_E_INVALID;
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    for (int q = 0; q < 8 * p->s; ++q) out[q] = 0.0;
+    if (p->n == 0) {
+        for (int j = 0; j < p->s; ++j) out[8 * j] = SBLAS_KRYLOV_CONVERGED;
+        return SBLAS_OK;
+    }
+    double h[SBLAS_KRYLOV_MULTI_MAX_RHS * KRYLOV_BLOCK_SLOTS];
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)p->s * KRYLOV_BLOCK_SLOTS * 8;
+    if (hipMemcpyAsync(h, p->blk, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
+    for (int j = 0; j < p->s; ++j) {
+        const double *hj = h + (size_t)j * KRYLOV_BLOCK_SLOTS;
+        long long ih[KRYLOV_BLOCK_SLOTS];
+        memcpy(ih, hj, sizeof ih);
+        double *o = out + 8 * j;
+        o[0] = (double)ih[KS_STATUS], o[1] = (double)ih[KS_ITER], o[2] = hj[KS_RNORM], o[3] = hj[KS_BNORM];
+        o[4] = hj[KS_ALPHA], o[5] = hj[KS_BETA], o[6] = hj[KS_OMEGA], o[7] = (double)ih[KS_WHICH];
+    }
+    return SBLAS_OK;
+}
+
+} // extern "C"

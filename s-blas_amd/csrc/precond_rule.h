@@ -16,6 +16,9 @@ inline bool precond_known(int kind) { return kind == SBLAS_PRECOND_NONE || kind 
 inline bool precond_takes_values(int kind) { return kind == SBLAS_PRECOND_JACOBI || kind == SBLAS_PRECOND_ILU0; }
 // may run with out == in: the two solves go through a temporary; a cycle or a polynomial reads in while it writes out
 inline bool precond_in_place(int kind) { return kind == SBLAS_PRECOND_ILU0; }
+// serves several right-hand sides at once (krylov_multi.hip): the kinds that ride in the solver's own kernels.  An applied
+// kind has no multi-column apply yet.
+inline bool precond_multi(int kind) { return precond_known(kind) && !precond_applied(kind); }
 // holds two plans, lower and upper; every other applied kind holds one handle in lower's place and no upper
 inline bool precond_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 

@@ -86,6 +86,14 @@ EXPORTS_CHEBY = [
     "sblas_hip_cheby_plan_destroy",
     "sblas_hip_amg_plan_setup_ex", "sblas_hip_amg_plan_eig", "sblas_amg_launches_cheb", "sblas_amg_cycle_cheb_ref", "sblas_amg_cycle_cheb_sa_ref",
 ]
+# what include/sblas_hip_krylov_multi.h declares (PCG and BiCGStab for several right-hand sides on one SpMM per product)
+EXPORTS_KRYLOV_MULTI = [
+    "sblas_krylov_multi_limits", "sblas_krylov_multi_precond_ok", "sblas_krylov_multi_launches", "sblas_krylov_multi_grid",
+    "sblas_krylov_scalar_step_ref",
+    "sblas_hip_krylov_multi_dot_workspace", "sblas_hip_krylov_multi_dot_f64", "sblas_hip_krylov_multi_update_f64",
+    "sblas_hip_krylov_multi_plan_create", "sblas_hip_krylov_multi_plan_info", "sblas_hip_krylov_multi_plan_destroy",
+    "sblas_hip_krylov_multi_start", "sblas_hip_krylov_multi_iterate", "sblas_hip_krylov_multi_status",
+]
 
 
 class SblasError(RuntimeError):
@@ -498,6 +506,35 @@ def lib():
     L.sblas_amg_cycle_cheb_ref.argtypes = [C.c_int, C.POINTER(i64)] + [C.POINTER(vp)] * 8 + [C.c_int, C.c_int, C.c_int, f64, vp, vp]
     L.sblas_amg_cycle_cheb_sa_ref.restype = C.c_int
     L.sblas_amg_cycle_cheb_sa_ref.argtypes = [C.c_int, C.POINTER(i64)] + [C.POINTER(vp)] * 11 + [C.c_int, C.c_int, C.c_int, f64, vp, vp]
+    L.sblas_krylov_multi_limits.restype = C.c_int
+    L.sblas_krylov_multi_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_krylov_multi_precond_ok.restype = C.c_int
+    L.sblas_krylov_multi_precond_ok.argtypes = [C.c_int]
+    L.sblas_krylov_multi_launches.restype = i64
+    L.sblas_krylov_multi_launches.argtypes = [C.c_int, C.c_int, i64]
+    L.sblas_krylov_multi_grid.restype = C.c_int
+    L.sblas_krylov_multi_grid.argtypes = [i64, C.c_int, C.POINTER(i64)]
+    L.sblas_krylov_scalar_step_ref.restype = C.c_int
+    L.sblas_krylov_scalar_step_ref.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, f64, f64, i64]
+    L.sblas_hip_krylov_multi_dot_workspace.restype = sz
+    L.sblas_hip_krylov_multi_dot_workspace.argtypes = [i64, C.c_int, C.c_int]
+    L.sblas_hip_krylov_multi_dot_f64.restype = C.c_int
+    L.sblas_hip_krylov_multi_dot_f64.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64),
+                                                 vp, vp, sz]
+    L.sblas_hip_krylov_multi_update_f64.restype = C.c_int
+    L.sblas_hip_krylov_multi_update_f64.argtypes = [C.c_int, vp, C.c_int, C.c_int, i64, C.c_int, vp, C.POINTER(vp), C.POINTER(i64), C.c_int, vp]
+    L.sblas_hip_krylov_multi_plan_create.restype = C.c_int
+    L.sblas_hip_krylov_multi_plan_create.argtypes = [C.c_int, vp, C.c_int, i64, i64, vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.sblas_hip_krylov_multi_plan_info.restype = C.c_int
+    L.sblas_hip_krylov_multi_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_krylov_multi_plan_destroy.restype = C.c_int
+    L.sblas_hip_krylov_multi_plan_destroy.argtypes = [vp]
+    L.sblas_hip_krylov_multi_start.restype = C.c_int
+    L.sblas_hip_krylov_multi_start.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64, f64, f64, i64]
+    L.sblas_hip_krylov_multi_iterate.restype = C.c_int
+    L.sblas_hip_krylov_multi_iterate.argtypes = [vp, vp, i64]
+    L.sblas_hip_krylov_multi_status.restype = C.c_int
+    L.sblas_hip_krylov_multi_status.argtypes = [vp, vp, C.POINTER(f64)]
     _lib = L
     return L
 
@@ -3308,6 +3345,312 @@ def pcg(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_ev
 def bicgstab(A, b, precond=None, x=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
     """x with A x = b by preconditioned BiCGStab, one shot, as pcg(); A need not be symmetric."""
     return _krylov_one_shot("bicgstab", A, b, precond, x, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
+
+
+# ------------------------------------------------------------------------------------------
+# PCG and BiCGStab for several right-hand sides on one SpMM per product (sblas_hip_krylov_multi_*)
+# ------------------------------------------------------------------------------------------
+def krylov_multi_limits():
+    """The multi-right-hand-side solvers' limits (sblas_krylov_multi_limits): dict(max_rhs, tile, cell, width, pcg_blocks,
+    bicgstab_blocks, max_dots, block_slots)."""
+    out = (C.c_int64 * 8)()
+    check(lib().sblas_krylov_multi_limits(out), "sblas_krylov_multi_limits")
+    return dict(max_rhs=int(out[0]), tile=int(out[1]), cell=int(out[2]), width=int(out[3]), pcg_blocks=int(out[4]),
+                bicgstab_blocks=int(out[5]), max_dots=int(out[6]), block_slots=int(out[7]))
+
+
+def _multi_precond(precond):
+    """precond of a multi-right-hand-side plan -> its code; the kinds without a multi-column apply are refused by name"""
+    kind = _precond_seat(precond)[0] if not isinstance(precond, str) or precond == "jacobi" else _PRECOND_CODE.get(precond, -1)
+    if kind < 0:
+        raise SblasError("precond must be None or 'jacobi', not %r" % (precond,))
+    if lib().sblas_krylov_multi_precond_ok(kind) != 0:
+        raise SblasError("the %s preconditioner has no multi-column apply: several right-hand sides take None or 'jacobi'"
+                         % _PRECOND_NAME[kind])
+    return kind
+
+
+def krylov_multi_launches(method="pcg", precond=None, spmm_launches=0):
+    """Launches of one lockstep iteration (sblas_krylov_multi_launches): the solver's own kernels and spmm_launches for
+    each product (PCG one, BiCGStab two)."""
+    if method not in _KRYLOV_METHOD:
+        raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
+    n = int(lib().sblas_krylov_multi_launches(_KRYLOV_METHOD[method], _multi_precond(precond), int(spmm_launches)))
+    if n < 0:
+        raise SblasError("sblas_krylov_multi_launches refused its arguments")
+    return n
+
+
+def krylov_multi_grid(n, nrhs):
+    """Workgroups of one multi-column pass (sblas_krylov_multi_grid): dict(cells, tiles, grid, last_tile)."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_krylov_multi_grid(int(n), int(nrhs), out), "sblas_krylov_multi_grid")
+    return dict(cells=int(out[0]), tiles=int(out[1]), grid=int(out[2]), last_tile=int(out[3]))
+
+
+KRYLOV_STEPS = {"start_b": 1, "start_r": 2, "rho0": 3, "pcg_alpha": 4, "pcg_res": 5, "pcg_beta": 6, "bicg_alpha": 7, "bicg_omega": 8,
+                "bicg_res": 9}                                              # SBLAS_KRYLOV_STEP_*
+
+
+def krylov_scalar_step_ref(op, d, block, flag=0, rtol=0.0, atol=0.0, max_iter=0):
+    """The solvers' scalar step on a host block (sblas_krylov_scalar_step_ref): the text the device folds run.  block: 16
+    float64 slots (the status, the count, max_iter, which and zero_x slots hold int64 bits), updated in place."""
+    if op not in KRYLOV_STEPS:
+        raise SblasError("op must be one of %s, not %r" % (sorted(KRYLOV_STEPS), op))
+    d = np.ascontiguousarray(d, np.float64)
+    if not isinstance(block, np.ndarray) or block.dtype != np.float64 or block.shape != (16,) or not block.flags.c_contiguous:
+        raise SblasError("block must be a contiguous float64 array of 16 slots")
+    check(lib().sblas_krylov_scalar_step_ref(KRYLOV_STEPS[op], len(d), int(flag), d.ctypes.data, block.ctypes.data, float(rtol), float(atol),
+                                             int(max_iter)), "sblas_krylov_scalar_step_ref")
+    return block
+
+
+def _krylov_block(name, t, n, s, device=None):
+    """an n x s row-major block: a 2-D float64 GPU tensor with unit stride along a row and a row stride >= s -> its ld"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+    if t.dtype != torch.float64:
+        raise SblasError("%s must be float64, got %s" % (name, t.dtype))
+    if t.dim() != 2 or tuple(t.shape) != (n, s):
+        raise SblasError("%s must be a (%d, %d) tensor, got shape %s" % (name, n, s, tuple(t.shape)))
+    if device is not None and t.device != device:
+        raise SblasError("%s is on %s, the plan on %s" % (name, t.device, device))
+    ld = t.stride(0) if n > 1 else max(t.stride(0), s)
+    if (s > 1 and t.stride(1) != 1) or ld < s:
+        raise SblasError("%s must be row-major with a leading dimension of at least %d, got strides %s" % (name, s, tuple(t.stride())))
+    return int(ld)
+
+
+def _multi_width(s):
+    if not 1 <= int(s) <= krylov_multi_limits()["max_rhs"]:
+        raise SblasError("between 1 and %d right-hand sides, not %d" % (krylov_multi_limits()["max_rhs"], s))
+    return int(s)
+
+
+def _blocks_overlap(a, lda, b, ldb, n, s):
+    span = lambda ld: ((n - 1) * ld + s) * 8 if n else 0
+    return a.data_ptr() < b.data_ptr() + span(ldb) and b.data_ptr() < a.data_ptr() + span(lda)
+
+
+def krylov_multi_dots(pairs, out=None, workspace=None, stream=None):
+    """The pinned dot of every column of up to three pairs of (n, s) row-major blocks in ONE pass over memory
+    (sblas_hip_krylov_multi_dot_f64): a (len(pairs), s) device tensor, entry [k, j] with exactly the bits krylov_dot
+    gives on column j of pair k.  A block may be a column slice of a wider tensor.  No synchronisation; with out and
+    workspace (float64, at least len(pairs) * s * ceil(n / cell) entries) given, nothing is allocated."""
+    import torch
+    k = len(pairs)
+    if not 1 <= k <= 3:
+        raise SblasError("one to three pairs, not %d" % k)
+    first = pairs[0][0]
+    if not isinstance(first, torch.Tensor) or first.dim() != 2:
+        raise SblasError("x[0] must be a 2-D GPU tensor")
+    n, s = int(first.shape[0]), _multi_width(first.shape[1])
+    device = first.device
+    lds = [(_krylov_block("x[%d]" % q, x, n, s, device), _krylov_block("y[%d]" % q, y, n, s, device)) for q, (x, y) in enumerate(pairs)]
+    if out is None:
+        out = torch.empty((k, s), dtype=torch.float64, device=device)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != k * s:
+        raise SblasError("out must be a contiguous float64 GPU tensor of %d entries" % (k * s))
+    need = int(lib().sblas_hip_krylov_multi_dot_workspace(n, s, k))
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous():
+        raise SblasError("workspace must be a contiguous float64 GPU tensor")
+    xs = (C.c_void_p * k)(*[x.data_ptr() if n else None for x, _ in pairs])
+    ys = (C.c_void_p * k)(*[y.data_ptr() if n else None for _, y in pairs])
+    ldx, ldy = (C.c_int64 * k)(*[a for a, _ in lds]), (C.c_int64 * k)(*[b for _, b in lds])
+    with torch.cuda.device(device):
+        check(lib().sblas_hip_krylov_multi_dot_f64(-1, _stream(stream), n, s, k, xs, ldx, ys, ldy, out.data_ptr(), workspace.data_ptr(),
+                                                   workspace.numel() * 8), "sblas_hip_krylov_multi_dot_f64")
+    return out
+
+
+_KRYLOV_MULTI_DINV = {"pcg_xr": 4, "bicg_p": 3, "bicg_s": 3}                # the place of dinv among an update's operands
+
+
+def krylov_multi_update(op, scalars, blocks, partial=None, jacobi=False, stream=None):
+    """One fused multi-column update on its own (sblas_hip_krylov_multi_update_f64).  op: a key of KRYLOV_UPDATES;
+    scalars: an (s, 16) device tensor of eight-byte slots, row j column j's block ([0] status as int64 -- anything but 0
+    and column j is neither read nor written -- [4] alpha, [5] beta, [6] omega); blocks: the op's operands in the
+    header's order, (n, s) row-major blocks, with jacobi the dinv vector of n entries at its place; partial: float64, at
+    least 2 * s * ceil(n / cell) entries, for the ops that are also a dot's first stage."""
+    import torch
+    if op not in KRYLOV_UPDATES:
+        raise SblasError("op must be one of %s, not %r" % (sorted(KRYLOV_UPDATES), op))
+    first = blocks[0] if len(blocks) else None
+    if not isinstance(first, torch.Tensor) or first.dim() != 2:
+        raise SblasError("blocks[0] must be a 2-D GPU tensor")
+    n, s = int(first.shape[0]), _multi_width(first.shape[1])
+    device = first.device
+    dp = _KRYLOV_MULTI_DINV.get(op, -1) if jacobi else -1
+    lds = []
+    for q, t in enumerate(blocks):
+        if q == dp:
+            _krylov_vector("dinv", t, n, device)
+            lds.append(0)
+        else:
+            lds.append(_krylov_block("blocks[%d]" % q, t, n, s, device))
+    if not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or scalars.dtype != torch.float64 or not scalars.is_contiguous() \
+            or scalars.numel() != 16 * s or scalars.device != device:
+        raise SblasError("scalars must be a contiguous float64 GPU tensor of %d x 16 slots" % s)
+    if partial is not None:
+        _krylov_vector("partial", partial, partial.numel() if isinstance(partial, torch.Tensor) else -1, device)
+        if partial.numel() < 2 * s * -(-n // krylov_limits()["cell"]):
+            raise SblasError("partial is too short")
+    v = (C.c_void_p * len(blocks))(*[t.data_ptr() if n else None for t in blocks])
+    ld = (C.c_int64 * len(blocks))(*lds)
+    with torch.cuda.device(device):
+        check(lib().sblas_hip_krylov_multi_update_f64(-1, _stream(stream), KRYLOV_UPDATES[op], 1 if jacobi else 0, n, s, scalars.data_ptr(), v,
+                                                      ld, len(blocks), partial.data_ptr() if partial is not None and partial.numel() else None),
+              "sblas_hip_krylov_multi_update_f64")
+
+
+class KrylovMultiPlan:
+    """PCG or BiCGStab for A X = B with nrhs right-hand sides at once on the n x n CSR structure (rowptr, colidx), int32
+    indices (sblas_hip_krylov_multi_plan_create): nrhs independent recurrences that share A and run in lockstep, one SpMM
+    per product instead of nrhs SpMVs.  method: "pcg" (A symmetric positive definite) or "bicgstab"; precond: None or
+    "jacobi" (start / solve take dinv, one inverse diagonal for all columns) -- ILU(0), AMG and Chebyshev have no
+    multi-column apply and are refused.  B and X are (n, nrhs) float64 GPU tensors, row-major: contiguous, or a column
+    slice of a wider tensor.  The plan owns an SpMM plan for this width, its workspace, the work blocks, the partial sums
+    and one scalar block a column, and keeps the structure tensors alive.
+
+    start() forms every r_j = b_j - A x_j and first direction; iterate(k) enqueues k lockstep iterations without
+    allocating or synchronising (graph-capturable); status() is the one call that synchronises.  Every column has its own
+    scalars and stopping test: once column j's test is met (or it breaks down) nothing reads or writes column j again,
+    while the others go on, so every column's x, count and |r| are those of its own stopping iteration, whatever
+    check_every is.  A solve equals the lockstep loop composed of the SpMM, the pinned dot per column and numpy updates
+    bit for bit; it is NOT promised to equal a KrylovPlan solve of one column, or a batch of another width."""
+
+    def __init__(self, n, rowptr, colidx, nrhs, method="pcg", precond=None, stream=None):
+        import torch
+        self.handle = None
+        if method not in _KRYLOV_METHOD:
+            raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
+        self.method, self.nrhs = method, _multi_width(nrhs)
+        self.precond, self.precond_kind = precond, _multi_precond(precond)
+        self.n, self.nnz = n, _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        self._keep = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_krylov_multi_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                          colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind, C.byref(h))
+        check(rc, "sblas_hip_krylov_multi_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_krylov_multi_plan_info(self.handle, out), "sblas_hip_krylov_multi_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
+                    precond=_PRECOND_NAME[out[3]], nrhs=int(out[4]), blocks=int(out[5]), block_bytes=int(out[6]), partial_bytes=int(out[7]),
+                    scalar_bytes=int(out[8]), workspace_bytes=int(out[9]), bytes=int(out[10]), launches=int(out[11]))
+
+    def start(self, val, B, X, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
+        """Begins a solve: X on entry holds the initial guesses and is updated in place by iterate().  dinv: the inverse
+        diagonal (precond "jacobi").  Every refusal comes before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        ldb = _krylov_block("B", B, self.n, self.nrhs, self.device)
+        ldx = _krylov_block("X", X, self.n, self.nrhs, self.device)
+        pre = None
+        if self.precond_kind == PRECOND_JACOBI:
+            if dinv is None:
+                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
+            _krylov_vector("dinv", dinv, self.n, self.device)
+            pre = dinv
+        if self.n and _blocks_overlap(X, ldx, B, ldb, self.n, self.nrhs):
+            raise SblasError("X must not overlap B")
+        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
+            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_krylov_multi_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                                    pre.data_ptr() if pre is not None and pre.numel() else None,
+                                                    B.data_ptr() if self.n else None, ldb, X.data_ptr() if self.n else None, ldx,
+                                                    float(rtol), float(atol), int(max_iter))
+        check(rc, "sblas_hip_krylov_multi_start")
+        self._keep = (val, B, X, pre)
+
+    def iterate(self, k, stream=None):
+        """Enqueues k lockstep iterations: allocates nothing, never synchronises, graph-capturable as a chain."""
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_krylov_multi_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_krylov_multi_iterate")
+
+    def status(self, stream=None):
+        """Copies the scalar blocks back and synchronises the stream -> dict of per-column numpy arrays (code, iterations,
+        rnorm, bnorm, alpha, beta, omega, which), lists status and breakdown (the names, as KrylovPlan.status gives them)
+        and running, the count of columns still running."""
+        import torch
+        out = (C.c_double * (8 * self.nrhs))()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_krylov_multi_status(self.handle, _stream(stream), out), "sblas_hip_krylov_multi_status")
+        a = np.array(out, np.float64).reshape(self.nrhs, 8)
+        code, which = a[:, 0].astype(np.int64), a[:, 7].astype(np.int64)
+        return dict(code=code, iterations=a[:, 1].astype(np.int64), rnorm=a[:, 2].copy(), bnorm=a[:, 3].copy(), alpha=a[:, 4].copy(),
+                    beta=a[:, 5].copy(), omega=a[:, 6].copy(), which=which, status=[KRYLOV_STATUS[int(c)] for c in code],
+                    breakdown=[KRYLOV_DENOM[int(w)] for w in which], running=int((code == KRYLOV_RUNNING).sum()))
+
+    def solve(self, val, B, X=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
+        """start(), then iterate(check_every) / status() until no column is running -> (X, status dict).  X: the initial
+        guesses, updated in place (zeros made here when None).  No column's result depends on check_every."""
+        import torch
+        if int(check_every) < 1:
+            raise SblasError("check_every must be at least 1")
+        if X is None:
+            _krylov_block("B", B, self.n, self.nrhs, self.device)
+            X = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=self.device)
+        self.start(val, B, X, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
+        while True:
+            self.iterate(int(check_every), stream=stream)
+            st = self.status(stream=stream)
+            if st["running"] == 0:
+                return X, st
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_krylov_multi_plan_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _krylov_multi_one_shot(method, A, B, precond, X, kw):
+    import torch
+    n, rowptr, colidx, val = A
+    kind = _multi_precond(precond)
+    if not isinstance(B, torch.Tensor) or B.dim() != 2:
+        raise SblasError("B must be an (n, nrhs) GPU tensor")
+    ilu = plan = dinv = None
+    try:
+        if kind == PRECOND_JACOBI:                                          # the diagonal's places, read off the ILU(0) plan
+            ilu = Ilu0Plan(n, rowptr, colidx)
+            dinv = ilu.pivots(val).reciprocal_()
+        plan = KrylovMultiPlan(n, rowptr, colidx, B.shape[1], method=method, precond=precond)
+        return plan.solve(val, B, X=X, dinv=dinv, **kw)
+    finally:
+        if plan is not None:
+            plan.destroy()
+        if ilu is not None:
+            ilu.destroy()
+
+
+def pcg_multi(A, B, precond=None, X=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
+    """X with A X = B by preconditioned CG on all columns of B at once, one shot: A = (n, rowptr, colidx, val) as GPU
+    tensors, symmetric positive definite; B an (n, nrhs) row-major tensor; precond None or "jacobi" (rows sorted with a
+    stored diagonal).  -> (X, status dict of per-column arrays).  The plans made here are destroyed before returning."""
+    return _krylov_multi_one_shot("pcg", A, B, precond, X, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
+
+
+def bicgstab_multi(A, B, precond=None, X=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
+    """X with A X = B by preconditioned BiCGStab on all columns of B at once, one shot, as pcg_multi(); A need not be
+    symmetric."""
+    return _krylov_multi_one_shot("bicgstab", A, B, precond, X, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
 
 
 # ------------------------------------------------------------------------------------------
