@@ -1267,4 +1267,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #include "sblas_hip_amg_dev.h"
 #include "sblas_hip_cheby.h"
 #include "sblas_hip_krylov_multi.h"
+#include "sblas_hip_amg_multi.h"
 #endif /* SBLAS_HIP_H */

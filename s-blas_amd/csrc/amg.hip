@@ -41,6 +41,11 @@
 // replaces a level's smoothings: the walk of amg.h takes a polynomial of `degree` launches where it takes a sweep, the
 // launches are cheby.hip's (cheby_launch.h: one ChebyOperator a level, wd as its dinv), and setup runs a level's eigenvalue
 // estimate where it ran the level's wd kernel.  Its buffers are made by a plan's first such setup, never by any other.
+//
+// The block cycle (sblas_hip_amg_plan_apply_multi) is the same walk on n x s row-major blocks: a second
+// Ops of amg_cycle whose launches are amg_multi_kernels.h's, the kernels above widened by a tile of eight columns.  Column
+// j of its result has the bits of apply() on column j.  Its level vectors are made by sblas_hip_amg_plan_reserve_multi,
+// never by any other call; a plan that never reserves keeps its bytes.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -50,6 +55,7 @@
 #include <vector>
 #include "../../include/sblas_hip.h"
 #include "amg.h"
+#include "amg_multi.h"
 #include "cheby.h"
 #include "cheby_launch.h"
 #include "krylov.h"
@@ -254,6 +260,12 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_wd_kernel(int64_t n, int leve
 
 inline unsigned grid_of(int64_t threads) { return (unsigned)((threads + AMG_THREADS - 1) / AMG_THREADS); }
 
+} // namespace
+
+#include "amg_multi_kernels.h" // the kernels above on a tile of columns: after Unit, the modes and contract(off)
+
+namespace {
+
 struct AmgLevel {
     int64_t n = 0, nnz = 0, n_coarse = 0, units = 0;
     const int32_t *rowptr = nullptr, *colidx = nullptr; // level 0: the caller's; below: the COO plan's of the level above
@@ -277,6 +289,9 @@ struct AmgLevel {
     double *d = nullptr;
     ChebyOperator cheb;
     size_t cheb_bytes = 0;
+    // the block cycle's, made by reserve_multi alone: x0 | x1 | res | b of n x the reserved width
+    DeviceBuffer mbuf;
+    double *mx[2] = {nullptr, nullptr}, *mres = nullptr, *mb = nullptr;
     ~AmgLevel()
     {
         if (coo) sblas_hip_coo_plan_destroy(coo);
@@ -309,6 +324,8 @@ struct AmgPlan {
     double *est[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t cheb_bytes = 0;
     int degree = 0; // of the last setup: 0 with the Jacobi and l1 sweeps
+    int multi_width = 0; // the block cycle's reserved columns
+    size_t multi_bytes = 0;
     int levels() const { return (int)lv.size(); }
 };
 
@@ -381,6 +398,81 @@ struct DeviceOps {
 };
 
 bool overlap(const double *a, const double *b, int64_t n) { return a < b + n && b < a + n; }
+
+// ---- the block cycle ---------------------------------------------------------------------------------------------------
+// an n x s row-major block at leading dimension ld
+struct Blk {
+    const double *p;
+    int64_t ld;
+};
+
+void launch_sweep_multi(hipStream_t st, const AmgLevel &L, int mode, int s, Blk b, Blk x, double *y, int64_t ldy)
+{
+    if (mode == MODE_FIRST) {
+        amg_first_multi_kernel<<<grid_of(L.n * s), AMG_THREADS, 0, st>>>(L.n, s, L.wd, b.p, b.ld, y, ldy);
+        return;
+    }
+    if (L.units == 0) return;
+    const SweepMultiArgs a{L.units, amg_multi_unit_blocks(L.units), s, L.d_units, L.colidx, L.val, L.wd, b.p, x.p, y, b.ld, x.ld, ldy};
+    if (mode == MODE_RESIDUAL) launch_sweep_multi_mode<MODE_RESIDUAL>(st, a);
+    else launch_sweep_multi_mode<MODE_SWEEP>(st, a);
+}
+
+void launch_restrict_multi(hipStream_t st, const AmgPlan &p, const AmgLevel &L, int s, Blk res, double *bc, int64_t ldc)
+{
+    if (p.smoothed()) {
+        if (L.r_units == 0) return;
+        launch_transfer_multi_mode<AMG_RESTRICT>(
+            st, TransferMultiArgs{L.r_units, amg_multi_unit_blocks(L.r_units), s, L.d_r_units, L.r_colidx, L.r_val, 0.0, res.p, bc, res.ld, ldc});
+    } else {
+        amg_restrict_multi_kernel<<<grid_of(L.n_coarse * s), AMG_THREADS, 0, st>>>(L.n_coarse, s, L.aggptr, L.members, res.p, res.ld, bc, ldc);
+    }
+}
+
+void launch_prolong_multi(hipStream_t st, const AmgPlan &p, const AmgLevel &L, int s, double scale, Blk e, double *x, int64_t ldx)
+{
+    if (p.smoothed()) {
+        if (L.p_units == 0) return;
+        launch_transfer_multi_mode<AMG_PROLONG>(
+            st, TransferMultiArgs{L.p_units, amg_multi_unit_blocks(L.p_units), s, L.d_p_units, L.p_colidx, L.p_val, scale, e.p, x, e.ld, ldx});
+    } else {
+        amg_prolong_multi_kernel<<<grid_of(L.n * s), AMG_THREADS, 0, st>>>(L.n, s, L.agg, scale, e.p, e.ld, x, ldx);
+    }
+}
+
+// the walk of amg.h on blocks; level 0 reads the caller's R (ldr) and ends in the caller's Z (ldz), the level vectors
+// inside the plan have leading dimension s.  The polynomial calls are never made: apply_multi passes degree 0.
+struct MultiOps {
+    const AmgPlan *p;
+    hipStream_t st;
+    int s;
+    Blk r;
+    double *z;
+    int64_t ldz;
+    const AmgLevel &lv(int l) const { return *p->lv[(size_t)l]; }
+    Blk b(int l) const { return l ? Blk{lv(l).mb, s} : r; }
+    double *x(int l, int k) const { return l == 0 && k == AMG_RESULT_BUFFER ? z : lv(l).mx[k]; }
+    int64_t ldx(int l, int k) const { return l == 0 && k == AMG_RESULT_BUFFER ? ldz : s; }
+    Blk xb(int l, int k) const { return Blk{x(l, k), ldx(l, k)}; }
+    void first(int l, int dst) { launch_sweep_multi(st, lv(l), MODE_FIRST, s, b(l), Blk{nullptr, 0}, x(l, dst), ldx(l, dst)); }
+    void sweep(int l, int src, int dst) { launch_sweep_multi(st, lv(l), MODE_SWEEP, s, b(l), xb(l, src), x(l, dst), ldx(l, dst)); }
+    void poly_first(int, int) {}
+    void poly_guess(int, int, int) {}
+    void poly_step(int, int, int, int) {}
+    void residual(int l, int src) { launch_sweep_multi(st, lv(l), MODE_RESIDUAL, s, b(l), xb(l, src), lv(l).mres, s); }
+    void restrict_to(int l) { launch_restrict_multi(st, *p, lv(l), s, Blk{lv(l).mres, s}, lv(l + 1).mb, s); }
+    void prolong(int l, int dst) { launch_prolong_multi(st, *p, lv(l), s, p->scale, xb(l + 1, AMG_RESULT_BUFFER), x(l, dst), ldx(l, dst)); }
+};
+
+inline size_t span_bytes(int64_t n, int s, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)s) * 8 : 0; }
+// two n_a x s and n_b x s blocks overlap as address ranges
+bool blocks_overlap(const double *a, int64_t na, int64_t lda, const double *b, int64_t nb, int64_t ldb, int s)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + span_bytes(nb, s, ldb) && b0 < a0 + span_bytes(na, s, lda);
+}
+// a block argument of a multi-column entry: present, 8-byte aligned, ld >= s
+bool block_ok(const double *p, int64_t ld, int s) { return p && ld >= s && (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // the plan's level `level` for a single-kernel entry, or null
 const AmgLevel *level_of(const void *plan, int level, bool need_setup)
@@ -922,6 +1014,103 @@ int sblas_hip_amg_pvalues_f64(const void *plan, void *stream, int level, const d
     if (L->nnz == 0) return SBLAS_OK;
     if (!val || !t || overlap(val, t, L->nnz)) return SBLAS_E_INVALID;
     launch_pvalues((hipStream_t)stream, *L, static_cast<const AmgPlan *>(plan)->omega_p, val, t);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+} // extern "C"
+
+// ---- the block cycle (include/sblas_hip_amg_multi.h) ---------------------------------------------------
+extern "C" {
+
+int sblas_hip_amg_plan_reserve_multi(void *plan, void *stream, int nrhs)
+{
+    AmgPlan *p = static_cast<AmgPlan *>(plan);
+    if (!p || !amg_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    if (nrhs <= p->multi_width) return SBLAS_OK; // only grows
+    if (p->n > 0) {
+        if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &capturing) != hipSuccess) return SBLAS_E_HIP;
+        if (capturing != hipStreamCaptureStatusNone) return SBLAS_E_INVALID; // an allocation
+        // every level's new buffer first: the plan keeps what it had if one of them fails
+        std::vector<DeviceBuffer> fresh(p->lv.size());
+        std::vector<size_t> vec(p->lv.size());
+        size_t bytes = 0;
+        for (size_t l = 0; l < p->lv.size(); ++l) {
+            vec[l] = ((size_t)p->lv[l]->n * (size_t)nrhs * 8 + 255) / 256 * 256;
+            if (fresh[l].alloc(p->dev, 4 * vec[l]) != hipSuccess) return SBLAS_E_HIP;
+            bytes += 4 * vec[l];
+        }
+        for (size_t l = 0; l < p->lv.size(); ++l) {
+            AmgLevel &L = *p->lv[l];
+            L.mbuf = std::move(fresh[l]);
+            L.mx[0] = L.mbuf.at<double>(), L.mx[1] = L.mbuf.at<double>(vec[l]), L.mres = L.mbuf.at<double>(2 * vec[l]), L.mb = L.mbuf.at<double>(3 * vec[l]);
+        }
+        p->multi_bytes = bytes;
+    }
+    p->multi_width = nrhs;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_multi_info(const void *plan, int64_t out[4])
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !out) return SBLAS_E_INVALID;
+    int64_t info[12];
+    sblas_hip_amg_plan_info(plan, info);
+    out[0] = p->multi_width, out[1] = (int64_t)p->multi_bytes, out[2] = info[5], out[3] = 0;
+    return SBLAS_OK;
+}
+
+int sblas_hip_amg_plan_apply_multi(const void *plan, void *stream, int nrhs, const double *R, int64_t ldr, double *Z, int64_t ldz)
+{
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!p || !p->ready || !amg_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    if (p->degree > 0) return SBLAS_E_INVALID; // the Chebyshev smoother has no block form
+    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
+    if (ldr < nrhs || ldz < nrhs) return SBLAS_E_INVALID;
+    if (nrhs > p->multi_width) return SBLAS_E_WORKSPACE;
+    if (p->n == 0) return SBLAS_OK;
+    if (!block_ok(R, ldr, nrhs) || !block_ok(Z, ldz, nrhs) || blocks_overlap(R, p->n, ldr, Z, p->n, ldz, nrhs)) return SBLAS_E_INVALID;
+    MultiOps ops{p, (hipStream_t)stream, nrhs, Blk{R, ldr}, Z, ldz};
+    amg_cycle(p->levels(), p->nu, p->coarse_sweeps, ops, 0, 0);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_sweep_multi_f64(const void *plan, void *stream, int level, int mode, int nrhs, const double *B, int64_t ldb, const double *X,
+                                  int64_t ldx, double *Y, int64_t ldy)
+{
+    const AmgLevel *L = level_of(plan, level, true);
+    if (!L || mode < MODE_SWEEP || mode > MODE_FIRST || !amg_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    const bool first = mode == MODE_FIRST;
+    if (ldb < nrhs || ldy < nrhs || (!first && ldx < nrhs)) return SBLAS_E_INVALID;
+    if (L->n == 0) return SBLAS_OK;
+    if (!block_ok(B, ldb, nrhs) || !block_ok(Y, ldy, nrhs) || blocks_overlap(B, L->n, ldb, Y, L->n, ldy, nrhs)) return SBLAS_E_INVALID;
+    if (!first && (!block_ok(X, ldx, nrhs) || blocks_overlap(X, L->n, ldx, Y, L->n, ldy, nrhs))) return SBLAS_E_INVALID;
+    launch_sweep_multi((hipStream_t)stream, *L, mode, nrhs, Blk{B, ldb}, Blk{first ? nullptr : X, first ? 0 : ldx}, Y, ldy);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_restrict_multi_f64(const void *plan, void *stream, int level, int nrhs, const double *RES, int64_t ldr, double *BC, int64_t ldc)
+{
+    const AmgLevel *L = level_of(plan, level, false);
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!L || L->n_coarse == 0 || !amg_multi_width_ok(nrhs) || !block_ok(RES, ldr, nrhs) || !block_ok(BC, ldc, nrhs)) return SBLAS_E_INVALID;
+    if (p->smoothed() && !p->ready) return SBLAS_E_INVALID; // R's values are setup's
+    if (blocks_overlap(RES, L->n, ldr, BC, L->n_coarse, ldc, nrhs)) return SBLAS_E_INVALID;
+    launch_restrict_multi((hipStream_t)stream, *p, *L, nrhs, Blk{RES, ldr}, BC, ldc);
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+int sblas_hip_amg_prolong_multi_f64(const void *plan, void *stream, int level, double scale, int nrhs, const double *E, int64_t lde, double *X,
+                                    int64_t ldx)
+{
+    const AmgLevel *L = level_of(plan, level, false);
+    const AmgPlan *p = static_cast<const AmgPlan *>(plan);
+    if (!L || L->n_coarse == 0 || !amg_multi_width_ok(nrhs) || !block_ok(E, lde, nrhs) || !block_ok(X, ldx, nrhs)) return SBLAS_E_INVALID;
+    if (p->smoothed() && !p->ready) return SBLAS_E_INVALID; // P's values are setup's
+    if (blocks_overlap(E, L->n_coarse, lde, X, L->n, ldx, nrhs)) return SBLAS_E_INVALID;
+    launch_prolong_multi((hipStream_t)stream, *p, *L, nrhs, scale, Blk{E, lde}, X, ldx);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }
 

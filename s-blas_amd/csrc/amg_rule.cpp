@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/sblas_hip.h"
 #include "amg.h"
+#include "amg_multi.h"
 #include "color.h"
 
 #pragma clang fp contract(off) // every product and sum below is rounded on its own; the row sums call fma() by name
@@ -361,6 +362,22 @@ int sblas_amg_limits(int64_t out[8])
     if (!out) return SBLAS_E_INVALID;
     out[0] = AMG_G4_MAX, out[1] = AMG_G16_MAX, out[2] = AMG_THREADS, out[3] = AMG_COARSE_MAX, out[4] = AMG_MAX_LEVELS;
     out[5] = AMG_NU, out[6] = AMG_COARSE_SWEEPS, out[7] = AMG_LEVEL_CAP;
+    return SBLAS_OK;
+}
+
+// the block cycle's sizes (amg_multi.h)
+int sblas_amg_multi_limits(int64_t out[4])
+{
+    if (!out) return SBLAS_E_INVALID;
+    out[0] = SBLAS_AMG_MULTI_MAX_RHS, out[1] = AMG_MULTI_TILE, out[2] = AMG_THREADS, out[3] = 0;
+    return SBLAS_OK;
+}
+
+int sblas_amg_multi_grid(int64_t units, int nrhs, int64_t out[4])
+{
+    if (!out || units < 0 || !amg_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    out[0] = amg_multi_unit_blocks(units), out[1] = amg_multi_tiles(nrhs), out[2] = out[0] * out[1];
+    out[3] = nrhs - (int)(out[1] - 1) * AMG_MULTI_TILE;
     return SBLAS_OK;
 }
 

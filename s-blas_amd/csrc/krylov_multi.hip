@@ -22,6 +22,12 @@
 // anything else -- the ragged last tile, a mixed tile, an odd leading dimension, a base offset by one element -- goes
 // double by double.  Same values, same order, same bits.
 //
+// An applied preconditioner: a plan seated through create_ex -- the AMG block cycle -- runs between the
+// solver's kernels where krylov.hip applies M^-1: PCG on R into Z, then the dots (r, z) and the fold that takes rho or
+// beta; BiCGStab on P into P^ and on S into S^.  It runs on ALL columns, into work blocks only and never into X: a
+// frozen column's operand no longer changes, so its result is recomputed to the same bits, and no column of the cycle
+// can reach another column.
+//
 // Arithmetic.  Contraction is off at file scope, as in krylov.hip: every product and every sum is rounded on its own.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -34,7 +40,7 @@
 #include "capi_util.h"
 #include "krylov.h"
 #include "krylov_multi.h"
-#include "precond_rule.h"
+#include "precond.h"
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
 
@@ -412,7 +418,10 @@ struct MultiPlan {
     const double *val = nullptr, *dinv = nullptr;
     double *x = nullptr;
     int64_t ldx = 0;
+    PrecondSeat pre; // an applied kind's plan (create_ex); NONE and JACOBI live in the kernels here
     bool jacobi() const { return precond == SBLAS_PRECOND_JACOBI; }
+    bool none() const { return precond == SBLAS_PRECOND_NONE; }
+    bool applied() const { return precond_multi_applied(precond); }
     double *w(int k) const { return vec + (size_t)k * (block_bytes / 8); }
     ~MultiPlan()
     {
@@ -457,32 +466,39 @@ int product(const MultiPlan *p, hipStream_t st, const double *in, int64_t ldin, 
 
 int pcg_iteration(const MultiPlan *p, hipStream_t st)
 {
-    const bool jac = p->jacobi();
+    const bool jac = p->jacobi(), app = p->applied();
     const int64_t s = p->s;
-    const Blk x{p->x, p->ldx}, r{p->w(V_R), s}, pp{p->w(V_P), s}, q{p->w(V_Q), s}, z{jac ? p->w(V_Z) : p->w(V_R), s};
+    const Blk x{p->x, p->ldx}, r{p->w(V_R), s}, pp{p->w(V_P), s}, q{p->w(V_Q), s}, z{p->none() ? p->w(V_R) : p->w(V_Z), s};
     const Blk dinv{const_cast<double *>(p->dinv), 0};
-    const int rc = product(p, st, pp.p, s, q.p);
+    int rc = product(p, st, pp.p, s, q.p);
     if (rc != SBLAS_OK) return rc;
     dot(p, st, pp, q);
     fold(p, st, FOLD_PCG_ALPHA, 1, 0);
     launch_update(st, SBLAS_KRYLOV_UP_PCG_XR, jac, up_args(p, {x, r, pp, q, dinv, z}));
-    fold(p, st, FOLD_PCG_RES, jac ? 2 : 1, 1);
+    fold(p, st, FOLD_PCG_RES, jac ? 2 : 1, !app);
+    if (app) { // krylov.hip's applied sequence, column-wise: on all columns, into Z only
+        if ((rc = p->pre.apply_multi(st, p->s, r.p, s, z.p, s)) != SBLAS_OK) return rc;
+        dot(p, st, r, z);
+        fold(p, st, FOLD_PCG_BETA, 1, 0);
+    }
     launch_update(st, SBLAS_KRYLOV_UP_PCG_P, false, up_args(p, {pp, z}));
     return SBLAS_OK;
 }
 
 int bicgstab_iteration(const MultiPlan *p, hipStream_t st)
 {
-    const bool jac = p->jacobi();
+    const bool jac = p->jacobi(), none = p->none(), app = p->applied();
     const int64_t s = p->s;
     const Blk x{p->x, p->ldx}, r{p->w(B_R), s}, rh{p->w(B_RHAT), s}, pp{p->w(B_P), s}, v{p->w(B_V), s}, sv{p->w(B_S), s}, t{p->w(B_T), s};
-    const Blk ph = jac ? Blk{p->w(B_PH), s} : pp, sh = jac ? Blk{p->w(B_SH), s} : sv, dinv{const_cast<double *>(p->dinv), 0};
+    const Blk ph = none ? pp : Blk{p->w(B_PH), s}, sh = none ? sv : Blk{p->w(B_SH), s}, dinv{const_cast<double *>(p->dinv), 0};
     int rc;
     launch_update(st, SBLAS_KRYLOV_UP_BICG_P, jac, up_args(p, {pp, r, v, dinv, ph}));
+    if (app && (rc = p->pre.apply_multi(st, p->s, pp.p, s, ph.p, s)) != SBLAS_OK) return rc;
     if ((rc = product(p, st, ph.p, s, v.p)) != SBLAS_OK) return rc;
     dot(p, st, rh, v);
     fold(p, st, FOLD_BICG_ALPHA, 1, 0);
     launch_update(st, SBLAS_KRYLOV_UP_BICG_S, jac, up_args(p, {sv, r, v, dinv, sh}));
+    if (app && (rc = p->pre.apply_multi(st, p->s, sv.p, s, sh.p, s)) != SBLAS_OK) return rc;
     if ((rc = product(p, st, sh.p, s, t.p)) != SBLAS_OK) return rc;
     dot(p, st, t, sv, t, t, sv, sv);
     fold(p, st, FOLD_BICG_OMEGA, 3, 0);
@@ -493,6 +509,64 @@ int bicgstab_iteration(const MultiPlan *p, hipStream_t st)
 
 // the bytes an n x s block at leading dimension ld spans
 inline size_t span_bytes(int64_t n, int s, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)s) * 8 : 0; }
+
+// launches of one cycle of the seated plan (an applied kind), else 0
+int64_t precond_cycle_launches(const MultiPlan *p)
+{
+    int64_t mi[4] = {0, 0, 0, 0};
+    if (p->applied()) sblas_hip_amg_plan_multi_info(p->pre.lower, mi);
+    return mi[2];
+}
+
+// both creates.  precond_plan: the plan of an applied kind (create_ex), which is seated and whose level vectors are
+// reserved for nrhs columns; the work blocks an applied kind writes -- Z, P^ and S^ -- are among the plan's own already.
+int create_plan(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, int nrhs, int precond,
+                void *precond_plan, void **plan_out)
+{
+    if (!krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
+    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
+    if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
+    const int device = resolve_device(dev);
+    std::unique_ptr<MultiPlan> p(new MultiPlan);
+    p->dev = device, p->method = method, p->precond = precond, p->s = nrhs, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
+    p->rowptr = rowptr, p->colidx = colidx;
+    p->n_blocks = method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS;
+    if (precond_plan) {
+        int64_t info[12];
+        if (n == 0 && sblas_hip_amg_plan_info(precond_plan, info) == SBLAS_OK && info[0] == 0) {
+            // an empty structure has no content to compare and an empty plan no device memory: it is seated as it is
+            p->pre.kind = precond, p->pre.lower = precond_plan, p->pre.rowptr = rowptr, p->pre.colidx = colidx;
+        } else if (p->pre.bind(precond, precond_plan, nullptr, device, n, nnz, rowptr, colidx) != SBLAS_OK) {
+            return SBLAS_E_INVALID;
+        }
+        DeviceScope scope(dev);
+        if (scope.err != hipSuccess) return SBLAS_E_HIP;
+        const int rc = sblas_hip_amg_plan_reserve_multi(precond_plan, stream, nrhs);
+        if (rc != SBLAS_OK) return rc;
+    }
+    if (n == 0) {
+        *plan_out = p.release();
+        return SBLAS_OK;
+    }
+    DeviceScope scope(dev);
+    if (scope.err != hipSuccess) return SBLAS_E_HIP;
+    int rc = sblas_hip_spmm_plan_create(device, stream, n, n, nnz, rowptr, colidx, nrhs, &p->spmm);
+    if (rc != SBLAS_OK) return rc;
+    p->scalar_bytes = pad256((size_t)nrhs * KRYLOV_BLOCK_SLOTS * 8);
+    p->partial_bytes = pad256((size_t)KRYLOV_MAX_DOTS * (size_t)nrhs * (size_t)p->cells * 8);
+    p->ws_bytes = pad256(sblas_hip_spmm_csr_f64_i32_workspace(n, n, nnz, nrhs));
+    p->block_bytes = pad256((size_t)n * (size_t)nrhs * 8);
+    p->bytes = p->scalar_bytes + p->partial_bytes + p->ws_bytes + (size_t)p->n_blocks * p->block_bytes;
+    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) return SBLAS_E_HIP;
+    p->blk = p->buf.at<double>(), p->part = p->buf.at<double>(p->scalar_bytes);
+    p->ws = p->ws_bytes ? p->buf.at<double>(p->scalar_bytes + p->partial_bytes) : nullptr;
+    p->vec = p->buf.at<double>(p->scalar_bytes + p->partial_bytes + p->ws_bytes);
+    // the work blocks start from zero: a product with beta 0 into a block that never held a value
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(p->blk, 0, p->bytes, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
+    *plan_out = p.release();
+    return SBLAS_OK;
+}
 
 } // namespace
 
@@ -556,37 +630,19 @@ int sblas_hip_krylov_multi_plan_create(int dev, void *stream, int method, int64_
     if (!plan_out) return SBLAS_E_INVALID;
     *plan_out = nullptr;
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
-    if (!precond_multi(precond)) return SBLAS_E_INVALID; // precond_rule.h: ILU(0), AMG and Chebyshev have no multi-column apply
-    if (!krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
-    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
-    if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
-    const int device = resolve_device(dev);
-    std::unique_ptr<MultiPlan> p(new MultiPlan);
-    p->dev = device, p->method = method, p->precond = precond, p->s = nrhs, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
-    p->rowptr = rowptr, p->colidx = colidx;
-    p->n_blocks = method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS;
-    if (n == 0) {
-        *plan_out = p.release();
-        return SBLAS_OK;
-    }
-    DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    int rc = sblas_hip_spmm_plan_create(device, stream, n, n, nnz, rowptr, colidx, nrhs, &p->spmm);
-    if (rc != SBLAS_OK) return rc;
-    p->scalar_bytes = pad256((size_t)nrhs * KRYLOV_BLOCK_SLOTS * 8);
-    p->partial_bytes = pad256((size_t)KRYLOV_MAX_DOTS * (size_t)nrhs * (size_t)p->cells * 8);
-    p->ws_bytes = pad256(sblas_hip_spmm_csr_f64_i32_workspace(n, n, nnz, nrhs));
-    p->block_bytes = pad256((size_t)n * (size_t)nrhs * 8);
-    p->bytes = p->scalar_bytes + p->partial_bytes + p->ws_bytes + (size_t)p->n_blocks * p->block_bytes;
-    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) return SBLAS_E_HIP;
-    p->blk = p->buf.at<double>(), p->part = p->buf.at<double>(p->scalar_bytes);
-    p->ws = p->ws_bytes ? p->buf.at<double>(p->scalar_bytes + p->partial_bytes) : nullptr;
-    p->vec = p->buf.at<double>(p->scalar_bytes + p->partial_bytes + p->ws_bytes);
-    // the work blocks start from zero: a product with beta 0 into a block that never held a value
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(p->blk, 0, p->bytes, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
-    *plan_out = p.release();
-    return SBLAS_OK;
+    if (!precond_multi(precond)) return SBLAS_E_INVALID; // precond_rule.h: an applied kind needs its plan, which create_ex takes
+    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, precond, nullptr, plan_out);
+}
+
+int sblas_hip_krylov_multi_plan_create_ex(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr,
+                                          const int32_t *colidx, int nrhs, int precond, void *precond_plan, void **plan_out)
+{
+    if (!plan_out) return SBLAS_E_INVALID;
+    *plan_out = nullptr;
+    if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
+    // precond_rule.h: a kind that rides in the kernels takes no plan, AMG takes its own, every other kind is refused
+    if (precond_multi(precond) ? precond_plan != nullptr : !(precond_multi_applied(precond) && precond_plan)) return SBLAS_E_INVALID;
+    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, precond, precond_plan, plan_out);
 }
 
 int sblas_hip_krylov_multi_plan_info(const void *plan, int64_t out[12])
@@ -595,7 +651,7 @@ int sblas_hip_krylov_multi_plan_info(const void *plan, int64_t out[12])
     const MultiPlan *p = static_cast<const MultiPlan *>(plan);
     out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->s, out[5] = p->n_blocks;
     out[6] = (int64_t)p->block_bytes, out[7] = (int64_t)p->partial_bytes, out[8] = (int64_t)p->scalar_bytes, out[9] = (int64_t)p->ws_bytes;
-    out[10] = (int64_t)p->bytes, out[11] = sblas_krylov_multi_launches(p->method, p->precond, 0);
+    out[10] = (int64_t)p->bytes, out[11] = sblas_krylov_multi_launches_ex(p->method, p->precond, 0, precond_cycle_launches(p));
     return SBLAS_OK;
 }
 
@@ -619,6 +675,10 @@ int sblas_hip_krylov_multi_start(void *plan, void *stream, const double *val, co
         return SBLAS_OK;
     }
     const bool jac = p->jacobi();
+    if (p->applied()) { // the block cycle needs a plan that is set up, with a smoother that has a block form
+        int64_t info[12];
+        if (sblas_hip_amg_plan_info(p->pre.lower, info) != SBLAS_OK || !info[10] || info[9] == SBLAS_AMG_CHEBYSHEV) return SBLAS_E_INVALID;
+    }
     if (!B || !X || (p->nnz > 0 && !val) || (jac && !dinv)) return SBLAS_E_INVALID;
     if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
     const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
@@ -636,10 +696,15 @@ int sblas_hip_krylov_multi_start(void *plan, void *stream, const double *val, co
     dot(p, st, b, b);
     fold(p, st, FOLD_START_B, 1, !pcg, rtol, atol, max_iter);
     if (pcg) {
-        const Blk r{p->w(V_R), s}, q{p->w(V_Q), s}, z{jac ? p->w(V_Z) : p->w(V_R), s}, pp{p->w(V_P), s};
+        const Blk r{p->w(V_R), s}, q{p->w(V_Q), s}, z{p->none() ? p->w(V_R) : p->w(V_Z), s}, pp{p->w(V_P), s};
         if ((rc = product(p, st, X, ldx, q.p)) != SBLAS_OK) return rc;
         launch_update(st, UP_START_PCG, jac, up_args(p, {r, b, q, di, z, x}));
         fold(p, st, FOLD_START_R, jac ? 2 : 1, 0);
+        if (p->applied()) { // krylov.hip's start: z = M^-1 r on all columns, then rho = (r, z)
+            if ((rc = p->pre.apply_multi(st, p->s, r.p, s, z.p, s)) != SBLAS_OK) return rc;
+            dot(p, st, r, z);
+            fold(p, st, FOLD_RHO0, 1, 0);
+        }
         launch_update(st, UP_COPY, false, up_args(p, {pp, z}));
     } else {
         const Blk r{p->w(B_R), s}, v{p->w(B_V), s}, rh{p->w(B_RHAT), s}, pp{p->w(B_P), s};

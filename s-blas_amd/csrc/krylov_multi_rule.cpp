@@ -1,6 +1,6 @@
 // krylov_multi_rule.cpp -- the host rule of the multi-right-hand-side Krylov solvers (krylov_multi.hip): the limits,
-// which preconditioner kinds a batch takes (precond_rule.h), the launches of one iteration, the grid of a pass, and the
-// scalar step both solvers' folds run (krylov_scalar.h), compiled here for the host.  No GPU call in this file, so it is
+// which preconditioner kinds a batch takes, alone or with a plan (precond_rule.h), the launches of one iteration, the
+// grid of a pass, and the scalar step both solvers' folds run (krylov_scalar.h), compiled here for the host.  No GPU call in this file, so it is
 // testable on a CPU box (and under a host sanitizer).
 #include <stdint.h>
 #include "../../include/sblas_hip.h"
@@ -32,6 +32,20 @@ int64_t sblas_krylov_multi_launches(int method, int precond, int64_t spmm_launch
     if (method == SBLAS_KRYLOV_PCG) return spmm_launches + 5;
     // p update; SpMM; (r^, v): stage 1, fold; s update; SpMM; (t, s), (t, t) and (s, s): stage 1, fold; x / r update; fold
     return 2 * spmm_launches + 8;
+}
+
+int sblas_krylov_multi_precond_plan_ok(int precond) { return sblas::precond_multi_applied(precond) ? SBLAS_OK : SBLAS_E_INVALID; }
+
+int64_t sblas_krylov_multi_launches_ex(int method, int precond, int64_t spmm_launches, int64_t precond_launches)
+{
+    if (precond_launches < 0) return -1;
+    if (sblas::precond_multi(precond)) return precond_launches == 0 ? sblas_krylov_multi_launches(method, precond, spmm_launches) : -1;
+    if (!sblas::precond_multi_applied(precond)) return -1;
+    const int64_t plain = sblas_krylov_multi_launches(method, SBLAS_PRECOND_NONE, spmm_launches);
+    if (plain < 0) return -1;
+    // PCG: after the residual's fold the block apply, the dots (r, z): stage 1, and the fold that takes beta (krylov.hip's
+    // pcg_iteration); BiCGStab: the block apply on P and on S
+    return method == SBLAS_KRYLOV_PCG ? plain + precond_launches + 2 : plain + 2 * precond_launches;
 }
 
 int sblas_krylov_multi_grid(int64_t n, int nrhs, int64_t out[4])

@@ -76,6 +76,14 @@ struct PrecondSeat {
         if (rc != SBLAS_OK) return rc;
         return sblas_hip_sptrsv_f64_i32_planned(upper, s, rowptr, colidx, values, 1.0, tmp, out);
     }
+
+    // OUT = M^-1 IN on n x s row-major blocks, for a kind with a multi-column apply (precond_multi_applied): the AMG block
+    // cycle, whose column j has apply()'s bits on column j.  OUT must not overlap IN.
+    int apply_multi(hipStream_t s, int nrhs, const double *in, int64_t ldin, double *out, int64_t ldout) const
+    {
+        if (kind != SBLAS_PRECOND_AMG) return SBLAS_E_INVALID;
+        return sblas_hip_amg_plan_apply_multi(lower, s, nrhs, in, ldin, out, ldout);
+    }
 };
 
 // y = A x of a solver plan: through its SpMV plan where it was given one

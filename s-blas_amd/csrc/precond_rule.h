@@ -17,8 +17,11 @@ inline bool precond_takes_values(int kind) { return kind == SBLAS_PRECOND_JACOBI
 // may run with out == in: the two solves go through a temporary; a cycle or a polynomial reads in while it writes out
 inline bool precond_in_place(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 // serves several right-hand sides at once (krylov_multi.hip): the kinds that ride in the solver's own kernels.  An applied
-// kind has no multi-column apply yet.
+// kind takes a plan: precond_multi_applied.
 inline bool precond_multi(int kind) { return precond_known(kind) && !precond_applied(kind); }
+// serves several right-hand sides at once through a plan of its own with a multi-column apply: the AMG
+// block cycle.  ILU(0) waits on a row-major sptrsm, Chebyshev on a block polynomial of its own.
+inline bool precond_multi_applied(int kind) { return kind == SBLAS_PRECOND_AMG; }
 // holds two plans, lower and upper; every other applied kind holds one handle in lower's place and no upper
 inline bool precond_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 

@@ -94,6 +94,13 @@ EXPORTS_KRYLOV_MULTI = [
     "sblas_hip_krylov_multi_plan_create", "sblas_hip_krylov_multi_plan_info", "sblas_hip_krylov_multi_plan_destroy",
     "sblas_hip_krylov_multi_start", "sblas_hip_krylov_multi_iterate", "sblas_hip_krylov_multi_status",
 ]
+# what include/sblas_hip_amg_multi.h declares (the AMG cycle on a block of columns and its seat under the solvers above)
+EXPORTS_AMG_MULTI = [
+    "sblas_amg_multi_limits", "sblas_amg_multi_grid", "sblas_krylov_multi_precond_plan_ok", "sblas_krylov_multi_launches_ex",
+    "sblas_hip_amg_plan_reserve_multi", "sblas_hip_amg_plan_multi_info", "sblas_hip_amg_plan_apply_multi",
+    "sblas_hip_amg_sweep_multi_f64", "sblas_hip_amg_restrict_multi_f64", "sblas_hip_amg_prolong_multi_f64",
+    "sblas_hip_krylov_multi_plan_create_ex",
+]
 
 
 class SblasError(RuntimeError):
@@ -535,6 +542,28 @@ def lib():
     L.sblas_hip_krylov_multi_iterate.argtypes = [vp, vp, i64]
     L.sblas_hip_krylov_multi_status.restype = C.c_int
     L.sblas_hip_krylov_multi_status.argtypes = [vp, vp, C.POINTER(f64)]
+    L.sblas_amg_multi_limits.restype = C.c_int
+    L.sblas_amg_multi_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_amg_multi_grid.restype = C.c_int
+    L.sblas_amg_multi_grid.argtypes = [i64, C.c_int, C.POINTER(i64)]
+    L.sblas_krylov_multi_precond_plan_ok.restype = C.c_int
+    L.sblas_krylov_multi_precond_plan_ok.argtypes = [C.c_int]
+    L.sblas_krylov_multi_launches_ex.restype = i64
+    L.sblas_krylov_multi_launches_ex.argtypes = [C.c_int, C.c_int, i64, i64]
+    L.sblas_hip_amg_plan_reserve_multi.restype = C.c_int
+    L.sblas_hip_amg_plan_reserve_multi.argtypes = [vp, vp, C.c_int]
+    L.sblas_hip_amg_plan_multi_info.restype = C.c_int
+    L.sblas_hip_amg_plan_multi_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_amg_plan_apply_multi.restype = C.c_int
+    L.sblas_hip_amg_plan_apply_multi.argtypes = [vp, vp, C.c_int, vp, i64, vp, i64]
+    L.sblas_hip_amg_sweep_multi_f64.restype = C.c_int
+    L.sblas_hip_amg_sweep_multi_f64.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64]
+    L.sblas_hip_amg_restrict_multi_f64.restype = C.c_int
+    L.sblas_hip_amg_restrict_multi_f64.argtypes = [vp, vp, C.c_int, C.c_int, vp, i64, vp, i64]
+    L.sblas_hip_amg_prolong_multi_f64.restype = C.c_int
+    L.sblas_hip_amg_prolong_multi_f64.argtypes = [vp, vp, C.c_int, f64, C.c_int, vp, i64, vp, i64]
+    L.sblas_hip_krylov_multi_plan_create_ex.restype = C.c_int
+    L.sblas_hip_krylov_multi_plan_create_ex.argtypes = [C.c_int, vp, C.c_int, i64, i64, vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -2612,7 +2641,10 @@ class AmgPlan:
     aggregation="device" (sblas_hip_amg_plan_create_dev, include/sblas_hip_amg_dev.h) aggregates every level on the device
     in Jones-Plassmann rounds and builds the same plan, array for array; "host" (the default) is create as it was.
     setup(val, smoother="chebyshev", degree=2, ...) (include/sblas_hip_cheby.h) smooths with a Chebyshev polynomial in
-    D^-1 A on every level's own device estimate of lambda_max; eig() shows the estimates."""
+    D^-1 A on every level's own device estimate of lambda_max; eig() shows the estimates.
+    apply_multi(R) (include/sblas_hip_amg_multi.h) is the cycle on an (n, s) row-major block, s <= 64: column j has exactly
+    the bits of apply(R[:, j]).  reserve(s) makes its level vectors (the one call that allocates); a KrylovMultiPlan takes
+    the plan as precond.  Not with the Chebyshev smoother."""
 
     def __init__(self, n, rowptr, colidx, val=None, theta=0.0, coarse_max=64, max_levels=20, seed=0, stream=None, prolongator="plain",
                  prolong_omega=AMG_PROLONG_OMEGA, min_reduction=None, aggregation="host"):
@@ -2778,6 +2810,55 @@ class AmgPlan:
         check(rc, "sblas_hip_amg_plan_apply")
         return out
 
+    def reserve(self, nrhs, stream=None):
+        """The block cycle's level vectors for nrhs columns (sblas_hip_amg_plan_reserve_multi): only grows -- a smaller
+        request changes nothing.  Allocates, so it is refused while a stream capture is under way.  Returns the width
+        reserved."""
+        import torch
+        nrhs = _amg_multi_width(nrhs)
+        with torch.cuda.device(self.device):
+            if nrhs > self.multi_info()["width"] and torch.cuda.is_current_stream_capturing():
+                raise SblasError("reserve allocates the block cycle's level vectors: call it before capturing a graph")
+            check(lib().sblas_hip_amg_plan_reserve_multi(self.handle, _stream(stream), nrhs), "sblas_hip_amg_plan_reserve_multi")
+        return self.multi_info()["width"]
+
+    def multi_info(self):
+        """dict(width, bytes, launches) of the block cycle (sblas_hip_amg_plan_multi_info): the reserved columns, the
+        bytes of the level vectors, the launches of one block cycle (one cycle's: a walk call is one launch)."""
+        out = (C.c_int64 * 4)()
+        check(lib().sblas_hip_amg_plan_multi_info(self.handle, out), "sblas_hip_amg_plan_multi_info")
+        return dict(width=int(out[0]), bytes=int(out[1]), launches=int(out[2]))
+
+    def apply_multi(self, R, out=None, stream=None):
+        """out = M^-1 R on an (n, s) row-major block, one block cycle (sblas_hip_amg_plan_apply_multi): out[:, j] has
+        exactly the bits of apply(R[:, j]).  R and out may be column slices of wider tensors; out is made here when None
+        and must not overlap R.  Reserves on demand when no capture is under way.  Every refusal comes before any launch."""
+        import torch
+        if not isinstance(R, torch.Tensor) or R.dim() != 2:
+            raise SblasError("R must be an (n, nrhs) GPU tensor")
+        s = _amg_multi_width(R.shape[1])
+        ldr = _krylov_block("R", R, self.n, s, self.device)
+        if out is None:
+            out = torch.empty((self.n, s), dtype=torch.float64, device=self.device)
+        ldz = _krylov_block("out", out, self.n, s, self.device)
+        info = self.info()
+        if not info["ready"]:
+            raise SblasError("apply_multi needs setup() first")
+        if info["smoother"] == "chebyshev":
+            raise SblasError("the Chebyshev smoother has no block cycle: apply_multi takes a plan set up with 'jacobi' or 'l1'")
+        if self.n and _blocks_overlap(R, ldr, out, ldz, self.n, s):
+            raise SblasError("out must not overlap R")
+        with torch.cuda.device(self.device):
+            if s > self.multi_info()["width"]:
+                if torch.cuda.is_current_stream_capturing():
+                    raise SblasError("the block cycle's level vectors are reserved for %d columns, not %d: call reserve(%d) before "
+                                     "capturing a graph" % (self.multi_info()["width"], s, s))
+                self.reserve(s, stream=stream)
+            rc = lib().sblas_hip_amg_plan_apply_multi(self.handle, _stream(stream), s, R.data_ptr() if self.n else None, ldr,
+                                                      out.data_ptr() if self.n else None, ldz)
+        check(rc, "sblas_hip_amg_plan_apply_multi")
+        return out
+
     def check(self, stream=None):
         """None, or (level, row) of the least diagonal the last setup() found not finite and > 0.  Synchronises."""
         import torch
@@ -2858,6 +2939,85 @@ def amg_prolong(plan, level, e, x, scale=1.0, stream=None):
     with torch.cuda.device(plan.device):
         check(lib().sblas_hip_amg_prolong_f64(plan.handle, _stream(stream), int(level), float(scale), pe, px), "sblas_hip_amg_prolong_f64")
     return x
+
+
+# ------------------------------------------------------------------------------------------
+# The AMG cycle on a block of columns (sblas_amg_multi_*, sblas_hip_amg_*_multi*; include/sblas_hip_amg_multi.h)
+# ------------------------------------------------------------------------------------------
+def amg_multi_limits():
+    """The block cycle's limits (sblas_amg_multi_limits): dict(max_rhs, tile, threads)."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_amg_multi_limits(out), "sblas_amg_multi_limits")
+    return dict(max_rhs=int(out[0]), tile=int(out[1]), threads=int(out[2]))
+
+
+def amg_multi_grid(units, nrhs):
+    """Workgroups of one multi-column row kernel over `units` four-lane units (sblas_amg_multi_grid): dict(unit_blocks,
+    tiles, grid, last_tile)."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_amg_multi_grid(int(units), int(nrhs), out), "sblas_amg_multi_grid")
+    return dict(unit_blocks=int(out[0]), tiles=int(out[1]), grid=int(out[2]), last_tile=int(out[3]))
+
+
+def _amg_multi_width(s):
+    if not 1 <= int(s) <= amg_multi_limits()["max_rhs"]:
+        raise SblasError("between 1 and %d columns, not %d" % (amg_multi_limits()["max_rhs"], s))
+    return int(s)
+
+
+def _amg_level_block(name, t, n, s, plan):
+    ld = _krylov_block(name, t, n, s, plan.device)
+    return (t.data_ptr() if n else None), ld
+
+
+def _amg_block_width(t):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise SblasError("a block must be a 2-D GPU tensor")
+    return _amg_multi_width(t.shape[1])
+
+
+def amg_sweep_multi(plan, level, B, X, Y, mode="sweep", stream=None):
+    """amg_sweep on (n_level, s) row-major blocks, one launch (sblas_hip_amg_sweep_multi_f64): column j of Y has the bits
+    amg_sweep gives on column j.  Y must overlap neither B nor X; X may be None with mode "first"."""
+    import torch
+    if mode not in AMG_SWEEP_MODES:
+        raise SblasError("mode must be 'sweep', 'residual' or 'first', not %r" % (mode,))
+    s = _amg_block_width(B)
+    n, _ = _amg_level_sizes(plan, level)
+    pb, ldb = _amg_level_block("B", B, n, s, plan)
+    py, ldy = _amg_level_block("Y", Y, n, s, plan)
+    px, ldx = _amg_level_block("X", X, n, s, plan) if (mode != "first" or X is not None) else (None, s)
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_sweep_multi_f64(plan.handle, _stream(stream), int(level), AMG_SWEEP_MODES[mode], s, pb, ldb, px, ldx, py, ldy),
+              "sblas_hip_amg_sweep_multi_f64")
+    return Y
+
+
+def amg_restrict_multi(plan, level, RES, BC, stream=None):
+    """amg_restrict on row-major blocks: RES (n_level, s) -> BC (n_coarse, s) (sblas_hip_amg_restrict_multi_f64)"""
+    import torch
+    s = _amg_block_width(RES)
+    n, nc = _amg_level_sizes(plan, level)
+    pr, ldr = _amg_level_block("RES", RES, n, s, plan)
+    pc, ldc = _amg_level_block("BC", BC, nc, s, plan)
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_restrict_multi_f64(plan.handle, _stream(stream), int(level), s, pr, ldr, pc, ldc),
+              "sblas_hip_amg_restrict_multi_f64")
+    return BC
+
+
+def amg_prolong_multi(plan, level, E, X, scale=1.0, stream=None):
+    """amg_prolong on row-major blocks: X (n_level, s) += scale * P E, E (n_coarse, s) (sblas_hip_amg_prolong_multi_f64)"""
+    import torch
+    s = _amg_block_width(X)
+    n, nc = _amg_level_sizes(plan, level)
+    pe, lde = _amg_level_block("E", E, nc, s, plan)
+    px, ldx = _amg_level_block("X", X, n, s, plan)
+    with torch.cuda.device(plan.device):
+        check(lib().sblas_hip_amg_prolong_multi_f64(plan.handle, _stream(stream), int(level), float(scale), s, pe, lde, px, ldx),
+              "sblas_hip_amg_prolong_multi_f64")
+    return X
 
 
 # ------------------------------------------------------------------------------------------
@@ -3360,7 +3520,10 @@ def krylov_multi_limits():
 
 
 def _multi_precond(precond):
-    """precond of a multi-right-hand-side plan -> its code; the kinds without a multi-column apply are refused by name"""
+    """precond of a multi-right-hand-side plan -> its code; the kinds without a multi-column apply are refused by name.
+    An AmgPlan INSTANCE is taken (its block cycle); the name "amg" carries no plan and stays refused."""
+    if isinstance(precond, AmgPlan) and lib().sblas_krylov_multi_precond_plan_ok(PRECOND_AMG) == 0:
+        return PRECOND_AMG
     kind = _precond_seat(precond)[0] if not isinstance(precond, str) or precond == "jacobi" else _PRECOND_CODE.get(precond, -1)
     if kind < 0:
         raise SblasError("precond must be None or 'jacobi', not %r" % (precond,))
@@ -3372,10 +3535,15 @@ def _multi_precond(precond):
 
 def krylov_multi_launches(method="pcg", precond=None, spmm_launches=0):
     """Launches of one lockstep iteration (sblas_krylov_multi_launches): the solver's own kernels and spmm_launches for
-    each product (PCG one, BiCGStab two)."""
+    each product (PCG one, BiCGStab two).  precond an AmgPlan: its block cycles, the dots and the fold that go with them
+    are counted too (sblas_krylov_multi_launches_ex with the plan's cycle)."""
     if method not in _KRYLOV_METHOD:
         raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
-    n = int(lib().sblas_krylov_multi_launches(_KRYLOV_METHOD[method], _multi_precond(precond), int(spmm_launches)))
+    kind = _multi_precond(precond)
+    if isinstance(precond, AmgPlan):
+        n = int(lib().sblas_krylov_multi_launches_ex(_KRYLOV_METHOD[method], kind, int(spmm_launches), precond.multi_info()["launches"]))
+    else:
+        n = int(lib().sblas_krylov_multi_launches(_KRYLOV_METHOD[method], kind, int(spmm_launches)))
     if n < 0:
         raise SblasError("sblas_krylov_multi_launches refused its arguments")
     return n
@@ -3510,8 +3678,12 @@ class KrylovMultiPlan:
     """PCG or BiCGStab for A X = B with nrhs right-hand sides at once on the n x n CSR structure (rowptr, colidx), int32
     indices (sblas_hip_krylov_multi_plan_create): nrhs independent recurrences that share A and run in lockstep, one SpMM
     per product instead of nrhs SpMVs.  method: "pcg" (A symmetric positive definite) or "bicgstab"; precond: None or
-    "jacobi" (start / solve take dinv, one inverse diagonal for all columns) -- ILU(0), AMG and Chebyshev have no
-    multi-column apply and are refused.  B and X are (n, nrhs) float64 GPU tensors, row-major: contiguous, or a column
+    "jacobi" (start / solve take dinv, one inverse diagonal for all columns), or an AmgPlan on the same tensors after its
+    setup() with "jacobi" or "l1" (sblas_hip_krylov_multi_plan_create_ex): its block cycle runs on all columns where the
+    single solver applies the cycle, column j with exactly AmgPlan.apply's bits; the solver reserves the plan's level
+    vectors for nrhs columns, keeps the plan alive and takes no dinv.  Two solvers seated on one AmgPlan share its level
+    vectors, as two single solvers do: do not run them at the same time.  ILU(0) and Chebyshev have no multi-column
+    apply and are refused, and so are the NAMES "ilu0", "amg" and "chebyshev", which carry no plan.  B and X are (n, nrhs) float64 GPU tensors, row-major: contiguous, or a column
     slice of a wider tensor.  The plan owns an SpMM plan for this width, its workspace, the work blocks, the partial sums
     and one scalar block a column, and keeps the structure tensors alive.
 
@@ -3534,9 +3706,19 @@ class KrylovMultiPlan:
         self._keep = None
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_krylov_multi_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
-                                                          colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind, C.byref(h))
-        check(rc, "sblas_hip_krylov_multi_plan_create")
+            if isinstance(precond, AmgPlan):                                # the plan travels with its kind; self.precond keeps it alive
+                if precond.n != n or precond.rowptr.data_ptr() != rowptr.data_ptr() or precond.colidx.data_ptr() != colidx.data_ptr():
+                    raise SblasError("the AmgPlan was made for another structure than this solver's (rowptr, colidx)")
+                precond.reserve(self.nrhs, stream=stream)
+                name = "sblas_hip_krylov_multi_plan_create_ex"
+                rc = lib().sblas_hip_krylov_multi_plan_create_ex(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                                 colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind,
+                                                                 precond.handle, C.byref(h))
+            else:
+                name = "sblas_hip_krylov_multi_plan_create"
+                rc = lib().sblas_hip_krylov_multi_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                              colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind, C.byref(h))
+        check(rc, name)
         self.handle = h
 
     def info(self):
@@ -3559,6 +3741,12 @@ class KrylovMultiPlan:
                 raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
             _krylov_vector("dinv", dinv, self.n, self.device)
             pre = dinv
+        elif self.precond_kind == PRECOND_AMG:
+            info = self.precond.info()
+            if not info["ready"]:
+                raise SblasError("the AmgPlan needs setup() before a solve")
+            if info["smoother"] == "chebyshev":
+                raise SblasError("the Chebyshev smoother has no block cycle: set the AmgPlan up with 'jacobi' or 'l1'")
         if self.n and _blocks_overlap(X, ldx, B, ldb, self.n, self.nrhs):
             raise SblasError("X must not overlap B")
         if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
@@ -3623,11 +3811,15 @@ class KrylovMultiPlan:
 def _krylov_multi_one_shot(method, A, B, precond, X, kw):
     import torch
     n, rowptr, colidx, val = A
-    kind = _multi_precond(precond)
+    one_shot_amg = isinstance(precond, str) and precond in ("amg", "amg_smoothed")
+    kind = PRECOND_AMG if one_shot_amg else _multi_precond(precond)
     if not isinstance(B, torch.Tensor) or B.dim() != 2:
         raise SblasError("B must be an (n, nrhs) GPU tensor")
-    ilu = plan = dinv = None
+    ilu = plan = dinv = amg = None
     try:
+        if one_shot_amg:                                                    # the defaults, as pcg(): V(1, 1), Jacobi 2/3, structure only
+            amg = precond = AmgPlan(n, rowptr, colidx, prolongator="smoothed" if precond == "amg_smoothed" else "plain")
+            amg.setup(val)
         if kind == PRECOND_JACOBI:                                          # the diagonal's places, read off the ILU(0) plan
             ilu = Ilu0Plan(n, rowptr, colidx)
             dinv = ilu.pivots(val).reciprocal_()
@@ -3638,12 +3830,14 @@ def _krylov_multi_one_shot(method, A, B, precond, X, kw):
             plan.destroy()
         if ilu is not None:
             ilu.destroy()
+        if amg is not None:
+            amg.destroy()
 
 
 def pcg_multi(A, B, precond=None, X=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
     """X with A X = B by preconditioned CG on all columns of B at once, one shot: A = (n, rowptr, colidx, val) as GPU
-    tensors, symmetric positive definite; B an (n, nrhs) row-major tensor; precond None or "jacobi" (rows sorted with a
-    stored diagonal).  -> (X, status dict of per-column arrays).  The plans made here are destroyed before returning."""
+    tensors, symmetric positive definite; B an (n, nrhs) row-major tensor; precond None, "jacobi", "amg" or
+    "amg_smoothed" (rows sorted with a stored diagonal; the last two build an AmgPlan with pcg()'s defaults and set it up).  -> (X, status dict of per-column arrays).  The plans made here are destroyed before returning."""
     return _krylov_multi_one_shot("pcg", A, B, precond, X, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every))
 
 
