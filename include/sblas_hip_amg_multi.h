@@ -40,8 +40,8 @@ int sblas_amg_multi_limits(int64_t out[4]);
  * [1, 64]. */
 int sblas_amg_multi_grid(int64_t units, int nrhs, int64_t out[4]);
 /* SBLAS_OK when a multi-right-hand-side solver plan takes this preconditioner kind WITH a plan of that kind
- * (sblas_hip_krylov_multi_plan_create_ex): SBLAS_PRECOND_AMG alone.  ILU(0) waits on a row-major sptrsm, Chebyshev on a
- * block polynomial of its own. */
+ * (sblas_hip_krylov_multi_plan_create_ex): SBLAS_PRECOND_AMG alone.  ILU(0) is seated as a PAIR of solve plans through
+ * a create of its own (sblas_hip_sptrsm_tile.h) and stays refused here; Chebyshev waits on a block polynomial of its own. */
 int sblas_krylov_multi_precond_plan_ok(int precond);
 /* Launches of ONE lockstep iteration with a product of spmm_launches launches and an applied preconditioner of
  * precond_launches launches.  NONE and JACOBI (precond_launches must be 0): sblas_krylov_multi_launches.  AMG: PCG

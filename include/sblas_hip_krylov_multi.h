@@ -16,8 +16,9 @@ extern "C" {
  * scalars, stopping test and bits.  It is not block CG: the directions never mix.
  *   - methods SBLAS_KRYLOV_PCG and SBLAS_KRYLOV_BICGSTAB; preconditioners SBLAS_PRECOND_NONE and SBLAS_PRECOND_JACOBI
  *     (one dinv vector of n entries, shared by the columns).  ILU(0), AMG and Chebyshev are refused at create
- *     (SBLAS_E_INVALID): ILU(0) and Chebyshev have no multi-column apply, and AMG's -- the block cycle of
- *     sblas_hip_amg_multi.h -- needs its plan, which sblas_hip_krylov_multi_plan_create_ex there takes.
+ *     (SBLAS_E_INVALID): Chebyshev has no multi-column apply, AMG's -- the block cycle of sblas_hip_amg_multi.h -- needs
+ *     its plan, which sblas_hip_krylov_multi_plan_create_ex there takes, and ILU(0)'s -- the two tiled solves of
+ *     sblas_hip_sptrsm_tile.h -- needs its pair of solve plans, which the create declared there takes.
  *   - A X is one call of sblas_hip_spmm_csr_ordered_f64_i32_planned per product, on a plan for width s the solver plan
  *     owns, both orders SBLAS_ROW_MAJOR, alpha 1 and beta 0.  PCG makes one such call an iteration, BiCGStab two.  The
  *     solver takes the SpMM's bits as they come.

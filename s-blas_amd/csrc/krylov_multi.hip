@@ -22,7 +22,8 @@
 // anything else -- the ragged last tile, a mixed tile, an odd leading dimension, a base offset by one element -- goes
 // double by double.  Same values, same order, same bits.
 //
-// An applied preconditioner: a plan seated through create_ex -- the AMG block cycle -- runs between the
+// An applied preconditioner: a plan seated through create_ex -- the AMG block cycle -- or a pair of
+// solve plans seated through create_pair -- ILU(0), the two tiled solves with the second in place -- runs between the
 // solver's kernels where krylov.hip applies M^-1: PCG on R into Z, then the dots (r, z) and the fold that takes rho or
 // beta; BiCGStab on P into P^ and on S into S^.  It runs on ALL columns, into work blocks only and never into X: a
 // frozen column's operand no longer changes, so its result is recomputed to the same bits, and no column of the cycle
@@ -418,10 +419,12 @@ struct MultiPlan {
     const double *val = nullptr, *dinv = nullptr;
     double *x = nullptr;
     int64_t ldx = 0;
-    PrecondSeat pre; // an applied kind's plan (create_ex); NONE and JACOBI live in the kernels here
+    PrecondSeat pre; // an applied kind's plan (create_ex) or pair of plans (create_pair); NONE and JACOBI live in the kernels here
     bool jacobi() const { return precond == SBLAS_PRECOND_JACOBI; }
     bool none() const { return precond == SBLAS_PRECOND_NONE; }
-    bool applied() const { return precond_multi_applied(precond); }
+    bool cycle() const { return precond_multi_applied(precond); } // one plan with a block apply of its own: AMG
+    bool pair() const { return precond_multi_pair(precond); }     // two solve plans: ILU(0) by the tiled solves
+    bool applied() const { return cycle() || pair(); }
     double *w(int k) const { return vec + (size_t)k * (block_bytes / 8); }
     ~MultiPlan()
     {
@@ -510,18 +513,25 @@ int bicgstab_iteration(const MultiPlan *p, hipStream_t st)
 // the bytes an n x s block at leading dimension ld spans
 inline size_t span_bytes(int64_t n, int s, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)s) * 8 : 0; }
 
-// launches of one cycle of the seated plan (an applied kind), else 0
-int64_t precond_cycle_launches(const MultiPlan *p)
+// launches of one iteration without the products': through the rule of the seat's kind
+int64_t iteration_launches(const MultiPlan *p)
 {
+    if (p->pair()) {
+        int64_t lower[12], upper[12];
+        p->pre.info(lower, upper);
+        return sblas_krylov_multi_launches_pair(p->method, p->precond, 0, lower[5], upper[5]);
+    }
     int64_t mi[4] = {0, 0, 0, 0};
-    if (p->applied()) sblas_hip_amg_plan_multi_info(p->pre.lower, mi);
-    return mi[2];
+    if (p->cycle()) sblas_hip_amg_plan_multi_info(p->pre.lower, mi);
+    return sblas_krylov_multi_launches_ex(p->method, p->precond, 0, mi[2]);
 }
 
-// both creates.  precond_plan: the plan of an applied kind (create_ex), which is seated and whose level vectors are
-// reserved for nrhs columns; the work blocks an applied kind writes -- Z, P^ and S^ -- are among the plan's own already.
+// the three creates.  precond_plan: the plan of an applied kind (create_ex), which is seated and whose level vectors are
+// reserved for nrhs columns; upper_plan: with it precond_plan is the lower one of a pair of solve plans (create_pair),
+// seated as PrecondSeat::bind seats the single solver's.  The work blocks an applied kind writes -- Z, P^ and S^ -- are
+// among the plan's own already.
 int create_plan(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, int nrhs, int precond,
-                void *precond_plan, void **plan_out)
+                void *precond_plan, const void *upper_plan, void **plan_out)
 {
     if (!krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
     if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
@@ -531,7 +541,9 @@ int create_plan(int dev, void *stream, int method, int64_t n, int64_t nnz, const
     p->dev = device, p->method = method, p->precond = precond, p->s = nrhs, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
     p->rowptr = rowptr, p->colidx = colidx;
     p->n_blocks = method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS;
-    if (precond_plan) {
+    if (upper_plan) {
+        if (p->pre.bind(precond, precond_plan, upper_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
+    } else if (precond_plan) {
         int64_t info[12];
         if (n == 0 && sblas_hip_amg_plan_info(precond_plan, info) == SBLAS_OK && info[0] == 0) {
             // an empty structure has no content to compare and an empty plan no device memory: it is seated as it is
@@ -631,7 +643,7 @@ int sblas_hip_krylov_multi_plan_create(int dev, void *stream, int method, int64_
     *plan_out = nullptr;
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
     if (!precond_multi(precond)) return SBLAS_E_INVALID; // precond_rule.h: an applied kind needs its plan, which create_ex takes
-    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, precond, nullptr, plan_out);
+    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, precond, nullptr, nullptr, plan_out);
 }
 
 int sblas_hip_krylov_multi_plan_create_ex(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr,
@@ -642,7 +654,17 @@ int sblas_hip_krylov_multi_plan_create_ex(int dev, void *stream, int method, int
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
     // precond_rule.h: a kind that rides in the kernels takes no plan, AMG takes its own, every other kind is refused
     if (precond_multi(precond) ? precond_plan != nullptr : !(precond_multi_applied(precond) && precond_plan)) return SBLAS_E_INVALID;
-    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, precond, precond_plan, plan_out);
+    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, precond, precond_plan, nullptr, plan_out);
+}
+
+int sblas_hip_krylov_multi_plan_create_pair(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr,
+                                            const int32_t *colidx, int nrhs, const void *lower_plan, const void *upper_plan, void **plan_out)
+{
+    if (!plan_out) return SBLAS_E_INVALID;
+    *plan_out = nullptr;
+    if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
+    if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
+    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, SBLAS_PRECOND_ILU0, const_cast<void *>(lower_plan), upper_plan, plan_out);
 }
 
 int sblas_hip_krylov_multi_plan_info(const void *plan, int64_t out[12])
@@ -651,7 +673,7 @@ int sblas_hip_krylov_multi_plan_info(const void *plan, int64_t out[12])
     const MultiPlan *p = static_cast<const MultiPlan *>(plan);
     out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->s, out[5] = p->n_blocks;
     out[6] = (int64_t)p->block_bytes, out[7] = (int64_t)p->partial_bytes, out[8] = (int64_t)p->scalar_bytes, out[9] = (int64_t)p->ws_bytes;
-    out[10] = (int64_t)p->bytes, out[11] = sblas_krylov_multi_launches_ex(p->method, p->precond, 0, precond_cycle_launches(p));
+    out[10] = (int64_t)p->bytes, out[11] = iteration_launches(p);
     return SBLAS_OK;
 }
 
@@ -675,11 +697,12 @@ int sblas_hip_krylov_multi_start(void *plan, void *stream, const double *val, co
         return SBLAS_OK;
     }
     const bool jac = p->jacobi();
-    if (p->applied()) { // the block cycle needs a plan that is set up, with a smoother that has a block form
+    if (p->cycle()) { // the block cycle needs a plan that is set up, with a smoother that has a block form
         int64_t info[12];
         if (sblas_hip_amg_plan_info(p->pre.lower, info) != SBLAS_OK || !info[10] || info[9] == SBLAS_AMG_CHEBYSHEV) return SBLAS_E_INVALID;
     }
     if (!B || !X || (p->nnz > 0 && !val) || (jac && !dinv)) return SBLAS_E_INVALID;
+    if (p->pair() && !p->pre.take(dinv)) return SBLAS_E_INVALID; // dinv carries the factor lu, as the single solver's lu_or_dinv
     if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
     const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
     if (b0 < x0 + span_bytes(p->n, p->s, ldx) && x0 < b0 + span_bytes(p->n, p->s, ldb)) return SBLAS_E_INVALID; // X overlaps B

@@ -48,6 +48,18 @@ int64_t sblas_krylov_multi_launches_ex(int method, int precond, int64_t spmm_lau
     return method == SBLAS_KRYLOV_PCG ? plain + precond_launches + 2 : plain + 2 * precond_launches;
 }
 
+int sblas_krylov_multi_precond_pair_ok(int precond) { return sblas::precond_multi_pair(precond) ? SBLAS_OK : SBLAS_E_INVALID; }
+
+int64_t sblas_krylov_multi_launches_pair(int method, int precond, int64_t spmm_launches, int64_t lower_launches, int64_t upper_launches)
+{
+    if (!sblas::precond_multi_pair(precond) || lower_launches < 0 || upper_launches < 0) return -1;
+    const int64_t plain = sblas_krylov_multi_launches(method, SBLAS_PRECOND_NONE, spmm_launches);
+    if (plain < 0) return -1;
+    // the count with a block cycle seated (above), the two solves' launches in the cycle's place
+    const int64_t apply = lower_launches + upper_launches;
+    return method == SBLAS_KRYLOV_PCG ? plain + apply + 2 : plain + 2 * apply;
+}
+
 int sblas_krylov_multi_grid(int64_t n, int nrhs, int64_t out[4])
 {
     if (!out || n < 0 || !sblas::krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;

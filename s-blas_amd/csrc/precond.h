@@ -78,9 +78,16 @@ struct PrecondSeat {
     }
 
     // OUT = M^-1 IN on n x s row-major blocks, for a kind with a multi-column apply (precond_multi_applied): the AMG block
-    // cycle, whose column j has apply()'s bits on column j.  OUT must not overlap IN.
+    // cycle, or with a pair of solve plans (precond_multi_pair): ILU(0), OUT = L^-1 IN by the tiled solve and then
+    // OUT = U^-1 OUT in place, with the factor start was given.  Column j has apply()'s bits on column j either way.  OUT
+    // must not overlap IN.
     int apply_multi(hipStream_t s, int nrhs, const double *in, int64_t ldin, double *out, int64_t ldout) const
     {
+        if (sblas::precond_multi_pair(kind)) {
+            const int rc = sblas_hip_sptrsm_tiled_f64_i32_planned(lower, s, rowptr, colidx, values, nrhs, 1.0, in, ldin, out, ldout);
+            if (rc != SBLAS_OK) return rc;
+            return sblas_hip_sptrsm_tiled_f64_i32_planned(upper, s, rowptr, colidx, values, nrhs, 1.0, out, ldout, out, ldout);
+        }
         if (kind != SBLAS_PRECOND_AMG) return SBLAS_E_INVALID;
         return sblas_hip_amg_plan_apply_multi(lower, s, nrhs, in, ldin, out, ldout);
     }

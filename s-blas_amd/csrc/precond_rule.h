@@ -20,8 +20,13 @@ inline bool precond_in_place(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 // kind takes a plan: precond_multi_applied.
 inline bool precond_multi(int kind) { return precond_known(kind) && !precond_applied(kind); }
 // serves several right-hand sides at once through a plan of its own with a multi-column apply: the AMG
-// block cycle.  ILU(0) waits on a row-major sptrsm, Chebyshev on a block polynomial of its own.
+// block cycle.  ILU(0) no longer waits on a row-major sptrsm -- the tiled solve is there -- but it is
+// seated as a pair of solve plans, not as one plan: precond_multi_pair.  Chebyshev waits on a block polynomial of its own.
 inline bool precond_multi_applied(int kind) { return kind == SBLAS_PRECOND_AMG; }
+// serves several right-hand sides at once through its PAIR of solve plans (sblas_hip_sptrsm_tile.h's create): ILU(0), as
+// OUT = L^-1 IN by the tiled solve and OUT = U^-1 OUT in place.  Kept apart from precond_multi_applied, whose answers
+// and the refusals of the creates that go by it are pinned.
+inline bool precond_multi_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 // holds two plans, lower and upper; every other applied kind holds one handle in lower's place and no upper
 inline bool precond_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 

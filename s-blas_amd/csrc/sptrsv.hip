@@ -172,6 +172,8 @@ inline int rhs_shift(int64_t nrhs)
 
 } // namespace
 
+#include "sptrsm_tile_kernels.h" // solve_row() over a tile of eight columns, and its two kernels
+
 extern "C" {
 
 int sblas_hip_sptrsv_plan_create(int dev, void *stream, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,
@@ -291,6 +293,38 @@ int sblas_hip_sptrsm_f64_i32_planned(const void *plan, void *stream, const int32
         } else {
             const int64_t first = p->h_level_ptr[q.l0], rows = p->h_level_ptr[q.l1] - first;
             sptrsm_wide_kernel<<<wide_grid(rows << ws, WIDE_THREADS), WIDE_THREADS, 0, s>>>(first, rows, ws, lower, p->desc, colidx, val, nrhs, alpha, B, ldb, X, ldx);
+        }
+    }
+    return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
+}
+
+// The tiled SpSM: the single solve's launches, each widened by ceil(nrhs / 8) tiles.
+int sblas_hip_sptrsm_tiled_f64_i32_planned(const void *plan, void *stream, const int32_t *rowptr, const int32_t *colidx, const double *val,
+                                           int64_t nrhs, double alpha, const double *B, int64_t ldb, double *X, int64_t ldx)
+{
+    const SptrsvPlan *p = static_cast<const SptrsvPlan *>(plan);
+    const int rc = level_plan_speaks_for(p, -1, rowptr, colidx);
+    if (rc != SBLAS_OK) return rc;
+    if (nrhs < 0 || ldb < nrhs || ldx < nrhs) return SBLAS_E_INVALID;
+    if (p->n == 0 || nrhs == 0) return SBLAS_OK;
+    if (!B || !X || (p->nnz > 0 && !val)) return SBLAS_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
+    // every grid is known from the plan: an nrhs whose widest launch would not fit is refused before anything is launched
+    for (const Launch &q : p->sched.launches)
+        if (sptrsm_tile_grid(q.chain ? 1 : p->h_level_unit_ptr[q.l1] - p->h_level_unit_ptr[q.l0], nrhs) < 0) return SBLAS_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const TileSolveArgs a{p->fill == SBLAS_FILL_LOWER, nrhs, p->units, colidx, val, alpha, B, ldb, X, ldx};
+    const bool wide = sptrsm_wide16(B, ldb) && sptrsm_wide16(X, ldx);
+    const unsigned tiles = (unsigned)sptrsm_tiles(nrhs);
+    for (const Launch &q : p->sched.launches) {
+        if (q.chain) {
+            if (wide) sptrsm_tile_chain_kernel<true><<<tiles, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, a);
+            else sptrsm_tile_chain_kernel<false><<<tiles, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, a);
+        } else {
+            const int64_t first = p->h_level_unit_ptr[q.l0], count = p->h_level_unit_ptr[q.l1] - first, blocks = sptrsm_unit_blocks(count);
+            const unsigned grid = (unsigned)sptrsm_tile_grid(count, nrhs);
+            if (wide) sptrsm_tile_wide_kernel<true><<<grid, SPTRSM_WIDE_THREADS, 0, s>>>(first, count, blocks, a);
+            else sptrsm_tile_wide_kernel<false><<<grid, SPTRSM_WIDE_THREADS, 0, s>>>(first, count, blocks, a);
         }
     }
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;

@@ -101,6 +101,12 @@ EXPORTS_AMG_MULTI = [
     "sblas_hip_amg_sweep_multi_f64", "sblas_hip_amg_restrict_multi_f64", "sblas_hip_amg_prolong_multi_f64",
     "sblas_hip_krylov_multi_plan_create_ex",
 ]
+# what include/sblas_hip_sptrsm_tile.h declares (the triangular solve on a block of columns with the single solve's bits, and
+# ILU(0)'s seat under the multi-right-hand-side solvers)
+EXPORTS_SPTRSM_TILE = [
+    "sblas_sptrsm_tile_limits", "sblas_sptrsm_tile_grid", "sblas_krylov_multi_precond_pair_ok", "sblas_krylov_multi_launches_pair",
+    "sblas_hip_sptrsm_tiled_f64_i32_planned", "sblas_hip_krylov_multi_plan_create_pair",
+]
 
 
 class SblasError(RuntimeError):
@@ -564,6 +570,18 @@ def lib():
     L.sblas_hip_amg_prolong_multi_f64.argtypes = [vp, vp, C.c_int, f64, C.c_int, vp, i64, vp, i64]
     L.sblas_hip_krylov_multi_plan_create_ex.restype = C.c_int
     L.sblas_hip_krylov_multi_plan_create_ex.argtypes = [C.c_int, vp, C.c_int, i64, i64, vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
+    L.sblas_sptrsm_tile_limits.restype = C.c_int
+    L.sblas_sptrsm_tile_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_sptrsm_tile_grid.restype = C.c_int
+    L.sblas_sptrsm_tile_grid.argtypes = [i64, i64, C.POINTER(i64)]
+    L.sblas_krylov_multi_precond_pair_ok.restype = C.c_int
+    L.sblas_krylov_multi_precond_pair_ok.argtypes = [C.c_int]
+    L.sblas_krylov_multi_launches_pair.restype = i64
+    L.sblas_krylov_multi_launches_pair.argtypes = [C.c_int, C.c_int, i64, i64, i64]
+    L.sblas_hip_sptrsm_tiled_f64_i32_planned.restype = C.c_int
+    L.sblas_hip_sptrsm_tiled_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, i64, f64, vp, i64, vp, i64]
+    L.sblas_hip_krylov_multi_plan_create_pair.restype = C.c_int
+    L.sblas_hip_krylov_multi_plan_create_pair.argtypes = [C.c_int, vp, C.c_int, i64, i64, vp, vp, C.c_int, vp, vp, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -2184,7 +2202,9 @@ class SptrsvPlan:
     every row needs exactly one.  A bad structure raises an SblasError that names the first bad row (.bad_row).  The plan
     keeps rowptr and colidx alive and solves on them as they are: do not change them.  mode: "auto" (a level above
     chain_rows rows is one launch, a run of narrower levels one single-workgroup launch), "per_level" or "chain";
-    chain_rows=0 takes the default.  solve() allocates nothing inside the library and is graph-capturable.  The
+    chain_rows=0 takes the default.  solve() allocates nothing inside the library and is graph-capturable.
+    solve_multi() is the tiled solve of an (n, nrhs) block (include/sblas_hip_sptrsm_tile.h): column j has exactly the bits
+    of solve() on column j, in solve()'s launches whatever nrhs is; solve()'s own 2-D path keeps its older kernels.  The
     transposed solve: a plan with the opposite `lower` on TransposePlan.csc()'s (colptr, rowidx), solved with its valT."""
 
     def __init__(self, n, rowptr, colidx, lower=True, unit_diag=False, mode="auto", chain_rows=0, stream=None):
@@ -2266,6 +2286,47 @@ class SptrsvPlan:
               "sblas_hip_sptrsm_f64_i32_planned")
         return x
 
+    def solve_multi(self, val, B, X=None, alpha=1.0, stream=None):
+        """X with T X = alpha * B by the tiled solve (sblas_hip_sptrsm_tiled_f64_i32_planned): B an (n, nrhs) float64
+        tensor with strides (ld, 1), and X[:, j] has EXACTLY the bits solve(val, B[:, j]) gives, for every nrhs, leading
+        dimension, alignment and mode.  The 2-D checks and refusals of solve().  X: like B, made here when None; X is B
+        solves in place.  The launches are solve()'s on one right-hand side, whatever nrhs is.  Returns X."""
+        import torch
+        for name, t in (("val", val), ("B", B)) + ((("X", X),) if X is not None else ()):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            if t.dtype != torch.float64:
+                raise SblasError("%s must be float64, got %s" % (name, t.dtype))
+            if t.device != self.device:
+                raise SblasError("%s is on %s, the plan on %s" % (name, t.device, self.device))
+        if not val.is_contiguous() or val.numel() != self.nnz:
+            raise SblasError("val must be contiguous with one value per stored entry (%d), got %d" % (self.nnz, val.numel()))
+        if B.dim() != 2 or B.shape[0] != self.n:
+            raise SblasError("B must be %d x nrhs, got shape %s" % (self.n, tuple(B.shape)))
+        if X is None:
+            X = torch.empty(tuple(B.shape), dtype=torch.float64, device=self.device)
+        if tuple(X.shape) != tuple(B.shape):
+            raise SblasError("X has shape %s, B %s" % (tuple(X.shape), tuple(B.shape)))
+        nrhs = int(B.shape[1])
+        ld = []
+        for name, t in (("B", B), ("X", X)):
+            if self.n > 0 and nrhs > 1 and t.stride(1) != 1:               # without rows there are no strides to read
+                raise SblasError("%s must be row-major (strides (ld, 1)), got strides %s" % (name, tuple(t.stride())))
+            l = int(t.stride(0)) if self.n > 1 else max(nrhs, 1)
+            if l < nrhs:
+                raise SblasError("%s has a leading dimension of %d for %d columns" % (name, l, nrhs))
+            ld.append(max(l, 1))
+        live = self.n > 0 and nrhs > 0
+        if live and X is not B and X.data_ptr() == B.data_ptr() and ld[0] != ld[1]:
+            raise SblasError("in place needs equal leading dimensions, got %d and %d" % (ld[0], ld[1]))
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_sptrsm_tiled_f64_i32_planned(self.handle, _stream(stream), self.rowptr.data_ptr(),
+                                                               self.colidx.data_ptr() if self.nnz else None,
+                                                               val.data_ptr() if self.nnz else None, nrhs, float(alpha),
+                                                               B.data_ptr() if live else None, ld[0], X.data_ptr() if live else None, ld[1]),
+                  "sblas_hip_sptrsm_tiled_f64_i32_planned")
+        return X
+
     def destroy(self):
         if self.handle:
             lib().sblas_hip_sptrsv_plan_destroy(self.handle)
@@ -2276,6 +2337,21 @@ class SptrsvPlan:
             self.destroy()
         except Exception:
             pass
+
+
+def sptrsm_tile_limits():
+    """The tiled SpSM's sizes (sblas_sptrsm_tile_limits): dict(tile, wide_threads, chain_threads, max_grid)."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_sptrsm_tile_limits(out), "sblas_sptrsm_tile_limits")
+    return dict(tile=int(out[0]), wide_threads=int(out[1]), chain_threads=int(out[2]), max_grid=int(out[3]))
+
+
+def sptrsm_tile_grid(units, nrhs):
+    """Workgroups of one wide launch of the tiled SpSM (sblas_sptrsm_tile_grid): dict(unit_blocks, tiles, grid, last_tile);
+    a chain launch is `tiles` workgroups."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_sptrsm_tile_grid(int(units), int(nrhs), out), "sblas_sptrsm_tile_grid")
+    return dict(unit_blocks=int(out[0]), tiles=int(out[1]), grid=int(out[2]), last_tile=int(out[3]))
 
 
 def sptrsv(A, b, lower=True, unit_diag=False, alpha=1.0, stream=None):
@@ -2392,6 +2468,14 @@ class Ilu0Plan:
         lower, upper = self.solvers()
         tmp = lower.solve(lu, r, x=tmp, stream=stream)
         return upper.solve(lu, tmp, x=out, stream=stream)
+
+    def apply_multi(self, lu, R, out=None, stream=None):
+        """out = U^-1 (L^-1 R) on an (n, s) row-major block by the tiled solves (SptrsvPlan.solve_multi), the second one
+        in place: out[:, j] has exactly the bits apply(lu, R[:, j]) gives, and no temporary is needed (out is R: both
+        solves in place).  With out given, and solvers() called before, nothing is allocated."""
+        lower, upper = self.solvers()
+        out = lower.solve_multi(lu, R, X=out, stream=stream)
+        return upper.solve_multi(lu, out, X=out, stream=stream)
 
     def destroy(self):
         if self._solvers is not None:
@@ -3519,29 +3603,40 @@ def krylov_multi_limits():
                 bicgstab_blocks=int(out[5]), max_dots=int(out[6]), block_slots=int(out[7]))
 
 
+def _solver_pair(precond):
+    return isinstance(precond, (tuple, list)) and len(precond) == 2 and all(isinstance(q, SptrsvPlan) for q in precond)
+
+
 def _multi_precond(precond):
     """precond of a multi-right-hand-side plan -> its code; the kinds without a multi-column apply are refused by name.
-    An AmgPlan INSTANCE is taken (its block cycle); the name "amg" carries no plan and stays refused."""
+    An AmgPlan INSTANCE is taken (its block cycle); the name "amg" carries no plan and stays refused.  ILU(0) comes in as
+    the PAIR of SptrsvPlans ilu.solvers() (the tiled solves); an Ilu0Plan instance and the name "ilu0" stay refused."""
     if isinstance(precond, AmgPlan) and lib().sblas_krylov_multi_precond_plan_ok(PRECOND_AMG) == 0:
         return PRECOND_AMG
+    if _solver_pair(precond) and lib().sblas_krylov_multi_precond_pair_ok(PRECOND_ILU0) == 0:
+        return PRECOND_ILU0
     kind = _precond_seat(precond)[0] if not isinstance(precond, str) or precond == "jacobi" else _PRECOND_CODE.get(precond, -1)
     if kind < 0:
         raise SblasError("precond must be None or 'jacobi', not %r" % (precond,))
     if lib().sblas_krylov_multi_precond_ok(kind) != 0:
-        raise SblasError("the %s preconditioner has no multi-column apply: several right-hand sides take None or 'jacobi'"
-                         % _PRECOND_NAME[kind])
+        raise SblasError("the %s preconditioner has no multi-column apply: several right-hand sides take None or 'jacobi'%s"
+                         % (_PRECOND_NAME[kind], ", or ILU(0) as the pair precond=ilu.solvers()" if kind == PRECOND_ILU0 else ""))
     return kind
 
 
 def krylov_multi_launches(method="pcg", precond=None, spmm_launches=0):
     """Launches of one lockstep iteration (sblas_krylov_multi_launches): the solver's own kernels and spmm_launches for
     each product (PCG one, BiCGStab two).  precond an AmgPlan: its block cycles, the dots and the fold that go with them
-    are counted too (sblas_krylov_multi_launches_ex with the plan's cycle)."""
+    are counted too (sblas_krylov_multi_launches_ex with the plan's cycle); a pair of SptrsvPlans (ilu.solvers()): the two
+    solves' launches in the cycle's place (sblas_krylov_multi_launches_pair)."""
     if method not in _KRYLOV_METHOD:
         raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
     kind = _multi_precond(precond)
     if isinstance(precond, AmgPlan):
         n = int(lib().sblas_krylov_multi_launches_ex(_KRYLOV_METHOD[method], kind, int(spmm_launches), precond.multi_info()["launches"]))
+    elif _solver_pair(precond):
+        n = int(lib().sblas_krylov_multi_launches_pair(_KRYLOV_METHOD[method], kind, int(spmm_launches), precond[0].info()["launches"],
+                                                       precond[1].info()["launches"]))
     else:
         n = int(lib().sblas_krylov_multi_launches(_KRYLOV_METHOD[method], kind, int(spmm_launches)))
     if n < 0:
@@ -3682,8 +3777,12 @@ class KrylovMultiPlan:
     setup() with "jacobi" or "l1" (sblas_hip_krylov_multi_plan_create_ex): its block cycle runs on all columns where the
     single solver applies the cycle, column j with exactly AmgPlan.apply's bits; the solver reserves the plan's level
     vectors for nrhs columns, keeps the plan alive and takes no dinv.  Two solvers seated on one AmgPlan share its level
-    vectors, as two single solvers do: do not run them at the same time.  ILU(0) and Chebyshev have no multi-column
-    apply and are refused, and so are the NAMES "ilu0", "amg" and "chebyshev", which carry no plan.  B and X are (n, nrhs) float64 GPU tensors, row-major: contiguous, or a column
+    vectors, as two single solvers do: do not run them at the same time.  ILU(0) is seated as the PAIR of SptrsvPlans
+    (lower, upper) that ilu.solvers() returns, the form KrylovPlan already accepts (sblas_hip_krylov_multi_plan_create_pair):
+    M^-1 is the two tiled solves (SptrsvPlan.solve_multi, the second in place), column j with exactly Ilu0Plan.apply's
+    bits; start / solve then take lu, the factor, and the solver keeps the two plans alive.  This door is the pair because
+    the older refusals are pinned: an Ilu0Plan INSTANCE, a ChebyshevPlan, and the NAMES "ilu0", "amg" and "chebyshev",
+    which carry no plan, stay refused as having no multi-column apply.  B and X are (n, nrhs) float64 GPU tensors, row-major: contiguous, or a column
     slice of a wider tensor.  The plan owns an SpMM plan for this width, its workspace, the work blocks, the partial sums
     and one scalar block a column, and keeps the structure tensors alive.
 
@@ -3714,6 +3813,16 @@ class KrylovMultiPlan:
                 rc = lib().sblas_hip_krylov_multi_plan_create_ex(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
                                                                  colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind,
                                                                  precond.handle, C.byref(h))
+            elif self.precond_kind == PRECOND_ILU0:                         # the pair of solve plans; self.precond keeps them alive
+                for q in precond:
+                    if q.n != n or q.rowptr.data_ptr() != rowptr.data_ptr() or q.colidx.data_ptr() != colidx.data_ptr():
+                        raise SblasError("the SptrsvPlans were made for another structure than this solver's (rowptr, colidx)")
+                if not (precond[0].lower and precond[0].unit_diag and not precond[1].lower and not precond[1].unit_diag):
+                    raise SblasError("the pair must be (lower with a unit diagonal, upper with a stored one), as Ilu0Plan.solvers() gives it")
+                name = "sblas_hip_krylov_multi_plan_create_pair"
+                rc = lib().sblas_hip_krylov_multi_plan_create_pair(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                                   colidx.data_ptr() if self.nnz else None, self.nrhs, precond[0].handle,
+                                                                   precond[1].handle, C.byref(h))
             else:
                 name = "sblas_hip_krylov_multi_plan_create"
                 rc = lib().sblas_hip_krylov_multi_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
@@ -3728,9 +3837,10 @@ class KrylovMultiPlan:
                     precond=_PRECOND_NAME[out[3]], nrhs=int(out[4]), blocks=int(out[5]), block_bytes=int(out[6]), partial_bytes=int(out[7]),
                     scalar_bytes=int(out[8]), workspace_bytes=int(out[9]), bytes=int(out[10]), launches=int(out[11]))
 
-    def start(self, val, B, X, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
+    def start(self, val, B, X, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None, lu=None):
         """Begins a solve: X on entry holds the initial guesses and is updated in place by iterate().  dinv: the inverse
-        diagonal (precond "jacobi").  Every refusal comes before any launch."""
+        diagonal (precond "jacobi"); lu: the ILU(0) factor (precond a pair of SptrsvPlans).  Every refusal comes before
+        any launch."""
         import torch
         _krylov_vector("val", val, self.nnz, self.device)
         ldb = _krylov_block("B", B, self.n, self.nrhs, self.device)
@@ -3741,6 +3851,11 @@ class KrylovMultiPlan:
                 raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
             _krylov_vector("dinv", dinv, self.n, self.device)
             pre = dinv
+        elif self.precond_kind == PRECOND_ILU0:
+            if lu is None:
+                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
+            _krylov_vector("lu", lu, self.nnz, self.device)
+            pre = lu
         elif self.precond_kind == PRECOND_AMG:
             info = self.precond.info()
             if not info["ready"]:
@@ -3779,7 +3894,7 @@ class KrylovMultiPlan:
                     beta=a[:, 5].copy(), omega=a[:, 6].copy(), which=which, status=[KRYLOV_STATUS[int(c)] for c in code],
                     breakdown=[KRYLOV_DENOM[int(w)] for w in which], running=int((code == KRYLOV_RUNNING).sum()))
 
-    def solve(self, val, B, X=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
+    def solve(self, val, B, X=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None, lu=None):
         """start(), then iterate(check_every) / status() until no column is running -> (X, status dict).  X: the initial
         guesses, updated in place (zeros made here when None).  No column's result depends on check_every."""
         import torch
@@ -3788,7 +3903,7 @@ class KrylovMultiPlan:
         if X is None:
             _krylov_block("B", B, self.n, self.nrhs, self.device)
             X = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=self.device)
-        self.start(val, B, X, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
+        self.start(val, B, X, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream, lu=lu)
         while True:
             self.iterate(int(check_every), stream=stream)
             st = self.status(stream=stream)
@@ -3812,7 +3927,9 @@ def _krylov_multi_one_shot(method, A, B, precond, X, kw):
     import torch
     n, rowptr, colidx, val = A
     one_shot_amg = isinstance(precond, str) and precond in ("amg", "amg_smoothed")
-    kind = PRECOND_AMG if one_shot_amg else _multi_precond(precond)
+    if _solver_pair(precond):                                               # a pair needs its factor at start: the plan's door
+        raise SblasError("the one-shots take no pair of solve plans: use KrylovMultiPlan(..., precond=ilu.solvers()).solve(..., lu=lu)")
+    kind =PRECOND_AMG if one_shot_amg else _multi_precond(precond)
     if not isinstance(B, torch.Tensor) or B.dim() != 2:
         raise SblasError("B must be an (n, nrhs) GPU tensor")
     ilu = plan = dinv = amg = None
