@@ -43,8 +43,8 @@
 // estimate where it ran the level's wd kernel.  Its buffers are made by a plan's first such setup, never by any other.
 //
 // The block cycle (sblas_hip_amg_plan_apply_multi) is the same walk on n x s row-major blocks: a second
-// Ops of amg_cycle whose launches are amg_multi_kernels.h's, the kernels above widened by a tile of eight columns.  Column
-// j of its result has the bits of apply() on column j.  Its level vectors are made by sblas_hip_amg_plan_reserve_multi,
+// Ops of amg_cycle whose launches are amg_multi_kernels.h's: sweep_row() and transfer_row() eight columns abreast.
+// Column j of its result has the bits of apply() on column j.  Its level vectors are made by sblas_hip_amg_plan_reserve_multi,
 // never by any other call; a plan that never reserves keeps its bytes.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -61,6 +61,7 @@
 #include "krylov.h"
 #include "level_kernels.h"
 #include "rowwise.h"
+#include "unit_row.h"
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings; the row sum calls the fused one by name
 
@@ -68,11 +69,6 @@ using namespace sblas;
 
 namespace {
 
-// four lanes of a sweep launch (level_plan.h); q: the unit's number in its row; a pad has row = -1
-struct Unit {
-    int32_t row, beg, end, q;
-};
-constexpr Unit NO_UNIT{-1, 0, 0, 0};
 constexpr unsigned long long FLAG_CLEAN = ~0ull;
 
 enum { MODE_SWEEP = 0, MODE_RESIDUAL = 1, MODE_FIRST = 2 };
@@ -80,27 +76,20 @@ enum { MODE_SWEEP = 0, MODE_RESIDUAL = 1, MODE_FIRST = 2 };
 // Row u.row of y.  Every lane of the wave calls this together (the butterfly moves data between lanes); `quad` is the
 // lane's place in its unit.  x and y are distinct arrays: other rows gather x while this one writes y.
 template <int MODE>
-__device__ __forceinline__ void sweep_row(const Unit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val,
+__device__ __forceinline__ void sweep_row(const SweepUnit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val,
                                           const double *__restrict__ wd, const double *__restrict__ b, const double *__restrict__ x,
                                           double *__restrict__ y)
 {
-    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg), G = 1 << gs;
+    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg);
     const int lane = 4 * u.q + quad; // the lane's place among the row's G lanes
     const bool writer = u.row >= 0 && lane == 0;
     // what the row's last step needs travels with its first entries instead of waiting behind the fold
     const double bi = writer ? b[u.row] : 0.0;
     const double xi = writer && MODE == MODE_SWEEP ? x[u.row] : 0.0;
     const double wi = writer && MODE == MODE_SWEEP ? wd[u.row] : 0.0;
-    double s = 0.0;
-    if (u.row >= 0)
-        for (int64_t e = (int64_t)u.beg + lane; e < u.end; e += G) s = __builtin_fma(val[e], x[colidx[e]], s);
-    const double f4 = fold_sum<4>(s);
-    double f16 = f4 + lane_partner<4>(f4);
-    f16 += lane_partner<8>(f16);
-    double f64 = f16 + lane_partner<16>(f16);
-    f64 += lane_partner<32>(f64);
+    const double si = unit_row_sum(u.row >= 0, u.beg, u.end, lane, gs, colidx, val, x);
     if (writer) {
-        const double d = bi - (gs == 2 ? f4 : gs == 4 ? f16 : f64);
+        const double d = bi - si;
         if constexpr (MODE == MODE_RESIDUAL) {
             y[u.row] = d;
         } else {
@@ -111,12 +100,12 @@ __device__ __forceinline__ void sweep_row(const Unit u, int quad, const int32_t 
 }
 
 template <int MODE>
-__global__ __launch_bounds__(AMG_THREADS) void amg_sweep_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ colidx,
+__global__ __launch_bounds__(AMG_THREADS) void amg_sweep_kernel(int64_t count, const SweepUnit *__restrict__ units, const int32_t *__restrict__ colidx,
                                                                 const double *__restrict__ val, const double *__restrict__ wd,
                                                                 const double *__restrict__ b, const double *__restrict__ x,
                                                                 double *__restrict__ y)
 {
-    sweep_row<MODE>(wide_unit<AMG_THREADS>(0, count, units, NO_UNIT), threadIdx.x & 3, colidx, val, wd, b, x, y);
+    sweep_row<MODE>(wide_unit<AMG_THREADS>(0, count, units, NO_SWEEP_UNIT), threadIdx.x & 3, colidx, val, wd, b, x, y);
 }
 
 // the first sweep from a zero guess: the row sums vanish, x_i + wd_i (b_i - 0) is wd_i b_i
@@ -151,23 +140,15 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_prolong_kernel(int64_t n, con
 // Row u.row of a transfer operator M (R_l or P_l) times `in`, sweep_row's row sum.  Every lane of the wave calls this
 // together.  `out` is never gathered: the prolongation updates it in place.
 template <int MODE>
-__device__ __forceinline__ void transfer_row(const Unit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val, double scale,
-                                             const double *__restrict__ in, double *__restrict__ out)
+__device__ __forceinline__ void transfer_row(const SweepUnit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val,
+                                             double scale, const double *__restrict__ in, double *__restrict__ out)
 {
-    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg), G = 1 << gs;
+    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg);
     const int lane = 4 * u.q + quad;
     const bool writer = u.row >= 0 && lane == 0;
     const double xi = writer && MODE == AMG_PROLONG ? out[u.row] : 0.0; // travels with the first entries, as in sweep_row
-    double s = 0.0;
-    if (u.row >= 0)
-        for (int64_t e = (int64_t)u.beg + lane; e < u.end; e += G) s = __builtin_fma(val[e], in[colidx[e]], s);
-    const double f4 = fold_sum<4>(s);
-    double f16 = f4 + lane_partner<4>(f4);
-    f16 += lane_partner<8>(f16);
-    double f64 = f16 + lane_partner<16>(f16);
-    f64 += lane_partner<32>(f64);
+    const double si = unit_row_sum(u.row >= 0, u.beg, u.end, lane, gs, colidx, val, in);
     if (writer) {
-        const double si = gs == 2 ? f4 : gs == 4 ? f16 : f64;
         if constexpr (MODE == AMG_RESTRICT) {
             out[u.row] = si;
         } else {
@@ -178,19 +159,19 @@ __device__ __forceinline__ void transfer_row(const Unit u, int quad, const int32
 }
 
 template <int MODE>
-__global__ __launch_bounds__(AMG_THREADS) void amg_transfer_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ colidx,
-                                                                   const double *__restrict__ val, double scale, const double *__restrict__ in,
-                                                                   double *__restrict__ out)
+__global__ __launch_bounds__(AMG_THREADS) void amg_transfer_kernel(int64_t count, const SweepUnit *__restrict__ units,
+                                                                   const int32_t *__restrict__ colidx, const double *__restrict__ val, double scale,
+                                                                   const double *__restrict__ in, double *__restrict__ out)
 {
-    transfer_row<MODE>(wide_unit<AMG_THREADS>(0, count, units, NO_UNIT), threadIdx.x & 3, colidx, val, scale, in, out);
+    transfer_row<MODE>(wide_unit<AMG_THREADS>(0, count, units, NO_SWEEP_UNIT), threadIdx.x & 3, colidx, val, scale, in, out);
 }
 
 // t for every stored entry of A_l, over the sweep's units: the row's G(p) lanes take the entries l, l + G, ...; every lane
 // forms q_i itself (one address a row).  No lane talks to another, so a pad's lanes leave at once.
-__global__ __launch_bounds__(AMG_THREADS) void amg_pvalues_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ dpos,
+__global__ __launch_bounds__(AMG_THREADS) void amg_pvalues_kernel(int64_t count, const SweepUnit *__restrict__ units, const int32_t *__restrict__ dpos,
                                                                   const double *__restrict__ val, double omega_p, double *__restrict__ t)
 {
-    const Unit u = wide_unit<AMG_THREADS>(0, count, units, NO_UNIT);
+    const SweepUnit u = wide_unit<AMG_THREADS>(0, count, units, NO_SWEEP_UNIT);
     if (u.row < 0) return;
     const int G = 1 << sptrsv_group_shift((int64_t)u.end - u.beg);
     const int lane = 4 * u.q + (threadIdx.x & 3);
@@ -262,7 +243,7 @@ inline unsigned grid_of(int64_t threads) { return (unsigned)((threads + AMG_THRE
 
 } // namespace
 
-#include "amg_multi_kernels.h" // the kernels above on a tile of columns: after Unit, the modes and contract(off)
+#include "amg_multi_kernels.h" // the kernels above on a tile of columns: after the modes, the row functions and contract(off)
 
 namespace {
 
@@ -272,7 +253,7 @@ struct AmgLevel {
     const double *val = nullptr;                        // level 0: setup's; below: own_val
     void *coo = nullptr;                                // the plan that makes level l + 1's structure and values
     DeviceBuffer ibuf, dbuf;                            // units | dpos | agg | aggptr | members;  wd | x0 | x1 | res | b | val
-    Unit *d_units = nullptr;
+    SweepUnit *d_units = nullptr;
     int32_t *dpos = nullptr, *agg = nullptr, *aggptr = nullptr, *members = nullptr;
     double *wd = nullptr, *x[2] = {nullptr, nullptr}, *res = nullptr, *b = nullptr, *own_val = nullptr;
     size_t bytes = 0;
@@ -281,7 +262,7 @@ struct AmgLevel {
     int64_t nnz_p = 0, nnz_ap = 0, p_units = 0, r_units = 0;
     const int32_t *p_rowptr = nullptr, *p_colidx = nullptr;                 // the COO plan's
     int32_t *r_rowptr = nullptr, *r_colidx = nullptr, *r_perm = nullptr; // tbuf: r_rowptr | r_colidx | r_perm | P's units | R's units
-    Unit *d_p_units = nullptr, *d_r_units = nullptr;
+    SweepUnit *d_p_units = nullptr, *d_r_units = nullptr;
     double *p_val = nullptr, *r_val = nullptr, *ap_val = nullptr;           // tval: p_val | r_val | ap_val
     DeviceBuffer tbuf, ubuf, tval;
     // the Chebyshev smoother's, made by the plan's first such setup: d | the scalar block with the table | the dots' partials
@@ -413,7 +394,7 @@ void launch_sweep_multi(hipStream_t st, const AmgLevel &L, int mode, int s, Blk 
         return;
     }
     if (L.units == 0) return;
-    const SweepMultiArgs a{L.units, amg_multi_unit_blocks(L.units), s, L.d_units, L.colidx, L.val, L.wd, b.p, x.p, y, b.ld, x.ld, ldy};
+    const SweepMultiArgs a{L.units, unit_blocks(L.units, AMG_UNITS_PER_BLOCK), s, L.d_units, L.colidx, L.val, L.wd, b.p, x.p, y, b.ld, x.ld, ldy};
     if (mode == MODE_RESIDUAL) launch_sweep_multi_mode<MODE_RESIDUAL>(st, a);
     else launch_sweep_multi_mode<MODE_SWEEP>(st, a);
 }
@@ -423,7 +404,7 @@ void launch_restrict_multi(hipStream_t st, const AmgPlan &p, const AmgLevel &L, 
     if (p.smoothed()) {
         if (L.r_units == 0) return;
         launch_transfer_multi_mode<AMG_RESTRICT>(
-            st, TransferMultiArgs{L.r_units, amg_multi_unit_blocks(L.r_units), s, L.d_r_units, L.r_colidx, L.r_val, 0.0, res.p, bc, res.ld, ldc});
+            st, TransferMultiArgs{L.r_units, unit_blocks(L.r_units, AMG_UNITS_PER_BLOCK), s, L.d_r_units, L.r_colidx, L.r_val, 0.0, res.p, bc, res.ld, ldc});
     } else {
         amg_restrict_multi_kernel<<<grid_of(L.n_coarse * s), AMG_THREADS, 0, st>>>(L.n_coarse, s, L.aggptr, L.members, res.p, res.ld, bc, ldc);
     }
@@ -434,7 +415,7 @@ void launch_prolong_multi(hipStream_t st, const AmgPlan &p, const AmgLevel &L, i
     if (p.smoothed()) {
         if (L.p_units == 0) return;
         launch_transfer_multi_mode<AMG_PROLONG>(
-            st, TransferMultiArgs{L.p_units, amg_multi_unit_blocks(L.p_units), s, L.d_p_units, L.p_colidx, L.p_val, scale, e.p, x, e.ld, ldx});
+            st, TransferMultiArgs{L.p_units, unit_blocks(L.p_units, AMG_UNITS_PER_BLOCK), s, L.d_p_units, L.p_colidx, L.p_val, scale, e.p, x, e.ld, ldx});
     } else {
         amg_prolong_multi_kernel<<<grid_of(L.n * s), AMG_THREADS, 0, st>>>(L.n, s, L.agg, scale, e.p, e.ld, x, ldx);
     }
@@ -473,6 +454,14 @@ bool blocks_overlap(const double *a, int64_t na, int64_t lda, const double *b, i
 }
 // a block argument of a multi-column entry: present, 8-byte aligned, ld >= s
 bool block_ok(const double *p, int64_t ld, int s) { return p && ld >= s && (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+// every row kernel of the level at s columns fits a launch: false where tile_grid() refuses
+bool multi_grids_ok(const AmgLevel &L, int s)
+{
+    for (const int64_t units : {L.units, L.r_units, L.p_units})
+        if (tile_grid(unit_blocks(units, AMG_UNITS_PER_BLOCK), s) < 0) return false;
+    return true;
+}
 
 // the plan's level `level` for a single-kernel entry, or null
 const AmgLevel *level_of(const void *plan, int level, bool need_setup)
@@ -656,9 +645,9 @@ int sblas_hip_amg_plan_create_dev(int dev, void *stream, int64_t n, int64_t nnz,
         // the rows packed as one wide level of a solve
         std::vector<int32_t> zero_level((size_t)nl, 0);
         LevelOrder o;
-        std::vector<Unit> units;
-        const auto unit_of = [&](int32_t i, int32_t q) { return Unit{i, h_rowptr[(size_t)i], h_rowptr[(size_t)i + 1], q}; };
-        level_pack(nl, h_rowptr.data(), zero_level.data(), 1, unit_of, NO_UNIT, o, units);
+        std::vector<SweepUnit> units;
+        const auto unit_of = [&](int32_t i, int32_t q) { return SweepUnit{i, h_rowptr[(size_t)i], h_rowptr[(size_t)i + 1], q}; };
+        level_pack(nl, h_rowptr.data(), zero_level.data(), 1, unit_of, NO_SWEEP_UNIT, o, units);
         L->units = (int64_t)units.size();
         Segment seg[5] = {Segment(units), Segment(dpos), Segment(agg), Segment(aggptr), Segment(members)};
         size_t ib = 0;
@@ -679,7 +668,7 @@ int sblas_hip_amg_plan_create_dev(int dev, void *stream, int64_t n, int64_t nnz,
             if (e == hipSuccess) e = hipStreamSynchronize(s); // the host vector of the units is read until here
             if (e != hipSuccess) return SBLAS_E_HIP;
         } else if (upload_segments(L->ibuf, p->dev, s, seg, last ? 2 : 5, &ib) != hipSuccess) return SBLAS_E_HIP; // the coarsest has no aggregates
-        L->d_units = L->ibuf.at<Unit>(), L->dpos = L->ibuf.at<int32_t>(seg[1].offset);
+        L->d_units = L->ibuf.at<SweepUnit>(), L->dpos = L->ibuf.at<int32_t>(seg[1].offset);
         if (!last) L->agg = L->ibuf.at<int32_t>(seg[2].offset), L->aggptr = L->ibuf.at<int32_t>(seg[3].offset), L->members = L->ibuf.at<int32_t>(seg[4].offset);
         // doubles: wd | x0 | x1 (below level 0) | res (above the coarsest) | b, val (below level 0)
         const size_t vec = ((size_t)nl * 8 + 255) / 256 * 256, vals = ((size_t)nnzl * 8 + 255) / 256 * 256;
@@ -728,16 +717,16 @@ int sblas_hip_amg_plan_create_dev(int dev, void *stream, int64_t n, int64_t nnz,
                 return SBLAS_E_HIP;
             std::vector<int32_t> zero_p((size_t)nl, 0), zero_r((size_t)nc, 0);
             LevelOrder op, orr;
-            std::vector<Unit> p_units, r_units;
-            const auto p_unit = [&](int32_t i, int32_t q) { return Unit{i, hp_rowptr[(size_t)i], hp_rowptr[(size_t)i + 1], q}; };
-            const auto r_unit = [&](int32_t i, int32_t q) { return Unit{i, hr_rowptr[(size_t)i], hr_rowptr[(size_t)i + 1], q}; };
-            level_pack(nl, hp_rowptr.data(), zero_p.data(), 1, p_unit, NO_UNIT, op, p_units);
-            level_pack(nc, hr_rowptr.data(), zero_r.data(), 1, r_unit, NO_UNIT, orr, r_units);
+            std::vector<SweepUnit> p_units, r_units;
+            const auto p_unit = [&](int32_t i, int32_t q) { return SweepUnit{i, hp_rowptr[(size_t)i], hp_rowptr[(size_t)i + 1], q}; };
+            const auto r_unit = [&](int32_t i, int32_t q) { return SweepUnit{i, hr_rowptr[(size_t)i], hr_rowptr[(size_t)i + 1], q}; };
+            level_pack(nl, hp_rowptr.data(), zero_p.data(), 1, p_unit, NO_SWEEP_UNIT, op, p_units);
+            level_pack(nc, hr_rowptr.data(), zero_r.data(), 1, r_unit, NO_SWEEP_UNIT, orr, r_units);
             L->p_units = (int64_t)p_units.size(), L->r_units = (int64_t)r_units.size();
             Segment useg[2] = {Segment(p_units), Segment(r_units)};
             size_t ub = 0;
             if (upload_segments(L->ubuf, p->dev, s, useg, 2, &ub) != hipSuccess) return SBLAS_E_HIP;
-            L->d_p_units = L->ubuf.at<Unit>(), L->d_r_units = L->ubuf.at<Unit>(useg[1].offset);
+            L->d_p_units = L->ubuf.at<SweepUnit>(), L->d_r_units = L->ubuf.at<SweepUnit>(useg[1].offset);
             // the products' plans: A_l P_l, then R_l (A_l P_l); a product too large for int32 is refused there
             rc = sblas_hip_spgemm_plan_create(p->dev, s, nl, nl, nc, d_rowptr, d_colidx, L->p_rowptr, L->p_colidx, SBLAS_SPGEMM_AUTO, 0, &L->ap);
             if (rc != SBLAS_OK) return rc;
@@ -1072,6 +1061,8 @@ int sblas_hip_amg_plan_apply_multi(const void *plan, void *stream, int nrhs, con
     if (nrhs > p->multi_width) return SBLAS_E_WORKSPACE;
     if (p->n == 0) return SBLAS_OK;
     if (!block_ok(R, ldr, nrhs) || !block_ok(Z, ldz, nrhs) || blocks_overlap(R, p->n, ldr, Z, p->n, ldz, nrhs)) return SBLAS_E_INVALID;
+    for (const auto &L : p->lv)
+        if (!multi_grids_ok(*L, nrhs)) return SBLAS_E_INVALID;
     MultiOps ops{p, (hipStream_t)stream, nrhs, Blk{R, ldr}, Z, ldz};
     amg_cycle(p->levels(), p->nu, p->coarse_sweeps, ops, 0, 0);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
@@ -1087,6 +1078,7 @@ int sblas_hip_amg_sweep_multi_f64(const void *plan, void *stream, int level, int
     if (L->n == 0) return SBLAS_OK;
     if (!block_ok(B, ldb, nrhs) || !block_ok(Y, ldy, nrhs) || blocks_overlap(B, L->n, ldb, Y, L->n, ldy, nrhs)) return SBLAS_E_INVALID;
     if (!first && (!block_ok(X, ldx, nrhs) || blocks_overlap(X, L->n, ldx, Y, L->n, ldy, nrhs))) return SBLAS_E_INVALID;
+    if (!multi_grids_ok(*L, nrhs)) return SBLAS_E_INVALID;
     launch_sweep_multi((hipStream_t)stream, *L, mode, nrhs, Blk{B, ldb}, Blk{first ? nullptr : X, first ? 0 : ldx}, Y, ldy);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }
@@ -1097,7 +1089,7 @@ int sblas_hip_amg_restrict_multi_f64(const void *plan, void *stream, int level, 
     const AmgPlan *p = static_cast<const AmgPlan *>(plan);
     if (!L || L->n_coarse == 0 || !amg_multi_width_ok(nrhs) || !block_ok(RES, ldr, nrhs) || !block_ok(BC, ldc, nrhs)) return SBLAS_E_INVALID;
     if (p->smoothed() && !p->ready) return SBLAS_E_INVALID; // R's values are setup's
-    if (blocks_overlap(RES, L->n, ldr, BC, L->n_coarse, ldc, nrhs)) return SBLAS_E_INVALID;
+    if (blocks_overlap(RES, L->n, ldr, BC, L->n_coarse, ldc, nrhs) || !multi_grids_ok(*L, nrhs)) return SBLAS_E_INVALID;
     launch_restrict_multi((hipStream_t)stream, *p, *L, nrhs, Blk{RES, ldr}, BC, ldc);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }
@@ -1109,7 +1101,7 @@ int sblas_hip_amg_prolong_multi_f64(const void *plan, void *stream, int level, d
     const AmgPlan *p = static_cast<const AmgPlan *>(plan);
     if (!L || L->n_coarse == 0 || !amg_multi_width_ok(nrhs) || !block_ok(E, lde, nrhs) || !block_ok(X, ldx, nrhs)) return SBLAS_E_INVALID;
     if (p->smoothed() && !p->ready) return SBLAS_E_INVALID; // P's values are setup's
-    if (blocks_overlap(E, L->n_coarse, lde, X, L->n, ldx, nrhs)) return SBLAS_E_INVALID;
+    if (blocks_overlap(E, L->n_coarse, lde, X, L->n, ldx, nrhs) || !multi_grids_ok(*L, nrhs)) return SBLAS_E_INVALID;
     launch_prolong_multi((hipStream_t)stream, *p, *L, nrhs, scale, Blk{E, lde}, X, ldx);
     return hipGetLastError() == hipSuccess ? SBLAS_OK : SBLAS_E_HIP;
 }

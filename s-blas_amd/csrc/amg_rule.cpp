@@ -369,15 +369,15 @@ int sblas_amg_limits(int64_t out[8])
 int sblas_amg_multi_limits(int64_t out[4])
 {
     if (!out) return SBLAS_E_INVALID;
-    out[0] = SBLAS_AMG_MULTI_MAX_RHS, out[1] = AMG_MULTI_TILE, out[2] = AMG_THREADS, out[3] = 0;
+    out[0] = SBLAS_AMG_MULTI_MAX_RHS, out[1] = TILE, out[2] = AMG_THREADS, out[3] = 0;
     return SBLAS_OK;
 }
 
 int sblas_amg_multi_grid(int64_t units, int nrhs, int64_t out[4])
 {
     if (!out || units < 0 || !amg_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
-    out[0] = amg_multi_unit_blocks(units), out[1] = amg_multi_tiles(nrhs), out[2] = out[0] * out[1];
-    out[3] = nrhs - (int)(out[1] - 1) * AMG_MULTI_TILE;
+    out[0] = unit_blocks(units, AMG_UNITS_PER_BLOCK), out[1] = tiles(nrhs), out[2] = out[0] * out[1];
+    out[3] = nrhs - (int)(out[1] - 1) * TILE;
     return SBLAS_OK;
 }
 

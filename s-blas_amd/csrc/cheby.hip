@@ -37,6 +37,7 @@
 #include "color.h"
 #include "level_kernels.h"
 #include "rowwise.h"
+#include "unit_row.h"
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings; the row sum calls the fused one by name
 
@@ -46,12 +47,6 @@ using namespace sblas;
 
 namespace {
 
-// four lanes of a launch (level_plan.h), amg.hip's record; q: the unit's number in its row; a pad has row = -1
-struct Unit {
-    int32_t row, beg, end, q;
-};
-constexpr Unit NO_UNIT{-1, 0, 0, 0};
-
 enum { MODE_PRODUCT = 0, MODE_FROM_GUESS = 1, MODE_STEP = 2 };
 enum { FOLD_START = 0, FOLD_PQ = 1, FOLD_RZ = 2 };
 
@@ -59,11 +54,11 @@ enum { FOLD_START = 0, FOLD_PQ = 1, FOLD_RZ = 2 };
 // is the lane's place in its unit.  x and y are distinct arrays: other rows gather x while this one writes y.  d is read
 // and written by its own row's writer alone.  coef: (c1_k, c2_k) of this step, one uniform address.
 template <int MODE>
-__device__ __forceinline__ void cheby_row(const Unit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val,
+__device__ __forceinline__ void cheby_row(const SweepUnit u, int quad, const int32_t *__restrict__ colidx, const double *__restrict__ val,
                                           const double *__restrict__ dinv, const double *__restrict__ coef, const double *__restrict__ b,
                                           const double *__restrict__ x, double *__restrict__ d, double *__restrict__ y)
 {
-    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg), G = 1 << gs;
+    const int gs = sptrsv_group_shift((int64_t)u.end - u.beg);
     const int lane = 4 * u.q + quad; // the lane's place among the row's G lanes
     const bool writer = u.row >= 0 && lane == 0;
     // what the row's last step needs travels with its first entries instead of waiting behind the fold
@@ -73,16 +68,8 @@ __device__ __forceinline__ void cheby_row(const Unit u, int quad, const int32_t 
     const double wi = writer && poly ? dinv[u.row] : 0.0;
     const double di = writer && MODE == MODE_STEP ? d[u.row] : 0.0;
     const double c1 = MODE == MODE_STEP ? coef[0] : 0.0, c2 = poly ? coef[1] : 0.0;
-    double s = 0.0;
-    if (u.row >= 0)
-        for (int64_t e = (int64_t)u.beg + lane; e < u.end; e += G) s = __builtin_fma(val[e], x[colidx[e]], s);
-    const double f4 = fold_sum<4>(s);
-    double f16 = f4 + lane_partner<4>(f4);
-    f16 += lane_partner<8>(f16);
-    double f64 = f16 + lane_partner<16>(f16);
-    f64 += lane_partner<32>(f64);
+    const double si = unit_row_sum(u.row >= 0, u.beg, u.end, lane, gs, colidx, val, x);
     if (writer) {
-        const double si = gs == 2 ? f4 : gs == 4 ? f16 : f64;
         if constexpr (MODE == MODE_PRODUCT) {
             y[u.row] = si;
         } else {
@@ -101,7 +88,7 @@ __device__ __forceinline__ void cheby_row(const Unit u, int quad, const int32_t 
 
 // status: the estimate's word (PRODUCT only): anything but RUNNING and the launch returns at entry, block-uniform
 template <int MODE>
-__global__ __launch_bounds__(CHEBY_THREADS) void cheby_step_kernel(int64_t count, const Unit *__restrict__ units, const int32_t *__restrict__ colidx,
+__global__ __launch_bounds__(CHEBY_THREADS) void cheby_step_kernel(int64_t count, const SweepUnit *__restrict__ units, const int32_t *__restrict__ colidx,
                                                                    const double *__restrict__ val, const double *__restrict__ dinv,
                                                                    const double *__restrict__ coef, const long long *__restrict__ status,
                                                                    const double *__restrict__ b, const double *__restrict__ x,
@@ -109,7 +96,7 @@ __global__ __launch_bounds__(CHEBY_THREADS) void cheby_step_kernel(int64_t count
 {
     if constexpr (MODE == MODE_PRODUCT)
         if (status[CS_STATUS] != CHEBY_RUNNING) return;
-    cheby_row<MODE>(wide_unit<CHEBY_THREADS>(0, count, units, NO_UNIT), threadIdx.x & 3, colidx, val, dinv, coef, b, x, d, y);
+    cheby_row<MODE>(wide_unit<CHEBY_THREADS>(0, count, units, NO_SWEEP_UNIT), threadIdx.x & 3, colidx, val, dinv, coef, b, x, d, y);
 }
 
 // step 0 from a zero guess: the row sums vanish, d_i = c2_0 (dinv_i b_i) and x_i = d_i
@@ -274,7 +261,7 @@ template <int MODE>
 void launch_step(hipStream_t s, const ChebyOperator &op, int k, const double *b, const double *x, double *d, double *y)
 {
     cheby_step_kernel<MODE><<<wide_grid(4 * op.units, CHEBY_THREADS), CHEBY_THREADS, 0, s>>>(
-        op.units, static_cast<const Unit *>(op.d_units), op.colidx, op.val, op.dinv, op.blk + CS_TABLE + 2 * k,
+        op.units, static_cast<const SweepUnit *>(op.d_units), op.colidx, op.val, op.dinv, op.blk + CS_TABLE + 2 * k,
         reinterpret_cast<const long long *>(op.blk), b, x, d, y);
 }
 
@@ -369,15 +356,15 @@ int sblas_hip_cheby_plan_create(int dev, void *stream, int64_t n, int64_t nnz, c
     // the rows packed as one wide level of a solve, as the AMG sweep's launch packs them
     std::vector<int32_t> zero_level((size_t)n, 0);
     LevelOrder o;
-    std::vector<Unit> units;
-    const auto unit_of = [&](int32_t i, int32_t q) { return Unit{i, h_rowptr[(size_t)i], h_rowptr[(size_t)i + 1], q}; };
-    level_pack(n, h_rowptr.data(), zero_level.data(), 1, unit_of, NO_UNIT, o, units);
+    std::vector<SweepUnit> units;
+    const auto unit_of = [&](int32_t i, int32_t q) { return SweepUnit{i, h_rowptr[(size_t)i], h_rowptr[(size_t)i + 1], q}; };
+    level_pack(n, h_rowptr.data(), zero_level.data(), 1, unit_of, NO_SWEEP_UNIT, o, units);
     p->units = p->op.units = (int64_t)units.size();
     Segment seg[2] = {Segment(units), Segment(dpos)};
     size_t ib = 0;
     if (upload_segments(p->ibuf, p->dev, s, seg, 2, &ib) != hipSuccess) return SBLAS_E_HIP;
     p->op.n = n, p->op.rowptr = rowptr, p->op.colidx = colidx;
-    p->op.d_units = p->ibuf.at<Unit>(), p->op.dpos = p->ibuf.at<int32_t>(seg[1].offset);
+    p->op.d_units = p->ibuf.at<SweepUnit>(), p->op.dpos = p->ibuf.at<int32_t>(seg[1].offset);
     const size_t block = pad256((size_t)CHEBY_BLOCK_SLOTS * 8), part = pad256((size_t)p->cells * 8), vec = pad256((size_t)n * 8);
     const size_t db = block + part + 5 * vec;
     if (p->dbuf.alloc(p->dev, db) != hipSuccess) return SBLAS_E_HIP;

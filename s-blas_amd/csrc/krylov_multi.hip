@@ -2,7 +2,7 @@
 // share A and run in lockstep, one SpMM per product instead of s SpMVs.  X, B and the work blocks are n x s row-major.
 // Everything between two SpMMs is one of krylov.hip's three kernels, widened by a column tile:
 //   dot     stage 1 of up to KRYLOV_MAX_DOTS dots of every column in one pass: one workgroup a cell of KRYLOV_CELL rows
-//           and a tile of KRYLOV_MULTI_TILE columns, a lane its row's eight doubles of each operand and one accumulator
+//           and a tile of TILE columns (tile.h), a lane its row's eight doubles of each operand and one accumulator
 //           per column and dot; the sum of dot k, column j, cell c to part[(k * s + j) * cells + c];
 //   update  the fused updates of krylov.hip with column j's own alpha, beta, omega from scalar block j, also stage 1 of
 //           the dots of what they wrote;
@@ -42,6 +42,7 @@
 #include "krylov.h"
 #include "krylov_multi.h"
 #include "precond.h"
+#include "unit_row.h" // tile_ld, tile_st, tile_id
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
 
@@ -52,7 +53,7 @@ using namespace sblas;
 
 namespace {
 
-constexpr int T = KRYLOV_MULTI_TILE;
+constexpr int T = TILE;
 // internal update ops, after the public SBLAS_KRYLOV_UP_* ones (krylov.hip's)
 enum { UP_COPY = 5, UP_START_PCG = 6, UP_START_BICG = 7 };
 
@@ -72,55 +73,6 @@ struct MDotArgs {
     int64_t ldx[KRYLOV_MAX_DOTS], ldy[KRYLOV_MAX_DOTS];
     double *part;
 };
-
-// ---- a row's eight columns ---------------------------------------------------------------------------------------------
-// FAST: four 16-byte accesses (the launch's alignment allows it, the tile is full and every column runs).  Otherwise
-// column by column under the mask: a column outside it is not touched and reads as 0.
-template <bool FAST> __device__ __forceinline__ void ld8(const double *p, unsigned mask, double (&x)[T])
-{
-    if constexpr (FAST) {
-        const double2 *q = reinterpret_cast<const double2 *>(p);
-#pragma unroll
-        for (int c = 0; c < T / 2; ++c) {
-            const double2 t = q[c];
-            x[2 * c] = t.x, x[2 * c + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < T; ++c) x[c] = (mask >> c & 1u) ? p[c] : 0.0;
-    }
-}
-
-template <bool FAST> __device__ __forceinline__ void st8(double *p, unsigned mask, const double (&x)[T])
-{
-    if constexpr (FAST) {
-        double2 *q = reinterpret_cast<double2 *>(p);
-#pragma unroll
-        for (int c = 0; c < T / 2; ++c) q[c] = make_double2(x[2 * c], x[2 * c + 1]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < T; ++c)
-            if (mask >> c & 1u) p[c] = x[c];
-    }
-}
-
-// Which cell and which column tile a workgroup takes.  The grid is one-dimensional, cells x tiles workgroups, numbered so
-// that the tiles of one cell are KRYLOV_MULTI_GROUP ids apart and next to each other in time: cells go in groups of
-// KRYLOV_MULTI_GROUP, and inside a group the id runs over the cells first, then over the tiles.  At s > 8 two tiles of
-// a cell read halves of the same memory lines (a row is s * 8 bytes, a tile 64 of them); workgroup ids that differ by
-// the number of L2 partitions are dispatched to the same partition, so the second tile finds the lines the first one
-// fetched.  The numbering cannot reach a bit: a (cell, tile) pair computes the same sums wherever it runs.
-constexpr int KRYLOV_MULTI_GROUP = 8;
-struct TileId {
-    int64_t cell;
-    int tile;
-};
-__device__ __forceinline__ TileId tile_id(int64_t cells, int s)
-{
-    const int64_t per = (int64_t)KRYLOV_MULTI_GROUP * ((s + T - 1) / T), id = blockIdx.x, g = id / per, rem = id - g * per;
-    const int64_t left = cells - KRYLOV_MULTI_GROUP * g, gc = left < KRYLOV_MULTI_GROUP ? left : KRYLOV_MULTI_GROUP; // the last group is short
-    return TileId{KRYLOV_MULTI_GROUP * g + rem % gc, (int)(rem / gc)};
-}
 
 // Lane t of a cell takes rows t, t + 256, ... of the cell in that order (cell_walk's order); absent rows are skipped.
 // Not unrolled eight times as cell_walk is: a row is already eight columns of every operand in registers.
@@ -152,20 +104,20 @@ template <int ND> __device__ __forceinline__ void tile_store(const double (&acc)
 // not a part of the freeze: like krylov.hip's dot it reads work blocks (or the caller's operands) and writes partials
 template <int ND, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES) void multi_dot_kernel(const MDotArgs a)
 {
-    const TileId id = tile_id(a.cells, a.s);
-    const int j0 = id.tile * T, w = a.s - j0 < T ? a.s - j0 : T;
+    const TileId id = tile_id(a.cells, tiles(a.s));
+    const int j0 = (int)id.tile * T, w = a.s - j0 < T ? a.s - j0 : T;
     const unsigned mask = (1u << w) - 1u;
     double acc[ND * T];
 #pragma unroll
     for (int q = 0; q < ND * T; ++q) acc[q] = 0.0;
     auto body = [&](auto fast) {
         constexpr bool F = decltype(fast)::value;
-        row_walk(id.cell, a.n, [&](int64_t i) {
+        row_walk(id.block, a.n, [&](int64_t i) {
 #pragma unroll
             for (int q = 0; q < ND; ++q) {
                 double x[T], y[T];
-                ld8<F>(a.x[q] + i * a.ldx[q] + j0, mask, x);
-                ld8<F>(a.y[q] + i * a.ldy[q] + j0, mask, y);
+                tile_ld<T, F>(a.x[q] + i * a.ldx[q] + j0, mask, x);
+                tile_ld<T, F>(a.y[q] + i * a.ldy[q] + j0, mask, y);
 #pragma unroll
                 for (int c = 0; c < T; ++c) acc[q * T + c] = acc[q * T + c] + x[c] * y[c];
             }
@@ -173,7 +125,7 @@ template <int ND, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES) void mul
     };
     if (WIDE && w == T) body(std::true_type{});
     else body(std::false_type{});
-    tile_store<ND>(acc, a.part, a.s, a.cells, id.cell, j0, mask);
+    tile_store<ND>(acc, a.part, a.s, a.cells, id.block, j0, mask);
 }
 
 // ---- the fused updates -----------------------------------------------------------------------------------------------
@@ -182,8 +134,8 @@ template <int ND, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES) void mul
 template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES) void multi_update_kernel(const MUpArgs a)
 {
     constexpr bool START = OP == UP_START_PCG || OP == UP_START_BICG;
-    const TileId id = tile_id(a.cells, a.s);
-    const int j0 = id.tile * T, w = a.s - j0 < T ? a.s - j0 : T;
+    const TileId id = tile_id(a.cells, tiles(a.s));
+    const int j0 = (int)id.tile * T, w = a.s - j0 < T ? a.s - j0 : T;
     unsigned mask = 0, zmask = 0; // the columns that run; of a start pass, those with b == 0
     double al[T], be[T], om[T];
 #pragma unroll
@@ -207,20 +159,20 @@ template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES
     auto at = [&](int q, int64_t i) { return v[q] + i * ld[q] + j0; };
     auto body = [&](auto fast) {
         constexpr bool F = decltype(fast)::value;
-        row_walk(id.cell, a.n, [&](int64_t i) {
+        row_walk(id.block, a.n, [&](int64_t i) {
             if constexpr (OP == SBLAS_KRYLOV_UP_PCG_XR) { // x, r, p, q, dinv, z
                 double x[T], p[T], r[T], q[T];
-                ld8<F>(at(0, i), mask, x), ld8<F>(at(2, i), mask, p);
+                tile_ld<T, F>(at(0, i), mask, x), tile_ld<T, F>(at(2, i), mask, p);
 #pragma unroll
                 for (int c = 0; c < T; ++c) x[c] = x[c] + al[c] * p[c];
-                st8<F>(at(0, i), mask, x);
-                ld8<F>(at(1, i), mask, r), ld8<F>(at(3, i), mask, q);
+                tile_st<T, F>(at(0, i), mask, x);
+                tile_ld<T, F>(at(1, i), mask, r), tile_ld<T, F>(at(3, i), mask, q);
 #pragma unroll
                 for (int c = 0; c < T; ++c) {
                     r[c] = r[c] - al[c] * q[c];
                     acc[c] = acc[c] + r[c] * r[c];
                 }
-                st8<F>(at(1, i), mask, r);
+                tile_st<T, F>(at(1, i), mask, r);
                 if constexpr (JAC) {
                     const double di = v[4][i];
                     double z[T];
@@ -229,60 +181,60 @@ template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES
                         z[c] = di * r[c];
                         acc[T + c] = acc[T + c] + r[c] * z[c];
                     }
-                    st8<F>(at(5, i), mask, z);
+                    tile_st<T, F>(at(5, i), mask, z);
                 }
             } else if constexpr (OP == SBLAS_KRYLOV_UP_PCG_P) { // p, z
                 double p[T], z[T];
-                ld8<F>(at(0, i), mask, p), ld8<F>(at(1, i), mask, z);
+                tile_ld<T, F>(at(0, i), mask, p), tile_ld<T, F>(at(1, i), mask, z);
 #pragma unroll
                 for (int c = 0; c < T; ++c) p[c] = z[c] + be[c] * p[c];
-                st8<F>(at(0, i), mask, p);
+                tile_st<T, F>(at(0, i), mask, p);
             } else if constexpr (OP == UP_COPY) { // dst, src
                 double x[T];
-                ld8<F>(at(1, i), mask, x);
-                st8<F>(at(0, i), mask, x);
+                tile_ld<T, F>(at(1, i), mask, x);
+                tile_st<T, F>(at(0, i), mask, x);
             } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_P) { // p, r, v, dinv, p^
                 double p[T], r[T], vv[T];
-                ld8<F>(at(0, i), mask, p), ld8<F>(at(1, i), mask, r), ld8<F>(at(2, i), mask, vv);
+                tile_ld<T, F>(at(0, i), mask, p), tile_ld<T, F>(at(1, i), mask, r), tile_ld<T, F>(at(2, i), mask, vv);
 #pragma unroll
                 for (int c = 0; c < T; ++c) p[c] = r[c] + be[c] * (p[c] - om[c] * vv[c]);
-                st8<F>(at(0, i), mask, p);
+                tile_st<T, F>(at(0, i), mask, p);
                 if constexpr (JAC) {
                     const double di = v[3][i];
 #pragma unroll
                     for (int c = 0; c < T; ++c) p[c] = di * p[c];
-                    st8<F>(at(4, i), mask, p);
+                    tile_st<T, F>(at(4, i), mask, p);
                 }
             } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_S) { // s, r, v, dinv, s^
                 double sv[T], r[T], vv[T];
-                ld8<F>(at(1, i), mask, r), ld8<F>(at(2, i), mask, vv);
+                tile_ld<T, F>(at(1, i), mask, r), tile_ld<T, F>(at(2, i), mask, vv);
 #pragma unroll
                 for (int c = 0; c < T; ++c) sv[c] = r[c] - al[c] * vv[c];
-                st8<F>(at(0, i), mask, sv);
+                tile_st<T, F>(at(0, i), mask, sv);
                 if constexpr (JAC) {
                     const double di = v[3][i];
 #pragma unroll
                     for (int c = 0; c < T; ++c) sv[c] = di * sv[c];
-                    st8<F>(at(4, i), mask, sv);
+                    tile_st<T, F>(at(4, i), mask, sv);
                 }
             } else if constexpr (OP == SBLAS_KRYLOV_UP_BICG_XR) { // x, r, p^, s^, s, t, r^
                 double x[T], ph[T], sh[T];
-                ld8<F>(at(0, i), mask, x), ld8<F>(at(2, i), mask, ph), ld8<F>(at(3, i), mask, sh);
+                tile_ld<T, F>(at(0, i), mask, x), tile_ld<T, F>(at(2, i), mask, ph), tile_ld<T, F>(at(3, i), mask, sh);
 #pragma unroll
                 for (int c = 0; c < T; ++c) x[c] = (x[c] + al[c] * ph[c]) + om[c] * sh[c];
-                st8<F>(at(0, i), mask, x);
+                tile_st<T, F>(at(0, i), mask, x);
                 double sv[T], t[T], rh[T];
-                ld8<F>(at(4, i), mask, sv), ld8<F>(at(5, i), mask, t), ld8<F>(at(6, i), mask, rh);
+                tile_ld<T, F>(at(4, i), mask, sv), tile_ld<T, F>(at(5, i), mask, t), tile_ld<T, F>(at(6, i), mask, rh);
 #pragma unroll
                 for (int c = 0; c < T; ++c) {
                     sv[c] = sv[c] - om[c] * t[c];
                     acc[c] = acc[c] + sv[c] * sv[c];
                     acc[T + c] = acc[T + c] + rh[c] * sv[c];
                 }
-                st8<F>(at(1, i), mask, sv);
+                tile_st<T, F>(at(1, i), mask, sv);
             } else if constexpr (OP == UP_START_PCG) { // r, b, q (= A x0), dinv, z, x
                 double b[T], q[T], r[T];
-                ld8<F>(at(1, i), mask, b), ld8<F>(at(2, i), mask, q);
+                tile_ld<T, F>(at(1, i), mask, b), tile_ld<T, F>(at(2, i), mask, q);
                 double *x = at(5, i);
 #pragma unroll
                 for (int c = 0; c < T; ++c) {
@@ -291,7 +243,7 @@ template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES
                     r[c] = zero ? 0.0 : b[c] - q[c];
                     acc[c] = acc[c] + r[c] * r[c];
                 }
-                st8<F>(at(0, i), mask, r);
+                tile_st<T, F>(at(0, i), mask, r);
                 if constexpr (JAC) {
                     const double di = v[3][i];
                     double z[T];
@@ -300,11 +252,11 @@ template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES
                         z[c] = (zmask >> c & 1u) ? 0.0 : di * r[c];
                         acc[T + c] = acc[T + c] + r[c] * z[c];
                     }
-                    st8<F>(at(4, i), mask, z);
+                    tile_st<T, F>(at(4, i), mask, z);
                 }
             } else { // UP_START_BICG: r, b, v (= A x0 on entry, 0 on exit), r^, p, x
                 double b[T], q[T], r[T], zero8[T];
-                ld8<F>(at(1, i), mask, b), ld8<F>(at(2, i), mask, q);
+                tile_ld<T, F>(at(1, i), mask, b), tile_ld<T, F>(at(2, i), mask, q);
                 double *x = at(5, i);
 #pragma unroll
                 for (int c = 0; c < T; ++c) {
@@ -314,14 +266,14 @@ template <int OP, bool JAC, bool WIDE> __global__ __launch_bounds__(KRYLOV_LANES
                     zero8[c] = 0.0;
                     acc[c] = acc[c] + r[c] * r[c];
                 }
-                st8<F>(at(0, i), mask, r), st8<F>(at(3, i), mask, r);
-                st8<F>(at(4, i), mask, zero8), st8<F>(at(2, i), mask, zero8);
+                tile_st<T, F>(at(0, i), mask, r), tile_st<T, F>(at(3, i), mask, r);
+                tile_st<T, F>(at(4, i), mask, zero8), tile_st<T, F>(at(2, i), mask, zero8);
             }
         });
     };
     if (WIDE && mask == (1u << T) - 1u) body(std::true_type{});
     else body(std::false_type{});
-    if constexpr (NP > 0) tile_store<NP>(acc, a.part, a.s, a.cells, id.cell, j0, mask);
+    if constexpr (NP > 0) tile_store<NP>(acc, a.part, a.s, a.cells, id.block, j0, mask);
 }
 
 // ---- stage 2, which is also the scalar step: one workgroup a column -------------------------------------------------------
@@ -340,14 +292,10 @@ __global__ __launch_bounds__(KRYLOV_LANES) void multi_fold_kernel(int op, int nd
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-inline bool wide16(const void *p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)(ld * 8)) & 15u) == 0; }
-
-inline unsigned tile_grid(int64_t cells, int s) { return (unsigned)(cells * krylov_multi_tiles(s)); } // tile_id() numbers it
-
 template <int ND> inline void launch_dot_nd(hipStream_t st, bool wide, const MDotArgs &a)
 {
-    if (wide) multi_dot_kernel<ND, true><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
-    else multi_dot_kernel<ND, false><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+    if (wide) multi_dot_kernel<ND, true><<<(unsigned)tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+    else multi_dot_kernel<ND, false><<<(unsigned)tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
 }
 
 inline void launch_dot(hipStream_t st, int nd, const MDotArgs &a)
@@ -367,8 +315,8 @@ inline void launch_fold(hipStream_t st, int op, int nd, int flag, int s, int64_t
 
 template <int OP, bool JAC> inline void launch_update_op(hipStream_t st, bool wide, const MUpArgs &a)
 {
-    if (wide) multi_update_kernel<OP, JAC, true><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
-    else multi_update_kernel<OP, JAC, false><<<tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+    if (wide) multi_update_kernel<OP, JAC, true><<<(unsigned)tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
+    else multi_update_kernel<OP, JAC, false><<<(unsigned)tile_grid(a.cells, a.s), KRYLOV_LANES, 0, st>>>(a);
 }
 
 // blocks of an op (the single update's counts) and the place of dinv among them with Jacobi, else -1

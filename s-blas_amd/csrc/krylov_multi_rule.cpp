@@ -16,7 +16,7 @@ extern "C" {
 int sblas_krylov_multi_limits(int64_t out[8])
 {
     if (!out) return SBLAS_E_INVALID;
-    out[0] = SBLAS_KRYLOV_MULTI_MAX_RHS, out[1] = sblas::KRYLOV_MULTI_TILE, out[2] = sblas::KRYLOV_CELL, out[3] = sblas::KRYLOV_LANES;
+    out[0] = SBLAS_KRYLOV_MULTI_MAX_RHS, out[1] = sblas::TILE, out[2] = sblas::KRYLOV_CELL, out[3] = sblas::KRYLOV_LANES;
     out[4] = sblas::KRYLOV_PCG_VECTORS, out[5] = sblas::KRYLOV_BICGSTAB_VECTORS, out[6] = sblas::KRYLOV_MAX_DOTS;
     out[7] = sblas::KRYLOV_BLOCK_SLOTS;
     return SBLAS_OK;
@@ -63,8 +63,8 @@ int64_t sblas_krylov_multi_launches_pair(int method, int precond, int64_t spmm_l
 int sblas_krylov_multi_grid(int64_t n, int nrhs, int64_t out[4])
 {
     if (!out || n < 0 || !sblas::krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
-    out[0] = sblas::krylov_cells(n), out[1] = sblas::krylov_multi_tiles(nrhs), out[2] = out[0] * out[1];
-    out[3] = nrhs - (int)(out[1] - 1) * sblas::KRYLOV_MULTI_TILE;
+    out[0] = sblas::krylov_cells(n), out[1] = sblas::tiles(nrhs), out[2] = out[0] * out[1];
+    out[3] = nrhs - (int)(out[1] - 1) * sblas::TILE;
     return SBLAS_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "level_kernels.h"
 #include "rowwise.h"
 #include "sptrsv.h"
+#include "unit_row.h"
 
 using namespace sblas;
 
@@ -64,12 +65,8 @@ __device__ __forceinline__ void solve_row(const Unit u, int quad, bool lower, co
             if (lower ? c < u.row : c > u.row) s = __builtin_fma(val[e], x[c], s); // the other triangle is never loaded
         }
     }
-    const double f4 = fold_sum<4>(s);
-    double f16 = f4 + lane_partner<4>(f4);
-    f16 += lane_partner<8>(f16);
-    double f64 = f16 + lane_partner<16>(f16);
-    f64 += lane_partner<32>(f64);
-    if (writer) x[u.row] = finish_row(alpha, bi, gs == 2 ? f4 : gs == 4 ? f16 : f64, pivot);
+    const double sum = group_fold(s, gs);
+    if (writer) x[u.row] = finish_row(alpha, bi, sum, pivot);
 }
 
 // Row `row` of X for one row: a lane per right-hand side, the stored entries one after another.  Column j's bits depend
@@ -311,18 +308,20 @@ int sblas_hip_sptrsm_tiled_f64_i32_planned(const void *plan, void *stream, const
     if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
     // every grid is known from the plan: an nrhs whose widest launch would not fit is refused before anything is launched
     for (const Launch &q : p->sched.launches)
-        if (sptrsm_tile_grid(q.chain ? 1 : p->h_level_unit_ptr[q.l1] - p->h_level_unit_ptr[q.l0], nrhs) < 0) return SBLAS_E_INVALID;
+        if (tile_grid(q.chain ? 1 : unit_blocks(p->h_level_unit_ptr[q.l1] - p->h_level_unit_ptr[q.l0], SPTRSM_UNITS_PER_BLOCK), nrhs) < 0)
+            return SBLAS_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const TileSolveArgs a{p->fill == SBLAS_FILL_LOWER, nrhs, p->units, colidx, val, alpha, B, ldb, X, ldx};
-    const bool wide = sptrsm_wide16(B, ldb) && sptrsm_wide16(X, ldx);
-    const unsigned tiles = (unsigned)sptrsm_tiles(nrhs);
+    const bool wide = wide16(B, ldb) && wide16(X, ldx);
+    const unsigned ntiles = (unsigned)tiles(nrhs);
     for (const Launch &q : p->sched.launches) {
         if (q.chain) {
-            if (wide) sptrsm_tile_chain_kernel<true><<<tiles, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, a);
-            else sptrsm_tile_chain_kernel<false><<<tiles, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, a);
+            if (wide) sptrsm_tile_chain_kernel<true><<<ntiles, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, a);
+            else sptrsm_tile_chain_kernel<false><<<ntiles, SPTRSV_CHAIN_THREADS, 0, s>>>(q.l0, q.l1, p->level_unit_ptr, a);
         } else {
-            const int64_t first = p->h_level_unit_ptr[q.l0], count = p->h_level_unit_ptr[q.l1] - first, blocks = sptrsm_unit_blocks(count);
-            const unsigned grid = (unsigned)sptrsm_tile_grid(count, nrhs);
+            const int64_t first = p->h_level_unit_ptr[q.l0], count = p->h_level_unit_ptr[q.l1] - first;
+            const int64_t blocks = unit_blocks(count, SPTRSM_UNITS_PER_BLOCK);
+            const unsigned grid = (unsigned)tile_grid(blocks, nrhs);
             if (wide) sptrsm_tile_wide_kernel<true><<<grid, SPTRSM_WIDE_THREADS, 0, s>>>(first, count, blocks, a);
             else sptrsm_tile_wide_kernel<false><<<grid, SPTRSM_WIDE_THREADS, 0, s>>>(first, count, blocks, a);
         }

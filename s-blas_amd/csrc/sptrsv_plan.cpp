@@ -25,17 +25,17 @@ int sblas_hip_sptrsv_limits(int64_t out[4])
 int sblas_sptrsm_tile_limits(int64_t out[4])
 {
     if (!out) return SBLAS_E_INVALID;
-    out[0] = sblas::SPTRSM_TILE, out[1] = sblas::SPTRSM_WIDE_THREADS, out[2] = sblas::SPTRSV_CHAIN_THREADS, out[3] = sblas::SPTRSM_MAX_GRID;
+    out[0] = sblas::TILE, out[1] = sblas::SPTRSM_WIDE_THREADS, out[2] = sblas::SPTRSV_CHAIN_THREADS, out[3] = sblas::SPTRSM_MAX_GRID;
     return SBLAS_OK;
 }
 
 int sblas_sptrsm_tile_grid(int64_t units, int64_t nrhs, int64_t out[4])
 {
     if (!out || units < 0 || nrhs < 1) return SBLAS_E_INVALID;
-    const int64_t grid = sblas::sptrsm_tile_grid(units, nrhs);
+    const int64_t blocks = sblas::unit_blocks(units, sblas::SPTRSM_UNITS_PER_BLOCK), grid = sblas::tile_grid(blocks, nrhs);
     if (grid < 0) return SBLAS_E_INVALID;
-    out[0] = sblas::sptrsm_unit_blocks(units), out[1] = sblas::sptrsm_tiles(nrhs), out[2] = grid;
-    out[3] = nrhs - (out[1] - 1) * sblas::SPTRSM_TILE;
+    out[0] = blocks, out[1] = sblas::tiles(nrhs), out[2] = grid;
+    out[3] = nrhs - (out[1] - 1) * sblas::TILE;
     return SBLAS_OK;
 }
 

@@ -221,26 +221,32 @@ def group(p):
     return 4 if p <= G4_MAX else 16 if p <= G16_MAX else 64
 
 
+def lane_order_sum(ci, val, x, beg, end, take=None):
+    """the sum of one stored row (entries beg .. end - 1; ci, val, x plain lists): G comes from the stored length; lane l
+    of G takes the entries l, l + G, ... with one fma each from +0, an entry whose take[e] is false takes none (take: a
+    mask over the stored entries, None for the whole row); the butterfly l ^ 1, l ^ 2, ... as written; lane 0"""
+    G = group(end - beg)
+    v = [0.0] * G
+    for l in range(min(G, end - beg)):
+        s = 0.0
+        for e in range(beg + l, end, G):
+            if take is None or take[e]:
+                s = fma(val[e], x[ci[e]], s)
+        v[l] = s
+    m = 1
+    while m < G:
+        v = [v[l] + v[l ^ m] for l in range(G)]
+        m <<= 1
+    return v[0]
+
+
 def row_sums(L, x):
-    """s_i for every row: lane l of G(p) takes the entries l, l + G, ... with one fma each from +0; the butterfly
-    l ^ 1, l ^ 2, ... as written; lane 0"""
+    """s_i for every row, each by lane_order_sum()"""
     rp, ci, val = L["rowptr"], L["colidx"].tolist(), L["val"].tolist()
     x = x.tolist()
     out = np.zeros(L["n"])
     for i in range(L["n"]):
-        beg, end = int(rp[i]), int(rp[i + 1])
-        G = group(end - beg)
-        v = [0.0] * G
-        for l in range(min(G, end - beg)):
-            s = 0.0
-            for e in range(beg + l, end, G):
-                s = fma(val[e], x[ci[e]], s)
-            v[l] = s
-        m = 1
-        while m < G:
-            v = [v[l] + v[l ^ m] for l in range(G)]
-            m <<= 1
-        out[i] = v[0]
+        out[i] = lane_order_sum(ci, val, x, int(rp[i]), int(rp[i + 1]))
     return out
 
 

@@ -8,6 +8,7 @@ stored diagonals and uses 1.
 - reference(): forward / backward substitution in double-double (the error-free pieces of numerics.py).
 - residual_bound(): the rounding-error bound on the residual that every correct evaluation order satisfies.
 - grid_problem(): integer data on which every order of every sum is exact, so the solve must return x with ==.
+- solve_lane_order(): SpSV's results contract restated operation by operation, for equality of bits.
 - the generators of the shapes the tests use."""
 import numpy as np
 
@@ -131,6 +132,29 @@ def reference(n, rowptr, colidx, val, b, lower=True, unit=False, alpha=1.0):
             assert len(d) == 1, "row %d stores %d diagonal entries" % (i, len(d))
             xh[i], xl[i] = _dd_div(rh, rl, d[0])
     return (xh + xl).reshape(np.shape(b))
+
+
+def solve_lane_order(n, rowptr, colidx, val, b, lower=True, unit=False, alpha=1.0):
+    """x with the bits the results contract of sptrsv.hip promises: row i's sum over its selected entries in lane order
+    (amg_numerics.lane_order_sum: G from the stored length of the whole row, a rejected entry takes no fma and is not
+    read), then three roundings -- alpha * b_i, the subtraction, the division by the stored diagonal (1 under unit).
+    One stored diagonal a row unless unit."""
+    import amg_numerics as AN                                               # here: amg_numerics' own imports lead back to this module
+    rp, ci = np.asarray(rowptr, np.int64), np.asarray(colidx, np.int64)
+    take, dg = selected(rp, ci, lower).tolist(), on_diagonal(rp, ci)
+    cl, vl, bl = ci.tolist(), np.asarray(val, np.float64).tolist(), np.asarray(b, np.float64).tolist()
+    x = [float("nan")] * n                                                  # a row that is read before it is solved shows
+    for i in (range(n) if lower else range(n - 1, -1, -1)):
+        beg, end = int(rp[i]), int(rp[i + 1])
+        s = AN.lane_order_sum(cl, vl, x, beg, end, take)
+        pivot = 1.0
+        if not unit:
+            d = np.flatnonzero(dg[beg:end])
+            assert len(d) == 1, "row %d stores %d diagonal entries" % (i, len(d))
+            pivot = vl[beg + int(d[0])]
+        t = float(alpha) * bl[i]
+        x[i] = (t - s) / pivot
+    return np.array(x, np.float64)
 
 
 def residual_bound(n, rowptr, colidx, val, b, x, lower=True, unit=False, alpha=1.0):

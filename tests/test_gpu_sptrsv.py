@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import amg_numerics as AN
 import numerics as NM
 import sptrsv_numerics as TN
 
@@ -178,6 +179,46 @@ def test_rows_around_every_group_width_boundary(env):
     rows = [list(rng.permutation(n - 1 - ci[rp[i]:rp[i + 1]])) for i in range(n - 1, -1, -1)]
     rp2, ci2 = TN.csr_of_rows(rows)
     run_case(env, "group widths, upper", n, rp2, ci2, lower=False, seed=11)
+
+
+@pytest.mark.parametrize("lower,unit", [(True, False), (False, False), (True, True), (False, True)])
+def test_bits_against_the_lane_order_restatement(env, lower, unit):
+    """SpSV's bits against the host restatement of its contract (TN.solve_lane_order), not against another schedule: 80
+    unsorted rows with entries in both triangles whose stored lengths are both sides of each G(p) boundary and 70 (two
+    rounds per lane of a whole wave).  Every ignored entry is NaN -- the other triangle and, under unit, the stored
+    diagonal -- so one that is multiplied by zero instead of skipped shows; alpha is not 1.  Equality of bits: no
+    tolerance."""
+    S, torch, cuda = env
+    lim = S.sptrsv_limits()
+    g4, g16 = lim["g4_max"], lim["g16_max"]
+    lengths = [1, g4, g4 + 1, g16, g16 + 1, 70]
+    assert (g4, g16) == (AN.G4_MAX, AN.G16_MAX) and 64 < lengths[-1] <= 80
+    n, alpha = 80, 0.3
+    rng = np.random.default_rng(41 + 2 * lower + unit)
+    rows = []
+    for i in range(n):
+        others = rng.choice(np.delete(np.arange(n), i), lengths[i % len(lengths)] - 1, replace=False)
+        rows.append(list(rng.permutation(np.concatenate([others, [i]]))))   # stored order: the triangles interleaved
+    rp, ci = TN.csr_of_rows(rows)
+    val = TN.dominant_values(rng, n, rp, ci, lower, unit)
+    ignored = TN.selected(rp, ci, not lower)
+    assert ignored.any() and TN.selected(rp, ci, lower).any()
+    val[ignored] = np.nan
+    if unit:
+        val[TN.on_diagonal(rp, ci)] = np.nan                                # ignored too: the diagonal is 1
+    b = NM.log_uniform(rng, n, 8)
+    want = TN.solve_lane_order(n, rp, ci, val, b, lower, unit, alpha)
+    assert np.isfinite(want).all()
+    drp, dci, dval, db = up(torch, cuda, rp, ci, val, b)
+    for mode, chain_rows in (("per_level", 0), ("chain", 0), ("auto", 8)):    # some twenty levels, up to some twenty rows wide
+        plan = S.SptrsvPlan(n, drp, dci, lower=lower, unit_diag=unit, mode=mode, chain_rows=chain_rows)
+        info = plan.info()
+        assert mode != "auto" or (info["wide_launches"] >= 1 and info["chain_launches"] >= 1), info
+        got = plan.solve(dval, db, alpha=alpha).cpu().numpy()
+        plan.destroy()
+        same = TN.bits(got) == TN.bits(want)
+        assert same.all(), "%s: %d of %d entries differ from the restatement, first at row %d (stored length %d): %r vs %r" % (
+            mode, (~same).sum(), n, np.argmax(~same), rp[np.argmax(~same) + 1] - rp[np.argmax(~same)], got[np.argmax(~same)], want[np.argmax(~same)])
 
 
 def test_unsorted_rows_with_duplicates(env):
