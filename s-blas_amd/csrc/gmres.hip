@@ -31,6 +31,7 @@
 
 #define GMRES_HD __host__ __device__
 #include "gmres.h"
+#include "gmres_fold.h" // the fold ops, who acts, the sums, lane 0's part, the close's lane
 #include "krylov_fold.h"
 
 using namespace sblas;
@@ -45,8 +46,6 @@ enum { MODE_FREE = 0,   // from the launch (the stand-alone entry points, start'
        MODE_FIRST = 1,  // a step's first kernels: columns + 1 while RUNNING with the cycle not full, else nothing
        MODE_ACTIVE = 2, // behind a step's first fold: columns + 1 while GS_ACTIVE
        MODE_CLOSE = 3 };// behind a close's first kernel: columns while GS_CLOSE
-// fold ops: what lane 0 does with the folded sums
-enum { GF_OUT = 0, GF_START_B, GF_BEGIN_START, GF_BEGIN_RESTART, GF_H1, GF_H2, GF_STEP };
 
 struct ColArgs {
     int64_t n, cells, ldv;
@@ -258,94 +257,21 @@ template <bool JAC> __global__ __launch_bounds__(KRYLOV_LANES) void gmres_x_kern
 __global__ void gmres_close_kernel(double *blk, double *mat)
 {
     if (threadIdx.x != 0) return;
-    long long *ib = reinterpret_cast<long long *>(blk);
-    const int k = (int)ib[GS_COLS];
-    const bool act = ib[GS_PENDING] != 0 && (ib[GS_COLS] == ib[GS_M] || ib[GS_STATUS] != GMRES_RUNNING);
-    ib[GS_CLOSE] = act;
-    if (!act) return;
-    gmres_back_substitute(k, mat + GM_R, GMRES_MAX_RESTART, mat + GM_G, mat + GM_Y);
-    ib[GS_PENDING] = 0; // applied: a second close changes nothing
+    gmres_close_lane(blk, mat);
 }
 
-// ---- stage 2, which is also the scalar step ----------------------------------------------------------------------------
+// ---- stage 2, which is also the scalar step (gmres_fold.h) -------------------------------------------------------------
 __global__ __launch_bounds__(KRYLOV_LANES) void gmres_fold_kernel(int op, int nd, int64_t cells, const double *part, double *blk, double *mat,
                                                                  double *out, double rtol, double atol, long long max_iter, int m)
 {
     __shared__ double ws[GMRES_MAX_DOTS][4];
     long long *ib = reinterpret_cast<long long *>(blk);
-    // who acts: block-uniform loads, before any barrier.  A fold that opens a sequence says so in GS_ACTIVE.
-    if (op == GF_H1 || op == GF_BEGIN_START || op == GF_BEGIN_RESTART) {
-        bool act = ib[GS_STATUS] == GMRES_RUNNING;
-        if (op == GF_H1) act = act && ib[GS_COLS] < ib[GS_M];
-        if (op == GF_BEGIN_RESTART) act = act && ib[GS_COLS] == ib[GS_M] && ib[GS_PENDING] == 0;
-        if (!act) {
-            if (threadIdx.x == 0) ib[GS_ACTIVE] = 0;
-            return;
-        }
-    } else if (op == GF_H2 || op == GF_STEP) {
-        if (!ib[GS_ACTIVE]) return;
-    }
+    if (!gmres_fold_acts(op, ib)) return;
     if (op == GF_H1 || op == GF_H2) nd = (int)ib[GS_COLS] + 1;
-    // the dots one after another, each as the single dot's second stage: lane t adds partial[t], partial[t + 256], ...
-    // in order from +0, then the butterfly
-    for (int q = 0; q < nd; ++q) {
-        double acc = 0.0;
-        for (int64_t c = threadIdx.x; c < cells; c += KRYLOV_LANES) acc = acc + part[(int64_t)q * cells + c];
-        const double v = wave_fold(acc);
-        if ((threadIdx.x & 63) == 0) ws[q][threadIdx.x >> 6] = v;
-    }
+    gmres_fold_sums(nd, cells, part, cells, ws);
     __syncthreads();
     if (threadIdx.x != 0) return;
-    auto d = [&](int q) { return (ws[q][0] + ws[q][1]) + (ws[q][2] + ws[q][3]); };
-    double *h = mat + GM_H, *h2 = mat + GM_H2, *g = mat + GM_G;
-    switch (op) {
-    case GF_OUT:
-        for (int q = 0; q < nd; ++q) out[q] = d(q);
-        break;
-    case GF_START_B: {
-        const double bnorm = sqrt(d(0)), t = rtol * bnorm;
-        blk[GS_RNORM] = 0.0, blk[GS_ETA] = 0.0, blk[GS_BNORM] = bnorm, blk[GS_TOL] = t >= atol ? t : atol;
-        ib[GS_ITER] = 0, ib[GS_RESTARTS] = 0, ib[GS_COLS] = 0, ib[GS_WHICH] = 0, ib[GS_PENDING] = 0, ib[GS_MAX_ITER] = max_iter;
-        ib[GS_M] = m, ib[GS_CLOSE] = 0, ib[GS_ACTIVE] = 0, ib[15] = 0;
-        const bool zero = d(0) == 0.0; // b == 0: x = 0, converged at iteration 0, and nothing is divided
-        ib[GS_ZERO_X] = zero, ib[GS_STATUS] = zero ? GMRES_CONVERGED : GMRES_RUNNING;
-        break;
-    }
-    case GF_BEGIN_START:
-    case GF_BEGIN_RESTART: {
-        const double beta = sqrt(d(0));
-        int64_t which = 0;
-        const int st = gmres_begin(beta, blk[GS_TOL], (int64_t)ib[GS_ITER], (int64_t)ib[GS_MAX_ITER], &which);
-        blk[GS_RNORM] = beta, ib[GS_COLS] = 0, ib[GS_STATUS] = st, ib[GS_WHICH] = which, ib[GS_ACTIVE] = st == GMRES_RUNNING;
-        if (op == GF_BEGIN_RESTART) ib[GS_RESTARTS] = ib[GS_RESTARTS] + 1;
-        if (st == GMRES_RUNNING) blk[GS_ETA] = beta, g[0] = beta; // g = beta e_1: the step writes g_{j+1} before it is read
-        break;
-    }
-    case GF_H1:
-        for (int q = 0; q < nd; ++q) h[q] = d(q);
-        ib[GS_ACTIVE] = 1;
-        break;
-    case GF_H2:
-        for (int q = 0; q < nd; ++q) {
-            const double cq = d(q);
-            h2[q] = cq, h[q] = h[q] + cq;
-        }
-        break;
-    case GF_STEP: {
-        const int j = (int)ib[GS_COLS];
-        const double eta = sqrt(d(0));
-        int64_t iter = (int64_t)ib[GS_ITER], which = 0;
-        double rnorm = blk[GS_RNORM];
-        const int st = gmres_step(j, h, eta, mat + GM_C, mat + GM_S, g, mat + GM_R + (int64_t)j * GMRES_MAX_RESTART, blk[GS_TOL],
-                                  (int64_t)ib[GS_MAX_ITER], &iter, &rnorm, &which);
-        blk[GS_ETA] = eta;
-        ib[GS_STATUS] = st, ib[GS_ACTIVE] = st == GMRES_RUNNING;
-        if (st == GMRES_BREAKDOWN) ib[GS_WHICH] = which; // column j is dropped: the columns before it stay pending
-        else ib[GS_ITER] = iter, blk[GS_RNORM] = rnorm, ib[GS_COLS] = j + 1, ib[GS_PENDING] = 1;
-        break;
-    }
-    default: break;
-    }
+    gmres_fold_lane0(op, nd, ws, blk, mat, out, 1, rtol, atol, max_iter, m);
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------

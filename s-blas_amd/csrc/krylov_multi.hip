@@ -48,6 +48,7 @@
 
 #include "krylov_fold.h"   // wave_fold, group_fold, cells_fold
 #include "krylov_scalar.h" // the fold ops and the scalar step
+#include "krylov_tile.h"   // row_walk, tile_store
 
 using namespace sblas;
 
@@ -73,32 +74,6 @@ struct MDotArgs {
     int64_t ldx[KRYLOV_MAX_DOTS], ldy[KRYLOV_MAX_DOTS];
     double *part;
 };
-
-// Lane t of a cell takes rows t, t + 256, ... of the cell in that order (cell_walk's order); absent rows are skipped.
-// Not unrolled eight times as cell_walk is: a row is already eight columns of every operand in registers.
-template <class F> __device__ __forceinline__ void row_walk(int64_t cell, int64_t n, F f)
-{
-    const int64_t first = cell * KRYLOV_CELL;
-#pragma unroll 2
-    for (int k = 0; k < KRYLOV_PER_LANE; ++k) {
-        const int64_t i = first + threadIdx.x + k * KRYLOV_LANES;
-        if (i < n) f(i);
-    }
-}
-
-// the tile's ND * T lane sums through group_fold; lane 0 stores the columns of the mask
-template <int ND> __device__ __forceinline__ void tile_store(const double (&acc)[ND * T], double *part, int s, int64_t cells, int64_t cell, int j0, unsigned mask)
-{
-    double out[ND * T];
-    group_fold<ND * T>(acc, out);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < ND; ++k)
-#pragma unroll
-            for (int c = 0; c < T; ++c)
-                if (mask >> c & 1u) part[((int64_t)k * s + j0 + c) * cells + cell] = out[k * T + c];
-    }
-}
 
 // ---- dot, stage 1 ----------------------------------------------------------------------------------------------------
 // not a part of the freeze: like krylov.hip's dot it reads work blocks (or the caller's operands) and writes partials

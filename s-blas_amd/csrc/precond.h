@@ -80,7 +80,8 @@ struct PrecondSeat {
     // OUT = M^-1 IN on n x s row-major blocks, for a kind with a multi-column apply (precond_multi_applied): the AMG block
     // cycle, or with a pair of solve plans (precond_multi_pair): ILU(0), OUT = L^-1 IN by the tiled solve and then
     // OUT = U^-1 OUT in place, with the factor start was given.  Column j has apply()'s bits on column j either way.  OUT
-    // must not overlap IN.
+    // must not overlap IN, except that a kind with in_place() takes OUT == IN at one leading dimension: both tiled solves
+    // then run in place.
     int apply_multi(hipStream_t s, int nrhs, const double *in, int64_t ldin, double *out, int64_t ldout) const
     {
         if (sblas::precond_multi_pair(kind)) {

@@ -27,6 +27,18 @@ inline bool precond_multi_applied(int kind) { return kind == SBLAS_PRECOND_AMG; 
 // OUT = L^-1 IN by the tiled solve and OUT = U^-1 OUT in place.  Kept apart from precond_multi_applied, whose answers
 // and the refusals of the creates that go by it are pinned.
 inline bool precond_multi_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
+// Launches of one block M^-1 under a multi-right-hand-side plan that takes every door in one create (gmres_multi.hip):
+// 0 for a kind that rides in the kernels (and then no launches may be named), the block cycle's for one plan
+// (lower_or_cycle, with upper 0), the two tiled solves' for a pair.  -1 for a kind without a multi-column apply, an
+// unknown kind or a negative count.
+inline int64_t precond_multi_launches(int kind, int64_t lower_or_cycle, int64_t upper)
+{
+    if (lower_or_cycle < 0 || upper < 0) return -1;
+    if (precond_multi(kind)) return lower_or_cycle == 0 && upper == 0 ? 0 : -1;
+    if (precond_multi_applied(kind)) return upper == 0 ? lower_or_cycle : -1;
+    if (precond_multi_pair(kind)) return lower_or_cycle + upper;
+    return -1;
+}
 // holds two plans, lower and upper; every other applied kind holds one handle in lower's place and no upper
 inline bool precond_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 

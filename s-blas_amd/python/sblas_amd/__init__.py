@@ -107,6 +107,15 @@ EXPORTS_SPTRSM_TILE = [
     "sblas_sptrsm_tile_limits", "sblas_sptrsm_tile_grid", "sblas_krylov_multi_precond_pair_ok", "sblas_krylov_multi_launches_pair",
     "sblas_hip_sptrsm_tiled_f64_i32_planned", "sblas_hip_krylov_multi_plan_create_pair",
 ]
+# what include/sblas_hip_gmres_multi.h declares (restarted GMRES for several right-hand sides on one SpMM per Arnoldi step)
+EXPORTS_GMRES_MULTI = [
+    "sblas_gmres_multi_limits", "sblas_gmres_multi_grid", "sblas_gmres_multi_launches", "sblas_gmres_multi_precond_ok",
+    "sblas_gmres_multi_precond_plan_ok", "sblas_gmres_multi_precond_pair_ok",
+    "sblas_hip_gmres_multi_dots_workspace", "sblas_hip_gmres_multi_dots_f64", "sblas_hip_gmres_multi_project_f64",
+    "sblas_hip_gmres_multi_combine_f64",
+    "sblas_hip_gmres_multi_plan_create", "sblas_hip_gmres_multi_plan_info", "sblas_hip_gmres_multi_plan_block",
+    "sblas_hip_gmres_multi_plan_destroy", "sblas_hip_gmres_multi_start", "sblas_hip_gmres_multi_iterate", "sblas_hip_gmres_multi_status",
+]
 
 
 class SblasError(RuntimeError):
@@ -582,6 +591,37 @@ def lib():
     L.sblas_hip_sptrsm_tiled_f64_i32_planned.argtypes = [vp, vp, vp, vp, vp, i64, f64, vp, i64, vp, i64]
     L.sblas_hip_krylov_multi_plan_create_pair.restype = C.c_int
     L.sblas_hip_krylov_multi_plan_create_pair.argtypes = [C.c_int, vp, C.c_int, i64, i64, vp, vp, C.c_int, vp, vp, C.POINTER(vp)]
+    L.sblas_gmres_multi_limits.restype = C.c_int
+    L.sblas_gmres_multi_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_gmres_multi_grid.restype = C.c_int
+    L.sblas_gmres_multi_grid.argtypes = [i64, C.c_int, C.POINTER(i64)]
+    L.sblas_gmres_multi_launches.restype = i64
+    L.sblas_gmres_multi_launches.argtypes = [C.c_int, C.c_int, i64, i64, i64, C.POINTER(i64)]
+    for name in ("sblas_gmres_multi_precond_ok", "sblas_gmres_multi_precond_plan_ok", "sblas_gmres_multi_precond_pair_ok"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_int]
+    L.sblas_hip_gmres_multi_dots_workspace.restype = sz
+    L.sblas_hip_gmres_multi_dots_workspace.argtypes = [i64, C.c_int, C.c_int]
+    L.sblas_hip_gmres_multi_dots_f64.restype = C.c_int
+    L.sblas_hip_gmres_multi_dots_f64.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, vp, i64, i64, vp, i64, vp, vp, vp, sz]
+    L.sblas_hip_gmres_multi_project_f64.restype = C.c_int
+    L.sblas_hip_gmres_multi_project_f64.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, vp, i64, i64, vp, i64, vp, i64, vp, vp]
+    L.sblas_hip_gmres_multi_combine_f64.restype = C.c_int
+    L.sblas_hip_gmres_multi_combine_f64.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, vp, i64, i64, vp, i64, vp, i64, vp]
+    L.sblas_hip_gmres_multi_plan_create.restype = C.c_int
+    L.sblas_hip_gmres_multi_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
+    L.sblas_hip_gmres_multi_plan_info.restype = C.c_int
+    L.sblas_hip_gmres_multi_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_gmres_multi_plan_block.restype = C.c_int
+    L.sblas_hip_gmres_multi_plan_block.argtypes = [vp, vp, C.c_int, vp]
+    L.sblas_hip_gmres_multi_plan_destroy.restype = C.c_int
+    L.sblas_hip_gmres_multi_plan_destroy.argtypes = [vp]
+    L.sblas_hip_gmres_multi_start.restype = C.c_int
+    L.sblas_hip_gmres_multi_start.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64, f64, f64, i64]
+    L.sblas_hip_gmres_multi_iterate.restype = C.c_int
+    L.sblas_hip_gmres_multi_iterate.argtypes = [vp, vp, i64]
+    L.sblas_hip_gmres_multi_status.restype = C.c_int
+    L.sblas_hip_gmres_multi_status.argtypes = [vp, vp, C.POINTER(f64)]
     _lib = L
     return L
 
@@ -3923,12 +3963,13 @@ class KrylovMultiPlan:
             pass
 
 
-def _krylov_multi_one_shot(method, A, B, precond, X, kw):
+def _krylov_multi_one_shot(method, A, B, precond, X, kw, make=None):
     import torch
     n, rowptr, colidx, val = A
     one_shot_amg = isinstance(precond, str) and precond in ("amg", "amg_smoothed")
     if _solver_pair(precond):                                               # a pair needs its factor at start: the plan's door
-        raise SblasError("the one-shots take no pair of solve plans: use KrylovMultiPlan(..., precond=ilu.solvers()).solve(..., lu=lu)")
+        raise SblasError("the one-shots take no pair of solve plans: use %s(..., precond=ilu.solvers()).solve(..., lu=lu)"
+                         % ("KrylovMultiPlan" if make is None else "GmresMultiPlan"))
     kind =PRECOND_AMG if one_shot_amg else _multi_precond(precond)
     if not isinstance(B, torch.Tensor) or B.dim() != 2:
         raise SblasError("B must be an (n, nrhs) GPU tensor")
@@ -3940,7 +3981,10 @@ def _krylov_multi_one_shot(method, A, B, precond, X, kw):
         if kind == PRECOND_JACOBI:                                          # the diagonal's places, read off the ILU(0) plan
             ilu = Ilu0Plan(n, rowptr, colidx)
             dinv = ilu.pivots(val).reciprocal_()
-        plan = KrylovMultiPlan(n, rowptr, colidx, B.shape[1], method=method, precond=precond)
+        if make is not None:                                                # another plan with the same doors (gmres_multi)
+            plan = make(n, rowptr, colidx, B.shape[1], precond)
+        else:
+            plan = KrylovMultiPlan(n, rowptr, colidx, B.shape[1], method=method, precond=precond)
         return plan.solve(val, B, X=X, dinv=dinv, **kw)
     finally:
         if plan is not None:
@@ -4101,6 +4145,308 @@ def gmres(A, b, precond=None, restart=30, x=None, rtol=1e-8, atol=0.0, max_iter=
     max_iter counts Arnoldi steps."""
     return _krylov_one_shot(None, A, b, precond, x, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every),
                             make=lambda n, rowptr, colidx, pre: GmresPlan(n, rowptr, colidx, restart=restart, precond=pre))
+
+
+# ------------------------------------------------------------------------------------------
+# Restarted GMRES(m) for several right-hand sides on one SpMM per Arnoldi step (sblas_hip_gmres_multi_*)
+# ------------------------------------------------------------------------------------------
+def gmres_multi_limits():
+    """The multi-right-hand-side GMRES's limits (sblas_gmres_multi_limits): dict(max_rhs, tile, cell, width, max_restart,
+    fixed_blocks, block_slots, matrix_doubles).  A plan of restart m owns m + 1 + fixed_blocks blocks (AMG adds one)."""
+    out = (C.c_int64 * 8)()
+    check(lib().sblas_gmres_multi_limits(out), "sblas_gmres_multi_limits")
+    keys = ("max_rhs", "tile", "cell", "width", "max_restart", "fixed_blocks", "block_slots", "matrix_doubles")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def gmres_multi_grid(n, nrhs):
+    """Workgroups of one multi-column pass (sblas_gmres_multi_grid): dict(cells, tiles, grid, last_tile)."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_gmres_multi_grid(int(n), int(nrhs), out), "sblas_gmres_multi_grid")
+    return dict(cells=int(out[0]), tiles=int(out[1]), grid=int(out[2]), last_tile=int(out[3]))
+
+
+def gmres_multi_launches(restart=30, precond=None, spmm_launches=0):
+    """Launches of the multi-right-hand-side GMRES (sblas_gmres_multi_launches) -> dict(step, close, restart, start, cycle):
+    the single solver's with spmm_launches in the SpMV's place.  precond: None, "jacobi", an AmgPlan (its block cycle's
+    launches are counted) or a pair of SptrsvPlans (the two tiled solves')."""
+    kind = _multi_precond(precond)
+    first = second = 0
+    if isinstance(precond, AmgPlan):
+        first = precond.multi_info()["launches"]
+    elif _solver_pair(precond):
+        first, second = precond[0].info()["launches"], precond[1].info()["launches"]
+    out = (C.c_int64 * 4)()
+    cycle = int(lib().sblas_gmres_multi_launches(int(restart), kind, int(spmm_launches), first, second, out))
+    if cycle < 0:
+        raise SblasError("sblas_gmres_multi_launches refused its arguments")
+    return dict(step=int(out[0]), close=int(out[1]), restart=int(out[2]), start=int(out[3]), cycle=cycle)
+
+
+def _gmres_multi_blocks(V, W, name):
+    """V: k basis blocks as a (k, n, s) float64 GPU tensor with unit stride along a row (a view with a larger row or block
+    stride serves); W: an (n, s) row-major block -> (k, n, s, ldv, block_stride, ldw)"""
+    import torch
+    if not isinstance(V, torch.Tensor) or not V.is_cuda:
+        raise SblasError("V must be a GPU tensor (no CPU path exists)")
+    if V.dtype != torch.float64 or V.dim() != 3:
+        raise SblasError("V must be a float64 tensor of shape (blocks, n, nrhs)")
+    k, n, s = (int(v) for v in V.shape)
+    _multi_width(s)
+    if not 1 <= k <= gmres_limits()["max_dots"]:
+        raise SblasError("one to %d basis blocks, not %d" % (gmres_limits()["max_dots"], k))
+    if s > 1 and V.stride(2) != 1:
+        raise SblasError("a row of V must be contiguous")
+    ldv = V.stride(1) if n > 1 else max(V.stride(1), s)
+    if ldv < s:
+        raise SblasError("the leading dimension %d of V is below nrhs = %d" % (ldv, s))
+    stride = V.stride(0) if k > 1 else n * ldv
+    if k > 1 and stride < n * ldv:
+        raise SblasError("the block stride %d is below n * ld = %d" % (stride, n * ldv))
+    return k, n, s, int(ldv), int(stride), _krylov_block(name, W, n, s, V.device)
+
+
+def _gmres_multi_scalars(scalars, s, device):
+    import torch
+    if scalars is None:
+        return None
+    if not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or scalars.dtype != torch.float64 or not scalars.is_contiguous() \
+            or scalars.numel() != 16 * s or scalars.device != device:
+        raise SblasError("scalars must be a contiguous float64 GPU tensor of %d x 16 slots" % s)
+    return scalars.data_ptr()
+
+
+def _gmres_multi_coef(name, H, s, k, device):
+    """column c's k coefficients at H[c, :k]: an (s, >= k) float64 GPU tensor with unit stride along a row -> its row stride"""
+    import torch
+    if not isinstance(H, torch.Tensor) or not H.is_cuda or H.dtype != torch.float64 or H.dim() != 2 or H.device != device:
+        raise SblasError("%s must be a 2-D float64 GPU tensor on the operands' device" % name)
+    if H.shape[0] != s or H.shape[1] < k or (H.shape[1] > 1 and H.stride(1) != 1):
+        raise SblasError("%s must hold %d rows of at least %d contiguous coefficients, got shape %s" % (name, s, k, tuple(H.shape)))
+    return int(H.stride(0)) if s > 1 else max(int(H.stride(0)), k)
+
+
+def gmres_multi_dots(V, W, scalars=None, out=None, workspace=None, stream=None):
+    """out[i, c] = (V[i][:, c], W[:, c]) for up to 65 basis blocks in ONE pass over memory (sblas_hip_gmres_multi_dots_f64),
+    each with exactly the bits krylov_dot gives on the two columns.  V: (k, n, s), see _gmres_multi_blocks; W: (n, s)
+    row-major.  scalars: None, or an (s, 16) tensor of eight-byte slots whose slot 0 is a status as int64: a column
+    that is not running is neither read nor written (its out entries keep what they held; zeros when made here).  No
+    synchronisation; with out and workspace (float64, at least k * s * ceil(n / cell) entries) given, nothing is allocated."""
+    import torch
+    k, n, s, ldv, stride, ldw = _gmres_multi_blocks(V, W, "W")
+    if out is None:
+        out = torch.zeros((k, s), dtype=torch.float64, device=V.device)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != k * s:
+        raise SblasError("out must be a contiguous float64 GPU tensor of %d entries" % (k * s))
+    need = int(lib().sblas_hip_gmres_multi_dots_workspace(n, s, k))
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=V.device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.dtype != torch.float64 or not workspace.is_contiguous():
+        raise SblasError("workspace must be a contiguous float64 GPU tensor")
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_gmres_multi_dots_f64(-1, _stream(stream), n, s, k, V.data_ptr() if n else None, ldv, stride,
+                                                   W.data_ptr() if n else None, ldw, _gmres_multi_scalars(scalars, s, V.device), out.data_ptr(),
+                                                   workspace.data_ptr(), workspace.numel() * 8), "sblas_hip_gmres_multi_dots_f64")
+    return out
+
+
+def gmres_multi_project(V, H, W, partial=None, scalars=None, stream=None):
+    """W[:, c] = W[:, c] - H[c, 0] V[0][:, c] - H[c, 1] V[1][:, c] - ... in place, ascending, each product and each
+    difference rounded (sblas_hip_gmres_multi_project_f64).  partial: None, or a float64 tensor of at least s * ceil(n /
+    cell) entries that receives the first stage of (w, w) over the new W, column c's cells at partial[c * cells:]."""
+    import torch
+    k, n, s, ldv, stride, ldw = _gmres_multi_blocks(V, W, "W")
+    ldh = _gmres_multi_coef("H", H, s, k, V.device)
+    if partial is not None:
+        _krylov_vector("partial", partial, partial.numel() if isinstance(partial, torch.Tensor) else -1, V.device)
+        if partial.numel() < s * -(-n // krylov_limits()["cell"]):
+            raise SblasError("partial is too short")
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_gmres_multi_project_f64(-1, _stream(stream), n, s, k, V.data_ptr() if n else None, ldv, stride, H.data_ptr(), ldh,
+                                                      W.data_ptr() if n else None, ldw, _gmres_multi_scalars(scalars, s, V.device),
+                                                      partial.data_ptr() if partial is not None and partial.numel() else None),
+              "sblas_hip_gmres_multi_project_f64")
+    return W
+
+
+def gmres_multi_combine(V, Y, out=None, scalars=None, stream=None):
+    """U[:, c] = Y[c, 0] V[0][:, c], then U[:, c] = U[:, c] + Y[c, l] V[l][:, c] ascending, rounded product and rounded sum
+    (sblas_hip_gmres_multi_combine_f64) -> U (out when given, an (n, s) row-major block that is no part of V)."""
+    import torch
+    if out is None:
+        if not isinstance(V, torch.Tensor) or V.dim() != 3:
+            raise SblasError("V must be a float64 tensor of shape (blocks, n, nrhs)")
+        out = torch.zeros(tuple(V.shape[1:]), dtype=torch.float64, device=V.device)
+    k, n, s, ldv, stride, ldu = _gmres_multi_blocks(V, out, "out")
+    ldy = _gmres_multi_coef("Y", Y, s, k, V.device)
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_gmres_multi_combine_f64(-1, _stream(stream), n, s, k, V.data_ptr() if n else None, ldv, stride, Y.data_ptr(), ldy,
+                                                      out.data_ptr() if n else None, ldu, _gmres_multi_scalars(scalars, s, V.device)),
+              "sblas_hip_gmres_multi_combine_f64")
+    return out
+
+
+class GmresMultiPlan:
+    """Right-preconditioned restarted GMRES(restart) for A X = B with nrhs right-hand sides at once on the n x n CSR
+    structure (rowptr, colidx), int32 indices (sblas_hip_gmres_multi_plan_create): nrhs independent GMRES(m) recurrences
+    that share A and run in lockstep, one SpMM per Arnoldi step instead of nrhs SpMVs.  A need not be symmetric.  precond:
+    as KrylovMultiPlan's -- None, "jacobi" (start / solve take dinv), an AmgPlan after its setup() with "jacobi" or "l1"
+    (its block cycle), or the pair of SptrsvPlans ilu.solvers() returns (the two tiled solves; start / solve take lu).  B
+    and X are (n, nrhs) float64 GPU tensors, row-major: contiguous, or a column slice of a wider tensor.  The plan owns an
+    SpMM plan for this width, restart + 1 basis blocks, the work blocks, and one scalar and one small-matrix block a column.
+
+    start() forms every r_c = b_c - A x_c and v_0; iterate(k) enqueues k lockstep steps -- a close and a restart behind
+    every restart-th, a close at its end -- without allocating or synchronising (graph-capturable); status() is the one
+    call that synchronises.  Every column has its own Hessenberg column, rotations and stopping test: once column c's
+    test is met (or it breaks down) nothing reads or writes column c again but the close that applies its pending
+    columns, so every column's x, count, |r| and restart count do not depend on check_every.  A solve equals the lockstep
+    loop composed of the SpMM, the pinned dot per column, numpy updates and the scalar step bit for bit; it is NOT
+    promised to equal a GmresPlan solve of one column, or a batch of another width."""
+
+    def __init__(self, n, rowptr, colidx, nrhs, restart=30, precond=None, stream=None):
+        import torch
+        self.handle = None
+        self.nrhs = _multi_width(nrhs)
+        if isinstance(restart, bool) or not isinstance(restart, int) or not 1 <= restart <= gmres_multi_limits()["max_restart"]:
+            raise SblasError("restart must be an integer in [1, %d], not %r" % (gmres_multi_limits()["max_restart"], restart))
+        self.restart = restart
+        self.precond, self.precond_kind = precond, _multi_precond(precond)
+        self.n, self.nnz = n, _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        self._keep = None
+        lower = upper = None
+        if isinstance(precond, AmgPlan):                                    # self.precond keeps the plans alive
+            if precond.n != n or precond.rowptr.data_ptr() != rowptr.data_ptr() or precond.colidx.data_ptr() != colidx.data_ptr():
+                raise SblasError("the AmgPlan was made for another structure than this solver's (rowptr, colidx)")
+            lower = precond.handle
+        elif self.precond_kind == PRECOND_ILU0:
+            for q in precond:
+                if q.n != n or q.rowptr.data_ptr() != rowptr.data_ptr() or q.colidx.data_ptr() != colidx.data_ptr():
+                    raise SblasError("the SptrsvPlans were made for another structure than this solver's (rowptr, colidx)")
+            if not (precond[0].lower and precond[0].unit_diag and not precond[1].lower and not precond[1].unit_diag):
+                raise SblasError("the pair must be (lower with a unit diagonal, upper with a stored one), as Ilu0Plan.solvers() gives it")
+            lower, upper = precond[0].handle, precond[1].handle
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            if isinstance(precond, AmgPlan):
+                precond.reserve(self.nrhs, stream=stream)
+            rc = lib().sblas_hip_gmres_multi_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
+                                                         colidx.data_ptr() if self.nnz else None, self.nrhs, restart, self.precond_kind,
+                                                         lower, upper, C.byref(h))
+        check(rc, "sblas_hip_gmres_multi_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 16)()
+        check(lib().sblas_hip_gmres_multi_plan_info(self.handle, out), "sblas_hip_gmres_multi_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), restart=int(out[2]), precond=_PRECOND_NAME[out[3]], nrhs=int(out[4]), blocks=int(out[5]),
+                    block_bytes=int(out[6]), partial_bytes=int(out[7]), scalar_bytes=int(out[8]), matrix_bytes=int(out[9]),
+                    workspace_bytes=int(out[10]), bytes=int(out[11]), step_launches=int(out[12]), close_launches=int(out[13]),
+                    restart_launches=int(out[14]), cycle_launches=int(out[15]))
+
+    def start(self, val, B, X, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
+        """Begins a solve: X on entry holds the initial guesses and is updated in place as cycles close.  dinv: the
+        inverse diagonal (precond "jacobi"); lu: the ILU(0) factor (precond a pair of SptrsvPlans).  Every refusal comes
+        before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        ldb = _krylov_block("B", B, self.n, self.nrhs, self.device)
+        ldx = _krylov_block("X", X, self.n, self.nrhs, self.device)
+        pre = None
+        if self.precond_kind == PRECOND_JACOBI:
+            if dinv is None:
+                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
+            _krylov_vector("dinv", dinv, self.n, self.device)
+            pre = dinv
+        elif self.precond_kind == PRECOND_ILU0:
+            if lu is None:
+                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
+            _krylov_vector("lu", lu, self.nnz, self.device)
+            pre = lu
+        elif self.precond_kind == PRECOND_AMG:
+            info = self.precond.info()
+            if not info["ready"]:
+                raise SblasError("the AmgPlan needs setup() before a solve")
+            if info["smoother"] == "chebyshev":
+                raise SblasError("the Chebyshev smoother has no block cycle: set the AmgPlan up with 'jacobi' or 'l1'")
+        if self.n and _blocks_overlap(X, ldx, B, ldb, self.n, self.nrhs):
+            raise SblasError("X must not overlap B")
+        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
+            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_gmres_multi_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                                   pre.data_ptr() if pre is not None and pre.numel() else None,
+                                                   B.data_ptr() if self.n else None, ldb, X.data_ptr() if self.n else None, ldx,
+                                                   float(rtol), float(atol), int(max_iter))
+        check(rc, "sblas_hip_gmres_multi_start")
+        self._keep = (val, B, X, pre)
+
+    def iterate(self, k, stream=None):
+        """Enqueues k lockstep steps: allocates nothing, never synchronises, graph-capturable as a chain."""
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_gmres_multi_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_gmres_multi_iterate")
+
+    def block(self, k, stream=None):
+        """A copy of block k of the plan as an (n, nrhs) tensor (sblas_hip_gmres_multi_plan_block): 0 .. restart are the
+        basis blocks V_k, then W, U, Z.  Stream-ordered; allocates its result."""
+        import torch
+        out = torch.empty((self.n, self.nrhs), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_gmres_multi_plan_block(self.handle, _stream(stream), int(k), out.data_ptr() if self.n else None),
+                  "sblas_hip_gmres_multi_plan_block")
+        return out
+
+    def status(self, stream=None):
+        """Copies the scalar blocks back and synchronises the stream -> dict of per-column numpy arrays (code, iterations,
+        rnorm, bnorm, restarts, columns, eta, which), lists status and breakdown (the names, as GmresPlan.status gives
+        them) and running, the count of columns still running."""
+        import torch
+        out = (C.c_double * (8 * self.nrhs))()
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_gmres_multi_status(self.handle, _stream(stream), out), "sblas_hip_gmres_multi_status")
+        a = np.array(out, np.float64).reshape(self.nrhs, 8)
+        code, which = a[:, 0].astype(np.int64), a[:, 7].astype(np.int64)
+        return dict(code=code, iterations=a[:, 1].astype(np.int64), rnorm=a[:, 2].copy(), bnorm=a[:, 3].copy(),
+                    restarts=a[:, 4].astype(np.int64), columns=a[:, 5].astype(np.int64), eta=a[:, 6].copy(), which=which,
+                    status=[KRYLOV_STATUS[int(c)] for c in code], breakdown=[GMRES_DENOM[int(w)] for w in which],
+                    running=int((code == KRYLOV_RUNNING).sum()))
+
+    def solve(self, val, B, X=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
+        """start(), then iterate(check_every) / status() until no column is running -> (X, status dict).  X: the initial
+        guesses, updated in place (zeros made here when None).  No column's result depends on check_every."""
+        import torch
+        if int(check_every) < 1:
+            raise SblasError("check_every must be at least 1")
+        if X is None:
+            _krylov_block("B", B, self.n, self.nrhs, self.device)
+            X = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=self.device)
+        self.start(val, B, X, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
+        while True:
+            self.iterate(int(check_every), stream=stream)
+            st = self.status(stream=stream)
+            if st["running"] == 0:
+                return X, st
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_gmres_multi_plan_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def gmres_multi(A, B, precond=None, restart=30, X=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):
+    """X with A X = B by right-preconditioned restarted GMRES(restart) on all columns of B at once, one shot, as
+    pcg_multi(): precond None, "jacobi", "amg" or "amg_smoothed"; A need not be symmetric and max_iter counts Arnoldi
+    steps.  -> (X, status dict of per-column arrays).  The plans made here are destroyed before returning."""
+    return _krylov_multi_one_shot(None, A, B, precond, X, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every),
+                                  make=lambda n, rowptr, colidx, nrhs, pre: GmresMultiPlan(n, rowptr, colidx, nrhs, restart=restart, precond=pre))
 
 
 # ------------------------------------------------------------------------------------------
