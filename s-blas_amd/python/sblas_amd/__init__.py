@@ -3719,6 +3719,8 @@ def _krylov_block(name, t, n, s, device=None):
         raise SblasError("%s must be a (%d, %d) tensor, got shape %s" % (name, n, s, tuple(t.shape)))
     if device is not None and t.device != device:
         raise SblasError("%s is on %s, the plan on %s" % (name, t.device, device))
+    if n == 0:                                                             # without rows there are no strides to read (an empty
+        return max(int(s), 1)                                              # tensor that came from numpy has strides (0, 0))
     ld = t.stride(0) if n > 1 else max(t.stride(0), s)
     if (s > 1 and t.stride(1) != 1) or ld < s:
         raise SblasError("%s must be row-major with a leading dimension of at least %d, got strides %s" % (name, s, tuple(t.stride())))

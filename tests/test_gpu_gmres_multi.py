@@ -614,6 +614,28 @@ def test_edges_per_column(env):
     plan.destroy()
 
 
+def test_one_atol_governs_some_columns_and_rtol_the_others(env):
+    """b, 1e3 b and 1e-3 b under one atol = 3e-7 |b| with rtol = 1e-8: rtol |b_j| is 1e-5, 1e-8 and 1e-11 |b|, so the first
+    column stops on rtol |b_j| and the other two on atol: max(rtol |b_j|, atol) per column"""
+    S, torch, cuda = env
+    A = n, rp, ci, val = KN.convection_diffusion(24)
+    b = np.random.default_rng(17).standard_normal(n)
+    B = np.ascontiguousarray(np.stack([1e3 * b, b, 1e-3 * b], axis=1))
+    X0 = np.zeros_like(B)
+    atol = 30.0 * RTOL * float(np.linalg.norm(b))
+    P = Parts(env, A, 3, "jacobi")
+    want = GMC.composed_gmres_multi(P.matvec, P.apply, P.dot, B, X0, 30, RTOL, 1000, atol=atol)
+    assert [w["status"] for w in want] == [GN.CONVERGED] * 3
+    assert RTOL * want[0]["bnorm"] > atol > RTOL * want[1]["bnorm"] > RTOL * want[2]["bnorm"]
+    assert want[0]["rnorm"] <= RTOL * want[0]["bnorm"] and all(RTOL * w["bnorm"] < w["rnorm"] <= atol for w in want[1:])
+    assert want[2]["iterations"] < want[1]["iterations"] < want[0]["iterations"]
+    plan = S.GmresMultiPlan(n, P.drp, P.dci, 3, restart=30, precond=P.seat)
+    X, st = plan.solve(P.dval, up(torch, cuda, B)[0], X=up(torch, cuda, X0)[0], rtol=RTOL, atol=atol, max_iter=1000, check_every=5, **P.kw())
+    assert_solved(st, X, dict(names=["1e3 b", "b", "1e-3 b"], want=want))
+    plan.destroy()
+    P.destroy()
+
+
 def test_refusals_come_before_any_launch(env):
     S, torch, cuda = env
     E = S.SblasError

@@ -541,6 +541,50 @@ def test_edges_per_column(env, lap):
     plan.destroy()
 
 
+@pytest.mark.parametrize("method", ["pcg", "bicgstab"])
+def test_one_atol_governs_some_columns_and_rtol_the_others(env, method):
+    """b, 1e3 b and 1e-3 b under one atol = 3e-9 |b| with rtol = 1e-10: rtol |b_j| is 1e-7, 1e-10 and 1e-13 |b|, so the
+    first column stops on rtol |b_j| and the other two on atol -- max(rtol |b_j|, atol) per column, not atol wherever it
+    is given and not one tolerance for the block.  Every column equals the composition, and the stops are where the
+    tolerances put them: the scaled copies of one right-hand side need more iterations the tighter their relative bound."""
+    S, torch, cuda = env
+    A = n, rp, ci, val = MATRICES[method]()
+    b = np.random.default_rng(17).standard_normal(n)
+    B = np.ascontiguousarray(np.stack([1e3 * b, b, 1e-3 * b], axis=1))
+    X0 = np.zeros_like(B)
+    atol = 3e-9 * float(np.linalg.norm(b))
+    P = MultiParts(env, A, 3, True)
+    loop = MC.composed_pcg_multi if method == "pcg" else MC.composed_bicgstab_multi
+    want = loop(P.matvec, P.apply, P.dot, B, X0, RTOL, 1000, atol=atol)
+    assert [w.status for w in want] == ["converged"] * 3
+    assert RTOL * want[0].bnorm > atol > RTOL * want[1].bnorm > RTOL * want[2].bnorm
+    assert want[0].rnorm <= RTOL * want[0].bnorm and all(RTOL * w.bnorm < w.rnorm <= atol for w in want[1:])
+    assert want[2].iterations < want[1].iterations and want[2].iterations < want[0].iterations     # 3e-6, 3e-9 and 1e-10 relative
+    plan = S.KrylovMultiPlan(n, P.drp, P.dci, 3, method=method, precond="jacobi")
+    X, st = plan.solve(P.dval, up(torch, cuda, B)[0], X=up(torch, cuda, X0)[0], dinv=P.ddinv, rtol=RTOL, atol=atol, max_iter=1000, check_every=5)
+    assert_solved(S, st, X, dict(names=["1e3 b", "b", "1e-3 b"], want=want))
+    plan.destroy()
+    P.destroy()
+
+
+def test_an_empty_block_that_came_from_numpy_is_taken(env):
+    """n = 0: a (0, s) tensor made from a numpy array has strides (0, 0), where torch.zeros((0, s)) has (s, 1).  Without
+    rows there are no strides to read: the plans, the one-shots and AmgPlan.apply_multi take either (found by
+    tools/fuzz_multi.py, case 3 of seed 5: the one-shots refused the block as not row-major)."""
+    S, torch, cuda = env
+    rp0, ci0 = torch.zeros(1, dtype=torch.int32, device=cuda), torch.zeros(0, dtype=torch.int32, device=cuda)
+    v0 = torch.zeros(0, dtype=torch.float64, device=cuda)
+    e = torch.from_numpy(np.zeros((0, 8))).to(cuda)
+    assert tuple(e.stride()) == (0, 0)
+    for call in (S.pcg_multi, S.bicgstab_multi, S.gmres_multi):
+        X, st = call((0, rp0, ci0, v0), e, X=e.clone())
+        assert tuple(X.shape) == (0, 8) and st["status"] == ["converged"] * 8 and st["running"] == 0 and not st["iterations"].any()
+    amg = S.AmgPlan(0, rp0, ci0)
+    amg.setup(v0)
+    assert tuple(amg.apply_multi(e).shape) == (0, 8)
+    amg.destroy()
+
+
 def test_refusals_come_before_any_launch(env, lap):
     S, torch, cuda = env
     E = S.SblasError
