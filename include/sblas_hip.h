@@ -1270,4 +1270,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #include "sblas_hip_amg_multi.h"
 #include "sblas_hip_sptrsm_tile.h"
 #include "sblas_hip_gmres_multi.h"
+#include "sblas_hip_geam.h"
 #endif /* SBLAS_HIP_H */

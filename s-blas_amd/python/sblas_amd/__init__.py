@@ -116,6 +116,12 @@ EXPORTS_GMRES_MULTI = [
     "sblas_hip_gmres_multi_plan_create", "sblas_hip_gmres_multi_plan_info", "sblas_hip_gmres_multi_plan_block",
     "sblas_hip_gmres_multi_plan_destroy", "sblas_hip_gmres_multi_start", "sblas_hip_gmres_multi_iterate", "sblas_hip_gmres_multi_status",
 ]
+# what include/sblas_hip_geam.h declares (CSR addition C = alpha * A + beta * B on a plan that re-adds)
+EXPORTS_GEAM = [
+    "sblas_geam_check_nnz", "sblas_geam_ref",
+    "sblas_hip_geam_plan_create", "sblas_hip_geam_plan_info", "sblas_hip_geam_plan_csr", "sblas_hip_geam_plan_maps",
+    "sblas_hip_geam_plan_numeric", "sblas_hip_geam_plan_destroy",
+]
 
 
 class SblasError(RuntimeError):
@@ -622,6 +628,22 @@ def lib():
     L.sblas_hip_gmres_multi_iterate.argtypes = [vp, vp, i64]
     L.sblas_hip_gmres_multi_status.restype = C.c_int
     L.sblas_hip_gmres_multi_status.argtypes = [vp, vp, C.POINTER(f64)]
+    L.sblas_geam_check_nnz.restype = C.c_int
+    L.sblas_geam_check_nnz.argtypes = [i64]
+    L.sblas_geam_ref.restype = C.c_int
+    L.sblas_geam_ref.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, f64, f64, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.sblas_hip_geam_plan_create.restype = C.c_int
+    L.sblas_hip_geam_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.sblas_hip_geam_plan_info.restype = C.c_int
+    L.sblas_hip_geam_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_geam_plan_csr.restype = C.c_int
+    L.sblas_hip_geam_plan_csr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_geam_plan_maps.restype = C.c_int
+    L.sblas_hip_geam_plan_maps.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_geam_plan_numeric.restype = C.c_int
+    L.sblas_hip_geam_plan_numeric.argtypes = [vp, vp, vp, vp, f64, f64, vp]
+    L.sblas_hip_geam_plan_destroy.restype = C.c_int
+    L.sblas_hip_geam_plan_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -790,6 +812,40 @@ def spgemm_group_width(products, a_len, span):
 def spgemm_check_nnz(nnz_c):
     """The return code of the plan's check on the counted nnz(C) (0: it fits an int32 index)."""
     return int(lib().sblas_hip_spgemm_check_nnz(int(nnz_c)))
+
+
+GEAM_AUTO, GEAM_GENERAL, GEAM_SCATTER = 0, 1, 2
+GEAM_PATH_SORTED, GEAM_PATH_GENERAL = 0, 1
+
+
+def geam_check_nnz(nnz_c):
+    """0 when nnz_c fits an int32 index, else the library's invalid-argument code (sblas_geam_check_nnz)."""
+    return int(lib().sblas_geam_check_nnz(int(nnz_c)))
+
+
+def geam_ref(rows, cols, rowptr_a, colidx_a, val_a, rowptr_b, colidx_b, val_b, alpha=1.0, beta=1.0):
+    """The GEAM contract as the library's scalar loop over numpy arrays (sblas_geam_ref; no GPU) -> (rowptr_c, colidx_c,
+    val_c, dest_a, dest_b): C = alpha * A + beta * B with A's terms of a row before B's, and the entry of C where each
+    input entry lands."""
+    rpa, rpb = np.ascontiguousarray(rowptr_a, np.int32), np.ascontiguousarray(rowptr_b, np.int32)
+    cia, cib = np.ascontiguousarray(colidx_a, np.int32), np.ascontiguousarray(colidx_b, np.int32)
+    va, vb = np.ascontiguousarray(val_a, np.float64), np.ascontiguousarray(val_b, np.float64)
+    if len(rpa) != rows + 1 or len(rpb) != rows + 1:
+        raise SblasError("rowptr_a and rowptr_b need rows + 1 = %d entries" % (rows + 1))
+    if len(va) != len(cia) or len(vb) != len(cib):
+        raise SblasError("val_a / val_b have %d / %d entries, colidx_a / colidx_b %d / %d" % (len(va), len(vb), len(cia), len(cib)))
+    if (rows and (int(rpa[-1]) > len(cia) or int(rpb[-1]) > len(cib))):
+        raise SblasError("a rowptr ends beyond its colidx")
+    total = len(cia) + len(cib)
+    rowptr_c = np.zeros(rows + 1, np.int32)
+    colidx_c, val_c = np.zeros(total, np.int32), np.zeros(total, np.float64)
+    dest_a, dest_b = np.zeros(len(cia), np.int32), np.zeros(len(cib), np.int32)
+    nnz_c = C.c_int64(0)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    check(lib().sblas_geam_ref(rows, cols, rpa.ctypes.data, ptr(cia), ptr(va), rpb.ctypes.data, ptr(cib), ptr(vb), float(alpha), float(beta),
+                               rowptr_c.ctypes.data, ptr(colidx_c), ptr(val_c), ptr(dest_a), ptr(dest_b), C.byref(nnz_c)), "sblas_geam_ref")
+    n = int(nnz_c.value)
+    return rowptr_c, colidx_c[:n].copy(), val_c[:n].copy(), dest_a, dest_b
 
 
 # triangular solves: fill, diagonal, plan modes and launch kinds (SBLAS_FILL_*, SBLAS_DIAG_*, SBLAS_SPTRSV_* in sblas_hip.h)
@@ -2212,6 +2268,143 @@ def spgemm(A, B, stream=None):
             stream.synchronize()
         else:
             import torch
+            torch.cuda.current_stream().synchronize()
+    finally:
+        plan.destroy()
+    return rowptr_c, colidx_c, val_c
+
+
+# ------------------------------------------------------------------------------------------
+# GEAM: C = alpha * A + beta * B for two CSR matrices (sblas_hip_geam_plan_*)
+# ------------------------------------------------------------------------------------------
+class GeamPlan:
+    """The structure of C = alpha * A + beta * B (sblas_hip_geam_plan_create): A and B are rows x cols CSR with int32
+    indices; rows may be unsorted and hold duplicates.  Creation checks both structures on the device (a bad one raises)
+    and builds C's rowptr and colidx and the maps dest_a / dest_b, which the plan owns; it keeps neither A's nor B's
+    structure.  add(val_a, val_b, alpha, beta) fills C's values; it allocates nothing inside the library and is
+    graph-capturable.  When every row of both operands is strictly ascending the plan takes the sorted path (one launch
+    over C's entries; scatter=True keeps the two-launch ordered scatter over the maps instead, the same bits, slower where
+    entries match: DESIGN.md 3.34); otherwise, or with general=True, it owns a CooPlan-like sort of the concatenated triplets.
+    destroy() / garbage collection frees the device buffers.
+
+    A time step on two assembled matrices, M + dt K with new values every step:
+        m, k = CooPlan(n, n, mrow, mcol, dup="sum"), CooPlan(n, n, krow, kcol, dup="sum")
+        plan = GeamPlan(n, n, m.csr()[0], m.csr()[1], k.csr()[0], k.csr()[1])
+        rowptr, colidx = plan.csr()                          # what Ilu0Plan / AmgPlan / KrylovPlan are built on
+        val = plan.add(m.assemble(mval), k.assemble(kval), 1.0, dt)
+    A shift A + sigma I:
+        eye = torch.arange(n + 1, dtype=torch.int32, device=dev)
+        plan = GeamPlan(n, n, rowptr, colidx, eye, eye[:n])
+        val = plan.add(val_a, torch.ones(n, dtype=torch.float64, device=dev), 1.0, sigma)
+    Symmetrising, A + A^T on the transpose plan's arrays:
+        t = TransposePlan(n, n, rowptr, colidx, val_a)
+        colptr, rowidx, val_t = t.csc()
+        plan = GeamPlan(n, n, rowptr, colidx, colptr, rowidx)
+        val = plan.add(val_a, val_t)"""
+
+    def __init__(self, rows, cols, rowptr_a, colidx_a, rowptr_b, colidx_b, general=False, stream=None, scatter=False):
+        import torch
+        self.rows, self.cols = rows, cols
+        if general and scatter:
+            raise SblasError("scatter is a form of the sorted path: general and scatter exclude each other")
+        self.handle = None
+        for name, t in (("rowptr_a", rowptr_a), ("colidx_a", colidx_a), ("rowptr_b", rowptr_b), ("colidx_b", colidx_b)):
+            if not isinstance(t, torch.Tensor):
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            _typed(name, t, torch.int32)
+        if rowptr_a.numel() != rows + 1 or rowptr_b.numel() != rows + 1:
+            raise SblasError("rowptr_a and rowptr_b need rows + 1 = %d entries, not %d and %d" % (rows + 1, rowptr_a.numel(), rowptr_b.numel()))
+        for name, t in (("rowptr_a", rowptr_a), ("colidx_a", colidx_a), ("rowptr_b", rowptr_b), ("colidx_b", colidx_b)):
+            if not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            if t.device != rowptr_a.device:
+                raise SblasError("%s is on %s, rowptr_a on %s" % (name, t.device, rowptr_a.device))
+        self.device = rowptr_a.device
+        self.nnz_a, self.nnz_b = int(colidx_a.numel()), int(colidx_b.numel())
+        h = C.c_void_p()
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        with torch.cuda.device(self.device):
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                ends = (int(rowptr_a[rows].item()), int(rowptr_b[rows].item()))   # the library reads colidx as far as rowptr says
+            if ends != (self.nnz_a, self.nnz_b):
+                raise SblasError("colidx_a / colidx_b have %d / %d entries, the row pointers end at %d / %d" % ((self.nnz_a, self.nnz_b) + ends))
+            check(lib().sblas_hip_geam_plan_create(-1, _stream(stream), rows, cols, ptr(rowptr_a), ptr(colidx_a), ptr(rowptr_b), ptr(colidx_b),
+                                                   GEAM_GENERAL if general else GEAM_SCATTER if scatter else GEAM_AUTO, C.byref(h)),
+                  "sblas_hip_geam_plan_create")
+        self.handle = h
+        self.nnz_c = self.info()["nnz_c"]
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_geam_plan_info(self.handle, out), "sblas_hip_geam_plan_info")
+        return dict(rows=int(out[0]), cols=int(out[1]), nnz_a=int(out[2]), nnz_b=int(out[3]), nnz_c=int(out[4]), matched=int(out[5]),
+                    path="sorted" if out[6] == GEAM_PATH_SORTED else "general", a_ascending=bool(out[7]), b_ascending=bool(out[8]),
+                    launches=int(out[9]), bytes=int(out[10]), general=out[11] == GEAM_GENERAL,
+                    scatter=out[11] == GEAM_SCATTER)
+
+    def _views(self, call, what, sizes):
+        import torch
+        ptrs = [C.c_void_p() for _ in sizes]
+        check(call(self.handle, *[C.byref(p) for p in ptrs]), what)
+        def one(p, n):
+            if n == 0:
+                return torch.empty(0, dtype=torch.int32, device=self.device)
+            return torch.as_tensor(_DeviceArray(p.value, n, "<i4"), device=self.device)
+        return tuple(one(p, n) for p, n in zip(ptrs, sizes))
+
+    def csr(self):
+        """(rowptr_c, colidx_c): torch views of the plan's device arrays; they live as long as the plan."""
+        return self._views(lib().sblas_hip_geam_plan_csr, "sblas_hip_geam_plan_csr", (self.rows + 1, self.nnz_c))
+
+    def maps(self):
+        """(dest_a, dest_b): the entry of C where each entry of A and of B lands; torch views that live as long as the plan."""
+        return self._views(lib().sblas_hip_geam_plan_maps, "sblas_hip_geam_plan_maps", (self.nnz_a, self.nnz_b))
+
+    def add(self, val_a, val_b, alpha=1.0, beta=1.0, out=None, stream=None):
+        """C's values (nnz_c of them) for the values val_a and val_b in A's and B's stored order, written to `out` when
+        given; `out` may not overlap val_a or val_b."""
+        import torch
+        _typed("val_a", val_a, torch.float64), _typed("val_b", val_b, torch.float64)
+        if val_a.numel() != self.nnz_a or val_b.numel() != self.nnz_b:
+            raise SblasError("val_a / val_b have %d / %d entries, the plan %d / %d" % (val_a.numel(), val_b.numel(), self.nnz_a, self.nnz_b))
+        if out is None:
+            out = torch.empty(self.nnz_c, dtype=torch.float64, device=self.device)
+        _typed("out", out, torch.float64)
+        if out.numel() < self.nnz_c:
+            raise SblasError("out has %d entries, C %d" % (out.numel(), self.nnz_c))
+        pa = _dev_ptr(val_a, torch.float64, "val_a") if self.nnz_a else None
+        pb = _dev_ptr(val_b, torch.float64, "val_b") if self.nnz_b else None
+        po = _dev_ptr(out, torch.float64, "out") if self.nnz_c else None
+        check(lib().sblas_hip_geam_plan_numeric(self.handle, _stream(stream), pa, pb, float(alpha), float(beta), po),
+              "sblas_hip_geam_plan_numeric")
+        return out
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_geam_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def csr_add(A, B, alpha=1.0, beta=1.0, stream=None):
+    """C = alpha * A + beta * B, one shot: A = (rows, cols, rowptr, colidx, val) and B likewise as GPU tensors -> (rowptr_c,
+    colidx_c, val_c), tensors of their own (the plan made here is destroyed before returning)."""
+    rows, cols, rowptr_a, colidx_a, val_a = A
+    rows_b, cols_b, rowptr_b, colidx_b, val_b = B
+    if rows != rows_b or cols != cols_b:
+        raise SblasError("A is %d x %d, B is %d x %d" % (rows, cols, rows_b, cols_b))
+    import torch
+    plan = GeamPlan(rows, cols, rowptr_a, colidx_a, rowptr_b, colidx_b, stream=stream)
+    try:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(plan.device)):
+            rowptr_c, colidx_c = plan.csr()                  # val_c is allocated, and the copies are made, on the stream that adds
+            val_c = plan.add(val_a, val_b, alpha, beta, stream=torch.cuda.current_stream())
+            rowptr_c, colidx_c = rowptr_c.clone(), colidx_c.clone()
             torch.cuda.current_stream().synchronize()
     finally:
         plan.destroy()

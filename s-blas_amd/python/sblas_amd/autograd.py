@@ -15,13 +15,15 @@ sddmm is the same pair read the other way: dX = A(dout) Y through the SpMM path,
 TransposePlan.  softmax keeps its output and runs the library's softmax backward on it.  attention keeps Q, K, V and two
 doubles per row; its backward recomputes the probabilities, takes dQ from the fused kernel and forms dK = A(dS)^T Q and
 dV = A(P)^T dO through the TransposePlan, from P and dS that live only inside that backward.
+csr_add(plan, val_a, val_b, alpha, beta), a function beside the operator, is the CSR sum on a GeamPlan, differentiable in
+both value arrays: its backward is a gather over the plan's maps.
 Backward of backward is not supported.  float64 values, int32 indices, GPU tensors only: there is no CPU path.
 torch is imported here, not by the package."""
 import torch
 
-from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, csr_attention,
+from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, GeamPlan, SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, csr_attention,
                csr_attention_backward, csr_attention_workspace_bytes, csr_softmax, csr_softmax_backward,
-               csr_softmax_workspace_bytes, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
+               csr_softmax_workspace_bytes, gather, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
 
 
 class CsrOperator:
@@ -325,3 +327,35 @@ class _Attention(torch.autograd.Function):
         dK = op._grad_dense_mm(dS, Q) if need_k else None    # A(dS)^T Q
         dV = op._grad_dense_mm(P, dO) if need_v else None    # A(P)^T dO
         return dQ, dK, dV, None, None
+
+
+class _CsrAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val_a, val_b, plan, alpha, beta):
+        ctx.plan, ctx.alpha, ctx.beta = plan, alpha, beta
+        return plan.add(val_a.detach(), val_b.detach(), alpha, beta)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dC):
+        plan = ctx.plan
+        dC = _laid_out(dC)
+        grads = []
+        for need, dest, scale in zip(ctx.needs_input_grad[:2], plan.maps(), (ctx.alpha, ctx.beta)):
+            g = None
+            if need:                                     # dval[e] = scale * dC[dest[e]]: the library's gather, then one rounding
+                g = torch.empty(dest.numel(), dtype=torch.float64, device=plan.device)
+                gather(dest, dC, g)
+                g.mul_(scale)
+            grads.append(g)
+        return grads[0], grads[1], None, None, None
+
+
+def csr_add(plan, val_a, val_b, alpha=1.0, beta=1.0):
+    """C's values of alpha * A + beta * B on a GeamPlan, differentiable in val_a and val_b (alpha and beta are plain
+    numbers): dval_a = alpha * dC[dest_a] and dval_b = beta * dC[dest_b] over the plan's maps, so a run of duplicates
+    that shares one entry of C shares its gradient.  Only the halves autograd asks for are computed; backward of backward
+    is not supported."""
+    if not isinstance(plan, GeamPlan):
+        raise SblasError("csr_add needs a GeamPlan")
+    return _CsrAdd.apply(val_a, val_b, plan, float(alpha), float(beta))
