@@ -1271,4 +1271,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #include "sblas_hip_sptrsm_tile.h"
 #include "sblas_hip_gmres_multi.h"
 #include "sblas_hip_geam.h"
+#include "sblas_hip_mspgemm.h"
 #endif /* SBLAS_HIP_H */

@@ -122,6 +122,11 @@ EXPORTS_GEAM = [
     "sblas_hip_geam_plan_create", "sblas_hip_geam_plan_info", "sblas_hip_geam_plan_csr", "sblas_hip_geam_plan_maps",
     "sblas_hip_geam_plan_numeric", "sblas_hip_geam_plan_destroy",
 ]
+# what include/sblas_hip_mspgemm.h declares (masked SpGEMM out = M o (X Y^T) on a CSR pattern, on a plan that re-multiplies)
+EXPORTS_MSPGEMM = [
+    "sblas_mspgemm_limits", "sblas_mspgemm_ref",
+    "sblas_hip_mspgemm_plan_create", "sblas_hip_mspgemm_plan_info", "sblas_hip_mspgemm_plan_numeric", "sblas_hip_mspgemm_plan_destroy",
+]
 
 
 class SblasError(RuntimeError):
@@ -644,6 +649,18 @@ def lib():
     L.sblas_hip_geam_plan_numeric.argtypes = [vp, vp, vp, vp, f64, f64, vp]
     L.sblas_hip_geam_plan_destroy.restype = C.c_int
     L.sblas_hip_geam_plan_destroy.argtypes = [vp]
+    L.sblas_mspgemm_limits.restype = C.c_int
+    L.sblas_mspgemm_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_mspgemm_ref.restype = C.c_int
+    L.sblas_mspgemm_ref.argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sblas_hip_mspgemm_plan_create.restype = C.c_int
+    L.sblas_hip_mspgemm_plan_create.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.sblas_hip_mspgemm_plan_info.restype = C.c_int
+    L.sblas_hip_mspgemm_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_mspgemm_plan_numeric.restype = C.c_int
+    L.sblas_hip_mspgemm_plan_numeric.argtypes = [vp, vp, vp, vp, vp]
+    L.sblas_hip_mspgemm_plan_destroy.restype = C.c_int
+    L.sblas_hip_mspgemm_plan_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -846,6 +863,37 @@ def geam_ref(rows, cols, rowptr_a, colidx_a, val_a, rowptr_b, colidx_b, val_b, a
                                rowptr_c.ctypes.data, ptr(colidx_c), ptr(val_c), ptr(dest_a), ptr(dest_b), C.byref(nnz_c)), "sblas_geam_ref")
     n = int(nnz_c.value)
     return rowptr_c, colidx_c[:n].copy(), val_c[:n].copy(), dest_a, dest_b
+
+
+MSPGEMM_AUTO, MSPGEMM_GENERAL = 0, 1
+MSPGEMM_PATH_SORTED, MSPGEMM_PATH_GENERAL = 0, 1
+
+
+def mspgemm_limits():
+    """The sizes the masked SpGEMM's kernels are built on (sblas_mspgemm_limits): the longest X row a wave stages in LDS
+    and the mask entries one workgroup takes."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_mspgemm_limits(out), "sblas_mspgemm_limits")
+    return dict(lds_row=int(out[0]), threads=int(out[1]))
+
+
+def mspgemm_ref(m, n, k, rowptr_m, colidx_m, rowptr_x, colidx_x, val_x, rowptr_y, colidx_y, val_y):
+    """The masked SpGEMM contract as the library's scalar loop over numpy arrays (sblas_mspgemm_ref; no GPU) -> out, one
+    double per stored mask entry: out = M o (X Y^T) with X m x k, Y n x k and the mask m x n."""
+    rpm, rpx, rpy = (np.ascontiguousarray(a, np.int32) for a in (rowptr_m, rowptr_x, rowptr_y))
+    cim, cix, ciy = (np.ascontiguousarray(a, np.int32) for a in (colidx_m, colidx_x, colidx_y))
+    vx, vy = np.ascontiguousarray(val_x, np.float64), np.ascontiguousarray(val_y, np.float64)
+    if len(rpm) != m + 1 or len(rpx) != m + 1 or len(rpy) != n + 1:
+        raise SblasError("rowptr_m and rowptr_x need m + 1 = %d entries and rowptr_y n + 1 = %d" % (m + 1, n + 1))
+    if len(vx) != len(cix) or len(vy) != len(ciy):
+        raise SblasError("val_x / val_y have %d / %d entries, colidx_x / colidx_y %d / %d" % (len(vx), len(vy), len(cix), len(ciy)))
+    if int(rpm[-1]) > len(cim) or int(rpx[-1]) > len(cix) or int(rpy[-1]) > len(ciy):
+        raise SblasError("a rowptr ends beyond its colidx")
+    out = np.zeros(len(cim), np.float64)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    check(lib().sblas_mspgemm_ref(m, n, k, rpm.ctypes.data, ptr(cim), rpx.ctypes.data, ptr(cix), ptr(vx), rpy.ctypes.data, ptr(ciy), ptr(vy),
+                                  ptr(out)), "sblas_mspgemm_ref")
+    return out
 
 
 # triangular solves: fill, diagonal, plan modes and launch kinds (SBLAS_FILL_*, SBLAS_DIAG_*, SBLAS_SPTRSV_* in sblas_hip.h)
@@ -2409,6 +2457,124 @@ def csr_add(A, B, alpha=1.0, beta=1.0, stream=None):
     finally:
         plan.destroy()
     return rowptr_c, colidx_c, val_c
+
+
+# ------------------------------------------------------------------------------------------
+# Masked SpGEMM: out = M o (X Y^T) on a CSR pattern (sblas_hip_mspgemm_plan_*)
+# ------------------------------------------------------------------------------------------
+class MaskedSpgemmPlan:
+    """out = M o (X Y^T) (sblas_hip_mspgemm_plan_create): the product of two sparse matrices evaluated only on a pattern.
+    X is m x k and Y n x k, both CSR with int32 indices; the mask is an m x n CSR pattern; rows of all three may be unsorted
+    and hold duplicates.  Creation checks the three structures on the device (a bad one raises) and copies them, so the
+    plan keeps none of the caller's arrays.  multiply(val_x, val_y) fills one double per stored mask entry, in the mask's
+    stored order: the products x * y over the columns X's row i and Y's row j share, added left to right in X's stored
+    order (include/sblas_hip_mspgemm.h has the contract); it allocates nothing inside the library and is graph-capturable.
+    When every row of X and of Y is strictly ascending the plan takes the sorted path (a lane per mask entry walks the
+    shorter row and binary-searches the longer); otherwise, or with general=True, the general path, which is quadratic in
+    the row lengths: the slow path.  destroy() / garbage collection frees the device buffers.
+
+    SpGEMM's values on its own pattern, bit for bit (the contract's order is SpGEMM's):
+        c = SpgemmPlan(m, k, n, rowptr_a, colidx_a, rowptr_b, colidx_b)
+        colptr, rowidx, val_t = TransposePlan(k, n, rowptr_b, colidx_b, val_b).csc()
+        plan = MaskedSpgemmPlan(m, n, k, *c.csr(), rowptr_a, colidx_a, colptr, rowidx)
+        val_c = plan.multiply(val_a, val_t)
+    The gradient of C = A B with respect to A's values, dA = (dC B^T) on A's pattern:
+        plan = MaskedSpgemmPlan(m, k, n, rowptr_a, colidx_a, *c.csr(), rowptr_b, colidx_b)
+        d_val_a = plan.multiply(d_val_c, val_b)"""
+
+    def __init__(self, m, n, k, rowptr_m, colidx_m, rowptr_x, colidx_x, rowptr_y, colidx_y, general=False, stream=None):
+        import torch
+        self.m, self.n, self.k = m, n, k
+        self.handle = None
+        named = (("rowptr_m", rowptr_m), ("colidx_m", colidx_m), ("rowptr_x", rowptr_x), ("colidx_x", colidx_x), ("rowptr_y", rowptr_y),
+                 ("colidx_y", colidx_y))
+        for name, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            _typed(name, t, torch.int32)
+        if rowptr_m.numel() != m + 1 or rowptr_x.numel() != m + 1 or rowptr_y.numel() != n + 1:
+            raise SblasError("rowptr_m and rowptr_x need m + 1 = %d entries and rowptr_y n + 1 = %d, not %d, %d and %d"
+                             % (m + 1, n + 1, rowptr_m.numel(), rowptr_x.numel(), rowptr_y.numel()))
+        for name, t in named:
+            if not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            if t.device != rowptr_m.device:
+                raise SblasError("%s is on %s, rowptr_m on %s" % (name, t.device, rowptr_m.device))
+        self.device = rowptr_m.device
+        self.nnz_m, self.nnz_x, self.nnz_y = int(colidx_m.numel()), int(colidx_x.numel()), int(colidx_y.numel())
+        h = C.c_void_p()
+        ptr = lambda t: t.data_ptr() if t.numel() else None
+        with torch.cuda.device(self.device):
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                ends = tuple(int(v) for v in torch.stack((rowptr_m[m], rowptr_x[m], rowptr_y[n])).tolist())   # the library reads colidx as far as rowptr says
+            if ends != (self.nnz_m, self.nnz_x, self.nnz_y):
+                raise SblasError("colidx_m / colidx_x / colidx_y have %d / %d / %d entries, the row pointers end at %d / %d / %d"
+                                 % ((self.nnz_m, self.nnz_x, self.nnz_y) + ends))
+            check(lib().sblas_hip_mspgemm_plan_create(-1, _stream(stream), m, n, k, ptr(rowptr_m), ptr(colidx_m), ptr(rowptr_x), ptr(colidx_x),
+                                                      ptr(rowptr_y), ptr(colidx_y), MSPGEMM_GENERAL if general else MSPGEMM_AUTO, C.byref(h)),
+                  "sblas_hip_mspgemm_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_mspgemm_plan_info(self.handle, out), "sblas_hip_mspgemm_plan_info")
+        return dict(m=int(out[0]), n=int(out[1]), k=int(out[2]), nnz_m=int(out[3]), nnz_x=int(out[4]), nnz_y=int(out[5]),
+                    path="sorted" if out[6] == MSPGEMM_PATH_SORTED else "general", x_ascending=bool(out[7]), y_ascending=bool(out[8]),
+                    launches=int(out[9]), bytes=int(out[10]), general=out[11] == MSPGEMM_GENERAL)
+
+    def multiply(self, val_x, val_y, out=None, stream=None):
+        """The masked product's values (nnz_m of them, in the mask's stored order) for the values val_x and val_y in X's
+        and Y's stored order, written to `out` when given; `out` may not overlap val_x or val_y."""
+        import torch
+        for name, t in (("val_x", val_x), ("val_y", val_y)):
+            if not isinstance(t, torch.Tensor):
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+            _typed(name, t, torch.float64)
+        if val_x.numel() != self.nnz_x or val_y.numel() != self.nnz_y:
+            raise SblasError("val_x / val_y have %d / %d entries, the plan %d / %d" % (val_x.numel(), val_y.numel(), self.nnz_x, self.nnz_y))
+        if out is None:
+            out = torch.empty(self.nnz_m, dtype=torch.float64, device=self.device)
+        _typed("out", out, torch.float64)
+        if out.numel() < self.nnz_m:
+            raise SblasError("out has %d entries, the mask %d" % (out.numel(), self.nnz_m))
+        for name, t in (("val_x", val_x), ("val_y", val_y), ("out", out)):
+            if t.is_cuda and t.device != self.device:
+                raise SblasError("%s is on %s, the plan on %s" % (name, t.device, self.device))
+        px = _dev_ptr(val_x, torch.float64, "val_x") if self.nnz_x else None
+        py = _dev_ptr(val_y, torch.float64, "val_y") if self.nnz_y else None
+        po = _dev_ptr(out, torch.float64, "out") if self.nnz_m else None
+        check(lib().sblas_hip_mspgemm_plan_numeric(self.handle, _stream(stream), px, py, po), "sblas_hip_mspgemm_plan_numeric")
+        return out
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_mspgemm_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def masked_spgemm(mask, X, Y, stream=None):
+    """out = M o (X Y^T), one shot: mask = (m, n, rowptr, colidx), X = (m, k, rowptr, colidx, val) and Y = (n, k, rowptr,
+    colidx, val) as GPU tensors -> one double per stored mask entry (the plan made here is destroyed before returning)."""
+    m, n, rowptr_m, colidx_m = mask
+    mx, k, rowptr_x, colidx_x, val_x = X
+    ny, ky, rowptr_y, colidx_y, val_y = Y
+    if mx != m or ny != n or ky != k:
+        raise SblasError("the mask is %d x %d, X is %d x %d and Y %d x %d: X Y^T is %d x %d" % (m, n, mx, k, ny, ky, mx, ny))
+    import torch
+    plan = MaskedSpgemmPlan(m, n, k, rowptr_m, colidx_m, rowptr_x, colidx_x, rowptr_y, colidx_y, stream=stream)
+    try:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(plan.device)):
+            out = plan.multiply(val_x, val_y, stream=torch.cuda.current_stream())     # out is allocated on the stream that multiplies
+            torch.cuda.current_stream().synchronize()
+    finally:
+        plan.destroy()
+    return out
 
 
 def _structure(n, rowptr, colidx):

@@ -17,13 +17,26 @@ doubles per row; its backward recomputes the probabilities, takes dQ from the fu
 dV = A(P)^T dO through the TransposePlan, from P and dS that live only inside that backward.
 csr_add(plan, val_a, val_b, alpha, beta), a function beside the operator, is the CSR sum on a GeamPlan, differentiable in
 both value arrays: its backward is a gather over the plan's maps.
+SpgemmOperator is the sparse-sparse product C = A B on a SpgemmPlan, differentiable in both value arrays:
+    op = SpgemmOperator(m, k, n, rowptr_a, colidx_a, rowptr_b, colidx_b)
+    rowptr_c, colidx_c = op.csr()
+    val_c = op.multiply(val_a, val_b)    # spgemm_multiply(op, val_a, val_b): SpgemmPlan.multiply's bits
+Both gradients are masked SpGEMMs (MaskedSpgemmPlan, out = M o (X Y^T)), each on a plan the first backward that needs it
+makes, with no transposed kernel:
+    dval_a = A's pattern o (dC B^T)               mask = A, X = dC on C's pattern, Y = B
+    dval_b = B's pattern o (A^T (dC^T)^T)         mask = B, X = A^T, Y = C^T: two TransposePlans, refreshed with that
+                                                  forward's val_a and with dC
+A duplicated entry of A or B receives the full gradient of its position, since C depends on the sum of the duplicates.
 Backward of backward is not supported.  float64 values, int32 indices, GPU tensors only: there is no CPU path.
 torch is imported here, not by the package."""
+import ctypes as C
+
 import torch
 
-from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, GeamPlan, SblasError, SpmmPlan, SpmvPlan, TransposePlan, _layout, csr_attention,
+from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, GeamPlan, MaskedSpgemmPlan, SblasError, SpgemmPlan, SpmmPlan, SpmvPlan, TransposePlan, _DeviceArray,
+               _layout, check, csr_attention,
                csr_attention_backward, csr_attention_workspace_bytes, csr_softmax, csr_softmax_backward,
-               csr_softmax_workspace_bytes, gather, sddmm_tensor, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
+               csr_softmax_workspace_bytes, gather, sddmm_tensor, lib, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
 
 
 class CsrOperator:
@@ -359,3 +372,102 @@ def csr_add(plan, val_a, val_b, alpha=1.0, beta=1.0):
     if not isinstance(plan, GeamPlan):
         raise SblasError("csr_add needs a GeamPlan")
     return _CsrAdd.apply(val_a, val_b, plan, float(alpha), float(beta))
+
+
+class SpgemmOperator:
+    """C = A B for two CSR structures (A m x k, B k x n, int32 rowptr / colidx on the GPU; rows may be unsorted and hold
+    duplicates) whose values change from call to call.  Owns the SpgemmPlan -- csr() passes through -- and, each made by
+    the first backward that needs it, the two MaskedSpgemmPlans of the gradients and the two TransposePlans dval_b reads
+    (grad_a_plan; grad_b_plan, transpose_a, transpose_c).  general=True sends the product and both gradients through their
+    general paths.  One call at a time per operator, as for the plans."""
+
+    def __init__(self, m, k, n, rowptr_a, colidx_a, rowptr_b, colidx_b, general=False):
+        for name, t in (("rowptr_a", rowptr_a), ("colidx_a", colidx_a), ("rowptr_b", rowptr_b), ("colidx_b", colidx_b)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+        self.m, self.k, self.n, self.general = int(m), int(k), int(n), bool(general)
+        self.a, self.b = (rowptr_a, colidx_a), (rowptr_b, colidx_b)
+        self.plan = SpgemmPlan(m, k, n, rowptr_a, colidx_a, rowptr_b, colidx_b, general=general)
+        self.device = self.plan.device
+        self.nnz_a, self.nnz_b, self.nnz_c = self.plan.nnz_a, self.plan.nnz_b, self.plan.nnz_c
+        self.grad_a_plan = self.grad_b_plan = self.transpose_a = self.transpose_c = None
+
+    def csr(self):
+        """(rowptr_c, colidx_c): the SpgemmPlan's views; they live as long as the operator."""
+        return self.plan.csr()
+
+    def multiply(self, val_a, val_b):
+        """C's values (nnz_c of them), differentiable in val_a and val_b: spgemm_multiply(self, val_a, val_b)."""
+        return spgemm_multiply(self, val_a, val_b)
+
+    def _no_pairs(self):
+        return self.nnz_a == 0 or self.nnz_b == 0 or self.nnz_c == 0     # every entry of both gradients is the empty sum, +0.0
+
+    def _grad_a(self, dC, val_b):
+        if self._no_pairs():
+            return torch.zeros(self.nnz_a, dtype=torch.float64, device=self.device)
+        if self.grad_a_plan is None:
+            self.grad_a_plan = MaskedSpgemmPlan(self.m, self.k, self.n, *self.a, *self.plan.csr(), *self.b, general=self.general)
+        return self.grad_a_plan.multiply(dC, val_b)
+
+    def _transposed(self, which, rows, cols, structure, val):
+        """the TransposePlan `which`, made with or refreshed to the values of `val`"""
+        tp = getattr(self, which)
+        if tp is None:
+            tp = TransposePlan(rows, cols, structure[0], structure[1], val)
+            setattr(self, which, tp)
+        else:
+            tp.update_values(val)
+        return tp
+
+    def _grad_b(self, val_a, dC):
+        if self._no_pairs():
+            return torch.zeros(self.nnz_b, dtype=torch.float64, device=self.device)
+        ta = self._transposed("transpose_a", self.m, self.k, self.a, val_a)
+        tc = self._transposed("transpose_c", self.m, self.n, self.plan.csr(), dC)
+        if self.grad_b_plan is None:                                     # the plan copies the structures it is given
+            self.grad_b_plan = MaskedSpgemmPlan(self.k, self.n, self.m, *self.b, *ta.csc()[:2], *tc.csc()[:2], general=self.general)
+        return self.grad_b_plan.multiply(_transposed_values(ta), _transposed_values(tc))
+
+    def destroy(self):
+        for p in (self.plan, self.grad_a_plan, self.grad_b_plan, self.transpose_a, self.transpose_c):
+            if p is not None:
+                p.destroy()
+        self.grad_a_plan = self.grad_b_plan = self.transpose_a = self.transpose_c = None
+
+
+def _transposed_values(tp):
+    """a view of a TransposePlan's own transposed values (nnz > 0): read at once, on the stream that refreshed them"""
+    vt = C.c_void_p()
+    check(lib().sblas_hip_transpose_plan_csc(tp.handle, None, None, C.byref(vt)), "sblas_hip_transpose_plan_csc")
+    return torch.as_tensor(_DeviceArray(vt.value, tp.nnz, "<f8"), device=tp.device)
+
+
+class _SpgemmMultiply(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val_a, val_b, op):
+        ctx.op = op
+        ctx.save_for_backward(val_a, val_b)
+        return op.plan.multiply(val_a.detach(), val_b.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dC):
+        val_a, val_b = ctx.saved_tensors
+        op = ctx.op
+        dC = _laid_out(dC)
+        dA = op._grad_a(dC, val_b) if ctx.needs_input_grad[0] else None
+        dB = op._grad_b(val_a, dC) if ctx.needs_input_grad[1] else None
+        return dA, dB, None
+
+
+def spgemm_multiply(op, val_a, val_b):
+    """C's values of A B on a SpgemmOperator, differentiable in val_a and val_b: dval_a = (dC B^T) on A's pattern and
+    dval_b = (A^T dC) on B's, both masked SpGEMMs in the contract's fixed order.  Only the halves autograd asks for are
+    computed; backward of backward is not supported."""
+    if not isinstance(op, SpgemmOperator):
+        raise SblasError("spgemm_multiply needs a SpgemmOperator")
+    for name, t in (("val_a", val_a), ("val_b", val_b)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
+    return _SpgemmMultiply.apply(val_a, val_b, op)
