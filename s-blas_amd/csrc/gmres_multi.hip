@@ -34,7 +34,6 @@
 #include <memory>
 #include <type_traits>
 #include "../../include/sblas_hip.h"
-#include "precond.h"
 
 #pragma clang fp contract(off) // file scope, ahead of gmres.h: a * b + c is two roundings in the scalar step and below
 
@@ -45,6 +44,7 @@
 #include "krylov_fold.h"
 #include "krylov_tile.h" // tile_store
 #include "unit_row.h"    // tile_ld, tile_st, tile_id
+#include "multi_plan.h"  // the plan base: bind, layout, product, the refusals of start, status
 
 using namespace sblas;
 
@@ -429,33 +429,20 @@ __global__ __launch_bounds__(KRYLOV_LANES) void gmres_multi_fold_kernel(int op, 
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-struct GmresMultiPlan {
-    int dev = -1, m = 0, s = 0;
-    int64_t n = 0, nnz = 0, cells = 0, vstride = 0;
-    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
-    void *spmm = nullptr;                               // the plan's own, for width s
-    PrecondSeat pre;                                    // start() gives it the caller's values
-    int n_blocks = 0;
-    size_t block_bytes = 0, partial_bytes = 0, scalar_bytes = 0, matrix_bytes = 0, ws_bytes = 0, bytes = 0;
-    DeviceBuffer buf; // scalar blocks | small matrices | partials | the SpMM's workspace | V_0 .. V_m, W, U, Z [, T]
-    double *blk = nullptr, *mat = nullptr, *part = nullptr, *vec = nullptr;
-    void *ws = nullptr;
-    // one solve: start() keeps what iterate() needs
-    bool started = false;
+struct GmresMultiPlan : MultiPlanBase {
+    int m = 0;
+    int64_t vstride = 0;
+    size_t matrix_bytes = 0;
+    double *mat = nullptr; // scalar blocks | small matrices | partials | the SpMM's workspace | V_0 .. V_m, W, U, Z [, T]
     int pos = 0; // steps enqueued since the chain's last restart (or start): where the next close and restart belong
-    const double *val = nullptr, *b = nullptr;
-    double *x = nullptr;
-    int64_t ldb = 0, ldx = 0;
+    const double *b = nullptr;
+    int64_t ldb = 0;
     double *block(int k) const { return vec + (size_t)k * (size_t)vstride; }
     double *w() const { return block(m + 1); }
     double *u() const { return block(m + 2); }
     double *z() const { return block(m + 3); }
     double *t() const { return block(m + 4); } // the close's second block, of a kind that cannot run in place
     bool second() const { return pre.applied() && !pre.in_place(); }
-    ~GmresMultiPlan()
-    {
-        if (spmm) sblas_hip_spmm_plan_destroy(spmm);
-    }
 };
 
 inline unsigned grid_of(int64_t cells, int s) { return (unsigned)tile_grid(cells, s); }
@@ -501,13 +488,6 @@ MVecArgs vec_args(const GmresMultiPlan *p)
 
 // the plan's own blocks have leading dimension s and 256-byte aligned bases: wide when s is even
 bool plan_wide(const GmresMultiPlan *p) { return wide16(p->vec, p->s) && ((p->vstride * 8) & 15) == 0; }
-
-// out = A in: ONE planned SpMM, both blocks row-major, alpha 1 and beta 0
-int product(const GmresMultiPlan *p, hipStream_t st, const double *in, int64_t ldin, double *out)
-{
-    return sblas_hip_spmm_csr_ordered_f64_i32_planned(p->spmm, p->dev, st, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, in, ldin,
-                                                      SBLAS_ROW_MAJOR, p->s, 1.0, 0.0, out, p->s, SBLAS_ROW_MAJOR, p->ws, p->ws_bytes);
-}
 
 void normalise(const GmresMultiPlan *p, hipStream_t st)
 {
@@ -582,9 +562,6 @@ int restart_launches(const GmresMultiPlan *p, hipStream_t st)
     normalise(p, st);
     return SBLAS_OK;
 }
-
-// the bytes an n x s block at leading dimension ld spans
-inline size_t span_bytes(int64_t n, int s, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)s) * 8 : 0; }
 
 // what the stand-alone entry points refuse: k basis blocks at V, an n x s block at w, column-wise coefficients at coef
 bool blocks_ok(int64_t n, int nrhs, int k, const double *V, int64_t ldv, int64_t stride, const void *w, int64_t ldw, const void *scalars)
@@ -668,55 +645,18 @@ int sblas_hip_gmres_multi_plan_create(int dev, void *stream, int64_t n, int64_t 
         : precond_multi_applied(precond) ? (!lower_plan || upper_plan)
         : precond_multi_pair(precond) ? (!lower_plan || !upper_plan) : true)
         return SBLAS_E_INVALID;
-    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
-    if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
-    const int device = resolve_device(dev);
     std::unique_ptr<GmresMultiPlan> p(new GmresMultiPlan);
-    p->dev = device, p->m = restart, p->s = nrhs, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
-    p->rowptr = rowptr, p->colidx = colidx;
-    if (precond_multi_applied(precond)) {
-        int64_t info[12];
-        if (n == 0 && sblas_hip_amg_plan_info(lower_plan, info) == SBLAS_OK && info[0] == 0) {
-            // an empty structure has no content to compare and an empty plan no device memory: it is seated as it is
-            p->pre.kind = precond, p->pre.lower = lower_plan, p->pre.rowptr = rowptr, p->pre.colidx = colidx;
-        } else if (p->pre.bind(precond, lower_plan, nullptr, device, n, nnz, rowptr, colidx) != SBLAS_OK) {
-            return SBLAS_E_INVALID;
-        }
-        DeviceScope scope(dev);
-        if (scope.err != hipSuccess) return SBLAS_E_HIP;
-        const int rc = sblas_hip_amg_plan_reserve_multi(const_cast<void *>(lower_plan), stream, nrhs);
-        if (rc != SBLAS_OK) return rc;
-    } else if (p->pre.bind(precond, lower_plan, upper_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) {
-        return SBLAS_E_INVALID;
-    }
-    p->n_blocks = restart + 1 + GMRES_MULTI_FIXED_BLOCKS + (p->second() ? 1 : 0);
-    if (n == 0) {
-        *plan_out = p.release();
-        return SBLAS_OK;
-    }
-    DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    const int rc = sblas_hip_spmm_plan_create(device, stream, n, n, nnz, rowptr, colidx, nrhs, &p->spmm);
+    p->m = restart;
+    int rc = multi_bind(p.get(), dev, stream, n, nnz, rowptr, colidx, nrhs, precond, lower_plan, upper_plan);
     if (rc != SBLAS_OK) return rc;
-    p->scalar_bytes = pad256((size_t)nrhs * GMRES_BLOCK_SLOTS * 8);
-    p->matrix_bytes = pad256((size_t)nrhs * (size_t)GMRES_MULTI_MATRIX_STRIDE * 8);
-    p->partial_bytes = pad256((size_t)(restart + 1) * (size_t)nrhs * (size_t)p->cells * 8);
-    p->ws_bytes = pad256(sblas_hip_spmm_csr_f64_i32_workspace(n, n, nnz, nrhs));
-    p->block_bytes = pad256((size_t)n * (size_t)nrhs * 8), p->vstride = (int64_t)(p->block_bytes / 8);
-    p->bytes = p->scalar_bytes + p->matrix_bytes + p->partial_bytes + p->ws_bytes + (size_t)p->n_blocks * p->block_bytes;
-    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) { // the plan and its SpMM plan go with p
-        (void)hipGetLastError();
-        return SBLAS_E_HIP;
-    }
-    size_t at = 0;
-    p->blk = p->buf.at<double>(at), at += p->scalar_bytes;
-    p->mat = p->buf.at<double>(at), at += p->matrix_bytes;
-    p->part = p->buf.at<double>(at), at += p->partial_bytes;
-    p->ws = p->ws_bytes ? p->buf.at<double>(at) : nullptr, at += p->ws_bytes;
-    p->vec = p->buf.at<double>(at);
-    // the one moment the whole buffer is written outside a solve: no kernel ever reads a value nobody wrote
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(p->buf.at<char>(), 0, p->bytes, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
+    p->n_blocks = restart + 1 + GMRES_MULTI_FIXED_BLOCKS + (p->second() ? 1 : 0);
+    rc = multi_layout(p.get(), stream, {{&p->blk, &p->scalar_bytes, (size_t)nrhs * GMRES_BLOCK_SLOTS * 8, 1},
+                                        {&p->mat, &p->matrix_bytes, (size_t)nrhs * (size_t)GMRES_MULTI_MATRIX_STRIDE * 8, 1},
+                                        {&p->part, &p->partial_bytes, (size_t)(restart + 1) * (size_t)nrhs * (size_t)p->cells * 8, 1},
+                                        multi_workspace(p.get()),
+                                        {&p->vec, &p->block_bytes, (size_t)n * (size_t)nrhs * 8, p->n_blocks}});
+    if (rc != SBLAS_OK) return rc;
+    p->vstride = (int64_t)(p->block_bytes / 8);
     *plan_out = p.release();
     return SBLAS_OK;
 }
@@ -755,24 +695,9 @@ int sblas_hip_gmres_multi_start(void *plan, void *stream, const double *val, con
                                 int64_t ldx, double rtol, double atol, int64_t max_iter)
 {
     GmresMultiPlan *p = static_cast<GmresMultiPlan *>(plan);
-    if (!p) return SBLAS_E_INVALID;
-    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
-    if (!(rtol >= 0.0) || !(atol >= 0.0) || max_iter < 0) return SBLAS_E_INVALID; // a NaN tolerance is refused too
-    if (ldb < p->s || ldx < p->s) return SBLAS_E_INVALID;
-    p->started = false;
-    if (p->n == 0) {
-        p->started = true;
-        return SBLAS_OK;
-    }
-    if (precond_multi_applied(p->pre.kind)) { // the block cycle needs a plan that is set up, with a smoother that has a block form
-        int64_t info[12];
-        if (sblas_hip_amg_plan_info(p->pre.lower, info) != SBLAS_OK || !info[10] || info[9] == SBLAS_AMG_CHEBYSHEV) return SBLAS_E_INVALID;
-    }
-    if (!B || !X || (p->nnz > 0 && !val) || !p->pre.take(lu_or_dinv)) return SBLAS_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
-    if (b0 < x0 + span_bytes(p->n, p->s, ldx) && x0 < b0 + span_bytes(p->n, p->s, ldb)) return SBLAS_E_INVALID; // X overlaps B
-    p->val = val, p->b = B, p->ldb = ldb, p->x = X, p->ldx = ldx, p->pos = 0;
+    const MultiStart go = multi_start(p, val, lu_or_dinv, B, ldb, X, ldx, rtol, atol, max_iter);
+    if (go != MULTI_GO) return go == MULTI_EMPTY ? SBLAS_OK : SBLAS_E_INVALID;
+    p->b = B, p->ldb = ldb, p->pos = 0;
     hipStream_t st = (hipStream_t)stream;
     // The work blocks start every solve from zero.  A column that is frozen from the start is never written, yet the SpMM
     // multiplies it -- and a non-finite value a previous solve left there would select other SpMM kernels for the whole
@@ -812,27 +737,9 @@ int sblas_hip_gmres_multi_iterate(void *plan, void *stream, int64_t k)
 
 int sblas_hip_gmres_multi_status(const void *plan, void *stream, double *out)
 {
-    const GmresMultiPlan *p = static_cast<const GmresMultiPlan *>(plan);
-    if (!p || !out || !p->started) return SBLAS_E_INVALID;
-    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
-    for (int q = 0; q < 8 * p->s; ++q) out[q] = 0.0;
-    if (p->n == 0) {
-        for (int c = 0; c < p->s; ++c) out[8 * c] = SBLAS_KRYLOV_CONVERGED;
-        return SBLAS_OK;
-    }
-    double h[SBLAS_GMRES_MULTI_MAX_RHS * GMRES_BLOCK_SLOTS];
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)p->s * GMRES_BLOCK_SLOTS * 8;
-    if (hipMemcpyAsync(h, p->blk, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
-    for (int c = 0; c < p->s; ++c) {
-        const double *hc = h + (size_t)c * GMRES_BLOCK_SLOTS;
-        long long ih[GMRES_BLOCK_SLOTS];
-        memcpy(ih, hc, sizeof ih);
-        double *o = out + 8 * c;
-        o[0] = (double)ih[GS_STATUS], o[1] = (double)ih[GS_ITER], o[2] = hc[GS_RNORM], o[3] = hc[GS_BNORM];
-        o[4] = (double)ih[GS_RESTARTS], o[5] = (double)ih[GS_COLS], o[6] = hc[GS_ETA], o[7] = (double)ih[GS_WHICH];
-    }
-    return SBLAS_OK;
+    static const StatusSlot table[8] = {{GS_STATUS, true}, {GS_ITER, true}, {GS_RNORM, false}, {GS_BNORM, false},
+                                        {GS_RESTARTS, true}, {GS_COLS, true}, {GS_ETA, false}, {GS_WHICH, true}};
+    return multi_status<GMRES_BLOCK_SLOTS>(static_cast<const GmresMultiPlan *>(plan), stream, out, table);
 }
 
 } // extern "C"

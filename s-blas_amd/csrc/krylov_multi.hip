@@ -41,8 +41,8 @@
 #include "capi_util.h"
 #include "krylov.h"
 #include "krylov_multi.h"
-#include "precond.h"
-#include "unit_row.h" // tile_ld, tile_st, tile_id
+#include "multi_plan.h" // the plan base: bind, layout, product, the refusals of start, status
+#include "unit_row.h"   // tile_ld, tile_st, tile_id
 
 #pragma clang fp contract(off) // file scope: a * b + c below is two roundings on every path
 
@@ -327,32 +327,10 @@ inline void launch_update(hipStream_t st, int op, bool jac, const MUpArgs &a)
 }
 
 // ---- the plan ----------------------------------------------------------------------------------------------------------
-struct MultiPlan {
-    int dev = -1, method = 0, precond = 0, s = 0;
-    int64_t n = 0, nnz = 0, cells = 0;
-    const int32_t *rowptr = nullptr, *colidx = nullptr; // the caller's
-    void *spmm = nullptr;                               // the plan's own, for width s
-    int n_blocks = 0;
-    size_t block_bytes = 0, partial_bytes = 0, scalar_bytes = 0, ws_bytes = 0, bytes = 0;
-    DeviceBuffer buf; // scalar blocks | partials | the SpMM's workspace | work blocks
-    double *blk = nullptr, *part = nullptr, *vec = nullptr;
-    void *ws = nullptr;
-    // one solve: start() keeps what iterate() needs
-    bool started = false;
-    const double *val = nullptr, *dinv = nullptr;
-    double *x = nullptr;
-    int64_t ldx = 0;
-    PrecondSeat pre; // an applied kind's plan (create_ex) or pair of plans (create_pair); NONE and JACOBI live in the kernels here
-    bool jacobi() const { return precond == SBLAS_PRECOND_JACOBI; }
-    bool none() const { return precond == SBLAS_PRECOND_NONE; }
-    bool cycle() const { return precond_multi_applied(precond); } // one plan with a block apply of its own: AMG
-    bool pair() const { return precond_multi_pair(precond); }     // two solve plans: ILU(0) by the tiled solves
-    bool applied() const { return cycle() || pair(); }
+struct MultiPlan : MultiPlanBase { // scalar blocks | partials | the SpMM's workspace | work blocks
+    int method = 0;
     double *w(int k) const { return vec + (size_t)k * (block_bytes / 8); }
-    ~MultiPlan()
-    {
-        if (spmm) sblas_hip_spmm_plan_destroy(spmm);
-    }
+    const double *dinv() const { return pre.jacobi() ? pre.values : nullptr; } // the kernels', NULL unless the kind is Jacobi
 };
 
 // work blocks of the plan, by slot (krylov.hip's)
@@ -383,19 +361,12 @@ void fold(const MultiPlan *p, hipStream_t st, int op, int nd, int flag, double r
     launch_fold(st, op, nd, flag, p->s, p->cells, p->part, p->blk, nullptr, rtol, atol, max_iter);
 }
 
-// out = A in: ONE planned SpMM, both blocks row-major, alpha 1 and beta 0
-int product(const MultiPlan *p, hipStream_t st, const double *in, int64_t ldin, double *out)
-{
-    return sblas_hip_spmm_csr_ordered_f64_i32_planned(p->spmm, p->dev, st, p->n, p->n, p->nnz, p->rowptr, p->colidx, p->val, in, ldin,
-                                                      SBLAS_ROW_MAJOR, p->s, 1.0, 0.0, out, p->s, SBLAS_ROW_MAJOR, p->ws, p->ws_bytes);
-}
-
 int pcg_iteration(const MultiPlan *p, hipStream_t st)
 {
-    const bool jac = p->jacobi(), app = p->applied();
+    const bool jac = p->pre.jacobi(), app = p->pre.applied();
     const int64_t s = p->s;
-    const Blk x{p->x, p->ldx}, r{p->w(V_R), s}, pp{p->w(V_P), s}, q{p->w(V_Q), s}, z{p->none() ? p->w(V_R) : p->w(V_Z), s};
-    const Blk dinv{const_cast<double *>(p->dinv), 0};
+    const Blk x{p->x, p->ldx}, r{p->w(V_R), s}, pp{p->w(V_P), s}, q{p->w(V_Q), s}, z{p->pre.none() ? p->w(V_R) : p->w(V_Z), s};
+    const Blk dinv{const_cast<double *>(p->dinv()), 0};
     int rc = product(p, st, pp.p, s, q.p);
     if (rc != SBLAS_OK) return rc;
     dot(p, st, pp, q);
@@ -413,10 +384,10 @@ int pcg_iteration(const MultiPlan *p, hipStream_t st)
 
 int bicgstab_iteration(const MultiPlan *p, hipStream_t st)
 {
-    const bool jac = p->jacobi(), none = p->none(), app = p->applied();
+    const bool jac = p->pre.jacobi(), none = p->pre.none(), app = p->pre.applied();
     const int64_t s = p->s;
     const Blk x{p->x, p->ldx}, r{p->w(B_R), s}, rh{p->w(B_RHAT), s}, pp{p->w(B_P), s}, v{p->w(B_V), s}, sv{p->w(B_S), s}, t{p->w(B_T), s};
-    const Blk ph = none ? pp : Blk{p->w(B_PH), s}, sh = none ? sv : Blk{p->w(B_SH), s}, dinv{const_cast<double *>(p->dinv), 0};
+    const Blk ph = none ? pp : Blk{p->w(B_PH), s}, sh = none ? sv : Blk{p->w(B_SH), s}, dinv{const_cast<double *>(p->dinv()), 0};
     int rc;
     launch_update(st, SBLAS_KRYLOV_UP_BICG_P, jac, up_args(p, {pp, r, v, dinv, ph}));
     if (app && (rc = p->pre.apply_multi(st, p->s, pp.p, s, ph.p, s)) != SBLAS_OK) return rc;
@@ -433,72 +404,37 @@ int bicgstab_iteration(const MultiPlan *p, hipStream_t st)
     return SBLAS_OK;
 }
 
-// the bytes an n x s block at leading dimension ld spans
-inline size_t span_bytes(int64_t n, int s, int64_t ld) { return n > 0 ? ((size_t)(n - 1) * (size_t)ld + (size_t)s) * 8 : 0; }
-
 // launches of one iteration without the products': through the rule of the seat's kind
 int64_t iteration_launches(const MultiPlan *p)
 {
-    if (p->pair()) {
+    const int kind = p->pre.kind;
+    if (precond_multi_pair(kind)) {
         int64_t lower[12], upper[12];
         p->pre.info(lower, upper);
-        return sblas_krylov_multi_launches_pair(p->method, p->precond, 0, lower[5], upper[5]);
+        return sblas_krylov_multi_launches_pair(p->method, kind, 0, lower[5], upper[5]);
     }
     int64_t mi[4] = {0, 0, 0, 0};
-    if (p->cycle()) sblas_hip_amg_plan_multi_info(p->pre.lower, mi);
-    return sblas_krylov_multi_launches_ex(p->method, p->precond, 0, mi[2]);
+    if (precond_multi_applied(kind)) sblas_hip_amg_plan_multi_info(p->pre.lower, mi);
+    return sblas_krylov_multi_launches_ex(p->method, kind, 0, mi[2]);
 }
 
-// the three creates.  precond_plan: the plan of an applied kind (create_ex), which is seated and whose level vectors are
-// reserved for nrhs columns; upper_plan: with it precond_plan is the lower one of a pair of solve plans (create_pair),
-// seated as PrecondSeat::bind seats the single solver's.  The work blocks an applied kind writes -- Z, P^ and S^ -- are
+// the three creates.  precond_plan: the plan of an applied kind (create_ex), or with upper_plan the lower one of a pair
+// of solve plans (create_pair); multi_bind seats either.  The work blocks an applied kind writes -- Z, P^ and S^ -- are
 // among the plan's own already.
 int create_plan(int dev, void *stream, int method, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx, int nrhs, int precond,
-                void *precond_plan, const void *upper_plan, void **plan_out)
+                const void *precond_plan, const void *upper_plan, void **plan_out)
 {
     if (!krylov_multi_width_ok(nrhs)) return SBLAS_E_INVALID;
-    if (n < 0 || nnz < 0 || n > INT_MAX - 64 || nnz > INT_MAX) return SBLAS_E_INVALID;
-    if (!rowptr || (nnz > 0 && !colidx) || (n == 0 && nnz != 0)) return SBLAS_E_INVALID;
-    const int device = resolve_device(dev);
     std::unique_ptr<MultiPlan> p(new MultiPlan);
-    p->dev = device, p->method = method, p->precond = precond, p->s = nrhs, p->n = n, p->nnz = nnz, p->cells = krylov_cells(n);
-    p->rowptr = rowptr, p->colidx = colidx;
-    p->n_blocks = method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS;
-    if (upper_plan) {
-        if (p->pre.bind(precond, precond_plan, upper_plan, device, n, nnz, rowptr, colidx) != SBLAS_OK) return SBLAS_E_INVALID;
-    } else if (precond_plan) {
-        int64_t info[12];
-        if (n == 0 && sblas_hip_amg_plan_info(precond_plan, info) == SBLAS_OK && info[0] == 0) {
-            // an empty structure has no content to compare and an empty plan no device memory: it is seated as it is
-            p->pre.kind = precond, p->pre.lower = precond_plan, p->pre.rowptr = rowptr, p->pre.colidx = colidx;
-        } else if (p->pre.bind(precond, precond_plan, nullptr, device, n, nnz, rowptr, colidx) != SBLAS_OK) {
-            return SBLAS_E_INVALID;
-        }
-        DeviceScope scope(dev);
-        if (scope.err != hipSuccess) return SBLAS_E_HIP;
-        const int rc = sblas_hip_amg_plan_reserve_multi(precond_plan, stream, nrhs);
-        if (rc != SBLAS_OK) return rc;
-    }
-    if (n == 0) {
-        *plan_out = p.release();
-        return SBLAS_OK;
-    }
-    DeviceScope scope(dev);
-    if (scope.err != hipSuccess) return SBLAS_E_HIP;
-    int rc = sblas_hip_spmm_plan_create(device, stream, n, n, nnz, rowptr, colidx, nrhs, &p->spmm);
+    p->method = method;
+    int rc = multi_bind(p.get(), dev, stream, n, nnz, rowptr, colidx, nrhs, precond, precond_plan, upper_plan);
     if (rc != SBLAS_OK) return rc;
-    p->scalar_bytes = pad256((size_t)nrhs * KRYLOV_BLOCK_SLOTS * 8);
-    p->partial_bytes = pad256((size_t)KRYLOV_MAX_DOTS * (size_t)nrhs * (size_t)p->cells * 8);
-    p->ws_bytes = pad256(sblas_hip_spmm_csr_f64_i32_workspace(n, n, nnz, nrhs));
-    p->block_bytes = pad256((size_t)n * (size_t)nrhs * 8);
-    p->bytes = p->scalar_bytes + p->partial_bytes + p->ws_bytes + (size_t)p->n_blocks * p->block_bytes;
-    if (p->buf.alloc(p->dev, p->bytes) != hipSuccess) return SBLAS_E_HIP;
-    p->blk = p->buf.at<double>(), p->part = p->buf.at<double>(p->scalar_bytes);
-    p->ws = p->ws_bytes ? p->buf.at<double>(p->scalar_bytes + p->partial_bytes) : nullptr;
-    p->vec = p->buf.at<double>(p->scalar_bytes + p->partial_bytes + p->ws_bytes);
-    // the work blocks start from zero: a product with beta 0 into a block that never held a value
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(p->blk, 0, p->bytes, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
+    p->n_blocks = method == SBLAS_KRYLOV_PCG ? KRYLOV_PCG_VECTORS : KRYLOV_BICGSTAB_VECTORS;
+    rc = multi_layout(p.get(), stream, {{&p->blk, &p->scalar_bytes, (size_t)nrhs * KRYLOV_BLOCK_SLOTS * 8, 1},
+                                        {&p->part, &p->partial_bytes, (size_t)KRYLOV_MAX_DOTS * (size_t)nrhs * (size_t)p->cells * 8, 1},
+                                        multi_workspace(p.get()),
+                                        {&p->vec, &p->block_bytes, (size_t)n * (size_t)nrhs * 8, p->n_blocks}});
+    if (rc != SBLAS_OK) return rc;
     *plan_out = p.release();
     return SBLAS_OK;
 }
@@ -587,14 +523,14 @@ int sblas_hip_krylov_multi_plan_create_pair(int dev, void *stream, int method, i
     *plan_out = nullptr;
     if (method != SBLAS_KRYLOV_PCG && method != SBLAS_KRYLOV_BICGSTAB) return SBLAS_E_INVALID;
     if (!lower_plan || !upper_plan) return SBLAS_E_INVALID;
-    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, SBLAS_PRECOND_ILU0, const_cast<void *>(lower_plan), upper_plan, plan_out);
+    return create_plan(dev, stream, method, n, nnz, rowptr, colidx, nrhs, SBLAS_PRECOND_ILU0, lower_plan, upper_plan, plan_out);
 }
 
 int sblas_hip_krylov_multi_plan_info(const void *plan, int64_t out[12])
 {
     if (!plan || !out) return SBLAS_E_INVALID;
     const MultiPlan *p = static_cast<const MultiPlan *>(plan);
-    out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->precond, out[4] = p->s, out[5] = p->n_blocks;
+    out[0] = p->n, out[1] = p->nnz, out[2] = p->method, out[3] = p->pre.kind, out[4] = p->s, out[5] = p->n_blocks;
     out[6] = (int64_t)p->block_bytes, out[7] = (int64_t)p->partial_bytes, out[8] = (int64_t)p->scalar_bytes, out[9] = (int64_t)p->ws_bytes;
     out[10] = (int64_t)p->bytes, out[11] = iteration_launches(p);
     return SBLAS_OK;
@@ -610,30 +546,13 @@ int sblas_hip_krylov_multi_start(void *plan, void *stream, const double *val, co
                                  int64_t ldx, double rtol, double atol, int64_t max_iter)
 {
     MultiPlan *p = static_cast<MultiPlan *>(plan);
-    if (!p) return SBLAS_E_INVALID;
-    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
-    if (!(rtol >= 0.0) || !(atol >= 0.0) || max_iter < 0) return SBLAS_E_INVALID; // a NaN tolerance is refused too
-    if (ldb < p->s || ldx < p->s) return SBLAS_E_INVALID;
-    p->started = false;
-    if (p->n == 0) {
-        p->started = true;
-        return SBLAS_OK;
-    }
-    const bool jac = p->jacobi();
-    if (p->cycle()) { // the block cycle needs a plan that is set up, with a smoother that has a block form
-        int64_t info[12];
-        if (sblas_hip_amg_plan_info(p->pre.lower, info) != SBLAS_OK || !info[10] || info[9] == SBLAS_AMG_CHEBYSHEV) return SBLAS_E_INVALID;
-    }
-    if (!B || !X || (p->nnz > 0 && !val) || (jac && !dinv)) return SBLAS_E_INVALID;
-    if (p->pair() && !p->pre.take(dinv)) return SBLAS_E_INVALID; // dinv carries the factor lu, as the single solver's lu_or_dinv
-    if ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(X)) & 7u) return SBLAS_E_INVALID;
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
-    if (b0 < x0 + span_bytes(p->n, p->s, ldx) && x0 < b0 + span_bytes(p->n, p->s, ldb)) return SBLAS_E_INVALID; // X overlaps B
-    p->val = val, p->dinv = jac ? dinv : nullptr, p->x = X, p->ldx = ldx;
+    const MultiStart go = multi_start(p, val, dinv, B, ldb, X, ldx, rtol, atol, max_iter); // dinv carries the factor lu of a pair
+    if (go != MULTI_GO) return go == MULTI_EMPTY ? SBLAS_OK : SBLAS_E_INVALID;
+    const bool jac = p->pre.jacobi();
     hipStream_t st = (hipStream_t)stream;
     const bool pcg = p->method == SBLAS_KRYLOV_PCG;
     const int64_t s = p->s;
-    const Blk b{const_cast<double *>(B), ldb}, x{X, ldx}, di{const_cast<double *>(p->dinv), 0};
+    const Blk b{const_cast<double *>(B), ldb}, x{X, ldx}, di{const_cast<double *>(p->dinv()), 0};
     int rc;
     // The work blocks start every solve from zero.  A column that is frozen from the start is never written, yet the SpMM
     // multiplies it -- and a non-finite value a previous solve left there would select other SpMM kernels for the whole
@@ -642,11 +561,11 @@ int sblas_hip_krylov_multi_start(void *plan, void *stream, const double *val, co
     dot(p, st, b, b);
     fold(p, st, FOLD_START_B, 1, !pcg, rtol, atol, max_iter);
     if (pcg) {
-        const Blk r{p->w(V_R), s}, q{p->w(V_Q), s}, z{p->none() ? p->w(V_R) : p->w(V_Z), s}, pp{p->w(V_P), s};
+        const Blk r{p->w(V_R), s}, q{p->w(V_Q), s}, z{p->pre.none() ? p->w(V_R) : p->w(V_Z), s}, pp{p->w(V_P), s};
         if ((rc = product(p, st, X, ldx, q.p)) != SBLAS_OK) return rc;
         launch_update(st, UP_START_PCG, jac, up_args(p, {r, b, q, di, z, x}));
         fold(p, st, FOLD_START_R, jac ? 2 : 1, 0);
-        if (p->applied()) { // krylov.hip's start: z = M^-1 r on all columns, then rho = (r, z)
+        if (p->pre.applied()) { // krylov.hip's start: z = M^-1 r on all columns, then rho = (r, z)
             if ((rc = p->pre.apply_multi(st, p->s, r.p, s, z.p, s)) != SBLAS_OK) return rc;
             dot(p, st, r, z);
             fold(p, st, FOLD_RHO0, 1, 0);
@@ -679,27 +598,9 @@ int sblas_hip_krylov_multi_iterate(void *plan, void *stream, int64_t k)
 
 int sblas_hip_krylov_multi_status(const void *plan, void *stream, double *out)
 {
-    const MultiPlan *p = static_cast<const MultiPlan *>(plan);
-    if (!p || !out || !p->started) return SBLAS_E_INVALID;
-    if (p->dev != resolve_device(-1)) return SBLAS_E_INVALID;
-    for (int q = 0; q < 8 * p->s; ++q) out[q] = 0.0;
-    if (p->n == 0) {
-        for (int j = 0; j < p->s; ++j) out[8 * j] = SBLAS_KRYLOV_CONVERGED;
-        return SBLAS_OK;
-    }
-    double h[SBLAS_KRYLOV_MULTI_MAX_RHS * KRYLOV_BLOCK_SLOTS];
-    hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)p->s * KRYLOV_BLOCK_SLOTS * 8;
-    if (hipMemcpyAsync(h, p->blk, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return SBLAS_E_HIP;
-    for (int j = 0; j < p->s; ++j) {
-        const double *hj = h + (size_t)j * KRYLOV_BLOCK_SLOTS;
-        long long ih[KRYLOV_BLOCK_SLOTS];
-        memcpy(ih, hj, sizeof ih);
-        double *o = out + 8 * j;
-        o[0] = (double)ih[KS_STATUS], o[1] = (double)ih[KS_ITER], o[2] = hj[KS_RNORM], o[3] = hj[KS_BNORM];
-        o[4] = hj[KS_ALPHA], o[5] = hj[KS_BETA], o[6] = hj[KS_OMEGA], o[7] = (double)ih[KS_WHICH];
-    }
-    return SBLAS_OK;
+    static const StatusSlot table[8] = {{KS_STATUS, true}, {KS_ITER, true}, {KS_RNORM, false}, {KS_BNORM, false},
+                                        {KS_ALPHA, false}, {KS_BETA, false}, {KS_OMEGA, false}, {KS_WHICH, true}};
+    return multi_status<KRYLOV_BLOCK_SLOTS>(static_cast<const MultiPlan *>(plan), stream, out, table);
 }
 
 } // extern "C"

@@ -1,4 +1,5 @@
-// precond.h -- the seat a solver plan (krylov.hip, gmres.hip) holds for its preconditioner, and the SpMV of such a plan.
+// precond.h -- the seat a solver plan (krylov.hip, gmres.hip; through multi_plan.h's base krylov_multi.hip and
+// gmres_multi.hip) holds for its preconditioner, and the SpMV of such a plan.
 // The seat answers the five questions a solver asks -- may this be seated (bind), whose values does it take at start
 // (take), what does it cost (info), apply it, and the predicates of the iteration code -- so that a solver names no kind
 // but NONE and JACOBI, which live in its own kernels.  A new kind is added here and in precond_rule.h.

@@ -3827,23 +3827,27 @@ class _SolverPlan:
     def _call(self, name):
         return getattr(lib(), "sblas_hip_%s_%s" % (self._c, name))
 
+    def _values(self, lu, dinv):
+        """start's lu / dinv, by the seated kind -> the tensor that travels as lu_or_dinv, or None"""
+        if self.precond_kind == PRECOND_ILU0:
+            if lu is None:
+                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
+            _krylov_vector("lu", lu, self.nnz, self.device)
+            return lu
+        if self.precond_kind == PRECOND_JACOBI:
+            if dinv is None:
+                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
+            _krylov_vector("dinv", dinv, self.n, self.device)
+            return dinv
+        return None
+
     def start(self, val, b, x, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
         """Begins a solve: x on entry is the initial guess and is updated in place by iterate().  lu: the ILU(0) factor
         (precond an Ilu0Plan); dinv: the inverse diagonal (precond "jacobi").  Every refusal comes before any launch."""
         import torch
         _krylov_vector("val", val, self.nnz, self.device), _krylov_vector("b", b, self.n, self.device)
         _krylov_vector("x", x, self.n, self.device)
-        pre = None
-        if self.precond_kind == PRECOND_ILU0:
-            if lu is None:
-                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
-            _krylov_vector("lu", lu, self.nnz, self.device)
-            pre = lu
-        elif self.precond_kind == PRECOND_JACOBI:
-            if dinv is None:
-                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
-            _krylov_vector("dinv", dinv, self.n, self.device)
-            pre = dinv
+        pre = self._values(lu, dinv)
         if self.n and x.data_ptr() == b.data_ptr():
             raise SblasError("x must not be b")
         if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
@@ -4170,7 +4174,96 @@ def krylov_multi_update(op, scalars, blocks, partial=None, jacobi=False, stream=
               "sblas_hip_krylov_multi_update_f64")
 
 
-class KrylovMultiPlan:
+class _MultiSolverPlan(_SolverPlan):
+    """What KrylovMultiPlan and GmresMultiPlan share beside _SolverPlan's iterate and handle's end: the seat of a
+    multi-column preconditioner, start / solve on (n, nrhs) blocks and the common columns of status().  A subclass names
+    its C functions in _c, checks its own arguments, creates the handle, gives info() and names the three status
+    columns of its own in _columns, as (name, is an integer), and the names of its breakdowns in _denom."""
+
+    def _seat_multi(self, n, rowptr, colidx, precond, stream):
+        """refuses precond, then the structure, then a plan made for another one -> (lower, upper), the handles that
+        travel with the kind; an AmgPlan's level vectors are reserved for nrhs columns.  self.precond keeps the plans alive."""
+        import torch
+        self.precond, self.precond_kind = precond, _multi_precond(precond)
+        self._bind(n, rowptr, colidx)
+        self._keep = None
+        same = lambda q: q.n == n and q.rowptr.data_ptr() == rowptr.data_ptr() and q.colidx.data_ptr() == colidx.data_ptr()
+        if isinstance(precond, AmgPlan):
+            if not same(precond):
+                raise SblasError("the AmgPlan was made for another structure than this solver's (rowptr, colidx)")
+            with torch.cuda.device(self.device):
+                precond.reserve(self.nrhs, stream=stream)
+            return precond.handle, None
+        if self.precond_kind == PRECOND_ILU0:
+            if not all(same(q) for q in precond):
+                raise SblasError("the SptrsvPlans were made for another structure than this solver's (rowptr, colidx)")
+            if not (precond[0].lower and precond[0].unit_diag and not precond[1].lower and not precond[1].unit_diag):
+                raise SblasError("the pair must be (lower with a unit diagonal, upper with a stored one), as Ilu0Plan.solvers() gives it")
+            return precond[0].handle, precond[1].handle
+        return None, None
+
+    def start(self, val, B, X, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
+        """Begins a solve: X on entry holds the initial guesses and is updated in place by iterate().  lu: the ILU(0)
+        factor (precond a pair of SptrsvPlans); dinv: the inverse diagonal (precond "jacobi").  Every refusal comes
+        before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        ldb = _krylov_block("B", B, self.n, self.nrhs, self.device)
+        ldx = _krylov_block("X", X, self.n, self.nrhs, self.device)
+        pre = self._values(lu, dinv)
+        if self.precond_kind == PRECOND_AMG:
+            info = self.precond.info()
+            if not info["ready"]:
+                raise SblasError("the AmgPlan needs setup() before a solve")
+            if info["smoother"] == "chebyshev":
+                raise SblasError("the Chebyshev smoother has no block cycle: set the AmgPlan up with 'jacobi' or 'l1'")
+        if self.n and _blocks_overlap(X, ldx, B, ldb, self.n, self.nrhs):
+            raise SblasError("X must not overlap B")
+        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
+            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
+        with torch.cuda.device(self.device):
+            rc = self._call("start")(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                     pre.data_ptr() if pre is not None and pre.numel() else None,
+                                     B.data_ptr() if self.n else None, ldb, X.data_ptr() if self.n else None, ldx,
+                                     float(rtol), float(atol), int(max_iter))
+        check(rc, "sblas_hip_%s_start" % self._c)
+        self._keep = (val, B, X, pre)
+
+    def status(self, stream=None):
+        """Copies the scalar blocks back and synchronises the stream -> dict of per-column numpy arrays (code, iterations,
+        rnorm, bnorm, the plan's own three, which), lists status and breakdown (the names, as the single solver's status
+        gives them) and running, the count of columns still running."""
+        import torch
+        out = (C.c_double * (8 * self.nrhs))()
+        with torch.cuda.device(self.device):
+            check(self._call("status")(self.handle, _stream(stream), out), "sblas_hip_%s_status" % self._c)
+        a = np.array(out, np.float64).reshape(self.nrhs, 8)
+        code, which = a[:, 0].astype(np.int64), a[:, 7].astype(np.int64)
+        st = dict(code=code, iterations=a[:, 1].astype(np.int64), rnorm=a[:, 2].copy(), bnorm=a[:, 3].copy())
+        for k, (name, integer) in enumerate(self._columns, 4):
+            st[name] = a[:, k].astype(np.int64) if integer else a[:, k].copy()
+        st.update(which=which, status=[KRYLOV_STATUS[int(c)] for c in code], breakdown=[self._denom[int(w)] for w in which],
+                  running=int((code == KRYLOV_RUNNING).sum()))
+        return st
+
+    def solve(self, val, B, X=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
+        """start(), then iterate(check_every) / status() until no column is running -> (X, status dict).  X: the initial
+        guesses, updated in place (zeros made here when None).  No column's result depends on check_every."""
+        import torch
+        if int(check_every) < 1:
+            raise SblasError("check_every must be at least 1")
+        if X is None:
+            _krylov_block("B", B, self.n, self.nrhs, self.device)
+            X = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=self.device)
+        self.start(val, B, X, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
+        while True:
+            self.iterate(int(check_every), stream=stream)
+            st = self.status(stream=stream)
+            if st["running"] == 0:
+                return X, st
+
+
+class KrylovMultiPlan(_MultiSolverPlan):
     """PCG or BiCGStab for A X = B with nrhs right-hand sides at once on the n x n CSR structure (rowptr, colidx), int32
     indices (sblas_hip_krylov_multi_plan_create): nrhs independent recurrences that share A and run in lockstep, one SpMM
     per product instead of nrhs SpMVs.  method: "pcg" (A symmetric positive definite) or "bicgstab"; precond: None or
@@ -4192,7 +4285,15 @@ class KrylovMultiPlan:
     scalars and stopping test: once column j's test is met (or it breaks down) nothing reads or writes column j again,
     while the others go on, so every column's x, count and |r| are those of its own stopping iteration, whatever
     check_every is.  A solve equals the lockstep loop composed of the SpMM, the pinned dot per column and numpy updates
-    bit for bit; it is NOT promised to equal a KrylovPlan solve of one column, or a batch of another width."""
+    bit for bit; it is NOT promised to equal a KrylovPlan solve of one column, or a batch of another width.
+
+    start / solve take (val, B, X, lu=None, dinv=None, rtol, atol, max_iter[, check_every], stream), the order of every
+    other solver plan; they once had dinv ahead of rtol and lu last.  Pass what follows X by keyword: a dinv passed by
+    position now arrives as lu, and the Jacobi plan refuses the call for its missing dinv."""
+
+    _c = "krylov_multi"
+    _columns = (("alpha", False), ("beta", False), ("omega", False))
+    _denom = KRYLOV_DENOM
 
     def __init__(self, n, rowptr, colidx, nrhs, method="pcg", precond=None, stream=None):
         import torch
@@ -4200,35 +4301,19 @@ class KrylovMultiPlan:
         if method not in _KRYLOV_METHOD:
             raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
         self.method, self.nrhs = method, _multi_width(nrhs)
-        self.precond, self.precond_kind = precond, _multi_precond(precond)
-        self.n, self.nnz = n, _structure(n, rowptr, colidx)
-        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
-        self._keep = None
+        lower, upper = self._seat_multi(n, rowptr, colidx, precond, stream)
+        # one create a door: the plan of an applied kind (AMG), the pair of solve plans (ILU(0)), or neither
+        if upper is not None:
+            door, plans = "_pair", (lower, upper)
+        elif lower is not None:
+            door, plans = "_ex", (self.precond_kind, lower)
+        else:
+            door, plans = "", (self.precond_kind,)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            if isinstance(precond, AmgPlan):                                # the plan travels with its kind; self.precond keeps it alive
-                if precond.n != n or precond.rowptr.data_ptr() != rowptr.data_ptr() or precond.colidx.data_ptr() != colidx.data_ptr():
-                    raise SblasError("the AmgPlan was made for another structure than this solver's (rowptr, colidx)")
-                precond.reserve(self.nrhs, stream=stream)
-                name = "sblas_hip_krylov_multi_plan_create_ex"
-                rc = lib().sblas_hip_krylov_multi_plan_create_ex(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
-                                                                 colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind,
-                                                                 precond.handle, C.byref(h))
-            elif self.precond_kind == PRECOND_ILU0:                         # the pair of solve plans; self.precond keeps them alive
-                for q in precond:
-                    if q.n != n or q.rowptr.data_ptr() != rowptr.data_ptr() or q.colidx.data_ptr() != colidx.data_ptr():
-                        raise SblasError("the SptrsvPlans were made for another structure than this solver's (rowptr, colidx)")
-                if not (precond[0].lower and precond[0].unit_diag and not precond[1].lower and not precond[1].unit_diag):
-                    raise SblasError("the pair must be (lower with a unit diagonal, upper with a stored one), as Ilu0Plan.solvers() gives it")
-                name = "sblas_hip_krylov_multi_plan_create_pair"
-                rc = lib().sblas_hip_krylov_multi_plan_create_pair(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
-                                                                   colidx.data_ptr() if self.nnz else None, self.nrhs, precond[0].handle,
-                                                                   precond[1].handle, C.byref(h))
-            else:
-                name = "sblas_hip_krylov_multi_plan_create"
-                rc = lib().sblas_hip_krylov_multi_plan_create(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
-                                                              colidx.data_ptr() if self.nnz else None, self.nrhs, self.precond_kind, C.byref(h))
-        check(rc, name)
+            rc = self._call("plan_create" + door)(-1, _stream(stream), _KRYLOV_METHOD[method], n, self.nnz, rowptr.data_ptr(),
+                                                  colidx.data_ptr() if self.nnz else None, self.nrhs, *plans, C.byref(h))
+        check(rc, "sblas_hip_krylov_multi_plan_create" + door)
         self.handle = h
 
     def info(self):
@@ -4237,91 +4322,6 @@ class KrylovMultiPlan:
         return dict(n=int(out[0]), nnz=int(out[1]), method=[k for k, v in _KRYLOV_METHOD.items() if v == out[2]][0],
                     precond=_PRECOND_NAME[out[3]], nrhs=int(out[4]), blocks=int(out[5]), block_bytes=int(out[6]), partial_bytes=int(out[7]),
                     scalar_bytes=int(out[8]), workspace_bytes=int(out[9]), bytes=int(out[10]), launches=int(out[11]))
-
-    def start(self, val, B, X, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None, lu=None):
-        """Begins a solve: X on entry holds the initial guesses and is updated in place by iterate().  dinv: the inverse
-        diagonal (precond "jacobi"); lu: the ILU(0) factor (precond a pair of SptrsvPlans).  Every refusal comes before
-        any launch."""
-        import torch
-        _krylov_vector("val", val, self.nnz, self.device)
-        ldb = _krylov_block("B", B, self.n, self.nrhs, self.device)
-        ldx = _krylov_block("X", X, self.n, self.nrhs, self.device)
-        pre = None
-        if self.precond_kind == PRECOND_JACOBI:
-            if dinv is None:
-                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
-            _krylov_vector("dinv", dinv, self.n, self.device)
-            pre = dinv
-        elif self.precond_kind == PRECOND_ILU0:
-            if lu is None:
-                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
-            _krylov_vector("lu", lu, self.nnz, self.device)
-            pre = lu
-        elif self.precond_kind == PRECOND_AMG:
-            info = self.precond.info()
-            if not info["ready"]:
-                raise SblasError("the AmgPlan needs setup() before a solve")
-            if info["smoother"] == "chebyshev":
-                raise SblasError("the Chebyshev smoother has no block cycle: set the AmgPlan up with 'jacobi' or 'l1'")
-        if self.n and _blocks_overlap(X, ldx, B, ldb, self.n, self.nrhs):
-            raise SblasError("X must not overlap B")
-        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
-            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
-        with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_krylov_multi_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
-                                                    pre.data_ptr() if pre is not None and pre.numel() else None,
-                                                    B.data_ptr() if self.n else None, ldb, X.data_ptr() if self.n else None, ldx,
-                                                    float(rtol), float(atol), int(max_iter))
-        check(rc, "sblas_hip_krylov_multi_start")
-        self._keep = (val, B, X, pre)
-
-    def iterate(self, k, stream=None):
-        """Enqueues k lockstep iterations: allocates nothing, never synchronises, graph-capturable as a chain."""
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib().sblas_hip_krylov_multi_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_krylov_multi_iterate")
-
-    def status(self, stream=None):
-        """Copies the scalar blocks back and synchronises the stream -> dict of per-column numpy arrays (code, iterations,
-        rnorm, bnorm, alpha, beta, omega, which), lists status and breakdown (the names, as KrylovPlan.status gives them)
-        and running, the count of columns still running."""
-        import torch
-        out = (C.c_double * (8 * self.nrhs))()
-        with torch.cuda.device(self.device):
-            check(lib().sblas_hip_krylov_multi_status(self.handle, _stream(stream), out), "sblas_hip_krylov_multi_status")
-        a = np.array(out, np.float64).reshape(self.nrhs, 8)
-        code, which = a[:, 0].astype(np.int64), a[:, 7].astype(np.int64)
-        return dict(code=code, iterations=a[:, 1].astype(np.int64), rnorm=a[:, 2].copy(), bnorm=a[:, 3].copy(), alpha=a[:, 4].copy(),
-                    beta=a[:, 5].copy(), omega=a[:, 6].copy(), which=which, status=[KRYLOV_STATUS[int(c)] for c in code],
-                    breakdown=[KRYLOV_DENOM[int(w)] for w in which], running=int((code == KRYLOV_RUNNING).sum()))
-
-    def solve(self, val, B, X=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None, lu=None):
-        """start(), then iterate(check_every) / status() until no column is running -> (X, status dict).  X: the initial
-        guesses, updated in place (zeros made here when None).  No column's result depends on check_every."""
-        import torch
-        if int(check_every) < 1:
-            raise SblasError("check_every must be at least 1")
-        if X is None:
-            _krylov_block("B", B, self.n, self.nrhs, self.device)
-            X = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=self.device)
-        self.start(val, B, X, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream, lu=lu)
-        while True:
-            self.iterate(int(check_every), stream=stream)
-            st = self.status(stream=stream)
-            if st["running"] == 0:
-                return X, st
-
-    def destroy(self):
-        if self.handle:
-            lib().sblas_hip_krylov_multi_plan_destroy(self.handle)
-            self.handle = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def _krylov_multi_one_shot(method, A, B, precond, X, kw, make=None):
@@ -4647,7 +4647,7 @@ def gmres_multi_combine(V, Y, out=None, scalars=None, stream=None):
     return out
 
 
-class GmresMultiPlan:
+class GmresMultiPlan(_MultiSolverPlan):
     """Right-preconditioned restarted GMRES(restart) for A X = B with nrhs right-hand sides at once on the n x n CSR
     structure (rowptr, colidx), int32 indices (sblas_hip_gmres_multi_plan_create): nrhs independent GMRES(m) recurrences
     that share A and run in lockstep, one SpMM per Arnoldi step instead of nrhs SpMVs.  A need not be symmetric.  precond:
@@ -4664,6 +4664,10 @@ class GmresMultiPlan:
     loop composed of the SpMM, the pinned dot per column, numpy updates and the scalar step bit for bit; it is NOT
     promised to equal a GmresPlan solve of one column, or a batch of another width."""
 
+    _c = "gmres_multi"
+    _columns = (("restarts", True), ("columns", True), ("eta", False))
+    _denom = GMRES_DENOM
+
     def __init__(self, n, rowptr, colidx, nrhs, restart=30, precond=None, stream=None):
         import torch
         self.handle = None
@@ -4671,26 +4675,9 @@ class GmresMultiPlan:
         if isinstance(restart, bool) or not isinstance(restart, int) or not 1 <= restart <= gmres_multi_limits()["max_restart"]:
             raise SblasError("restart must be an integer in [1, %d], not %r" % (gmres_multi_limits()["max_restart"], restart))
         self.restart = restart
-        self.precond, self.precond_kind = precond, _multi_precond(precond)
-        self.n, self.nnz = n, _structure(n, rowptr, colidx)
-        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
-        self._keep = None
-        lower = upper = None
-        if isinstance(precond, AmgPlan):                                    # self.precond keeps the plans alive
-            if precond.n != n or precond.rowptr.data_ptr() != rowptr.data_ptr() or precond.colidx.data_ptr() != colidx.data_ptr():
-                raise SblasError("the AmgPlan was made for another structure than this solver's (rowptr, colidx)")
-            lower = precond.handle
-        elif self.precond_kind == PRECOND_ILU0:
-            for q in precond:
-                if q.n != n or q.rowptr.data_ptr() != rowptr.data_ptr() or q.colidx.data_ptr() != colidx.data_ptr():
-                    raise SblasError("the SptrsvPlans were made for another structure than this solver's (rowptr, colidx)")
-            if not (precond[0].lower and precond[0].unit_diag and not precond[1].lower and not precond[1].unit_diag):
-                raise SblasError("the pair must be (lower with a unit diagonal, upper with a stored one), as Ilu0Plan.solvers() gives it")
-            lower, upper = precond[0].handle, precond[1].handle
+        lower, upper = self._seat_multi(n, rowptr, colidx, precond, stream)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            if isinstance(precond, AmgPlan):
-                precond.reserve(self.nrhs, stream=stream)
             rc = lib().sblas_hip_gmres_multi_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(),
                                                          colidx.data_ptr() if self.nnz else None, self.nrhs, restart, self.precond_kind,
                                                          lower, upper, C.byref(h))
@@ -4705,49 +4692,6 @@ class GmresMultiPlan:
                     workspace_bytes=int(out[10]), bytes=int(out[11]), step_launches=int(out[12]), close_launches=int(out[13]),
                     restart_launches=int(out[14]), cycle_launches=int(out[15]))
 
-    def start(self, val, B, X, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, stream=None):
-        """Begins a solve: X on entry holds the initial guesses and is updated in place as cycles close.  dinv: the
-        inverse diagonal (precond "jacobi"); lu: the ILU(0) factor (precond a pair of SptrsvPlans).  Every refusal comes
-        before any launch."""
-        import torch
-        _krylov_vector("val", val, self.nnz, self.device)
-        ldb = _krylov_block("B", B, self.n, self.nrhs, self.device)
-        ldx = _krylov_block("X", X, self.n, self.nrhs, self.device)
-        pre = None
-        if self.precond_kind == PRECOND_JACOBI:
-            if dinv is None:
-                raise SblasError("the Jacobi preconditioner needs dinv, the inverse diagonal")
-            _krylov_vector("dinv", dinv, self.n, self.device)
-            pre = dinv
-        elif self.precond_kind == PRECOND_ILU0:
-            if lu is None:
-                raise SblasError("an ILU(0) preconditioner needs lu, its factor")
-            _krylov_vector("lu", lu, self.nnz, self.device)
-            pre = lu
-        elif self.precond_kind == PRECOND_AMG:
-            info = self.precond.info()
-            if not info["ready"]:
-                raise SblasError("the AmgPlan needs setup() before a solve")
-            if info["smoother"] == "chebyshev":
-                raise SblasError("the Chebyshev smoother has no block cycle: set the AmgPlan up with 'jacobi' or 'l1'")
-        if self.n and _blocks_overlap(X, ldx, B, ldb, self.n, self.nrhs):
-            raise SblasError("X must not overlap B")
-        if not (rtol >= 0.0 and atol >= 0.0) or int(max_iter) < 0:
-            raise SblasError("rtol and atol must be >= 0 and max_iter >= 0")
-        with torch.cuda.device(self.device):
-            rc = lib().sblas_hip_gmres_multi_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
-                                                   pre.data_ptr() if pre is not None and pre.numel() else None,
-                                                   B.data_ptr() if self.n else None, ldb, X.data_ptr() if self.n else None, ldx,
-                                                   float(rtol), float(atol), int(max_iter))
-        check(rc, "sblas_hip_gmres_multi_start")
-        self._keep = (val, B, X, pre)
-
-    def iterate(self, k, stream=None):
-        """Enqueues k lockstep steps: allocates nothing, never synchronises, graph-capturable as a chain."""
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib().sblas_hip_gmres_multi_iterate(self.handle, _stream(stream), int(k)), "sblas_hip_gmres_multi_iterate")
-
     def block(self, k, stream=None):
         """A copy of block k of the plan as an (n, nrhs) tensor (sblas_hip_gmres_multi_plan_block): 0 .. restart are the
         basis blocks V_k, then W, U, Z.  Stream-ordered; allocates its result."""
@@ -4757,49 +4701,6 @@ class GmresMultiPlan:
             check(lib().sblas_hip_gmres_multi_plan_block(self.handle, _stream(stream), int(k), out.data_ptr() if self.n else None),
                   "sblas_hip_gmres_multi_plan_block")
         return out
-
-    def status(self, stream=None):
-        """Copies the scalar blocks back and synchronises the stream -> dict of per-column numpy arrays (code, iterations,
-        rnorm, bnorm, restarts, columns, eta, which), lists status and breakdown (the names, as GmresPlan.status gives
-        them) and running, the count of columns still running."""
-        import torch
-        out = (C.c_double * (8 * self.nrhs))()
-        with torch.cuda.device(self.device):
-            check(lib().sblas_hip_gmres_multi_status(self.handle, _stream(stream), out), "sblas_hip_gmres_multi_status")
-        a = np.array(out, np.float64).reshape(self.nrhs, 8)
-        code, which = a[:, 0].astype(np.int64), a[:, 7].astype(np.int64)
-        return dict(code=code, iterations=a[:, 1].astype(np.int64), rnorm=a[:, 2].copy(), bnorm=a[:, 3].copy(),
-                    restarts=a[:, 4].astype(np.int64), columns=a[:, 5].astype(np.int64), eta=a[:, 6].copy(), which=which,
-                    status=[KRYLOV_STATUS[int(c)] for c in code], breakdown=[GMRES_DENOM[int(w)] for w in which],
-                    running=int((code == KRYLOV_RUNNING).sum()))
-
-    def solve(self, val, B, X=None, lu=None, dinv=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8, stream=None):
-        """start(), then iterate(check_every) / status() until no column is running -> (X, status dict).  X: the initial
-        guesses, updated in place (zeros made here when None).  No column's result depends on check_every."""
-        import torch
-        if int(check_every) < 1:
-            raise SblasError("check_every must be at least 1")
-        if X is None:
-            _krylov_block("B", B, self.n, self.nrhs, self.device)
-            X = torch.zeros((self.n, self.nrhs), dtype=torch.float64, device=self.device)
-        self.start(val, B, X, lu=lu, dinv=dinv, rtol=rtol, atol=atol, max_iter=max_iter, stream=stream)
-        while True:
-            self.iterate(int(check_every), stream=stream)
-            st = self.status(stream=stream)
-            if st["running"] == 0:
-                return X, st
-
-    def destroy(self):
-        if self.handle:
-            lib().sblas_hip_gmres_multi_plan_destroy(self.handle)
-            self.handle = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 def gmres_multi(A, B, precond=None, restart=30, X=None, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8):

@@ -4,6 +4,8 @@ floats of tests/solver_compose.py, and the lockstep loops of tests/multi_compose
 import math
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -159,6 +161,61 @@ def test_one_text_of_the_scalar_step():
         assert "switch (op)" not in text.split("// ---- launches")[0] and "KS_BETA] =" not in text, name
     assert src("krylov_scalar.h").count("switch (op)") == 1
     assert "contract(off)" in src("krylov_multi.hip").split("__global__")[0]      # at file scope, ahead of every kernel
+
+
+def test_one_text_of_the_plan_plumbing(sblas):
+    """krylov_multi.hip and gmres_multi.hip keep their plans on multi_plan.h's base, and the two Python classes on
+    _MultiSolverPlan: neither side holds a copy of what the base holds"""
+    src = lambda name: open(os.path.join(ROOT, "s-blas_amd", "csrc", name)).read()
+    base = src("multi_plan.h")
+    for name in ("krylov_multi.hip", "gmres_multi.hip"):
+        text = src(name)
+        assert '#include "multi_plan.h"' in text, name
+        assert "span_bytes" not in text and not re.search(r"^\w[\w \*]*\bproduct\(", text, re.M), name
+        for call in ("sblas_hip_spmm_plan_create", "sblas_hip_amg_plan_reserve_multi", "hipMemcpyDeviceToHost"):
+            assert call not in text and call in base, (name, call)
+    assert "span_bytes" in src("krylov_multi.h") and re.search(r"^inline int product\(", base, re.M)
+    for name in ("start", "solve", "iterate", "destroy", "status"):
+        assert getattr(sblas.KrylovMultiPlan, name) is getattr(sblas.GmresMultiPlan, name), name
+
+
+def overlap_cases():
+    """the rows of tools/krylov_multi_rule_check.cpp's table: (n, s, x0, ldx, b0, ldb, overlap)"""
+    text = open(os.path.join(ROOT, "tools", "krylov_multi_rule_check.cpp")).read()
+    table = text.split("OVERLAP_CASES[] = {")[1].split("};")[0]
+    rows = re.findall(r"\{(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (true|false)\}", table)
+    return [tuple(int(v) for v in r[:6]) + (r[6] == "true",) for r in rows]
+
+
+def test_the_overlap_table_is_pythons_answer_too(sblas):
+    """the literals the rule check holds the C predicate to are what _blocks_overlap answers, either way round"""
+    class At:
+        def __init__(self, ptr):
+            self.ptr = ptr
+
+        def data_ptr(self):
+            return self.ptr
+
+    cases = overlap_cases()
+    assert len(cases) >= 8 and {c[6] for c in cases} == {True, False} and {c[0] for c in cases} >= {0, 1, 5}
+    for n, s, x0, ldx, b0, ldb, want in cases:
+        assert bool(sblas._blocks_overlap(At(x0), ldx, At(b0), ldb, n, s)) == want, (n, s, x0, ldx, b0, ldb)
+        assert bool(sblas._blocks_overlap(At(b0), ldb, At(x0), ldx, n, s)) == want, (n, s, x0, ldx, b0, ldb)
+
+
+def test_the_rule_check_runs_clean_under_the_sanitizers(tmp_path):
+    """tools/krylov_multi_rule_check.cpp, host code only and a program of its own, under the address and
+    undefined-behaviour sanitizers (as test_gmres_multi_host.py runs its rule check)"""
+    cxx = next((p for p in (shutil.which("clang++"), "/opt/rocm/lib/llvm/bin/clang++", shutil.which("g++")) if p and os.path.exists(p)), None)
+    if cxx is None:
+        pytest.skip("no host compiler")
+    exe = str(tmp_path / "krylov_multi_rule_check")
+    src = [os.path.join(ROOT, "tools", "krylov_multi_rule_check.cpp"), os.path.join(ROOT, "s-blas_amd", "csrc", "krylov_multi_rule.cpp")]
+    subprocess.check_call([cxx, "-std=c++17", "-g", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+                          + src + ["-o", exe])
+    done = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    assert done.returncode == 0, done.stdout.decode()
+    assert b"krylov_multi_rule_check: ok" in done.stdout
 
 
 # ---------------------------------------------------------------------------------------------------------------------

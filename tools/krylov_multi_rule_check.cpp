@@ -4,7 +4,8 @@
 //   clang++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       tools/krylov_multi_rule_check.cpp s-blas_amd/csrc/krylov_multi_rule.cpp -o /tmp/krylov_multi_rule_check && /tmp/krylov_multi_rule_check
 // It takes the limits, the kinds a batch accepts, the launch counts and the grid of every width from 1 to 64 at the edge
-// sizes, and drives whole PCG and BiCGStab recurrences of scalar steps on blocks of exactly 16 slots and sums of exactly
+// sizes, asks the overlap predicate both multi-right-hand-side plans refuse "X overlaps B" by (krylov_multi.h, through
+// multi_plan.h) a table of exact cases, and drives whole PCG and BiCGStab recurrences of scalar steps on blocks of exactly 16 slots and sums of exactly
 // nd entries (so a read or write past either end is the sanitizer's to find), against a second restatement of the
 // written order, with a zero, an infinity and a NaN put into every denominator.
 #include <math.h>
@@ -13,6 +14,7 @@
 #include <string.h>
 #include <vector>
 #include "../include/sblas_hip.h"
+#include "../s-blas_amd/csrc/krylov_multi.h" // span_bytes, blocks_overlap: no HIP in there
 
 #pragma clang fp contract(off)
 
@@ -150,6 +152,32 @@ static int bicg_run(int at, int which, double poison)
     return bad;
 }
 
+// The overlap predicate of start (krylov_multi.h), on exact cases: two n x s blocks at byte addresses x0 and b0 with
+// leading dimensions ldx and ldb, and the answer written out.  tests/test_krylov_multi_host.py reads these rows and asks
+// Python's _blocks_overlap the same questions.
+struct OverlapCase {
+    int64_t n;
+    int s;
+    uintptr_t x0;
+    int64_t ldx;
+    uintptr_t b0;
+    int64_t ldb;
+    bool overlap;
+};
+static const OverlapCase OVERLAP_CASES[] = {
+    {0, 3, 4096, 3, 4096, 3, false}, // n = 0 never overlaps, not even at one address
+    {0, 3, 4096, 6, 4104, 6, false},
+    {1, 3, 4096, 3, 4096, 3, true},  // n = 1: one row of s entries, 24 bytes, whatever the leading dimension
+    {1, 3, 4096, 9, 4112, 9, true},
+    {1, 3, 4096, 9, 4120, 9, false},
+    {5, 3, 4096, 3, 4216, 3, false}, // two blocks that touch: b0 == x0 + span, span = (4 * 3 + 3) * 8 = 120
+    {5, 3, 4096, 3, 4215, 3, true},  // one byte less
+    {5, 3, 4096, 4, 4248, 3, false}, // each side by its own leading dimension: span = (4 * 4 + 3) * 8 = 152
+    {5, 3, 4096, 4, 4247, 3, true},
+    {5, 3, 4096, 6, 4120, 6, true},  // the two column halves of one (5, 6) tensor at ld = 6
+    {1, 3, 4096, 6, 4120, 6, false}, // the same halves of a (1, 6) tensor: two rows side by side
+};
+
 int main()
 {
     int bad = 0;
@@ -219,6 +247,11 @@ int main()
         bad += c.i(STATUS) != SBLAS_KRYLOV_RUNNING || c.i(ZERO_X) != 0;
         bad += step(SBLAS_KRYLOV_STEP_PCG_ALPHA, 0, {NAN}, c) != SBLAS_OK;
         bad += c.i(STATUS) != SBLAS_KRYLOV_BREAKDOWN || c.i(WHICH) != SBLAS_KRYLOV_DENOM_PQ || c.i(ITER) != 0;
+    }
+    // start's "X overlaps B", both ways round
+    for (const OverlapCase &c : OVERLAP_CASES) {
+        bad += sblas::blocks_overlap(c.x0, c.ldx, c.b0, c.ldb, c.n, c.s) != c.overlap;
+        bad += sblas::blocks_overlap(c.b0, c.ldb, c.x0, c.ldx, c.n, c.s) != c.overlap;
     }
     printf(bad ? "krylov_multi_rule_check: %d mismatches\n" : "krylov_multi_rule_check: ok\n", bad);
     return bad ? 1 : 0;
