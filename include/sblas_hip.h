@@ -1272,4 +1272,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #include "sblas_hip_gmres_multi.h"
 #include "sblas_hip_geam.h"
 #include "sblas_hip_mspgemm.h"
+#include "sblas_hip_sddmm_narrow.h"
 #endif /* SBLAS_HIP_H */

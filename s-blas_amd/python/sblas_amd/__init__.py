@@ -127,6 +127,10 @@ EXPORTS_MSPGEMM = [
     "sblas_mspgemm_limits", "sblas_mspgemm_ref",
     "sblas_hip_mspgemm_plan_create", "sblas_hip_mspgemm_plan_info", "sblas_hip_mspgemm_plan_numeric", "sblas_hip_mspgemm_plan_destroy",
 ]
+# what include/sblas_hip_sddmm_narrow.h declares (SDDMM at k <= 8 on a part of a CSR pattern: the values gradient of the solves)
+EXPORTS_SDDMM_NARROW = [
+    "sblas_sddmm_narrow_limits", "sblas_sddmm_narrow_ref", "sblas_hip_sddmm_narrow_f64_i32",
+]
 
 
 class SblasError(RuntimeError):
@@ -661,6 +665,11 @@ def lib():
     L.sblas_hip_mspgemm_plan_numeric.argtypes = [vp, vp, vp, vp, vp]
     L.sblas_hip_mspgemm_plan_destroy.restype = C.c_int
     L.sblas_hip_mspgemm_plan_destroy.argtypes = [vp]
+    L.sblas_sddmm_narrow_limits.restype = C.c_int
+    L.sblas_sddmm_narrow_limits.argtypes = [C.POINTER(i64)]
+    for fn in (L.sblas_sddmm_narrow_ref, L.sblas_hip_sddmm_narrow_f64_i32):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, vp, i64, C.c_int, f64, f64, C.c_int, vp]
     _lib = L
     return L
 
@@ -894,6 +903,62 @@ def mspgemm_ref(m, n, k, rowptr_m, colidx_m, rowptr_x, colidx_x, val_x, rowptr_y
     check(lib().sblas_mspgemm_ref(m, n, k, rpm.ctypes.data, ptr(cim), rpx.ctypes.data, ptr(cix), ptr(vx), rpy.ctypes.data, ptr(ciy), ptr(vy),
                                   ptr(out)), "sblas_mspgemm_ref")
     return out
+
+
+# the parts of a pattern the narrow SDDMM fills (SBLAS_PART_* in sblas_hip_sddmm_narrow.h)
+PART_ALL, PART_LOWER, PART_UPPER, PART_STRICT_LOWER, PART_STRICT_UPPER = 0, 1, 2, 3, 4
+_PARTS = {"all": PART_ALL, "lower": PART_LOWER, "upper": PART_UPPER, "strict_lower": PART_STRICT_LOWER, "strict_upper": PART_STRICT_UPPER}
+
+
+def _part(part):
+    if part in _PARTS:
+        return _PARTS[part]
+    if isinstance(part, int) and not isinstance(part, bool):
+        return part                                # the library refuses a number it does not know
+    raise SblasError("part must be one of %s, not %r" % (", ".join(repr(p) for p in _PARTS), part))
+
+
+def sddmm_narrow_limits():
+    """The sizes the narrow SDDMM's kernel is built on (sblas_sddmm_narrow_limits): the widest k, the stored entries one
+    workgroup takes (a run), the threads of a workgroup and the consecutive entries one lane owns."""
+    out = (C.c_int64 * 4)()
+    check(lib().sblas_sddmm_narrow_limits(out), "sblas_sddmm_narrow_limits")
+    return dict(max_k=int(out[0]), chunk=int(out[1]), threads=int(out[2]), entries_per_lane=int(out[3]))
+
+
+def sddmm_narrow_ref(rows, cols, rowptr, colidx, X, Y, out=None, alpha=1.0, beta=0.0, part="all"):
+    """The narrow SDDMM's contract as the library's scalar loop over numpy arrays (sblas_sddmm_narrow_ref; no GPU) -> out,
+    one double per stored entry: alpha * <X[row(e), :k], Y[col(e), :k]> + beta * out[e] inside `part`, +0.0 or beta *
+    out[e] outside.  X (rows x k) and Y (cols x k) are read in place when their last axis is contiguous (any row stride
+    of at least k), so a slice of a wider array keeps its leading dimension; a 1-D X or Y is k = 1.  beta != 0 needs
+    `out`, which is not modified: the result is a new array."""
+    rp, ci = np.ascontiguousarray(rowptr, np.int32), np.ascontiguousarray(colidx, np.int32)
+
+    def dense(t, n, what):
+        t = np.asarray(t, np.float64)
+        if t.ndim == 1:
+            t = t.reshape(-1, 1)
+        if t.ndim != 2 or t.shape[0] != n:
+            raise SblasError("%s must have %d rows, got shape %s" % (what, n, t.shape))
+        if t.size and (t.strides[1] != 8 or t.strides[0] % 8 or t.strides[0] < 8 * t.shape[1]) and not (t.shape[0] <= 1 and t.strides[1] == 8):
+            t = np.ascontiguousarray(t)
+        ld = t.strides[0] // 8 if t.size and t.shape[0] > 1 else max(int(t.shape[1]), 1)
+        return t, int(ld)
+    X, ldx = dense(X, rows, "X")
+    Y, ldy = dense(Y, cols, "Y")
+    if X.shape[1] != Y.shape[1]:
+        raise SblasError("X and Y must have the same number of columns, got %d and %d" % (X.shape[1], Y.shape[1]))
+    if len(rp) != rows + 1 or int(rp[-1]) != len(ci):
+        raise SblasError("rowptr needs rows + 1 = %d entries and must end at nnz = %d" % (rows + 1, len(ci)))
+    if beta != 0.0 and out is None:
+        raise SblasError("beta != 0 needs out")
+    res = np.zeros(len(ci), np.float64) if out is None else np.array(out, np.float64).reshape(-1)
+    if len(res) != len(ci):
+        raise SblasError("out must hold one value per stored entry (%d), got %d" % (len(ci), len(res)))
+    ptr = lambda a: a.ctypes.data if a.size else None
+    check(lib().sblas_sddmm_narrow_ref(-1, None, rows, cols, len(ci), rp.ctypes.data, ptr(ci), ptr(X), max(ldx, 1), ptr(Y), max(ldy, 1),
+                                       int(X.shape[1]), float(alpha), float(beta), _part(part), ptr(res)), "sblas_sddmm_narrow_ref")
+    return res
 
 
 # triangular solves: fill, diagonal, plan modes and launch kinds (SBLAS_FILL_*, SBLAS_DIAG_*, SBLAS_SPTRSV_* in sblas_hip.h)
@@ -4772,6 +4837,66 @@ def sddmm_tensor(A, X, Y, out, alpha=1.0, beta=0.0, workspace=None, stream=None)
     _sddmm_call(rows, cols, nnz, _dev_ptr(rowptr, torch.int32, "rowptr"), _dev_ptr(colidx, torch.int32, "colidx") if nnz else None,
                 px if k and nnz else None, ldx, order_x, py if k and nnz else None, ldy, order_y, k, alpha, beta,
                 pout if nnz else None, workspace, stream)
+
+
+def _narrow_operand(t, n, what):
+    """(pointer, leading dimension, k) of a row-major operand of the narrow SDDMM: n x k with strides (ld, 1), or 1-D (k = 1,
+    any positive stride)"""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.shape[0] != n:
+        raise SblasError("%s must be a tensor of %d rows with 1 or 2 dimensions" % (what, n))
+    if t.dtype != torch.float64:
+        raise SblasError("%s must be float64 (sddmm_narrow handles float64 values and int32 indices only)" % what)
+    if not t.is_cuda:
+        raise SblasError("%s must be a GPU tensor (no CPU path exists)" % what)
+    if t.dim() == 1:
+        ld = int(t.stride(0)) if n > 1 else 1
+        if ld < 1:
+            raise SblasError("%s has stride %d: a 1-D operand needs a positive stride" % (what, ld))
+        return t.data_ptr(), ld, 1
+    k = int(t.shape[1])
+    order, ld = _layout(t, n, k, what)
+    if order != ROW_MAJOR and k > 1 and n > 1:
+        raise SblasError("%s must be row-major (strides (ld, 1)): the narrow SDDMM stages nothing" % what)
+    if order != ROW_MAJOR:                         # one row or one column: the strides name no order
+        ld = int(t.stride(0)) if k == 1 and n > 1 else max(k, 1)
+    return t.data_ptr(), int(ld), k
+
+
+def sddmm_narrow(A, X, Y, out, alpha=1.0, beta=0.0, part="all", stream=None):
+    """The narrow SDDMM (sblas_hip_sddmm_narrow_f64_i32): out[e] = alpha * <X[row(e), :k], Y[col(e), :k]> + beta * out[e]
+    for the stored entries of A = (rows, cols, rowptr, colidx) that lie in `part` ("all", "lower": col <= row, "upper",
+    "strict_lower", "strict_upper"); an entry outside gets +0.0 (beta == 0) or beta * out[e], and its rows of X and Y are
+    never read.  X rows x k and Y cols x k are row-major views (strides (ld, 1)) with 1 <= k <= 8; a 1-D X or Y is k = 1.
+    out: a contiguous float64 tensor of nnz entries.  For part="all" the bits are sddmm_tensor's; one launch, no
+    workspace, graph-capturable."""
+    import torch
+    rows, cols, rowptr, colidx = A
+    if not isinstance(rowptr, torch.Tensor) or not isinstance(colidx, torch.Tensor) or rowptr.dtype != torch.int32 or colidx.dtype != torch.int32:
+        raise SblasError("sddmm_narrow handles float64 values and int32 indices only")
+    px, ldx, kx = _narrow_operand(X, rows, "X")
+    py, ldy, ky = _narrow_operand(Y, cols, "Y")
+    if kx != ky:
+        raise SblasError("X and Y must have the same number of columns, got %d and %d" % (kx, ky))
+    nnz = int(colidx.numel())
+    if rowptr.numel() != rows + 1:
+        raise SblasError("rowptr has %d entries for %d rows" % (rowptr.numel(), rows))
+    if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.numel() != nnz:
+        raise SblasError("out must hold one value per stored entry (%d)" % nnz)
+    pout = _dev_ptr(out, torch.float64, "out")
+    prow, pcol = _dev_ptr(rowptr, torch.int32, "rowptr"), _dev_ptr(colidx, torch.int32, "colidx")
+    for name, t in (("colidx", colidx), ("X", X), ("Y", Y), ("out", out)):
+        if t.device != rowptr.device:
+            raise SblasError("%s is on %s, the pattern on %s" % (name, t.device, rowptr.device))
+    if nnz:                                        # the kernel reads X and Y while it writes out: the extents must be apart
+        for name, p, ld, n in (("X", px, ldx, rows), ("Y", py, ldy, cols)):
+            if n and pout < p + 8 * ((n - 1) * ld + kx) and p < pout + 8 * nnz:
+                raise SblasError("out must not overlap %s" % name)
+    with torch.cuda.device(rowptr.device):
+        check(lib().sblas_hip_sddmm_narrow_f64_i32(-1, _stream(stream), rows, cols, nnz, prow, pcol if nnz else None, px if nnz else None,
+                                                   ldx, py if nnz else None, ldy, kx, float(alpha), float(beta), _part(part),
+                                                   pout if nnz else None), "sblas_hip_sddmm_narrow_f64_i32")
+    return out
 
 
 # ------------------------------------------------------------------------------------------

@@ -27,16 +27,23 @@ makes, with no transposed kernel:
     dval_b = B's pattern o (A^T (dC^T)^T)         mask = B, X = A^T, Y = C^T: two TransposePlans, refreshed with that
                                                   forward's val_a and with dC
 A duplicated entry of A or B receives the full gradient of its position, since C depends on the sum of the duplicates.
+TriangularOperator and SolveOperator make the solves differentiable in the matrix values and the right-hand side:
+    x = TriangularOperator(n, rowptr, colidx, lower=True).solve(val, b, alpha)       # SptrsvPlan's solve, its bits
+    x = SolveOperator(n, rowptr, colidx, method="gmres", precond="ilu0").solve(val, b)   # the Krylov plans
+Backward is one more solve, with the transposed matrix, g = A^-T xbar, then bbar = g and valbar[e] = -<g[row e], x[col e]>
+on the pattern, an SDDMM as narrow as the block of right-hand sides: sddmm_narrow on a triangle of up to four columns,
+where it was measured faster, sddmm_tensor everywhere else (the two agree bit for bit).
 Backward of backward is not supported.  float64 values, int32 indices, GPU tensors only: there is no CPU path.
 torch is imported here, not by the package."""
 import ctypes as C
 
 import torch
 
-from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, GeamPlan, MaskedSpgemmPlan, SblasError, SpgemmPlan, SpmmPlan, SpmvPlan, TransposePlan, _DeviceArray,
+from . import (ATTENTION_MAX_WIDTH, ROW_MAJOR, AmgPlan, GeamPlan, GmresMultiPlan, GmresPlan, Ilu0Plan, KrylovMultiPlan, KrylovPlan,
+               MaskedSpgemmPlan, SblasError, SpgemmPlan, SpmmPlan, SpmvPlan, SptrsvPlan, TransposePlan, _DeviceArray,
                _layout, check, csr_attention,
                csr_attention_backward, csr_attention_workspace_bytes, csr_softmax, csr_softmax_backward,
-               csr_softmax_workspace_bytes, gather, sddmm_tensor, lib, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
+               csr_softmax_workspace_bytes, gather, sddmm_narrow, sddmm_tensor, lib, sddmm_workspace_bytes, spmm_tensor, spmm_workspace_bytes)
 
 
 class CsrOperator:
@@ -471,3 +478,320 @@ def spgemm_multiply(op, val_a, val_b):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise SblasError("%s must be a GPU tensor (no CPU path exists)" % name)
     return _SpgemmMultiply.apply(val_a, val_b, op)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Differentiable solves.  From T x = alpha b:  dx = -T^-1 dT x + alpha T^-1 db.  With g = T^-T xbar this gives
+#     bbar = alpha g        valbar[e] = -<g[row(e), :], x[col(e), :]>   on the stored entries the solve reads
+# an SDDMM at k = the number of right-hand sides.  sddmm_narrow and sddmm_tensor agree bit for bit, so the choice between
+# them is a question of time only, and the rule is: the narrow kernel where tools/solve_grad_bench.py measured it faster
+# on most of its matrices, sddmm_tensor everywhere else (profiles/r30_solve_grad.json).  On the whole pattern it is not
+# (1.02 - 1.03 x sddmm_tensor's time at k = 1 and 2 on three matrices of four, more beyond), so a SolveOperator's values
+# gradient is sddmm_tensor at every width.  On a triangle sddmm_tensor computes every entry and needs a mask pass after
+# it, while the narrow kernel reads only the rows of the entries inside the part: 0.66 - 0.79 x the time of sddmm_tensor
+# + masked_fill_ at k = 1, 2 and 4 on all four matrices, but 0.83 - 1.07 x at k = 8, faster on two of four.  So a
+# TriangularOperator takes the narrow kernel up to NARROW_TRIANGLE_MAX = 4 columns (3 lies between two measured widths;
+# 5 to 7 were not measured and go with 8).
+# ----------------------------------------------------------------------------------------------------------------------
+NARROW_TRIANGLE_MAX = 4
+
+
+def _row_major(g):
+    """an incoming gradient as the solves read it: 1-D contiguous, or 2-D with strides (ld, 1)"""
+    g = _laid_out(g)
+    if g.dim() == 2 and g.shape[1] > 1 and g.stride(1) != 1:
+        g = g.contiguous()
+    return g
+
+
+def _check_solve_args(n, nnz, val, b, what):
+    for name, t in (("val", val), ("b", b)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise SblasError("%s: %s must be a GPU tensor (no CPU path exists)" % (what, name))
+        if t.dtype != torch.float64:
+            raise SblasError("%s: %s must be float64, got %s" % (what, name, t.dtype))
+    if val.dim() != 1 or val.numel() != nnz:
+        raise SblasError("%s: val must hold one value per stored entry (%d), got shape %s" % (what, nnz, tuple(val.shape)))
+    if b.dim() not in (1, 2) or b.shape[0] != n:
+        raise SblasError("%s: b must hold %d entries or be %d x s, got shape %s" % (what, n, n, tuple(b.shape)))
+
+
+def _values_gradient(pattern, g, x, part, mask):
+    """-<g[row(e), :], x[col(e), :]> on the part of the pattern; mask() gives the part as a bool tensor for the wide route"""
+    out = torch.empty(int(pattern[3].numel()), dtype=torch.float64, device=pattern[2].device)
+    s = 1 if g.dim() == 1 else int(g.shape[1])
+    if part != "all" and s <= NARROW_TRIANGLE_MAX:
+        return sddmm_narrow(pattern, g, x, out, -1.0, 0.0, part=part)
+    if g.dim() == 1:
+        g, x = g.view(-1, 1), x.view(-1, 1)
+    sddmm_tensor(pattern, g, x, out, -1.0, 0.0)
+    if part != "all":
+        out.masked_fill_(~mask(), 0.0)                   # beyond the narrow kernel's widths the part is cut out afterwards
+    return out
+
+
+class TriangularOperator:
+    """T x = alpha b on the lower or upper triangle of one n x n CSR structure (int32 rowptr / colidx on the GPU; rows may
+    be unsorted, hold duplicates and entries of the other triangle) whose values change from call to call, differentiable
+    in val and b:
+
+        op = TriangularOperator(n, rowptr, colidx, lower=True, unit_diag=False)
+        x = op.solve(val, b, alpha=1.0)        # triangular_solve(op, val, b, alpha); b: n entries, or n x s row-major
+
+    Forward is SptrsvPlan.solve (b 1-D) or solve_multi (b 2-D), with their bits.  Backward solves T^T g = xbar on a second
+    SptrsvPlan with the opposite `lower` over TransposePlan.csc()'s arrays -- both made by the first backward, the
+    transposed values refreshed from that forward's val -- and returns bbar = alpha g and valbar[e] = -<g[row(e)],
+    x[col(e)]> on the part of the pattern the solve reads: LOWER / UPPER, STRICT_* with unit_diag.  Entries the solve
+    ignores receive exactly +0.0; a duplicated off-diagonal entry receives the full gradient of its position.  Only the
+    halves autograd asks for are computed; backward of backward is not supported.  One call at a time per operator."""
+
+    def __init__(self, n, rowptr, colidx, lower=True, unit_diag=False, mode="auto"):
+        self.plan = SptrsvPlan(n, rowptr, colidx, lower=lower, unit_diag=unit_diag, mode=mode)
+        self.n, self.rowptr, self.colidx, self.nnz = int(n), rowptr, colidx, int(colidx.numel())
+        self.lower, self.unit_diag, self.mode, self.device = bool(lower), bool(unit_diag), mode, rowptr.device
+        self.part = ("strict_" if unit_diag else "") + ("lower" if lower else "upper")
+        self.transpose_plan = self.adjoint_plan = None   # made by the first backward
+        self._csc = self._mask = None
+
+    def solve(self, val, b, alpha=1.0):
+        """x with T(val) x = alpha b, differentiable in val and b."""
+        return triangular_solve(self, val, b, alpha)
+
+    def _pattern(self):
+        return self.n, self.n, self.rowptr, self.colidx
+
+    def _part_mask(self):
+        if self._mask is None:
+            rows = torch.repeat_interleave(torch.arange(self.n, dtype=torch.int32, device=self.device),
+                                           (self.rowptr[1:] - self.rowptr[:-1]).long())
+            c = self.colidx
+            self._mask = {"lower": c <= rows, "upper": c >= rows, "strict_lower": c < rows, "strict_upper": c > rows}[self.part]
+        return self._mask
+
+    def _forward(self, val, b, alpha):
+        if b.dim() == 1:
+            return self.plan.solve(val, b.contiguous(), alpha=alpha)
+        return self.plan.solve_multi(val, _row_major(b), alpha=alpha)
+
+    def _adjoint(self, val, dx):
+        """g with T(val)^T g = dx"""
+        if self.transpose_plan is None:
+            self.transpose_plan = TransposePlan(self.n, self.n, self.rowptr, self.colidx, val)
+            self._csc = self.transpose_plan.csc()[:2]    # the adjoint plan keeps these copies alive and solves on them
+            self.adjoint_plan = SptrsvPlan(self.n, self._csc[0], self._csc[1], lower=not self.lower, unit_diag=self.unit_diag,
+                                           mode=self.mode)
+        else:
+            self.transpose_plan.update_values(val)
+        val_t = _transposed_values(self.transpose_plan) if self.nnz else val
+        return self.adjoint_plan.solve(val_t, dx) if dx.dim() == 1 else self.adjoint_plan.solve_multi(val_t, dx)
+
+    def destroy(self):
+        for p in (self.plan, self.adjoint_plan, self.transpose_plan):
+            if p is not None:
+                p.destroy()
+        self.adjoint_plan = self.transpose_plan = self._csc = self._mask = None
+
+
+class _TriangularSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val, b, op, alpha):
+        ctx.op, ctx.alpha = op, alpha
+        x = op._forward(val.detach().contiguous(), b.detach(), alpha)
+        ctx.save_for_backward(val, x)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dx):
+        val, x = ctx.saved_tensors
+        op = ctx.op
+        g = op._adjoint(val.detach().contiguous(), _row_major(dx))
+        dval = _values_gradient(op._pattern(), g, x, op.part, op._part_mask) if ctx.needs_input_grad[0] else None
+        db = (g if ctx.alpha == 1.0 else g * ctx.alpha) if ctx.needs_input_grad[1] else None
+        return dval, db, None, None
+
+
+def triangular_solve(op, val, b, alpha=1.0):
+    """x with T(val) x = alpha b on a TriangularOperator, differentiable in val and b (alpha is a plain number)."""
+    if not isinstance(op, TriangularOperator):
+        raise SblasError("triangular_solve needs a TriangularOperator")
+    _check_solve_args(op.n, op.nnz, val, b, "triangular_solve")
+    return _TriangularSolve.apply(val, b, op, float(alpha))
+
+
+_SOLVE_METHODS = ("pcg", "bicgstab", "gmres")
+_SOLVE_PRECONDS = (None, "jacobi", "ilu0", "amg", "amg_smoothed")
+
+
+class _SolveSide:
+    """The plans of one system of a SolveOperator -- A's or A^T's: the preconditioner it owns and refreshes from the values,
+    and a solver plan per width (0: one right-hand side on KrylovPlan / GmresPlan; s: KrylovMultiPlan / GmresMultiPlan)."""
+
+    def __init__(self, op, rowptr, colidx, dinv_from=None):
+        self.op, self.rowptr, self.colidx = op, rowptr, colidx
+        self.plans, self.ilu, self.amg, self.dinv, self.lu = {}, None, None, None, None
+        self.dinv_from = dinv_from                       # Jacobi: diag(A^T) = diag(A), the forward side's dinv serves
+        n = op.n
+        if op.precond == "ilu0" or (op.precond == "jacobi" and dinv_from is None):
+            self.ilu = Ilu0Plan(n, rowptr, colidx)       # Jacobi takes only the diagonal's positions from it
+        elif op.precond in ("amg", "amg_smoothed"):
+            self.amg = AmgPlan(n, rowptr, colidx, prolongator="smoothed" if op.precond == "amg_smoothed" else "plain")
+
+    def _refresh(self, val):
+        """the preconditioner for these values -> what solve() takes beside them"""
+        p = self.op.precond
+        if p == "jacobi":
+            if self.dinv_from is not None:
+                return dict(dinv=self.dinv_from.dinv)
+            self.dinv = self.ilu.pivots(val, out=self.dinv).reciprocal_()
+            return dict(dinv=self.dinv)
+        if p == "ilu0":
+            self.lu = self.ilu.factor(val, out=self.lu)
+            return dict(lu=self.lu)
+        if self.amg is not None:
+            self.amg.setup(val)
+        return {}
+
+    def _plan(self, s):
+        if s not in self.plans:
+            op, p = self.op, self.op.precond
+            seat = p if p in (None, "jacobi") else self.amg if self.amg is not None else self.ilu if s == 0 else self.ilu.solvers()
+            args = (op.n, self.rowptr, self.colidx) + ((s,) if s else ())
+            if op.method == "gmres":
+                self.plans[s] = (GmresMultiPlan if s else GmresPlan)(*args, restart=op.restart, precond=seat)
+            else:
+                self.plans[s] = (KrylovMultiPlan if s else KrylovPlan)(*args, method=op.method, precond=seat)
+        return self.plans[s]
+
+    def solve(self, val, b, max_iter):
+        op = self.op
+        plan = self._plan(0 if b.dim() == 1 else int(b.shape[1]))
+        return plan.solve(val, b, None, rtol=op.rtol, atol=op.atol, max_iter=max_iter, check_every=op.check_every, **self._refresh(val))
+
+    def destroy(self):
+        for p in list(self.plans.values()) + [self.ilu, self.amg]:
+            if p is not None:
+                p.destroy()
+        self.plans, self.ilu, self.amg = {}, None, None
+
+
+class SolveOperator:
+    """x = A(val)^-1 b by a Krylov solve on one n x n CSR structure (int32 rowptr / colidx on the GPU) whose values change
+    from call to call, differentiable in val and b:
+
+        op = SolveOperator(n, rowptr, colidx, method="bicgstab", precond="ilu0", rtol=1e-10)
+        x = op.solve(val, b)                   # sparse_solve(op, val, b); b: n entries, or n x s row-major, 1 <= s <= 64
+
+    method: "pcg" (A symmetric positive definite), "bicgstab" or "gmres" (restart).  precond: None, "jacobi", "ilu0", "amg"
+    or "amg_smoothed" (ILU(0), AMG and Jacobi's diagonal need ascending rows that store their diagonal); "chebyshev" is
+    refused.  A 1-D b runs on KrylovPlan / GmresPlan, an (n, s) b on KrylovMultiPlan / GmresMultiPlan, one plan per s, made
+    at first use and kept.  The operator owns its preconditioner and refreshes it from val in every forward (Ilu0Plan.factor,
+    AmgPlan.setup, or the inverse diagonal).
+
+    Backward solves A^T g = xbar with the same method, preconditioner kind, tolerances and limits (backward_max_iter, when
+    set, replaces max_iter there), then bbar = g and valbar[e] = -<g[row(e)], x[col(e)]> on the whole pattern.  With "pcg"
+    the adjoint system is the forward's own and reuses its plans.  Otherwise the first backward makes a TransposePlan and,
+    on its csc() arrays, a SECOND set of solver plans and a preconditioner of the same kind, so a non-symmetric operator
+    holds two sets of plans; Jacobi's inverse diagonal is shared.  A zero xbar, or a zero column of it, gives zeros.
+
+    The gradient is exact only up to kappa(A) * rtol: both solves stop at |r| <= max(rtol |b|, atol), and neither the
+    forward's error in x nor the backward's in g is differentiated.  op.last = dict(forward=status, backward=status) keeps
+    the plans' status dicts.  strict=True raises SblasError, naming the phase, the status and |r|, when a solve ends other
+    than "converged"; strict=False returns what the solve left.  Only the halves autograd asks for are computed; backward
+    of backward is not supported.  One call at a time per operator."""
+
+    def __init__(self, n, rowptr, colidx, method="pcg", precond=None, restart=30, rtol=1e-8, atol=0.0, max_iter=1000, check_every=8,
+                 strict=True):
+        if precond == "chebyshev":
+            raise SblasError("SolveOperator: the 'chebyshev' preconditioner is not supported (None, 'jacobi', 'ilu0', 'amg', 'amg_smoothed')")
+        if method not in _SOLVE_METHODS:
+            raise SblasError("SolveOperator: method must be 'pcg', 'bicgstab' or 'gmres', not %r" % (method,))
+        if precond not in _SOLVE_PRECONDS:
+            raise SblasError("SolveOperator: precond must be None, 'jacobi', 'ilu0', 'amg' or 'amg_smoothed', not %r" % (precond,))
+        for name, t in (("rowptr", rowptr), ("colidx", colidx)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise SblasError("SolveOperator: %s must be a GPU tensor (no CPU path exists)" % name)
+        self.n, self.rowptr, self.colidx, self.nnz, self.device = int(n), rowptr, colidx, int(colidx.numel()), rowptr.device
+        self.method, self.precond, self.restart = method, precond, int(restart)
+        self.rtol, self.atol, self.max_iter, self.check_every, self.strict = float(rtol), float(atol), int(max_iter), int(check_every), bool(strict)
+        self.backward_max_iter = None
+        self.last = dict(forward=None, backward=None)
+        self.forward_side = _SolveSide(self, rowptr, colidx)
+        self.adjoint_side = self.forward_side if method == "pcg" else None
+        self.transpose_plan = self._csc = None
+
+    def solve(self, val, b):
+        """x with A(val) x = b, differentiable in val and b."""
+        return sparse_solve(self, val, b)
+
+    def _pattern(self):
+        return self.n, self.n, self.rowptr, self.colidx
+
+    def _finish(self, phase, st):
+        self.last[phase] = st
+        names = st["status"] if isinstance(st["status"], list) else [st["status"]]
+        if self.strict and any(s != "converged" for s in names):
+            j = [s != "converged" for s in names].index(True)
+            rnorm = float(st["rnorm"][j]) if isinstance(st["status"], list) else float(st["rnorm"])
+            why = st["breakdown"][j] if isinstance(st["status"], list) else st["breakdown"]
+            raise SblasError("sparse_solve: the %s solve ended with status %r (|r| = %g%s%s)"
+                             % (phase, names[j], rnorm, ", column %d" % j if len(names) > 1 else "",
+                                ", denominator %s" % why if why else ""))
+
+    def _forward(self, val, b):
+        x, st = self.forward_side.solve(val, b, self.max_iter)
+        self._finish("forward", st)
+        return x
+
+    def _adjoint(self, val, dx):
+        """g with A(val)^T g = dx"""
+        if self.method == "pcg":
+            side, val_t = self.forward_side, val
+        else:
+            if self.transpose_plan is None:
+                self.transpose_plan = TransposePlan(self.n, self.n, self.rowptr, self.colidx, val)
+                self._csc = self.transpose_plan.csc()[:2]
+                self.adjoint_side = _SolveSide(self, self._csc[0], self._csc[1], dinv_from=self.forward_side)
+            else:
+                self.transpose_plan.update_values(val)
+            side, val_t = self.adjoint_side, (_transposed_values(self.transpose_plan) if self.nnz else val)
+            if self.precond == "jacobi":
+                self.forward_side._refresh(val)          # the shared inverse diagonal, of these values
+        g, st = side.solve(val_t, dx, self.max_iter if self.backward_max_iter is None else int(self.backward_max_iter))
+        self._finish("backward", st)
+        return g
+
+    def destroy(self):
+        for p in (self.forward_side, self.adjoint_side if self.adjoint_side is not self.forward_side else None, self.transpose_plan):
+            if p is not None:
+                p.destroy()
+        self.adjoint_side = self.transpose_plan = self._csc = None
+
+
+class _SparseSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val, b, op):
+        ctx.op = op
+        b = b.detach()
+        x = op._forward(val.detach().contiguous(), b.contiguous() if b.dim() == 1 else _row_major(b))
+        ctx.save_for_backward(val, x)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dx):
+        val, x = ctx.saved_tensors
+        op = ctx.op
+        g = op._adjoint(val.detach().contiguous(), _row_major(dx))
+        dval = _values_gradient(op._pattern(), g, x, "all", None) if ctx.needs_input_grad[0] else None
+        return dval, (g if ctx.needs_input_grad[1] else None), None
+
+
+def sparse_solve(op, val, b):
+    """x with A(val) x = b on a SolveOperator, differentiable in val and b."""
+    if not isinstance(op, SolveOperator):
+        raise SblasError("sparse_solve needs a SolveOperator")
+    _check_solve_args(op.n, op.nnz, val, b, "sparse_solve")
+    if b.dim() == 2 and not 1 <= int(b.shape[1]) <= 64:
+        raise SblasError("sparse_solve: b must have between 1 and 64 columns, got %d" % b.shape[1])
+    return _SparseSolve.apply(val, b, op)
