@@ -12,7 +12,7 @@ namespace {
 
 struct PrecondSeat {
     int kind = SBLAS_PRECOND_NONE;
-    // the caller's plans: ILU(0)'s two solves; an AMG or a Chebyshev plan's handle sits in lower, with upper NULL
+    // the caller's plans: ILU(0)'s two solves; an AMG, a Chebyshev or an FSAI plan's handle sits in lower, with upper NULL
     const void *lower = nullptr, *upper = nullptr;
     const int32_t *rowptr = nullptr, *colidx = nullptr; // the structure the solves read
     const double *values = nullptr; // start's lu_or_dinv: the factor or the inverse diagonal; nullptr where the kind holds its own
@@ -38,8 +38,9 @@ struct PrecondSeat {
             }
         } else if (sblas::precond_applied(precond)) {
             if (!lower_plan || upper_plan) return SBLAS_E_INVALID;
-            const int rc = precond == SBLAS_PRECOND_AMG ? sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rp, ci)
-                                                        : sblas_hip_cheby_plan_speaks_for(lower_plan, device, n, nnz, rp, ci);
+            const int rc = precond == SBLAS_PRECOND_AMG    ? sblas_hip_amg_plan_speaks_for(lower_plan, device, n, nnz, rp, ci)
+                           : precond == SBLAS_PRECOND_FSAI ? sblas_hip_fsai_plan_speaks_for(lower_plan, device, n, nnz, rp, ci)
+                                                           : sblas_hip_cheby_plan_speaks_for(lower_plan, device, n, nnz, rp, ci);
             if (rc != SBLAS_OK) return SBLAS_E_INVALID;
         } else if (lower_plan || upper_plan) {
             return SBLAS_E_INVALID;
@@ -64,15 +65,17 @@ struct PrecondSeat {
         if (kind == SBLAS_PRECOND_ILU0) sblas_hip_sptrsv_plan_info(lower, lower_info), sblas_hip_sptrsv_plan_info(upper, upper_info);
         else if (kind == SBLAS_PRECOND_AMG) sblas_hip_amg_plan_info(lower, lower_info);
         else if (kind == SBLAS_PRECOND_CHEBYSHEV) sblas_hip_cheby_plan_info(lower, lower_info);
+        else if (kind == SBLAS_PRECOND_FSAI) sblas_hip_fsai_plan_info(lower, lower_info);
     }
 
     // out = M^-1 in, for an applied kind.  ILU(0): out = U^-1 (L^-1 in) through tmp with the factor start was given; out
-    // may be in.  AMG: one cycle, Chebyshev: the polynomial, each with the values of its own setup; tmp stays unused
+    // may be in.  AMG: one cycle, Chebyshev: the polynomial, FSAI: z = G^T (G r), each with the values of its own setup; tmp stays unused
     // and out must not overlap in (in_place() says which).
     int apply(hipStream_t s, const double *in, double *tmp, double *out) const
     {
         if (kind == SBLAS_PRECOND_AMG) return sblas_hip_amg_plan_apply(lower, s, in, out);
         if (kind == SBLAS_PRECOND_CHEBYSHEV) return sblas_hip_cheby_plan_apply(lower, s, in, out);
+        if (kind == SBLAS_PRECOND_FSAI) return sblas_hip_fsai_plan_apply(lower, s, in, out);
         const int rc = sblas_hip_sptrsv_f64_i32_planned(lower, s, rowptr, colidx, values, 1.0, in, tmp);
         if (rc != SBLAS_OK) return rc;
         return sblas_hip_sptrsv_f64_i32_planned(upper, s, rowptr, colidx, values, 1.0, tmp, out);

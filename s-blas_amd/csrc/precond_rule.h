@@ -8,9 +8,12 @@
 
 namespace sblas {
 
-// applied by launches of its own between the solver's kernels: the two solves, an AMG cycle, a polynomial.  (Jacobi
-// rides in the solvers' own kernels.)
-inline bool precond_applied(int kind) { return kind == SBLAS_PRECOND_ILU0 || kind == SBLAS_PRECOND_AMG || kind == SBLAS_PRECOND_CHEBYSHEV; }
+// applied by launches of its own between the solver's kernels: the two solves, an AMG cycle, a polynomial, FSAI's two
+// products.  (Jacobi rides in the solvers' own kernels.)  FSAI's code is 6: 5 stays no kind.
+inline bool precond_applied(int kind)
+{
+    return kind == SBLAS_PRECOND_ILU0 || kind == SBLAS_PRECOND_AMG || kind == SBLAS_PRECOND_CHEBYSHEV || kind == SBLAS_PRECOND_FSAI;
+}
 inline bool precond_known(int kind) { return kind == SBLAS_PRECOND_NONE || kind == SBLAS_PRECOND_JACOBI || precond_applied(kind); }
 // takes the caller's values at start (the inverse diagonal, the factor); the other kinds hold those of their own setup
 inline bool precond_takes_values(int kind) { return kind == SBLAS_PRECOND_JACOBI || kind == SBLAS_PRECOND_ILU0; }
@@ -21,7 +24,8 @@ inline bool precond_in_place(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 inline bool precond_multi(int kind) { return precond_known(kind) && !precond_applied(kind); }
 // serves several right-hand sides at once through a plan of its own with a multi-column apply: the AMG
 // block cycle.  ILU(0) no longer waits on a row-major sptrsm -- the tiled solve is there -- but it is
-// seated as a pair of solve plans, not as one plan: precond_multi_pair.  Chebyshev waits on a block polynomial of its own.
+// seated as a pair of solve plans, not as one plan: precond_multi_pair.  Chebyshev waits on a block polynomial of its own,
+// FSAI on a block apply as two SpMMs.
 inline bool precond_multi_applied(int kind) { return kind == SBLAS_PRECOND_AMG; }
 // serves several right-hand sides at once through its PAIR of solve plans (sblas_hip_sptrsm_tile.h's create): ILU(0), as
 // OUT = L^-1 IN by the tiled solve and OUT = U^-1 OUT in place.  Kept apart from precond_multi_applied, whose answers
@@ -43,7 +47,7 @@ inline int64_t precond_multi_launches(int kind, int64_t lower_or_cycle, int64_t 
 inline bool precond_pair(int kind) { return kind == SBLAS_PRECOND_ILU0; }
 
 // Launches of one M^-1, from [5] of the plans' info (sblas_hip_sptrsv_plan_info of the two solves; with one handle
-// sblas_hip_amg_plan_info, one cycle's, or sblas_hip_cheby_plan_info, the degree).  0 for a kind that is not applied,
+// sblas_hip_amg_plan_info, one cycle's, sblas_hip_cheby_plan_info, the degree, or sblas_hip_fsai_plan_info, 2).  0 for a kind that is not applied,
 // whatever the infos; -1 for an unknown kind, a missing info or a negative [5].
 inline int64_t precond_launches(int kind, const int64_t *lower_info, const int64_t *upper_info)
 {

@@ -131,6 +131,12 @@ EXPORTS_MSPGEMM = [
 EXPORTS_SDDMM_NARROW = [
     "sblas_sddmm_narrow_limits", "sblas_sddmm_narrow_ref", "sblas_hip_sddmm_narrow_f64_i32",
 ]
+# what include/sblas_hip_fsai.h declares (FSAI: a factorised sparse approximate inverse on a device plan)
+EXPORTS_FSAI = [
+    "sblas_fsai_limits", "sblas_fsai_pattern", "sblas_fsai_ref",
+    "sblas_hip_fsai_plan_create", "sblas_hip_fsai_plan_setup", "sblas_hip_fsai_plan_apply", "sblas_hip_fsai_plan_check",
+    "sblas_hip_fsai_plan_csr", "sblas_hip_fsai_plan_info", "sblas_hip_fsai_plan_speaks_for", "sblas_hip_fsai_plan_destroy",
+]
 
 
 class SblasError(RuntimeError):
@@ -670,6 +676,28 @@ def lib():
     for fn in (L.sblas_sddmm_narrow_ref, L.sblas_hip_sddmm_narrow_f64_i32):
         fn.restype = C.c_int
         fn.argtypes = [C.c_int, vp, i64, i64, i64, vp, vp, vp, i64, vp, i64, C.c_int, f64, f64, C.c_int, vp]
+    L.sblas_fsai_limits.restype = C.c_int
+    L.sblas_fsai_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_fsai_pattern.restype = C.c_int
+    L.sblas_fsai_pattern.argtypes = [i64, vp, vp, i64, vp, vp, C.c_int, vp, vp, C.POINTER(i64)]
+    L.sblas_fsai_ref.restype = C.c_int
+    L.sblas_fsai_ref.argtypes = [i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.sblas_hip_fsai_plan_create.restype = C.c_int
+    L.sblas_hip_fsai_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, i64, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_fsai_plan_setup.restype = C.c_int
+    L.sblas_hip_fsai_plan_setup.argtypes = [vp, vp, vp]
+    L.sblas_hip_fsai_plan_apply.restype = C.c_int
+    L.sblas_hip_fsai_plan_apply.argtypes = [vp, vp, vp, vp]
+    L.sblas_hip_fsai_plan_check.restype = C.c_int
+    L.sblas_hip_fsai_plan_check.argtypes = [vp, vp, C.POINTER(i64)]
+    L.sblas_hip_fsai_plan_csr.restype = C.c_int
+    L.sblas_hip_fsai_plan_csr.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.sblas_hip_fsai_plan_info.restype = C.c_int
+    L.sblas_hip_fsai_plan_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_fsai_plan_speaks_for.restype = C.c_int
+    L.sblas_hip_fsai_plan_speaks_for.argtypes = [vp, C.c_int, i64, i64, vp, vp]
+    L.sblas_hip_fsai_plan_destroy.restype = C.c_int
+    L.sblas_hip_fsai_plan_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -1094,13 +1122,14 @@ def color_ref(n, rowptr, colidx, seed=0):
 # Krylov solvers: methods, preconditioners, status words and the denominators a breakdown names (SBLAS_KRYLOV_*, SBLAS_PRECOND_*)
 KRYLOV_PCG, KRYLOV_BICGSTAB = 0, 1
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_ILU0, PRECOND_AMG, PRECOND_CHEBYSHEV = 0, 1, 2, 3, 4
+PRECOND_FSAI = 6                                                            # SBLAS_PRECOND_FSAI; 5 is no kind
 KRYLOV_RUNNING, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN, KRYLOV_LIMIT = 0, 1, 2, 3
 KRYLOV_STATUS = {KRYLOV_RUNNING: "running", KRYLOV_CONVERGED: "converged", KRYLOV_BREAKDOWN: "breakdown", KRYLOV_LIMIT: "limit"}
 KRYLOV_DENOM = {0: None, 1: "(p, q)", 2: "rho", 3: "(r^, v)", 4: "(t, t)", 5: "omega"}
 KRYLOV_UPDATES = {"pcg_xr": 0, "pcg_p": 1, "bicg_p": 2, "bicg_s": 3, "bicg_xr": 4}
 _KRYLOV_METHOD = {"pcg": KRYLOV_PCG, "bicgstab": KRYLOV_BICGSTAB}
-_PRECOND_NAME = (None, "jacobi", "ilu0", "amg", "chebyshev")                # a kind's name, at its code PRECOND_*
-_PRECOND_CODE = {name: code for code, name in enumerate(_PRECOND_NAME)}
+_PRECOND_NAME = (None, "jacobi", "ilu0", "amg", "chebyshev", None, "fsai")  # a kind's name, at its code PRECOND_*; 5 is a hole
+_PRECOND_CODE = {name: code for code, name in enumerate(_PRECOND_NAME) if code != 5}
 
 
 def krylov_limits():
@@ -1124,7 +1153,7 @@ def krylov_dot_ref(x, y):
 def krylov_launches(method="pcg", precond=None, lower_launches=0, upper_launches=0):
     """Launches of one iteration (sblas_krylov_launches).  precond: None, "jacobi" or "ilu0"; lower_launches /
     upper_launches: SptrsvPlan.info()["launches"] of the two solves, read with "ilu0" only; with "amg" lower_launches is
-    AmgPlan.info()["launches"], one cycle's; with "chebyshev" it is the polynomial's degree."""
+    AmgPlan.info()["launches"], one cycle's; with "chebyshev" it is the polynomial's degree; with "fsai" FsaiPlan.info()["launches"], 2."""
     if method not in _KRYLOV_METHOD:
         raise SblasError("method must be 'pcg' or 'bicgstab', not %r" % (method,))
     lo, up = (C.c_int64 * 12)(), (C.c_int64 * 12)()
@@ -1190,7 +1219,7 @@ def gmres_solve_ref(R, g):
 def gmres_launches(restart=30, precond=None, lower_launches=0, upper_launches=0):
     """Launches of GMRES (sblas_gmres_launches) -> dict(step, close, restart, start, cycle); a step's do not depend on j.
     precond: None, "jacobi" or "ilu0"; lower_launches / upper_launches: SptrsvPlan.info()["launches"], read with "ilu0" only;
-    with "amg" lower_launches is one cycle's, with "chebyshev" the polynomial's degree."""
+    with "amg" lower_launches is one cycle's, with "chebyshev" the polynomial's degree, with "fsai" 2."""
     lo, up, out = (C.c_int64 * 12)(), (C.c_int64 * 12)(), (C.c_int64 * 4)()
     lo[5], up[5] = int(lower_launches), int(upper_launches)
     cycle = int(lib().sblas_gmres_launches(int(restart), _PRECOND_CODE.get(precond, -1), lo, up, out))
@@ -3792,6 +3821,188 @@ class ChebyshevPlan:
 
 
 # ------------------------------------------------------------------------------------------
+# FSAI: a factorised sparse approximate inverse on a device plan (sblas_fsai_*, sblas_hip_fsai_plan_*; include/sblas_hip_fsai.h)
+# ------------------------------------------------------------------------------------------
+def fsai_limits():
+    """The FSAI plan's limits (sblas_fsai_limits): dict(threads, row_max, g4_max, g16_max, tri_per_lane, vec_per_lane,
+    lds_bytes) -- the setup kernel's workgroup, the longest row of G, the longest rows that 4 and 16 lanes take, and the
+    LDS a lane and a workgroup own."""
+    out = (C.c_int64 * 8)()
+    check(lib().sblas_fsai_limits(out), "sblas_fsai_limits")
+    return dict(zip(("threads", "row_max", "g4_max", "g16_max", "tri_per_lane", "vec_per_lane", "lds_bytes"), (int(v) for v in out)))
+
+
+def _fsai_max_row(max_row):
+    """max_row as the library takes it: None is 0 (a row above row_max entries is refused)"""
+    if max_row is None:
+        return 0
+    if isinstance(max_row, bool) or not isinstance(max_row, int) or not 1 <= max_row <= fsai_limits()["row_max"]:
+        raise SblasError("max_row must be None or an integer in [1, %d], not %r" % (fsai_limits()["row_max"], max_row))
+    return max_row
+
+
+def _fsai_structure(n, rowptr, colidx, what):
+    rowptr = np.ascontiguousarray(rowptr, np.int32)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    if len(rowptr) != int(n) + 1 or (n and int(rowptr[-1]) != len(colidx)):
+        raise SblasError("%s: rowptr needs n + 1 entries that end at len(colidx)" % what)
+    return rowptr, colidx
+
+
+def fsai_pattern(n, rowptr, colidx, pattern=None, max_row=None):
+    """G's pattern on the host (sblas_fsai_pattern, numpy arrays) -> (rowptr_g, colidx_g): row i holds the stored entries
+    of A's row i with column <= i, or those of pattern = (rowptr_p, colidx_p); max_row = k keeps of every longer row its
+    diagonal and the k - 1 entries of largest column below it.  A refused structure raises an SblasError whose .bad_row
+    is the first bad row: a row of A out of order or without its diagonal, a pattern row that does not ascend or lacks
+    its diagonal, a row of G above row_max entries without max_row."""
+    k = _fsai_max_row(max_row)
+    rowptr, colidx = _fsai_structure(n, rowptr, colidx, "A")
+    if pattern is not None:
+        rp, cp = _fsai_structure(n, pattern[0], pattern[1], "pattern")
+    out_rp = np.zeros(int(n) + 1, np.int32)
+    out_ci = np.zeros(max(len(cp) if pattern is not None else len(colidx), 1), np.int32)
+    bad = C.c_int64(-1)
+    rc = lib().sblas_fsai_pattern(int(n), rowptr.ctypes.data, colidx.ctypes.data, len(cp) if pattern is not None else 0,
+                                  rp.ctypes.data if pattern is not None else None, cp.ctypes.data if pattern is not None else None, k,
+                                  out_rp.ctypes.data, out_ci.ctypes.data, C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_fsai_pattern", rc, bad.value)
+    return out_rp, out_ci[:int(out_rp[-1])].copy()
+
+
+def fsai_ref(n, rowptr, colidx, val, rowptr_g, colidx_g):
+    """G's values by the scalar loop that is the contract (sblas_fsai_ref, numpy arrays), on a pattern fsai_pattern gave
+    -> (val_g, bad_row): bad_row is the least row whose dense system failed (written as its diagonal alone), or None."""
+    rowptr, colidx, val = _cheby_csr(n, rowptr, colidx, val)
+    rowptr_g, colidx_g = _fsai_structure(n, rowptr_g, colidx_g, "G")
+    val_g = np.zeros(max(len(colidx_g), 1))
+    bad = C.c_int64(-1)
+    rc = lib().sblas_fsai_ref(int(n), rowptr.ctypes.data, colidx.ctypes.data, val.ctypes.data, rowptr_g.ctypes.data, colidx_g.ctypes.data,
+                              val_g.ctypes.data, C.byref(bad))
+    if rc != 0:
+        raise _bad_structure("sblas_fsai_ref", rc, bad.value)
+    return val_g[:len(colidx_g)].copy(), None if bad.value < 0 else int(bad.value)
+
+
+class FsaiPlan:
+    """The factorised sparse approximate inverse of Kolotilina and Yeremin for the symmetric positive definite n x n CSR
+    matrix (rowptr, colidx), int32 indices (sblas_hip_fsai_plan_create): a sparse lower-triangular G with G A G^T ~ I,
+    applied as z = G^T (G r) by two planned SpMVs.  Every row must be strictly ascending in column and store its diagonal;
+    only entries with column <= row are ever read.  pattern None: row i of G holds the stored entries of A's row i with
+    column <= i; pattern = (rowptr_g, colidx_g), GPU int32 tensors: the caller's (ascending rows; entries above the
+    diagonal are ignored; positions A does not store count as zero).  A row of G above 64 entries is refused unless
+    max_row = k (1 <= k <= 64): every longer row then keeps its diagonal and the k - 1 entries of largest column below
+    it -- a structural and crude thinning that knows no value (on A^2 of a grid it drops the far neighbours first and
+    costs more iterations than A's own pattern).  A bad structure raises an SblasError that names the first bad row
+    (.bad_row).  The plan keeps rowptr and colidx alive and gathers from them: do not change them.  setup(val) is one
+    launch of the gather-and-Cholesky kernel and the transpose's value update: device work only, repeatable and
+    graph-capturable; apply() allocates nothing inside the library and never synchronises; check() is the one call that
+    synchronises.  Every bit is pinned (include/sblas_hip_fsai.h; fsai_pattern and fsai_ref restate it on the host).
+    KrylovPlan and GmresPlan take the plan as precond.
+
+    The lower triangle of A^2 as the pattern, through SpgemmPlan and a lower-triangle filter:
+
+        sq = SpgemmPlan(n, n, n, rowptr, colidx, rowptr, colidx)
+        rp2, ci2 = sq.csr()                                  # rows ascend when A's do
+        rows = torch.repeat_interleave(torch.arange(n, device=ci2.device), (rp2[1:] - rp2[:-1]).long())
+        keep = ci2.long() <= rows
+        counts = torch.zeros(n, dtype=torch.long, device=ci2.device).index_add_(0, rows[keep], torch.ones_like(rows[keep]))
+        rpl = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).int()
+        plan = FsaiPlan(n, rowptr, colidx, pattern=(rpl, ci2[keep].contiguous()))
+    """
+
+    def __init__(self, n, rowptr, colidx, pattern=None, max_row=None, stream=None):
+        import torch
+        self.n, self.handle, self._val = n, None, None
+        k = _fsai_max_row(max_row)
+        self.nnz = _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device = rowptr, colidx, rowptr.device
+        self.pattern = None
+        nnz_p, rp_p, ci_p = 0, None, None
+        if pattern is not None:
+            if not isinstance(pattern, (tuple, list)) or len(pattern) != 2:
+                raise SblasError("pattern must be None or a pair (rowptr_g, colidx_g)")
+            nnz_p = _structure(n, pattern[0], pattern[1])
+            if pattern[0].device != self.device or pattern[1].device != self.device:
+                raise SblasError("pattern is on %s, the matrix on %s" % (pattern[0].device, self.device))
+            self.pattern = (pattern[0], pattern[1])
+            rp_p = pattern[0].data_ptr()
+            ci_p = pattern[1].data_ptr() if nnz_p else None
+        if colidx.device != self.device:
+            raise SblasError("colidx is on %s, rowptr on %s" % (colidx.device, self.device))
+        h, bad = C.c_void_p(), C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_fsai_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr() if n else None,
+                                                  colidx.data_ptr() if self.nnz else None, nnz_p, rp_p, ci_p, k, C.byref(h), C.byref(bad))
+        if rc != 0:
+            raise _bad_structure("sblas_hip_fsai_plan_create", rc, bad.value)
+        self.handle = h
+        self.nnz_g = self.info()["nnz_g"]
+
+    def info(self):
+        out = (C.c_int64 * 12)()
+        check(lib().sblas_hip_fsai_plan_info(self.handle, out), "sblas_hip_fsai_plan_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), nnz_g=int(out[2]), longest=int(out[3]), units=int(out[4]), launches=int(out[5]),
+                    bytes=int(out[6]), ready=bool(out[7]), rows_g4=int(out[8]), rows_g16=int(out[9]), rows_g64=int(out[10]))
+
+    def csr(self):
+        """(rowptr_g, colidx_g, val_g): torch views of the plan's device arrays; they live as long as the plan, and val_g
+        holds what the last setup() wrote."""
+        import torch
+        ptrs = [C.c_void_p() for _ in range(3)]
+        check(lib().sblas_hip_fsai_plan_csr(self.handle, *[C.byref(p) for p in ptrs]), "sblas_hip_fsai_plan_csr")
+        def one(p, n, typestr, dtype):
+            if n == 0 or not p.value:
+                return torch.zeros(n, dtype=dtype, device=self.device)
+            return torch.as_tensor(_DeviceArray(p.value, n, typestr), device=self.device)
+        return (one(ptrs[0], self.n + 1, "<i4", torch.int32), one(ptrs[1], self.nnz_g, "<i4", torch.int32),
+                one(ptrs[2], self.nnz_g, "<f8", torch.float64))
+
+    def setup(self, val, stream=None):
+        """G's values from val, on the device.  Every refusal comes before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_fsai_plan_setup(self.handle, _stream(stream), val.data_ptr() if self.nnz else None)
+        check(rc, "sblas_hip_fsai_plan_setup")
+        self._val = val
+
+    def apply(self, r, out=None, stream=None):
+        """out = G^T (G r).  out: made here when None; it must not overlap r.  Returns out."""
+        import torch
+        _krylov_vector("r", r, self.n, self.device)
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        _krylov_vector("out", out, self.n, self.device)
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_fsai_plan_apply(self.handle, _stream(stream), r.data_ptr() if self.n else None,
+                                                 out.data_ptr() if self.n else None)
+        check(rc, "sblas_hip_fsai_plan_apply")
+        return out
+
+    def check(self, stream=None):
+        """The least row whose dense system the last setup() failed (it was written as its diagonal alone), or None.
+        Synchronises."""
+        import torch
+        bad = C.c_int64(-1)
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_fsai_plan_check(self.handle, _stream(stream), C.byref(bad)), "sblas_hip_fsai_plan_check")
+        return None if bad.value < 0 else int(bad.value)
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_fsai_plan_destroy(self.handle)
+            self.handle = None
+        self._val = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------------------------------
 # Krylov solvers on a plan, resident on the device: PCG and BiCGStab (sblas_hip_krylov_*)
 # ------------------------------------------------------------------------------------------
 def krylov_dots(pairs, out=None, workspace=None, stream=None):
@@ -3853,7 +4064,7 @@ def krylov_update(op, scalars, vectors, partial=None, jacobi=False, stream=None)
 
 def _precond_seat(precond):
     """precond as a solver plan takes it -> (kind, lower, upper): the code PRECOND_* and the plans whose handles go with it.
-    An AmgPlan's or a ChebyshevPlan's handle travels in the lower plan's place, with no upper one."""
+    An AmgPlan's, a ChebyshevPlan's or an FsaiPlan's handle travels in the lower plan's place, with no upper one."""
     if precond is None:
         return PRECOND_NONE, None, None
     if isinstance(precond, str) and precond == "jacobi":
@@ -3866,7 +4077,10 @@ def _precond_seat(precond):
         return PRECOND_AMG, precond, None
     if isinstance(precond, ChebyshevPlan):
         return PRECOND_CHEBYSHEV, precond, None
-    raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan or a ChebyshevPlan, not %r" % (precond,))
+    if isinstance(precond, FsaiPlan):
+        return PRECOND_FSAI, precond, None
+    raise SblasError("precond must be None, 'jacobi', an Ilu0Plan, a pair of SptrsvPlans, an AmgPlan, a ChebyshevPlan or an FsaiPlan, not %r"
+                     % (precond,))
 
 
 class _SolverPlan:
@@ -4018,8 +4232,8 @@ class KrylovPlan(_SolverPlan):
 def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
     import torch
     n, rowptr, colidx, val = A
-    if precond not in (None, "jacobi", "ilu0", "amg", "amg_smoothed", "chebyshev"):
-        raise SblasError("precond must be None, 'jacobi', 'ilu0', 'amg', 'amg_smoothed' or 'chebyshev', not %r" % (precond,))
+    if precond not in (None, "jacobi", "ilu0", "amg", "amg_smoothed", "chebyshev", "fsai"):
+        raise SblasError("precond must be None, 'jacobi', 'ilu0', 'amg', 'amg_smoothed', 'chebyshev' or 'fsai', not %r" % (precond,))
     ilu = plan = amg = None
     lu = dinv = None
     try:
@@ -4028,6 +4242,9 @@ def _krylov_one_shot(method, A, b, precond, x, kw, make=None):
             amg.setup(val)
         elif precond == "chebyshev":                                        # the defaults: degree 4 on the device's estimate
             amg = ChebyshevPlan(n, rowptr, colidx)
+            amg.setup(val)
+        elif precond == "fsai":                                             # the default: G on A's lower pattern
+            amg = FsaiPlan(n, rowptr, colidx)
             amg.setup(val)
         elif precond is not None:                                           # both read the diagonal's places off the ILU(0) plan
             ilu = Ilu0Plan(n, rowptr, colidx)
