@@ -1274,4 +1274,5 @@ int sblas_mm_read_csr(const char *path, int32_t *rowptr, int32_t *colidx, double
 #include "sblas_hip_mspgemm.h"
 #include "sblas_hip_sddmm_narrow.h"
 #include "sblas_hip_fsai.h"
+#include "sblas_hip_eigsh.h"
 #endif /* SBLAS_HIP_H */

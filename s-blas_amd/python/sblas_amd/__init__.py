@@ -139,6 +139,15 @@ EXPORTS_FSAI = [
 ]
 
 
+# what include/sblas_hip_eigsh.h declares (thick-restart Lanczos eigenpairs on a device plan)
+EXPORTS_EIGSH = [
+    "sblas_eigsh_limits", "sblas_eigsh_sizes", "sblas_eigsh_launches", "sblas_eigsh_jacobi_ref", "sblas_eigsh_ritz_ref", "sblas_eigsh_step_ref",
+    "sblas_eigsh_rotate_ref", "sblas_hip_eigsh_rotate_f64", "sblas_hip_eigsh_ritz_f64", "sblas_hip_eigsh_plan_create", "sblas_hip_eigsh_start",
+    "sblas_hip_eigsh_iterate", "sblas_hip_eigsh_status", "sblas_hip_eigsh_values", "sblas_hip_eigsh_vectors", "sblas_hip_eigsh_info",
+    "sblas_hip_eigsh_destroy",
+]
+
+
 class SblasError(RuntimeError):
     pass
 
@@ -698,6 +707,40 @@ def lib():
     L.sblas_hip_fsai_plan_speaks_for.argtypes = [vp, C.c_int, i64, i64, vp, vp]
     L.sblas_hip_fsai_plan_destroy.restype = C.c_int
     L.sblas_hip_fsai_plan_destroy.argtypes = [vp]
+    L.sblas_eigsh_limits.restype = C.c_int
+    L.sblas_eigsh_limits.argtypes = [C.POINTER(i64)]
+    L.sblas_eigsh_sizes.restype = C.c_int
+    L.sblas_eigsh_sizes.argtypes = [i64, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]
+    L.sblas_eigsh_launches.restype = i64
+    L.sblas_eigsh_launches.argtypes = [C.c_int, C.c_int, C.POINTER(i64)]
+    L.sblas_eigsh_jacobi_ref.restype = C.c_int
+    L.sblas_eigsh_jacobi_ref.argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.sblas_eigsh_ritz_ref.restype = C.c_int
+    L.sblas_eigsh_ritz_ref.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp]
+    L.sblas_eigsh_step_ref.restype = C.c_int
+    L.sblas_eigsh_step_ref.argtypes = [C.c_int, vp, f64, vp, vp]
+    L.sblas_eigsh_rotate_ref.restype = C.c_int
+    L.sblas_eigsh_rotate_ref.argtypes = [i64, C.c_int, C.c_int, vp, i64, vp, C.c_int]
+    L.sblas_hip_eigsh_rotate_f64.restype = C.c_int
+    L.sblas_hip_eigsh_rotate_f64.argtypes = [C.c_int, vp, i64, C.c_int, C.c_int, vp, i64, vp, C.c_int]
+    L.sblas_hip_eigsh_ritz_f64.restype = C.c_int
+    L.sblas_hip_eigsh_ritz_f64.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.sblas_hip_eigsh_plan_create.restype = C.c_int
+    L.sblas_hip_eigsh_plan_create.argtypes = [C.c_int, vp, i64, i64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u32, C.POINTER(vp)]
+    L.sblas_hip_eigsh_start.restype = C.c_int
+    L.sblas_hip_eigsh_start.argtypes = [vp, vp, vp, vp, f64, f64, i64]
+    L.sblas_hip_eigsh_iterate.restype = C.c_int
+    L.sblas_hip_eigsh_iterate.argtypes = [vp, vp, i64]
+    L.sblas_hip_eigsh_status.restype = C.c_int
+    L.sblas_hip_eigsh_status.argtypes = [vp, vp, C.POINTER(f64), vp, vp]
+    L.sblas_hip_eigsh_values.restype = C.c_int
+    L.sblas_hip_eigsh_values.argtypes = [vp, vp, vp]
+    L.sblas_hip_eigsh_vectors.restype = C.c_int
+    L.sblas_hip_eigsh_vectors.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.sblas_hip_eigsh_info.restype = C.c_int
+    L.sblas_hip_eigsh_info.argtypes = [vp, C.POINTER(i64)]
+    L.sblas_hip_eigsh_destroy.restype = C.c_int
+    L.sblas_hip_eigsh_destroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -4991,6 +5034,328 @@ def gmres_multi(A, B, precond=None, restart=30, X=None, rtol=1e-8, atol=0.0, max
     steps.  -> (X, status dict of per-column arrays).  The plans made here are destroyed before returning."""
     return _krylov_multi_one_shot(None, A, B, precond, X, dict(rtol=rtol, atol=atol, max_iter=max_iter, check_every=check_every),
                                   make=lambda n, rowptr, colidx, nrhs, pre: GmresMultiPlan(n, rowptr, colidx, nrhs, restart=restart, precond=pre))
+
+
+# ------------------------------------------------------------------------------------------
+# Eigenpairs of a symmetric matrix: thick-restart Lanczos on a plan (sblas_hip_eigsh_*)
+# ------------------------------------------------------------------------------------------
+EIGSH_WHICH = {"LA": 0, "SA": 1, "LM": 2}
+EIGSH_DENOM = {0: None, 1: "v0", 2: "beta", 3: "t", 4: "invariant"}
+
+
+def eigsh_limits():
+    """The eigenvalue plan's limits (sblas_eigsh_limits): dict(max_ncv, default_ncv, ld, max_sweeps, block_slots,
+    matrix_doubles, the offsets t, y, theta, rho, q, h, c in the small-matrix block, rotate_rows, ritz_threads)."""
+    out = (C.c_int64 * 16)()
+    check(lib().sblas_eigsh_limits(out), "sblas_eigsh_limits")
+    names = ("max_ncv", "default_ncv", "ld", "max_sweeps", "block_slots", "matrix_doubles", "t", "y", "theta", "rho", "q", "h", "c",
+             "rotate_rows", "ritz_threads")
+    return {name: int(out[i]) for i, name in enumerate(names)}
+
+
+def _eigsh_sizes(n, k, ncv, keep, which):
+    """the refusals of k, ncv, keep and which, in the Krylov plans' style -> (ncv, keep) with the defaults put in"""
+    lim = eigsh_limits()
+    if which not in EIGSH_WHICH:
+        raise SblasError("which must be 'LA', 'SA' or 'LM', not %r" % (which,))
+    for name, v in (("n", n), ("k", k), ("ncv", ncv), ("keep", keep)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) and not (v is None and name in ("ncv", "keep")):
+            raise SblasError("%s must be an integer, not %r" % (name, v))
+    if k < 1:
+        raise SblasError("k must be at least 1, not %d" % k)
+    if ncv is None:
+        ncv = min(max(2 * k + 1, lim["default_ncv"]), lim["max_ncv"], n - 1)
+    if ncv > lim["max_ncv"]:
+        raise SblasError("ncv must be at most %d, not %d" % (lim["max_ncv"], ncv))
+    if ncv >= n:
+        raise SblasError("ncv must be below n = %d, not %d" % (n, ncv))
+    if k >= ncv:
+        raise SblasError("k must be below ncv = %d, not %d" % (ncv, k))
+    if keep is None:
+        keep = k + (ncv - k) // 2
+    if not k <= keep <= ncv - 1:
+        raise SblasError("keep must be in [k, ncv - 1] = [%d, %d], not %d" % (k, ncv - 1, keep))
+    return int(ncv), int(keep)
+
+
+def eigsh_launches(ncv=20, keep=12):
+    """Launches of the eigenvalue plan (sblas_eigsh_launches) -> dict(step, start, cycle, tail): a step's do not depend
+    on its column; tail is the cycle's Ritz kernel and rotation."""
+    out = (C.c_int64 * 4)()
+    if int(lib().sblas_eigsh_launches(int(ncv), int(keep), out)) < 0:
+        raise SblasError("sblas_eigsh_launches refused its arguments")
+    return dict(step=int(out[0]), start=int(out[1]), cycle=int(out[2]), tail=int(out[3]))
+
+
+def eigsh_jacobi_ref(T):
+    """The cyclic Jacobi loop restated on the host (sblas_eigsh_jacobi_ref): T symmetric (mm, mm), finite -> dict(theta,
+    Y, sweeps): the diagonal the loop ends with (unordered), the eigenvectors by columns, the sweeps that rotated."""
+    T = np.asarray(T, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] != T.shape[1] or not 1 <= T.shape[0] <= eigsh_limits()["max_ncv"]:
+        raise SblasError("T must be square with 1 to %d rows, got shape %s" % (eigsh_limits()["max_ncv"], T.shape))
+    mm = T.shape[0]
+    cols = np.ascontiguousarray(T.T)
+    theta, Y, sweeps = np.zeros(mm), np.zeros((mm, mm)), C.c_int(0)
+    check(lib().sblas_eigsh_jacobi_ref(mm, cols.ctypes.data, mm, theta.ctypes.data, Y.ctypes.data, mm, C.byref(sweeps)), "sblas_eigsh_jacobi_ref")
+    return dict(theta=theta, Y=np.ascontiguousarray(Y.T), sweeps=int(sweeps.value))
+
+
+def eigsh_step_ref(j, h, beta, T=None, matvecs=0):
+    """The scalar part of step j's last fold restated on the host (sblas_eigsh_step_ref): h, the j + 1 coefficients,
+    becomes column j and row j of T ((ncv, ncv), updated in a copy; zeros when None), the matvec is counted and beta
+    decides -> dict(T, columns, matvecs, beta, forms (v_{j+1} = w / beta is formed), invariant, status, breakdown)."""
+    lim = eigsh_limits()
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    if not 0 <= int(j) < lim["max_ncv"] or h.shape != (int(j) + 1,):
+        raise SblasError("0 <= j < %d and h of j + 1 entries, not j = %r and h of shape %s" % (lim["max_ncv"], j, h.shape))
+    T = np.zeros((j + 1, j + 1)) if T is None else np.array(T, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] != T.shape[1] or not j < T.shape[0] <= lim["max_ncv"]:
+        raise SblasError("T must be square with j + 1 to %d rows, got shape %s" % (lim["max_ncv"], T.shape))
+    blk, mat = _eigsh_blocks(T, 0.0, 0.0, 0.0, 0, 0, False, 0)
+    blk[2], blk[3] = int(matvecs), int(j)
+    forms = int(lib().sblas_eigsh_step_ref(int(j), h.ctypes.data, float(beta), blk.ctypes.data, mat.ctypes.data))
+    if forms < 0:
+        raise SblasError("sblas_eigsh_step_ref refused its arguments")
+    ld, m = lim["ld"], T.shape[0]
+    return dict(T=mat[lim["t"]:lim["t"] + ld * ld].reshape(ld, ld).T[:m, :m].copy(), columns=int(blk[3]), matvecs=int(blk[2]),
+                beta=float(blk.view(np.float64)[4]), forms=bool(forms), invariant=bool(blk[12]), status=KRYLOV_STATUS[int(blk[0])],
+                breakdown=EIGSH_DENOM[int(blk[5])])
+
+
+def _eigsh_blocks(T, beta, rtol, atol, restarts, max_restarts, invariant, status):
+    """the two blocks of a Ritz step over T's mm columns as host arrays: (blk as int64 with a float64 view, mat)"""
+    lim = eigsh_limits()
+    T = np.asarray(T, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] != T.shape[1] or not 1 <= T.shape[0] <= lim["max_ncv"]:
+        raise SblasError("T must be square with 1 to %d rows, got shape %s" % (lim["max_ncv"], T.shape))
+    mm, ld = T.shape[0], lim["ld"]
+    blk = np.zeros(lim["block_slots"], dtype=np.int64)
+    fb = blk.view(np.float64)
+    blk[0], blk[1], blk[3], blk[10], blk[12] = int(status), int(restarts), mm, int(max_restarts), 1 if invariant else 0
+    fb[4], fb[8], fb[9] = float(beta), float(rtol), float(atol)
+    mat = np.zeros(lim["matrix_doubles"])
+    mat[lim["t"]:lim["t"] + ld * ld].reshape(ld, ld)[:mm, :mm] = T.T
+    return blk, mat
+
+
+def _eigsh_ritz_result(blk, mat, mm):
+    lim = eigsh_limits()
+    ld, fb = lim["ld"], blk.view(np.float64)
+    square = lambda key: mat[lim[key]:lim[key] + ld * ld].reshape(ld, ld).T.copy()
+    kk = int(blk[14])
+    return dict(status=KRYLOV_STATUS[int(blk[0])], code=int(blk[0]), restarts=int(blk[1]), converged=int(blk[11]), columns=int(blk[3]),
+                breakdown=EIGSH_DENOM[int(blk[5])], act=int(blk[6]), mm=int(blk[13]), kk=kk, beta=float(fb[4]),
+                theta=mat[lim["theta"]:lim["theta"] + mm].copy(), residuals=mat[lim["rho"]:lim["rho"] + mm].copy(),
+                T=square("t"), Y=square("y"), Q=square("q")[:mm, :kk].copy(), blk=blk.copy(), mat=mat.copy())
+
+
+def _eigsh_ritz_args(k, keep, which):
+    if which not in EIGSH_WHICH:
+        raise SblasError("which must be 'LA', 'SA' or 'LM', not %r" % (which,))
+    if not 1 <= int(k) <= int(keep) <= eigsh_limits()["max_ncv"] - 1:
+        raise SblasError("1 <= k <= keep <= %d, not k = %r, keep = %r" % (eigsh_limits()["max_ncv"] - 1, k, keep))
+    return int(k), int(keep), EIGSH_WHICH[which]
+
+
+def eigsh_ritz_ref(T, beta, k, keep, which="LA", rtol=1e-8, atol=0.0, restarts=0, max_restarts=300, invariant=False, status=0):
+    """The whole Ritz step restated on the host (sblas_eigsh_ritz_ref) over the mm = T.shape[0] finished columns ->
+    dict(status, code, restarts, converged, columns, breakdown, act, mm, kk, beta, theta, residuals (mm each, in the
+    order of which), T, Y (64 x 64, as rows and columns), Q (mm x kk), blk, mat (the raw blocks))."""
+    k, keep, w = _eigsh_ritz_args(k, keep, which)
+    blk, mat = _eigsh_blocks(T, beta, rtol, atol, restarts, max_restarts, invariant, status)
+    check(lib().sblas_eigsh_ritz_ref(k, keep, w, blk.ctypes.data, mat.ctypes.data), "sblas_eigsh_ritz_ref")
+    return _eigsh_ritz_result(blk, mat, np.asarray(T).shape[0])
+
+
+def eigsh_ritz(T, beta, k, keep, which="LA", rtol=1e-8, atol=0.0, restarts=0, max_restarts=300, invariant=False, status=0,
+               device=None, stream=None):
+    """The Ritz kernel alone (sblas_hip_eigsh_ritz_f64): the host arrays of eigsh_ritz_ref go to the device, one workgroup
+    runs, and everything comes back -> the same dict.  Synchronises (a test and measurement door, not a solver's)."""
+    import torch
+    k, keep, w = _eigsh_ritz_args(k, keep, which)
+    blk, mat = _eigsh_blocks(T, beta, rtol, atol, restarts, max_restarts, invariant, status)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    dblk, dmat = torch.from_numpy(blk).to(device), torch.from_numpy(mat).to(device)
+    with torch.cuda.device(device):
+        check(lib().sblas_hip_eigsh_ritz_f64(-1, _stream(stream), k, keep, w, dblk.data_ptr(), dmat.data_ptr()), "sblas_hip_eigsh_ritz_f64")
+    return _eigsh_ritz_result(dblk.cpu().numpy(), dmat.cpu().numpy(), np.asarray(T).shape[0])
+
+
+def eigsh_rotate_ref(V, Q):
+    """The basis rotation restated on the host (sblas_eigsh_rotate_ref).  V: (mm + 1, n) rows as columns of the basis; Q:
+    (mm, keep).  -> a new (mm + 1, n) array: rows 0 .. keep - 1 are sum_l Q[l][i] V[l] in gmres_combine's order, row keep
+    is row mm, the others are unchanged."""
+    V = np.array(V, dtype=np.float64, order="C")
+    Q = np.asarray(Q, dtype=np.float64)
+    if V.ndim != 2 or Q.ndim != 2 or V.shape[0] != Q.shape[0] + 1 or not 1 <= Q.shape[1] <= Q.shape[0] <= eigsh_limits()["max_ncv"]:
+        raise SblasError("V must be (mm + 1, n) and Q (mm, keep) with 1 <= keep <= mm <= %d, got %s and %s"
+                         % (eigsh_limits()["max_ncv"], V.shape, Q.shape))
+    mm, keep = Q.shape
+    n = V.shape[1]
+    cols = np.ascontiguousarray(Q.T)
+    check(lib().sblas_eigsh_rotate_ref(n, mm, keep, V.ctypes.data, max(n, 1), cols.ctypes.data, mm), "sblas_eigsh_rotate_ref")
+    return V
+
+
+def eigsh_rotate(V, Q, stream=None):
+    """V[i] <- sum_l Q[l][i] V[l] for i < keep over l < mm, in place and in ONE pass over V, and V[keep] <- V[mm]
+    (sblas_hip_eigsh_rotate_f64): row i has exactly the bits of gmres_combine(V[:mm], Q[:, i]).  V: (mm + 1, n) float64 on
+    the GPU, each row contiguous, rows a constant stride >= n apart (see _gmres_columns); Q: (mm, keep) float64 on the
+    same device.  No synchronisation.  -> V."""
+    import torch
+    k1, n, ldv = _gmres_columns(V, eigsh_limits()["max_ncv"] + 1)
+    if not isinstance(Q, torch.Tensor) or Q.dtype != torch.float64 or Q.device != V.device or Q.dim() != 2:
+        raise SblasError("Q must be a float64 (mm, keep) tensor on V's device")
+    mm, keep = int(Q.shape[0]), int(Q.shape[1])
+    if k1 != mm + 1 or not 1 <= keep <= mm:
+        raise SblasError("V must have mm + 1 = %d rows and 1 <= keep <= mm, got %d rows and keep = %d" % (mm + 1, k1, keep))
+    cols = Q.t().contiguous()
+    with torch.cuda.device(V.device):
+        check(lib().sblas_hip_eigsh_rotate_f64(-1, _stream(stream), n, mm, keep, V.data_ptr() if n else None, ldv, cols.data_ptr(), mm),
+              "sblas_hip_eigsh_rotate_f64")
+    return V
+
+
+class _DeviceColumns:
+    """k columns of n doubles a column stride apart in a plan's device memory, as the array interface torch reads: what
+    lets EigshPlan.vectors() be a view.  Holds the plan, so the plan object outlives every view."""
+
+    def __init__(self, owner, ptr, k, n, ld):
+        self.owner = owner
+        self.__cuda_array_interface__ = dict(shape=(k, n), typestr="<f8", data=(ptr, False), version=2, strides=(ld * 8, 8))
+
+
+class EigshPlan:
+    """k eigenpairs at one end of the spectrum of a SYMMETRIC n x n CSR matrix (rowptr, colidx), int32 indices, fp64
+    values, by thick-restart Lanczos with full reorthogonalisation, resident on the device (sblas_hip_eigsh_plan_create).
+    Symmetry is the caller's promise, as with PCG: it is not checked, and a matrix that is not symmetric gives numbers
+    that mean nothing.  which: "LA" (largest), "SA" (smallest) or "LM" (largest magnitude).  1 <= k < ncv <= min(64, n -
+    1), default ncv = min(max(2 k + 1, 20), 64, n - 1); k <= keep <= ncv - 1 Ritz vectors survive a restart, default k +
+    (ncv - k) // 2.  spmv_plan: an SpmvPlan on the same tensors, or None.  seed: of the default start vector.
+
+    A single-vector Lanczos method finds ONE copy of a multiple eigenvalue.  On a matrix whose wanted eigenvalues are not
+    simple (the square-grid Laplacian is one) the k values returned can all have small residuals and still not be the k
+    extremal eigenvalues counted with multiplicity; that needs a block method.
+
+    start() normalises v0 and enqueues the first `keep` steps; iterate(cycles) enqueues restart cycles without allocating
+    or synchronising (graph-capturable, always the same chain); status() is the one call that synchronises.  Once the
+    status is not "running", cycles already enqueued change nothing.  Every bit is pinned (include/sblas_hip_eigsh.h)."""
+
+    def __init__(self, n, rowptr, colidx, k, ncv=None, which="LA", keep=None, spmv_plan=None, seed=0, stream=None):
+        import torch
+        self.handle = None
+        self.ncv, self.keep = _eigsh_sizes(n, k, ncv, keep, which)
+        self.k, self.which, self.seed = int(k), which, int(seed) & 0xffffffff
+        self.n, self.nnz = n, _structure(n, rowptr, colidx)
+        self.rowptr, self.colidx, self.device, self.spmv_plan = rowptr, colidx, rowptr.device, spmv_plan
+        if spmv_plan is not None and not isinstance(spmv_plan, SpmvPlan):
+            raise SblasError("spmv_plan must be an SpmvPlan or None")
+        self._keep = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_eigsh_plan_create(-1, _stream(stream), n, self.nnz, rowptr.data_ptr(), colidx.data_ptr() if self.nnz else None,
+                                                   self.k, self.ncv, self.keep, EIGSH_WHICH[which],
+                                                   spmv_plan.handle if spmv_plan is not None else None, self.seed, C.byref(h))
+        check(rc, "sblas_hip_eigsh_plan_create")
+        self.handle = h
+
+    def info(self):
+        out = (C.c_int64 * 14)()
+        check(lib().sblas_hip_eigsh_info(self.handle, out), "sblas_hip_eigsh_info")
+        return dict(n=int(out[0]), nnz=int(out[1]), k=int(out[2]), ncv=int(out[3]), keep=int(out[4]),
+                    which=[w for w, v in EIGSH_WHICH.items() if v == out[5]][0], vectors=int(out[3]) + 2, vector_bytes=int(out[6]),
+                    partial_bytes=int(out[7]), scalar_bytes=int(out[8]), matrix_bytes=int(out[9]), bytes=int(out[10]),
+                    step_launches=int(out[11]), start_launches=int(out[12]), cycle_launches=int(out[13]))
+
+    def start(self, val, v0=None, rtol=1e-8, atol=0.0, max_restarts=300, stream=None):
+        """Begins a solve on the values val: v0 (n doubles, or None: cheby_start_ref's hashed vector with the plan's seed)
+        is normalised and the first `keep` steps are enqueued.  Every refusal comes before any launch."""
+        import torch
+        _krylov_vector("val", val, self.nnz, self.device)
+        if v0 is not None:
+            _krylov_vector("v0", v0, self.n, self.device)
+        if not (rtol >= 0.0 and atol >= 0.0) or int(max_restarts) < 0:
+            raise SblasError("rtol and atol must be >= 0 and max_restarts >= 0")
+        with torch.cuda.device(self.device):
+            rc = lib().sblas_hip_eigsh_start(self.handle, _stream(stream), val.data_ptr() if self.nnz else None,
+                                             v0.data_ptr() if v0 is not None else None, float(rtol), float(atol), int(max_restarts))
+        check(rc, "sblas_hip_eigsh_start")
+        self._keep = (val, v0)
+
+    def iterate(self, cycles, stream=None):
+        """Enqueues `cycles` restart cycles (steps keep .. ncv - 1, the Ritz kernel, the rotation): allocates nothing,
+        never synchronises, graph-capturable as a chain."""
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_eigsh_iterate(self.handle, _stream(stream), int(cycles)), "sblas_hip_eigsh_iterate")
+
+    def status(self, stream=None):
+        """Copies the scalar block and the first k Ritz values and estimates back and synchronises the stream ->
+        dict(status, code, restarts, matvecs, converged, theta, residuals, breakdown, columns, beta): converged counts the
+        first k estimates that met the test; breakdown is a value of EIGSH_DENOM ("invariant": the Krylov space ended at
+        `columns` < k columns)."""
+        import torch
+        out, theta, res = (C.c_double * 8)(), np.zeros(self.k), np.zeros(self.k)
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_eigsh_status(self.handle, _stream(stream), out, theta.ctypes.data, res.ctypes.data), "sblas_hip_eigsh_status")
+        return dict(status=KRYLOV_STATUS[int(out[0])], code=int(out[0]), restarts=int(out[1]), matvecs=int(out[2]), converged=int(out[3]),
+                    theta=theta, residuals=res, breakdown=EIGSH_DENOM[int(out[5])], columns=int(out[6]), beta=float(out[4]))
+
+    def values(self, stream=None):
+        """The k Ritz values in the order of which, as a device tensor.  No synchronisation."""
+        import torch
+        out = torch.empty(self.k, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().sblas_hip_eigsh_values(self.handle, _stream(stream), out.data_ptr()), "sblas_hip_eigsh_values")
+        return out
+
+    def vectors(self, copy=False):
+        """The first k columns of V as a (k, n) device tensor, row i the Ritz vector of values()[i] once the solve has
+        ended: a VIEW of the plan's memory (rows a column stride apart), which the next start overwrites and destroy()
+        frees; the view keeps the plan object alive but cannot keep it from being destroyed.  copy=True gives a tensor of
+        its own.  No launch, no synchronisation: work already enqueued on the stream writes into what the view shows."""
+        import torch
+        ptr, ldv = C.c_void_p(), C.c_int64()
+        check(lib().sblas_hip_eigsh_vectors(self.handle, C.byref(ptr), C.byref(ldv)), "sblas_hip_eigsh_vectors")
+        view = torch.as_tensor(_DeviceColumns(self, ptr.value, self.k, self.n, ldv.value), device=self.device)
+        return view.clone() if copy else view
+
+    def solve(self, val, v0=None, rtol=1e-8, atol=0.0, max_restarts=300, check_every=1, stream=None):
+        """start(), then iterate(check_every) / status() until the status is not "running" -> (values, vectors, status
+        dict); vectors is vectors()'s view.  The result does not depend on check_every."""
+        if int(check_every) < 1:
+            raise SblasError("check_every must be at least 1")
+        self.start(val, v0=v0, rtol=rtol, atol=atol, max_restarts=max_restarts, stream=stream)
+        while True:
+            self.iterate(int(check_every), stream=stream)
+            st = self.status(stream=stream)
+            if st["code"] != KRYLOV_RUNNING:
+                return self.values(stream=stream), self.vectors(), st
+
+    def destroy(self):
+        if self.handle:
+            lib().sblas_hip_eigsh_destroy(self.handle)
+            self.handle = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def eigsh(A, k, which="LA", ncv=None, keep=None, v0=None, rtol=1e-8, atol=0.0, max_restarts=300, check_every=1, seed=0):
+    """k eigenpairs of the symmetric A = (n, rowptr, colidx, val) (GPU tensors), one shot, as pcg() is -> (values (k),
+    vectors (k, n), status dict).  See EigshPlan for the limits, and for what a multiple eigenvalue does to the answer.
+    The plan made here is destroyed before returning."""
+    n, rowptr, colidx, val = A
+    plan = EigshPlan(n, rowptr, colidx, k, ncv=ncv, which=which, keep=keep, seed=seed)
+    try:
+        values, vectors, st = plan.solve(val, v0=v0, rtol=rtol, atol=atol, max_restarts=max_restarts, check_every=check_every)
+        return values, vectors.clone(), st                                   # the plan's memory ends with the plan
+    finally:
+        plan.destroy()
 
 
 # ------------------------------------------------------------------------------------------
